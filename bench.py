@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: Qwen3-4B int4 (W4A16, group 128) single-stream KV-cache decode on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K decode steps and prints the line; `--dump-outputs DIR` also writes what the
+last timed step computed (DIR/logits.npy: its logits [1, vocab] as float32; DIR/tokens.npy: the ids of the timed steps, up to
+the last 4,096, as float64), for comparing two builds output for output -- the weights and the prompt derive from --seed only.
+`--full` adds everything else below (roofline leg and its rocprofv3 child, GPU clocks, the short configs[2] / configs[4] /
+64-sequence runs, the CPU baselines and checkers): runs of their own that the headline figure does not need.
 
 Workload (BASELINE.json configs[1], the configuration the metric is quoted on): one request per GPU, a
 128-token synthetic prompt (token ids drawn like the reference's build_requests, benches/bench.py:201-225),
@@ -11,7 +17,7 @@ downloaded here.  N > 1: one process per GPU (torch.distributed.run), every rank
 request-level data parallelism with NO collective on the data path; RCCL is used only for the
 barrier and the max-over-ranks of the elapsed time.
 
-One JSON line on stdout (rank 0).  Extra objects:
+One JSON line on stdout (rank 0).  Extra objects (filled by --full; a plain run keeps roofline.step_* only):
   roofline     — the dominant kernel (tl::qmv3_kernel, the W4A16 decode GEMV: 145 launches per step streaming
                  all 2.137 GB of weights).  `achieved` / `frac` = algorithmic bytes of those launches / the sum of
                  their durations in a `rocprofv3 --kernel-trace --stats` run of THIS command, taken by this process
@@ -243,6 +249,18 @@ class SleepEngine:
     def read_tokens(self, slot, n): return [0] * n
     def stats(self): return {"graph_captures": 0, "graph_replays": 0, "decode_steps": self.steps, "kv_bytes": 0}
     def release(self, slot): pass
+
+
+def dump_outputs(out_dir: Path, engine, steps: int, dry: bool) -> None:
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the logits [1, vocab] (bf16 on the device,
+    exact in float32) and the greedy ids of the timed steps (the engine's ring holds the last 4,096) -- as DIR/<name>.npy."""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    ids = engine.read_tokens(0, min(steps, 4096))
+    np.save(out_dir / "tokens.npy", np.asarray(ids, dtype=np.float64))
+    if not dry:
+        np.save(out_dir / "logits.npy", engine.logits(1).float().cpu().numpy().astype(np.float32))
 
 
 def aggregate_value(n_gpus: int, steps: int, elapsed_max_s: float) -> float:
@@ -842,6 +860,11 @@ def main() -> None:
                          "frac from its kernel durations; committed: replay the newest committed summary; off: in-kernel stamps only")
     ap.add_argument("--engine", default="hip", choices=("hip", "sleep"),
                     help="sleep = launch-path plumbing test without a GPU (gloo); never a measurement")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (logits float32, token ids float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: roofline leg + rocprofv3 child, GPU clocks, extra configs, "
+                         "CPU baselines / checkers (a plain run only sets up, warms up and times --steps steps)")
     args = ap.parse_args()
     t_start = time.perf_counter()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -920,10 +943,12 @@ def main() -> None:
     engine.decode(max(args.warmup, 2), batch=1, use_graph=use_graph)  # >= 2: eager warm step + graph capture
     sync()
     bytes_first = engine.step_bytes(1)
-    clocks = None if dry or args.no_clocks else {"before": gpu_clocks(local_rank)}
+    clocks = None if dry or args.no_clocks or not args.full else {"before": gpu_clocks(local_rank)}
     progress("timed region")
     elapsed, local_elapsed = timed_steps(lambda k: engine.decode(k, batch=1, use_graph=use_graph), sync, args.steps, dist, device)
     bytes_last = engine.step_bytes(1)
+    if args.dump_outputs and rank == 0:  # before anything else runs on the engine: the last timed step's logits and the timed ids
+        dump_outputs(Path(args.dump_outputs), engine, args.steps, dry)
     if clocks is not None:
         clocks["after"] = gpu_clocks(local_rank)
         if rank == 0:
@@ -946,7 +971,7 @@ def main() -> None:
 
     # ---- roofline leg: per-kernel device-clock durations of real decode steps (not part of the timed region)
     prof = None
-    for _ in range(max(args.profile_steps, 0)):
+    for _ in range(max(args.profile_steps, 0) if args.full else 0):
         p = engine.profile_step(1)
         if prof is None:
             prof = p
@@ -1068,7 +1093,7 @@ def main() -> None:
     roofline["step_bytes"] = int(step_bytes)
 
     extra = None
-    if args.gpus == 1 and not dry and args.config == 2 and not args.no_extra_configs:
+    if args.full and args.gpus == 1 and not dry and args.config == 2 and not args.no_extra_configs:
         progress("extra configs: 8k, 32k, 64 sequences")
         extra = extra_configs_leg(mlx_model, cfg, device, args.seed, page)
         progress("extra configs done; serving trace at 64 slots")
@@ -1080,7 +1105,7 @@ def main() -> None:
         progress("serving trace done")
 
     cpu = None
-    if args.gpus == 1 and not args.no_cpu_baseline:
+    if args.full and args.gpus == 1 and not args.no_cpu_baseline:
         # at the bench's own prompt length (bounded at 128 tokens: the C checkers walk the prompt token by token), through the
         # bench's own prefill chunking, so that the checked decode steps run the attention plan of the timed ones
         sample_prompt = min(args.prompt_len, max(8, args.cpu_prompt))

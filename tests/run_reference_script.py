@@ -39,6 +39,10 @@ def main() -> None:
                   ROOT / "tiny-llm_amd" / "extensions_hip", REFERENCE]
     os.environ["PYTHONPATH"] = os.pathsep.join(str(p) for p in child_path)
     os.environ["REFSOL_ORACLE_FAKELIB"] = "1"
+    # Python imports tests/facade_site/usercustomize.py only with the user site enabled: a suite run without it
+    # (PYTHONNOUSERSITE) enables it again for the children, on a user base that holds no site-packages at all
+    os.environ.pop("PYTHONNOUSERSITE", None)
+    os.environ["PYTHONUSERBASE"] = str(ROOT / "tests" / "facade_site")
     os.chdir(REFERENCE)
     sys.argv = [str(script), *sys.argv[2:]]
     runpy.run_path(str(script), run_name="__main__")

@@ -1,6 +1,5 @@
 #!/bin/bash
-# Evidence run of a round (copied into profiles/ by tools/collect_evidence.py): whole GPU suite (with the reference's own tests when staged:
-# tools/stage_reference_tests.sh), smoke, bench configs 2/3/5 (+ rocprofv3 kernel stats of each), batched decode
+# Evidence run of a round (copied into profiles/ by tools/collect_evidence.py): whole GPU suite, smoke, bench configs 2/3/5 (+ rocprofv3 kernel stats of each), batched decode
 # table, serving (one GPU, reference admission and packed admission), acceptance run, operator / attention microbenches.
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/evidence
@@ -12,9 +11,9 @@ timeout 1800 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider --d
 echo "pytest rc=$?" >> $OUT/pytest.log
 grep -E "^E   |^FAILED|passed|failed" $OUT/pytest.log | cut -c1-300 | tail -20
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-timeout 600 python bench.py --config 3 --no-cpu-baseline > $OUT/bench_c3.json 2> $OUT/bench_c3.err
-timeout 600 python bench.py --config 5 --no-cpu-baseline > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 600 python bench.py --config 3 --full --no-cpu-baseline > $OUT/bench_c3.json 2> $OUT/bench_c3.err
+timeout 600 python bench.py --config 5 --full --no-cpu-baseline > $OUT/bench_c5.json 2> $OUT/bench_c5.err
 python - <<'PY'
 import json
 for c in ("bench","bench_c3","bench_c5"):

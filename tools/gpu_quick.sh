@@ -4,7 +4,7 @@ OUT=gpurun_out/quick
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q -x -p no:cacheprovider 2>&1 | tail -12 | tee $OUT/tests.log
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -c 2500 $OUT/bench.json | head -c 1200; echo
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; tail -c 2500 $OUT/bench.json | head -c 1200; echo
 python - <<'PY'
 import json
 b=json.loads(open("gpurun_out/quick/bench.json").read().strip().splitlines()[-1]); r=b["roofline"]
