@@ -26,6 +26,10 @@ def main(argv=None):
                     help="K / V pages as bfloat16 (the reference's cache) or FP8 E4M3 codes + power-of-two row scales (extension)")
     ap.add_argument("--enable-thinking", action="store_true")
     ap.add_argument("--raw-prompts", action="store_true", help="do not wrap the prompts in the chat template")
+    ap.add_argument("--sampler-temp", type=float, default=0.0, help="0 = greedy; otherwise the device sampler per request")
+    ap.add_argument("--sampler-top-p", type=float, default=None)
+    ap.add_argument("--sampler-top-k", type=int, default=None)
+    ap.add_argument("--sampler-seed", type=int, default=0, help="request i draws from seed + i")
     ap.add_argument("--prompts-file", default=None, help="one prompt per line (default: five built-in questions)")
     args = ap.parse_args(argv)
 
@@ -48,7 +52,10 @@ def main(argv=None):
                           max_batch=args.batch_size + 1, max_prefill_rows=args.prefill_step, kv_format=args.kv_format)
     try:
         done = batch_generate_ids(engine, encoded, limits, batch_size=args.batch_size, prefill_step=args.prefill_step,
-                                  eos_token_id=tokenizer.eos_token_id)
+                                  eos_token_id=tokenizer.eos_token_id,
+                                  sampling=None if not args.sampler_temp else {"temperature": args.sampler_temp, "top_k": args.sampler_top_k,
+                                                                               "top_p": args.sampler_top_p},
+                                  base_seed=args.sampler_seed)
     finally:
         engine.close()
     results = []

@@ -193,9 +193,32 @@ int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, int n, int32
 /* Set the pending input token of a slot explicitly (e.g. sampled on the host). */
 int tl_engine_set_token(tl_engine *e, int slot, int32_t token);
 
-/* Run `steps` greedy decode steps over the live slots [0, batch): each step feeds
- * every slot's pending token at position context_len, appends K/V, and leaves the
- * argmax token as the next pending token.  Generated ids are appended to an
+/* Per-slot sampling on the device (csrc/sample.h).  The live slot draws every token it produces from here on --
+ * the first token of a later prefill with want_logits, and every decode step -- under (temperature, top_k, top_p, seed):
+ *   order   tokens by logit, highest first, equal logits by the lower id first (NaN logits are never ranked, counted or drawn);
+ *   top-k   top_k > 0: exactly the first min(top_k, V) tokens of that order (ties at the k-th are cut by id; the host mirror
+ *           tiny_llm_hip.make_sampler keeps every token tied with the k-th instead);
+ *   top-p   0 < top_p < 1: a token stays while the temperature-1 probability exp(l - m) / sum_V exp(l - m) (full vocabulary, m the
+ *           row maximum, NOT renormalised after top-k) of the kept tokens ranked before it sums to less than top_p; the first stays;
+ *   draw    w_i = exp((l_i - m) / T) over the kept set, W = sum w_i (fp32); u = Philox4x32-10 with key (seed & 0xffffffff, seed >> 32)
+ *           and counter (position, 0, 0x53414d50, 0), u = (word 0 >> 8) * 2^-24; the token is the first kept token in ascending id
+ *           whose inclusive cumulative w exceeds u W (rounding leaving none: the last kept token).  position = tokens in the sequence
+ *           before the sampled one (the prompt length for the first token after a prefill, +1 per decode step), so a draw depends
+ *           on (logits row, parameters, seed, position) only -- not on the slot, the batch, the replay route or how steps are split.
+ * temperature 0 (the default) is greedy: the same id as an engine that never calls this.  temperature must be finite and >= 0;
+ * top_k 0 or >= V: no top-k; top_p outside (0, 1): no top-p.  Sampling needs V <= 524,288.  The parameters live in a host mirror
+ * and a per-slot device array written on the engine stream between steps.  tl_engine_begin / tl_engine_release reset the slot to
+ * greedy, tl_engine_move moves the parameters with the sequence, tl_engine_fork copies them (seed included: give the child its own
+ * seed, or both draw the same tokens).  tl_engine_verify refuses a sampling slot (verification is greedy). */
+int tl_engine_set_sampling(tl_engine *e, int slot, float temperature, int top_k, float top_p, uint64_t seed);
+
+/* Run `steps` decode steps over the live slots [0, batch): each step feeds every
+ * slot's pending token at position context_len, appends K/V, and leaves the next
+ * token as the next pending token: the argmax, or, for a slot with a nonzero
+ * temperature (tl_engine_set_sampling), the token drawn by the per-slot sampler on
+ * the device.  A step in which some live slot samples ends with the sampling twin
+ * of the step-end launch (its own captured plan; greedy slots inside it keep the
+ * argmax and its tie rule); otherwise the step is the greedy program unchanged.  Generated ids are appended to an
  * on-device ring [capacity, max_batch] readable via tl_engine_read_tokens.
  * The step is captured in a hipGraph on first use (re-captured when the
  * attention split bucket or batch changes); use_graph = 0 launches eagerly.
@@ -402,6 +425,12 @@ int tl_decode_attention_fused_fp8(const void *qkv_dev, const void *q_norm_dev, c
                                   int num_heads, int num_kv_heads, int head_dim, int page_size, int max_pages, float rope_theta,
                                   float eps, int max_context, void *workspace_dev, size_t workspace_bytes, void *stream,
                                   tl_attention_info *info);
+
+/* The device sampler of tl_engine_set_sampling over caller rows: logits [rows, vocab] bf16 (vocab <= 524,288), per-row device arrays
+ * temperature (float; 0 = greedy), top_k (int32), top_p (float), seed (uint64) and position (int32) -> ids_dev [rows] int32.  One
+ * 1,024-thread workgroup per row, the engine's routine and semantics.  Stream ordered. */
+int tl_sample_logits(const void *logits_dev, int rows, int vocab, const float *temperature_dev, const int32_t *top_k_dev,
+                     const float *top_p_dev, const uint64_t *seed_dev, const int32_t *position_dev, int32_t *ids_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sampler-temp", type=float, default=0)
     ap.add_argument("--sampler-top-p", type=float, default=None)
     ap.add_argument("--sampler-top-k", type=int, default=None)
+    ap.add_argument("--sampler-seed", type=int, default=None,
+                    help="with --solution engine and a nonzero --sampler-temp: sample on the device, in decode(N) calls, from this seed")
     ap.add_argument("--enable-thinking", action="store_true")
     ap.add_argument("--raw-prompt", action="store_true", help="do not wrap the prompt in the chat template")
     ap.add_argument("--max-new-tokens", type=int, default=256)
@@ -76,6 +78,12 @@ def main(argv=None) -> str:
                                                proposal_length=min(args.proposal_length, 7), eos_token_id=eos)
             finally:
                 draft.close()
+        elif args.sampler_temp and args.sampler_seed is not None:
+            # the per-slot sampler on the device: the whole generation in one prefill + one decode(N) call
+            out = engine.generate(ids, args.max_new_tokens, temperature=args.sampler_temp, top_k=args.sampler_top_k,
+                                  top_p=args.sampler_top_p, seed=args.sampler_seed)
+            if eos in out:
+                out = out[:out.index(eos)]
         elif args.sampler_temp:
             out = sample_with_engine(engine, ids, args, eos)
         else:

@@ -13,6 +13,7 @@
 #include "../../include/tinyllm_engine.h"
 #include "common.h"
 #include "engine_kernels.h"
+#include "sample.h"
 #include "qmv.h"
 #include "qmv3.h"
 #include "qmm3.h"
@@ -149,6 +150,20 @@ struct tl_engine {
     std::vector<char> page_was_used;
     std::vector<int> page_refs;  // sequences holding each page (prefix sharing after tl_engine_fork); 0 = free
     tl_engine_stats stats{};
+    // per-slot sampling (tl_engine_set_sampling, sample.h): host mirror + device arrays [max_batch] each, written on the stream between
+    // steps by poke; temperature 0 = greedy (the default, and what begin / release restore)
+    struct SampleParams {
+        float temperature = 0.f;
+        int top_k = 0;
+        float top_p = 0.f;
+        uint64_t seed = 0;
+        bool samples() const { return temperature > 0.f; }
+    };
+    std::vector<SampleParams> smp;
+    char *smp_mem = nullptr;
+    float *smp_temp = nullptr, *smp_topp = nullptr;
+    int32_t *smp_topk = nullptr;
+    uint64_t *smp_seed = nullptr;
 
     bool warmed = false;
     std::map<std::pair<int, long>, hipGraphExec_t> graphs;  // (batch, n_splits << 32 | tokens_per_split)
@@ -242,6 +257,132 @@ static int poke(tl_engine *e, std::vector<std::pair<int32_t *, int32_t>> &items)
     items.clear();
     TL_CHECK_LAUNCH("engine poke");
     return TL_OK;
+}
+
+// ---- per-slot sampling (sample.h) ------------------------------------------------------------------
+// The sampling twin of step_end_kernel: the token of every row is chosen by smp_select under its slot's parameters (a slot with
+// temperature 0 takes the greedy id, first maximum), then exactly step_end_kernel's tail: record, advance, RoPE factors, next
+// embedding row, sums of squares.  It writes what step_end_kernel writes, nothing else.  grid = rows, block = 1024.
+// (one struct by value, like every kernel of a decode step: csrc/aql.cpp copies a captured node's argument block as it is)
+struct SampleStepEndArgs {
+    StepEndArgs s;
+    const float *temperature;  // [max_batch]
+    const int32_t *top_k;
+    const float *top_p;
+    const uint64_t *seed;
+};
+
+static __global__ __launch_bounds__(1024) void sample_step_end_kernel(const SampleStepEndArgs q) {
+    const StepEndArgs &p = q.s;
+    __shared__ SampleSmem sm;
+    __shared__ float s_val[16];
+    __shared__ int s_token, s_ctx;
+    const prof_t prof_t0 = prof_begin(p.prof);
+    const int i = blockIdx.x;
+    const int slot = p.slot0 + i;
+    const SmpRow row(p.logits + (long)i * p.vocab, p.vocab);
+    const float temperature = q.temperature[slot], top_p = q.top_p[slot];
+    const int top_k = q.top_k[slot];
+    const uint64_t seed = q.seed[slot];
+    const int live = p.live[slot];
+    // the sampled token's position: tokens before it (decode: the context after this step's advance; prefill: the prompt length)
+    const uint32_t position = (uint32_t)(p.context_lens[slot] + (p.advance && live ? 1 : 0));
+    float m_given = __builtin_nanf("");
+    if (p.tile_max) {  // uniform: the row maximum from the lm_head GEMV's per-tile pairs
+        const f32x2 *tm = p.tile_max + (long)i * p.tiles;
+        float t = -INFINITY;
+        for (int k = threadIdx.x; k < p.tiles; k += 1024) t = fmaxf(t, act_load(tm + k)[0]);
+        m_given = smp_block_max(t, sm);
+    }
+    const int bi = smp_select(row, m_given, temperature, top_k, top_p, seed, position, sm);
+    __syncthreads();  // every thread has read context_lens[slot] above
+    if (threadIdx.x == 0) {
+        s_token = bi;
+        int ctx_now = p.context_lens[slot];
+        if (live) {
+            p.tokens[slot] = bi;
+            const int n = p.produced[slot];
+            p.ring[(long)slot * p.ring_cap + (n % p.ring_cap)] = bi;
+            p.produced[slot] = n + 1;
+            if (p.advance) p.context_lens[slot] = ++ctx_now;
+        }
+        s_ctx = ctx_now;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < p.rope_half) {
+        const int pos = min(s_ctx, p.rope_positions - 1);  // the slot's NEXT position
+        p.rope_cur[(long)slot * p.rope_half + threadIdx.x] = p.rope_table[(long)pos * p.rope_half + threadIdx.x];
+    }
+    const int token = s_token;
+    const int words = p.hidden / 8;
+    const int groups = p.hidden / 128;
+    float sumsq = 0.f;
+    for (int w = threadIdx.x; w < words; w += 1024) {
+        const uint32_t packed = p.emb_w[(long)token * words + w];
+        const float scale = BF16::to_float(p.emb_s[(long)token * groups + w / 16]);
+        const float bias = BF16::to_float(p.emb_b[(long)token * groups + w / 16]);
+        uint16_t o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            o[e] = BF16::from_float((float)((packed >> (4 * e)) & 0xfu) * scale + bias);
+            const float v = BF16::to_float(o[e]);
+            sumsq += v * v;
+        }
+        *reinterpret_cast<uint4 *>(p.x + (long)slot * p.hidden + w * 8) = *reinterpret_cast<const uint4 *>(o);
+    }
+    if (p.ss_out) {
+        const float ws = wave_sum(sumsq);
+        if ((threadIdx.x & 63) == 0) s_val[threadIdx.x >> 6] = ws;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float tot = 0.f;
+            for (int w = 0; w < 16; ++w) tot += s_val[w];
+            p.ss_out[(long)slot * 8] = tot;
+            for (int i = 1; i < 8; ++i) p.ss_out[(long)slot * 8 + i] = 0.f;
+        }
+    }
+    prof_end(p.prof, prof_t0);
+}
+
+// tl_sample_logits: the same selection over caller rows, parameters per row.  grid = rows, block = 1024.
+static __global__ __launch_bounds__(1024) void sample_rows_kernel(const uint16_t *logits, int vocab, const float *temperature, const int32_t *top_k,
+                                                                  const float *top_p, const uint64_t *seed, const int32_t *position, int32_t *ids) {
+    __shared__ SampleSmem sm;
+    const int i = blockIdx.x;
+    const SmpRow row(logits + (long)i * vocab, vocab);
+    const int tok = smp_select(row, __builtin_nanf(""), temperature[i], top_k[i], top_p[i], seed[i], (uint32_t)position[i], sm);
+    if (threadIdx.x == 0) ids[i] = tok;
+}
+
+// does some live slot of [0, batch) sample?  (the plan-key bit of tl_engine_decode; with it clear a step is today's greedy program)
+static bool step_samples(const tl_engine *e, int batch) {
+    for (int b = 0; b < batch; ++b)
+        if (e->slot_live[b] && e->smp[b].samples()) return true;
+    return false;
+}
+
+// the device copy of a slot's parameters follows the host mirror (stream-ordered, between steps)
+static int smp_write(tl_engine *e, int slot, const tl_engine::SampleParams &v) {
+    std::vector<std::pair<int32_t *, int32_t>> pk;
+    pk.emplace_back((int32_t *)(e->smp_temp + slot), __builtin_bit_cast(int32_t, v.temperature));
+    pk.emplace_back(e->smp_topk + slot, v.top_k);
+    pk.emplace_back((int32_t *)(e->smp_topp + slot), __builtin_bit_cast(int32_t, v.top_p));
+    pk.emplace_back((int32_t *)(e->smp_seed + slot), (int32_t)(uint32_t)v.seed);
+    pk.emplace_back((int32_t *)(e->smp_seed + slot) + 1, (int32_t)(uint32_t)(v.seed >> 32));
+    e->smp[slot] = v;
+    return poke(e, pk);
+}
+static bool smp_is_default(const tl_engine::SampleParams &v) { return v.temperature == 0.f && v.top_k == 0 && v.top_p == 0.f && v.seed == 0; }
+static int smp_reset(tl_engine *e, int slot) { return smp_is_default(e->smp[slot]) ? TL_OK : smp_write(e, slot, tl_engine::SampleParams{}); }
+
+// step end of a decode step / a prefill's last row: greedy kernel, or its sampling twin when the plan samples
+static void launch_step_end(tl_engine *e, const StepEndArgs &s, int rows, bool samples) {
+    if (samples) {
+        const SampleStepEndArgs q{s, e->smp_temp, e->smp_topk, e->smp_topp, e->smp_seed};
+        hipLaunchKernelGGL(sample_step_end_kernel, dim3(rows), dim3(1024), 0, e->stream, q);
+    } else {
+        hipLaunchKernelGGL(step_end_kernel, dim3(rows), dim3(1024), 0, e->stream, s);
+    }
 }
 
 static int check_w4(const tl_w4 &w, int rows, int cols, const char *name) {
@@ -1078,7 +1219,7 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, ProfCtx *pc = nul
     s.rope_half = c.head_dim / 2;
     s.ss_out = e->ss_x;
     s.prof = pc ? pc->buf : nullptr;
-    hipLaunchKernelGGL(step_end_kernel, dim3(batch), dim3(1024), 0, e->stream, s);
+    launch_step_end(e, s, batch, step_samples(e, batch));
     if (pc) prof_after(e, pc, 7, batch);
     TL_CHECK_LAUNCH("engine step end");
     return TL_OK;
@@ -1294,6 +1435,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
 
     auto cleanup_fail = [&](const std::string &msg) {
         if (e->arena) (void)hipFree(e->arena);
+        if (e->smp_mem) (void)hipFree(e->smp_mem);
         if (e->kpool) (void)hipFree(e->kpool);
         if (e->vpool) (void)hipFree(e->vpool);
         if (e->kscale_pool) (void)hipFree(e->kscale_pool);
@@ -1311,6 +1453,13 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
         return fail(TL_ERR_HIP, msg);
     };
     if (hipMalloc((void **)&e->arena, e->arena_bytes) != hipSuccess) return cleanup_fail("engine_create: hipMalloc(arena) failed");
+    // sampling parameters per slot (all zero: greedy): seeds first for their 8-byte alignment
+    if (hipMalloc((void **)&e->smp_mem, (size_t)c.max_batch * 20) != hipSuccess) return cleanup_fail("engine_create: hipMalloc(sampling) failed");
+    e->smp_seed = (uint64_t *)e->smp_mem;
+    e->smp_temp = (float *)(e->smp_mem + (size_t)c.max_batch * 8);
+    e->smp_topk = (int32_t *)(e->smp_mem + (size_t)c.max_batch * 12);
+    e->smp_topp = (float *)(e->smp_mem + (size_t)c.max_batch * 16);
+    if (hipMemsetAsync(e->smp_mem, 0, (size_t)c.max_batch * 20, e->stream) != hipSuccess) return cleanup_fail("engine_create: memset failed");
     e->layer_pool_elems = (size_t)c.num_pages * c.num_kv_heads * c.page_size * c.head_dim;
     const size_t pool_bytes = e->layer_pool_elems * e->kv_elem_bytes() * c.num_layers;
     if (hipMalloc((void **)&e->kpool, pool_bytes) != hipSuccess) return cleanup_fail("engine_create: hipMalloc(key pages) failed");
@@ -1546,6 +1695,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->slot_ctx.assign(c.max_batch, 0);
     e->slot_live.assign(c.max_batch, 0);
     e->slot_produced.assign(c.max_batch, 0);
+    e->smp.assign(c.max_batch, tl_engine::SampleParams{});
     e->free_pages.resize(c.num_pages);
     for (int i = 0; i < c.num_pages; ++i) e->free_pages[i] = c.num_pages - 1 - i;  // pop_back hands out 0,1,2,...
     e->page_was_used.assign(c.num_pages, 0);
@@ -1648,6 +1798,7 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     if (e->moe_ws) (void)hipFree(e->moe_ws);
     for (auto &kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
     if (e->arena) (void)hipFree(e->arena);
+    if (e->smp_mem) (void)hipFree(e->smp_mem);
     if (e->kpool) (void)hipFree(e->kpool);
     if (e->vpool) (void)hipFree(e->vpool);
     if (e->kscale_pool) (void)hipFree(e->kscale_pool);
@@ -1690,7 +1841,8 @@ extern "C" int tl_engine_begin(tl_engine *e, int slot) {
     pk.emplace_back(e->context_lens + slot, 0);
     pk.emplace_back(e->produced + slot, 0);
     pk.emplace_back(e->tokens + slot, 0);
-    return poke(e, pk);
+    TL_TRY(poke(e, pk));
+    return smp_reset(e, slot);
 }
 
 extern "C" int tl_engine_reserve(tl_engine *e, int slot, int total_tokens) {
@@ -1717,7 +1869,8 @@ extern "C" int tl_engine_release(tl_engine *e, int slot) {
     pk.emplace_back(e->context_lens + slot, 0);
     pk.emplace_back(e->tokens + slot, 0);
     e->stats.pages_free = (int)e->free_pages.size();
-    return poke(e, pk);
+    TL_TRY(poke(e, pk));
+    return smp_reset(e, slot);
 }
 
 extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
@@ -1793,6 +1946,8 @@ extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
     // the pending input token travels on the device
     TL_HIP(hipMemcpyAsync(e->tokens + dst, e->tokens + src, sizeof(int32_t), hipMemcpyDeviceToDevice, e->stream));
     e->stats.pages_free = (int)e->free_pages.size();
+    // the sampling parameters are copied too (seed included: give the child its own seed, or both draw the same tokens)
+    if (!smp_is_default(e->smp[src]) || !smp_is_default(e->smp[dst])) TL_TRY(smp_write(e, dst, e->smp[src]));
     return TL_OK;
 }
 
@@ -1826,6 +1981,12 @@ extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
     e->slot_live[src] = 0;
     e->slot_produced[dst] = 0;
     e->slot_produced[src] = 0;
+    // the sampling parameters go with the sequence
+    if (!smp_is_default(e->smp[src]) || !smp_is_default(e->smp[dst])) {
+        const tl_engine::SampleParams v = e->smp[src];
+        TL_TRY(smp_write(e, dst, v));
+        TL_TRY(smp_write(e, src, tl_engine::SampleParams{}));
+    }
     return TL_OK;
 }
 
@@ -1850,6 +2011,31 @@ extern "C" int tl_engine_set_token(tl_engine *e, int slot, int32_t token) {
     std::vector<std::pair<int32_t *, int32_t>> pk;
     pk.emplace_back(e->tokens + slot, token);
     return poke(e, pk);
+}
+
+extern "C" int tl_engine_set_sampling(tl_engine *e, int slot, float temperature, int top_k, float top_p, uint64_t seed) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(std::isfinite(temperature) && temperature >= 0.f, "engine_set_sampling: temperature must be finite and >= 0");
+    TL_REQUIRE(top_k >= 0, "engine_set_sampling: top_k must be >= 0 (0 = no top-k)");
+    TL_REQUIRE(!std::isnan(top_p), "engine_set_sampling: top_p is NaN");
+    TL_REQUIRE(temperature == 0.f || e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_set_sampling: vocabulary larger than the sampler's 524,288 tokens");
+    tl_engine::SampleParams v;
+    v.temperature = temperature;
+    v.top_k = top_k >= e->cfg.vocab_size ? 0 : top_k;  // beyond the vocabulary: no top-k
+    v.top_p = top_p > 0.f && top_p < 1.f ? top_p : 0.f;  // outside (0, 1): no top-p
+    v.seed = seed;
+    return smp_write(e, slot, v);
+}
+
+extern "C" int tl_sample_logits(const void *logits_dev, int rows, int vocab, const float *temperature_dev, const int32_t *top_k_dev,
+                                const float *top_p_dev, const uint64_t *seed_dev, const int32_t *position_dev, int32_t *ids_dev, void *stream) {
+    TL_REQUIRE(logits_dev && temperature_dev && top_k_dev && top_p_dev && seed_dev && position_dev && ids_dev, "sample_logits: null argument");
+    TL_REQUIRE(rows > 0 && rows <= 65535, "sample_logits: rows out of range");
+    TL_REQUIRE(vocab > 0 && vocab <= SMP_MAX_VOCAB, "sample_logits: vocabulary out of range (1 .. 524,288)");
+    hipLaunchKernelGGL(sample_rows_kernel, dim3(rows), dim3(1024), 0, (hipStream_t)stream, (const uint16_t *)logits_dev, vocab, temperature_dev,
+                       top_k_dev, top_p_dev, seed_dev, position_dev, ids_dev);
+    TL_CHECK_LAUNCH("sample_logits");
+    return TL_OK;
 }
 
 // logits_mode: 0 = none, 1 = last row (greedy id recorded as the slot's pending token), 2 = every row (n <= 8: greedy ids
@@ -1978,7 +2164,7 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
         s.rope_cur = e->rope_cur;
         s.rope_positions = e->rope_positions;
         s.rope_half = c.head_dim / 2;
-        hipLaunchKernelGGL(step_end_kernel, dim3(1), dim3(1024), 0, e->stream, s);
+        launch_step_end(e, s, 1, e->smp[slot].samples());
         TL_CHECK_LAUNCH("engine prefill argmax");
         e->slot_produced[slot] += 1;
     }
@@ -2119,7 +2305,7 @@ static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const
             s.rope_cur = e->rope_cur;
             s.rope_positions = e->rope_positions;
             s.rope_half = c.head_dim / 2;
-            hipLaunchKernelGGL(step_end_kernel, dim3(1), dim3(1024), 0, e->stream, s);
+            launch_step_end(e, s, 1, e->smp[slots[i]].samples());
             TL_CHECK_LAUNCH("engine packed prefill argmax");
             e->slot_produced[slots[i]] += 1;
             ++j;
@@ -2141,6 +2327,8 @@ extern "C" int tl_engine_prefill(tl_engine *e, int slot, const int32_t *tokens, 
 extern "C" int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, int n, int32_t *out_ids) {
     TL_REQUIRE(e && out_ids, "engine_verify: null argument");
     TL_REQUIRE(n >= 1 && n <= 8, "engine_verify: between 1 and 8 tokens per call (the paged decode kernel's query rows)");
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(!e->smp[slot].samples(), "engine_verify: the slot samples (verification is greedy; set temperature 0 first)");
     TL_TRY(prefill_impl(e, slot, tokens, n, 2));
     TL_HIP(hipMemcpyAsync(out_ids, e->verify_ids, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
     TL_HIP(hipStreamSynchronize(e->stream));
@@ -2182,6 +2370,7 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
                        c.vocab_size, e->context_lens, e->rope_table, e->rope_cur, e->rope_positions, c.head_dim / 2, e->ss_x);
     TL_CHECK_LAUNCH("engine embed");
     std::vector<std::pair<int32_t *, int32_t>> pk;
+    const bool samples = step_samples(e, batch);
     bool on_queue = false;  // steps of this call are in flight on the AQL queue (the stream is idle and must stay so until they are drained)
     for (int s = 0; s < steps; ++s) {
         int max_ctx = 1;
@@ -2200,7 +2389,8 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
         }
         const SplitPlan sp = pick_decode_splits(e, batch, max_ctx);
         if (use_graph && e->warmed) {
-            const auto key = std::make_pair(batch, sp.key());
+            // bit 62: the step ends with the sampling twin of step_end_kernel (re-derived every call from the slots' parameters)
+            const auto key = std::make_pair(batch, sp.key() | (samples ? (1L << 62) : 0L));
             auto it = e->graphs.find(key);
             if (it == e->graphs.end()) {
                 // The split plan (and with it the key) changes every 64 * n_splits tokens of context: a long run would keep one

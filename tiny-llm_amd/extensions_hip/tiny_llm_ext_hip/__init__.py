@@ -182,6 +182,8 @@ _SIGNATURES.update({
     "tl_engine_prefill_packed": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int), _P(ctypes.c_int32), _P(ctypes.c_int), _P(ctypes.c_int)]),
     "tl_engine_verify": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _P(ctypes.c_int32)]),
     "tl_engine_set_token": (_c_int, [_c_void_p, _c_int, ctypes.c_int32]),
+    "tl_engine_set_sampling": (_c_int, [_c_void_p, _c_int, _c_float, _c_int, _c_float, ctypes.c_uint64]),
+    "tl_sample_logits": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 7),
     "tl_engine_decode": (_c_int, [_c_void_p, _c_int, _c_int, _c_int]),
     "tl_engine_read_tokens": (_c_int, [_c_void_p, _c_int, _c_int, _P(ctypes.c_int32)]),
     "tl_engine_logits_dev": (_c_void_p, [_c_void_p]),
@@ -898,3 +900,31 @@ def decode_attention_fused_fp8(qkv: torch.Tensor, q_norm: torch.Tensor, k_norm: 
 def paged_attention_waves(waves: int = 0) -> int:
     """Test / lab hook (tl_paged_attention_waves): 8 or 4 waves per workgroup in the bf16 FlashAttention prefill kernel; returns the previous value."""
     return int(_lib.tl_paged_attention_waves(int(waves)))
+
+
+def sample_logits(logits: torch.Tensor, temperature, top_k, top_p, seed, position) -> torch.Tensor:
+    """The decode engine's device sampler (tl_sample_logits) over rows of bf16 logits [rows, vocab]: per-row temperature (0 = greedy),
+    top_k (0 = off), top_p (outside (0, 1) = off), seed (uint64) and position -> int32 ids [rows].  Each parameter is a scalar or one
+    value per row."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("sample_logits takes a [rows, vocab] bf16 tensor on the GPU")
+    logits = logits.contiguous()
+    rows, dev = logits.shape[0], logits.device
+
+    def per_row(v, dtype):
+        t = torch.as_tensor(v, dtype=dtype).reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(rows)
+        if t.numel() != rows:
+            raise ValueError("a sampling parameter needs one value per row")
+        return t.contiguous().to(dev)
+
+    seeds = [int(s) & 0xFFFFFFFFFFFFFFFF for s in (seed if hasattr(seed, "__len__") else [seed] * rows)]
+    seed_t = torch.tensor([s - (1 << 64) if s >= 1 << 63 else s for s in seeds], dtype=torch.int64).to(dev)  # uint64 bits
+    if seed_t.numel() != rows:
+        raise ValueError("a sampling parameter needs one value per row")
+    t_t, k_t, p_t, pos_t = per_row(temperature, torch.float32), per_row(top_k, torch.int32), per_row(top_p, torch.float32), per_row(position, torch.int32)
+    ids = torch.empty(rows, dtype=torch.int32, device=dev)
+    check(_lib.tl_sample_logits(logits.data_ptr(), rows, logits.shape[1], t_t.data_ptr(), k_t.data_ptr(), p_t.data_ptr(), seed_t.data_ptr(),
+                                pos_t.data_ptr(), ids.data_ptr(), _stream()))
+    return ids

@@ -13,6 +13,7 @@ rows interleaved) and then exposes a request-level API: ``begin`` / ``prefill`` 
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import Any, Sequence
 
@@ -196,6 +197,14 @@ class DecodeEngine:
     def set_token(self, slot: int, token: int) -> None:
         _ext.check(_lib.tl_engine_set_token(self._h, slot, int(token)))
 
+    def set_sampling(self, slot: int, temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None,
+                     seed: int = 0) -> None:
+        """Per-slot sampling on the device (tl_engine_set_sampling): every token the live slot produces from now on is drawn under
+        (temperature, top_k, top_p, seed); temperature 0 is greedy.  begin / release reset the slot to greedy, move carries the
+        parameters along, fork copies them (give a forked child its own seed)."""
+        t, k, p, s = sampling_args(temperature, top_k, top_p, seed)
+        _ext.check(_lib.tl_engine_set_sampling(self._h, slot, t, k, p, s))
+
     # -- compute -----------------------------------------------------------------------------------
     def prefill(self, slot: int, tokens: Sequence[int], *, chunk: int | None = None, want_logits: bool = True) -> None:
         """Chunked prefill (reference Request.try_prefill, batch.py:48-76): all chunks append K/V, the last one
@@ -236,7 +245,8 @@ class DecodeEngine:
         return list(out)
 
     def decode(self, steps: int, batch: int | None = None, use_graph: bool = True) -> None:
-        """Enqueue ``steps`` greedy decode steps over slots [0, batch); does not synchronise."""
+        """Enqueue ``steps`` decode steps over slots [0, batch) (greedy, or each slot's sampler: set_sampling); does not synchronise
+        on the hipGraph route."""
         _ext.check(_lib.tl_engine_decode(self._h, batch or self.max_batch, int(steps), int(use_graph)))
 
     def read_tokens(self, slot: int, count: int) -> list[int]:
@@ -287,9 +297,15 @@ class DecodeEngine:
         return {name: getattr(s, name) for name, _ in s._fields_}
 
     # -- convenience: one request, like benches/bench.py:run_one_request_week2 --------------------------
-    def generate(self, prompt: Sequence[int], max_new_tokens: int, *, slot: int = 0, chunk: int | None = None) -> list[int]:
+    def generate(self, prompt: Sequence[int], max_new_tokens: int, *, slot: int = 0, chunk: int | None = None,
+                 temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None, seed: int = 0) -> list[int]:
+        """One request: prefill, then ``max_new_tokens - 1`` decode steps in one call; greedy unless ``temperature`` > 0 (the
+        device sampler, set_sampling)."""
+        args = sampling_args(temperature, top_k, top_p, seed)
         self.begin(slot)
         try:
+            if args[0] > 0.0:
+                self.set_sampling(slot, *args)
             self.prefill(slot, prompt, chunk=chunk)
             if max_new_tokens > 1:
                 self.decode(max_new_tokens - 1, batch=slot + 1)
@@ -298,13 +314,57 @@ class DecodeEngine:
             self.release(slot)
 
 
+def sampling_args(temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None,
+                  seed: int = 0) -> tuple[float, int, float, int]:
+    """Validated (temperature, top_k, top_p, seed) for tl_engine_set_sampling: temperature finite and >= 0 (0 = greedy); top_k None
+    or 0 = no top-k, else a positive int (beyond the vocabulary: none); top_p None = no top-p, else in (0, 1] (1 = none); seed an
+    int in [0, 2^64)."""
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or temperature < 0:
+        raise ValueError(f"temperature must be a finite number >= 0, got {temperature!r}")
+    if top_k is None:
+        top_k = 0
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
+        raise ValueError(f"top_k must be None or an int >= 0, got {top_k!r}")
+    if top_p is None:
+        top_p = 1.0
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not (0.0 < top_p <= 1.0):
+        raise ValueError(f"top_p must be None or in (0, 1], got {top_p!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must be an int in [0, 2**64), got {seed!r}")
+    return float(temperature), min(int(top_k), 2**31 - 1), float(top_p), int(seed)
+
+
+def request_sampling(sampling, n_prompts: int, base_seed: int = 0) -> list[tuple[float, int, float, int]] | None:
+    """batch_generate_ids' ``sampling``: None (greedy, today's behaviour), one dict for every request, or one dict per prompt, with
+    keys temperature / top_k / top_p / seed.  A request without a seed gets base_seed + its prompt index, so requests do not share
+    a random stream."""
+    if sampling is None:
+        return None
+    if isinstance(sampling, dict):
+        sampling = [sampling] * n_prompts
+    sampling = list(sampling)
+    if len(sampling) != n_prompts:
+        raise ValueError("sampling needs one dict per prompt (or one dict for all)")
+    out = []
+    for i, d in enumerate(sampling):
+        if not isinstance(d, dict):
+            raise ValueError("sampling entries must be dicts")
+        unknown = set(d) - {"temperature", "top_k", "top_p", "seed"}
+        if unknown:
+            raise ValueError(f"unknown sampling keys: {sorted(unknown)}")
+        seed = d.get("seed")
+        out.append(sampling_args(d.get("temperature", 0.0), d.get("top_k"), d.get("top_p"),
+                                 (base_seed + i) & 0xFFFFFFFFFFFFFFFF if seed is None else seed))
+    return out
+
+
 # decode row counts used by the scheduler: exact up to 4 rows (fused GEMV), then the row-block sizes of the skinny matmul
 _DECODE_ROW_BUCKETS = (1, 2, 3, 4, 8, 16, 32, 48, 64, 96, 128, 192, 256)
 
 
 def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], max_new_tokens: int | Sequence[int],
                        batch_size: int, prefill_step: int = 128, eos_token_id: int | None = None,
-                       on_step=None) -> list[tuple[int, list[int]]]:
+                       on_step=None, sampling=None, base_seed: int = 0) -> list[tuple[int, list[int]]]:
     """Continuous batching over engine slots with the reference scheduler's shape (batch_generate,
     src/tiny_llm_ref/batch.py:136-285; benches/bench.py:run_batch_requests_serving 351-572): every loop turn
     (a) admits one pending request and prefills ONE chunk of at most ``prefill_step`` tokens in the staging slot,
@@ -312,12 +372,15 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     the occupied prefix of the slots (the reference steps all ``batch_size`` rows; idle rows carry context 0 and produce
     nothing, so skipping the idle tail changes no result), (d) retires finished requests and returns their pages.
     Token-id in, token-id out (no tokenizer can be downloaded here).  Needs ``engine.max_batch >= batch_size + 1``:
-    the last slot is the prefill staging slot.  Returns [(prompt_idx, generated ids)] in completion order."""
+    the last slot is the prefill staging slot.  Returns [(prompt_idx, generated ids)] in completion order.
+    ``sampling``: None (greedy), one dict or one dict per prompt (request_sampling); applied when a request enters the staging slot,
+    and carried by the engine through its slot moves."""
     if batch_size <= 0 or prefill_step <= 0:
         raise ValueError("batch_size and prefill_step must be positive")
     if engine.max_batch < batch_size + 1:
         raise ValueError("engine needs batch_size + 1 slots (one prefill staging slot)")
     limits = [max_new_tokens] * len(prompts) if isinstance(max_new_tokens, int) else list(max_new_tokens)
+    per_request = request_sampling(sampling, len(prompts), base_seed)
     staging = batch_size
     queue = list(range(len(prompts)))
     slots: list[dict | None] = [None] * batch_size
@@ -330,6 +393,8 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                 idx = queue.pop(0)
                 engine.begin(staging)
                 live_slots.add(staging)
+                if per_request is not None and per_request[idx][0] > 0.0:
+                    engine.set_sampling(staging, *per_request[idx])
                 pending = {"idx": idx, "tokens": [int(t) for t in prompts[idx]], "offset": 0, "out": [], "limit": limits[idx]}
             if pending is not None:
                 total = len(pending["tokens"])
