@@ -212,6 +212,48 @@ int tl_engine_set_token(tl_engine *e, int slot, int32_t token);
  * seed, or both draw the same tokens).  tl_engine_verify refuses a sampling slot (verification is greedy). */
 int tl_engine_set_sampling(tl_engine *e, int slot, float temperature, int top_k, float top_p, uint64_t seed);
 
+/* Per-token log-probabilities (csrc/logprob.h).  For a bf16 logits row l of V entries, m its maximum over non-NaN
+ * entries:
+ *   lse      m + log(sum_j exp(l_j - m)), summed in fp32 over non-NaN entries;  logprob(t) = l_t - lse.  This is the model's
+ *            distribution at temperature 1, unfiltered (the reference's logits - logsumexp(logits)).  For a slot that samples, the value
+ *            reported is still the model's log-probability of the token drawn -- NOT its probability under the sampler's truncated or
+ *            rescaled distribution;
+ *   top-N    (0 <= N <= TL_MAX_TOP_LOGPROBS) the first N tokens in exactly the sampler's order: logit descending, equal logits by the
+ *            lower id, NaN never ranked (the kept set of top_k = N, listed in that order).  Entries past N, or past the number of
+ *            rankable tokens, are id -1 with logprob -inf;
+ *   edges    a NaN logit has logprob NaN; a row without a finite maximum (all NaN / -inf, or holding +inf) has every logprob NaN,
+ *            and its top-N ids still follow the order.
+ * A row's values depend on the row alone: not on the batch, the replay route, eager or captured steps or how steps are split.
+ *
+ * tl_engine_set_logprobs: top_n -1 switches the slot off (the default), 0 .. 20 records one tl_token_logprob per token the slot
+ * produces from its next one on -- the first token of a later prefill with want_logits (tl_engine_prefill, tl_engine_prefill_packed)
+ * and every decode step.  A step in which some live slot records ends with the logprob twin of the step-end launch (its own captured
+ * plan); otherwise the step is unchanged.  The first call that switches a slot on allocates the records (max_batch x ring capacity x
+ * 164 bytes); an engine that never asks allocates nothing.  tl_engine_begin / tl_engine_release switch the slot off, tl_engine_move
+ * carries the setting and the pending record with the sequence, tl_engine_fork copies them.  tl_engine_verify records nothing.
+ * tl_engine_read_logprobs: the records of the last `count` tokens of the slot (like tl_engine_read_tokens: the same ring capacity,
+ * restarted by tl_engine_move); TL_ERR_INVALID when count exceeds the tokens produced since logprobs were switched on (0 while off).
+ * tl_engine_read_pending_logprobs: the record of each pending token of slots [0, count) (a slot that never recorded: logprob NaN,
+ * ids -1), one copy after synchronising -- the companion of tl_engine_read_pending. */
+#define TL_MAX_TOP_LOGPROBS 20
+typedef struct tl_token_logprob {           /* 164 bytes */
+    float logprob;                           /* log p(token) of the produced token */
+    int32_t top_ids[TL_MAX_TOP_LOGPROBS];    /* -1 past top_n */
+    float top_logprobs[TL_MAX_TOP_LOGPROBS]; /* -inf past top_n */
+} tl_token_logprob;
+int tl_engine_set_logprobs(tl_engine *e, int slot, int top_n);
+int tl_engine_read_logprobs(tl_engine *e, int slot, int count, tl_token_logprob *out);
+int tl_engine_read_pending_logprobs(tl_engine *e, int count, tl_token_logprob *out);
+
+/* Scoring a given text: behaves like tl_engine_prefill(e, slot, tokens, n, want_logits = 0) for the KV cache and the context (same
+ * limits: n <= max_prefill_rows, chunks longer than 8 tokens need head_dim 128), and also keeps every row: the final RMSNorm over the
+ * chunk, the lm_head through the W4 GEMM in blocks of rows into a scoring scratch (allocated on first use), then the log-probability
+ * routine per row.  out_logprobs[i] = log p(tokens[i+1] | the sequence through tokens[i]) for i < n - 1, out_logprobs[n-1] = that of
+ * next_token (NaN when next_token < 0: a caller chunking a long text passes the next chunk's first token); out_argmax[i] (may be NULL)
+ * = row i's greedy id.  The pending token, the logits of tl_engine_logits_dev, the token ring and the produced count are untouched.
+ * Works for bf16 and FP8 KV pages and MoE engines.  Synchronises. */
+int tl_engine_score(tl_engine *e, int slot, const int32_t *tokens, int n, int32_t next_token, float *out_logprobs, int32_t *out_argmax);
+
 /* Run `steps` decode steps over the live slots [0, batch): each step feeds every
  * slot's pending token at position context_len, appends K/V, and leaves the next
  * token as the next pending token: the argmax, or, for a slot with a nonzero
@@ -431,6 +473,12 @@ int tl_decode_attention_fused_fp8(const void *qkv_dev, const void *q_norm_dev, c
  * 1,024-thread workgroup per row, the engine's routine and semantics.  Stream ordered. */
 int tl_sample_logits(const void *logits_dev, int rows, int vocab, const float *temperature_dev, const int32_t *top_k_dev,
                      const float *top_p_dev, const uint64_t *seed_dev, const int32_t *position_dev, int32_t *ids_dev, void *stream);
+
+/* The log-probability routine of tl_engine_set_logprobs over caller rows: logits [rows, vocab] bf16 (vocab <= 524,288); ids_dev [rows]
+ * int32 (may be NULL: each row's greedy id, the first maximum; an id < 0 gives NaN) -> logprob_dev [rows] float; top_n 0 .. 20 ->
+ * top_ids_dev / top_logprobs_dev [rows, top_n] (may be NULL when top_n is 0).  One 1,024-thread workgroup per row.  Stream ordered. */
+int tl_logprob_rows(const void *logits_dev, int rows, int vocab, const int32_t *ids_dev, int top_n, float *logprob_dev, int32_t *top_ids_dev,
+                    float *top_logprobs_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--enable-thinking", action="store_true")
     ap.add_argument("--raw-prompt", action="store_true", help="do not wrap the prompt in the chat template")
     ap.add_argument("--max-new-tokens", type=int, default=256)
+    ap.add_argument("--logprobs", type=int, default=None, metavar="N",
+                    help="with --solution engine (greedy or device sampling): print each generated token with its log-probability "
+                         "and its N (0-20) most likely alternatives")
     ap.add_argument("--proposal-length", type=int, default=4)
     return ap
 
@@ -67,6 +70,7 @@ def main(argv=None) -> str:
     pages = (len(ids) + args.max_new_tokens) // 128 + 2
     engine = DecodeEngine(model, page_size=128, num_pages=pages, max_batch=1, max_prefill_rows=4096)
     eos = tokenizer.eos_token_id
+    records = None
     try:
         if args.draft_model:
             draft_model, draft_tok = load(args.draft_model)
@@ -81,17 +85,27 @@ def main(argv=None) -> str:
         elif args.sampler_temp and args.sampler_seed is not None:
             # the per-slot sampler on the device: the whole generation in one prefill + one decode(N) call
             out = engine.generate(ids, args.max_new_tokens, temperature=args.sampler_temp, top_k=args.sampler_top_k,
-                                  top_p=args.sampler_top_p, seed=args.sampler_seed)
+                                  top_p=args.sampler_top_p, seed=args.sampler_seed, logprobs=args.logprobs)
+            if args.logprobs is not None:
+                out, records = out
             if eos in out:
                 out = out[:out.index(eos)]
         elif args.sampler_temp:
             out = sample_with_engine(engine, ids, args, eos)
         else:
-            out = engine.generate(ids, args.max_new_tokens)
+            out = engine.generate(ids, args.max_new_tokens, logprobs=args.logprobs)
+            if args.logprobs is not None:
+                out, records = out
             if eos in out:
                 out = out[:out.index(eos)]
     finally:
         engine.close()
+    if records is not None:
+        for t, r in zip(out, records):
+            alts = " ".join(f"{tokenizer.decode([i])!r}:{v:.4f}" for i, v in r.top)
+            print(f"{tokenizer.decode([t])!r}\t{r.logprob:.4f}\t{alts}")
+    elif args.logprobs is not None:
+        print("note: --logprobs applies to the engine's greedy decode and its device sampler (--sampler-seed) only")
     text = tokenizer.decode(out)
     print(text)
     return text

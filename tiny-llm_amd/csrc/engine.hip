@@ -6,6 +6,7 @@
 //   * multi-token prefill on the MFMA W4 GEMM + paged FlashAttention operators of tinyllm_hip.h
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -14,6 +15,7 @@
 #include "common.h"
 #include "engine_kernels.h"
 #include "sample.h"
+#include "logprob.h"
 #include "qmv.h"
 #include "qmv3.h"
 #include "qmm3.h"
@@ -164,6 +166,17 @@ struct tl_engine {
     float *smp_temp = nullptr, *smp_topp = nullptr;
     int32_t *smp_topk = nullptr;
     uint64_t *smp_seed = nullptr;
+    // per-slot log-probability records (tl_engine_set_logprobs, logprob.h): allocated on the first set_logprobs -- top-N per slot
+    // (-1: off), the record ring [max_batch, ring_cap] and the pending record per slot; the host mirror of top-N and, per slot, the
+    // value of slot_produced when its records began (tokens since then have records)
+    char *lp_mem = nullptr;
+    int32_t *lp_topn = nullptr;
+    uint32_t *lp_ring = nullptr, *lp_pending = nullptr;
+    std::vector<int> lp_n, lp_from;
+    // tl_engine_score: the logits of one block of rows and the per-row targets / results, allocated on first use
+    uint16_t *score_logits = nullptr;
+    int32_t *score_ids = nullptr, *score_argmax = nullptr;
+    float *score_lp = nullptr;
 
     bool warmed = false;
     std::map<std::pair<int, long>, hipGraphExec_t> graphs;  // (batch, n_splits << 32 | tokens_per_split)
@@ -344,6 +357,139 @@ static __global__ __launch_bounds__(1024) void sample_step_end_kernel(const Samp
     prof_end(p.prof, prof_t0);
 }
 
+// Log-probability records (logprob.h, tl_engine_set_logprobs): the third twin of step_end_kernel.  It chooses the token as the sampling
+// twin does, runs its tail, and then writes the record of the produced token -- in the same launch, because the token a later launch of
+// the step would read is a plain store of this one (no cache maintenance between the launches of a step on the AQL route).
+struct LogprobStepEndArgs {
+    SampleStepEndArgs q;
+    const int32_t *top_n;  // [max_batch] -1: the slot records nothing
+    uint32_t *ring;        // [max_batch, ring_cap] records of LP_RECORD_WORDS words
+    uint32_t *pending;     // [max_batch] the record of each slot's pending token
+};
+
+static __global__ __launch_bounds__(1024) void logprob_step_end_kernel(const LogprobStepEndArgs lq) {
+    const SampleStepEndArgs &q = lq.q;
+    const StepEndArgs &p = q.s;
+    __shared__ SampleSmem sm;
+    __shared__ LogprobSmem ls;
+    __shared__ float s_val[16];
+    __shared__ int s_token, s_ctx, s_n;
+    const prof_t prof_t0 = prof_begin(p.prof);
+    const int i = blockIdx.x;
+    const int slot = p.slot0 + i;
+    const SmpRow row(p.logits + (long)i * p.vocab, p.vocab);
+    const float temperature = q.temperature[slot], top_p = q.top_p[slot];
+    const int top_k = q.top_k[slot];
+    const uint64_t seed = q.seed[slot];
+    const int live = p.live[slot];
+    // the sampled token's position: tokens before it (decode: the context after this step's advance; prefill: the prompt length)
+    const uint32_t position = (uint32_t)(p.context_lens[slot] + (p.advance && live ? 1 : 0));
+    float m_given = __builtin_nanf("");
+    if (p.tile_max) {  // uniform: the row maximum from the lm_head GEMV's per-tile pairs
+        const f32x2 *tm = p.tile_max + (long)i * p.tiles;
+        float t = -INFINITY;
+        for (int k = threadIdx.x; k < p.tiles; k += 1024) t = fmaxf(t, act_load(tm + k)[0]);
+        m_given = smp_block_max(t, sm);
+    }
+    if (m_given != m_given) {  // once for both routines
+        float t = -INFINITY;
+        smp_for_each(row, [&](int, int, uint32_t b) { t = fmaxf(t, __uint_as_float(b << 16)); });  // fmaxf drops NaN
+        m_given = smp_block_max(t, sm);
+    }
+    const int top_n = lq.top_n[slot];
+    const bool record = live && top_n >= 0;  // uniform
+    // a greedy slot that records takes the routine's own first maximum (smp_select's greedy id): one pass instead of two
+    float lse = 0.f;
+    if (record && temperature == 0.f) lse = lp_row(row, m_given, top_n, sm, ls);
+    const int bi = record && temperature == 0.f ? ls.greedy : smp_select(row, m_given, temperature, top_k, top_p, seed, position, sm);
+    __syncthreads();  // every thread has read context_lens[slot] above
+    if (threadIdx.x == 0) {
+        s_token = bi;
+        int ctx_now = p.context_lens[slot];
+        if (live) {
+            p.tokens[slot] = bi;
+            const int n = p.produced[slot];
+            p.ring[(long)slot * p.ring_cap + (n % p.ring_cap)] = bi;
+            p.produced[slot] = n + 1;
+            if (p.advance) p.context_lens[slot] = ++ctx_now;
+            s_n = n;
+        }
+        s_ctx = ctx_now;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < p.rope_half) {
+        const int pos = min(s_ctx, p.rope_positions - 1);  // the slot's NEXT position
+        p.rope_cur[(long)slot * p.rope_half + threadIdx.x] = p.rope_table[(long)pos * p.rope_half + threadIdx.x];
+    }
+    const int token = s_token;
+    const int words = p.hidden / 8;
+    const int groups = p.hidden / 128;
+    float sumsq = 0.f;
+    for (int w = threadIdx.x; w < words; w += 1024) {
+        const uint32_t packed = p.emb_w[(long)token * words + w];
+        const float scale = BF16::to_float(p.emb_s[(long)token * groups + w / 16]);
+        const float bias = BF16::to_float(p.emb_b[(long)token * groups + w / 16]);
+        uint16_t o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            o[e] = BF16::from_float((float)((packed >> (4 * e)) & 0xfu) * scale + bias);
+            const float v = BF16::to_float(o[e]);
+            sumsq += v * v;
+        }
+        *reinterpret_cast<uint4 *>(p.x + (long)slot * p.hidden + w * 8) = *reinterpret_cast<const uint4 *>(o);
+    }
+    if (p.ss_out) {
+        const float ws = wave_sum(sumsq);
+        if ((threadIdx.x & 63) == 0) s_val[threadIdx.x >> 6] = ws;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float tot = 0.f;
+            for (int w = 0; w < 16; ++w) tot += s_val[w];
+            p.ss_out[(long)slot * 8] = tot;
+            for (int i = 1; i < 8; ++i) p.ss_out[(long)slot * 8 + i] = 0.f;
+        }
+    }
+    if (record) {
+        if (temperature != 0.f) lse = lp_row(row, m_given, top_n, sm, ls);
+        if (threadIdx.x == 0) ls.rec[0] = __float_as_uint(BF16::to_float(act_load(row.lg + token)) - lse);
+        __syncthreads();
+        if ((int)threadIdx.x < LP_RECORD_WORDS) {
+            const uint32_t v = ls.rec[threadIdx.x];
+            lq.ring[((long)slot * p.ring_cap + (s_n % p.ring_cap)) * LP_RECORD_WORDS + threadIdx.x] = v;
+            lq.pending[(long)slot * LP_RECORD_WORDS + threadIdx.x] = v;
+        }
+    }
+    prof_end(p.prof, prof_t0);
+}
+
+// tl_logprob_rows / tl_engine_score: the routine over rows of logits.  grid = rows, block = 1024.
+struct LogprobRowsArgs {
+    const uint16_t *logits;  // [rows, vocab]
+    int vocab, top_n;
+    const int32_t *ids;      // [rows] the token whose log-probability is asked for (< 0: NaN); nullptr: each row's greedy id
+    float *logprob;          // [rows]
+    int32_t *top_ids;        // [rows, top_n] (top_n > 0)
+    float *top_logprobs;     // [rows, top_n]
+    int32_t *argmax;         // [rows] greedy ids, or nullptr
+};
+
+static __global__ __launch_bounds__(1024) void logprob_rows_kernel(const LogprobRowsArgs a) {
+    __shared__ SampleSmem sm;
+    __shared__ LogprobSmem ls;
+    const int i = blockIdx.x;
+    const SmpRow row(a.logits + (long)i * a.vocab, a.vocab);
+    const float lse = lp_row(row, __builtin_nanf(""), a.top_n, sm, ls);
+    if (threadIdx.x == 0) {
+        const int t = a.ids ? a.ids[i] : ls.greedy;
+        a.logprob[i] = t >= 0 && t < a.vocab ? BF16::to_float(row.lg[t]) - lse : __builtin_nanf("");
+        if (a.argmax) a.argmax[i] = ls.greedy;
+    }
+    if ((int)threadIdx.x < a.top_n) {
+        a.top_ids[(long)i * a.top_n + threadIdx.x] = (int32_t)ls.rec[1 + threadIdx.x];
+        a.top_logprobs[(long)i * a.top_n + threadIdx.x] = __uint_as_float(ls.rec[1 + LP_MAX_TOP + threadIdx.x]);
+    }
+}
+
 // tl_sample_logits: the same selection over caller rows, parameters per row.  grid = rows, block = 1024.
 static __global__ __launch_bounds__(1024) void sample_rows_kernel(const uint16_t *logits, int vocab, const float *temperature, const int32_t *top_k,
                                                                   const float *top_p, const uint64_t *seed, const int32_t *position, int32_t *ids) {
@@ -375,14 +521,63 @@ static int smp_write(tl_engine *e, int slot, const tl_engine::SampleParams &v) {
 static bool smp_is_default(const tl_engine::SampleParams &v) { return v.temperature == 0.f && v.top_k == 0 && v.top_p == 0.f && v.seed == 0; }
 static int smp_reset(tl_engine *e, int slot) { return smp_is_default(e->smp[slot]) ? TL_OK : smp_write(e, slot, tl_engine::SampleParams{}); }
 
-// step end of a decode step / a prefill's last row: greedy kernel, or its sampling twin when the plan samples
-static void launch_step_end(tl_engine *e, const StepEndArgs &s, int rows, bool samples) {
-    if (samples) {
+// does some live slot of [0, batch) record log-probabilities?  (the plan-key bit next to step_samples')
+static bool step_logprobs_slot(const tl_engine *e, int slot) { return !e->lp_n.empty() && e->slot_live[slot] && e->lp_n[slot] >= 0; }
+static bool step_logprobs(const tl_engine *e, int batch) {
+    for (int b = 0; b < batch; ++b)
+        if (step_logprobs_slot(e, b)) return true;
+    return false;
+}
+
+// step end of a decode step / a prefill's last row: greedy kernel, its sampling twin when the plan samples, or the logprob twin
+// (which also samples) when a slot records log-probabilities
+static void launch_step_end(tl_engine *e, const StepEndArgs &s, int rows, bool samples, bool logprobs) {
+    if (logprobs) {
+        const LogprobStepEndArgs l{{s, e->smp_temp, e->smp_topk, e->smp_topp, e->smp_seed}, e->lp_topn, e->lp_ring, e->lp_pending};
+        hipLaunchKernelGGL(logprob_step_end_kernel, dim3(rows), dim3(1024), 0, e->stream, l);
+    } else if (samples) {
         const SampleStepEndArgs q{s, e->smp_temp, e->smp_topk, e->smp_topp, e->smp_seed};
         hipLaunchKernelGGL(sample_step_end_kernel, dim3(rows), dim3(1024), 0, e->stream, q);
     } else {
         hipLaunchKernelGGL(step_end_kernel, dim3(rows), dim3(1024), 0, e->stream, s);
     }
+}
+
+// tl_engine_score: rows of the lm_head per W4 GEMM + logprob launch (the scratch holds one block of logits: 311 MB at Qwen3's vocabulary)
+constexpr int SCORE_BLOCK_ROWS = 1024;
+
+// ---- log-probability records (logprob.h) ----------------------------------------------------------------
+// the slot's top-N on the device follows the host mirror (stream-ordered, between steps); the first switch-on allocates the records
+static int lp_write(tl_engine *e, int slot, int top_n) {
+    if (e->lp_n.empty() ? top_n < 0 : e->lp_n[slot] == top_n) return TL_OK;
+    if (!e->lp_mem) {
+        const int B = e->cfg.max_batch;
+        const size_t rec = (size_t)LP_RECORD_WORDS * 4, bytes = (size_t)B * 4 + ((size_t)B * e->ring_cap + B) * rec;
+        if (hipMalloc((void **)&e->lp_mem, bytes) != hipSuccess) return fail(TL_ERR_HIP, "engine_set_logprobs: hipMalloc(records) failed");
+        e->lp_topn = (int32_t *)e->lp_mem;
+        e->lp_pending = (uint32_t *)(e->lp_mem + (size_t)B * 4);
+        e->lp_ring = e->lp_pending + (size_t)B * LP_RECORD_WORDS;
+        // all ones: top-N -1 (off), and a record nobody wrote reads as logprob NaN with ids -1
+        TL_HIP(hipMemsetAsync(e->lp_mem, 0xff, (size_t)B * 4 + (size_t)B * rec, e->stream));
+        e->lp_n.assign(B, -1);
+        e->lp_from.assign(B, 0);
+    }
+    std::vector<std::pair<int32_t *, int32_t>> pk;
+    pk.emplace_back(e->lp_topn + slot, top_n);
+    if (e->lp_n[slot] < 0) e->lp_from[slot] = e->slot_produced[slot];  // records begin with the next produced token
+    e->lp_n[slot] = top_n;
+    return poke(e, pk);
+}
+
+// tl_engine_move (move = true) / tl_engine_fork: dst takes src's setting and pending record; a move switches src off
+static int lp_carry(tl_engine *e, int src, int dst, bool move) {
+    if (e->lp_n.empty()) return TL_OK;
+    const int n = e->lp_n[src];
+    TL_TRY(lp_write(e, dst, n));
+    e->lp_from[dst] = 0;  // slot_produced[dst] restarts at 0 with the sequence
+    TL_HIP(hipMemcpyAsync(e->lp_pending + (size_t)dst * LP_RECORD_WORDS, e->lp_pending + (size_t)src * LP_RECORD_WORDS, LP_RECORD_WORDS * 4,
+                          hipMemcpyDeviceToDevice, e->stream));
+    return move ? lp_write(e, src, -1) : TL_OK;
 }
 
 static int check_w4(const tl_w4 &w, int rows, int cols, const char *name) {
@@ -1219,7 +1414,7 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, ProfCtx *pc = nul
     s.rope_half = c.head_dim / 2;
     s.ss_out = e->ss_x;
     s.prof = pc ? pc->buf : nullptr;
-    launch_step_end(e, s, batch, step_samples(e, batch));
+    launch_step_end(e, s, batch, step_samples(e, batch), step_logprobs(e, batch));
     if (pc) prof_after(e, pc, 7, batch);
     TL_CHECK_LAUNCH("engine step end");
     return TL_OK;
@@ -1799,6 +1994,8 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     for (auto &kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
     if (e->arena) (void)hipFree(e->arena);
     if (e->smp_mem) (void)hipFree(e->smp_mem);
+    if (e->lp_mem) (void)hipFree(e->lp_mem);
+    if (e->score_logits) (void)hipFree(e->score_logits);
     if (e->kpool) (void)hipFree(e->kpool);
     if (e->vpool) (void)hipFree(e->vpool);
     if (e->kscale_pool) (void)hipFree(e->kscale_pool);
@@ -1842,6 +2039,7 @@ extern "C" int tl_engine_begin(tl_engine *e, int slot) {
     pk.emplace_back(e->produced + slot, 0);
     pk.emplace_back(e->tokens + slot, 0);
     TL_TRY(poke(e, pk));
+    TL_TRY(lp_write(e, slot, -1));
     return smp_reset(e, slot);
 }
 
@@ -1870,6 +2068,7 @@ extern "C" int tl_engine_release(tl_engine *e, int slot) {
     pk.emplace_back(e->tokens + slot, 0);
     e->stats.pages_free = (int)e->free_pages.size();
     TL_TRY(poke(e, pk));
+    TL_TRY(lp_write(e, slot, -1));
     return smp_reset(e, slot);
 }
 
@@ -1948,6 +2147,8 @@ extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
     e->stats.pages_free = (int)e->free_pages.size();
     // the sampling parameters are copied too (seed included: give the child its own seed, or both draw the same tokens)
     if (!smp_is_default(e->smp[src]) || !smp_is_default(e->smp[dst])) TL_TRY(smp_write(e, dst, e->smp[src]));
+    // ... and the log-probability setting with the pending token's record
+    TL_TRY(lp_carry(e, src, dst, false));
     return TL_OK;
 }
 
@@ -1987,7 +2188,8 @@ extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
         TL_TRY(smp_write(e, dst, v));
         TL_TRY(smp_write(e, src, tl_engine::SampleParams{}));
     }
-    return TL_OK;
+    // ... and so do the log-probability setting and the pending token's record (the record ring restarts, like the token ring)
+    return lp_carry(e, src, dst, true);
 }
 
 // Pending token ids of slots [0, count) after synchronising the stream (one copy per decode step instead of one
@@ -2038,8 +2240,53 @@ extern "C" int tl_sample_logits(const void *logits_dev, int rows, int vocab, con
     return TL_OK;
 }
 
+extern "C" int tl_engine_set_logprobs(tl_engine *e, int slot, int top_n) {
+    TL_TRY(slot_check(e, slot, false));
+    TL_REQUIRE(top_n >= -1 && top_n <= LP_MAX_TOP, "engine_set_logprobs: top_n must be -1 (off) or 0 .. 20");
+    TL_REQUIRE(top_n < 0 || e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_set_logprobs: vocabulary larger than the routine's 524,288 tokens");
+    return lp_write(e, slot, top_n);
+}
+
+extern "C" int tl_engine_read_logprobs(tl_engine *e, int slot, int count, tl_token_logprob *out) {
+    TL_TRY(slot_check(e, slot, false));
+    TL_REQUIRE(out && count >= 0 && count <= e->ring_cap, "engine_read_logprobs: bad count");
+    const int have = e->lp_n.empty() || e->lp_n[slot] < 0 ? 0 : e->slot_produced[slot] - e->lp_from[slot];
+    TL_REQUIRE(count <= have, "engine_read_logprobs: fewer tokens have been produced since logprobs were switched on");
+    if (count == 0) return TL_OK;
+    TL_HIP(hipStreamSynchronize(e->stream));
+    const size_t rec = (size_t)LP_RECORD_WORDS * 4;
+    const int produced = e->slot_produced[slot];
+    std::vector<char> ring((size_t)e->ring_cap * rec);
+    TL_HIP(hipMemcpy(ring.data(), e->lp_ring + (size_t)slot * e->ring_cap * LP_RECORD_WORDS, ring.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < count; ++i) memcpy(out + i, ring.data() + (size_t)((produced - count + i) % e->ring_cap) * rec, rec);
+    return TL_OK;
+}
+
+extern "C" int tl_engine_read_pending_logprobs(tl_engine *e, int count, tl_token_logprob *out) {
+    TL_REQUIRE(e && out, "engine_read_pending_logprobs: null argument");
+    TL_REQUIRE(count > 0 && count <= e->cfg.max_batch, "engine_read_pending_logprobs: count out of range");
+    TL_REQUIRE(e->lp_mem, "engine_read_pending_logprobs: no slot has recorded log-probabilities (tl_engine_set_logprobs)");
+    TL_HIP(hipStreamSynchronize(e->stream));
+    TL_HIP(hipMemcpy(out, e->lp_pending, (size_t)count * LP_RECORD_WORDS * 4, hipMemcpyDeviceToHost));
+    return TL_OK;
+}
+
+extern "C" int tl_logprob_rows(const void *logits_dev, int rows, int vocab, const int32_t *ids_dev, int top_n, float *logprob_dev,
+                               int32_t *top_ids_dev, float *top_logprobs_dev, void *stream) {
+    TL_REQUIRE(logits_dev && logprob_dev, "logprob_rows: null argument");
+    TL_REQUIRE(rows > 0 && rows <= 65535, "logprob_rows: rows out of range");
+    TL_REQUIRE(vocab > 0 && vocab <= SMP_MAX_VOCAB, "logprob_rows: vocabulary out of range (1 .. 524,288)");
+    TL_REQUIRE(top_n >= 0 && top_n <= LP_MAX_TOP, "logprob_rows: top_n must be 0 .. 20");
+    TL_REQUIRE(top_n == 0 || (top_ids_dev && top_logprobs_dev), "logprob_rows: top_n > 0 needs top_ids and top_logprobs");
+    const LogprobRowsArgs a{(const uint16_t *)logits_dev, vocab, top_n, ids_dev, logprob_dev, top_ids_dev, top_logprobs_dev, nullptr};
+    hipLaunchKernelGGL(logprob_rows_kernel, dim3(rows), dim3(1024), 0, (hipStream_t)stream, a);
+    TL_CHECK_LAUNCH("logprob_rows");
+    return TL_OK;
+}
+
 // logits_mode: 0 = none, 1 = last row (greedy id recorded as the slot's pending token), 2 = every row (n <= 8: greedy ids
-// land in e->verify_ids, nothing is recorded; speculative verification)
+// land in e->verify_ids, nothing is recorded; speculative verification), 3 = every row scored (tl_engine_score: the log-probability
+// of e->score_ids[i] and the greedy id of every row into e->score_lp / e->score_argmax, nothing recorded, e->logits untouched)
 // the paged attention operator over layer l's pages, by the engine's page format
 static int engine_paged_attention(tl_engine *e, int l, const uint16_t *q_t, const int32_t *block_row, const int32_t *ctx_dev, uint16_t *attn_t,
                                   int n, int ctx_hint) {
@@ -2133,6 +2380,18 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
     pk.emplace_back(e->context_lens + slot, start + n);
     TL_TRY(poke(e, pk));
     e->stats.prefill_tokens += n;
+    if (logits_mode == 3) {
+        // the final RMSNorm over the chunk's rows, then the lm_head through the W4 GEMM a block of rows at a time into the scoring
+        // scratch, each block followed by the logprob routine in gather mode
+        TL_TRY(tl_rms_norm(e->x, e->final_norm, e->xn, n, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
+        for (int r0 = 0; r0 < n; r0 += SCORE_BLOCK_ROWS) {
+            const int rows = std::min(SCORE_BLOCK_ROWS, n - r0);
+            TL_TRY(engine_gemm(e, e->head(), e->xn + (size_t)r0 * c.hidden_size, e->score_logits, rows, EPI_STORE, nullptr));
+            const LogprobRowsArgs a{e->score_logits, c.vocab_size, 0, e->score_ids + r0, e->score_lp + r0, nullptr, nullptr, e->score_argmax + r0};
+            hipLaunchKernelGGL(logprob_rows_kernel, dim3(rows), dim3(1024), 0, e->stream, a);
+            TL_CHECK_LAUNCH("engine score logprobs");
+        }
+    }
     if (logits_mode == 2) {
         TL_TRY(engine_qmv(e, e->head(), e->x, e->logits, n, PRO_RMSNORM, EPI_STORE, e->final_norm, nullptr));
         e->logits_rows = n;
@@ -2164,7 +2423,7 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
         s.rope_cur = e->rope_cur;
         s.rope_positions = e->rope_positions;
         s.rope_half = c.head_dim / 2;
-        launch_step_end(e, s, 1, e->smp[slot].samples());
+        launch_step_end(e, s, 1, e->smp[slot].samples(), step_logprobs_slot(e, slot));
         TL_CHECK_LAUNCH("engine prefill argmax");
         e->slot_produced[slot] += 1;
     }
@@ -2305,7 +2564,7 @@ static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const
             s.rope_cur = e->rope_cur;
             s.rope_positions = e->rope_positions;
             s.rope_half = c.head_dim / 2;
-            launch_step_end(e, s, 1, e->smp[slots[i]].samples());
+            launch_step_end(e, s, 1, e->smp[slots[i]].samples(), step_logprobs_slot(e, slots[i]));
             TL_CHECK_LAUNCH("engine packed prefill argmax");
             e->slot_produced[slots[i]] += 1;
             ++j;
@@ -2322,6 +2581,29 @@ extern "C" int tl_engine_prefill_packed(tl_engine *e, int n_seqs, const int *slo
 
 extern "C" int tl_engine_prefill(tl_engine *e, int slot, const int32_t *tokens, int n, int want_logits) {
     return prefill_impl(e, slot, tokens, n, want_logits ? 1 : 0);
+}
+
+extern "C" int tl_engine_score(tl_engine *e, int slot, const int32_t *tokens, int n, int32_t next_token, float *out_logprobs,
+                               int32_t *out_argmax) {
+    TL_REQUIRE(e && tokens && out_logprobs, "engine_score: null argument");
+    TL_REQUIRE(n >= 1 && n <= e->cfg.max_prefill_rows, "engine_score: between 1 and max_prefill_rows tokens per call");
+    TL_REQUIRE(next_token < e->cfg.vocab_size, "engine_score: next_token out of range");
+    TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_score: vocabulary larger than the routine's 524,288 tokens");
+    if (!e->score_logits) {
+        const size_t R = (size_t)e->cfg.max_prefill_rows, logit_bytes = align_up((size_t)SCORE_BLOCK_ROWS * e->cfg.vocab_size * 2, 256);
+        if (hipMalloc((void **)&e->score_logits, logit_bytes + R * 12) != hipSuccess) return fail(TL_ERR_HIP, "engine_score: hipMalloc(scratch) failed");
+        e->score_ids = (int32_t *)((char *)e->score_logits + logit_bytes);
+        e->score_lp = (float *)(e->score_ids + R);
+        e->score_argmax = e->score_ids + 2 * R;
+    }
+    std::vector<int32_t> targets(tokens + 1, tokens + n);
+    targets.push_back(next_token < 0 ? -1 : next_token);
+    TL_HIP(hipMemcpyAsync(e->score_ids, targets.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    TL_TRY(prefill_impl(e, slot, tokens, n, 3));
+    TL_HIP(hipMemcpyAsync(out_logprobs, e->score_lp, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    if (out_argmax) TL_HIP(hipMemcpyAsync(out_argmax, e->score_argmax, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    TL_HIP(hipStreamSynchronize(e->stream));
+    return TL_OK;
 }
 
 extern "C" int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, int n, int32_t *out_ids) {
@@ -2370,7 +2652,7 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
                        c.vocab_size, e->context_lens, e->rope_table, e->rope_cur, e->rope_positions, c.head_dim / 2, e->ss_x);
     TL_CHECK_LAUNCH("engine embed");
     std::vector<std::pair<int32_t *, int32_t>> pk;
-    const bool samples = step_samples(e, batch);
+    const bool samples = step_samples(e, batch), logprobs = step_logprobs(e, batch);
     bool on_queue = false;  // steps of this call are in flight on the AQL queue (the stream is idle and must stay so until they are drained)
     for (int s = 0; s < steps; ++s) {
         int max_ctx = 1;
@@ -2389,8 +2671,9 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
         }
         const SplitPlan sp = pick_decode_splits(e, batch, max_ctx);
         if (use_graph && e->warmed) {
-            // bit 62: the step ends with the sampling twin of step_end_kernel (re-derived every call from the slots' parameters)
-            const auto key = std::make_pair(batch, sp.key() | (samples ? (1L << 62) : 0L));
+            // bit 62: the step ends with the sampling twin of step_end_kernel, bit 61: with the logprob twin (both re-derived every call
+            // from the slots' parameters)
+            const auto key = std::make_pair(batch, sp.key() | (samples ? (1L << 62) : 0L) | (logprobs ? (1L << 61) : 0L));
             auto it = e->graphs.find(key);
             if (it == e->graphs.end()) {
                 // The split plan (and with it the key) changes every 64 * n_splits tokens of context: a long run would keep one

@@ -221,6 +221,95 @@ __device__ __forceinline__ int smp_find(const SmpRow &row, F val, float ufrac, f
     return res;
 }
 
+// The boundary of the kept set, in windows of 256 keys counted down from kmax: sets bkey (the key of the last kept logit; -1: every
+// ranked token is kept) and keep_r (how many tokens of that key are kept, the first ones in token order), keeping at most K tokens and,
+// with use_p, stopping where the temperature-1 mass exp(l - m) * inv_z ranked before a token reaches top_p.  Expanded in place in
+// smp_select and lp_row (logprob.h) over their locals row, sm, tid, lane, w, m, kmax, K, use_p, top_p, inv_z, bkey, keep_r: a function
+// would be simplified on its own before it is inlined, and the sampler's machine code would change with it.
+#define SMP_BOUNDARY_SEARCH() \
+        /* wave 0's running totals over the windows already scanned */                                                          \
+        float c_above = 0.f, m_above = 0.f;                                                                                     \
+        int base = 0;                                                                                                           \
+        for (;;) {                                                                                                              \
+                    if (tid < 256) sm.hist[tid] = 0u;                                                                           \
+            __syncthreads();                                                                                                    \
+            int dnext = 0x7fffffff;                                                                                             \
+            smp_for_each(row, [&](int, int, uint32_t b) {                                                                       \
+                if (smp_nan(b)) return;                                                                                         \
+                const int d = kmax - smp_key(b) - base;                                                                         \
+                if ((unsigned)d < 256u) atomicAdd(&sm.hist[d], 1u);                                                             \
+                else if (d >= 256) dnext = min(dnext, d + base);                                                                \
+            });                                                                                                                 \
+            {                                                                                                                   \
+                const float dn = -wave_max(-(float)dnext);                                                                      \
+                if (lane == 0) sm.f[w] = dn;                                                                                    \
+            }                                                                                                                   \
+            __syncthreads();                                                                                                    \
+            if (w == 0) {                                                                                                       \
+                float gmin = sm.f[0];                                                                                           \
+                for (int q = 1; q < 16; ++q) gmin = fminf(gmin, sm.f[q]);                                                       \
+                float cnt[4], pk[4];                                                                                            \
+                float lc = 0.f, lm = 0.f;                                                                                       \
+_Pragma("unroll")                                                                                                               \
+                for (int q = 0; q < 4; ++q) {                                                                                   \
+                    const int bin = lane * 4 + q;                                                                               \
+                    cnt[q] = (float)sm.hist[bin];                                                                               \
+                    const int key = kmax - base - bin;                                                                          \
+                    pk[q] = (use_p && cnt[q] > 0.f) ? exp2_hw((smp_key_value(key) - m) * 1.44269504089f) * inv_z : 0.f;         \
+                    lc += cnt[q];                                                                                               \
+                    lm += cnt[q] * pk[q];                                                                                       \
+                }                                                                                                               \
+                float ic = lc, im = lm;  /* inclusive lane scans (counts are exact in fp32) */                                  \
+_Pragma("unroll")                                                                                                               \
+                for (int o = 1; o < 64; o <<= 1) {                                                                              \
+                    const float yc = __shfl_up(ic, o, 64), ym = __shfl_up(im, o, 64);                                           \
+                    if (lane >= o) ic += yc, im += ym;                                                                          \
+                }                                                                                                               \
+                float cb = c_above + (ic - lc), mb = m_above + __shfl_up(im, 1, 64);                                            \
+                if (lane == 0) mb = m_above;                                                                                    \
+                int hit_bin = -1, hit_r = 0;                                                                                    \
+_Pragma("unroll")                                                                                                               \
+                for (int q = 0; q < 4; ++q) {                                                                                   \
+                    if (hit_bin < 0 && cnt[q] > 0.f) {                                                                          \
+                        const float rk = (float)K - cb;                                                                         \
+                        float rp = 3.0e38f;                                                                                     \
+                        if (use_p && pk[q] > 0.f) rp = fminf(ceilf((top_p - mb) / pk[q]), 3.0e38f);                             \
+                        if (cb == 0.f) rp = fmaxf(rp, 1.f);                                                                     \
+                        const float r = fminf(cnt[q], fminf(rk, rp));                                                           \
+                        const bool boundary = r < cnt[q] || cb + cnt[q] >= (float)K || (use_p && mb + cnt[q] * pk[q] >= top_p); \
+                        if (boundary) hit_bin = lane * 4 + q, hit_r = (int)fmaxf(r, 1.f);                                       \
+                    }                                                                                                           \
+                    cb += cnt[q];                                                                                               \
+                    mb += cnt[q] * pk[q];                                                                                       \
+                }                                                                                                               \
+                const unsigned long long bal = __ballot(hit_bin >= 0);                                                          \
+                const float tot_c = __shfl(ic, 63, 64), tot_m = __shfl(im, 63, 64);                                             \
+                if (bal) {                                                                                                      \
+                    if (lane == __ffsll((long long)bal) - 1) {                                                                  \
+                        sm.bkey = kmax - base - hit_bin;                                                                        \
+                        sm.keep_r = hit_r;                                                                                      \
+                        sm.done = 1;                                                                                            \
+                    }                                                                                                           \
+                } else {                                                                                                        \
+                    c_above += tot_c;                                                                                           \
+                    m_above += tot_m;                                                                                           \
+                    if (lane == 0) {                                                                                            \
+                        sm.done = gmin > 1.0e9f ? 2 : 0;  /* 2: no key below the window, every token is kept */                 \
+                        sm.base = gmin > 1.0e9f ? base : (int)gmin;                                                             \
+                    }                                                                                                           \
+                }                                                                                                               \
+            }                                                                                                                   \
+            __syncthreads();                                                                                                    \
+            const int done = sm.done;                                                                                           \
+            base = sm.base;                                                                                                     \
+            if (done == 1) {                                                                                                    \
+                bkey = sm.bkey;                                                                                                 \
+                keep_r = sm.keep_r;                                                                                             \
+            }                                                                                                                   \
+            __syncthreads();                                                                                                    \
+            if (done) break;                                                                                                    \
+        }
+
 // The token of one row (the same value in every thread).  m_given: the row's maximum when the caller has it (the lm_head GEMV's tile
 // maxima), NaN to reduce it here.
 __device__ __forceinline__ int smp_select(const SmpRow &row, float m_given, float temperature, int top_k, float top_p,
@@ -251,88 +340,7 @@ __device__ __forceinline__ int smp_select(const SmpRow &row, float m_given, floa
             });
             inv_z = 1.f / smp_block_sum(z, sm);
         }
-        // wave 0's running totals over the windows already scanned
-        float c_above = 0.f, m_above = 0.f;
-        int base = 0;
-        for (;;) {
-                    if (tid < 256) sm.hist[tid] = 0u;
-            __syncthreads();
-            int dnext = 0x7fffffff;
-            smp_for_each(row, [&](int, int, uint32_t b) {
-                if (smp_nan(b)) return;
-                const int d = kmax - smp_key(b) - base;
-                if ((unsigned)d < 256u) atomicAdd(&sm.hist[d], 1u);
-                else if (d >= 256) dnext = min(dnext, d + base);
-            });
-            {
-                const float dn = -wave_max(-(float)dnext);
-                if (lane == 0) sm.f[w] = dn;
-            }
-            __syncthreads();
-            if (w == 0) {
-                float gmin = sm.f[0];
-                for (int q = 1; q < 16; ++q) gmin = fminf(gmin, sm.f[q]);
-                float cnt[4], pk[4];
-                float lc = 0.f, lm = 0.f;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int bin = lane * 4 + q;
-                    cnt[q] = (float)sm.hist[bin];
-                    const int key = kmax - base - bin;
-                    pk[q] = (use_p && cnt[q] > 0.f) ? exp2_hw((smp_key_value(key) - m) * 1.44269504089f) * inv_z : 0.f;
-                    lc += cnt[q];
-                    lm += cnt[q] * pk[q];
-                }
-                float ic = lc, im = lm;  // inclusive lane scans (counts are exact in fp32)
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const float yc = __shfl_up(ic, o, 64), ym = __shfl_up(im, o, 64);
-                    if (lane >= o) ic += yc, im += ym;
-                }
-                float cb = c_above + (ic - lc), mb = m_above + __shfl_up(im, 1, 64);
-                if (lane == 0) mb = m_above;
-                int hit_bin = -1, hit_r = 0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (hit_bin < 0 && cnt[q] > 0.f) {
-                        const float rk = (float)K - cb;
-                        float rp = 3.0e38f;
-                        if (use_p && pk[q] > 0.f) rp = fminf(ceilf((top_p - mb) / pk[q]), 3.0e38f);
-                        if (cb == 0.f) rp = fmaxf(rp, 1.f);
-                        const float r = fminf(cnt[q], fminf(rk, rp));
-                        const bool boundary = r < cnt[q] || cb + cnt[q] >= (float)K || (use_p && mb + cnt[q] * pk[q] >= top_p);
-                        if (boundary) hit_bin = lane * 4 + q, hit_r = (int)fmaxf(r, 1.f);
-                    }
-                    cb += cnt[q];
-                    mb += cnt[q] * pk[q];
-                }
-                const unsigned long long bal = __ballot(hit_bin >= 0);
-                const float tot_c = __shfl(ic, 63, 64), tot_m = __shfl(im, 63, 64);
-                if (bal) {
-                    if (lane == __ffsll((long long)bal) - 1) {
-                        sm.bkey = kmax - base - hit_bin;
-                        sm.keep_r = hit_r;
-                        sm.done = 1;
-                    }
-                } else {
-                    c_above += tot_c;
-                    m_above += tot_m;
-                    if (lane == 0) {
-                        sm.done = gmin > 1.0e9f ? 2 : 0;  // 2: no key below the window, every token is kept
-                        sm.base = gmin > 1.0e9f ? base : (int)gmin;
-                    }
-                }
-            }
-            __syncthreads();
-            const int done = sm.done;
-            base = sm.base;
-            if (done == 1) {
-                bkey = sm.bkey;
-                keep_r = sm.keep_r;
-            }
-            __syncthreads();
-            if (done) break;
-        }
+        SMP_BOUNDARY_SEARCH();
     }
     // the cut inside the boundary key: the keep_r-th token of that key in token order is the last one kept
     int cutoff = 0x7fffffff;

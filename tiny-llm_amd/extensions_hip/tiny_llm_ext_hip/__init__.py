@@ -122,6 +122,15 @@ class TlStepCheck(ctypes.Structure):
                 ("first_offset", ctypes.c_long)]
 
 
+TL_MAX_TOP_LOGPROBS = 20
+
+
+class TlTokenLogprob(ctypes.Structure):
+    """tl_token_logprob (include/tinyllm_engine.h): the produced token's log-probability and the top-N entries (id -1 / -inf past N)."""
+    _fields_ = [("logprob", ctypes.c_float), ("top_ids", ctypes.c_int32 * TL_MAX_TOP_LOGPROBS),
+                ("top_logprobs", ctypes.c_float * TL_MAX_TOP_LOGPROBS)]
+
+
 class TlLinearInfo(ctypes.Structure):
     _fields_ = [("kernel", _c_int), ("launches", _c_int), ("rows_per_pass", _c_int), ("p", _c_int * 5)]
 
@@ -184,6 +193,11 @@ _SIGNATURES.update({
     "tl_engine_set_token": (_c_int, [_c_void_p, _c_int, ctypes.c_int32]),
     "tl_engine_set_sampling": (_c_int, [_c_void_p, _c_int, _c_float, _c_int, _c_float, ctypes.c_uint64]),
     "tl_sample_logits": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 7),
+    "tl_engine_set_logprobs": (_c_int, [_c_void_p, _c_int, _c_int]),
+    "tl_engine_read_logprobs": (_c_int, [_c_void_p, _c_int, _c_int, _P(TlTokenLogprob)]),
+    "tl_engine_read_pending_logprobs": (_c_int, [_c_void_p, _c_int, _P(TlTokenLogprob)]),
+    "tl_engine_score": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, ctypes.c_int32, _P(_c_float), _P(ctypes.c_int32)]),
+    "tl_logprob_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "tl_engine_decode": (_c_int, [_c_void_p, _c_int, _c_int, _c_int]),
     "tl_engine_read_tokens": (_c_int, [_c_void_p, _c_int, _c_int, _P(ctypes.c_int32)]),
     "tl_engine_logits_dev": (_c_void_p, [_c_void_p]),
@@ -928,3 +942,29 @@ def sample_logits(logits: torch.Tensor, temperature, top_k, top_p, seed, positio
     check(_lib.tl_sample_logits(logits.data_ptr(), rows, logits.shape[1], t_t.data_ptr(), k_t.data_ptr(), p_t.data_ptr(), seed_t.data_ptr(),
                                 pos_t.data_ptr(), ids.data_ptr(), _stream()))
     return ids
+
+
+def logprob_rows(logits: torch.Tensor, ids=None, top_n: int = 0):
+    """The decode engine's log-probability routine (tl_logprob_rows) over rows of bf16 logits [rows, vocab]: ``ids`` None (each row's
+    greedy id), one id for every row or one per row (an id < 0 gives NaN); ``top_n`` 0 .. 20.  Returns (logprob float32 [rows],
+    top_ids int32 [rows, top_n], top_logprobs float32 [rows, top_n])."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("logprob_rows takes a [rows, vocab] bf16 tensor on the GPU")
+    if isinstance(top_n, bool) or not isinstance(top_n, int) or not 0 <= top_n <= TL_MAX_TOP_LOGPROBS:
+        raise ValueError(f"top_n must be an int in [0, {TL_MAX_TOP_LOGPROBS}], got {top_n!r}")
+    logits = logits.contiguous()
+    rows, dev = logits.shape[0], logits.device
+    ids_t = None
+    if ids is not None:
+        ids_t = torch.as_tensor(ids, dtype=torch.int32).reshape(-1)
+        if ids_t.numel() == 1:
+            ids_t = ids_t.expand(rows)
+        if ids_t.numel() != rows:
+            raise ValueError("ids needs one value per row")
+        ids_t = ids_t.contiguous().to(dev)
+    lp = torch.empty(rows, dtype=torch.float32, device=dev)
+    top_ids = torch.empty((rows, top_n), dtype=torch.int32, device=dev)
+    top_lp = torch.empty((rows, top_n), dtype=torch.float32, device=dev)
+    check(_lib.tl_logprob_rows(logits.data_ptr(), rows, logits.shape[1], ids_t.data_ptr() if ids_t is not None else None, top_n,
+                               lp.data_ptr(), top_ids.data_ptr() if top_n else None, top_lp.data_ptr() if top_n else None, _stream()))
+    return lp, top_ids, top_lp

@@ -15,7 +15,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from typing import Any, Sequence
+from typing import Any, NamedTuple, Sequence
 
 import torch
 
@@ -205,6 +205,25 @@ class DecodeEngine:
         t, k, p, s = sampling_args(temperature, top_k, top_p, seed)
         _ext.check(_lib.tl_engine_set_sampling(self._h, slot, t, k, p, s))
 
+    def set_logprobs(self, slot: int, top_n: int | None) -> None:
+        """Per-token log-probabilities (tl_engine_set_logprobs): from the slot's next produced token on, record the model's
+        temperature-1 log-probability of every token it produces and its ``top_n`` (0 .. 20) most likely alternatives; None switches
+        recording off.  begin / release switch it off, move carries it along, fork copies it."""
+        _ext.check(_lib.tl_engine_set_logprobs(self._h, slot, logprobs_arg(top_n)))
+
+    def read_logprobs(self, slot: int, count: int) -> list["TokenLogprob"]:
+        """Records of the slot's last ``count`` produced tokens (like read_tokens); synchronises."""
+        out = (_ext.TlTokenLogprob * max(count, 1))()
+        _ext.check(_lib.tl_engine_read_logprobs(self._h, slot, count, out))
+        return [TokenLogprob.of(out[i]) for i in range(count)]
+
+    def read_pending_logprobs(self, count: int | None = None) -> list["TokenLogprob"]:
+        """Record of the pending token of slots [0, count) (the companion of read_pending); synchronises."""
+        count = count or self.max_batch
+        out = (_ext.TlTokenLogprob * count)()
+        _ext.check(_lib.tl_engine_read_pending_logprobs(self._h, count, out))
+        return [TokenLogprob.of(out[i]) for i in range(count)]
+
     # -- compute -----------------------------------------------------------------------------------
     def prefill(self, slot: int, tokens: Sequence[int], *, chunk: int | None = None, want_logits: bool = True) -> None:
         """Chunked prefill (reference Request.try_prefill, batch.py:48-76): all chunks append K/V, the last one
@@ -243,6 +262,30 @@ class DecodeEngine:
         out = (ctypes.c_int32 * len(tokens))()
         _ext.check(_lib.tl_engine_verify(self._h, slot, arr, len(tokens), out))
         return list(out)
+
+    def score(self, tokens: Sequence[int], *, slot: int = 0, chunk: int | None = None) -> list[float]:
+        """Log-probabilities of ``tokens[1:]``, each given the tokens before it (tl_engine_score), on the free ``slot`` as a fresh
+        sequence, in chunks of at most ``chunk`` (default: max_prefill_rows) tokens; each chunk's last row scores the next chunk's
+        first token.  The slot is released afterwards.  Synchronises."""
+        tokens = [int(t) for t in tokens]
+        if not tokens:
+            raise ValueError("score needs at least one token")
+        chunk = self.max_prefill_rows if chunk is None else chunk
+        if isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= self.max_prefill_rows:
+            raise ValueError(f"chunk must be an int in [1, {self.max_prefill_rows}], got {chunk!r}")
+        out: list[float] = []
+        self.begin(slot)
+        try:
+            for start in range(0, len(tokens), chunk):
+                part = tokens[start:start + chunk]
+                nxt = tokens[start + chunk] if start + chunk < len(tokens) else -1
+                arr = (ctypes.c_int32 * len(part))(*part)
+                lp = (ctypes.c_float * len(part))()
+                _ext.check(_lib.tl_engine_score(self._h, slot, arr, len(part), nxt, lp, None))
+                out.extend(lp)
+        finally:
+            self.release(slot)
+        return out[:-1]
 
     def decode(self, steps: int, batch: int | None = None, use_graph: bool = True) -> None:
         """Enqueue ``steps`` decode steps over slots [0, batch) (greedy, or each slot's sampler: set_sampling); does not synchronise
@@ -298,20 +341,45 @@ class DecodeEngine:
 
     # -- convenience: one request, like benches/bench.py:run_one_request_week2 --------------------------
     def generate(self, prompt: Sequence[int], max_new_tokens: int, *, slot: int = 0, chunk: int | None = None,
-                 temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None, seed: int = 0) -> list[int]:
+                 temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None, seed: int = 0,
+                 logprobs: int | None = None):
         """One request: prefill, then ``max_new_tokens - 1`` decode steps in one call; greedy unless ``temperature`` > 0 (the
-        device sampler, set_sampling)."""
+        device sampler, set_sampling).  With ``logprobs`` an int (0 .. 20 alternatives, set_logprobs): returns (ids, records)."""
         args = sampling_args(temperature, top_k, top_p, seed)
+        top_n = logprobs_arg(logprobs)
         self.begin(slot)
         try:
             if args[0] > 0.0:
                 self.set_sampling(slot, *args)
+            if top_n >= 0:
+                self.set_logprobs(slot, top_n)
             self.prefill(slot, prompt, chunk=chunk)
             if max_new_tokens > 1:
                 self.decode(max_new_tokens - 1, batch=slot + 1)
-            return self.read_tokens(slot, max_new_tokens)
+            ids = self.read_tokens(slot, max_new_tokens)
+            return (ids, self.read_logprobs(slot, max_new_tokens)) if top_n >= 0 else ids
         finally:
             self.release(slot)
+
+
+class TokenLogprob(NamedTuple):
+    """One produced token's record: its log-probability under the model (temperature 1, unfiltered) and the top-N alternatives as
+    (id, log-probability) pairs, most likely first."""
+    logprob: float
+    top: list
+
+    @staticmethod
+    def of(rec: "_ext.TlTokenLogprob") -> "TokenLogprob":
+        return TokenLogprob(float(rec.logprob), [(int(i), float(v)) for i, v in zip(rec.top_ids, rec.top_logprobs) if i >= 0])
+
+
+def logprobs_arg(top_n: int | None) -> int:
+    """tl_engine_set_logprobs' top_n: None -> -1 (off), else an int in [0, 20]."""
+    if top_n is None:
+        return -1
+    if isinstance(top_n, bool) or not isinstance(top_n, int) or not 0 <= top_n <= _ext.TL_MAX_TOP_LOGPROBS:
+        raise ValueError(f"logprobs must be None or an int in [0, {_ext.TL_MAX_TOP_LOGPROBS}], got {top_n!r}")
+    return top_n
 
 
 def sampling_args(temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None,
@@ -364,7 +432,7 @@ _DECODE_ROW_BUCKETS = (1, 2, 3, 4, 8, 16, 32, 48, 64, 96, 128, 192, 256)
 
 def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], max_new_tokens: int | Sequence[int],
                        batch_size: int, prefill_step: int = 128, eos_token_id: int | None = None,
-                       on_step=None, sampling=None, base_seed: int = 0) -> list[tuple[int, list[int]]]:
+                       on_step=None, sampling=None, base_seed: int = 0, logprobs: int | None = None) -> list[tuple]:
     """Continuous batching over engine slots with the reference scheduler's shape (batch_generate,
     src/tiny_llm_ref/batch.py:136-285; benches/bench.py:run_batch_requests_serving 351-572): every loop turn
     (a) admits one pending request and prefills ONE chunk of at most ``prefill_step`` tokens in the staging slot,
@@ -374,13 +442,16 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     Token-id in, token-id out (no tokenizer can be downloaded here).  Needs ``engine.max_batch >= batch_size + 1``:
     the last slot is the prefill staging slot.  Returns [(prompt_idx, generated ids)] in completion order.
     ``sampling``: None (greedy), one dict or one dict per prompt (request_sampling); applied when a request enters the staging slot,
-    and carried by the engine through its slot moves."""
+    and carried by the engine through its slot moves.  ``logprobs``: None, or an int (0 .. 20 alternatives): every request records
+    its tokens' log-probabilities (set_logprobs), read in the same turn as the pending ids, and the result is
+    [(prompt_idx, generated ids, records)]."""
     if batch_size <= 0 or prefill_step <= 0:
         raise ValueError("batch_size and prefill_step must be positive")
     if engine.max_batch < batch_size + 1:
         raise ValueError("engine needs batch_size + 1 slots (one prefill staging slot)")
     limits = [max_new_tokens] * len(prompts) if isinstance(max_new_tokens, int) else list(max_new_tokens)
     per_request = request_sampling(sampling, len(prompts), base_seed)
+    top_n = logprobs_arg(logprobs)
     staging = batch_size
     queue = list(range(len(prompts)))
     slots: list[dict | None] = [None] * batch_size
@@ -395,7 +466,9 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                 live_slots.add(staging)
                 if per_request is not None and per_request[idx][0] > 0.0:
                     engine.set_sampling(staging, *per_request[idx])
-                pending = {"idx": idx, "tokens": [int(t) for t in prompts[idx]], "offset": 0, "out": [], "limit": limits[idx]}
+                if top_n >= 0:
+                    engine.set_logprobs(staging, top_n)
+                pending = {"idx": idx, "tokens": [int(t) for t in prompts[idx]], "offset": 0, "out": [], "limit": limits[idx], "lp": []}
             if pending is not None:
                 total = len(pending["tokens"])
                 if pending["offset"] < total:
@@ -405,12 +478,14 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                     pending["offset"] += len(chunk)
                     if last:
                         pending["out"].append(engine.read_tokens(staging, 1)[0])
+                        if top_n >= 0:
+                            pending["lp"].append(engine.read_logprobs(staging, 1)[0])
                 if pending["offset"] >= total:
                     done = len(pending["out"]) >= pending["limit"] or pending["out"][-1] == eos_token_id
                     if done:
                         engine.release(staging)
                         live_slots.discard(staging)
-                        finished.append((pending["idx"], pending["out"]))
+                        finished.append((pending["idx"], pending["out"]) + ((pending["lp"],) if top_n >= 0 else ()))
                         pending = None
                     else:
                         free = next((i for i, s in enumerate(slots) if s is None), None)
@@ -448,16 +523,19 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                 rows = bucket(top)
                 engine.decode(1, batch=rows)
                 tokens = engine.read_pending(rows)
+                records = engine.read_pending_logprobs(rows) if top_n >= 0 else None
                 if on_step is not None:
                     on_step(sum(s is not None for s in slots))
                 for i, req in enumerate(slots):
                     if req is None:
                         continue
                     req["out"].append(tokens[i])
+                    if records is not None:
+                        req["lp"].append(records[i])
                     if len(req["out"]) >= req["limit"] or tokens[i] == eos_token_id:
                         engine.release(i)
                         live_slots.discard(i)
-                        finished.append((req["idx"], req["out"]))
+                        finished.append((req["idx"], req["out"]) + ((req["lp"],) if top_n >= 0 else ()))
                         slots[i] = None
     finally:
         for slot in list(live_slots):
