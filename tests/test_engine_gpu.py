@@ -646,6 +646,34 @@ def test_packed_prefill_of_several_slots(ckpt, err):
         eng.close()
 
 
+@pytest.mark.parametrize("n_prompt", [5, 37, 200])
+def test_one_sequence_packed_prefill_equals_solo_prefill(ckpt, n_prompt):
+    """A packed prefill of one sequence runs the same layer pass as a solo prefill: the last-row logits, the pending token and
+    the logits of the following decode step must be bit-identical on the same engine."""
+    from tiny_llm_hip.engine import DecodeEngine
+
+    prompt = prompt_ids(n_prompt, seed=900 + n_prompt)
+    eng = DecodeEngine(ckpt[1], page_size=16, num_pages=64, max_batch=1, max_prefill_rows=256)
+    try:
+        runs = []
+        for packed in (False, True):
+            eng.begin(0)
+            if packed:
+                eng.prefill_packed([(0, prompt, True)])
+            else:
+                eng.prefill(0, prompt)
+            first, pending = eng.logits(1), eng.read_pending(1)
+            eng.decode(1, batch=1, use_graph=False)
+            runs.append((first, pending, eng.logits(1)))
+            eng.release(0)
+        (solo_first, solo_pending, solo_next), (packed_first, packed_pending, packed_next) = runs
+        assert torch.equal(solo_first, packed_first), "last-row logits of the prefill"
+        assert solo_pending == packed_pending, "pending token after the prefill"
+        assert torch.equal(solo_next, packed_next), "logits of the decode step after the prefill"
+    finally:
+        eng.close()
+
+
 NORM_CFG = dict(hidden_size=2560, num_hidden_layers=3, num_attention_heads=4, num_key_value_heads=2, head_dim=128, intermediate_size=1024,
                 vocab_size=2048, rope_theta=1000000, rms_norm_eps=1e-6, max_position_embeddings=4096, tie_word_embeddings=True)
 

@@ -252,6 +252,22 @@ struct ProfCtx {
     prof_t *pairs = nullptr;  // [n][2] reduced (start, end) per launch
     std::vector<int> kinds;
     int cap = 0;
+    ProfCtx() = default;
+    ProfCtx(const ProfCtx &) = delete;
+    ~ProfCtx() {
+        if (buf) (void)hipFree(buf);
+        if (pairs) (void)hipFree(pairs);
+    }
+    // room for one eagerly launched step over `batch` rows (tl_engine_profile_step, tl_engine_check_step): the largest grid of the
+    // step -- the lm_head GEMV (4 rows per workgroup at worst) or the attention grid -- and up to 11 launches per layer at 5 .. 64 rows
+    // (four skinny matmuls + reductions, attention, merge, norms); the stamps start zeroed, stream-ordered
+    bool alloc(const tl_engine *e, int batch) {
+        const tl_engine_config &c = e->cfg;
+        const size_t buf_bytes = (size_t)(std::max(c.vocab_size / 4 + 64, 64 * 4 * c.num_kv_heads * batch) + 1024) * 2 * sizeof(prof_t);
+        cap = c.num_layers * 12 + 8;
+        return hipMalloc((void **)&buf, buf_bytes) == hipSuccess && hipMalloc((void **)&pairs, (size_t)cap * 2 * sizeof(prof_t)) == hipSuccess &&
+               hipMemsetAsync(buf, 0, buf_bytes, e->stream) == hipSuccess;
+    }
 };
 
 static void prof_after(tl_engine *e, ProfCtx *pc, int kind, int n_wg);
@@ -527,6 +543,38 @@ static bool step_logprobs(const tl_engine *e, int batch) {
     for (int b = 0; b < batch; ++b)
         if (step_logprobs_slot(e, b)) return true;
     return false;
+}
+
+// StepEndArgs over the engine's state: rows of `logits` for slots slot0.., the context advance (1: decode; 0: a prefill sets it on the host
+// side) and the next embedding rows into x; tile maxima, sums of squares and stamps where the step has them
+static StepEndArgs step_end_args(const tl_engine *e, const uint16_t *logits, int slot0, int advance, uint16_t *x, const f32x2 *tile_max = nullptr,
+                                 int tiles = 0, float *ss_out = nullptr, prof_t *prof = nullptr) {
+    const tl_engine_config &c = e->cfg;
+    StepEndArgs s{};
+    s.logits = logits;
+    s.vocab = c.vocab_size;
+    s.slot0 = slot0;
+    s.tokens = e->tokens;
+    s.context_lens = e->context_lens;
+    s.live = e->live;
+    s.produced = e->produced;
+    s.ring = e->ring;
+    s.ring_cap = e->ring_cap;
+    s.advance = advance;
+    s.emb_w = e->embed.weight_dev;
+    s.emb_s = (const uint16_t *)e->embed.scales_dev;
+    s.emb_b = (const uint16_t *)e->embed.biases_dev;
+    s.x = x;
+    s.hidden = c.hidden_size;
+    s.rope_table = e->rope_table;
+    s.rope_cur = e->rope_cur;
+    s.rope_positions = e->rope_positions;
+    s.rope_half = c.head_dim / 2;
+    s.ss_out = ss_out;
+    s.prof = prof;
+    s.tile_max = tile_max;
+    s.tiles = tiles;
+    return s;
 }
 
 // step end of a decode step / a prefill's last row: greedy kernel, its sampling twin when the plan samples, or the logprob twin
@@ -1391,29 +1439,9 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, ProfCtx *pc = nul
                                             x_ss ? ssx_cur : nullptr, nullptr, nullptr, nullptr, x_ss);
     e->want_tile_max = false;
     TL_TRY(head_rc);
-    StepEndArgs s{};
-    if (e->tile_max_rows == batch) s.tile_max = e->lm_tile_max, s.tiles = e->head().rows / 16;
-    s.logits = e->logits;
-    s.vocab = c.vocab_size;
-    s.slot0 = 0;
-    s.tokens = e->tokens;
-    s.context_lens = e->context_lens;
-    s.live = e->live;
-    s.produced = e->produced;
-    s.ring = e->ring;
-    s.ring_cap = e->ring_cap;
-    s.advance = 1;
-    s.emb_w = e->embed.weight_dev;
-    s.emb_s = (const uint16_t *)e->embed.scales_dev;
-    s.emb_b = (const uint16_t *)e->embed.biases_dev;
-    s.x = e->x;
-    s.hidden = c.hidden_size;
-    s.rope_table = e->rope_table;
-    s.rope_cur = e->rope_cur;
-    s.rope_positions = e->rope_positions;
-    s.rope_half = c.head_dim / 2;
-    s.ss_out = e->ss_x;
-    s.prof = pc ? pc->buf : nullptr;
+    const bool tile_max = e->tile_max_rows == batch;
+    const StepEndArgs s = step_end_args(e, e->logits, 0, 1, e->x, tile_max ? e->lm_tile_max : nullptr, tile_max ? e->head().rows / 16 : 0, e->ss_x,
+                                        pc ? pc->buf : nullptr);
     launch_step_end(e, s, batch, step_samples(e, batch), step_logprobs(e, batch));
     if (pc) prof_after(e, pc, 7, batch);
     TL_CHECK_LAUNCH("engine step end");
@@ -1628,54 +1656,40 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     const size_t o_ws = carve(e->attn_ws_bytes);
     e->arena_bytes = off;
 
-    auto cleanup_fail = [&](const std::string &msg) {
-        if (e->arena) (void)hipFree(e->arena);
-        if (e->smp_mem) (void)hipFree(e->smp_mem);
-        if (e->kpool) (void)hipFree(e->kpool);
-        if (e->vpool) (void)hipFree(e->vpool);
-        if (e->kscale_pool) (void)hipFree(e->kscale_pool);
-        if (e->vscale_pool) (void)hipFree(e->vscale_pool);
-        if (e->rope_table) (void)hipFree(e->rope_table);
-        if (e->rope_cur) (void)hipFree(e->rope_cur);
-        if (e->splitk_ws) (void)hipFree(e->splitk_ws);
-        for (auto &kv : e->tiled) {
-            (void)hipFree(kv.second.wt);
-            (void)hipFree(kv.second.sbt);
-        }
-        for (auto &kv : e->bf16w) (void)hipFree(kv.second);
-        if (e->owns_stream) (void)hipStreamDestroy(e->stream);
-        delete e;
+    // from here on a failure tears the partly built engine down like any other: tl_engine_destroy frees whatever it holds
+    auto destroy_fail = [&](const std::string &msg) {
+        tl_engine_destroy(e);
         return fail(TL_ERR_HIP, msg);
     };
-    if (hipMalloc((void **)&e->arena, e->arena_bytes) != hipSuccess) return cleanup_fail("engine_create: hipMalloc(arena) failed");
+    if (hipMalloc((void **)&e->arena, e->arena_bytes) != hipSuccess) return destroy_fail("engine_create: hipMalloc(arena) failed");
     // sampling parameters per slot (all zero: greedy): seeds first for their 8-byte alignment
-    if (hipMalloc((void **)&e->smp_mem, (size_t)c.max_batch * 20) != hipSuccess) return cleanup_fail("engine_create: hipMalloc(sampling) failed");
+    if (hipMalloc((void **)&e->smp_mem, (size_t)c.max_batch * 20) != hipSuccess) return destroy_fail("engine_create: hipMalloc(sampling) failed");
     e->smp_seed = (uint64_t *)e->smp_mem;
     e->smp_temp = (float *)(e->smp_mem + (size_t)c.max_batch * 8);
     e->smp_topk = (int32_t *)(e->smp_mem + (size_t)c.max_batch * 12);
     e->smp_topp = (float *)(e->smp_mem + (size_t)c.max_batch * 16);
-    if (hipMemsetAsync(e->smp_mem, 0, (size_t)c.max_batch * 20, e->stream) != hipSuccess) return cleanup_fail("engine_create: memset failed");
+    if (hipMemsetAsync(e->smp_mem, 0, (size_t)c.max_batch * 20, e->stream) != hipSuccess) return destroy_fail("engine_create: memset failed");
     e->layer_pool_elems = (size_t)c.num_pages * c.num_kv_heads * c.page_size * c.head_dim;
     const size_t pool_bytes = e->layer_pool_elems * e->kv_elem_bytes() * c.num_layers;
-    if (hipMalloc((void **)&e->kpool, pool_bytes) != hipSuccess) return cleanup_fail("engine_create: hipMalloc(key pages) failed");
-    if (hipMalloc((void **)&e->vpool, pool_bytes) != hipSuccess) return cleanup_fail("engine_create: hipMalloc(value pages) failed");
+    if (hipMalloc((void **)&e->kpool, pool_bytes) != hipSuccess) return destroy_fail("engine_create: hipMalloc(key pages) failed");
+    if (hipMalloc((void **)&e->vpool, pool_bytes) != hipSuccess) return destroy_fail("engine_create: hipMalloc(value pages) failed");
     e->kv_bytes = 2 * pool_bytes;
     if (kv_format == TL_KV_FP8_E4M3) {
         // one float32 scale per (page, kv head, slot) row; zero like the codes (a zero scale times a zero code is the zero the bf16 pool holds)
         e->layer_scale_elems = (size_t)c.num_pages * c.num_kv_heads * c.page_size;
         const size_t scale_bytes = e->layer_scale_elems * 4 * c.num_layers;
-        if (hipMalloc((void **)&e->kscale_pool, scale_bytes) != hipSuccess) return cleanup_fail("engine_create: hipMalloc(key scales) failed");
-        if (hipMalloc((void **)&e->vscale_pool, scale_bytes) != hipSuccess) return cleanup_fail("engine_create: hipMalloc(value scales) failed");
+        if (hipMalloc((void **)&e->kscale_pool, scale_bytes) != hipSuccess) return destroy_fail("engine_create: hipMalloc(key scales) failed");
+        if (hipMalloc((void **)&e->vscale_pool, scale_bytes) != hipSuccess) return destroy_fail("engine_create: hipMalloc(value scales) failed");
         if (hipMemsetAsync(e->kscale_pool, 0, scale_bytes, e->stream) != hipSuccess ||
             hipMemsetAsync(e->vscale_pool, 0, scale_bytes, e->stream) != hipSuccess)
-            return cleanup_fail("engine_create: memset(KV scales) failed");
+            return destroy_fail("engine_create: memset(KV scales) failed");
         e->kv_bytes += 2 * scale_bytes;
     }
     // Masked (out-of-context) token slots are still loaded and multiplied by a zero weight in the decode kernel,
     // so the pools must never hold NaN/Inf bit patterns: start from zeros (kernels only ever write finite values).
     if (hipMemsetAsync(e->kpool, 0, pool_bytes, e->stream) != hipSuccess ||
         hipMemsetAsync(e->vpool, 0, pool_bytes, e->stream) != hipSuccess)
-        return cleanup_fail("engine_create: memset(KV pools) failed");
+        return destroy_fail("engine_create: memset(KV pools) failed");
 
     char *A = e->arena;
     e->block_table = (int32_t *)(A + o_bt);
@@ -1753,10 +1767,8 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
                 }
                 const size_t per_layer = 2 * b_x + 2 * b_xf + b_qkv + b_attn + b_act + 2 * b_ss + b_ws + b_pl[0] + b_pl[1];
                 if (hipMalloc((void **)&e->layer_act_mem, per_layer * c.num_layers) != hipSuccess ||
-                    hipMemsetAsync(e->layer_act_mem, 0, per_layer * c.num_layers, e->stream) != hipSuccess) {
-                    tl_engine_destroy(e);
-                    return fail(TL_ERR_HIP, "engine_create: hipMalloc(per-layer decode activations) failed");
-                }
+                    hipMemsetAsync(e->layer_act_mem, 0, per_layer * c.num_layers, e->stream) != hipSuccess)
+                    return destroy_fail("engine_create: hipMalloc(per-layer decode activations) failed");
                 e->layer_act.resize(c.num_layers);
                 for (int l = 0; l < c.num_layers; ++l) {
                     char *m = e->layer_act_mem + (size_t)l * per_layer;
@@ -1783,10 +1795,10 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     }
 
     // state words: zero everything up to the activations, then the block table to -1
-    if (hipMemsetAsync(e->arena, 0, o_x, e->stream) != hipSuccess) return cleanup_fail("engine_create: memset failed");
+    if (hipMemsetAsync(e->arena, 0, o_x, e->stream) != hipSuccess) return destroy_fail("engine_create: memset failed");
     const int bt_n = c.max_batch * c.max_pages_per_seq;
     hipLaunchKernelGGL(fill_i32_kernel, dim3(ceil_div(bt_n, 256)), dim3(256), 0, e->stream, e->block_table, -1, bt_n);
-    if (hipGetLastError() != hipSuccess) return cleanup_fail("engine_create: block-table init failed");
+    if (hipGetLastError() != hipSuccess) return destroy_fail("engine_create: block-table init failed");
 
     // RoPE table for every position a sequence can reach
     {
@@ -1794,13 +1806,13 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
         e->rope_positions = (int)max_pos;
         const int half = c.head_dim / 2;
         if (hipMalloc((void **)&e->rope_table, (size_t)max_pos * half * sizeof(float2)) != hipSuccess)
-            return cleanup_fail("engine_create: hipMalloc(rope table) failed");
+            return destroy_fail("engine_create: hipMalloc(rope table) failed");
         hipLaunchKernelGGL(rope_table_kernel, dim3(ceil_div(max_pos * half, 256)), dim3(256), 0, e->stream, e->rope_table,
                            (int)max_pos, half, c.rope_theta);
-        if (hipGetLastError() != hipSuccess) return cleanup_fail("engine_create: rope table kernel failed");
+        if (hipGetLastError() != hipSuccess) return destroy_fail("engine_create: rope table kernel failed");
         if (hipMalloc((void **)&e->rope_cur, (size_t)c.max_batch * half * sizeof(float2)) != hipSuccess ||
             hipMemsetAsync(e->rope_cur, 0, (size_t)c.max_batch * half * sizeof(float2), e->stream) != hipSuccess)
-            return cleanup_fail("engine_create: hipMalloc(rope state) failed");
+            return destroy_fail("engine_create: hipMalloc(rope state) failed");
     }
 
     // decode-path weight copies in the tiled MFMA layout
@@ -1830,7 +1842,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
             if (l.wgu.weight_dev) ok = ok && add_tiled(l.wgu) && add_tiled(l.wdown);
         }
         ok = ok && add_tiled(e->head());
-        if (!ok) return cleanup_fail("engine_create: hipMalloc(tiled weights) failed");
+        if (!ok) return destroy_fail("engine_create: hipMalloc(tiled weights) failed");
     }
     if (c.max_prefill_rows >= GEMM8_MIN_ROWS) {  // the caller asked for chunks the plain bf16 GEMM takes: expand the layer matrices once
         auto add_bf16 = [&](const tl_w4 &w) -> bool {
@@ -1851,11 +1863,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
             ok = ok && add_bf16(l.wqkv) && add_bf16(l.wo);
             if (l.wgu.weight_dev) ok = ok && add_bf16(l.wgu) && add_bf16(l.wdown);
         }
-        if (!ok) {
-            for (auto &kv : e->bf16w) (void)hipFree(kv.second);
-            e->bf16w.clear();
-            return cleanup_fail("engine_create: hipMalloc(bf16 weights for the prefill GEMM) failed");
-        }
+        if (!ok) return destroy_fail("engine_create: hipMalloc(bf16 weights for the prefill GEMM) failed");
     }
 
     {
@@ -1880,7 +1888,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
                 need = std::max(need, tl_quantized_matmul_workspace_bytes(M, w->cols, w->rows, TL_BF16, 1, 1));
         }
         if (need > 0) {
-            if (hipMalloc(&e->splitk_ws, need) != hipSuccess) return cleanup_fail("engine_create: hipMalloc(matmul workspace) failed");
+            if (hipMalloc(&e->splitk_ws, need) != hipSuccess) return destroy_fail("engine_create: hipMalloc(matmul workspace) failed");
             e->splitk_ws_bytes = need;
         }
     }
@@ -2284,9 +2292,6 @@ extern "C" int tl_logprob_rows(const void *logits_dev, int rows, int vocab, cons
     return TL_OK;
 }
 
-// logits_mode: 0 = none, 1 = last row (greedy id recorded as the slot's pending token), 2 = every row (n <= 8: greedy ids
-// land in e->verify_ids, nothing is recorded; speculative verification), 3 = every row scored (tl_engine_score: the log-probability
-// of e->score_ids[i] and the greedy id of every row into e->score_lp / e->score_argmax, nothing recorded, e->logits untouched)
 // the paged attention operator over layer l's pages, by the engine's page format
 static int engine_paged_attention(tl_engine *e, int l, const uint16_t *q_t, const int32_t *block_row, const int32_t *ctx_dev, uint16_t *attn_t,
                                   int n, int ctx_hint) {
@@ -2312,74 +2317,109 @@ static void launch_qkv_post(tl_engine *e, int l, QkvPostArgs &q, int n) {
     }
 }
 
+// One sequence's chunk in a prefill pass: its slot, the position of its first token, its first row among the pass's rows, its length
+struct PrefillSeq {
+    int slot, start, row0, len;
+};
+
+// The multi-token pass over the `total` rows of the chunks in `seqs`, side by side: their pages reserved (the caller has checked
+// whatever could fail part way) and their tokens embedded, then every layer -- the projections once over all rows, RoPE / KV append, the
+// paged FlashAttention and the head transpose per sequence (each has its own block-table row, start position and causal mask) -- and
+// the slots' context lengths advanced.  The last layer's rows stay in x.  `packed` names the caller in the errors.
+static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const int32_t *tokens, int total, bool packed) {
+    const tl_engine_config &c = e->cfg;
+    std::vector<std::pair<int32_t *, int32_t>> pk;
+    for (int i = 0; i < n_seqs; ++i) {
+        TL_TRY(reserve_locked(e, seqs[i].slot, seqs[i].start + seqs[i].len, pk));
+        pk.emplace_back(e->scratch_ctx + i, seqs[i].start + seqs[i].len);
+    }
+    e->stats.pages_free = (int)e->free_pages.size();
+    TL_TRY(poke(e, pk));
+    TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens, (size_t)total * 4, hipMemcpyHostToDevice, e->stream));
+
+    const int D = c.head_dim, Hq = c.num_heads, Hkv = c.num_kv_heads;
+    TL_TRY(tl_quantized_embedding(e->prefill_tokens, 0, e->embed.scales_dev, e->embed.biases_dev, e->embed.weight_dev, e->x,
+                                  total, c.hidden_size, c.vocab_size, 128, 4, TL_BF16, e->stream));
+    for (int i = 0; i < n_seqs; ++i)
+        TL_REQUIRE(tl_paged_attention_workspace_bytes(Hq, seqs[i].len, D, c.page_size, c.max_pages_per_seq, Hq, Hkv, seqs[i].start + seqs[i].len) <=
+                       e->attn_ws_bytes, std::string(packed ? "engine_prefill_packed" : "engine_prefill") + ": attention workspace too small");
+    bool x_normed = false;  // the previous layer's w_down reduction left this layer's normalised rows in xn (engine_gemm)
+    for (int l = 0; l < c.num_layers; ++l) {
+        const tl_layer_weights &w = e->layers[l];
+        if (!x_normed) TL_TRY(tl_rms_norm(e->x, w.input_norm_dev, e->xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
+        x_normed = false;
+        TL_TRY(engine_gemm(e, w.wqkv, e->xn, e->qkv, total, EPI_STORE, nullptr));
+        for (int i = 0; i < n_seqs; ++i) {
+            const int n = seqs[i].len, start = seqs[i].start;
+            const int32_t *block_row = e->block_table + (size_t)seqs[i].slot * c.max_pages_per_seq;
+            uint16_t *q_t = e->q_t + (size_t)seqs[i].row0 * Hq * D;  // this sequence's [Hq][n][D] block
+            uint16_t *attn_t = e->attn_t + (size_t)seqs[i].row0 * Hq * D;
+            QkvPostArgs q{};
+            q.qkv = e->qkv + (size_t)seqs[i].row0 * (Hq + 2 * Hkv) * D;
+            q.q_norm_w = (const uint16_t *)w.q_norm_dev;
+            q.k_norm_w = (const uint16_t *)w.k_norm_dev;
+            q.q_t = q_t;
+            q.key_pages = e->layer_k(l);
+            q.value_pages = e->layer_v(l);
+            q.block_row = block_row;
+            q.T = n;
+            q.start = start;
+            q.page_size = c.page_size;
+            q.max_pages = c.max_pages_per_seq;
+            q.num_heads = Hq;
+            q.num_kv_heads = Hkv;
+            q.eps = c.rms_norm_eps;
+            q.rope_base = c.rope_theta;
+            launch_qkv_post(e, l, q, n);
+            TL_CHECK_LAUNCH("engine qkv_post");
+            TL_TRY(engine_paged_attention(e, l, q_t, block_row, e->scratch_ctx + i, attn_t, n, start + n));
+            const long items = (long)Hq * n * (D / 8);
+            hipLaunchKernelGGL(heads_to_rows_kernel, dim3(ceil_div(items, 256)), dim3(256), 0, e->stream, attn_t,
+                               e->attn + (size_t)seqs[i].row0 * Hq * D, Hq, n, D);
+        }
+        bool h_normed = false;
+        TL_TRY(engine_gemm(e, w.wo, e->attn, e->h, total, EPI_RESIDUAL, e->x, w.post_norm_dev, e->xn, &h_normed));
+        if (!h_normed) TL_TRY(tl_rms_norm(e->h, w.post_norm_dev, e->xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
+        if (e->is_moe(l)) {
+            TL_TRY(engine_moe_mlp(e, l, e->xn, e->h, e->x, total, nullptr));
+        } else {
+            TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
+            TL_TRY(engine_gemm(e, w.wgu, e->xn, e->act, total, EPI_SWIGLU, nullptr));
+            TL_TRY(engine_gemm(e, w.wdown, e->act, e->x, total, EPI_RESIDUAL, e->h, l + 1 < c.num_layers ? e->layers[l + 1].input_norm_dev : nullptr, e->xn,
+                               &x_normed));
+        }
+        TL_CHECK_LAUNCH(packed ? "engine packed prefill layer" : "engine prefill layer");
+    }
+    for (int i = 0; i < n_seqs; ++i) {
+        e->slot_ctx[seqs[i].slot] = seqs[i].start + seqs[i].len;
+        pk.emplace_back(e->context_lens + seqs[i].slot, seqs[i].start + seqs[i].len);
+    }
+    TL_TRY(poke(e, pk));
+    e->stats.prefill_tokens += total;
+    return TL_OK;
+}
+
+// The first token of a prefilled slot from its logits row: the step end (advance 0: the prefill has set the context length), after which
+// the slot has produced one id.  Its embedding row goes to scratch: the prefill activations in x must stay intact; decode re-embeds from tokens
+static int prefill_first_token(tl_engine *e, int slot, const uint16_t *logits, const char *what) {
+    launch_step_end(e, step_end_args(e, logits, slot, 0, e->h), 1, e->smp[slot].samples(), step_logprobs_slot(e, slot));
+    TL_CHECK_LAUNCH(what);
+    e->slot_produced[slot] += 1;
+    return TL_OK;
+}
+
+// logits_mode: 0 = none, 1 = last row (greedy id recorded as the slot's pending token), 2 = every row (n <= 8: greedy ids
+// land in e->verify_ids, nothing is recorded; speculative verification), 3 = every row scored (tl_engine_score: the log-probability
+// of e->score_ids[i] and the greedy id of every row into e->score_lp / e->score_argmax, nothing recorded, e->logits untouched)
 static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, int logits_mode) {
-    const int want_logits = logits_mode == 1;
     TL_TRY(slot_check(e, slot, true));
     TL_REQUIRE(tokens && n > 0, "engine_prefill: need at least one token");
     TL_REQUIRE(n <= e->cfg.max_prefill_rows, "engine_prefill: chunk exceeds max_prefill_rows");
     const tl_engine_config &c = e->cfg;
     TL_REQUIRE(n <= 8 || c.head_dim == 128, "engine_prefill: chunks longer than 8 tokens need head_dim 128 (bf16 FlashAttention)");
     for (int i = 0; i < n; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < c.vocab_size, "engine_prefill: token id out of range");
-    const int start = e->slot_ctx[slot];
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    TL_TRY(reserve_locked(e, slot, start + n, pk));
-    e->stats.pages_free = (int)e->free_pages.size();
-    pk.emplace_back(e->scratch_ctx, start + n);
-    TL_TRY(poke(e, pk));
-    TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-
-    const int D = c.head_dim, Hq = c.num_heads, Hkv = c.num_kv_heads;
-    const int32_t *block_row = e->block_table + (size_t)slot * c.max_pages_per_seq;
-    TL_TRY(tl_quantized_embedding(e->prefill_tokens, 0, e->embed.scales_dev, e->embed.biases_dev, e->embed.weight_dev, e->x,
-                                  n, c.hidden_size, c.vocab_size, 128, 4, TL_BF16, e->stream));
-    const size_t attn_ws_need = tl_paged_attention_workspace_bytes(Hq, n, D, c.page_size, c.max_pages_per_seq, Hq, Hkv, start + n);
-    TL_REQUIRE(attn_ws_need <= e->attn_ws_bytes, "engine_prefill: attention workspace too small");
-    bool x_normed = false;  // the previous layer's w_down reduction left this layer's normalised rows in xn (engine_gemm)
-    for (int l = 0; l < c.num_layers; ++l) {
-        const tl_layer_weights &w = e->layers[l];
-        if (!x_normed) TL_TRY(tl_rms_norm(e->x, w.input_norm_dev, e->xn, n, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
-        x_normed = false;
-        TL_TRY(engine_gemm(e, w.wqkv, e->xn, e->qkv, n, EPI_STORE, nullptr));
-        QkvPostArgs q{};
-        q.qkv = e->qkv;
-        q.q_norm_w = (const uint16_t *)w.q_norm_dev;
-        q.k_norm_w = (const uint16_t *)w.k_norm_dev;
-        q.q_t = e->q_t;
-        q.key_pages = e->layer_k(l);
-        q.value_pages = e->layer_v(l);
-        q.block_row = block_row;
-        q.T = n;
-        q.start = start;
-        q.page_size = c.page_size;
-        q.max_pages = c.max_pages_per_seq;
-        q.num_heads = Hq;
-        q.num_kv_heads = Hkv;
-        q.eps = c.rms_norm_eps;
-        q.rope_base = c.rope_theta;
-        launch_qkv_post(e, l, q, n);
-        TL_CHECK_LAUNCH("engine qkv_post");
-        TL_TRY(engine_paged_attention(e, l, e->q_t, block_row, e->scratch_ctx, e->attn_t, n, start + n));
-        {
-            const long total = (long)Hq * n * (D / 8);
-            hipLaunchKernelGGL(heads_to_rows_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, e->stream, e->attn_t, e->attn, Hq, n, D);
-        }
-        bool h_normed = false;
-        TL_TRY(engine_gemm(e, w.wo, e->attn, e->h, n, EPI_RESIDUAL, e->x, w.post_norm_dev, e->xn, &h_normed));
-        if (!h_normed) TL_TRY(tl_rms_norm(e->h, w.post_norm_dev, e->xn, n, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
-        if (e->is_moe(l)) {
-            TL_TRY(engine_moe_mlp(e, l, e->xn, e->h, e->x, n, nullptr));
-        } else {
-            TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
-            TL_TRY(engine_gemm(e, w.wgu, e->xn, e->act, n, EPI_SWIGLU, nullptr));
-            TL_TRY(engine_gemm(e, w.wdown, e->act, e->x, n, EPI_RESIDUAL, e->h, l + 1 < c.num_layers ? e->layers[l + 1].input_norm_dev : nullptr, e->xn,
-                               &x_normed));
-        }
-        TL_CHECK_LAUNCH("engine prefill layer");
-    }
-    e->slot_ctx[slot] = start + n;
-    pk.emplace_back(e->context_lens + slot, start + n);
-    TL_TRY(poke(e, pk));
-    e->stats.prefill_tokens += n;
+    const PrefillSeq seq{slot, e->slot_ctx[slot], 0, n};
+    TL_TRY(prefill_pass(e, &seq, 1, tokens, n, false));
     if (logits_mode == 3) {
         // the final RMSNorm over the chunk's rows, then the lm_head through the W4 GEMM a block of rows at a time into the scoring
         // scratch, each block followed by the logprob routine in gather mode
@@ -2398,41 +2438,18 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
         hipLaunchKernelGGL(argmax_rows_kernel, dim3(n), dim3(1024), 0, e->stream, e->logits, c.vocab_size, e->verify_ids);
         TL_CHECK_LAUNCH("engine verify argmax");
     }
-    if (want_logits) {
+    if (logits_mode == 1) {
         // logits_to_keep = 1 (reference qwen3_week3.py:331-336): last row only
         const uint16_t *last = e->x + (size_t)(n - 1) * c.hidden_size;
         TL_TRY(engine_qmv(e, e->head(), last, e->logits, 1, PRO_RMSNORM, EPI_STORE, e->final_norm, nullptr));
         e->logits_rows = 1;
-        StepEndArgs s{};
-        s.logits = e->logits;
-        s.vocab = c.vocab_size;
-        s.slot0 = slot;
-        s.tokens = e->tokens;
-        s.context_lens = e->context_lens;
-        s.live = e->live;
-        s.produced = e->produced;
-        s.ring = e->ring;
-        s.ring_cap = e->ring_cap;
-        s.advance = 0;
-        s.emb_w = e->embed.weight_dev;
-        s.emb_s = (const uint16_t *)e->embed.scales_dev;
-        s.emb_b = (const uint16_t *)e->embed.biases_dev;
-        s.x = e->h;  // scratch: the prefill activations in x[0..n) must stay intact; decode re-embeds from tokens
-        s.hidden = c.hidden_size;
-        s.rope_table = e->rope_table;
-        s.rope_cur = e->rope_cur;
-        s.rope_positions = e->rope_positions;
-        s.rope_half = c.head_dim / 2;
-        launch_step_end(e, s, 1, e->smp[slot].samples(), step_logprobs_slot(e, slot));
-        TL_CHECK_LAUNCH("engine prefill argmax");
-        e->slot_produced[slot] += 1;
+        TL_TRY(prefill_first_token(e, slot, e->logits, "engine prefill argmax"));
     }
     return TL_OK;
 }
 
-// Several sequences' chunks in ONE pass of the multi-token path.  The projections (97 % of the prefill FLOPs) run once over the
-// concatenated rows -- a 2,048-row GEMM instead of several 300-row ones -- while RoPE / KV append, the paged FlashAttention
-// and the head transpose stay per sequence (each has its own block-table row, start position and causal mask).
+// Several sequences' chunks in ONE prefill pass: the projections (97 % of the prefill FLOPs) run once over the concatenated rows -- a
+// 2,048-row GEMM instead of several 300-row ones.
 static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, const int *want_logits) {
     const tl_engine_config &c = e->cfg;
     TL_REQUIRE(e && slots && tokens && lens && want_logits, "engine_prefill_packed: null argument");
@@ -2458,115 +2475,28 @@ static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const
     TL_REQUIRE(extra_pages <= e->free_pages.size(), "engine: KV page pool exhausted");  // checked before anything is mutated
     for (int i = 0; i < total; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < c.vocab_size, "engine_prefill_packed: token id out of range");
 
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    std::vector<int> start(n_seqs), row0(n_seqs);
+    std::vector<PrefillSeq> seqs(n_seqs);
     int rows = 0;
     for (int i = 0; i < n_seqs; ++i) {
-        start[i] = e->slot_ctx[slots[i]];
-        row0[i] = rows;
+        seqs[i] = {slots[i], e->slot_ctx[slots[i]], rows, lens[i]};
         rows += lens[i];
-        TL_TRY(reserve_locked(e, slots[i], start[i] + lens[i], pk));  // cannot fail after the checks above
-        pk.emplace_back(e->scratch_ctx + i, start[i] + lens[i]);
     }
-    e->stats.pages_free = (int)e->free_pages.size();
-    TL_TRY(poke(e, pk));
-    pk.clear();
-    TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens, (size_t)total * 4, hipMemcpyHostToDevice, e->stream));
-
-    const int D = c.head_dim, Hq = c.num_heads, Hkv = c.num_kv_heads;
-    TL_TRY(tl_quantized_embedding(e->prefill_tokens, 0, e->embed.scales_dev, e->embed.biases_dev, e->embed.weight_dev, e->x,
-                                  total, c.hidden_size, c.vocab_size, 128, 4, TL_BF16, e->stream));
-    for (int i = 0; i < n_seqs; ++i)
-        TL_REQUIRE(tl_paged_attention_workspace_bytes(Hq, lens[i], D, c.page_size, c.max_pages_per_seq, Hq, Hkv, start[i] + lens[i]) <=
-                       e->attn_ws_bytes, "engine_prefill_packed: attention workspace too small");
-    bool x_normed = false;  // the previous layer's w_down reduction left this layer's normalised rows in xn (engine_gemm)
-    for (int l = 0; l < c.num_layers; ++l) {
-        const tl_layer_weights &w = e->layers[l];
-        if (!x_normed) TL_TRY(tl_rms_norm(e->x, w.input_norm_dev, e->xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
-        x_normed = false;
-        TL_TRY(engine_gemm(e, w.wqkv, e->xn, e->qkv, total, EPI_STORE, nullptr));
-        for (int i = 0; i < n_seqs; ++i) {
-            const int n = lens[i];
-            const int32_t *block_row = e->block_table + (size_t)slots[i] * c.max_pages_per_seq;
-            uint16_t *q_t = e->q_t + (size_t)row0[i] * Hq * D;        // this sequence's [Hq][n][D] block
-            uint16_t *attn_t = e->attn_t + (size_t)row0[i] * Hq * D;
-            QkvPostArgs q{};
-            q.qkv = e->qkv + (size_t)row0[i] * (Hq + 2 * Hkv) * D;
-            q.q_norm_w = (const uint16_t *)w.q_norm_dev;
-            q.k_norm_w = (const uint16_t *)w.k_norm_dev;
-            q.q_t = q_t;
-            q.key_pages = e->layer_k(l);
-            q.value_pages = e->layer_v(l);
-            q.block_row = block_row;
-            q.T = n;
-            q.start = start[i];
-            q.page_size = c.page_size;
-            q.max_pages = c.max_pages_per_seq;
-            q.num_heads = Hq;
-            q.num_kv_heads = Hkv;
-            q.eps = c.rms_norm_eps;
-            q.rope_base = c.rope_theta;
-            launch_qkv_post(e, l, q, n);
-            TL_CHECK_LAUNCH("engine qkv_post");
-            TL_TRY(engine_paged_attention(e, l, q_t, block_row, e->scratch_ctx + i, attn_t, n, start[i] + n));
-            const long items = (long)Hq * n * (D / 8);
-            hipLaunchKernelGGL(heads_to_rows_kernel, dim3(ceil_div(items, 256)), dim3(256), 0, e->stream, attn_t,
-                               e->attn + (size_t)row0[i] * Hq * D, Hq, n, D);
-        }
-        bool h_normed = false;
-        TL_TRY(engine_gemm(e, w.wo, e->attn, e->h, total, EPI_RESIDUAL, e->x, w.post_norm_dev, e->xn, &h_normed));
-        if (!h_normed) TL_TRY(tl_rms_norm(e->h, w.post_norm_dev, e->xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
-        if (e->is_moe(l)) {
-            TL_TRY(engine_moe_mlp(e, l, e->xn, e->h, e->x, total, nullptr));
-        } else {
-            TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
-            TL_TRY(engine_gemm(e, w.wgu, e->xn, e->act, total, EPI_SWIGLU, nullptr));
-            TL_TRY(engine_gemm(e, w.wdown, e->act, e->x, total, EPI_RESIDUAL, e->h, l + 1 < c.num_layers ? e->layers[l + 1].input_norm_dev : nullptr, e->xn,
-                               &x_normed));
-        }
-        TL_CHECK_LAUNCH("engine packed prefill layer");
-    }
+    TL_TRY(prefill_pass(e, seqs.data(), n_seqs, tokens, total, true));
     int n_logits = 0;
     for (int i = 0; i < n_seqs; ++i) {
-        e->slot_ctx[slots[i]] = start[i] + lens[i];
-        pk.emplace_back(e->context_lens + slots[i], start[i] + lens[i]);
-        if (want_logits[i]) {  // last rows side by side in xn: one lm_head pass over them (logits_to_keep = 1, qwen3_week3.py:331-336)
-            TL_HIP(hipMemcpyAsync(e->xn + (size_t)n_logits * c.hidden_size, e->x + (size_t)(row0[i] + lens[i] - 1) * c.hidden_size,
-                                  (size_t)c.hidden_size * 2, hipMemcpyDeviceToDevice, e->stream));
-            ++n_logits;
-        }
+        if (!want_logits[i]) continue;
+        // last rows side by side in xn: one lm_head pass over them (logits_to_keep = 1, qwen3_week3.py:331-336)
+        TL_HIP(hipMemcpyAsync(e->xn + (size_t)n_logits * c.hidden_size, e->x + (size_t)(seqs[i].row0 + lens[i] - 1) * c.hidden_size,
+                              (size_t)c.hidden_size * 2, hipMemcpyDeviceToDevice, e->stream));
+        ++n_logits;
     }
-    TL_TRY(poke(e, pk));
-    e->stats.prefill_tokens += total;
     if (n_logits > 0) {
         TL_TRY(engine_qmv(e, e->head(), e->xn, e->logits, n_logits, PRO_RMSNORM, EPI_STORE, e->final_norm, nullptr));
         e->logits_rows = n_logits;
         int j = 0;
         for (int i = 0; i < n_seqs; ++i) {
             if (!want_logits[i]) continue;
-            StepEndArgs s{};
-            s.logits = e->logits + (size_t)j * c.vocab_size;
-            s.vocab = c.vocab_size;
-            s.slot0 = slots[i];
-            s.tokens = e->tokens;
-            s.context_lens = e->context_lens;
-            s.live = e->live;
-            s.produced = e->produced;
-            s.ring = e->ring;
-            s.ring_cap = e->ring_cap;
-            s.advance = 0;
-            s.emb_w = e->embed.weight_dev;
-            s.emb_s = (const uint16_t *)e->embed.scales_dev;
-            s.emb_b = (const uint16_t *)e->embed.biases_dev;
-            s.x = e->h;  // scratch, as in prefill_impl
-            s.hidden = c.hidden_size;
-            s.rope_table = e->rope_table;
-            s.rope_cur = e->rope_cur;
-            s.rope_positions = e->rope_positions;
-            s.rope_half = c.head_dim / 2;
-            launch_step_end(e, s, 1, e->smp[slots[i]].samples(), step_logprobs_slot(e, slots[i]));
-            TL_CHECK_LAUNCH("engine packed prefill argmax");
-            e->slot_produced[slots[i]] += 1;
+            TL_TRY(prefill_first_token(e, slots[i], e->logits + (size_t)j * c.vocab_size, "engine packed prefill argmax"));
             ++j;
         }
     }
@@ -2635,6 +2565,49 @@ static int aql_drain(tl_engine *e) {
     return TL_OK;
 }
 
+// ---- the parts of a decode step around enqueue_step (tl_engine_decode, tl_engine_profile_step, tl_engine_check_step)
+// input activations of slots [0, batch) from their pending token ids, with the RoPE factors and sums of squares of the first step
+static void launch_embed_slots(tl_engine *e, int batch) {
+    const tl_engine_config &c = e->cfg;
+    hipLaunchKernelGGL(embed_slots_kernel, dim3(batch), dim3(256), 0, e->stream, e->tokens, e->embed.weight_dev,
+                       (const uint16_t *)e->embed.scales_dev, (const uint16_t *)e->embed.biases_dev, e->x, c.hidden_size,
+                       c.vocab_size, e->context_lens, e->rope_table, e->rope_cur, e->rope_positions, c.head_dim / 2, e->ss_x);
+}
+
+// the pages of this step's token in every live slot of [0, batch), poked into the block table, and the step's split plan.  A caller with
+// steps in flight on the AQL queue passes `on_queue`: a new page id drains them first (the poke is a stream launch and must land between
+// the steps), and a failed reservation returns with the queue drained.
+static int prepare_step(tl_engine *e, int batch, SplitPlan *sp, bool *on_queue = nullptr) {
+    std::vector<std::pair<int32_t *, int32_t>> pk;
+    int max_ctx = 1;
+    const int rc = reserve_step_locked(e, batch, pk, &max_ctx);
+    if (rc != TL_OK) {
+        if (on_queue) (void)aql_drain(e);
+        return rc;
+    }
+    if (!pk.empty()) {
+        e->stats.pages_free = (int)e->free_pages.size();
+        if (on_queue && *on_queue) {
+            TL_TRY(aql_drain(e));
+            *on_queue = false;
+        }
+        TL_TRY(poke(e, pk));
+    }
+    *sp = pick_decode_splits(e, batch, max_ctx);
+    return TL_OK;
+}
+
+// the host mirrors after a step over slots [0, batch): every live slot holds one more token and has produced one more id
+static void step_done(tl_engine *e, int batch) {
+    for (int b = 0; b < batch; ++b) {
+        if (!e->slot_live[b]) continue;
+        e->slot_ctx[b] += 1;
+        e->slot_produced[b] += 1;
+    }
+    e->stats.decode_steps++;
+    e->logits_rows = batch;
+}
+
 extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_graph) {
     TL_REQUIRE(e, "engine_decode: null engine");
     TL_REQUIRE(batch > 0 && batch <= e->cfg.max_batch, "engine_decode: batch out of range");
@@ -2645,31 +2618,14 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
         TL_HIP(hipGetDevice(&dev_now));
         TL_REQUIRE(dev_now == e->device, "engine_decode: the current HIP device is not the device this engine was created on");
     }
-    const tl_engine_config &c = e->cfg;
     // input activations of the first step come from the pending token ids
-    hipLaunchKernelGGL(embed_slots_kernel, dim3(batch), dim3(256), 0, e->stream, e->tokens, e->embed.weight_dev,
-                       (const uint16_t *)e->embed.scales_dev, (const uint16_t *)e->embed.biases_dev, e->x, c.hidden_size,
-                       c.vocab_size, e->context_lens, e->rope_table, e->rope_cur, e->rope_positions, c.head_dim / 2, e->ss_x);
+    launch_embed_slots(e, batch);
     TL_CHECK_LAUNCH("engine embed");
-    std::vector<std::pair<int32_t *, int32_t>> pk;
     const bool samples = step_samples(e, batch), logprobs = step_logprobs(e, batch);
     bool on_queue = false;  // steps of this call are in flight on the AQL queue (the stream is idle and must stay so until they are drained)
     for (int s = 0; s < steps; ++s) {
-        int max_ctx = 1;
-        const int rrc = reserve_step_locked(e, batch, pk, &max_ctx);
-        if (rrc != TL_OK) {
-            (void)aql_drain(e);
-            return rrc;
-        }
-        if (!pk.empty()) {
-            e->stats.pages_free = (int)e->free_pages.size();
-            if (on_queue) {  // a page id changes: the poke is a stream launch and must land between the steps
-                TL_TRY(aql_drain(e));
-                on_queue = false;
-            }
-            TL_TRY(poke(e, pk));
-        }
-        const SplitPlan sp = pick_decode_splits(e, batch, max_ctx);
+        SplitPlan sp;
+        TL_TRY(prepare_step(e, batch, &sp, &on_queue));
         if (use_graph && e->warmed) {
             // bit 62: the step ends with the sampling twin of step_end_kernel, bit 61: with the logprob twin (both re-derived every call
             // from the slots' parameters)
@@ -2740,16 +2696,10 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
             TL_TRY(enqueue_step(e, batch, sp));
             e->warmed = true;
         }
-        for (int b = 0; b < batch; ++b) {
-            if (!e->slot_live[b]) continue;
-            e->slot_ctx[b] += 1;
-            e->slot_produced[b] += 1;
-        }
-        e->stats.decode_steps++;
+        step_done(e, batch);
     }
     // the queue is not the stream: what follows this call (reads, prefills, the next call's embedding gather) is stream-ordered
     if (on_queue) TL_TRY(aql_drain(e));
-    e->logits_rows = batch;
     return TL_OK;
 }
 
@@ -2801,63 +2751,32 @@ extern "C" size_t tl_engine_step_bytes(const tl_engine *e, int batch) {
 extern "C" int tl_engine_profile_step(tl_engine *e, int batch, tl_step_profile *out) {
     TL_REQUIRE(e && out, "engine_profile_step: null argument");
     TL_REQUIRE(batch > 0 && batch <= e->cfg.max_batch, "engine_profile_step: batch out of range");
-    const tl_engine_config &c = e->cfg;
     int rate_khz = 0;
     int dev = 0;
     TL_HIP(hipGetDevice(&dev));
     TL_HIP(hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev));
     TL_REQUIRE(rate_khz > 0, "engine_profile_step: device reports no wall clock rate");
-    // largest grid of the step: the lm_head GEMV (4 rows per workgroup at worst) or the attention grid
-    const int max_wg = std::max(c.vocab_size / 4 + 64, 64 * 4 * c.num_kv_heads * batch) + 1024;
-    ProfCtx pc;
-    pc.cap = c.num_layers * 12 + 8;  // up to 11 launches per layer at 5 .. 64 rows (four skinny matmuls + reductions, attention, merge, norms)
     TL_HIP(hipStreamSynchronize(e->stream));
-    TL_HIP(hipMalloc((void **)&pc.buf, (size_t)max_wg * 2 * sizeof(prof_t)));
-    TL_HIP(hipMalloc((void **)&pc.pairs, (size_t)pc.cap * 2 * sizeof(prof_t)));
-    auto cleanup = [&]() {
-        (void)hipFree(pc.buf);
-        (void)hipFree(pc.pairs);
-    };
-    if (hipMemsetAsync(pc.buf, 0, (size_t)max_wg * 2 * sizeof(prof_t), e->stream) != hipSuccess) {
-        cleanup();
-        return fail(TL_ERR_HIP, "engine_profile_step: memset failed");
-    }
-    hipLaunchKernelGGL(embed_slots_kernel, dim3(batch), dim3(256), 0, e->stream, e->tokens, e->embed.weight_dev,
-                       (const uint16_t *)e->embed.scales_dev, (const uint16_t *)e->embed.biases_dev, e->x, c.hidden_size,
-                       c.vocab_size, e->context_lens, e->rope_table, e->rope_cur, e->rope_positions, c.head_dim / 2, e->ss_x);
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    int max_ctx = 1;
-    int rc = reserve_step_locked(e, batch, pk, &max_ctx);
-    if (rc != TL_OK) {
-        cleanup();
-        return rc;
-    }
-    rc = pk.empty() ? TL_OK : poke(e, pk);
-    const SplitPlan sp = pick_decode_splits(e, batch, max_ctx);
-    const int n_splits = sp.n_splits;
+    ProfCtx pc;
+    if (!pc.alloc(e, batch)) return fail(TL_ERR_HIP, "engine_profile_step: hipMalloc / memset of the stamp buffers failed");
+    launch_embed_slots(e, batch);
+    SplitPlan sp;
+    int rc = prepare_step(e, batch, &sp);
     if (rc == TL_OK) rc = enqueue_step(e, batch, sp, &pc);
     if (rc != TL_OK) {
         (void)hipStreamSynchronize(e->stream);
-        cleanup();
         return rc;
     }
     e->warmed = true;
-    for (int b = 0; b < batch; ++b) {
-        if (!e->slot_live[b]) continue;
-        e->slot_ctx[b] += 1;
-        e->slot_produced[b] += 1;
-    }
-    e->stats.decode_steps++;
-    e->logits_rows = batch;
+    step_done(e, batch);
     std::vector<prof_t> pairs(pc.kinds.size() * 2);
     hipError_t he = hipStreamSynchronize(e->stream);
     if (he == hipSuccess) he = hipMemcpy(pairs.data(), pc.pairs, pairs.size() * sizeof(prof_t), hipMemcpyDeviceToHost);
-    cleanup();
     if (he != hipSuccess) return fail(TL_ERR_HIP, std::string("engine_profile_step: ") + hipGetErrorString(he));
 
     *out = tl_step_profile{};
     out->clock_khz = rate_khz;
-    out->n_splits = n_splits;
+    out->n_splits = sp.n_splits;
     const double us_per_tick = 1e3 / (double)rate_khz;
     prof_t first = ~0ull, last = 0;
     for (size_t i = 0; i < pc.kinds.size(); ++i) {
@@ -2885,7 +2804,6 @@ extern "C" int tl_engine_profile_step(tl_engine *e, int batch, tl_step_profile *
 extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out) {
     TL_REQUIRE(e && out, "engine_check_step: null argument");
     TL_REQUIRE(batch > 0 && batch <= e->cfg.max_batch, "engine_check_step: batch out of range");
-    const tl_engine_config &c = e->cfg;
     *out = tl_step_check{};
     out->first_launch = -1, out->first_kind = -1, out->first_region = -1, out->first_offset = -1;
     TL_TRY(aql_drain(e));
@@ -2894,17 +2812,13 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
     ck = tl_engine::WrittenOnceCheck{};
     ck.region[0] = e->arena + e->arena_act_off, ck.bytes[0] = (e->arena_bytes - e->arena_act_off) / 4 * 4;
     ck.region[1] = e->layer_act_mem, ck.bytes[1] = e->layer_act_mem ? e->layer_act_bytes / 4 * 4 : 0;
-    const int max_wg = std::max(c.vocab_size / 4 + 64, 64 * 4 * c.num_kv_heads * batch) + 1024;
     ProfCtx pc;
-    pc.cap = c.num_layers * 12 + 8;
     auto cleanup = [&]() {
         for (int rg = 0; rg < 2; ++rg) {
             if (ck.shadow[rg]) (void)hipFree(ck.shadow[rg]);
             if (ck.written[rg]) (void)hipFree(ck.written[rg]);
         }
         if (ck.report) (void)hipFree(ck.report);
-        if (pc.buf) (void)hipFree(pc.buf);
-        if (pc.pairs) (void)hipFree(pc.pairs);
         ck = tl_engine::WrittenOnceCheck{};
     };
     auto bail = [&](int code, const std::string &msg) {
@@ -2912,31 +2826,24 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
         cleanup();
         return fail(code, msg);
     };
-    bool ok = hipMalloc((void **)&pc.buf, (size_t)max_wg * 2 * sizeof(prof_t)) == hipSuccess && hipMalloc((void **)&pc.pairs, (size_t)pc.cap * 2 * sizeof(prof_t)) == hipSuccess &&
-              hipMalloc((void **)&ck.report, 8 * sizeof(unsigned long long)) == hipSuccess;
+    bool ok = pc.alloc(e, batch) && hipMalloc((void **)&ck.report, 8 * sizeof(unsigned long long)) == hipSuccess;
     for (int rg = 0; rg < 2 && ok; ++rg)
         if (ck.bytes[rg]) ok = hipMalloc((void **)&ck.shadow[rg], ck.bytes[rg]) == hipSuccess && hipMalloc((void **)&ck.written[rg], ck.bytes[rg] / 2) == hipSuccess;
     if (!ok) return bail(TL_ERR_HIP, "engine_check_step: hipMalloc of the shadow buffers failed");
     // the per-layer buffers start the step POISONED (every 16-bit and 32-bit pattern a NaN): a value read before this step wrote it
     // reaches the logits as NaN; the shared activations carry state between steps (x, its sums of squares) and keep their contents
     const unsigned long long report0[8] = {0, ~0ull, 0, 0, 0, 0, 0, 0};
-    ok = hipMemsetAsync(pc.buf, 0, (size_t)max_wg * 2 * sizeof(prof_t), e->stream) == hipSuccess &&
-         hipMemcpyAsync(ck.report, report0, sizeof(report0), hipMemcpyHostToDevice, e->stream) == hipSuccess;
+    ok = hipMemcpyAsync(ck.report, report0, sizeof(report0), hipMemcpyHostToDevice, e->stream) == hipSuccess;
     if (ok && ck.bytes[1]) ok = hipMemsetAsync(ck.region[1], 0xff, ck.bytes[1], e->stream) == hipSuccess;
     if (!ok) return bail(TL_ERR_HIP, "engine_check_step: initialisation failed");
-    hipLaunchKernelGGL(embed_slots_kernel, dim3(batch), dim3(256), 0, e->stream, e->tokens, e->embed.weight_dev,
-                       (const uint16_t *)e->embed.scales_dev, (const uint16_t *)e->embed.biases_dev, e->x, c.hidden_size,
-                       c.vocab_size, e->context_lens, e->rope_table, e->rope_cur, e->rope_positions, c.head_dim / 2, e->ss_x);
+    launch_embed_slots(e, batch);
     // the shadows = the regions as the step finds them; nothing written yet
     for (int rg = 0; rg < 2 && ok; ++rg)
         if (ck.bytes[rg]) ok = hipMemcpyAsync(ck.shadow[rg], ck.region[rg], ck.bytes[rg], hipMemcpyDeviceToDevice, e->stream) == hipSuccess &&
                                hipMemsetAsync(ck.written[rg], 0, ck.bytes[rg] / 2, e->stream) == hipSuccess;
     if (!ok) return bail(TL_ERR_HIP, "engine_check_step: shadow copy failed");
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    int max_ctx = 1;
-    int rc = reserve_step_locked(e, batch, pk, &max_ctx);
-    if (rc == TL_OK && !pk.empty()) rc = poke(e, pk);
-    const SplitPlan sp = pick_decode_splits(e, batch, max_ctx);
+    SplitPlan sp;
+    int rc = prepare_step(e, batch, &sp);
     if (rc == TL_OK) {
         ck.on = true;
         rc = enqueue_step(e, batch, sp, &pc);
@@ -2948,17 +2855,11 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
         return rc;
     }
     e->warmed = true;
-    for (int b = 0; b < batch; ++b) {
-        if (!e->slot_live[b]) continue;
-        e->slot_ctx[b] += 1;
-        e->slot_produced[b] += 1;
-    }
-    e->stats.decode_steps++;
-    e->logits_rows = batch;
+    step_done(e, batch);
     unsigned long long report[8] = {0};
     hipError_t he = hipStreamSynchronize(e->stream);
     if (he == hipSuccess) he = hipMemcpy(report, ck.report, sizeof(report), hipMemcpyDeviceToHost);
-    const std::vector<int> kinds = pc.kinds;
+    const std::vector<int> &kinds = pc.kinds;
     cleanup();
     if (he != hipSuccess) return fail(TL_ERR_HIP, std::string("engine_check_step: ") + hipGetErrorString(he));
     out->launches = (int)kinds.size();
