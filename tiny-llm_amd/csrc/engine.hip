@@ -4,45 +4,24 @@
 //   * one fused decode step = 5 launches per layer (+ merge when the context is split) + 2 at the end,
 //     captured into a hipGraph per (batch, n_splits) and replayed
 //   * multi-token prefill on the MFMA W4 GEMM + paged FlashAttention operators of tinyllm_hip.h
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
+#include <dlfcn.h>
 
-#include "../../include/tinyllm_engine.h"
-#include "common.h"
-#include "engine_kernels.h"
+#include <cstring>
+#include <memory>
+
+#include "decode_linear.h"  // the projection router; with it common.h, engine_kernels.h and the decode matmuls' headers
 #include "sample.h"
 #include "logprob.h"
-#include "qmv.h"
-#include "qmv3.h"
-#include "qmm3.h"
-#include "qmm6.h"
-#include "qmm7.h"
-#include "gemm8.h"
 #include "attn_mfma.h"
 #include "aql.h"
 
-#include <dlfcn.h>
-#include <memory>
-
 namespace tl {
-
-#define TL_TRY(expr)                  \
-    do {                              \
-        const int rc__ = (expr);      \
-        if (rc__ != TL_OK) return rc__; \
-    } while (0)
 
 #define TL_HIP(expr)                                                                           \
     do {                                                                                       \
         const hipError_t e__ = (expr);                                                         \
         if (e__ != hipSuccess) return fail(TL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
     } while (0)
-
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace tl
 
@@ -68,33 +47,20 @@ struct tl_engine {
     size_t kv_elem_bytes() const { return kv_format == TL_KV_FP8_E4M3 ? 1 : 2; }
     float *layer_ks(int l) const { return kscale_pool ? kscale_pool + (size_t)l * layer_scale_elems : nullptr; }
     float *layer_vs(int l) const { return vscale_pool ? vscale_pool + (size_t)l * layer_scale_elems : nullptr; }
-    void *splitk_ws = nullptr;
-    size_t splitk_ws_bytes = 0;
-    // decode-path copy of every W4 matrix in the tiled MFMA layout (qmv3.h); keyed by the checkpoint pointer
-    struct Tiled {
-        uint32_t *wt = nullptr, *sbt = nullptr;
-    };
-    std::map<const uint32_t *, Tiled> tiled;
-    size_t tiled_bytes = 0;
-    // Prefill chunks of GEMM8_MIN_ROWS (1,536) rows and more (an engine created with max_prefill_rows that large): the layer matrices once more as
-    // bf16 -- bf16(q * s + beta), the B operand the reference's tile GEMM forms in threadgroup memory (quantized_matmul.metal:96-249) -- for
-    // the plain bf16 GEMM of gemm8.h (256 x 256 tiles by LDS-DMA, no dequantisation in the loop).  7.3 GB at Qwen3-4B, of 288.
-    std::map<const uint32_t *, uint16_t *> bf16w;
-    size_t bf16w_bytes = 0;
-    bool use_gemm8 = true;  // tl_engine_set_option "gemm8" = 0: every chunk through the W4 GEMM (qmm.hip), the twin
-    bool fuse_reduce_norm = true;  // "prefill_reduce_norm" = 0: the split-K residual reduction and the RMSNorm behind it as two launches, the twin
+    // what the projection router reads (decode_linear.h): weight copies, matmul workspace, routing options; stream, eps and xn as below
+    LinearCtx lin;
+    size_t tiled_bytes = 0, bf16w_bytes = 0;
 
     int32_t *block_table = nullptr, *context_lens = nullptr, *tokens = nullptr, *live = nullptr, *produced = nullptr,
             *ring = nullptr, *scratch_ctx = nullptr, *prefill_tokens = nullptr;
     uint16_t *x = nullptr, *h = nullptr, *xn = nullptr, *qkv = nullptr, *q_t = nullptr, *attn_t = nullptr,
-             *attn = nullptr, *gu = nullptr, *act = nullptr, *tmp = nullptr, *logits = nullptr;
+             *attn = nullptr, *act = nullptr, *logits = nullptr;
     float *attn_ws = nullptr;
     int last_attn_launches = 0;
     // lm_head GEMV of a 1-4-row decode step: per 16-logit tile (max, lowest index) pairs for step_end_kernel (qmv3.h tile_max);
     // tl_engine_set_option "lmhead_tile_max" = 0: step_end reads the logits row again
     f32x2 *lm_tile_max = nullptr;            // [8][vocab / 16]
-    bool lm_tile_max_on = true, want_tile_max = false;
-    int tile_max_rows = 0;                   // rows of the last lm_head launch that left pairs (0 = none)
+    bool lm_tile_max_on = true;
     float *ss_x = nullptr, *ss_h = nullptr;  // [max_batch][QM3_SS] partial sums of squares of the rows of x / h (qmm3.h)
     // At 5 .. 64 decode rows the qkv projection's slice reduction is not launched; the decode-attention kernel adds the fp32 slice
     // partials itself (engine_kernels.h, QP).  Measured in round 3 (profiles/r03_labs/batched_decode_status.jsonl): 5 / 8 / 16 / 64
@@ -106,26 +72,7 @@ struct tl_engine {
     // merging GEMV costs +0.9 / +2.0 us per layer, the merge launch cost 0.6 us + a boundary); 64-token windows stay the best
     // (128-token windows: 1.022).  Other split counts, more sequences or another head size keep the merge launch (wo_merge_applicable).
     bool wo_merges_attn = true;
-    // The 1-4-row GEMVs add the partial sums of squares their producer left instead of re-deriving them (a row without partials --
-    // the first step after a MoE layer, a packed-dot fallback -- is still re-derived inside the kernel: qmv3.h, ss_given):
-    // qkv -0.44 us, gate|up -1.1 us per layer (abl_lab, bit 8)
-    bool gemv_producer_ss = true;
-    // The wo GEMV of 1-4 decode rows also leaves h * post_attention_layernorm (bf16) and the gate|up GEMV stages THAT row and
-    // multiplies its sums by the row's 1 / rms at the end (qmv3.h, PRO_RMS_WEIGHTED): the 1,216 workgroups of gate|up no longer
-    // fetch the norm weights and normalise the whole row each.  tools/lab/trace_lab, back to back: gate|up 7.82 -> 7.08 us, wo
-    // 3.91 -> 4.06; the qkv and lm_head GEMVs gain nothing from it and keep the fused RMSNorm (weighted_rows_apply decides by shape).
-    bool gemv_weighted_rows = true;
-    bool fuse_norm = true;                   // the skinny matmul normalises its own slice whenever its producer left sums of squares
     int32_t *verify_ids = nullptr;  // greedy ids of the rows of the last tl_engine_verify
-    int qmm3_min_rows = 5;  // rows from which a projection uses the K-sliced skinny matmul instead of the GEMV (TL_QMM3_MIN_M)
-    bool use_qmm3 = true;   // tl_engine_set_option "qmm3" = 0: rows > 8 go through the prefill GEMM path instead
-    // 5 .. 64 rows: the register-resident matmul (qmm6.h) takes every projection whose plan fits; rows travel WEIGHTED between the
-    // projections (qkv <- w_down / the embedding, gate|up <- wo).  tl_engine_set_option "qmm6" = 0: the K-sliced skinny matmul as before.
-    bool use_qmm6 = true;
-    // ... and, where its plan exists (round 6: gate|up and qkv of a 2,560-wide model), the row-streaming matmul (qmm7.h) instead of the
-    // register-resident one: the rows' arrival overlaps the walk, a step costs by its 16-row blocks (3 included).  force_qmm7: the
-    // kernel-level entry point asked for it by name (an error where it does not apply).
-    bool use_qmm7 = true, force_qmm7 = false;
     int attn_rq = 0;             // query heads per decode-attention workgroup; 0 = by context (TL_ATTN_RQ at create: 1 or 4)
     int attn_rq1_ctx = 4096;     // contexts up to this many tokens use one query head per workgroup
     int attn_rq1_batch = 2;      // ... and up to this many sequences; at 4 the re-read windows cost 261 vs 180 us
@@ -135,10 +82,6 @@ struct tl_engine {
     bool attn_mfma = true;       // TL_ATTN_MFMA=0: the GQA-group walk on the VALU (attn_decode_fused_kernel), the A/B twin of attn_mfma.h
     int attn_max_splits = 64;    // most context splits per sequence (TL_ATTN_MAX_SPLITS, a power of two <= 256)
     int attn_max_splits_gqa = 32;  // ... when a workgroup takes a whole GQA group (TL_ATTN_MAX_SPLITS sets both)
-    tl_linear_info *linfo = nullptr;    // kernel-level entry points: which kernel a projection ran
-    int force_linear = 0;               // kernel-level entry points: 1 = fused GEMV, 2 = skinny matmul
-    int qmm3_mode = -1;                 // skinny matmul grid: -1 by shape (qmm3_plan), 0 one-shot, 1 persistent
-    bool gemm_fused_epilogue = true;    // tl_engine_set_option "gemm_fused_epilogue" = 0: residual / SwiGLU of the prefill GEMM as separate launches
     size_t attn_ws_bytes = 0;
     int rows_cap = 0;
     int ring_cap = 4096;
@@ -205,20 +148,7 @@ struct tl_engine {
     int layer_act_rows = 0;       // rows the per-layer buffers hold (0: none)
     size_t layer_ws_bytes = 0;    // attention partials per layer
     size_t layer_plane_bytes[2] = {0, 0};  // slice planes per layer: [0] wo, [1] w_down
-    // the K-sliced matmul writes its fp32 planes here instead of splitk_ws while a per-layer batched step is enqueued (engine_linear)
-    float *planes_now = nullptr;
-    size_t planes_now_bytes = 0;
     bool step_written_once = false;  // the last enqueued step used the per-layer buffers throughout (enqueue_step)
-    // tl_engine_check_step (test-only): the hand-over regions -- [0] the shared activations of the arena, [1] the per-layer buffers -- with
-    // a shadow copy and one "written this step" byte per 2-byte element each, alive only inside the call
-    struct WrittenOnceCheck {
-        bool on = false;
-        char *region[2] = {nullptr, nullptr};
-        size_t bytes[2] = {0, 0};
-        uint32_t *shadow[2] = {nullptr, nullptr};
-        uint8_t *written[2] = {nullptr, nullptr};
-        unsigned long long *report = nullptr;
-    } check;
     size_t arena_act_off = 0;        // where the activations start inside the arena (behind the state words)
     size_t layer_act_bytes = 0;      // size of layer_act_mem
     // Qwen3-MoE layers (tl_engine_set_moe_layer): router + stacked experts instead of the dense gate|up / w_down of that layer
@@ -244,33 +174,6 @@ static int aql_drain(tl_engine *e);
 static std::string library_dir();
 
 namespace tl {
-
-// ---- profile step bookkeeping -------------------------------------------------------------------------
-// kinds: 0..4 GEMV (qkv, o, gate_up, down, lm_head), 5 attention, 6 merge, 7 step end
-struct ProfCtx {
-    prof_t *buf = nullptr;    // per-workgroup (start, end) pairs of the launch in flight
-    prof_t *pairs = nullptr;  // [n][2] reduced (start, end) per launch
-    std::vector<int> kinds;
-    int cap = 0;
-    ProfCtx() = default;
-    ProfCtx(const ProfCtx &) = delete;
-    ~ProfCtx() {
-        if (buf) (void)hipFree(buf);
-        if (pairs) (void)hipFree(pairs);
-    }
-    // room for one eagerly launched step over `batch` rows (tl_engine_profile_step, tl_engine_check_step): the largest grid of the
-    // step -- the lm_head GEMV (4 rows per workgroup at worst) or the attention grid -- and up to 11 launches per layer at 5 .. 64 rows
-    // (four skinny matmuls + reductions, attention, merge, norms); the stamps start zeroed, stream-ordered
-    bool alloc(const tl_engine *e, int batch) {
-        const tl_engine_config &c = e->cfg;
-        const size_t buf_bytes = (size_t)(std::max(c.vocab_size / 4 + 64, 64 * 4 * c.num_kv_heads * batch) + 1024) * 2 * sizeof(prof_t);
-        cap = c.num_layers * 12 + 8;
-        return hipMalloc((void **)&buf, buf_bytes) == hipSuccess && hipMalloc((void **)&pairs, (size_t)cap * 2 * sizeof(prof_t)) == hipSuccess &&
-               hipMemsetAsync(buf, 0, buf_bytes, e->stream) == hipSuccess;
-    }
-};
-
-static void prof_after(tl_engine *e, ProfCtx *pc, int kind, int n_wg);
 
 // ---- small launch helpers ----------------------------------------------------------------------
 static int poke(tl_engine *e, std::vector<std::pair<int32_t *, int32_t>> &items) {
@@ -628,356 +531,6 @@ static int lp_carry(tl_engine *e, int src, int dst, bool move) {
     return move ? lp_write(e, src, -1) : TL_OK;
 }
 
-static int check_w4(const tl_w4 &w, int rows, int cols, const char *name) {
-    if (!w.weight_dev || !w.scales_dev || !w.biases_dev)
-        return fail(TL_ERR_INVALID, std::string("engine: null weight pointer in ") + name);
-    if (w.rows != rows || w.cols != cols)
-        return fail(TL_ERR_INVALID, std::string("engine: unexpected shape for ") + name + " (got " +
-                                        std::to_string(w.rows) + "x" + std::to_string(w.cols) + ", want " +
-                                        std::to_string(rows) + "x" + std::to_string(cols) + ")");
-    if ((uintptr_t)w.weight_dev % 16 != 0)
-        return fail(TL_ERR_INVALID, std::string("engine: weight not 16-byte aligned: ") + name);
-    return TL_OK;
-}
-
-// GEMV with fused prologue/epilogue over M <= 8 rows; splits the rows when the activation tile exceeds LDS.
-// ss_in / ss_in_n: partial sums of squares of the rows of `a` ([M][ss_in_n]) when its producer left them; ss_out: where an
-// EPI_RESIDUAL GEMV leaves those of `out` ([M][rows / 16]); *ss_out_n = partials per row actually written (0 = none).
-static int engine_qmv(tl_engine *e, const tl_w4 &w, const uint16_t *a, uint16_t *out, int M, int pro, int epi,
-                      const void *norm_w, const uint16_t *residual, ProfCtx *pc = nullptr, int kind = 0,
-                      const float *ss_in = nullptr, int ss_in_n = 0, float *ss_out = nullptr, int *ss_out_n = nullptr,
-                      const void *norm_out = nullptr, uint16_t *out_w = nullptr) {
-    // norm_out / out_w (EPI_RESIDUAL): also leave out * norm_out for a PRO_RMS_WEIGHTED consumer; the caller has checked
-    // (weighted_rows_apply) that the MFMA GEMV takes all rows in one pass -- anything else is an error, not a silent fallback
-    if (ss_out_n) *ss_out_n = 0;
-    bool all_emitted = ss_out != nullptr && epi == EPI_RESIDUAL && e->gemv_producer_ss;
-    int step = std::min(M, 8);  // both GEMV kernels hold at most 8 activation rows (MR <= 8): more rows go in passes of 8
-    const bool has_tiled = e->tiled.count(w.weight_dev) != 0;
-    auto fits = [&](int rows) {
-        return (has_tiled && qmv3_plan(rows, w.cols, w.rows).ok) || qmv_plan(rows, w.cols, w.rows).lds <= 150 * 1024;
-    };
-    while (!fits(step) && step > 1) step = (step + 1) / 2;
-    const int out_cols = epi == EPI_SWIGLU ? w.rows / 2 : w.rows;
-    for (int m0 = 0; m0 < M; m0 += step) {
-        QmvArgs args{};
-        args.scales = (const uint16_t *)w.scales_dev;
-        args.biases = (const uint16_t *)w.biases_dev;
-        args.b = w.weight_dev;
-        args.a = a + (size_t)m0 * w.cols;
-        args.out = out + (size_t)m0 * out_cols;
-        args.norm_w = (const uint16_t *)norm_w;
-        args.residual = residual ? residual + (size_t)m0 * w.rows : nullptr;
-        args.eps = e->cfg.rms_norm_eps;
-        args.M = std::min(step, M - m0);
-        args.N = w.cols;
-        args.K = w.rows;
-        args.prof = pc ? pc->buf : nullptr;
-        const auto tiled = e->tiled.find(w.weight_dev);
-        const Qmv3Plan p3 = qmv3_plan(args.M, args.N, args.K);
-        if (tiled != e->tiled.end() && p3.ok) {
-            Qmv3Args a3{};
-            a3.wt = tiled->second.wt;
-            a3.sbt = tiled->second.sbt;
-            a3.a = args.a;
-            a3.out = args.out;
-            a3.norm_w = args.norm_w;
-            a3.residual = args.residual;
-            a3.eps = args.eps;
-            a3.M = args.M;
-            a3.N = args.N;
-            a3.K = args.K;
-            a3.prof = args.prof;
-            if (e->gemv_producer_ss) {
-                if ((pro == PRO_RMSNORM || pro == PRO_RMS_WEIGHTED) && ss_in && ss_in_n > 0) a3.ss_in = ss_in + (size_t)m0 * ss_in_n, a3.ss_n = ss_in_n;
-                if (epi == EPI_RESIDUAL && ss_out) a3.ss_out = ss_out + (size_t)m0 * (w.rows / 16);
-            }
-            if (e->want_tile_max && e->lm_tile_max && epi == EPI_STORE && step == M && w.rows % 16 == 0) {
-                a3.tile_max = e->lm_tile_max;
-                e->tile_max_rows = M;
-            }
-            if (out_w) {
-                TL_REQUIRE(epi == EPI_RESIDUAL && norm_out && step == M, "engine: weighted rows need the residual epilogue and one pass");
-                a3.norm_out = (const uint16_t *)norm_out;
-                a3.out_w = out_w;
-            }
-            if (launch_qmv3_bf16(a3, pro, epi, e->stream) != 0)
-                return fail(TL_ERR_UNSUPPORTED, "engine: MFMA GEMV launch failed");
-            if (pc) prof_after(e, pc, kind, p3.blocks);
-            if (e->linfo) {
-                tl_linear_info &li = *e->linfo;
-                li.kernel = li.kernel == 0 || li.kernel == 1 ? 1 : li.kernel;
-                li.launches += 1;
-                li.rows_per_pass = step;
-                li.p[0] = p3.MR, li.p[1] = p3.KS, li.p[2] = p3.CW, li.p[3] = p3.LM, li.p[4] = p3.blocks;
-            }
-            continue;
-        }
-        all_emitted = false;  // the packed-dot fallback leaves no partials
-        TL_REQUIRE(out_w == nullptr && pro != PRO_RMS_WEIGHTED, "engine: weighted rows are a route of the MFMA GEMV only");
-        if (launch_qmv_fused_bf16(args, pro, epi, e->stream) != 0)
-            return fail(TL_ERR_UNSUPPORTED, "engine: no GEMV configuration for this shape");
-        if (pc) prof_after(e, pc, kind, qmv_plan(args.M, args.N, args.K).blocks);
-        if (e->linfo) {
-            e->linfo->kernel = 3;  // the packed-dot fallback ran (at least once)
-            e->linfo->launches += 1;
-            e->linfo->rows_per_pass = step;
-        }
-    }
-    TL_CHECK_LAUNCH("engine gemv");
-    if (ss_out_n && all_emitted && w.rows % 16 == 0) *ss_out_n = w.rows / 16;
-    return TL_OK;
-}
-
-// The split-K / skinny-matmul workspace is sized ONCE in tl_engine_create for every shape the engine can launch
-// (instantiated graphs hold its address, and a capture cannot synchronise or allocate): a request beyond it is an error.
-static int ensure_splitk(tl_engine *e, size_t bytes) {
-    if (bytes <= e->splitk_ws_bytes) return TL_OK;
-    return fail(TL_ERR_INVALID, "engine: matmul workspace too small for this shape (sized at tl_engine_create: " +
-                                    std::to_string(e->splitk_ws_bytes) + " bytes, need " + std::to_string(bytes) + ")");
-}
-
-// Reference-semantics GEMM over the checkpoint layout (weights rounded to bf16 first): tl_quantized_matmul.
-static int engine_qmm(tl_engine *e, const tl_w4 &w, const uint16_t *a, uint16_t *out, int M) {
-    const size_t need = tl_quantized_matmul_workspace_bytes(M, w.cols, w.rows, TL_BF16, 1, 1);
-    TL_TRY(ensure_splitk(e, need));
-    return tl_quantized_matmul(w.scales_dev, w.biases_dev, a, w.weight_dev, out, M, w.cols, w.rows, 128, 4, TL_BF16, 1, 1,
-                               e->splitk_ws, e->splitk_ws_bytes, e->stream);
-}
-
-// out = epilogue(a @ W^T) for any number of rows (chunked prefill, batches above 64): the reference's own op sequence --
-// W4 MFMA GEMM over the checkpoint layout (quantize.py:54-65 routes rows > 8 to the matmul path, whose tile kernel rounds
-// the dequantised weights to bf16 first), then SwiGLU / residual as separate launches.
-// From this many rows a chunk's projections run on the plain bf16 GEMM (gemm8.h).  In the lab (back-to-back launches on one weight matrix, which then sits in the
-// 256-MB Infinity Cache) gemm8 wins from ~1,500 rows; in the ENGINE every layer streams its own 202 MB of bf16 weights from HBM and the grid counts in
-// whole 256-row bands, measured at the end of round 6 (chunked prefill of 6,144 / 8,192 tokens, gemm8 / W4 GEMM, tokens/s): 1,536-row chunks 63.0k / 71.7k,
-// 2,048 83.8k / 75.6k, 3,072 77.7k / 78.0k, 4,096 100.5k / 75.9k -- so from 7 bands (until then the constant was 1,536: 12 % slower at exactly that size).
-constexpr int GEMM8_MIN_ROWS = 1792;
-static bool gemm8_wins(int M, int out_features) {
-    (void)out_features;
-    return M >= GEMM8_MIN_ROWS;
-}
-// norm_w / norm_out / norm_done: the RMSNorm that follows an EPI_RESIDUAL projection, taken along by its split-K reduction pass where there is one
-// (small chunks on the W4 GEMM); *norm_done says whether norm_out was written -- the caller launches tl_rms_norm otherwise
-static int engine_gemm(tl_engine *e, const tl_w4 &w, const uint16_t *a, uint16_t *out, int M, int epi,
-                       const uint16_t *residual, const void *norm_w = nullptr, uint16_t *norm_out = nullptr, bool *norm_done = nullptr) {
-    if (norm_done) *norm_done = false;
-    if (e->use_gemm8 && gemm8_wins(M, w.rows)) {
-        const auto wb = e->bf16w.find(w.weight_dev);
-        if (wb != e->bf16w.end() && gemm8_applicable(M, w.rows, w.cols)) {
-            Gemm8Args g{};
-            g.a = a, g.w = wb->second, g.out = out, g.residual = residual, g.M = M, g.N = w.rows, g.K = w.cols;
-            if (launch_gemm8_bf16(g, epi, e->stream) != 0) return fail(TL_ERR_UNSUPPORTED, "engine: bf16 GEMM launch failed");
-            TL_CHECK_LAUNCH("engine bf16 matmul");
-            return TL_OK;
-        }
-    }
-    if (epi != EPI_STORE && M > 8 && e->gemm_fused_epilogue) {  // residual / SwiGLU inside the GEMM store or its split-K reduction
-        const size_t need = tl_quantized_matmul_workspace_bytes(M, w.cols, w.rows, TL_BF16, 1, 1);
-        TL_TRY(ensure_splitk(e, need));
-        TL_TRY(qmm_bf16_epilogue(w.scales_dev, w.biases_dev, a, w.weight_dev, out, M, w.cols, w.rows, epi, residual, e->splitk_ws,
-                                 e->splitk_ws_bytes, e->stream, e->fuse_reduce_norm ? (const uint16_t *)norm_w : nullptr, norm_out, e->cfg.rms_norm_eps,
-                                 norm_done));
-        TL_CHECK_LAUNCH("engine matmul");
-        return TL_OK;
-    }
-    uint16_t *plain = epi == EPI_STORE ? out : (epi == EPI_SWIGLU ? e->gu : e->tmp);
-    TL_TRY(engine_qmm(e, w, a, plain, M));
-    if (epi == EPI_SWIGLU) {
-        const long n4 = (long)M * (w.rows / 2) / 4;
-        hipLaunchKernelGGL(swiglu_interleaved_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, e->stream, plain, out, n4);
-    } else if (epi == EPI_RESIDUAL) {
-        const long n8 = (long)M * w.rows / 8;
-        hipLaunchKernelGGL(residual_add_kernel, dim3(ceil_div(n8, 256)), dim3(256), 0, e->stream, residual, plain, out, n8);
-    }
-    TL_CHECK_LAUNCH("engine matmul");
-    return TL_OK;
-}
-
-// Does the register-resident matmul (qmm6.h) take this projection at M rows?
-static bool qmm6_takes(const tl_engine *e, const tl_w4 &w, int M) {
-    return e->use_qmm6 && e->force_linear == 0 && M >= e->qmm3_min_rows && M <= 64 && e->tiled.count(w.weight_dev) != 0 && qmm6_plan(M, w.cols, w.rows).ok;
-}
-// The weighted rows of a batched step (5 .. 64 rows) travel in fragment order (qmm6.h) from 9 rows -- and from 5 where the row-streaming
-// matmul (qmm7.h) is the consumer: ONE answer per (engine, batch) for every producer and consumer of a step.
-static bool rows_travel_in_fragment_order(const tl_engine *e, int batch) {
-    if (batch > 8) return true;
-    if (!e->use_qmm7 || e->layers.empty() || !e->layers[0].wgu.weight_dev) return false;
-    return qmm7_plan(batch, e->layers[0].wgu.cols, e->layers[0].wgu.rows).ok && qmm7_plan(batch, e->layers[0].wqkv.cols, e->layers[0].wqkv.rows).ok;
-}
-// One projection through qmm6: `a` plain rows, or (ss_in given) WEIGHTED rows whose 1 / rms scales the result.  EPI_RESIDUAL: ss_out
-// receives rows / 16 partial sums of squares per row, out_w the rows weighted for the next RMSNorm (norm_out).
-static int engine_qmm6(tl_engine *e, const tl_w4 &w, const uint16_t *a, uint16_t *out, int M, int epi, const uint16_t *residual,
-                       ProfCtx *pc, int kind, const float *ss_in, int ss_in_n, float *ss_out, int *ss_out_n, const void *norm_out,
-                       uint16_t *out_w, bool frag = false, int out_w_frag = -1) {
-    // frag: the weighted rows on either side (`a` with ss_in, `out_w`) lie in fragment order (qmm6.h) -- the engine's own hand-over;
-    // out_w_frag >= 0 decides for out_w alone (the kernel-level entry point)
-    if (ss_out_n) *ss_out_n = 0;
-    const auto tiled = e->tiled.find(w.weight_dev);
-    TL_REQUIRE(tiled != e->tiled.end(), "engine: the register-resident matmul needs the tiled weights");
-    const bool a_frag = frag && ss_in != nullptr && epi != EPI_RESIDUAL;
-    const Qmm7Plan p7 = (e->use_qmm7 || e->force_qmm7) && a_frag && out_w == nullptr ? qmm7_plan(M, w.cols, w.rows) : Qmm7Plan{};
-    TL_REQUIRE(p7.ok || !e->force_qmm7, "engine: the row-streaming matmul takes weighted rows in fragment order (store / SwiGLU) at the shapes of qmm7_plan");
-    const Qmm6Plan pl = qmm6_plan(M, w.cols, w.rows, a_frag);
-    TL_REQUIRE(p7.ok || pl.ok, "engine: the register-resident matmul does not cover this shape");
-    Qmm6Args q{};
-    q.wt = tiled->second.wt;
-    q.sbt = tiled->second.sbt;
-    q.a = a;
-    q.out = out;
-    q.residual = residual;
-    q.norm_out = (const uint16_t *)norm_out;
-    q.out_w = out_w;
-    q.ss = ss_in;
-    q.ss_n = ss_in ? ss_in_n : 0;
-    q.ss_out = epi == EPI_RESIDUAL ? ss_out : nullptr;
-    q.eps = e->cfg.rms_norm_eps;
-    q.M = M;
-    q.N = w.cols;
-    q.K = w.rows;
-    q.prof = pc ? pc->buf : nullptr;
-    q.a_frag = a_frag;
-    q.out_w_frag = (out_w_frag >= 0 ? out_w_frag != 0 : frag) && out_w != nullptr;
-    int n_wg = 0;
-    if (p7.ok) {
-        if (launch_qmm7_bf16(q, epi, e->stream, &n_wg) != 0) return fail(TL_ERR_UNSUPPORTED, "engine: row-streaming matmul launch failed");
-        if (pc) prof_after(e, pc, kind, n_wg);
-        if (e->linfo) {
-            tl_linear_info &li = *e->linfo;
-            li.kernel = 6;
-            li.launches += 1;
-            li.rows_per_pass = p7.MB * 16;
-            li.p[0] = p7.MB, li.p[1] = p7.GPW, li.p[2] = p7.T, li.p[3] = p7.row_blocks, li.p[4] = n_wg;
-        }
-        TL_CHECK_LAUNCH("engine row-streaming matmul");
-        return TL_OK;
-    }
-    if (launch_qmm6_bf16(q, epi, e->stream, &n_wg) != 0) return fail(TL_ERR_UNSUPPORTED, "engine: register-resident matmul launch failed");
-    if (pc) prof_after(e, pc, kind, n_wg);
-    if (ss_out_n && q.ss_out) *ss_out_n = w.rows / 16;
-    if (e->linfo) {
-        tl_linear_info &li = *e->linfo;
-        li.kernel = 5;
-        li.launches += 1;
-        li.rows_per_pass = pl.MB * 16;
-        li.p[0] = pl.MB, li.p[1] = pl.GPW, li.p[2] = pl.NSETS, li.p[3] = pl.row_blocks, li.p[4] = n_wg;
-    }
-    TL_CHECK_LAUNCH("engine register-resident matmul");
-    return TL_OK;
-}
-
-// One projection of the decode step over `M` activation rows.  Up to 4 rows: the fused MFMA GEMV (weights streamed once,
-// RMSNorm / residual / SwiGLU inside).  5 .. 64 rows: the skinny matmul (qmm3.h) for every projection -- at 8 rows the GEMV
-// re-stages all rows in every workgroup (qkv 10.3 us against 4.8 + reduction; profiles/r02_labs/batched_rows_routing.log).  More rows, or option "qmm3" = 0: the
-// reference's own op sequence -- RMSNorm kernel, W4 MFMA GEMM (quantize.py:54-65 routes rows > 8 to the matmul path),
-// then SwiGLU / residual kernels.
-// ss_in: partial sums of squares of the rows of `a` when its producer emitted them (fused RMSNorm of the skinny matmul),
-// else nullptr.  ss_out / *ss_emitted: where the slice reduction should leave the partials of `out`, and whether it did.
-// keep (EPI_STORE only): the caller's consumer adds the slices itself -- the reduction launch is skipped and *keep says where the
-// fp32 planes are; `out` is then NOT written.  Left empty (partial == nullptr) when another kernel took the projection.
-// rows that engine_linear hands to the GEMV before it considers anything else
-static bool gemv_takes_rows(const tl_engine *e, int M) {
-    return e->force_linear == 1 || (e->force_linear != 2 && (M < e->qmm3_min_rows || (M <= 8 && !e->use_qmm3)));
-}
-// Can `producer` (EPI_RESIDUAL) leave its rows weighted for `consumer` (PRO_RMS_WEIGHTED)?  Both must be single-pass MFMA GEMVs,
-// the producer must leave the sums of squares, and the consumer's row must sit in its register chunks (qmv3.h, reg_path).
-static bool weighted_rows_apply(const tl_engine *e, const tl_w4 &producer, const tl_w4 &consumer, int M) {
-    if (!e->gemv_weighted_rows || !e->gemv_producer_ss || !gemv_takes_rows(e, M) || M > 8) return false;
-    if (e->tiled.count(producer.weight_dev) == 0 || e->tiled.count(consumer.weight_dev) == 0) return false;
-    const Qmv3Plan pp = qmv3_plan(M, producer.cols, producer.rows), pcn = qmv3_plan(M, consumer.cols, consumer.rows);
-    if (!pp.ok || !pcn.ok || producer.rows != consumer.cols) return false;
-    return qmv3_takes_weighted_rows(pcn, consumer.cols, producer.rows / 16);
-}
-// Does engine_linear send M rows of this projection to the K-sliced skinny matmul (qmm3.h)?  ONE predicate for the router below and for
-// every caller that plans around its answer (enqueue_step decides from it whether a producer will leave weighted rows).
-static bool takes_skinny_matmul(const tl_engine *e, const tl_w4 &w, int M) {
-    return !gemv_takes_rows(e, M) && e->use_qmm3 && M <= 64 && e->tiled.count(w.weight_dev) != 0 && qmm3_plan(M, w.cols, w.rows, e->qmm3_mode).ok;
-}
-struct KeptPartials {
-    const float *partial = nullptr;
-    int slices = 0;
-    long plane = 0;  // elements between slices (= rows * output columns)
-};
-static int engine_linear(tl_engine *e, const tl_w4 &w, const uint16_t *a, uint16_t *out, int M, int pro, int epi,
-                         const void *norm_w, const uint16_t *residual, ProfCtx *pc, int kind, const float *ss_in_any = nullptr,
-                         float *ss_out = nullptr, bool *ss_emitted = nullptr, KeptPartials *keep = nullptr, int ss_in_n = QM3_SS,
-                         int *ss_out_n = nullptr, const void *norm_out = nullptr, uint16_t *out_w = nullptr, bool out_w_frag = false) {
-    // ss_in_any holds ss_in_n partials per row; the skinny matmul reads exactly QM3_SS of them, the GEMV any number.
-    // *ss_out_n (when asked for) = partials per row left in ss_out: QM3_SS by the slice reduction, rows / 16 by a GEMV, 0 = none
-    if (ss_emitted) *ss_emitted = false;
-    if (ss_out_n) *ss_out_n = 0;
-    if (keep) *keep = KeptPartials{};
-    const float *ss_in = qmm3_takes_ss(ss_in_n) ? ss_in_any : nullptr;
-    if (gemv_takes_rows(e, M))
-        return engine_qmv(e, w, a, out, M, pro, epi, norm_w, residual, pc, kind, ss_in_any, ss_in_n, ss_out, ss_out_n, norm_out, out_w);
-    TL_REQUIRE(pro != PRO_RMS_WEIGHTED && (out_w == nullptr || (epi == EPI_RESIDUAL && norm_out != nullptr)),
-               "engine: the skinny matmul leaves weighted rows behind a residual epilogue only, and takes none");
-    const tl_engine_config &c = e->cfg;
-    const uint16_t *in = a;
-    // qmm3_min_rows .. 64 rows (batched decode): K-sliced skinny MFMA matmul over the tiled weights, then the slice
-    // reduction with the epilogue.  RMSNorm runs as its own launch (a slice does not see the whole row).
-    const auto tiled = e->tiled.find(w.weight_dev);
-    const Qmm3Plan p3 = qmm3_plan(M, w.cols, w.rows, e->qmm3_mode);
-    if (takes_skinny_matmul(e, w, M)) {
-        const bool fused_norm = pro == PRO_RMSNORM && ss_in != nullptr && e->fuse_norm;
-        if (pro == PRO_RMSNORM && !fused_norm) {
-            TL_TRY(tl_rms_norm(a, norm_w, e->xn, M, w.cols, c.rms_norm_eps, TL_BF16, e->stream));
-            in = e->xn;
-        }
-        if (e->planes_now) TL_REQUIRE(p3.partial_bytes <= e->planes_now_bytes, "engine: per-layer slice planes too small for this shape");
-        else TL_TRY(ensure_splitk(e, p3.partial_bytes));
-        Qmm3Args q{};
-        q.wt = tiled->second.wt;
-        q.sbt = tiled->second.sbt;
-        q.a = in;
-        q.partial = e->planes_now ? e->planes_now : (float *)e->splitk_ws;
-        q.M = M;
-        q.N = w.cols;
-        q.K = w.rows;
-        q.prof = pc ? pc->buf : nullptr;
-        q.norm_w = (const uint16_t *)norm_w;
-        q.ss = ss_in;
-        q.ss_n = ss_in_n;
-        q.eps = c.rms_norm_eps;
-        if (launch_qmm3_bf16(q, e->stream, fused_norm ? PRO_RMSNORM : PRO_NONE, e->qmm3_mode) != 0)
-            return fail(TL_ERR_UNSUPPORTED, "engine: skinny matmul launch failed");
-        if (pc) prof_after(e, pc, kind, p3.persistent ? p3.grid_x : p3.grid_x * p3.slices);
-        float *ss_dst = (ss_out && e->fuse_norm && qmm3_reduce_can_emit_ss(epi, w.rows)) ? ss_out : nullptr;
-        const bool kept = keep != nullptr && epi == EPI_STORE && ss_dst == nullptr;
-        if (kept) {
-            keep->partial = q.partial;
-            keep->slices = p3.slices;
-            keep->plane = (long)M * w.rows;
-        } else {
-            int reduce_wg = 0;
-            if (launch_qmm3_reduce_bf16(q.partial, p3.slices, M, w.rows, epi, residual, out, q.prof, e->stream, ss_dst, &reduce_wg,
-                                        out_w ? (const uint16_t *)norm_out : nullptr, out_w, out_w_frag ? 1 : 0) != 0)
-                return fail(TL_ERR_UNSUPPORTED, "engine: skinny matmul reduction launch failed");
-            if (pc) prof_after(e, pc, kind, reduce_wg);
-        }
-        if (ss_emitted) *ss_emitted = ss_dst != nullptr;
-        if (ss_out_n) *ss_out_n = ss_dst != nullptr ? QM3_SS : 0;
-        TL_CHECK_LAUNCH("engine skinny matmul");
-        if (e->linfo) {
-            tl_linear_info &li = *e->linfo;
-            li.kernel = 2;
-            li.launches += (kept ? 1 : 2) + (pro == PRO_RMSNORM && !fused_norm ? 1 : 0);
-            li.rows_per_pass = M;
-            li.p[0] = p3.MB, li.p[1] = p3.persistent ? 0 : p3.TW, li.p[2] = p3.LM, li.p[3] = p3.slices;
-            li.p[4] = p3.persistent ? p3.grid_x : p3.grid_x * p3.slices;
-        }
-        return TL_OK;
-    }
-    if (e->force_linear == 2) return fail(TL_ERR_UNSUPPORTED, "engine: the skinny matmul does not cover this shape");
-    TL_REQUIRE(out_w == nullptr, "engine: no kernel leaves weighted rows for this shape");
-    if (M <= 8) return engine_qmv(e, w, a, out, M, pro, epi, norm_w, residual, pc, kind, ss_in_any, ss_in_n, ss_out, ss_out_n);
-    if (pro == PRO_RMSNORM) {
-        TL_TRY(tl_rms_norm(a, norm_w, e->xn, M, w.cols, c.rms_norm_eps, TL_BF16, e->stream));
-        in = e->xn;
-    }
-    if (e->linfo) e->linfo->kernel = 4;
-    return engine_gemm(e, w, in, out, M, epi, residual);
-}
-
 // Context split of the decode attention: power-of-two bucket >= context, fixed windows of C tokens per workgroup.
 struct SplitPlan {
     int n_splits, tokens_per_split;
@@ -1110,49 +663,28 @@ static void launch_attn_decode(const AttnDecodeArgs &a, dim3 grid, hipStream_t s
 // Can the wo GEMV of ONE decode row take the attention split partials instead of the merged row (qmv3.hip,
 // launch_qmv3_attn_merge_bf16: the instantiated plans)?
 static bool wo_merge_applicable(const tl_engine *e, const tl_w4 &wo, int batch, const SplitPlan &sp) {
-    if (!e->wo_merges_attn || batch != 1 || e->force_linear != 0) return false;
+    if (!e->wo_merges_attn || batch != 1 || e->lin.force_linear != 0) return false;
     if (sp.n_splits != 2 && sp.n_splits != 4 && sp.n_splits != 8) return false;
-    if (e->cfg.head_dim != 128 || wo.cols != e->cfg.num_heads * 128 || e->tiled.count(wo.weight_dev) == 0) return false;
-    if (1 >= e->qmm3_min_rows && e->use_qmm3) return false;  // a single row would not take the GEMV
+    if (e->cfg.head_dim != 128 || wo.cols != e->cfg.num_heads * 128 || e->lin.tiled.count(wo.weight_dev) == 0) return false;
+    if (1 >= e->lin.qmm3_min_rows && e->lin.use_qmm3) return false;  // a single row would not take the GEMV
     const Qmv3Plan pl = qmv3_plan(1, wo.cols, wo.rows);
     const bool shape = (pl.KS == 2 && pl.CW == 4) || (pl.KS == 4 && pl.CW == 4) || (pl.KS == 8 && pl.CW == 8);
     return pl.ok && pl.MR == 1 && shape && wo.cols / 8 <= 2 * pl.CW * 64;
 }
-// h = x + merge(attention partials) @ wo^T for one row.
-static int engine_wo_merge(tl_engine *e, const tl_w4 &wo, const uint16_t *residual, uint16_t *out, int n_splits, ProfCtx *pc,
-                           float *ss_out = nullptr, int *ss_out_n = nullptr, const void *norm_out = nullptr, uint16_t *out_w = nullptr) {
-    if (ss_out_n) *ss_out_n = 0;
-    const auto tiled = e->tiled.find(wo.weight_dev);
-    Qmv3Args a3{};
-    a3.wt = tiled->second.wt;
-    a3.sbt = tiled->second.sbt;
-    a3.a = nullptr;
-    a3.out = out;
-    a3.residual = residual;
-    a3.eps = e->cfg.rms_norm_eps;
-    a3.M = 1;
-    a3.N = wo.cols;
-    a3.K = wo.rows;
-    a3.prof = pc ? pc->buf : nullptr;
-    a3.merge_ws = e->attn_ws;
-    if (ss_out && e->gemv_producer_ss && wo.rows % 16 == 0) {
-        a3.ss_out = ss_out;
-        if (ss_out_n) *ss_out_n = wo.rows / 16;
-    }
-    if (out_w) a3.norm_out = (const uint16_t *)norm_out, a3.out_w = out_w;
-    if (launch_qmv3_attn_merge_bf16(a3, n_splits, e->stream) != 0)
-        return fail(TL_ERR_UNSUPPORTED, "engine: no wo GEMV that merges the attention partials for this shape");
-    if (pc) prof_after(e, pc, 1, qmv3_plan(1, wo.cols, wo.rows).blocks);
-    TL_CHECK_LAUNCH("engine wo gemv with merge");
-    return TL_OK;
-}
 
-// q/k-norm + RoPE + KV append + decode attention of one layer over slots [0, batch) (+ the merge launch when the context
-// is split).  qkv [batch, (Hq + 2 Hkv) D] -> out [batch, Hq D]; partials in e->attn_ws.
-static int engine_attention(tl_engine *e, const uint16_t *qkv, const void *q_norm, const void *k_norm, uint16_t *key_pages,
-                            uint16_t *value_pages, uint16_t *out, int batch, const SplitPlan &sp, ProfCtx *pc,
-                            const KeptPartials *qkv_parts = nullptr, const tl_w4 *merging_wo = nullptr, bool *merge_left = nullptr,
-                            float *key_scales = nullptr, float *value_scales = nullptr) {
+// One layer's decode attention: qkv [batch, (Hq + 2 Hkv) D] -> out [batch, Hq D] over slots [0, batch), split partials in ws.
+struct AttnCall {
+    const uint16_t *qkv = nullptr;
+    const void *q_norm = nullptr, *k_norm = nullptr;
+    uint16_t *key_pages = nullptr, *value_pages = nullptr;
+    float *key_scales = nullptr, *value_scales = nullptr;  // FP8 pages (kv8.h)
+    uint16_t *out = nullptr;
+    float *ws = nullptr;
+    KeptPartials qkv_parts;                   // where the qkv projection left its slice planes: the kernel adds them itself
+    const tl_w4 *merging_wo = nullptr;        // the wo projection behind it, where its GEMV may merge the split partials (wo_merge_applicable)
+};
+// q/k-norm + RoPE + KV append + decode attention of one layer (+ the merge launch when the context is split and *merge_left stays false)
+static int engine_attention(tl_engine *e, const AttnCall &t, int batch, const SplitPlan &sp, ProfCtx *pc, bool *merge_left = nullptr) {
     if (merge_left) *merge_left = false;
     const tl_engine_config &c = e->cfg;
     const int D = c.head_dim;
@@ -1160,18 +692,18 @@ static int engine_attention(tl_engine *e, const uint16_t *qkv, const void *q_nor
     const int rep = c.num_heads / c.num_kv_heads;
     const int chunks = (rep + sp.rq - 1) / sp.rq;
     AttnDecodeArgs a{};
-    a.qkv = qkv;
-    a.q_norm_w = (const uint16_t *)q_norm;
-    a.k_norm_w = (const uint16_t *)k_norm;
-    a.key_pages = key_pages;
-    a.value_pages = value_pages;
-    a.key_scales = key_scales;
-    a.value_scales = value_scales;
-    TL_REQUIRE(key_scales == nullptr || D == 128, "engine: FP8 pages need head_dim 128");
+    a.qkv = t.qkv;
+    a.q_norm_w = (const uint16_t *)t.q_norm;
+    a.k_norm_w = (const uint16_t *)t.k_norm;
+    a.key_pages = t.key_pages;
+    a.value_pages = t.value_pages;
+    a.key_scales = t.key_scales;
+    a.value_scales = t.value_scales;
+    TL_REQUIRE(t.key_scales == nullptr || D == 128, "engine: FP8 pages need head_dim 128");
     a.block_table = e->block_table;
     a.context_lens = e->context_lens;
-    a.out = out;
-    a.ws = e->attn_ws;
+    a.out = t.out;
+    a.ws = t.ws;
     a.page_size = c.page_size;
     a.max_pages = c.max_pages_per_seq;
     a.num_heads = c.num_heads;
@@ -1190,11 +722,11 @@ static int engine_attention(tl_engine *e, const uint16_t *qkv, const void *q_nor
         if ((1 << sh) == c.page_size) a.page_shift = sh;
     a.rope_cur = e->rope_cur;
     a.prof = pc ? pc->buf : nullptr;
-    if (qkv_parts && qkv_parts->partial) {
+    if (t.qkv_parts.partial) {
         TL_REQUIRE(attn_takes_qkv_partials(D, sp.rq), "engine: this decode-attention plan does not read qkv slice partials");
-        a.qkv_partial = qkv_parts->partial;
-        a.qkv_slices = qkv_parts->slices;
-        a.qkv_plane = qkv_parts->plane;
+        a.qkv_partial = t.qkv_parts.partial;
+        a.qkv_slices = t.qkv_parts.slices;
+        a.qkv_plane = t.qkv_parts.plane;
     }
     TL_REQUIRE((size_t)batch * c.num_heads * n_splits * (D + ATTN_WS_PAD) * sizeof(float) <= e->attn_ws_bytes || n_splits == 1,
                "engine: attention workspace too small for this split plan");
@@ -1205,9 +737,9 @@ static int engine_attention(tl_engine *e, const uint16_t *qkv, const void *q_nor
         case 32: launch_attn_decode<2>(a, grid, e->stream, sp.rq, false); break;
         default: return fail(TL_ERR_UNSUPPORTED, "engine: head_dim must be 32, 64 or 128");
     }
-    if (pc) prof_after(e, pc, 5, (int)(grid.x * grid.y * grid.z));
+    if (pc) prof_after(pc, 5, (int)(grid.x * grid.y * grid.z));
     // the consumer (the wo GEMV of a single row) merges the partials itself: no merge launch, `out` is not written
-    const bool leave_merge = merging_wo != nullptr && merge_left != nullptr && wo_merge_applicable(e, *merging_wo, batch, sp);
+    const bool leave_merge = t.merging_wo != nullptr && merge_left != nullptr && wo_merge_applicable(e, *t.merging_wo, batch, sp);
     if (leave_merge) *merge_left = true;
     e->last_attn_launches = 1 + ((n_splits > 1 && !leave_merge) ? 1 : 0);
     if (n_splits > 1 && !leave_merge) {
@@ -1215,16 +747,16 @@ static int engine_attention(tl_engine *e, const uint16_t *qkv, const void *q_nor
         prof_t *pb = pc ? pc->buf : nullptr;
         int merge_wg = batch * c.num_heads;
         switch (n_splits) {
-            case 2: hipLaunchKernelGGL(attn_merge_kernel<2>, mg, mb, 0, e->stream, e->attn_ws, out, D, pb); break;
-            case 4: hipLaunchKernelGGL(attn_merge_kernel<4>, mg, mb, 0, e->stream, e->attn_ws, out, D, pb); break;
-            case 8: hipLaunchKernelGGL(attn_merge_kernel<8>, mg, mb, 0, e->stream, e->attn_ws, out, D, pb); break;
+            case 2: hipLaunchKernelGGL(attn_merge_kernel<2>, mg, mb, 0, e->stream, t.ws, t.out, D, pb); break;
+            case 4: hipLaunchKernelGGL(attn_merge_kernel<4>, mg, mb, 0, e->stream, t.ws, t.out, D, pb); break;
+            case 8: hipLaunchKernelGGL(attn_merge_kernel<8>, mg, mb, 0, e->stream, t.ws, t.out, D, pb); break;
             default:  // 16 and more splits: a row's partials spread over D / 32 workgroups x 8 split groups
                 merge_wg *= (D + 31) / 32;
-                hipLaunchKernelGGL(attn_merge_cols_kernel, dim3(batch * c.num_heads, (D + 31) / 32), dim3(256), 0, e->stream, e->attn_ws,
-                                   out, D, n_splits, pb);
+                hipLaunchKernelGGL(attn_merge_cols_kernel, dim3(batch * c.num_heads, (D + 31) / 32), dim3(256), 0, e->stream, t.ws,
+                                   t.out, D, n_splits, pb);
                 break;
         }
-        if (pc) prof_after(e, pc, 6, merge_wg);
+        if (pc) prof_after(pc, 6, merge_wg);
     }
     TL_CHECK_LAUNCH("engine attention");
     return TL_OK;
@@ -1237,7 +769,7 @@ static int engine_moe_mlp(tl_engine *e, int l, const uint16_t *xn, const uint16_
     const int D = e->cfg.hidden_size, E = m.num_experts, k = m.experts_per_token, I = m.intermediate_size;
     TL_REQUIRE(e->moe_ws != nullptr && rows <= e->rows_cap && (long)rows * k <= 65535, "engine: MoE workspace missing or too many expert rows");
     // router logits [rows, E] through the reference-semantics matmul (quantized_linear of the router, moe.py:44)
-    TL_TRY(engine_qmm(e, m.router, xn, e->moe_logits, rows));
+    TL_TRY(engine_qmm(e->lin, m.router, xn, e->moe_logits, rows));
     hipLaunchKernelGGL(moe_route_kernel, dim3(rows), dim3(256), 0, e->stream, e->moe_logits, E, k, m.norm_topk_prob, e->moe_ids, e->moe_scores);
     const int er = rows * k;  // expert rows: token-major, the token's top_k experts in descending probability
     TL_TRY(gather_qmv_bf16(m.gate_scales_dev, m.gate_biases_dev, xn, m.gate_dev, e->moe_ids, e->moe_gate, er, D, I, E, k, e->stream));
@@ -1251,213 +783,144 @@ static int engine_moe_mlp(tl_engine *e, int l, const uint16_t *xn, const uint16_
     return TL_OK;
 }
 
+// The routes of one decode step over `batch` rows, decided before its first launch: every layer's (plan_layer), the lm_head's, the row
+// order of the weighted hand-over, and whose hand-over buffers the step uses.
+struct StepRoute {
+    std::vector<LayerRoute> layers;
+    bool frag = false;   // rows_travel_in_fragment_order
+    bool head6 = false;  // lm_head on the register-resident matmul wherever the last layer leaves weighted rows
+    // per-layer hand-over buffers: the fused-GEMV rows of a dense model whose attention partials fit the per-layer workspace (per_layer),
+    // or the rows of the batched-matmul step (5 .. 64) when every layer hands over inside its own buffers and slice planes (per_layer_b)
+    bool per_layer = false, per_layer_b = false;
+};
+static StepRoute plan_step(const tl_engine *e, int batch, const SplitPlan &sp) {
+    const LinearCtx &ctx = e->lin;
+    StepRoute s;
+    s.frag = rows_travel_in_fragment_order(ctx, e->layers[0], batch);
+    s.head6 = qmm6_takes(ctx, e->head(), batch);
+    const bool ws_fits = sp.n_splits == 1 || (size_t)batch * e->cfg.num_heads * sp.n_splits * (e->cfg.head_dim + ATTN_WS_PAD) * sizeof(float) <= e->layer_ws_bytes;
+    const bool own_buffers = e->layer_act_rows > 0 && batch <= e->layer_act_rows && ws_fits;
+    s.per_layer = own_buffers && gemv_takes_rows(ctx, batch);
+    s.per_layer_b = own_buffers && !gemv_takes_rows(ctx, batch) && ctx.force_linear == 0 && s.head6;
+    for (int l = 0; l < e->cfg.num_layers; ++l) {
+        s.layers.push_back(plan_layer(ctx, e->layers[l], batch, e->is_moe(l)));
+        if (e->is_moe(l)) s.per_layer = false;  // a MoE layer reads and writes the shared buffers
+        if (!s.layers.back().batched_written_once()) s.per_layer_b = false;
+    }
+    return s;
+}
+
 // One fused decode step over slots [0, batch).
 static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, ProfCtx *pc = nullptr) {
     const tl_engine_config &c = e->cfg;
+    LinearCtx &ctx = e->lin;
+    const StepRoute route = plan_step(e, batch, sp);
+    // only a step whose hand-overs all live at addresses written once per step may be replayed without cache maintenance (tl_engine_decode)
+    e->step_written_once = route.per_layer || route.per_layer_b;
     // x enters the step from the embedding gather (embed_slots_kernel / the previous step's step_end_kernel), which leaves the
     // per-row partial sums of squares in ss_x; every slice reduction that rewrites x or h refreshes them (or says it did not)
-    int x_ss = QM3_SS;  // partials per row in ss_x (0 = none): QM3_SS from the embedding kernels, then whatever the last writer of x left
-    // 5 .. 64 rows on the register-resident matmul: xn holds x weighted by the NEXT RMSNorm's weight whenever xw is set (written by
+    int x_ss = QM3_SS;  // partials per row in ssx_cur (0 = none): QM3_SS from the embedding kernels, then whatever the last writer of x left
+    // 5 .. 64 rows on the register-resident matmul: xw_cur holds x weighted by the NEXT RMSNorm's weight whenever xw is set (written by
     // the w_down epilogue of the previous layer, or by one pointwise launch ahead of layer 0)
     bool xw = false;
-    // where the residual stream and its sums of squares stand (the shared buffers, or the last layer's own in per-layer mode)
-    uint16_t *x_cur = e->x;
+    // where the residual stream, its weighted copy and its sums of squares stand (the shared buffers, or the last layer's own in a per-layer mode)
+    uint16_t *x_cur = e->x, *xw_cur = e->xn;
     float *ssx_cur = e->ss_x;
-    // per-layer hand-over buffers: the fused-GEMV rows of a dense model whose attention partials fit the per-layer workspace
-    const bool ws_fits = sp.n_splits == 1 || (size_t)batch * c.num_heads * sp.n_splits * (c.head_dim + ATTN_WS_PAD) * sizeof(float) <= e->layer_ws_bytes;
-    bool per_layer = e->layer_act_rows > 0 && batch <= e->layer_act_rows && gemv_takes_rows(e, batch) && ws_fits;
-    // ... and the rows of the batched-matmul step (5 .. 64): every projection on the register-resident or the K-sliced matmul with its
-    // hand-over through weighted rows (the branch below), slice planes inside the per-layer ones
-    bool per_layer_b = e->layer_act_rows > 0 && batch <= e->layer_act_rows && !gemv_takes_rows(e, batch) && ws_fits && e->force_linear == 0;
+    // a layer's hand-over buffers: the shared ones, or -- the AQL route's per-layer modes -- its own (written once per step)
+    tl_engine::LayerAct shared{};
+    shared.x_out = e->x, shared.h = e->h, shared.xn = e->xn, shared.xw = e->xn, shared.qkv = e->qkv, shared.attn = e->attn, shared.act = e->act;
+    shared.ss_x_out = e->ss_x, shared.ss_h = e->ss_h, shared.attn_ws = e->attn_ws;  // (no slice planes: the context's workspace)
     for (int l = 0; l < c.num_layers; ++l) {
-        if (e->is_moe(l)) per_layer = per_layer_b = false;
         const tl_layer_weights &w = e->layers[l];
-        if (per_layer_b) {  // every condition of the batched branch below, known ahead: no layer may fall out of it half way through a step
-            const bool wo_ok = (qmm6_takes(e, w.wo, batch) && qmm3_takes_ss(w.wo.rows / 16)) ||
-                               (takes_skinny_matmul(e, w.wo, batch) && e->fuse_norm && qmm3_reduce_can_emit_ss(EPI_RESIDUAL, w.wo.rows));
-            const bool down_ok = (takes_skinny_matmul(e, w.wdown, batch) && e->fuse_norm && qmm3_reduce_can_emit_ss(EPI_RESIDUAL, w.wdown.rows)) ||
-                                 (qmm6_takes(e, w.wdown, batch) && qmm3_takes_ss(w.wdown.rows / 16));
-            if (!(w.wgu.weight_dev && qmm6_takes(e, w.wqkv, batch) && qmm6_takes(e, w.wgu, batch) && qmm6_takes(e, e->head(), batch) && wo_ok && down_ok))
-                per_layer_b = false;
+        const LayerRoute &rt = route.layers[l];
+        // The one input of a route that is not known ahead: are the row's sums of squares there when the layer starts?  In a dense model
+        // they are -- QM3_SS per row from the embedding kernels, QM3_SS or rows / 16 from a w_down that leaves weighted rows -- so this cannot
+        // fire there; should it ever, the step must not be replayed as "written once" over buffers written several times
+        const bool batched = rt.batched && x_ss > 0 && qmm3_takes_ss(x_ss);
+        TL_REQUIRE(batched || !route.per_layer_b, "engine: a layer fell out of the batched branch of a step planned on the per-layer buffers");
+        const tl_engine::LayerAct &b = (batched ? route.per_layer_b : route.per_layer) ? e->layer_act[l] : shared;
+        ProjResult r;
+        if (batched && rt.qkv6) {
+            if (!xw) {
+                const long n8 = (long)batch * c.hidden_size / 8;
+                hipLaunchKernelGGL(weight_rows_kernel, dim3(ceil_div(n8, 256)), dim3(256), 0, e->stream, x_cur, (const uint16_t *)w.input_norm_dev,
+                                   e->xn, n8, c.hidden_size / 8, route.frag ? 1 : 0);
+                xw_cur = e->xn;
+            }
+            Proj p = proj(w.wqkv, xw_cur, b.qkv, batch);
+            p.ss_in = ssx_cur, p.ss_in_n = x_ss, p.frag = route.frag;
+            TL_TRY(engine_qmm6(ctx, p, pc));
+        } else {
+            Proj p = proj(w.wqkv, x_cur, b.qkv, batch);
+            p.pro = PRO_RMSNORM, p.norm_w = w.input_norm_dev, p.ss_in = x_ss ? ssx_cur : nullptr, p.ss_in_n = x_ss;
+            p.keep = e->attn_qkv_partials && attn_takes_qkv_partials(c.head_dim, sp.rq);
+            TL_TRY(engine_linear(ctx, p, pc, &r));
         }
-    }
-    // only a step whose hand-overs all live at addresses written once per step may be replayed without cache maintenance (tl_engine_decode)
-    e->step_written_once = per_layer || per_layer_b;
-    // the residual stream of the batched branch: where x, x weighted for the next RMSNorm and its sums of squares stand
-    uint16_t *bx = e->x, *bxw = e->xn;
-    float *bssx = e->ss_x;
-    for (int l = 0; l < c.num_layers; ++l) {
-        const tl_layer_weights &w = e->layers[l];
-        // the sliced matmul as the producer of weighted rows (its reduction writes them): wo here, w_down below
-        auto sliced_leaves_weighted = [&](const tl_w4 &m) {  // (the router's own predicate + what its reduction needs to emit the hand-over)
-            return takes_skinny_matmul(e, m, batch) && e->fuse_norm && qmm3_reduce_can_emit_ss(EPI_RESIDUAL, m.rows);
-        };
-        const bool wo6_ok = !e->is_moe(l) && qmm6_takes(e, w.wo, batch) && qmm3_takes_ss(w.wo.rows / 16);
-        if (!e->is_moe(l) && w.wgu.weight_dev != nullptr && qmm6_takes(e, w.wgu, batch) && x_ss > 0 && qmm3_takes_ss(x_ss) &&
-            (wo6_ok || sliced_leaves_weighted(w.wo))) {
-            // gate|up and lm_head are the register-resident kernel's at every row count; qkv and wo where it measured ahead on a fast AND
-            // on a slow box (profiles/r04_labs/README.md: its per-workgroup copy of the rows rides the L2 -> CU path, the part of the chip
-            // that differs most between boxes): wo up to 16 and from 33 rows (qkv: below).  Both kinds of producer leave x / h weighted AND plain.
-            // the weighted rows travel in fragment order from 9 rows (same-box A/B, profiles/r04_labs/README.md: 16 / 32 / 64 sequences
-            // -1.5 / -4 / -1.3 % per step; at 8 sequences +2 %: row-major there)
-            // (round 6: from 5 rows wherever the row-streaming matmul takes the layer's gate|up -- it reads nothing else)
-            const bool frag = rows_travel_in_fragment_order(e, batch);
-            // qkv on this kernel at every row count since round 5 (rows in fragment order from 9 rows): same-box A/B at 128-token contexts,
-            // two alternating rounds, 24 / 32 / 48 / 64 sequences 1.91 / 1.95 / 2.56 / 2.69 -> 1.87 / 1.89 / 2.50 / 2.59 ms per step
-            // (profiles/r05_labs/batched_qkv_on_qmm6_ab.log; round 4 had measured -1 ... -2.9 % on a fast box and left 17-64 rows on the sliced
-            // matmul, whose slices the attention kernel adds -- that route is now the one behind option "qmm6" = 0 only)
-            const bool qkv6 = qmm6_takes(e, w.wqkv, batch);
-            // wo on the register-resident kernel at EVERY row count (round 6: its planner now deals 16-row blocks to more workgroups where the rows are long --
-            // 17-32 rows 6.9 us against 8.4-9.1 for the sliced matmul + reduction that took them until then, 33-48 rows 10.1 -> 7.1; qmm6.h, qmm6_plan)
-            const bool wo6 = wo6_ok;
-            // this layer's hand-over buffers: the shared ones, or -- the AQL route's per-layer mode -- its own (written once per step)
-            uint16_t *hb = e->h, *hwb = e->xn, *qkvb = e->qkv, *attnb = e->attn, *actb = e->act, *x_out = e->x, *xw_out = e->xn;
-            float *sshb = e->ss_h, *ssx_out = e->ss_x;
-            float *const ws_shared = e->attn_ws;
-            if (per_layer_b) {
-                const tl_engine::LayerAct &la = e->layer_act[l];
-                hb = la.h, hwb = la.xn, qkvb = la.qkv, attnb = la.attn, actb = la.act, x_out = la.x_out, xw_out = la.xw, sshb = la.ss_h, ssx_out = la.ss_x_out;
-                e->attn_ws = la.attn_ws;  // engine_attention reads the member
-            }
-            auto planes = [&](int which) {  // the K-sliced matmul's fp32 planes of the NEXT engine_linear call
-                e->planes_now = per_layer_b ? e->layer_act[l].planes[which] : nullptr;
-                e->planes_now_bytes = per_layer_b ? e->layer_plane_bytes[which] : 0;
-            };
-            auto run_layer_b = [&]() -> int {
-            KeptPartials parts;
-            if (qkv6) {
-                if (!xw) {
-                    const long n8 = (long)batch * c.hidden_size / 8;
-                    hipLaunchKernelGGL(weight_rows_kernel, dim3(ceil_div(n8, 256)), dim3(256), 0, e->stream, bx, (const uint16_t *)w.input_norm_dev,
-                                       e->xn, n8, c.hidden_size / 8, frag ? 1 : 0);
-                    bxw = e->xn;
-                }
-                TL_TRY(engine_qmm6(e, w.wqkv, bxw, qkvb, batch, EPI_STORE, nullptr, pc, 0, bssx, x_ss, nullptr, nullptr, nullptr, nullptr, frag));
-            } else {
-                const bool keep_qkv = e->attn_qkv_partials && attn_takes_qkv_partials(c.head_dim, sp.rq);
-                TL_TRY(engine_linear(e, w.wqkv, bx, qkvb, batch, PRO_RMSNORM, EPI_STORE, w.input_norm_dev, nullptr, pc, 0, bssx, nullptr, nullptr,
-                                     keep_qkv ? &parts : nullptr, x_ss));
-            }
-            bool merged = false;
-            TL_TRY(engine_attention(e, qkvb, w.q_norm_dev, w.k_norm_dev, e->layer_k(l), e->layer_v(l), attnb, batch, sp, pc, &parts, &w.wo, &merged, e->layer_ks(l), e->layer_vs(l)));
-            TL_REQUIRE(!merged, "engine: a batched step left its attention windows unmerged");
-            int h_ss = 0;
-            if (wo6) TL_TRY(engine_qmm6(e, w.wo, attnb, hb, batch, EPI_RESIDUAL, bx, pc, 1, nullptr, 0, sshb, &h_ss, w.post_norm_dev, hwb, frag));
-            else {
-                planes(0);
-                TL_TRY(engine_linear(e, w.wo, attnb, hb, batch, PRO_NONE, EPI_RESIDUAL, nullptr, bx, pc, 1, nullptr, sshb, nullptr, nullptr, QM3_SS, &h_ss,
-                                     w.post_norm_dev, hwb, frag));
-            }
-            TL_REQUIRE(h_ss > 0 && qmm3_takes_ss(h_ss), "engine: the wo projection left no sums of squares for its weighted rows");
-            TL_TRY(engine_qmm6(e, w.wgu, hwb, actb, batch, EPI_SWIGLU, nullptr, pc, 2, sshb, h_ss, nullptr, nullptr, nullptr, nullptr, frag));
-            // the rows w_down leaves are weighted for their next reader: the next layer's input norm, or the final norm ahead of lm_head
-            const void *next_norm = l + 1 < c.num_layers ? e->layers[l + 1].input_norm_dev : e->final_norm;
-            // w_down: 76 groups against 160 tiles -- every workgroup of the register-resident kernel would pull 311 KB of rows for ONE tile
-            // (measured 9.0 us at 8 rows, 18.9 at 64, against 6.5 / 13.0 for the K-sliced matmul + reduction): the sliced kernel keeps
-            // it wherever its plan exists, and its reduction leaves the weighted rows
-            planes(1);
-            if (sliced_leaves_weighted(w.wdown)) {
-                TL_TRY(engine_linear(e, w.wdown, actb, x_out, batch, PRO_NONE, EPI_RESIDUAL, nullptr, hb, pc, 3, nullptr, ssx_out, nullptr, nullptr,
-                                     QM3_SS, &x_ss, next_norm, xw_out, frag));
-                xw = x_ss > 0;
-            } else if (qmm6_takes(e, w.wdown, batch) && qmm3_takes_ss(w.wdown.rows / 16)) {
-                TL_TRY(engine_qmm6(e, w.wdown, actb, x_out, batch, EPI_RESIDUAL, hb, pc, 3, nullptr, 0, ssx_out, &x_ss, next_norm, xw_out, frag));
-                xw = true;
-            } else {
-                TL_TRY(engine_linear(e, w.wdown, actb, x_out, batch, PRO_NONE, EPI_RESIDUAL, nullptr, hb, pc, 3, nullptr, ssx_out, nullptr, nullptr, QM3_SS, &x_ss));
-                xw = false;
-            }
-            return TL_OK;
-            };
-            const int rc_b = run_layer_b();
-            e->attn_ws = ws_shared;
-            e->planes_now = nullptr, e->planes_now_bytes = 0;
-            TL_TRY(rc_b);
-            bx = x_out, bxw = xw_out, bssx = ssx_out;
-            x_cur = bx, ssx_cur = bssx;
+        xw = false;
+        AttnCall at{};
+        at.qkv = b.qkv, at.q_norm = w.q_norm_dev, at.k_norm = w.k_norm_dev, at.key_pages = e->layer_k(l), at.value_pages = e->layer_v(l);
+        at.key_scales = e->layer_ks(l), at.value_scales = e->layer_vs(l), at.out = b.attn, at.ws = b.attn_ws;
+        at.qkv_parts = r.kept, at.merging_wo = &w.wo;
+        bool merge_left = false;  // the wo GEMV of one row merges the attention windows itself where engine_attention leaves them to it
+        TL_TRY(engine_attention(e, at, batch, sp, pc, &merge_left));
+        TL_REQUIRE(!(batched && merge_left), "engine: a batched step left its attention windows unmerged");
+        Proj po = proj(w.wo, b.attn, b.h, batch);
+        po.epi = EPI_RESIDUAL, po.residual = x_cur, po.kind = 1;
+        if (merge_left) po.pro = PRO_ATTN_MERGE, po.merge_ws = b.attn_ws, po.n_splits = sp.n_splits;
+        x_cur = b.x_out, ssx_cur = b.ss_x_out;  // where the layer leaves the residual stream
+        if (e->is_moe(l)) {  // wo + residual, then the MoE MLP as its own launches (no producer-side sums for the next layer)
+            TL_TRY(engine_linear(ctx, po, pc));
+            TL_TRY(tl_rms_norm(b.h, w.post_norm_dev, b.xn, batch, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
+            TL_TRY(engine_moe_mlp(e, l, b.xn, b.h, b.x_out, batch, pc));
+            x_ss = 0;
             continue;
         }
-        // (a layer outside the batched branch reads and writes the shared buffers: a per-layer batched step has none -- per_layer_b above.
-        // The pre-check restates the branch's conditions; should the two ever diverge -- the row's sums of squares missing, say -- the step
-        // must not be captured as "written once": it would be replayed without cache maintenance over buffers written several times)
-        TL_REQUIRE(!per_layer_b, "engine: a layer fell out of the batched branch of a step planned on the per-layer buffers");
-        xw = false;
-        // this layer's hand-over buffers: the shared ones, or -- per-layer mode -- its own (written once per step)
-        uint16_t *x_in = x_cur, *x_out = e->x, *hb = e->h, *xnb = e->xn, *qkvb = e->qkv, *attnb = e->attn, *actb = e->act;
-        float *ssx_in = ssx_cur, *ssx_out = e->ss_x, *sshb = e->ss_h;
-        float *const ws_shared = e->attn_ws;
-        if (per_layer) {
-            const tl_engine::LayerAct &la = e->layer_act[l];
-            x_out = la.x_out, hb = la.h, xnb = la.xn, qkvb = la.qkv, attnb = la.attn, actb = la.act, ssx_out = la.ss_x_out, sshb = la.ss_h;
-            e->attn_ws = la.attn_ws;  // engine_attention / engine_wo_merge read the member
-        }
-        auto restore_ws = [&]() { e->attn_ws = ws_shared; };
-        auto run_layer = [&]() -> int {
-        KeptPartials qkv_parts;
-        const bool keep_qkv = e->attn_qkv_partials && attn_takes_qkv_partials(c.head_dim, sp.rq);
-        TL_TRY(engine_linear(e, w.wqkv, x_in, qkvb, batch, PRO_RMSNORM, EPI_STORE, w.input_norm_dev, nullptr, pc, 0,
-                             x_ss ? ssx_in : nullptr, nullptr, nullptr, keep_qkv ? &qkv_parts : nullptr, x_ss));
-        bool merge_left = false;
-        TL_TRY(engine_attention(e, qkvb, w.q_norm_dev, w.k_norm_dev, e->layer_k(l), e->layer_v(l), attnb, batch, sp, pc, &qkv_parts,
-                                &w.wo, &merge_left, e->layer_ks(l), e->layer_vs(l)));
-        int h_ss = 0;
-        if (e->is_moe(l)) {  // wo + residual, then the MoE MLP as its own launches (no producer-side sums for the next layer)
-            if (merge_left) TL_TRY(engine_wo_merge(e, w.wo, x_in, hb, sp.n_splits, pc, nullptr, nullptr));
-            else TL_TRY(engine_linear(e, w.wo, attnb, hb, batch, PRO_NONE, EPI_RESIDUAL, nullptr, x_in, pc, 1));
-            TL_TRY(tl_rms_norm(hb, w.post_norm_dev, xnb, batch, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
-            TL_TRY(engine_moe_mlp(e, l, xnb, hb, x_out, batch, pc));
-            x_ss = 0;
-            return TL_OK;
-        }
         TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
-        // h leaves the wo GEMV twice when the gate|up GEMV can take it weighted: as the residual stream and, in xn, times the
-        // post-attention norm weight
-        const bool weighted = weighted_rows_apply(e, w.wo, w.wgu, batch);
-        uint16_t *hw = weighted ? xnb : nullptr;
-        if (merge_left) TL_TRY(engine_wo_merge(e, w.wo, x_in, hb, sp.n_splits, pc, sshb, &h_ss, w.post_norm_dev, hw));
-        else TL_TRY(engine_linear(e, w.wo, attnb, hb, batch, PRO_NONE, EPI_RESIDUAL, nullptr, x_in, pc, 1, nullptr, sshb, nullptr, nullptr, QM3_SS, &h_ss, w.post_norm_dev, hw));
-        if (weighted) {
-            TL_REQUIRE(h_ss > 0, "engine: the wo GEMV left no sums of squares for its weighted rows");
-            TL_TRY(engine_linear(e, w.wgu, xnb, actb, batch, PRO_RMS_WEIGHTED, EPI_SWIGLU, nullptr, nullptr, pc, 2, sshb, nullptr, nullptr, nullptr, h_ss));
-        } else
-        TL_TRY(engine_linear(e, w.wgu, hb, actb, batch, PRO_RMSNORM, EPI_SWIGLU, w.post_norm_dev, nullptr, pc, 2,
-                             h_ss ? sshb : nullptr, nullptr, nullptr, nullptr, h_ss));
-        TL_TRY(engine_linear(e, w.wdown, actb, x_out, batch, PRO_NONE, EPI_RESIDUAL, nullptr, hb, pc, 3, nullptr, ssx_out, nullptr, nullptr, QM3_SS, &x_ss));
-        return TL_OK;
-        };
-        const int layer_rc = run_layer();
-        restore_ws();
-        TL_TRY(layer_rc);
-        x_cur = x_out;
-        ssx_cur = ssx_out;
+        // h leaves wo twice when gate|up can take it weighted (a batched layer; the GEMVs by weighted_rows_apply): as the residual
+        // stream and, in xn, times the post-attention norm weight
+        const bool h_weighted = batched || rt.gemv_weighted;
+        po.ss_out = b.ss_h, po.norm_out = w.post_norm_dev, po.out_w = h_weighted ? b.xn : nullptr, po.frag = batched && route.frag;
+        po.planes = b.planes[0], po.planes_bytes = e->layer_plane_bytes[0];
+        TL_TRY(batched && rt.wo6 ? engine_qmm6(ctx, po, pc, &r) : engine_linear(ctx, po, pc, &r));
+        const int h_ss = r.ss_n;
+        if (batched) TL_REQUIRE(h_ss > 0 && qmm3_takes_ss(h_ss), "engine: the wo projection left no sums of squares for its weighted rows");
+        else if (h_weighted) TL_REQUIRE(h_ss > 0, "engine: the wo GEMV left no sums of squares for its weighted rows");
+        Proj pg = proj(w.wgu, h_weighted ? b.xn : b.h, b.act, batch);
+        pg.epi = EPI_SWIGLU, pg.kind = 2, pg.ss_in = h_ss ? b.ss_h : nullptr, pg.ss_in_n = h_ss, pg.frag = batched && route.frag;
+        if (!batched) pg.pro = h_weighted ? PRO_RMS_WEIGHTED : PRO_RMSNORM, pg.norm_w = h_weighted ? nullptr : w.post_norm_dev;
+        TL_TRY(batched ? engine_qmm6(ctx, pg, pc) : engine_linear(ctx, pg, pc));
+        Proj pd = proj(w.wdown, b.act, b.x_out, batch);
+        pd.epi = EPI_RESIDUAL, pd.residual = b.h, pd.kind = 3, pd.ss_out = b.ss_x_out;
+        pd.planes = b.planes[1], pd.planes_bytes = e->layer_plane_bytes[1];
+        const bool x_weighted = batched && rt.down != LayerRoute::DOWN_ROUTER;
+        if (x_weighted) {
+            // the rows w_down leaves are weighted for their next reader: the next layer's input norm, or the final norm ahead of lm_head
+            pd.norm_out = l + 1 < c.num_layers ? e->layers[l + 1].input_norm_dev : e->final_norm;
+            pd.out_w = b.xw, pd.frag = route.frag;
+            xw_cur = b.xw;
+        }
+        TL_TRY(batched && rt.down == LayerRoute::DOWN_QMM6 ? engine_qmm6(ctx, pd, pc, &r) : engine_linear(ctx, pd, pc, &r));
+        x_ss = r.ss_n;
+        xw = x_weighted && x_ss > 0;
     }
-    e->want_tile_max = e->lm_tile_max_on;
-    e->tile_max_rows = 0;
-    const int head_rc = xw && qmm6_takes(e, e->head(), batch) && qmm3_takes_ss(x_ss)
-                            ? engine_qmm6(e, e->head(), bxw, e->logits, batch, EPI_STORE, nullptr, pc, 4, bssx, x_ss, nullptr, nullptr, nullptr, nullptr, rows_travel_in_fragment_order(e, batch))
-                            : engine_linear(e, e->head(), x_cur, e->logits, batch, PRO_RMSNORM, EPI_STORE, e->final_norm, nullptr, pc, 4,
-                                            x_ss ? ssx_cur : nullptr, nullptr, nullptr, nullptr, x_ss);
-    e->want_tile_max = false;
-    TL_TRY(head_rc);
-    const bool tile_max = e->tile_max_rows == batch;
+    ProjResult rh;
+    if (xw && route.head6 && qmm3_takes_ss(x_ss)) {
+        Proj ph = proj(e->head(), xw_cur, e->logits, batch);
+        ph.kind = 4, ph.ss_in = ssx_cur, ph.ss_in_n = x_ss, ph.frag = route.frag;
+        TL_TRY(engine_qmm6(ctx, ph, pc));
+    } else {
+        Proj ph = proj(e->head(), x_cur, e->logits, batch);
+        ph.pro = PRO_RMSNORM, ph.norm_w = e->final_norm, ph.kind = 4, ph.ss_in = x_ss ? ssx_cur : nullptr, ph.ss_in_n = x_ss;
+        ph.tile_max = e->lm_tile_max_on ? e->lm_tile_max : nullptr;
+        TL_TRY(engine_linear(ctx, ph, pc, &rh));
+    }
+    const bool tile_max = rh.maxima_rows == batch;
     const StepEndArgs s = step_end_args(e, e->logits, 0, 1, e->x, tile_max ? e->lm_tile_max : nullptr, tile_max ? e->head().rows / 16 : 0, e->ss_x,
                                         pc ? pc->buf : nullptr);
     launch_step_end(e, s, batch, step_samples(e, batch), step_logprobs(e, batch));
-    if (pc) prof_after(e, pc, 7, batch);
+    if (pc) prof_after(pc, 7, batch);
     TL_CHECK_LAUNCH("engine step end");
     return TL_OK;
-}
-
-static void prof_after(tl_engine *e, ProfCtx *pc, int kind, int n_wg) {
-    const int idx = (int)pc->kinds.size();
-    if (idx >= pc->cap) return;
-    hipLaunchKernelGGL(prof_reduce_kernel, dim3(1), dim3(1024), 0, e->stream, pc->buf, n_wg, pc->pairs + 2 * (size_t)idx);
-    pc->kinds.push_back(kind);
-    if (e->check.on)  // tl_engine_check_step: what this launch (and any unstamped one ahead of it) stored, against "written once per step"
-        for (int rg = 0; rg < 2; ++rg)
-            if (e->check.bytes[rg])
-                hipLaunchKernelGGL(written_once_check_kernel, dim3(1024), dim3(256), 0, e->stream, (const uint32_t *)e->check.region[rg], e->check.shadow[rg],
-                                   e->check.written[rg], e->check.bytes[rg] / 4, idx, rg, e->check.report);
 }
 
 // ---- page ownership: a page is shared by every sequence forked from a common prefix and returns to the free list when
@@ -1703,12 +1166,12 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->x = (uint16_t *)(A + o_x);
     e->h = (uint16_t *)(A + o_h);
     e->xn = (uint16_t *)(A + o_xn);
-    e->tmp = (uint16_t *)(A + o_tmp);
+    e->lin.tmp = (uint16_t *)(A + o_tmp);
     e->qkv = (uint16_t *)(A + o_qkv);
     e->q_t = (uint16_t *)(A + o_qt);
     e->attn_t = (uint16_t *)(A + o_at);
     e->attn = (uint16_t *)(A + o_attn);
-    e->gu = (uint16_t *)(A + o_gu);
+    e->lin.gu = (uint16_t *)(A + o_gu);
     e->act = (uint16_t *)(A + o_act);
     e->logits = (uint16_t *)(A + o_log);
     e->attn_ws = (float *)(A + o_ws);
@@ -1716,7 +1179,8 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->lm_tile_max = (f32x2 *)(A + o_tmax);
     e->ss_x = (float *)(A + o_ssx);
     e->ss_h = (float *)(A + o_ssh);
-    if (const char *q = getenv("TL_QMM3_MIN_M")) e->qmm3_min_rows = std::max(1, atoi(q));
+    e->lin.stream = e->stream, e->lin.rms_norm_eps = c.rms_norm_eps, e->lin.xn = e->xn;
+    e->lin.read_env();
     read_attention_knobs(e);
     // Decode steps replay as AQL packets on the engine's own HSA queue (aql.h) unless TL_AQL=0: the same captured step, without the
     // cache maintenance HIP puts between its launches (0.987 -> 0.929 ms per token at Qwen3-4B, logits bit-identical).  Where the route is
@@ -1760,7 +1224,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
                              b_ws = align_up((size_t)std::min(rows * 64, std::max(4 * 64, std::min(rows * 16, 1024))) * c.num_heads * ws_row * 4, 256);
                 // slice planes of the sliced matmuls a batched step can take (wo, w_down), the largest over 5 .. rows rows
                 size_t b_pl[2] = {0, 0};
-                for (int M = std::min(5, e->qmm3_min_rows); M <= rows; ++M) {
+                for (int M = std::min(5, e->lin.qmm3_min_rows); M <= rows; ++M) {
                     const Qmm3Plan pw = qmm3_plan(M, q_dim, c.hidden_size, -1), pd = qmm3_plan(M, c.intermediate_size, c.hidden_size, -1);
                     if (pw.ok) b_pl[0] = std::max(b_pl[0], align_up(pw.partial_bytes, 256));
                     if (pd.ok) b_pl[1] = std::max(b_pl[1], align_up(pd.partial_bytes, 256));
@@ -1818,8 +1282,8 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     // decode-path weight copies in the tiled MFMA layout
     {
         auto add_tiled = [&](const tl_w4 &w) -> bool {
-            if (w.rows % 16 != 0 || w.cols % 128 != 0 || e->tiled.count(w.weight_dev)) return true;
-            tl_engine::Tiled t;
+            if (w.rows % 16 != 0 || w.cols % 128 != 0 || e->lin.tiled.count(w.weight_dev)) return true;
+            TiledW4 t;
             const size_t wbytes = (size_t)w.rows * w.cols / 2, sbytes = (size_t)w.rows * (w.cols / 128) * 4;
             if (hipMalloc((void **)&t.wt, wbytes + 16384) != hipSuccess) return false;  // + slack: fixed-length wave slices
             if (hipMalloc((void **)&t.sbt, sbytes + 1024) != hipSuccess) {
@@ -1832,7 +1296,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
                 (void)hipFree(t.sbt);
                 return false;
             }
-            e->tiled[w.weight_dev] = t;
+            e->lin.tiled[w.weight_dev] = t;
             e->tiled_bytes += wbytes + sbytes;
             return true;
         };
@@ -1846,7 +1310,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     }
     if (c.max_prefill_rows >= GEMM8_MIN_ROWS) {  // the caller asked for chunks the plain bf16 GEMM takes: expand the layer matrices once
         auto add_bf16 = [&](const tl_w4 &w) -> bool {
-            if (!w.weight_dev || w.cols % 128 != 0 || e->bf16w.count(w.weight_dev) || !gemm8_applicable(c.max_prefill_rows, w.rows, w.cols)) return true;
+            if (!w.weight_dev || w.cols % 128 != 0 || e->lin.bf16w.count(w.weight_dev) || !gemm8_applicable(c.max_prefill_rows, w.rows, w.cols)) return true;
             uint16_t *wb = nullptr;
             const size_t bytes = (size_t)w.rows * w.cols * 2;
             if (hipMalloc((void **)&wb, bytes) != hipSuccess) return false;
@@ -1854,7 +1318,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
                 (void)hipFree(wb);
                 return false;
             }
-            e->bf16w[w.weight_dev] = wb;
+            e->lin.bf16w[w.weight_dev] = wb;
             e->bf16w_bytes += bytes;
             return true;
         };
@@ -1888,8 +1352,8 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
                 need = std::max(need, tl_quantized_matmul_workspace_bytes(M, w->cols, w->rows, TL_BF16, 1, 1));
         }
         if (need > 0) {
-            if (hipMalloc(&e->splitk_ws, need) != hipSuccess) return destroy_fail("engine_create: hipMalloc(matmul workspace) failed");
-            e->splitk_ws_bytes = need;
+            if (hipMalloc(&e->lin.splitk_ws, need) != hipSuccess) return destroy_fail("engine_create: hipMalloc(matmul workspace) failed");
+            e->lin.splitk_ws_bytes = need;
         }
     }
 
@@ -1927,7 +1391,7 @@ extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_wei
     TL_REQUIRE((long)e->rows_cap * w->experts_per_token <= 65535, "engine_set_moe_layer: max_prefill_rows x experts_per_token must stay below 65536 (one grouped launch)");
     // the router's matmul must fit the workspace sized at tl_engine_create (it does for every E <= the widest projection)
     for (int M : {1, 8, 9, e->rows_cap})
-        TL_REQUIRE(tl_quantized_matmul_workspace_bytes(std::min(M, e->rows_cap), c.hidden_size, w->num_experts, TL_BF16, 1, 1) <= e->splitk_ws_bytes,
+        TL_REQUIRE(tl_quantized_matmul_workspace_bytes(std::min(M, e->rows_cap), c.hidden_size, w->num_experts, TL_BF16, 1, 1) <= e->lin.splitk_ws_bytes,
                    "engine_set_moe_layer: the router matmul does not fit the engine's matmul workspace");
     const int k = std::max(e->moe_k_max, w->experts_per_token), E = std::max(e->moe_e_max, w->num_experts),
               I = std::max(e->moe_i_max, w->intermediate_size);
@@ -1978,14 +1442,14 @@ extern "C" int tl_engine_set_option(tl_engine *e, const char *name, int value) {
                "engine_set_option: call it before the first prefill / decode (captured steps hold the routes they were captured with)");
     const std::string n = name;
     const bool on = value != 0;
-    if (n == "qmm3") e->use_qmm3 = on;
-    else if (n == "qmm6") e->use_qmm6 = on;
-    else if (n == "qmm7") e->use_qmm7 = on;
+    if (n == "qmm3") e->lin.use_qmm3 = on;
+    else if (n == "qmm6") e->lin.use_qmm6 = on;
+    else if (n == "qmm7") e->lin.use_qmm7 = on;
     else if (n == "attn_qkv_partials") e->attn_qkv_partials = on;
     else if (n == "lmhead_tile_max") e->lm_tile_max_on = on;
-    else if (n == "gemm_fused_epilogue") e->gemm_fused_epilogue = on;
-    else if (n == "gemm8") e->use_gemm8 = on;
-    else if (n == "prefill_reduce_norm") e->fuse_reduce_norm = on;
+    else if (n == "gemm_fused_epilogue") e->lin.gemm_fused_epilogue = on;
+    else if (n == "gemm8") e->lin.use_gemm8 = on;
+    else if (n == "prefill_reduce_norm") e->lin.fuse_reduce_norm = on;
     else if (n == "aql_fences") e->aql_fences.inner_acquire = e->aql_fences.inner_release = on ? HSA_FENCE_SCOPE_AGENT : HSA_FENCE_SCOPE_NONE;
     else return fail(TL_ERR_INVALID, "engine_set_option: unknown option '" + n + "' (qmm3, qmm6, qmm7, gemm8, prefill_reduce_norm, attn_qkv_partials, lmhead_tile_max, gemm_fused_epilogue, aql_fences)");
     return TL_OK;
@@ -2008,14 +1472,14 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     if (e->vpool) (void)hipFree(e->vpool);
     if (e->kscale_pool) (void)hipFree(e->kscale_pool);
     if (e->vscale_pool) (void)hipFree(e->vscale_pool);
-    if (e->splitk_ws) (void)hipFree(e->splitk_ws);
+    if (e->lin.splitk_ws) (void)hipFree(e->lin.splitk_ws);
     if (e->rope_table) (void)hipFree(e->rope_table);
     if (e->rope_cur) (void)hipFree(e->rope_cur);
-    for (auto &kv : e->tiled) {
+    for (auto &kv : e->lin.tiled) {
         (void)hipFree(kv.second.wt);
         (void)hipFree(kv.second.sbt);
     }
-    for (auto &kv : e->bf16w) (void)hipFree(kv.second);
+    for (auto &kv : e->lin.bf16w) (void)hipFree(kv.second);
     if (e->owns_stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -2326,6 +1790,13 @@ struct PrefillSeq {
 // whatever could fail part way) and their tokens embedded, then every layer -- the projections once over all rows, RoPE / KV append, the
 // paged FlashAttention and the head transpose per sequence (each has its own block-table row, start position and causal mask) -- and
 // the slots' context lengths advanced.  The last layer's rows stay in x.  `packed` names the caller in the errors.
+// the lm_head over `rows` rows of the residual stream through the GEMV with the final RMSNorm fused (a prefill's last rows, verification)
+static int lm_head_rows(tl_engine *e, const uint16_t *x, int rows) {
+    Proj p = proj(e->head(), x, e->logits, rows);
+    p.pro = PRO_RMSNORM, p.norm_w = e->final_norm;
+    return engine_qmv(e->lin, p);
+}
+
 static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const int32_t *tokens, int total, bool packed) {
     const tl_engine_config &c = e->cfg;
     std::vector<std::pair<int32_t *, int32_t>> pk;
@@ -2348,7 +1819,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
         const tl_layer_weights &w = e->layers[l];
         if (!x_normed) TL_TRY(tl_rms_norm(e->x, w.input_norm_dev, e->xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
         x_normed = false;
-        TL_TRY(engine_gemm(e, w.wqkv, e->xn, e->qkv, total, EPI_STORE, nullptr));
+        TL_TRY(engine_gemm(e->lin, proj(w.wqkv, e->xn, e->qkv, total)));
         for (int i = 0; i < n_seqs; ++i) {
             const int n = seqs[i].len, start = seqs[i].start;
             const int32_t *block_row = e->block_table + (size_t)seqs[i].slot * c.max_pages_per_seq;
@@ -2378,15 +1849,20 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
                                e->attn + (size_t)seqs[i].row0 * Hq * D, Hq, n, D);
         }
         bool h_normed = false;
-        TL_TRY(engine_gemm(e, w.wo, e->attn, e->h, total, EPI_RESIDUAL, e->x, w.post_norm_dev, e->xn, &h_normed));
+        Proj po = proj(w.wo, e->attn, e->h, total);
+        po.epi = EPI_RESIDUAL, po.residual = e->x, po.norm_out = w.post_norm_dev, po.out_w = e->xn;
+        TL_TRY(engine_gemm(e->lin, po, &h_normed));
         if (!h_normed) TL_TRY(tl_rms_norm(e->h, w.post_norm_dev, e->xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
         if (e->is_moe(l)) {
             TL_TRY(engine_moe_mlp(e, l, e->xn, e->h, e->x, total, nullptr));
         } else {
             TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
-            TL_TRY(engine_gemm(e, w.wgu, e->xn, e->act, total, EPI_SWIGLU, nullptr));
-            TL_TRY(engine_gemm(e, w.wdown, e->act, e->x, total, EPI_RESIDUAL, e->h, l + 1 < c.num_layers ? e->layers[l + 1].input_norm_dev : nullptr, e->xn,
-                               &x_normed));
+            Proj pg = proj(w.wgu, e->xn, e->act, total);
+            pg.epi = EPI_SWIGLU;
+            TL_TRY(engine_gemm(e->lin, pg));
+            Proj pd = proj(w.wdown, e->act, e->x, total);
+            pd.epi = EPI_RESIDUAL, pd.residual = e->h, pd.norm_out = l + 1 < c.num_layers ? e->layers[l + 1].input_norm_dev : nullptr, pd.out_w = e->xn;
+            TL_TRY(engine_gemm(e->lin, pd, &x_normed));
         }
         TL_CHECK_LAUNCH(packed ? "engine packed prefill layer" : "engine prefill layer");
     }
@@ -2426,14 +1902,14 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
         TL_TRY(tl_rms_norm(e->x, e->final_norm, e->xn, n, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
         for (int r0 = 0; r0 < n; r0 += SCORE_BLOCK_ROWS) {
             const int rows = std::min(SCORE_BLOCK_ROWS, n - r0);
-            TL_TRY(engine_gemm(e, e->head(), e->xn + (size_t)r0 * c.hidden_size, e->score_logits, rows, EPI_STORE, nullptr));
+            TL_TRY(engine_gemm(e->lin, proj(e->head(), e->xn + (size_t)r0 * c.hidden_size, e->score_logits, rows)));
             const LogprobRowsArgs a{e->score_logits, c.vocab_size, 0, e->score_ids + r0, e->score_lp + r0, nullptr, nullptr, e->score_argmax + r0};
             hipLaunchKernelGGL(logprob_rows_kernel, dim3(rows), dim3(1024), 0, e->stream, a);
             TL_CHECK_LAUNCH("engine score logprobs");
         }
     }
     if (logits_mode == 2) {
-        TL_TRY(engine_qmv(e, e->head(), e->x, e->logits, n, PRO_RMSNORM, EPI_STORE, e->final_norm, nullptr));
+        TL_TRY(lm_head_rows(e, e->x, n));
         e->logits_rows = n;
         hipLaunchKernelGGL(argmax_rows_kernel, dim3(n), dim3(1024), 0, e->stream, e->logits, c.vocab_size, e->verify_ids);
         TL_CHECK_LAUNCH("engine verify argmax");
@@ -2441,7 +1917,7 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
     if (logits_mode == 1) {
         // logits_to_keep = 1 (reference qwen3_week3.py:331-336): last row only
         const uint16_t *last = e->x + (size_t)(n - 1) * c.hidden_size;
-        TL_TRY(engine_qmv(e, e->head(), last, e->logits, 1, PRO_RMSNORM, EPI_STORE, e->final_norm, nullptr));
+        TL_TRY(lm_head_rows(e, last, 1));
         e->logits_rows = 1;
         TL_TRY(prefill_first_token(e, slot, e->logits, "engine prefill argmax"));
     }
@@ -2491,7 +1967,7 @@ static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const
         ++n_logits;
     }
     if (n_logits > 0) {
-        TL_TRY(engine_qmv(e, e->head(), e->xn, e->logits, n_logits, PRO_RMSNORM, EPI_STORE, e->final_norm, nullptr));
+        TL_TRY(lm_head_rows(e, e->xn, n_logits));
         e->logits_rows = n_logits;
         int j = 0;
         for (int i = 0; i < n_seqs; ++i) {
@@ -2758,7 +2234,7 @@ extern "C" int tl_engine_profile_step(tl_engine *e, int batch, tl_step_profile *
     TL_REQUIRE(rate_khz > 0, "engine_profile_step: device reports no wall clock rate");
     TL_HIP(hipStreamSynchronize(e->stream));
     ProfCtx pc;
-    if (!pc.alloc(e, batch)) return fail(TL_ERR_HIP, "engine_profile_step: hipMalloc / memset of the stamp buffers failed");
+    if (!pc.alloc(e->cfg, batch, e->stream)) return fail(TL_ERR_HIP, "engine_profile_step: hipMalloc / memset of the stamp buffers failed");
     launch_embed_slots(e, batch);
     SplitPlan sp;
     int rc = prepare_step(e, batch, &sp);
@@ -2808,8 +2284,7 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
     out->first_launch = -1, out->first_kind = -1, out->first_region = -1, out->first_offset = -1;
     TL_TRY(aql_drain(e));
     TL_HIP(hipStreamSynchronize(e->stream));
-    tl_engine::WrittenOnceCheck &ck = e->check;
-    ck = tl_engine::WrittenOnceCheck{};
+    WrittenOnceCheck ck;
     ck.region[0] = e->arena + e->arena_act_off, ck.bytes[0] = (e->arena_bytes - e->arena_act_off) / 4 * 4;
     ck.region[1] = e->layer_act_mem, ck.bytes[1] = e->layer_act_mem ? e->layer_act_bytes / 4 * 4 : 0;
     ProfCtx pc;
@@ -2819,14 +2294,13 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
             if (ck.written[rg]) (void)hipFree(ck.written[rg]);
         }
         if (ck.report) (void)hipFree(ck.report);
-        ck = tl_engine::WrittenOnceCheck{};
     };
     auto bail = [&](int code, const std::string &msg) {
         (void)hipStreamSynchronize(e->stream);
         cleanup();
         return fail(code, msg);
     };
-    bool ok = pc.alloc(e, batch) && hipMalloc((void **)&ck.report, 8 * sizeof(unsigned long long)) == hipSuccess;
+    bool ok = pc.alloc(e->cfg, batch, e->stream) && hipMalloc((void **)&ck.report, 8 * sizeof(unsigned long long)) == hipSuccess;
     for (int rg = 0; rg < 2 && ok; ++rg)
         if (ck.bytes[rg]) ok = hipMalloc((void **)&ck.shadow[rg], ck.bytes[rg]) == hipSuccess && hipMalloc((void **)&ck.written[rg], ck.bytes[rg] / 2) == hipSuccess;
     if (!ok) return bail(TL_ERR_HIP, "engine_check_step: hipMalloc of the shadow buffers failed");
@@ -2845,9 +2319,8 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
     SplitPlan sp;
     int rc = prepare_step(e, batch, &sp);
     if (rc == TL_OK) {
-        ck.on = true;
+        pc.check = &ck;
         rc = enqueue_step(e, batch, sp, &pc);
-        ck.on = false;
     }
     if (rc != TL_OK) {
         (void)hipStreamSynchronize(e->stream);
@@ -2876,199 +2349,7 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
     return TL_OK;
 }
 
-// ================================================================================================
-// Kernel-level entry points of the decode path (include/tinyllm_engine.h, last section): the SAME launch code the engine
-// runs per projection / per layer, on caller-owned buffers.  Used by the operator microbenches and by the parity tests at
-// the real Qwen3-4B shapes.
-struct tl_tiled_w4 {
-    tl_w4 w{};
-    tl_engine::Tiled t{};
-};
-
-extern "C" int tl_tiled_w4_create(const tl_w4 *w, void *stream, tl_tiled_w4 **out) {
-    TL_REQUIRE(w && out, "tiled_w4_create: null argument");
-    TL_TRY(check_w4(*w, w->rows, w->cols, "tiled_w4_create"));
-    TL_REQUIRE(w->rows > 0 && w->rows % 16 == 0 && w->cols > 0 && w->cols % 128 == 0,
-               "tiled_w4_create: rows must be a multiple of 16 and cols a multiple of 128");
-    auto *t = new tl_tiled_w4();
-    t->w = *w;
-    const size_t wbytes = (size_t)w->rows * w->cols / 2, sbytes = (size_t)w->rows * (w->cols / 128) * 4;
-    if (hipMalloc((void **)&t->t.wt, wbytes + 16384) != hipSuccess) {
-        delete t;
-        return fail(TL_ERR_HIP, "tiled_w4_create: hipMalloc failed");
-    }
-    if (hipMalloc((void **)&t->t.sbt, sbytes + 1024) != hipSuccess) {
-        (void)hipFree(t->t.wt);
-        delete t;
-        return fail(TL_ERR_HIP, "tiled_w4_create: hipMalloc failed");
-    }
-    if (repack_w4_tiled(w->weight_dev, (const uint16_t *)w->scales_dev, (const uint16_t *)w->biases_dev, t->t.wt, t->t.sbt, w->rows,
-                        w->cols, (hipStream_t)stream) != 0) {
-        (void)hipFree(t->t.wt);
-        (void)hipFree(t->t.sbt);
-        delete t;
-        return fail(TL_ERR_HIP, "tiled_w4_create: repack launch failed");
-    }
-    *out = t;
-    return TL_OK;
-}
-
-extern "C" void tl_tiled_w4_destroy(tl_tiled_w4 *t) {
-    if (!t) return;
-    (void)hipFree(t->t.wt);
-    (void)hipFree(t->t.sbt);
-    delete t;
-}
-
-extern "C" size_t tl_decode_linear_workspace_bytes(int M, int rows, int cols) {
-    if (M <= 0 || rows <= 0 || cols <= 0) return 0;
-    size_t need = align_up((size_t)((M + 15) / 16 * 16) * cols * 2, 256);  // RMSNorm output ahead of the skinny matmul / rows in fragment order (kernel 5)
-    size_t partial = 0;
-    for (int mode = 0; mode < 2; ++mode) {  // either grid of the skinny matmul (kernel 3 / 4 pin one)
-        const Qmm3Plan p3 = qmm3_plan(std::min(M, 64), cols, rows, mode);
-        if (p3.ok) partial = std::max(partial, p3.partial_bytes);
-    }
-    return need + partial;
-}
-
-static int decode_linear_impl(const tl_tiled_w4 *w, const void *a_dev, void *out_dev, int M, int prologue, int epilogue,
-                              const void *norm_w_dev, const void *residual_dev, float eps, int kernel, void *workspace_dev,
-                              size_t workspace_bytes, void *stream, const tl_linear_ex *ex, tl_linear_info *info) {
-    TL_REQUIRE(w && out_dev, "decode_linear: null argument");
-    TL_REQUIRE(M >= 1 && M <= 64, "decode_linear: between 1 and 64 activation rows");
-    TL_REQUIRE(prologue == PRO_NONE || prologue == PRO_RMSNORM || (ex && (prologue == PRO_ATTN_MERGE || prologue == PRO_RMS_WEIGHTED)),
-               "decode_linear: prologue is 0 (none) or 1 (RMSNorm); tl_decode_linear_ex also takes 2 (merge of attention partials) and 3 (weighted rows)");
-    TL_REQUIRE(epilogue == EPI_STORE || epilogue == EPI_RESIDUAL || epilogue == EPI_SWIGLU,
-               "decode_linear: epilogue is 0 (store), 1 (residual add) or 2 (SwiGLU over interleaved rows)");
-    TL_REQUIRE(prologue == PRO_ATTN_MERGE || a_dev, "decode_linear: null activation rows");
-    TL_REQUIRE(prologue != PRO_RMSNORM || norm_w_dev, "decode_linear: the RMSNorm prologue needs its weight");
-    TL_REQUIRE(epilogue != EPI_RESIDUAL || residual_dev, "decode_linear: the residual epilogue needs the residual rows");
-    TL_REQUIRE(kernel >= 0 && kernel <= 6,
-               "decode_linear: kernel is 0 (engine routing), 1 (fused GEMV), 2 (skinny matmul), 3 / 4 (its one-shot / persistent grid), 5 (register-resident matmul), 6 (row-streaming matmul)");
-    TL_REQUIRE(epilogue != EPI_SWIGLU || w->w.rows % 2 == 0, "decode_linear: SwiGLU needs an even number of weight rows");
-    // the engine's own fused variants: RMSNorm+store (qkv, lm_head), residual (wo, w_down), RMSNorm+SwiGLU (gate|up), plain;
-    // through tl_decode_linear_ex also: merged attention partials + residual (wo of one row), weighted rows + SwiGLU (gate|up)
-    TL_REQUIRE((prologue == PRO_NONE && epilogue != EPI_SWIGLU) || (prologue == PRO_RMSNORM && epilogue != EPI_RESIDUAL) ||
-                   (prologue == PRO_ATTN_MERGE && epilogue == EPI_RESIDUAL) || (prologue == PRO_RMS_WEIGHTED && epilogue == EPI_SWIGLU) ||
-                   ((kernel == 5 || kernel == 6) && prologue == PRO_RMS_WEIGHTED && epilogue == EPI_STORE),
-               "decode_linear: no fused variant for this prologue / epilogue pair");
-    const size_t need = tl_decode_linear_workspace_bytes(M, w->w.rows, w->w.cols);
-    TL_REQUIRE(workspace_dev && workspace_bytes >= need, "decode_linear: workspace is missing or too small");
-    tl_engine e;  // only the fields the projection code reads
-    e.cfg.rms_norm_eps = eps;
-    e.stream = (hipStream_t)stream;
-    e.tiled[w->w.weight_dev] = w->t;
-    e.xn = (uint16_t *)workspace_dev;
-    const size_t xn_bytes = align_up((size_t)((M + 15) / 16 * 16) * w->w.cols * 2, 256);
-    e.splitk_ws = (char *)workspace_dev + xn_bytes;
-    e.splitk_ws_bytes = workspace_bytes - xn_bytes;
-    e.force_linear = kernel >= 2 && kernel <= 4 ? 2 : (kernel >= 5 ? 0 : kernel);
-    e.use_qmm7 = false, e.force_qmm7 = kernel == 6;  // 5 and 6 name their kernel
-    e.qmm3_mode = kernel == 3 ? 0 : (kernel == 4 ? 1 : -1);
-    tl_linear_info li{};
-    e.linfo = &li;
-    if (const char *q = getenv("TL_QMM3_MIN_M")) e.qmm3_min_rows = std::max(1, atoi(q));
-    int rc = TL_OK;
-    auto done = [&](int code) {
-        e.splitk_ws = nullptr;  // borrowed
-        e.tiled.clear();
-        if (info) *info = li;
-        return code;
-    };
-    if (kernel == 6 && (prologue != PRO_RMS_WEIGHTED || epilogue == EPI_RESIDUAL))
-        return done(fail(TL_ERR_INVALID, "decode_linear: the row-streaming matmul takes weighted rows with ss_in (prologue 3) and stores or applies SwiGLU (epilogue 0 / 2)"));
-    if (kernel == 5 || kernel == 6) {  // qmm6.h / qmm7.h: plain rows (qmm6 only), or weighted rows with their partial sums of squares
-        const bool weighted = prologue == PRO_RMS_WEIGHTED;
-        if (prologue == PRO_RMSNORM || prologue == PRO_ATTN_MERGE)
-            return done(fail(TL_ERR_INVALID, "decode_linear: the register-resident matmul takes plain rows (prologue 0) or weighted rows with ss_in (prologue 3)"));
-        if (weighted && (!ex || !ex->ss_in_dev || !qmm3_takes_ss(ex->ss_in_n)))
-            return done(fail(TL_ERR_INVALID, "decode_linear_ex: weighted rows need ss_in (a multiple of 4, at most 256 partials per row)"));
-        if (ex && ((ex->out_w_dev != nullptr) != (ex->norm_out_dev != nullptr) || ((ex->out_w_dev || ex->ss_out_dev) && epilogue != EPI_RESIDUAL)))
-            return done(fail(TL_ERR_INVALID, "decode_linear_ex: ss_out / (norm_out, out_w) belong to the residual epilogue; norm_out and out_w come together"));
-        if (kernel == 5 && !qmm6_plan(M, w->w.cols, w->w.rows).ok)
-            return done(fail(TL_ERR_UNSUPPORTED, "decode_linear: the register-resident matmul does not cover this shape"));
-        if (kernel == 6 && !qmm7_plan(M, w->w.cols, w->w.rows).ok)
-            return done(fail(TL_ERR_UNSUPPORTED, "decode_linear: the row-streaming matmul does not cover this shape"));
-        // weighted rows enter the kernel in fragment order (qmm6.h): as the caller left them (ex->fragment_order), or re-ordered here
-        const uint16_t *a6 = (const uint16_t *)a_dev;
-        if (weighted && !ex->fragment_order) {
-            const long n8 = (long)M * w->w.cols / 8;
-            hipLaunchKernelGGL(weight_rows_kernel, dim3(ceil_div(n8, 256)), dim3(256), 0, e.stream, a6, (const uint16_t *)nullptr, e.xn, n8, w->w.cols / 8, 1);
-            a6 = e.xn;
-        }
-        int ss_n6 = 0;
-        rc = engine_qmm6(&e, w->w, a6, (uint16_t *)out_dev, M, epilogue, (const uint16_t *)residual_dev, nullptr, 0,
-                         weighted ? ex->ss_in_dev : nullptr, weighted ? ex->ss_in_n : 0, ex ? ex->ss_out_dev : nullptr, &ss_n6,
-                         ex ? ex->norm_out_dev : nullptr, ex ? (uint16_t *)ex->out_w_dev : nullptr, weighted, ex ? (ex->fragment_order ? 1 : 0) : 0);
-        return done(rc);
-    }
-    if (!ex) {
-        rc = engine_linear(&e, w->w, (const uint16_t *)a_dev, (uint16_t *)out_dev, M, prologue, epilogue, norm_w_dev,
-                           (const uint16_t *)residual_dev, nullptr, 0);
-        return done(rc);
-    }
-    // ---- the routes only the engine could reach before round 4 (qmv3.h: PRO_ATTN_MERGE, PRO_RMS_WEIGHTED, ss_in / ss_out, out_w)
-    const bool skinny_forced = kernel >= 2 && kernel <= 4;  // its slice reduction also leaves weighted rows (not the GEMV's 16-row sums of squares)
-    const bool gemv_only = prologue == PRO_ATTN_MERGE || prologue == PRO_RMS_WEIGHTED || ex->ss_out_dev || (ex->out_w_dev && !skinny_forced);
-    if (gemv_only && !(kernel == 1 || (kernel == 0 && M < e.qmm3_min_rows)))
-        return done(fail(TL_ERR_INVALID, "decode_linear_ex: merged partials, weighted rows, ss_out and out_w are routes of the fused GEMV (kernel 1, or 0 with fewer than 5 rows)"));
-    if ((ex->out_w_dev != nullptr) != (ex->norm_out_dev != nullptr) || (ex->out_w_dev && epilogue != EPI_RESIDUAL) ||
-        (ex->ss_out_dev && epilogue != EPI_RESIDUAL))
-        return done(fail(TL_ERR_INVALID, "decode_linear_ex: ss_out / (norm_out, out_w) belong to the residual epilogue; norm_out and out_w come together"));
-    if (ex->ss_in_dev && (ex->ss_in_n <= 0 || !(prologue == PRO_RMSNORM || prologue == PRO_RMS_WEIGHTED)))
-        return done(fail(TL_ERR_INVALID, "decode_linear_ex: ss_in needs ss_in_n > 0 and a normalising prologue (1 or 3)"));
-    int ss_n = 0;
-    if (prologue == PRO_ATTN_MERGE) {
-        if (M != 1 || !ex->merge_ws_dev) return done(fail(TL_ERR_INVALID, "decode_linear_ex: the merging prologue takes ONE row and the split partials (merge_ws_dev)"));
-        e.attn_ws = const_cast<float *>(ex->merge_ws_dev);
-        rc = engine_wo_merge(&e, w->w, (const uint16_t *)residual_dev, (uint16_t *)out_dev, ex->n_splits, nullptr, ex->ss_out_dev, &ss_n,
-                             ex->norm_out_dev, (uint16_t *)ex->out_w_dev);
-        e.attn_ws = nullptr;  // borrowed
-        if (rc == TL_OK) {
-            const Qmv3Plan pl = qmv3_plan(1, w->w.cols, w->w.rows);
-            li.kernel = 1, li.launches = 1, li.rows_per_pass = 1;
-            li.p[0] = pl.MR, li.p[1] = pl.KS, li.p[2] = pl.CW, li.p[3] = pl.LM, li.p[4] = pl.blocks;
-        }
-        return done(rc);
-    }
-    if (prologue == PRO_RMS_WEIGHTED) {
-        const Qmv3Plan pl = qmv3_plan(std::min(M, 8), w->w.cols, w->w.rows);
-        if (!ex->ss_in_dev || M > 8 || !qmv3_takes_weighted_rows(pl, w->w.cols, ex->ss_in_n))
-            return done(fail(TL_ERR_INVALID, "decode_linear_ex: weighted rows need ss_in (a multiple of 4, at most 256 partials per row), at most 8 rows and a row that fits the staging registers"));
-    }
-    if (gemv_only || kernel == 1 || (kernel == 0 && M < e.qmm3_min_rows)) {
-        if (M > 8) return done(fail(TL_ERR_INVALID, "decode_linear_ex: the fused GEMV takes at most 8 rows"));
-        rc = engine_qmv(&e, w->w, (const uint16_t *)a_dev, (uint16_t *)out_dev, M, prologue, epilogue, norm_w_dev,
-                        (const uint16_t *)residual_dev, nullptr, 0, ex->ss_in_dev, ex->ss_in_n, ex->ss_out_dev, &ss_n, ex->norm_out_dev,
-                        (uint16_t *)ex->out_w_dev);
-        if (rc == TL_OK && ex->ss_out_dev && ss_n != w->w.rows / 16)
-            rc = fail(TL_ERR_UNSUPPORTED, "decode_linear_ex: the GEMV that ran left no sums of squares (packed-dot fallback or several passes)");
-        return done(rc);
-    }
-    // skinny matmul with its fused RMSNorm (any multiple of 4 up to 256 partials per row)
-    if (ex->ss_in_dev && !qmm3_takes_ss(ex->ss_in_n))
-        return done(fail(TL_ERR_INVALID, "decode_linear_ex: the skinny matmul reads a multiple of 4, at most 256, partial sums of squares per row"));
-    rc = engine_linear(&e, w->w, (const uint16_t *)a_dev, (uint16_t *)out_dev, M, prologue, epilogue, norm_w_dev,
-                       (const uint16_t *)residual_dev, nullptr, 0, ex->ss_in_dev, nullptr, nullptr, nullptr, ex->ss_in_dev ? ex->ss_in_n : 0,
-                       nullptr, ex->norm_out_dev, (uint16_t *)ex->out_w_dev, ex->fragment_order != 0);
-    return done(rc);
-}
-
-extern "C" int tl_decode_linear(const tl_tiled_w4 *w, const void *a_dev, void *out_dev, int M, int prologue, int epilogue,
-                                const void *norm_w_dev, const void *residual_dev, float eps, int kernel, void *workspace_dev,
-                                size_t workspace_bytes, void *stream, tl_linear_info *info) {
-    return decode_linear_impl(w, a_dev, out_dev, M, prologue, epilogue, norm_w_dev, residual_dev, eps, kernel, workspace_dev,
-                              workspace_bytes, stream, nullptr, info);
-}
-
-extern "C" int tl_decode_linear_ex(const tl_tiled_w4 *w, const void *a_dev, void *out_dev, int M, int prologue, int epilogue,
-                                   const void *norm_w_dev, const void *residual_dev, float eps, int kernel, void *workspace_dev,
-                                   size_t workspace_bytes, void *stream, const tl_linear_ex *ex, tl_linear_info *info) {
-    TL_REQUIRE(ex, "decode_linear_ex: null extension block (use tl_decode_linear)");
-    return decode_linear_impl(w, a_dev, out_dev, M, prologue, epilogue, norm_w_dev, residual_dev, eps, kernel, workspace_dev,
-                              workspace_bytes, stream, ex, info);
-}
-
+// ---- kernel-level entry points beside tl_decode_linear[_ex] (decode_linear.h): the prefill GEMM, the decode attention, the plans ----
 // The prefill projection of large chunks on caller buffers (header): W4 -> bf16 expansion, then the plain bf16 GEMM of gemm8.h.
 extern "C" int tl_prefill_weights_bf16(const tl_w4 *w, void *out_dev, void *stream) {
     TL_REQUIRE(w && out_dev, "prefill_weights_bf16: null argument");
@@ -3140,16 +2421,16 @@ static int decode_attention_fused_impl(const void *qkv_dev, const void *q_norm_d
     e.context_lens = const_cast<int32_t *>(context_lens_dev);
     e.rope_cur = (float2 *)workspace_dev;
     const size_t rc_bytes = align_up((size_t)batch * (head_dim / 2) * sizeof(float2), 256);
-    e.attn_ws = (float *)((char *)workspace_dev + rc_bytes);
     e.attn_ws_bytes = workspace_bytes - rc_bytes;
     read_attention_knobs(&e);
     hipLaunchKernelGGL(rope_rows_kernel, dim3(batch), dim3(64), 0, e.stream, context_lens_dev, e.rope_cur, head_dim / 2, rope_theta);
     TL_CHECK_LAUNCH("decode_attention_fused rope");
     const SplitPlan sp = pick_decode_splits(&e, batch, std::max(1, max_context + 1));
-    const int rc = engine_attention(&e, (const uint16_t *)qkv_dev, q_norm_dev, k_norm_dev, (uint16_t *)key_pages_dev,
-                                    (uint16_t *)value_pages_dev, (uint16_t *)out_dev, batch, sp, nullptr, nullptr, nullptr, nullptr,
-                                    key_scales_dev, value_scales_dev);
-    e.rope_cur = nullptr;  // borrowed
+    AttnCall at{};
+    at.qkv = (const uint16_t *)qkv_dev, at.q_norm = q_norm_dev, at.k_norm = k_norm_dev, at.out = (uint16_t *)out_dev;
+    at.key_pages = (uint16_t *)key_pages_dev, at.value_pages = (uint16_t *)value_pages_dev, at.key_scales = key_scales_dev, at.value_scales = value_scales_dev;
+    at.ws = (float *)((char *)workspace_dev + rc_bytes);
+    const int rc = engine_attention(&e, at, batch, sp, nullptr);
     if (info) {
         info->n_splits = sp.n_splits;
         info->tokens_per_split = sp.tokens_per_split;
