@@ -30,6 +30,9 @@ def main(argv=None):
     ap.add_argument("--sampler-top-p", type=float, default=None)
     ap.add_argument("--sampler-top-k", type=int, default=None)
     ap.add_argument("--sampler-seed", type=int, default=0, help="request i draws from seed + i")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0, help="per request, on the device; over prompt and output (1 = off)")
+    ap.add_argument("--presence-penalty", type=float, default=0.0, help="per request, on the device; over the output (0 = off)")
+    ap.add_argument("--frequency-penalty", type=float, default=0.0, help="per request, on the device; times the count in the output (0 = off)")
     ap.add_argument("--prompts-file", default=None, help="one prompt per line (default: five built-in questions)")
     args = ap.parse_args(argv)
 
@@ -50,12 +53,15 @@ def main(argv=None):
     pages_per_seq = args.max_seq_len // 128 + 2
     engine = DecodeEngine(model, page_size=128, num_pages=pages_per_seq * (args.batch_size + 1) + 2,
                           max_batch=args.batch_size + 1, max_prefill_rows=args.prefill_step, kv_format=args.kv_format)
+    sampling = {}
+    if args.sampler_temp:
+        sampling.update(temperature=args.sampler_temp, top_k=args.sampler_top_k, top_p=args.sampler_top_p)
+    if (args.repetition_penalty, args.presence_penalty, args.frequency_penalty) != (1.0, 0.0, 0.0):
+        sampling.update(repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty,
+                        frequency_penalty=args.frequency_penalty)
     try:
         done = batch_generate_ids(engine, encoded, limits, batch_size=args.batch_size, prefill_step=args.prefill_step,
-                                  eos_token_id=tokenizer.eos_token_id,
-                                  sampling=None if not args.sampler_temp else {"temperature": args.sampler_temp, "top_k": args.sampler_top_k,
-                                                                               "top_p": args.sampler_top_p},
-                                  base_seed=args.sampler_seed)
+                                  eos_token_id=tokenizer.eos_token_id, sampling=sampling or None, base_seed=args.sampler_seed)
     finally:
         engine.close()
     results = []

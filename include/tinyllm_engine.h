@@ -245,6 +245,48 @@ int tl_engine_set_logprobs(tl_engine *e, int slot, int top_n);
 int tl_engine_read_logprobs(tl_engine *e, int slot, int count, tl_token_logprob *out);
 int tl_engine_read_pending_logprobs(tl_engine *e, int count, tl_token_logprob *out);
 
+/* Penalties and logit bias (csrc/logit_process.h): what changes the logits BEFORE the choice.  For a slot that
+ * processes, every logits row the slot would choose a token from -- each decode step, and the last row of a prefill / packed prefill with
+ * want_logits -- is first turned into a processed bf16 row, and the existing choice (greedy first maximum, or the sampler of
+ * tl_engine_set_sampling) runs on the processed row exactly as it runs on a raw row otherwise.
+ *   history  per slot and token id j:  prompt[j] (a flag): j was among the tokens the slot consumed through tl_engine_prefill,
+ *            tl_engine_prefill_packed or tl_engine_score while it was processing;  count[j]: how many of the tokens the slot produced and
+ *            then fed back were j -- it goes up by one in every decode step the slot takes while processing, for that step's input token
+ *            (the pending token the previous step end, or a prefill with want_logits, produced), BEFORE the step's row is processed.  So
+ *            when token n + 1 is chosen, tokens 1 .. n of the output are counted, and a pending token that is never fed (the slot is
+ *            released, or prefilled further) is never counted.  count saturates at 32,767.  (The split of vLLM and the OpenAI API:
+ *            repetition looks at prompt and output, presence and frequency at the output only.)
+ *   element  in fp32, ONE IEEE-754 single-precision operation per line, no fused multiply-add, division correctly rounded:
+ *                v = float(l[j])                                                    the bf16 logit
+ *                if prompt[j] or count[j] > 0:  v = v / r  if v > 0 else  v * r     r = repetition_penalty
+ *                v = v - (frequency_penalty * float(count[j]))                      two operations
+ *                if count[j] > 0:               v = v - presence_penalty
+ *                v = v + bias[j]                                                    0 where the slot has no entry
+ *                out[j] = bf16 round to nearest even of v
+ *            A row that processes goes through every line, neutral stages included (a -0.0 logit may come out as +0.0 after v + 0.0; the
+ *            two tie in every routine).  A row that does not process is copied bit for bit.  A NaN logit stays NaN (the sampler never
+ *            ranks it); -inf as a bias value bans the token.  Subnormal fp32 values follow the device's fp32 denormal mode.
+ *   slots    repetition_penalty finite and > 0 (1 = off), presence_penalty and frequency_penalty finite (0 = off; negative values
+ *            encourage repetition, as in the OpenAI API).  Logit bias: up to TL_MAX_LOGIT_BIAS pairs (id, value), ids in [0, vocab) and
+ *            distinct, values finite or -inf; a call replaces the slot's whole list, n = 0 clears it.  Anything else is TL_ERR_INVALID
+ *            with nothing changed.  A slot PROCESSES iff some parameter is not neutral or its list is not empty.  History is tracked from
+ *            the call that makes the slot process (set the parameters before the prompt's prefill); the call that makes it neutral again
+ *            forgets the history.  Vocabulary limit as for the sampler (524,288).
+ *   unchanged  tl_engine_logits_dev / tl_engine_copy_logits keep returning the RAW logits.  Log-probability records stay the model's
+ *            distribution at temperature 1, unfiltered: computed from the raw row, for the token chosen from the processed row (a banned
+ *            token is never the produced token, but may appear in the top-N).  The Philox position, the draw and the tie rules.  A step
+ *            in which no live slot processes is the program it was: same captured plan, same kernels, same launches; a step in which one
+ *            does has one more launch (many workgroups per row) between the lm_head and the step end, in a captured plan of its own.
+ *   life     tl_engine_begin / tl_engine_release make the slot neutral and empty its history, tl_engine_move carries parameters, bias
+ *            list and history with the sequence, tl_engine_fork copies them.  tl_engine_verify, tl_engine_rewind and tl_engine_set_token
+ *            refuse a processing slot with TL_ERR_INVALID (after them the history would no longer be the tokens the sequence holds); they
+ *            work again once the slot is neutral or re-begun.
+ * The history table (max_batch x vocab x 2 bytes), the processed rows (the same size) and the bias lists are allocated by the first call
+ * that makes a slot process; an engine that never asks allocates nothing. */
+#define TL_MAX_LOGIT_BIAS 1024
+int tl_engine_set_penalties(tl_engine *e, int slot, float repetition_penalty, float presence_penalty, float frequency_penalty);
+int tl_engine_set_logit_bias(tl_engine *e, int slot, const int32_t *ids, const float *values, int n);
+
 /* Scoring a given text: behaves like tl_engine_prefill(e, slot, tokens, n, want_logits = 0) for the KV cache and the context (same
  * limits: n <= max_prefill_rows, chunks longer than 8 tokens need head_dim 128), and also keeps every row: the final RMSNorm over the
  * chunk, the lm_head through the W4 GEMM in blocks of rows into a scoring scratch (allocated on first use), then the log-probability
@@ -308,7 +350,7 @@ size_t tl_engine_step_bytes(const tl_engine *e, int batch);
  * tl_engine_decode(e, batch, 1, 0)) with every kernel stamping the device wall clock at its first
  * workgroup's start and its last wave's end.  kernel_us[k] / launches[k] are summed per kind:
  *   0 qkv GEMV, 1 wo GEMV, 2 gate|up GEMV, 3 w_down GEMV, 4 lm_head GEMV, 5 attention, 6 attention merge,
- *   7 step end (argmax + embed).
+ *   7 step end (argmax + embed; with a processing slot also the logit-processing launch ahead of it).
  * gemv_bytes[k] = algorithmic W4 bytes those launches stream (packed nibbles + bf16 scales and biases).
  * span_us = first start to last end of the step (includes the small reduce kernels this mode inserts
  * between launches, so it is NOT the production step time).  Synchronises the stream. */
@@ -479,6 +521,16 @@ int tl_sample_logits(const void *logits_dev, int rows, int vocab, const float *t
  * top_ids_dev / top_logprobs_dev [rows, top_n] (may be NULL when top_n is 0).  One 1,024-thread workgroup per row.  Stream ordered. */
 int tl_logprob_rows(const void *logits_dev, int rows, int vocab, const int32_t *ids_dev, int top_n, float *logprob_dev, int32_t *top_ids_dev,
                     float *top_logprobs_dev, void *stream);
+
+/* The processing routine of tl_engine_set_penalties / tl_engine_set_logit_bias over caller rows: logits [rows, vocab] bf16 (vocab <=
+ * 524,288) -> out_dev [rows, vocab] bf16, the engine's kernel and semantics, nothing counted.  history_dev [rows, vocab]: one uint16 per
+ * (row, token), bit 15 = prompt, bits 0-14 = count (saturated at 32,767).  repetition / presence / frequency [rows]; bias_n_dev [rows]
+ * entries of each row's list in bias_ids_dev / bias_values_dev [rows, TL_MAX_LOGIT_BIAS] (distinct ids in [0, vocab); both may be NULL
+ * when every n is 0).  A row whose parameters are all neutral and whose list is empty is copied bit for bit.  One launch of
+ * ceil(vocab / 2,048) x rows workgroups.  Stream ordered. */
+int tl_process_logits(const void *logits_dev, int rows, int vocab, const uint16_t *history_dev, const float *repetition_dev,
+                      const float *presence_dev, const float *frequency_dev, const int32_t *bias_ids_dev, const float *bias_values_dev,
+                      const int32_t *bias_n_dev, void *out_dev, void *stream);
 
 #ifdef __cplusplus
 }

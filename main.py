@@ -29,6 +29,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sampler-top-k", type=int, default=None)
     ap.add_argument("--sampler-seed", type=int, default=None,
                     help="with --solution engine and a nonzero --sampler-temp: sample on the device, in decode(N) calls, from this seed")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0,
+                    help="with --solution engine: divide (multiply, where negative) the logits of the tokens of the prompt and the output "
+                         "by this before each choice, on the device (1 = off)")
+    ap.add_argument("--presence-penalty", type=float, default=0.0,
+                    help="with --solution engine: subtract this from the logit of every token the output already holds (0 = off)")
+    ap.add_argument("--frequency-penalty", type=float, default=0.0,
+                    help="with --solution engine: subtract this times the token's count in the output (0 = off)")
     ap.add_argument("--enable-thinking", action="store_true")
     ap.add_argument("--raw-prompt", action="store_true", help="do not wrap the prompt in the chat template")
     ap.add_argument("--max-new-tokens", type=int, default=256)
@@ -50,6 +57,7 @@ def main(argv=None) -> str:
     from tiny_llm_hip import load
 
     model, tokenizer = load(args.model)
+    penalties = (args.repetition_penalty, args.presence_penalty, args.frequency_penalty)
     prompt = args.prompt if args.raw_prompt else chat_prompt(tokenizer, args.prompt, args.enable_thinking)
     if args.solution == "ops":
         from tiny_llm_hip import Qwen3ModelWeek3, make_sampler, simple_generate_with_kv_cache, speculative_generate
@@ -59,6 +67,8 @@ def main(argv=None) -> str:
             draft, draft_tok = load(args.draft_model)
             return speculative_generate(Qwen3ModelWeek3(draft), net, draft_tok, tokenizer, prompt,
                                         proposal_length=args.proposal_length)
+        if penalties != (1.0, 0.0, 0.0):
+            print("note: the penalty flags apply to --solution engine only")
         if args.sampler_temp:
             print("note: the KV-cache loop is greedy like the reference's; sampler flags apply to --solution engine only")
         _ = make_sampler  # sampler surface kept importable for callers of the library
@@ -76,16 +86,22 @@ def main(argv=None) -> str:
             draft_model, draft_tok = load(args.draft_model)
             if draft_tok.get_vocab() != tokenizer.get_vocab():
                 raise ValueError("draft and target tokenizers use different token ids")
+            if penalties != (1.0, 0.0, 0.0):
+                print("note: speculative decoding verifies the raw logits; the penalty flags do not apply with a draft model")
             draft = DecodeEngine(draft_model, page_size=128, num_pages=pages, max_batch=1, max_prefill_rows=4096)
             try:
                 out = speculative_generate_ids(engine, draft, ids, args.max_new_tokens,
                                                proposal_length=min(args.proposal_length, 7), eos_token_id=eos)
             finally:
                 draft.close()
-        elif args.sampler_temp and args.sampler_seed is not None:
-            # the per-slot sampler on the device: the whole generation in one prefill + one decode(N) call
+        elif args.sampler_temp and (args.sampler_seed is not None or penalties != (1.0, 0.0, 0.0)):
+            # the per-slot sampler on the device: the whole generation in one prefill + one decode(N) call.  The penalties exist on the
+            # device only, so they select this path
+            if args.sampler_seed is None:
+                print("note: the penalty flags select the device sampler; no --sampler-seed given: seed 0")
             out = engine.generate(ids, args.max_new_tokens, temperature=args.sampler_temp, top_k=args.sampler_top_k,
-                                  top_p=args.sampler_top_p, seed=args.sampler_seed, logprobs=args.logprobs)
+                                  top_p=args.sampler_top_p, seed=args.sampler_seed or 0, logprobs=args.logprobs,
+                                  repetition_penalty=penalties[0], presence_penalty=penalties[1], frequency_penalty=penalties[2])
             if args.logprobs is not None:
                 out, records = out
             if eos in out:
@@ -93,7 +109,8 @@ def main(argv=None) -> str:
         elif args.sampler_temp:
             out = sample_with_engine(engine, ids, args, eos)
         else:
-            out = engine.generate(ids, args.max_new_tokens, logprobs=args.logprobs)
+            out = engine.generate(ids, args.max_new_tokens, logprobs=args.logprobs, repetition_penalty=penalties[0],
+                                  presence_penalty=penalties[1], frequency_penalty=penalties[2])
             if args.logprobs is not None:
                 out, records = out
             if eos in out:

@@ -12,6 +12,7 @@
 #include "decode_linear.h"  // the projection router; with it common.h, engine_kernels.h and the decode matmuls' headers
 #include "sample.h"
 #include "logprob.h"
+#include "logit_process.h"
 #include "attn_mfma.h"
 #include "aql.h"
 
@@ -116,6 +117,20 @@ struct tl_engine {
     int32_t *lp_topn = nullptr;
     uint32_t *lp_ring = nullptr, *lp_pending = nullptr;
     std::vector<int> lp_n, lp_from;
+    // per-slot logit processing (tl_engine_set_penalties / tl_engine_set_logit_bias, logit_process.h): the host mirror, and -- allocated by the
+    // first call that makes a slot process -- the history table [max_batch, vocab], the processed rows [max(max_batch, 8), vocab] the step
+    // end chooses from, and the per-slot parameters and bias lists
+    struct PenaltyParams {
+        float repetition = 1.f, presence = 0.f, frequency = 0.f;
+        std::vector<int32_t> bias_ids;
+        std::vector<float> bias_values;
+        bool processes() const { return repetition != 1.f || presence != 0.f || frequency != 0.f || !bias_ids.empty(); }
+    };
+    std::vector<PenaltyParams> pen;
+    char *pen_mem = nullptr;
+    uint16_t *pen_history = nullptr, *pen_rows = nullptr;
+    float *pen_rep = nullptr, *pen_pres = nullptr, *pen_freq = nullptr, *pen_bias_values = nullptr;
+    int32_t *pen_bias_n = nullptr, *pen_bias_ids = nullptr;
     // tl_engine_score: the logits of one block of rows and the per-row targets / results, allocated on first use
     uint16_t *score_logits = nullptr;
     int32_t *score_ids = nullptr, *score_argmax = nullptr;
@@ -284,6 +299,7 @@ struct LogprobStepEndArgs {
     const int32_t *top_n;  // [max_batch] -1: the slot records nothing
     uint32_t *ring;        // [max_batch, ring_cap] records of LP_RECORD_WORDS words
     uint32_t *pending;     // [max_batch] the record of each slot's pending token
+    const uint16_t *choice;  // [rows, vocab] the processed rows the token is chosen from (logit_process.h); nullptr: q.s.logits themselves
 };
 
 static __global__ __launch_bounds__(1024) void logprob_step_end_kernel(const LogprobStepEndArgs lq) {
@@ -297,6 +313,9 @@ static __global__ __launch_bounds__(1024) void logprob_step_end_kernel(const Log
     const int i = blockIdx.x;
     const int slot = p.slot0 + i;
     const SmpRow row(p.logits + (long)i * p.vocab, p.vocab);
+    // the record describes the raw row; with processed rows (uniform) the token is chosen from those
+    const bool split = lq.choice != nullptr;
+    const SmpRow crow(split ? lq.choice + (long)i * p.vocab : row.lg, p.vocab);
     const float temperature = q.temperature[slot], top_p = q.top_p[slot];
     const int top_k = q.top_k[slot];
     const uint64_t seed = q.seed[slot];
@@ -310,17 +329,19 @@ static __global__ __launch_bounds__(1024) void logprob_step_end_kernel(const Log
         for (int k = threadIdx.x; k < p.tiles; k += 1024) t = fmaxf(t, act_load(tm + k)[0]);
         m_given = smp_block_max(t, sm);
     }
-    if (m_given != m_given) {  // once for both routines
+    const int top_n = lq.top_n[slot];
+    const bool record = live && top_n >= 0;  // uniform
+    if (m_given != m_given && (record || !split)) {  // the raw row's maximum, once for both routines
         float t = -INFINITY;
         smp_for_each(row, [&](int, int, uint32_t b) { t = fmaxf(t, __uint_as_float(b << 16)); });  // fmaxf drops NaN
         m_given = smp_block_max(t, sm);
     }
-    const int top_n = lq.top_n[slot];
-    const bool record = live && top_n >= 0;  // uniform
-    // a greedy slot that records takes the routine's own first maximum (smp_select's greedy id): one pass instead of two
+    // a greedy slot that records takes the routine's own first maximum (smp_select's greedy id): one pass instead of two -- unless the
+    // choice is made on another row than the record's
+    const bool lp_first = record && temperature == 0.f && !split;
     float lse = 0.f;
-    if (record && temperature == 0.f) lse = lp_row(row, m_given, top_n, sm, ls);
-    const int bi = record && temperature == 0.f ? ls.greedy : smp_select(row, m_given, temperature, top_k, top_p, seed, position, sm);
+    if (lp_first) lse = lp_row(row, m_given, top_n, sm, ls);
+    const int bi = lp_first ? ls.greedy : smp_select(crow, split ? __builtin_nanf("") : m_given, temperature, top_k, top_p, seed, position, sm);
     __syncthreads();  // every thread has read context_lens[slot] above
     if (threadIdx.x == 0) {
         s_token = bi;
@@ -369,7 +390,7 @@ static __global__ __launch_bounds__(1024) void logprob_step_end_kernel(const Log
         }
     }
     if (record) {
-        if (temperature != 0.f) lse = lp_row(row, m_given, top_n, sm, ls);
+        if (!lp_first) lse = lp_row(row, m_given, top_n, sm, ls);
         if (threadIdx.x == 0) ls.rec[0] = __float_as_uint(BF16::to_float(act_load(row.lg + token)) - lse);
         __syncthreads();
         if ((int)threadIdx.x < LP_RECORD_WORDS) {
@@ -482,9 +503,11 @@ static StepEndArgs step_end_args(const tl_engine *e, const uint16_t *logits, int
 
 // step end of a decode step / a prefill's last row: greedy kernel, its sampling twin when the plan samples, or the logprob twin
 // (which also samples) when a slot records log-probabilities
-static void launch_step_end(tl_engine *e, const StepEndArgs &s, int rows, bool samples, bool logprobs) {
+// `raw`: the rows of the model's logits where s.logits are processed rows (logit_process.h) -- the logprob twin records from them
+static void launch_step_end(tl_engine *e, const StepEndArgs &s, int rows, bool samples, bool logprobs, const uint16_t *raw = nullptr) {
     if (logprobs) {
-        const LogprobStepEndArgs l{{s, e->smp_temp, e->smp_topk, e->smp_topp, e->smp_seed}, e->lp_topn, e->lp_ring, e->lp_pending};
+        LogprobStepEndArgs l{{s, e->smp_temp, e->smp_topk, e->smp_topp, e->smp_seed}, e->lp_topn, e->lp_ring, e->lp_pending, nullptr};
+        if (raw) l.choice = s.logits, l.q.s.logits = raw;
         hipLaunchKernelGGL(logprob_step_end_kernel, dim3(rows), dim3(1024), 0, e->stream, l);
     } else if (samples) {
         const SampleStepEndArgs q{s, e->smp_temp, e->smp_topk, e->smp_topp, e->smp_seed};
@@ -529,6 +552,92 @@ static int lp_carry(tl_engine *e, int src, int dst, bool move) {
     TL_HIP(hipMemcpyAsync(e->lp_pending + (size_t)dst * LP_RECORD_WORDS, e->lp_pending + (size_t)src * LP_RECORD_WORDS, LP_RECORD_WORDS * 4,
                           hipMemcpyDeviceToDevice, e->stream));
     return move ? lp_write(e, src, -1) : TL_OK;
+}
+
+// ---- per-slot logit processing (logit_process.h) ------------------------------------------------------------
+// does some live slot of [0, batch) process its logits?  (the plan-key bit next to step_samples' and step_logprobs')
+static bool step_processes_slot(const tl_engine *e, int slot) { return e->pen_mem && e->slot_live[slot] && e->pen[slot].processes(); }
+static bool step_processes(const tl_engine *e, int batch) {
+    for (int b = 0; b < batch; ++b)
+        if (step_processes_slot(e, b)) return true;
+    return false;
+}
+
+// the history table, the processed rows and the per-slot parameters: one allocation, made by the first call that makes a slot process
+static int pen_alloc(tl_engine *e) {
+    if (e->pen_mem) return TL_OK;
+    const size_t B = (size_t)e->cfg.max_batch, V = (size_t)e->cfg.vocab_size;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return at;
+    };
+    const size_t o_hist = carve(B * V * 2), o_rows = carve(std::max<size_t>(B, 8) * V * 2), o_rep = carve(B * 4), o_pres = carve(B * 4),
+                 o_freq = carve(B * 4), o_n = carve(B * 4), o_ids = carve(B * LPR_MAX_BIAS * 4), o_vals = carve(B * LPR_MAX_BIAS * 4);
+    char *m = nullptr;
+    if (hipMalloc((void **)&m, off) != hipSuccess) return fail(TL_ERR_HIP, "engine: hipMalloc(logit processing) failed");
+    // everything zero (empty histories, presence / frequency 0, empty lists) but the repetition penalties: 1
+    if (hipMemsetAsync(m, 0, off, e->stream) != hipSuccess) {
+        (void)hipFree(m);
+        return fail(TL_ERR_HIP, "engine: memset(logit processing) failed");
+    }
+    hipLaunchKernelGGL(fill_i32_kernel, dim3(ceil_div((long)B, 256)), dim3(256), 0, e->stream, (int32_t *)(m + o_rep), __builtin_bit_cast(int32_t, 1.0f), (int)B);
+    e->pen_mem = m;
+    e->pen_history = (uint16_t *)(m + o_hist);
+    e->pen_rows = (uint16_t *)(m + o_rows);
+    e->pen_rep = (float *)(m + o_rep), e->pen_pres = (float *)(m + o_pres), e->pen_freq = (float *)(m + o_freq);
+    e->pen_bias_n = (int32_t *)(m + o_n), e->pen_bias_ids = (int32_t *)(m + o_ids), e->pen_bias_values = (float *)(m + o_vals);
+    e->stats.workspace_bytes += off;
+    TL_CHECK_LAUNCH("engine logit-processing init");
+    return TL_OK;
+}
+
+// the slot's parameters and bias list become `v` (validated by the caller): the device copy follows the host mirror, stream-ordered
+// between steps.  History is tracked from the call that makes the slot process: that call empties the slot's row of the table.
+static int pen_write(tl_engine *e, int slot, const tl_engine::PenaltyParams &v) {
+    tl_engine::PenaltyParams &cur = e->pen[slot];
+    const bool was = cur.processes(), now = v.processes();
+    if (!e->pen_mem && !now) return TL_OK;  // neutral on an engine that never processed: nothing to write
+    TL_TRY(pen_alloc(e));
+    const size_t V = (size_t)e->cfg.vocab_size;
+    if (now && !was) TL_HIP(hipMemsetAsync(e->pen_history + (size_t)slot * V, 0, V * 2, e->stream));
+    std::vector<std::pair<int32_t *, int32_t>> pk;
+    if (cur.repetition != v.repetition) pk.emplace_back((int32_t *)(e->pen_rep + slot), __builtin_bit_cast(int32_t, v.repetition));
+    if (cur.presence != v.presence) pk.emplace_back((int32_t *)(e->pen_pres + slot), __builtin_bit_cast(int32_t, v.presence));
+    if (cur.frequency != v.frequency) pk.emplace_back((int32_t *)(e->pen_freq + slot), __builtin_bit_cast(int32_t, v.frequency));
+    const bool bias_changed = cur.bias_ids != v.bias_ids || memcmp(cur.bias_values.data(), v.bias_values.data(), v.bias_values.size() * 4) != 0;
+    if (bias_changed) pk.emplace_back(e->pen_bias_n + slot, (int32_t)v.bias_ids.size());
+    cur = v;
+    if (bias_changed && !cur.bias_ids.empty()) {  // (from the mirror: it outlives the copy)
+        TL_HIP(hipMemcpyAsync(e->pen_bias_ids + (size_t)slot * LPR_MAX_BIAS, cur.bias_ids.data(), cur.bias_ids.size() * 4, hipMemcpyHostToDevice, e->stream));
+        TL_HIP(hipMemcpyAsync(e->pen_bias_values + (size_t)slot * LPR_MAX_BIAS, cur.bias_values.data(), cur.bias_values.size() * 4, hipMemcpyHostToDevice, e->stream));
+    }
+    return pk.empty() ? TL_OK : poke(e, pk);
+}
+static int pen_reset(tl_engine *e, int slot) { return e->pen[slot].processes() ? pen_write(e, slot, tl_engine::PenaltyParams{}) : TL_OK; }
+
+// tl_engine_move (move = true) / tl_engine_fork: dst takes src's parameters, bias list and history (a device-to-device copy of the
+// slot's row on the engine stream: no synchronisation); a move makes src neutral
+static int pen_carry(tl_engine *e, int src, int dst, bool move) {
+    if (!e->pen[src].processes() && !e->pen[dst].processes()) return TL_OK;
+    const tl_engine::PenaltyParams v = e->pen[src];
+    TL_TRY(pen_write(e, dst, v));
+    if (v.processes()) {
+        const size_t V = (size_t)e->cfg.vocab_size;
+        TL_HIP(hipMemcpyAsync(e->pen_history + (size_t)dst * V, e->pen_history + (size_t)src * V, V * 2, hipMemcpyDeviceToDevice, e->stream));
+    }
+    return move ? pen_reset(e, src) : TL_OK;
+}
+
+// the processing launch over `rows` rows of raw logits for slots slot0 .. (logit_process.h): processed rows into `out`.  A decode step
+// passes the pending tokens (counted before the row is processed); a prefill's last row has none to count.
+static void launch_logit_process(tl_engine *e, const uint16_t *logits, uint16_t *out, int rows, int slot0, const int32_t *tokens, ProfCtx *pc) {
+    const LogitProcessArgs a{logits, out, e->cfg.vocab_size, slot0, e->pen_history, e->pen_rep, e->pen_pres, e->pen_freq, e->pen_bias_n,
+                             e->pen_bias_ids, e->pen_bias_values, tokens, pc ? pc->buf : nullptr};
+    const dim3 grid(ceil_div(e->cfg.vocab_size, LPR_CHUNK), rows);
+    hipLaunchKernelGGL(logit_process_kernel, grid, dim3(LPR_THREADS), 0, e->stream, a);
+    if (pc) prof_after(pc, 7, (int)(grid.x * grid.y));
 }
 
 // Context split of the decode attention: power-of-two bucket >= context, fixed windows of C tokens per workgroup.
@@ -914,10 +1023,14 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, ProfCtx *pc = nul
         ph.tile_max = e->lm_tile_max_on ? e->lm_tile_max : nullptr;
         TL_TRY(engine_linear(ctx, ph, pc, &rh));
     }
-    const bool tile_max = rh.maxima_rows == batch;
-    const StepEndArgs s = step_end_args(e, e->logits, 0, 1, e->x, tile_max ? e->lm_tile_max : nullptr, tile_max ? e->head().rows / 16 : 0, e->ss_x,
-                                        pc ? pc->buf : nullptr);
-    launch_step_end(e, s, batch, step_samples(e, batch), step_logprobs(e, batch));
+    // a plan in which some live slot processes its logits: one more launch turns the raw rows into processed rows (rows of other slots
+    // are copied), and the step end chooses from those; the lm_head's tile maxima describe the raw rows and are not used
+    const bool processes = step_processes(e, batch);
+    if (processes) launch_logit_process(e, e->logits, e->pen_rows, batch, 0, e->tokens, pc);
+    const bool tile_max = rh.maxima_rows == batch && !processes;
+    const StepEndArgs s = step_end_args(e, processes ? e->pen_rows : e->logits, 0, 1, e->x, tile_max ? e->lm_tile_max : nullptr,
+                                        tile_max ? e->head().rows / 16 : 0, e->ss_x, pc ? pc->buf : nullptr);
+    launch_step_end(e, s, batch, step_samples(e, batch), step_logprobs(e, batch), processes ? e->logits : nullptr);
     if (pc) prof_after(pc, 7, batch);
     TL_CHECK_LAUNCH("engine step end");
     return TL_OK;
@@ -1363,6 +1476,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->slot_live.assign(c.max_batch, 0);
     e->slot_produced.assign(c.max_batch, 0);
     e->smp.assign(c.max_batch, tl_engine::SampleParams{});
+    e->pen.assign(c.max_batch, tl_engine::PenaltyParams{});
     e->free_pages.resize(c.num_pages);
     for (int i = 0; i < c.num_pages; ++i) e->free_pages[i] = c.num_pages - 1 - i;  // pop_back hands out 0,1,2,...
     e->page_was_used.assign(c.num_pages, 0);
@@ -1467,6 +1581,7 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     if (e->arena) (void)hipFree(e->arena);
     if (e->smp_mem) (void)hipFree(e->smp_mem);
     if (e->lp_mem) (void)hipFree(e->lp_mem);
+    if (e->pen_mem) (void)hipFree(e->pen_mem);
     if (e->score_logits) (void)hipFree(e->score_logits);
     if (e->kpool) (void)hipFree(e->kpool);
     if (e->vpool) (void)hipFree(e->vpool);
@@ -1512,6 +1627,7 @@ extern "C" int tl_engine_begin(tl_engine *e, int slot) {
     pk.emplace_back(e->tokens + slot, 0);
     TL_TRY(poke(e, pk));
     TL_TRY(lp_write(e, slot, -1));
+    TL_TRY(pen_reset(e, slot));
     return smp_reset(e, slot);
 }
 
@@ -1541,12 +1657,14 @@ extern "C" int tl_engine_release(tl_engine *e, int slot) {
     e->stats.pages_free = (int)e->free_pages.size();
     TL_TRY(poke(e, pk));
     TL_TRY(lp_write(e, slot, -1));
+    TL_TRY(pen_reset(e, slot));
     return smp_reset(e, slot);
 }
 
 extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
     TL_TRY(slot_check(e, slot, true));
     TL_REQUIRE(n >= 0 && n <= e->slot_ctx[slot], "engine_rewind: cannot rewind past the start of the sequence");
+    TL_REQUIRE(!e->pen[slot].processes(), "engine_rewind: the slot processes its logits (its history would keep the dropped tokens; make it neutral first)");
     const int ctx = e->slot_ctx[slot] - n;
     const int keep = (ctx + e->cfg.page_size - 1) / e->cfg.page_size;
     std::vector<std::pair<int32_t *, int32_t>> pk;
@@ -1621,7 +1739,8 @@ extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
     if (!smp_is_default(e->smp[src]) || !smp_is_default(e->smp[dst])) TL_TRY(smp_write(e, dst, e->smp[src]));
     // ... and the log-probability setting with the pending token's record
     TL_TRY(lp_carry(e, src, dst, false));
-    return TL_OK;
+    // ... and the penalties, the bias list and the history
+    return pen_carry(e, src, dst, false);
 }
 
 // Move a (prefilled) sequence from slot `src` to the free slot `dst`: the reference prefills a request in its own
@@ -1661,7 +1780,9 @@ extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
         TL_TRY(smp_write(e, src, tl_engine::SampleParams{}));
     }
     // ... and so do the log-probability setting and the pending token's record (the record ring restarts, like the token ring)
-    return lp_carry(e, src, dst, true);
+    TL_TRY(lp_carry(e, src, dst, true));
+    // ... and the penalties, the bias list and the history
+    return pen_carry(e, src, dst, true);
 }
 
 // Pending token ids of slots [0, count) after synchronising the stream (one copy per decode step instead of one
@@ -1682,6 +1803,7 @@ extern "C" int tl_engine_context_len(const tl_engine *e, int slot) {
 extern "C" int tl_engine_set_token(tl_engine *e, int slot, int32_t token) {
     TL_TRY(slot_check(e, slot, true));
     TL_REQUIRE(token >= 0 && token < e->cfg.vocab_size, "engine_set_token: token id out of range");
+    TL_REQUIRE(!e->pen[slot].processes(), "engine_set_token: the slot processes its logits (its history counts the tokens the engine produced; make it neutral first)");
     std::vector<std::pair<int32_t *, int32_t>> pk;
     pk.emplace_back(e->tokens + slot, token);
     return poke(e, pk);
@@ -1699,6 +1821,48 @@ extern "C" int tl_engine_set_sampling(tl_engine *e, int slot, float temperature,
     v.top_p = top_p > 0.f && top_p < 1.f ? top_p : 0.f;  // outside (0, 1): no top-p
     v.seed = seed;
     return smp_write(e, slot, v);
+}
+
+extern "C" int tl_engine_set_penalties(tl_engine *e, int slot, float repetition_penalty, float presence_penalty, float frequency_penalty) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(std::isfinite(repetition_penalty) && repetition_penalty > 0.f, "engine_set_penalties: repetition_penalty must be finite and > 0 (1 = off)");
+    TL_REQUIRE(std::isfinite(presence_penalty) && std::isfinite(frequency_penalty), "engine_set_penalties: presence_penalty and frequency_penalty must be finite (0 = off)");
+    TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_set_penalties: vocabulary larger than 524,288 tokens");
+    tl_engine::PenaltyParams v = e->pen[slot];
+    v.repetition = repetition_penalty, v.presence = presence_penalty, v.frequency = frequency_penalty;
+    return pen_write(e, slot, v);
+}
+
+extern "C" int tl_engine_set_logit_bias(tl_engine *e, int slot, const int32_t *ids, const float *values, int n) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(n >= 0 && n <= TL_MAX_LOGIT_BIAS, "engine_set_logit_bias: between 0 and TL_MAX_LOGIT_BIAS (1,024) entries");
+    TL_REQUIRE(n == 0 || (ids && values), "engine_set_logit_bias: null argument");
+    TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_set_logit_bias: vocabulary larger than 524,288 tokens");
+    tl_engine::PenaltyParams v = e->pen[slot];
+    v.bias_ids.assign(ids, ids + n);
+    v.bias_values.assign(values, values + n);
+    std::vector<int32_t> sorted(v.bias_ids);
+    std::sort(sorted.begin(), sorted.end());
+    for (int i = 0; i < n; ++i) {
+        TL_REQUIRE(sorted[i] >= 0 && sorted[i] < e->cfg.vocab_size, "engine_set_logit_bias: token id out of range");
+        TL_REQUIRE(i == 0 || sorted[i] != sorted[i - 1], "engine_set_logit_bias: a token id appears twice");
+        TL_REQUIRE(std::isfinite(values[i]) || values[i] == -INFINITY, "engine_set_logit_bias: values must be finite or -inf");
+    }
+    return pen_write(e, slot, v);
+}
+
+extern "C" int tl_process_logits(const void *logits_dev, int rows, int vocab, const uint16_t *history_dev, const float *repetition_dev,
+                                 const float *presence_dev, const float *frequency_dev, const int32_t *bias_ids_dev, const float *bias_values_dev,
+                                 const int32_t *bias_n_dev, void *out_dev, void *stream) {
+    TL_REQUIRE(logits_dev && history_dev && repetition_dev && presence_dev && frequency_dev && bias_n_dev && out_dev, "process_logits: null argument");
+    TL_REQUIRE(rows > 0 && rows <= 65535, "process_logits: rows out of range");
+    TL_REQUIRE(vocab > 0 && vocab <= SMP_MAX_VOCAB, "process_logits: vocabulary out of range (1 .. 524,288)");
+    // (without lists every n must be 0: the kernel reads no entry then)
+    const LogitProcessArgs a{(const uint16_t *)logits_dev, (uint16_t *)out_dev, vocab, 0, const_cast<uint16_t *>(history_dev), repetition_dev, presence_dev,
+                             frequency_dev, bias_n_dev, bias_ids_dev, bias_values_dev, nullptr, nullptr};
+    hipLaunchKernelGGL(logit_process_kernel, dim3(ceil_div(vocab, LPR_CHUNK), rows), dim3(LPR_THREADS), 0, (hipStream_t)stream, a);
+    TL_CHECK_LAUNCH("process_logits");
+    return TL_OK;
 }
 
 extern "C" int tl_sample_logits(const void *logits_dev, int rows, int vocab, const float *temperature_dev, const int32_t *top_k_dev,
@@ -1807,6 +1971,12 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
     e->stats.pages_free = (int)e->free_pages.size();
     TL_TRY(poke(e, pk));
     TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens, (size_t)total * 4, hipMemcpyHostToDevice, e->stream));
+    for (int i = 0; i < n_seqs; ++i) {  // the chunk's tokens enter the history of a slot that processes its logits (logit_process.h)
+        if (!step_processes_slot(e, seqs[i].slot)) continue;
+        const LogitMarkArgs mk{e->prefill_tokens + seqs[i].row0, seqs[i].len, c.vocab_size, (uint32_t *)e->pen_history, (long)seqs[i].slot * c.vocab_size};
+        hipLaunchKernelGGL(logit_mark_prompt_kernel, dim3(ceil_div(seqs[i].len, 256)), dim3(256), 0, e->stream, mk);
+        TL_CHECK_LAUNCH("engine prompt marking");
+    }
 
     const int D = c.head_dim, Hq = c.num_heads, Hkv = c.num_kv_heads;
     TL_TRY(tl_quantized_embedding(e->prefill_tokens, 0, e->embed.scales_dev, e->embed.biases_dev, e->embed.weight_dev, e->x,
@@ -1878,7 +2048,13 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
 // The first token of a prefilled slot from its logits row: the step end (advance 0: the prefill has set the context length), after which
 // the slot has produced one id.  Its embedding row goes to scratch: the prefill activations in x must stay intact; decode re-embeds from tokens
 static int prefill_first_token(tl_engine *e, int slot, const uint16_t *logits, const char *what) {
-    launch_step_end(e, step_end_args(e, logits, slot, 0, e->h), 1, e->smp[slot].samples(), step_logprobs_slot(e, slot));
+    const uint16_t *raw = nullptr;
+    if (step_processes_slot(e, slot)) {  // the row is processed first (no pending token to count here), into the row of the same index
+        uint16_t *out = e->pen_rows + (logits - e->logits);
+        launch_logit_process(e, logits, out, 1, slot, nullptr, nullptr);
+        raw = logits, logits = out;
+    }
+    launch_step_end(e, step_end_args(e, logits, slot, 0, e->h), 1, e->smp[slot].samples(), step_logprobs_slot(e, slot), raw);
     TL_CHECK_LAUNCH(what);
     e->slot_produced[slot] += 1;
     return TL_OK;
@@ -2017,6 +2193,7 @@ extern "C" int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, i
     TL_REQUIRE(n >= 1 && n <= 8, "engine_verify: between 1 and 8 tokens per call (the paged decode kernel's query rows)");
     TL_TRY(slot_check(e, slot, true));
     TL_REQUIRE(!e->smp[slot].samples(), "engine_verify: the slot samples (verification is greedy; set temperature 0 first)");
+    TL_REQUIRE(!e->pen[slot].processes(), "engine_verify: the slot processes its logits (verification takes the raw rows; make it neutral first)");
     TL_TRY(prefill_impl(e, slot, tokens, n, 2));
     TL_HIP(hipMemcpyAsync(out_ids, e->verify_ids, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
     TL_HIP(hipStreamSynchronize(e->stream));
@@ -2097,7 +2274,7 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
     // input activations of the first step come from the pending token ids
     launch_embed_slots(e, batch);
     TL_CHECK_LAUNCH("engine embed");
-    const bool samples = step_samples(e, batch), logprobs = step_logprobs(e, batch);
+    const bool samples = step_samples(e, batch), logprobs = step_logprobs(e, batch), processes = step_processes(e, batch);
     bool on_queue = false;  // steps of this call are in flight on the AQL queue (the stream is idle and must stay so until they are drained)
     for (int s = 0; s < steps; ++s) {
         SplitPlan sp;
@@ -2105,7 +2282,8 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
         if (use_graph && e->warmed) {
             // bit 62: the step ends with the sampling twin of step_end_kernel, bit 61: with the logprob twin (both re-derived every call
             // from the slots' parameters)
-            const auto key = std::make_pair(batch, sp.key() | (samples ? (1L << 62) : 0L) | (logprobs ? (1L << 61) : 0L));
+            // bit 60: the processing launch (logit_process.h) stands between the lm_head and the step end
+            const auto key = std::make_pair(batch, sp.key() | (samples ? (1L << 62) : 0L) | (logprobs ? (1L << 61) : 0L) | (processes ? (1L << 60) : 0L));
             auto it = e->graphs.find(key);
             if (it == e->graphs.end()) {
                 // The split plan (and with it the key) changes every 64 * n_splits tokens of context: a long run would keep one

@@ -1,0 +1,145 @@
+// Logit processing ahead of the token choice (include/tinyllm_engine.h "penalties and logit bias"): repetition,
+// presence and frequency penalties and a per-slot logit bias turn a raw bf16 logits row into a processed bf16 row; the greedy rule and
+// the sampler then run on the processed row unchanged.
+//
+// Per element, in fp32, one IEEE-754 operation per line (no fused multiply-add; the division is the correctly rounded one):
+//   v = float(l[j])
+//   if prompt[j] or count[j] > 0:  v = v > 0 ? v / r : v * r
+//   v = v - (f * float(count[j]))
+//   if count[j] > 0:               v = v - p
+//   v = v + bias[j]                (0 where the slot has no entry)
+//   out[j] = bf16(v), round to nearest even
+// History: one uint16 per (slot, token): bit 15 = the token was in the prompt, bits 0-14 = how often the slot produced and fed it back,
+// saturating at 32,767.  A row whose slot does not process (r = 1, p = f = 0, no bias entry) is copied bit for bit.
+//
+// One launch over (chunks of LPR_CHUNK tokens) x rows: a pass of ONE workgroup over a 304 KB row costs ~12 us, and this
+// pass reads two rows and writes one.  8 logits per lane by 16-byte loads and stores where the rows are 16-byte aligned.  The workgroup
+// whose chunk holds the slot's pending token counts it (the only store to the history inside a step); the slot's bias entries that fall
+// into the chunk are scattered into LDS and added from there.
+#pragma once
+#include "common.h"
+
+namespace tl {
+
+constexpr int LPR_THREADS = 256;
+constexpr int LPR_CHUNK = LPR_THREADS * 8;  // tokens per workgroup
+constexpr int LPR_MAX_BIAS = 1024;          // TL_MAX_LOGIT_BIAS
+constexpr uint32_t LPR_PROMPT = 0x8000u, LPR_COUNT = 0x7fffu;
+
+// (one struct by value, like every kernel of a decode step: csrc/aql.cpp copies a captured node's argument block as it is)
+struct LogitProcessArgs {
+    const uint16_t *logits;   // [rows, vocab] raw; row i belongs to slot slot0 + i
+    uint16_t *out;            // [rows, vocab] processed
+    int vocab, slot0;
+    uint16_t *history;        // [slots, vocab]
+    const float *repetition;  // [slots]
+    const float *presence;
+    const float *frequency;
+    const int32_t *bias_n;       // [slots] entries in the slot's list
+    const int32_t *bias_ids;     // [slots, LPR_MAX_BIAS]
+    const float *bias_values;    // [slots, LPR_MAX_BIAS]
+    const int32_t *tokens;       // [slots] pending token ids: a decode step counts them; nullptr: nothing is counted (prefill, caller rows)
+    prof_t *prof;
+};
+
+__device__ __forceinline__ uint32_t lpr_count_up(uint32_t h) { return (h & LPR_COUNT) < LPR_COUNT ? h + 1u : h; }
+
+// the six lines of the definition, each one instruction: contraction is off inside this function only (HIP's default would fuse the
+// frequency product into the subtraction)
+__device__ __forceinline__ uint32_t lpr_element(uint32_t l, uint32_t h, float r, float p, float f, float b) {
+#pragma clang fp contract(off)
+    float v = __uint_as_float(l << 16);
+    const uint32_t count = h & LPR_COUNT;
+    if (h != 0u) v = v > 0.f ? v / r : v * r;
+    const float fc = f * (float)count;
+    v = v - fc;
+    if (count != 0u) v = v - p;
+    v = v + b;
+    return (uint32_t)BF16::from_float(v);
+}
+
+static __global__ __launch_bounds__(LPR_THREADS) void logit_process_kernel(const LogitProcessArgs a) {
+    __shared__ float s_bias[LPR_CHUNK];
+    const prof_t prof_t0 = prof_begin(a.prof);
+    const int row = blockIdx.y, slot = a.slot0 + row;
+    const int c0 = blockIdx.x * LPR_CHUNK, c = c0 + (int)threadIdx.x * 8;
+    const uint16_t *lg = a.logits + (long)row * a.vocab;
+    uint16_t *out = a.out + (long)row * a.vocab;
+    uint16_t *hist = a.history + (long)slot * a.vocab;
+    const float r = a.repetition[slot], p = a.presence[slot], f = a.frequency[slot];
+    const int nb = min(a.bias_n[slot], LPR_MAX_BIAS);
+    const bool on = r != 1.f || p != 0.f || f != 0.f || nb > 0;  // uniform
+    const bool vec = (((uintptr_t)lg | (uintptr_t)out | (uintptr_t)hist) & 15) == 0 && c + 8 <= a.vocab;
+    if (!on) {  // the row of a slot that does not process: copied, so that the step end reads one buffer
+        if (vec) {
+            act_store16(out + c, act_load(reinterpret_cast<const u32x4 *>(lg + c)));
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                if (c + e < a.vocab) act_store(out + c + e, act_load(lg + c + e));
+        }
+        prof_end(a.prof, prof_t0);
+        return;
+    }
+    // loads first: logits and history are in flight while the bias entries are scattered
+    u32x4 lv = {0u, 0u, 0u, 0u}, hv = {0u, 0u, 0u, 0u};
+    if (vec) {
+        lv = act_load(reinterpret_cast<const u32x4 *>(lg + c));
+        hv = *reinterpret_cast<const u32x4 *>(hist + c);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if (c + e >= a.vocab) continue;
+            lv[e >> 1] |= (uint32_t)act_load(lg + c + e) << ((e & 1) * 16);
+            hv[e >> 1] |= (uint32_t)hist[c + e] << ((e & 1) * 16);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s_bias[threadIdx.x * 8 + e] = 0.f;
+    __syncthreads();
+    for (int k = threadIdx.x; k < nb; k += LPR_THREADS) {  // ids are distinct: no two lanes write one entry
+        const int d = a.bias_ids[(long)slot * LPR_MAX_BIAS + k] - c0;
+        if ((unsigned)d < (unsigned)LPR_CHUNK) s_bias[d] = a.bias_values[(long)slot * LPR_MAX_BIAS + k];
+    }
+    __syncthreads();
+    // the pending token (what the previous step produced and this step consumed) is counted before the row is processed
+    const int pending = a.tokens ? a.tokens[slot] : -1;
+    uint32_t o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        uint32_t h = (hv[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
+        if (c + e == pending && c + e < a.vocab) {
+            h = lpr_count_up(h);
+            act_store(hist + c + e, (uint16_t)h);
+        }
+        const uint32_t l = (lv[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
+        o[e >> 1] |= lpr_element(l, h, r, p, f, s_bias[threadIdx.x * 8 + e]) << ((e & 1) * 16);
+    }
+    if (vec) {
+        act_store16(out + c, u32x4{o[0], o[1], o[2], o[3]});
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            if (c + e < a.vocab) act_store(out + c + e, (uint16_t)((o[e >> 1] >> ((e & 1) * 16)) & 0xffffu));
+    }
+    prof_end(a.prof, prof_t0);
+}
+
+// Prompt marking: bit 15 of history[token] for n consumed tokens of one slot (behind the token upload of a prefill / score chunk).
+// A vector atomic OR on the containing 32-bit word: neighbours of one word may be marked by different lanes.  grid = ceil(n / 256).
+struct LogitMarkArgs {
+    const int32_t *tokens;  // [n]
+    int n, vocab;
+    uint32_t *table;        // the history table as 32-bit words (two tokens each)
+    long row;               // the slot's first element in the table: slot * vocab (odd where the vocabulary is)
+};
+static __global__ __launch_bounds__(256) void logit_mark_prompt_kernel(const LogitMarkArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const int t = a.tokens[i];
+    if (t < 0 || t >= a.vocab) return;
+    const long el = a.row + t;
+    atomicOr(a.table + (el >> 1), (el & 1) ? (LPR_PROMPT << 16) : LPR_PROMPT);
+}
+
+}  // namespace tl

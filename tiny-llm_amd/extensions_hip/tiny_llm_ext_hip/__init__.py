@@ -123,6 +123,7 @@ class TlStepCheck(ctypes.Structure):
 
 
 TL_MAX_TOP_LOGPROBS = 20
+TL_MAX_LOGIT_BIAS = 1024  # entries of a slot's logit-bias list (include/tinyllm_engine.h)
 
 
 class TlTokenLogprob(ctypes.Structure):
@@ -194,6 +195,9 @@ _SIGNATURES.update({
     "tl_engine_set_sampling": (_c_int, [_c_void_p, _c_int, _c_float, _c_int, _c_float, ctypes.c_uint64]),
     "tl_sample_logits": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 7),
     "tl_engine_set_logprobs": (_c_int, [_c_void_p, _c_int, _c_int]),
+    "tl_engine_set_penalties": (_c_int, [_c_void_p, _c_int, _c_float, _c_float, _c_float]),
+    "tl_engine_set_logit_bias": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _P(_c_float), _c_int]),
+    "tl_process_logits": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 9),
     "tl_engine_read_logprobs": (_c_int, [_c_void_p, _c_int, _c_int, _P(TlTokenLogprob)]),
     "tl_engine_read_pending_logprobs": (_c_int, [_c_void_p, _c_int, _P(TlTokenLogprob)]),
     "tl_engine_score": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, ctypes.c_int32, _P(_c_float), _P(ctypes.c_int32)]),
@@ -968,3 +972,66 @@ def logprob_rows(logits: torch.Tensor, ids=None, top_n: int = 0):
     check(_lib.tl_logprob_rows(logits.data_ptr(), rows, logits.shape[1], ids_t.data_ptr() if ids_t is not None else None, top_n,
                                lp.data_ptr(), top_ids.data_ptr() if top_n else None, top_lp.data_ptr() if top_n else None, _stream()))
     return lp, top_ids, top_lp
+
+
+def process_logits(logits: torch.Tensor, history: torch.Tensor, repetition=1.0, presence=0.0, frequency=0.0, bias=None) -> torch.Tensor:
+    """The decode engine's logit processing (tl_process_logits) over rows of bf16 logits [rows, vocab]: ``history`` [rows, vocab] of
+    uint16 bits in an int16 tensor (bit 15 = the token was in the prompt, bits 0-14 = how often it was produced); per-row repetition /
+    presence / frequency penalties (a scalar or one value per row); ``bias`` None, or one {id: value} dict per row (None for a row
+    without a list; at most TL_MAX_LOGIT_BIAS entries each).  Returns the processed rows [rows, vocab] bf16."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("process_logits takes a [rows, vocab] bf16 tensor on the GPU")
+    if history.dtype != torch.int16 or history.shape != logits.shape or not history.is_cuda:
+        raise ValueError("history must be an int16 tensor (uint16 bits) of the logits' shape on the GPU")
+    logits, history = logits.contiguous(), history.contiguous()
+    rows, vocab, dev = logits.shape[0], logits.shape[1], logits.device
+
+    def per_row(v):
+        t = torch.as_tensor(v, dtype=torch.float32).reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(rows)
+        if t.numel() != rows:
+            raise ValueError("a penalty needs one value per row")
+        return t.contiguous().to(dev)
+
+    r_t, p_t, f_t = per_row(repetition), per_row(presence), per_row(frequency)
+    lists = [None] * rows if bias is None else list(bias)
+    if len(lists) != rows:
+        raise ValueError("bias needs one dict (or None) per row")
+    n_h = torch.zeros(rows, dtype=torch.int32)
+    ids_h = torch.zeros((rows, TL_MAX_LOGIT_BIAS), dtype=torch.int32)
+    vals_h = torch.zeros((rows, TL_MAX_LOGIT_BIAS), dtype=torch.float32)
+    for i, d in enumerate(lists):
+        ids, vals = logit_bias_arg(d, vocab)
+        n_h[i] = len(ids)
+        if ids:
+            ids_h[i, :len(ids)] = torch.tensor(ids, dtype=torch.int32)
+            vals_h[i, :len(ids)] = torch.tensor(vals, dtype=torch.float32)
+    n_t, ids_t, vals_t = n_h.to(dev), ids_h.to(dev), vals_h.to(dev)
+    out = torch.empty_like(logits)
+    check(_lib.tl_process_logits(logits.data_ptr(), rows, vocab, history.data_ptr(), r_t.data_ptr(), p_t.data_ptr(), f_t.data_ptr(),
+                                 ids_t.data_ptr(), vals_t.data_ptr(), n_t.data_ptr(), out.data_ptr(), _stream()))
+    return out
+
+
+def logit_bias_arg(bias, vocab: int) -> tuple[list[int], list[float]]:
+    """Validated (ids, values) of a logit-bias list for tl_engine_set_logit_bias: None or a mapping {token id: value} of at most
+    TL_MAX_LOGIT_BIAS entries, ids ints in [0, vocab) (distinct: 3 and 3.0 or True are refused, not merged), values finite or -inf."""
+    if bias is None:
+        return [], []
+    if not hasattr(bias, "items"):
+        raise ValueError("logit_bias must be None or a mapping {token id: value}")
+    items = list(bias.items())
+    if len(items) > TL_MAX_LOGIT_BIAS:
+        raise ValueError(f"logit_bias takes at most {TL_MAX_LOGIT_BIAS} entries, got {len(items)}")
+    ids, vals = [], []
+    for k, v in items:
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < vocab:
+            raise ValueError(f"logit_bias id must be an int in [0, {vocab}), got {k!r}")
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v == float("inf"):
+            raise ValueError(f"logit_bias value must be finite or -inf, got {v!r}")
+        ids.append(int(k))
+        vals.append(float(v))
+    if len(set(ids)) != len(ids):
+        raise ValueError("logit_bias ids must be distinct")
+    return ids, vals

@@ -211,6 +211,20 @@ class DecodeEngine:
         recording off.  begin / release switch it off, move carries it along, fork copies it."""
         _ext.check(_lib.tl_engine_set_logprobs(self._h, slot, logprobs_arg(top_n)))
 
+    def set_penalties(self, slot: int, repetition: float = 1.0, presence: float = 0.0, frequency: float = 0.0) -> None:
+        """Per-slot penalties on the device (tl_engine_set_penalties): every logits row the live slot chooses a token from is first
+        processed -- the repetition penalty over the tokens of its prompt and its output, presence and frequency over its output.  The
+        history is tracked from the call that makes the slot process, so call this before the prompt's prefill; all-neutral values
+        (1, 0, 0) forget it.  begin / release make the slot neutral, move carries everything along, fork copies it."""
+        _ext.check(_lib.tl_engine_set_penalties(self._h, slot, *penalty_args(repetition, presence, frequency)))
+
+    def set_logit_bias(self, slot: int, bias) -> None:
+        """The slot's logit bias (tl_engine_set_logit_bias): a mapping {token id: value} of at most 1,024 entries added to the logits
+        before the choice (-inf bans a token, a large value forces it); None or {} clears the list.  A call replaces the whole list."""
+        ids, vals = _ext.logit_bias_arg(bias, self.vocab_size)
+        n = len(ids)
+        _ext.check(_lib.tl_engine_set_logit_bias(self._h, slot, (ctypes.c_int32 * max(n, 1))(*ids), (ctypes.c_float * max(n, 1))(*vals), n))
+
     def read_logprobs(self, slot: int, count: int) -> list["TokenLogprob"]:
         """Records of the slot's last ``count`` produced tokens (like read_tokens); synchronises."""
         out = (_ext.TlTokenLogprob * max(count, 1))()
@@ -342,13 +356,22 @@ class DecodeEngine:
     # -- convenience: one request, like benches/bench.py:run_one_request_week2 --------------------------
     def generate(self, prompt: Sequence[int], max_new_tokens: int, *, slot: int = 0, chunk: int | None = None,
                  temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None, seed: int = 0,
-                 logprobs: int | None = None):
+                 logprobs: int | None = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                 frequency_penalty: float = 0.0, logit_bias=None):
         """One request: prefill, then ``max_new_tokens - 1`` decode steps in one call; greedy unless ``temperature`` > 0 (the
-        device sampler, set_sampling).  With ``logprobs`` an int (0 .. 20 alternatives, set_logprobs): returns (ids, records)."""
+        device sampler, set_sampling).  With ``logprobs`` an int (0 .. 20 alternatives, set_logprobs): returns (ids, records).
+        ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` (set_penalties, set_logit_bias) are set
+        before the prefill, so the prompt's tokens are in the slot's history."""
         args = sampling_args(temperature, top_k, top_p, seed)
         top_n = logprobs_arg(logprobs)
+        pen = penalty_args(repetition_penalty, presence_penalty, frequency_penalty)
+        bias = _ext.logit_bias_arg(logit_bias, self.vocab_size)
         self.begin(slot)
         try:
+            if pen != (1.0, 0.0, 0.0):
+                self.set_penalties(slot, *pen)
+            if bias[0]:
+                self.set_logit_bias(slot, logit_bias)
             if args[0] > 0.0:
                 self.set_sampling(slot, *args)
             if top_n >= 0:
@@ -402,10 +425,49 @@ def sampling_args(temperature: float = 0.0, top_k: int | None = None, top_p: flo
     return float(temperature), min(int(top_k), 2**31 - 1), float(top_p), int(seed)
 
 
+def penalty_args(repetition: float = 1.0, presence: float = 0.0, frequency: float = 0.0) -> tuple[float, float, float]:
+    """Validated (repetition, presence, frequency) for tl_engine_set_penalties: repetition finite and > 0 (1 = off), presence and
+    frequency finite (0 = off; negative values encourage repetition)."""
+    for name, v in (("repetition_penalty", repetition), ("presence_penalty", presence), ("frequency_penalty", frequency)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+    if not repetition > 0:
+        raise ValueError(f"repetition_penalty must be > 0, got {repetition!r}")
+    return float(repetition), float(presence), float(frequency)
+
+
+_SAMPLING_KEYS = {"temperature", "top_k", "top_p", "seed"}
+_PENALTY_KEYS = {"repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias"}
+
+
+def request_penalties(sampling, n_prompts: int, vocab_size: int) -> list[tuple[tuple[float, float, float], dict]] | None:
+    """The penalty half of batch_generate_ids' ``sampling`` dicts (request_sampling reads the other keys): per prompt
+    ((repetition, presence, frequency), logit bias dict), validated; None when ``sampling`` is None."""
+    if sampling is None:
+        return None
+    if isinstance(sampling, dict):
+        sampling = [sampling] * n_prompts
+    sampling = list(sampling)
+    if len(sampling) != n_prompts:
+        raise ValueError("sampling needs one dict per prompt (or one dict for all)")
+    out = []
+    for d in sampling:
+        if not isinstance(d, dict):
+            raise ValueError("sampling entries must be dicts")
+        unknown = set(d) - _SAMPLING_KEYS - _PENALTY_KEYS
+        if unknown:
+            raise ValueError(f"unknown sampling keys: {sorted(unknown)}")
+        bias = d.get("logit_bias")
+        _ext.logit_bias_arg(bias, vocab_size)
+        out.append((penalty_args(d.get("repetition_penalty", 1.0), d.get("presence_penalty", 0.0), d.get("frequency_penalty", 0.0)),
+                    dict(bias) if bias else {}))
+    return out
+
+
 def request_sampling(sampling, n_prompts: int, base_seed: int = 0) -> list[tuple[float, int, float, int]] | None:
     """batch_generate_ids' ``sampling``: None (greedy, today's behaviour), one dict for every request, or one dict per prompt, with
     keys temperature / top_k / top_p / seed.  A request without a seed gets base_seed + its prompt index, so requests do not share
-    a random stream."""
+    a random stream.  The keys repetition_penalty / presence_penalty / frequency_penalty / logit_bias are read by request_penalties."""
     if sampling is None:
         return None
     if isinstance(sampling, dict):
@@ -417,7 +479,7 @@ def request_sampling(sampling, n_prompts: int, base_seed: int = 0) -> list[tuple
     for i, d in enumerate(sampling):
         if not isinstance(d, dict):
             raise ValueError("sampling entries must be dicts")
-        unknown = set(d) - {"temperature", "top_k", "top_p", "seed"}
+        unknown = set(d) - _SAMPLING_KEYS - _PENALTY_KEYS  # (the penalty keys are request_penalties')
         if unknown:
             raise ValueError(f"unknown sampling keys: {sorted(unknown)}")
         seed = d.get("seed")
@@ -441,7 +503,8 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     nothing, so skipping the idle tail changes no result), (d) retires finished requests and returns their pages.
     Token-id in, token-id out (no tokenizer can be downloaded here).  Needs ``engine.max_batch >= batch_size + 1``:
     the last slot is the prefill staging slot.  Returns [(prompt_idx, generated ids)] in completion order.
-    ``sampling``: None (greedy), one dict or one dict per prompt (request_sampling); applied when a request enters the staging slot,
+    ``sampling``: None (greedy), one dict or one dict per prompt (request_sampling; the dicts also take repetition_penalty /
+    presence_penalty / frequency_penalty / logit_bias, request_penalties); applied when a request enters the staging slot,
     and carried by the engine through its slot moves.  ``logprobs``: None, or an int (0 .. 20 alternatives): every request records
     its tokens' log-probabilities (set_logprobs), read in the same turn as the pending ids, and the result is
     [(prompt_idx, generated ids, records)]."""
@@ -451,6 +514,7 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
         raise ValueError("engine needs batch_size + 1 slots (one prefill staging slot)")
     limits = [max_new_tokens] * len(prompts) if isinstance(max_new_tokens, int) else list(max_new_tokens)
     per_request = request_sampling(sampling, len(prompts), base_seed)
+    per_request_pen = None if sampling is None else request_penalties(sampling, len(prompts), engine.vocab_size)
     top_n = logprobs_arg(logprobs)
     staging = batch_size
     queue = list(range(len(prompts)))
@@ -466,6 +530,12 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                 live_slots.add(staging)
                 if per_request is not None and per_request[idx][0] > 0.0:
                     engine.set_sampling(staging, *per_request[idx])
+                if per_request_pen is not None:
+                    pen, bias = per_request_pen[idx]
+                    if pen != (1.0, 0.0, 0.0):
+                        engine.set_penalties(staging, *pen)
+                    if bias:
+                        engine.set_logit_bias(staging, bias)
                 if top_n >= 0:
                     engine.set_logprobs(staging, top_n)
                 pending = {"idx": idx, "tokens": [int(t) for t in prompts[idx]], "offset": 0, "out": [], "limit": limits[idx], "lp": []}
