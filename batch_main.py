@@ -33,6 +33,8 @@ def main(argv=None):
     ap.add_argument("--repetition-penalty", type=float, default=1.0, help="per request, on the device; over prompt and output (1 = off)")
     ap.add_argument("--presence-penalty", type=float, default=0.0, help="per request, on the device; over the output (0 = off)")
     ap.add_argument("--frequency-penalty", type=float, default=0.0, help="per request, on the device; times the count in the output (0 = off)")
+    ap.add_argument("--regex", default=None, metavar="PATTERN",
+                    help="every answer must match PATTERN in full (tiny_llm_hip.grammar's dialect), enforced on the device per request")
     ap.add_argument("--prompts-file", default=None, help="one prompt per line (default: five built-in questions)")
     args = ap.parse_args(argv)
 
@@ -59,14 +61,20 @@ def main(argv=None):
     if (args.repetition_penalty, args.presence_penalty, args.frequency_penalty) != (1.0, 0.0, 0.0):
         sampling.update(repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty,
                         frequency_penalty=args.frequency_penalty)
+    stops = {tokenizer.eos_token_id}
     try:
+        if args.regex:
+            from tiny_llm_hip.grammar import regex_grammar
+
+            sampling["grammar"] = regex_grammar(engine, tokenizer, args.regex)
+            stops |= set(sampling["grammar"].eos_ids)
         done = batch_generate_ids(engine, encoded, limits, batch_size=args.batch_size, prefill_step=args.prefill_step,
                                   eos_token_id=tokenizer.eos_token_id, sampling=sampling or None, base_seed=args.sampler_seed)
     finally:
         engine.close()
     results = []
     for idx, ids in done:
-        if ids and ids[-1] == tokenizer.eos_token_id:
+        if ids and ids[-1] in stops:
             ids = ids[:-1]
         text = tokenizer.decode(ids)
         results.append((idx, text))

@@ -287,6 +287,61 @@ int tl_engine_read_pending_logprobs(tl_engine *e, int count, tl_token_logprob *o
 int tl_engine_set_penalties(tl_engine *e, int slot, float repetition_penalty, float presence_penalty, float frequency_penalty);
 int tl_engine_set_logit_bias(tl_engine *e, int slot, const int32_t *ids, const float *values, int n);
 
+/* Grammars: regex-constrained decoding on the device (csrc/grammar.h).  A slot with a grammar may only produce
+ * text that a byte-level DFA can still accept; the allowed set changes with every token and is decided inside the processing launch,
+ * from tables uploaded once.  Nothing is uploaded per step.
+ *   vocabulary  tl_vocab: for each token id j in [0, V) a byte string, given as offsets[V + 1] (int32, non-decreasing, offsets[0] = 0)
+ *            plus bytes[offsets[V]].  A token with an empty byte string (special / control tokens) is never allowed under a grammar,
+ *            unless it is one of the grammar's EOS ids.
+ *   automaton  tl_grammar: n_states in 1 .. 32,768; table[n_states][256] uint16: the next state, 0xFFFF = no transition;
+ *            accepting[n_states] uint8; start; eos_ids[n_eos], 1 <= n_eos <= 8, distinct, in [0, V).
+ *            walk(s, j): feed token j's bytes from state s; the state reached, or DEAD if any step has no transition; an empty string
+ *            is DEAD.
+ *   state    per slot: a DFA state or TL_GRAMMAR_END.  tl_engine_set_grammar sets it to the start state.  Every token the slot produces
+ *            AND THEN FEEDS BACK advances it, at the moment penalties count a token: the pending token, at the start of the decode step
+ *            that consumes it, before that step's row is processed.  state' = END if the token is an EOS id or state is END, else
+ *            walk(state, token) with DEAD -> END.  A pending token that is never fed advances nothing.
+ *   allowed  in END: exactly the EOS ids.  Otherwise: token j with walk(s, j) != DEAD, plus the EOS ids iff accepting[s].  An EOS id is
+ *            decided by the state alone, whatever its bytes: allowed in END and in an accepting state, disallowed in every other state
+ *            even if its byte string could be walked (an EOS id ends the text; it never counts as text).
+ *   element  one more line at the end of the processing definition above, after v = v + bias[j]:
+ *                if not allowed[j]:  v = -inf
+ *            so a bias cannot resurrect a disallowed token, and a NaN logit of a disallowed token becomes -inf.  A slot with a grammar
+ *            PROCESSES: every rule of a processing slot applies to it.  Raw logits and log-probability records stay raw.
+ *   edge     a state that is not accepting and in which no token of the vocabulary can be walked gives an all -inf row.  The choice
+ *            routines then do what they do on any row without a finite maximum: token 0 (csrc/sample.h, the greedy rule and the
+ *            sampler alike); token 0 cannot be walked from that state, so the next state is END.  A vocabulary that holds all 256
+ *            single-byte tokens rules this out for an automaton whose every state can reach acceptance.
+ *   life     tl_engine_begin / tl_engine_release clear the grammar; tl_engine_move carries grammar and state, tl_engine_fork copies
+ *            them; tl_engine_verify, tl_engine_rewind and tl_engine_set_token refuse a grammar slot as they refuse any processing slot.
+ *            g == NULL clears the grammar (the slot stops processing if nothing else makes it process); setting a grammar, the same one
+ *            included, restarts at its start state.  Set on a slot that already holds a pending token, that token is still fed by the
+ *            next step and advances the new state then (tl_engine_grammar_state includes it at once).  Grammar and vocabulary memory is borrowed: both must outlive the slots that use
+ *            them, the vocabulary the grammars made from it; its V must be cfg.vocab_size.  Set the grammar before the prompt's
+ *            prefill: the last row of a prefill with want_logits is masked with the state as it stands, and nothing advances there.
+ *   determinism  a row's result depends on (row, parameters, history, state) only: not on the batch, the replay route, eager or captured
+ *            steps, or how steps are split over calls.
+ * A step with a live grammar slot runs the grammar twin of the processing launch, in a captured plan of its own; every other step is the
+ * program it was.  tl_grammar_create also walks every token of more than 16 bytes from every state, once, on the device, and keeps one bit
+ * per (state, such token) beside the table (n_states x long tokens / 8 bytes), so that no step walks a long token.
+ * The per-slot pointers and state records are allocated by the first tl_engine_set_grammar.  Bad input (offsets, a
+ * transition outside the table, start, the EOS ids, a vocabulary of another size) is TL_ERR_INVALID with nothing changed. */
+typedef struct tl_vocab tl_vocab;
+typedef struct tl_grammar tl_grammar;
+#define TL_GRAMMAR_END (-1)
+int tl_vocab_create(int vocab, const int32_t *offsets, const uint8_t *bytes, void *stream, tl_vocab **out);
+void tl_vocab_destroy(tl_vocab *v);
+int tl_grammar_create(const tl_vocab *v, int n_states, const uint16_t *table, const uint8_t *accepting, int start, const int32_t *eos_ids,
+                      int n_eos, void *stream, tl_grammar **out);
+void tl_grammar_destroy(tl_grammar *g);
+int tl_engine_set_grammar(tl_engine *e, int slot, const tl_grammar *g);
+/* state of the slot's sequence INCLUDING its pending token (the host walks the pending token on its mirror when the device has not
+ * consumed it yet); *accepting = 1 when EOS would be allowed next.  Synchronises. */
+int tl_engine_grammar_state(tl_engine *e, int slot, int *state, int *accepting);
+/* the routine over caller rows: out[i][j] = logits[i][j] where j is allowed in states_dev[i] (a state or TL_GRAMMAR_END), else -inf;
+ * nothing else of the processing definition, nothing advanced.  Stream ordered. */
+int tl_grammar_mask_rows(const tl_grammar *g, const void *logits_dev, int rows, const int32_t *states_dev, void *out_dev, void *stream);
+
 /* Scoring a given text: behaves like tl_engine_prefill(e, slot, tokens, n, want_logits = 0) for the KV cache and the context (same
  * limits: n <= max_prefill_rows, chunks longer than 8 tokens need head_dim 128), and also keeps every row: the final RMSNorm over the
  * chunk, the lm_head through the W4 GEMM in blocks of rows into a scoring scratch (allocated on first use), then the log-probability

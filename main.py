@@ -36,6 +36,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --solution engine: subtract this from the logit of every token the output already holds (0 = off)")
     ap.add_argument("--frequency-penalty", type=float, default=0.0,
                     help="with --solution engine: subtract this times the token's count in the output (0 = off)")
+    ap.add_argument("--regex", default=None, metavar="PATTERN",
+                    help="with --solution engine: the answer must match PATTERN in full (tiny_llm_hip.grammar's dialect), enforced on the "
+                         "device token by token; the vocabulary comes from the loaded tokenizer")
     ap.add_argument("--enable-thinking", action="store_true")
     ap.add_argument("--raw-prompt", action="store_true", help="do not wrap the prompt in the chat template")
     ap.add_argument("--max-new-tokens", type=int, default=256)
@@ -67,8 +70,8 @@ def main(argv=None) -> str:
             draft, draft_tok = load(args.draft_model)
             return speculative_generate(Qwen3ModelWeek3(draft), net, draft_tok, tokenizer, prompt,
                                         proposal_length=args.proposal_length)
-        if penalties != (1.0, 0.0, 0.0):
-            print("note: the penalty flags apply to --solution engine only")
+        if penalties != (1.0, 0.0, 0.0) or args.regex:
+            print("note: the penalty flags and --regex apply to --solution engine only")
         if args.sampler_temp:
             print("note: the KV-cache loop is greedy like the reference's; sampler flags apply to --solution engine only")
         _ = make_sampler  # sampler surface kept importable for callers of the library
@@ -81,40 +84,44 @@ def main(argv=None) -> str:
     engine = DecodeEngine(model, page_size=128, num_pages=pages, max_batch=1, max_prefill_rows=4096)
     eos = tokenizer.eos_token_id
     records = None
+    grammar = None
     try:
+        if args.regex and not args.draft_model:
+            from tiny_llm_hip.grammar import regex_grammar
+
+            grammar = regex_grammar(engine, tokenizer, args.regex)
         if args.draft_model:
             draft_model, draft_tok = load(args.draft_model)
             if draft_tok.get_vocab() != tokenizer.get_vocab():
                 raise ValueError("draft and target tokenizers use different token ids")
-            if penalties != (1.0, 0.0, 0.0):
-                print("note: speculative decoding verifies the raw logits; the penalty flags do not apply with a draft model")
+            if penalties != (1.0, 0.0, 0.0) or args.regex:
+                print("note: speculative decoding verifies the raw logits; the penalty flags and --regex do not apply with a draft model")
             draft = DecodeEngine(draft_model, page_size=128, num_pages=pages, max_batch=1, max_prefill_rows=4096)
             try:
                 out = speculative_generate_ids(engine, draft, ids, args.max_new_tokens,
                                                proposal_length=min(args.proposal_length, 7), eos_token_id=eos)
             finally:
                 draft.close()
-        elif args.sampler_temp and (args.sampler_seed is not None or penalties != (1.0, 0.0, 0.0)):
-            # the per-slot sampler on the device: the whole generation in one prefill + one decode(N) call.  The penalties exist on the
-            # device only, so they select this path
+        elif args.sampler_temp and (args.sampler_seed is not None or penalties != (1.0, 0.0, 0.0) or grammar is not None):
+            # the per-slot sampler on the device: the whole generation in one prefill + one decode(N) call.  The penalties and the
+            # grammar exist on the device only, so they select this path
             if args.sampler_seed is None:
-                print("note: the penalty flags select the device sampler; no --sampler-seed given: seed 0")
+                print("note: the penalty flags and --regex select the device sampler; no --sampler-seed given: seed 0")
             out = engine.generate(ids, args.max_new_tokens, temperature=args.sampler_temp, top_k=args.sampler_top_k,
                                   top_p=args.sampler_top_p, seed=args.sampler_seed or 0, logprobs=args.logprobs,
-                                  repetition_penalty=penalties[0], presence_penalty=penalties[1], frequency_penalty=penalties[2])
+                                  repetition_penalty=penalties[0], presence_penalty=penalties[1], frequency_penalty=penalties[2],
+                                  grammar=grammar)
             if args.logprobs is not None:
                 out, records = out
-            if eos in out:
-                out = out[:out.index(eos)]
+            out = cut_at_eos(out, eos, grammar)
         elif args.sampler_temp:
             out = sample_with_engine(engine, ids, args, eos)
         else:
             out = engine.generate(ids, args.max_new_tokens, logprobs=args.logprobs, repetition_penalty=penalties[0],
-                                  presence_penalty=penalties[1], frequency_penalty=penalties[2])
+                                  presence_penalty=penalties[1], frequency_penalty=penalties[2], grammar=grammar)
             if args.logprobs is not None:
                 out, records = out
-            if eos in out:
-                out = out[:out.index(eos)]
+            out = cut_at_eos(out, eos, grammar)
     finally:
         engine.close()
     if records is not None:
@@ -126,6 +133,14 @@ def main(argv=None) -> str:
     text = tokenizer.decode(out)
     print(text)
     return text
+
+
+def cut_at_eos(out, eos, grammar=None):
+    """The ids before the first EOS id: the tokenizer's, or any of the grammar's."""
+    stops = set(grammar.eos_ids) if grammar is not None else set()
+    stops.add(eos)
+    cut = next((k for k, t in enumerate(out) if t in stops), len(out))
+    return out[:cut]
 
 
 def sample_with_engine(engine, ids, args, eos):

@@ -28,6 +28,42 @@ namespace tl {
 
 using namespace tl;
 
+// the vocabulary as byte strings and a byte-level automaton over it (grammar.h): device copies for the kernels, host copies for
+// validation and tl_engine_grammar_state's walk of a pending token
+struct tl_vocab {
+    int vocab = 0;
+    std::vector<int32_t> offsets;
+    std::vector<uint8_t> bytes;
+    char *mem = nullptr;
+    int32_t *offsets_dev = nullptr;
+    uint8_t *bytes_dev = nullptr;
+    // the long tokens (more than GR_LONG bytes): their ids, ascending, and per token its number among them
+    std::vector<int32_t> long_ids;
+    int32_t *long_index_dev = nullptr, *long_ids_dev = nullptr;
+};
+struct tl_grammar {
+    const tl_vocab *vocab = nullptr;
+    int n_states = 0, start = 0;
+    std::vector<uint16_t> table;
+    std::vector<uint8_t> accepting;
+    std::vector<int32_t> eos;
+    char *mem = nullptr;
+    GrammarDev *dev = nullptr;  // what a slot's pointer is poked to
+    bool is_eos(int token) const { return std::find(eos.begin(), eos.end(), token) != eos.end(); }
+    // state' of the definition, on the host copies
+    int advance(int state, int token) const {
+        if (state < 0 || token < 0 || token >= vocab->vocab || is_eos(token)) return GR_END;
+        const int b0 = vocab->offsets[token], b1 = vocab->offsets[token + 1];
+        if (b1 <= b0) return GR_END;
+        uint32_t st = (uint32_t)state;
+        for (int k = b0; k < b1; ++k) {
+            st = table[(size_t)st * 256 + vocab->bytes[k]];
+            if (st == GR_DEAD) return GR_END;
+        }
+        return (int)st;
+    }
+};
+
 struct tl_engine {
     tl_engine_config cfg{};
     std::vector<tl_layer_weights> layers;
@@ -124,13 +160,20 @@ struct tl_engine {
         float repetition = 1.f, presence = 0.f, frequency = 0.f;
         std::vector<int32_t> bias_ids;
         std::vector<float> bias_values;
-        bool processes() const { return repetition != 1.f || presence != 0.f || frequency != 0.f || !bias_ids.empty(); }
+        const tl_grammar *grammar = nullptr;  // tl_engine_set_grammar (borrowed)
+        bool processes() const { return repetition != 1.f || presence != 0.f || frequency != 0.f || !bias_ids.empty() || grammar; }
     };
     std::vector<PenaltyParams> pen;
     char *pen_mem = nullptr;
     uint16_t *pen_history = nullptr, *pen_rows = nullptr;
     float *pen_rep = nullptr, *pen_pres = nullptr, *pen_freq = nullptr, *pen_bias_values = nullptr;
     int32_t *pen_bias_n = nullptr, *pen_bias_ids = nullptr;
+    // grammars (tl_engine_set_grammar, grammar.h): allocated by the first call that sets one -- per slot the automaton's device pointer
+    // and the state record; gr_pending (kept for every slot, grammar or not): the slot holds a pending token no step has consumed yet
+    char *gr_mem = nullptr;
+    const GrammarDev **gr_ptr = nullptr;
+    GrammarRecord *gr_state = nullptr;
+    std::vector<char> gr_pending;
     // tl_engine_score: the logits of one block of rows and the per-row targets / results, allocated on first use
     uint16_t *score_logits = nullptr;
     int32_t *score_ids = nullptr, *score_argmax = nullptr;
@@ -563,6 +606,35 @@ static bool step_processes(const tl_engine *e, int batch) {
     return false;
 }
 
+// does some live slot of [0, batch) hold a grammar?  (its own plan-key bit: the step's processing launch is the grammar twin)
+static bool step_grammar(const tl_engine *e, int batch) {
+    for (int b = 0; b < batch; ++b)
+        if (step_processes_slot(e, b) && e->pen[b].grammar) return true;
+    return false;
+}
+
+// the per-slot automaton pointers and state records: allocated by the first tl_engine_set_grammar
+static int gr_alloc(tl_engine *e) {
+    if (e->gr_mem) return TL_OK;
+    const size_t B = (size_t)e->cfg.max_batch, bytes = B * (sizeof(GrammarDev *) + sizeof(GrammarRecord));
+    char *m = nullptr;
+    if (hipMalloc((void **)&m, bytes) != hipSuccess) return fail(TL_ERR_HIP, "engine: hipMalloc(grammar slots) failed");
+    if (hipMemsetAsync(m, 0, bytes, e->stream) != hipSuccess) {
+        (void)hipFree(m);
+        return fail(TL_ERR_HIP, "engine: memset(grammar slots) failed");
+    }
+    e->gr_mem = m;
+    e->gr_ptr = (const GrammarDev **)m;
+    e->gr_state = (GrammarRecord *)(m + B * sizeof(GrammarDev *));
+    e->stats.workspace_bytes += bytes;
+    return TL_OK;
+}
+// the slot's record becomes {no context length, state}
+static void gr_poke_state(tl_engine *e, int slot, int state, std::vector<std::pair<int32_t *, int32_t>> &pk) {
+    pk.emplace_back(&e->gr_state[slot].tag, -1);
+    pk.emplace_back(&e->gr_state[slot].state, state);
+}
+
 // the history table, the processed rows and the per-slot parameters: one allocation, made by the first call that makes a slot process
 static int pen_alloc(tl_engine *e) {
     if (e->pen_mem) return TL_OK;
@@ -608,6 +680,13 @@ static int pen_write(tl_engine *e, int slot, const tl_engine::PenaltyParams &v) 
     if (cur.frequency != v.frequency) pk.emplace_back((int32_t *)(e->pen_freq + slot), __builtin_bit_cast(int32_t, v.frequency));
     const bool bias_changed = cur.bias_ids != v.bias_ids || memcmp(cur.bias_values.data(), v.bias_values.data(), v.bias_values.size() * 4) != 0;
     if (bias_changed) pk.emplace_back(e->pen_bias_n + slot, (int32_t)v.bias_ids.size());
+    if (cur.grammar != v.grammar) {  // the automaton's pointer (two words) and, for a new one, the record at its start state
+        TL_TRY(gr_alloc(e));
+        const uint64_t ptr = (uint64_t)(uintptr_t)(v.grammar ? v.grammar->dev : nullptr);
+        pk.emplace_back((int32_t *)(e->gr_ptr + slot), (int32_t)(uint32_t)ptr);
+        pk.emplace_back((int32_t *)(e->gr_ptr + slot) + 1, (int32_t)(uint32_t)(ptr >> 32));
+        if (v.grammar) gr_poke_state(e, slot, v.grammar->start, pk);
+    }
     cur = v;
     if (bias_changed && !cur.bias_ids.empty()) {  // (from the mirror: it outlives the copy)
         TL_HIP(hipMemcpyAsync(e->pen_bias_ids + (size_t)slot * LPR_MAX_BIAS, cur.bias_ids.data(), cur.bias_ids.size() * 4, hipMemcpyHostToDevice, e->stream));
@@ -627,16 +706,23 @@ static int pen_carry(tl_engine *e, int src, int dst, bool move) {
         const size_t V = (size_t)e->cfg.vocab_size;
         TL_HIP(hipMemcpyAsync(e->pen_history + (size_t)dst * V, e->pen_history + (size_t)src * V, V * 2, hipMemcpyDeviceToDevice, e->stream));
     }
+    if (v.grammar) {  // the automaton state travels like the history
+        TL_HIP(hipMemcpyAsync(e->gr_state + dst, e->gr_state + src, sizeof(GrammarRecord), hipMemcpyDeviceToDevice, e->stream));
+    }
     return move ? pen_reset(e, src) : TL_OK;
 }
 
 // the processing launch over `rows` rows of raw logits for slots slot0 .. (logit_process.h): processed rows into `out`.  A decode step
 // passes the pending tokens (counted before the row is processed); a prefill's last row has none to count.
 static void launch_logit_process(tl_engine *e, const uint16_t *logits, uint16_t *out, int rows, int slot0, const int32_t *tokens, ProfCtx *pc) {
+    bool grammar = false;
+    for (int i = 0; i < rows; ++i) grammar |= step_processes_slot(e, slot0 + i) && e->pen[slot0 + i].grammar;
     const LogitProcessArgs a{logits, out, e->cfg.vocab_size, slot0, e->pen_history, e->pen_rep, e->pen_pres, e->pen_freq, e->pen_bias_n,
-                             e->pen_bias_ids, e->pen_bias_values, tokens, pc ? pc->buf : nullptr};
+                             e->pen_bias_ids, e->pen_bias_values, tokens, pc ? pc->buf : nullptr,
+                             grammar ? e->gr_ptr : nullptr, grammar ? e->gr_state : nullptr, grammar ? e->context_lens : nullptr};
     const dim3 grid(ceil_div(e->cfg.vocab_size, LPR_CHUNK), rows);
-    hipLaunchKernelGGL(logit_process_kernel, grid, dim3(LPR_THREADS), 0, e->stream, a);
+    if (grammar) hipLaunchKernelGGL(logit_process_kernel<true>, grid, dim3(LPR_THREADS), 0, e->stream, a);
+    else hipLaunchKernelGGL(logit_process_kernel<false>, grid, dim3(LPR_THREADS), 0, e->stream, a);
     if (pc) prof_after(pc, 7, (int)(grid.x * grid.y));
 }
 
@@ -1477,6 +1563,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->slot_produced.assign(c.max_batch, 0);
     e->smp.assign(c.max_batch, tl_engine::SampleParams{});
     e->pen.assign(c.max_batch, tl_engine::PenaltyParams{});
+    e->gr_pending.assign(c.max_batch, 0);
     e->free_pages.resize(c.num_pages);
     for (int i = 0; i < c.num_pages; ++i) e->free_pages[i] = c.num_pages - 1 - i;  // pop_back hands out 0,1,2,...
     e->page_was_used.assign(c.num_pages, 0);
@@ -1582,6 +1669,7 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     if (e->smp_mem) (void)hipFree(e->smp_mem);
     if (e->lp_mem) (void)hipFree(e->lp_mem);
     if (e->pen_mem) (void)hipFree(e->pen_mem);
+    if (e->gr_mem) (void)hipFree(e->gr_mem);
     if (e->score_logits) (void)hipFree(e->score_logits);
     if (e->kpool) (void)hipFree(e->kpool);
     if (e->vpool) (void)hipFree(e->vpool);
@@ -1620,6 +1708,7 @@ extern "C" int tl_engine_begin(tl_engine *e, int slot) {
     e->slot_live[slot] = 1;
     e->slot_ctx[slot] = 0;
     e->slot_produced[slot] = 0;
+    e->gr_pending[slot] = 0;
     std::vector<std::pair<int32_t *, int32_t>> pk;
     pk.emplace_back(e->live + slot, 1);
     pk.emplace_back(e->context_lens + slot, 0);
@@ -1651,6 +1740,7 @@ extern "C" int tl_engine_release(tl_engine *e, int slot) {
     pages.clear();
     e->slot_live[slot] = 0;
     e->slot_ctx[slot] = 0;
+    e->gr_pending[slot] = 0;
     pk.emplace_back(e->live + slot, 0);
     pk.emplace_back(e->context_lens + slot, 0);
     pk.emplace_back(e->tokens + slot, 0);
@@ -1728,6 +1818,7 @@ extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
     e->slot_live[dst] = 1;
     e->slot_ctx[dst] = ctx;
     e->slot_produced[dst] = 0;
+    e->gr_pending[dst] = e->gr_pending[src];
     pk.emplace_back(e->live + dst, 1);
     pk.emplace_back(e->context_lens + dst, ctx);
     pk.emplace_back(e->produced + dst, 0);
@@ -1773,6 +1864,8 @@ extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
     e->slot_live[src] = 0;
     e->slot_produced[dst] = 0;
     e->slot_produced[src] = 0;
+    e->gr_pending[dst] = e->gr_pending[src];
+    e->gr_pending[src] = 0;
     // the sampling parameters go with the sequence
     if (!smp_is_default(e->smp[src]) || !smp_is_default(e->smp[dst])) {
         const tl_engine::SampleParams v = e->smp[src];
@@ -1851,6 +1944,145 @@ extern "C" int tl_engine_set_logit_bias(tl_engine *e, int slot, const int32_t *i
     return pen_write(e, slot, v);
 }
 
+// ---- grammars (grammar.h) ----------------------------------------------------------------------------------------------------------
+extern "C" int tl_vocab_create(int vocab, const int32_t *offsets, const uint8_t *bytes, void *stream, tl_vocab **out) {
+    TL_REQUIRE(out, "vocab_create: null argument");
+    *out = nullptr;
+    TL_REQUIRE(offsets, "vocab_create: null argument");
+    TL_REQUIRE(vocab > 0 && vocab <= SMP_MAX_VOCAB, "vocab_create: vocabulary out of range (1 .. 524,288)");
+    TL_REQUIRE(offsets[0] == 0, "vocab_create: offsets[0] must be 0");
+    for (int j = 0; j < vocab; ++j) TL_REQUIRE(offsets[j + 1] >= offsets[j], "vocab_create: offsets must be non-decreasing");
+    const size_t nb = (size_t)offsets[vocab];
+    TL_REQUIRE(nb == 0 || bytes, "vocab_create: null bytes");
+    auto v = std::make_unique<tl_vocab>();
+    v->vocab = vocab;
+    v->offsets.assign(offsets, offsets + vocab + 1);
+    v->bytes.assign(bytes, bytes + nb);
+    std::vector<int32_t> long_index((size_t)vocab, 0);
+    for (int j = 0; j < vocab; ++j)
+        if (offsets[j + 1] - offsets[j] > GR_LONG) {
+            long_index[j] = (int32_t)v->long_ids.size();
+            v->long_ids.push_back(j);
+        }
+    const size_t o_bytes = align_up((size_t)(vocab + 1) * 4, 256), o_index = o_bytes + align_up(nb + 16, 256),
+                 o_ids = o_index + align_up((size_t)vocab * 4, 256), total = o_ids + align_up(v->long_ids.size() * 4 + 4, 256);
+    if (hipMalloc((void **)&v->mem, total) != hipSuccess) return fail(TL_ERR_HIP, "vocab_create: hipMalloc failed");
+    v->offsets_dev = (int32_t *)v->mem, v->bytes_dev = (uint8_t *)(v->mem + o_bytes);
+    v->long_index_dev = (int32_t *)(v->mem + o_index), v->long_ids_dev = (int32_t *)(v->mem + o_ids);
+    hipError_t he = hipMemcpyAsync(v->offsets_dev, v->offsets.data(), (size_t)(vocab + 1) * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess && nb) he = hipMemcpyAsync(v->bytes_dev, v->bytes.data(), nb, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(v->long_index_dev, long_index.data(), (size_t)vocab * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess && !v->long_ids.empty())
+        he = hipMemcpyAsync(v->long_ids_dev, v->long_ids.data(), v->long_ids.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipStreamSynchronize((hipStream_t)stream);
+    if (he != hipSuccess) {
+        (void)hipFree(v->mem);
+        return fail(TL_ERR_HIP, std::string("vocab_create: ") + hipGetErrorString(he));
+    }
+    *out = v.release();
+    return TL_OK;
+}
+
+extern "C" void tl_vocab_destroy(tl_vocab *v) {
+    if (!v) return;
+    if (v->mem) (void)hipFree(v->mem);
+    delete v;
+}
+
+extern "C" int tl_grammar_create(const tl_vocab *v, int n_states, const uint16_t *table, const uint8_t *accepting, int start, const int32_t *eos_ids,
+                                 int n_eos, void *stream, tl_grammar **out) {
+    TL_REQUIRE(out, "grammar_create: null argument");
+    *out = nullptr;
+    TL_REQUIRE(v && table && accepting && eos_ids, "grammar_create: null argument");
+    TL_REQUIRE(n_states >= 1 && n_states <= GR_MAX_STATES, "grammar_create: between 1 and 32,768 states");
+    TL_REQUIRE(start >= 0 && start < n_states, "grammar_create: start state out of range");
+    TL_REQUIRE(n_eos >= 1 && n_eos <= GR_MAX_EOS, "grammar_create: between 1 and 8 EOS ids");
+    for (int i = 0; i < n_eos; ++i) {
+        TL_REQUIRE(eos_ids[i] >= 0 && eos_ids[i] < v->vocab, "grammar_create: EOS id out of range");
+        for (int k = 0; k < i; ++k) TL_REQUIRE(eos_ids[k] != eos_ids[i], "grammar_create: an EOS id appears twice");
+    }
+    const size_t cells = (size_t)n_states * 256;
+    for (size_t i = 0; i < cells; ++i) TL_REQUIRE(table[i] == GR_DEAD || table[i] < n_states, "grammar_create: a transition leads outside the table");
+    auto g = std::make_unique<tl_grammar>();
+    g->vocab = v, g->n_states = n_states, g->start = start;
+    g->table.assign(table, table + cells);
+    g->accepting.assign(accepting, accepting + n_states);
+    g->eos.assign(eos_ids, eos_ids + n_eos);
+    // long_bits: one bit per (state, long token of the vocabulary), rows of whole 64-bit ballots
+    const int n_long = (int)v->long_ids.size(), long_words = 2 * ceil_div(n_long, 64);
+    const size_t o_table = 256, o_acc = o_table + align_up(cells * 2, 256), o_long = o_acc + align_up((size_t)n_states, 256),
+                 total = o_long + align_up((size_t)n_states * long_words * 4 + 4, 256);
+    if (hipMalloc((void **)&g->mem, total) != hipSuccess) return fail(TL_ERR_HIP, "grammar_create: hipMalloc failed");
+    GrammarDev d{};
+    d.table = (const uint16_t *)(g->mem + o_table), d.accepting = (const uint8_t *)(g->mem + o_acc);
+    d.offsets = v->offsets_dev, d.bytes = v->bytes_dev, d.n_states = n_states, d.n_eos = n_eos;
+    d.long_index = v->long_index_dev, d.long_bits = (const uint32_t *)(g->mem + o_long), d.long_words = long_words;
+    for (int i = 0; i < GR_MAX_EOS; ++i) d.eos[i] = i < n_eos ? eos_ids[i] : -1;
+    static_assert(sizeof(GrammarDev) <= 256, "GrammarDev heads the grammar's allocation");
+    hipError_t he = hipMemcpyAsync(g->mem, &d, sizeof(d), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(g->mem + o_table, g->table.data(), cells * 2, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(g->mem + o_acc, g->accepting.data(), (size_t)n_states, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess && n_long > 0) {  // the walks of the long tokens from every state, once, on the device
+        const GrammarLongArgs la{d.table, d.offsets, d.bytes, v->long_ids_dev, n_long, long_words, (uint32_t *)(g->mem + o_long)};
+        hipLaunchKernelGGL(grammar_long_bits_kernel, dim3(long_words / 2, n_states), dim3(64), 0, (hipStream_t)stream, la);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipStreamSynchronize((hipStream_t)stream);
+    if (he != hipSuccess) {
+        (void)hipFree(g->mem);
+        return fail(TL_ERR_HIP, std::string("grammar_create: ") + hipGetErrorString(he));
+    }
+    g->dev = (GrammarDev *)g->mem;
+    *out = g.release();
+    return TL_OK;
+}
+
+extern "C" void tl_grammar_destroy(tl_grammar *g) {
+    if (!g) return;
+    if (g->mem) (void)hipFree(g->mem);
+    delete g;
+}
+
+extern "C" int tl_engine_set_grammar(tl_engine *e, int slot, const tl_grammar *g) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(!g || g->vocab->vocab == e->cfg.vocab_size, "engine_set_grammar: the grammar's vocabulary is not the engine's size");
+    tl_engine::PenaltyParams v = e->pen[slot];
+    const bool same = g && v.grammar == g;
+    v.grammar = g;
+    TL_TRY(pen_write(e, slot, v));
+    if (same) {  // the same automaton again: back to its start state
+        std::vector<std::pair<int32_t *, int32_t>> pk;
+        gr_poke_state(e, slot, g->start, pk);
+        return poke(e, pk);
+    }
+    return TL_OK;
+}
+
+extern "C" int tl_engine_grammar_state(tl_engine *e, int slot, int *state, int *accepting) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(state, "engine_grammar_state: null argument");
+    const tl_grammar *g = e->pen[slot].grammar;
+    TL_REQUIRE(g, "engine_grammar_state: the slot has no grammar");
+    TL_HIP(hipStreamSynchronize(e->stream));
+    GrammarRecord rec{};
+    int32_t pending = 0;
+    TL_HIP(hipMemcpy(&rec, e->gr_state + slot, sizeof(rec), hipMemcpyDeviceToHost));
+    TL_HIP(hipMemcpy(&pending, e->tokens + slot, 4, hipMemcpyDeviceToHost));
+    const int st = e->gr_pending[slot] ? g->advance(rec.state, pending) : rec.state;
+    *state = st;
+    if (accepting) *accepting = st < 0 || g->accepting[st] ? 1 : 0;
+    return TL_OK;
+}
+
+extern "C" int tl_grammar_mask_rows(const tl_grammar *g, const void *logits_dev, int rows, const int32_t *states_dev, void *out_dev, void *stream) {
+    TL_REQUIRE(g && logits_dev && states_dev && out_dev, "grammar_mask_rows: null argument");
+    TL_REQUIRE(rows > 0 && rows <= 65535, "grammar_mask_rows: rows out of range");
+    const GrammarMaskArgs a{g->dev, (const uint16_t *)logits_dev, (uint16_t *)out_dev, states_dev, g->vocab->vocab};
+    hipLaunchKernelGGL(grammar_mask_rows_kernel, dim3(ceil_div(g->vocab->vocab, 2048), rows), dim3(256), 0, (hipStream_t)stream, a);
+    TL_CHECK_LAUNCH("grammar_mask_rows");
+    return TL_OK;
+}
+
 extern "C" int tl_process_logits(const void *logits_dev, int rows, int vocab, const uint16_t *history_dev, const float *repetition_dev,
                                  const float *presence_dev, const float *frequency_dev, const int32_t *bias_ids_dev, const float *bias_values_dev,
                                  const int32_t *bias_n_dev, void *out_dev, void *stream) {
@@ -1859,8 +2091,8 @@ extern "C" int tl_process_logits(const void *logits_dev, int rows, int vocab, co
     TL_REQUIRE(vocab > 0 && vocab <= SMP_MAX_VOCAB, "process_logits: vocabulary out of range (1 .. 524,288)");
     // (without lists every n must be 0: the kernel reads no entry then)
     const LogitProcessArgs a{(const uint16_t *)logits_dev, (uint16_t *)out_dev, vocab, 0, const_cast<uint16_t *>(history_dev), repetition_dev, presence_dev,
-                             frequency_dev, bias_n_dev, bias_ids_dev, bias_values_dev, nullptr, nullptr};
-    hipLaunchKernelGGL(logit_process_kernel, dim3(ceil_div(vocab, LPR_CHUNK), rows), dim3(LPR_THREADS), 0, (hipStream_t)stream, a);
+                             frequency_dev, bias_n_dev, bias_ids_dev, bias_values_dev, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(logit_process_kernel<false>, dim3(ceil_div(vocab, LPR_CHUNK), rows), dim3(LPR_THREADS), 0, (hipStream_t)stream, a);
     TL_CHECK_LAUNCH("process_logits");
     return TL_OK;
 }
@@ -2038,6 +2270,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
     }
     for (int i = 0; i < n_seqs; ++i) {
         e->slot_ctx[seqs[i].slot] = seqs[i].start + seqs[i].len;
+        e->gr_pending[seqs[i].slot] = 0;  // a pending token that is prefilled past is never fed
         pk.emplace_back(e->context_lens + seqs[i].slot, seqs[i].start + seqs[i].len);
     }
     TL_TRY(poke(e, pk));
@@ -2057,6 +2290,7 @@ static int prefill_first_token(tl_engine *e, int slot, const uint16_t *logits, c
     launch_step_end(e, step_end_args(e, logits, slot, 0, e->h), 1, e->smp[slot].samples(), step_logprobs_slot(e, slot), raw);
     TL_CHECK_LAUNCH(what);
     e->slot_produced[slot] += 1;
+    e->gr_pending[slot] = 1;
     return TL_OK;
 }
 
@@ -2256,6 +2490,7 @@ static void step_done(tl_engine *e, int batch) {
         if (!e->slot_live[b]) continue;
         e->slot_ctx[b] += 1;
         e->slot_produced[b] += 1;
+        e->gr_pending[b] = 1;
     }
     e->stats.decode_steps++;
     e->logits_rows = batch;
@@ -2275,6 +2510,7 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
     launch_embed_slots(e, batch);
     TL_CHECK_LAUNCH("engine embed");
     const bool samples = step_samples(e, batch), logprobs = step_logprobs(e, batch), processes = step_processes(e, batch);
+    const bool grammar = processes && step_grammar(e, batch);
     bool on_queue = false;  // steps of this call are in flight on the AQL queue (the stream is idle and must stay so until they are drained)
     for (int s = 0; s < steps; ++s) {
         SplitPlan sp;
@@ -2283,7 +2519,9 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
             // bit 62: the step ends with the sampling twin of step_end_kernel, bit 61: with the logprob twin (both re-derived every call
             // from the slots' parameters)
             // bit 60: the processing launch (logit_process.h) stands between the lm_head and the step end
-            const auto key = std::make_pair(batch, sp.key() | (samples ? (1L << 62) : 0L) | (logprobs ? (1L << 61) : 0L) | (processes ? (1L << 60) : 0L));
+            // bit 59: ... and it is the grammar twin (grammar.h)
+            const auto key = std::make_pair(batch, sp.key() | (samples ? (1L << 62) : 0L) | (logprobs ? (1L << 61) : 0L) | (processes ? (1L << 60) : 0L) |
+                                                       (grammar ? (1L << 59) : 0L));
             auto it = e->graphs.find(key);
             if (it == e->graphs.end()) {
                 // The split plan (and with it the key) changes every 64 * n_splits tokens of context: a long run would keep one

@@ -8,6 +8,7 @@
 //   v = v - (f * float(count[j]))
 //   if count[j] > 0:               v = v - p
 //   v = v + bias[j]                (0 where the slot has no entry)
+//   if not allowed[j]:  v = -inf   (a slot with a grammar only: grammar.h, the GRAMMAR = true twin below)
 //   out[j] = bf16(v), round to nearest even
 // History: one uint16 per (slot, token): bit 15 = the token was in the prompt, bits 0-14 = how often the slot produced and fed it back,
 // saturating at 32,767.  A row whose slot does not process (r = 1, p = f = 0, no bias entry) is copied bit for bit.
@@ -18,6 +19,7 @@
 // into the chunk are scattered into LDS and added from there.
 #pragma once
 #include "common.h"
+#include "grammar.h"
 
 namespace tl {
 
@@ -40,6 +42,10 @@ struct LogitProcessArgs {
     const float *bias_values;    // [slots, LPR_MAX_BIAS]
     const int32_t *tokens;       // [slots] pending token ids: a decode step counts them; nullptr: nothing is counted (prefill, caller rows)
     prof_t *prof;
+    // the grammar twin only (logit_process_kernel<true>, grammar.h); poked between steps like the parameters above
+    const GrammarDev *const *grammar;  // [slots] the slot's automaton; nullptr: none
+    GrammarRecord *grammar_state;      // [slots]
+    const int32_t *context_lens;       // [slots] the tag of a record is compared with
 };
 
 __device__ __forceinline__ uint32_t lpr_count_up(uint32_t h) { return (h & LPR_COUNT) < LPR_COUNT ? h + 1u : h; }
@@ -58,8 +64,15 @@ __device__ __forceinline__ uint32_t lpr_element(uint32_t l, uint32_t h, float r,
     return (uint32_t)BF16::from_float(v);
 }
 
+// GRAMMAR = false: the program of a step without a live grammar slot, as it was.  GRAMMAR = true (its own plan-key bit): one more line at
+// the end of the element -- a token that is not allowed in the slot's automaton state becomes -inf -- and the state's advance: every
+// workgroup of a row derives the state that includes the pending token from the slot's record ({tag, state}: a record whose tag equals
+// the slot's context length already includes it, any other record is advanced here), and the row's first workgroup stores it.
+template <bool GRAMMAR>
 static __global__ __launch_bounds__(LPR_THREADS) void logit_process_kernel(const LogitProcessArgs a) {
     __shared__ float s_bias[LPR_CHUNK];
+    __shared__ __attribute__((aligned(16))) uint16_t s_table[GRAMMAR ? GR_LDS_STATES * 256 : 8];
+    __shared__ int s_state;
     const prof_t prof_t0 = prof_begin(a.prof);
     const int row = blockIdx.y, slot = a.slot0 + row;
     const int c0 = blockIdx.x * LPR_CHUNK, c = c0 + (int)threadIdx.x * 8;
@@ -68,7 +81,9 @@ static __global__ __launch_bounds__(LPR_THREADS) void logit_process_kernel(const
     uint16_t *hist = a.history + (long)slot * a.vocab;
     const float r = a.repetition[slot], p = a.presence[slot], f = a.frequency[slot];
     const int nb = min(a.bias_n[slot], LPR_MAX_BIAS);
-    const bool on = r != 1.f || p != 0.f || f != 0.f || nb > 0;  // uniform
+    const GrammarDev *gp = nullptr;
+    if constexpr (GRAMMAR) gp = a.grammar[slot];
+    const bool on = r != 1.f || p != 0.f || f != 0.f || nb > 0 || gp != nullptr;  // uniform
     const bool vec = (((uintptr_t)lg | (uintptr_t)out | (uintptr_t)hist) & 15) == 0 && c + 8 <= a.vocab;
     if (!on) {  // the row of a slot that does not process: copied, so that the step end reads one buffer
         if (vec) {
@@ -102,6 +117,15 @@ static __global__ __launch_bounds__(LPR_THREADS) void logit_process_kernel(const
         if ((unsigned)d < (unsigned)LPR_CHUNK) s_bias[d] = a.bias_values[(long)slot * LPR_MAX_BIAS + k];
     }
     __syncthreads();
+    uint32_t allowed = 0xffu;
+    if constexpr (GRAMMAR) {
+        if (gp) {  // uniform
+            GrRef g = *GR_GLOBAL(GrammarDev, gp);
+            const int state = gr_row_state(g, a.grammar_state, a.tokens, a.context_lens, slot, a.vocab, blockIdx.x == 0, &s_state);
+            const bool whole = gr_stage_table(g, state, s_table, LPR_THREADS);
+            allowed = gr_allowed8(g, state, c, a.vocab, s_table, whole);
+        }
+    }
     // the pending token (what the previous step produced and this step consumed) is counted before the row is processed
     const int pending = a.tokens ? a.tokens[slot] : -1;
     uint32_t o[4] = {0u, 0u, 0u, 0u};
@@ -113,7 +137,9 @@ static __global__ __launch_bounds__(LPR_THREADS) void logit_process_kernel(const
             act_store(hist + c + e, (uint16_t)h);
         }
         const uint32_t l = (lv[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
-        o[e >> 1] |= lpr_element(l, h, r, p, f, s_bias[threadIdx.x * 8 + e]) << ((e & 1) * 16);
+        uint32_t v = lpr_element(l, h, r, p, f, s_bias[threadIdx.x * 8 + e]);
+        if constexpr (GRAMMAR) v = (allowed >> e & 1u) ? v : 0xff80u;  // -inf
+        o[e >> 1] |= v << ((e & 1) * 16);
     }
     if (vec) {
         act_store16(out + c, u32x4{o[0], o[1], o[2], o[3]});

@@ -198,6 +198,13 @@ _SIGNATURES.update({
     "tl_engine_set_penalties": (_c_int, [_c_void_p, _c_int, _c_float, _c_float, _c_float]),
     "tl_engine_set_logit_bias": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _P(_c_float), _c_int]),
     "tl_process_logits": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 9),
+    "tl_vocab_create": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p, _P(_c_void_p)]),
+    "tl_vocab_destroy": (None, [_c_void_p]),
+    "tl_grammar_create": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _P(_c_void_p)]),
+    "tl_grammar_destroy": (None, [_c_void_p]),
+    "tl_engine_set_grammar": (_c_int, [_c_void_p, _c_int, _c_void_p]),
+    "tl_engine_grammar_state": (_c_int, [_c_void_p, _c_int, _P(_c_int), _P(_c_int)]),
+    "tl_grammar_mask_rows": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "tl_engine_read_logprobs": (_c_int, [_c_void_p, _c_int, _c_int, _P(TlTokenLogprob)]),
     "tl_engine_read_pending_logprobs": (_c_int, [_c_void_p, _c_int, _P(TlTokenLogprob)]),
     "tl_engine_score": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, ctypes.c_int32, _P(_c_float), _P(ctypes.c_int32)]),

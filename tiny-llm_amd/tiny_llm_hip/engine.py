@@ -225,6 +225,38 @@ class DecodeEngine:
         n = len(ids)
         _ext.check(_lib.tl_engine_set_logit_bias(self._h, slot, (ctypes.c_int32 * max(n, 1))(*ids), (ctypes.c_float * max(n, 1))(*vals), n))
 
+    def make_vocab(self, offsets, data=None) -> "Vocab":
+        """The vocabulary as byte strings on the device (tl_vocab_create): ``offsets`` [V + 1] and ``data`` (the concatenated bytes), as
+        grammar.vocabulary_bytes / vocabulary_bytes_from_strings return them -- or a list of V byte strings alone.  Upload it once."""
+        if data is None:
+            from .grammar import vocabulary_bytes_from_strings
+            offsets, data = vocabulary_bytes_from_strings(offsets)
+        self._vocab = Vocab(offsets, data)
+        return self._vocab
+
+    def make_grammar(self, dfa, eos_ids, vocab: "Vocab | None" = None) -> "Grammar":
+        """A byte-level automaton (grammar.compile_regex) with the token ids that end the text (tl_grammar_create), over ``vocab``
+        (default: the vocabulary of the last make_vocab)."""
+        vocab = vocab if vocab is not None else getattr(self, "_vocab", None)
+        if vocab is None:
+            raise ValueError("make_grammar: call make_vocab first (or pass a Vocab)")
+        return Grammar(vocab, dfa, eos_ids)
+
+    def set_grammar(self, slot: int, grammar: "Grammar | None") -> None:
+        """Constrain the live slot to the grammar's language (tl_engine_set_grammar), from its start state; None lifts the constraint.
+        Set it before the prompt's prefill.  begin / release clear it, move carries grammar and state, fork copies them.  The Grammar
+        (and its Vocab) must stay alive while a slot uses it."""
+        if grammar is not None and not isinstance(grammar, Grammar):
+            raise ValueError("set_grammar takes a Grammar (DecodeEngine.make_grammar) or None")
+        _ext.check(_lib.tl_engine_set_grammar(self._h, slot, grammar._h if grammar is not None else None))
+
+    def grammar_state(self, slot: int) -> tuple[int, bool]:
+        """(automaton state of the slot's sequence including its pending token, or GRAMMAR_END; whether EOS is allowed next);
+        synchronises."""
+        state, acc = ctypes.c_int(), ctypes.c_int()
+        _ext.check(_lib.tl_engine_grammar_state(self._h, slot, ctypes.byref(state), ctypes.byref(acc)))
+        return state.value, bool(acc.value)
+
     def read_logprobs(self, slot: int, count: int) -> list["TokenLogprob"]:
         """Records of the slot's last ``count`` produced tokens (like read_tokens); synchronises."""
         out = (_ext.TlTokenLogprob * max(count, 1))()
@@ -357,11 +389,12 @@ class DecodeEngine:
     def generate(self, prompt: Sequence[int], max_new_tokens: int, *, slot: int = 0, chunk: int | None = None,
                  temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None, seed: int = 0,
                  logprobs: int | None = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                 frequency_penalty: float = 0.0, logit_bias=None):
+                 frequency_penalty: float = 0.0, logit_bias=None, grammar: "Grammar | None" = None):
         """One request: prefill, then ``max_new_tokens - 1`` decode steps in one call; greedy unless ``temperature`` > 0 (the
         device sampler, set_sampling).  With ``logprobs`` an int (0 .. 20 alternatives, set_logprobs): returns (ids, records).
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` (set_penalties, set_logit_bias) are set
-        before the prefill, so the prompt's tokens are in the slot's history."""
+        before the prefill, so the prompt's tokens are in the slot's history; so is ``grammar`` (set_grammar): the ids are then text of
+        its language, followed by EOS ids once it has ended."""
         args = sampling_args(temperature, top_k, top_p, seed)
         top_n = logprobs_arg(logprobs)
         pen = penalty_args(repetition_penalty, presence_penalty, frequency_penalty)
@@ -372,6 +405,8 @@ class DecodeEngine:
                 self.set_penalties(slot, *pen)
             if bias[0]:
                 self.set_logit_bias(slot, logit_bias)
+            if grammar is not None:
+                self.set_grammar(slot, grammar)
             if args[0] > 0.0:
                 self.set_sampling(slot, *args)
             if top_n >= 0:
@@ -425,6 +460,78 @@ def sampling_args(temperature: float = 0.0, top_k: int | None = None, top_p: flo
     return float(temperature), min(int(top_k), 2**31 - 1), float(top_p), int(seed)
 
 
+GRAMMAR_END = -1  # TL_GRAMMAR_END
+
+
+class Vocab:
+    """tl_vocab: token id -> byte string, on the device.  ``offsets`` int32 [V + 1], ``data`` the bytes."""
+
+    def __init__(self, offsets, data):
+        import numpy as np
+
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        data = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data, dtype=np.uint8)
+        if offsets.ndim != 1 or offsets.size < 2 or data.ndim != 1 or int(offsets[-1]) != data.size:
+            raise ValueError("Vocab: offsets [V + 1] must end at len(data)")
+        self.size = offsets.size - 1
+        handle = ctypes.c_void_p()
+        _ext.check(_lib.tl_vocab_create(self.size, offsets.ctypes.data, data.ctypes.data if data.size else None, None, ctypes.byref(handle)))
+        self._h = handle
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _lib.tl_vocab_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Grammar:
+    """tl_grammar: a ByteDFA (table uint16 [S, 256], accepting, start) over a Vocab, with its EOS ids."""
+
+    def __init__(self, vocab: Vocab, dfa, eos_ids):
+        import numpy as np
+
+        table = np.ascontiguousarray(dfa.table, dtype=np.uint16)
+        accepting = np.ascontiguousarray(dfa.accepting, dtype=np.uint8)
+        if table.ndim != 2 or table.shape[1] != 256 or accepting.shape != (table.shape[0],):
+            raise ValueError("Grammar: table must be [S, 256] and accepting [S]")
+        eos = [int(t) for t in eos_ids]
+        arr = (ctypes.c_int32 * max(len(eos), 1))(*eos)
+        handle = ctypes.c_void_p()
+        _ext.check(_lib.tl_grammar_create(vocab._h, table.shape[0], table.ctypes.data, accepting.ctypes.data, int(dfa.start), arr, len(eos),
+                                          None, ctypes.byref(handle)))
+        self._h = handle
+        self.vocab, self.dfa, self.eos_ids = vocab, dfa, tuple(eos)  # (the vocabulary must outlive the grammar)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _lib.tl_grammar_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def request_grammars(sampling, n_prompts: int) -> list["Grammar | None"] | None:
+    """The ``"grammar"`` key of batch_generate_ids' ``sampling`` dicts: per prompt a Grammar or None."""
+    if sampling is None:
+        return None
+    dicts = [sampling] * n_prompts if isinstance(sampling, dict) else list(sampling)
+    out = [d.get("grammar") if isinstance(d, dict) else None for d in dicts]
+    for g in out:
+        if g is not None and not isinstance(g, Grammar):
+            raise ValueError("sampling['grammar'] must be a Grammar (DecodeEngine.make_grammar) or None")
+    return out
+
+
 def penalty_args(repetition: float = 1.0, presence: float = 0.0, frequency: float = 0.0) -> tuple[float, float, float]:
     """Validated (repetition, presence, frequency) for tl_engine_set_penalties: repetition finite and > 0 (1 = off), presence and
     frequency finite (0 = off; negative values encourage repetition)."""
@@ -437,7 +544,7 @@ def penalty_args(repetition: float = 1.0, presence: float = 0.0, frequency: floa
 
 
 _SAMPLING_KEYS = {"temperature", "top_k", "top_p", "seed"}
-_PENALTY_KEYS = {"repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias"}
+_PENALTY_KEYS = {"repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "grammar"}  # (grammar: request_grammars)
 
 
 def request_penalties(sampling, n_prompts: int, vocab_size: int) -> list[tuple[tuple[float, float, float], dict]] | None:
@@ -504,7 +611,8 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     Token-id in, token-id out (no tokenizer can be downloaded here).  Needs ``engine.max_batch >= batch_size + 1``:
     the last slot is the prefill staging slot.  Returns [(prompt_idx, generated ids)] in completion order.
     ``sampling``: None (greedy), one dict or one dict per prompt (request_sampling; the dicts also take repetition_penalty /
-    presence_penalty / frequency_penalty / logit_bias, request_penalties); applied when a request enters the staging slot,
+    presence_penalty / frequency_penalty / logit_bias, request_penalties, and ``grammar``: a Grammar, whose EOS ids then end the request
+    like ``eos_token_id``); applied when a request enters the staging slot,
     and carried by the engine through its slot moves.  ``logprobs``: None, or an int (0 .. 20 alternatives): every request records
     its tokens' log-probabilities (set_logprobs), read in the same turn as the pending ids, and the result is
     [(prompt_idx, generated ids, records)]."""
@@ -515,6 +623,11 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     limits = [max_new_tokens] * len(prompts) if isinstance(max_new_tokens, int) else list(max_new_tokens)
     per_request = request_sampling(sampling, len(prompts), base_seed)
     per_request_pen = None if sampling is None else request_penalties(sampling, len(prompts), engine.vocab_size)
+    per_request_gr = request_grammars(sampling, len(prompts))
+
+    def ends(req, token):  # the request's own EOS ids where it has a grammar
+        return token == eos_token_id or (req["eos"] is not None and token in req["eos"])
+
     top_n = logprobs_arg(logprobs)
     staging = batch_size
     queue = list(range(len(prompts)))
@@ -536,9 +649,12 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                         engine.set_penalties(staging, *pen)
                     if bias:
                         engine.set_logit_bias(staging, bias)
+                grammar = per_request_gr[idx] if per_request_gr is not None else None
+                if grammar is not None:
+                    engine.set_grammar(staging, grammar)
                 if top_n >= 0:
                     engine.set_logprobs(staging, top_n)
-                pending = {"idx": idx, "tokens": [int(t) for t in prompts[idx]], "offset": 0, "out": [], "limit": limits[idx], "lp": []}
+                pending = {"eos": grammar.eos_ids if grammar is not None else None, "idx": idx, "tokens": [int(t) for t in prompts[idx]], "offset": 0, "out": [], "limit": limits[idx], "lp": []}
             if pending is not None:
                 total = len(pending["tokens"])
                 if pending["offset"] < total:
@@ -551,7 +667,7 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                         if top_n >= 0:
                             pending["lp"].append(engine.read_logprobs(staging, 1)[0])
                 if pending["offset"] >= total:
-                    done = len(pending["out"]) >= pending["limit"] or pending["out"][-1] == eos_token_id
+                    done = len(pending["out"]) >= pending["limit"] or ends(pending, pending["out"][-1])
                     if done:
                         engine.release(staging)
                         live_slots.discard(staging)
@@ -602,7 +718,7 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                     req["out"].append(tokens[i])
                     if records is not None:
                         req["lp"].append(records[i])
-                    if len(req["out"]) >= req["limit"] or tokens[i] == eos_token_id:
+                    if len(req["out"]) >= req["limit"] or ends(req, tokens[i]):
                         engine.release(i)
                         live_slots.discard(i)
                         finished.append((req["idx"], req["out"]) + ((req["lp"],) if top_n >= 0 else ()))
