@@ -33,8 +33,13 @@ def main(argv=None):
     ap.add_argument("--repetition-penalty", type=float, default=1.0, help="per request, on the device; over prompt and output (1 = off)")
     ap.add_argument("--presence-penalty", type=float, default=0.0, help="per request, on the device; over the output (0 = off)")
     ap.add_argument("--frequency-penalty", type=float, default=0.0, help="per request, on the device; times the count in the output (0 = off)")
-    ap.add_argument("--regex", default=None, metavar="PATTERN",
-                    help="every answer must match PATTERN in full (tiny_llm_hip.grammar's dialect), enforced on the device per request")
+    constraint = ap.add_mutually_exclusive_group()
+    constraint.add_argument("--regex", default=None, metavar="PATTERN",
+                            help="every answer must match PATTERN in full (tiny_llm_hip.grammar's dialect), enforced on the device per request")
+    constraint.add_argument("--json", default=None, choices=["object", "value"],
+                            help="JSON mode: every answer is one JSON object (or any JSON value), enforced on the device per request")
+    constraint.add_argument("--json-schema", default=None, metavar="FILE",
+                            help="every answer is compact JSON that conforms to the schema in FILE (tiny_llm_hip.grammar.schema_regex)")
     ap.add_argument("--prompts-file", default=None, help="one prompt per line (default: five built-in questions)")
     args = ap.parse_args(argv)
 
@@ -63,11 +68,12 @@ def main(argv=None):
                         frequency_penalty=args.frequency_penalty)
     stops = {tokenizer.eos_token_id}
     try:
-        if args.regex:
-            from tiny_llm_hip.grammar import regex_grammar
+        from tiny_llm_hip.grammar import cli_grammar
 
-            sampling["grammar"] = regex_grammar(engine, tokenizer, args.regex)
-            stops |= set(sampling["grammar"].eos_ids)
+        grammar = cli_grammar(engine, tokenizer, args.regex, args.json, args.json_schema)
+        if grammar is not None:
+            sampling["grammar"] = grammar
+            stops |= set(grammar.eos_ids)
         done = batch_generate_ids(engine, encoded, limits, batch_size=args.batch_size, prefill_step=args.prefill_step,
                                   eos_token_id=tokenizer.eos_token_id, sampling=sampling or None, base_seed=args.sampler_seed)
     finally:

@@ -342,6 +342,44 @@ int tl_engine_grammar_state(tl_engine *e, int slot, int *state, int *accepting);
  * nothing else of the processing definition, nothing advanced.  Stream ordered. */
 int tl_grammar_mask_rows(const tl_grammar *g, const void *logits_dev, int rows, const int32_t *states_dev, void *out_dev, void *stream);
 
+/* Stack grammars: JSON mode (csrc/grammar_stack.h).  Nested brackets are not regular; a stack grammar is the
+ * automaton above with a bounded stack beside the state.  It is a tl_grammar made by a second constructor: everything that takes a
+ * tl_grammar accepts it (tl_engine_set_grammar in particular), and every rule of the grammar section holds with a CONFIGURATION in place
+ * of a state.
+ *   tables   table[n_states][256] uint16: 0xFFFF = no transition; otherwise the next state or, for a pop, an index into pop_table.
+ *            ops[n_states][256] uint8: 0 = no stack operation, 1 .. 4 = push symbol op - 1 (four stack symbols), 5 = pop; any other
+ *            value is TL_ERR_INVALID.  pop_table[n_pop][5] uint16, 0 <= n_pop <= 65,535: the state after a pop, indexed by the NEW top of
+ *            the stack (0 .. 3), or 4 when the stack became empty; 0xFFFF = dead.  accepting, start, eos_ids as above.  A non-pop
+ *            entry must be < n_states, a pop entry < n_pop, a pop_table entry 0xFFFF or < n_states.
+ *   configuration  per slot (state, depth, stack): depth in 0 .. 32; stack a uint64 with the symbol of level i (0 = bottom) in bits
+ *            2i, 2i + 1 and zero above bit 2 * depth.  TL_GRAMMAR_END is (-1, 0, 0).  tl_engine_set_grammar sets (start, 0, 0).
+ *   one byte b from (s, d, stack):  t = table[s][b]; DEAD if t == 0xFFFF.  op 0: s' = t.  Push a: DEAD if d == 32, else append a and
+ *            s' = t.  Pop: DEAD if d == 0, else drop the top; top' = the new top, or 4 when the stack is now empty;
+ *            s' = pop_table[t][top'], DEAD if that is 0xFFFF.
+ *   walk / advance / allowed  the definitions above on configurations, for a token of up to 16 bytes; the advance of a slot with its
+ *            pending token walks the real stack at ANY token length.  EOS is allowed iff accepting[state] (acceptance by final state:
+ *            an automaton that wants "empty stack" at the end encodes the top of the stack in its states, as grammar.compile_json
+ *            does), or in END.
+ *   long tokens  (more than 16 bytes) are not walked in a step, and a bit per (state, token) cannot know the stack.  A long token is
+ *            allowed in (s, d, stack) iff its walk from (s, EMPTY stack) never dies -- so it never pops below the level it starts at --
+ *            and the largest depth m that walk reaches satisfies d + m <= 32.  tl_grammar_create_stack computes one byte per
+ *            (state, long token), once, on the device: m, or 0xFF.  RESTRICTION: a long token that closes a container opened before
+ *            it is therefore never allowed, and one that returns to its starting level continues as if the stack were empty there;
+ *            the text stays reachable through shorter tokens.
+ *   life     as for any grammar: begin / release clear, move carries, fork copies the configuration; verify, rewind and set_token
+ *            refuse the slot.
+ * A step with a live stack-grammar slot runs the third twin of the processing launch, in a captured plan of its own; it serves the
+ * regex-grammar and grammar-less rows of that step with the results the other twins give.  Every other step is the program it was. */
+int tl_grammar_create_stack(const tl_vocab *v, int n_states, const uint16_t *table, const uint8_t *ops, int n_pop, const uint16_t *pop_table,
+                            const uint8_t *accepting, int start, const int32_t *eos_ids, int n_eos, void *stream, tl_grammar **out);
+/* companion of tl_engine_grammar_state (which keeps returning the state alone): the configuration of the slot's sequence INCLUDING its
+ * pending token; a regex grammar reports depth 0 and an empty stack.  Synchronises. */
+int tl_engine_grammar_config(tl_engine *e, int slot, int *state, int *depth, uint64_t *stack, int *accepting);
+/* the routine over caller rows for a stack grammar: row i is masked in (states_dev[i], depths_dev[i], stacks_dev[i]); a state of
+ * TL_GRAMMAR_END ignores the rest.  tl_grammar_mask_rows refuses a stack grammar, this routine a regex grammar (TL_ERR_INVALID). */
+int tl_grammar_mask_rows_stack(const tl_grammar *g, const void *logits_dev, int rows, const int32_t *states_dev, const int32_t *depths_dev,
+                               const uint64_t *stacks_dev, void *out_dev, void *stream);
+
 /* Scoring a given text: behaves like tl_engine_prefill(e, slot, tokens, n, want_logits = 0) for the KV cache and the context (same
  * limits: n <= max_prefill_rows, chunks longer than 8 tokens need head_dim 128), and also keeps every row: the final RMSNorm over the
  * chunk, the lm_head through the W4 GEMM in blocks of rows into a scoring scratch (allocated on first use), then the log-probability
@@ -387,6 +425,10 @@ int tl_engine_read_pending(tl_engine *e, int count, int32_t *out);
 const void *tl_engine_logits_dev(const tl_engine *e);
 /* Stream-ordered device-to-device copy of the first `rows` logits rows into dst_dev ([rows, vocab] bf16). */
 int tl_engine_copy_logits(tl_engine *e, void *dst_dev, int rows);
+/* The same for the PROCESSED rows of the last decode step in which some live slot processed its logits (penalties, bias, grammar): row
+ * i is what slot i's token was chosen from; the row of a slot that does not process is its raw row.  TL_ERR_INVALID before any slot of
+ * the engine has processed. */
+int tl_engine_copy_processed_logits(tl_engine *e, void *dst_dev, int rows);
 /* Device pointer to the pending token ids [max_batch] int32. */
 const int32_t *tl_engine_tokens_dev(const tl_engine *e);
 

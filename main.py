@@ -36,9 +36,16 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --solution engine: subtract this from the logit of every token the output already holds (0 = off)")
     ap.add_argument("--frequency-penalty", type=float, default=0.0,
                     help="with --solution engine: subtract this times the token's count in the output (0 = off)")
-    ap.add_argument("--regex", default=None, metavar="PATTERN",
-                    help="with --solution engine: the answer must match PATTERN in full (tiny_llm_hip.grammar's dialect), enforced on the "
-                         "device token by token; the vocabulary comes from the loaded tokenizer")
+    constraint = ap.add_mutually_exclusive_group()
+    constraint.add_argument("--regex", default=None, metavar="PATTERN",
+                            help="with --solution engine: the answer must match PATTERN in full (tiny_llm_hip.grammar's dialect), enforced "
+                                 "on the device token by token; the vocabulary comes from the loaded tokenizer")
+    constraint.add_argument("--json", default=None, choices=["object", "value"],
+                            help="with --solution engine: JSON mode -- the answer is one JSON object (or any JSON value), nested up to "
+                                 "32 levels, enforced on the device by a stack automaton (tiny_llm_hip.grammar.compile_json)")
+    constraint.add_argument("--json-schema", default=None, metavar="FILE",
+                            help="with --solution engine: the answer is compact JSON that conforms to the schema in FILE (the "
+                                 "non-recursive subset of tiny_llm_hip.grammar.schema_regex)")
     ap.add_argument("--enable-thinking", action="store_true")
     ap.add_argument("--raw-prompt", action="store_true", help="do not wrap the prompt in the chat template")
     ap.add_argument("--max-new-tokens", type=int, default=256)
@@ -70,8 +77,8 @@ def main(argv=None) -> str:
             draft, draft_tok = load(args.draft_model)
             return speculative_generate(Qwen3ModelWeek3(draft), net, draft_tok, tokenizer, prompt,
                                         proposal_length=args.proposal_length)
-        if penalties != (1.0, 0.0, 0.0) or args.regex:
-            print("note: the penalty flags and --regex apply to --solution engine only")
+        if penalties != (1.0, 0.0, 0.0) or args.regex or args.json or args.json_schema:
+            print("note: the penalty flags, --regex, --json and --json-schema apply to --solution engine only")
         if args.sampler_temp:
             print("note: the KV-cache loop is greedy like the reference's; sampler flags apply to --solution engine only")
         _ = make_sampler  # sampler surface kept importable for callers of the library
@@ -86,16 +93,17 @@ def main(argv=None) -> str:
     records = None
     grammar = None
     try:
-        if args.regex and not args.draft_model:
-            from tiny_llm_hip.grammar import regex_grammar
+        if not args.draft_model:
+            from tiny_llm_hip.grammar import cli_grammar
 
-            grammar = regex_grammar(engine, tokenizer, args.regex)
+            grammar = cli_grammar(engine, tokenizer, args.regex, args.json, args.json_schema)
         if args.draft_model:
             draft_model, draft_tok = load(args.draft_model)
             if draft_tok.get_vocab() != tokenizer.get_vocab():
                 raise ValueError("draft and target tokenizers use different token ids")
-            if penalties != (1.0, 0.0, 0.0) or args.regex:
-                print("note: speculative decoding verifies the raw logits; the penalty flags and --regex do not apply with a draft model")
+            if penalties != (1.0, 0.0, 0.0) or args.regex or args.json or args.json_schema:
+                print("note: speculative decoding verifies the raw logits; the penalty flags, --regex, --json and --json-schema do not "
+                      "apply with a draft model")
             draft = DecodeEngine(draft_model, page_size=128, num_pages=pages, max_batch=1, max_prefill_rows=4096)
             try:
                 out = speculative_generate_ids(engine, draft, ids, args.max_new_tokens,

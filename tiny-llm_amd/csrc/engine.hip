@@ -13,6 +13,7 @@
 #include "sample.h"
 #include "logprob.h"
 #include "logit_process.h"
+#include "grammar_stack.h"
 #include "attn_mfma.h"
 #include "aql.h"
 
@@ -61,6 +62,40 @@ struct tl_grammar {
             if (st == GR_DEAD) return GR_END;
         }
         return (int)st;
+    }
+    // a stack grammar (tl_grammar_create_stack, grammar_stack.h): ops and the pop table beside the table
+    bool stack = false;
+    int n_pop = 0;
+    std::vector<uint8_t> ops;
+    std::vector<uint16_t> pop_table;  // [n_pop][5]
+    // advance of the definition on a configuration, on the host copies
+    GrsConfig advance_config(GrsConfig c, int token) const {
+        const GrsConfig end{GR_END, 0, 0ull};
+        if (c.state < 0 || token < 0 || token >= vocab->vocab || is_eos(token)) return end;
+        const int b0 = vocab->offsets[token], b1 = vocab->offsets[token + 1];
+        if (b1 <= b0) return end;
+        for (int k = b0; k < b1; ++k) {
+            const size_t at = (size_t)c.state * 256 + vocab->bytes[k];
+            const uint32_t t = table[at], op = ops[at];
+            if (t == GR_DEAD) return end;
+            if (op == 0) {
+                c.state = (int)t;
+            } else if (op < GRS_POP) {
+                if (c.depth == GRS_DEPTH) return end;
+                c.stack |= (uint64_t)(op - 1) << (2 * c.depth);
+                c.depth += 1;
+                c.state = (int)t;
+            } else {
+                if (c.depth == 0) return end;
+                c.depth -= 1;
+                c.stack &= grs_mask(c.depth);
+                const uint32_t top = c.depth ? (uint32_t)(c.stack >> (2 * (c.depth - 1))) & 3u : 4u;
+                const uint32_t to = pop_table[(size_t)t * 5 + top];
+                if (to == GR_DEAD) return end;
+                c.state = (int)to;
+            }
+        }
+        return c;
     }
 };
 
@@ -174,6 +209,7 @@ struct tl_engine {
     const GrammarDev **gr_ptr = nullptr;
     GrammarRecord *gr_state = nullptr;
     std::vector<char> gr_pending;
+    GrammarStackRecord *gr_stack = nullptr;  // [slots] the records of slots with a stack grammar: allocated by the first one set
     // tl_engine_score: the logits of one block of rows and the per-row targets / results, allocated on first use
     uint16_t *score_logits = nullptr;
     int32_t *score_ids = nullptr, *score_argmax = nullptr;
@@ -613,6 +649,13 @@ static bool step_grammar(const tl_engine *e, int batch) {
     return false;
 }
 
+// ... a STACK grammar?  (its own plan-key bit: the third twin, grammar_stack.h)
+static bool step_stack_grammar(const tl_engine *e, int batch) {
+    for (int b = 0; b < batch; ++b)
+        if (step_processes_slot(e, b) && e->pen[b].grammar && e->pen[b].grammar->stack) return true;
+    return false;
+}
+
 // the per-slot automaton pointers and state records: allocated by the first tl_engine_set_grammar
 static int gr_alloc(tl_engine *e) {
     if (e->gr_mem) return TL_OK;
@@ -629,10 +672,24 @@ static int gr_alloc(tl_engine *e) {
     e->stats.workspace_bytes += bytes;
     return TL_OK;
 }
-// the slot's record becomes {no context length, state}
-static void gr_poke_state(tl_engine *e, int slot, int state, std::vector<std::pair<int32_t *, int32_t>> &pk) {
-    pk.emplace_back(&e->gr_state[slot].tag, -1);
-    pk.emplace_back(&e->gr_state[slot].state, state);
+static int gr_stack_alloc(tl_engine *e) {
+    if (e->gr_stack) return TL_OK;
+    const size_t bytes = (size_t)e->cfg.max_batch * sizeof(GrammarStackRecord);
+    if (hipMalloc((void **)&e->gr_stack, bytes) != hipSuccess) return fail(TL_ERR_HIP, "engine: hipMalloc(stack grammar slots) failed");
+    if (hipMemsetAsync(e->gr_stack, 0, bytes, e->stream) != hipSuccess) {
+        (void)hipFree(e->gr_stack);
+        e->gr_stack = nullptr;
+        return fail(TL_ERR_HIP, "engine: memset(stack grammar slots) failed");
+    }
+    e->stats.workspace_bytes += bytes;
+    return TL_OK;
+}
+// the slot's record becomes {no context length, state}; a stack grammar's: {no context length, (state, depth 0, word 0)} (the stack
+// words are masked by the depth when they are read)
+static void gr_poke_state(tl_engine *e, int slot, const tl_grammar *g, std::vector<std::pair<int32_t *, int32_t>> &pk) {
+    int32_t *rec = g->stack ? (int32_t *)&e->gr_stack[slot].rec : &e->gr_state[slot].tag;
+    pk.emplace_back(rec, -1);
+    pk.emplace_back(rec + 1, g->start);
 }
 
 // the history table, the processed rows and the per-slot parameters: one allocation, made by the first call that makes a slot process
@@ -682,10 +739,11 @@ static int pen_write(tl_engine *e, int slot, const tl_engine::PenaltyParams &v) 
     if (bias_changed) pk.emplace_back(e->pen_bias_n + slot, (int32_t)v.bias_ids.size());
     if (cur.grammar != v.grammar) {  // the automaton's pointer (two words) and, for a new one, the record at its start state
         TL_TRY(gr_alloc(e));
+        if (v.grammar && v.grammar->stack) TL_TRY(gr_stack_alloc(e));
         const uint64_t ptr = (uint64_t)(uintptr_t)(v.grammar ? v.grammar->dev : nullptr);
         pk.emplace_back((int32_t *)(e->gr_ptr + slot), (int32_t)(uint32_t)ptr);
         pk.emplace_back((int32_t *)(e->gr_ptr + slot) + 1, (int32_t)(uint32_t)(ptr >> 32));
-        if (v.grammar) gr_poke_state(e, slot, v.grammar->start, pk);
+        if (v.grammar) gr_poke_state(e, slot, v.grammar, pk);
     }
     cur = v;
     if (bias_changed && !cur.bias_ids.empty()) {  // (from the mirror: it outlives the copy)
@@ -706,7 +764,9 @@ static int pen_carry(tl_engine *e, int src, int dst, bool move) {
         const size_t V = (size_t)e->cfg.vocab_size;
         TL_HIP(hipMemcpyAsync(e->pen_history + (size_t)dst * V, e->pen_history + (size_t)src * V, V * 2, hipMemcpyDeviceToDevice, e->stream));
     }
-    if (v.grammar) {  // the automaton state travels like the history
+    if (v.grammar && v.grammar->stack) {  // the automaton state travels like the history
+        TL_HIP(hipMemcpyAsync(e->gr_stack + dst, e->gr_stack + src, sizeof(GrammarStackRecord), hipMemcpyDeviceToDevice, e->stream));
+    } else if (v.grammar) {
         TL_HIP(hipMemcpyAsync(e->gr_state + dst, e->gr_state + src, sizeof(GrammarRecord), hipMemcpyDeviceToDevice, e->stream));
     }
     return move ? pen_reset(e, src) : TL_OK;
@@ -715,13 +775,17 @@ static int pen_carry(tl_engine *e, int src, int dst, bool move) {
 // the processing launch over `rows` rows of raw logits for slots slot0 .. (logit_process.h): processed rows into `out`.  A decode step
 // passes the pending tokens (counted before the row is processed); a prefill's last row has none to count.
 static void launch_logit_process(tl_engine *e, const uint16_t *logits, uint16_t *out, int rows, int slot0, const int32_t *tokens, ProfCtx *pc) {
-    bool grammar = false;
-    for (int i = 0; i < rows; ++i) grammar |= step_processes_slot(e, slot0 + i) && e->pen[slot0 + i].grammar;
+    bool grammar = false, stack = false;
+    for (int i = 0; i < rows; ++i) {
+        const tl_grammar *g = step_processes_slot(e, slot0 + i) ? e->pen[slot0 + i].grammar : nullptr;
+        grammar |= g != nullptr, stack |= g && g->stack;
+    }
     const LogitProcessArgs a{logits, out, e->cfg.vocab_size, slot0, e->pen_history, e->pen_rep, e->pen_pres, e->pen_freq, e->pen_bias_n,
                              e->pen_bias_ids, e->pen_bias_values, tokens, pc ? pc->buf : nullptr,
                              grammar ? e->gr_ptr : nullptr, grammar ? e->gr_state : nullptr, grammar ? e->context_lens : nullptr};
     const dim3 grid(ceil_div(e->cfg.vocab_size, LPR_CHUNK), rows);
-    if (grammar) hipLaunchKernelGGL(logit_process_kernel<true>, grid, dim3(LPR_THREADS), 0, e->stream, a);
+    if (stack) hipLaunchKernelGGL(logit_process_stack_kernel, grid, dim3(LPR_THREADS), 0, e->stream, LogitProcessStackArgs{a, e->gr_stack});
+    else if (grammar) hipLaunchKernelGGL(logit_process_kernel<true>, grid, dim3(LPR_THREADS), 0, e->stream, a);
     else hipLaunchKernelGGL(logit_process_kernel<false>, grid, dim3(LPR_THREADS), 0, e->stream, a);
     if (pc) prof_after(pc, 7, (int)(grid.x * grid.y));
 }
@@ -1670,6 +1734,7 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     if (e->lp_mem) (void)hipFree(e->lp_mem);
     if (e->pen_mem) (void)hipFree(e->pen_mem);
     if (e->gr_mem) (void)hipFree(e->gr_mem);
+    if (e->gr_stack) (void)hipFree(e->gr_stack);
     if (e->score_logits) (void)hipFree(e->score_logits);
     if (e->kpool) (void)hipFree(e->kpool);
     if (e->vpool) (void)hipFree(e->vpool);
@@ -2037,6 +2102,70 @@ extern "C" int tl_grammar_create(const tl_vocab *v, int n_states, const uint16_t
     return TL_OK;
 }
 
+extern "C" int tl_grammar_create_stack(const tl_vocab *v, int n_states, const uint16_t *table, const uint8_t *ops, int n_pop, const uint16_t *pop_table,
+                                       const uint8_t *accepting, int start, const int32_t *eos_ids, int n_eos, void *stream, tl_grammar **out) {
+    TL_REQUIRE(out, "grammar_create_stack: null argument");
+    *out = nullptr;
+    TL_REQUIRE(v && table && ops && accepting && eos_ids, "grammar_create_stack: null argument");
+    TL_REQUIRE(n_states >= 1 && n_states <= GR_MAX_STATES, "grammar_create_stack: between 1 and 32,768 states");
+    TL_REQUIRE(n_pop >= 0 && n_pop <= GRS_MAX_POPS && (n_pop == 0 || pop_table), "grammar_create_stack: between 0 and 65,535 pop entries");
+    TL_REQUIRE(start >= 0 && start < n_states, "grammar_create_stack: start state out of range");
+    TL_REQUIRE(n_eos >= 1 && n_eos <= GR_MAX_EOS, "grammar_create_stack: between 1 and 8 EOS ids");
+    for (int i = 0; i < n_eos; ++i) {
+        TL_REQUIRE(eos_ids[i] >= 0 && eos_ids[i] < v->vocab, "grammar_create_stack: EOS id out of range");
+        for (int k = 0; k < i; ++k) TL_REQUIRE(eos_ids[k] != eos_ids[i], "grammar_create_stack: an EOS id appears twice");
+    }
+    const size_t cells = (size_t)n_states * 256;
+    std::vector<uint32_t> fused(cells);
+    for (size_t i = 0; i < cells; ++i) {
+        TL_REQUIRE(ops[i] <= GRS_POP, "grammar_create_stack: an op byte is not 0 .. 5");
+        if (table[i] != GR_DEAD) {
+            if (ops[i] == GRS_POP) TL_REQUIRE(table[i] < n_pop, "grammar_create_stack: a pop entry leads outside the pop table");
+            else TL_REQUIRE(table[i] < n_states, "grammar_create_stack: a transition leads outside the table");
+        }
+        fused[i] = (uint32_t)table[i] | (table[i] != GR_DEAD ? (uint32_t)ops[i] << 16 : 0u);
+    }
+    std::vector<uint16_t> pop8((size_t)std::max(n_pop, 1) * 8, (uint16_t)GR_DEAD);
+    for (size_t i = 0; i < (size_t)n_pop * 5; ++i) {
+        TL_REQUIRE(pop_table[i] == GR_DEAD || pop_table[i] < n_states, "grammar_create_stack: a pop leads outside the table");
+        pop8[i / 5 * 8 + i % 5] = pop_table[i];
+    }
+    auto g = std::make_unique<tl_grammar>();
+    g->vocab = v, g->n_states = n_states, g->start = start, g->stack = true, g->n_pop = n_pop;
+    g->table.assign(table, table + cells);
+    g->ops.assign(ops, ops + cells);
+    g->pop_table.assign(pop_table, pop_table + (size_t)n_pop * 5);
+    g->accepting.assign(accepting, accepting + n_states);
+    g->eos.assign(eos_ids, eos_ids + n_eos);
+    const int n_long = (int)v->long_ids.size();
+    const size_t o_fused = 256, o_pop = o_fused + align_up(cells * 4, 256), o_acc = o_pop + align_up(pop8.size() * 2, 256),
+                 o_long = o_acc + align_up((size_t)n_states, 256), total = o_long + align_up((size_t)n_states * n_long + 4, 256);
+    if (hipMalloc((void **)&g->mem, total) != hipSuccess) return fail(TL_ERR_HIP, "grammar_create_stack: hipMalloc failed");
+    GrammarDev d{};
+    d.accepting = (const uint8_t *)(g->mem + o_acc);
+    d.offsets = v->offsets_dev, d.bytes = v->bytes_dev, d.n_states = n_states, d.n_eos = n_eos, d.long_index = v->long_index_dev;
+    d.kind = 1, d.n_pop = n_pop, d.n_long = n_long;
+    d.fused = (const uint32_t *)(g->mem + o_fused), d.pop = (const uint16_t *)(g->mem + o_pop), d.long_m = (const uint8_t *)(g->mem + o_long);
+    for (int i = 0; i < GR_MAX_EOS; ++i) d.eos[i] = i < n_eos ? eos_ids[i] : -1;
+    hipError_t he = hipMemcpyAsync(g->mem, &d, sizeof(d), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(g->mem + o_fused, fused.data(), cells * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(g->mem + o_pop, pop8.data(), pop8.size() * 2, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(g->mem + o_acc, g->accepting.data(), (size_t)n_states, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess && n_long > 0) {  // the walks of the long tokens from every state with an empty stack, once, on the device
+        const GrammarLongDepthArgs la{d.fused, d.pop, d.offsets, d.bytes, v->long_ids_dev, n_long, (uint8_t *)(g->mem + o_long)};
+        hipLaunchKernelGGL(grammar_long_depth_kernel, dim3(ceil_div(n_long, 64), n_states), dim3(64), 0, (hipStream_t)stream, la);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipStreamSynchronize((hipStream_t)stream);  // (the pageable host copies above are locals)
+    if (he != hipSuccess) {
+        (void)hipFree(g->mem);
+        return fail(TL_ERR_HIP, std::string("grammar_create_stack: ") + hipGetErrorString(he));
+    }
+    g->dev = (GrammarDev *)g->mem;
+    *out = g.release();
+    return TL_OK;
+}
+
 extern "C" void tl_grammar_destroy(tl_grammar *g) {
     if (!g) return;
     if (g->mem) (void)hipFree(g->mem);
@@ -2052,7 +2181,7 @@ extern "C" int tl_engine_set_grammar(tl_engine *e, int slot, const tl_grammar *g
     TL_TRY(pen_write(e, slot, v));
     if (same) {  // the same automaton again: back to its start state
         std::vector<std::pair<int32_t *, int32_t>> pk;
-        gr_poke_state(e, slot, g->start, pk);
+        gr_poke_state(e, slot, g, pk);
         return poke(e, pk);
     }
     return TL_OK;
@@ -2063,6 +2192,11 @@ extern "C" int tl_engine_grammar_state(tl_engine *e, int slot, int *state, int *
     TL_REQUIRE(state, "engine_grammar_state: null argument");
     const tl_grammar *g = e->pen[slot].grammar;
     TL_REQUIRE(g, "engine_grammar_state: the slot has no grammar");
+    if (g->stack) {
+        int depth = 0;
+        uint64_t stack = 0;
+        return tl_engine_grammar_config(e, slot, state, &depth, &stack, accepting);
+    }
     TL_HIP(hipStreamSynchronize(e->stream));
     GrammarRecord rec{};
     int32_t pending = 0;
@@ -2074,8 +2208,46 @@ extern "C" int tl_engine_grammar_state(tl_engine *e, int slot, int *state, int *
     return TL_OK;
 }
 
+extern "C" int tl_engine_grammar_config(tl_engine *e, int slot, int *state, int *depth, uint64_t *stack, int *accepting) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(state && depth && stack, "engine_grammar_config: null argument");
+    const tl_grammar *g = e->pen[slot].grammar;
+    TL_REQUIRE(g, "engine_grammar_config: the slot has no grammar");
+    GrsConfig c{GR_END, 0, 0ull};
+    if (!g->stack) {  // a regex grammar: its state, no stack
+        TL_TRY(tl_engine_grammar_state(e, slot, &c.state, nullptr));
+    } else {
+        TL_HIP(hipStreamSynchronize(e->stream));
+        GrammarStackRecord rec{};
+        int32_t pending = 0;
+        TL_HIP(hipMemcpy(&rec, e->gr_stack + slot, sizeof(rec), hipMemcpyDeviceToHost));
+        TL_HIP(hipMemcpy(&pending, e->tokens + slot, 4, hipMemcpyDeviceToHost));
+        const uint32_t packed = (uint32_t)(rec.rec >> 32);
+        if (packed != 0xffffffffu) {
+            c.state = (int)(packed & 0xffffu), c.depth = (int)(packed >> 16 & 0xffu);
+            c.stack = rec.stack[packed >> 24 & 1u] & grs_mask(c.depth);
+        }
+        if (e->gr_pending[slot]) c = g->advance_config(c, pending);
+    }
+    *state = c.state, *depth = c.depth, *stack = c.stack;
+    if (accepting) *accepting = c.state < 0 || g->accepting[c.state] ? 1 : 0;
+    return TL_OK;
+}
+
+extern "C" int tl_grammar_mask_rows_stack(const tl_grammar *g, const void *logits_dev, int rows, const int32_t *states_dev, const int32_t *depths_dev,
+                                          const uint64_t *stacks_dev, void *out_dev, void *stream) {
+    TL_REQUIRE(g && logits_dev && states_dev && depths_dev && stacks_dev && out_dev, "grammar_mask_rows_stack: null argument");
+    TL_REQUIRE(g->stack, "grammar_mask_rows_stack: not a stack grammar (tl_grammar_mask_rows)");
+    TL_REQUIRE(rows > 0 && rows <= 65535, "grammar_mask_rows_stack: rows out of range");
+    const GrammarStackMaskArgs a{g->dev, (const uint16_t *)logits_dev, (uint16_t *)out_dev, states_dev, depths_dev, stacks_dev, g->vocab->vocab};
+    hipLaunchKernelGGL(grammar_stack_mask_rows_kernel, dim3(ceil_div(g->vocab->vocab, 2048), rows), dim3(256), 0, (hipStream_t)stream, a);
+    TL_CHECK_LAUNCH("grammar_mask_rows_stack");
+    return TL_OK;
+}
+
 extern "C" int tl_grammar_mask_rows(const tl_grammar *g, const void *logits_dev, int rows, const int32_t *states_dev, void *out_dev, void *stream) {
     TL_REQUIRE(g && logits_dev && states_dev && out_dev, "grammar_mask_rows: null argument");
+    TL_REQUIRE(!g->stack, "grammar_mask_rows: a stack grammar (tl_grammar_mask_rows_stack)");
     TL_REQUIRE(rows > 0 && rows <= 65535, "grammar_mask_rows: rows out of range");
     const GrammarMaskArgs a{g->dev, (const uint16_t *)logits_dev, (uint16_t *)out_dev, states_dev, g->vocab->vocab};
     hipLaunchKernelGGL(grammar_mask_rows_kernel, dim3(ceil_div(g->vocab->vocab, 2048), rows), dim3(256), 0, (hipStream_t)stream, a);
@@ -2510,7 +2682,7 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
     launch_embed_slots(e, batch);
     TL_CHECK_LAUNCH("engine embed");
     const bool samples = step_samples(e, batch), logprobs = step_logprobs(e, batch), processes = step_processes(e, batch);
-    const bool grammar = processes && step_grammar(e, batch);
+    const bool grammar = processes && step_grammar(e, batch), stack_grammar = grammar && step_stack_grammar(e, batch);
     bool on_queue = false;  // steps of this call are in flight on the AQL queue (the stream is idle and must stay so until they are drained)
     for (int s = 0; s < steps; ++s) {
         SplitPlan sp;
@@ -2519,9 +2691,9 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
             // bit 62: the step ends with the sampling twin of step_end_kernel, bit 61: with the logprob twin (both re-derived every call
             // from the slots' parameters)
             // bit 60: the processing launch (logit_process.h) stands between the lm_head and the step end
-            // bit 59: ... and it is the grammar twin (grammar.h)
+            // bit 59: ... and it is the grammar twin (grammar.h); bit 58: the stack-grammar twin (grammar_stack.h)
             const auto key = std::make_pair(batch, sp.key() | (samples ? (1L << 62) : 0L) | (logprobs ? (1L << 61) : 0L) | (processes ? (1L << 60) : 0L) |
-                                                       (grammar ? (1L << 59) : 0L));
+                                                       (grammar ? (1L << 59) : 0L) | (stack_grammar ? (1L << 58) : 0L));
             auto it = e->graphs.find(key);
             if (it == e->graphs.end()) {
                 // The split plan (and with it the key) changes every 64 * n_splits tokens of context: a long run would keep one
@@ -2612,6 +2784,13 @@ extern "C" int tl_engine_copy_logits(tl_engine *e, void *dst_dev, int rows) {
     TL_REQUIRE(e && dst_dev, "engine_copy_logits: null argument");
     TL_REQUIRE(rows > 0 && rows <= e->cfg.max_batch, "engine_copy_logits: rows out of range");
     TL_HIP(hipMemcpyAsync(dst_dev, e->logits, (size_t)rows * e->cfg.vocab_size * 2, hipMemcpyDeviceToDevice, e->stream));
+    return TL_OK;
+}
+extern "C" int tl_engine_copy_processed_logits(tl_engine *e, void *dst_dev, int rows) {
+    TL_REQUIRE(e && dst_dev, "engine_copy_processed_logits: null argument");
+    TL_REQUIRE(rows > 0 && rows <= e->cfg.max_batch, "engine_copy_processed_logits: rows out of range");
+    TL_REQUIRE(e->pen_rows, "engine_copy_processed_logits: no slot of this engine has processed its logits yet");
+    TL_HIP(hipMemcpyAsync(dst_dev, e->pen_rows, (size_t)rows * e->cfg.vocab_size * 2, hipMemcpyDeviceToDevice, e->stream));
     return TL_OK;
 }
 extern "C" const int32_t *tl_engine_tokens_dev(const tl_engine *e) { return e ? e->tokens : nullptr; }

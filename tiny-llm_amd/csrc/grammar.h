@@ -33,6 +33,11 @@ struct GrammarDev {
     const int32_t *long_index;  // [vocab] the vocabulary's: the token's number among the long tokens (undefined for a short one)
     const uint32_t *long_bits;  // [n_states][long_words]
     int long_words;
+    // a stack grammar only (grammar_stack.h; kind != 0): table, long_bits and long_words above are unused
+    int kind, n_pop, n_long;
+    const uint32_t *fused;   // [n_states][256] entry | op << 16
+    const uint16_t *pop;     // [max(n_pop, 1)][8] the state after a pop by the new top (0 .. 3, 4 = empty stack); 5 .. 7 padding
+    const uint8_t *long_m;   // [n_states][n_long]
 };
 
 // the slot's state record: `state` includes the pending token of the step in which the slot's context length was `tag`

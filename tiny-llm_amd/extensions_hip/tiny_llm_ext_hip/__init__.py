@@ -205,6 +205,10 @@ _SIGNATURES.update({
     "tl_engine_set_grammar": (_c_int, [_c_void_p, _c_int, _c_void_p]),
     "tl_engine_grammar_state": (_c_int, [_c_void_p, _c_int, _P(_c_int), _P(_c_int)]),
     "tl_grammar_mask_rows": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "tl_grammar_create_stack": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int,
+                                         _c_void_p, _P(_c_void_p)]),
+    "tl_engine_grammar_config": (_c_int, [_c_void_p, _c_int, _P(_c_int), _P(_c_int), _P(ctypes.c_uint64), _P(_c_int)]),
+    "tl_grammar_mask_rows_stack": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "tl_engine_read_logprobs": (_c_int, [_c_void_p, _c_int, _c_int, _P(TlTokenLogprob)]),
     "tl_engine_read_pending_logprobs": (_c_int, [_c_void_p, _c_int, _P(TlTokenLogprob)]),
     "tl_engine_score": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, ctypes.c_int32, _P(_c_float), _P(ctypes.c_int32)]),
@@ -213,6 +217,7 @@ _SIGNATURES.update({
     "tl_engine_read_tokens": (_c_int, [_c_void_p, _c_int, _c_int, _P(ctypes.c_int32)]),
     "tl_engine_logits_dev": (_c_void_p, [_c_void_p]),
     "tl_engine_copy_logits": (_c_int, [_c_void_p, _c_void_p, _c_int]),
+    "tl_engine_copy_processed_logits": (_c_int, [_c_void_p, _c_void_p, _c_int]),
     "tl_engine_tokens_dev": (_c_void_p, [_c_void_p]),
     "tl_engine_get_stats": (_c_int, [_c_void_p, _P(TlEngineStats)]),
     "tl_engine_replay_route": (ctypes.c_char_p, [_c_void_p]),

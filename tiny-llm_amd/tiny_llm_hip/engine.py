@@ -235,7 +235,7 @@ class DecodeEngine:
         return self._vocab
 
     def make_grammar(self, dfa, eos_ids, vocab: "Vocab | None" = None) -> "Grammar":
-        """A byte-level automaton (grammar.compile_regex) with the token ids that end the text (tl_grammar_create), over ``vocab``
+        """A byte-level automaton (grammar.compile_regex, or a StackDFA: grammar.compile_json) with the token ids that end the text (tl_grammar_create), over ``vocab``
         (default: the vocabulary of the last make_vocab)."""
         vocab = vocab if vocab is not None else getattr(self, "_vocab", None)
         if vocab is None:
@@ -256,6 +256,14 @@ class DecodeEngine:
         state, acc = ctypes.c_int(), ctypes.c_int()
         _ext.check(_lib.tl_engine_grammar_state(self._h, slot, ctypes.byref(state), ctypes.byref(acc)))
         return state.value, bool(acc.value)
+
+    def grammar_config(self, slot: int) -> tuple[int, int, int, bool]:
+        """(state, depth, stack, whether EOS is allowed next) of the slot's sequence including its pending token
+        (tl_engine_grammar_config): the configuration of a stack grammar (grammar.StackDFA; GRAMMAR_END is (-1, 0, 0)); a regex grammar
+        reports its state with depth 0 and an empty stack.  Synchronises."""
+        state, depth, acc, stack = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_uint64()
+        _ext.check(_lib.tl_engine_grammar_config(self._h, slot, ctypes.byref(state), ctypes.byref(depth), ctypes.byref(stack), ctypes.byref(acc)))
+        return state.value, depth.value, stack.value, bool(acc.value)
 
     def read_logprobs(self, slot: int, count: int) -> list["TokenLogprob"]:
         """Records of the slot's last ``count`` produced tokens (like read_tokens); synchronises."""
@@ -348,6 +356,16 @@ class DecodeEngine:
         out = torch.empty((rows, self.vocab_size), dtype=torch.bfloat16, device=self.device)
         torch.cuda.current_stream().synchronize()  # `out` is allocated on torch's stream
         _ext.check(_lib.tl_engine_copy_logits(self._h, out.data_ptr(), rows))
+        self.synchronize()
+        return out
+
+    def processed_logits(self, rows: int = 1) -> torch.Tensor:
+        """A copy of the processed rows [rows, vocab] (bf16) of the last decode step in which some slot processed its logits
+        (tl_engine_copy_processed_logits): row i is what slot i's token was chosen from; the row of a slot that does not process is its
+        raw row."""
+        out = torch.empty((rows, self.vocab_size), dtype=torch.bfloat16, device=self.device)
+        torch.cuda.current_stream().synchronize()
+        _ext.check(_lib.tl_engine_copy_processed_logits(self._h, out.data_ptr(), rows))
         self.synchronize()
         return out
 
@@ -491,7 +509,8 @@ class Vocab:
 
 
 class Grammar:
-    """tl_grammar: a ByteDFA (table uint16 [S, 256], accepting, start) over a Vocab, with its EOS ids."""
+    """tl_grammar: a ByteDFA (table uint16 [S, 256], accepting, start) or a StackDFA (with ops and pop_table: tl_grammar_create_stack)
+    over a Vocab, with its EOS ids."""
 
     def __init__(self, vocab: Vocab, dfa, eos_ids):
         import numpy as np
@@ -503,8 +522,17 @@ class Grammar:
         eos = [int(t) for t in eos_ids]
         arr = (ctypes.c_int32 * max(len(eos), 1))(*eos)
         handle = ctypes.c_void_p()
-        _ext.check(_lib.tl_grammar_create(vocab._h, table.shape[0], table.ctypes.data, accepting.ctypes.data, int(dfa.start), arr, len(eos),
-                                          None, ctypes.byref(handle)))
+        if hasattr(dfa, "pop_table"):
+            ops = np.ascontiguousarray(dfa.ops, dtype=np.uint8)
+            pops = np.ascontiguousarray(dfa.pop_table, dtype=np.uint16).reshape(-1, 5)
+            if ops.shape != table.shape:
+                raise ValueError("Grammar: ops must have the table's shape")
+            _ext.check(_lib.tl_grammar_create_stack(vocab._h, table.shape[0], table.ctypes.data, ops.ctypes.data, pops.shape[0],
+                                                    pops.ctypes.data if pops.size else None, accepting.ctypes.data, int(dfa.start), arr, len(eos),
+                                                    None, ctypes.byref(handle)))
+        else:
+            _ext.check(_lib.tl_grammar_create(vocab._h, table.shape[0], table.ctypes.data, accepting.ctypes.data, int(dfa.start), arr, len(eos),
+                                              None, ctypes.byref(handle)))
         self._h = handle
         self.vocab, self.dfa, self.eos_ids = vocab, dfa, tuple(eos)  # (the vocabulary must outlive the grammar)
 

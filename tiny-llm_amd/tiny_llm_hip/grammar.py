@@ -532,3 +532,337 @@ def regex_grammar(engine, tokenizer, pattern: str | bytes, check: bool = True):
         dfa.check_vocabulary(offsets, data)
     vocab = engine.make_vocab(offsets, data)
     return engine.make_grammar(dfa, tokenizer_eos_ids(tokenizer), vocab)
+
+
+# ---- stack grammars: JSON mode (include/tinyllm_engine.h "stack grammars") ------------------------------------------------------------
+# Nested JSON is not regular.  A StackDFA is a byte-level DFA with a bounded stack of 2-bit symbols beside the state; the engine keeps
+# the configuration (state, depth, stack) per slot on the device, as it keeps a regex grammar's state.
+
+MAX_DEPTH = 32
+OP_POP = 5
+_EMPTY = 4  # pop_table column: the stack became empty
+
+
+class StackDFA:
+    """``table`` uint16 [S, 256] (0xFFFF = none; else the next state or, for a pop, a row of ``pop_table``), ``ops`` uint8 [S, 256]
+    (0 none, 1 .. 4 push symbol op - 1, 5 pop), ``pop_table`` uint16 [P, 5] (the state after a pop by the new top 0 .. 3, column 4 =
+    the stack became empty; 0xFFFF = dead), ``accepting`` uint8 [S], ``start``.  A configuration is (state, depth, stack): depth in
+    0 .. 32, stack an int with the symbol of level i (0 = bottom) in bits 2i, 2i + 1."""
+
+    def __init__(self, table, ops, pop_table, accepting, start: int):
+        self.table = np.ascontiguousarray(table, dtype=np.uint16)
+        self.ops = np.ascontiguousarray(ops, dtype=np.uint8)
+        self.pop_table = np.ascontiguousarray(pop_table, dtype=np.uint16).reshape(-1, 5)
+        self.accepting = np.ascontiguousarray(accepting, dtype=np.uint8)
+        self.start = int(start)
+        if self.table.ndim != 2 or self.table.shape[1] != 256 or self.ops.shape != self.table.shape or self.accepting.shape != (self.table.shape[0],):
+            raise ValueError("StackDFA: table and ops must be [S, 256], accepting [S]")
+
+    @property
+    def n_states(self) -> int:
+        return self.table.shape[0]
+
+    @property
+    def n_pop(self) -> int:
+        return self.pop_table.shape[0]
+
+    def walk(self, config, data: bytes):
+        """The configuration after feeding `data` from `config`; None once a byte has no transition, pushes onto a full stack or pops
+        an empty one."""
+        state, depth, stack = config
+        for b in data:
+            t, op = int(self.table[state, b]), int(self.ops[state, b])
+            if t == DEAD:
+                return None
+            if op == 0:
+                state = t
+            elif op < OP_POP:
+                if depth == MAX_DEPTH:
+                    return None
+                stack |= (op - 1) << (2 * depth)
+                depth += 1
+                state = t
+            else:
+                if depth == 0:
+                    return None
+                depth -= 1
+                stack &= (1 << (2 * depth)) - 1
+                state = int(self.pop_table[t, (stack >> (2 * (depth - 1))) & 3 if depth else _EMPTY])
+                if state == DEAD:
+                    return None
+        return state, depth, stack
+
+    def accepts(self, data: bytes) -> bool:
+        c = self.walk((self.start, 0, 0), data)
+        return c is not None and bool(self.accepting[c[0]])
+
+    def check_vocabulary(self, offsets: Sequence[int], data) -> None:
+        """Raises ValueError, naming a state, if from some non-accepting state no token of the vocabulary can be walked whatever is
+        on the stack (tried: the empty stack and every stack of one or two symbols)."""
+        offsets = np.asarray(offsets, dtype=np.int64)
+        data = bytes(data) if not isinstance(data, np.ndarray) else data.tobytes()
+        by_first: dict[int, list[bytes]] = {}
+        for j in range(len(offsets) - 1):
+            tok = data[offsets[j]:offsets[j + 1]]
+            if tok:
+                by_first.setdefault(tok[0], []).append(tok)
+        for toks in by_first.values():
+            toks.sort(key=len)
+        stacks = [(0, 0)] + [(1, a) for a in range(4)] + [(2, a | b << 2) for a in range(4) for b in range(4)]
+        for s in range(self.n_states):
+            if self.accepting[s]:
+                continue
+            firsts = [int(b) for b in np.nonzero(self.table[s] != DEAD)[0]]
+            if not any(self.walk((s, d, st), tok) is not None for b in firsts for tok in by_first.get(b, ()) for d, st in stacks):
+                raise ValueError(f"check_vocabulary: no token of the vocabulary can be produced in state {s} (not accepting)")
+
+
+def compile_json(top: str = "object", whitespace: str = "compact", max_depth: int = MAX_DEPTH) -> StackDFA:
+    """RFC 8259 JSON as a StackDFA.  ``top``: "value" (any JSON text) or "object" (the text must be an object).  ``whitespace``: "free"
+    (RFC whitespace wherever the RFC has it) or "compact" (none, but at most one space after ``:`` and ``,`` -- what
+    ``json.dumps`` writes with either pair of separators).  Strings are well-formed UTF-8 (no overlong forms, no surrogates, nothing
+    above U+10FFFF) without raw bytes below 0x20; escapes are ``\\" \\\\ \\/ \\b \\f \\n \\r \\t \\uXXXX``.  Stack symbols: 0 = object,
+    1 = array; the kind of the innermost container is part of the state, so an accepting state implies an empty stack.  Containers
+    nest up to the engine's 32 levels (``max_depth`` must be 32: the bound is the device's stack, not the automaton's)."""
+    if top not in ("object", "value") or whitespace not in ("compact", "free"):
+        raise ValueError('compile_json: top is "object" or "value", whitespace "compact" or "free"')
+    if max_depth != MAX_DEPTH:
+        raise ValueError("compile_json: max_depth must be 32 (the depth of the engine's stack)")
+    free = whitespace == "free"
+    ws = b" \t\n\r" if free else b""
+    names: dict[str, int] = {}
+    table: list[list[int]] = []
+    ops: list[list[int]] = []
+    accepting: list[int] = []
+
+    def state(name: str) -> int:
+        if name not in names:
+            names[name] = len(table)
+            table.append([DEAD] * 256)
+            ops.append([0] * 256)
+            accepting.append(0)
+        return names[name]
+
+    def edge(src: str, byte_values, dst: str | int, op: int = 0) -> None:
+        s, d = state(src), dst if isinstance(dst, int) else state(dst)
+        for b in byte_values:
+            assert table[s][b] == DEAD, (src, b)
+            table[s][b], ops[s][b] = d, op
+
+    digits, digits19, hexes = b"0123456789", b"123456789", b"0123456789abcdefABCDEF"
+
+    def spaced(name: str) -> str:
+        """the state entered after ':' or ',': `name` itself with free whitespace, else a state that also takes one space"""
+        return name if free else name + ".sp"
+
+    def after_value(src: str, ctx: str) -> None:
+        edge(src, ws, "AV." + ctx)
+        if ctx == "O":
+            edge(src, b",", spaced("KX"))
+            edge(src, b"}", 0, OP_POP)
+        elif ctx == "A":
+            edge(src, b",", spaced("V.A"))
+            edge(src, b"]", 0, OP_POP)
+
+    def value_start(src: str, ctx: str) -> None:
+        edge(src, b'"', f"S.{ctx}")
+        edge(src, b"-", f"NM.{ctx}")
+        edge(src, b"0", f"NZ.{ctx}")
+        edge(src, digits19, f"NI.{ctx}")
+        for word in (b"true", b"false", b"null"):
+            edge(src, word[:1], f"L.{ctx}.{word[:1].decode()}")
+        edge(src, b"{", "O0", 1)
+        edge(src, b"[", "A0", 2)
+
+    def string(p: str, exit_: str) -> None:
+        edge(p, [b for b in range(0x20, 0x80) if b not in b'"\\'], p)
+        edge(p, b'"', exit_)
+        edge(p, b"\\", p + ".esc")
+        edge(p, range(0xC2, 0xE0), p + ".c1")
+        edge(p, [0xE0], p + ".e0")
+        edge(p, [b for b in range(0xE1, 0xF0) if b != 0xED], p + ".c2")
+        edge(p, [0xED], p + ".ed")
+        edge(p, [0xF0], p + ".f0")
+        edge(p, range(0xF1, 0xF4), p + ".c3")
+        edge(p, [0xF4], p + ".f4")
+        edge(p + ".c1", range(0x80, 0xC0), p)
+        edge(p + ".c2", range(0x80, 0xC0), p + ".c1")
+        edge(p + ".e0", range(0xA0, 0xC0), p + ".c1")
+        edge(p + ".ed", range(0x80, 0xA0), p + ".c1")
+        edge(p + ".c3", range(0x80, 0xC0), p + ".c2")
+        edge(p + ".f0", range(0x90, 0xC0), p + ".c2")
+        edge(p + ".f4", range(0x80, 0x90), p + ".c2")
+        edge(p + ".esc", b'"\\/bfnrt', p)
+        edge(p + ".esc", b"u", p + ".h1")
+        for k in (1, 2, 3):
+            edge(f"{p}.h{k}", hexes, f"{p}.h{k + 1}")
+        edge(p + ".h4", hexes, p)
+
+    start = "V.T" if top == "value" else "START"
+    state(start)
+    if top == "value":
+        edge("V.T", ws, "V.T")
+        value_start("V.T", "T")
+    else:
+        edge("START", ws, "START")
+        edge("START", b"{", "O0", 1)
+    for ctx in ("T", "O", "A"):
+        after_value("AV." + ctx, ctx)
+        string("S." + ctx, "AV." + ctx)
+        edge(f"NM.{ctx}", b"0", f"NZ.{ctx}")
+        edge(f"NM.{ctx}", digits19, f"NI.{ctx}")
+        edge(f"NI.{ctx}", digits, f"NI.{ctx}")
+        for n in ("NZ", "NI"):
+            edge(f"{n}.{ctx}", b".", f"NF0.{ctx}")
+        edge(f"NF0.{ctx}", digits, f"NF.{ctx}")
+        edge(f"NF.{ctx}", digits, f"NF.{ctx}")
+        for n in ("NZ", "NI", "NF"):
+            edge(f"{n}.{ctx}", b"eE", f"NE0.{ctx}")
+        edge(f"NE0.{ctx}", b"+-", f"NE1.{ctx}")
+        for n in ("NE0", "NE1", "NE"):
+            edge(f"{n}.{ctx}", digits, f"NE.{ctx}")
+        for n in ("NZ", "NI", "NF", "NE"):
+            after_value(f"{n}.{ctx}", ctx)
+        for word in (b"true", b"false", b"null"):
+            for k in range(1, len(word)):
+                edge(f"L.{ctx}.{word[:k].decode()}", word[k:k + 1], f"L.{ctx}.{word[:k + 1].decode()}" if k + 1 < len(word) else f"AV.{ctx}")
+    for n in ("AV", "NZ", "NI", "NF", "NE"):
+        accepting[state(n + ".T")] = 1
+    # containers: O0 / A0 just opened; KX a key after ','; COL the ':' after a key; V.O / V.A a value after ':' / ','
+    edge("O0", ws, "O0")
+    edge("O0", b'"', "KS")
+    edge("O0", b"}", 0, OP_POP)
+    edge("KX", ws, "KX")
+    edge("KX", b'"', "KS")
+    string("KS", "COL")
+    edge("COL", ws, "COL")
+    edge("COL", b":", spaced("V.O"))
+    edge("A0", ws, "A0")
+    value_start("A0", "A")
+    edge("A0", b"]", 0, OP_POP)
+    for ctx in ("O", "A"):
+        edge("V." + ctx, ws, "V." + ctx)
+        value_start("V." + ctx, ctx)
+    if not free:
+        edge("KX.sp", b" ", "KX")
+        edge("KX.sp", b'"', "KS")
+        for ctx in ("O", "A"):
+            edge(f"V.{ctx}.sp", b" ", "V." + ctx)
+            value_start(f"V.{ctx}.sp", ctx)
+    pop_table = [[names["AV.O"], names["AV.A"], DEAD, DEAD, names["AV.T"]]]
+    # drop what cannot be reached from the start (top="object": the values of the top level)
+    seen, todo = {names[start]}, [names[start]]
+    while todo:
+        s = todo.pop()
+        for b in range(256):
+            if table[s][b] == DEAD:
+                continue
+            for d in ([x for x in pop_table[table[s][b]] if x != DEAD] if ops[s][b] == OP_POP else [table[s][b]]):
+                if d not in seen:
+                    seen.add(d)
+                    todo.append(d)
+    order = sorted(seen)
+    new = {s: i for i, s in enumerate(order)}
+    out_table = np.full((len(order), 256), DEAD, dtype=np.uint16)
+    out_ops = np.zeros((len(order), 256), dtype=np.uint8)
+    for s in order:
+        for b in range(256):
+            if table[s][b] != DEAD:
+                out_table[new[s], b] = table[s][b] if ops[s][b] == OP_POP else new[table[s][b]]
+                out_ops[new[s], b] = ops[s][b]
+    out_pop = np.asarray([[new.get(x, DEAD) if x != DEAD else DEAD for x in row] for row in pop_table], dtype=np.uint16)
+    return StackDFA(out_table, out_ops, out_pop, np.asarray([accepting[s] for s in order], dtype=np.uint8), new[names[start]])
+
+
+_SCHEMA_ANNOTATIONS = {"title", "description", "$schema", "$id", "default", "examples"}
+_JSON_CHAR = b'(?:[^"\\\\\\x00-\\x1f]|\\\\(?:["\\\\/bfnrt]|u[0-9a-fA-F]{4}))'
+_JSON_INT = b"-?(?:0|[1-9][0-9]*)"
+_JSON_NUMBER = _JSON_INT + b"(?:\\.[0-9]+)?(?:[eE][+-]?[0-9]+)?"
+
+
+def schema_regex(schema: dict) -> bytes:
+    """A pattern (for compile_regex; also a valid ``re`` bytes pattern) of the COMPACT JSON texts -- ``json.dumps(x, separators=(",",
+    ":"))`` -- that conform to a non-recursive JSON-Schema subset: ``type`` object (``properties`` in the given order, all of them
+    required), string (``enum``, ``const``, ``maxLength``), integer, number, boolean, null, array (``items``, ``minItems``,
+    ``maxItems``), ``anyOf``, ``enum`` / ``const`` of scalars, nested freely.  Any other keyword raises ValueError naming it."""
+    import json
+
+    if not isinstance(schema, dict):
+        raise ValueError("schema_regex: a schema is a dict")
+
+    def only(allowed):
+        for key in schema:
+            if key not in allowed and key not in _SCHEMA_ANNOTATIONS:
+                raise ValueError(f"schema_regex: unsupported keyword {key!r}")
+
+    def literal(value) -> bytes:
+        if isinstance(value, (dict, list)):
+            raise ValueError("schema_regex: unsupported keyword 'enum' / 'const' with a value that is not a scalar")
+        return escape(json.dumps(value))
+
+    if "anyOf" in schema:
+        only({"anyOf"})
+        return b"(?:" + b"|".join(schema_regex(s) for s in schema["anyOf"]) + b")"
+    if "const" in schema:
+        only({"const", "type"})
+        return literal(schema["const"])
+    if "enum" in schema:
+        only({"enum", "type"})
+        if not schema["enum"]:
+            raise ValueError("schema_regex: unsupported keyword 'enum' without values")
+        return b"(?:" + b"|".join(literal(v) for v in schema["enum"]) + b")"
+    kind = schema.get("type")
+    if kind is None:
+        only(set())
+        raise ValueError("schema_regex: a schema needs 'type', 'enum', 'const' or 'anyOf'")
+    if kind == "string":
+        only({"type", "maxLength"})
+        return b'"' + _JSON_CHAR + (b"{0,%d}" % int(schema["maxLength"]) if "maxLength" in schema else b"*") + b'"'
+    if kind in ("integer", "number", "boolean", "null"):
+        only({"type"})
+        return {"integer": _JSON_INT, "number": _JSON_NUMBER, "boolean": b"(?:true|false)", "null": b"null"}[kind]
+    if kind == "array":
+        only({"type", "items", "minItems", "maxItems"})
+        if "items" not in schema:
+            raise ValueError("schema_regex: unsupported keyword 'array' without 'items'")
+        item, lo, hi = schema_regex(schema["items"]), int(schema.get("minItems", 0)), schema.get("maxItems")
+        if hi is not None and (int(hi) < lo or int(hi) < 0):
+            raise ValueError("schema_regex: unsupported keyword 'maxItems' below 'minItems'")
+        if hi is not None and int(hi) == 0:
+            return b"\\[\\]"
+        more = b"(?:," + item + b")" + (b"{%d,}" % max(lo - 1, 0) if hi is None else b"{%d,%d}" % (max(lo - 1, 0), int(hi) - 1))
+        return b"\\[" + (b"(?:" + item + more + b")?" if lo == 0 else item + more) + b"\\]"
+    if kind == "object":
+        only({"type", "properties", "required", "additionalProperties"})
+        props = schema.get("properties", {})
+        if "required" in schema and set(schema["required"]) != set(props):
+            raise ValueError("schema_regex: unsupported keyword 'required' that does not list every property")
+        if schema.get("additionalProperties", False) is not False:
+            raise ValueError("schema_regex: unsupported keyword 'additionalProperties' other than false")
+        return b"\\{" + b",".join(escape(json.dumps(k)) + b":" + schema_regex(v) for k, v in props.items()) + b"\\}"
+    raise ValueError(f"schema_regex: unsupported keyword 'type': {kind!r}")
+
+
+def json_grammar(engine, tokenizer, top: str = "object", whitespace: str = "compact", check: bool = True):
+    """regex_grammar's companion for JSON mode: a Grammar for ``engine`` from a loaded byte-level BPE tokenizer and compile_json."""
+    dfa = compile_json(top, whitespace)
+    offsets, data = vocabulary_bytes(tokenizer, engine.vocab_size)
+    if len(offsets) - 1 != engine.vocab_size:
+        raise ValueError(f"the tokenizer has {len(offsets) - 1} ids, the model {engine.vocab_size}")
+    if check:
+        dfa.check_vocabulary(offsets, data)
+    vocab = engine.make_vocab(offsets, data)
+    return engine.make_grammar(dfa, tokenizer_eos_ids(tokenizer), vocab)
+
+
+def cli_grammar(engine, tokenizer, regex=None, json_top=None, json_schema_file=None):
+    """The Grammar of main.py's and batch_main.py's --regex PATTERN / --json object|value / --json-schema FILE (at most one of them), or
+    None."""
+    if json_top:
+        return json_grammar(engine, tokenizer, top=json_top)
+    if json_schema_file:
+        import json
+
+        with open(json_schema_file, encoding="utf-8") as f:
+            return regex_grammar(engine, tokenizer, schema_regex(json.load(f)))
+    return regex_grammar(engine, tokenizer, regex) if regex else None
