@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Continuous-batching CLI over the fused engine (counterpart of the reference batch-main.py:62-101).
 
-  python batch_main.py --model <checkpoint dir> [--batch-size 5] [--prefill-step 128] [--max-seq-len 512] [--prompts-file f]
+  python batch_main.py --model <checkpoint dir> [--batch-size 5] [--prefill-step 128] [--max-seq-len 512] [--prompts-file f] [--prefix-cache [PAGES]]
 """
 import argparse
 import sys
@@ -40,6 +40,9 @@ def main(argv=None):
                             help="JSON mode: every answer is one JSON object (or any JSON value), enforced on the device per request")
     constraint.add_argument("--json-schema", default=None, metavar="FILE",
                             help="every answer is compact JSON that conforms to the schema in FILE (tiny_llm_hip.grammar.schema_regex)")
+    ap.add_argument("--prefix-cache", nargs="?", type=int, const=0, default=None, metavar="PAGES",
+                    help="keep the K / V of finished requests and reuse it for later prompts that start with the same tokens (the chat "
+                         "template, a shared system prompt); PAGES caps the retained pages (default: no cap)")
     ap.add_argument("--prompts-file", default=None, help="one prompt per line (default: five built-in questions)")
     args = ap.parse_args(argv)
 
@@ -59,7 +62,8 @@ def main(argv=None):
         limits.append(args.max_seq_len - len(ids))
     pages_per_seq = args.max_seq_len // 128 + 2
     engine = DecodeEngine(model, page_size=128, num_pages=pages_per_seq * (args.batch_size + 1) + 2,
-                          max_batch=args.batch_size + 1, max_prefill_rows=args.prefill_step, kv_format=args.kv_format)
+                          max_batch=args.batch_size + 1, max_prefill_rows=args.prefill_step, kv_format=args.kv_format,
+                          prefix_cache=False if args.prefix_cache is None else (args.prefix_cache or True))
     sampling = {}
     if args.sampler_temp:
         sampling.update(temperature=args.sampler_temp, top_k=args.sampler_top_k, top_p=args.sampler_top_p)

@@ -8,6 +8,11 @@ step takes ~4 ms, a 128-token chunk ~7 ms, and requests finish as fast as they a
 ``prefill_budget`` therefore lets a turn spend up to that many prompt tokens on admission (default = one chunk, the
 reference's schedule), which is what lets config 4 ("64 concurrent requests") actually reach 64.
 
+An engine whose ``prefix_cache_enabled`` is true (DecodeEngine(prefix_cache=...)) has every admitted request attach the cached
+prefix of its prompt (``prefix_attach`` right after ``begin``: the prompt then starts at the matched offset) and declare the answer
+tokens it fed at retirement (``prefix_extend(slot, out[:-1])`` before ``release``); the loops then also keep the produced ids.  With
+the cache off the call sequence is unchanged.
+
 The engine is duck-typed (begin / prefill / move / decode / release / synchronize / stats): ``ScheduleOnlyEngine``
 runs the same schedule against a cost model instead of a GPU (capacity planning, and the CPU tests of the scheduler
 and of the multi-replica dealer).
@@ -107,6 +112,21 @@ def _close_holes(engine, slots: list, live: set) -> None:
         live.add(lo)
 
 
+def _admit(engine, cached: bool, slot: int, request) -> dict:
+    """The state of a request that has just begun in ``slot``: with the prefix cache on it starts behind the cached part of its prompt."""
+    state = {"req": request, "offset": 0, "count": 0, "ctx": 0, "out": []}
+    if cached and len(request.prompt_token_ids) > 0:
+        state["offset"] = state["ctx"] = engine.prefix_attach(slot, request.prompt_token_ids)
+    return state
+
+
+def _retire(engine, cached: bool, slot: int, state: dict) -> None:
+    """Release the slot; with the prefix cache on the answer tokens that were fed are declared first (the last one never was)."""
+    if cached:
+        engine.prefix_extend(slot, state["out"][:-1])
+    engine.release(slot)
+
+
 def serve_requests(engine, requests, *, batch_size: int, prefill_step: int, prefill_budget: int | None = None,
                    page_size: int = 128, kv_bytes_per_page: int = 0, capacity_pages: int = 0,
                    clock=time.perf_counter, staging_slots: int = 1, compact: bool = True) -> ServingMetrics:
@@ -123,6 +143,7 @@ def serve_requests(engine, requests, *, batch_size: int, prefill_step: int, pref
                                       prefill_budget=prefill_budget, page_size=page_size, kv_bytes_per_page=kv_bytes_per_page,
                                       capacity_pages=capacity_pages, clock=clock, staging_slots=staging_slots, compact=compact)
     m = ServingMetrics()
+    cached = bool(getattr(engine, "prefix_cache_enabled", False))
     staging = batch_size
     slots: list[dict | None] = [None] * batch_size
     pending: dict | None = None
@@ -155,7 +176,7 @@ def serve_requests(engine, requests, *, batch_size: int, prefill_step: int, pref
                         break
                     engine.begin(staging)
                     live.add(staging)
-                    pending = {"req": requests[next_idx], "offset": 0, "count": 0, "ctx": 0}
+                    pending = _admit(engine, cached, staging, requests[next_idx])
                     next_idx += 1
                 tokens = pending["req"].prompt_token_ids
                 if pending["offset"] < len(tokens):
@@ -172,11 +193,13 @@ def serve_requests(engine, requests, *, batch_size: int, prefill_step: int, pref
                     if last:
                         pending["count"] = 1
                         m.generated_tokens += 1
+                        if cached:
+                            pending["out"].append(engine.read_tokens(staging, 1)[0])
                     snapshot()
                 if pending["offset"] < len(tokens):
                     continue
                 if pending["count"] >= pending["req"].max_new_tokens:  # a one-token request never enters the batch
-                    engine.release(staging)
+                    _retire(engine, cached, staging, pending)
                     live.discard(staging)
                     pending = None
                     continue
@@ -205,16 +228,19 @@ def serve_requests(engine, requests, *, batch_size: int, prefill_step: int, pref
             if last_completion is not None:
                 gaps_ms.append((now - last_completion) * 1e3)
             last_completion = now
+            produced = engine.read_pending(rows) if cached else None
             for i in active:
                 s = slots[i]
                 s["count"] += 1
                 s["ctx"] += 1
                 m.generated_tokens += 1
                 m.decode_tokens += 1
+                if produced is not None:
+                    s["out"].append(produced[i])
             snapshot()
             for i in active:
                 if slots[i]["count"] >= slots[i]["req"].max_new_tokens:
-                    engine.release(i)
+                    _retire(engine, cached, i, slots[i])
                     live.discard(i)
                     slots[i] = None
     finally:
@@ -247,6 +273,7 @@ def _serve_requests_packed(engine, requests, *, batch_size, prefill_step, prefil
     per prompt, 16 prompts), moves the prompts that finished into free decode slots (admission order), then runs one decode
     step over the occupied prefix.  Same counters as the one-at-a-time loop."""
     m = ServingMetrics()
+    cached = bool(getattr(engine, "prefix_cache_enabled", False))
     staging_slots = min(staging_slots, 16)
     slots: list[dict | None] = [None] * batch_size
     staged: list[dict] = []  # admission order; each holds its staging slot index
@@ -277,7 +304,7 @@ def _serve_requests_packed(engine, requests, *, batch_size, prefill_step, prefil
                 st = free_staging.pop(0)
                 engine.begin(st)
                 live.add(st)
-                staged.append({"req": requests[next_idx], "offset": 0, "count": 0, "ctx": 0, "staging": st})
+                staged.append({**_admit(engine, cached, st, requests[next_idx]), "staging": st})
                 next_idx += 1
             budget = prefill_budget
             chunks = []
@@ -301,12 +328,14 @@ def _serve_requests_packed(engine, requests, *, batch_size, prefill_step, prefil
                     if last:
                         p["count"] = 1
                         m.generated_tokens += 1
+                        if cached:
+                            p["out"].append(engine.read_tokens(p["staging"], 1)[0])
                 snapshot()
             for p in list(staged):  # admission order: the first prompt that finished takes the first free slot
                 if p["offset"] < len(p["req"].prompt_token_ids):
                     continue
                 if p["count"] >= p["req"].max_new_tokens:  # a one-token request never enters the batch
-                    engine.release(p["staging"])
+                    _retire(engine, cached, p["staging"], p)
                 elif (free := next((i for i, s in enumerate(slots) if s is None), None)) is not None:
                     engine.move(p["staging"], free)
                     live.add(free)
@@ -333,16 +362,19 @@ def _serve_requests_packed(engine, requests, *, batch_size, prefill_step, prefil
             if last_completion is not None:
                 gaps_ms.append((now - last_completion) * 1e3)
             last_completion = now
+            produced = engine.read_pending(rows) if cached else None
             for i in active:
                 s = slots[i]
                 s["count"] += 1
                 s["ctx"] += 1
                 m.generated_tokens += 1
                 m.decode_tokens += 1
+                if produced is not None:
+                    s["out"].append(produced[i])
             snapshot()
             for i in active:
                 if slots[i]["count"] >= slots[i]["req"].max_new_tokens:
-                    engine.release(i)
+                    _retire(engine, cached, i, slots[i])
                     live.discard(i)
                     slots[i] = None
     finally:
@@ -392,12 +424,23 @@ class ScheduleOnlyEngine:
     ``prefill_ms_per_token`` per prompt token and ``decode_ms(rows)`` per batched step.  Enforces the slot protocol (a slot
     is begun once, moved into a free slot, released once) so that scheduler bugs surface without hardware."""
 
-    def __init__(self, slots: int, prefill_ms_per_token: float = 0.055, decode_ms=lambda rows: 1.1 + 0.07 * rows):
+    def __init__(self, slots: int, prefill_ms_per_token: float = 0.055, decode_ms=lambda rows: 1.1 + 0.07 * rows,
+                 prefix_cache: bool = False, page_size: int = 128):
+        """``prefix_cache``: a page-granular model of the engine's prefix cache (include/tinyllm_engine.h "Prefix cache"): the full
+        pages of every token sequence a slot is known to hold are remembered (no eviction: the model has no pool), prefix_attach
+        matches whole pages plus the longest partial page, never more than len(tokens) - 1, and the virtual clock charges only the
+        tokens that are actually prefilled.  Produced ids are 0 (read_tokens / read_pending), so answers cache like prompts."""
         self.slots = [None] * slots  # context length per live slot
         self.now = 0.0
         self.prefill_ms_per_token = prefill_ms_per_token
         self.decode_ms = decode_ms
         self.page_allocations = 0
+        self.prefix_cache_enabled = bool(prefix_cache)
+        self.page_size = page_size
+        self.known = [None] * slots            # token ids the engine knows per live slot (prompt chunks, declared answers)
+        self.cached_pages: set[tuple] = set()  # every cached chain of full pages, as the tuple of its tokens
+        self.prefilled_tokens = 0
+        self.counters = {"lookups": 0, "hits": 0, "tokens_matched": 0, "tail_rows_copied": 0, "pages_registered": 0}
 
     def clock(self) -> float:
         return self.now
@@ -406,11 +449,72 @@ class ScheduleOnlyEngine:
         if self.slots[slot] is not None:
             raise RuntimeError("slot already holds a sequence")
         self.slots[slot] = 0
+        self.known[slot] = []
 
-    def prefill(self, slot, tokens, chunk=None, want_logits=True):
+    def _append(self, slot, tokens):
         if self.slots[slot] is None:
             raise RuntimeError("slot holds no sequence")
+        if self.prefix_cache_enabled and len(self.known[slot]) == self.slots[slot]:
+            self.known[slot].extend(int(t) for t in tokens)
+            self._publish(slot)
         self.slots[slot] += len(tokens)
+        self.prefilled_tokens += len(tokens)
+
+    def _publish(self, slot):
+        known, P = self.known[slot], self.page_size
+        for end in range(P, len(known) + 1, P):
+            chain = tuple(known[:end])
+            if chain not in self.cached_pages:
+                self.cached_pages.add(chain)
+                self.counters["pages_registered"] += 1
+
+    def prefix_attach(self, slot, tokens) -> int:
+        if self.slots[slot] != 0:
+            raise RuntimeError("prefix_attach needs a freshly begun slot")
+        if not self.prefix_cache_enabled:
+            return 0
+        tokens, P = [int(t) for t in tokens], self.page_size
+        limit = len(tokens) - 1
+        self.counters["lookups"] += 1
+        full = 0
+        while (full + 1) * P <= limit and tuple(tokens[:(full + 1) * P]) in self.cached_pages:
+            full += 1
+        head, tail = tuple(tokens[:full * P]), 0
+        for chain in self.cached_pages:  # the longest partial page among the children of the last matched page
+            if len(chain) == (full + 1) * P and chain[:full * P] == head:
+                rows = 0
+                while rows < min(P, limit - full * P) and chain[full * P + rows] == tokens[full * P + rows]:
+                    rows += 1
+                tail = max(tail, rows)
+        matched = full * P + tail
+        self.counters["hits"] += matched > 0
+        self.counters["tokens_matched"] += matched
+        self.counters["tail_rows_copied"] += tail
+        self.slots[slot] = matched
+        self.known[slot] = tokens[:matched]
+        return matched
+
+    def prefix_extend(self, slot, tokens):
+        if self.slots[slot] is None:
+            raise RuntimeError("slot holds no sequence")
+        if not self.prefix_cache_enabled or not tokens:
+            return
+        if len(self.known[slot]) + len(tokens) > self.slots[slot]:
+            raise RuntimeError("prefix_extend declares more tokens than the slot holds")
+        self.known[slot].extend(int(t) for t in tokens)
+        self._publish(slot)
+
+    def prefix_stats(self):
+        return {**self.counters, "entries": len(self.cached_pages), "enabled": int(self.prefix_cache_enabled)}
+
+    def read_tokens(self, slot, count):
+        return [0] * count
+
+    def read_pending(self, count=None):
+        return [0] * (count or len(self.slots))
+
+    def prefill(self, slot, tokens, chunk=None, want_logits=True):
+        self._append(slot, tokens)
         self.now += len(tokens) * self.prefill_ms_per_token * 1e-3
 
     def prefill_packed(self, chunks):
@@ -418,15 +522,14 @@ class ScheduleOnlyEngine:
         if len({c[0] for c in chunks}) != len(chunks):
             raise RuntimeError("a slot appears twice in a packed prefill")
         for slot, tokens, _last in chunks:
-            if self.slots[slot] is None:
-                raise RuntimeError("slot holds no sequence")
-            self.slots[slot] += len(tokens)
+            self._append(slot, tokens)
         self.now += sum(len(c[1]) for c in chunks) * self.prefill_ms_per_token * 1e-3
 
     def move(self, src, dst):
         if self.slots[src] is None or self.slots[dst] is not None:
             raise RuntimeError("bad move")
         self.slots[dst], self.slots[src] = self.slots[src], None
+        self.known[dst], self.known[src] = self.known[src], None
 
     def decode(self, steps, batch=None):
         for i in range(batch):
@@ -438,6 +541,7 @@ class ScheduleOnlyEngine:
         if self.slots[slot] is None:
             raise RuntimeError("slot holds no sequence")
         self.slots[slot] = None
+        self.known[slot] = None
 
     def synchronize(self):
         pass

@@ -184,6 +184,74 @@ int tl_engine_prefill_packed(tl_engine *e, int n_seqs, const int *slots, const i
  * both slots decode, rewind and release independently. */
 int tl_engine_fork(tl_engine *e, int src, int dst);
 
+/* Prefix cache: K/V reuse ACROSS requests (csrc/prefix_cache.h, csrc/kv_copy.h; the reference lists cross-request
+ * prefix caching as not covered, README.md:134-135: an extension, off by default).  With the cache off the engine is the program it
+ * was: tl_engine_release returns every page to the free list, and nothing below is allocated.  It touches no decode step.
+ *   record   while the cache is enabled the engine keeps, per live slot, the token ids of positions [0, known) on the host.
+ *            tl_engine_prefill, tl_engine_prefill_packed, tl_engine_score and tl_engine_verify extend it when they append at position
+ *            == known.  Decode steps do not (their ids live on the device): tl_engine_prefix_extend lets the caller declare the tokens
+ *            of [known, known + n), known + n <= context length, from tl_engine_read_tokens.  THE ENGINE CANNOT VERIFY DECLARED IDS: a
+ *            caller that declares other tokens than the slot holds publishes K/V under a wrong key.  tl_engine_rewind sets known =
+ *            min(known, context), tl_engine_move carries the record, tl_engine_fork copies it, begin / release empty it.
+ *   index    a full page whose page_size tokens all lie inside known is registered as an ENTRY, keyed by (parent entry, the page's
+ *            tokens); the root is the parent of page 0.  Registration is stream ordered, like tl_engine_fork: a later attach reads the
+ *            bytes behind everything enqueued before it.  A hash speeds the lookup up; a match is decided by comparing the stored
+ *            tokens, never by the hash alone.  If an equal entry already exists under another physical page, the existing entry
+ *            stays, the slot's page stays private and the slot's later pages register as children of the existing entry.  An indexed
+ *            page is never written again.
+ *   retention  when the last slot lets go of an indexed page it becomes RETAINED, not free: pages_in_use + pages_free +
+ *            pages_retained == num_pages at every return.  Wherever a need was compared with the free pages (reserve, a decode step's
+ *            pages, rewind's and fork's copy, packed prefill) it is compared with free + evictable pages, all-or-nothing as before; a
+ *            page is taken from the free list first, then by eviction, and only then is the answer "KV page pool exhausted".
+ *   eviction  victims are entries that no slot references and that have no indexed child, least recently used first, ties by the
+ *            lower page id.  An attach or a registration touches the whole chain, so ancestors are never older than descendants and
+ *            eviction is leaf first; an entry never stays indexed under a parent that is gone; a page a slot references is never
+ *            taken.  (A retained entry above a referenced descendant -- a slot that registered under an equal entry of another
+ *            request -- waits for the descendant.)  max_retained_pages > 0 caps the retained pages: whenever a page becomes retained,
+ *            victims go back to the free list until the cap holds or no victim is left; 0 = no cap.
+ *   attach   tl_engine_prefix_attach(e, slot, tokens, n, &matched): the slot is live, its context is 0, it holds no pages, n >= 1.
+ *            Cache disabled: TL_OK and matched = 0 (a scheduler may call it unconditionally).  Otherwise matched is the largest
+ *            m <= n - 1 obtainable -- one token is always left to prefill, because its row yields the logits: walk the chain of full
+ *            pages while page j's tokens equal tokens[j P, (j + 1) P) and (j + 1) P <= n - 1; these f pages are shared (reference
+ *            counted).  Then the child of the last matched entry (a page-0 entry when f = 0) with the longest common prefix r >= 1
+ *            against tokens[f P, min(n - 1, (f + 1) P)) -- ties by most recent use, then the lower page id -- has its first r rows copied
+ *            into a fresh private page (one launch, tl_kv_copy_rows): m = f P + r.  A prompt that ends exactly on a cached page
+ *            boundary therefore matches n - 1 tokens.  If no page can be had for the copy the tail is skipped; that is no error.
+ *            The block-table row, the device and host context length change exactly as tl_engine_fork changes them, known = m, the
+ *            pending token does not change: tl_engine_set_token + tl_engine_decode work afterwards as after a fork.  A slot that
+ *            processes its logits has the matched tokens marked as prompt tokens in its history (the launch prefill uses), so a hit
+ *            equals a cold run with the parameters set before the prefill.  Sampling positions, grammar state and log-probability
+ *            settings depend on the context length alone.
+ *   rewind   the copy-on-write condition of tl_engine_rewind is "the tail page is shared OR INDEXED": a rewind that lands inside an
+ *            indexed page gives the slot a private copy before anything is appended.
+ *   reproducibility  a hit reads the publisher's K/V bytes: the result is that of a cold run whose prefix was prefilled in the
+ *            publisher's chunks, bit for bit; against a cold run chunked differently it agrees within the usual chunked-versus-
+ *            one-shot band.
+ * tl_engine_prefix_cache: enabled 0 / 1, max_retained_pages >= 0; switching off clears the index first; legal at any time (a slot that
+ * is live when the cache is switched on has known = 0).  The first enabling call allocates the index and a device table of the pools;
+ * an engine that never enables the cache allocates nothing.  tl_engine_prefix_extend with the cache disabled is TL_OK and does nothing.
+ * tl_engine_prefix_clear drops every entry: retained pages return to the free list, pages in use stay with their slots.  Bad input is
+ * TL_ERR_INVALID with nothing changed. */
+typedef struct tl_prefix_stats {
+    long lookups, hits, tokens_matched, tail_rows_copied, pages_registered, pages_evicted;
+    int entries, pages_retained, max_retained_pages, enabled;
+} tl_prefix_stats;
+int tl_engine_prefix_cache(tl_engine *e, int enabled, int max_retained_pages);
+int tl_engine_prefix_attach(tl_engine *e, int slot, const int32_t *tokens, int n, int *matched);
+int tl_engine_prefix_extend(tl_engine *e, int slot, const int32_t *tokens, int n);
+int tl_engine_prefix_clear(tl_engine *e);
+int tl_engine_prefix_stats(const tl_engine *e, tl_prefix_stats *out);
+/* The tail copy over caller pools, in one launch (csrc/kv_copy.h): pools_dev is a DEVICE table of n_pools descriptors; pool i is
+ * [pages][heads][page_size][row_bytes_i] bytes.  Rows [0, rows) of every head of page from_page are copied to page to_page in every
+ * pool (16 bytes per lane where a head's run is 16-byte aligned, 4 bytes per lane otherwise, e.g. row_bytes 4); nothing else is
+ * written.  1 <= rows <= page_size, from_page != to_page; the page ids are the caller's to keep inside its pools.  Stream ordered. */
+typedef struct tl_kv_pool_desc {
+    void *base_dev;
+    size_t row_bytes;
+} tl_kv_pool_desc;
+int tl_kv_copy_rows(const tl_kv_pool_desc *pools_dev, int n_pools, int heads, int page_size, int from_page, int to_page, int rows,
+                    void *stream);
+
 /* Speculative verification (reference speculative_generate, generate.py:84-322: one target call over the pending token
  * plus the draft's proposals, logits_to_keep = all rows).  Appends n (1..8) tokens to the slot exactly like a prefill chunk
  * and returns in out_ids[i] the greedy token that follows tokens[0..i].  Nothing is recorded as generated; the caller

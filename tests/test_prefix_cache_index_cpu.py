@@ -1,0 +1,46 @@
+"""CPU tier: the prefix cache's index and page bookkeeping (csrc/prefix_cache.h) against a brute-force model.
+
+tests/prefix_cache_model_check.cpp is a stand-alone program over the header: 20,000 seeded random operations of the engine's slot
+protocol (requests that attach and publish, releases, decode tokens declared later, long prefills under pool pressure, rewinds, forks,
+clears, cap changes, the cache switched off and on) on 24 pages of 4 tokens over a 3-token alphabet, every answer compared with a scan
+of every indexed sequence and every invariant of include/tinyllm_engine.h "Prefix cache" checked after every operation.  It is built
+with AddressSanitizer and UBSan and run as its own process.  A second build forces the hash to a constant: the same answers prove that
+token equality, not the hash, decides a match."""
+
+import pathlib
+import re
+import subprocess
+
+import pytest
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+DRIVER = ROOT / "tests" / "prefix_cache_model_check.cpp"
+FLAGS = ["g++", "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", str(ROOT / "tiny-llm_amd" / "csrc")]
+
+
+def build_and_run(tmp_path, name, extra=()):
+    exe = tmp_path / name
+    subprocess.run([*FLAGS, *extra, str(DRIVER), "-o", str(exe)], check=True)
+    done = subprocess.run([str(exe), "20000", "12345"], capture_output=True, text=True, timeout=300)
+    assert done.returncode == 0, done.stdout[-2000:] + done.stderr[-4000:]
+    return done.stdout.strip()
+
+
+@pytest.fixture(scope="module")
+def real_hash_line(tmp_path_factory):
+    return build_and_run(tmp_path_factory.mktemp("prefix_model"), "model_check")
+
+
+def test_random_operations_agree_with_the_brute_force_model(real_hash_line):
+    line = real_hash_line
+    assert line.startswith("ok ops=20000 "), line
+    counts = {k: int(v) for k, v in re.findall(r"(\w+)=(\d+)\b", line)}
+    # the run exercises what it claims to: hits with and without tails, evictions, every kind of operation
+    for key in ("requests", "releases", "decodes", "extends", "rewinds", "forks", "clears", "caps", "toggles"):
+        assert counts[key] >= 100, (key, line)
+    assert counts["hits"] >= 1000 and counts["tails"] >= 1000 and counts["matched"] > counts["tails"], line
+    assert counts["registered"] >= 1000 and counts["evicted"] >= 1000, line
+
+
+def test_a_constant_hash_gives_identical_answers(tmp_path, real_hash_line):
+    assert build_and_run(tmp_path, "model_check_const_hash", ["-DTL_PREFIX_HASH_HOOK(h)=7"]) == real_hash_line

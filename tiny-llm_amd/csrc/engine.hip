@@ -16,6 +16,8 @@
 #include "grammar_stack.h"
 #include "attn_mfma.h"
 #include "aql.h"
+#include "prefix_cache.h"
+#include "kv_copy.h"
 
 namespace tl {
 
@@ -163,9 +165,13 @@ struct tl_engine {
     std::vector<int> slot_ctx;
     std::vector<char> slot_live;
     std::vector<int> slot_produced;
-    std::vector<int> free_pages;
     std::vector<char> page_was_used;
-    std::vector<int> page_refs;  // sequences holding each page (prefix sharing after tl_engine_fork); 0 = free
+    // the free list, the sequences holding each page (prefix sharing after tl_engine_fork) and, once tl_engine_prefix_cache enables it,
+    // the index of full pages by their tokens (prefix_cache.h); per slot the tokens the engine knows and the entries of its pages
+    PagePool pool;
+    std::vector<SlotRecord> prefix_rec;
+    tl_kv_pool_desc *kv_pools_dev = nullptr;  // [kv_pools_n] every K / V (and scale) pool, for the tail copy of a hit (kv_copy.h)
+    int kv_pools_n = 0;
     tl_engine_stats stats{};
     // per-slot sampling (tl_engine_set_sampling, sample.h): host mirror + device arrays [max_batch] each, written on the stream between
     // steps by poke; temperature 0 = greedy (the default, and what begin / release restore)
@@ -1188,22 +1194,29 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, ProfCtx *pc = nul
 
 // ---- page ownership: a page is shared by every sequence forked from a common prefix and returns to the free list when
 // the last holder lets go of it
+// the pool's counters as the statistics report them (pages_in_use + pages_free + retained pages == num_pages)
+static void page_stats(tl_engine *e) {
+    e->stats.pages_in_use = e->pool.in_use();
+    e->stats.pages_free = (int)e->pool.free_pages.size();
+    e->stats.peak_pages_in_use = std::max(e->stats.peak_pages_in_use, e->stats.pages_in_use);
+}
+// the one allocation path (prefix_cache.h): the free list first, then the least recently used retained page.  The caller has checked
+// e->pool.can_take
 static int take_page(tl_engine *e) {
-    const int id = e->free_pages.back();
-    e->free_pages.pop_back();
-    e->page_refs[id] = 1;
+    const int id = e->pool.take();
     e->stats.page_allocations++;
     if (e->page_was_used[id]) e->stats.reused_page_allocations++;
     e->page_was_used[id] = 1;
-    e->stats.pages_in_use++;
-    e->stats.peak_pages_in_use = std::max(e->stats.peak_pages_in_use, e->stats.pages_in_use);
+    page_stats(e);
     return id;
 }
 static void drop_page(tl_engine *e, int id) {
-    if (--e->page_refs[id] == 0) {
-        e->free_pages.push_back(id);
-        e->stats.pages_in_use--;
-    }
+    e->pool.drop(id);
+    page_stats(e);
+}
+// the slot's pages that became full inside its known tokens enter the index (no-op while the cache is off)
+static void prefix_publish(tl_engine *e, int slot) {
+    if (e->pool.enabled) e->pool.register_slot(e->prefix_rec[slot], e->slot_pages[slot]);
 }
 // K and V rows of one page, every layer (device to device, stream ordered)
 static int copy_page(tl_engine *e, int from, int to) {
@@ -1234,7 +1247,7 @@ static int reserve_locked(tl_engine *e, int slot, int total_tokens,
     if (need <= have) return TL_OK;
     if (need > c.max_pages_per_seq)
         return fail(TL_ERR_INVALID, "engine: sequence exceeds max_pages_per_seq * page_size tokens");
-    if (need - have > (int)e->free_pages.size())
+    if (!e->pool.can_take((size_t)(need - have)))
         return fail(TL_ERR_INVALID, "engine: KV page pool exhausted");
     for (int j = have; j < need; ++j) {
         const int id = take_page(e);
@@ -1257,7 +1270,7 @@ static int reserve_step_locked(tl_engine *e, int batch, std::vector<std::pair<in
             return fail(TL_ERR_INVALID, "engine: sequence exceeds max_pages_per_seq * page_size tokens");
         if (need > (int)e->slot_pages[b].size()) extra += (size_t)need - e->slot_pages[b].size();
     }
-    if (extra > e->free_pages.size()) return fail(TL_ERR_INVALID, "engine: KV page pool exhausted");
+    if (!e->pool.can_take(extra)) return fail(TL_ERR_INVALID, "engine: KV page pool exhausted");
     for (int b = 0; b < batch; ++b) {
         if (!e->slot_live[b]) continue;
         TL_TRY(reserve_locked(e, b, e->slot_ctx[b] + 1, pokes));  // cannot fail after the checks above
@@ -1628,10 +1641,8 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->smp.assign(c.max_batch, tl_engine::SampleParams{});
     e->pen.assign(c.max_batch, tl_engine::PenaltyParams{});
     e->gr_pending.assign(c.max_batch, 0);
-    e->free_pages.resize(c.num_pages);
-    for (int i = 0; i < c.num_pages; ++i) e->free_pages[i] = c.num_pages - 1 - i;  // pop_back hands out 0,1,2,...
+    e->pool.init(c.num_pages, c.page_size);  // (hands out 0, 1, 2, ...)
     e->page_was_used.assign(c.num_pages, 0);
-    e->page_refs.assign(c.num_pages, 0);
     e->stats.pages_free = c.num_pages;
     e->stats.kv_bytes = e->kv_bytes;
     e->stats.workspace_bytes = e->arena_bytes + e->tiled_bytes + e->bf16w_bytes;
@@ -1735,6 +1746,7 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     if (e->pen_mem) (void)hipFree(e->pen_mem);
     if (e->gr_mem) (void)hipFree(e->gr_mem);
     if (e->gr_stack) (void)hipFree(e->gr_stack);
+    if (e->kv_pools_dev) (void)hipFree(e->kv_pools_dev);
     if (e->score_logits) (void)hipFree(e->score_logits);
     if (e->kpool) (void)hipFree(e->kpool);
     if (e->vpool) (void)hipFree(e->vpool);
@@ -1774,6 +1786,7 @@ extern "C" int tl_engine_begin(tl_engine *e, int slot) {
     e->slot_ctx[slot] = 0;
     e->slot_produced[slot] = 0;
     e->gr_pending[slot] = 0;
+    if (e->pool.enabled) e->prefix_rec[slot].clear();
     std::vector<std::pair<int32_t *, int32_t>> pk;
     pk.emplace_back(e->live + slot, 1);
     pk.emplace_back(e->context_lens + slot, 0);
@@ -1790,7 +1803,7 @@ extern "C" int tl_engine_reserve(tl_engine *e, int slot, int total_tokens) {
     TL_REQUIRE(total_tokens >= 0, "engine_reserve: total_tokens must be nonnegative");
     std::vector<std::pair<int32_t *, int32_t>> pk;
     TL_TRY(reserve_locked(e, slot, total_tokens, pk));
-    e->stats.pages_free = (int)e->free_pages.size();
+    page_stats(e);
     return poke(e, pk);
 }
 
@@ -1803,13 +1816,14 @@ extern "C" int tl_engine_release(tl_engine *e, int slot) {
         pk.emplace_back(e->block_table + (size_t)slot * e->cfg.max_pages_per_seq + j, -1);
     }
     pages.clear();
+    if (e->pool.enabled) e->prefix_rec[slot].clear();
     e->slot_live[slot] = 0;
     e->slot_ctx[slot] = 0;
     e->gr_pending[slot] = 0;
     pk.emplace_back(e->live + slot, 0);
     pk.emplace_back(e->context_lens + slot, 0);
     pk.emplace_back(e->tokens + slot, 0);
-    e->stats.pages_free = (int)e->free_pages.size();
+    page_stats(e);
     TL_TRY(poke(e, pk));
     TL_TRY(lp_write(e, slot, -1));
     TL_TRY(pen_reset(e, slot));
@@ -1827,10 +1841,16 @@ extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
     {
         // the copy of a shared tail page needs one free page; pages this rewind itself returns count.  Checked before
         // anything is mutated, so a failing rewind leaves host mirrors and device tables untouched.
-        const bool cow = keep > 0 && ctx % e->cfg.page_size != 0 && keep <= (int)pages.size() && e->page_refs[pages[keep - 1]] > 1;
-        size_t will_free = 0;
-        for (int j = keep; j < (int)pages.size(); ++j) will_free += e->page_refs[pages[j]] == 1 ? 1 : 0;
-        TL_REQUIRE(!cow || e->free_pages.size() + will_free >= 1, "engine_rewind: KV page pool exhausted (copy of a shared tail page)");
+        // (the pages it returns are counted as they will stand: their holds are taken off while the pool is asked)
+        const bool cow = keep > 0 && ctx % e->cfg.page_size != 0 && keep <= (int)pages.size() &&
+                         (e->pool.refs[pages[keep - 1]] > 1 || e->pool.is_indexed(pages[keep - 1]));
+        if (cow) {
+            size_t will_free = 0;
+            for (int j = keep; j < (int)pages.size(); ++j) will_free += --e->pool.refs[pages[j]] == 0 && !e->pool.is_indexed(pages[j]) ? 1 : 0;
+            const bool ok = will_free >= 1 || e->pool.can_take(1);
+            for (int j = keep; j < (int)pages.size(); ++j) e->pool.refs[pages[j]]++;
+            TL_REQUIRE(ok, "engine_rewind: KV page pool exhausted (copy of a shared tail page)");
+        }
     }
     while ((int)pages.size() > keep) {
         drop_page(e, pages.back());
@@ -1838,7 +1858,7 @@ extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
         pages.pop_back();
     }
     // the next append lands in the tail page: if a fork shares it, give this sequence its own copy first
-    if (keep > 0 && ctx % e->cfg.page_size != 0 && e->page_refs[pages[keep - 1]] > 1) {
+    if (keep > 0 && ctx % e->cfg.page_size != 0 && (e->pool.refs[pages[keep - 1]] > 1 || e->pool.is_indexed(pages[keep - 1]))) {
         const int old_id = pages[keep - 1];  // a free page exists: checked above
         const int fresh = take_page(e);
         TL_TRY(copy_page(e, old_id, fresh));
@@ -1847,8 +1867,9 @@ extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
         pk.emplace_back(e->block_table + (size_t)slot * e->cfg.max_pages_per_seq + (keep - 1), fresh);
     }
     e->slot_ctx[slot] = ctx;
+    if (e->pool.enabled) e->prefix_rec[slot].rewind(ctx, e->cfg.page_size);
     pk.emplace_back(e->context_lens + slot, ctx);
-    e->stats.pages_free = (int)e->free_pages.size();
+    page_stats(e);
     return poke(e, pk);
 }
 
@@ -1864,13 +1885,13 @@ extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
     const int ctx = e->slot_ctx[src];
     const int full = ctx / c.page_size;
     const bool partial = ctx % c.page_size != 0;
-    TL_REQUIRE(!partial || !e->free_pages.empty(), "engine_fork: KV page pool exhausted");
+    TL_REQUIRE(!partial || e->pool.can_take(1), "engine_fork: KV page pool exhausted");
     const auto &from = e->slot_pages[src];
     auto &to = e->slot_pages[dst];
     to.clear();
     std::vector<std::pair<int32_t *, int32_t>> pk;
     for (int j = 0; j < full; ++j) {
-        e->page_refs[from[j]]++;
+        e->pool.share(from[j]);
         to.push_back(from[j]);
         pk.emplace_back(e->block_table + (size_t)dst * c.max_pages_per_seq + j, from[j]);
     }
@@ -1884,19 +1905,122 @@ extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
     e->slot_ctx[dst] = ctx;
     e->slot_produced[dst] = 0;
     e->gr_pending[dst] = e->gr_pending[src];
+    if (e->pool.enabled) e->prefix_rec[dst] = e->prefix_rec[src];
     pk.emplace_back(e->live + dst, 1);
     pk.emplace_back(e->context_lens + dst, ctx);
     pk.emplace_back(e->produced + dst, 0);
     TL_TRY(poke(e, pk));
     // the pending input token travels on the device
     TL_HIP(hipMemcpyAsync(e->tokens + dst, e->tokens + src, sizeof(int32_t), hipMemcpyDeviceToDevice, e->stream));
-    e->stats.pages_free = (int)e->free_pages.size();
+    page_stats(e);
     // the sampling parameters are copied too (seed included: give the child its own seed, or both draw the same tokens)
     if (!smp_is_default(e->smp[src]) || !smp_is_default(e->smp[dst])) TL_TRY(smp_write(e, dst, e->smp[src]));
     // ... and the log-probability setting with the pending token's record
     TL_TRY(lp_carry(e, src, dst, false));
     // ... and the penalties, the bias list and the history
     return pen_carry(e, src, dst, false);
+}
+
+// ---- prefix cache (include/tinyllm_engine.h "Prefix cache"; the index is prefix_cache.h, the tail copy kv_copy.h) ----------------------
+extern "C" int tl_engine_prefix_cache(tl_engine *e, int enabled, int max_retained_pages) {
+    TL_REQUIRE(e, "engine_prefix_cache: null engine");
+    TL_REQUIRE(enabled == 0 || enabled == 1, "engine_prefix_cache: enabled is 0 or 1");
+    TL_REQUIRE(max_retained_pages >= 0, "engine_prefix_cache: max_retained_pages must be nonnegative (0 = no cap)");
+    const tl_engine_config &c = e->cfg;
+    if (!enabled) {
+        e->pool.disable();
+        e->prefix_rec.clear();
+        page_stats(e);
+        return TL_OK;
+    }
+    if (!e->kv_pools_dev) {  // the table of every pool, once: pool addresses never change after creation
+        std::vector<tl_kv_pool_desc> pools;
+        for (int l = 0; l < c.num_layers; ++l) {
+            pools.push_back({e->layer_k(l), (size_t)c.head_dim * e->kv_elem_bytes()});
+            pools.push_back({e->layer_v(l), (size_t)c.head_dim * e->kv_elem_bytes()});
+            if (e->kv_format == TL_KV_FP8_E4M3) {
+                pools.push_back({e->layer_ks(l), sizeof(float)});
+                pools.push_back({e->layer_vs(l), sizeof(float)});
+            }
+        }
+        if (hipMalloc((void **)&e->kv_pools_dev, pools.size() * sizeof(tl_kv_pool_desc)) != hipSuccess)
+            return fail(TL_ERR_HIP, "engine_prefix_cache: hipMalloc(pool table) failed");
+        const hipError_t rc = hipMemcpy(e->kv_pools_dev, pools.data(), pools.size() * sizeof(tl_kv_pool_desc), hipMemcpyHostToDevice);
+        if (rc != hipSuccess) {
+            (void)hipFree(e->kv_pools_dev);
+            e->kv_pools_dev = nullptr;
+            return fail(TL_ERR_HIP, std::string("engine_prefix_cache: hipMemcpy(pool table): ") + hipGetErrorString(rc));
+        }
+        e->kv_pools_n = (int)pools.size();
+    }
+    if (!e->pool.enabled) e->prefix_rec.assign(c.max_batch, SlotRecord{});
+    e->pool.enable(max_retained_pages);
+    page_stats(e);
+    return TL_OK;
+}
+
+extern "C" int tl_engine_prefix_clear(tl_engine *e) {
+    TL_REQUIRE(e, "engine_prefix_clear: null engine");
+    e->pool.clear();
+    page_stats(e);
+    return TL_OK;
+}
+
+extern "C" int tl_engine_prefix_stats(const tl_engine *e, tl_prefix_stats *out) {
+    TL_REQUIRE(e && out, "engine_prefix_stats: null argument");
+    const PrefixCounters &k = e->pool.ctr;
+    *out = tl_prefix_stats{k.lookups, k.hits, k.tokens_matched, k.tail_rows_copied, k.pages_registered, k.pages_evicted,
+                           e->pool.n_entries, e->pool.retained, e->pool.max_retained, e->pool.enabled ? 1 : 0};
+    return TL_OK;
+}
+
+extern "C" int tl_engine_prefix_extend(tl_engine *e, int slot, const int32_t *tokens, int n) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(tokens && n >= 1, "engine_prefix_extend: need at least one token");
+    if (!e->pool.enabled) return TL_OK;
+    auto &known = e->prefix_rec[slot].known;
+    TL_REQUIRE((long)known.size() + n <= e->slot_ctx[slot], "engine_prefix_extend: more tokens than the slot holds beyond its known ones");
+    for (int i = 0; i < n; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < e->cfg.vocab_size, "engine_prefix_extend: token id out of range");
+    known.insert(known.end(), tokens, tokens + n);
+    prefix_publish(e, slot);
+    page_stats(e);
+    return TL_OK;
+}
+
+extern "C" int tl_engine_prefix_attach(tl_engine *e, int slot, const int32_t *tokens, int n, int *matched) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(tokens && matched && n >= 1, "engine_prefix_attach: need at least one token and a place for the result");
+    TL_REQUIRE(e->slot_ctx[slot] == 0 && e->slot_pages[slot].empty(), "engine_prefix_attach: the slot already holds tokens or pages");
+    *matched = 0;
+    if (!e->pool.enabled) return TL_OK;
+    const tl_engine_config &c = e->cfg;
+    auto &pages = e->slot_pages[slot];
+    const AttachResult a = e->pool.attach(e->prefix_rec[slot], pages, tokens, n, c.max_pages_per_seq);
+    if (a.tail_rows > 0) {
+        e->stats.page_allocations++;
+        if (e->page_was_used[a.tail_to]) e->stats.reused_page_allocations++;
+        e->page_was_used[a.tail_to] = 1;
+    }
+    page_stats(e);
+    if (a.matched == 0) return TL_OK;
+    if (a.tail_rows > 0)
+        TL_TRY(kv_copy_rows(e->kv_pools_dev, e->kv_pools_n, c.num_kv_heads, c.page_size, a.tail_from, a.tail_to, a.tail_rows, e->stream));
+    std::vector<std::pair<int32_t *, int32_t>> pk;
+    for (size_t j = 0; j < pages.size(); ++j) pk.emplace_back(e->block_table + (size_t)slot * c.max_pages_per_seq + j, pages[j]);
+    e->slot_ctx[slot] = a.matched;
+    pk.emplace_back(e->context_lens + slot, a.matched);
+    TL_TRY(poke(e, pk));
+    if (step_processes_slot(e, slot)) {  // the matched tokens are prompt tokens of the slot's history, as a prefill would have marked them
+        for (int at = 0; at < a.matched; at += c.max_prefill_rows) {
+            const int len = std::min(c.max_prefill_rows, a.matched - at);
+            TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens + at, (size_t)len * 4, hipMemcpyHostToDevice, e->stream));
+            const LogitMarkArgs mk{e->prefill_tokens, len, c.vocab_size, (uint32_t *)e->pen_history, (long)slot * c.vocab_size};
+            hipLaunchKernelGGL(logit_mark_prompt_kernel, dim3(ceil_div(len, 256)), dim3(256), 0, e->stream, mk);
+            TL_CHECK_LAUNCH("engine prompt marking");
+        }
+    }
+    *matched = a.matched;
+    return TL_OK;
 }
 
 // Move a (prefilled) sequence from slot `src` to the free slot `dst`: the reference prefills a request in its own
@@ -1931,6 +2055,10 @@ extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
     e->slot_produced[src] = 0;
     e->gr_pending[dst] = e->gr_pending[src];
     e->gr_pending[src] = 0;
+    if (e->pool.enabled) {
+        e->prefix_rec[dst] = std::move(e->prefix_rec[src]);
+        e->prefix_rec[src].clear();
+    }
     // the sampling parameters go with the sequence
     if (!smp_is_default(e->smp[src]) || !smp_is_default(e->smp[dst])) {
         const tl_engine::SampleParams v = e->smp[src];
@@ -2372,7 +2500,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
         TL_TRY(reserve_locked(e, seqs[i].slot, seqs[i].start + seqs[i].len, pk));
         pk.emplace_back(e->scratch_ctx + i, seqs[i].start + seqs[i].len);
     }
-    e->stats.pages_free = (int)e->free_pages.size();
+    page_stats(e);
     TL_TRY(poke(e, pk));
     TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens, (size_t)total * 4, hipMemcpyHostToDevice, e->stream));
     for (int i = 0; i < n_seqs; ++i) {  // the chunk's tokens enter the history of a slot that processes its logits (logit_process.h)
@@ -2441,6 +2569,13 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
         TL_CHECK_LAUNCH(packed ? "engine packed prefill layer" : "engine prefill layer");
     }
     for (int i = 0; i < n_seqs; ++i) {
+        if (e->pool.enabled) {  // tokens appended where the record ends extend it, and pages that filled up enter the index
+            auto &known = e->prefix_rec[seqs[i].slot].known;
+            if ((int)known.size() == seqs[i].start) {
+                known.insert(known.end(), tokens + seqs[i].row0, tokens + seqs[i].row0 + seqs[i].len);
+                prefix_publish(e, seqs[i].slot);
+            }
+        }
         e->slot_ctx[seqs[i].slot] = seqs[i].start + seqs[i].len;
         e->gr_pending[seqs[i].slot] = 0;  // a pending token that is prefilled past is never fed
         pk.emplace_back(e->context_lens + seqs[i].slot, seqs[i].start + seqs[i].len);
@@ -2530,7 +2665,7 @@ static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const
         for (int i = 0; i < n_seqs; ++i) wanted += want_logits[i] ? 1 : 0;
         TL_REQUIRE(wanted <= std::max(c.max_batch, 8), "engine_prefill_packed: more prompts end in this pass than the logits buffer has rows (max(max_batch, 8))");
     }
-    TL_REQUIRE(extra_pages <= e->free_pages.size(), "engine: KV page pool exhausted");  // checked before anything is mutated
+    TL_REQUIRE(e->pool.can_take(extra_pages), "engine: KV page pool exhausted");  // checked before anything is mutated
     for (int i = 0; i < total; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < c.vocab_size, "engine_prefill_packed: token id out of range");
 
     std::vector<PrefillSeq> seqs(n_seqs);
@@ -2645,7 +2780,7 @@ static int prepare_step(tl_engine *e, int batch, SplitPlan *sp, bool *on_queue =
         return rc;
     }
     if (!pk.empty()) {
-        e->stats.pages_free = (int)e->free_pages.size();
+        page_stats(e);
         if (on_queue && *on_queue) {
             TL_TRY(aql_drain(e));
             *on_queue = false;
@@ -2798,7 +2933,7 @@ extern "C" const int32_t *tl_engine_tokens_dev(const tl_engine *e) { return e ? 
 extern "C" int tl_engine_get_stats(const tl_engine *e, tl_engine_stats *out) {
     TL_REQUIRE(e && out, "engine_get_stats: null argument");
     *out = e->stats;
-    out->pages_free = (int)e->free_pages.size();
+    out->pages_free = (int)e->pool.free_pages.size();
     return TL_OK;
 }
 
@@ -3092,4 +3227,9 @@ extern "C" int tl_decode_attention_plan(int batch, int max_context, int num_head
     const SplitPlan sp = pick_decode_splits(&e, batch, std::max(1, max_context + 1));
     out3[0] = sp.n_splits, out3[1] = sp.tokens_per_split, out3[2] = sp.rq;
     return 1;
+}
+
+extern "C" int tl_kv_copy_rows(const tl_kv_pool_desc *pools_dev, int n_pools, int heads, int page_size, int from_page, int to_page,
+                               int rows, void *stream) {
+    return kv_copy_rows(pools_dev, n_pools, heads, page_size, from_page, to_page, rows, (hipStream_t)stream);
 }

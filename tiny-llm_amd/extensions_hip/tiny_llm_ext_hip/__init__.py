@@ -141,6 +141,18 @@ class TlLinearEx(ctypes.Structure):
                 ("ss_out_dev", _c_void_p), ("norm_out_dev", _c_void_p), ("out_w_dev", _c_void_p), ("fragment_order", _c_int)]
 
 
+class TlPrefixStats(ctypes.Structure):
+    """tl_prefix_stats (include/tinyllm_engine.h): the prefix cache's counters."""
+    _fields_ = [("lookups", ctypes.c_long), ("hits", ctypes.c_long), ("tokens_matched", ctypes.c_long),
+                ("tail_rows_copied", ctypes.c_long), ("pages_registered", ctypes.c_long), ("pages_evicted", ctypes.c_long),
+                ("entries", _c_int), ("pages_retained", _c_int), ("max_retained_pages", _c_int), ("enabled", _c_int)]
+
+
+class TlKvPoolDesc(ctypes.Structure):
+    """tl_kv_pool_desc: one pool [pages][heads][page_size][row_bytes] of tl_kv_copy_rows' device table."""
+    _fields_ = [("base_dev", _c_void_p), ("row_bytes", _c_size_t)]
+
+
 class TlAttentionInfo(ctypes.Structure):
     _fields_ = [("n_splits", _c_int), ("tokens_per_split", _c_int), ("heads_per_workgroup", _c_int),
                 ("launches", _c_int)]
@@ -188,6 +200,12 @@ _SIGNATURES.update({
     "tl_engine_move": (_c_int, [_c_void_p, _c_int, _c_int]),
     "tl_engine_fork": (_c_int, [_c_void_p, _c_int, _c_int]),
     "tl_engine_read_pending": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32)]),
+    "tl_engine_prefix_cache": (_c_int, [_c_void_p, _c_int, _c_int]),
+    "tl_engine_prefix_attach": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _P(_c_int)]),
+    "tl_engine_prefix_extend": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int]),
+    "tl_engine_prefix_clear": (_c_int, [_c_void_p]),
+    "tl_engine_prefix_stats": (_c_int, [_c_void_p, _P(TlPrefixStats)]),
+    "tl_kv_copy_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p]),
     "tl_engine_prefill": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _c_int]),
     "tl_engine_prefill_packed": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int), _P(ctypes.c_int32), _P(ctypes.c_int), _P(ctypes.c_int)]),
     "tl_engine_verify": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _P(ctypes.c_int32)]),

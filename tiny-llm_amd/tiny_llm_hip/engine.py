@@ -62,8 +62,11 @@ class DecodeEngine:
 
     def __init__(self, mlx_model: Any, *, page_size: int = 128, num_pages: int = 512, max_batch: int = 1,
                  max_pages_per_seq: int | None = None, max_prefill_rows: int = 2048, options: dict | None = None,
-                 kv_format: str = "bf16"):
-        """``kv_format``: "bf16" (the reference's cache) or "fp8" -- K / V pages as OCP FP8 E4M3 codes with one power-of-two scale per
+                 kv_format: str = "bf16", prefix_cache: bool | int = False):
+        """``prefix_cache``: keep the K / V of full pages after their request is released and hand them to later requests that start
+        with the same tokens (tl_engine_prefix_cache; prefix_attach / prefix_extend); an int (> 0) also caps the retained pages.  Off
+        by default: the engine then is the program it was.
+        ``kv_format``: "bf16" (the reference's cache) or "fp8" -- K / V pages as OCP FP8 E4M3 codes with one power-of-two scale per
         row (tl_engine_create_kv; head_dim 128; the reference has no quantised cache, README.md:134-135: an extension, off by default).
         ``options`` (tests / lab tools only): routes with an A/B twin, by the names of tl_engine_set_option (include/tinyllm_engine.h),
         e.g. {"qmm7": 0}; the environment variable TL_ENGINE_OPTIONS ("qmm7=0,aql_fences=1") adds to them for the A/B scripts under tools/."""
@@ -129,6 +132,15 @@ class DecodeEngine:
             _ext.check(_lib.tl_engine_set_option(self._h, str(name).strip().encode(), int(value)))
         for i, mlp in moe_layers.items():
             self._attach_moe(i, mlp, args)
+        if isinstance(prefix_cache, bool):
+            cap = 0
+        elif isinstance(prefix_cache, int) and prefix_cache > 0:
+            cap = prefix_cache
+        else:
+            raise ValueError(f"prefix_cache must be a bool or a positive int (the retention cap in pages), got {prefix_cache!r}")
+        self.prefix_cache_enabled = bool(prefix_cache)
+        if self.prefix_cache_enabled:
+            _ext.check(_lib.tl_engine_prefix_cache(self._h, 1, cap))
 
     def _attach_moe(self, layer: int, mlp: Any, args: Any) -> None:
         """Hand the router and the stacked experts of one sparse layer to the engine (tl_engine_set_moe_layer)."""
@@ -183,6 +195,43 @@ class DecodeEngine:
     def fork(self, src: int, dst: int) -> None:
         """Make free slot ``dst`` a copy-on-write twin of ``src`` (shared prefix pages, own tail page)."""
         _ext.check(_lib.tl_engine_fork(self._h, src, dst))
+
+    # -- prefix cache (tl_engine_prefix_*; include/tinyllm_engine.h "Prefix cache") --------------------------
+    def prefix_attach(self, slot: int, tokens: Sequence[int]) -> int:
+        """Give the freshly begun ``slot`` the cached K / V of the longest known prefix of ``tokens`` (at most len(tokens) - 1 of them:
+        the last token's row yields the logits) and return how many tokens it now holds: prefill ``tokens[matched:]``.  0 with the cache
+        off.  Call it after the slot's settings (penalties, grammar, sampling) and before its first chunk."""
+        tokens = [int(t) for t in tokens]
+        if not tokens:
+            raise ValueError("prefix_attach needs at least one token")
+        arr = (ctypes.c_int32 * len(tokens))(*tokens)
+        matched = ctypes.c_int(0)
+        _ext.check(_lib.tl_engine_prefix_attach(self._h, slot, arr, len(tokens), ctypes.byref(matched)))
+        return matched.value
+
+    def prefix_extend(self, slot: int, tokens: Sequence[int]) -> None:
+        """Declare the ids of the tokens the slot holds beyond the ones the engine knows (decode steps keep their ids on the device):
+        a scheduler passes ``out[:-1]`` before ``release`` -- the last produced token was never fed -- so that a follow-up turn finds
+        prompt and answer cached.  The engine cannot verify the ids.  Nothing happens for an empty list or with the cache off."""
+        tokens = [int(t) for t in tokens]
+        if not tokens:
+            return
+        arr = (ctypes.c_int32 * len(tokens))(*tokens)
+        _ext.check(_lib.tl_engine_prefix_extend(self._h, slot, arr, len(tokens)))
+
+    def set_prefix_cache(self, enabled: bool, max_retained_pages: int = 0) -> None:
+        """Switch the cache on or off at any time (tl_engine_prefix_cache); off drops every entry first.  0 pages = no cap."""
+        _ext.check(_lib.tl_engine_prefix_cache(self._h, int(bool(enabled)), int(max_retained_pages)))
+        self.prefix_cache_enabled = bool(enabled)
+
+    def prefix_clear(self) -> None:
+        """Drop every cached entry; retained pages return to the free list."""
+        _ext.check(_lib.tl_engine_prefix_clear(self._h))
+
+    def prefix_stats(self) -> dict:
+        s = _ext.TlPrefixStats()
+        _ext.check(_lib.tl_engine_prefix_stats(self._h, ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in s._fields_}
 
     def read_pending(self, count: int | None = None) -> list[int]:
         """Pending (= most recently generated) token id of slots [0, count); synchronises."""
@@ -412,7 +461,8 @@ class DecodeEngine:
         device sampler, set_sampling).  With ``logprobs`` an int (0 .. 20 alternatives, set_logprobs): returns (ids, records).
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` (set_penalties, set_logit_bias) are set
         before the prefill, so the prompt's tokens are in the slot's history; so is ``grammar`` (set_grammar): the ids are then text of
-        its language, followed by EOS ids once it has ended."""
+        its language, followed by EOS ids once it has ended.  On an engine with the prefix cache on, the slot first attaches the cached
+        prefix of the prompt (prefix_attach) and prefills the rest, and declares the answer before its release (prefix_extend)."""
         args = sampling_args(temperature, top_k, top_p, seed)
         top_n = logprobs_arg(logprobs)
         pen = penalty_args(repetition_penalty, presence_penalty, frequency_penalty)
@@ -429,10 +479,14 @@ class DecodeEngine:
                 self.set_sampling(slot, *args)
             if top_n >= 0:
                 self.set_logprobs(slot, top_n)
-            self.prefill(slot, prompt, chunk=chunk)
+            prompt = [int(t) for t in prompt]
+            matched = self.prefix_attach(slot, prompt) if self.prefix_cache_enabled and prompt else 0
+            self.prefill(slot, prompt[matched:], chunk=chunk)
             if max_new_tokens > 1:
                 self.decode(max_new_tokens - 1, batch=slot + 1)
             ids = self.read_tokens(slot, max_new_tokens)
+            if self.prefix_cache_enabled:  # the answer's fed tokens are declared, so that a follow-up turn finds prompt and answer cached
+                self.prefix_extend(slot, ids[:-1])
             return (ids, self.read_logprobs(slot, max_new_tokens)) if top_n >= 0 else ids
         finally:
             self.release(slot)
@@ -643,7 +697,10 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     like ``eos_token_id``); applied when a request enters the staging slot,
     and carried by the engine through its slot moves.  ``logprobs``: None, or an int (0 .. 20 alternatives): every request records
     its tokens' log-probabilities (set_logprobs), read in the same turn as the pending ids, and the result is
-    [(prompt_idx, generated ids, records)]."""
+    [(prompt_idx, generated ids, records)].
+    An engine built with ``prefix_cache`` has every request attach the cached prefix of its prompt (prefix_attach: after its settings,
+    before its first chunk, which then starts at the matched offset) and declare its fed answer tokens at retirement (prefix_extend
+    before release), so a follow-up turn finds prompt and answer cached.  Results keep their order and content rules."""
     if batch_size <= 0 or prefill_step <= 0:
         raise ValueError("batch_size and prefill_step must be positive")
     if engine.max_batch < batch_size + 1:
@@ -655,6 +712,13 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
 
     def ends(req, token):  # the request's own EOS ids where it has a grammar
         return token == eos_token_id or (req["eos"] is not None and token in req["eos"])
+
+    cached = bool(getattr(engine, "prefix_cache_enabled", False))
+
+    def retire(slot, req):  # with the cache on, the answer's fed tokens are declared first (the last produced one was never fed)
+        if cached:
+            engine.prefix_extend(slot, req["out"][:-1])
+        engine.release(slot)
 
     top_n = logprobs_arg(logprobs)
     staging = batch_size
@@ -683,6 +747,8 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                 if top_n >= 0:
                     engine.set_logprobs(staging, top_n)
                 pending = {"eos": grammar.eos_ids if grammar is not None else None, "idx": idx, "tokens": [int(t) for t in prompts[idx]], "offset": 0, "out": [], "limit": limits[idx], "lp": []}
+                if cached and pending["tokens"]:  # after the settings, before the first chunk: the prompt starts behind the cached prefix
+                    pending["offset"] = engine.prefix_attach(staging, pending["tokens"])
             if pending is not None:
                 total = len(pending["tokens"])
                 if pending["offset"] < total:
@@ -697,7 +763,7 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                 if pending["offset"] >= total:
                     done = len(pending["out"]) >= pending["limit"] or ends(pending, pending["out"][-1])
                     if done:
-                        engine.release(staging)
+                        retire(staging, pending)
                         live_slots.discard(staging)
                         finished.append((pending["idx"], pending["out"]) + ((pending["lp"],) if top_n >= 0 else ()))
                         pending = None
@@ -747,7 +813,7 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                     if records is not None:
                         req["lp"].append(records[i])
                     if len(req["out"]) >= req["limit"] or ends(req, tokens[i]):
-                        engine.release(i)
+                        retire(i, req)
                         live_slots.discard(i)
                         finished.append((req["idx"], req["out"]) + ((req["lp"],) if top_n >= 0 else ()))
                         slots[i] = None
