@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Continuous-batching CLI over the fused engine (counterpart of the reference batch-main.py:62-101).
 
-  python batch_main.py --model <checkpoint dir> [--batch-size 5] [--prefill-step 128] [--max-seq-len 512] [--prompts-file f] [--prefix-cache [PAGES]]
+  python batch_main.py --model <checkpoint dir> [--batch-size 5] [--prefill-step 128] [--max-seq-len 512] [--prompts-file f] [--prefix-cache [PAGES]] [--swap-pages N]
 """
 import argparse
 import sys
@@ -43,6 +43,9 @@ def main(argv=None):
     ap.add_argument("--prefix-cache", nargs="?", type=int, const=0, default=None, metavar="PAGES",
                     help="keep the K / V of finished requests and reuse it for later prompts that start with the same tokens (the chat "
                          "template, a shared system prompt); PAGES caps the retained pages (default: no cap)")
+    ap.add_argument("--swap-pages", type=int, default=0, metavar="N",
+                    help="room for N KV pages in pinned host memory: under page pressure the youngest request is preempted (its K / V "
+                         "swapped out, or its prefill redone) instead of the run failing with 'KV page pool exhausted' (default 0: off)")
     ap.add_argument("--prompts-file", default=None, help="one prompt per line (default: five built-in questions)")
     args = ap.parse_args(argv)
 
@@ -63,7 +66,7 @@ def main(argv=None):
     pages_per_seq = args.max_seq_len // 128 + 2
     engine = DecodeEngine(model, page_size=128, num_pages=pages_per_seq * (args.batch_size + 1) + 2,
                           max_batch=args.batch_size + 1, max_prefill_rows=args.prefill_step, kv_format=args.kv_format,
-                          prefix_cache=False if args.prefix_cache is None else (args.prefix_cache or True))
+                          prefix_cache=False if args.prefix_cache is None else (args.prefix_cache or True), swap_pages=args.swap_pages)
     sampling = {}
     if args.sampler_temp:
         sampling.update(temperature=args.sampler_temp, top_k=args.sampler_top_k, top_p=args.sampler_top_p)

@@ -13,6 +13,12 @@ prefix of its prompt (``prefix_attach`` right after ``begin``: the prompt then s
 tokens it fed at retirement (``prefix_extend(slot, out[:-1])`` before ``release``); the loops then also keep the produced ids.  With
 the cache off the call sequence is unchanged.
 
+An engine whose ``swap_enabled`` is true (DecodeEngine(swap_pages=N), ScheduleOnlyEngine(num_pages=..., swap_pages=N)) is preempted
+under page pressure instead of failing with "KV page pool exhausted": before a decode step the youngest staging request is released
+and re-queued, or the running request admitted last is parked (its K/V swapped to host memory); parked requests resume oldest first
+and nothing new is admitted while one is parked (tiny_llm_hip.preempt, shared with batch_generate_ids).  Without swap space the
+call sequence is unchanged, error included.
+
 The engine is duck-typed (begin / prefill / move / decode / release / synchronize / stats): ``ScheduleOnlyEngine``
 runs the same schedule against a cost model instead of a GPU (capacity planning, and the CPU tests of the scheduler
 and of the multi-replica dealer).
@@ -61,6 +67,9 @@ class ServingMetrics:
     # not in the reference: what the scheduler did
     prefill_chunks: int = 0
     turns: int = 0
+    preemptions: int = 0    # requests that gave way under page pressure: parked, or released and re-queued (tiny_llm_hip.preempt)
+    recomputed: int = 0     # ... of which released from the staging slot and prefilled again
+    pages_swapped: int = 0  # KV pages moved to host memory and back (engine.swap_stats: pages_out + pages_in)
     decode_bytes: int = 0  # algorithmic HBM bytes of all decode steps: per step W + 147,456 B x sum of live contexts
     decode_step_ms: list = field(default_factory=list, repr=False)
 
@@ -112,6 +121,41 @@ def _close_holes(engine, slots: list, live: set) -> None:
         live.add(lo)
 
 
+class _NoPreemption:
+    """What the loops ask of tiny_llm_hip.preempt.Preemption, for an engine without swap space: every answer is "go ahead"."""
+    active = False
+
+    @staticmethod
+    def parked(state) -> bool:
+        return False
+
+    def admitted(self, state) -> None:
+        pass
+
+    def may_admit(self, slots) -> bool:
+        return True
+
+    def may_prefill(self, slot, tokens, slots, promised=0) -> bool:
+        return True
+
+    def chunk_pages(self, slot, tokens) -> int:
+        return 0
+
+    def before_step(self, slots, rows_of, staged, requeue) -> None:
+        pass
+
+    def report(self, metrics) -> None:
+        pass
+
+
+def _preemption(engine):
+    if not getattr(engine, "swap_enabled", False):
+        return _NoPreemption()
+    from tiny_llm_hip.preempt import Preemption  # pure host logic (the package is only needed by an engine that swaps)
+
+    return Preemption(engine)
+
+
 def _admit(engine, cached: bool, slot: int, request) -> dict:
     """The state of a request that has just begun in ``slot``: with the prefix cache on it starts behind the cached part of its prompt."""
     state = {"req": request, "offset": 0, "count": 0, "ctx": 0, "out": []}
@@ -144,10 +188,12 @@ def serve_requests(engine, requests, *, batch_size: int, prefill_step: int, pref
                                       capacity_pages=capacity_pages, clock=clock, staging_slots=staging_slots, compact=compact)
     m = ServingMetrics()
     cached = bool(getattr(engine, "prefix_cache_enabled", False))
+    pre = _preemption(engine)
     staging = batch_size
     slots: list[dict | None] = [None] * batch_size
     pending: dict | None = None
     next_idx = 0
+    front: list = []  # requests a preemption put back: they are admitted before requests[next_idx]
     live: set[int] = set()
     gaps_ms: list[float] = []
     last_completion: float | None = None
@@ -167,19 +213,24 @@ def serve_requests(engine, requests, *, batch_size: int, prefill_step: int, pref
             m.peak_tail_waste_fraction = waste / (pages * page_size) if pages else 0.0
 
     try:
-        while next_idx < len(requests) or pending is not None or any(s is not None for s in slots):
+        while front or next_idx < len(requests) or pending is not None or any(s is not None for s in slots):
             m.turns += 1
             budget = prefill_budget
             while budget > 0:
                 if pending is None:
-                    if next_idx >= len(requests):
+                    if (not front and next_idx >= len(requests)) or not pre.may_admit(slots):
                         break
                     engine.begin(staging)
                     live.add(staging)
-                    pending = _admit(engine, cached, staging, requests[next_idx])
-                    next_idx += 1
+                    if front:
+                        pending = _admit(engine, cached, staging, front.pop(0))
+                    else:
+                        pending = _admit(engine, cached, staging, requests[next_idx])
+                        next_idx += 1
                 tokens = pending["req"].prompt_token_ids
                 if pending["offset"] < len(tokens):
+                    if not pre.may_prefill(staging, min(prefill_step, len(tokens) - pending["offset"]), slots):
+                        break  # the pool cannot hold the chunk yet: decoding goes on, pages come back
                     chunk = tokens[pending["offset"]:pending["offset"] + prefill_step]
                     last = pending["offset"] + len(chunk) >= len(tokens)
                     t0 = clock()
@@ -210,10 +261,21 @@ def serve_requests(engine, requests, *, batch_size: int, prefill_step: int, pref
                 live.discard(staging)
                 live.add(free)
                 slots[free] = pending
+                pre.admitted(pending)
                 pending = None
+            if pre.active and any(s is not None for s in slots):
+                def requeue(slot, state):  # the staging request gives way: released, admitted again first
+                    nonlocal pending
+                    engine.release(slot)
+                    live.discard(slot)
+                    m.generated_tokens -= state["count"]
+                    front.insert(0, state["req"])
+                    pending = None
+
+                pre.before_step(slots, lambda: batch_size, [(staging, pending)] if pending is not None else [], requeue)
             if compact:
                 _close_holes(engine, slots, live)
-            active = [i for i, s in enumerate(slots) if s is not None]
+            active = [i for i, s in enumerate(slots) if s is not None and not pre.parked(s)]
             if not active:
                 last_completion = None  # idle time without an active decode request is not a fairness gap
                 continue
@@ -249,6 +311,7 @@ def serve_requests(engine, requests, *, batch_size: int, prefill_step: int, pref
                 engine.release(slot)
             except RuntimeError:
                 pass
+    pre.report(m)
     return _finish_metrics(engine, m, gaps_ms)
 
 
@@ -274,6 +337,8 @@ def _serve_requests_packed(engine, requests, *, batch_size, prefill_step, prefil
     step over the occupied prefix.  Same counters as the one-at-a-time loop."""
     m = ServingMetrics()
     cached = bool(getattr(engine, "prefix_cache_enabled", False))
+    pre = _preemption(engine)
+    front: list = []  # requests a preemption put back: they are admitted before requests[next_idx]
     staging_slots = min(staging_slots, 16)
     slots: list[dict | None] = [None] * batch_size
     staged: list[dict] = []  # admission order; each holds its staging slot index
@@ -298,22 +363,29 @@ def _serve_requests_packed(engine, requests, *, batch_size, prefill_step, prefil
             m.peak_tail_waste_fraction = waste / (pages * page_size) if pages else 0.0
 
     try:
-        while next_idx < len(requests) or staged or any(s is not None for s in slots):
+        while front or next_idx < len(requests) or staged or any(s is not None for s in slots):
             m.turns += 1
-            while free_staging and next_idx < len(requests):
+            while free_staging and (front or next_idx < len(requests)) and pre.may_admit(slots):
                 st = free_staging.pop(0)
                 engine.begin(st)
                 live.add(st)
-                staged.append({**_admit(engine, cached, st, requests[next_idx]), "staging": st})
-                next_idx += 1
+                if front:
+                    staged.append({**_admit(engine, cached, st, front.pop(0)), "staging": st})
+                else:
+                    staged.append({**_admit(engine, cached, st, requests[next_idx]), "staging": st})
+                    next_idx += 1
             budget = prefill_budget
             chunks = []
+            promised = 0  # pages of the chunks already in this pass (only counted by an engine with swap space)
             for p in staged:
                 tokens = p["req"].prompt_token_ids
                 rem = len(tokens) - p["offset"]
                 if rem <= 0 or budget <= 0:
                     continue
                 n = min(prefill_step, rem, budget)
+                if not pre.may_prefill(p["staging"], n, slots, promised):
+                    continue  # the pool cannot hold this chunk beside the pass's earlier ones yet
+                promised += pre.chunk_pages(p["staging"], n)
                 chunks.append((p, tokens[p["offset"]:p["offset"] + n], p["offset"] + n >= len(tokens)))
                 budget -= n
             if chunks:
@@ -340,14 +412,25 @@ def _serve_requests_packed(engine, requests, *, batch_size, prefill_step, prefil
                     engine.move(p["staging"], free)
                     live.add(free)
                     slots[free] = p
+                    pre.admitted(p)
                 else:
                     continue  # prefilled and waiting for a slot
                 live.discard(p["staging"])
                 free_staging.append(p["staging"])
                 staged.remove(p)
+            if pre.active and any(s is not None for s in slots):
+                def requeue(slot, state):  # a staged request gives way: released, admitted again first
+                    engine.release(slot)
+                    live.discard(slot)
+                    free_staging.append(slot)
+                    staged.remove(state)
+                    m.generated_tokens -= state["count"]
+                    front.insert(0, state["req"])
+
+                pre.before_step(slots, lambda: batch_size, [(p["staging"], p) for p in staged], requeue)
             if compact:
                 _close_holes(engine, slots, live)
-            active = [i for i, s in enumerate(slots) if s is not None]
+            active = [i for i, s in enumerate(slots) if s is not None and not pre.parked(s)]
             if not active:
                 last_completion = None
                 continue
@@ -383,6 +466,7 @@ def _serve_requests_packed(engine, requests, *, batch_size, prefill_step, prefil
                 engine.release(slot)
             except RuntimeError:
                 pass
+    pre.report(m)
     return _finish_metrics(engine, m, gaps_ms)
 
 
@@ -425,8 +509,14 @@ class ScheduleOnlyEngine:
     is begun once, moved into a free slot, released once) so that scheduler bugs surface without hardware."""
 
     def __init__(self, slots: int, prefill_ms_per_token: float = 0.055, decode_ms=lambda rows: 1.1 + 0.07 * rows,
-                 prefix_cache: bool = False, page_size: int = 128):
-        """``prefix_cache``: a page-granular model of the engine's prefix cache (include/tinyllm_engine.h "Prefix cache"): the full
+                 prefix_cache: bool = False, page_size: int = 128, num_pages: int | None = None, swap_pages: int = 0,
+                 swap_ms_per_page: float = 0.05):
+        """``num_pages``: a page POOL of that many pages (None, the default: no pool, nothing ever runs short): every unparked slot holds
+        ceil(context / page_size) private pages, and a prefill or decode step that needs more than the pool has left raises the
+        engine's "KV page pool exhausted" with nothing changed.  ``swap_pages``: swap space of that many host records (include/
+        tinyllm_engine.h "KV swap"): park / unpark / is_parked / step_pages / swap_stats as the engine has them, each moved page
+        costing ``swap_ms_per_page`` on the virtual clock.
+        ``prefix_cache``: a page-granular model of the engine's prefix cache (include/tinyllm_engine.h "Prefix cache"): the full
         pages of every token sequence a slot is known to hold are remembered (no eviction: the model has no pool), prefix_attach
         matches whole pages plus the longest partial page, never more than len(tokens) - 1, and the virtual clock charges only the
         tokens that are actually prefilled.  Produced ids are 0 (read_tokens / read_pending), so answers cache like prompts."""
@@ -441,6 +531,66 @@ class ScheduleOnlyEngine:
         self.cached_pages: set[tuple] = set()  # every cached chain of full pages, as the tuple of its tokens
         self.prefilled_tokens = 0
         self.counters = {"lookups": 0, "hits": 0, "tokens_matched": 0, "tail_rows_copied": 0, "pages_registered": 0}
+        self.num_pages = num_pages
+        self.swap_pages = int(swap_pages)
+        self.swap_enabled = self.swap_pages > 0
+        self.swap_ms_per_page = swap_ms_per_page
+        self.parked_slots: set[int] = set()
+        self.swap_counters = {"parks": 0, "unparks": 0, "pages_out": 0, "pages_in": 0}
+
+    # ---- the page pool and the swap space (only with num_pages / swap_pages) ---------------------------------------------
+    def _pages(self, tokens: int) -> int:
+        return (tokens + self.page_size - 1) // self.page_size
+
+    def _free_pages(self) -> int:
+        held = sum(self._pages(c) for i, c in enumerate(self.slots) if c is not None and i not in self.parked_slots)
+        return (self.num_pages if self.num_pages is not None else 1 << 30) - held
+
+    def _take(self, pages: int) -> None:
+        if pages > self._free_pages():
+            raise RuntimeError("engine: KV page pool exhausted")
+
+    def _unparked(self, slot, what):
+        if self.slots[slot] is None:
+            raise RuntimeError("slot holds no sequence")
+        if slot in self.parked_slots:
+            raise RuntimeError(f"{what}: the slot is parked")
+
+    def context_len(self, slot) -> int:
+        return -1 if self.slots[slot] is None else self.slots[slot]
+
+    def is_parked(self, slot) -> bool:
+        return slot in self.parked_slots
+
+    def step_pages(self, batch=None):
+        rows = range(batch or len(self.slots))
+        need = sum(self._pages(self.slots[i] + 1) - self._pages(self.slots[i]) for i in rows if self.slots[i] is not None and i not in self.parked_slots)
+        return need, self._free_pages()
+
+    def park(self, slot):
+        self._unparked(slot, "park")
+        pages = self._pages(self.slots[slot])
+        in_use = sum(self._pages(self.slots[i]) for i in self.parked_slots)
+        if self.slots[slot] < 1 or pages > self.swap_pages - in_use:
+            raise RuntimeError("engine_park: not enough free host records")
+        self.parked_slots.add(slot)
+        self.swap_counters["parks"] += 1
+        self.swap_counters["pages_out"] += pages
+        self.now += pages * self.swap_ms_per_page * 1e-3
+
+    def unpark(self, slot):
+        if slot not in self.parked_slots:
+            raise RuntimeError("engine_unpark: the slot is not parked")
+        pages = self._pages(self.slots[slot])
+        if pages > self._free_pages():
+            raise RuntimeError("engine_unpark: KV page pool exhausted")
+        self.parked_slots.discard(slot)
+        self.swap_counters["unparks"] += 1
+        self.swap_counters["pages_in"] += pages
+        self.now += pages * self.swap_ms_per_page * 1e-3
+
+    def swap_stats(self):
+        return {"host_pages": self.swap_pages, "host_pages_in_use": sum(self._pages(self.slots[i]) for i in self.parked_slots), **self.swap_counters}
 
     def clock(self) -> float:
         return self.now
@@ -452,8 +602,8 @@ class ScheduleOnlyEngine:
         self.known[slot] = []
 
     def _append(self, slot, tokens):
-        if self.slots[slot] is None:
-            raise RuntimeError("slot holds no sequence")
+        self._unparked(slot, "prefill")
+        self._take(self._pages(self.slots[slot] + len(tokens)) - self._pages(self.slots[slot]))
         if self.prefix_cache_enabled and len(self.known[slot]) == self.slots[slot]:
             self.known[slot].extend(int(t) for t in tokens)
             self._publish(slot)
@@ -521,6 +671,7 @@ class ScheduleOnlyEngine:
         """One pass over several slots' chunks: rows cost the same, the fixed per-pass overhead is paid once."""
         if len({c[0] for c in chunks}) != len(chunks):
             raise RuntimeError("a slot appears twice in a packed prefill")
+        self._take(sum(self._pages(self.slots[s] + len(t)) - self._pages(self.slots[s]) for s, t, _ in chunks if self.slots[s] is not None))
         for slot, tokens, _last in chunks:
             self._append(slot, tokens)
         self.now += sum(len(c[1]) for c in chunks) * self.prefill_ms_per_token * 1e-3
@@ -530,11 +681,15 @@ class ScheduleOnlyEngine:
             raise RuntimeError("bad move")
         self.slots[dst], self.slots[src] = self.slots[src], None
         self.known[dst], self.known[src] = self.known[src], None
+        if src in self.parked_slots:  # the parked records move with the slot
+            self.parked_slots.discard(src)
+            self.parked_slots.add(dst)
 
     def decode(self, steps, batch=None):
-        for i in range(batch):
-            if self.slots[i] is not None:
-                self.slots[i] += steps
+        rows = [i for i in range(batch) if self.slots[i] is not None and i not in self.parked_slots]
+        self._take(sum(self._pages(self.slots[i] + steps) - self._pages(self.slots[i]) for i in rows))
+        for i in rows:
+            self.slots[i] += steps
         self.now += steps * self.decode_ms(batch) * 1e-3
 
     def release(self, slot):
@@ -542,13 +697,14 @@ class ScheduleOnlyEngine:
             raise RuntimeError("slot holds no sequence")
         self.slots[slot] = None
         self.known[slot] = None
+        self.parked_slots.discard(slot)
 
     def synchronize(self):
         pass
 
     def step_bytes(self, batch=None):
         """W + 147,456 B x the live contexts of the step (Qwen3-4B W4: W = 2,136,832,000 B)."""
-        return 2_136_832_000 + 147_456 * sum(c for c in self.slots[:batch] if c is not None)
+        return 2_136_832_000 + 147_456 * sum(c for i, c in enumerate(self.slots[:batch]) if c is not None and i not in self.parked_slots)
 
     def stats(self):
         return {"reused_page_allocations": 0, "pages_in_use": 0}

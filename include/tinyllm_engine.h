@@ -252,6 +252,65 @@ typedef struct tl_kv_pool_desc {
 int tl_kv_copy_rows(const tl_kv_pool_desc *pools_dev, int n_pools, int heads, int page_size, int from_page, int to_page, int rows,
                     void *stream);
 
+/* KV swap: preempt a sequence under page pressure by moving its K/V to host memory, resume it later (csrc/kv_swap.h,
+ * csrc/kv_swap_model.h; the reference has no preemption: an extension, off by default).  It touches no decode step
+ * and no existing kernel, and an engine that never calls tl_engine_swap_space allocates nothing.
+ *   swap space  tl_engine_swap_space(e, host_pages): a pinned host arena of host_pages PAGE RECORDS and a device staging buffer (up to 32 MiB
+ *            of records, at least one); 0 frees both; TL_ERR_INVALID while a slot is parked.  A record holds one page of every pool
+ *            (tl_kv_page_record_bytes); tl_swap_stats.record_bytes reports it.
+ *   park     tl_engine_park(e, slot): the slot is live, not parked, context >= 1, and ceil(context / page_size) host records are free --
+ *            otherwise TL_ERR_INVALID with nothing changed.  On the engine stream, in groups of at most the staging buffer's pages: one
+ *            gather launch (tl_kv_gather_pages over the slot's block-table row), then one device-to-host copy per run of consecutive
+ *            records (one per group unless the arena is fragmented).  Then the slot lets go of its pages exactly as tl_engine_release
+ *            does -- reference counts drop, pages others share stay with them, indexed pages become retained, the rest return to the free
+ *            list (pages reserved beyond the context go too) -- its block-table row becomes -1 and the DEVICE context length and live
+ *            word become 0.  Everything else of the slot stays where it is: pending token, sampling parameters, log-probability setting
+ *            and pending record, penalties, bias list and history row, grammar and its state, token ring and produced count, the prefix
+ *            record's known tokens, and the host context length (tl_engine_context_len keeps answering it).  Freed pages may be taken
+ *            again at once: the gather is enqueued first and stream order protects the bytes.  The call does not synchronise; unpark
+ *            and release order themselves behind it on the same stream.
+ *   unpark   tl_engine_unpark(e, slot): needs ceil(context / page_size) obtainable pages (free first, then eviction), otherwise
+ *            TL_ERR_INVALID, nothing changes and the slot stays parked.  Fresh private pages, host-to-device copies + one scatter launch
+ *            per group, block-table row, context length and live word restored, host records returned to the arena.  With the prefix
+ *            cache on, the slot's full pages inside its known tokens go through the registration a prefill uses (an equal entry under
+ *            another page stays, the slot's page stays private).  pages_in_use + pages_free + pages_retained == num_pages at every return.
+ *   a parked slot  is a slot without a sequence to tl_engine_decode: plan selection, page reservation, tl_engine_step_bytes and the step's
+ *            kernels leave every piece of its state untouched (its device penalty / bias / grammar parameters are held neutral while it
+ *            is parked and written back by unpark, because the processing launch does not read the live word; the step end rewrites the
+ *            activation row and RoPE factors of every row of the range, and the next tl_engine_decode derives both again from the pending
+ *            token and the context length before its first step).  tl_engine_move carries the parked records with the slot;
+ *            tl_engine_release returns them to the arena.  Refused with TL_ERR_INVALID, nothing changed: prefill, prefill_packed, score,
+ *            verify, fork (as source), rewind, reserve, prefix_attach, prefix_extend, and park again.  Still accepted: the set_* calls
+ *            (they write per-slot arrays only) and the read calls.
+ *   routes   both replay routes are supported: park and unpark are stream work, and on the AQL route tl_engine_decode waits for the
+ *            stream before its first captured step and drains its queue before it returns, which orders a step behind an unpark and a
+ *            park behind a step.
+ * tl_engine_slot_parked: 1 / 0, < 0 if the slot is free.  tl_engine_step_pages (host only): `need` = pages the next decode step over
+ * slots [0, batch) would take, `obtainable` = free + evictable pages: a scheduler preempts while need > obtainable. */
+typedef struct tl_swap_stats {
+    int host_pages, host_pages_in_use;
+    long parks, unparks, pages_out, pages_in;
+    size_t record_bytes;
+} tl_swap_stats;
+int tl_engine_swap_space(tl_engine *e, int host_pages);
+int tl_engine_park(tl_engine *e, int slot);
+int tl_engine_unpark(tl_engine *e, int slot);
+int tl_engine_slot_parked(const tl_engine *e, int slot);
+int tl_engine_step_pages(const tl_engine *e, int batch, int *need, int *obtainable);
+int tl_engine_swap_stats(const tl_engine *e, tl_swap_stats *out);
+/* The two launches over caller pools (csrc/kv_swap.h): the pages named by the DEVICE list page_ids_dev[n_pages] are copied into
+ * (gather) / out of (scatter) a contiguous staging buffer of page records.  Record j lies at j * record_bytes and holds, pool after pool
+ * in table order, that pool's [heads][page_size][row_bytes_i] bytes; record_offsets_dev[i] = heads * page_size * (row_bytes_0 + .. +
+ * row_bytes_{i-1}) is a device table the caller fills once; record_bytes >= tl_kv_page_record_bytes(...) (0 on bad input).  Of the LAST
+ * page only rows [0, tail_rows) of every head move, 1 <= tail_rows <= page_size: gather leaves the rest of that record, scatter the
+ * rest of that page, as it was; scatter writes nothing outside the named pages.  A negative page id is skipped.  1 <= n_pages <= 65,535.
+ * Stream ordered; bad input is TL_ERR_INVALID. */
+size_t tl_kv_page_record_bytes(const tl_kv_pool_desc *pools_host, int n_pools, int heads, int page_size);
+int tl_kv_gather_pages(const tl_kv_pool_desc *pools_dev, const size_t *record_offsets_dev, int n_pools, int heads, int page_size,
+                       const int32_t *page_ids_dev, int n_pages, int tail_rows, void *staging_dev, size_t record_bytes, void *stream);
+int tl_kv_scatter_pages(const tl_kv_pool_desc *pools_dev, const size_t *record_offsets_dev, int n_pools, int heads, int page_size,
+                        const int32_t *page_ids_dev, int n_pages, int tail_rows, const void *staging_dev, size_t record_bytes, void *stream);
+
 /* Speculative verification (reference speculative_generate, generate.py:84-322: one target call over the pending token
  * plus the draft's proposals, logits_to_keep = all rows).  Appends n (1..8) tokens to the slot exactly like a prefill chunk
  * and returns in out_ids[i] the greedy token that follows tokens[0..i].  Nothing is recorded as generated; the caller

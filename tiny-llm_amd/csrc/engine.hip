@@ -18,6 +18,8 @@
 #include "aql.h"
 #include "prefix_cache.h"
 #include "kv_copy.h"
+#include "kv_swap.h"
+#include "kv_swap_model.h"
 
 namespace tl {
 
@@ -172,6 +174,19 @@ struct tl_engine {
     std::vector<SlotRecord> prefix_rec;
     tl_kv_pool_desc *kv_pools_dev = nullptr;  // [kv_pools_n] every K / V (and scale) pool, for the tail copy of a hit (kv_copy.h)
     int kv_pools_n = 0;
+    std::vector<tl_kv_pool_desc> kv_pools_host;  // the same table on the host (record offsets of kv_swap.h)
+    // KV swap (tl_engine_swap_space / _park / _unpark; kv_swap.h, kv_swap_model.h): nothing is allocated before the first swap_space.  A
+    // parked slot stays live on the host (slot_live, slot_ctx and every per-slot setting keep their values) and is a slot without a
+    // sequence on the device (live 0, context 0, block-table row -1): slot_runs() is what a decode step asks
+    std::vector<char> slot_parked;
+    std::vector<std::vector<int>> slot_records;  // a parked slot's records in the host arena, one per page
+    SwapArena swap_arena;
+    char *swap_host = nullptr, *swap_staging = nullptr;  // pinned arena [records][record_bytes]; device staging [swap_staging_pages][record_bytes]
+    size_t *swap_offsets_dev = nullptr;                  // [kv_pools_n] where each pool's bytes start inside a record
+    size_t swap_record_bytes = 0;
+    int swap_staging_pages = 0;
+    long swap_parks = 0, swap_unparks = 0, swap_pages_out = 0, swap_pages_in = 0;
+    bool slot_runs(int slot) const { return slot_live[slot] && !slot_parked[slot]; }
     tl_engine_stats stats{};
     // per-slot sampling (tl_engine_set_sampling, sample.h): host mirror + device arrays [max_batch] each, written on the stream between
     // steps by poke; temperature 0 = greedy (the default, and what begin / release restore)
@@ -528,7 +543,7 @@ static __global__ __launch_bounds__(1024) void sample_rows_kernel(const uint16_t
 // does some live slot of [0, batch) sample?  (the plan-key bit of tl_engine_decode; with it clear a step is today's greedy program)
 static bool step_samples(const tl_engine *e, int batch) {
     for (int b = 0; b < batch; ++b)
-        if (e->slot_live[b] && e->smp[b].samples()) return true;
+        if (e->slot_runs(b) && e->smp[b].samples()) return true;
     return false;
 }
 
@@ -547,7 +562,7 @@ static bool smp_is_default(const tl_engine::SampleParams &v) { return v.temperat
 static int smp_reset(tl_engine *e, int slot) { return smp_is_default(e->smp[slot]) ? TL_OK : smp_write(e, slot, tl_engine::SampleParams{}); }
 
 // does some live slot of [0, batch) record log-probabilities?  (the plan-key bit next to step_samples')
-static bool step_logprobs_slot(const tl_engine *e, int slot) { return !e->lp_n.empty() && e->slot_live[slot] && e->lp_n[slot] >= 0; }
+static bool step_logprobs_slot(const tl_engine *e, int slot) { return !e->lp_n.empty() && e->slot_runs(slot) && e->lp_n[slot] >= 0; }
 static bool step_logprobs(const tl_engine *e, int batch) {
     for (int b = 0; b < batch; ++b)
         if (step_logprobs_slot(e, b)) return true;
@@ -641,7 +656,7 @@ static int lp_carry(tl_engine *e, int src, int dst, bool move) {
 
 // ---- per-slot logit processing (logit_process.h) ------------------------------------------------------------
 // does some live slot of [0, batch) process its logits?  (the plan-key bit next to step_samples' and step_logprobs')
-static bool step_processes_slot(const tl_engine *e, int slot) { return e->pen_mem && e->slot_live[slot] && e->pen[slot].processes(); }
+static bool step_processes_slot(const tl_engine *e, int slot) { return e->pen_mem && e->slot_runs(slot) && e->pen[slot].processes(); }
 static bool step_processes(const tl_engine *e, int batch) {
     for (int b = 0; b < batch; ++b)
         if (step_processes_slot(e, b)) return true;
@@ -728,6 +743,28 @@ static int pen_alloc(tl_engine *e) {
     return TL_OK;
 }
 
+// The processing launch of a step reads a row's parameters from the device whatever the row's `live` word says, and a row that processes
+// counts its pending token and advances its grammar record.  A PARKED slot (tl_engine_park) keeps its pending token, so its device
+// parameters are switched to neutral while it is parked (on = false: penalties 1 / 0 / 0, an empty bias list, no automaton -- the row is
+// copied, nothing of the slot is written) and written back from the host mirror by tl_engine_unpark (on = true).  The bias entries, the
+// history row and the grammar record themselves are not touched either way.
+static int pen_device_switch(tl_engine *e, int slot, bool on) {
+    if (!e->pen_mem) return TL_OK;
+    const tl_engine::PenaltyParams neutral{};
+    const tl_engine::PenaltyParams &v = on ? e->pen[slot] : neutral;
+    std::vector<std::pair<int32_t *, int32_t>> pk;
+    pk.emplace_back((int32_t *)(e->pen_rep + slot), __builtin_bit_cast(int32_t, v.repetition));
+    pk.emplace_back((int32_t *)(e->pen_pres + slot), __builtin_bit_cast(int32_t, v.presence));
+    pk.emplace_back((int32_t *)(e->pen_freq + slot), __builtin_bit_cast(int32_t, v.frequency));
+    pk.emplace_back(e->pen_bias_n + slot, (int32_t)v.bias_ids.size());
+    if (e->gr_mem) {
+        const uint64_t ptr = (uint64_t)(uintptr_t)(v.grammar ? v.grammar->dev : nullptr);
+        pk.emplace_back((int32_t *)(e->gr_ptr + slot), (int32_t)(uint32_t)ptr);
+        pk.emplace_back((int32_t *)(e->gr_ptr + slot) + 1, (int32_t)(uint32_t)(ptr >> 32));
+    }
+    return poke(e, pk);
+}
+
 // the slot's parameters and bias list become `v` (validated by the caller): the device copy follows the host mirror, stream-ordered
 // between steps.  History is tracked from the call that makes the slot process: that call empties the slot's row of the table.
 static int pen_write(tl_engine *e, int slot, const tl_engine::PenaltyParams &v) {
@@ -756,7 +793,8 @@ static int pen_write(tl_engine *e, int slot, const tl_engine::PenaltyParams &v) 
         TL_HIP(hipMemcpyAsync(e->pen_bias_ids + (size_t)slot * LPR_MAX_BIAS, cur.bias_ids.data(), cur.bias_ids.size() * 4, hipMemcpyHostToDevice, e->stream));
         TL_HIP(hipMemcpyAsync(e->pen_bias_values + (size_t)slot * LPR_MAX_BIAS, cur.bias_values.data(), cur.bias_values.size() * 4, hipMemcpyHostToDevice, e->stream));
     }
-    return pk.empty() ? TL_OK : poke(e, pk);
+    if (!pk.empty()) TL_TRY(poke(e, pk));
+    return e->slot_parked[slot] ? pen_device_switch(e, slot, false) : TL_OK;  // a parked slot's row of a step stays a copy (below)
 }
 static int pen_reset(tl_engine *e, int slot) { return e->pen[slot].processes() ? pen_write(e, slot, tl_engine::PenaltyParams{}) : TL_OK; }
 
@@ -1264,7 +1302,7 @@ static int reserve_step_locked(tl_engine *e, int batch, std::vector<std::pair<in
     const tl_engine_config &c = e->cfg;
     size_t extra = 0;
     for (int b = 0; b < batch; ++b) {
-        if (!e->slot_live[b]) continue;
+        if (!e->slot_runs(b)) continue;
         const int need = (e->slot_ctx[b] + 1 + c.page_size - 1) / c.page_size;
         if (need > c.max_pages_per_seq)
             return fail(TL_ERR_INVALID, "engine: sequence exceeds max_pages_per_seq * page_size tokens");
@@ -1272,7 +1310,7 @@ static int reserve_step_locked(tl_engine *e, int batch, std::vector<std::pair<in
     }
     if (!e->pool.can_take(extra)) return fail(TL_ERR_INVALID, "engine: KV page pool exhausted");
     for (int b = 0; b < batch; ++b) {
-        if (!e->slot_live[b]) continue;
+        if (!e->slot_runs(b)) continue;
         TL_TRY(reserve_locked(e, b, e->slot_ctx[b] + 1, pokes));  // cannot fail after the checks above
         *max_ctx = std::max(*max_ctx, e->slot_ctx[b] + 1);
     }
@@ -1283,6 +1321,12 @@ static int slot_check(const tl_engine *e, int slot, bool must_be_live) {
     if (!e) return fail(TL_ERR_INVALID, "engine: null engine");
     if (slot < 0 || slot >= e->cfg.max_batch) return fail(TL_ERR_INVALID, "engine: slot out of range");
     if (must_be_live && !e->slot_live[slot]) return fail(TL_ERR_INVALID, "engine: slot holds no sequence");
+    return TL_OK;
+}
+// ... for the calls that read or write the slot's K/V: a parked slot has none on the device (tl_engine_unpark first)
+static int slot_check_unparked(const tl_engine *e, int slot) {
+    TL_TRY(slot_check(e, slot, true));
+    if (e->slot_parked[slot]) return fail(TL_ERR_INVALID, "engine: the slot is parked (its KV lies in host memory; tl_engine_unpark first)");
     return TL_OK;
 }
 
@@ -1637,6 +1681,8 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->slot_pages.assign(c.max_batch, {});
     e->slot_ctx.assign(c.max_batch, 0);
     e->slot_live.assign(c.max_batch, 0);
+    e->slot_parked.assign(c.max_batch, 0);
+    e->slot_records.assign(c.max_batch, {});
     e->slot_produced.assign(c.max_batch, 0);
     e->smp.assign(c.max_batch, tl_engine::SampleParams{});
     e->pen.assign(c.max_batch, tl_engine::PenaltyParams{});
@@ -1747,6 +1793,9 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     if (e->gr_mem) (void)hipFree(e->gr_mem);
     if (e->gr_stack) (void)hipFree(e->gr_stack);
     if (e->kv_pools_dev) (void)hipFree(e->kv_pools_dev);
+    if (e->swap_host) (void)hipHostFree(e->swap_host);
+    if (e->swap_staging) (void)hipFree(e->swap_staging);
+    if (e->swap_offsets_dev) (void)hipFree(e->swap_offsets_dev);
     if (e->score_logits) (void)hipFree(e->score_logits);
     if (e->kpool) (void)hipFree(e->kpool);
     if (e->vpool) (void)hipFree(e->vpool);
@@ -1799,7 +1848,7 @@ extern "C" int tl_engine_begin(tl_engine *e, int slot) {
 }
 
 extern "C" int tl_engine_reserve(tl_engine *e, int slot, int total_tokens) {
-    TL_TRY(slot_check(e, slot, true));
+    TL_TRY(slot_check_unparked(e, slot));
     TL_REQUIRE(total_tokens >= 0, "engine_reserve: total_tokens must be nonnegative");
     std::vector<std::pair<int32_t *, int32_t>> pk;
     TL_TRY(reserve_locked(e, slot, total_tokens, pk));
@@ -1816,6 +1865,10 @@ extern "C" int tl_engine_release(tl_engine *e, int slot) {
         pk.emplace_back(e->block_table + (size_t)slot * e->cfg.max_pages_per_seq + j, -1);
     }
     pages.clear();
+    if (e->slot_parked[slot]) {  // a parked slot holds no pages: its host records return to the arena (stream order protects their bytes)
+        e->swap_arena.give(e->slot_records[slot]);
+        e->slot_parked[slot] = 0;
+    }
     if (e->pool.enabled) e->prefix_rec[slot].clear();
     e->slot_live[slot] = 0;
     e->slot_ctx[slot] = 0;
@@ -1831,7 +1884,7 @@ extern "C" int tl_engine_release(tl_engine *e, int slot) {
 }
 
 extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
-    TL_TRY(slot_check(e, slot, true));
+    TL_TRY(slot_check_unparked(e, slot));
     TL_REQUIRE(n >= 0 && n <= e->slot_ctx[slot], "engine_rewind: cannot rewind past the start of the sequence");
     TL_REQUIRE(!e->pen[slot].processes(), "engine_rewind: the slot processes its logits (its history would keep the dropped tokens; make it neutral first)");
     const int ctx = e->slot_ctx[slot] - n;
@@ -1877,7 +1930,7 @@ extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
 // dense caches, agent/branching.py:42-208; here on the page pool).  Full pages are shared by reference count -- they are
 // never written again -- and a partially filled tail page is copied, so both sequences can append independently.
 extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
-    TL_TRY(slot_check(e, src, true));
+    TL_TRY(slot_check_unparked(e, src));
     TL_TRY(slot_check(e, dst, false));
     TL_REQUIRE(src != dst, "engine_fork: source and destination are the same slot");
     TL_REQUIRE(!e->slot_live[dst], "engine_fork: destination slot already holds a sequence");
@@ -1921,6 +1974,33 @@ extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
     return pen_carry(e, src, dst, false);
 }
 
+// the device table of every K / V (and scale) pool, built once by the first call that needs it (prefix cache, swap space): pool
+// addresses never change after creation
+static int ensure_pool_table(tl_engine *e) {
+    if (e->kv_pools_dev) return TL_OK;
+    const tl_engine_config &c = e->cfg;
+    std::vector<tl_kv_pool_desc> pools;
+    for (int l = 0; l < c.num_layers; ++l) {
+        pools.push_back({e->layer_k(l), (size_t)c.head_dim * e->kv_elem_bytes()});
+        pools.push_back({e->layer_v(l), (size_t)c.head_dim * e->kv_elem_bytes()});
+        if (e->kv_format == TL_KV_FP8_E4M3) {
+            pools.push_back({e->layer_ks(l), sizeof(float)});
+            pools.push_back({e->layer_vs(l), sizeof(float)});
+        }
+    }
+    if (hipMalloc((void **)&e->kv_pools_dev, pools.size() * sizeof(tl_kv_pool_desc)) != hipSuccess)
+        return fail(TL_ERR_HIP, "engine: hipMalloc(pool table) failed");
+    const hipError_t rc = hipMemcpy(e->kv_pools_dev, pools.data(), pools.size() * sizeof(tl_kv_pool_desc), hipMemcpyHostToDevice);
+    if (rc != hipSuccess) {
+        (void)hipFree(e->kv_pools_dev);
+        e->kv_pools_dev = nullptr;
+        return fail(TL_ERR_HIP, std::string("engine: hipMemcpy(pool table): ") + hipGetErrorString(rc));
+    }
+    e->kv_pools_n = (int)pools.size();
+    e->kv_pools_host = std::move(pools);
+    return TL_OK;
+}
+
 // ---- prefix cache (include/tinyllm_engine.h "Prefix cache"; the index is prefix_cache.h, the tail copy kv_copy.h) ----------------------
 extern "C" int tl_engine_prefix_cache(tl_engine *e, int enabled, int max_retained_pages) {
     TL_REQUIRE(e, "engine_prefix_cache: null engine");
@@ -1933,26 +2013,7 @@ extern "C" int tl_engine_prefix_cache(tl_engine *e, int enabled, int max_retaine
         page_stats(e);
         return TL_OK;
     }
-    if (!e->kv_pools_dev) {  // the table of every pool, once: pool addresses never change after creation
-        std::vector<tl_kv_pool_desc> pools;
-        for (int l = 0; l < c.num_layers; ++l) {
-            pools.push_back({e->layer_k(l), (size_t)c.head_dim * e->kv_elem_bytes()});
-            pools.push_back({e->layer_v(l), (size_t)c.head_dim * e->kv_elem_bytes()});
-            if (e->kv_format == TL_KV_FP8_E4M3) {
-                pools.push_back({e->layer_ks(l), sizeof(float)});
-                pools.push_back({e->layer_vs(l), sizeof(float)});
-            }
-        }
-        if (hipMalloc((void **)&e->kv_pools_dev, pools.size() * sizeof(tl_kv_pool_desc)) != hipSuccess)
-            return fail(TL_ERR_HIP, "engine_prefix_cache: hipMalloc(pool table) failed");
-        const hipError_t rc = hipMemcpy(e->kv_pools_dev, pools.data(), pools.size() * sizeof(tl_kv_pool_desc), hipMemcpyHostToDevice);
-        if (rc != hipSuccess) {
-            (void)hipFree(e->kv_pools_dev);
-            e->kv_pools_dev = nullptr;
-            return fail(TL_ERR_HIP, std::string("engine_prefix_cache: hipMemcpy(pool table): ") + hipGetErrorString(rc));
-        }
-        e->kv_pools_n = (int)pools.size();
-    }
+    TL_TRY(ensure_pool_table(e));
     if (!e->pool.enabled) e->prefix_rec.assign(c.max_batch, SlotRecord{});
     e->pool.enable(max_retained_pages);
     page_stats(e);
@@ -1975,7 +2036,7 @@ extern "C" int tl_engine_prefix_stats(const tl_engine *e, tl_prefix_stats *out) 
 }
 
 extern "C" int tl_engine_prefix_extend(tl_engine *e, int slot, const int32_t *tokens, int n) {
-    TL_TRY(slot_check(e, slot, true));
+    TL_TRY(slot_check_unparked(e, slot));
     TL_REQUIRE(tokens && n >= 1, "engine_prefix_extend: need at least one token");
     if (!e->pool.enabled) return TL_OK;
     auto &known = e->prefix_rec[slot].known;
@@ -1988,7 +2049,7 @@ extern "C" int tl_engine_prefix_extend(tl_engine *e, int slot, const int32_t *to
 }
 
 extern "C" int tl_engine_prefix_attach(tl_engine *e, int slot, const int32_t *tokens, int n, int *matched) {
-    TL_TRY(slot_check(e, slot, true));
+    TL_TRY(slot_check_unparked(e, slot));
     TL_REQUIRE(tokens && matched && n >= 1, "engine_prefix_attach: need at least one token and a place for the result");
     TL_REQUIRE(e->slot_ctx[slot] == 0 && e->slot_pages[slot].empty(), "engine_prefix_attach: the slot already holds tokens or pages");
     *matched = 0;
@@ -2038,12 +2099,18 @@ extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
         pk.emplace_back(e->block_table + (size_t)dst * W + j, pages[j]);
         pk.emplace_back(e->block_table + (size_t)src * W + j, -1);
     }
-    pk.emplace_back(e->context_lens + dst, e->slot_ctx[src]);
+    // a parked sequence stays parked at dst: no sequence on the device, its host records move with it
+    const bool parked = e->slot_parked[src];
+    pk.emplace_back(e->context_lens + dst, parked ? 0 : e->slot_ctx[src]);
     pk.emplace_back(e->context_lens + src, 0);
-    pk.emplace_back(e->live + dst, 1);
+    pk.emplace_back(e->live + dst, parked ? 0 : 1);
     pk.emplace_back(e->live + src, 0);
     pk.emplace_back(e->produced + dst, 0);
     TL_TRY(poke(e, pk));
+    e->slot_records[dst] = std::move(e->slot_records[src]);
+    e->slot_records[src].clear();
+    e->slot_parked[dst] = parked;
+    e->slot_parked[src] = 0;
     TL_HIP(hipMemcpyAsync(e->tokens + dst, e->tokens + src, 4, hipMemcpyDeviceToDevice, e->stream));
     e->slot_pages[dst] = std::move(e->slot_pages[src]);
     e->slot_pages[src].clear();
@@ -2069,6 +2136,175 @@ extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
     TL_TRY(lp_carry(e, src, dst, true));
     // ... and the penalties, the bias list and the history
     return pen_carry(e, src, dst, true);
+}
+
+
+// ---- KV swap (include/tinyllm_engine.h "KV swap"; kernels kv_swap.h, host accounting kv_swap_model.h) ------------------------------------
+static int swap_free(tl_engine *e) {
+    if (!e->swap_host && !e->swap_staging) return TL_OK;
+    TL_HIP(hipStreamSynchronize(e->stream));  // copies into / out of the arena may be in flight
+    if (e->swap_host) (void)hipHostFree(e->swap_host);
+    if (e->swap_staging) (void)hipFree(e->swap_staging);
+    e->stats.workspace_bytes -= (size_t)e->swap_staging_pages * e->swap_record_bytes;
+    e->swap_host = e->swap_staging = nullptr;
+    e->swap_staging_pages = 0;
+    e->swap_arena.init(0);
+    return TL_OK;
+}
+
+extern "C" int tl_engine_swap_space(tl_engine *e, int host_pages) {
+    TL_REQUIRE(e, "engine_swap_space: null engine");
+    TL_REQUIRE(host_pages >= 0, "engine_swap_space: host_pages must be nonnegative (0 frees the swap space)");
+    for (char p : e->slot_parked) TL_REQUIRE(!p, "engine_swap_space: a slot is parked (unpark or release it first)");
+    TL_TRY(swap_free(e));
+    if (host_pages == 0) return TL_OK;
+    const tl_engine_config &c = e->cfg;
+    TL_TRY(ensure_pool_table(e));
+    const size_t rec = kv_page_record_bytes(e->kv_pools_host.data(), e->kv_pools_n, c.num_kv_heads, c.page_size);
+    if (!e->swap_offsets_dev) {
+        std::vector<size_t> offsets(e->kv_pools_n);
+        size_t at = 0;
+        for (int i = 0; i < e->kv_pools_n; ++i) {
+            offsets[i] = at;
+            at += (size_t)c.num_kv_heads * c.page_size * e->kv_pools_host[i].row_bytes;
+        }
+        if (hipMalloc((void **)&e->swap_offsets_dev, offsets.size() * sizeof(size_t)) != hipSuccess)
+            return fail(TL_ERR_HIP, "engine_swap_space: hipMalloc(record offsets) failed");
+        const hipError_t rc = hipMemcpy(e->swap_offsets_dev, offsets.data(), offsets.size() * sizeof(size_t), hipMemcpyHostToDevice);
+        if (rc != hipSuccess) {
+            (void)hipFree(e->swap_offsets_dev);
+            e->swap_offsets_dev = nullptr;
+            return fail(TL_ERR_HIP, std::string("engine_swap_space: hipMemcpy(record offsets): ") + hipGetErrorString(rc));
+        }
+    }
+    // the staging buffer: up to 32 MiB of records (a group of pages per gather + copy), at least one, never more than the arena holds
+    const int staging_pages = (int)std::min<size_t>((size_t)host_pages, std::max<size_t>(1, ((size_t)32 << 20) / rec));
+    if (hipHostMalloc((void **)&e->swap_host, (size_t)host_pages * rec, hipHostMallocDefault) != hipSuccess) {
+        e->swap_host = nullptr;
+        return fail(TL_ERR_HIP, "engine_swap_space: hipHostMalloc(host arena) failed");
+    }
+    if (hipMalloc((void **)&e->swap_staging, (size_t)staging_pages * rec) != hipSuccess) {
+        (void)hipHostFree(e->swap_host);
+        e->swap_host = e->swap_staging = nullptr;
+        return fail(TL_ERR_HIP, "engine_swap_space: hipMalloc(staging) failed");
+    }
+    e->swap_record_bytes = rec;
+    e->swap_staging_pages = staging_pages;
+    e->swap_arena.init(host_pages);
+    e->stats.workspace_bytes += (size_t)staging_pages * rec;
+    return TL_OK;
+}
+
+extern "C" int tl_engine_park(tl_engine *e, int slot) {
+    TL_TRY(slot_check_unparked(e, slot));
+    const tl_engine_config &c = e->cfg;
+    const int ctx = e->slot_ctx[slot], n = swap_pages_of(ctx, c.page_size);
+    TL_REQUIRE(ctx >= 1, "engine_park: the slot holds no tokens");
+    TL_REQUIRE(e->swap_host, "engine_park: no swap space (tl_engine_swap_space)");
+    TL_REQUIRE(n <= e->swap_arena.available(), "engine_park: not enough free host records");
+    TL_REQUIRE(n <= (int)e->slot_pages[slot].size(), "engine_park: the slot holds fewer pages than its context needs");
+    // the pages leave through the slot's block-table row, which holds their ids on the device already; everything below is enqueued
+    // before the row is cleared and before anybody can take a freed page
+    std::vector<int> records;
+    e->swap_arena.take(n, records);
+    const int32_t *row = e->block_table + (size_t)slot * c.max_pages_per_seq;
+    const size_t rec = e->swap_record_bytes;
+    int rc = TL_OK;
+    for (int j0 = 0; j0 < n && rc == TL_OK; j0 += e->swap_staging_pages) {
+        const int j1 = std::min(n, j0 + e->swap_staging_pages);
+        const int tail = j1 == n ? ctx - (n - 1) * c.page_size : c.page_size;
+        rc = kv_swap_pages<true>(e->kv_pools_dev, e->swap_offsets_dev, e->kv_pools_n, c.num_kv_heads, c.page_size, row + j0, j1 - j0, tail,
+                                 e->swap_staging, rec, e->stream);
+        for (const auto &run : swap_runs(records, j0, j1)) {  // one copy per group while the arena hands out consecutive records
+            if (rc != TL_OK) break;
+            if (hipMemcpyAsync(e->swap_host + (size_t)records[run.first] * rec, e->swap_staging + (size_t)(run.first - j0) * rec,
+                               (size_t)run.second * rec, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
+                rc = fail(TL_ERR_HIP, "engine_park: hipMemcpyAsync(device to host) failed");
+        }
+    }
+    if (rc != TL_OK) {  // nothing of the slot has changed: the records go back
+        e->swap_arena.give(records);
+        return rc;
+    }
+    std::vector<std::pair<int32_t *, int32_t>> pk;
+    auto &pages = e->slot_pages[slot];
+    for (size_t j = 0; j < pages.size(); ++j) pk.emplace_back(e->block_table + (size_t)slot * c.max_pages_per_seq + j, -1);
+    e->swap_arena.give(records);  // (swap_park_host takes them again: one accounting routine for the engine and the model check)
+    if (!swap_park_host(e->pool, e->swap_arena, e->pool.enabled ? &e->prefix_rec[slot] : nullptr, pages, ctx, e->slot_records[slot]))
+        return fail(TL_ERR_INVALID, "engine_park: the slot's pages and records disagree");  // (checked above: cannot happen)
+    e->slot_parked[slot] = 1;
+    pk.emplace_back(e->live + slot, 0);
+    pk.emplace_back(e->context_lens + slot, 0);
+    page_stats(e);
+    e->swap_parks++;
+    e->swap_pages_out += n;
+    TL_TRY(poke(e, pk));
+    return e->pen[slot].processes() ? pen_device_switch(e, slot, false) : TL_OK;
+}
+
+extern "C" int tl_engine_unpark(tl_engine *e, int slot) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(e->slot_parked[slot], "engine_unpark: the slot is not parked");
+    const tl_engine_config &c = e->cfg;
+    const int ctx = e->slot_ctx[slot], n = swap_pages_of(ctx, c.page_size);
+    TL_REQUIRE(e->pool.can_take((size_t)n), "engine_unpark: KV page pool exhausted");
+    const std::vector<int> records = e->slot_records[slot];
+    auto &pages = e->slot_pages[slot];
+    if (!swap_unpark_host(e->pool, e->swap_arena, e->pool.enabled ? &e->prefix_rec[slot] : nullptr, pages, ctx, e->slot_records[slot]))
+        return fail(TL_ERR_INVALID, "engine_unpark: the slot's records do not cover its context");  // (nothing changed)
+    std::vector<std::pair<int32_t *, int32_t>> pk;
+    for (int j = 0; j < n; ++j) {
+        e->stats.page_allocations++;
+        if (e->page_was_used[pages[j]]) e->stats.reused_page_allocations++;
+        e->page_was_used[pages[j]] = 1;
+        pk.emplace_back(e->block_table + (size_t)slot * c.max_pages_per_seq + j, pages[j]);
+    }
+    page_stats(e);
+    e->slot_parked[slot] = 0;
+    e->swap_unparks++;
+    e->swap_pages_in += n;
+    TL_TRY(poke(e, pk));  // the row first: the scatter reads the page ids from it
+    const int32_t *row = e->block_table + (size_t)slot * c.max_pages_per_seq;
+    const size_t rec = e->swap_record_bytes;
+    for (int j0 = 0; j0 < n; j0 += e->swap_staging_pages) {
+        const int j1 = std::min(n, j0 + e->swap_staging_pages);
+        const int tail = j1 == n ? ctx - (n - 1) * c.page_size : c.page_size;
+        for (const auto &run : swap_runs(records, j0, j1))
+            TL_HIP(hipMemcpyAsync(e->swap_staging + (size_t)(run.first - j0) * rec, e->swap_host + (size_t)records[run.first] * rec,
+                                  (size_t)run.second * rec, hipMemcpyHostToDevice, e->stream));
+        TL_TRY(kv_swap_pages<false>(e->kv_pools_dev, e->swap_offsets_dev, e->kv_pools_n, c.num_kv_heads, c.page_size, row + j0, j1 - j0, tail,
+                                    e->swap_staging, rec, e->stream));
+    }
+    pk.emplace_back(e->context_lens + slot, ctx);
+    pk.emplace_back(e->live + slot, 1);
+    TL_TRY(poke(e, pk));
+    return e->pen[slot].processes() ? pen_device_switch(e, slot, true) : TL_OK;
+}
+
+extern "C" int tl_engine_slot_parked(const tl_engine *e, int slot) {
+    if (!e || slot < 0 || slot >= e->cfg.max_batch || !e->slot_live[slot]) return -1;
+    return e->slot_parked[slot] ? 1 : 0;
+}
+
+extern "C" int tl_engine_step_pages(const tl_engine *e, int batch, int *need, int *obtainable) {
+    TL_REQUIRE(e && need && obtainable, "engine_step_pages: null argument");
+    TL_REQUIRE(batch > 0 && batch <= e->cfg.max_batch, "engine_step_pages: batch out of range");
+    int extra = 0;
+    for (int b = 0; b < batch; ++b) {
+        if (!e->slot_runs(b)) continue;
+        const int pages = swap_pages_of(e->slot_ctx[b] + 1, e->cfg.page_size);
+        extra += std::max(0, pages - (int)e->slot_pages[b].size());
+    }
+    *need = extra;
+    *obtainable = (int)e->pool.available();
+    return TL_OK;
+}
+
+extern "C" int tl_engine_swap_stats(const tl_engine *e, tl_swap_stats *out) {
+    TL_REQUIRE(e && out, "engine_swap_stats: null argument");
+    *out = tl_swap_stats{e->swap_arena.capacity(), e->swap_arena.in_use, e->swap_parks, e->swap_unparks, e->swap_pages_out, e->swap_pages_in,
+                         e->swap_host ? e->swap_record_bytes : 0};
+    return TL_OK;
 }
 
 // Pending token ids of slots [0, count) after synchronising the stream (one copy per decode step instead of one
@@ -2605,7 +2841,7 @@ static int prefill_first_token(tl_engine *e, int slot, const uint16_t *logits, c
 // land in e->verify_ids, nothing is recorded; speculative verification), 3 = every row scored (tl_engine_score: the log-probability
 // of e->score_ids[i] and the greedy id of every row into e->score_lp / e->score_argmax, nothing recorded, e->logits untouched)
 static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, int logits_mode) {
-    TL_TRY(slot_check(e, slot, true));
+    TL_TRY(slot_check_unparked(e, slot));
     TL_REQUIRE(tokens && n > 0, "engine_prefill: need at least one token");
     TL_REQUIRE(n <= e->cfg.max_prefill_rows, "engine_prefill: chunk exceeds max_prefill_rows");
     const tl_engine_config &c = e->cfg;
@@ -2651,7 +2887,7 @@ static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const
     int total = 0;
     size_t extra_pages = 0;
     for (int i = 0; i < n_seqs; ++i) {
-        TL_TRY(slot_check(e, slots[i], true));
+        TL_TRY(slot_check_unparked(e, slots[i]));
         TL_REQUIRE(lens[i] > 0, "engine_prefill_packed: every sequence needs at least one token");
         for (int j = 0; j < i; ++j) TL_REQUIRE(slots[j] != slots[i], "engine_prefill_packed: a slot appears twice");
         const int need = (e->slot_ctx[slots[i]] + lens[i] + c.page_size - 1) / c.page_size;
@@ -2712,6 +2948,7 @@ extern "C" int tl_engine_score(tl_engine *e, int slot, const int32_t *tokens, in
     TL_REQUIRE(n >= 1 && n <= e->cfg.max_prefill_rows, "engine_score: between 1 and max_prefill_rows tokens per call");
     TL_REQUIRE(next_token < e->cfg.vocab_size, "engine_score: next_token out of range");
     TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_score: vocabulary larger than the routine's 524,288 tokens");
+    TL_TRY(slot_check_unparked(e, slot));
     if (!e->score_logits) {
         const size_t R = (size_t)e->cfg.max_prefill_rows, logit_bytes = align_up((size_t)SCORE_BLOCK_ROWS * e->cfg.vocab_size * 2, 256);
         if (hipMalloc((void **)&e->score_logits, logit_bytes + R * 12) != hipSuccess) return fail(TL_ERR_HIP, "engine_score: hipMalloc(scratch) failed");
@@ -2732,7 +2969,7 @@ extern "C" int tl_engine_score(tl_engine *e, int slot, const int32_t *tokens, in
 extern "C" int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, int n, int32_t *out_ids) {
     TL_REQUIRE(e && out_ids, "engine_verify: null argument");
     TL_REQUIRE(n >= 1 && n <= 8, "engine_verify: between 1 and 8 tokens per call (the paged decode kernel's query rows)");
-    TL_TRY(slot_check(e, slot, true));
+    TL_TRY(slot_check_unparked(e, slot));
     TL_REQUIRE(!e->smp[slot].samples(), "engine_verify: the slot samples (verification is greedy; set temperature 0 first)");
     TL_REQUIRE(!e->pen[slot].processes(), "engine_verify: the slot processes its logits (verification takes the raw rows; make it neutral first)");
     TL_TRY(prefill_impl(e, slot, tokens, n, 2));
@@ -2794,7 +3031,7 @@ static int prepare_step(tl_engine *e, int batch, SplitPlan *sp, bool *on_queue =
 // the host mirrors after a step over slots [0, batch): every live slot holds one more token and has produced one more id
 static void step_done(tl_engine *e, int batch) {
     for (int b = 0; b < batch; ++b) {
-        if (!e->slot_live[b]) continue;
+        if (!e->slot_runs(b)) continue;
         e->slot_ctx[b] += 1;
         e->slot_produced[b] += 1;
         e->gr_pending[b] = 1;
@@ -2948,7 +3185,7 @@ extern "C" size_t tl_engine_step_bytes(const tl_engine *e, int batch) {
     const size_t kv_per_token = e->kv_format == TL_KV_FP8_E4M3 ? (size_t)2 * c.num_layers * c.num_kv_heads * (c.head_dim + 4)
                                                                : (size_t)2 * c.num_layers * c.num_kv_heads * c.head_dim * 2;
     for (int b = 0; b < batch && b < c.max_batch; ++b)
-        if (e->slot_live[b]) total += kv_per_token * (size_t)e->slot_ctx[b];
+        if (e->slot_runs(b)) total += kv_per_token * (size_t)e->slot_ctx[b];
     return total;
 }
 
@@ -3232,4 +3469,18 @@ extern "C" int tl_decode_attention_plan(int batch, int max_context, int num_head
 extern "C" int tl_kv_copy_rows(const tl_kv_pool_desc *pools_dev, int n_pools, int heads, int page_size, int from_page, int to_page,
                                int rows, void *stream) {
     return kv_copy_rows(pools_dev, n_pools, heads, page_size, from_page, to_page, rows, (hipStream_t)stream);
+}
+
+extern "C" size_t tl_kv_page_record_bytes(const tl_kv_pool_desc *pools_host, int n_pools, int heads, int page_size) {
+    return kv_page_record_bytes(pools_host, n_pools, heads, page_size);
+}
+extern "C" int tl_kv_gather_pages(const tl_kv_pool_desc *pools_dev, const size_t *record_offsets_dev, int n_pools, int heads, int page_size,
+                                  const int32_t *page_ids_dev, int n_pages, int tail_rows, void *staging_dev, size_t record_bytes, void *stream) {
+    return kv_swap_pages<true>(pools_dev, record_offsets_dev, n_pools, heads, page_size, page_ids_dev, n_pages, tail_rows, staging_dev, record_bytes,
+                               (hipStream_t)stream);
+}
+extern "C" int tl_kv_scatter_pages(const tl_kv_pool_desc *pools_dev, const size_t *record_offsets_dev, int n_pools, int heads, int page_size,
+                                   const int32_t *page_ids_dev, int n_pages, int tail_rows, const void *staging_dev, size_t record_bytes, void *stream) {
+    return kv_swap_pages<false>(pools_dev, record_offsets_dev, n_pools, heads, page_size, page_ids_dev, n_pages, tail_rows, (void *)staging_dev,
+                                record_bytes, (hipStream_t)stream);
 }

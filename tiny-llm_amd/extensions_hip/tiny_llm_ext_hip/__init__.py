@@ -153,6 +153,12 @@ class TlKvPoolDesc(ctypes.Structure):
     _fields_ = [("base_dev", _c_void_p), ("row_bytes", _c_size_t)]
 
 
+class TlSwapStats(ctypes.Structure):
+    """tl_swap_stats (include/tinyllm_engine.h): the swap space's records and the park / unpark counters."""
+    _fields_ = [("host_pages", _c_int), ("host_pages_in_use", _c_int), ("parks", ctypes.c_long), ("unparks", ctypes.c_long),
+                ("pages_out", ctypes.c_long), ("pages_in", ctypes.c_long), ("record_bytes", _c_size_t)]
+
+
 class TlAttentionInfo(ctypes.Structure):
     _fields_ = [("n_splits", _c_int), ("tokens_per_split", _c_int), ("heads_per_workgroup", _c_int),
                 ("launches", _c_int)]
@@ -206,6 +212,15 @@ _SIGNATURES.update({
     "tl_engine_prefix_clear": (_c_int, [_c_void_p]),
     "tl_engine_prefix_stats": (_c_int, [_c_void_p, _P(TlPrefixStats)]),
     "tl_kv_copy_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p]),
+    "tl_engine_swap_space": (_c_int, [_c_void_p, _c_int]),
+    "tl_engine_park": (_c_int, [_c_void_p, _c_int]),
+    "tl_engine_unpark": (_c_int, [_c_void_p, _c_int]),
+    "tl_engine_slot_parked": (_c_int, [_c_void_p, _c_int]),
+    "tl_engine_step_pages": (_c_int, [_c_void_p, _c_int, _P(_c_int), _P(_c_int)]),
+    "tl_engine_swap_stats": (_c_int, [_c_void_p, _P(TlSwapStats)]),
+    "tl_kv_page_record_bytes": (_c_size_t, [_c_void_p, _c_int, _c_int, _c_int]),
+    "tl_kv_gather_pages": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_size_t, _c_void_p]),
+    "tl_kv_scatter_pages": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_size_t, _c_void_p]),
     "tl_engine_prefill": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _c_int]),
     "tl_engine_prefill_packed": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int), _P(ctypes.c_int32), _P(ctypes.c_int), _P(ctypes.c_int)]),
     "tl_engine_verify": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _P(ctypes.c_int32)]),

@@ -62,8 +62,11 @@ class DecodeEngine:
 
     def __init__(self, mlx_model: Any, *, page_size: int = 128, num_pages: int = 512, max_batch: int = 1,
                  max_pages_per_seq: int | None = None, max_prefill_rows: int = 2048, options: dict | None = None,
-                 kv_format: str = "bf16", prefix_cache: bool | int = False):
-        """``prefix_cache``: keep the K / V of full pages after their request is released and hand them to later requests that start
+                 kv_format: str = "bf16", prefix_cache: bool | int = False, swap_pages: int = 0):
+        """``swap_pages``: room for that many KV pages in pinned host memory (tl_engine_swap_space): ``park`` moves a sequence's K / V
+        there and frees its pages, ``unpark`` brings it back, and the serving loops preempt under page pressure instead of failing
+        (tiny_llm_hip.preempt).  0 (the default): nothing is allocated and the loops are the programs they were.
+        ``prefix_cache``: keep the K / V of full pages after their request is released and hand them to later requests that start
         with the same tokens (tl_engine_prefix_cache; prefix_attach / prefix_extend); an int (> 0) also caps the retained pages.  Off
         by default: the engine then is the program it was.
         ``kv_format``: "bf16" (the reference's cache) or "fp8" -- K / V pages as OCP FP8 E4M3 codes with one power-of-two scale per
@@ -141,6 +144,11 @@ class DecodeEngine:
         self.prefix_cache_enabled = bool(prefix_cache)
         if self.prefix_cache_enabled:
             _ext.check(_lib.tl_engine_prefix_cache(self._h, 1, cap))
+        if isinstance(swap_pages, bool) or not isinstance(swap_pages, int) or swap_pages < 0:
+            raise ValueError(f"swap_pages must be an int >= 0 (host records of one KV page each), got {swap_pages!r}")
+        self.swap_enabled = swap_pages > 0
+        if self.swap_enabled:
+            _ext.check(_lib.tl_engine_swap_space(self._h, swap_pages))
 
     def _attach_moe(self, layer: int, mlp: Any, args: Any) -> None:
         """Hand the router and the stacked experts of one sparse layer to the engine (tl_engine_set_moe_layer)."""
@@ -231,6 +239,36 @@ class DecodeEngine:
     def prefix_stats(self) -> dict:
         s = _ext.TlPrefixStats()
         _ext.check(_lib.tl_engine_prefix_stats(self._h, ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in s._fields_}
+
+    # -- KV swap (tl_engine_swap_space / _park / _unpark; include/tinyllm_engine.h "KV swap") ----------------------
+    def set_swap_space(self, host_pages: int) -> None:
+        """Allocate (or, with 0, free) the host arena of ``host_pages`` page records; an error while a slot is parked."""
+        _ext.check(_lib.tl_engine_swap_space(self._h, int(host_pages)))
+        self.swap_enabled = int(host_pages) > 0
+
+    def park(self, slot: int) -> None:
+        """Move the live slot's K / V to host memory and let go of its pages (tl_engine_park); everything else of the slot -- pending
+        token, sampling, penalties, grammar state, log-probability records, produced ids -- stays.  Does not synchronise."""
+        _ext.check(_lib.tl_engine_park(self._h, slot))
+
+    def unpark(self, slot: int) -> None:
+        """Bring a parked slot's K / V back into fresh pages (tl_engine_unpark); an error, with the slot still parked, when the pool
+        cannot give ceil(context / page_size) pages."""
+        _ext.check(_lib.tl_engine_unpark(self._h, slot))
+
+    def is_parked(self, slot: int) -> bool:
+        return _lib.tl_engine_slot_parked(self._h, slot) == 1
+
+    def step_pages(self, batch: int | None = None) -> tuple[int, int]:
+        """(pages the next decode step over slots [0, batch) would take, free + evictable pages): host only."""
+        need, obtainable = ctypes.c_int(), ctypes.c_int()
+        _ext.check(_lib.tl_engine_step_pages(self._h, batch or self.max_batch, ctypes.byref(need), ctypes.byref(obtainable)))
+        return need.value, obtainable.value
+
+    def swap_stats(self) -> dict:
+        s = _ext.TlSwapStats()
+        _ext.check(_lib.tl_engine_swap_stats(self._h, ctypes.byref(s)))
         return {name: getattr(s, name) for name, _ in s._fields_}
 
     def read_pending(self, count: int | None = None) -> list[int]:
@@ -700,7 +738,12 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     [(prompt_idx, generated ids, records)].
     An engine built with ``prefix_cache`` has every request attach the cached prefix of its prompt (prefix_attach: after its settings,
     before its first chunk, which then starts at the matched offset) and declare its fed answer tokens at retirement (prefix_extend
-    before release), so a follow-up turn finds prompt and answer cached.  Results keep their order and content rules."""
+    before release), so a follow-up turn finds prompt and answer cached.  Results keep their order and content rules.
+    An engine built with ``swap_pages`` preempts under page pressure instead of failing with "KV page pool exhausted"
+    (tiny_llm_hip.preempt): before a decode step the staging request is released and re-queued, or the running request admitted last
+    is parked; parked requests resume oldest first, and nothing new is admitted while one is parked.  A request's ids do not depend on
+    being preempted beyond the usual row-bucket band (a step's arithmetic follows its row count)."""
+    from .preempt import Preemption
     if batch_size <= 0 or prefill_step <= 0:
         raise ValueError("batch_size and prefill_step must be positive")
     if engine.max_batch < batch_size + 1:
@@ -720,6 +763,7 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
             engine.prefix_extend(slot, req["out"][:-1])
         engine.release(slot)
 
+    pre = Preemption(engine)
     top_n = logprobs_arg(logprobs)
     staging = batch_size
     queue = list(range(len(prompts)))
@@ -729,7 +773,7 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     live_slots: set[int] = set()
     try:
         while queue or pending is not None or any(s is not None for s in slots):
-            if queue and pending is None:
+            if queue and pending is None and pre.may_admit(slots):
                 idx = queue.pop(0)
                 engine.begin(staging)
                 live_slots.add(staging)
@@ -751,7 +795,7 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                     pending["offset"] = engine.prefix_attach(staging, pending["tokens"])
             if pending is not None:
                 total = len(pending["tokens"])
-                if pending["offset"] < total:
+                if pending["offset"] < total and pre.may_prefill(staging, min(prefill_step, total - pending["offset"]), slots):
                     chunk = pending["tokens"][pending["offset"]:pending["offset"] + prefill_step]
                     last = pending["offset"] + len(chunk) >= total
                     engine.prefill(staging, chunk, chunk=len(chunk), want_logits=last)
@@ -774,8 +818,19 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                             live_slots.discard(staging)
                             live_slots.add(free)
                             slots[free] = pending
+                            pre.admitted(pending)
                             pending = None
-            if any(s is not None for s in slots):
+            if pre.active and any(s is not None for s in slots):
+                def requeue(slot, req):  # the staging request gives way: released, back at the front of the queue
+                    nonlocal pending
+                    engine.release(slot)
+                    live_slots.discard(slot)
+                    queue.insert(0, req["idx"])
+                    pending = None
+
+                pre.before_step(slots, lambda: batch_size,
+                                [(staging, pending)] if pending is not None else [], requeue)
+            if any(s is not None and not pre.parked(s) for s in slots):
                 # slots fill lowest-first, so rows above the highest occupied one are idle: decode only a bucket that
                 # covers the occupied prefix (the engine keeps one captured graph per row count; buckets bound their number)
                 def bucket(n):
@@ -805,9 +860,9 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                 tokens = engine.read_pending(rows)
                 records = engine.read_pending_logprobs(rows) if top_n >= 0 else None
                 if on_step is not None:
-                    on_step(sum(s is not None for s in slots))
+                    on_step(sum(s is not None and not pre.parked(s) for s in slots))
                 for i, req in enumerate(slots):
-                    if req is None:
+                    if req is None or pre.parked(req):
                         continue
                     req["out"].append(tokens[i])
                     if records is not None:
