@@ -1,9 +1,13 @@
 """CPU tier: KV swap without a device (include/tinyllm_engine.h "KV swap").
 
-* tests/kv_swap_model_check.cpp, a stand-alone program over csrc/kv_swap_model.h and csrc/prefix_cache.h: 20,000 seeded random
-  begin / append / fork / park / unpark / move / release / evict operations, the prefix cache on for the second half; after every
-  operation the page identity, "a page a slot references is never free", "host records in use == sum over parked slots", and every
-  unparked slot reading its own tokens' fingerprints back.  Built with AddressSanitizer and UBSan and run as its own process.
+* tests/kv_swap_model_check.cpp, a stand-alone program that drives csrc/slot_table.h -- the slot protocol the engine itself runs --
+  through 20,000 seeded random begin / prefill / decode step / rewind / attach / fork / park / unpark / move / release / evict
+  operations on slots in every state, the prefix cache on for the second half.  Its model of the device (block table, page and record
+  contents) learns of the table's decisions only through the edits a call reports (tests/slot_model_check.h).  After every operation:
+  the page identity, "a page a slot references is never free", "host records in use == sum over parked slots", every take and
+  eviction the brute-force victim, every unparked slot reading its own tokens' fingerprints back, and a refused call -- a decode step
+  over several slots that the pool cannot serve among them -- changing nothing.  Built with AddressSanitizer and UBSan and run as its
+  own process.
 * the new struct's ctypes mirror has the C compiler's layout; the new symbols are exported and bound; the entry points refuse a null
   engine and bad host arguments with TL_ERR_INVALID before anything is launched."""
 
@@ -32,8 +36,10 @@ def test_random_operations_keep_the_page_and_record_invariants(tmp_path):
         line = done.stdout.strip()
         assert line.startswith("ok ops=20000 "), line
         counts = {k: int(v) for k, v in re.findall(r"(\w+)=(\d+)\b", line)}
-        # the run exercises what it claims to: every kind of operation, both refusals, the cache's registrations and evictions
-        for key in ("begins", "forks", "parks", "park_refusals", "unparks", "unpark_refusals", "moves", "releases", "evicted", "registered"):
+        # the run exercises what it claims to: every kind of operation, the refusals for want of pages or records, the cache's
+        # registrations and evictions
+        for key in ("begins", "forks", "parks", "park_refusals", "unparks", "unpark_refusals", "moves", "releases", "evicted", "registered",
+                    "rewinds", "rewind_refusals", "attaches", "fork_refusals", "step_refusals"):
             assert counts[key] >= 100, (key, line)
         assert counts["appends"] >= 5000, line
         lines.append(line)

@@ -1,9 +1,11 @@
-"""CPU tier: the prefix cache's index and page bookkeeping (csrc/prefix_cache.h) against a brute-force model.
+"""CPU tier: the prefix cache's index (csrc/prefix_cache.h) under the engine's slot protocol (csrc/slot_table.h) against a brute-force model.
 
-tests/prefix_cache_model_check.cpp is a stand-alone program over the header: 20,000 seeded random operations of the engine's slot
-protocol (requests that attach and publish, releases, decode tokens declared later, long prefills under pool pressure, rewinds, forks,
-clears, cap changes, the cache switched off and on) on 24 pages of 4 tokens over a 3-token alphabet, every answer compared with a scan
-of every indexed sequence and every invariant of include/tinyllm_engine.h "Prefix cache" checked after every operation.  It is built
+tests/prefix_cache_model_check.cpp is a stand-alone program that drives SlotTable -- the code the engine itself runs -- through 20,000
+seeded random operations (requests that attach and publish, releases, decode steps whose tokens are declared later, long prefills under
+pool pressure, rewinds, forks, clears, cap changes, the cache switched off and on) on 24 pages of 4 tokens over a 3-token alphabet.  Its
+model of the device learns of the table's decisions only through the edits a call reports (tests/slot_model_check.h); every answer is
+compared with a scan of every indexed sequence and every invariant of include/tinyllm_engine.h "Prefix cache" checked after every
+operation.  It is built
 with AddressSanitizer and UBSan and run as its own process.  A second build forces the hash to a constant: the same answers prove that
 token equality, not the hash, decides a match."""
 

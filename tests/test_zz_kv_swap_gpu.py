@@ -1,4 +1,4 @@
-"""GPU tier: KV swap in the decode engine (include/tinyllm_engine.h "KV swap"; csrc/kv_swap.h, csrc/kv_swap_model.h,
+"""GPU tier: KV swap in the decode engine (include/tinyllm_engine.h "KV swap"; csrc/kv_swap.h, csrc/slot_table.h,
 tiny_llm_hip/preempt.py).
 
 A parked and resumed sequence reads back the bytes it wrote, so it must equal -- torch.equal on bf16 logits rows, == on ids -- an

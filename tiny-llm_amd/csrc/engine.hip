@@ -1,5 +1,5 @@
 // Decode engine: host side of include/tinyllm_engine.h.
-//   * page allocator + slot table (host mirrors of block_table / context_lens), transactional reserve
+//   * page allocator + slot table (slot_table.h: the host mirror of block_table / context_lens), transactional reserve
 //     (reference semantics: TinyKvPagedPool / TinyKvPagedCache, src/tiny_llm_ref/paged_kv_cache.py:21-443)
 //   * one fused decode step = 5 launches per layer (+ merge when the context is split) + 2 at the end,
 //     captured into a hipGraph per (batch, n_splits) and replayed
@@ -19,7 +19,7 @@
 #include "prefix_cache.h"
 #include "kv_copy.h"
 #include "kv_swap.h"
-#include "kv_swap_model.h"
+#include "slot_table.h"
 
 namespace tl {
 
@@ -162,31 +162,22 @@ struct tl_engine {
     int rows_cap = 0;
     int ring_cap = 4096;
 
-    // host mirrors
-    std::vector<std::vector<int>> slot_pages;
-    std::vector<int> slot_ctx;
-    std::vector<char> slot_live;
-    std::vector<int> slot_produced;
-    std::vector<char> page_was_used;
-    // the free list, the sequences holding each page (prefix sharing after tl_engine_fork) and, once tl_engine_prefix_cache enables it,
-    // the index of full pages by their tokens (prefix_cache.h); per slot the tokens the engine knows and the entries of its pages
-    PagePool pool;
-    std::vector<SlotRecord> prefix_rec;
+    // the host mirror of block_table / context_lens / live: the page pool, the host arena's records and what each slot holds of them
+    // (slot_table.h).  Its calls report edits; apply_edits puts them on the stream.  `step_edits`: the decode step's list, reused
+    SlotTable table;
+    SlotEdits step_edits;
     tl_kv_pool_desc *kv_pools_dev = nullptr;  // [kv_pools_n] every K / V (and scale) pool, for the tail copy of a hit (kv_copy.h)
     int kv_pools_n = 0;
     std::vector<tl_kv_pool_desc> kv_pools_host;  // the same table on the host (record offsets of kv_swap.h)
-    // KV swap (tl_engine_swap_space / _park / _unpark; kv_swap.h, kv_swap_model.h): nothing is allocated before the first swap_space.  A
-    // parked slot stays live on the host (slot_live, slot_ctx and every per-slot setting keep their values) and is a slot without a
+    // KV swap (tl_engine_swap_space / _park / _unpark; kv_swap.h, slot_table.h): nothing is allocated before the first swap_space.  A
+    // parked slot stays live on the host (the table's slot and every per-slot setting keep their values) and is a slot without a
     // sequence on the device (live 0, context 0, block-table row -1): slot_runs() is what a decode step asks
-    std::vector<char> slot_parked;
-    std::vector<std::vector<int>> slot_records;  // a parked slot's records in the host arena, one per page
-    SwapArena swap_arena;
     char *swap_host = nullptr, *swap_staging = nullptr;  // pinned arena [records][record_bytes]; device staging [swap_staging_pages][record_bytes]
     size_t *swap_offsets_dev = nullptr;                  // [kv_pools_n] where each pool's bytes start inside a record
     size_t swap_record_bytes = 0;
     int swap_staging_pages = 0;
     long swap_parks = 0, swap_unparks = 0, swap_pages_out = 0, swap_pages_in = 0;
-    bool slot_runs(int slot) const { return slot_live[slot] && !slot_parked[slot]; }
+    bool slot_runs(int slot) const { return table.runs(slot); }
     tl_engine_stats stats{};
     // per-slot sampling (tl_engine_set_sampling, sample.h): host mirror + device arrays [max_batch] each, written on the stream between
     // steps by poke; temperature 0 = greedy (the default, and what begin / release restore)
@@ -204,7 +195,7 @@ struct tl_engine {
     uint64_t *smp_seed = nullptr;
     // per-slot log-probability records (tl_engine_set_logprobs, logprob.h): allocated on the first set_logprobs -- top-N per slot
     // (-1: off), the record ring [max_batch, ring_cap] and the pending record per slot; the host mirror of top-N and, per slot, the
-    // value of slot_produced when its records began (tokens since then have records)
+    // value of the slot's `produced` when its records began (tokens since then have records)
     char *lp_mem = nullptr;
     int32_t *lp_topn = nullptr;
     uint32_t *lp_ring = nullptr, *lp_pending = nullptr;
@@ -638,7 +629,7 @@ static int lp_write(tl_engine *e, int slot, int top_n) {
     }
     std::vector<std::pair<int32_t *, int32_t>> pk;
     pk.emplace_back(e->lp_topn + slot, top_n);
-    if (e->lp_n[slot] < 0) e->lp_from[slot] = e->slot_produced[slot];  // records begin with the next produced token
+    if (e->lp_n[slot] < 0) e->lp_from[slot] = e->table.slots[slot].produced;  // records begin with the next produced token
     e->lp_n[slot] = top_n;
     return poke(e, pk);
 }
@@ -648,7 +639,7 @@ static int lp_carry(tl_engine *e, int src, int dst, bool move) {
     if (e->lp_n.empty()) return TL_OK;
     const int n = e->lp_n[src];
     TL_TRY(lp_write(e, dst, n));
-    e->lp_from[dst] = 0;  // slot_produced[dst] restarts at 0 with the sequence
+    e->lp_from[dst] = 0;  // dst's `produced` restarts at 0 with the sequence
     TL_HIP(hipMemcpyAsync(e->lp_pending + (size_t)dst * LP_RECORD_WORDS, e->lp_pending + (size_t)src * LP_RECORD_WORDS, LP_RECORD_WORDS * 4,
                           hipMemcpyDeviceToDevice, e->stream));
     return move ? lp_write(e, src, -1) : TL_OK;
@@ -794,7 +785,7 @@ static int pen_write(tl_engine *e, int slot, const tl_engine::PenaltyParams &v) 
         TL_HIP(hipMemcpyAsync(e->pen_bias_values + (size_t)slot * LPR_MAX_BIAS, cur.bias_values.data(), cur.bias_values.size() * 4, hipMemcpyHostToDevice, e->stream));
     }
     if (!pk.empty()) TL_TRY(poke(e, pk));
-    return e->slot_parked[slot] ? pen_device_switch(e, slot, false) : TL_OK;  // a parked slot's row of a step stays a copy (below)
+    return e->table.slots[slot].parked ? pen_device_switch(e, slot, false) : TL_OK;  // a parked slot's row of a step stays a copy (below)
 }
 static int pen_reset(tl_engine *e, int slot) { return e->pen[slot].processes() ? pen_write(e, slot, tl_engine::PenaltyParams{}) : TL_OK; }
 
@@ -1230,32 +1221,12 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, ProfCtx *pc = nul
     return TL_OK;
 }
 
-// ---- page ownership: a page is shared by every sequence forked from a common prefix and returns to the free list when
-// the last holder lets go of it
-// the pool's counters as the statistics report them (pages_in_use + pages_free + retained pages == num_pages)
-static void page_stats(tl_engine *e) {
-    e->stats.pages_in_use = e->pool.in_use();
-    e->stats.pages_free = (int)e->pool.free_pages.size();
-    e->stats.peak_pages_in_use = std::max(e->stats.peak_pages_in_use, e->stats.pages_in_use);
-}
-// the one allocation path (prefix_cache.h): the free list first, then the least recently used retained page.  The caller has checked
-// e->pool.can_take
-static int take_page(tl_engine *e) {
-    const int id = e->pool.take();
-    e->stats.page_allocations++;
-    if (e->page_was_used[id]) e->stats.reused_page_allocations++;
-    e->page_was_used[id] = 1;
-    page_stats(e);
-    return id;
-}
-static void drop_page(tl_engine *e, int id) {
-    e->pool.drop(id);
-    page_stats(e);
-}
-// the slot's pages that became full inside its known tokens enter the index (no-op while the cache is off)
-static void prefix_publish(tl_engine *e, int slot) {
-    if (e->pool.enabled) e->pool.register_slot(e->prefix_rec[slot], e->slot_pages[slot]);
-}
+// ---- the slot table (slot_table.h) on the device ---------------------------------------------------------------------------
+using Pokes = std::vector<std::pair<int32_t *, int32_t>>;
+
+// a refusal of the table as the engine reports it
+static int table_rc(const char *why) { return why ? fail(TL_ERR_INVALID, why) : TL_OK; }
+
 // K and V rows of one page, every layer (device to device, stream ordered)
 static int copy_page(tl_engine *e, int from, int to) {
     const tl_engine_config &c = e->cfg;
@@ -1276,58 +1247,61 @@ static int copy_page(tl_engine *e, int from, int to) {
     return TL_OK;
 }
 
-static int reserve_locked(tl_engine *e, int slot, int total_tokens,
-                          std::vector<std::pair<int32_t *, int32_t>> &pokes) {
-    const tl_engine_config &c = e->cfg;
-    const int need = (total_tokens + c.page_size - 1) / c.page_size;
-    auto &pages = e->slot_pages[slot];
-    const int have = (int)pages.size();
-    if (need <= have) return TL_OK;
-    if (need > c.max_pages_per_seq)
-        return fail(TL_ERR_INVALID, "engine: sequence exceeds max_pages_per_seq * page_size tokens");
-    if (!e->pool.can_take((size_t)(need - have)))
-        return fail(TL_ERR_INVALID, "engine: KV page pool exhausted");
-    for (int j = have; j < need; ++j) {
-        const int id = take_page(e);
-        pages.push_back(id);
-        pokes.emplace_back(e->block_table + (size_t)slot * c.max_pages_per_seq + j, id);
-    }
-    return TL_OK;
+// the pool's counters as the statistics report them (pages_in_use + pages_free + retained pages == num_pages)
+static void page_stats(const SlotTable &t, tl_engine_stats *out) {
+    out->pages_in_use = t.pages_in_use();
+    out->pages_free = t.pages_free();
+    out->peak_pages_in_use = t.peak_pages_in_use;
+    out->page_allocations = t.page_allocations;
+    out->reused_page_allocations = t.reused_page_allocations;
 }
 
-// Pages for ONE more token in every live slot of [0, batch): all or nothing.  The totals are checked before anything is
-// mutated, so a failing step leaves the host mirrors and the device block table exactly as they were (a half-applied
-// reservation would leave a slot that owns a page on the host and -1 on the device: silently dropped K/V).
-static int reserve_step_locked(tl_engine *e, int batch, std::vector<std::pair<int32_t *, int32_t>> &pokes, int *max_ctx) {
+// The table's edits on the stream: the page copies are enqueued first (a fresh page is filled before the row entry that publishes
+// it), then the block-table writes join `pk`, which the caller pokes together with the words of its own (context, live, ...).
+static int apply_edits(tl_engine *e, const SlotEdits &ed, Pokes &pk) {
     const tl_engine_config &c = e->cfg;
-    size_t extra = 0;
-    for (int b = 0; b < batch; ++b) {
-        if (!e->slot_runs(b)) continue;
-        const int need = (e->slot_ctx[b] + 1 + c.page_size - 1) / c.page_size;
-        if (need > c.max_pages_per_seq)
-            return fail(TL_ERR_INVALID, "engine: sequence exceeds max_pages_per_seq * page_size tokens");
-        if (need > (int)e->slot_pages[b].size()) extra += (size_t)need - e->slot_pages[b].size();
+    for (const SlotEdits::Copy &cp : ed.copies) {
+        if (cp.rows == c.page_size) TL_TRY(copy_page(e, cp.from, cp.to));
+        else TL_TRY(kv_copy_rows(e->kv_pools_dev, e->kv_pools_n, c.num_kv_heads, c.page_size, cp.from, cp.to, cp.rows, e->stream));
     }
-    if (!e->pool.can_take(extra)) return fail(TL_ERR_INVALID, "engine: KV page pool exhausted");
-    for (int b = 0; b < batch; ++b) {
-        if (!e->slot_runs(b)) continue;
-        TL_TRY(reserve_locked(e, b, e->slot_ctx[b] + 1, pokes));  // cannot fail after the checks above
-        *max_ctx = std::max(*max_ctx, e->slot_ctx[b] + 1);
-    }
+    for (const SlotEdits::Row &r : ed.rows) pk.emplace_back(e->block_table + (size_t)r.slot * c.max_pages_per_seq + r.index, r.page);
     return TL_OK;
 }
 
 static int slot_check(const tl_engine *e, int slot, bool must_be_live) {
     if (!e) return fail(TL_ERR_INVALID, "engine: null engine");
-    if (slot < 0 || slot >= e->cfg.max_batch) return fail(TL_ERR_INVALID, "engine: slot out of range");
-    if (must_be_live && !e->slot_live[slot]) return fail(TL_ERR_INVALID, "engine: slot holds no sequence");
-    return TL_OK;
+    return table_rc(e->table.check(slot, must_be_live));
 }
 // ... for the calls that read or write the slot's K/V: a parked slot has none on the device (tl_engine_unpark first)
 static int slot_check_unparked(const tl_engine *e, int slot) {
-    TL_TRY(slot_check(e, slot, true));
-    if (e->slot_parked[slot]) return fail(TL_ERR_INVALID, "engine: the slot is parked (its KV lies in host memory; tl_engine_unpark first)");
-    return TL_OK;
+    if (!e) return fail(TL_ERR_INVALID, "engine: null engine");
+    return table_rc(e->table.check_unparked(slot));
+}
+
+// ---- the per-slot settings across the lifecycle: sampling, log-probability records, penalties / bias / grammar, the pending token ----
+// begin / release: everything back to the defaults (each skipped while it is the default already)
+static int settings_reset(tl_engine *e, int slot) {
+    e->gr_pending[slot] = 0;
+    TL_TRY(lp_write(e, slot, -1));
+    TL_TRY(pen_reset(e, slot));
+    return smp_reset(e, slot);
+}
+// fork / move (move = true): dst takes what src has, and a move leaves src at the defaults
+static int settings_carry(tl_engine *e, int src, int dst, bool move) {
+    e->gr_pending[dst] = e->gr_pending[src];
+    if (move) e->gr_pending[src] = 0;
+    // the pending input token travels on the device
+    TL_HIP(hipMemcpyAsync(e->tokens + dst, e->tokens + src, sizeof(int32_t), hipMemcpyDeviceToDevice, e->stream));
+    // the sampling parameters (seed included: give a fork's child its own seed, or both draw the same tokens)
+    if (!smp_is_default(e->smp[src]) || !smp_is_default(e->smp[dst])) {
+        const tl_engine::SampleParams v = e->smp[src];
+        TL_TRY(smp_write(e, dst, v));
+        if (move) TL_TRY(smp_write(e, src, tl_engine::SampleParams{}));
+    }
+    // ... the log-probability setting with the pending token's record (the record ring restarts, like the token ring)
+    TL_TRY(lp_carry(e, src, dst, move));
+    // ... and the penalties, the bias list, the history and the grammar's state
+    return pen_carry(e, src, dst, move);
 }
 
 }  // namespace tl
@@ -1678,18 +1652,10 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     }
 
     e->moe.assign(c.num_layers, tl_moe_weights{});
-    e->slot_pages.assign(c.max_batch, {});
-    e->slot_ctx.assign(c.max_batch, 0);
-    e->slot_live.assign(c.max_batch, 0);
-    e->slot_parked.assign(c.max_batch, 0);
-    e->slot_records.assign(c.max_batch, {});
-    e->slot_produced.assign(c.max_batch, 0);
+    e->table.init(c.max_batch, c.num_pages, c.page_size, c.max_pages_per_seq);  // (the pool hands out 0, 1, 2, ...)
     e->smp.assign(c.max_batch, tl_engine::SampleParams{});
     e->pen.assign(c.max_batch, tl_engine::PenaltyParams{});
     e->gr_pending.assign(c.max_batch, 0);
-    e->pool.init(c.num_pages, c.page_size);  // (hands out 0, 1, 2, ...)
-    e->page_was_used.assign(c.num_pages, 0);
-    e->stats.pages_free = c.num_pages;
     e->stats.kv_bytes = e->kv_bytes;
     e->stats.workspace_bytes = e->arena_bytes + e->tiled_bytes + e->bf16w_bytes;
     *out = e;
@@ -1829,100 +1795,48 @@ extern "C" int tl_engine_synchronize(tl_engine *e) {
 }
 
 extern "C" int tl_engine_begin(tl_engine *e, int slot) {
-    TL_TRY(slot_check(e, slot, false));
-    TL_REQUIRE(!e->slot_live[slot], "engine_begin: slot already holds a sequence (release it first)");
-    e->slot_live[slot] = 1;
-    e->slot_ctx[slot] = 0;
-    e->slot_produced[slot] = 0;
-    e->gr_pending[slot] = 0;
-    if (e->pool.enabled) e->prefix_rec[slot].clear();
-    std::vector<std::pair<int32_t *, int32_t>> pk;
+    TL_REQUIRE(e, "engine: null engine");
+    TL_TRY(table_rc(e->table.begin(slot)));
+    Pokes pk;
     pk.emplace_back(e->live + slot, 1);
     pk.emplace_back(e->context_lens + slot, 0);
     pk.emplace_back(e->produced + slot, 0);
     pk.emplace_back(e->tokens + slot, 0);
     TL_TRY(poke(e, pk));
-    TL_TRY(lp_write(e, slot, -1));
-    TL_TRY(pen_reset(e, slot));
-    return smp_reset(e, slot);
+    return settings_reset(e, slot);
 }
 
 extern "C" int tl_engine_reserve(tl_engine *e, int slot, int total_tokens) {
     TL_TRY(slot_check_unparked(e, slot));
     TL_REQUIRE(total_tokens >= 0, "engine_reserve: total_tokens must be nonnegative");
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    TL_TRY(reserve_locked(e, slot, total_tokens, pk));
-    page_stats(e);
+    SlotEdits ed;
+    Pokes pk;
+    TL_TRY(table_rc(e->table.reserve(slot, total_tokens, ed)));
+    TL_TRY(apply_edits(e, ed, pk));
     return poke(e, pk);
 }
 
 extern "C" int tl_engine_release(tl_engine *e, int slot) {
-    TL_TRY(slot_check(e, slot, true));
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    auto &pages = e->slot_pages[slot];
-    for (size_t j = 0; j < pages.size(); ++j) {
-        drop_page(e, pages[j]);
-        pk.emplace_back(e->block_table + (size_t)slot * e->cfg.max_pages_per_seq + j, -1);
-    }
-    pages.clear();
-    if (e->slot_parked[slot]) {  // a parked slot holds no pages: its host records return to the arena (stream order protects their bytes)
-        e->swap_arena.give(e->slot_records[slot]);
-        e->slot_parked[slot] = 0;
-    }
-    if (e->pool.enabled) e->prefix_rec[slot].clear();
-    e->slot_live[slot] = 0;
-    e->slot_ctx[slot] = 0;
-    e->gr_pending[slot] = 0;
+    TL_REQUIRE(e, "engine: null engine");
+    SlotEdits ed;
+    Pokes pk;
+    TL_TRY(table_rc(e->table.release(slot, ed)));
+    TL_TRY(apply_edits(e, ed, pk));
     pk.emplace_back(e->live + slot, 0);
     pk.emplace_back(e->context_lens + slot, 0);
     pk.emplace_back(e->tokens + slot, 0);
-    page_stats(e);
     TL_TRY(poke(e, pk));
-    TL_TRY(lp_write(e, slot, -1));
-    TL_TRY(pen_reset(e, slot));
-    return smp_reset(e, slot);
+    return settings_reset(e, slot);
 }
 
 extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
     TL_TRY(slot_check_unparked(e, slot));
-    TL_REQUIRE(n >= 0 && n <= e->slot_ctx[slot], "engine_rewind: cannot rewind past the start of the sequence");
     TL_REQUIRE(!e->pen[slot].processes(), "engine_rewind: the slot processes its logits (its history would keep the dropped tokens; make it neutral first)");
-    const int ctx = e->slot_ctx[slot] - n;
-    const int keep = (ctx + e->cfg.page_size - 1) / e->cfg.page_size;
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    auto &pages = e->slot_pages[slot];
-    {
-        // the copy of a shared tail page needs one free page; pages this rewind itself returns count.  Checked before
-        // anything is mutated, so a failing rewind leaves host mirrors and device tables untouched.
-        // (the pages it returns are counted as they will stand: their holds are taken off while the pool is asked)
-        const bool cow = keep > 0 && ctx % e->cfg.page_size != 0 && keep <= (int)pages.size() &&
-                         (e->pool.refs[pages[keep - 1]] > 1 || e->pool.is_indexed(pages[keep - 1]));
-        if (cow) {
-            size_t will_free = 0;
-            for (int j = keep; j < (int)pages.size(); ++j) will_free += --e->pool.refs[pages[j]] == 0 && !e->pool.is_indexed(pages[j]) ? 1 : 0;
-            const bool ok = will_free >= 1 || e->pool.can_take(1);
-            for (int j = keep; j < (int)pages.size(); ++j) e->pool.refs[pages[j]]++;
-            TL_REQUIRE(ok, "engine_rewind: KV page pool exhausted (copy of a shared tail page)");
-        }
-    }
-    while ((int)pages.size() > keep) {
-        drop_page(e, pages.back());
-        pk.emplace_back(e->block_table + (size_t)slot * e->cfg.max_pages_per_seq + (pages.size() - 1), -1);
-        pages.pop_back();
-    }
-    // the next append lands in the tail page: if a fork shares it, give this sequence its own copy first
-    if (keep > 0 && ctx % e->cfg.page_size != 0 && (e->pool.refs[pages[keep - 1]] > 1 || e->pool.is_indexed(pages[keep - 1]))) {
-        const int old_id = pages[keep - 1];  // a free page exists: checked above
-        const int fresh = take_page(e);
-        TL_TRY(copy_page(e, old_id, fresh));
-        drop_page(e, old_id);
-        pages[keep - 1] = fresh;
-        pk.emplace_back(e->block_table + (size_t)slot * e->cfg.max_pages_per_seq + (keep - 1), fresh);
-    }
-    e->slot_ctx[slot] = ctx;
-    if (e->pool.enabled) e->prefix_rec[slot].rewind(ctx, e->cfg.page_size);
-    pk.emplace_back(e->context_lens + slot, ctx);
-    page_stats(e);
+    SlotEdits ed;
+    Pokes pk;
+    TL_TRY(table_rc(e->table.rewind(slot, n, ed)));
+    TL_TRY(apply_edits(e, ed, pk));  // the copy of a shared tail page before the row entry that publishes the fresh page
+    pk.emplace_back(e->context_lens + slot, e->table.slots[slot].ctx);
     return poke(e, pk);
 }
 
@@ -1930,48 +1844,16 @@ extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
 // dense caches, agent/branching.py:42-208; here on the page pool).  Full pages are shared by reference count -- they are
 // never written again -- and a partially filled tail page is copied, so both sequences can append independently.
 extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
-    TL_TRY(slot_check_unparked(e, src));
-    TL_TRY(slot_check(e, dst, false));
-    TL_REQUIRE(src != dst, "engine_fork: source and destination are the same slot");
-    TL_REQUIRE(!e->slot_live[dst], "engine_fork: destination slot already holds a sequence");
-    const tl_engine_config &c = e->cfg;
-    const int ctx = e->slot_ctx[src];
-    const int full = ctx / c.page_size;
-    const bool partial = ctx % c.page_size != 0;
-    TL_REQUIRE(!partial || e->pool.can_take(1), "engine_fork: KV page pool exhausted");
-    const auto &from = e->slot_pages[src];
-    auto &to = e->slot_pages[dst];
-    to.clear();
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    for (int j = 0; j < full; ++j) {
-        e->pool.share(from[j]);
-        to.push_back(from[j]);
-        pk.emplace_back(e->block_table + (size_t)dst * c.max_pages_per_seq + j, from[j]);
-    }
-    if (partial) {
-        const int fresh = take_page(e);
-        TL_TRY(copy_page(e, from[full], fresh));
-        to.push_back(fresh);
-        pk.emplace_back(e->block_table + (size_t)dst * c.max_pages_per_seq + full, fresh);
-    }
-    e->slot_live[dst] = 1;
-    e->slot_ctx[dst] = ctx;
-    e->slot_produced[dst] = 0;
-    e->gr_pending[dst] = e->gr_pending[src];
-    if (e->pool.enabled) e->prefix_rec[dst] = e->prefix_rec[src];
+    TL_REQUIRE(e, "engine: null engine");
+    SlotEdits ed;
+    Pokes pk;
+    TL_TRY(table_rc(e->table.fork(src, dst, ed)));
+    TL_TRY(apply_edits(e, ed, pk));
     pk.emplace_back(e->live + dst, 1);
-    pk.emplace_back(e->context_lens + dst, ctx);
+    pk.emplace_back(e->context_lens + dst, e->table.slots[dst].ctx);
     pk.emplace_back(e->produced + dst, 0);
     TL_TRY(poke(e, pk));
-    // the pending input token travels on the device
-    TL_HIP(hipMemcpyAsync(e->tokens + dst, e->tokens + src, sizeof(int32_t), hipMemcpyDeviceToDevice, e->stream));
-    page_stats(e);
-    // the sampling parameters are copied too (seed included: give the child its own seed, or both draw the same tokens)
-    if (!smp_is_default(e->smp[src]) || !smp_is_default(e->smp[dst])) TL_TRY(smp_write(e, dst, e->smp[src]));
-    // ... and the log-probability setting with the pending token's record
-    TL_TRY(lp_carry(e, src, dst, false));
-    // ... and the penalties, the bias list and the history
-    return pen_carry(e, src, dst, false);
+    return settings_carry(e, src, dst, false);
 }
 
 // the device table of every K / V (and scale) pool, built once by the first call that needs it (prefix cache, swap space): pool
@@ -2006,81 +1888,59 @@ extern "C" int tl_engine_prefix_cache(tl_engine *e, int enabled, int max_retaine
     TL_REQUIRE(e, "engine_prefix_cache: null engine");
     TL_REQUIRE(enabled == 0 || enabled == 1, "engine_prefix_cache: enabled is 0 or 1");
     TL_REQUIRE(max_retained_pages >= 0, "engine_prefix_cache: max_retained_pages must be nonnegative (0 = no cap)");
-    const tl_engine_config &c = e->cfg;
     if (!enabled) {
-        e->pool.disable();
-        e->prefix_rec.clear();
-        page_stats(e);
+        e->table.prefix_disable();
         return TL_OK;
     }
     TL_TRY(ensure_pool_table(e));
-    if (!e->pool.enabled) e->prefix_rec.assign(c.max_batch, SlotRecord{});
-    e->pool.enable(max_retained_pages);
-    page_stats(e);
+    e->table.prefix_enable(max_retained_pages);
     return TL_OK;
 }
 
 extern "C" int tl_engine_prefix_clear(tl_engine *e) {
     TL_REQUIRE(e, "engine_prefix_clear: null engine");
-    e->pool.clear();
-    page_stats(e);
+    e->table.pool.clear();
     return TL_OK;
 }
 
 extern "C" int tl_engine_prefix_stats(const tl_engine *e, tl_prefix_stats *out) {
     TL_REQUIRE(e && out, "engine_prefix_stats: null argument");
-    const PrefixCounters &k = e->pool.ctr;
+    const PagePool &pool = e->table.pool;
+    const PrefixCounters &k = pool.ctr;
     *out = tl_prefix_stats{k.lookups, k.hits, k.tokens_matched, k.tail_rows_copied, k.pages_registered, k.pages_evicted,
-                           e->pool.n_entries, e->pool.retained, e->pool.max_retained, e->pool.enabled ? 1 : 0};
+                           pool.n_entries, pool.retained, pool.max_retained, pool.enabled ? 1 : 0};
     return TL_OK;
 }
 
 extern "C" int tl_engine_prefix_extend(tl_engine *e, int slot, const int32_t *tokens, int n) {
     TL_TRY(slot_check_unparked(e, slot));
     TL_REQUIRE(tokens && n >= 1, "engine_prefix_extend: need at least one token");
-    if (!e->pool.enabled) return TL_OK;
-    auto &known = e->prefix_rec[slot].known;
-    TL_REQUIRE((long)known.size() + n <= e->slot_ctx[slot], "engine_prefix_extend: more tokens than the slot holds beyond its known ones");
+    if (!e->table.pool.enabled) return TL_OK;
     for (int i = 0; i < n; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < e->cfg.vocab_size, "engine_prefix_extend: token id out of range");
-    known.insert(known.end(), tokens, tokens + n);
-    prefix_publish(e, slot);
-    page_stats(e);
-    return TL_OK;
+    return table_rc(e->table.extend(slot, tokens, n));
 }
 
 extern "C" int tl_engine_prefix_attach(tl_engine *e, int slot, const int32_t *tokens, int n, int *matched) {
     TL_TRY(slot_check_unparked(e, slot));
     TL_REQUIRE(tokens && matched && n >= 1, "engine_prefix_attach: need at least one token and a place for the result");
-    TL_REQUIRE(e->slot_ctx[slot] == 0 && e->slot_pages[slot].empty(), "engine_prefix_attach: the slot already holds tokens or pages");
-    *matched = 0;
-    if (!e->pool.enabled) return TL_OK;
     const tl_engine_config &c = e->cfg;
-    auto &pages = e->slot_pages[slot];
-    const AttachResult a = e->pool.attach(e->prefix_rec[slot], pages, tokens, n, c.max_pages_per_seq);
-    if (a.tail_rows > 0) {
-        e->stats.page_allocations++;
-        if (e->page_was_used[a.tail_to]) e->stats.reused_page_allocations++;
-        e->page_was_used[a.tail_to] = 1;
-    }
-    page_stats(e);
-    if (a.matched == 0) return TL_OK;
-    if (a.tail_rows > 0)
-        TL_TRY(kv_copy_rows(e->kv_pools_dev, e->kv_pools_n, c.num_kv_heads, c.page_size, a.tail_from, a.tail_to, a.tail_rows, e->stream));
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    for (size_t j = 0; j < pages.size(); ++j) pk.emplace_back(e->block_table + (size_t)slot * c.max_pages_per_seq + j, pages[j]);
-    e->slot_ctx[slot] = a.matched;
-    pk.emplace_back(e->context_lens + slot, a.matched);
+    SlotEdits ed;
+    TL_TRY(table_rc(e->table.attach(slot, tokens, n, ed, matched)));
+    const int got = *matched;
+    if (got == 0) return TL_OK;
+    Pokes pk;
+    TL_TRY(apply_edits(e, ed, pk));  // the tail rows' copy before the row and the context
+    pk.emplace_back(e->context_lens + slot, got);
     TL_TRY(poke(e, pk));
     if (step_processes_slot(e, slot)) {  // the matched tokens are prompt tokens of the slot's history, as a prefill would have marked them
-        for (int at = 0; at < a.matched; at += c.max_prefill_rows) {
-            const int len = std::min(c.max_prefill_rows, a.matched - at);
+        for (int at = 0; at < got; at += c.max_prefill_rows) {
+            const int len = std::min(c.max_prefill_rows, got - at);
             TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens + at, (size_t)len * 4, hipMemcpyHostToDevice, e->stream));
             const LogitMarkArgs mk{e->prefill_tokens, len, c.vocab_size, (uint32_t *)e->pen_history, (long)slot * c.vocab_size};
             hipLaunchKernelGGL(logit_mark_prompt_kernel, dim3(ceil_div(len, 256)), dim3(256), 0, e->stream, mk);
             TL_CHECK_LAUNCH("engine prompt marking");
         }
     }
-    *matched = a.matched;
     return TL_OK;
 }
 
@@ -2088,58 +1948,24 @@ extern "C" int tl_engine_prefix_attach(tl_engine *e, int slot, const int32_t *to
 // cache and then adopts it into a batch slot (BatchingKvCache.add_request, kv_cache.py:226-238); here only the
 // block-table row, context length and pending token change hands — no K/V byte moves.
 extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
-    TL_TRY(slot_check(e, src, true));
-    TL_TRY(slot_check(e, dst, false));
-    TL_REQUIRE(src != dst, "engine_move: source and destination are the same slot");
-    TL_REQUIRE(!e->slot_live[dst], "engine_move: destination slot already holds a sequence");
-    const int W = e->cfg.max_pages_per_seq;
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    auto &pages = e->slot_pages[src];
-    for (size_t j = 0; j < pages.size(); ++j) {
-        pk.emplace_back(e->block_table + (size_t)dst * W + j, pages[j]);
-        pk.emplace_back(e->block_table + (size_t)src * W + j, -1);
-    }
-    // a parked sequence stays parked at dst: no sequence on the device, its host records move with it
-    const bool parked = e->slot_parked[src];
-    pk.emplace_back(e->context_lens + dst, parked ? 0 : e->slot_ctx[src]);
+    TL_REQUIRE(e, "engine: null engine");
+    SlotEdits ed;
+    Pokes pk;
+    TL_TRY(table_rc(e->table.move(src, dst, ed)));
+    TL_TRY(apply_edits(e, ed, pk));
+    // a parked sequence stays parked at dst: no sequence on the device, its host records have moved with it
+    const Slot &d = e->table.slots[dst];
+    pk.emplace_back(e->context_lens + dst, d.parked ? 0 : d.ctx);
     pk.emplace_back(e->context_lens + src, 0);
-    pk.emplace_back(e->live + dst, parked ? 0 : 1);
+    pk.emplace_back(e->live + dst, d.parked ? 0 : 1);
     pk.emplace_back(e->live + src, 0);
     pk.emplace_back(e->produced + dst, 0);
     TL_TRY(poke(e, pk));
-    e->slot_records[dst] = std::move(e->slot_records[src]);
-    e->slot_records[src].clear();
-    e->slot_parked[dst] = parked;
-    e->slot_parked[src] = 0;
-    TL_HIP(hipMemcpyAsync(e->tokens + dst, e->tokens + src, 4, hipMemcpyDeviceToDevice, e->stream));
-    e->slot_pages[dst] = std::move(e->slot_pages[src]);
-    e->slot_pages[src].clear();
-    e->slot_ctx[dst] = e->slot_ctx[src];
-    e->slot_ctx[src] = 0;
-    e->slot_live[dst] = 1;
-    e->slot_live[src] = 0;
-    e->slot_produced[dst] = 0;
-    e->slot_produced[src] = 0;
-    e->gr_pending[dst] = e->gr_pending[src];
-    e->gr_pending[src] = 0;
-    if (e->pool.enabled) {
-        e->prefix_rec[dst] = std::move(e->prefix_rec[src]);
-        e->prefix_rec[src].clear();
-    }
-    // the sampling parameters go with the sequence
-    if (!smp_is_default(e->smp[src]) || !smp_is_default(e->smp[dst])) {
-        const tl_engine::SampleParams v = e->smp[src];
-        TL_TRY(smp_write(e, dst, v));
-        TL_TRY(smp_write(e, src, tl_engine::SampleParams{}));
-    }
-    // ... and so do the log-probability setting and the pending token's record (the record ring restarts, like the token ring)
-    TL_TRY(lp_carry(e, src, dst, true));
-    // ... and the penalties, the bias list and the history
-    return pen_carry(e, src, dst, true);
+    return settings_carry(e, src, dst, true);
 }
 
 
-// ---- KV swap (include/tinyllm_engine.h "KV swap"; kernels kv_swap.h, host accounting kv_swap_model.h) ------------------------------------
+// ---- KV swap (include/tinyllm_engine.h "KV swap"; kernels kv_swap.h, host accounting slot_table.h) ------------------------------------
 static int swap_free(tl_engine *e) {
     if (!e->swap_host && !e->swap_staging) return TL_OK;
     TL_HIP(hipStreamSynchronize(e->stream));  // copies into / out of the arena may be in flight
@@ -2148,14 +1974,14 @@ static int swap_free(tl_engine *e) {
     e->stats.workspace_bytes -= (size_t)e->swap_staging_pages * e->swap_record_bytes;
     e->swap_host = e->swap_staging = nullptr;
     e->swap_staging_pages = 0;
-    e->swap_arena.init(0);
+    e->table.arena.init(0);
     return TL_OK;
 }
 
 extern "C" int tl_engine_swap_space(tl_engine *e, int host_pages) {
     TL_REQUIRE(e, "engine_swap_space: null engine");
     TL_REQUIRE(host_pages >= 0, "engine_swap_space: host_pages must be nonnegative (0 frees the swap space)");
-    for (char p : e->slot_parked) TL_REQUIRE(!p, "engine_swap_space: a slot is parked (unpark or release it first)");
+    for (const Slot &s : e->table.slots) TL_REQUIRE(!s.parked, "engine_swap_space: a slot is parked (unpark or release it first)");
     TL_TRY(swap_free(e));
     if (host_pages == 0) return TL_OK;
     const tl_engine_config &c = e->cfg;
@@ -2190,23 +2016,20 @@ extern "C" int tl_engine_swap_space(tl_engine *e, int host_pages) {
     }
     e->swap_record_bytes = rec;
     e->swap_staging_pages = staging_pages;
-    e->swap_arena.init(host_pages);
+    e->table.arena.init(host_pages);
     e->stats.workspace_bytes += (size_t)staging_pages * rec;
     return TL_OK;
 }
 
 extern "C" int tl_engine_park(tl_engine *e, int slot) {
-    TL_TRY(slot_check_unparked(e, slot));
+    TL_REQUIRE(e, "engine: null engine");
+    TL_TRY(table_rc(e->table.park_begin(slot)));
     const tl_engine_config &c = e->cfg;
-    const int ctx = e->slot_ctx[slot], n = swap_pages_of(ctx, c.page_size);
-    TL_REQUIRE(ctx >= 1, "engine_park: the slot holds no tokens");
-    TL_REQUIRE(e->swap_host, "engine_park: no swap space (tl_engine_swap_space)");
-    TL_REQUIRE(n <= e->swap_arena.available(), "engine_park: not enough free host records");
-    TL_REQUIRE(n <= (int)e->slot_pages[slot].size(), "engine_park: the slot holds fewer pages than its context needs");
+    const Slot &s = e->table.slots[slot];
+    const std::vector<int> &records = s.records;
+    const int ctx = s.ctx, n = (int)records.size();
     // the pages leave through the slot's block-table row, which holds their ids on the device already; everything below is enqueued
     // before the row is cleared and before anybody can take a freed page
-    std::vector<int> records;
-    e->swap_arena.take(n, records);
     const int32_t *row = e->block_table + (size_t)slot * c.max_pages_per_seq;
     const size_t rec = e->swap_record_bytes;
     int rc = TL_OK;
@@ -2223,19 +2046,15 @@ extern "C" int tl_engine_park(tl_engine *e, int slot) {
         }
     }
     if (rc != TL_OK) {  // nothing of the slot has changed: the records go back
-        e->swap_arena.give(records);
+        e->table.park_abort(slot);
         return rc;
     }
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    auto &pages = e->slot_pages[slot];
-    for (size_t j = 0; j < pages.size(); ++j) pk.emplace_back(e->block_table + (size_t)slot * c.max_pages_per_seq + j, -1);
-    e->swap_arena.give(records);  // (swap_park_host takes them again: one accounting routine for the engine and the model check)
-    if (!swap_park_host(e->pool, e->swap_arena, e->pool.enabled ? &e->prefix_rec[slot] : nullptr, pages, ctx, e->slot_records[slot]))
-        return fail(TL_ERR_INVALID, "engine_park: the slot's pages and records disagree");  // (checked above: cannot happen)
-    e->slot_parked[slot] = 1;
+    SlotEdits ed;
+    Pokes pk;
+    e->table.park_commit(slot, ed);
+    TL_TRY(apply_edits(e, ed, pk));
     pk.emplace_back(e->live + slot, 0);
     pk.emplace_back(e->context_lens + slot, 0);
-    page_stats(e);
     e->swap_parks++;
     e->swap_pages_out += n;
     TL_TRY(poke(e, pk));
@@ -2243,26 +2062,16 @@ extern "C" int tl_engine_park(tl_engine *e, int slot) {
 }
 
 extern "C" int tl_engine_unpark(tl_engine *e, int slot) {
-    TL_TRY(slot_check(e, slot, true));
-    TL_REQUIRE(e->slot_parked[slot], "engine_unpark: the slot is not parked");
+    TL_REQUIRE(e, "engine: null engine");
     const tl_engine_config &c = e->cfg;
-    const int ctx = e->slot_ctx[slot], n = swap_pages_of(ctx, c.page_size);
-    TL_REQUIRE(e->pool.can_take((size_t)n), "engine_unpark: KV page pool exhausted");
-    const std::vector<int> records = e->slot_records[slot];
-    auto &pages = e->slot_pages[slot];
-    if (!swap_unpark_host(e->pool, e->swap_arena, e->pool.enabled ? &e->prefix_rec[slot] : nullptr, pages, ctx, e->slot_records[slot]))
-        return fail(TL_ERR_INVALID, "engine_unpark: the slot's records do not cover its context");  // (nothing changed)
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    for (int j = 0; j < n; ++j) {
-        e->stats.page_allocations++;
-        if (e->page_was_used[pages[j]]) e->stats.reused_page_allocations++;
-        e->page_was_used[pages[j]] = 1;
-        pk.emplace_back(e->block_table + (size_t)slot * c.max_pages_per_seq + j, pages[j]);
-    }
-    page_stats(e);
-    e->slot_parked[slot] = 0;
+    SlotEdits ed;
+    Pokes pk;
+    std::vector<int> records;
+    TL_TRY(table_rc(e->table.unpark(slot, ed, records)));
+    const int ctx = e->table.slots[slot].ctx, n = (int)records.size();
     e->swap_unparks++;
     e->swap_pages_in += n;
+    TL_TRY(apply_edits(e, ed, pk));
     TL_TRY(poke(e, pk));  // the row first: the scatter reads the page ids from it
     const int32_t *row = e->block_table + (size_t)slot * c.max_pages_per_seq;
     const size_t rec = e->swap_record_bytes;
@@ -2282,8 +2091,8 @@ extern "C" int tl_engine_unpark(tl_engine *e, int slot) {
 }
 
 extern "C" int tl_engine_slot_parked(const tl_engine *e, int slot) {
-    if (!e || slot < 0 || slot >= e->cfg.max_batch || !e->slot_live[slot]) return -1;
-    return e->slot_parked[slot] ? 1 : 0;
+    if (!e || e->table.check(slot, true)) return -1;
+    return e->table.slots[slot].parked ? 1 : 0;
 }
 
 extern "C" int tl_engine_step_pages(const tl_engine *e, int batch, int *need, int *obtainable) {
@@ -2292,17 +2101,17 @@ extern "C" int tl_engine_step_pages(const tl_engine *e, int batch, int *need, in
     int extra = 0;
     for (int b = 0; b < batch; ++b) {
         if (!e->slot_runs(b)) continue;
-        const int pages = swap_pages_of(e->slot_ctx[b] + 1, e->cfg.page_size);
-        extra += std::max(0, pages - (int)e->slot_pages[b].size());
+        const Slot &s = e->table.slots[b];
+        extra += std::max(0, swap_pages_of(s.ctx + 1, e->cfg.page_size) - (int)s.pages.size());
     }
     *need = extra;
-    *obtainable = (int)e->pool.available();
+    *obtainable = (int)e->table.pool.available();
     return TL_OK;
 }
 
 extern "C" int tl_engine_swap_stats(const tl_engine *e, tl_swap_stats *out) {
     TL_REQUIRE(e && out, "engine_swap_stats: null argument");
-    *out = tl_swap_stats{e->swap_arena.capacity(), e->swap_arena.in_use, e->swap_parks, e->swap_unparks, e->swap_pages_out, e->swap_pages_in,
+    *out = tl_swap_stats{e->table.arena.capacity(), e->table.arena.in_use, e->swap_parks, e->swap_unparks, e->swap_pages_out, e->swap_pages_in,
                          e->swap_host ? e->swap_record_bytes : 0};
     return TL_OK;
 }
@@ -2318,8 +2127,8 @@ extern "C" int tl_engine_read_pending(tl_engine *e, int count, int32_t *out) {
 }
 
 extern "C" int tl_engine_context_len(const tl_engine *e, int slot) {
-    if (!e || slot < 0 || slot >= e->cfg.max_batch || !e->slot_live[slot]) return -1;
-    return e->slot_ctx[slot];
+    if (!e || e->table.check(slot, true)) return -1;
+    return e->table.slots[slot].ctx;
 }
 
 extern "C" int tl_engine_set_token(tl_engine *e, int slot, int32_t token) {
@@ -2654,12 +2463,12 @@ extern "C" int tl_engine_set_logprobs(tl_engine *e, int slot, int top_n) {
 extern "C" int tl_engine_read_logprobs(tl_engine *e, int slot, int count, tl_token_logprob *out) {
     TL_TRY(slot_check(e, slot, false));
     TL_REQUIRE(out && count >= 0 && count <= e->ring_cap, "engine_read_logprobs: bad count");
-    const int have = e->lp_n.empty() || e->lp_n[slot] < 0 ? 0 : e->slot_produced[slot] - e->lp_from[slot];
+    const int have = e->lp_n.empty() || e->lp_n[slot] < 0 ? 0 : e->table.slots[slot].produced - e->lp_from[slot];
     TL_REQUIRE(count <= have, "engine_read_logprobs: fewer tokens have been produced since logprobs were switched on");
     if (count == 0) return TL_OK;
     TL_HIP(hipStreamSynchronize(e->stream));
     const size_t rec = (size_t)LP_RECORD_WORDS * 4;
-    const int produced = e->slot_produced[slot];
+    const int produced = e->table.slots[slot].produced;
     std::vector<char> ring((size_t)e->ring_cap * rec);
     TL_HIP(hipMemcpy(ring.data(), e->lp_ring + (size_t)slot * e->ring_cap * LP_RECORD_WORDS, ring.size(), hipMemcpyDeviceToHost));
     for (int i = 0; i < count; ++i) memcpy(out + i, ring.data() + (size_t)((produced - count + i) % e->ring_cap) * rec, rec);
@@ -2731,12 +2540,13 @@ static int lm_head_rows(tl_engine *e, const uint16_t *x, int rows) {
 
 static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const int32_t *tokens, int total, bool packed) {
     const tl_engine_config &c = e->cfg;
-    std::vector<std::pair<int32_t *, int32_t>> pk;
+    SlotEdits ed;
+    Pokes pk;
     for (int i = 0; i < n_seqs; ++i) {
-        TL_TRY(reserve_locked(e, seqs[i].slot, seqs[i].start + seqs[i].len, pk));
+        TL_TRY(table_rc(e->table.reserve(seqs[i].slot, seqs[i].start + seqs[i].len, ed)));
         pk.emplace_back(e->scratch_ctx + i, seqs[i].start + seqs[i].len);
     }
-    page_stats(e);
+    TL_TRY(apply_edits(e, ed, pk));
     TL_TRY(poke(e, pk));
     TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens, (size_t)total * 4, hipMemcpyHostToDevice, e->stream));
     for (int i = 0; i < n_seqs; ++i) {  // the chunk's tokens enter the history of a slot that processes its logits (logit_process.h)
@@ -2805,14 +2615,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
         TL_CHECK_LAUNCH(packed ? "engine packed prefill layer" : "engine prefill layer");
     }
     for (int i = 0; i < n_seqs; ++i) {
-        if (e->pool.enabled) {  // tokens appended where the record ends extend it, and pages that filled up enter the index
-            auto &known = e->prefix_rec[seqs[i].slot].known;
-            if ((int)known.size() == seqs[i].start) {
-                known.insert(known.end(), tokens + seqs[i].row0, tokens + seqs[i].row0 + seqs[i].len);
-                prefix_publish(e, seqs[i].slot);
-            }
-        }
-        e->slot_ctx[seqs[i].slot] = seqs[i].start + seqs[i].len;
+        e->table.appended(seqs[i].slot, tokens + seqs[i].row0, seqs[i].len);  // (seqs[i].start is the slot's context)
         e->gr_pending[seqs[i].slot] = 0;  // a pending token that is prefilled past is never fed
         pk.emplace_back(e->context_lens + seqs[i].slot, seqs[i].start + seqs[i].len);
     }
@@ -2832,7 +2635,7 @@ static int prefill_first_token(tl_engine *e, int slot, const uint16_t *logits, c
     }
     launch_step_end(e, step_end_args(e, logits, slot, 0, e->h), 1, e->smp[slot].samples(), step_logprobs_slot(e, slot), raw);
     TL_CHECK_LAUNCH(what);
-    e->slot_produced[slot] += 1;
+    e->table.slots[slot].produced += 1;
     e->gr_pending[slot] = 1;
     return TL_OK;
 }
@@ -2847,7 +2650,7 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
     const tl_engine_config &c = e->cfg;
     TL_REQUIRE(n <= 8 || c.head_dim == 128, "engine_prefill: chunks longer than 8 tokens need head_dim 128 (bf16 FlashAttention)");
     for (int i = 0; i < n; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < c.vocab_size, "engine_prefill: token id out of range");
-    const PrefillSeq seq{slot, e->slot_ctx[slot], 0, n};
+    const PrefillSeq seq{slot, e->table.slots[slot].ctx, 0, n};
     TL_TRY(prefill_pass(e, &seq, 1, tokens, n, false));
     if (logits_mode == 3) {
         // the final RMSNorm over the chunk's rows, then the lm_head through the W4 GEMM a block of rows at a time into the scoring
@@ -2890,9 +2693,10 @@ static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const
         TL_TRY(slot_check_unparked(e, slots[i]));
         TL_REQUIRE(lens[i] > 0, "engine_prefill_packed: every sequence needs at least one token");
         for (int j = 0; j < i; ++j) TL_REQUIRE(slots[j] != slots[i], "engine_prefill_packed: a slot appears twice");
-        const int need = (e->slot_ctx[slots[i]] + lens[i] + c.page_size - 1) / c.page_size;
+        const Slot &s = e->table.slots[slots[i]];
+        const int need = (s.ctx + lens[i] + c.page_size - 1) / c.page_size;
         TL_REQUIRE(need <= c.max_pages_per_seq, "engine: sequence exceeds max_pages_per_seq * page_size tokens");
-        if (need > (int)e->slot_pages[slots[i]].size()) extra_pages += (size_t)need - e->slot_pages[slots[i]].size();
+        if (need > (int)s.pages.size()) extra_pages += (size_t)need - s.pages.size();
         total += lens[i];
     }
     TL_REQUIRE(total <= c.max_prefill_rows, "engine_prefill_packed: the chunks together exceed max_prefill_rows");
@@ -2901,13 +2705,13 @@ static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const
         for (int i = 0; i < n_seqs; ++i) wanted += want_logits[i] ? 1 : 0;
         TL_REQUIRE(wanted <= std::max(c.max_batch, 8), "engine_prefill_packed: more prompts end in this pass than the logits buffer has rows (max(max_batch, 8))");
     }
-    TL_REQUIRE(e->pool.can_take(extra_pages), "engine: KV page pool exhausted");  // checked before anything is mutated
+    TL_REQUIRE(e->table.pool.can_take(extra_pages), "engine: KV page pool exhausted");  // checked before anything is mutated
     for (int i = 0; i < total; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < c.vocab_size, "engine_prefill_packed: token id out of range");
 
     std::vector<PrefillSeq> seqs(n_seqs);
     int rows = 0;
     for (int i = 0; i < n_seqs; ++i) {
-        seqs[i] = {slots[i], e->slot_ctx[slots[i]], rows, lens[i]};
+        seqs[i] = {slots[i], e->table.slots[slots[i]].ctx, rows, lens[i]};
         rows += lens[i];
     }
     TL_TRY(prefill_pass(e, seqs.data(), n_seqs, tokens, total, true));
@@ -3009,19 +2813,21 @@ static void launch_embed_slots(tl_engine *e, int batch) {
 // steps in flight on the AQL queue passes `on_queue`: a new page id drains them first (the poke is a stream launch and must land between
 // the steps), and a failed reservation returns with the queue drained.
 static int prepare_step(tl_engine *e, int batch, SplitPlan *sp, bool *on_queue = nullptr) {
-    std::vector<std::pair<int32_t *, int32_t>> pk;
+    SlotEdits &ed = e->step_edits;  // (reused: a step in which no slot crosses a page boundary allocates nothing)
+    ed.clear();
     int max_ctx = 1;
-    const int rc = reserve_step_locked(e, batch, pk, &max_ctx);
+    const int rc = table_rc(e->table.reserve_step(batch, ed, &max_ctx));
     if (rc != TL_OK) {
         if (on_queue) (void)aql_drain(e);
         return rc;
     }
-    if (!pk.empty()) {
-        page_stats(e);
+    if (!ed.rows.empty()) {
         if (on_queue && *on_queue) {
             TL_TRY(aql_drain(e));
             *on_queue = false;
         }
+        Pokes pk;
+        TL_TRY(apply_edits(e, ed, pk));
         TL_TRY(poke(e, pk));
     }
     *sp = pick_decode_splits(e, batch, max_ctx);
@@ -3030,12 +2836,9 @@ static int prepare_step(tl_engine *e, int batch, SplitPlan *sp, bool *on_queue =
 
 // the host mirrors after a step over slots [0, batch): every live slot holds one more token and has produced one more id
 static void step_done(tl_engine *e, int batch) {
-    for (int b = 0; b < batch; ++b) {
-        if (!e->slot_runs(b)) continue;
-        e->slot_ctx[b] += 1;
-        e->slot_produced[b] += 1;
-        e->gr_pending[b] = 1;
-    }
+    e->table.step_done(batch);
+    for (int b = 0; b < batch; ++b)
+        if (e->slot_runs(b)) e->gr_pending[b] = 1;
     e->stats.decode_steps++;
     e->logits_rows = batch;
 }
@@ -3142,11 +2945,11 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
 extern "C" int tl_engine_read_tokens(tl_engine *e, int slot, int count, int32_t *out) {
     TL_TRY(slot_check(e, slot, false));
     TL_REQUIRE(out && count >= 0 && count <= e->ring_cap, "engine_read_tokens: bad count");
-    TL_REQUIRE(count <= e->slot_produced[slot], "engine_read_tokens: fewer ids have been produced");
+    TL_REQUIRE(count <= e->table.slots[slot].produced, "engine_read_tokens: fewer ids have been produced");
     TL_HIP(hipStreamSynchronize(e->stream));
     std::vector<int32_t> ring(e->ring_cap);
     TL_HIP(hipMemcpy(ring.data(), e->ring + (size_t)slot * e->ring_cap, (size_t)e->ring_cap * 4, hipMemcpyDeviceToHost));
-    const int produced = e->slot_produced[slot];
+    const int produced = e->table.slots[slot].produced;
     for (int i = 0; i < count; ++i) out[i] = ring[(produced - count + i) % e->ring_cap];
     return TL_OK;
 }
@@ -3170,7 +2973,7 @@ extern "C" const int32_t *tl_engine_tokens_dev(const tl_engine *e) { return e ? 
 extern "C" int tl_engine_get_stats(const tl_engine *e, tl_engine_stats *out) {
     TL_REQUIRE(e && out, "engine_get_stats: null argument");
     *out = e->stats;
-    out->pages_free = (int)e->pool.free_pages.size();
+    page_stats(e->table, out);
     return TL_OK;
 }
 
@@ -3185,7 +2988,7 @@ extern "C" size_t tl_engine_step_bytes(const tl_engine *e, int batch) {
     const size_t kv_per_token = e->kv_format == TL_KV_FP8_E4M3 ? (size_t)2 * c.num_layers * c.num_kv_heads * (c.head_dim + 4)
                                                                : (size_t)2 * c.num_layers * c.num_kv_heads * c.head_dim * 2;
     for (int b = 0; b < batch && b < c.max_batch; ++b)
-        if (e->slot_runs(b)) total += kv_per_token * (size_t)e->slot_ctx[b];
+        if (e->slot_runs(b)) total += kv_per_token * (size_t)e->table.slots[b].ctx;
     return total;
 }
 

@@ -1,15 +1,9 @@
-// KV swap, host side (include/tinyllm_engine.h "KV swap"): the allocator of the host arena's page records and the
-// page accounting of tl_engine_park / tl_engine_unpark over PagePool (prefix_cache.h).  Host only, no HIP include: engine.hip calls
-// it, and tests/kv_swap_model_check.cpp drives it alone.
+// KV swap, host side (include/tinyllm_engine.h "KV swap"): the allocator of the host arena's page records.  The
+// page and record accounting of tl_engine_park / tl_engine_unpark is SlotTable's (slot_table.h: park_begin / park_commit / park_abort,
+// unpark), which owns the arena.  Host only, no HIP include.
 //
 //   record    room for one KV page of every pool in the pinned host arena; record r lies at r * record_bytes.  A parked slot holds
 //             ceil(context / page_size) records, one per page, in page order.
-//   park      the slot lets go of its pages exactly as a release does (reference counts drop, pages others share stay with them, indexed
-//             pages become retained, the rest go to the free list) and keeps its records; its known tokens stay, the entries of its pages
-//             are forgotten (unpark registers again).
-//   unpark    fresh private pages from the one allocation path (free list first, then eviction), the records return to the arena, the
-//             full pages inside the known tokens go through PagePool::register_slot like a prefill's.
-// Both are all-or-nothing: a call that cannot be served changes nothing.
 #pragma once
 
 #include "prefix_cache.h"
@@ -57,29 +51,6 @@ inline std::vector<std::pair<int, int>> swap_runs(const std::vector<int> &record
         else runs.emplace_back(j, 1);
     }
     return runs;
-}
-
-// park on the host.  `rec`: the slot's prefix record, or nullptr while the cache is off.  false: not enough free records, nothing changed
-inline bool swap_park_host(PagePool &pool, SwapArena &arena, SlotRecord *rec, std::vector<int> &pages, int context, std::vector<int> &records) {
-    const int n = swap_pages_of(context, pool.page_size);
-    if (context < 1 || n > (int)pages.size() || !records.empty() || !arena.take(n, records)) return false;
-    for (int id : pages) pool.drop(id);
-    pages.clear();
-    if (rec) {
-        rec->nodes.clear();
-        rec->stuck = false;
-    }
-    return true;
-}
-
-// unpark on the host: `pages` becomes n fresh private pages.  false: fewer than n pages can be had, nothing changed
-inline bool swap_unpark_host(PagePool &pool, SwapArena &arena, SlotRecord *rec, std::vector<int> &pages, int context, std::vector<int> &records) {
-    const int n = swap_pages_of(context, pool.page_size);
-    if (n != (int)records.size() || !pages.empty() || !pool.can_take((size_t)n)) return false;
-    for (int j = 0; j < n; ++j) pages.push_back(pool.take());
-    arena.give(records);
-    if (rec) pool.register_slot(*rec, pages);
-    return true;
 }
 
 }  // namespace tl

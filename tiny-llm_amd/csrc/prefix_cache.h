@@ -1,6 +1,7 @@
 // Cross-request prefix cache: the KV page pool's bookkeeping (free list, reference counts) and the index of full pages by the
-// tokens they hold (include/tinyllm_engine.h, "Prefix cache").  Host only, no HIP include: engine.hip calls
-// it, and tests/prefix_cache_model_check.cpp drives it alone against a brute-force model.
+// tokens they hold (include/tinyllm_engine.h, "Prefix cache").  Host only, no HIP include.  Which slot holds
+// which page is SlotTable's business (slot_table.h), which owns the pool: engine.hip and tests/prefix_cache_model_check.cpp both reach
+// it through the table, the latter against a brute-force model.
 //
 //   page states   free (on the free list) | in use (refs > 0) | retained (refs == 0 and indexed).  in_use + free + retained ==
 //                 num_pages after every call.
