@@ -516,6 +516,34 @@ int tl_grammar_mask_rows_stack(const tl_grammar *g, const void *logits_dev, int 
  * Works for bf16 and FP8 KV pages and MoE engines.  Synchronises. */
 int tl_engine_score(tl_engine *e, int slot, const int32_t *tokens, int n, int32_t next_token, float *out_logprobs, int32_t *out_argmax);
 
+/* Embeddings: a text's vector is pooled from the model's output rows -- the final RMSNorm of the last layer's hidden rows, bf16 -- and
+ * optionally truncated and L2-normalised (csrc/pool.h).  Qwen3-Embedding models are plain Qwen3 decoders that pool
+ * the last token's row and normalise it.
+ *   pooling    TL_POOL_LAST: the row of the text's last token, widened to fp32.  TL_POOL_MEAN: the mean of the rows of all its tokens:
+ *              fp32 column sums per chunk join a per-slot running sum [hidden] (allocated for all slots by the first MEAN call), divided
+ *              by the number of rows on finish.  Fixed summation order, no atomics: a text's vector depends on its tokens and on how they
+ *              were cut into chunks, not on its slot, its place in a pass or its neighbours.
+ *   finish     the first `dim` (1 .. hidden_size) components; with normalize != 0 divided by their Euclidean norm (fp32; a vector of norm
+ *              0 stays all zeros, NaN propagates).  fp32 [dim].
+ * tl_engine_embed_packed behaves exactly like tl_engine_prefill_packed with want_logits = 0 for the KV cache, the contexts, the prefix
+ * cache's token record and the limits (head_dim 128, 1 .. 16 sequences, sum of lens <= max_prefill_rows, everything checked before
+ * anything is reserved); tl_engine_embed is one slot through tl_engine_prefill's path with that call's limits.  finish[i] != 0 marks the
+ * chunk that ends its text: that sequence's vector goes to the next `dim` floats of out_host, in the order of the call (out_host may be
+ * NULL when nothing finishes).  The call synchronises when some sequence finishes and only enqueues otherwise.  The pending token, the
+ * logits of tl_engine_logits_dev, the token ring, the produced count and every sampling / grammar / penalty / logprob setting are untouched.
+ *   running mean   per slot the engine knows how many rows its running sum holds, or that it holds none.  A MEAN chunk must start at
+ *              context 0 (the mean restarts) or at a context of exactly that many rows; anything else -- a context that came from
+ *              tl_engine_prefix_attach, a prefill, a decode step, a fork, a move, a rewind or an unpark -- is TL_ERR_INVALID with nothing
+ *              changed.  begin, release, move, fork (the new slot), rewind, park and unpark forget the sum.  LAST has no such rule: a
+ *              prompt whose prefix was attached from the prefix cache embeds from its remaining tokens.
+ * TL_ERR_INVALID with nothing changed: an unknown pooling mode, dim out of range, a null pointer, a parked or dead slot, a slot named
+ * twice, a token id out of range.  bf16 and FP8 KV pages and MoE engines work unchanged (pooling reads the hidden rows only). */
+#define TL_POOL_LAST 0
+#define TL_POOL_MEAN 1
+int tl_engine_embed_packed(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, const int *finish, int pooling,
+                           int normalize, int dim, float *out_host);
+int tl_engine_embed(tl_engine *e, int slot, const int32_t *tokens, int n, int finish, int pooling, int normalize, int dim, float *out_host);
+
 /* Run `steps` decode steps over the live slots [0, batch): each step feeds every
  * slot's pending token at position context_len, appends K/V, and leaves the next
  * token as the next pending token: the argmax, or, for a slot with a nonzero
@@ -745,6 +773,15 @@ int tl_sample_logits(const void *logits_dev, int rows, int vocab, const float *t
  * top_ids_dev / top_logprobs_dev [rows, top_n] (may be NULL when top_n is 0).  One 1,024-thread workgroup per row.  Stream ordered. */
 int tl_logprob_rows(const void *logits_dev, int rows, int vocab, const int32_t *ids_dev, int top_n, float *logprob_dev, int32_t *top_ids_dev,
                     float *top_logprobs_dev, void *stream);
+
+/* The pooling routine of tl_engine_embed over caller rows: rows_dev [total, hidden] bf16 (hidden even, 4-byte aligned), already final-normalised;
+ * n_seqs (1 .. 16) sequences, sequence i the rows [row0[i], row0[i] + len[i]) (host arrays; the caller vouches for the rows).
+ * TL_POOL_MEAN: the chunk's column sums join sums_dev [n_seqs, hidden] fp32, row i of it -- replacing it when prior[i] (the rows it
+ * already holds, a host array) is 0; TL_POOL_LAST ignores prior and sums_dev (both may be NULL).  A sequence with finish[i] != 0 writes
+ * its vector -- `dim` (1 .. hidden) components, divided by their norm when normalize != 0 -- to the next `dim` floats of out_dev, in
+ * order.  Stream ordered. */
+int tl_pool_rows(const void *rows_dev, int hidden, int n_seqs, const int *row0, const int *len, const int *finish, const int *prior, int pooling,
+                 float *sums_dev, int normalize, int dim, float *out_dev, void *stream);
 
 /* The processing routine of tl_engine_set_penalties / tl_engine_set_logit_bias over caller rows: logits [rows, vocab] bf16 (vocab <=
  * 524,288) -> out_dev [rows, vocab] bf16, the engine's kernel and semantics, nothing counted.  history_dev [rows, vocab]: one uint16 per

@@ -19,6 +19,7 @@
 #include "prefix_cache.h"
 #include "kv_copy.h"
 #include "kv_swap.h"
+#include "pool.h"
 #include "slot_table.h"
 
 namespace tl {
@@ -226,6 +227,11 @@ struct tl_engine {
     uint16_t *score_logits = nullptr;
     int32_t *score_ids = nullptr, *score_argmax = nullptr;
     float *score_lp = nullptr;
+    // embeddings (tl_engine_embed / _embed_packed, pool.h): the vectors of a call's finishing sequences [16, hidden] fp32, allocated by the
+    // first embed call; the running sums of mean pooling [max_batch, hidden] fp32, allocated by the first MEAN call; and per slot (host
+    // only) how many rows its running sum holds, -1: none
+    float *emb_out = nullptr, *emb_sums = nullptr;
+    std::vector<int> emb_rows;
 
     bool warmed = false;
     std::map<std::pair<int, long>, hipGraphExec_t> graphs;  // (batch, n_splits << 32 | tokens_per_split)
@@ -1282,6 +1288,7 @@ static int slot_check_unparked(const tl_engine *e, int slot) {
 // begin / release: everything back to the defaults (each skipped while it is the default already)
 static int settings_reset(tl_engine *e, int slot) {
     e->gr_pending[slot] = 0;
+    e->emb_rows[slot] = -1;
     TL_TRY(lp_write(e, slot, -1));
     TL_TRY(pen_reset(e, slot));
     return smp_reset(e, slot);
@@ -1290,6 +1297,8 @@ static int settings_reset(tl_engine *e, int slot) {
 static int settings_carry(tl_engine *e, int src, int dst, bool move) {
     e->gr_pending[dst] = e->gr_pending[src];
     if (move) e->gr_pending[src] = 0;
+    e->emb_rows[dst] = -1;  // a running mean (pool.h) does not travel: the context of dst did not come from MEAN chunks of its own
+    if (move) e->emb_rows[src] = -1;
     // the pending input token travels on the device
     TL_HIP(hipMemcpyAsync(e->tokens + dst, e->tokens + src, sizeof(int32_t), hipMemcpyDeviceToDevice, e->stream));
     // the sampling parameters (seed included: give a fork's child its own seed, or both draw the same tokens)
@@ -1656,6 +1665,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->smp.assign(c.max_batch, tl_engine::SampleParams{});
     e->pen.assign(c.max_batch, tl_engine::PenaltyParams{});
     e->gr_pending.assign(c.max_batch, 0);
+    e->emb_rows.assign(c.max_batch, -1);
     e->stats.kv_bytes = e->kv_bytes;
     e->stats.workspace_bytes = e->arena_bytes + e->tiled_bytes + e->bf16w_bytes;
     *out = e;
@@ -1763,6 +1773,8 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     if (e->swap_staging) (void)hipFree(e->swap_staging);
     if (e->swap_offsets_dev) (void)hipFree(e->swap_offsets_dev);
     if (e->score_logits) (void)hipFree(e->score_logits);
+    if (e->emb_out) (void)hipFree(e->emb_out);
+    if (e->emb_sums) (void)hipFree(e->emb_sums);
     if (e->kpool) (void)hipFree(e->kpool);
     if (e->vpool) (void)hipFree(e->vpool);
     if (e->kscale_pool) (void)hipFree(e->kscale_pool);
@@ -1835,6 +1847,7 @@ extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
     SlotEdits ed;
     Pokes pk;
     TL_TRY(table_rc(e->table.rewind(slot, n, ed)));
+    e->emb_rows[slot] = -1;
     TL_TRY(apply_edits(e, ed, pk));  // the copy of a shared tail page before the row entry that publishes the fresh page
     pk.emplace_back(e->context_lens + slot, e->table.slots[slot].ctx);
     return poke(e, pk);
@@ -2052,6 +2065,7 @@ extern "C" int tl_engine_park(tl_engine *e, int slot) {
     SlotEdits ed;
     Pokes pk;
     e->table.park_commit(slot, ed);
+    e->emb_rows[slot] = -1;
     TL_TRY(apply_edits(e, ed, pk));
     pk.emplace_back(e->live + slot, 0);
     pk.emplace_back(e->context_lens + slot, 0);
@@ -2068,6 +2082,7 @@ extern "C" int tl_engine_unpark(tl_engine *e, int slot) {
     Pokes pk;
     std::vector<int> records;
     TL_TRY(table_rc(e->table.unpark(slot, ed, records)));
+    e->emb_rows[slot] = -1;
     const int ctx = e->table.slots[slot].ctx, n = (int)records.size();
     e->swap_unparks++;
     e->swap_pages_in += n;
@@ -2497,6 +2512,12 @@ extern "C" int tl_logprob_rows(const void *logits_dev, int rows, int vocab, cons
     return TL_OK;
 }
 
+extern "C" int tl_pool_rows(const void *rows_dev, int hidden, int n_seqs, const int *row0, const int *len, const int *finish, const int *prior,
+                            int pooling, float *sums_dev, int normalize, int dim, float *out_dev, void *stream) {
+    return pool_rows((const uint16_t *)rows_dev, hidden, n_seqs, row0, len, finish, prior, nullptr, pooling, sums_dev, normalize, dim, out_dev,
+                     (hipStream_t)stream);
+}
+
 // the paged attention operator over layer l's pages, by the engine's page format
 static int engine_paged_attention(tl_engine *e, int l, const uint16_t *q_t, const int32_t *block_row, const int32_t *ctx_dev, uint16_t *attn_t,
                                   int n, int ctx_hint) {
@@ -2680,40 +2701,52 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
     return TL_OK;
 }
 
-// Several sequences' chunks in ONE prefill pass: the projections (97 % of the prefill FLOPs) run once over the concatenated rows -- a
-// 2,048-row GEMM instead of several 300-row ones.
-static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, const int *want_logits) {
+// The checks of a packed pass, all before anything is reserved, and the pass's sequences: `ends` (may be NULL: none) marks the chunks
+// that want a logits row.  `what` names the caller in the errors.
+static int packed_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, const int *ends, const char *what,
+                       std::vector<PrefillSeq> &seqs) {
     const tl_engine_config &c = e->cfg;
-    TL_REQUIRE(e && slots && tokens && lens && want_logits, "engine_prefill_packed: null argument");
-    TL_REQUIRE(n_seqs >= 1 && n_seqs <= 16, "engine_prefill_packed: between 1 and 16 sequences per call");
-    TL_REQUIRE(c.head_dim == 128, "engine_prefill_packed: head_dim 128 (bf16 FlashAttention)");
+    const std::string w = std::string(what) + ": ";
+    TL_REQUIRE(n_seqs >= 1 && n_seqs <= 16, w + "between 1 and 16 sequences per call");
+    TL_REQUIRE(c.head_dim == 128, w + "head_dim 128 (bf16 FlashAttention)");
     int total = 0;
     size_t extra_pages = 0;
     for (int i = 0; i < n_seqs; ++i) {
         TL_TRY(slot_check_unparked(e, slots[i]));
-        TL_REQUIRE(lens[i] > 0, "engine_prefill_packed: every sequence needs at least one token");
-        for (int j = 0; j < i; ++j) TL_REQUIRE(slots[j] != slots[i], "engine_prefill_packed: a slot appears twice");
+        TL_REQUIRE(lens[i] > 0, w + "every sequence needs at least one token");
+        for (int j = 0; j < i; ++j) TL_REQUIRE(slots[j] != slots[i], w + "a slot appears twice");
         const Slot &s = e->table.slots[slots[i]];
         const int need = (s.ctx + lens[i] + c.page_size - 1) / c.page_size;
         TL_REQUIRE(need <= c.max_pages_per_seq, "engine: sequence exceeds max_pages_per_seq * page_size tokens");
         if (need > (int)s.pages.size()) extra_pages += (size_t)need - s.pages.size();
         total += lens[i];
     }
-    TL_REQUIRE(total <= c.max_prefill_rows, "engine_prefill_packed: the chunks together exceed max_prefill_rows");
-    {
+    TL_REQUIRE(total <= c.max_prefill_rows, w + "the chunks together exceed max_prefill_rows");
+    if (ends) {
         int wanted = 0;
-        for (int i = 0; i < n_seqs; ++i) wanted += want_logits[i] ? 1 : 0;
-        TL_REQUIRE(wanted <= std::max(c.max_batch, 8), "engine_prefill_packed: more prompts end in this pass than the logits buffer has rows (max(max_batch, 8))");
+        for (int i = 0; i < n_seqs; ++i) wanted += ends[i] ? 1 : 0;
+        TL_REQUIRE(wanted <= std::max(c.max_batch, 8), w + "more prompts end in this pass than the logits buffer has rows (max(max_batch, 8))");
     }
     TL_REQUIRE(e->table.pool.can_take(extra_pages), "engine: KV page pool exhausted");  // checked before anything is mutated
-    for (int i = 0; i < total; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < c.vocab_size, "engine_prefill_packed: token id out of range");
-
-    std::vector<PrefillSeq> seqs(n_seqs);
+    for (int i = 0; i < total; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < c.vocab_size, w + "token id out of range");
+    seqs.resize(n_seqs);
     int rows = 0;
     for (int i = 0; i < n_seqs; ++i) {
         seqs[i] = {slots[i], e->table.slots[slots[i]].ctx, rows, lens[i]};
         rows += lens[i];
     }
+    return TL_OK;
+}
+
+// Several sequences' chunks in ONE prefill pass: the projections (97 % of the prefill FLOPs) run once over the concatenated rows -- a
+// 2,048-row GEMM instead of several 300-row ones.
+static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, const int *want_logits) {
+    const tl_engine_config &c = e->cfg;
+    TL_REQUIRE(e && slots && tokens && lens && want_logits, "engine_prefill_packed: null argument");
+    std::vector<PrefillSeq> seqs;
+    TL_TRY(packed_seqs(e, n_seqs, slots, tokens, lens, want_logits, "engine_prefill_packed", seqs));
+    int total = 0;
+    for (int i = 0; i < n_seqs; ++i) total += lens[i];
     TL_TRY(prefill_pass(e, seqs.data(), n_seqs, tokens, total, true));
     int n_logits = 0;
     for (int i = 0; i < n_seqs; ++i) {
@@ -2768,6 +2801,96 @@ extern "C" int tl_engine_score(tl_engine *e, int slot, const int32_t *tokens, in
     if (out_argmax) TL_HIP(hipMemcpyAsync(out_argmax, e->score_argmax, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
     TL_HIP(hipStreamSynchronize(e->stream));
     return TL_OK;
+}
+
+// ---- embeddings (include/tinyllm_engine.h "Embeddings"; the kernels are pool.h) -----------------------------------------------------------
+// what an embed call checks before it looks at a slot
+static int embed_args_check(const tl_engine *e, int pooling, int dim, bool finishes, const float *out_host) {
+    TL_REQUIRE(pooling == TL_POOL_LAST || pooling == TL_POOL_MEAN, "engine_embed: pooling is TL_POOL_LAST or TL_POOL_MEAN");
+    TL_REQUIRE(dim >= 1 && dim <= e->cfg.hidden_size, "engine_embed: dim must be 1 .. hidden_size");
+    TL_REQUIRE(e->cfg.hidden_size % 2 == 0, "engine_embed: hidden_size must be even");
+    TL_REQUIRE(!finishes || out_host, "engine_embed: a text finishes and out_host is null");
+    return TL_OK;
+}
+// MEAN: every chunk restarts its slot's running sum at context 0 or continues it at exactly the rows the sum holds
+static int embed_mean_check(const tl_engine *e, const PrefillSeq *seqs, int n_seqs) {
+    for (int i = 0; i < n_seqs; ++i)
+        TL_REQUIRE(seqs[i].start == 0 || e->emb_rows[seqs[i].slot] == seqs[i].start,
+                   "engine_embed: mean pooling continues a text embedded from context 0 with TL_POOL_MEAN chunks only (the slot's context came from elsewhere)");
+    return TL_OK;
+}
+static int embed_alloc(tl_engine *e, bool mean) {
+    const size_t H = (size_t)e->cfg.hidden_size;
+    if (!e->emb_out) {
+        const size_t bytes = POOL_MAX_SEQS * H * sizeof(float);
+        if (hipMalloc((void **)&e->emb_out, bytes) != hipSuccess) return fail(TL_ERR_HIP, "engine_embed: hipMalloc(vectors) failed");
+        e->stats.workspace_bytes += bytes;
+    }
+    if (mean && !e->emb_sums) {
+        const size_t bytes = (size_t)e->cfg.max_batch * H * sizeof(float);
+        if (hipMalloc((void **)&e->emb_sums, bytes) != hipSuccess) return fail(TL_ERR_HIP, "engine_embed: hipMalloc(running sums) failed");
+        e->stats.workspace_bytes += bytes;
+    }
+    return TL_OK;
+}
+// The pooling stage behind a prefill pass whose rows are still in x.  LAST: the finishing sequences' last rows side by side in h (as
+// prefill_packed_impl gathers the rows of the lm_head), the final RMSNorm over those, the finish.  MEAN: the final RMSNorm over every
+// row of the pass (as tl_engine_score), the column sums into the slots' running sums, the finish.  Synchronises when a text finishes.
+static int embed_pool(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const int *finish, int pooling, int normalize, int dim, float *out_host) {
+    const tl_engine_config &c = e->cfg;
+    const size_t H = (size_t)c.hidden_size;
+    const bool mean = pooling == TL_POOL_MEAN;
+    TL_TRY(embed_alloc(e, mean));
+    int row0[POOL_MAX_SEQS], len[POOL_MAX_SEQS], prior[POOL_MAX_SEQS], sum_index[POOL_MAX_SEQS], fin[POOL_MAX_SEQS];
+    int n = 0, n_finish = 0, total = 0;
+    for (int i = 0; i < n_seqs; ++i) {
+        const PrefillSeq &q = seqs[i];
+        total += q.len;
+        if (mean) {
+            row0[n] = q.row0, len[n] = q.len, sum_index[n] = q.slot, fin[n] = finish[i] ? 1 : 0;
+            prior[n] = q.start == 0 ? 0 : e->emb_rows[q.slot];
+            e->emb_rows[q.slot] = prior[n] + q.len;
+            n_finish += fin[n++];
+            continue;
+        }
+        e->emb_rows[q.slot] = -1;
+        if (!finish[i]) continue;
+        TL_HIP(hipMemcpyAsync(e->h + (size_t)n * H, e->x + (size_t)(q.row0 + q.len - 1) * H, H * 2, hipMemcpyDeviceToDevice, e->stream));
+        row0[n] = n, len[n] = 1, prior[n] = 0, sum_index[n] = 0, fin[n] = 1;
+        ++n, ++n_finish;
+    }
+    if (n == 0) return TL_OK;  // LAST chunks that end no text: the pass has appended their K/V, nothing to pool
+    TL_TRY(tl_rms_norm(mean ? e->x : e->h, e->final_norm, e->xn, mean ? total : n, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
+    TL_TRY(pool_rows(e->xn, c.hidden_size, n, row0, len, fin, prior, sum_index, pooling, e->emb_sums, normalize, dim, e->emb_out, e->stream));
+    if (n_finish == 0) return TL_OK;
+    TL_HIP(hipMemcpyAsync(out_host, e->emb_out, (size_t)n_finish * dim * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    TL_HIP(hipStreamSynchronize(e->stream));
+    return TL_OK;
+}
+
+extern "C" int tl_engine_embed_packed(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, const int *finish,
+                                      int pooling, int normalize, int dim, float *out_host) {
+    TL_REQUIRE(e && slots && tokens && lens && finish, "engine_embed_packed: null argument");
+    std::vector<PrefillSeq> seqs;
+    TL_TRY(packed_seqs(e, n_seqs, slots, tokens, lens, nullptr, "engine_embed_packed", seqs));
+    bool finishes = false;
+    int total = 0;
+    for (int i = 0; i < n_seqs; ++i) finishes |= finish[i] != 0, total += lens[i];
+    TL_TRY(embed_args_check(e, pooling, dim, finishes, out_host));
+    if (pooling == TL_POOL_MEAN) TL_TRY(embed_mean_check(e, seqs.data(), n_seqs));
+    TL_TRY(prefill_pass(e, seqs.data(), n_seqs, tokens, total, true));
+    return embed_pool(e, seqs.data(), n_seqs, finish, pooling, normalize, dim, out_host);
+}
+
+extern "C" int tl_engine_embed(tl_engine *e, int slot, const int32_t *tokens, int n, int finish, int pooling, int normalize, int dim,
+                               float *out_host) {
+    TL_REQUIRE(e && tokens, "engine_embed: null argument");
+    TL_TRY(slot_check_unparked(e, slot));
+    TL_TRY(embed_args_check(e, pooling, dim, finish != 0, out_host));
+    const PrefillSeq seq{slot, e->table.slots[slot].ctx, 0, n};
+    if (pooling == TL_POOL_MEAN) TL_TRY(embed_mean_check(e, &seq, 1));
+    TL_TRY(prefill_impl(e, slot, tokens, n, 0));
+    return embed_pool(e, &seq, 1, &finish, pooling, normalize, dim, out_host);
 }
 
 extern "C" int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, int n, int32_t *out_ids) {

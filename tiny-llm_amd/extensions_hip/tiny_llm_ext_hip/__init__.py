@@ -246,6 +246,11 @@ _SIGNATURES.update({
     "tl_engine_read_pending_logprobs": (_c_int, [_c_void_p, _c_int, _P(TlTokenLogprob)]),
     "tl_engine_score": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, ctypes.c_int32, _P(_c_float), _P(ctypes.c_int32)]),
     "tl_logprob_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "tl_engine_embed_packed": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int), _P(ctypes.c_int32), _P(ctypes.c_int), _P(ctypes.c_int), _c_int, _c_int,
+                                        _c_int, _P(_c_float)]),
+    "tl_engine_embed": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _c_int, _c_int, _c_int, _c_int, _P(_c_float)]),
+    "tl_pool_rows": (_c_int, [_c_void_p, _c_int, _c_int, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _c_int, _c_void_p,
+                              _c_int, _c_int, _c_void_p, _c_void_p]),
     "tl_engine_decode": (_c_int, [_c_void_p, _c_int, _c_int, _c_int]),
     "tl_engine_read_tokens": (_c_int, [_c_void_p, _c_int, _c_int, _P(ctypes.c_int32)]),
     "tl_engine_logits_dev": (_c_void_p, [_c_void_p]),
@@ -1017,6 +1022,55 @@ def logprob_rows(logits: torch.Tensor, ids=None, top_n: int = 0):
     check(_lib.tl_logprob_rows(logits.data_ptr(), rows, logits.shape[1], ids_t.data_ptr() if ids_t is not None else None, top_n,
                                lp.data_ptr(), top_ids.data_ptr() if top_n else None, top_lp.data_ptr() if top_n else None, _stream()))
     return lp, top_ids, top_lp
+
+
+POOL_LAST, POOL_MEAN = 0, 1  # TL_POOL_LAST / TL_POOL_MEAN
+POOLING_MODES = {"last": POOL_LAST, "mean": POOL_MEAN}
+
+
+def pooling_args(pooling, normalize, dim, hidden: int) -> tuple[int, int, int]:
+    """(pooling mode, normalize, dim) as the C ABI takes them; ``dim`` None = ``hidden``.  ValueError for anything else."""
+    if not isinstance(pooling, str) or pooling not in POOLING_MODES:
+        raise ValueError(f"pooling must be 'last' or 'mean', got {pooling!r}")
+    if not isinstance(normalize, (bool, int)) or normalize not in (0, 1):
+        raise ValueError(f"normalize must be a bool, got {normalize!r}")
+    dim = hidden if dim is None else dim
+    if isinstance(dim, bool) or not isinstance(dim, int) or not 1 <= dim <= hidden:
+        raise ValueError(f"dim must be an int in [1, {hidden}], got {dim!r}")
+    return POOLING_MODES[pooling], int(normalize), dim
+
+
+def pool_rows(rows: torch.Tensor, seqs, *, pooling: str = "last", normalize: bool = True, dim: int | None = None, finish=None, prior=None,
+              sums: torch.Tensor | None = None) -> torch.Tensor:
+    """The engine's pooling routine (tl_pool_rows) over final-normalised bf16 rows [total, hidden]: ``seqs`` = up to 16 (row0, len) pairs;
+    ``finish`` (default: all) marks the sequences whose vector is written; mean pooling accumulates into ``sums`` [n_seqs, hidden] float32
+    (allocated when None), whose row i already holds ``prior[i]`` rows (default 0: it is replaced).  Returns float32 [finishing, dim]."""
+    if rows.dtype != torch.bfloat16 or rows.dim() != 2 or not rows.is_cuda:
+        raise ValueError("pool_rows takes a [total, hidden] bf16 tensor on the GPU")
+    rows = rows.contiguous()
+    total, hidden = rows.shape
+    mode, norm, dim = pooling_args(pooling, normalize, dim, hidden)
+    seqs = [(int(a), int(b)) for a, b in seqs]
+    n = len(seqs)
+    if not 1 <= n <= 16:
+        raise ValueError("pool_rows takes between 1 and 16 sequences")
+    for r0, ln in seqs:
+        if r0 < 0 or ln < 1 or r0 + ln > total:
+            raise ValueError(f"sequence ({r0}, {ln}) is outside the {total} rows")
+    finish = [1] * n if finish is None else [int(bool(f)) for f in finish]
+    prior = [0] * n if prior is None else [int(p) for p in prior]
+    if len(finish) != n or len(prior) != n:
+        raise ValueError("finish and prior need one value per sequence")
+    if mode == POOL_MEAN:
+        if sums is None:
+            sums = torch.zeros((n, hidden), dtype=torch.float32, device=rows.device)
+        if sums.dtype != torch.float32 or tuple(sums.shape) != (n, hidden) or not sums.is_cuda or not sums.is_contiguous():
+            raise ValueError("sums must be a contiguous [n_seqs, hidden] float32 tensor on the GPU")
+    out = torch.empty((sum(finish), dim), dtype=torch.float32, device=rows.device)
+    ints = lambda v: (ctypes.c_int * n)(*v)
+    check(_lib.tl_pool_rows(rows.data_ptr(), hidden, n, ints([s[0] for s in seqs]), ints([s[1] for s in seqs]), ints(finish), ints(prior), mode,
+                            sums.data_ptr() if mode == POOL_MEAN else None, norm, dim, out.data_ptr() if out.numel() else None, _stream()))
+    return out
 
 
 def process_logits(logits: torch.Tensor, history: torch.Tensor, repetition=1.0, presence=0.0, frequency=0.0, bias=None) -> torch.Tensor:

@@ -116,6 +116,7 @@ class DecodeEngine:
             page_size, num_pages, max_batch, max_pages_per_seq, max_prefill_rows)
         self.page_size, self.max_batch, self.vocab_size = page_size, max_batch, args.vocab_size
         self.max_prefill_rows = int(max_prefill_rows)
+        self.max_pages_per_seq = int(max_pages_per_seq)
         self.num_hidden_layers = int(args.num_hidden_layers)
         self.device = emb.weight.device
         handle = ctypes.c_void_p()
@@ -427,6 +428,56 @@ class DecodeEngine:
         finally:
             self.release(slot)
         return out[:-1]
+
+    def embed(self, tokens: Sequence[int], *, slot: int = 0, pooling: str = "last", normalize: bool = True, dim: int | None = None,
+              chunk: int | None = None):
+        """The text's embedding (tl_engine_embed), float32 [dim] as a numpy array: the model's output rows -- final RMSNorm included --
+        pooled by ``pooling`` ("last": the last token's row, what Qwen3-Embedding models use; "mean": the mean over all tokens), cut to
+        the first ``dim`` components (default: hidden_size) and, with ``normalize``, divided by their Euclidean norm.  Runs on the free
+        ``slot`` as a fresh sequence in chunks of at most ``chunk`` (default: max_prefill_rows) tokens and releases it.  Synchronises."""
+        import numpy as np
+
+        tokens = [int(t) for t in tokens]
+        if not tokens:
+            raise ValueError("embed needs at least one token")
+        mode, norm, dim = _ext.pooling_args(pooling, normalize, dim, int(self.args.hidden_size))
+        chunk = self.max_prefill_rows if chunk is None else chunk
+        if isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= self.max_prefill_rows:
+            raise ValueError(f"chunk must be an int in [1, {self.max_prefill_rows}], got {chunk!r}")
+        out = np.empty(dim, dtype=np.float32)
+        out_p = out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        self.begin(slot)
+        try:
+            for start in range(0, len(tokens), chunk):
+                part = tokens[start:start + chunk]
+                arr = (ctypes.c_int32 * len(part))(*part)
+                last = start + chunk >= len(tokens)
+                _ext.check(_lib.tl_engine_embed(self._h, slot, arr, len(part), int(last), mode, norm, dim, out_p))
+        finally:
+            self.release(slot)
+        return out
+
+    def embed_packed(self, chunks: Sequence[tuple[int, Sequence[int], bool]], *, pooling: str = "last", normalize: bool = True,
+                     dim: int | None = None):
+        """One pass of the multi-token path over several slots' chunks, pooled (tl_engine_embed_packed): ``chunks`` = (slot, token ids,
+        ends_text) for up to 16 live slots, together at most ``max_prefill_rows`` tokens.  Returns float32 [chunks that end their
+        text, dim] in the order of ``chunks``; synchronises only when some chunk ends its text.  The slots stay live: the caller
+        begins and releases them."""
+        import numpy as np
+
+        if not 1 <= len(chunks) <= 16:
+            raise ValueError("embed_packed takes between 1 and 16 chunks")
+        mode, norm, dim = _ext.pooling_args(pooling, normalize, dim, int(self.args.hidden_size))
+        flat = [int(t) for _, toks, _ in chunks for t in toks]
+        n = len(chunks)
+        slots = (ctypes.c_int * n)(*[int(c[0]) for c in chunks])
+        lens = (ctypes.c_int * n)(*[len(c[1]) for c in chunks])
+        finish = (ctypes.c_int * n)(*[int(bool(c[2])) for c in chunks])
+        arr = (ctypes.c_int32 * max(len(flat), 1))(*flat)
+        out = np.empty((sum(finish), dim), dtype=np.float32)
+        _ext.check(_lib.tl_engine_embed_packed(self._h, n, slots, arr, lens, finish, mode, norm, dim,
+                                               out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return out
 
     def decode(self, steps: int, batch: int | None = None, use_graph: bool = True) -> None:
         """Enqueue ``steps`` decode steps over slots [0, batch) (greedy, or each slot's sampler: set_sampling); does not synchronise
