@@ -33,6 +33,11 @@ def main(argv=None):
     ap.add_argument("--repetition-penalty", type=float, default=1.0, help="per request, on the device; over prompt and output (1 = off)")
     ap.add_argument("--presence-penalty", type=float, default=0.0, help="per request, on the device; over the output (0 = off)")
     ap.add_argument("--frequency-penalty", type=float, default=0.0, help="per request, on the device; times the count in the output (0 = off)")
+    ap.add_argument("--sampler-min-p", type=float, default=0.0, help="per sampling request, on the device: keep tokens with p >= min_p * p_max (0 = off)")
+    ap.add_argument("--sampler-typical-p", type=float, default=None, help="... locally typical sampling with this mass (1 = off)")
+    ap.add_argument("--mirostat-tau", type=float, default=0.0,
+                    help="... Mirostat v2 with this target surprise in bits (0 = off); excludes top-k, top-p, min-p and typical-p")
+    ap.add_argument("--mirostat-eta", type=float, default=0.1, help="Mirostat's learning rate, in (0, 1]")
     constraint = ap.add_mutually_exclusive_group()
     constraint.add_argument("--regex", default=None, metavar="PATTERN",
                             help="every answer must match PATTERN in full (tiny_llm_hip.grammar's dialect), enforced on the device per request")
@@ -48,6 +53,9 @@ def main(argv=None):
                          "swapped out, or its prefill redone) instead of the run failing with 'KV page pool exhausted' (default 0: off)")
     ap.add_argument("--prompts-file", default=None, help="one prompt per line (default: five built-in questions)")
     args = ap.parse_args(argv)
+    from main import check_truncation_flags
+
+    truncates = check_truncation_flags(ap, args)
 
     from tiny_llm_hip import load
     from tiny_llm_hip.engine import DecodeEngine, batch_generate_ids
@@ -70,6 +78,8 @@ def main(argv=None):
     sampling = {}
     if args.sampler_temp:
         sampling.update(temperature=args.sampler_temp, top_k=args.sampler_top_k, top_p=args.sampler_top_p)
+        if truncates:
+            sampling.update(min_p=args.sampler_min_p, typical_p=args.sampler_typical_p, mirostat_tau=args.mirostat_tau, mirostat_eta=args.mirostat_eta)
     if (args.repetition_penalty, args.presence_penalty, args.frequency_penalty) != (1.0, 0.0, 0.0):
         sampling.update(repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty,
                         frequency_penalty=args.frequency_penalty)

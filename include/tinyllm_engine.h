@@ -414,6 +414,50 @@ int tl_engine_read_pending_logprobs(tl_engine *e, int count, tl_token_logprob *o
 int tl_engine_set_penalties(tl_engine *e, int slot, float repetition_penalty, float presence_penalty, float frequency_penalty);
 int tl_engine_set_logit_bias(tl_engine *e, int slot, const int32_t *ids, const float *values, int n);
 
+/* Truncation: min-p, locally typical sampling and Mirostat v2 (csrc/truncate.h).  For a slot that SAMPLES
+ * (temperature T > 0) and truncates, the bf16 row x the choice would be made from -- the raw row, or the processed row when the slot
+ * processes penalties, bias or a grammar -- is first turned into a FILTERED bf16 row, and the existing choice runs on the filtered row
+ * exactly as it runs on any row.  A greedy slot is never filtered: every filter below keeps the maximum.  With m the row maximum,
+ * p_i = exp((x_i - m) / T) / sum_j exp((x_j - m) / T), summed over non-NaN entries in fp32 (NaN logits are never kept, as in the sampler).
+ * The stages run in this order, each over the survivors of the one before:
+ *   min-p      0 < min_p <= 1 (0 = off): token i stays iff p_i >= min_p * p_max, i.e. (x_i - m) / T >= ln(min_p)
+ *              (transformers.MinPLogitsWarper applied to x / T);
+ *   typical-p  0 < typical_p < 1 (anything else = off): over the survivors, renormalised, H = -sum p ln p and d_i = |(-ln p_i) - H|;
+ *              delta* is the smallest deviation for which the mass of {d_i <= delta*} reaches typical_p; token i stays iff
+ *              d_i <= delta*.  EVERY token tied with the boundary on deviation stays: the set depends on no ordering and no key is cut
+ *              (transformers.TypicalLogitsWarper's kept set, closed under ties);
+ *   Mirostat   v2 (Basu et al. 2021, algorithm 2): tau > 0, 0 < eta <= 1; per-slot state mu, 2 tau from every tl_engine_set_mirostat
+ *              call with tau > 0.  Token i stays iff -log2 p_i <= mu; the first maximum always stays.  After the slot's token t has been
+ *              drawn: s = -log2(p_t / sum_kept p) and mu <- mu - eta (s - tau), in fp32.  Mirostat excludes every other truncation of
+ *              the slot (top-k, top-p, min-p, typical-p), as in llama.cpp: the call that would combine them -- tl_engine_set_sampling
+ *              as much as the two calls below -- is TL_ERR_INVALID with nothing changed.
+ *   filtered   tokens that stay keep their bf16 bits, every other token becomes bf16 -inf.  A row whose maximum is not finite (all NaN /
+ *              -inf, or holding +inf) is copied bit for bit: its choice (token 0, the first +inf) depends on no filter.  So is the row
+ *              of a slot that does not truncate or does not sample.
+ *   sees it    the sampling twin and the logprob twin of the step end, with their tie rules, Philox position and draw; the slot's top-k
+ *              and top-p therefore see the filtered row (top-p's mass is over the survivors).  Log-probability records stay the model's
+ *              raw distribution, as for processed rows.  tl_engine_logits_dev / tl_engine_copy_logits keep returning the raw rows and
+ *              tl_engine_copy_processed_logits keeps its meaning; tl_engine_copy_filtered_logits copies the filtered rows of the last
+ *              step in which some live slot truncated (stream ordered; TL_ERR_INVALID before any slot has truncated).
+ *   plan       a step in which no live slot truncates is the program it was.  One in which one does has one launch more ahead of the
+ *              step end (one 1,024-thread workgroup per row, writing rows of its own: nothing is filtered in place) and the Mirostat
+ *              update launch behind it (a no-op for rows without Mirostat), in a captured plan of its own.  The same pair runs where a
+ *              prefill / packed prefill with want_logits chooses the slot's first token.  A plan with a live Mirostat slot stays on
+ *              hipGraphLaunch (the update reads the token the step end stored, which only a launch boundary with cache maintenance
+ *              hands over); tl_engine_replay_route says so while such a slot is live.
+ *   life       tl_engine_begin / tl_engine_release reset the parameters, tl_engine_move carries them and mu with the sequence,
+ *              tl_engine_fork copies them, park / unpark leave them alone.  tl_engine_rewind and tl_engine_set_token refuse a MIROSTAT
+ *              slot with TL_ERR_INVALID (mu would no longer belong to the tokens held); min-p / typical-p slots are not refused.
+ *              tl_engine_verify already refuses a sampling slot.
+ * tl_engine_set_truncation: min_p in [0, 1], typical_p not NaN.  tl_engine_set_mirostat: tau finite and >= 0 (0 switches it off), eta
+ * in (0, 1] when tau > 0.  tl_engine_mirostat_mu: the slot's mu (NaN without Mirostat) after synchronising.  Vocabulary limit as for
+ * the sampler.  The filtered rows (max_batch x vocab x 2 bytes) and the parameters are allocated by the first call that makes a slot
+ * truncate; an engine that never asks allocates nothing. */
+int tl_engine_set_truncation(tl_engine *e, int slot, float min_p, float typical_p);
+int tl_engine_set_mirostat(tl_engine *e, int slot, float tau, float eta);
+int tl_engine_mirostat_mu(tl_engine *e, int slot, float *mu);
+int tl_engine_copy_filtered_logits(tl_engine *e, void *dst_dev, int rows);
+
 /* Grammars: regex-constrained decoding on the device (csrc/grammar.h).  A slot with a grammar may only produce
  * text that a byte-level DFA can still accept; the allowed set changes with every token and is decided inside the processing launch,
  * from tables uploaded once.  Nothing is uploaded per step.
@@ -782,6 +826,17 @@ int tl_logprob_rows(const void *logits_dev, int rows, int vocab, const int32_t *
  * order.  Stream ordered. */
 int tl_pool_rows(const void *rows_dev, int hidden, int n_seqs, const int *row0, const int *len, const int *finish, const int *prior, int pooling,
                  float *sums_dev, int normalize, int dim, float *out_dev, void *stream);
+
+/* The truncation routine of tl_engine_set_truncation / tl_engine_set_mirostat over caller rows: logits [rows, vocab] bf16 (vocab <=
+ * 524,288), per-row device arrays of temperature, min_p, typical_p and mu (NaN = no Mirostat; a Mirostat row ignores min_p and
+ * typical_p), filtered rows into out_dev (never the input) and, where kept_logsum_dev is not null, per row ln sum_kept exp(x_i / T) of a
+ * Mirostat row (NaN for any other).  tl_mirostat_update_rows: the update for the tokens ids_dev[rows] chosen from the filtered rows,
+ * mu_dev[rows] in place; a row with tau 0, temperature 0, an id outside the vocabulary or a surprise that is not finite keeps its mu.
+ * Stream ordered, no synchronisation. */
+int tl_truncate_rows(const void *logits_dev, int rows, int vocab, const float *temperature_dev, const float *min_p_dev, const float *typical_p_dev,
+                     const float *mu_dev, void *out_dev, float *kept_logsum_dev, void *stream);
+int tl_mirostat_update_rows(const void *filtered_dev, int rows, int vocab, const int32_t *ids_dev, const float *temperature_dev,
+                            const float *kept_logsum_dev, const float *tau_dev, const float *eta_dev, float *mu_dev, void *stream);
 
 /* The processing routine of tl_engine_set_penalties / tl_engine_set_logit_bias over caller rows: logits [rows, vocab] bf16 (vocab <=
  * 524,288) -> out_dev [rows, vocab] bf16, the engine's kernel and semantics, nothing counted.  history_dev [rows, vocab]: one uint16 per

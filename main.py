@@ -37,6 +37,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--frequency-penalty", type=float, default=0.0,
                     help="with --solution engine: subtract this times the token's count in the output (0 = off)")
     constraint = ap.add_mutually_exclusive_group()
+    ap.add_argument("--sampler-min-p", type=float, default=0.0,
+                    help="with --solution engine and a nonzero --sampler-temp, on the device: keep tokens with p >= min_p * p_max (0 = off)")
+    ap.add_argument("--sampler-typical-p", type=float, default=None,
+                    help="... locally typical sampling: keep the tokens closest to the entropy until their mass reaches this (1 = off)")
+    ap.add_argument("--mirostat-tau", type=float, default=0.0,
+                    help="... Mirostat v2 with this target surprise in bits (0 = off); excludes top-k, top-p, min-p and typical-p")
+    ap.add_argument("--mirostat-eta", type=float, default=0.1, help="Mirostat's learning rate, in (0, 1]")
     constraint.add_argument("--regex", default=None, metavar="PATTERN",
                             help="with --solution engine: the answer must match PATTERN in full (tiny_llm_hip.grammar's dialect), enforced "
                                  "on the device token by token; the vocabulary comes from the loaded tokenizer")
@@ -56,6 +63,15 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def check_truncation_flags(ap, args) -> bool:
+    """The exclusivity rule of the engine (tl_engine_set_mirostat), raised before anything is loaded; True when a truncation flag is set."""
+    others = args.sampler_min_p > 0 or (args.sampler_typical_p is not None and args.sampler_typical_p < 1) or bool(args.sampler_top_k) or \
+        (args.sampler_top_p is not None and args.sampler_top_p < 1)
+    if args.mirostat_tau > 0 and others:
+        ap.error("Mirostat excludes every other truncation (--sampler-top-k, --sampler-top-p, --sampler-min-p, --sampler-typical-p)")
+    return args.mirostat_tau > 0 or args.sampler_min_p > 0 or (args.sampler_typical_p is not None and args.sampler_typical_p < 1)
+
+
 def chat_prompt(tokenizer, text: str, enable_thinking: bool) -> str:
     messages = [{"role": "system", "content": "You are a helpful assistant."}, {"role": "user", "content": text}]
     return tokenizer.apply_chat_template(messages, tokenize=False, add_generation_prompt=True,
@@ -63,7 +79,9 @@ def chat_prompt(tokenizer, text: str, enable_thinking: bool) -> str:
 
 
 def main(argv=None) -> str:
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    truncates = check_truncation_flags(ap, args)
     from tiny_llm_hip import load
 
     model, tokenizer = load(args.model)
@@ -110,15 +128,16 @@ def main(argv=None) -> str:
                                                proposal_length=min(args.proposal_length, 7), eos_token_id=eos)
             finally:
                 draft.close()
-        elif args.sampler_temp and (args.sampler_seed is not None or penalties != (1.0, 0.0, 0.0) or grammar is not None):
+        elif args.sampler_temp and (args.sampler_seed is not None or penalties != (1.0, 0.0, 0.0) or grammar is not None or truncates):
             # the per-slot sampler on the device: the whole generation in one prefill + one decode(N) call.  The penalties and the
-            # grammar exist on the device only, so they select this path
+            # grammar exist on the device only, so they select this path; so do min-p, typical-p and Mirostat
             if args.sampler_seed is None:
-                print("note: the penalty flags and --regex select the device sampler; no --sampler-seed given: seed 0")
+                print("note: the penalty, truncation and Mirostat flags and --regex select the device sampler; no --sampler-seed given: seed 0")
             out = engine.generate(ids, args.max_new_tokens, temperature=args.sampler_temp, top_k=args.sampler_top_k,
                                   top_p=args.sampler_top_p, seed=args.sampler_seed or 0, logprobs=args.logprobs,
                                   repetition_penalty=penalties[0], presence_penalty=penalties[1], frequency_penalty=penalties[2],
-                                  grammar=grammar)
+                                  grammar=grammar, min_p=args.sampler_min_p, typical_p=args.sampler_typical_p,
+                                  mirostat_tau=args.mirostat_tau, mirostat_eta=args.mirostat_eta)
             if args.logprobs is not None:
                 out, records = out
             out = cut_at_eos(out, eos, grammar)

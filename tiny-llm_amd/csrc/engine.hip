@@ -13,6 +13,7 @@
 #include "sample.h"
 #include "logprob.h"
 #include "logit_process.h"
+#include "truncate.h"
 #include "grammar_stack.h"
 #include "attn_mfma.h"
 #include "aql.h"
@@ -223,6 +224,19 @@ struct tl_engine {
     GrammarRecord *gr_state = nullptr;
     std::vector<char> gr_pending;
     GrammarStackRecord *gr_stack = nullptr;  // [slots] the records of slots with a stack grammar: allocated by the first one set
+    // per-slot truncation (tl_engine_set_truncation / tl_engine_set_mirostat, truncate.h): the host mirror, and -- allocated by the first
+    // call that makes a slot truncate -- the filtered rows [max(max_batch, 8), vocab] the step end chooses from, the per-slot parameters
+    // and Mirostat's state mu [max_batch] (NaN: no Mirostat) and the kept log-sums [max(max_batch, 8)] of the rows of one launch
+    struct TruncParams {
+        float min_p = 0.f, typical_p = 1.f, tau = 0.f, eta = 0.f;
+        bool stateless() const { return min_p > 0.f || (typical_p > 0.f && typical_p < 1.f); }
+        bool mirostat() const { return tau > 0.f; }
+        bool truncates() const { return stateless() || mirostat(); }
+    };
+    std::vector<TruncParams> trn;
+    char *trn_mem = nullptr;
+    uint16_t *trn_rows = nullptr;
+    float *trn_minp = nullptr, *trn_typ = nullptr, *trn_tau = nullptr, *trn_eta = nullptr, *trn_mu = nullptr, *trn_logsum = nullptr;
     // tl_engine_score: the logits of one block of rows and the per-row targets / results, allocated on first use
     uint16_t *score_logits = nullptr;
     int32_t *score_ids = nullptr, *score_argmax = nullptr;
@@ -831,6 +845,98 @@ static void launch_logit_process(tl_engine *e, const uint16_t *logits, uint16_t 
     if (pc) prof_after(pc, 7, (int)(grid.x * grid.y));
 }
 
+// ---- per-slot truncation (truncate.h) -------------------------------------------------------------------------
+// does some live slot of [0, batch) truncate?  (its own plan-key bit.)  Truncation applies to a slot that samples: a greedy slot is never
+// filtered (every filter keeps the maximum), so its parameters do not change the plan.
+static bool step_truncates_slot(const tl_engine *e, int slot) {
+    return e->trn_mem && e->slot_runs(slot) && e->trn[slot].truncates() && e->smp[slot].samples();
+}
+static bool step_truncates(const tl_engine *e, int batch) {
+    for (int b = 0; b < batch; ++b)
+        if (step_truncates_slot(e, b)) return true;
+    return false;
+}
+// ... with Mirostat?  Its update launch reads the token the step end has just stored -- a plain store, which only a launch boundary
+// with cache maintenance hands over: such a plan keeps the hipGraphLaunch route (tl_engine_replay_route says so)
+static bool step_mirostat(const tl_engine *e, int batch) {
+    for (int b = 0; b < batch; ++b)
+        if (step_truncates_slot(e, b) && e->trn[b].mirostat()) return true;
+    return false;
+}
+
+// the filtered rows, the per-slot parameters and the per-row log-sums: one allocation, made by the first call that makes a slot truncate
+static int trn_alloc(tl_engine *e) {
+    if (e->trn_mem) return TL_OK;
+    const size_t B = (size_t)e->cfg.max_batch, R = std::max<size_t>(B, 8), V = (size_t)e->cfg.vocab_size;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return at;
+    };
+    const size_t o_rows = carve(R * V * 2), o_minp = carve(B * 4), o_tau = carve(B * 4), o_eta = carve(B * 4), o_sum = carve(R * 4), o_typ = carve(B * 4),
+                 o_mu = carve(B * 4);
+    char *m = nullptr;
+    if (hipMalloc((void **)&m, off) != hipSuccess) return fail(TL_ERR_HIP, "engine: hipMalloc(truncation) failed");
+    // zero (min-p, tau, eta off) up to the typical-p array; typical-p and mu: all ones, a NaN (typical-p off, no Mirostat)
+    if (hipMemsetAsync(m, 0, o_typ, e->stream) != hipSuccess || hipMemsetAsync(m + o_typ, 0xff, off - o_typ, e->stream) != hipSuccess) {
+        (void)hipFree(m);
+        return fail(TL_ERR_HIP, "engine: memset(truncation) failed");
+    }
+    e->trn_mem = m;
+    e->trn_rows = (uint16_t *)(m + o_rows);
+    e->trn_minp = (float *)(m + o_minp), e->trn_typ = (float *)(m + o_typ), e->trn_tau = (float *)(m + o_tau), e->trn_eta = (float *)(m + o_eta);
+    e->trn_mu = (float *)(m + o_mu), e->trn_logsum = (float *)(m + o_sum);
+    e->stats.workspace_bytes += off;
+    return TL_OK;
+}
+
+// the slot's parameters become `v` (validated by the caller): the device copy follows the host mirror, stream-ordered between steps.
+// restart_mu: mu becomes 2 tau (NaN without Mirostat); move / fork copy the source's mu behind this call instead
+static int trn_write(tl_engine *e, int slot, const tl_engine::TruncParams &v, bool restart_mu = true) {
+    if (!e->trn_mem && !v.truncates()) {  // an engine that never truncated: nothing to write
+        e->trn[slot] = v;
+        return TL_OK;
+    }
+    TL_TRY(trn_alloc(e));
+    std::vector<std::pair<int32_t *, int32_t>> pk;
+    pk.emplace_back((int32_t *)(e->trn_minp + slot), __builtin_bit_cast(int32_t, v.min_p));
+    pk.emplace_back((int32_t *)(e->trn_typ + slot), __builtin_bit_cast(int32_t, v.typical_p));
+    pk.emplace_back((int32_t *)(e->trn_tau + slot), __builtin_bit_cast(int32_t, v.tau));
+    pk.emplace_back((int32_t *)(e->trn_eta + slot), __builtin_bit_cast(int32_t, v.eta));
+    if (restart_mu) pk.emplace_back((int32_t *)(e->trn_mu + slot), v.mirostat() ? __builtin_bit_cast(int32_t, 2.f * v.tau) : (int32_t)0x7fc00000);
+    e->trn[slot] = v;
+    return poke(e, pk);
+}
+static int trn_reset(tl_engine *e, int slot) {
+    const tl_engine::TruncParams d{};
+    const tl_engine::TruncParams &c = e->trn[slot];
+    if (c.min_p == d.min_p && c.typical_p == d.typical_p && c.tau == d.tau && c.eta == d.eta) return TL_OK;
+    return trn_write(e, slot, d);
+}
+// tl_engine_move (move = true) / tl_engine_fork: dst takes src's parameters and mu; a move leaves src at the defaults
+static int trn_carry(tl_engine *e, int src, int dst, bool move) {
+    if (!e->trn[src].truncates() && !e->trn[dst].truncates()) return TL_OK;
+    const tl_engine::TruncParams v = e->trn[src];
+    TL_TRY(trn_write(e, dst, v, false));
+    if (e->trn_mem) TL_HIP(hipMemcpyAsync(e->trn_mu + dst, e->trn_mu + src, sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+    return move ? trn_reset(e, src) : TL_OK;
+}
+
+// the truncation launch over `rows` rows for slots slot0 .. (the rows the choice would be made from -> filtered rows into `out`), and the
+// Mirostat update launch behind the step end; `row0`: the index of the first row inside the engine's row buffers
+static void launch_truncate(tl_engine *e, const uint16_t *rows_in, uint16_t *out, int rows, int slot0, int row0, ProfCtx *pc) {
+    const TruncateArgs a{rows_in, out, e->cfg.vocab_size, slot0, e->smp_temp, e->trn_minp, e->trn_typ, e->trn_mu, e->trn_logsum + row0, pc ? pc->buf : nullptr};
+    hipLaunchKernelGGL(truncate_rows_kernel, dim3(rows), dim3(1024), 0, e->stream, a);
+    if (pc) prof_after(pc, 7, rows);
+}
+static void launch_mirostat_update(tl_engine *e, const uint16_t *filtered, int rows, int slot0, int row0, ProfCtx *pc) {
+    const MirostatUpdateArgs a{filtered, e->cfg.vocab_size, slot0, e->tokens, e->smp_temp, e->trn_logsum + row0, e->trn_tau, e->trn_eta, e->trn_mu, e->live,
+                               pc ? pc->buf : nullptr};
+    hipLaunchKernelGGL(mirostat_update_kernel, dim3(rows), dim3(64), 0, e->stream, a);
+    if (pc) prof_after(pc, 7, rows);
+}
+
 // Context split of the decode attention: power-of-two bucket >= context, fixed windows of C tokens per workgroup.
 struct SplitPlan {
     int n_splits, tokens_per_split;
@@ -1218,11 +1324,20 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, ProfCtx *pc = nul
     // are copied), and the step end chooses from those; the lm_head's tile maxima describe the raw rows and are not used
     const bool processes = step_processes(e, batch);
     if (processes) launch_logit_process(e, e->logits, e->pen_rows, batch, 0, e->tokens, pc);
-    const bool tile_max = rh.maxima_rows == batch && !processes;
-    const StepEndArgs s = step_end_args(e, processes ? e->pen_rows : e->logits, 0, 1, e->x, tile_max ? e->lm_tile_max : nullptr,
+    // a plan in which some live slot truncates (truncate.h): one more launch filters the rows the choice would be made from into rows of
+    // their own (rows of other slots are copied), the step end chooses from those, and the Mirostat update runs behind it
+    const bool truncates = step_truncates(e, batch);
+    const uint16_t *choice = processes ? e->pen_rows : e->logits;
+    if (truncates) {
+        launch_truncate(e, choice, e->trn_rows, batch, 0, 0, pc);
+        choice = e->trn_rows;
+    }
+    const bool tile_max = rh.maxima_rows == batch && !processes && !truncates;
+    const StepEndArgs s = step_end_args(e, choice, 0, 1, e->x, tile_max ? e->lm_tile_max : nullptr,
                                         tile_max ? e->head().rows / 16 : 0, e->ss_x, pc ? pc->buf : nullptr);
-    launch_step_end(e, s, batch, step_samples(e, batch), step_logprobs(e, batch), processes ? e->logits : nullptr);
+    launch_step_end(e, s, batch, step_samples(e, batch), step_logprobs(e, batch), processes || truncates ? e->logits : nullptr);
     if (pc) prof_after(pc, 7, batch);
+    if (truncates) launch_mirostat_update(e, e->trn_rows, batch, 0, 0, pc);
     TL_CHECK_LAUNCH("engine step end");
     return TL_OK;
 }
@@ -1291,6 +1406,7 @@ static int settings_reset(tl_engine *e, int slot) {
     e->emb_rows[slot] = -1;
     TL_TRY(lp_write(e, slot, -1));
     TL_TRY(pen_reset(e, slot));
+    TL_TRY(trn_reset(e, slot));
     return smp_reset(e, slot);
 }
 // fork / move (move = true): dst takes what src has, and a move leaves src at the defaults
@@ -1309,8 +1425,10 @@ static int settings_carry(tl_engine *e, int src, int dst, bool move) {
     }
     // ... the log-probability setting with the pending token's record (the record ring restarts, like the token ring)
     TL_TRY(lp_carry(e, src, dst, move));
-    // ... and the penalties, the bias list, the history and the grammar's state
-    return pen_carry(e, src, dst, move);
+    // ... the penalties, the bias list, the history and the grammar's state
+    TL_TRY(pen_carry(e, src, dst, move));
+    // ... and the truncation parameters with Mirostat's mu
+    return trn_carry(e, src, dst, move);
 }
 
 }  // namespace tl
@@ -1664,6 +1782,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->table.init(c.max_batch, c.num_pages, c.page_size, c.max_pages_per_seq);  // (the pool hands out 0, 1, 2, ...)
     e->smp.assign(c.max_batch, tl_engine::SampleParams{});
     e->pen.assign(c.max_batch, tl_engine::PenaltyParams{});
+    e->trn.assign(c.max_batch, tl_engine::TruncParams{});
     e->gr_pending.assign(c.max_batch, 0);
     e->emb_rows.assign(c.max_batch, -1);
     e->stats.kv_bytes = e->kv_bytes;
@@ -1766,6 +1885,7 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     if (e->smp_mem) (void)hipFree(e->smp_mem);
     if (e->lp_mem) (void)hipFree(e->lp_mem);
     if (e->pen_mem) (void)hipFree(e->pen_mem);
+    if (e->trn_mem) (void)hipFree(e->trn_mem);
     if (e->gr_mem) (void)hipFree(e->gr_mem);
     if (e->gr_stack) (void)hipFree(e->gr_stack);
     if (e->kv_pools_dev) (void)hipFree(e->kv_pools_dev);
@@ -1797,6 +1917,8 @@ extern "C" const char *tl_engine_replay_route(const tl_engine *e) {
     static thread_local std::string text;
     if (!e) return "";
     text = e->aql_on ? std::string("aql") : ("hipgraph" + (e->aql_why.empty() ? std::string() : ": " + e->aql_why));
+    // (a plan with a Mirostat slot keeps hipGraphLaunch on an engine whose other plans ride the route: step_mirostat)
+    if (e->aql_on && step_mirostat(e, e->cfg.max_batch)) text = "hipgraph: a Mirostat slot is live (the update launch reads the token the step end stored)";
     return text.c_str();
 }
 
@@ -1844,6 +1966,7 @@ extern "C" int tl_engine_release(tl_engine *e, int slot) {
 extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
     TL_TRY(slot_check_unparked(e, slot));
     TL_REQUIRE(!e->pen[slot].processes(), "engine_rewind: the slot processes its logits (its history would keep the dropped tokens; make it neutral first)");
+    TL_REQUIRE(!e->trn[slot].mirostat(), "engine_rewind: the slot has Mirostat on (mu would no longer belong to the tokens held; switch it off first)");
     SlotEdits ed;
     Pokes pk;
     TL_TRY(table_rc(e->table.rewind(slot, n, ed)));
@@ -2150,6 +2273,7 @@ extern "C" int tl_engine_set_token(tl_engine *e, int slot, int32_t token) {
     TL_TRY(slot_check(e, slot, true));
     TL_REQUIRE(token >= 0 && token < e->cfg.vocab_size, "engine_set_token: token id out of range");
     TL_REQUIRE(!e->pen[slot].processes(), "engine_set_token: the slot processes its logits (its history counts the tokens the engine produced; make it neutral first)");
+    TL_REQUIRE(!e->trn[slot].mirostat(), "engine_set_token: the slot has Mirostat on (mu would no longer belong to the tokens held; switch it off first)");
     std::vector<std::pair<int32_t *, int32_t>> pk;
     pk.emplace_back(e->tokens + slot, token);
     return poke(e, pk);
@@ -2166,7 +2290,75 @@ extern "C" int tl_engine_set_sampling(tl_engine *e, int slot, float temperature,
     v.top_k = top_k >= e->cfg.vocab_size ? 0 : top_k;  // beyond the vocabulary: no top-k
     v.top_p = top_p > 0.f && top_p < 1.f ? top_p : 0.f;  // outside (0, 1): no top-p
     v.seed = seed;
+    TL_REQUIRE(!e->trn[slot].mirostat() || (v.top_k == 0 && v.top_p == 0.f), "engine_set_sampling: the slot has Mirostat on, which excludes top-k and top-p");
     return smp_write(e, slot, v);
+}
+
+extern "C" int tl_engine_set_truncation(tl_engine *e, int slot, float min_p, float typical_p) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(min_p >= 0.f && min_p <= 1.f, "engine_set_truncation: min_p must be in [0, 1] (0 = off)");
+    TL_REQUIRE(!std::isnan(typical_p), "engine_set_truncation: typical_p is NaN");
+    TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_set_truncation: vocabulary larger than the sampler's 524,288 tokens");
+    tl_engine::TruncParams v = e->trn[slot];
+    v.min_p = min_p;
+    v.typical_p = typical_p > 0.f && typical_p < 1.f ? typical_p : 1.f;  // outside (0, 1): off
+    TL_REQUIRE(!v.mirostat() || !v.stateless(), "engine_set_truncation: the slot has Mirostat on, which excludes min-p and typical-p");
+    return trn_write(e, slot, v, false);
+}
+
+extern "C" int tl_engine_set_mirostat(tl_engine *e, int slot, float tau, float eta) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(std::isfinite(tau) && tau >= 0.f, "engine_set_mirostat: tau must be finite and >= 0 (0 = off)");
+    TL_REQUIRE(tau == 0.f || (eta > 0.f && eta <= 1.f), "engine_set_mirostat: eta must be in (0, 1]");
+    TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_set_mirostat: vocabulary larger than the sampler's 524,288 tokens");
+    tl_engine::TruncParams v = e->trn[slot];
+    if (tau > 0.f) {
+        TL_REQUIRE(!v.stateless() && e->smp[slot].top_k == 0 && e->smp[slot].top_p == 0.f,
+                   "engine_set_mirostat: Mirostat excludes every other truncation of the slot (top-k, top-p, min-p, typical-p)");
+    }
+    v.tau = tau, v.eta = tau > 0.f ? eta : 0.f;
+    return trn_write(e, slot, v);  // mu restarts at 2 tau
+}
+
+extern "C" int tl_engine_mirostat_mu(tl_engine *e, int slot, float *mu) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(mu, "engine_mirostat_mu: null argument");
+    *mu = __builtin_nanf("");
+    if (!e->trn_mem) return TL_OK;
+    TL_HIP(hipStreamSynchronize(e->stream));
+    TL_HIP(hipMemcpy(mu, e->trn_mu + slot, sizeof(float), hipMemcpyDeviceToHost));
+    return TL_OK;
+}
+
+extern "C" int tl_engine_copy_filtered_logits(tl_engine *e, void *dst_dev, int rows) {
+    TL_REQUIRE(e && dst_dev, "engine_copy_filtered_logits: null argument");
+    TL_REQUIRE(rows > 0 && rows <= e->cfg.max_batch, "engine_copy_filtered_logits: rows out of range");
+    TL_REQUIRE(e->trn_rows, "engine_copy_filtered_logits: no slot of this engine has truncated yet");
+    TL_HIP(hipMemcpyAsync(dst_dev, e->trn_rows, (size_t)rows * e->cfg.vocab_size * 2, hipMemcpyDeviceToDevice, e->stream));
+    return TL_OK;
+}
+
+extern "C" int tl_truncate_rows(const void *logits_dev, int rows, int vocab, const float *temperature_dev, const float *min_p_dev, const float *typical_p_dev,
+                                const float *mu_dev, void *out_dev, float *kept_logsum_dev, void *stream) {
+    TL_REQUIRE(logits_dev && temperature_dev && min_p_dev && typical_p_dev && mu_dev && out_dev, "truncate_rows: null argument");
+    TL_REQUIRE(logits_dev != out_dev, "truncate_rows: rows are never filtered in place");
+    TL_REQUIRE(rows > 0 && rows <= 65535, "truncate_rows: rows out of range");
+    TL_REQUIRE(vocab > 0 && vocab <= SMP_MAX_VOCAB, "truncate_rows: vocabulary out of range (1 .. 524,288)");
+    const TruncateArgs a{(const uint16_t *)logits_dev, (uint16_t *)out_dev, vocab, 0, temperature_dev, min_p_dev, typical_p_dev, mu_dev, kept_logsum_dev, nullptr};
+    hipLaunchKernelGGL(truncate_rows_kernel, dim3(rows), dim3(1024), 0, (hipStream_t)stream, a);
+    TL_CHECK_LAUNCH("truncate_rows");
+    return TL_OK;
+}
+
+extern "C" int tl_mirostat_update_rows(const void *filtered_dev, int rows, int vocab, const int32_t *ids_dev, const float *temperature_dev,
+                                       const float *kept_logsum_dev, const float *tau_dev, const float *eta_dev, float *mu_dev, void *stream) {
+    TL_REQUIRE(filtered_dev && ids_dev && temperature_dev && kept_logsum_dev && tau_dev && eta_dev && mu_dev, "mirostat_update_rows: null argument");
+    TL_REQUIRE(rows > 0 && rows <= 65535, "mirostat_update_rows: rows out of range");
+    TL_REQUIRE(vocab > 0 && vocab <= SMP_MAX_VOCAB, "mirostat_update_rows: vocabulary out of range (1 .. 524,288)");
+    const MirostatUpdateArgs a{(const uint16_t *)filtered_dev, vocab, 0, ids_dev, temperature_dev, kept_logsum_dev, tau_dev, eta_dev, mu_dev, nullptr, nullptr};
+    hipLaunchKernelGGL(mirostat_update_kernel, dim3(rows), dim3(64), 0, (hipStream_t)stream, a);
+    TL_CHECK_LAUNCH("mirostat_update_rows");
+    return TL_OK;
 }
 
 extern "C" int tl_engine_set_penalties(tl_engine *e, int slot, float repetition_penalty, float presence_penalty, float frequency_penalty) {
@@ -2654,7 +2846,16 @@ static int prefill_first_token(tl_engine *e, int slot, const uint16_t *logits, c
         launch_logit_process(e, logits, out, 1, slot, nullptr, nullptr);
         raw = logits, logits = out;
     }
+    const bool truncates = step_truncates_slot(e, slot);
+    const int row0 = (int)(((raw ? raw : logits) - e->logits) / e->cfg.vocab_size);
+    if (truncates) {  // ... and filtered (truncate.h), into the row of the same index again
+        uint16_t *out = e->trn_rows + (size_t)row0 * e->cfg.vocab_size;
+        launch_truncate(e, logits, out, 1, slot, row0, nullptr);
+        if (!raw) raw = logits;
+        logits = out;
+    }
     launch_step_end(e, step_end_args(e, logits, slot, 0, e->h), 1, e->smp[slot].samples(), step_logprobs_slot(e, slot), raw);
+    if (truncates) launch_mirostat_update(e, logits, 1, slot, row0, nullptr);
     TL_CHECK_LAUNCH(what);
     e->table.slots[slot].produced += 1;
     e->gr_pending[slot] = 1;
@@ -2981,6 +3182,7 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
     TL_CHECK_LAUNCH("engine embed");
     const bool samples = step_samples(e, batch), logprobs = step_logprobs(e, batch), processes = step_processes(e, batch);
     const bool grammar = processes && step_grammar(e, batch), stack_grammar = grammar && step_stack_grammar(e, batch);
+    const bool truncates = step_truncates(e, batch), mirostat = truncates && step_mirostat(e, batch);
     bool on_queue = false;  // steps of this call are in flight on the AQL queue (the stream is idle and must stay so until they are drained)
     for (int s = 0; s < steps; ++s) {
         SplitPlan sp;
@@ -2991,7 +3193,10 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
             // bit 60: the processing launch (logit_process.h) stands between the lm_head and the step end
             // bit 59: ... and it is the grammar twin (grammar.h); bit 58: the stack-grammar twin (grammar_stack.h)
             const auto key = std::make_pair(batch, sp.key() | (samples ? (1L << 62) : 0L) | (logprobs ? (1L << 61) : 0L) | (processes ? (1L << 60) : 0L) |
-                                                       (grammar ? (1L << 59) : 0L) | (stack_grammar ? (1L << 58) : 0L));
+                                                       (grammar ? (1L << 59) : 0L) | (stack_grammar ? (1L << 58) : 0L) |
+                                                       // bit 57: the truncation launch (truncate.h) stands ahead of the step end and the Mirostat update behind
+                                                       // it; bit 56: ... and a slot has Mirostat on (the plan keeps the hipGraphLaunch route: step_mirostat)
+                                                       (truncates ? (1L << 57) : 0L) | (mirostat ? (1L << 56) : 0L));
             auto it = e->graphs.find(key);
             if (it == e->graphs.end()) {
                 // The split plan (and with it the key) changes every 64 * n_splits tokens of context: a long run would keep one
@@ -3020,7 +3225,8 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
                 hipGraphExec_t exec = nullptr;
                 const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
                 if (ie == hipSuccess && e->aql_on && !e->step_written_once) e->aql_why = "a hand-over of this plan lives in a shared buffer (written more than once per step)";
-                if (ie == hipSuccess && e->aql_on && e->step_written_once) {  // the same nodes as packet templates (aql.h); a plan that cannot be built keeps the graph route
+                if (ie == hipSuccess && e->aql_on && e->step_written_once && mirostat) e->aql_why = "a Mirostat slot is live (the update launch reads the token the step end stored)";
+                if (ie == hipSuccess && e->aql_on && e->step_written_once && !mirostat) {  // the same nodes as packet templates (aql.h); a plan that cannot be built keeps the graph route
                     auto prog = std::make_unique<AqlProgram>();
                     if (aql_program_from_graph(*e->aql_rt, graph, e->stream, *prog, e->aql_why) == 0) e->aql_programs[key] = std::move(prog);
                 }

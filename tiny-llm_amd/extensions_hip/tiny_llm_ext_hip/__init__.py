@@ -231,6 +231,12 @@ _SIGNATURES.update({
     "tl_engine_set_penalties": (_c_int, [_c_void_p, _c_int, _c_float, _c_float, _c_float]),
     "tl_engine_set_logit_bias": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _P(_c_float), _c_int]),
     "tl_process_logits": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 9),
+    "tl_engine_set_truncation": (_c_int, [_c_void_p, _c_int, _c_float, _c_float]),
+    "tl_engine_set_mirostat": (_c_int, [_c_void_p, _c_int, _c_float, _c_float]),
+    "tl_engine_mirostat_mu": (_c_int, [_c_void_p, _c_int, _P(_c_float)]),
+    "tl_engine_copy_filtered_logits": (_c_int, [_c_void_p, _c_void_p, _c_int]),
+    "tl_truncate_rows": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 7),
+    "tl_mirostat_update_rows": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 7),
     "tl_vocab_create": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p, _P(_c_void_p)]),
     "tl_vocab_destroy": (None, [_c_void_p]),
     "tl_grammar_create": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _P(_c_void_p)]),
@@ -1111,6 +1117,48 @@ def process_logits(logits: torch.Tensor, history: torch.Tensor, repetition=1.0, 
     check(_lib.tl_process_logits(logits.data_ptr(), rows, vocab, history.data_ptr(), r_t.data_ptr(), p_t.data_ptr(), f_t.data_ptr(),
                                  ids_t.data_ptr(), vals_t.data_ptr(), n_t.data_ptr(), out.data_ptr(), _stream()))
     return out
+
+
+def _rows_f32(v, rows: int, dev, what: str) -> torch.Tensor:
+    t = torch.as_tensor(v, dtype=torch.float32).reshape(-1)
+    if t.numel() == 1:
+        t = t.expand(rows)
+    if t.numel() != rows:
+        raise ValueError(f"{what} needs one value per row")
+    return t.contiguous().to(dev)
+
+
+def truncate_rows(logits: torch.Tensor, temperature, min_p=0.0, typical_p=1.0, mu=float("nan")):
+    """The decode engine's truncation (tl_truncate_rows) over rows of bf16 logits [rows, vocab]: per-row temperature, min_p (0 = off),
+    typical_p (outside (0, 1) = off) and Mirostat's mu (NaN = no Mirostat; a Mirostat row ignores the other two), each a scalar or one
+    value per row.  Returns (filtered rows [rows, vocab] bf16, kept log-sums float32 [rows]: ln sum_kept exp(x / T) of a Mirostat row)."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("truncate_rows takes a [rows, vocab] bf16 tensor on the GPU")
+    logits = logits.contiguous()
+    rows, dev = logits.shape[0], logits.device
+    t_t, m_t, y_t, mu_t = (_rows_f32(v, rows, dev, "a truncation parameter") for v in (temperature, min_p, typical_p, mu))
+    out = torch.empty_like(logits)
+    logsum = torch.empty(rows, dtype=torch.float32, device=dev)
+    check(_lib.tl_truncate_rows(logits.data_ptr(), rows, logits.shape[1], t_t.data_ptr(), m_t.data_ptr(), y_t.data_ptr(), mu_t.data_ptr(),
+                                out.data_ptr(), logsum.data_ptr(), _stream()))
+    return out, logsum
+
+
+def mirostat_update_rows(filtered: torch.Tensor, ids, temperature, kept_logsum: torch.Tensor, tau, eta, mu) -> torch.Tensor:
+    """Mirostat's update (tl_mirostat_update_rows) for the tokens ``ids`` [rows] chosen from the filtered rows of truncate_rows and
+    their kept log-sums: returns the new mu float32 [rows] (``mu`` itself is not changed)."""
+    if filtered.dtype != torch.bfloat16 or filtered.dim() != 2 or not filtered.is_cuda:
+        raise ValueError("mirostat_update_rows takes a [rows, vocab] bf16 tensor on the GPU")
+    filtered = filtered.contiguous()
+    rows, dev = filtered.shape[0], filtered.device
+    ids_t = torch.as_tensor(ids, dtype=torch.int32).reshape(-1).contiguous().to(dev)
+    if ids_t.numel() != rows or kept_logsum.dtype != torch.float32 or kept_logsum.numel() != rows or not kept_logsum.is_cuda:
+        raise ValueError("ids and kept_logsum (float32, on the GPU) need one value per row")
+    t_t, tau_t, eta_t = (_rows_f32(v, rows, dev, "a Mirostat parameter") for v in (temperature, tau, eta))
+    mu_t = _rows_f32(mu, rows, dev, "mu").clone()
+    check(_lib.tl_mirostat_update_rows(filtered.data_ptr(), rows, filtered.shape[1], ids_t.data_ptr(), t_t.data_ptr(), kept_logsum.contiguous().data_ptr(),
+                                       tau_t.data_ptr(), eta_t.data_ptr(), mu_t.data_ptr(), _stream()))
+    return mu_t
 
 
 def logit_bias_arg(bias, vocab: int) -> tuple[list[int], list[float]]:

@@ -306,6 +306,27 @@ class DecodeEngine:
         (1, 0, 0) forget it.  begin / release make the slot neutral, move carries everything along, fork copies it."""
         _ext.check(_lib.tl_engine_set_penalties(self._h, slot, *penalty_args(repetition, presence, frequency)))
 
+    def set_truncation(self, slot: int, min_p: float = 0.0, typical_p: float = 1.0) -> None:
+        """Per-slot min-p and locally typical sampling on the device (tl_engine_set_truncation): every row a SAMPLING slot chooses a
+        token from is first filtered -- min-p keeps p_i >= min_p * p_max (0 = off), typical-p the tokens whose surprise is closest to
+        the entropy until their mass reaches typical_p (1 = off), ties with the boundary included -- and the sampler (with the slot's
+        top-k / top-p) runs on the filtered row.  begin / release reset, move carries, fork copies.  Refused on a Mirostat slot."""
+        m, y, _, _ = truncation_args(min_p, typical_p)
+        _ext.check(_lib.tl_engine_set_truncation(self._h, slot, m, y))
+
+    def set_mirostat(self, slot: int, tau: float, eta: float = 0.1) -> None:
+        """Mirostat v2 on the device (tl_engine_set_mirostat): tokens whose surprise -log2 p exceeds the slot's state mu are dropped,
+        and after every draw mu <- mu - eta (s - tau); mu starts at 2 tau with this call.  tau 0 switches it off.  Mirostat excludes
+        top-k, top-p, min-p and typical-p on the slot (ValueError / RuntimeError for the call that would combine them)."""
+        _, _, t, h = truncation_args(mirostat_tau=tau, mirostat_eta=eta)
+        _ext.check(_lib.tl_engine_set_mirostat(self._h, slot, t, h))
+
+    def mirostat_mu(self, slot: int) -> float:
+        """The slot's Mirostat state mu (tl_engine_mirostat_mu; NaN without Mirostat); synchronises."""
+        mu = ctypes.c_float()
+        _ext.check(_lib.tl_engine_mirostat_mu(self._h, slot, ctypes.byref(mu)))
+        return float(mu.value)
+
     def set_logit_bias(self, slot: int, bias) -> None:
         """The slot's logit bias (tl_engine_set_logit_bias): a mapping {token id: value} of at most 1,024 entries added to the logits
         before the choice (-inf bans a token, a large value forces it); None or {} clears the list.  A call replaces the whole list."""
@@ -507,6 +528,16 @@ class DecodeEngine:
         self.synchronize()
         return out
 
+    def filtered_logits(self, rows: int = 1) -> torch.Tensor:
+        """A copy of the filtered rows [rows, vocab] (bf16) of the last decode step in which some slot truncated
+        (tl_engine_copy_filtered_logits): row i is what slot i's token was drawn from -- kept tokens with their bits, the others -inf;
+        the row of a slot that does not truncate is its processed or raw row."""
+        out = torch.empty((rows, self.vocab_size), dtype=torch.bfloat16, device=self.device)
+        torch.cuda.current_stream().synchronize()
+        _ext.check(_lib.tl_engine_copy_filtered_logits(self._h, out.data_ptr(), rows))
+        self.synchronize()
+        return out
+
     def synchronize(self) -> None:
         _ext.check(_lib.tl_engine_synchronize(self._h))
 
@@ -545,14 +576,18 @@ class DecodeEngine:
     def generate(self, prompt: Sequence[int], max_new_tokens: int, *, slot: int = 0, chunk: int | None = None,
                  temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None, seed: int = 0,
                  logprobs: int | None = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                 frequency_penalty: float = 0.0, logit_bias=None, grammar: "Grammar | None" = None):
+                 frequency_penalty: float = 0.0, logit_bias=None, grammar: "Grammar | None" = None, min_p: float = 0.0,
+                 typical_p: float = 1.0, mirostat_tau: float = 0.0, mirostat_eta: float = 0.1):
         """One request: prefill, then ``max_new_tokens - 1`` decode steps in one call; greedy unless ``temperature`` > 0 (the
         device sampler, set_sampling).  With ``logprobs`` an int (0 .. 20 alternatives, set_logprobs): returns (ids, records).
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` (set_penalties, set_logit_bias) are set
         before the prefill, so the prompt's tokens are in the slot's history; so is ``grammar`` (set_grammar): the ids are then text of
-        its language, followed by EOS ids once it has ended.  On an engine with the prefix cache on, the slot first attaches the cached
+        its language, followed by EOS ids once it has ended.  ``min_p`` / ``typical_p`` (set_truncation) and ``mirostat_tau`` /
+        ``mirostat_eta`` (set_mirostat) filter the rows a sampling request draws from; Mirostat excludes top_k, top_p, min_p and
+        typical_p (ValueError).  On an engine with the prefix cache on, the slot first attaches the cached
         prefix of the prompt (prefix_attach) and prefills the rest, and declares the answer before its release (prefix_extend)."""
         args = sampling_args(temperature, top_k, top_p, seed)
+        trn = truncation_args(min_p, typical_p, mirostat_tau, mirostat_eta, top_k=args[1], top_p=args[2])
         top_n = logprobs_arg(logprobs)
         pen = penalty_args(repetition_penalty, presence_penalty, frequency_penalty)
         bias = _ext.logit_bias_arg(logit_bias, self.vocab_size)
@@ -566,6 +601,7 @@ class DecodeEngine:
                 self.set_grammar(slot, grammar)
             if args[0] > 0.0:
                 self.set_sampling(slot, *args)
+            apply_truncation(self, slot, trn)
             if top_n >= 0:
                 self.set_logprobs(slot, top_n)
             prompt = [int(t) for t in prompt]
@@ -619,6 +655,29 @@ def sampling_args(temperature: float = 0.0, top_k: int | None = None, top_p: flo
     if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
         raise ValueError(f"seed must be an int in [0, 2**64), got {seed!r}")
     return float(temperature), min(int(top_k), 2**31 - 1), float(top_p), int(seed)
+
+
+def truncation_args(min_p: float = 0.0, typical_p: float | None = 1.0, mirostat_tau: float = 0.0, mirostat_eta: float = 0.1, *,
+                    top_k: int = 0, top_p: float = 1.0) -> tuple[float, float, float, float]:
+    """Validated (min_p, typical_p, tau, eta) for tl_engine_set_truncation / tl_engine_set_mirostat: min_p in [0, 1] (0 = off),
+    typical_p None or in (0, 1] (1 = off), mirostat_tau finite and >= 0 (0 = off), mirostat_eta in (0, 1].  Mirostat excludes every
+    other truncation: with tau > 0, min_p, typical_p and the request's ``top_k`` / ``top_p`` (as sampling_args returns them) must be off."""
+    if typical_p is None:
+        typical_p = 1.0
+    for name, v in (("min_p", min_p), ("typical_p", typical_p), ("mirostat_tau", mirostat_tau), ("mirostat_eta", mirostat_eta)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+    if not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"min_p must be in [0, 1], got {min_p!r}")
+    if not 0.0 < typical_p <= 1.0:
+        raise ValueError(f"typical_p must be None or in (0, 1], got {typical_p!r}")
+    if mirostat_tau < 0:
+        raise ValueError(f"mirostat_tau must be >= 0, got {mirostat_tau!r}")
+    if not 0.0 < mirostat_eta <= 1.0:
+        raise ValueError(f"mirostat_eta must be in (0, 1], got {mirostat_eta!r}")
+    if mirostat_tau > 0 and (min_p > 0 or typical_p < 1 or top_k > 0 or top_p < 1):
+        raise ValueError("Mirostat excludes every other truncation (top_k, top_p, min_p, typical_p)")
+    return float(min_p), float(typical_p), float(mirostat_tau), float(mirostat_eta) if mirostat_tau > 0 else 0.0
 
 
 GRAMMAR_END = -1  # TL_GRAMMAR_END
@@ -714,7 +773,7 @@ def penalty_args(repetition: float = 1.0, presence: float = 0.0, frequency: floa
     return float(repetition), float(presence), float(frequency)
 
 
-_SAMPLING_KEYS = {"temperature", "top_k", "top_p", "seed"}
+_SAMPLING_KEYS = {"temperature", "top_k", "top_p", "seed", "min_p", "typical_p", "mirostat_tau", "mirostat_eta"}  # (the last four: request_truncation)
 _PENALTY_KEYS = {"repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "grammar"}  # (grammar: request_grammars)
 
 
@@ -766,6 +825,29 @@ def request_sampling(sampling, n_prompts: int, base_seed: int = 0) -> list[tuple
     return out
 
 
+def apply_truncation(engine, slot: int, trn: tuple[float, float, float, float]) -> None:
+    """truncation_args' tuple on a slot; the defaults make no call."""
+    if trn[0] > 0.0 or trn[1] < 1.0:
+        engine.set_truncation(slot, trn[0], trn[1])
+    if trn[2] > 0.0:
+        engine.set_mirostat(slot, trn[2], trn[3])
+
+
+def request_truncation(sampling, n_prompts: int) -> list[tuple[float, float, float, float]] | None:
+    """The truncation keys of batch_generate_ids' ``sampling`` dicts -- min_p / typical_p / mirostat_tau / mirostat_eta -- per prompt as
+    truncation_args returns them (exclusivity against the same dict's top_k / top_p included); None when ``sampling`` is None."""
+    if sampling is None:
+        return None
+    dicts = [sampling] * n_prompts if isinstance(sampling, dict) else list(sampling)
+    out = []
+    for d in dicts:
+        if not isinstance(d, dict):
+            raise ValueError("sampling entries must be dicts")
+        _, k, p, _ = sampling_args(d.get("temperature", 0.0), d.get("top_k"), d.get("top_p"), 0)
+        out.append(truncation_args(d.get("min_p", 0.0), d.get("typical_p"), d.get("mirostat_tau", 0.0), d.get("mirostat_eta", 0.1), top_k=k, top_p=p))
+    return out
+
+
 # decode row counts used by the scheduler: exact up to 4 rows (fused GEMV), then the row-block sizes of the skinny matmul
 _DECODE_ROW_BUCKETS = (1, 2, 3, 4, 8, 16, 32, 48, 64, 96, 128, 192, 256)
 
@@ -783,7 +865,7 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     the last slot is the prefill staging slot.  Returns [(prompt_idx, generated ids)] in completion order.
     ``sampling``: None (greedy), one dict or one dict per prompt (request_sampling; the dicts also take repetition_penalty /
     presence_penalty / frequency_penalty / logit_bias, request_penalties, and ``grammar``: a Grammar, whose EOS ids then end the request
-    like ``eos_token_id``); applied when a request enters the staging slot,
+    like ``eos_token_id``; and min_p / typical_p / mirostat_tau / mirostat_eta, request_truncation); applied when a request enters the staging slot,
     and carried by the engine through its slot moves.  ``logprobs``: None, or an int (0 .. 20 alternatives): every request records
     its tokens' log-probabilities (set_logprobs), read in the same turn as the pending ids, and the result is
     [(prompt_idx, generated ids, records)].
@@ -793,7 +875,8 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     An engine built with ``swap_pages`` preempts under page pressure instead of failing with "KV page pool exhausted"
     (tiny_llm_hip.preempt): before a decode step the staging request is released and re-queued, or the running request admitted last
     is parked; parked requests resume oldest first, and nothing new is admitted while one is parked.  A request's ids do not depend on
-    being preempted beyond the usual row-bucket band (a step's arithmetic follows its row count)."""
+    being preempted beyond the usual row-bucket band (a step's arithmetic follows its row count) -- except that a Mirostat request
+    which is recomputed instead of unparked (the staging request that gives way) restarts its mu at 2 tau."""
     from .preempt import Preemption
     if batch_size <= 0 or prefill_step <= 0:
         raise ValueError("batch_size and prefill_step must be positive")
@@ -803,6 +886,7 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     per_request = request_sampling(sampling, len(prompts), base_seed)
     per_request_pen = None if sampling is None else request_penalties(sampling, len(prompts), engine.vocab_size)
     per_request_gr = request_grammars(sampling, len(prompts))
+    per_request_trn = request_truncation(sampling, len(prompts))
 
     def ends(req, token):  # the request's own EOS ids where it has a grammar
         return token == eos_token_id or (req["eos"] is not None and token in req["eos"])
@@ -830,6 +914,8 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                 live_slots.add(staging)
                 if per_request is not None and per_request[idx][0] > 0.0:
                     engine.set_sampling(staging, *per_request[idx])
+                if per_request_trn is not None:
+                    apply_truncation(engine, staging, per_request_trn[idx])
                 if per_request_pen is not None:
                     pen, bias = per_request_pen[idx]
                     if pen != (1.0, 0.0, 0.0):

@@ -10,7 +10,7 @@ import test_kernel_resources_cpu as T  # noqa: E402
 
 DEFAULT = ["qmv3_kernelILi1ELi4ELi4ELi1ELi0ELi5", "qmv3_kernelILi1ELi4ELi4ELi0ELi1ELi8", "qmv3_kernelILi1ELi4ELi4ELi2ELi1ELi8", "qmv3_kernelILi1ELi4ELi4ELi1ELi2ELi5",
            "qmv3_kernelILi1ELi8ELi8ELi0ELi1ELi10", "qmv3_kernelILi1ELi16ELi16", "attn_decode_fused_kernelILi8ELi4ELi1E", "attn_decode_fused_kernelILi8ELi4ELi4E",
-           "attn_merge_kernel", "attn_merge_cols_kernel", "step_end_kernel", "qmm3_kernelILi1E", "qmm3_kernelILi4ELi1E", "qmm3p_kernel", "qmm3_reduce_kernel",
+           "attn_merge_kernel", "attn_merge_cols_kernel", "step_end_kernel", "truncate_rows_kernel", "mirostat_update_kernel", "qmm3_kernelILi1E", "qmm3_kernelILi4ELi1E", "qmm3p_kernel", "qmm3_reduce_kernel",
            "paged_fa_bf16_d128_kernel", "qmm_mfma_kernel"]
 
 
