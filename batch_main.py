@@ -16,7 +16,7 @@ DEFAULT_PROMPTS = ["What is the capital of France?", "Where is New York City?", 
                    "What is the capital of China?", "Give me a short introduction to large language model."]
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--model", required=True)
     ap.add_argument("--batch-size", type=int, default=5)
@@ -52,6 +52,17 @@ def main(argv=None):
                     help="room for N KV pages in pinned host memory: under page pressure the youngest request is preempted (its K / V "
                          "swapped out, or its prefill redone) instead of the run failing with 'KV page pool exhausted' (default 0: off)")
     ap.add_argument("--prompts-file", default=None, help="one prompt per line (default: five built-in questions)")
+    ap.add_argument("--lora", action="append", default=[], metavar="DIR",
+                    help="a LoRA adapter directory (PEFT or mlx_lm layout; tiny_llm_hip.lora) to keep resident beside the frozen weights; "
+                         "repeat the flag for several adapters (up to 32), which then share decode steps")
+    ap.add_argument("--lora-assign", default="round-robin", choices=["round-robin", "first"],
+                    help="which request runs under which adapter: round-robin = request i under adapter i mod n; first = request 0 under "
+                         "the first adapter, every other request on the base model")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     from main import check_truncation_flags
 
@@ -86,6 +97,10 @@ def main(argv=None):
     stops = {tokenizer.eos_token_id}
     try:
         from tiny_llm_hip.grammar import cli_grammar
+        from tiny_llm_hip.lora import assign_adapters
+
+        if args.lora:
+            sampling["lora"] = assign_adapters(len(encoded), [engine.load_lora(d) for d in args.lora], args.lora_assign)
 
         grammar = cli_grammar(engine, tokenizer, args.regex, args.json, args.json_schema)
         if grammar is not None:

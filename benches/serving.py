@@ -159,6 +159,9 @@ def _preemption(engine):
 def _admit(engine, cached: bool, slot: int, request) -> dict:
     """The state of a request that has just begun in ``slot``: with the prefix cache on it starts behind the cached part of its prompt."""
     state = {"req": request, "offset": 0, "count": 0, "ctx": 0, "out": []}
+    lora = getattr(request, "lora", None)  # the id of a resident LoRA adapter (DecodeEngine.load_lora); such a request bypasses the prefix cache
+    if lora is not None and lora >= 0:
+        engine.set_lora(slot, lora)
     if cached and len(request.prompt_token_ids) > 0:
         state["offset"] = state["ctx"] = engine.prefix_attach(slot, request.prompt_token_ids)
     return state

@@ -588,6 +588,75 @@ int tl_engine_embed_packed(tl_engine *e, int n_seqs, const int *slots, const int
                            int normalize, int dim, float *out_host);
 int tl_engine_embed(tl_engine *e, int slot, const int32_t *tokens, int n, int finish, int pooling, int normalize, int dim, float *out_host);
 
+/* LoRA adapters: many fine-tunes over one resident base model, a different one per slot, mixed in one batch (csrc/lora.h; DESIGN.md
+ * section 4).  For an adapted projection with base weight W and an adapter (A [rank, in], B [out, rank], scale), all bf16, row-major, the
+ * PEFT orientation, and x the input as the base projection sees it (after the RMSNorm where the projection has one):
+ *     y = W x + scale * B (A x)     A x and B t accumulate in fp32, scale multiplies in fp32, rounding to bf16 only where a value is
+ *                                   stored: bf16(base + delta) for q, k, v, gate and up, bf16(residual + delta) ahead of the base
+ *                                   projection's residual epilogue for o and down.
+ * No float atomics, one summation order: a row's result does not depend on its slot, its neighbours or their adapters, and a slot without
+ * an adapter gets exactly the base result of the route it ran on.
+ *   load     tl_engine_lora_load copies the adapter into engine-owned device memory in the fused layouts of the base weights (qkv: the A of
+ *            q, k, v stacked, B block-wise; gate|up: the A of gate and up stacked, B rows interleaved like wgu); a target with a NULL pair
+ *            is not adapted and costs nothing.  rank a multiple of 8 up to TL_MAX_LORA_RANK, the same for all targets of one adapter and
+ *            free per adapter; scale finite; up to TL_MAX_LORA_ADAPTERS resident; *adapter receives the lowest free id.  A NULL A with a
+ *            non-NULL B (or the reverse), a layer without any target in every layer, a bad rank: TL_ERR_INVALID.  An MLP target (gate, up,
+ *            down) on a MoE layer: TL_ERR_UNSUPPORTED (attention targets there are fine).  The first load allocates the device table, the
+ *            per-slot ids and the workspaces; an engine that never loads an adapter allocates nothing.  Synchronises.
+ *   unload   TL_ERR_INVALID while a live or parked slot carries the adapter; the id is reused by a later load.  Synchronises.
+ *   slots    tl_engine_set_lora(e, slot, adapter): adapter -1 = none, or a resident id; only on a live slot whose context is 0 -- a
+ *            sequence's K/V are all computed under one adapter.  tl_engine_begin / tl_engine_release reset the slot to none,
+ *            tl_engine_move moves the id, tl_engine_fork copies it, park / unpark keep it.  tl_engine_slot_lora: the id, -1 = none
+ *            (also for a free slot).
+ *   decode   a step in which some live slot of [0, batch) carries an adapter is a plan of its own (bit 55 of the graph key): every
+ *            projection leaves complete bf16 rows in the shared buffers (no fragment-order hand-over, no kept slice planes, attention merges
+ *            its own windows, gate|up through the store epilogue), with the shrink / expand launches around them: 8 launches more per
+ *            layer.  Such a plan replays through hipGraphLaunch (tl_engine_replay_route says so while such a slot is live).  Every other
+ *            step is the program it was, launch for launch: loading, unloading or assigning an adapter re-captures nothing.
+ *   prefill  tl_engine_prefill, _prefill_packed, _verify, _score, _embed and _embed_packed: a pass in which some sequence carries an
+ *            adapter runs shrink / expand per adapted projection group over tiles of 16 rows that never straddle two sequences; a pass
+ *            without adapters is unchanged.
+ *   prefix cache  K/V depend on the adapter.  A slot with an adapter bypasses the cache: tl_engine_prefix_attach matches 0 tokens and
+ *            the slot's token ids are not recorded as known, so its pages are never indexed or retained.  PER-ADAPTER CACHING IS OUT OF
+ *            SCOPE; the cache's own semantics are unchanged.
+ * Not covered: adapters on the embedding / lm_head, DoRA, MLP targets on MoE layers. */
+#define TL_MAX_LORA_RANK 64
+#define TL_MAX_LORA_ADAPTERS 32
+enum { TL_LORA_Q, TL_LORA_K, TL_LORA_V, TL_LORA_O, TL_LORA_GATE, TL_LORA_UP, TL_LORA_DOWN, TL_LORA_TARGETS };
+typedef struct tl_lora_layer {
+    const void *a_dev[TL_LORA_TARGETS], *b_dev[TL_LORA_TARGETS]; /* A [rank, in], B [out, rank] bf16; NULL pair = not adapted */
+} tl_lora_layer;
+typedef struct tl_lora_stats {
+    int resident;              /* adapters loaded */
+    size_t bytes;              /* device bytes of their matrices */
+    long adapter_steps;        /* decode steps that ran the adapter plan */
+    long adapter_prefill_rows; /* rows of prefill passes that belonged to a sequence with an adapter */
+} tl_lora_stats;
+int tl_engine_lora_load(tl_engine *e, const tl_lora_layer *layers, int rank, float scale, int *adapter);
+int tl_engine_lora_unload(tl_engine *e, int adapter);
+int tl_engine_set_lora(tl_engine *e, int slot, int adapter);
+int tl_engine_slot_lora(const tl_engine *e, int slot);
+int tl_engine_lora_stats(const tl_engine *e, tl_lora_stats *out);
+
+/* The LoRA routine over caller rows (csrc/lora.h): x_dev [rows, in] bf16, one projection group of out columns.  row_adapter_dev [rows]
+ * int32 names each row's adapter (-1 = none) among adapters[n_adapters] (host array of device matrices in the FUSED layout: a_dev
+ * [rank * present segments, in], b_dev [out, rank]; seg_mask bit s = segment s is present).  seg_mode 0: one segment; 1: three blocks of
+ * columns [0, seg_end0), [seg_end0, seg_end1), [seg_end1, out) (q | k | v); 2: interleaved, column parity (gate | up).  Tiles: n_tiles = 0
+ * cuts the rows into blocks of 16 that look every row's adapter up; otherwise tile i is rows [tile_row0[i], + tile_rows[i] <= 16) with
+ * adapter tile_adapter[i] (-1 none, -2 = look up per row).  mode TL_LORA_ADD: out_dev [rows, out] += delta in place; TL_LORA_RESIDUAL_PRE:
+ * out_dev = bf16(base_or_residual_dev + delta); TL_LORA_SWIGLU: base_or_residual_dev holds interleaved gate|up rows [rows, out], out_dev
+ * [rows, out / 2].  norm_w_dev != NULL: x is the row BEFORE an RMSNorm of that weight and eps, applied inside.  Allocates its table and
+ * workspace per call and synchronises the stream: a test and measurement aid. */
+enum { TL_LORA_ADD = 0, TL_LORA_RESIDUAL_PRE = 1, TL_LORA_SWIGLU = 2 };
+typedef struct tl_lora_matrices {
+    const void *a_dev, *b_dev;
+    int rank, seg_mask;
+    float scale;
+} tl_lora_matrices;
+int tl_lora_rows(const void *x_dev, int rows, int in, int out, const int32_t *row_adapter_dev, const tl_lora_matrices *adapters, int n_adapters,
+                 int seg_mode, int seg_end0, int seg_end1, const int *tile_row0, const int *tile_rows, const int *tile_adapter, int n_tiles, int mode,
+                 const void *base_or_residual_dev, void *out_dev, const void *norm_w_dev, float eps, void *stream);
+
 /* Run `steps` decode steps over the live slots [0, batch): each step feeds every
  * slot's pending token at position context_len, appends K/V, and leaves the next
  * token as the next pending token: the argmax, or, for a slot with a nonzero

@@ -60,6 +60,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --solution engine (greedy or device sampling): print each generated token with its log-probability "
                          "and its N (0-20) most likely alternatives")
     ap.add_argument("--proposal-length", type=int, default=4)
+    ap.add_argument("--lora", default=None, metavar="DIR",
+                    help="with --solution engine: run the request under the LoRA adapter in DIR (a PEFT or an mlx_lm adapter directory; "
+                         "tiny_llm_hip.lora), applied on the device beside the frozen weights")
     return ap
 
 
@@ -110,7 +113,13 @@ def main(argv=None) -> str:
     eos = tokenizer.eos_token_id
     records = None
     grammar = None
+    lora = None
     try:
+        if args.lora:
+            if args.draft_model:
+                print("note: --lora does not apply with a draft model")
+            else:
+                lora = engine.load_lora(args.lora)
         if not args.draft_model:
             from tiny_llm_hip.grammar import cli_grammar
 
@@ -128,7 +137,7 @@ def main(argv=None) -> str:
                                                proposal_length=min(args.proposal_length, 7), eos_token_id=eos)
             finally:
                 draft.close()
-        elif args.sampler_temp and (args.sampler_seed is not None or penalties != (1.0, 0.0, 0.0) or grammar is not None or truncates):
+        elif args.sampler_temp and (args.sampler_seed is not None or lora is not None or penalties != (1.0, 0.0, 0.0) or grammar is not None or truncates):
             # the per-slot sampler on the device: the whole generation in one prefill + one decode(N) call.  The penalties and the
             # grammar exist on the device only, so they select this path; so do min-p, typical-p and Mirostat
             if args.sampler_seed is None:
@@ -137,7 +146,7 @@ def main(argv=None) -> str:
                                   top_p=args.sampler_top_p, seed=args.sampler_seed or 0, logprobs=args.logprobs,
                                   repetition_penalty=penalties[0], presence_penalty=penalties[1], frequency_penalty=penalties[2],
                                   grammar=grammar, min_p=args.sampler_min_p, typical_p=args.sampler_typical_p,
-                                  mirostat_tau=args.mirostat_tau, mirostat_eta=args.mirostat_eta)
+                                  mirostat_tau=args.mirostat_tau, mirostat_eta=args.mirostat_eta, lora=lora)
             if args.logprobs is not None:
                 out, records = out
             out = cut_at_eos(out, eos, grammar)
@@ -145,7 +154,7 @@ def main(argv=None) -> str:
             out = sample_with_engine(engine, ids, args, eos)
         else:
             out = engine.generate(ids, args.max_new_tokens, logprobs=args.logprobs, repetition_penalty=penalties[0],
-                                  presence_penalty=penalties[1], frequency_penalty=penalties[2], grammar=grammar)
+                                  presence_penalty=penalties[1], frequency_penalty=penalties[2], grammar=grammar, lora=lora)
             if args.logprobs is not None:
                 out, records = out
             out = cut_at_eos(out, eos, grammar)

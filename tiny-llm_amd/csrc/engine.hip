@@ -21,6 +21,7 @@
 #include "kv_copy.h"
 #include "kv_swap.h"
 #include "pool.h"
+#include "lora.h"
 #include "slot_table.h"
 
 namespace tl {
@@ -246,6 +247,27 @@ struct tl_engine {
     // only) how many rows its running sum holds, -1: none
     float *emb_out = nullptr, *emb_sums = nullptr;
     std::vector<int> emb_rows;
+    // LoRA adapters (tl_engine_lora_load / tl_engine_set_lora, lora.h): per slot the adapter id on the host (-1: none; kept for every
+    // slot) and -- allocated by the first load -- the device table [TL_MAX_LORA_ADAPTERS][layers][4 groups], the per-slot ids the
+    // decode step's tiles look up, the tile lists (decode: fixed blocks of 16 rows; prefill: written per pass), the shrink's partials and
+    // sums of squares, and the rows of residual + delta ahead of a base projection's residual epilogue
+    enum { LORA_QKV, LORA_O, LORA_GU, LORA_DOWN, LORA_GROUPS };
+    struct LoraResident {
+        char *mem = nullptr;  // the fused matrices of every layer
+        size_t bytes = 0;
+        int rank = 0;
+        std::vector<char> has;  // [layers][groups]: the adapter adapts that group
+    };
+    std::vector<LoraResident> lora_ad;
+    std::vector<int> lora_of;
+    char *lora_mem = nullptr;
+    LoraDesc *lora_table = nullptr;
+    int32_t *lora_slot_dev = nullptr;
+    LoraTile *lora_tiles_decode = nullptr, *lora_tiles_prefill = nullptr;
+    float *lora_partial = nullptr, *lora_ss = nullptr;
+    uint16_t *lora_tmp = nullptr;
+    long lora_steps = 0, lora_prefill_rows = 0;
+    bool lora_slot(int slot) const { return lora_of[slot] >= 0; }
 
     bool warmed = false;
     std::map<std::pair<int, long>, hipGraphExec_t> graphs;  // (batch, n_splits << 32 | tokens_per_split)
@@ -938,6 +960,87 @@ static void launch_mirostat_update(tl_engine *e, const uint16_t *filtered, int r
 }
 
 // Context split of the decode attention: power-of-two bucket >= context, fixed windows of C tokens per workgroup.
+// ---- LoRA adapters (lora.h) ---------------------------------------------------------------------------
+// the slot's adapter id, on the host and -- once an adapter has been loaded -- on the device (skipped while it is the value already)
+static int lora_write(tl_engine *e, int slot, int adapter) {
+    if (e->lora_of[slot] == adapter) return TL_OK;
+    e->lora_of[slot] = adapter;
+    if (!e->lora_slot_dev) return TL_OK;
+    std::vector<std::pair<int32_t *, int32_t>> pk;
+    pk.emplace_back(e->lora_slot_dev + slot, adapter);
+    return poke(e, pk);
+}
+// some slot of [0, batch) that takes part in a decode step carries an adapter: the step runs the adapter plan (enqueue_step)
+static bool step_lora(const tl_engine *e, int batch) {
+    if (!e->lora_mem) return false;
+    for (int b = 0; b < batch && b < e->cfg.max_batch; ++b)
+        if (e->slot_runs(b) && e->lora_of[b] >= 0) return true;
+    return false;
+}
+// input and output columns of a projection group and how its output columns map to segments
+struct LoraShape {
+    int in, out, seg_mode, seg_end0, seg_end1;
+};
+static LoraShape lora_shape(const tl_engine *e, int group) {
+    const tl_engine_config &c = e->cfg;
+    const int q_dim = e->q_dim(), kv_dim = c.num_kv_heads * c.head_dim;
+    switch (group) {
+        case tl_engine::LORA_QKV: return {c.hidden_size, e->qkv_dim(), LORA_SEG_BLOCKS, q_dim, q_dim + kv_dim};
+        case tl_engine::LORA_O: return {q_dim, c.hidden_size, LORA_SEG_PLAIN, 0, 0};
+        case tl_engine::LORA_GU: return {c.hidden_size, 2 * c.intermediate_size, LORA_SEG_INTERLEAVED, 0, 0};
+        default: return {c.intermediate_size, c.hidden_size, LORA_SEG_PLAIN, 0, 0};
+    }
+}
+static int lora_tiles_cap(const tl_engine *e) { return std::max(lora_max_tiles(e->rows_cap, 16), ceil_div(e->cfg.max_batch, LORA_TILE)); }
+// the first load: the device table (all zero: nothing adapted), the per-slot ids (all none), the tile lists and the workspaces
+static int lora_alloc(tl_engine *e) {
+    if (e->lora_mem) return TL_OK;
+    const tl_engine_config &c = e->cfg;
+    const int in_max = std::max(std::max(c.hidden_size, e->q_dim()), c.intermediate_size);
+    const int cap = lora_tiles_cap(e), decode_tiles = ceil_div(c.max_batch, LORA_TILE);
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return at;
+    };
+    const size_t table_bytes = (size_t)TL_MAX_LORA_ADAPTERS * c.num_layers * tl_engine::LORA_GROUPS * sizeof(LoraDesc);
+    const size_t o_table = carve(table_bytes), o_slot = carve((size_t)c.max_batch * 4);
+    const size_t o_td = carve((size_t)decode_tiles * sizeof(LoraTile)), o_tp = carve((size_t)cap * sizeof(LoraTile));
+    const size_t o_part = carve(lora_partial_floats(cap, in_max) * 4), o_ss = carve(lora_ss_floats(cap, in_max) * 4);
+    const size_t o_tmp = carve((size_t)e->rows_cap * c.hidden_size * 2);
+    char *mem = nullptr;
+    if (hipMalloc((void **)&mem, off) != hipSuccess) return fail(TL_ERR_HIP, "engine_lora_load: hipMalloc(adapter table and workspaces) failed");
+    std::vector<LoraTile> tiles;
+    lora_lookup_tiles(c.max_batch, tiles);
+    hipError_t rc = hipMemset(mem + o_table, 0, table_bytes);
+    if (rc == hipSuccess) rc = hipMemset(mem + o_slot, 0xff, (size_t)c.max_batch * 4);
+    if (rc == hipSuccess) rc = hipMemcpy(mem + o_td, tiles.data(), tiles.size() * sizeof(LoraTile), hipMemcpyHostToDevice);
+    if (rc != hipSuccess) {
+        (void)hipFree(mem);
+        return fail(TL_ERR_HIP, std::string("engine_lora_load: ") + hipGetErrorString(rc));
+    }
+    e->lora_mem = mem;
+    e->lora_table = (LoraDesc *)(mem + o_table), e->lora_slot_dev = (int32_t *)(mem + o_slot);
+    e->lora_tiles_decode = (LoraTile *)(mem + o_td), e->lora_tiles_prefill = (LoraTile *)(mem + o_tp);
+    e->lora_partial = (float *)(mem + o_part), e->lora_ss = (float *)(mem + o_ss), e->lora_tmp = (uint16_t *)(mem + o_tmp);
+    e->lora_ad.assign(TL_MAX_LORA_ADAPTERS, tl_engine::LoraResident{});
+    return TL_OK;
+}
+// One adapted projection group of layer l over `n_tiles` tiles: the shrink and the expand launch (lora.h).  norm_w: x is the row ahead
+// of that RMSNorm (a decode step), else the row the base projection reads
+static int lora_group(tl_engine *e, int l, int group, const LoraTile *tiles_dev, int n_tiles, int total_rows, const uint16_t *x, const void *norm_w,
+                      int mode, const uint16_t *base, uint16_t *dst) {
+    const LoraShape s = lora_shape(e, group);
+    LoraCall c;
+    c.table = e->lora_table, c.stride = e->cfg.num_layers * tl_engine::LORA_GROUPS, c.index = l * tl_engine::LORA_GROUPS + group;
+    c.n_adapters = TL_MAX_LORA_ADAPTERS, c.row_adapter = e->lora_slot_dev, c.tiles_dev = tiles_dev, c.n_tiles = n_tiles, c.total_rows = total_rows;
+    c.x = x, c.in = s.in, c.out = s.out, c.norm_w = (const uint16_t *)norm_w, c.eps = e->cfg.rms_norm_eps;
+    c.partial = e->lora_partial, c.ss = e->lora_ss, c.seg_mode = s.seg_mode, c.seg_end0 = s.seg_end0, c.seg_end1 = s.seg_end1;
+    c.mode = mode, c.base = base, c.dst = dst;
+    return lora_apply(c, e->stream);
+}
+
 struct SplitPlan {
     int n_splits, tokens_per_split;
     int rq;  // query heads per workgroup
@@ -1220,7 +1323,12 @@ static StepRoute plan_step(const tl_engine *e, int batch, const SplitPlan &sp) {
 static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, ProfCtx *pc = nullptr) {
     const tl_engine_config &c = e->cfg;
     LinearCtx &ctx = e->lin;
-    const StepRoute route = plan_step(e, batch, sp);
+    StepRoute route = plan_step(e, batch, sp);
+    // A step in which a live slot carries a LoRA adapter (lora.h): every projection leaves complete bf16 rows in the shared buffers, the
+    // shrink / expand launches stand around them (8 more per dense layer), and the step keeps its launch boundaries
+    const bool lora = step_lora(e, batch);
+    if (lora) route.per_layer = route.per_layer_b = false;
+    const int lora_tiles = ceil_div(batch, LORA_TILE);
     // only a step whose hand-overs all live at addresses written once per step may be replayed without cache maintenance (tl_engine_decode)
     e->step_written_once = route.per_layer || route.per_layer_b;
     // x enters the step from the embedding gather (embed_slots_kernel / the previous step's step_end_kernel), which leaves the
@@ -1239,6 +1347,44 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, ProfCtx *pc = nul
     for (int l = 0; l < c.num_layers; ++l) {
         const tl_layer_weights &w = e->layers[l];
         const LayerRoute &rt = route.layers[l];
+        if (lora) {
+            const tl_engine::LayerAct &b = shared;
+            ProjResult r;
+            Proj p = proj(w.wqkv, x_cur, b.qkv, batch);
+            p.pro = PRO_RMSNORM, p.norm_w = w.input_norm_dev, p.ss_in = x_ss ? ssx_cur : nullptr, p.ss_in_n = x_ss;
+            TL_TRY(engine_linear(ctx, p, pc, &r));
+            TL_TRY(lora_group(e, l, tl_engine::LORA_QKV, e->lora_tiles_decode, lora_tiles, batch, x_cur, w.input_norm_dev, TL_LORA_ADD, nullptr, b.qkv));
+            AttnCall at{};
+            at.qkv = b.qkv, at.q_norm = w.q_norm_dev, at.k_norm = w.k_norm_dev, at.key_pages = e->layer_k(l), at.value_pages = e->layer_v(l);
+            at.key_scales = e->layer_ks(l), at.value_scales = e->layer_vs(l), at.out = b.attn, at.ws = b.attn_ws;
+            TL_TRY(engine_attention(e, at, batch, sp, pc));  // (no merging wo: the attention merges its own windows)
+            TL_TRY(lora_group(e, l, tl_engine::LORA_O, e->lora_tiles_decode, lora_tiles, batch, b.attn, nullptr, TL_LORA_RESIDUAL_PRE, x_cur, e->lora_tmp));
+            Proj po = proj(w.wo, b.attn, b.h, batch);
+            po.epi = EPI_RESIDUAL, po.residual = e->lora_tmp, po.kind = 1;
+            x_cur = b.x_out, ssx_cur = b.ss_x_out;
+            xw = false;
+            if (e->is_moe(l)) {
+                TL_TRY(engine_linear(ctx, po, pc));
+                TL_TRY(tl_rms_norm(b.h, w.post_norm_dev, b.xn, batch, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
+                TL_TRY(engine_moe_mlp(e, l, b.xn, b.h, b.x_out, batch, pc));
+                x_ss = 0;
+                continue;
+            }
+            TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
+            po.ss_out = b.ss_h;
+            TL_TRY(engine_linear(ctx, po, pc, &r));
+            const int h_ss = r.ss_n;
+            Proj pg = proj(w.wgu, b.h, ctx.gu, batch);  // complete gate|up rows; the expand launch's SwiGLU over base + delta
+            pg.pro = PRO_RMSNORM, pg.norm_w = w.post_norm_dev, pg.kind = 2, pg.ss_in = h_ss ? b.ss_h : nullptr, pg.ss_in_n = h_ss;
+            TL_TRY(engine_linear(ctx, pg, pc));
+            TL_TRY(lora_group(e, l, tl_engine::LORA_GU, e->lora_tiles_decode, lora_tiles, batch, b.h, w.post_norm_dev, TL_LORA_SWIGLU, ctx.gu, b.act));
+            TL_TRY(lora_group(e, l, tl_engine::LORA_DOWN, e->lora_tiles_decode, lora_tiles, batch, b.act, nullptr, TL_LORA_RESIDUAL_PRE, b.h, e->lora_tmp));
+            Proj pd = proj(w.wdown, b.act, b.x_out, batch);
+            pd.epi = EPI_RESIDUAL, pd.residual = e->lora_tmp, pd.kind = 3, pd.ss_out = b.ss_x_out;
+            TL_TRY(engine_linear(ctx, pd, pc, &r));
+            x_ss = r.ss_n;
+            continue;
+        }
         // The one input of a route that is not known ahead: are the row's sums of squares there when the layer starts?  In a dense model
         // they are -- QM3_SS per row from the embedding kernels, QM3_SS or rows / 16 from a w_down that leaves weighted rows -- so this cannot
         // fire there; should it ever, the step must not be replayed as "written once" over buffers written several times
@@ -1407,6 +1553,7 @@ static int settings_reset(tl_engine *e, int slot) {
     TL_TRY(lp_write(e, slot, -1));
     TL_TRY(pen_reset(e, slot));
     TL_TRY(trn_reset(e, slot));
+    TL_TRY(lora_write(e, slot, LORA_NONE));
     return smp_reset(e, slot);
 }
 // fork / move (move = true): dst takes what src has, and a move leaves src at the defaults
@@ -1427,8 +1574,11 @@ static int settings_carry(tl_engine *e, int src, int dst, bool move) {
     TL_TRY(lp_carry(e, src, dst, move));
     // ... the penalties, the bias list, the history and the grammar's state
     TL_TRY(pen_carry(e, src, dst, move));
-    // ... and the truncation parameters with Mirostat's mu
-    return trn_carry(e, src, dst, move);
+    // ... the truncation parameters with Mirostat's mu
+    TL_TRY(trn_carry(e, src, dst, move));
+    // ... and the LoRA adapter
+    TL_TRY(lora_write(e, dst, e->lora_of[src]));
+    return move ? lora_write(e, src, LORA_NONE) : TL_OK;
 }
 
 }  // namespace tl
@@ -1785,6 +1935,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->trn.assign(c.max_batch, tl_engine::TruncParams{});
     e->gr_pending.assign(c.max_batch, 0);
     e->emb_rows.assign(c.max_batch, -1);
+    e->lora_of.assign(c.max_batch, LORA_NONE);
     e->stats.kv_bytes = e->kv_bytes;
     e->stats.workspace_bytes = e->arena_bytes + e->tiled_bytes + e->bf16w_bytes;
     *out = e;
@@ -1895,6 +2046,9 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     if (e->score_logits) (void)hipFree(e->score_logits);
     if (e->emb_out) (void)hipFree(e->emb_out);
     if (e->emb_sums) (void)hipFree(e->emb_sums);
+    for (auto &r : e->lora_ad)
+        if (r.mem) (void)hipFree(r.mem);
+    if (e->lora_mem) (void)hipFree(e->lora_mem);
     if (e->kpool) (void)hipFree(e->kpool);
     if (e->vpool) (void)hipFree(e->vpool);
     if (e->kscale_pool) (void)hipFree(e->kscale_pool);
@@ -1919,6 +2073,7 @@ extern "C" const char *tl_engine_replay_route(const tl_engine *e) {
     text = e->aql_on ? std::string("aql") : ("hipgraph" + (e->aql_why.empty() ? std::string() : ": " + e->aql_why));
     // (a plan with a Mirostat slot keeps hipGraphLaunch on an engine whose other plans ride the route: step_mirostat)
     if (e->aql_on && step_mirostat(e, e->cfg.max_batch)) text = "hipgraph: a Mirostat slot is live (the update launch reads the token the step end stored)";
+    if (e->aql_on && step_lora(e, e->cfg.max_batch)) text = "hipgraph: a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)";
     return text.c_str();
 }
 
@@ -2051,7 +2206,7 @@ extern "C" int tl_engine_prefix_stats(const tl_engine *e, tl_prefix_stats *out) 
 extern "C" int tl_engine_prefix_extend(tl_engine *e, int slot, const int32_t *tokens, int n) {
     TL_TRY(slot_check_unparked(e, slot));
     TL_REQUIRE(tokens && n >= 1, "engine_prefix_extend: need at least one token");
-    if (!e->table.pool.enabled) return TL_OK;
+    if (!e->table.pool.enabled || e->lora_slot(slot)) return TL_OK;  // (a slot with a LoRA adapter bypasses the cache: nothing becomes known)
     for (int i = 0; i < n; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < e->cfg.vocab_size, "engine_prefix_extend: token id out of range");
     return table_rc(e->table.extend(slot, tokens, n));
 }
@@ -2060,6 +2215,11 @@ extern "C" int tl_engine_prefix_attach(tl_engine *e, int slot, const int32_t *to
     TL_TRY(slot_check_unparked(e, slot));
     TL_REQUIRE(tokens && matched && n >= 1, "engine_prefix_attach: need at least one token and a place for the result");
     const tl_engine_config &c = e->cfg;
+    if (e->lora_slot(slot)) {  // K/V depend on the adapter and the index is keyed by token ids alone: a slot with an adapter matches nothing
+        TL_REQUIRE(e->table.slots[slot].ctx == 0 && e->table.slots[slot].pages.empty(), "engine_prefix_attach: the slot already holds tokens or pages");
+        *matched = 0;
+        return TL_OK;
+    }
     SlotEdits ed;
     TL_TRY(table_rc(e->table.attach(slot, tokens, n, ed, matched)));
     const int got = *matched;
@@ -2711,6 +2871,210 @@ extern "C" int tl_pool_rows(const void *rows_dev, int hidden, int n_seqs, const 
 }
 
 // the paged attention operator over layer l's pages, by the engine's page format
+// ---- LoRA adapters (include/tinyllm_engine.h "LoRA adapters"; kernels lora.h) -----------------------------------------------------------
+extern "C" int tl_engine_lora_load(tl_engine *e, const tl_lora_layer *layers, int rank, float scale, int *adapter) {
+    TL_REQUIRE(e && layers && adapter, "engine_lora_load: null argument");
+    TL_REQUIRE(rank >= 8 && rank <= TL_MAX_LORA_RANK && rank % 8 == 0, "engine_lora_load: rank must be a multiple of 8 up to 64");
+    TL_REQUIRE(std::isfinite(scale), "engine_lora_load: scale must be finite");
+    const tl_engine_config &c = e->cfg;
+    const int L = c.num_layers, G = tl_engine::LORA_GROUPS;
+    const int q_dim = e->q_dim(), kv_dim = c.num_kv_heads * c.head_dim, H = c.hidden_size, I = c.intermediate_size;
+    // per target: its group, its segment inside the group, input and output columns
+    const int t_group[TL_LORA_TARGETS] = {tl_engine::LORA_QKV, tl_engine::LORA_QKV, tl_engine::LORA_QKV, tl_engine::LORA_O,
+                                          tl_engine::LORA_GU, tl_engine::LORA_GU, tl_engine::LORA_DOWN};
+    const int t_seg[TL_LORA_TARGETS] = {0, 1, 2, 0, 0, 1, 0};
+    const int t_in[TL_LORA_TARGETS] = {H, H, H, q_dim, H, H, I};
+    const int t_out[TL_LORA_TARGETS] = {q_dim, kv_dim, kv_dim, H, I, I, H};
+    bool any = false;
+    for (int l = 0; l < L; ++l)
+        for (int t = 0; t < TL_LORA_TARGETS; ++t) {
+            const void *a = layers[l].a_dev[t], *b = layers[l].b_dev[t];
+            TL_REQUIRE((a == nullptr) == (b == nullptr), "engine_lora_load: a target needs both A and B (or neither)");
+            if (!a) continue;
+            any = true;
+            TL_REQUIRE((uintptr_t)a % 2 == 0 && (uintptr_t)b % 2 == 0, "engine_lora_load: misaligned matrix");
+            if (t >= TL_LORA_GATE && e->is_moe(l)) return fail(TL_ERR_UNSUPPORTED, "engine_lora_load: MLP targets on a MoE layer are not supported");
+            if (t_in[t] % 32 != 0 || t_in[t] > LORA_KS * LORA_MAX_SLICES || t_out[t] % 2 != 0)
+                return fail(TL_ERR_UNSUPPORTED, "engine_lora_load: the kernels need input widths that are multiples of 32 (up to 32,768) and even output widths");
+        }
+    TL_REQUIRE(any, "engine_lora_load: the adapter adapts nothing");
+    int id = -1;
+    for (int i = 0; i < (int)e->lora_ad.size() && id < 0; ++i)
+        if (!e->lora_ad[i].mem) id = i;
+    if (e->lora_ad.empty()) id = 0;
+    TL_REQUIRE(id >= 0, "engine_lora_load: 32 adapters are resident (tl_engine_lora_unload one first)");
+    TL_TRY(aql_drain(e));
+    TL_HIP(hipStreamSynchronize(e->stream));
+    TL_TRY(lora_alloc(e));
+    // the fused matrices: per layer and group, A = the present targets' A stacked, B [out, rank] (rows of a missing target stay zero and unread)
+    std::vector<LoraDesc> descs((size_t)L * G, LoraDesc{});
+    std::vector<size_t> a_off(descs.size(), 0), b_off(descs.size(), 0);
+    size_t bytes = 0;
+    for (int l = 0; l < L; ++l)
+        for (int g = 0; g < G; ++g) {
+            LoraDesc &d = descs[(size_t)l * G + g];
+            d.t_off[0] = d.t_off[1] = d.t_off[2] = -1;
+            int in = 0, out = 0;
+            for (int t = 0; t < TL_LORA_TARGETS; ++t) {
+                if (t_group[t] != g) continue;
+                out += t_out[t];
+                if (!layers[l].a_dev[t]) continue;
+                in = t_in[t];
+                d.t_off[t_seg[t]] = d.rtot;
+                d.rtot += rank;
+            }
+            if (d.rtot == 0) continue;
+            d.rank = rank, d.scale = scale;
+            a_off[(size_t)l * G + g] = bytes;
+            bytes = align_up(bytes + (size_t)d.rtot * in * 2, 256);
+            b_off[(size_t)l * G + g] = bytes;
+            bytes = align_up(bytes + (size_t)out * rank * 2, 256);
+        }
+    char *mem = nullptr;
+    if (hipMalloc((void **)&mem, bytes) != hipSuccess) return fail(TL_ERR_HIP, "engine_lora_load: hipMalloc(adapter) failed");
+    auto undo = [&](const std::string &msg) {
+        (void)hipStreamSynchronize(e->stream);
+        (void)hipFree(mem);
+        return fail(TL_ERR_HIP, "engine_lora_load: " + msg);
+    };
+    if (hipMemsetAsync(mem, 0, bytes, e->stream) != hipSuccess) return undo("memset failed");
+    for (int l = 0; l < L; ++l)
+        for (int t = 0; t < TL_LORA_TARGETS; ++t) {
+            if (!layers[l].a_dev[t]) continue;
+            const int g = t_group[t];
+            LoraDesc &d = descs[(size_t)l * G + g];
+            char *a_dst = mem + a_off[(size_t)l * G + g] + (size_t)d.t_off[t_seg[t]] * t_in[t] * 2;
+            char *b_base = mem + b_off[(size_t)l * G + g];
+            hipError_t rc = hipMemcpyAsync(a_dst, layers[l].a_dev[t], (size_t)rank * t_in[t] * 2, hipMemcpyDeviceToDevice, e->stream);
+            const size_t row = (size_t)rank * 2;
+            if (rc == hipSuccess) {
+                if (g == tl_engine::LORA_GU)  // row i of gate / up -> row 2 i / 2 i + 1, like wgu
+                    rc = hipMemcpy2DAsync(b_base + (size_t)t_seg[t] * row, 2 * row, layers[l].b_dev[t], row, row, (size_t)t_out[t], hipMemcpyDeviceToDevice, e->stream);
+                else {
+                    const size_t first = g == tl_engine::LORA_QKV ? (t == TL_LORA_Q ? 0 : (t == TL_LORA_K ? q_dim : q_dim + kv_dim)) : 0;
+                    rc = hipMemcpyAsync(b_base + first * row, layers[l].b_dev[t], (size_t)t_out[t] * row, hipMemcpyDeviceToDevice, e->stream);
+                }
+            }
+            if (rc != hipSuccess) return undo(std::string("copy failed: ") + hipGetErrorString(rc));
+        }
+    for (size_t i = 0; i < descs.size(); ++i)
+        if (descs[i].rank > 0) descs[i].a = (const uint16_t *)(mem + a_off[i]), descs[i].b = (const uint16_t *)(mem + b_off[i]);
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return undo("the copies failed");
+    if (hipMemcpy(e->lora_table + (size_t)id * descs.size(), descs.data(), descs.size() * sizeof(LoraDesc), hipMemcpyHostToDevice) != hipSuccess)
+        return undo("hipMemcpy(table) failed");
+    tl_engine::LoraResident &r = e->lora_ad[id];
+    r.mem = mem, r.bytes = bytes, r.rank = rank;
+    r.has.assign(descs.size(), 0);
+    for (size_t i = 0; i < descs.size(); ++i) r.has[i] = descs[i].rank > 0;
+    *adapter = id;
+    return TL_OK;
+}
+
+extern "C" int tl_engine_lora_unload(tl_engine *e, int adapter) {
+    TL_REQUIRE(e, "engine_lora_unload: null engine");
+    TL_REQUIRE(adapter >= 0 && adapter < (int)e->lora_ad.size() && e->lora_ad[adapter].mem, "engine_lora_unload: no such adapter");
+    for (int s = 0; s < e->cfg.max_batch; ++s)
+        TL_REQUIRE(e->lora_of[s] != adapter, "engine_lora_unload: a live or parked slot carries the adapter (release it first)");
+    TL_TRY(aql_drain(e));
+    TL_HIP(hipStreamSynchronize(e->stream));
+    const size_t n = (size_t)e->cfg.num_layers * tl_engine::LORA_GROUPS;
+    TL_HIP(hipMemset(e->lora_table + (size_t)adapter * n, 0, n * sizeof(LoraDesc)));
+    TL_HIP(hipDeviceSynchronize());
+    (void)hipFree(e->lora_ad[adapter].mem);
+    e->lora_ad[adapter] = tl_engine::LoraResident{};
+    return TL_OK;
+}
+
+extern "C" int tl_engine_set_lora(tl_engine *e, int slot, int adapter) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(adapter == LORA_NONE || (adapter >= 0 && adapter < (int)e->lora_ad.size() && e->lora_ad[adapter].mem),
+               "engine_set_lora: the adapter is -1 (none) or the id of a resident adapter");
+    TL_REQUIRE(e->table.slots[slot].ctx == 0 && e->table.slots[slot].pages.empty(),
+               "engine_set_lora: the slot already holds tokens (a sequence's K/V are all computed under one adapter: set it before the first prefill)");
+    return lora_write(e, slot, adapter);
+}
+
+extern "C" int tl_engine_slot_lora(const tl_engine *e, int slot) {
+    if (!e || slot < 0 || slot >= e->cfg.max_batch) return LORA_NONE;
+    return e->lora_of[slot];
+}
+
+extern "C" int tl_engine_lora_stats(const tl_engine *e, tl_lora_stats *out) {
+    TL_REQUIRE(e && out, "engine_lora_stats: null argument");
+    *out = tl_lora_stats{};
+    for (const tl_engine::LoraResident &r : e->lora_ad)
+        if (r.mem) out->resident += 1, out->bytes += r.bytes;
+    out->adapter_steps = e->lora_steps;
+    out->adapter_prefill_rows = e->lora_prefill_rows;
+    return TL_OK;
+}
+
+extern "C" int tl_lora_rows(const void *x_dev, int rows, int in, int out, const int32_t *row_adapter_dev, const tl_lora_matrices *adapters, int n_adapters,
+                            int seg_mode, int seg_end0, int seg_end1, const int *tile_row0, const int *tile_rows, const int *tile_adapter, int n_tiles,
+                            int mode, const void *base_or_residual_dev, void *out_dev, const void *norm_w_dev, float eps, void *stream) {
+    TL_REQUIRE(x_dev && out_dev && adapters, "lora_rows: null argument");
+    TL_REQUIRE(rows >= 1 && n_adapters >= 1 && n_adapters <= TL_MAX_LORA_ADAPTERS, "lora_rows: at least one row and 1 .. 32 adapters");
+    TL_REQUIRE(seg_mode >= LORA_SEG_PLAIN && seg_mode <= LORA_SEG_INTERLEAVED, "lora_rows: seg_mode is 0 (one segment), 1 (three blocks) or 2 (interleaved)");
+    TL_REQUIRE(seg_mode != LORA_SEG_BLOCKS || (0 <= seg_end0 && seg_end0 <= seg_end1 && seg_end1 <= out), "lora_rows: block ends out of order");
+    const int n_seg = seg_mode == LORA_SEG_BLOCKS ? 3 : (seg_mode == LORA_SEG_INTERLEAVED ? 2 : 1);
+    std::vector<LoraDesc> descs(n_adapters, LoraDesc{});
+    for (int i = 0; i < n_adapters; ++i) {
+        const tl_lora_matrices &m = adapters[i];
+        LoraDesc &d = descs[i];
+        TL_REQUIRE(m.a_dev && m.b_dev && (uintptr_t)m.a_dev % 16 == 0 && (uintptr_t)m.b_dev % 16 == 0, "lora_rows: adapter matrices must be 16-byte aligned");
+        TL_REQUIRE(m.rank >= 8 && m.rank <= TL_MAX_LORA_RANK && m.rank % 8 == 0, "lora_rows: rank must be a multiple of 8 up to 64");
+        TL_REQUIRE(std::isfinite(m.scale), "lora_rows: scale must be finite");
+        TL_REQUIRE(m.seg_mask > 0 && m.seg_mask < (1 << n_seg), "lora_rows: seg_mask names no segment, or one the layout does not have");
+        d.a = (const uint16_t *)m.a_dev, d.b = (const uint16_t *)m.b_dev, d.scale = m.scale, d.rank = m.rank;
+        for (int s = 0; s < 3; ++s) {
+            d.t_off[s] = -1;
+            if (s < n_seg && ((m.seg_mask >> s) & 1)) d.t_off[s] = d.rtot, d.rtot += m.rank;
+        }
+    }
+    std::vector<LoraTile> tiles;
+    bool looks_up = n_tiles == 0;
+    if (n_tiles == 0) lora_lookup_tiles(rows, tiles);
+    else {
+        TL_REQUIRE(n_tiles > 0 && tile_row0 && tile_rows && tile_adapter, "lora_rows: a tile list needs its three arrays");
+        for (int i = 0; i < n_tiles; ++i) {
+            TL_REQUIRE(tile_row0[i] >= 0 && tile_rows[i] >= 0 && tile_rows[i] <= LORA_TILE && (long)tile_row0[i] + tile_rows[i] <= rows,
+                       "lora_rows: a tile is up to 16 rows inside [0, rows)");
+            TL_REQUIRE(tile_adapter[i] >= LORA_ROW_LOOKUP && tile_adapter[i] < n_adapters, "lora_rows: a tile's adapter is -2 (per row), -1 (none) or an index");
+            looks_up = looks_up || tile_adapter[i] == LORA_ROW_LOOKUP;
+            tiles.push_back(LoraTile{tile_row0[i], tile_rows[i], tile_adapter[i], 0});
+        }
+    }
+    TL_REQUIRE(!looks_up || row_adapter_dev, "lora_rows: tiles that look their rows' adapters up need row_adapter_dev");
+    const int nt = (int)tiles.size();
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return at;
+    };
+    const size_t o_table = carve(descs.size() * sizeof(LoraDesc)), o_tiles = carve(tiles.size() * sizeof(LoraTile));
+    const size_t o_part = carve(lora_partial_floats(nt, std::max(in, 1)) * 4), o_ss = carve(lora_ss_floats(nt, std::max(in, 1)) * 4);
+    char *mem = nullptr;
+    if (hipMalloc((void **)&mem, off) != hipSuccess) return fail(TL_ERR_HIP, "lora_rows: hipMalloc(workspace) failed");
+    int rc = TL_OK;
+    if (hipMemcpy(mem + o_table, descs.data(), descs.size() * sizeof(LoraDesc), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(mem + o_tiles, tiles.data(), tiles.size() * sizeof(LoraTile), hipMemcpyHostToDevice) != hipSuccess)
+        rc = fail(TL_ERR_HIP, "lora_rows: hipMemcpy(table) failed");
+    if (rc == TL_OK) {
+        LoraCall c;
+        c.table = (const LoraDesc *)(mem + o_table), c.stride = 1, c.index = 0, c.n_adapters = n_adapters, c.row_adapter = row_adapter_dev;
+        c.tiles_dev = (const LoraTile *)(mem + o_tiles), c.n_tiles = nt, c.total_rows = rows, c.x = (const uint16_t *)x_dev, c.in = in, c.out = out;
+        c.norm_w = (const uint16_t *)norm_w_dev, c.eps = eps, c.partial = (float *)(mem + o_part), c.ss = (float *)(mem + o_ss);
+        c.seg_mode = seg_mode, c.seg_end0 = seg_end0, c.seg_end1 = seg_end1, c.mode = mode;
+        c.base = (const uint16_t *)base_or_residual_dev, c.dst = (uint16_t *)out_dev;
+        rc = lora_apply(c, (hipStream_t)stream);
+    }
+    const hipError_t se = hipStreamSynchronize((hipStream_t)stream);
+    (void)hipFree(mem);
+    if (rc == TL_OK && se != hipSuccess) rc = fail(TL_ERR_HIP, std::string("lora_rows: ") + hipGetErrorString(se));
+    return rc;
+}
+
 static int engine_paged_attention(tl_engine *e, int l, const uint16_t *q_t, const int32_t *block_row, const int32_t *ctx_dev, uint16_t *attn_t,
                                   int n, int ctx_hint) {
     const tl_engine_config &c = e->cfg;
@@ -2775,12 +3139,39 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
     for (int i = 0; i < n_seqs; ++i)
         TL_REQUIRE(tl_paged_attention_workspace_bytes(Hq, seqs[i].len, D, c.page_size, c.max_pages_per_seq, Hq, Hkv, seqs[i].start + seqs[i].len) <=
                        e->attn_ws_bytes, std::string(packed ? "engine_prefill_packed" : "engine_prefill") + ": attention workspace too small");
+    // a pass in which some sequence carries a LoRA adapter (lora.h): tiles of 16 rows that never straddle two sequences, written here;
+    // lora_on(l, g): some sequence's adapter adapts group g of layer l -- the shrink / expand launches run around that projection
+    int lora_tiles = 0;
+    std::vector<LoraTile> lora_list;
+    {
+        int row0[16], len[16], ad[16];
+        bool any = false;
+        for (int i = 0; i < n_seqs; ++i) {
+            row0[i] = seqs[i].row0, len[i] = seqs[i].len, ad[i] = e->lora_of[seqs[i].slot];
+            if (ad[i] >= 0) any = true, e->lora_prefill_rows += seqs[i].len;
+        }
+        if (any) {
+            TL_REQUIRE(lora_build_tiles(n_seqs, row0, len, ad, lora_list) && (int)lora_list.size() <= lora_tiles_cap(e), "engine: bad LoRA tile list");
+            lora_tiles = (int)lora_list.size();
+            TL_HIP(hipMemcpyAsync(e->lora_tiles_prefill, lora_list.data(), lora_list.size() * sizeof(LoraTile), hipMemcpyHostToDevice, e->stream));
+        }
+    }
+    const auto lora_on = [&](int l, int g) {
+        if (lora_tiles == 0) return false;
+        for (int i = 0; i < n_seqs; ++i) {
+            const int a = e->lora_of[seqs[i].slot];
+            if (a >= 0 && e->lora_ad[a].has[(size_t)l * tl_engine::LORA_GROUPS + g]) return true;
+        }
+        return false;
+    };
     bool x_normed = false;  // the previous layer's w_down reduction left this layer's normalised rows in xn (engine_gemm)
     for (int l = 0; l < c.num_layers; ++l) {
         const tl_layer_weights &w = e->layers[l];
         if (!x_normed) TL_TRY(tl_rms_norm(e->x, w.input_norm_dev, e->xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
         x_normed = false;
         TL_TRY(engine_gemm(e->lin, proj(w.wqkv, e->xn, e->qkv, total)));
+        if (lora_on(l, tl_engine::LORA_QKV))
+            TL_TRY(lora_group(e, l, tl_engine::LORA_QKV, e->lora_tiles_prefill, lora_tiles, total, e->xn, nullptr, TL_LORA_ADD, nullptr, e->qkv));
         for (int i = 0; i < n_seqs; ++i) {
             const int n = seqs[i].len, start = seqs[i].start;
             const int32_t *block_row = e->block_table + (size_t)seqs[i].slot * c.max_pages_per_seq;
@@ -2812,6 +3203,10 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
         bool h_normed = false;
         Proj po = proj(w.wo, e->attn, e->h, total);
         po.epi = EPI_RESIDUAL, po.residual = e->x, po.norm_out = w.post_norm_dev, po.out_w = e->xn;
+        if (lora_on(l, tl_engine::LORA_O)) {  // x + delta first: the projection's residual epilogue then adds its product to that
+            TL_TRY(lora_group(e, l, tl_engine::LORA_O, e->lora_tiles_prefill, lora_tiles, total, e->attn, nullptr, TL_LORA_RESIDUAL_PRE, e->x, e->lora_tmp));
+            po.residual = e->lora_tmp;
+        }
         TL_TRY(engine_gemm(e->lin, po, &h_normed));
         if (!h_normed) TL_TRY(tl_rms_norm(e->h, w.post_norm_dev, e->xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
         if (e->is_moe(l)) {
@@ -2820,15 +3215,26 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
             TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
             Proj pg = proj(w.wgu, e->xn, e->act, total);
             pg.epi = EPI_SWIGLU;
-            TL_TRY(engine_gemm(e->lin, pg));
+            if (lora_on(l, tl_engine::LORA_GU)) {  // the unfused route: complete gate|up rows, then the expand launch's SwiGLU over base + delta
+                pg.out = e->lin.gu, pg.epi = EPI_STORE;
+                TL_TRY(engine_gemm(e->lin, pg));
+                TL_TRY(lora_group(e, l, tl_engine::LORA_GU, e->lora_tiles_prefill, lora_tiles, total, e->xn, nullptr, TL_LORA_SWIGLU, e->lin.gu, e->act));
+            } else {
+                TL_TRY(engine_gemm(e->lin, pg));
+            }
             Proj pd = proj(w.wdown, e->act, e->x, total);
             pd.epi = EPI_RESIDUAL, pd.residual = e->h, pd.norm_out = l + 1 < c.num_layers ? e->layers[l + 1].input_norm_dev : nullptr, pd.out_w = e->xn;
+            if (lora_on(l, tl_engine::LORA_DOWN)) {
+                TL_TRY(lora_group(e, l, tl_engine::LORA_DOWN, e->lora_tiles_prefill, lora_tiles, total, e->act, nullptr, TL_LORA_RESIDUAL_PRE, e->h, e->lora_tmp));
+                pd.residual = e->lora_tmp;
+            }
             TL_TRY(engine_gemm(e->lin, pd, &x_normed));
         }
         TL_CHECK_LAUNCH(packed ? "engine packed prefill layer" : "engine prefill layer");
     }
     for (int i = 0; i < n_seqs; ++i) {
-        e->table.appended(seqs[i].slot, tokens + seqs[i].row0, seqs[i].len);  // (seqs[i].start is the slot's context)
+        // (seqs[i].start is the slot's context; the ids of a slot with a LoRA adapter stay unknown to the prefix cache: its K/V are the adapter's)
+        e->table.appended(seqs[i].slot, tokens + seqs[i].row0, seqs[i].len, !e->lora_slot(seqs[i].slot));
         e->gr_pending[seqs[i].slot] = 0;  // a pending token that is prefilled past is never fed
         pk.emplace_back(e->context_lens + seqs[i].slot, seqs[i].start + seqs[i].len);
     }
@@ -3183,6 +3589,7 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
     const bool samples = step_samples(e, batch), logprobs = step_logprobs(e, batch), processes = step_processes(e, batch);
     const bool grammar = processes && step_grammar(e, batch), stack_grammar = grammar && step_stack_grammar(e, batch);
     const bool truncates = step_truncates(e, batch), mirostat = truncates && step_mirostat(e, batch);
+    const bool lora = step_lora(e, batch);
     bool on_queue = false;  // steps of this call are in flight on the AQL queue (the stream is idle and must stay so until they are drained)
     for (int s = 0; s < steps; ++s) {
         SplitPlan sp;
@@ -3196,7 +3603,9 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
                                                        (grammar ? (1L << 59) : 0L) | (stack_grammar ? (1L << 58) : 0L) |
                                                        // bit 57: the truncation launch (truncate.h) stands ahead of the step end and the Mirostat update behind
                                                        // it; bit 56: ... and a slot has Mirostat on (the plan keeps the hipGraphLaunch route: step_mirostat)
-                                                       (truncates ? (1L << 57) : 0L) | (mirostat ? (1L << 56) : 0L));
+                                                       (truncates ? (1L << 57) : 0L) | (mirostat ? (1L << 56) : 0L) |
+                                                       // bit 55: a live slot of [0, batch) carries a LoRA adapter: the adapter plan (lora.h; hipGraphLaunch)
+                                                       (lora ? (1L << 55) : 0L));
             auto it = e->graphs.find(key);
             if (it == e->graphs.end()) {
                 // The split plan (and with it the key) changes every 64 * n_splits tokens of context: a long run would keep one
@@ -3224,7 +3633,9 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
                 if (ce != hipSuccess) return fail(TL_ERR_HIP, std::string("engine_decode: graph capture failed: ") + hipGetErrorString(ce));
                 hipGraphExec_t exec = nullptr;
                 const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-                if (ie == hipSuccess && e->aql_on && !e->step_written_once) e->aql_why = "a hand-over of this plan lives in a shared buffer (written more than once per step)";
+                if (ie == hipSuccess && e->aql_on && !e->step_written_once)
+                    e->aql_why = lora ? "a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)"
+                                      : "a hand-over of this plan lives in a shared buffer (written more than once per step)";
                 if (ie == hipSuccess && e->aql_on && e->step_written_once && mirostat) e->aql_why = "a Mirostat slot is live (the update launch reads the token the step end stored)";
                 if (ie == hipSuccess && e->aql_on && e->step_written_once && !mirostat) {  // the same nodes as packet templates (aql.h); a plan that cannot be built keeps the graph route
                     auto prog = std::make_unique<AqlProgram>();
@@ -3265,6 +3676,7 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
             e->warmed = true;
         }
         step_done(e, batch);
+        if (lora) e->lora_steps++;
     }
     // the queue is not the stream: what follows this call (reads, prefills, the next call's embedding gather) is stream-ordered
     if (on_queue) TL_TRY(aql_drain(e));

@@ -141,9 +141,10 @@ public:
     }
     // after a prefill of n tokens into pages reserved before: tokens appended where the slot's known tokens end extend them, and pages
     // that filled up enter the index
-    void appended(int slot, const int32_t *tokens, int n) {
+    // (record = false: the tokens stay unknown to the prefix cache -- a slot whose K/V the token ids alone do not determine)
+    void appended(int slot, const int32_t *tokens, int n, bool record = true) {
         Slot &s = slots[slot];
-        const bool extends = pool.enabled && (int)s.rec.known.size() == s.ctx;
+        const bool extends = record && pool.enabled && (int)s.rec.known.size() == s.ctx;
         s.ctx += n;
         if (extends) {
             s.rec.known.insert(s.rec.known.end(), tokens, tokens + n);

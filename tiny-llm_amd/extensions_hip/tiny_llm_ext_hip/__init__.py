@@ -159,6 +159,28 @@ class TlSwapStats(ctypes.Structure):
                 ("pages_out", ctypes.c_long), ("pages_in", ctypes.c_long), ("record_bytes", _c_size_t)]
 
 
+TL_MAX_LORA_RANK = 64
+TL_MAX_LORA_ADAPTERS = 32
+LORA_TARGETS = ("q", "k", "v", "o", "gate", "up", "down")  # TL_LORA_Q .. TL_LORA_DOWN
+LORA_MODES = {"add": 0, "residual_pre": 1, "swiglu": 2}    # TL_LORA_ADD, TL_LORA_RESIDUAL_PRE, TL_LORA_SWIGLU
+LORA_SEG_MODES = {"plain": 0, "blocks": 1, "interleaved": 2}
+
+
+class TlLoraLayer(ctypes.Structure):
+    """tl_lora_layer: per target (LORA_TARGETS) the device matrices A [rank, in] and B [out, rank], bf16; a NULL pair = not adapted."""
+    _fields_ = [("a_dev", _c_void_p * len(LORA_TARGETS)), ("b_dev", _c_void_p * len(LORA_TARGETS))]
+
+
+class TlLoraStats(ctypes.Structure):
+    """tl_lora_stats (include/tinyllm_engine.h): resident adapters, their device bytes, adapter decode steps, adapter prefill rows."""
+    _fields_ = [("resident", _c_int), ("bytes", _c_size_t), ("adapter_steps", ctypes.c_long), ("adapter_prefill_rows", ctypes.c_long)]
+
+
+class TlLoraMatrices(ctypes.Structure):
+    """tl_lora_matrices: one adapter of tl_lora_rows in the fused layout -- A [rank * present segments, in], B [out, rank]."""
+    _fields_ = [("a_dev", _c_void_p), ("b_dev", _c_void_p), ("rank", _c_int), ("seg_mask", _c_int), ("scale", _c_float)]
+
+
 class TlAttentionInfo(ctypes.Structure):
     _fields_ = [("n_splits", _c_int), ("tokens_per_split", _c_int), ("heads_per_workgroup", _c_int),
                 ("launches", _c_int)]
@@ -257,6 +279,13 @@ _SIGNATURES.update({
     "tl_engine_embed": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _c_int, _c_int, _c_int, _c_int, _P(_c_float)]),
     "tl_pool_rows": (_c_int, [_c_void_p, _c_int, _c_int, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _c_int, _c_void_p,
                               _c_int, _c_int, _c_void_p, _c_void_p]),
+    "tl_engine_lora_load": (_c_int, [_c_void_p, _P(TlLoraLayer), _c_int, _c_float, _P(_c_int)]),
+    "tl_engine_lora_unload": (_c_int, [_c_void_p, _c_int]),
+    "tl_engine_set_lora": (_c_int, [_c_void_p, _c_int, _c_int]),
+    "tl_engine_slot_lora": (_c_int, [_c_void_p, _c_int]),
+    "tl_engine_lora_stats": (_c_int, [_c_void_p, _P(TlLoraStats)]),
+    "tl_lora_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _P(TlLoraMatrices), _c_int, _c_int, _c_int, _c_int, _P(ctypes.c_int),
+                              _P(ctypes.c_int), _P(ctypes.c_int), _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_float, _c_void_p]),
     "tl_engine_decode": (_c_int, [_c_void_p, _c_int, _c_int, _c_int]),
     "tl_engine_read_tokens": (_c_int, [_c_void_p, _c_int, _c_int, _P(ctypes.c_int32)]),
     "tl_engine_logits_dev": (_c_void_p, [_c_void_p]),
@@ -1076,6 +1105,59 @@ def pool_rows(rows: torch.Tensor, seqs, *, pooling: str = "last", normalize: boo
     ints = lambda v: (ctypes.c_int * n)(*v)
     check(_lib.tl_pool_rows(rows.data_ptr(), hidden, n, ints([s[0] for s in seqs]), ints([s[1] for s in seqs]), ints(finish), ints(prior), mode,
                             sums.data_ptr() if mode == POOL_MEAN else None, norm, dim, out.data_ptr() if out.numel() else None, _stream()))
+    return out
+
+
+def lora_rows(x: torch.Tensor, row_adapter, adapters, *, out_cols: int, mode: str = "add", base: torch.Tensor | None = None,
+              seg_mode: str = "plain", seg_ends=(0, 0), tiles=None, norm_weight: torch.Tensor | None = None, eps: float = 1e-6) -> torch.Tensor:
+    """The engine's LoRA routine (tl_lora_rows, csrc/lora.h) over bf16 rows ``x`` [rows, in] for one projection group of ``out_cols``
+    columns.  ``row_adapter``: per row the index of its adapter in ``adapters`` or -1; ``adapters``: (A, B, scale, seg_mask) in the
+    FUSED layout -- A [rank * present segments, in], B [out_cols, rank], bf16 on the GPU; seg_mask bit s = segment s is present.
+    ``seg_mode``: "plain", "blocks" (three column blocks ending at seg_ends[0], seg_ends[1], out_cols: q | k | v) or "interleaved"
+    (column parity: gate | up).  ``tiles``: None (blocks of 16 rows that look every row up) or (row0, rows <= 16, adapter) triples with
+    adapter -1 = none, -2 = per row.  ``mode``: "add" -> bf16(base + delta) [rows, out_cols]; "residual_pre" -> the same over a residual;
+    "swiglu" -> base holds interleaved gate|up rows, returns [rows, out_cols / 2].  ``norm_weight``: x is the row ahead of an RMSNorm of
+    that weight and ``eps``, applied inside."""
+    if mode not in LORA_MODES or seg_mode not in LORA_SEG_MODES:
+        raise ValueError(f"lora_rows: mode is one of {sorted(LORA_MODES)}, seg_mode one of {sorted(LORA_SEG_MODES)}")
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or not x.is_cuda:
+        raise ValueError("lora_rows takes a [rows, in] bf16 tensor on the GPU")
+    x = x.contiguous()
+    rows, cols = x.shape
+    if base is None or base.dtype != torch.bfloat16 or tuple(base.shape) != (rows, out_cols) or not base.is_cuda:
+        raise ValueError("lora_rows: base must be a [rows, out_cols] bf16 tensor on the GPU")
+    base = base.contiguous()
+    keep = []
+    mats = (TlLoraMatrices * max(len(adapters), 1))()
+    for i, (a, b, scale, mask) in enumerate(adapters):
+        if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or not a.is_cuda or not b.is_cuda or a.dim() != 2 or b.dim() != 2:
+            raise ValueError("lora_rows: adapter matrices are 2-D bf16 tensors on the GPU")
+        a, b = a.contiguous(), b.contiguous()
+        rank = b.shape[1]
+        if a.shape[1] != cols or b.shape[0] != out_cols or a.shape[0] != rank * bin(int(mask)).count("1"):
+            raise ValueError("lora_rows: A must be [rank * present segments, in] and B [out_cols, rank]")
+        keep += [a, b]
+        mats[i] = TlLoraMatrices(a.data_ptr(), b.data_ptr(), int(rank), int(mask), float(scale))
+    ids = torch.as_tensor(list(row_adapter), dtype=torch.int32).to(x.device) if not isinstance(row_adapter, torch.Tensor) else row_adapter.to(x.device, torch.int32).contiguous()
+    if ids.numel() != rows:
+        raise ValueError("lora_rows: row_adapter needs one id per row")
+    if int(ids.max()) >= len(adapters) or int(ids.min()) < -1:
+        raise ValueError("lora_rows: a row's adapter is -1 or an index into adapters")
+    if norm_weight is not None:
+        if norm_weight.dtype != torch.bfloat16 or tuple(norm_weight.shape) != (cols,) or not norm_weight.is_cuda:
+            raise ValueError("lora_rows: norm_weight must be a [in] bf16 tensor on the GPU")
+        norm_weight = norm_weight.contiguous()
+    n_tiles = 0 if tiles is None else len(tiles)
+    arr = lambda k: (ctypes.c_int * max(n_tiles, 1))(*[int(t[k]) for t in (tiles or [])])
+    if LORA_MODES[mode] == 0:
+        out = base.clone()
+    elif LORA_MODES[mode] == 1:
+        out = torch.empty_like(base)
+    else:
+        out = torch.empty((rows, out_cols // 2), dtype=torch.bfloat16, device=x.device)
+    check(_lib.tl_lora_rows(x.data_ptr(), rows, cols, out_cols, ids.data_ptr(), mats, len(adapters), LORA_SEG_MODES[seg_mode], int(seg_ends[0]),
+                            int(seg_ends[1]), arr(0), arr(1), arr(2), n_tiles, LORA_MODES[mode], base.data_ptr(), out.data_ptr(),
+                            norm_weight.data_ptr() if norm_weight is not None else None, float(eps), _stream()))
     return out
 
 

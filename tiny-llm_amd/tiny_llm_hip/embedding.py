@@ -51,7 +51,7 @@ class QuantizedEmbedding:
 PACKED_SEQS = 16  # sequences per packed pass (tl_engine_embed_packed)
 
 
-def embed_ids(engine, prompts, *, pooling: str = "last", normalize: bool = True, dim: int | None = None):
+def embed_ids(engine, prompts, *, pooling: str = "last", normalize: bool = True, dim: int | None = None, lora=None):
     """Embeddings of ``prompts`` (lists of token ids) as float32 [len(prompts), dim], in input order.
 
     A batch scheduler over ``engine.embed_packed``: every pass is filled with up to 16 sequences (and the engine's ``max_batch``
@@ -61,8 +61,14 @@ def embed_ids(engine, prompts, *, pooling: str = "last", normalize: bool = True,
     be (``max_pages_per_seq * page_size``), is an error raised before anything runs or with every slot released.  With the prefix
     cache on and ``pooling="last"`` a prompt first attaches its cached prefix (``prefix_attach``) and embeds from its remaining
     tokens; never for ``"mean"``, whose vector needs every row.  Uses slots [0, min(16, max_batch)), which must be free; every slot
-    it began is released, also on error."""
+    it began is released, also on error.  ``lora``: the id of a resident LoRA adapter (DecodeEngine.load_lora) for every prompt, or a
+    list with one id (or None / -1) per prompt; a prompt under an adapter bypasses the prefix cache."""
     import numpy as np
+
+    loras = list(lora) if isinstance(lora, (list, tuple)) else [lora] * len(prompts)
+    if len(loras) != len(prompts):
+        raise ValueError("embed_ids: lora needs one adapter id per prompt (or one for all)")
+    loras = [-1 if a is None else int(a) for a in loras]
 
     mode_args = tiny_llm_ext_hip.pooling_args(pooling, normalize, dim, int(engine.args.hidden_size))
     dim = mode_args[2]
@@ -117,6 +123,8 @@ def embed_ids(engine, prompts, *, pooling: str = "last", normalize: bool = True,
                 engine.begin(slot)
                 held[slot] = idx
                 promised += need
+                if loras[idx] >= 0:
+                    engine.set_lora(slot, loras[idx])
                 pos = engine.prefix_attach(slot, prompts[idx]) if attach else 0
                 take(slot, idx, pos)
             vectors = engine.embed_packed(chunks, pooling=pooling, normalize=normalize, dim=dim)

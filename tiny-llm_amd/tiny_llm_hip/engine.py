@@ -272,6 +272,46 @@ class DecodeEngine:
         _ext.check(_lib.tl_engine_swap_stats(self._h, ctypes.byref(s)))
         return {name: getattr(s, name) for name, _ in s._fields_}
 
+    # -- LoRA adapters (tl_engine_lora_*; include/tinyllm_engine.h "LoRA adapters") ---------------------------------
+    def load_lora(self, adapter) -> int:
+        """Make a ``lora.LoraAdapter`` (or an adapter directory: lora.load_adapter) resident and return its id (tl_engine_lora_load):
+        the engine copies the matrices into the fused layouts of its base weights, so nothing of ``adapter`` needs to stay alive."""
+        from .lora import TARGETS, LoraAdapter, check_adapter, load_adapter
+
+        if not isinstance(adapter, LoraAdapter):
+            adapter = load_adapter(adapter)
+        check_adapter(adapter)
+        layers = (_ext.TlLoraLayer * self.num_hidden_layers)()
+        keep = []
+        for (layer, target), (a, b) in adapter.weights.items():
+            if layer >= self.num_hidden_layers:
+                raise ValueError(f"the adapter has layer {layer}, the model {self.num_hidden_layers} layers")
+            a_dev, b_dev = (t.to(self.device, torch.bfloat16).contiguous() for t in (a, b))
+            keep += [a_dev, b_dev]
+            t = TARGETS.index(target)
+            layers[layer].a_dev[t], layers[layer].b_dev[t] = a_dev.data_ptr(), b_dev.data_ptr()
+        torch.cuda.current_stream().synchronize()  # the uploads ran on torch's stream
+        out = ctypes.c_int(-1)
+        _ext.check(_lib.tl_engine_lora_load(self._h, layers, int(adapter.rank), float(adapter.scale), ctypes.byref(out)))
+        return out.value
+
+    def unload_lora(self, adapter: int) -> None:
+        """Free a resident adapter (tl_engine_lora_unload); an error while a live or parked slot carries it."""
+        _ext.check(_lib.tl_engine_lora_unload(self._h, int(adapter)))
+
+    def set_lora(self, slot: int, adapter: int | None) -> None:
+        """The live slot's adapter (tl_engine_set_lora): an id from load_lora, or None / -1 for the base model.  Only while the slot
+        holds no tokens: a sequence's K / V are all computed under one adapter.  begin / release reset it, move carries it, fork copies it."""
+        _ext.check(_lib.tl_engine_set_lora(self._h, slot, -1 if adapter is None else int(adapter)))
+
+    def slot_lora(self, slot: int) -> int:
+        return _lib.tl_engine_slot_lora(self._h, slot)
+
+    def lora_stats(self) -> dict:
+        s = _ext.TlLoraStats()
+        _ext.check(_lib.tl_engine_lora_stats(self._h, ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in s._fields_}
+
     def read_pending(self, count: int | None = None) -> list[int]:
         """Pending (= most recently generated) token id of slots [0, count); synchronises."""
         count = count or self.max_batch
@@ -577,14 +617,15 @@ class DecodeEngine:
                  temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None, seed: int = 0,
                  logprobs: int | None = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                  frequency_penalty: float = 0.0, logit_bias=None, grammar: "Grammar | None" = None, min_p: float = 0.0,
-                 typical_p: float = 1.0, mirostat_tau: float = 0.0, mirostat_eta: float = 0.1):
+                 typical_p: float = 1.0, mirostat_tau: float = 0.0, mirostat_eta: float = 0.1, lora: int | None = None):
         """One request: prefill, then ``max_new_tokens - 1`` decode steps in one call; greedy unless ``temperature`` > 0 (the
         device sampler, set_sampling).  With ``logprobs`` an int (0 .. 20 alternatives, set_logprobs): returns (ids, records).
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` (set_penalties, set_logit_bias) are set
         before the prefill, so the prompt's tokens are in the slot's history; so is ``grammar`` (set_grammar): the ids are then text of
         its language, followed by EOS ids once it has ended.  ``min_p`` / ``typical_p`` (set_truncation) and ``mirostat_tau`` /
         ``mirostat_eta`` (set_mirostat) filter the rows a sampling request draws from; Mirostat excludes top_k, top_p, min_p and
-        typical_p (ValueError).  On an engine with the prefix cache on, the slot first attaches the cached
+        typical_p (ValueError).  ``lora``: the id of a resident adapter (load_lora) the request runs under; such a request bypasses the
+        prefix cache.  On an engine with the prefix cache on, the slot first attaches the cached
         prefix of the prompt (prefix_attach) and prefills the rest, and declares the answer before its release (prefix_extend)."""
         args = sampling_args(temperature, top_k, top_p, seed)
         trn = truncation_args(min_p, typical_p, mirostat_tau, mirostat_eta, top_k=args[1], top_p=args[2])
@@ -593,6 +634,8 @@ class DecodeEngine:
         bias = _ext.logit_bias_arg(logit_bias, self.vocab_size)
         self.begin(slot)
         try:
+            if lora is not None and lora >= 0:
+                self.set_lora(slot, lora)
             if pen != (1.0, 0.0, 0.0):
                 self.set_penalties(slot, *pen)
             if bias[0]:
@@ -774,7 +817,7 @@ def penalty_args(repetition: float = 1.0, presence: float = 0.0, frequency: floa
 
 
 _SAMPLING_KEYS = {"temperature", "top_k", "top_p", "seed", "min_p", "typical_p", "mirostat_tau", "mirostat_eta"}  # (the last four: request_truncation)
-_PENALTY_KEYS = {"repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "grammar"}  # (grammar: request_grammars)
+_PENALTY_KEYS = {"repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "grammar", "lora"}  # (grammar: request_grammars; lora: lora.request_loras)
 
 
 def request_penalties(sampling, n_prompts: int, vocab_size: int) -> list[tuple[tuple[float, float, float], dict]] | None:
@@ -872,6 +915,9 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     An engine built with ``prefix_cache`` has every request attach the cached prefix of its prompt (prefix_attach: after its settings,
     before its first chunk, which then starts at the matched offset) and declare its fed answer tokens at retirement (prefix_extend
     before release), so a follow-up turn finds prompt and answer cached.  Results keep their order and content rules.
+    ``sampling["lora"]``: the id of a resident adapter (DecodeEngine.load_lora) -- one for every request, a list with one per request,
+    or per dict -- set when the request enters the staging slot and carried by the engine through its slot moves; None / -1 = the base
+    model.  Requests under different adapters share decode steps; a request with an adapter bypasses the prefix cache.
     An engine built with ``swap_pages`` preempts under page pressure instead of failing with "KV page pool exhausted"
     (tiny_llm_hip.preempt): before a decode step the staging request is released and re-queued, or the running request admitted last
     is parked; parked requests resume oldest first, and nothing new is admitted while one is parked.  A request's ids do not depend on
@@ -887,6 +933,8 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     per_request_pen = None if sampling is None else request_penalties(sampling, len(prompts), engine.vocab_size)
     per_request_gr = request_grammars(sampling, len(prompts))
     per_request_trn = request_truncation(sampling, len(prompts))
+    from .lora import request_loras
+    per_request_lora = request_loras(sampling, len(prompts))  # ("lora": an adapter id for every request, or a list with one per request)
 
     def ends(req, token):  # the request's own EOS ids where it has a grammar
         return token == eos_token_id or (req["eos"] is not None and token in req["eos"])
@@ -912,6 +960,8 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                 idx = queue.pop(0)
                 engine.begin(staging)
                 live_slots.add(staging)
+                if per_request_lora is not None and per_request_lora[idx] >= 0:
+                    engine.set_lora(staging, per_request_lora[idx])
                 if per_request is not None and per_request[idx][0] > 0.0:
                     engine.set_sampling(staging, *per_request[idx])
                 if per_request_trn is not None:
