@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import logprob_oracle as L
 import truncation_oracle as R
 from helpers import TINY_CFG
 
@@ -155,8 +156,8 @@ def _engine(model, n, route=None, **kw):
             os.environ["TL_AQL"] = old
 
 
-def _cfg(T=0.0, seed=0, top_k=None, top_p=None, min_p=0.0, typ=1.0, tau=0.0, eta=0.1, pen=None, bias=None, grammar=None):
-    return dict(T=T, seed=seed, top_k=top_k, top_p=top_p, min_p=min_p, typ=typ, tau=tau, eta=eta, pen=pen, bias=bias, grammar=grammar)
+def _cfg(T=0.0, seed=0, top_k=None, top_p=None, min_p=0.0, typ=1.0, tau=0.0, eta=0.1, pen=None, bias=None, grammar=None, lp=None):
+    return dict(T=T, seed=seed, top_k=top_k, top_p=top_p, min_p=min_p, typ=typ, tau=tau, eta=eta, pen=pen, bias=bias, grammar=grammar, lp=lp)
 
 
 KINDS = ("greedy", "min_p", "typical", "mirostat", "both", "greedy+min_p")
@@ -171,12 +172,13 @@ def _kind(kind, i):
 class Run:
     """An engine and, beside it, what the header says a truncating slot holds: its parameters and Mirostat's mu."""
 
-    def __init__(self, model, n, kinds=KINDS, route=None, **kw):
-        self.eng = _engine(model, n, route, **kw)
+    def __init__(self, model, n, kinds=KINDS, route=None, eng=None, **kw):
+        """kinds = None: no slot is started (the caller starts them); eng: an engine the caller made and closes"""
+        self.eng = eng if eng is not None else _engine(model, n, route, **kw)
         self.n, self.cfg, self.mu, self.out = n, {}, {}, {}
         rng = np.random.default_rng(n)
         try:
-            for i in range(n):
+            for i in range(n if kinds else 0):
                 self.start(i, _kind(kinds[i % len(kinds)], i), rng.integers(0, 1000, 5 + i % 11).tolist())
         except Exception:
             self.eng.close()
@@ -199,6 +201,8 @@ class Run:
             e.set_truncation(i, c["min_p"], c["typ"])
         if c["tau"] > 0:
             e.set_mirostat(i, c["tau"], c["eta"])
+        if c["lp"] is not None:
+            e.set_logprobs(i, c["lp"])
         self.cfg[i] = c
         self.mu[i] = 2 * c["tau"] if c["tau"] > 0 else NAN
 
@@ -218,6 +222,8 @@ class Run:
         self.out[i] = [tok]
         if self.truncates(i):
             self.check_row(i, 0, tok, 1)
+        if c["lp"] is not None:
+            self.check_record(i, self.eng.logits(1).float().cpu().numpy()[0], tok, self.eng.read_logprobs(i, 1)[0])
 
     def check_row(self, i, row, tok, rows):
         """the filtered row `row` of the last launch against the oracle on the row the choice would have been made from; mu follows"""
@@ -232,13 +238,27 @@ class Run:
             self.mu[i] = self.eng.mirostat_mu(i)
             assert abs(self.mu[i] - want) <= 1e-4, (i, self.mu[i], want)
 
+    def check_record(self, i, raw, tok, rec):
+        """the record of the produced token describes the RAW row, whatever row the token was chosen from (the comparison and
+        tolerance of test_zz_logit_processing_gpu.test_logprob_records_describe_the_raw_row)"""
+        TOL = 2e-4  # tests/test_zz_logprobs_gpu.py: fp32 sum of the row's terms in a fixed order, with margin
+        assert abs(rec.logprob - L.logprob(raw, tok)) <= TOL, (i, rec, tok)
+        ids, lps = L.top(raw, self.cfg[i]["lp"])
+        assert [t for t, _ in rec.top] == ids.tolist(), (i, rec, ids)
+        assert all(abs(g - w) <= TOL for (_, g), w in zip(rec.top, lps)), (i, rec, lps)
+
     def step(self, check=True, use_graph=True):
         self.eng.decode(1, batch=self.n, use_graph=use_graph)
         got = self.eng.read_pending(self.n)
-        for i in range(self.n):
+        for i in sorted(self.cfg):
             self.out[i].append(got[i])
             if check:
                 self.check_row(i, i, got[i], self.n)
+        if check and any(c["lp"] is not None for c in self.cfg.values()):
+            raw, recs = self.eng.logits(self.n).float().cpu().numpy(), self.eng.read_pending_logprobs(self.n)
+            for i, c in self.cfg.items():
+                if c["lp"] is not None:
+                    self.check_record(i, raw[i], got[i], recs[i])
 
 
 @pytest.mark.parametrize("n", [1, 4, 5, 64])
@@ -318,6 +338,72 @@ def test_first_token_after_prefill_and_packed_prefill_is_filtered(tiny):
         eng.close()
 
 
+# the slot kinds of the whole-chain case, repeated over the batch.  "all" carries no min-p: the engine refuses min-p beside Mirostat
+# (test_slot_lifecycle), so min-p rides on another row of the packed pass below.  "idle": a slot that holds no sequence during the steps
+# -- begun and released without a prefill; a slot that stays begun is live, and every live slot of [0, batch) takes the step from token 0.
+# Four rows hold every kind but the plain greedy one, five hold all.
+CHAIN_KINDS = ("sampled", "pen+lp", "all", "idle", "greedy")
+CHAIN_PEN, CHAIN_BIAS = (1.3, 0.5, 0.25), {t: -math.inf for t in range(48, 52)}
+
+
+def _chain_kind(kind, i):
+    return {"greedy": _cfg(), "sampled": _cfg(0.8, 100 + i, top_k=40), "pen+lp": _cfg(pen=CHAIN_PEN, bias=CHAIN_BIAS, lp=3),
+            "all": _cfg(0.9, 100 + i, tau=5.0, eta=0.3, pen=CHAIN_PEN, bias=CHAIN_BIAS, lp=5),
+            "min_p+pen+lp": _cfg(0.8, 100 + i, top_k=40, min_p=0.05, pen=CHAIN_PEN, bias=CHAIN_BIAS, lp=2)}[kind]
+
+
+@pytest.mark.parametrize("n", [4, 5])
+def test_every_launch_of_the_chain_in_one_batch(tiny, n):
+    """Processing, truncation, the logprob step end and the Mirostat update in ONE step (4 rows: the GEMV step; 5: the batched-matmul
+    step), beside greedy, sampled and idle rows: per step the filtered row against the oracle on the processed row, the produced token
+    kept, mu, and the record of the produced token against the raw row; the idle slot's `produced` and context do not move.  Then one
+    packed prefill of three prompts that all end in the pass, the processing + Mirostat + logprob slot third: its first token comes from
+    row 2 of logits / processed rows / filtered rows / log-sums."""
+    run = Run(tiny, n, None)
+    eng = run.eng
+    try:
+        rng = np.random.default_rng(n)
+        idle = []
+        for i in range(n):
+            kind, prompt = CHAIN_KINDS[i % len(CHAIN_KINDS)], rng.integers(0, 1000, 5 + i % 11).tolist()
+            if kind == "idle":
+                eng.begin(i)
+                eng.release(i)
+                idle.append(i)
+            else:
+                run.start(i, _chain_kind(kind, i), prompt)
+        assert idle
+        for _ in range(4):
+            run.step()
+            for i in idle:  # the device's pending-token word (the commit's first store), and the host's side of the slot
+                assert eng.read_pending(n)[i] == 0 and eng.context_len(i) == -1
+                with pytest.raises(RuntimeError, match="fewer ids"):  # produced == 0
+                    eng.read_tokens(i, 1)
+        assert all(len(run.out[i]) == 5 and eng.context_len(i) == 5 + i % 11 + 4 for i in run.cfg)
+        assert "Mirostat" in eng.replay_route() and eng.stats()["graph_replays"] == 3
+    finally:
+        run.close()
+    # the packed pass: rows 0, 1, 2 of the row buffers belong to slots 2, 0, 1
+    run = Run(tiny, 4, None)
+    eng = run.eng
+    try:
+        order = [(2, "min_p+pen+lp"), (0, "greedy"), (1, "all")]
+        for slot, kind in order:
+            eng.begin(slot)
+            run.configure(slot, _chain_kind(kind, slot))
+        eng.prefill_packed([(slot, list(range(40 + 10 * slot, 47 + 11 * slot)), True) for slot, _ in order])
+        raw, recs = eng.logits(3).float().cpu().numpy(), {slot: eng.read_logprobs(slot, 1)[0] for slot in (2, 1)}
+        for row, (slot, kind) in enumerate(order):
+            tok = eng.read_tokens(slot, 1)[0]
+            if kind == "greedy":
+                assert tok == int(np.argmax(raw[row]))
+                continue
+            run.check_row(slot, row, tok, 3)
+            run.check_record(slot, raw[row], tok, recs[slot])
+    finally:
+        run.close()
+
+
 def test_slot_lifecycle(tiny):
     eng = _engine(tiny, 4)
     try:
@@ -395,8 +481,7 @@ def test_min_p_sees_the_processed_row_and_the_text_stays_in_the_language(tiny):
     dev = GG.Device(1024)
     eng = _engine(tiny, 2)
     try:
-        run = Run.__new__(Run)
-        run.eng, run.n, run.cfg, run.mu, run.out = eng, 1, {}, {}, {}
+        run = Run(tiny, 1, None, eng=eng)
         ban = {int(t): -math.inf for t in range(48, 52)}  # the digits 0-3
         run.start(0, _cfg(0.9, 7, top_k=40, min_p=0.2, pen=(1.3, 0.5, 0.25), bias=ban, grammar=dev.grammar(GG.NUMBER)), list(range(100, 112)))
         for _ in range(32):

@@ -10,8 +10,7 @@
 #include <memory>
 
 #include "decode_linear.h"  // the projection router; with it common.h, engine_kernels.h and the decode matmuls' headers
-#include "sample.h"
-#include "logprob.h"
+#include "step_end.h"  // the three step-end kernels; with it sample.h and logprob.h
 #include "logit_process.h"
 #include "truncate.h"
 #include "grammar_stack.h"
@@ -324,7 +323,9 @@ static std::string library_dir();
 namespace tl {
 
 // ---- small launch helpers ----------------------------------------------------------------------
-static int poke(tl_engine *e, std::vector<std::pair<int32_t *, int32_t>> &items) {
+// words written on the stream between steps, as (address, value): eight per poke launch
+using Pokes = std::vector<std::pair<int32_t *, int32_t>>;
+static int poke(tl_engine *e, Pokes &items) {
     for (size_t i = 0; i < items.size(); i += 8) {
         PokeArgs a{};
         a.n = (int)std::min<size_t>(8, items.size() - i);
@@ -338,203 +339,23 @@ static int poke(tl_engine *e, std::vector<std::pair<int32_t *, int32_t>> &items)
     TL_CHECK_LAUNCH("engine poke");
     return TL_OK;
 }
-
-// ---- per-slot sampling (sample.h) ------------------------------------------------------------------
-// The sampling twin of step_end_kernel: the token of every row is chosen by smp_select under its slot's parameters (a slot with
-// temperature 0 takes the greedy id, first maximum), then exactly step_end_kernel's tail: record, advance, RoPE factors, next
-// embedding row, sums of squares.  It writes what step_end_kernel writes, nothing else.  grid = rows, block = 1024.
-// (one struct by value, like every kernel of a decode step: csrc/aql.cpp copies a captured node's argument block as it is)
-struct SampleStepEndArgs {
-    StepEndArgs s;
-    const float *temperature;  // [max_batch]
-    const int32_t *top_k;
-    const float *top_p;
-    const uint64_t *seed;
+// one allocation laid out front to back: carve(bytes) is where the next 256-byte-aligned piece starts, carve.off the bytes taken so far
+struct Carve {
+    size_t off = 0;
+    size_t operator()(size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return at;
+    }
 };
-
-static __global__ __launch_bounds__(1024) void sample_step_end_kernel(const SampleStepEndArgs q) {
-    const StepEndArgs &p = q.s;
-    __shared__ SampleSmem sm;
-    __shared__ float s_val[16];
-    __shared__ int s_token, s_ctx;
-    const prof_t prof_t0 = prof_begin(p.prof);
-    const int i = blockIdx.x;
-    const int slot = p.slot0 + i;
-    const SmpRow row(p.logits + (long)i * p.vocab, p.vocab);
-    const float temperature = q.temperature[slot], top_p = q.top_p[slot];
-    const int top_k = q.top_k[slot];
-    const uint64_t seed = q.seed[slot];
-    const int live = p.live[slot];
-    // the sampled token's position: tokens before it (decode: the context after this step's advance; prefill: the prompt length)
-    const uint32_t position = (uint32_t)(p.context_lens[slot] + (p.advance && live ? 1 : 0));
-    float m_given = __builtin_nanf("");
-    if (p.tile_max) {  // uniform: the row maximum from the lm_head GEMV's per-tile pairs
-        const f32x2 *tm = p.tile_max + (long)i * p.tiles;
-        float t = -INFINITY;
-        for (int k = threadIdx.x; k < p.tiles; k += 1024) t = fmaxf(t, act_load(tm + k)[0]);
-        m_given = smp_block_max(t, sm);
-    }
-    const int bi = smp_select(row, m_given, temperature, top_k, top_p, seed, position, sm);
-    __syncthreads();  // every thread has read context_lens[slot] above
-    if (threadIdx.x == 0) {
-        s_token = bi;
-        int ctx_now = p.context_lens[slot];
-        if (live) {
-            p.tokens[slot] = bi;
-            const int n = p.produced[slot];
-            p.ring[(long)slot * p.ring_cap + (n % p.ring_cap)] = bi;
-            p.produced[slot] = n + 1;
-            if (p.advance) p.context_lens[slot] = ++ctx_now;
-        }
-        s_ctx = ctx_now;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < p.rope_half) {
-        const int pos = min(s_ctx, p.rope_positions - 1);  // the slot's NEXT position
-        p.rope_cur[(long)slot * p.rope_half + threadIdx.x] = p.rope_table[(long)pos * p.rope_half + threadIdx.x];
-    }
-    const int token = s_token;
-    const int words = p.hidden / 8;
-    const int groups = p.hidden / 128;
-    float sumsq = 0.f;
-    for (int w = threadIdx.x; w < words; w += 1024) {
-        const uint32_t packed = p.emb_w[(long)token * words + w];
-        const float scale = BF16::to_float(p.emb_s[(long)token * groups + w / 16]);
-        const float bias = BF16::to_float(p.emb_b[(long)token * groups + w / 16]);
-        uint16_t o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            o[e] = BF16::from_float((float)((packed >> (4 * e)) & 0xfu) * scale + bias);
-            const float v = BF16::to_float(o[e]);
-            sumsq += v * v;
-        }
-        *reinterpret_cast<uint4 *>(p.x + (long)slot * p.hidden + w * 8) = *reinterpret_cast<const uint4 *>(o);
-    }
-    if (p.ss_out) {
-        const float ws = wave_sum(sumsq);
-        if ((threadIdx.x & 63) == 0) s_val[threadIdx.x >> 6] = ws;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float tot = 0.f;
-            for (int w = 0; w < 16; ++w) tot += s_val[w];
-            p.ss_out[(long)slot * 8] = tot;
-            for (int i = 1; i < 8; ++i) p.ss_out[(long)slot * 8 + i] = 0.f;
-        }
-    }
-    prof_end(p.prof, prof_t0);
+// a float as its word; a 64-bit value (a pointer, a seed) as its two words
+static void poke_float(Pokes &pk, float *at, float v) { pk.emplace_back((int32_t *)at, __builtin_bit_cast(int32_t, v)); }
+static void poke_u64(Pokes &pk, void *at, uint64_t v) {
+    pk.emplace_back((int32_t *)at, (int32_t)(uint32_t)v);
+    pk.emplace_back((int32_t *)at + 1, (int32_t)(uint32_t)(v >> 32));
 }
 
-// Log-probability records (logprob.h, tl_engine_set_logprobs): the third twin of step_end_kernel.  It chooses the token as the sampling
-// twin does, runs its tail, and then writes the record of the produced token -- in the same launch, because the token a later launch of
-// the step would read is a plain store of this one (no cache maintenance between the launches of a step on the AQL route).
-struct LogprobStepEndArgs {
-    SampleStepEndArgs q;
-    const int32_t *top_n;  // [max_batch] -1: the slot records nothing
-    uint32_t *ring;        // [max_batch, ring_cap] records of LP_RECORD_WORDS words
-    uint32_t *pending;     // [max_batch] the record of each slot's pending token
-    const uint16_t *choice;  // [rows, vocab] the processed rows the token is chosen from (logit_process.h); nullptr: q.s.logits themselves
-};
-
-static __global__ __launch_bounds__(1024) void logprob_step_end_kernel(const LogprobStepEndArgs lq) {
-    const SampleStepEndArgs &q = lq.q;
-    const StepEndArgs &p = q.s;
-    __shared__ SampleSmem sm;
-    __shared__ LogprobSmem ls;
-    __shared__ float s_val[16];
-    __shared__ int s_token, s_ctx, s_n;
-    const prof_t prof_t0 = prof_begin(p.prof);
-    const int i = blockIdx.x;
-    const int slot = p.slot0 + i;
-    const SmpRow row(p.logits + (long)i * p.vocab, p.vocab);
-    // the record describes the raw row; with processed rows (uniform) the token is chosen from those
-    const bool split = lq.choice != nullptr;
-    const SmpRow crow(split ? lq.choice + (long)i * p.vocab : row.lg, p.vocab);
-    const float temperature = q.temperature[slot], top_p = q.top_p[slot];
-    const int top_k = q.top_k[slot];
-    const uint64_t seed = q.seed[slot];
-    const int live = p.live[slot];
-    // the sampled token's position: tokens before it (decode: the context after this step's advance; prefill: the prompt length)
-    const uint32_t position = (uint32_t)(p.context_lens[slot] + (p.advance && live ? 1 : 0));
-    float m_given = __builtin_nanf("");
-    if (p.tile_max) {  // uniform: the row maximum from the lm_head GEMV's per-tile pairs
-        const f32x2 *tm = p.tile_max + (long)i * p.tiles;
-        float t = -INFINITY;
-        for (int k = threadIdx.x; k < p.tiles; k += 1024) t = fmaxf(t, act_load(tm + k)[0]);
-        m_given = smp_block_max(t, sm);
-    }
-    const int top_n = lq.top_n[slot];
-    const bool record = live && top_n >= 0;  // uniform
-    if (m_given != m_given && (record || !split)) {  // the raw row's maximum, once for both routines
-        float t = -INFINITY;
-        smp_for_each(row, [&](int, int, uint32_t b) { t = fmaxf(t, __uint_as_float(b << 16)); });  // fmaxf drops NaN
-        m_given = smp_block_max(t, sm);
-    }
-    // a greedy slot that records takes the routine's own first maximum (smp_select's greedy id): one pass instead of two -- unless the
-    // choice is made on another row than the record's
-    const bool lp_first = record && temperature == 0.f && !split;
-    float lse = 0.f;
-    if (lp_first) lse = lp_row(row, m_given, top_n, sm, ls);
-    const int bi = lp_first ? ls.greedy : smp_select(crow, split ? __builtin_nanf("") : m_given, temperature, top_k, top_p, seed, position, sm);
-    __syncthreads();  // every thread has read context_lens[slot] above
-    if (threadIdx.x == 0) {
-        s_token = bi;
-        int ctx_now = p.context_lens[slot];
-        if (live) {
-            p.tokens[slot] = bi;
-            const int n = p.produced[slot];
-            p.ring[(long)slot * p.ring_cap + (n % p.ring_cap)] = bi;
-            p.produced[slot] = n + 1;
-            if (p.advance) p.context_lens[slot] = ++ctx_now;
-            s_n = n;
-        }
-        s_ctx = ctx_now;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < p.rope_half) {
-        const int pos = min(s_ctx, p.rope_positions - 1);  // the slot's NEXT position
-        p.rope_cur[(long)slot * p.rope_half + threadIdx.x] = p.rope_table[(long)pos * p.rope_half + threadIdx.x];
-    }
-    const int token = s_token;
-    const int words = p.hidden / 8;
-    const int groups = p.hidden / 128;
-    float sumsq = 0.f;
-    for (int w = threadIdx.x; w < words; w += 1024) {
-        const uint32_t packed = p.emb_w[(long)token * words + w];
-        const float scale = BF16::to_float(p.emb_s[(long)token * groups + w / 16]);
-        const float bias = BF16::to_float(p.emb_b[(long)token * groups + w / 16]);
-        uint16_t o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            o[e] = BF16::from_float((float)((packed >> (4 * e)) & 0xfu) * scale + bias);
-            const float v = BF16::to_float(o[e]);
-            sumsq += v * v;
-        }
-        *reinterpret_cast<uint4 *>(p.x + (long)slot * p.hidden + w * 8) = *reinterpret_cast<const uint4 *>(o);
-    }
-    if (p.ss_out) {
-        const float ws = wave_sum(sumsq);
-        if ((threadIdx.x & 63) == 0) s_val[threadIdx.x >> 6] = ws;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float tot = 0.f;
-            for (int w = 0; w < 16; ++w) tot += s_val[w];
-            p.ss_out[(long)slot * 8] = tot;
-            for (int i = 1; i < 8; ++i) p.ss_out[(long)slot * 8 + i] = 0.f;
-        }
-    }
-    if (record) {
-        if (!lp_first) lse = lp_row(row, m_given, top_n, sm, ls);
-        if (threadIdx.x == 0) ls.rec[0] = __float_as_uint(BF16::to_float(act_load(row.lg + token)) - lse);
-        __syncthreads();
-        if ((int)threadIdx.x < LP_RECORD_WORDS) {
-            const uint32_t v = ls.rec[threadIdx.x];
-            lq.ring[((long)slot * p.ring_cap + (s_n % p.ring_cap)) * LP_RECORD_WORDS + threadIdx.x] = v;
-            lq.pending[(long)slot * LP_RECORD_WORDS + threadIdx.x] = v;
-        }
-    }
-    prof_end(p.prof, prof_t0);
-}
-
+// ---- per-slot sampling (sample.h) and log-probabilities (logprob.h) over caller rows; the step-end kernels are in step_end.h ----
 // tl_logprob_rows / tl_engine_score: the routine over rows of logits.  grid = rows, block = 1024.
 struct LogprobRowsArgs {
     const uint16_t *logits;  // [rows, vocab]
@@ -573,34 +394,25 @@ static __global__ __launch_bounds__(1024) void sample_rows_kernel(const uint16_t
     if (threadIdx.x == 0) ids[i] = tok;
 }
 
-// does some live slot of [0, batch) sample?  (the plan-key bit of tl_engine_decode; with it clear a step is today's greedy program)
-static bool step_samples(const tl_engine *e, int batch) {
-    for (int b = 0; b < batch; ++b)
-        if (e->slot_runs(b) && e->smp[b].samples()) return true;
-    return false;
-}
+// The per-slot predicates of a step's plan (StepFeatures below ORs them over the step's slots).  Does the slot, taking part in a decode
+// step, sample?  (with no such slot a step is the greedy program)
+static bool step_samples_slot(const tl_engine *e, int slot) { return e->slot_runs(slot) && e->smp[slot].samples(); }
 
 // the device copy of a slot's parameters follows the host mirror (stream-ordered, between steps)
 static int smp_write(tl_engine *e, int slot, const tl_engine::SampleParams &v) {
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    pk.emplace_back((int32_t *)(e->smp_temp + slot), __builtin_bit_cast(int32_t, v.temperature));
+    Pokes pk;
+    poke_float(pk, e->smp_temp + slot, v.temperature);
     pk.emplace_back(e->smp_topk + slot, v.top_k);
-    pk.emplace_back((int32_t *)(e->smp_topp + slot), __builtin_bit_cast(int32_t, v.top_p));
-    pk.emplace_back((int32_t *)(e->smp_seed + slot), (int32_t)(uint32_t)v.seed);
-    pk.emplace_back((int32_t *)(e->smp_seed + slot) + 1, (int32_t)(uint32_t)(v.seed >> 32));
+    poke_float(pk, e->smp_topp + slot, v.top_p);
+    poke_u64(pk, e->smp_seed + slot, v.seed);
     e->smp[slot] = v;
     return poke(e, pk);
 }
 static bool smp_is_default(const tl_engine::SampleParams &v) { return v.temperature == 0.f && v.top_k == 0 && v.top_p == 0.f && v.seed == 0; }
 static int smp_reset(tl_engine *e, int slot) { return smp_is_default(e->smp[slot]) ? TL_OK : smp_write(e, slot, tl_engine::SampleParams{}); }
 
-// does some live slot of [0, batch) record log-probabilities?  (the plan-key bit next to step_samples')
+// ... record log-probabilities?
 static bool step_logprobs_slot(const tl_engine *e, int slot) { return !e->lp_n.empty() && e->slot_runs(slot) && e->lp_n[slot] >= 0; }
-static bool step_logprobs(const tl_engine *e, int batch) {
-    for (int b = 0; b < batch; ++b)
-        if (step_logprobs_slot(e, b)) return true;
-    return false;
-}
 
 // StepEndArgs over the engine's state: rows of `logits` for slots slot0.., the context advance (1: decode; 0: a prefill sets it on the host
 // side) and the next embedding rows into x; tile maxima, sums of squares and stamps where the step has them
@@ -669,7 +481,7 @@ static int lp_write(tl_engine *e, int slot, int top_n) {
         e->lp_n.assign(B, -1);
         e->lp_from.assign(B, 0);
     }
-    std::vector<std::pair<int32_t *, int32_t>> pk;
+    Pokes pk;
     pk.emplace_back(e->lp_topn + slot, top_n);
     if (e->lp_n[slot] < 0) e->lp_from[slot] = e->table.slots[slot].produced;  // records begin with the next produced token
     e->lp_n[slot] = top_n;
@@ -688,27 +500,11 @@ static int lp_carry(tl_engine *e, int src, int dst, bool move) {
 }
 
 // ---- per-slot logit processing (logit_process.h) ------------------------------------------------------------
-// does some live slot of [0, batch) process its logits?  (the plan-key bit next to step_samples' and step_logprobs')
+// does the slot, taking part in a step, process its logits?
 static bool step_processes_slot(const tl_engine *e, int slot) { return e->pen_mem && e->slot_runs(slot) && e->pen[slot].processes(); }
-static bool step_processes(const tl_engine *e, int batch) {
-    for (int b = 0; b < batch; ++b)
-        if (step_processes_slot(e, b)) return true;
-    return false;
-}
-
-// does some live slot of [0, batch) hold a grammar?  (its own plan-key bit: the step's processing launch is the grammar twin)
-static bool step_grammar(const tl_engine *e, int batch) {
-    for (int b = 0; b < batch; ++b)
-        if (step_processes_slot(e, b) && e->pen[b].grammar) return true;
-    return false;
-}
-
-// ... a STACK grammar?  (its own plan-key bit: the third twin, grammar_stack.h)
-static bool step_stack_grammar(const tl_engine *e, int batch) {
-    for (int b = 0; b < batch; ++b)
-        if (step_processes_slot(e, b) && e->pen[b].grammar && e->pen[b].grammar->stack) return true;
-    return false;
-}
+// ... and the grammar it processes them under, or null (with one the step's processing launch is the grammar twin; with a stack grammar,
+// g->stack, the third twin of grammar_stack.h)
+static const tl_grammar *step_grammar_slot(const tl_engine *e, int slot) { return step_processes_slot(e, slot) ? e->pen[slot].grammar : nullptr; }
 
 // the per-slot automaton pointers and state records: allocated by the first tl_engine_set_grammar
 static int gr_alloc(tl_engine *e) {
@@ -740,7 +536,7 @@ static int gr_stack_alloc(tl_engine *e) {
 }
 // the slot's record becomes {no context length, state}; a stack grammar's: {no context length, (state, depth 0, word 0)} (the stack
 // words are masked by the depth when they are read)
-static void gr_poke_state(tl_engine *e, int slot, const tl_grammar *g, std::vector<std::pair<int32_t *, int32_t>> &pk) {
+static void gr_poke_state(tl_engine *e, int slot, const tl_grammar *g, Pokes &pk) {
     int32_t *rec = g->stack ? (int32_t *)&e->gr_stack[slot].rec : &e->gr_state[slot].tag;
     pk.emplace_back(rec, -1);
     pk.emplace_back(rec + 1, g->start);
@@ -750,18 +546,13 @@ static void gr_poke_state(tl_engine *e, int slot, const tl_grammar *g, std::vect
 static int pen_alloc(tl_engine *e) {
     if (e->pen_mem) return TL_OK;
     const size_t B = (size_t)e->cfg.max_batch, V = (size_t)e->cfg.vocab_size;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
+    Carve carve;
     const size_t o_hist = carve(B * V * 2), o_rows = carve(std::max<size_t>(B, 8) * V * 2), o_rep = carve(B * 4), o_pres = carve(B * 4),
                  o_freq = carve(B * 4), o_n = carve(B * 4), o_ids = carve(B * LPR_MAX_BIAS * 4), o_vals = carve(B * LPR_MAX_BIAS * 4);
     char *m = nullptr;
-    if (hipMalloc((void **)&m, off) != hipSuccess) return fail(TL_ERR_HIP, "engine: hipMalloc(logit processing) failed");
+    if (hipMalloc((void **)&m, carve.off) != hipSuccess) return fail(TL_ERR_HIP, "engine: hipMalloc(logit processing) failed");
     // everything zero (empty histories, presence / frequency 0, empty lists) but the repetition penalties: 1
-    if (hipMemsetAsync(m, 0, off, e->stream) != hipSuccess) {
+    if (hipMemsetAsync(m, 0, carve.off, e->stream) != hipSuccess) {
         (void)hipFree(m);
         return fail(TL_ERR_HIP, "engine: memset(logit processing) failed");
     }
@@ -771,7 +562,7 @@ static int pen_alloc(tl_engine *e) {
     e->pen_rows = (uint16_t *)(m + o_rows);
     e->pen_rep = (float *)(m + o_rep), e->pen_pres = (float *)(m + o_pres), e->pen_freq = (float *)(m + o_freq);
     e->pen_bias_n = (int32_t *)(m + o_n), e->pen_bias_ids = (int32_t *)(m + o_ids), e->pen_bias_values = (float *)(m + o_vals);
-    e->stats.workspace_bytes += off;
+    e->stats.workspace_bytes += carve.off;
     TL_CHECK_LAUNCH("engine logit-processing init");
     return TL_OK;
 }
@@ -785,16 +576,12 @@ static int pen_device_switch(tl_engine *e, int slot, bool on) {
     if (!e->pen_mem) return TL_OK;
     const tl_engine::PenaltyParams neutral{};
     const tl_engine::PenaltyParams &v = on ? e->pen[slot] : neutral;
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    pk.emplace_back((int32_t *)(e->pen_rep + slot), __builtin_bit_cast(int32_t, v.repetition));
-    pk.emplace_back((int32_t *)(e->pen_pres + slot), __builtin_bit_cast(int32_t, v.presence));
-    pk.emplace_back((int32_t *)(e->pen_freq + slot), __builtin_bit_cast(int32_t, v.frequency));
+    Pokes pk;
+    poke_float(pk, e->pen_rep + slot, v.repetition);
+    poke_float(pk, e->pen_pres + slot, v.presence);
+    poke_float(pk, e->pen_freq + slot, v.frequency);
     pk.emplace_back(e->pen_bias_n + slot, (int32_t)v.bias_ids.size());
-    if (e->gr_mem) {
-        const uint64_t ptr = (uint64_t)(uintptr_t)(v.grammar ? v.grammar->dev : nullptr);
-        pk.emplace_back((int32_t *)(e->gr_ptr + slot), (int32_t)(uint32_t)ptr);
-        pk.emplace_back((int32_t *)(e->gr_ptr + slot) + 1, (int32_t)(uint32_t)(ptr >> 32));
-    }
+    if (e->gr_mem) poke_u64(pk, e->gr_ptr + slot, (uint64_t)(uintptr_t)(v.grammar ? v.grammar->dev : nullptr));
     return poke(e, pk);
 }
 
@@ -807,18 +594,16 @@ static int pen_write(tl_engine *e, int slot, const tl_engine::PenaltyParams &v) 
     TL_TRY(pen_alloc(e));
     const size_t V = (size_t)e->cfg.vocab_size;
     if (now && !was) TL_HIP(hipMemsetAsync(e->pen_history + (size_t)slot * V, 0, V * 2, e->stream));
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    if (cur.repetition != v.repetition) pk.emplace_back((int32_t *)(e->pen_rep + slot), __builtin_bit_cast(int32_t, v.repetition));
-    if (cur.presence != v.presence) pk.emplace_back((int32_t *)(e->pen_pres + slot), __builtin_bit_cast(int32_t, v.presence));
-    if (cur.frequency != v.frequency) pk.emplace_back((int32_t *)(e->pen_freq + slot), __builtin_bit_cast(int32_t, v.frequency));
+    Pokes pk;
+    if (cur.repetition != v.repetition) poke_float(pk, e->pen_rep + slot, v.repetition);
+    if (cur.presence != v.presence) poke_float(pk, e->pen_pres + slot, v.presence);
+    if (cur.frequency != v.frequency) poke_float(pk, e->pen_freq + slot, v.frequency);
     const bool bias_changed = cur.bias_ids != v.bias_ids || memcmp(cur.bias_values.data(), v.bias_values.data(), v.bias_values.size() * 4) != 0;
     if (bias_changed) pk.emplace_back(e->pen_bias_n + slot, (int32_t)v.bias_ids.size());
     if (cur.grammar != v.grammar) {  // the automaton's pointer (two words) and, for a new one, the record at its start state
         TL_TRY(gr_alloc(e));
         if (v.grammar && v.grammar->stack) TL_TRY(gr_stack_alloc(e));
-        const uint64_t ptr = (uint64_t)(uintptr_t)(v.grammar ? v.grammar->dev : nullptr);
-        pk.emplace_back((int32_t *)(e->gr_ptr + slot), (int32_t)(uint32_t)ptr);
-        pk.emplace_back((int32_t *)(e->gr_ptr + slot) + 1, (int32_t)(uint32_t)(ptr >> 32));
+        poke_u64(pk, e->gr_ptr + slot, (uint64_t)(uintptr_t)(v.grammar ? v.grammar->dev : nullptr));
         if (v.grammar) gr_poke_state(e, slot, v.grammar, pk);
     }
     cur = v;
@@ -851,12 +636,8 @@ static int pen_carry(tl_engine *e, int src, int dst, bool move) {
 
 // the processing launch over `rows` rows of raw logits for slots slot0 .. (logit_process.h): processed rows into `out`.  A decode step
 // passes the pending tokens (counted before the row is processed); a prefill's last row has none to count.
-static void launch_logit_process(tl_engine *e, const uint16_t *logits, uint16_t *out, int rows, int slot0, const int32_t *tokens, ProfCtx *pc) {
-    bool grammar = false, stack = false;
-    for (int i = 0; i < rows; ++i) {
-        const tl_grammar *g = step_processes_slot(e, slot0 + i) ? e->pen[slot0 + i].grammar : nullptr;
-        grammar |= g != nullptr, stack |= g && g->stack;
-    }
+static void launch_logit_process(tl_engine *e, const uint16_t *logits, uint16_t *out, int rows, int slot0, const int32_t *tokens, bool grammar,
+                                 bool stack, ProfCtx *pc) {
     const LogitProcessArgs a{logits, out, e->cfg.vocab_size, slot0, e->pen_history, e->pen_rep, e->pen_pres, e->pen_freq, e->pen_bias_n,
                              e->pen_bias_ids, e->pen_bias_values, tokens, pc ? pc->buf : nullptr,
                              grammar ? e->gr_ptr : nullptr, grammar ? e->gr_state : nullptr, grammar ? e->context_lens : nullptr};
@@ -868,40 +649,26 @@ static void launch_logit_process(tl_engine *e, const uint16_t *logits, uint16_t 
 }
 
 // ---- per-slot truncation (truncate.h) -------------------------------------------------------------------------
-// does some live slot of [0, batch) truncate?  (its own plan-key bit.)  Truncation applies to a slot that samples: a greedy slot is never
-// filtered (every filter keeps the maximum), so its parameters do not change the plan.
+// does the slot, taking part in a step, truncate?  Truncation applies to a slot that samples: a greedy slot is never filtered (every
+// filter keeps the maximum), so its parameters do not change the plan.
 static bool step_truncates_slot(const tl_engine *e, int slot) {
     return e->trn_mem && e->slot_runs(slot) && e->trn[slot].truncates() && e->smp[slot].samples();
 }
-static bool step_truncates(const tl_engine *e, int batch) {
-    for (int b = 0; b < batch; ++b)
-        if (step_truncates_slot(e, b)) return true;
-    return false;
-}
 // ... with Mirostat?  Its update launch reads the token the step end has just stored -- a plain store, which only a launch boundary
 // with cache maintenance hands over: such a plan keeps the hipGraphLaunch route (tl_engine_replay_route says so)
-static bool step_mirostat(const tl_engine *e, int batch) {
-    for (int b = 0; b < batch; ++b)
-        if (step_truncates_slot(e, b) && e->trn[b].mirostat()) return true;
-    return false;
-}
+static bool step_mirostat_slot(const tl_engine *e, int slot) { return step_truncates_slot(e, slot) && e->trn[slot].mirostat(); }
 
 // the filtered rows, the per-slot parameters and the per-row log-sums: one allocation, made by the first call that makes a slot truncate
 static int trn_alloc(tl_engine *e) {
     if (e->trn_mem) return TL_OK;
     const size_t B = (size_t)e->cfg.max_batch, R = std::max<size_t>(B, 8), V = (size_t)e->cfg.vocab_size;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
+    Carve carve;
     const size_t o_rows = carve(R * V * 2), o_minp = carve(B * 4), o_tau = carve(B * 4), o_eta = carve(B * 4), o_sum = carve(R * 4), o_typ = carve(B * 4),
                  o_mu = carve(B * 4);
     char *m = nullptr;
-    if (hipMalloc((void **)&m, off) != hipSuccess) return fail(TL_ERR_HIP, "engine: hipMalloc(truncation) failed");
+    if (hipMalloc((void **)&m, carve.off) != hipSuccess) return fail(TL_ERR_HIP, "engine: hipMalloc(truncation) failed");
     // zero (min-p, tau, eta off) up to the typical-p array; typical-p and mu: all ones, a NaN (typical-p off, no Mirostat)
-    if (hipMemsetAsync(m, 0, o_typ, e->stream) != hipSuccess || hipMemsetAsync(m + o_typ, 0xff, off - o_typ, e->stream) != hipSuccess) {
+    if (hipMemsetAsync(m, 0, o_typ, e->stream) != hipSuccess || hipMemsetAsync(m + o_typ, 0xff, carve.off - o_typ, e->stream) != hipSuccess) {
         (void)hipFree(m);
         return fail(TL_ERR_HIP, "engine: memset(truncation) failed");
     }
@@ -909,7 +676,7 @@ static int trn_alloc(tl_engine *e) {
     e->trn_rows = (uint16_t *)(m + o_rows);
     e->trn_minp = (float *)(m + o_minp), e->trn_typ = (float *)(m + o_typ), e->trn_tau = (float *)(m + o_tau), e->trn_eta = (float *)(m + o_eta);
     e->trn_mu = (float *)(m + o_mu), e->trn_logsum = (float *)(m + o_sum);
-    e->stats.workspace_bytes += off;
+    e->stats.workspace_bytes += carve.off;
     return TL_OK;
 }
 
@@ -921,11 +688,11 @@ static int trn_write(tl_engine *e, int slot, const tl_engine::TruncParams &v, bo
         return TL_OK;
     }
     TL_TRY(trn_alloc(e));
-    std::vector<std::pair<int32_t *, int32_t>> pk;
-    pk.emplace_back((int32_t *)(e->trn_minp + slot), __builtin_bit_cast(int32_t, v.min_p));
-    pk.emplace_back((int32_t *)(e->trn_typ + slot), __builtin_bit_cast(int32_t, v.typical_p));
-    pk.emplace_back((int32_t *)(e->trn_tau + slot), __builtin_bit_cast(int32_t, v.tau));
-    pk.emplace_back((int32_t *)(e->trn_eta + slot), __builtin_bit_cast(int32_t, v.eta));
+    Pokes pk;
+    poke_float(pk, e->trn_minp + slot, v.min_p);
+    poke_float(pk, e->trn_typ + slot, v.typical_p);
+    poke_float(pk, e->trn_tau + slot, v.tau);
+    poke_float(pk, e->trn_eta + slot, v.eta);
     if (restart_mu) pk.emplace_back((int32_t *)(e->trn_mu + slot), v.mirostat() ? __builtin_bit_cast(int32_t, 2.f * v.tau) : (int32_t)0x7fc00000);
     e->trn[slot] = v;
     return poke(e, pk);
@@ -966,17 +733,13 @@ static int lora_write(tl_engine *e, int slot, int adapter) {
     if (e->lora_of[slot] == adapter) return TL_OK;
     e->lora_of[slot] = adapter;
     if (!e->lora_slot_dev) return TL_OK;
-    std::vector<std::pair<int32_t *, int32_t>> pk;
+    Pokes pk;
     pk.emplace_back(e->lora_slot_dev + slot, adapter);
     return poke(e, pk);
 }
-// some slot of [0, batch) that takes part in a decode step carries an adapter: the step runs the adapter plan (enqueue_step)
-static bool step_lora(const tl_engine *e, int batch) {
-    if (!e->lora_mem) return false;
-    for (int b = 0; b < batch && b < e->cfg.max_batch; ++b)
-        if (e->slot_runs(b) && e->lora_of[b] >= 0) return true;
-    return false;
-}
+// the slot, taking part in a decode step, carries an adapter: the step runs the adapter plan (enqueue_step)
+static bool step_lora_slot(const tl_engine *e, int slot) { return e->lora_mem && e->slot_runs(slot) && e->lora_of[slot] >= 0; }
+
 // input and output columns of a projection group and how its output columns map to segments
 struct LoraShape {
     int in, out, seg_mode, seg_end0, seg_end1;
@@ -998,19 +761,14 @@ static int lora_alloc(tl_engine *e) {
     const tl_engine_config &c = e->cfg;
     const int in_max = std::max(std::max(c.hidden_size, e->q_dim()), c.intermediate_size);
     const int cap = lora_tiles_cap(e), decode_tiles = ceil_div(c.max_batch, LORA_TILE);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
+    Carve carve;
     const size_t table_bytes = (size_t)TL_MAX_LORA_ADAPTERS * c.num_layers * tl_engine::LORA_GROUPS * sizeof(LoraDesc);
     const size_t o_table = carve(table_bytes), o_slot = carve((size_t)c.max_batch * 4);
     const size_t o_td = carve((size_t)decode_tiles * sizeof(LoraTile)), o_tp = carve((size_t)cap * sizeof(LoraTile));
     const size_t o_part = carve(lora_partial_floats(cap, in_max) * 4), o_ss = carve(lora_ss_floats(cap, in_max) * 4);
     const size_t o_tmp = carve((size_t)e->rows_cap * c.hidden_size * 2);
     char *mem = nullptr;
-    if (hipMalloc((void **)&mem, off) != hipSuccess) return fail(TL_ERR_HIP, "engine_lora_load: hipMalloc(adapter table and workspaces) failed");
+    if (hipMalloc((void **)&mem, carve.off) != hipSuccess) return fail(TL_ERR_HIP, "engine_lora_load: hipMalloc(adapter table and workspaces) failed");
     std::vector<LoraTile> tiles;
     lora_lookup_tiles(c.max_batch, tiles);
     hipError_t rc = hipMemset(mem + o_table, 0, table_bytes);
@@ -1039,6 +797,67 @@ static int lora_group(tl_engine *e, int l, int group, const LoraTile *tiles_dev,
     c.partial = e->lora_partial, c.ss = e->lora_ss, c.seg_mode = s.seg_mode, c.seg_end0 = s.seg_end0, c.seg_end1 = s.seg_end1;
     c.mode = mode, c.base = base, c.dst = dst;
     return lora_apply(c, e->stream);
+}
+
+// ---- which launches a step needs ---------------------------------------------------------------------------------------------------
+// One record for slots [slot0, slot0 + n), re-derived from the slots' parameters by every call that enqueues or replays a step: the
+// per-slot predicates above, ORed.  A decode step asks over [0, batch), a prefill's first token over its one slot.
+struct StepFeatures {
+    bool samples = false, logprobs = false, processes = false, grammar = false, stack_grammar = false, truncates = false, mirostat = false,
+         lora = false;
+    // the bits a decode plan's key carries above its split plan (tl_engine_decode): with all clear the step is the greedy program
+    long key_bits() const {
+        // bit 62: the step ends with the sampling twin of step_end_kernel, bit 61: with the logprob twin (step_end.h)
+        return (samples ? (1L << 62) : 0L) | (logprobs ? (1L << 61) : 0L) |
+               // bit 60: the processing launch (logit_process.h) stands between the lm_head and the step end
+               // bit 59: ... and it is the grammar twin (grammar.h); bit 58: the stack-grammar twin (grammar_stack.h)
+               (processes ? (1L << 60) : 0L) | (grammar ? (1L << 59) : 0L) | (stack_grammar ? (1L << 58) : 0L) |
+               // bit 57: the truncation launch (truncate.h) stands ahead of the step end and the Mirostat update behind it
+               // bit 56: ... and a slot has Mirostat on (the plan keeps the hipGraphLaunch route)
+               (truncates ? (1L << 57) : 0L) | (mirostat ? (1L << 56) : 0L) |
+               // bit 55: a slot carries a LoRA adapter: the adapter plan (lora.h; hipGraphLaunch)
+               (lora ? (1L << 55) : 0L);
+    }
+};
+static StepFeatures step_features(const tl_engine *e, int slot0, int n) {
+    StepFeatures f;
+    for (int slot = slot0; slot < slot0 + n && slot < e->cfg.max_batch; ++slot) {
+        const tl_grammar *g = step_grammar_slot(e, slot);
+        f.samples |= step_samples_slot(e, slot);
+        f.logprobs |= step_logprobs_slot(e, slot);
+        f.processes |= step_processes_slot(e, slot);
+        f.grammar |= g != nullptr;  // (only with processes: step_grammar_slot)
+        f.stack_grammar |= g && g->stack;
+        f.truncates |= step_truncates_slot(e, slot);
+        f.mirostat |= step_mirostat_slot(e, slot);  // (only with truncates)
+        f.lora |= step_lora_slot(e, slot);
+    }
+    return f;
+}
+
+// The chain behind the lm_head over `rows` raw rows -- rows [row0, row0 + rows) of the engine's row buffers, slots slot0 .. -- in the one
+// order a decode step and a prefill's first token share: processing (logit_process.h), truncation (truncate.h), the step end, the
+// Mirostat update, each where `f` has it.
+//   advance, x, ss_out: the step end's context advance, where the next embedding rows go and their sums of squares (step_end_args)
+//   tile_max, tiles: the lm_head's per-tile pairs; they describe the raw rows, so only a step that neither processes nor truncates uses them
+//   tokens: the pending tokens a decode step's processing launch counts first (e->tokens); a prefill's row has none (null)
+static void launch_logit_chain(tl_engine *e, const uint16_t *raw, int row0, int rows, int slot0, int advance, uint16_t *x, const f32x2 *tile_max,
+                               int tiles, float *ss_out, const int32_t *tokens, const StepFeatures &f, ProfCtx *pc) {
+    const size_t at = (size_t)row0 * e->cfg.vocab_size;
+    const uint16_t *choice = raw;  // the rows the token is chosen from
+    if (f.processes) {  // raw rows -> processed rows (rows of slots that do not process are copied)
+        launch_logit_process(e, choice, e->pen_rows + at, rows, slot0, tokens, f.grammar, f.stack_grammar, pc);
+        choice = e->pen_rows + at;
+    }
+    if (f.truncates) {  // ... -> filtered rows (rows of slots that do not truncate are copied)
+        launch_truncate(e, choice, e->trn_rows + at, rows, slot0, row0, pc);
+        choice = e->trn_rows + at;
+    }
+    const bool maxima = tile_max && choice == raw;
+    const StepEndArgs s = step_end_args(e, choice, slot0, advance, x, maxima ? tile_max : nullptr, maxima ? tiles : 0, ss_out, pc ? pc->buf : nullptr);
+    launch_step_end(e, s, rows, f.samples, f.logprobs, choice != raw ? raw : nullptr);  // (the logprob twin records from the raw rows)
+    if (pc) prof_after(pc, 7, rows);
+    if (f.truncates) launch_mirostat_update(e, choice, rows, slot0, row0, pc);
 }
 
 struct SplitPlan {
@@ -1319,14 +1138,14 @@ static StepRoute plan_step(const tl_engine *e, int batch, const SplitPlan &sp) {
     return s;
 }
 
-// One fused decode step over slots [0, batch).
-static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, ProfCtx *pc = nullptr) {
+// One fused decode step over slots [0, batch); `f`: step_features(e, 0, batch).
+static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, const StepFeatures &f, ProfCtx *pc = nullptr) {
     const tl_engine_config &c = e->cfg;
     LinearCtx &ctx = e->lin;
     StepRoute route = plan_step(e, batch, sp);
     // A step in which a live slot carries a LoRA adapter (lora.h): every projection leaves complete bf16 rows in the shared buffers, the
     // shrink / expand launches stand around them (8 more per dense layer), and the step keeps its launch boundaries
-    const bool lora = step_lora(e, batch);
+    const bool lora = f.lora;
     if (lora) route.per_layer = route.per_layer_b = false;
     const int lora_tiles = ceil_div(batch, LORA_TILE);
     // only a step whose hand-overs all live at addresses written once per step may be replayed without cache maintenance (tl_engine_decode)
@@ -1466,31 +1285,13 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, ProfCtx *pc = nul
         ph.tile_max = e->lm_tile_max_on ? e->lm_tile_max : nullptr;
         TL_TRY(engine_linear(ctx, ph, pc, &rh));
     }
-    // a plan in which some live slot processes its logits: one more launch turns the raw rows into processed rows (rows of other slots
-    // are copied), and the step end chooses from those; the lm_head's tile maxima describe the raw rows and are not used
-    const bool processes = step_processes(e, batch);
-    if (processes) launch_logit_process(e, e->logits, e->pen_rows, batch, 0, e->tokens, pc);
-    // a plan in which some live slot truncates (truncate.h): one more launch filters the rows the choice would be made from into rows of
-    // their own (rows of other slots are copied), the step end chooses from those, and the Mirostat update runs behind it
-    const bool truncates = step_truncates(e, batch);
-    const uint16_t *choice = processes ? e->pen_rows : e->logits;
-    if (truncates) {
-        launch_truncate(e, choice, e->trn_rows, batch, 0, 0, pc);
-        choice = e->trn_rows;
-    }
-    const bool tile_max = rh.maxima_rows == batch && !processes && !truncates;
-    const StepEndArgs s = step_end_args(e, choice, 0, 1, e->x, tile_max ? e->lm_tile_max : nullptr,
-                                        tile_max ? e->head().rows / 16 : 0, e->ss_x, pc ? pc->buf : nullptr);
-    launch_step_end(e, s, batch, step_samples(e, batch), step_logprobs(e, batch), processes || truncates ? e->logits : nullptr);
-    if (pc) prof_after(pc, 7, batch);
-    if (truncates) launch_mirostat_update(e, e->trn_rows, batch, 0, 0, pc);
+    const bool tile_max = rh.maxima_rows == batch;
+    launch_logit_chain(e, e->logits, 0, batch, 0, 1, e->x, tile_max ? e->lm_tile_max : nullptr, tile_max ? e->head().rows / 16 : 0, e->ss_x, e->tokens, f, pc);
     TL_CHECK_LAUNCH("engine step end");
     return TL_OK;
 }
 
 // ---- the slot table (slot_table.h) on the device ---------------------------------------------------------------------------
-using Pokes = std::vector<std::pair<int32_t *, int32_t>>;
-
 // a refusal of the table as the engine reports it
 static int table_rc(const char *why) { return why ? fail(TL_ERR_INVALID, why) : TL_OK; }
 
@@ -1646,12 +1447,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
 
     // ---- arena layout
     const size_t R = (size_t)e->rows_cap;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
+    Carve carve;
     const size_t o_bt = carve((size_t)c.max_batch * c.max_pages_per_seq * 4);
     const size_t o_ctx = carve((size_t)c.max_batch * 4);
     const size_t o_tok = carve((size_t)c.max_batch * 4);
@@ -1688,7 +1484,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
                                                                                          c.max_pages_per_seq, c.num_heads,
                                                                                          c.num_kv_heads, 0));
     const size_t o_ws = carve(e->attn_ws_bytes);
-    e->arena_bytes = off;
+    e->arena_bytes = carve.off;
 
     // from here on a failure tears the partly built engine down like any other: tl_engine_destroy frees whatever it holds
     auto destroy_fail = [&](const std::string &msg) {
@@ -1965,19 +1761,14 @@ extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_wei
               I = std::max(e->moe_i_max, w->intermediate_size);
     if (k != e->moe_k_max || E != e->moe_e_max || I != e->moe_i_max) {  // (re)size the workspace: nothing captured holds it yet
         const size_t R = (size_t)e->rows_cap;
-        size_t off = 0;
-        auto carve = [&](size_t bytes) {
-            const size_t at = off;
-            off = align_up(off + bytes, 256);
-            return at;
-        };
+        Carve carve;
         const size_t o_log = carve(R * E * 2), o_ids = carve(R * k * 4), o_sc = carve(R * k * 2), o_g = carve(R * k * I * 2),
                      o_u = carve(R * k * I * 2), o_a = carve(R * k * I * 2), o_y = carve(R * k * c.hidden_size * 2);
         TL_HIP(hipStreamSynchronize(e->stream));
         if (e->moe_ws) (void)hipFree(e->moe_ws);
         e->moe_ws = nullptr;
-        TL_HIP(hipMalloc((void **)&e->moe_ws, off));
-        e->moe_ws_bytes = off;
+        TL_HIP(hipMalloc((void **)&e->moe_ws, carve.off));
+        e->moe_ws_bytes = carve.off;
         char *A = e->moe_ws;
         e->moe_logits = (uint16_t *)(A + o_log);
         e->moe_ids = (int32_t *)(A + o_ids);
@@ -2071,9 +1862,10 @@ extern "C" const char *tl_engine_replay_route(const tl_engine *e) {
     static thread_local std::string text;
     if (!e) return "";
     text = e->aql_on ? std::string("aql") : ("hipgraph" + (e->aql_why.empty() ? std::string() : ": " + e->aql_why));
-    // (a plan with a Mirostat slot keeps hipGraphLaunch on an engine whose other plans ride the route: step_mirostat)
-    if (e->aql_on && step_mirostat(e, e->cfg.max_batch)) text = "hipgraph: a Mirostat slot is live (the update launch reads the token the step end stored)";
-    if (e->aql_on && step_lora(e, e->cfg.max_batch)) text = "hipgraph: a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)";
+    // (a plan with a Mirostat slot keeps hipGraphLaunch on an engine whose other plans ride the route)
+    const StepFeatures f = step_features(e, 0, e->cfg.max_batch);
+    if (e->aql_on && f.mirostat) text = "hipgraph: a Mirostat slot is live (the update launch reads the token the step end stored)";
+    if (e->aql_on && f.lora) text = "hipgraph: a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)";
     return text.c_str();
 }
 
@@ -2434,7 +2226,7 @@ extern "C" int tl_engine_set_token(tl_engine *e, int slot, int32_t token) {
     TL_REQUIRE(token >= 0 && token < e->cfg.vocab_size, "engine_set_token: token id out of range");
     TL_REQUIRE(!e->pen[slot].processes(), "engine_set_token: the slot processes its logits (its history counts the tokens the engine produced; make it neutral first)");
     TL_REQUIRE(!e->trn[slot].mirostat(), "engine_set_token: the slot has Mirostat on (mu would no longer belong to the tokens held; switch it off first)");
-    std::vector<std::pair<int32_t *, int32_t>> pk;
+    Pokes pk;
     pk.emplace_back(e->tokens + slot, token);
     return poke(e, pk);
 }
@@ -2720,7 +2512,7 @@ extern "C" int tl_engine_set_grammar(tl_engine *e, int slot, const tl_grammar *g
     v.grammar = g;
     TL_TRY(pen_write(e, slot, v));
     if (same) {  // the same automaton again: back to its start state
-        std::vector<std::pair<int32_t *, int32_t>> pk;
+        Pokes pk;
         gr_poke_state(e, slot, g, pk);
         return poke(e, pk);
     }
@@ -3046,16 +2838,11 @@ extern "C" int tl_lora_rows(const void *x_dev, int rows, int in, int out, const 
     }
     TL_REQUIRE(!looks_up || row_adapter_dev, "lora_rows: tiles that look their rows' adapters up need row_adapter_dev");
     const int nt = (int)tiles.size();
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
+    Carve carve;
     const size_t o_table = carve(descs.size() * sizeof(LoraDesc)), o_tiles = carve(tiles.size() * sizeof(LoraTile));
     const size_t o_part = carve(lora_partial_floats(nt, std::max(in, 1)) * 4), o_ss = carve(lora_ss_floats(nt, std::max(in, 1)) * 4);
     char *mem = nullptr;
-    if (hipMalloc((void **)&mem, off) != hipSuccess) return fail(TL_ERR_HIP, "lora_rows: hipMalloc(workspace) failed");
+    if (hipMalloc((void **)&mem, carve.off) != hipSuccess) return fail(TL_ERR_HIP, "lora_rows: hipMalloc(workspace) failed");
     int rc = TL_OK;
     if (hipMemcpy(mem + o_table, descs.data(), descs.size() * sizeof(LoraDesc), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(mem + o_tiles, tiles.data(), tiles.size() * sizeof(LoraTile), hipMemcpyHostToDevice) != hipSuccess)
@@ -3243,25 +3030,11 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
     return TL_OK;
 }
 
-// The first token of a prefilled slot from its logits row: the step end (advance 0: the prefill has set the context length), after which
-// the slot has produced one id.  Its embedding row goes to scratch: the prefill activations in x must stay intact; decode re-embeds from tokens
-static int prefill_first_token(tl_engine *e, int slot, const uint16_t *logits, const char *what) {
-    const uint16_t *raw = nullptr;
-    if (step_processes_slot(e, slot)) {  // the row is processed first (no pending token to count here), into the row of the same index
-        uint16_t *out = e->pen_rows + (logits - e->logits);
-        launch_logit_process(e, logits, out, 1, slot, nullptr, nullptr);
-        raw = logits, logits = out;
-    }
-    const bool truncates = step_truncates_slot(e, slot);
-    const int row0 = (int)(((raw ? raw : logits) - e->logits) / e->cfg.vocab_size);
-    if (truncates) {  // ... and filtered (truncate.h), into the row of the same index again
-        uint16_t *out = e->trn_rows + (size_t)row0 * e->cfg.vocab_size;
-        launch_truncate(e, logits, out, 1, slot, row0, nullptr);
-        if (!raw) raw = logits;
-        logits = out;
-    }
-    launch_step_end(e, step_end_args(e, logits, slot, 0, e->h), 1, e->smp[slot].samples(), step_logprobs_slot(e, slot), raw);
-    if (truncates) launch_mirostat_update(e, logits, 1, slot, row0, nullptr);
+// The first token of a prefilled slot from row `row` of the logits: the chain behind the lm_head (advance 0: the prefill has set the
+// context length), after which the slot has produced one id.  Its embedding row goes to scratch: the prefill activations in x must stay
+// intact; decode re-embeds from tokens
+static int prefill_first_token(tl_engine *e, int slot, int row, const char *what) {
+    launch_logit_chain(e, e->logits + (size_t)row * e->cfg.vocab_size, row, 1, slot, 0, e->h, nullptr, 0, nullptr, nullptr, step_features(e, slot, 1), nullptr);
     TL_CHECK_LAUNCH(what);
     e->table.slots[slot].produced += 1;
     e->gr_pending[slot] = 1;
@@ -3303,7 +3076,7 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
         const uint16_t *last = e->x + (size_t)(n - 1) * c.hidden_size;
         TL_TRY(lm_head_rows(e, last, 1));
         e->logits_rows = 1;
-        TL_TRY(prefill_first_token(e, slot, e->logits, "engine prefill argmax"));
+        TL_TRY(prefill_first_token(e, slot, 0, "engine prefill argmax"));
     }
     return TL_OK;
 }
@@ -3369,7 +3142,7 @@ static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const
         int j = 0;
         for (int i = 0; i < n_seqs; ++i) {
             if (!want_logits[i]) continue;
-            TL_TRY(prefill_first_token(e, slots[i], e->logits + (size_t)j * c.vocab_size, "engine packed prefill argmax"));
+            TL_TRY(prefill_first_token(e, slots[i], j, "engine packed prefill argmax"));
             ++j;
         }
     }
@@ -3586,26 +3359,13 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
     // input activations of the first step come from the pending token ids
     launch_embed_slots(e, batch);
     TL_CHECK_LAUNCH("engine embed");
-    const bool samples = step_samples(e, batch), logprobs = step_logprobs(e, batch), processes = step_processes(e, batch);
-    const bool grammar = processes && step_grammar(e, batch), stack_grammar = grammar && step_stack_grammar(e, batch);
-    const bool truncates = step_truncates(e, batch), mirostat = truncates && step_mirostat(e, batch);
-    const bool lora = step_lora(e, batch);
+    const StepFeatures f = step_features(e, 0, batch);
     bool on_queue = false;  // steps of this call are in flight on the AQL queue (the stream is idle and must stay so until they are drained)
     for (int s = 0; s < steps; ++s) {
         SplitPlan sp;
         TL_TRY(prepare_step(e, batch, &sp, &on_queue));
         if (use_graph && e->warmed) {
-            // bit 62: the step ends with the sampling twin of step_end_kernel, bit 61: with the logprob twin (both re-derived every call
-            // from the slots' parameters)
-            // bit 60: the processing launch (logit_process.h) stands between the lm_head and the step end
-            // bit 59: ... and it is the grammar twin (grammar.h); bit 58: the stack-grammar twin (grammar_stack.h)
-            const auto key = std::make_pair(batch, sp.key() | (samples ? (1L << 62) : 0L) | (logprobs ? (1L << 61) : 0L) | (processes ? (1L << 60) : 0L) |
-                                                       (grammar ? (1L << 59) : 0L) | (stack_grammar ? (1L << 58) : 0L) |
-                                                       // bit 57: the truncation launch (truncate.h) stands ahead of the step end and the Mirostat update behind
-                                                       // it; bit 56: ... and a slot has Mirostat on (the plan keeps the hipGraphLaunch route: step_mirostat)
-                                                       (truncates ? (1L << 57) : 0L) | (mirostat ? (1L << 56) : 0L) |
-                                                       // bit 55: a live slot of [0, batch) carries a LoRA adapter: the adapter plan (lora.h; hipGraphLaunch)
-                                                       (lora ? (1L << 55) : 0L));
+            const auto key = std::make_pair(batch, sp.key() | f.key_bits());
             auto it = e->graphs.find(key);
             if (it == e->graphs.end()) {
                 // The split plan (and with it the key) changes every 64 * n_splits tokens of context: a long run would keep one
@@ -3624,7 +3384,7 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
                 }
                 hipGraph_t graph = nullptr;
                 TL_HIP(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-                const int rc = enqueue_step(e, batch, sp);
+                const int rc = enqueue_step(e, batch, sp, f);
                 const hipError_t ce = hipStreamEndCapture(e->stream, &graph);
                 if (rc != TL_OK) {
                     if (graph) (void)hipGraphDestroy(graph);
@@ -3634,10 +3394,10 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
                 hipGraphExec_t exec = nullptr;
                 const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
                 if (ie == hipSuccess && e->aql_on && !e->step_written_once)
-                    e->aql_why = lora ? "a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)"
+                    e->aql_why = f.lora ? "a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)"
                                       : "a hand-over of this plan lives in a shared buffer (written more than once per step)";
-                if (ie == hipSuccess && e->aql_on && e->step_written_once && mirostat) e->aql_why = "a Mirostat slot is live (the update launch reads the token the step end stored)";
-                if (ie == hipSuccess && e->aql_on && e->step_written_once && !mirostat) {  // the same nodes as packet templates (aql.h); a plan that cannot be built keeps the graph route
+                if (ie == hipSuccess && e->aql_on && e->step_written_once && f.mirostat) e->aql_why = "a Mirostat slot is live (the update launch reads the token the step end stored)";
+                if (ie == hipSuccess && e->aql_on && e->step_written_once && !f.mirostat) {  // the same nodes as packet templates (aql.h); a plan that cannot be built keeps the graph route
                     auto prog = std::make_unique<AqlProgram>();
                     if (aql_program_from_graph(*e->aql_rt, graph, e->stream, *prog, e->aql_why) == 0) e->aql_programs[key] = std::move(prog);
                 }
@@ -3672,11 +3432,11 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
                 TL_TRY(aql_drain(e));
                 on_queue = false;
             }
-            TL_TRY(enqueue_step(e, batch, sp));
+            TL_TRY(enqueue_step(e, batch, sp, f));
             e->warmed = true;
         }
         step_done(e, batch);
-        if (lora) e->lora_steps++;
+        if (f.lora) e->lora_steps++;
     }
     // the queue is not the stream: what follows this call (reads, prefills, the next call's embedding gather) is stream-ordered
     if (on_queue) TL_TRY(aql_drain(e));
@@ -3749,7 +3509,7 @@ extern "C" int tl_engine_profile_step(tl_engine *e, int batch, tl_step_profile *
     launch_embed_slots(e, batch);
     SplitPlan sp;
     int rc = prepare_step(e, batch, &sp);
-    if (rc == TL_OK) rc = enqueue_step(e, batch, sp, &pc);
+    if (rc == TL_OK) rc = enqueue_step(e, batch, sp, step_features(e, 0, batch), &pc);
     if (rc != TL_OK) {
         (void)hipStreamSynchronize(e->stream);
         return rc;
@@ -3831,7 +3591,7 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
     int rc = prepare_step(e, batch, &sp);
     if (rc == TL_OK) {
         pc.check = &ck;
-        rc = enqueue_step(e, batch, sp, &pc);
+        rc = enqueue_step(e, batch, sp, step_features(e, 0, batch), &pc);
     }
     if (rc != TL_OK) {
         (void)hipStreamSynchronize(e->stream);

@@ -755,176 +755,6 @@ static __global__ __launch_bounds__(256) void attn_merge_cols_kernel(const float
     prof_end(prof, prof_t0);
 }
 
-// ---------------------------------------------------------------------------------------------
-// End of step: greedy argmax over bf16 logits (first maximum wins, like argmax), record the id, advance
-// the slot, and dequantize the id's embedding row into the next step's input activation.
-//   grid = rows; block = 1024.  Block i reads logits row i and serves slot slot0 + i.
-//   reference: mx.argmax(logits[:, -1]) (benches/bench.py:234-243) + QuantizedEmbedding (embedding.py:38-54).
-// ---------------------------------------------------------------------------------------------
-struct StepEndArgs {
-    const uint16_t *logits;  // [rows, vocab]
-    int vocab;
-    int slot0;
-    int32_t *tokens;        // [max_batch] pending input token per slot
-    int32_t *context_lens;  // [max_batch]
-    const int32_t *live;    // [max_batch] 1 = slot holds a sequence
-    int32_t *produced;      // [max_batch] number of ids recorded so far
-    int32_t *ring;          // [max_batch, ring_cap]
-    int ring_cap;
-    int advance;  // 1: context_lens[slot] += 1 (decode); 0: prefill sets it on the host side
-    // next-step embedding
-    const uint32_t *emb_w;
-    const uint16_t *emb_s, *emb_b;
-    uint16_t *x;  // [max_batch, hidden], row = slot
-    int hidden;
-    // RoPE factors of the slot's next position (read by the next step's attention kernels)
-    const float2 *rope_table;
-    float2 *rope_cur;
-    int rope_positions, rope_half;
-    // optional: [max_batch][8] partial sums of squares of the embedded row (entry 0; the rest zero) for the fused RMSNorm of
-    // the next step's skinny QKV matmul (qmm3.h)
-    float *ss_out;
-    prof_t *prof;
-    // optional: per 16-logit tile (largest bf16 logit, lowest index holding it), left by the lm_head GEMV's epilogue (qmv3.h tile_max):
-    // [rows][tiles] pairs; the greedy id is then picked from `tiles` pairs and the logits row is not read again
-    const f32x2 *tile_max;
-    int tiles;
-};
-
-static __global__ __launch_bounds__(1024) void step_end_kernel(const StepEndArgs p) {
-    __shared__ float s_val[16];
-    __shared__ int s_idx[16];
-    __shared__ int s_token, s_ctx;
-    const prof_t prof_t0 = prof_begin(p.prof);
-    const int i = blockIdx.x;
-    const int slot = p.slot0 + i;
-    const uint16_t *lg = p.logits + (long)i * p.vocab;
-    float best = -INFINITY;
-    int best_i = 0x7fffffff;
-    int vec_end = ((uintptr_t)lg % 16 == 0) ? (p.vocab & ~7) : 0;
-    int scalar_from = vec_end;
-    if (p.tile_max) {  // uniform: 9,496 pairs instead of 151,936 logits; same rule (strictly greater wins, the lower index on a tie)
-        const f32x2 *tm = p.tile_max + (long)i * p.tiles;
-        constexpr int TM_NB = 10;
-        for (int t0 = threadIdx.x; t0 < p.tiles; t0 += 1024 * TM_NB) {
-            f32x2 pr[TM_NB];
-#pragma unroll
-            for (int j = 0; j < TM_NB; ++j) pr[j] = act_load(tm + min(t0 + j * 1024, p.tiles - 1));  // (the lm_head launch of this step wrote them)
-#pragma unroll
-            for (int j = 0; j < TM_NB; ++j) {
-                if (t0 + j * 1024 >= p.tiles) continue;
-                const float v = pr[j][0];
-                const int idx = pr[j][1] < 1.0e30f ? (int)pr[j][1] : 0x7fffffff;
-                if (v > best || (v == best && idx < best_i)) {
-                    best = v;
-                    best_i = idx;
-                }
-            }
-        }
-        vec_end = 0;
-        scalar_from = p.vocab;  // nothing of the row itself is read
-    }
-    // ONE workgroup reads the whole row (304 KB at Qwen3's vocabulary): a plain loop is a chain of 19 dependent L2 round trips
-    // (12 us in the step profile).  The loads go out ten 16-byte chunks at a time, from clamped addresses, and are looked at after:
-    // two round trips.
-    constexpr int SE_NB = 10;
-    for (int c0 = threadIdx.x * 8; c0 < vec_end; c0 += 1024 * 8 * SE_NB) {
-        u32x4 rawv[SE_NB];
-#pragma unroll
-        for (int j = 0; j < SE_NB; ++j) rawv[j] = act_load(reinterpret_cast<const u32x4 *>(lg + min(c0 + j * 8192, vec_end - 8)));
-#pragma unroll
-        for (int j = 0; j < SE_NB; ++j) {
-            const int c = c0 + j * 8192;
-            if (c >= vec_end) continue;
-            uint16_t raw[8];
-            *reinterpret_cast<u32x4 *>(raw) = rawv[j];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float v = BF16::to_float(raw[e]);
-                if (v > best) {  // strictly greater: the earliest index of a tie stays
-                    best = v;
-                    best_i = c + e;
-                }
-            }
-        }
-    }
-    for (int c = scalar_from + threadIdx.x; c < p.vocab; c += 1024) {
-        const float v = BF16::to_float(act_load(lg + c));
-        if (v > best || (v == best && c < best_i)) {
-            best = v;
-            best_i = c;
-        }
-    }
-    {   // wave-wide (maximum, lowest index that holds it) by DPP rotations instead of twelve ds_bpermute round trips: indices are
-        // below 2^24, exact as floats, so the lowest index is -max(-index) over the lanes that hold the maximum
-        const float m = wave_max(best);
-        const float cand = (best == m && best_i != 0x7fffffff) ? (float)best_i : 3.0e38f;
-        const float lowest = -wave_max(-cand);
-        best = m;
-        best_i = lowest < 1.0e30f ? (int)lowest : 0x7fffffff;
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_val[threadIdx.x >> 6] = best;
-        s_idx[threadIdx.x >> 6] = best_i;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float bv = s_val[0];
-        int bi = s_idx[0];
-        for (int w = 1; w < 16; ++w) {
-            if (s_val[w] > bv || (s_val[w] == bv && s_idx[w] < bi)) {
-                bv = s_val[w];
-                bi = s_idx[w];
-            }
-        }
-        if (bi < 0 || bi >= p.vocab) bi = 0;  // all-NaN / -inf row
-        s_token = bi;
-        int ctx_now = p.context_lens[slot];
-        if (p.live[slot]) {
-            p.tokens[slot] = bi;
-            const int n = p.produced[slot];
-            p.ring[(long)slot * p.ring_cap + (n % p.ring_cap)] = bi;
-            p.produced[slot] = n + 1;
-            if (p.advance) p.context_lens[slot] = ++ctx_now;
-        }
-        s_ctx = ctx_now;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < p.rope_half) {
-        const int pos = min(s_ctx, p.rope_positions - 1);  // the slot's NEXT position
-        p.rope_cur[(long)slot * p.rope_half + threadIdx.x] = p.rope_table[(long)pos * p.rope_half + threadIdx.x];
-    }
-    const int token = s_token;
-    const int words = p.hidden / 8;
-    const int groups = p.hidden / 128;
-    float sumsq = 0.f;
-    for (int w = threadIdx.x; w < words; w += 1024) {
-        const uint32_t packed = p.emb_w[(long)token * words + w];
-        const float scale = BF16::to_float(p.emb_s[(long)token * groups + w / 16]);
-        const float bias = BF16::to_float(p.emb_b[(long)token * groups + w / 16]);
-        uint16_t o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            o[e] = BF16::from_float((float)((packed >> (4 * e)) & 0xfu) * scale + bias);
-            const float v = BF16::to_float(o[e]);
-            sumsq += v * v;
-        }
-        *reinterpret_cast<uint4 *>(p.x + (long)slot * p.hidden + w * 8) = *reinterpret_cast<const uint4 *>(o);
-    }
-    if (p.ss_out) {  // uniform.  s_val is free again: its last readers ran before the barrier above
-        const float ws = wave_sum(sumsq);
-        if ((threadIdx.x & 63) == 0) s_val[threadIdx.x >> 6] = ws;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float tot = 0.f;
-            for (int w = 0; w < 16; ++w) tot += s_val[w];
-            p.ss_out[(long)slot * 8] = tot;
-            for (int i = 1; i < 8; ++i) p.ss_out[(long)slot * 8 + i] = 0.f;
-        }
-    }
-    prof_end(p.prof, prof_t0);
-}
-
 // Greedy id of every logits row (speculative verification): same tie rule as step_end_kernel (first maximum wins).
 //   grid = rows, block = 1024
 static __global__ __launch_bounds__(1024) void argmax_rows_kernel(const uint16_t *__restrict__ logits, int vocab,

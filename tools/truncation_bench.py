@@ -3,7 +3,11 @@ runs alternated in one process at one temperature: single-stream decode (128-tok
 one step per call.  Prints one JSON line: ms per step (best of rounds) per setting, the difference to the sampled step without
 truncation in microseconds, and the replay route each setting ran on.
 
-    python tools/truncation_bench.py [--steps 256] [--rounds 3] [--batch 64] [--out profiles/truncation.json]"""
+    python tools/truncation_bench.py [--steps 256] [--rounds 3] [--batch 64] [--out profiles/truncation.json]
+
+Under `rocprofv3 --kernel-trace` run it with TL_AQL=0 (the sampled step end is sample_step_end_kernel on either route): the run submits
+more packets than the engine's 8,192-slot AQL ring holds, and the profiler's queue interception faults on the first submission that
+wraps the ring.  (The --profile-rows runs of sampling_bench / logprobs_bench and bench.py's own rocprofv3 child stay below one ring.)"""
 
 import argparse
 import json
