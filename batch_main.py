@@ -45,6 +45,9 @@ def build_parser() -> argparse.ArgumentParser:
                             help="JSON mode: every answer is one JSON object (or any JSON value), enforced on the device per request")
     constraint.add_argument("--json-schema", default=None, metavar="FILE",
                             help="every answer is compact JSON that conforms to the schema in FILE (tiny_llm_hip.grammar.schema_regex)")
+    ap.add_argument("--stop", action="append", default=[], metavar="STRING",
+                    help="end an answer where its text holds STRING (matched on the device, across token boundaries); repeatable (16)")
+    ap.add_argument("--stop-id", action="append", type=int, default=[], metavar="N", help="end an answer at token id N; repeatable")
     ap.add_argument("--prefix-cache", nargs="?", type=int, const=0, default=None, metavar="PAGES",
                     help="keep the K / V of finished requests and reuse it for later prompts that start with the same tokens (the chat "
                          "template, a shared system prompt); PAGES caps the retained pages (default: no cap)")
@@ -106,15 +109,23 @@ def main(argv=None):
         if grammar is not None:
             sampling["grammar"] = grammar
             stops |= set(grammar.eos_ids)
-        done = batch_generate_ids(engine, encoded, limits, batch_size=args.batch_size, prefill_step=args.prefill_step,
-                                  eos_token_id=tokenizer.eos_token_id, sampling=sampling or None, base_seed=args.sampler_seed)
+        from tiny_llm_hip.stop import cli_stop_set, cut_text
+
+        stop, token_bytes = cli_stop_set(engine, tokenizer, args.stop, args.stop_id, sorted(i for i in stops if i is not None))
+        stops |= set(args.stop_id)
+        if stop is not None:  # the device ends every request: at a stop string, a stop id (the EOS ids among them) or its budget
+            done = batch_generate_ids(engine, encoded, limits, batch_size=args.batch_size, prefill_step=args.prefill_step,
+                                      sampling=sampling or None, base_seed=args.sampler_seed, stop=stop)
+        else:
+            done = batch_generate_ids(engine, encoded, limits, batch_size=args.batch_size, prefill_step=args.prefill_step,
+                                      eos_token_id=tokenizer.eos_token_id, sampling=sampling or None, base_seed=args.sampler_seed)
     finally:
         engine.close()
     results = []
     for idx, ids in done:
         if ids and ids[-1] in stops:
             ids = ids[:-1]
-        text = tokenizer.decode(ids)
+        text = cut_text(ids, token_bytes, args.stop) if args.stop else tokenizer.decode(ids)
         results.append((idx, text))
         print(f"--- {idx} ---\nQ: {prompts[idx]}\nA: {text}")
     return results

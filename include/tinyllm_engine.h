@@ -657,6 +657,76 @@ int tl_lora_rows(const void *x_dev, int rows, int in, int out, const int32_t *ro
                  int seg_mode, int seg_end0, int seg_end1, const int *tile_row0, const int *tile_rows, const int *tile_adapter, int n_tiles, int mode,
                  const void *base_or_residual_dev, void *out_dev, const void *norm_w_dev, float eps, void *stream);
 
+/* Stop conditions: stop ids, stop strings and token budgets, decided on the device (csrc/stop.h, csrc/stop_set.h).
+ * A slot may be ARMED with a stop set and a budget.  From arming on, each token t the step end COMMITS for the slot -- the first token of a
+ * prefill with want_logits, and each decode step -- is examined once, in this order:
+ *   1. generated += 1;
+ *   2. stop id   t is one of the set's ids: stop with reason TL_STOP_ID, index = the position of t in the id list.  The token's bytes do not
+ *                count as text: text_bytes is unchanged and cut_bytes = text_bytes;
+ *   3. stop string  otherwise the bytes of t (tl_vocab; a token may have none) join the slot's text and are walked through the set's
+ *                automaton one byte at a time.  With j the first byte of this token at which at least one stop string ends in the text
+ *                produced since arming: stop with reason TL_STOP_STRING, index = the LONGEST stop string ending there (the earliest
+ *                start).  text_bytes includes the whole token; cut_bytes = the text bytes before the match starts.  Matches span token
+ *                boundaries: the automaton's state is per slot, lives on the device and starts at the root at arming;
+ *   4. budget    otherwise, if max_new_tokens > 0 and generated == max_new_tokens: stop with reason TL_STOP_LENGTH, cut_bytes = text_bytes.
+ *   freeze    on a stop the slot FREEZES AT THAT TOKEN: the stopping token is the slot's pending token and the last entry of its id ring,
+ *             `produced` and the context length are as the step end left them, and from the next launch on the slot is a slot without a
+ *             running sequence, for the rest of the call and for later calls.  Context length, produced count and id ring, the
+ *             log-probability ring and its pending record, the penalty history, the grammar state / configuration, Mirostat's mu and the
+ *             sampling position stand exactly where a run that executed `generated` tokens and then stopped calling the engine would have
+ *             left them.  Other slots of the batch are unaffected, bit for bit.  (The launch clears the slot's device live word; the step
+ *             end, the log-probability record, the Mirostat update and the processing launch's count and grammar advance test it.  The
+ *             step end still leaves the uncommitted choice's embedding row as the slot's next input, so the attention launch keeps
+ *             rewriting the K/V row at position `context` of the slot: outside the context, in a page the slot owns privately or in none,
+ *             and written again from the real pending token when the slot resumes.)
+ *   sets      tl_stop_create: up to TL_MAX_STOP_IDS ids, distinct, in [0, V); up to TL_MAX_STOP_STRINGS byte strings (bytes + offsets
+ *             [n_strings + 1], offsets[0] = 0), non-empty, distinct, TL_MAX_STOP_BYTES in all; at least one id or string.  A set with
+ *             strings needs a tl_vocab (of the engine's vocabulary size: checked when a slot is armed); a set of ids needs none (v may be
+ *             NULL; its ids are checked against the engine's size when a slot is armed).  TEXT IS COUNTED IN THE SET'S VOCABULARY: a slot
+ *             armed with a set made without one, or with a budget alone, knows no token's bytes -- text_bytes and cut_bytes stay 0.  The library builds the byte automaton itself -- a
+ *             dense Aho-Corasick DFA [n_states][256] uint16 with, per state, the longest string ending there and its length -- and uploads it
+ *             once.  A set is immutable and may be shared between slots, like a tl_grammar; set and vocabulary are borrowed by the slots.
+ *   arming    tl_engine_set_stop(e, slot, set, max_new_tokens): set may be NULL (a budget alone); NULL with max_new_tokens 0 disarms.  The
+ *             call ALWAYS resets the slot's record (generated 0, automaton at the root, text 0) and clears a stopped state: it is the one
+ *             way to resume a stopped slot.  The state lives in a host mirror and per-slot device arrays poked on the engine stream between
+ *             steps; the first arming call allocates them, an engine that never arms a slot allocates nothing.
+ *   state     tl_engine_stop_state: the slot's record -- reason TL_STOP_NONE while it runs -- and its context length.  Synchronises.
+ *   plan      a step in which a running slot is armed ends with one more launch (one wave per row; an unarmed, dead or stopped row
+ *             leaves at once) in a captured plan of its own, bit 54 of the plan key.  Such a plan replays through hipGraphLaunch
+ *             (tl_engine_replay_route says so while such a slot runs): the launch reads a plain store of the step end and writes the live
+ *             word the next step's launches read.  Every other step is the program it was: same key, same launches, same route.
+ *   mirrors   the host mirrors advance per step for every running slot, so a slot that froze in mid-call leaves them ahead of the device.
+ *             A call that enqueued a stop launch is followed by a reconciliation -- wait for the stream, read the records in one copy, give
+ *             every newly stopped slot the device's context length and produced count, mark it stopped -- by tl_engine_decode before it
+ *             plans and before it returns, and by every call below that asks about a stopped state.  Pages reserved for steps the slot did
+ *             not take stay with it, as after tl_engine_reserve; release or a rewind returns them.  pages_in_use + pages_free +
+ *             pages_retained == num_pages at every return.
+ *   life      tl_engine_begin / tl_engine_release disarm; tl_engine_move carries set, record and stopped state; tl_engine_fork copies
+ *             them; park / unpark keep them (an unparked stopped slot stays stopped).  tl_engine_rewind, tl_engine_set_token and the
+ *             read calls work on a stopped slot.  tl_engine_prefill, _prefill_packed, _verify, _score, _embed and _embed_packed on a stopped
+ *             slot are TL_ERR_INVALID with nothing changed (re-arm or disarm first).  tl_engine_decode treats a stopped slot as it treats a
+ *             parked one.  Bad input anywhere is TL_ERR_INVALID with nothing changed.
+ * tl_stop_rows: the routine over caller rows, stream ordered: row i examines tokens_dev[i] under `set` (NULL: a budget alone) and
+ * max_new_dev[i], with its record states_dev[i] and automaton state automaton_dev[i] read and written in place (a fresh row: all zero).
+ * armed_dev (may be NULL: every row is armed) marks the rows that take part; an unarmed row and a row whose record already holds a reason
+ * are left bit-identical.  The record's context field is not touched. */
+#define TL_MAX_STOP_IDS 16
+#define TL_MAX_STOP_STRINGS 16
+#define TL_MAX_STOP_BYTES 1024
+enum { TL_STOP_NONE = 0, TL_STOP_ID = 1, TL_STOP_STRING = 2, TL_STOP_LENGTH = 3 };
+typedef struct tl_stop tl_stop;
+typedef struct tl_stop_state {
+    int32_t reason, index, generated, context;
+    uint32_t text_bytes, cut_bytes;
+} tl_stop_state;
+int tl_stop_create(const tl_vocab *v, const int32_t *ids, int n_ids, const uint8_t *bytes, const int32_t *offsets, int n_strings, void *stream,
+                   tl_stop **out);
+void tl_stop_destroy(tl_stop *s);
+int tl_engine_set_stop(tl_engine *e, int slot, const tl_stop *set, int max_new_tokens);
+int tl_engine_stop_state(tl_engine *e, int slot, tl_stop_state *out);
+int tl_stop_rows(const tl_stop *set, const int32_t *tokens_dev, int rows, const int32_t *armed_dev, const int32_t *max_new_dev,
+                 int32_t *automaton_dev, tl_stop_state *states_dev, void *stream);
+
 /* Run `steps` decode steps over the live slots [0, batch): each step feeds every
  * slot's pending token at position context_len, appends K/V, and leaves the next
  * token as the next pending token: the argmax, or, for a slot with a nonzero
@@ -676,7 +746,9 @@ int tl_lora_rows(const void *x_dev, int rows, int in, int out, const int32_t *ro
  * "hipgraph" route (TL_AQL=0, or a plan the AQL route does not take) and with
  * use_graph = 0 the call only enqueues on the engine stream and does not
  * synchronise: a caller that overlaps host work with decode steps (a draft
- * model free-running beside its target) wants that route.
+ * model free-running beside its target) wants that route.  A call in which a
+ * running slot is armed with stop conditions (tl_engine_set_stop) RETURNS
+ * SYNCHRONISED on every route: it reads the stop records before it returns.
  * Must be called with the engine's own device current (the one current at
  * tl_engine_create): anything else is TL_ERR_INVALID. */
 int tl_engine_decode(tl_engine *e, int batch, int steps, int use_graph);

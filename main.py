@@ -53,6 +53,11 @@ def build_parser() -> argparse.ArgumentParser:
     constraint.add_argument("--json-schema", default=None, metavar="FILE",
                             help="with --solution engine: the answer is compact JSON that conforms to the schema in FILE (the "
                                  "non-recursive subset of tiny_llm_hip.grammar.schema_regex)")
+    ap.add_argument("--stop", action="append", default=[], metavar="STRING",
+                    help="with --solution engine: end the answer where its text holds STRING (matched on the device, across token "
+                         "boundaries; the text is printed up to the match); repeat the flag for up to 16 strings")
+    ap.add_argument("--stop-id", action="append", type=int, default=[], metavar="N",
+                    help="with --solution engine: end the answer at token id N (not printed); repeatable")
     ap.add_argument("--enable-thinking", action="store_true")
     ap.add_argument("--raw-prompt", action="store_true", help="do not wrap the prompt in the chat template")
     ap.add_argument("--max-new-tokens", type=int, default=256)
@@ -114,6 +119,7 @@ def main(argv=None) -> str:
     records = None
     grammar = None
     lora = None
+    stop, token_bytes = None, None
     try:
         if args.lora:
             if args.draft_model:
@@ -124,6 +130,12 @@ def main(argv=None) -> str:
             from tiny_llm_hip.grammar import cli_grammar
 
             grammar = cli_grammar(engine, tokenizer, args.regex, args.json, args.json_schema)
+            from tiny_llm_hip.stop import cli_stop_set
+
+            # (the EOS ids join the set: the device ends the request at whichever comes first)
+            stop, token_bytes = cli_stop_set(engine, tokenizer, args.stop, args.stop_id, [eos, *(grammar.eos_ids if grammar is not None else ())])
+        elif args.stop or args.stop_id:
+            print("note: --stop and --stop-id do not apply with a draft model")
         if args.draft_model:
             draft_model, draft_tok = load(args.draft_model)
             if draft_tok.get_vocab() != tokenizer.get_vocab():
@@ -137,7 +149,8 @@ def main(argv=None) -> str:
                                                proposal_length=min(args.proposal_length, 7), eos_token_id=eos)
             finally:
                 draft.close()
-        elif args.sampler_temp and (args.sampler_seed is not None or lora is not None or penalties != (1.0, 0.0, 0.0) or grammar is not None or truncates):
+        elif args.sampler_temp and (args.sampler_seed is not None or lora is not None or penalties != (1.0, 0.0, 0.0) or grammar is not None or truncates
+                                    or stop is not None):
             # the per-slot sampler on the device: the whole generation in one prefill + one decode(N) call.  The penalties and the
             # grammar exist on the device only, so they select this path; so do min-p, typical-p and Mirostat
             if args.sampler_seed is None:
@@ -146,7 +159,7 @@ def main(argv=None) -> str:
                                   top_p=args.sampler_top_p, seed=args.sampler_seed or 0, logprobs=args.logprobs,
                                   repetition_penalty=penalties[0], presence_penalty=penalties[1], frequency_penalty=penalties[2],
                                   grammar=grammar, min_p=args.sampler_min_p, typical_p=args.sampler_typical_p,
-                                  mirostat_tau=args.mirostat_tau, mirostat_eta=args.mirostat_eta, lora=lora)
+                                  mirostat_tau=args.mirostat_tau, mirostat_eta=args.mirostat_eta, lora=lora, stop=stop)
             if args.logprobs is not None:
                 out, records = out
             out = cut_at_eos(out, eos, grammar)
@@ -154,10 +167,11 @@ def main(argv=None) -> str:
             out = sample_with_engine(engine, ids, args, eos)
         else:
             out = engine.generate(ids, args.max_new_tokens, logprobs=args.logprobs, repetition_penalty=penalties[0],
-                                  presence_penalty=penalties[1], frequency_penalty=penalties[2], grammar=grammar, lora=lora)
+                                  presence_penalty=penalties[1], frequency_penalty=penalties[2], grammar=grammar, lora=lora, stop=stop)
             if args.logprobs is not None:
                 out, records = out
             out = cut_at_eos(out, eos, grammar)
+        ended = engine.last_stop_state if stop is not None else None
     finally:
         engine.close()
     if records is not None:
@@ -166,7 +180,12 @@ def main(argv=None) -> str:
             print(f"{tokenizer.decode([t])!r}\t{r.logprob:.4f}\t{alts}")
     elif args.logprobs is not None:
         print("note: --logprobs applies to the engine's greedy decode and its device sampler (--sampler-seed) only")
-    text = tokenizer.decode(out)
+    if ended is not None and ended.reason == "string":  # the text up to the matched string, as the device counted it
+        from tiny_llm_hip.stop import cut_text
+
+        text = cut_text(out, token_bytes, cut_bytes=ended.cut_bytes)
+    else:
+        text = tokenizer.decode(out[:-1] if ended is not None and ended.reason == "id" and out and out[-1] in args.stop_id else out)
     print(text)
     return text
 

@@ -22,6 +22,8 @@
 #include "pool.h"
 #include "lora.h"
 #include "slot_table.h"
+#include "stop.h"
+#include "stop_set.h"
 
 namespace tl {
 
@@ -103,6 +105,14 @@ struct tl_grammar {
         }
         return c;
     }
+};
+
+// a stop set (tl_stop_create; stop_set.h builds it, stop.h reads it): the host copy for validation, one device allocation for the kernel
+struct tl_stop {
+    StopSet set;
+    const tl_vocab *vocab = nullptr;  // the vocabulary the text is counted and the strings are matched in (borrowed); may be null for a set of ids
+    char *mem = nullptr;
+    StopDev *dev = nullptr;  // what a slot's pointer is poked to
 };
 
 struct tl_engine {
@@ -267,6 +277,21 @@ struct tl_engine {
     uint16_t *lora_tmp = nullptr;
     long lora_steps = 0, lora_prefill_rows = 0;
     bool lora_slot(int slot) const { return lora_of[slot] >= 0; }
+    // stop conditions (tl_engine_set_stop, stop.h): per slot the host mirror of (set, budget, armed) and the records as the last
+    // reconciliation read them; allocated by the first call that arms a slot: the per-slot set pointers, armed words, budgets, automaton
+    // states and records.  stop_dirty: a stop launch was enqueued since the records were last read (stop_reconcile)
+    struct StopSlot {
+        const tl_stop *set = nullptr;
+        int max_new = 0;
+        bool armed = false;
+    };
+    std::vector<StopSlot> stop;
+    std::vector<StopRecord> stop_host;
+    char *stop_mem = nullptr;
+    const StopDev **stop_sets = nullptr;
+    int32_t *stop_armed = nullptr, *stop_max_new = nullptr, *stop_automaton = nullptr;
+    StopRecord *stop_rec = nullptr;
+    bool stop_dirty = false;
 
     bool warmed = false;
     std::map<std::pair<int, long>, hipGraphExec_t> graphs;  // (batch, n_splits << 32 | tokens_per_split)
@@ -640,7 +665,8 @@ static void launch_logit_process(tl_engine *e, const uint16_t *logits, uint16_t 
                                  bool stack, ProfCtx *pc) {
     const LogitProcessArgs a{logits, out, e->cfg.vocab_size, slot0, e->pen_history, e->pen_rep, e->pen_pres, e->pen_freq, e->pen_bias_n,
                              e->pen_bias_ids, e->pen_bias_values, tokens, pc ? pc->buf : nullptr,
-                             grammar ? e->gr_ptr : nullptr, grammar ? e->gr_state : nullptr, grammar ? e->context_lens : nullptr};
+                             grammar ? e->gr_ptr : nullptr, grammar ? e->gr_state : nullptr, grammar ? e->context_lens : nullptr,
+                             tokens ? e->live : nullptr};
     const dim3 grid(ceil_div(e->cfg.vocab_size, LPR_CHUNK), rows);
     if (stack) hipLaunchKernelGGL(logit_process_stack_kernel, grid, dim3(LPR_THREADS), 0, e->stream, LogitProcessStackArgs{a, e->gr_stack});
     else if (grammar) hipLaunchKernelGGL(logit_process_kernel<true>, grid, dim3(LPR_THREADS), 0, e->stream, a);
@@ -799,12 +825,99 @@ static int lora_group(tl_engine *e, int l, int group, const LoraTile *tiles_dev,
     return lora_apply(c, e->stream);
 }
 
+// ---- stop conditions (stop.h) ---------------------------------------------------------------------------------------
+// the slot, taking part in a step, is armed: the step ends with the stop launch, in a plan of its own that keeps the hipGraphLaunch route
+// (the launch reads the token the step end stored and writes the live word the next step's launches read)
+static bool step_stop_slot(const tl_engine *e, int slot) { return e->stop_mem && e->slot_runs(slot) && e->stop[slot].armed; }
+
+// the per-slot arrays, all zero (unarmed, no budget, automaton at the root, empty records): made by the first call that arms a slot
+static int stop_alloc(tl_engine *e) {
+    if (e->stop_mem) return TL_OK;
+    const size_t B = (size_t)e->cfg.max_batch;
+    Carve carve;
+    const size_t o_sets = carve(B * sizeof(StopDev *)), o_armed = carve(B * 4), o_max = carve(B * 4), o_state = carve(B * 4), o_rec = carve(B * sizeof(StopRecord));
+    char *m = nullptr;
+    if (hipMalloc((void **)&m, carve.off) != hipSuccess) return fail(TL_ERR_HIP, "engine_set_stop: hipMalloc(stop records) failed");
+    if (hipMemsetAsync(m, 0, carve.off, e->stream) != hipSuccess) {
+        (void)hipFree(m);
+        return fail(TL_ERR_HIP, "engine_set_stop: memset(stop records) failed");
+    }
+    e->stop_mem = m;
+    e->stop_sets = (const StopDev **)(m + o_sets);
+    e->stop_armed = (int32_t *)(m + o_armed), e->stop_max_new = (int32_t *)(m + o_max), e->stop_automaton = (int32_t *)(m + o_state);
+    e->stop_rec = (StopRecord *)(m + o_rec);
+    e->stop_host.assign(B, StopRecord{});
+    e->stats.workspace_bytes += carve.off;
+    return TL_OK;
+}
+
+// Host mirrors after a stop.  The mirrors advance per step for every running slot, so a slot that froze in mid-call leaves them ahead of
+// the device.  Behind any call that enqueued a stop launch: wait for the stream (and the AQL queue), read the records in one copy, and
+// for every slot that newly stopped take the device's context length -- `produced` went up with it, one per step -- and mark the slot
+// stopped (slot_table.h).  Pages reserved for steps the slot did not take stay with it, as after tl_engine_reserve.
+static int stop_reconcile(tl_engine *e) {
+    if (!e->stop_dirty) return TL_OK;
+    TL_TRY(aql_drain(e));
+    TL_HIP(hipStreamSynchronize(e->stream));
+    TL_HIP(hipMemcpy(e->stop_host.data(), e->stop_rec, e->stop_host.size() * sizeof(StopRecord), hipMemcpyDeviceToHost));
+    e->stop_dirty = false;
+    for (int b = 0; b < e->cfg.max_batch; ++b) {
+        const Slot &s = e->table.slots[b];
+        if (!s.live || s.stopped || !e->stop[b].armed || e->stop_host[b].reason == STOP_NONE) continue;
+        const int ctx = e->stop_host[b].context;
+        e->table.stop(b, ctx, s.produced - (s.ctx - ctx));
+    }
+    return TL_OK;
+}
+
+// the slot's device words: set pointer, armed, budget, automaton at the root, an empty record
+static void stop_poke(tl_engine *e, int slot, const tl_engine::StopSlot &v, Pokes &pk) {
+    poke_u64(pk, e->stop_sets + slot, (uint64_t)(uintptr_t)(v.set ? v.set->dev : nullptr));
+    pk.emplace_back(e->stop_armed + slot, v.armed ? 1 : 0);
+    pk.emplace_back(e->stop_max_new + slot, v.max_new);
+    pk.emplace_back(e->stop_automaton + slot, 0);
+    for (int w = 0; w < (int)(sizeof(StopRecord) / 4); ++w) pk.emplace_back((int32_t *)(e->stop_rec + slot) + w, 0);
+}
+// begin / release: the slot is unarmed and its record empty (the table's slot starts over: not stopped)
+static int stop_reset(tl_engine *e, int slot) {
+    if (!e->stop_mem || !e->stop[slot].armed) return TL_OK;
+    e->stop[slot] = tl_engine::StopSlot{};
+    e->stop_host[slot] = StopRecord{};
+    Pokes pk;
+    stop_poke(e, slot, e->stop[slot], pk);
+    return poke(e, pk);
+}
+// tl_engine_move (move = true) / tl_engine_fork: dst takes src's set, budget, record and automaton state (the table carried `stopped`);
+// a move leaves src unarmed
+static int stop_carry(tl_engine *e, int src, int dst, bool move) {
+    if (!e->stop_mem || (!e->stop[src].armed && !e->stop[dst].armed)) return TL_OK;
+    e->stop[dst] = e->stop[src];
+    e->stop_host[dst] = e->stop_host[src];
+    Pokes pk;
+    poke_u64(pk, e->stop_sets + dst, (uint64_t)(uintptr_t)(e->stop[dst].set ? e->stop[dst].set->dev : nullptr));
+    pk.emplace_back(e->stop_armed + dst, e->stop[dst].armed ? 1 : 0);
+    pk.emplace_back(e->stop_max_new + dst, e->stop[dst].max_new);
+    TL_TRY(poke(e, pk));
+    TL_HIP(hipMemcpyAsync(e->stop_automaton + dst, e->stop_automaton + src, 4, hipMemcpyDeviceToDevice, e->stream));
+    TL_HIP(hipMemcpyAsync(e->stop_rec + dst, e->stop_rec + src, sizeof(StopRecord), hipMemcpyDeviceToDevice, e->stream));
+    return move ? stop_reset(e, src) : TL_OK;
+}
+
+// the stop launch over `rows` rows for slots slot0 .., behind the step end (and the Mirostat update)
+static void launch_stop(tl_engine *e, int rows, int slot0, ProfCtx *pc) {
+    const StopArgs a{e->tokens, slot0, e->stop_sets, nullptr, e->stop_armed, e->stop_max_new, e->stop_automaton, e->stop_rec, e->live, e->context_lens,
+                     pc ? pc->buf : nullptr};
+    hipLaunchKernelGGL(stop_check_kernel, dim3(rows), dim3(64), 0, e->stream, a);
+    if (pc) prof_after(pc, 7, rows);
+    e->stop_dirty = true;
+}
+
 // ---- which launches a step needs ---------------------------------------------------------------------------------------------------
 // One record for slots [slot0, slot0 + n), re-derived from the slots' parameters by every call that enqueues or replays a step: the
 // per-slot predicates above, ORed.  A decode step asks over [0, batch), a prefill's first token over its one slot.
 struct StepFeatures {
     bool samples = false, logprobs = false, processes = false, grammar = false, stack_grammar = false, truncates = false, mirostat = false,
-         lora = false;
+         lora = false, stop = false;
     // the bits a decode plan's key carries above its split plan (tl_engine_decode): with all clear the step is the greedy program
     long key_bits() const {
         // bit 62: the step ends with the sampling twin of step_end_kernel, bit 61: with the logprob twin (step_end.h)
@@ -816,7 +929,9 @@ struct StepFeatures {
                // bit 56: ... and a slot has Mirostat on (the plan keeps the hipGraphLaunch route)
                (truncates ? (1L << 57) : 0L) | (mirostat ? (1L << 56) : 0L) |
                // bit 55: a slot carries a LoRA adapter: the adapter plan (lora.h; hipGraphLaunch)
-               (lora ? (1L << 55) : 0L);
+               (lora ? (1L << 55) : 0L) |
+               // bit 54: a slot is armed with stop conditions: the stop launch (stop.h) stands last (hipGraphLaunch)
+               (stop ? (1L << 54) : 0L);
     }
 };
 static StepFeatures step_features(const tl_engine *e, int slot0, int n) {
@@ -831,13 +946,14 @@ static StepFeatures step_features(const tl_engine *e, int slot0, int n) {
         f.truncates |= step_truncates_slot(e, slot);
         f.mirostat |= step_mirostat_slot(e, slot);  // (only with truncates)
         f.lora |= step_lora_slot(e, slot);
+        f.stop |= step_stop_slot(e, slot);
     }
     return f;
 }
 
 // The chain behind the lm_head over `rows` raw rows -- rows [row0, row0 + rows) of the engine's row buffers, slots slot0 .. -- in the one
 // order a decode step and a prefill's first token share: processing (logit_process.h), truncation (truncate.h), the step end, the
-// Mirostat update, each where `f` has it.
+// Mirostat update, the stop check (stop.h), each where `f` has it.
 //   advance, x, ss_out: the step end's context advance, where the next embedding rows go and their sums of squares (step_end_args)
 //   tile_max, tiles: the lm_head's per-tile pairs; they describe the raw rows, so only a step that neither processes nor truncates uses them
 //   tokens: the pending tokens a decode step's processing launch counts first (e->tokens); a prefill's row has none (null)
@@ -858,6 +974,7 @@ static void launch_logit_chain(tl_engine *e, const uint16_t *raw, int row0, int 
     launch_step_end(e, s, rows, f.samples, f.logprobs, choice != raw ? raw : nullptr);  // (the logprob twin records from the raw rows)
     if (pc) prof_after(pc, 7, rows);
     if (f.truncates) launch_mirostat_update(e, choice, rows, slot0, row0, pc);
+    if (f.stop) launch_stop(e, rows, slot0, pc);
 }
 
 struct SplitPlan {
@@ -1345,6 +1462,15 @@ static int slot_check_unparked(const tl_engine *e, int slot) {
     if (!e) return fail(TL_ERR_INVALID, "engine: null engine");
     return table_rc(e->table.check_unparked(slot));
 }
+// ... for the calls that feed the slot tokens (prefill, packed prefill, verify, score, embed): a slot a stop has frozen takes none
+// until tl_engine_set_stop resumes it; what an earlier call's stop launch decided is read first
+static int slot_check_feeds(tl_engine *e, int slot) {
+    if (!e) return fail(TL_ERR_INVALID, "engine: null engine");
+    TL_TRY(stop_reconcile(e));
+    TL_TRY(table_rc(e->table.check_unparked(slot)));
+    if (e->table.slots[slot].stopped) return fail(TL_ERR_INVALID, "engine: the slot has stopped (tl_engine_set_stop re-arms or disarms it first)");
+    return TL_OK;
+}
 
 // ---- the per-slot settings across the lifecycle: sampling, log-probability records, penalties / bias / grammar, the pending token ----
 // begin / release: everything back to the defaults (each skipped while it is the default already)
@@ -1355,6 +1481,7 @@ static int settings_reset(tl_engine *e, int slot) {
     TL_TRY(pen_reset(e, slot));
     TL_TRY(trn_reset(e, slot));
     TL_TRY(lora_write(e, slot, LORA_NONE));
+    TL_TRY(stop_reset(e, slot));
     return smp_reset(e, slot);
 }
 // fork / move (move = true): dst takes what src has, and a move leaves src at the defaults
@@ -1377,6 +1504,8 @@ static int settings_carry(tl_engine *e, int src, int dst, bool move) {
     TL_TRY(pen_carry(e, src, dst, move));
     // ... the truncation parameters with Mirostat's mu
     TL_TRY(trn_carry(e, src, dst, move));
+    // ... the stop set, its record and the automaton's state
+    TL_TRY(stop_carry(e, src, dst, move));
     // ... and the LoRA adapter
     TL_TRY(lora_write(e, dst, e->lora_of[src]));
     return move ? lora_write(e, src, LORA_NONE) : TL_OK;
@@ -1732,6 +1861,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->gr_pending.assign(c.max_batch, 0);
     e->emb_rows.assign(c.max_batch, -1);
     e->lora_of.assign(c.max_batch, LORA_NONE);
+    e->stop.assign(c.max_batch, tl_engine::StopSlot{});
     e->stats.kv_bytes = e->kv_bytes;
     e->stats.workspace_bytes = e->arena_bytes + e->tiled_bytes + e->bf16w_bytes;
     *out = e;
@@ -1840,6 +1970,7 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     for (auto &r : e->lora_ad)
         if (r.mem) (void)hipFree(r.mem);
     if (e->lora_mem) (void)hipFree(e->lora_mem);
+    if (e->stop_mem) (void)hipFree(e->stop_mem);
     if (e->kpool) (void)hipFree(e->kpool);
     if (e->vpool) (void)hipFree(e->vpool);
     if (e->kscale_pool) (void)hipFree(e->kscale_pool);
@@ -1866,6 +1997,7 @@ extern "C" const char *tl_engine_replay_route(const tl_engine *e) {
     const StepFeatures f = step_features(e, 0, e->cfg.max_batch);
     if (e->aql_on && f.mirostat) text = "hipgraph: a Mirostat slot is live (the update launch reads the token the step end stored)";
     if (e->aql_on && f.lora) text = "hipgraph: a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)";
+    if (e->aql_on && f.stop) text = "hipgraph: a slot is armed with stop conditions (the stop launch reads the token the step end stored and writes the live word)";
     return text.c_str();
 }
 
@@ -1928,11 +2060,12 @@ extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
 // never written again -- and a partially filled tail page is copied, so both sequences can append independently.
 extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
     TL_REQUIRE(e, "engine: null engine");
+    TL_TRY(stop_reconcile(e));
     SlotEdits ed;
     Pokes pk;
     TL_TRY(table_rc(e->table.fork(src, dst, ed)));
     TL_TRY(apply_edits(e, ed, pk));
-    pk.emplace_back(e->live + dst, 1);
+    pk.emplace_back(e->live + dst, e->table.slots[dst].stopped ? 0 : 1);  // (a stopped sequence's copy is stopped: no sequence to a step)
     pk.emplace_back(e->context_lens + dst, e->table.slots[dst].ctx);
     pk.emplace_back(e->produced + dst, 0);
     TL_TRY(poke(e, pk));
@@ -2037,6 +2170,7 @@ extern "C" int tl_engine_prefix_attach(tl_engine *e, int slot, const int32_t *to
 // block-table row, context length and pending token change hands — no K/V byte moves.
 extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
     TL_REQUIRE(e, "engine: null engine");
+    TL_TRY(stop_reconcile(e));
     SlotEdits ed;
     Pokes pk;
     TL_TRY(table_rc(e->table.move(src, dst, ed)));
@@ -2045,7 +2179,7 @@ extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
     const Slot &d = e->table.slots[dst];
     pk.emplace_back(e->context_lens + dst, d.parked ? 0 : d.ctx);
     pk.emplace_back(e->context_lens + src, 0);
-    pk.emplace_back(e->live + dst, d.parked ? 0 : 1);
+    pk.emplace_back(e->live + dst, d.parked || d.stopped ? 0 : 1);  // (a stopped sequence stays stopped at dst)
     pk.emplace_back(e->live + src, 0);
     pk.emplace_back(e->produced + dst, 0);
     TL_TRY(poke(e, pk));
@@ -2111,6 +2245,7 @@ extern "C" int tl_engine_swap_space(tl_engine *e, int host_pages) {
 
 extern "C" int tl_engine_park(tl_engine *e, int slot) {
     TL_REQUIRE(e, "engine: null engine");
+    TL_TRY(stop_reconcile(e));
     TL_TRY(table_rc(e->table.park_begin(slot)));
     const tl_engine_config &c = e->cfg;
     const Slot &s = e->table.slots[slot];
@@ -2175,7 +2310,7 @@ extern "C" int tl_engine_unpark(tl_engine *e, int slot) {
                                     e->swap_staging, rec, e->stream));
     }
     pk.emplace_back(e->context_lens + slot, ctx);
-    pk.emplace_back(e->live + slot, 1);
+    pk.emplace_back(e->live + slot, e->table.slots[slot].stopped ? 0 : 1);  // (an unparked stopped slot stays stopped)
     TL_TRY(poke(e, pk));
     return e->pen[slot].processes() ? pen_device_switch(e, slot, true) : TL_OK;
 }
@@ -2563,6 +2698,100 @@ extern "C" int tl_engine_grammar_config(tl_engine *e, int slot, int *state, int 
     }
     *state = c.state, *depth = c.depth, *stack = c.stack;
     if (accepting) *accepting = c.state < 0 || g->accepting[c.state] ? 1 : 0;
+    return TL_OK;
+}
+
+// ---- stop conditions (include/tinyllm_engine.h "Stop conditions"; the automaton is stop_set.h, the launch stop.h) ---------------------
+extern "C" int tl_stop_create(const tl_vocab *v, const int32_t *ids, int n_ids, const uint8_t *bytes, const int32_t *offsets, int n_strings,
+                              void *stream, tl_stop **out) {
+    TL_REQUIRE(out, "stop_create: null argument");
+    *out = nullptr;
+    TL_REQUIRE(n_strings <= 0 || v, "stop_create: stop strings need a vocabulary (tl_vocab_create)");
+    auto s = std::make_unique<tl_stop>();
+    if (const char *why = stop_set_build(v ? v->vocab : 0, ids, n_ids, bytes, offsets, n_strings, s->set)) return fail(TL_ERR_INVALID, why);
+    const StopSet &h = s->set;
+    s->vocab = v;
+    Carve carve;
+    const size_t o_dev = carve(sizeof(StopDev)), o_ids = carve(h.ids.size() * 4 + 4), o_table = carve(h.table.size() * 2 + 2),
+                 o_match = carve(h.match.size() * 2 + 2), o_len = carve(h.match_len.size() * 2 + 2);
+    if (hipMalloc((void **)&s->mem, carve.off) != hipSuccess) return fail(TL_ERR_HIP, "stop_create: hipMalloc failed");
+    StopDev d{};
+    d.ids = (const int32_t *)(s->mem + o_ids);
+    d.n_ids = (int)h.ids.size(), d.max_len = h.max_len, d.n_states = h.n_states;
+    if (h.n_strings) {
+        d.table = (const uint16_t *)(s->mem + o_table), d.match = (const int16_t *)(s->mem + o_match), d.match_len = (const uint16_t *)(s->mem + o_len);
+    }
+    if (v) d.offsets = v->offsets_dev, d.bytes = v->bytes_dev, d.vocab = v->vocab;
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t he = hipMemcpyAsync(s->mem + o_dev, &d, sizeof(d), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && !h.ids.empty()) he = hipMemcpyAsync(s->mem + o_ids, h.ids.data(), h.ids.size() * 4, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && h.n_strings) he = hipMemcpyAsync(s->mem + o_table, h.table.data(), h.table.size() * 2, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && h.n_strings) he = hipMemcpyAsync(s->mem + o_match, h.match.data(), h.match.size() * 2, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && h.n_strings) he = hipMemcpyAsync(s->mem + o_len, h.match_len.data(), h.match_len.size() * 2, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);  // (the copies read this frame's `d`)
+    if (he != hipSuccess) {
+        (void)hipFree(s->mem);
+        return fail(TL_ERR_HIP, std::string("stop_create: ") + hipGetErrorString(he));
+    }
+    s->dev = (StopDev *)(s->mem + o_dev);
+    *out = s.release();
+    return TL_OK;
+}
+
+extern "C" void tl_stop_destroy(tl_stop *s) {
+    if (!s) return;
+    if (s->mem) (void)hipFree(s->mem);
+    delete s;
+}
+
+extern "C" int tl_engine_set_stop(tl_engine *e, int slot, const tl_stop *set, int max_new_tokens) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(max_new_tokens >= 0, "engine_set_stop: max_new_tokens must be nonnegative (0 = no budget)");
+    if (set) {
+        TL_REQUIRE(!set->vocab || set->vocab->vocab == e->cfg.vocab_size, "engine_set_stop: the set's vocabulary is not the engine's size");
+        for (int32_t id : set->set.ids) TL_REQUIRE(id < e->cfg.vocab_size, "engine_set_stop: a stop id lies outside the engine's vocabulary");
+    }
+    TL_TRY(stop_reconcile(e));
+    const bool arm = set != nullptr || max_new_tokens > 0;
+    Slot &s = e->table.slots[slot];
+    if (!arm && !e->stop_mem) return TL_OK;  // disarming on an engine that never armed a slot: nothing to write
+    TL_TRY(stop_alloc(e));
+    e->stop[slot] = tl_engine::StopSlot{set, max_new_tokens, arm};
+    e->stop_host[slot] = StopRecord{};
+    Pokes pk;
+    stop_poke(e, slot, e->stop[slot], pk);
+    if (s.stopped) {  // the one way to resume: a decode step takes the slot again
+        e->table.resume(slot);
+        if (!s.parked) pk.emplace_back(e->live + slot, 1);
+    }
+    return poke(e, pk);
+}
+
+extern "C" int tl_engine_stop_state(tl_engine *e, int slot, tl_stop_state *out) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_REQUIRE(out, "engine_stop_state: null argument");
+    TL_TRY(stop_reconcile(e));
+    *out = tl_stop_state{};
+    out->context = e->table.slots[slot].ctx;
+    if (!e->stop_mem || !e->stop[slot].armed) return TL_OK;
+    if (!e->table.slots[slot].stopped) {  // a running slot's record: read now (a stopped slot's was read when it stopped)
+        TL_TRY(aql_drain(e));
+        TL_HIP(hipStreamSynchronize(e->stream));
+        TL_HIP(hipMemcpy(&e->stop_host[slot], e->stop_rec + slot, sizeof(StopRecord), hipMemcpyDeviceToHost));
+    }
+    const StopRecord &r = e->stop_host[slot];
+    *out = tl_stop_state{r.reason, r.index, r.generated, e->table.slots[slot].ctx, r.text_bytes, r.cut_bytes};
+    return TL_OK;
+}
+
+extern "C" int tl_stop_rows(const tl_stop *set, const int32_t *tokens_dev, int rows, const int32_t *armed_dev, const int32_t *max_new_dev,
+                            int32_t *automaton_dev, tl_stop_state *states_dev, void *stream) {
+    TL_REQUIRE(tokens_dev && max_new_dev && automaton_dev && states_dev, "stop_rows: null argument");
+    TL_REQUIRE(rows > 0 && rows <= 65535, "stop_rows: rows out of range");
+    static_assert(sizeof(tl_stop_state) == sizeof(StopRecord), "tl_stop_state is the device record");
+    const StopArgs a{tokens_dev, 0, nullptr, set ? set->dev : nullptr, armed_dev, max_new_dev, automaton_dev, (StopRecord *)states_dev, nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(stop_check_kernel, dim3(rows), dim3(64), 0, (hipStream_t)stream, a);
+    TL_CHECK_LAUNCH("stop_rows");
     return TL_OK;
 }
 
@@ -3045,7 +3274,7 @@ static int prefill_first_token(tl_engine *e, int slot, int row, const char *what
 // land in e->verify_ids, nothing is recorded; speculative verification), 3 = every row scored (tl_engine_score: the log-probability
 // of e->score_ids[i] and the greedy id of every row into e->score_lp / e->score_argmax, nothing recorded, e->logits untouched)
 static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, int logits_mode) {
-    TL_TRY(slot_check_unparked(e, slot));
+    TL_TRY(slot_check_feeds(e, slot));
     TL_REQUIRE(tokens && n > 0, "engine_prefill: need at least one token");
     TL_REQUIRE(n <= e->cfg.max_prefill_rows, "engine_prefill: chunk exceeds max_prefill_rows");
     const tl_engine_config &c = e->cfg;
@@ -3092,7 +3321,7 @@ static int packed_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t
     int total = 0;
     size_t extra_pages = 0;
     for (int i = 0; i < n_seqs; ++i) {
-        TL_TRY(slot_check_unparked(e, slots[i]));
+        TL_TRY(slot_check_feeds(e, slots[i]));
         TL_REQUIRE(lens[i] > 0, w + "every sequence needs at least one token");
         for (int j = 0; j < i; ++j) TL_REQUIRE(slots[j] != slots[i], w + "a slot appears twice");
         const Slot &s = e->table.slots[slots[i]];
@@ -3165,7 +3394,7 @@ extern "C" int tl_engine_score(tl_engine *e, int slot, const int32_t *tokens, in
     TL_REQUIRE(n >= 1 && n <= e->cfg.max_prefill_rows, "engine_score: between 1 and max_prefill_rows tokens per call");
     TL_REQUIRE(next_token < e->cfg.vocab_size, "engine_score: next_token out of range");
     TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_score: vocabulary larger than the routine's 524,288 tokens");
-    TL_TRY(slot_check_unparked(e, slot));
+    TL_TRY(slot_check_feeds(e, slot));
     if (!e->score_logits) {
         const size_t R = (size_t)e->cfg.max_prefill_rows, logit_bytes = align_up((size_t)SCORE_BLOCK_ROWS * e->cfg.vocab_size * 2, 256);
         if (hipMalloc((void **)&e->score_logits, logit_bytes + R * 12) != hipSuccess) return fail(TL_ERR_HIP, "engine_score: hipMalloc(scratch) failed");
@@ -3265,7 +3494,7 @@ extern "C" int tl_engine_embed_packed(tl_engine *e, int n_seqs, const int *slots
 extern "C" int tl_engine_embed(tl_engine *e, int slot, const int32_t *tokens, int n, int finish, int pooling, int normalize, int dim,
                                float *out_host) {
     TL_REQUIRE(e && tokens, "engine_embed: null argument");
-    TL_TRY(slot_check_unparked(e, slot));
+    TL_TRY(slot_check_feeds(e, slot));
     TL_TRY(embed_args_check(e, pooling, dim, finish != 0, out_host));
     const PrefillSeq seq{slot, e->table.slots[slot].ctx, 0, n};
     if (pooling == TL_POOL_MEAN) TL_TRY(embed_mean_check(e, &seq, 1));
@@ -3276,7 +3505,7 @@ extern "C" int tl_engine_embed(tl_engine *e, int slot, const int32_t *tokens, in
 extern "C" int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, int n, int32_t *out_ids) {
     TL_REQUIRE(e && out_ids, "engine_verify: null argument");
     TL_REQUIRE(n >= 1 && n <= 8, "engine_verify: between 1 and 8 tokens per call (the paged decode kernel's query rows)");
-    TL_TRY(slot_check_unparked(e, slot));
+    TL_TRY(slot_check_feeds(e, slot));
     TL_REQUIRE(!e->smp[slot].samples(), "engine_verify: the slot samples (verification is greedy; set temperature 0 first)");
     TL_REQUIRE(!e->pen[slot].processes(), "engine_verify: the slot processes its logits (verification takes the raw rows; make it neutral first)");
     TL_TRY(prefill_impl(e, slot, tokens, n, 2));
@@ -3356,10 +3585,12 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
         TL_HIP(hipGetDevice(&dev_now));
         TL_REQUIRE(dev_now == e->device, "engine_decode: the current HIP device is not the device this engine was created on");
     }
+    TL_TRY(stop_reconcile(e));  // (a prefill's first token may have stopped its slot: the plan below asks the table)
     // input activations of the first step come from the pending token ids
     launch_embed_slots(e, batch);
     TL_CHECK_LAUNCH("engine embed");
     const StepFeatures f = step_features(e, 0, batch);
+    if (f.stop) e->stop_dirty = true;  // (a replayed plan launches the stop check without passing through launch_stop)
     bool on_queue = false;  // steps of this call are in flight on the AQL queue (the stream is idle and must stay so until they are drained)
     for (int s = 0; s < steps; ++s) {
         SplitPlan sp;
@@ -3397,7 +3628,9 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
                     e->aql_why = f.lora ? "a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)"
                                       : "a hand-over of this plan lives in a shared buffer (written more than once per step)";
                 if (ie == hipSuccess && e->aql_on && e->step_written_once && f.mirostat) e->aql_why = "a Mirostat slot is live (the update launch reads the token the step end stored)";
-                if (ie == hipSuccess && e->aql_on && e->step_written_once && !f.mirostat) {  // the same nodes as packet templates (aql.h); a plan that cannot be built keeps the graph route
+                if (ie == hipSuccess && e->aql_on && e->step_written_once && f.stop)
+                    e->aql_why = "a slot is armed with stop conditions (the stop launch reads the token the step end stored and writes the live word)";
+                if (ie == hipSuccess && e->aql_on && e->step_written_once && !f.mirostat && !f.stop) {  // the same nodes as packet templates (aql.h); a plan that cannot be built keeps the graph route
                     auto prog = std::make_unique<AqlProgram>();
                     if (aql_program_from_graph(*e->aql_rt, graph, e->stream, *prog, e->aql_why) == 0) e->aql_programs[key] = std::move(prog);
                 }
@@ -3440,7 +3673,8 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
     }
     // the queue is not the stream: what follows this call (reads, prefills, the next call's embedding gather) is stream-ordered
     if (on_queue) TL_TRY(aql_drain(e));
-    return TL_OK;
+    // a plan with an armed slot: the host mirrors follow the device before the call returns (synchronises, on every route)
+    return stop_reconcile(e);
 }
 
 extern "C" int tl_engine_read_tokens(tl_engine *e, int slot, int count, int32_t *out) {
@@ -3516,6 +3750,7 @@ extern "C" int tl_engine_profile_step(tl_engine *e, int batch, tl_step_profile *
     }
     e->warmed = true;
     step_done(e, batch);
+    TL_TRY(stop_reconcile(e));
     std::vector<prof_t> pairs(pc.kinds.size() * 2);
     hipError_t he = hipStreamSynchronize(e->stream);
     if (he == hipSuccess) he = hipMemcpy(pairs.data(), pc.pairs, pairs.size() * sizeof(prof_t), hipMemcpyDeviceToHost);
@@ -3600,6 +3835,7 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
     }
     e->warmed = true;
     step_done(e, batch);
+    (void)stop_reconcile(e);
     unsigned long long report[8] = {0};
     hipError_t he = hipStreamSynchronize(e->stream);
     if (he == hipSuccess) he = hipMemcpy(report, ck.report, sizeof(report), hipMemcpyDeviceToHost);

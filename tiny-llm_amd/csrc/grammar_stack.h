@@ -293,6 +293,7 @@ static __global__ __launch_bounds__(LPR_THREADS) void logit_process_stack_kernel
     const int nb = min(a.bias_n[slot], LPR_MAX_BIAS);
     const GrammarDev *gp = a.grammar[slot];
     const bool on = r != 1.f || p != 0.f || f != 0.f || nb > 0 || gp != nullptr;  // uniform
+    const int32_t *tokens = (a.live && a.live[slot] == 0) ? nullptr : a.tokens;      // uniform (logit_process.h: a frozen slot)
     const bool vec = (((uintptr_t)lg | (uintptr_t)out | (uintptr_t)hist) & 15) == 0 && c + 8 <= a.vocab;
     if (!on) {
         if (vec) {
@@ -329,18 +330,18 @@ static __global__ __launch_bounds__(LPR_THREADS) void logit_process_stack_kernel
     if (gp) {  // uniform
         GrRef g = *GR_GLOBAL(GrammarDev, gp);
         if (g.kind != 0) {
-            const GrsConfig cfg = grs_row_config(g, sa.stack_state, a.tokens, a.context_lens, slot, a.vocab, blockIdx.x == 0, s_cfg);
+            const GrsConfig cfg = grs_row_config(g, sa.stack_state, tokens, a.context_lens, slot, a.vocab, blockIdx.x == 0, s_cfg);
             bool whole, pop_lds;
             grs_stage_tables(g, cfg.state, s_table, s_pop, LPR_THREADS, &whole, &pop_lds);
             allowed = grs_allowed8(g, cfg, c, a.vocab, s_table, s_pop, whole, pop_lds);
         } else {
             uint16_t *s_table16 = reinterpret_cast<uint16_t *>(s_table);
-            const int state = gr_row_state(g, a.grammar_state, a.tokens, a.context_lens, slot, a.vocab, blockIdx.x == 0, &s_state);
+            const int state = gr_row_state(g, a.grammar_state, tokens, a.context_lens, slot, a.vocab, blockIdx.x == 0, &s_state);
             const bool whole = gr_stage_table(g, state, s_table16, LPR_THREADS);
             allowed = gr_allowed8(g, state, c, a.vocab, s_table16, whole);
         }
     }
-    const int pending = a.tokens ? a.tokens[slot] : -1;
+    const int pending = tokens ? tokens[slot] : -1;
     uint32_t o[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int e = 0; e < 8; ++e) {

@@ -46,6 +46,9 @@ struct LogitProcessArgs {
     const GrammarDev *const *grammar;  // [slots] the slot's automaton; nullptr: none
     GrammarRecord *grammar_state;      // [slots]
     const int32_t *context_lens;       // [slots] the tag of a record is compared with
+    // [slots] the slots' live words; nullptr: not looked at.  A slot whose word is 0 counts nothing and advances no grammar record: a slot
+    // frozen by a stop (stop.h) keeps its pending token uncounted until it is resumed.  Every slot that processes otherwise is live.
+    const int32_t *live;
 };
 
 __device__ __forceinline__ uint32_t lpr_count_up(uint32_t h) { return (h & LPR_COUNT) < LPR_COUNT ? h + 1u : h; }
@@ -84,6 +87,7 @@ static __global__ __launch_bounds__(LPR_THREADS) void logit_process_kernel(const
     const GrammarDev *gp = nullptr;
     if constexpr (GRAMMAR) gp = a.grammar[slot];
     const bool on = r != 1.f || p != 0.f || f != 0.f || nb > 0 || gp != nullptr;  // uniform
+    const int32_t *tokens = (a.live && a.live[slot] == 0) ? nullptr : a.tokens;      // uniform
     const bool vec = (((uintptr_t)lg | (uintptr_t)out | (uintptr_t)hist) & 15) == 0 && c + 8 <= a.vocab;
     if (!on) {  // the row of a slot that does not process: copied, so that the step end reads one buffer
         if (vec) {
@@ -121,13 +125,13 @@ static __global__ __launch_bounds__(LPR_THREADS) void logit_process_kernel(const
     if constexpr (GRAMMAR) {
         if (gp) {  // uniform
             GrRef g = *GR_GLOBAL(GrammarDev, gp);
-            const int state = gr_row_state(g, a.grammar_state, a.tokens, a.context_lens, slot, a.vocab, blockIdx.x == 0, &s_state);
+            const int state = gr_row_state(g, a.grammar_state, tokens, a.context_lens, slot, a.vocab, blockIdx.x == 0, &s_state);
             const bool whole = gr_stage_table(g, state, s_table, LPR_THREADS);
             allowed = gr_allowed8(g, state, c, a.vocab, s_table, whole);
         }
     }
     // the pending token (what the previous step produced and this step consumed) is counted before the row is processed
-    const int pending = a.tokens ? a.tokens[slot] : -1;
+    const int pending = tokens ? tokens[slot] : -1;
     uint32_t o[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int e = 0; e < 8; ++e) {

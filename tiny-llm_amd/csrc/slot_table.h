@@ -4,7 +4,8 @@
 //
 //   state     the page pool (prefix_cache.h: free list, reference counts, the prefix index), the host arena's records
 //             (kv_swap_model.h) and one Slot per batch slot.  A slot is free | live | live and parked (its KV lies in host records,
-//             it holds no page).  A live unparked slot holds at least ceil(ctx / page_size) pages.
+//             it holds no page).  A live unparked slot holds at least ceil(ctx / page_size) pages.  A live slot may also be STOPPED
+//             (parked or not): it keeps its pages or records and every call works on it, but no decode step takes it.
 //   calls     every operation is all-or-nothing.  It returns nullptr, or the refusal's message with nothing changed.
 //   edits     a call that succeeds APPENDS to the caller's SlotEdits what the device must learn: block-table writes, page copies and
 //             the ids of the pages it took, each in the order it made them.  The caller applies the copies before the writes (a
@@ -20,6 +21,7 @@ namespace tl {
 
 struct Slot {
     bool live = false, parked = false;
+    bool stopped = false;             // a stop condition froze the sequence on the device (stop.h): no decode step takes it
     int ctx = 0, produced = 0;        // tokens whose K/V the slot holds; ids produced since begin / fork / move
     std::vector<int> pages, records;  // pages in block-table order; a parked slot's host records, one per page
     SlotRecord rec;                   // what the prefix index knows of the slot (empty while the cache is off)
@@ -63,7 +65,16 @@ public:
         was_used.assign(pages, 0);
         page_size = page_tokens, max_pages = pages_per_seq;
     }
-    bool runs(int slot) const { return slots[slot].live && !slots[slot].parked; }  // what a decode step asks
+    bool runs(int slot) const { return slots[slot].live && !slots[slot].parked && !slots[slot].stopped; }  // what a decode step asks
+
+    // A stop condition froze the slot on the device after the steps up to context `ctx` and `produced` ids: the mirrors, which went on
+    // with every step of the call, take the device's values.  The slot keeps every page it holds -- those reserved for the steps it
+    // did not take too, as after reserve(); release() or a rewind() returns them.  resume(): a decode step takes the slot again.
+    void stop(int slot, int ctx, int produced) {
+        Slot &s = slots[slot];
+        s.ctx = ctx, s.produced = produced, s.stopped = true;
+    }
+    void resume(int slot) { slots[slot].stopped = false; }
     int pages_in_use() const { return pool.in_use(); }
     int pages_free() const { return (int)pool.free_pages.size(); }
 
@@ -95,6 +106,7 @@ public:
         Slot &s = slots[slot];
         if (s.live) return "engine_begin: slot already holds a sequence (release it first)";
         s.live = true;
+        s.stopped = false;
         s.ctx = s.produced = 0;
         s.rec.clear();
         return nullptr;
@@ -222,6 +234,7 @@ public:
             ed.rows.push_back({dst, full, d.pages.back()});
         }
         d.live = true;
+        d.stopped = s.stopped;
         d.ctx = s.ctx;
         d.rec = s.rec;
         return nullptr;

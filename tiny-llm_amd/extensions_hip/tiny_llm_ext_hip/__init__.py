@@ -181,6 +181,19 @@ class TlLoraMatrices(ctypes.Structure):
     _fields_ = [("a_dev", _c_void_p), ("b_dev", _c_void_p), ("rank", _c_int), ("seg_mask", _c_int), ("scale", _c_float)]
 
 
+TL_MAX_STOP_IDS = 16
+TL_MAX_STOP_STRINGS = 16
+TL_MAX_STOP_BYTES = 1024
+STOP_REASONS = ("none", "id", "string", "length")  # TL_STOP_NONE .. TL_STOP_LENGTH
+
+
+class TlStopState(ctypes.Structure):
+    """tl_stop_state (include/tinyllm_engine.h): a slot's stop record -- reason (STOP_REASONS), index into the set's ids / strings,
+    tokens examined since arming, context length, text bytes since arming and the bytes ahead of the matched string."""
+    _fields_ = [("reason", ctypes.c_int32), ("index", ctypes.c_int32), ("generated", ctypes.c_int32), ("context", ctypes.c_int32),
+                ("text_bytes", ctypes.c_uint32), ("cut_bytes", ctypes.c_uint32)]
+
+
 class TlAttentionInfo(ctypes.Structure):
     _fields_ = [("n_splits", _c_int), ("tokens_per_split", _c_int), ("heads_per_workgroup", _c_int),
                 ("launches", _c_int)]
@@ -286,6 +299,11 @@ _SIGNATURES.update({
     "tl_engine_lora_stats": (_c_int, [_c_void_p, _P(TlLoraStats)]),
     "tl_lora_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _P(TlLoraMatrices), _c_int, _c_int, _c_int, _c_int, _P(ctypes.c_int),
                               _P(ctypes.c_int), _P(ctypes.c_int), _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_float, _c_void_p]),
+    "tl_stop_create": (_c_int, [_c_void_p, _P(ctypes.c_int32), _c_int, _c_void_p, _P(ctypes.c_int32), _c_int, _c_void_p, _P(_c_void_p)]),
+    "tl_stop_destroy": (None, [_c_void_p]),
+    "tl_engine_set_stop": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int]),
+    "tl_engine_stop_state": (_c_int, [_c_void_p, _c_int, _P(TlStopState)]),
+    "tl_stop_rows": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "tl_engine_decode": (_c_int, [_c_void_p, _c_int, _c_int, _c_int]),
     "tl_engine_read_tokens": (_c_int, [_c_void_p, _c_int, _c_int, _P(ctypes.c_int32)]),
     "tl_engine_logits_dev": (_c_void_p, [_c_void_p]),
@@ -1241,6 +1259,19 @@ def mirostat_update_rows(filtered: torch.Tensor, ids, temperature, kept_logsum: 
     check(_lib.tl_mirostat_update_rows(filtered.data_ptr(), rows, filtered.shape[1], ids_t.data_ptr(), t_t.data_ptr(), kept_logsum.contiguous().data_ptr(),
                                        tau_t.data_ptr(), eta_t.data_ptr(), mu_t.data_ptr(), _stream()))
     return mu_t
+
+
+def stop_rows(stop, tokens: torch.Tensor, states: torch.Tensor, automaton: torch.Tensor, max_new: torch.Tensor, armed: torch.Tensor | None = None) -> None:
+    """The stop check (tl_stop_rows) over caller rows, in place: ``stop`` a tl_stop handle (a tiny_llm_hip.stop.StopSet's ``_h``) or
+    None (budgets alone); ``tokens`` int32 [rows]; ``states`` int32 [rows, 6], the rows' tl_stop_state records (reason, index,
+    generated, context, text_bytes, cut_bytes); ``automaton`` int32 [rows]; ``max_new`` int32 [rows]; ``armed`` int32 [rows] or None
+    (every row).  All on the GPU and contiguous."""
+    rows = tokens.numel()
+    for t, shape in ((tokens, (rows,)), (states, (rows, 6)), (automaton, (rows,)), (max_new, (rows,))) + (((armed, (rows,)),) if armed is not None else ()):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("stop_rows takes contiguous int32 tensors on the GPU: tokens / automaton / max_new / armed [rows], states [rows, 6]")
+    check(_lib.tl_stop_rows(stop, tokens.data_ptr(), rows, armed.data_ptr() if armed is not None else None, max_new.data_ptr(), automaton.data_ptr(),
+                            states.data_ptr(), _stream()))
 
 
 def logit_bias_arg(bias, vocab: int) -> tuple[list[int], list[float]]:

@@ -186,24 +186,36 @@ class DecodeEngine:
             pass
 
     # -- slots -------------------------------------------------------------------------------------
+    def _held_stops(self) -> dict:
+        """slot -> the StopSet it is armed with (set_stop): the engine borrows the set, this keeps it alive."""
+        return self.__dict__.setdefault("_stop_sets", {})
+
     def begin(self, slot: int = 0) -> None:
         _ext.check(_lib.tl_engine_begin(self._h, slot))
+        self._held_stops().pop(slot, None)
 
     def reserve(self, slot: int, total_tokens: int) -> None:
         _ext.check(_lib.tl_engine_reserve(self._h, slot, total_tokens))
 
     def release(self, slot: int = 0) -> None:
         _ext.check(_lib.tl_engine_release(self._h, slot))
+        self._held_stops().pop(slot, None)
 
     def rewind(self, slot: int, n: int) -> None:
         _ext.check(_lib.tl_engine_rewind(self._h, slot, n))
 
     def move(self, src: int, dst: int) -> None:
         _ext.check(_lib.tl_engine_move(self._h, src, dst))
+        held = self._held_stops()
+        if src in held:
+            held[dst] = held.pop(src)
 
     def fork(self, src: int, dst: int) -> None:
         """Make free slot ``dst`` a copy-on-write twin of ``src`` (shared prefix pages, own tail page)."""
         _ext.check(_lib.tl_engine_fork(self._h, src, dst))
+        held = self._held_stops()
+        if src in held:
+            held[dst] = held[src]
 
     # -- prefix cache (tl_engine_prefix_*; include/tinyllm_engine.h "Prefix cache") --------------------------
     def prefix_attach(self, slot: int, tokens: Sequence[int]) -> int:
@@ -414,6 +426,35 @@ class DecodeEngine:
         _ext.check(_lib.tl_engine_grammar_config(self._h, slot, ctypes.byref(state), ctypes.byref(depth), ctypes.byref(stack), ctypes.byref(acc)))
         return state.value, depth.value, stack.value, bool(acc.value)
 
+    def make_stop_set(self, ids=(), strings=(), vocab: "Vocab | None" = None) -> "StopSet":
+        """A stop set (tl_stop_create; tiny_llm_hip.stop.StopSet): token ``ids`` and byte ``strings`` (bytes, or str -> UTF-8) that end
+        a sequence.  Strings are matched in the text the tokens spell, across token boundaries, so they need a vocabulary: ``vocab``,
+        or the one of the last make_vocab.  A set of ids works without one; the record's text_bytes / cut_bytes then stay 0 (text is
+        counted in the set's vocabulary).  Upload it once; it may arm any number of slots."""
+        from .stop import StopSet
+        if vocab is None:
+            vocab = getattr(self, "_vocab", None)
+        return StopSet(ids, strings, vocab, vocab_size=self.vocab_size)
+
+    def set_stop(self, slot: int, stop: "StopSet | None" = None, max_new_tokens: int = 0) -> None:
+        """Arm the live slot (tl_engine_set_stop): from now on every token it commits is checked on the device against the set's ids,
+        its strings and the budget (0 = none), and the slot freezes at the token that stops it.  ``None`` with budget 0 disarms.  The
+        call always restarts the slot's record and resumes a stopped slot.  begin / release disarm, move carries, fork copies."""
+        from .stop import StopSet
+        if stop is not None and not isinstance(stop, StopSet):
+            raise ValueError("set_stop takes a StopSet (DecodeEngine.make_stop_set) or None")
+        if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 0:
+            raise ValueError("set_stop: max_new_tokens is a nonnegative int (0 = no budget)")
+        _ext.check(_lib.tl_engine_set_stop(self._h, slot, stop._h if stop is not None else None, max_new_tokens))
+        self._held_stops()[slot] = stop  # (the slot borrows the set: it stays alive while the slot is armed with it)
+
+    def stop_state(self, slot: int) -> "StopState":
+        """The slot's stop record (tl_engine_stop_state; tiny_llm_hip.stop.StopState); synchronises."""
+        from .stop import REASONS, StopState
+        st = _ext.TlStopState()
+        _ext.check(_lib.tl_engine_stop_state(self._h, slot, ctypes.byref(st)))
+        return StopState(REASONS[st.reason], st.index, st.generated, st.context, st.text_bytes, st.cut_bytes)
+
     def read_logprobs(self, slot: int, count: int) -> list["TokenLogprob"]:
         """Records of the slot's last ``count`` produced tokens (like read_tokens); synchronises."""
         out = (_ext.TlTokenLogprob * max(count, 1))()
@@ -617,7 +658,8 @@ class DecodeEngine:
                  temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None, seed: int = 0,
                  logprobs: int | None = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                  frequency_penalty: float = 0.0, logit_bias=None, grammar: "Grammar | None" = None, min_p: float = 0.0,
-                 typical_p: float = 1.0, mirostat_tau: float = 0.0, mirostat_eta: float = 0.1, lora: int | None = None):
+                 typical_p: float = 1.0, mirostat_tau: float = 0.0, mirostat_eta: float = 0.1, lora: int | None = None,
+                 stop: "StopSet | None" = None, decode_block: int = 32):
         """One request: prefill, then ``max_new_tokens - 1`` decode steps in one call; greedy unless ``temperature`` > 0 (the
         device sampler, set_sampling).  With ``logprobs`` an int (0 .. 20 alternatives, set_logprobs): returns (ids, records).
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` (set_penalties, set_logit_bias) are set
@@ -626,7 +668,13 @@ class DecodeEngine:
         ``mirostat_eta`` (set_mirostat) filter the rows a sampling request draws from; Mirostat excludes top_k, top_p, min_p and
         typical_p (ValueError).  ``lora``: the id of a resident adapter (load_lora) the request runs under; such a request bypasses the
         prefix cache.  On an engine with the prefix cache on, the slot first attaches the cached
-        prefix of the prompt (prefix_attach) and prefills the rest, and declares the answer before its release (prefix_extend)."""
+        prefix of the prompt (prefix_attach) and prefills the rest, and declares the answer before its release (prefix_extend).
+        ``stop``: a StopSet (make_stop_set).  The slot is armed with it and the budget ``max_new_tokens`` before the prefill, decodes in
+        blocks of ``decode_block`` steps and leaves after the block in which it stopped; the result is the ids up to and including the
+        stopping token -- exactly ``stop_state().generated`` of them -- and likewise the records; ``last_stop_state`` keeps the slot's
+        final StopState.  Without ``stop`` the call is unchanged."""
+        if stop is not None and (isinstance(decode_block, bool) or not isinstance(decode_block, int) or decode_block < 1):
+            raise ValueError("generate: decode_block is a positive int")
         args = sampling_args(temperature, top_k, top_p, seed)
         trn = truncation_args(min_p, typical_p, mirostat_tau, mirostat_eta, top_k=args[1], top_p=args[2])
         top_n = logprobs_arg(logprobs)
@@ -647,9 +695,24 @@ class DecodeEngine:
             apply_truncation(self, slot, trn)
             if top_n >= 0:
                 self.set_logprobs(slot, top_n)
+            if stop is not None:
+                self.set_stop(slot, stop, max_new_tokens)
             prompt = [int(t) for t in prompt]
             matched = self.prefix_attach(slot, prompt) if self.prefix_cache_enabled and prompt else 0
             self.prefill(slot, prompt[matched:], chunk=chunk)
+            if stop is not None:
+                left = max_new_tokens - 1
+                state = self.stop_state(slot)
+                while not state.stopped and left > 0:
+                    steps = min(decode_block, left)
+                    self.decode(steps, batch=slot + 1)
+                    left -= steps
+                    state = self.stop_state(slot)
+                ids = self.read_tokens(slot, state.generated)
+                self.last_stop_state = state  # (why and where the request ended: the slot is released below)
+                if self.prefix_cache_enabled:  # only fed tokens are declared: the stopping token never was
+                    self.prefix_extend(slot, ids[:-1])
+                return (ids, self.read_logprobs(slot, state.generated)) if top_n >= 0 else ids
             if max_new_tokens > 1:
                 self.decode(max_new_tokens - 1, batch=slot + 1)
             ids = self.read_tokens(slot, max_new_tokens)
@@ -897,7 +960,8 @@ _DECODE_ROW_BUCKETS = (1, 2, 3, 4, 8, 16, 32, 48, 64, 96, 128, 192, 256)
 
 def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], max_new_tokens: int | Sequence[int],
                        batch_size: int, prefill_step: int = 128, eos_token_id: int | None = None,
-                       on_step=None, sampling=None, base_seed: int = 0, logprobs: int | None = None) -> list[tuple]:
+                       on_step=None, sampling=None, base_seed: int = 0, logprobs: int | None = None, stop=None,
+                       decode_block: int = 1) -> list[tuple]:
     """Continuous batching over engine slots with the reference scheduler's shape (batch_generate,
     src/tiny_llm_ref/batch.py:136-285; benches/bench.py:run_batch_requests_serving 351-572): every loop turn
     (a) admits one pending request and prefills ONE chunk of at most ``prefill_step`` tokens in the staging slot,
@@ -922,8 +986,23 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     (tiny_llm_hip.preempt): before a decode step the staging request is released and re-queued, or the running request admitted last
     is parked; parked requests resume oldest first, and nothing new is admitted while one is parked.  A request's ids do not depend on
     being preempted beyond the usual row-bucket band (a step's arithmetic follows its row count) -- except that a Mirostat request
-    which is recomputed instead of unparked (the staging request that gives way) restarts its mu at 2 tau."""
+    which is recomputed instead of unparked (the staging request that gives way) restarts its mu at 2 tau.
+    ``stop``: one StopSet (DecodeEngine.make_stop_set) for every request, or a sequence with one (or None) per request.  Each request
+    is then armed on the device with its set and its ``max_new_tokens`` budget when it enters the staging slot (set_stop), and retires
+    on its stop state (stop_state) instead of the host's comparison: its ids end with the stopping token.  ``eos_token_id`` is not
+    combined with it (put the id into the set), and a grammar's EOS ids end such a request only where the set holds them.
+    ``decode_block`` > 1 (with ``stop``): while the queue is empty, nothing is staged and the engine has no swap space, a turn runs
+    that many decode steps in one call -- a slot that stops inside the block freezes at its stopping token -- and reads each slot's
+    ids of the block from the ring by its ``generated`` count.  Calls that pass neither argument behave exactly as before."""
     from .preempt import Preemption
+    from .stop import request_stops
+    per_request_stop = request_stops(stop, len(prompts))
+    if isinstance(decode_block, bool) or not isinstance(decode_block, int) or decode_block < 1:
+        raise ValueError("decode_block is a positive int")
+    if per_request_stop is None and decode_block != 1:
+        raise ValueError("decode_block > 1 needs stop conditions on the device (stop=)")
+    if per_request_stop is not None and eos_token_id is not None:
+        raise ValueError("stop= and eos_token_id= are not combined: put the id into the stop set")
     if batch_size <= 0 or prefill_step <= 0:
         raise ValueError("batch_size and prefill_step must be positive")
     if engine.max_batch < batch_size + 1:
@@ -977,6 +1056,8 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                     engine.set_grammar(staging, grammar)
                 if top_n >= 0:
                     engine.set_logprobs(staging, top_n)
+                if per_request_stop is not None:
+                    engine.set_stop(staging, per_request_stop[idx], limits[idx])
                 pending = {"eos": grammar.eos_ids if grammar is not None else None, "idx": idx, "tokens": [int(t) for t in prompts[idx]], "offset": 0, "out": [], "limit": limits[idx], "lp": []}
                 if cached and pending["tokens"]:  # after the settings, before the first chunk: the prompt starts behind the cached prefix
                     pending["offset"] = engine.prefix_attach(staging, pending["tokens"])
@@ -992,7 +1073,10 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                         if top_n >= 0:
                             pending["lp"].append(engine.read_logprobs(staging, 1)[0])
                 if pending["offset"] >= total:
-                    done = len(pending["out"]) >= pending["limit"] or ends(pending, pending["out"][-1])
+                    if per_request_stop is not None:
+                        done = engine.stop_state(staging).stopped
+                    else:
+                        done = len(pending["out"]) >= pending["limit"] or ends(pending, pending["out"][-1])
                     if done:
                         retire(staging, pending)
                         live_slots.discard(staging)
@@ -1043,6 +1127,28 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
                         live_slots.add(lo)
                     top = count
                 rows = bucket(top)
+                if per_request_stop is not None:
+                    # the device decides: decode_block steps in one call while nothing waits to be admitted, staged or resumed (a slot
+                    # that stops inside the block freezes there), then each slot's new ids from its ring, as many as its record counted
+                    steps = decode_block if not queue and pending is None and not pre.active else 1
+                    engine.decode(steps, batch=rows)
+                    if on_step is not None:
+                        for _ in range(steps):
+                            on_step(sum(s is not None and not pre.parked(s) for s in slots))
+                    for i, req in enumerate(slots):
+                        if req is None or pre.parked(req):
+                            continue
+                        state = engine.stop_state(i)
+                        new = state.generated - len(req["out"])
+                        req["out"].extend(engine.read_tokens(i, new))
+                        if top_n >= 0:
+                            req["lp"].extend(engine.read_logprobs(i, new))
+                        if state.stopped:
+                            retire(i, req)
+                            live_slots.discard(i)
+                            finished.append((req["idx"], req["out"]) + ((req["lp"],) if top_n >= 0 else ()))
+                            slots[i] = None
+                    continue
                 engine.decode(1, batch=rows)
                 tokens = engine.read_pending(rows)
                 records = engine.read_pending_logprobs(rows) if top_n >= 0 else None
