@@ -317,6 +317,19 @@ int tl_kv_scatter_pages(const tl_kv_pool_desc *pools_dev, const size_t *record_o
  * rewinds the rejected suffix with tl_engine_rewind and sets the next input with tl_engine_set_token.  Synchronises. */
 int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, int n, int32_t *out_ids);
 
+/* Speculative sampling: verification for a slot that samples (csrc/spec_sample.h; Leviathan et al. 2023, Chen et
+ * al. 2023).  Appends the n (1..8) tokens exactly like tl_engine_verify, then runs tl_spec_sample_rows once on the engine stream over the n
+ * rows of logits: the slot's own (temperature, top_k, top_p, seed) for the target; proposals tokens[1..n-1] and -1 (a bonus row) for the
+ * last row; draft_logits_dev [n-1, V] bf16 on the device, row i the row the draft drew tokens[i+1] from under (draft_temperature,
+ * draft_top_k, draft_top_p) (may be NULL when n == 1); position of row i = context length before the call + i + 1, the sampler's own
+ * position rule.  With a = the first rejected row (n-1 when none is): out_ids[0..a) = tokens[1..a+1), out_ids[a] = that row's alt,
+ * *out_count = a + 1 -- tokens distributed exactly as if the slot had sampled them alone, whatever the draft.  Nothing is recorded as
+ * generated; the caller rewinds n - 1 - a tokens and sets the next input, as after tl_engine_verify.  Refuses what tl_engine_verify
+ * refuses except sampling, and a slot that truncates (min-p / typical-p) or runs Mirostat (their kept sets are not this routine's); a
+ * greedy slot is verified greedily.  The 8-row scratch is allocated by the first call.  Synchronises. */
+int tl_engine_verify_sampled(tl_engine *e, int slot, const int32_t *tokens, int n, const void *draft_logits_dev, float draft_temperature,
+                             int draft_top_k, float draft_top_p, int32_t *out_ids, int *out_count);
+
 /* Set the pending input token of a slot explicitly (e.g. sampled on the host). */
 int tl_engine_set_token(tl_engine *e, int slot, int32_t token);
 
@@ -336,7 +349,8 @@ int tl_engine_set_token(tl_engine *e, int slot, int32_t token);
  * top_k 0 or >= V: no top-k; top_p outside (0, 1): no top-p.  Sampling needs V <= 524,288.  The parameters live in a host mirror
  * and a per-slot device array written on the engine stream between steps.  tl_engine_begin / tl_engine_release reset the slot to
  * greedy, tl_engine_move moves the parameters with the sequence, tl_engine_fork copies them (seed included: give the child its own
- * seed, or both draw the same tokens).  tl_engine_verify refuses a sampling slot (verification is greedy). */
+ * seed, or both draw the same tokens).  tl_engine_verify refuses a sampling slot (verification is greedy; tl_engine_verify_sampled
+ * verifies one). */
 int tl_engine_set_sampling(tl_engine *e, int slot, float temperature, int top_k, float top_p, uint64_t seed);
 
 /* Per-token log-probabilities (csrc/logprob.h).  For a bf16 logits row l of V entries, m its maximum over non-NaN
@@ -952,6 +966,24 @@ int tl_decode_attention_fused_fp8(const void *qkv_dev, const void *q_norm_dev, c
  * 1,024-thread workgroup per row, the engine's routine and semantics.  Stream ordered. */
 int tl_sample_logits(const void *logits_dev, int rows, int vocab, const float *temperature_dev, const int32_t *top_k_dev,
                      const float *top_p_dev, const uint64_t *seed_dev, const int32_t *position_dev, int32_t *ids_dev, void *stream);
+
+/* Speculative sampling over caller rows (csrc/spec_sample.h): row i holds a target logits row and the draft logits row its proposal was
+ * drawn from, each [vocab] bf16 (vocab <= 524,288), and per-row device arrays: proposal (int32), the target's temperature / top_k / top_p
+ * and the draft's, seed (uint64) and position (int32).  Kept set and weights are tl_engine_set_sampling's, applied to each row with its
+ * own parameters: wp, Wp = sum wp (fp32) for the target, wq, Wq for the draft; a row with temperature 0, without a finite maximum or
+ * holding +inf is one-hot (w = W = 1) at the id tl_sample_logits gives it.  Uniforms as the sampler's with the third counter word
+ * 0x53504143 (u_acc) and 0x53505253 (u_res).
+ *   proposal < 0   a bonus row: accept 0, alt = exactly what tl_sample_logits returns for the target row;
+ *   proposal >= V  rejected without a read at it;
+ *   accept         iff u_acc wq_x Wp < wp_x Wq in fp32, no division; alt = -1;
+ *   reject         r_j = max(wp_j Wq - wq_j Wp, 0), R = sum r: alt = the first id in ascending order whose inclusive cumulative r exceeds
+ *                  u_res R (rounding leaving none: the last id with r > 0; R == 0: the inverse-CDF draw from wp with u_res).
+ * -> accept_dev, alt_dev [rows] int32.  Rows are independent; the caller picks the first rejection.  One 1,024-thread workgroup per row.
+ * Stream ordered. */
+int tl_spec_sample_rows(const void *target_logits_dev, const void *draft_logits_dev, int rows, int vocab, const int32_t *proposal_dev,
+                        const float *temperature_dev, const int32_t *top_k_dev, const float *top_p_dev, const float *draft_temperature_dev,
+                        const int32_t *draft_top_k_dev, const float *draft_top_p_dev, const uint64_t *seed_dev, const int32_t *position_dev,
+                        int32_t *accept_dev, int32_t *alt_dev, void *stream);
 
 /* The log-probability routine of tl_engine_set_logprobs over caller rows: logits [rows, vocab] bf16 (vocab <= 524,288); ids_dev [rows]
  * int32 (may be NULL: each row's greedy id, the first maximum; an id < 0 gives NaN) -> logprob_dev [rows] float; top_n 0 .. 20 ->

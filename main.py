@@ -4,7 +4,8 @@ feature exists here).
 
   python main.py --model <checkpoint dir or cached repo> --prompt "..." [--solution engine|ops] [--draft-model <dir>]
 
---solution engine  fused decode engine (tl_engine_*): greedy, or speculative with --draft-model
+--solution engine  fused decode engine (tl_engine_*): greedy, or speculative with --draft-model (speculative sampling with a nonzero
+                   --sampler-temp: the answer is distributed as the model's own samples)
 --solution ops     the op-by-op Week-3 model on the HIP operators (reference call structure); supports the sampler flags
 Checkpoints are MLX-format 4-bit directories (tiny_llm_hip.load); there is no network, so --model must exist locally.
 """
@@ -143,10 +144,18 @@ def main(argv=None) -> str:
             if penalties != (1.0, 0.0, 0.0) or args.regex or args.json or args.json_schema:
                 print("note: speculative decoding verifies the raw logits; the penalty flags, --regex, --json and --json-schema do not "
                       "apply with a draft model")
+            if truncates:
+                print("note: speculative sampling verifies under temperature, top-k and top-p; --sampler-min-p, --sampler-typical-p and "
+                      "--mirostat-tau do not apply with a draft model")
+            if args.sampler_temp and args.sampler_seed is None:
+                print("note: a draft model with a nonzero --sampler-temp selects the device sampler; no --sampler-seed given: seed 0")
             draft = DecodeEngine(draft_model, page_size=128, num_pages=pages, max_batch=1, max_prefill_rows=4096)
             try:
+                # --sampler-temp 0: greedy speculative decoding; > 0: speculative sampling, both engines drawing on the device
                 out = speculative_generate_ids(engine, draft, ids, args.max_new_tokens,
-                                               proposal_length=min(args.proposal_length, 7), eos_token_id=eos)
+                                               proposal_length=min(args.proposal_length, 7), eos_token_id=eos,
+                                               temperature=args.sampler_temp, top_k=args.sampler_top_k, top_p=args.sampler_top_p,
+                                               seed=args.sampler_seed or 0)
             finally:
                 draft.close()
         elif args.sampler_temp and (args.sampler_seed is not None or lora is not None or penalties != (1.0, 0.0, 0.0) or grammar is not None or truncates

@@ -6,6 +6,7 @@
 //   * multi-token prefill on the MFMA W4 GEMM + paged FlashAttention operators of tinyllm_hip.h
 #include <dlfcn.h>
 
+#include <cstddef>
 #include <cstring>
 #include <memory>
 
@@ -161,6 +162,19 @@ struct tl_engine {
     // (128-token windows: 1.022).  Other split counts, more sequences or another head size keep the merge launch (wo_merge_applicable).
     bool wo_merges_attn = true;
     int32_t *verify_ids = nullptr;  // greedy ids of the rows of the last tl_engine_verify
+    // tl_engine_verify_sampled: the per-row arrays of its one tl_spec_sample_rows launch (8 rows), allocated by the first call
+    struct SpecRecord {
+        int32_t proposal[8];
+        float t_temperature[8];
+        int32_t t_top_k[8];
+        float t_top_p[8], d_temperature[8];
+        int32_t d_top_k[8];
+        float d_top_p[8];
+        int32_t position[8];
+        uint64_t seed[8];
+        int32_t accept[8], alt[8];  // (results: behind everything the host writes)
+    };
+    SpecRecord *spec_rec = nullptr;
     int attn_rq = 0;             // query heads per decode-attention workgroup; 0 = by context (TL_ATTN_RQ at create: 1 or 4)
     int attn_rq1_ctx = 4096;     // contexts up to this many tokens use one query head per workgroup
     int attn_rq1_batch = 2;      // ... and up to this many sequences; at 4 the re-read windows cost 261 vs 180 us
@@ -1965,6 +1979,7 @@ extern "C" void tl_engine_destroy(tl_engine *e) {
     if (e->swap_staging) (void)hipFree(e->swap_staging);
     if (e->swap_offsets_dev) (void)hipFree(e->swap_offsets_dev);
     if (e->score_logits) (void)hipFree(e->score_logits);
+    if (e->spec_rec) (void)hipFree(e->spec_rec);
     if (e->emb_out) (void)hipFree(e->emb_out);
     if (e->emb_sums) (void)hipFree(e->emb_sums);
     for (auto &r : e->lora_ad)
@@ -3511,6 +3526,45 @@ extern "C" int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, i
     TL_TRY(prefill_impl(e, slot, tokens, n, 2));
     TL_HIP(hipMemcpyAsync(out_ids, e->verify_ids, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
     TL_HIP(hipStreamSynchronize(e->stream));
+    return TL_OK;
+}
+
+extern "C" int tl_engine_verify_sampled(tl_engine *e, int slot, const int32_t *tokens, int n, const void *draft_logits_dev, float draft_temperature,
+                                        int draft_top_k, float draft_top_p, int32_t *out_ids, int *out_count) {
+    TL_REQUIRE(e && tokens && out_ids && out_count, "engine_verify_sampled: null argument");
+    TL_REQUIRE(n >= 1 && n <= 8, "engine_verify_sampled: between 1 and 8 tokens per call (the paged decode kernel's query rows)");
+    TL_REQUIRE(n == 1 || draft_logits_dev, "engine_verify_sampled: the rows the proposals were drawn from are missing");
+    TL_REQUIRE(std::isfinite(draft_temperature) && draft_temperature >= 0.f, "engine_verify_sampled: the draft's temperature must be finite and >= 0");
+    TL_TRY(slot_check_feeds(e, slot));
+    TL_REQUIRE(!e->pen[slot].processes(), "engine_verify_sampled: the slot processes its logits (verification takes the raw rows; make it neutral first)");
+    TL_REQUIRE(!e->trn[slot].truncates(), "engine_verify_sampled: the slot truncates (min-p / typical-p / Mirostat keep other sets than the verification's; switch them off first)");
+    TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_verify_sampled: vocabulary larger than the sampler's 524,288 tokens");
+    using Rec = tl_engine::SpecRecord;
+    if (!e->spec_rec) {
+        if (hipMalloc((void **)&e->spec_rec, sizeof(Rec)) != hipSuccess) return fail(TL_ERR_HIP, "engine_verify_sampled: hipMalloc failed");
+        e->stats.workspace_bytes += sizeof(Rec);
+    }
+    const int ctx = e->table.slots[slot].ctx;
+    const tl_engine::SampleParams &sp = e->smp[slot];
+    TL_TRY(prefill_impl(e, slot, tokens, n, 2));
+    Rec r{};
+    for (int i = 0; i < n; ++i) {
+        r.proposal[i] = i + 1 < n ? tokens[i + 1] : -1;  // the last row is the bonus row
+        r.t_temperature[i] = sp.temperature, r.t_top_k[i] = sp.top_k, r.t_top_p[i] = sp.top_p, r.seed[i] = sp.seed;
+        r.d_temperature[i] = draft_temperature, r.d_top_k[i] = draft_top_k, r.d_top_p[i] = draft_top_p;
+        r.position[i] = ctx + i + 1;
+    }
+    Rec *d = e->spec_rec;
+    TL_HIP(hipMemcpyAsync(d, &r, offsetof(Rec, accept), hipMemcpyHostToDevice, e->stream));
+    // (a bonus row's draft row is never read: with n == 1 the target's rows stand in for the missing pointer)
+    TL_TRY(tl_spec_sample_rows(e->logits, draft_logits_dev ? draft_logits_dev : e->logits, n, e->cfg.vocab_size, d->proposal, d->t_temperature, d->t_top_k,
+                               d->t_top_p, d->d_temperature, d->d_top_k, d->d_top_p, d->seed, d->position, d->accept, d->alt, e->stream));
+    TL_HIP(hipMemcpyAsync(r.accept, d->accept, sizeof(r.accept) + sizeof(r.alt), hipMemcpyDeviceToHost, e->stream));
+    TL_HIP(hipStreamSynchronize(e->stream));
+    int a = 0;
+    while (a < n - 1 && r.accept[a]) out_ids[a] = tokens[a + 1], ++a;
+    out_ids[a] = r.alt[a];
+    *out_count = a + 1;
     return TL_OK;
 }
 

@@ -259,6 +259,8 @@ _SIGNATURES.update({
     "tl_engine_prefill": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _c_int]),
     "tl_engine_prefill_packed": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int), _P(ctypes.c_int32), _P(ctypes.c_int), _P(ctypes.c_int)]),
     "tl_engine_verify": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _P(ctypes.c_int32)]),
+    "tl_engine_verify_sampled": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _c_void_p, ctypes.c_float, _c_int, ctypes.c_float,
+                                          _P(ctypes.c_int32), _P(_c_int)]),
     "tl_engine_set_token": (_c_int, [_c_void_p, _c_int, ctypes.c_int32]),
     "tl_engine_set_sampling": (_c_int, [_c_void_p, _c_int, _c_float, _c_int, _c_float, ctypes.c_uint64]),
     "tl_sample_logits": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 7),
@@ -271,6 +273,7 @@ _SIGNATURES.update({
     "tl_engine_mirostat_mu": (_c_int, [_c_void_p, _c_int, _P(_c_float)]),
     "tl_engine_copy_filtered_logits": (_c_int, [_c_void_p, _c_void_p, _c_int]),
     "tl_truncate_rows": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 7),
+    "tl_spec_sample_rows": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int] + [_c_void_p] * 12),
     "tl_mirostat_update_rows": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 7),
     "tl_vocab_create": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p, _P(_c_void_p)]),
     "tl_vocab_destroy": (None, [_c_void_p]),
@@ -1049,6 +1052,42 @@ def sample_logits(logits: torch.Tensor, temperature, top_k, top_p, seed, positio
     check(_lib.tl_sample_logits(logits.data_ptr(), rows, logits.shape[1], t_t.data_ptr(), k_t.data_ptr(), p_t.data_ptr(), seed_t.data_ptr(),
                                 pos_t.data_ptr(), ids.data_ptr(), _stream()))
     return ids
+
+
+def spec_sample_rows(target: torch.Tensor, draft: torch.Tensor, proposal, temperature, top_k, top_p, draft_temperature, draft_top_k,
+                     draft_top_p, seed, position):
+    """Speculative sampling (tl_spec_sample_rows) over rows of bf16 logits: ``target`` and ``draft`` [rows, vocab], row i of ``draft`` the
+    row proposal i was drawn from; per-row proposal (< 0: a bonus row), the target's and the draft's temperature / top_k / top_p, seed
+    (uint64) and position, each a scalar or one value per row.  Returns (accept int32 [rows], alt int32 [rows]: -1 where accepted)."""
+    for t in (target, draft):
+        if t.dtype != torch.bfloat16 or t.dim() != 2 or not t.is_cuda:
+            raise ValueError("spec_sample_rows takes [rows, vocab] bf16 tensors on the GPU")
+    if target.shape != draft.shape or target.device != draft.device:
+        raise ValueError("spec_sample_rows: target and draft rows must have one shape and one device")
+    target, draft = target.contiguous(), draft.contiguous()
+    rows, dev = target.shape[0], target.device
+
+    def per_row(v, dtype):
+        t = torch.as_tensor(v, dtype=dtype).reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(rows)
+        if t.numel() != rows:
+            raise ValueError("a speculative-sampling parameter needs one value per row")
+        return t.contiguous().to(dev)
+
+    seeds = [int(s) & 0xFFFFFFFFFFFFFFFF for s in (seed if hasattr(seed, "__len__") else [seed] * rows)]
+    if len(seeds) != rows:
+        raise ValueError("a speculative-sampling parameter needs one value per row")
+    seed_t = torch.tensor([s - (1 << 64) if s >= 1 << 63 else s for s in seeds], dtype=torch.int64).to(dev)  # uint64 bits
+    x_t, pos_t = per_row(proposal, torch.int32), per_row(position, torch.int32)
+    tt, tk, tp = per_row(temperature, torch.float32), per_row(top_k, torch.int32), per_row(top_p, torch.float32)
+    dt, dk, dp = per_row(draft_temperature, torch.float32), per_row(draft_top_k, torch.int32), per_row(draft_top_p, torch.float32)
+    accept = torch.empty(rows, dtype=torch.int32, device=dev)
+    alt = torch.empty(rows, dtype=torch.int32, device=dev)
+    check(_lib.tl_spec_sample_rows(target.data_ptr(), draft.data_ptr(), rows, target.shape[1], x_t.data_ptr(), tt.data_ptr(), tk.data_ptr(),
+                                   tp.data_ptr(), dt.data_ptr(), dk.data_ptr(), dp.data_ptr(), seed_t.data_ptr(), pos_t.data_ptr(),
+                                   accept.data_ptr(), alt.data_ptr(), _stream()))
+    return accept, alt
 
 
 def logprob_rows(logits: torch.Tensor, ids=None, top_n: int = 0):

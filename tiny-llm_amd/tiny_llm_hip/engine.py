@@ -507,6 +507,33 @@ class DecodeEngine:
         _ext.check(_lib.tl_engine_verify(self._h, slot, arr, len(tokens), out))
         return list(out)
 
+    def verify_sampled(self, slot: int, tokens: Sequence[int], draft_rows: torch.Tensor | None, draft_sampling=(0.0, None, None)) -> list[int]:
+        """Speculative sampling (tl_engine_verify_sampled): append 1..8 tokens to the slot -- its pending token and the draft's
+        proposals -- and verify the proposals under the slot's own sampling parameters (set_sampling).  ``draft_rows`` [>= n-1, vocab]
+        bf16 on the device: row i is the logits row the draft drew ``tokens[i+1]`` from under ``draft_sampling`` = (temperature, top_k,
+        top_p) (or a dict with those keys); None with a single token.  Returns the accepted proposals followed by one more token -- the
+        residual draw where a proposal was rejected, the slot's ordinary draw after the last row where none was -- distributed exactly
+        as if the slot had sampled them alone.  The caller rewinds ``len(tokens) - len(result)`` tokens and sets the next input, as
+        after ``verify``.  The rows must be complete before the call (they are read on this engine's stream).  Synchronises."""
+        tokens = [int(t) for t in tokens]
+        if not 1 <= len(tokens) <= 8:
+            raise ValueError("verify_sampled takes between 1 and 8 tokens")
+        if isinstance(draft_sampling, dict):
+            draft_sampling = (draft_sampling.get("temperature", 0.0), draft_sampling.get("top_k"), draft_sampling.get("top_p"))
+        t, k, p, _ = sampling_args(*draft_sampling)
+        n = len(tokens)
+        ptr = None
+        if n > 1:
+            if draft_rows is None or draft_rows.dtype != torch.bfloat16 or draft_rows.dim() != 2 or not draft_rows.is_cuda \
+                    or not draft_rows.is_contiguous() or draft_rows.shape[0] < n - 1 or draft_rows.shape[1] != self.vocab_size:
+                raise ValueError(f"draft_rows must be a contiguous bf16 tensor [>= {n - 1}, {self.vocab_size}] on the GPU")
+            ptr = draft_rows.data_ptr()
+        arr = (ctypes.c_int32 * n)(*tokens)
+        out = (ctypes.c_int32 * n)()
+        count = ctypes.c_int(0)
+        _ext.check(_lib.tl_engine_verify_sampled(self._h, slot, arr, n, ptr, t, k, p, out, ctypes.byref(count)))
+        return list(out[:count.value])
+
     def score(self, tokens: Sequence[int], *, slot: int = 0, chunk: int | None = None) -> list[float]:
         """Log-probabilities of ``tokens[1:]``, each given the tokens before it (tl_engine_score), on the free ``slot`` as a fresh
         sequence, in chunks of at most ``chunk`` (default: max_prefill_rows) tokens; each chunk's last row scores the next chunk's
@@ -598,6 +625,20 @@ class DecodeEngine:
         _ext.check(_lib.tl_engine_copy_logits(self._h, out.data_ptr(), rows))
         self.synchronize()
         return out
+
+    def logits_buffer(self, rows: int) -> torch.Tensor:
+        """An uninitialised [rows, vocab] bf16 tensor on the engine's device for ``copy_logits_into``, safe to write on the engine
+        stream (torch's stream, which allocated it, has finished with the memory)."""
+        out = torch.empty((rows, self.vocab_size), dtype=torch.bfloat16, device=self.device)
+        torch.cuda.current_stream().synchronize()
+        return out
+
+    def copy_logits_into(self, dst: torch.Tensor, rows: int = 1) -> None:
+        """Enqueue a copy of the most recent logits rows into ``dst`` (contiguous bf16 on the device, at least rows * vocab elements)
+        on the engine stream (tl_engine_copy_logits); does not synchronise.  ``dst`` must not be in use on another stream."""
+        if dst.dtype != torch.bfloat16 or not dst.is_cuda or not dst.is_contiguous() or dst.numel() < rows * self.vocab_size:
+            raise ValueError(f"copy_logits_into needs a contiguous bf16 tensor of at least {rows} x {self.vocab_size} elements on the GPU")
+        _ext.check(_lib.tl_engine_copy_logits(self._h, dst.data_ptr(), rows))
 
     def processed_logits(self, rows: int = 1) -> torch.Tensor:
         """A copy of the processed rows [rows, vocab] (bf16) of the last decode step in which some slot processed its logits
@@ -1176,12 +1217,25 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
 
 def speculative_generate_ids(target: DecodeEngine, draft: DecodeEngine, prompt: Sequence[int], max_new_tokens: int,
                              proposal_length: int = 4, eos_token_id: int | None = None, *, slot: int = 0,
-                             chunk: int = 2048, stats: dict | None = None) -> list[int]:
-    """Greedy speculative decoding over two engines (reference speculative_generate, src/tiny_llm_ref/generate.py:84-322;
+                             chunk: int = 2048, stats: dict | None = None, temperature: float = 0.0, top_k: int | None = None,
+                             top_p: float | None = None, seed: int = 0) -> list[int]:
+    """Speculative decoding over two engines (reference speculative_generate, src/tiny_llm_ref/generate.py:84-322;
     token ids in, token ids out).  The draft engine free-runs ``proposal_length`` fused decode steps on the device; the
     target scores the pending token plus the proposals in one ``verify`` call (at most 8 rows through the paged decode
     kernel) and both KV caches are rewound to the accepted prefix.  Returns exactly the target's greedy continuation
-    (up to ``max_new_tokens`` ids, stopping before ``eos_token_id``); ``stats`` receives call and acceptance counts."""
+    (up to ``max_new_tokens`` ids, stopping before ``eos_token_id``); ``stats`` receives call and acceptance counts.
+
+    ``temperature`` > 0: speculative sampling (Leviathan et al. 2023).  Both engines sample on the device under (temperature, top_k,
+    top_p) -- the target from ``seed``, the draft from a seed derived from it; the draft runs one step per ``decode`` call, each
+    followed by a stream-ordered copy of its logits row, and the target accepts or redraws in one ``verify_sampled`` call.  The ids
+    are distributed exactly as if the target had sampled alone, and the same arguments give the same ids.  ``stats["resampled"]``
+    counts the rounds that ended in a residual draw."""
+    sampled = sampling_args(temperature, top_k, top_p, seed)
+    sampling = sampled[0] > 0
+    if sampling and proposal_length and draft.vocab_size != target.vocab_size:
+        raise ValueError("speculative sampling needs one vocabulary: the draft's rows are compared with the target's")
+    if sampling and slot != 0:
+        raise ValueError("speculative sampling runs on slot 0 (the draft's logits row is copied from the front of its rows)")
     if not isinstance(proposal_length, int) or isinstance(proposal_length, bool) or proposal_length < 0:
         raise ValueError("proposal_length must be a non-negative integer")
     if proposal_length > 7:
@@ -1189,17 +1243,23 @@ def speculative_generate_ids(target: DecodeEngine, draft: DecodeEngine, prompt: 
     prompt = [int(t) for t in prompt]
     if not prompt:
         raise ValueError("prompt must hold at least one token")
-    counts = {"target_calls": 0, "draft_steps": 0, "proposed": 0, "accepted": 0}
+    counts = {"target_calls": 0, "draft_steps": 0, "proposed": 0, "accepted": 0, "resampled": 0}
     out: list[int] = []
     target.begin(slot)
     draft_live = False
+    draft_rows = None
     try:
+        if sampling:
+            target.set_sampling(slot, temperature, top_k, top_p, seed)
         target.prefill(slot, prompt, chunk=chunk)
         token = target.read_tokens(slot, 1)[0]
         counts["target_calls"] += 1
         if proposal_length > 0:
             draft.begin(slot)
             draft_live = True
+            if sampling:  # the draft's own stream of draws; its rows go to the target through this buffer
+                draft.set_sampling(slot, temperature, top_k, top_p, seed ^ 0x9E3779B97F4A7C15)
+                draft_rows = draft.logits_buffer(7)
             draft.prefill(slot, prompt, chunk=chunk, want_logits=False)
         while len(out) < max_new_tokens and token != eos_token_id:
             room = max_new_tokens - len(out) - 1          # proposals that could still be emitted after `token`
@@ -1207,14 +1267,42 @@ def speculative_generate_ids(target: DecodeEngine, draft: DecodeEngine, prompt: 
             proposals: list[int] = []
             if k > 0:
                 draft.set_token(slot, token)
-                draft.decode(k, batch=slot + 1)
-                proposals = draft.read_tokens(slot, k)
+                if sampling:  # one step per call: a multi-step call would overwrite the rows the proposals were drawn from
+                    for i in range(k):
+                        draft.decode(1, batch=slot + 1)
+                        draft.copy_logits_into(draft_rows[i], 1)
+                else:
+                    draft.decode(k, batch=slot + 1)
+                proposals = draft.read_tokens(slot, k)             # (synchronises the draft's stream: the copied rows are complete)
                 counts["draft_steps"] += k
                 if eos_token_id in proposals:              # the draft stops proposing after its own EOS
                     keep = proposals.index(eos_token_id) + 1
                     draft.rewind(slot, k - keep)
                     proposals = proposals[:keep]
             fed = [token] + proposals
+            if sampling:
+                emitted = target.verify_sampled(slot, fed, draft_rows, (temperature, top_k, top_p))
+                counts["target_calls"] += 1
+                counts["proposed"] += len(proposals)
+                a = len(emitted) - 1                       # proposals accepted; emitted[a] follows fed[0..a]
+                stop = next((i for i in range(1, a + 1) if fed[i] == eos_token_id), None)
+                if stop is None and a == len(proposals):   # everything accepted: the last row's own draw is a bonus token
+                    out.extend(fed)
+                    counts["accepted"] += len(proposals)
+                    if proposals:
+                        draft.decode(1, batch=slot + 1)
+                        counts["draft_steps"] += 1
+                    token = emitted[a]
+                    continue
+                cut = a + 1 if stop is None else stop      # fed[:cut] is emitted, fed[cut:] leaves both caches
+                out.extend(fed[:cut])
+                counts["accepted"] += cut - 1
+                counts["resampled"] += int(stop is None)
+                target.rewind(slot, len(fed) - cut)
+                if proposals:
+                    draft.rewind(slot, len(proposals) - cut)
+                token = emitted[a] if stop is None else eos_token_id
+                continue
             predicted = target.verify(slot, fed)
             counts["target_calls"] += 1
             counts["proposed"] += len(proposals)
