@@ -7,11 +7,13 @@
 #include <cstdlib>
 #include <initializer_list>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/tinyllm_engine.h"
 #include "common.h"
+#include "device_block.h"
 #include "engine_kernels.h"
 #include "qmv.h"
 #include "qmv3.h"
@@ -28,8 +30,6 @@ namespace tl {
         if (rc__ != TL_OK) return rc__; \
     } while (0)
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // ---- profile step bookkeeping -------------------------------------------------------------------------
 // tl_engine_check_step (test-only): the hand-over regions -- [0] the shared activations of the arena, [1] the per-layer buffers -- with
 // a shadow copy and one "written this step" byte per 2-byte element each, alive only inside the call
@@ -45,16 +45,11 @@ struct WrittenOnceCheck {
 struct ProfCtx {
     hipStream_t stream = nullptr;             // the stream of the stamped launches
     const WrittenOnceCheck *check = nullptr;  // tl_engine_check_step: the checker runs behind every stamped launch
+    DeviceBlock buf_mem, pairs_mem;
     prof_t *buf = nullptr;    // per-workgroup (start, end) pairs of the launch in flight
     prof_t *pairs = nullptr;  // [n][2] reduced (start, end) per launch
     std::vector<int> kinds;
     int cap = 0;
-    ProfCtx() = default;
-    ProfCtx(const ProfCtx &) = delete;
-    ~ProfCtx() {
-        if (buf) (void)hipFree(buf);
-        if (pairs) (void)hipFree(pairs);
-    }
     // room for one eagerly launched step over `batch` rows (tl_engine_profile_step, tl_engine_check_step): the largest grid of the
     // step -- the lm_head GEMV (4 rows per workgroup at worst) or the attention grid -- and up to 11 launches per layer at 5 .. 64 rows
     // (four skinny matmuls + reductions, attention, merge, norms); the stamps start zeroed, stream-ordered
@@ -62,8 +57,10 @@ struct ProfCtx {
         stream = st;
         const size_t buf_bytes = (size_t)(std::max(c.vocab_size / 4 + 64, 64 * 4 * c.num_kv_heads * batch) + 1024) * 2 * sizeof(prof_t);
         cap = c.num_layers * 12 + 8;
-        return hipMalloc((void **)&buf, buf_bytes) == hipSuccess && hipMalloc((void **)&pairs, (size_t)cap * 2 * sizeof(prof_t)) == hipSuccess &&
-               hipMemsetAsync(buf, 0, buf_bytes, stream) == hipSuccess;
+        if (buf_mem.alloc(buf_bytes, "hipMalloc(stamps) failed") != TL_OK || pairs_mem.alloc((size_t)cap * 2 * sizeof(prof_t), "hipMalloc(stamp pairs) failed") != TL_OK)
+            return false;
+        buf = buf_mem.at<prof_t>(), pairs = pairs_mem.at<prof_t>();
+        return hipMemsetAsync(buf, 0, buf_bytes, stream) == hipSuccess;
     }
 };
 
@@ -84,6 +81,23 @@ static void prof_after(ProfCtx *pc, int kind, int n_wg) {
 struct TiledW4 {
     uint32_t *wt = nullptr, *sbt = nullptr;
 };
+// ... and the owner of its two allocations
+struct TiledW4Mem {
+    DeviceBlock wt, sbt;
+};
+// the tiled copy of `w` (rows a multiple of 16, columns of 128) into fresh allocations, repacked on `st`; all or nothing
+static int tiled_w4_make(const tl_w4 &w, hipStream_t st, TiledW4Mem &mem, TiledW4 &t, const char *alloc_failed, const char *repack_failed) {
+    const size_t wbytes = (size_t)w.rows * w.cols / 2, sbytes = (size_t)w.rows * (w.cols / 128) * 4;
+    TiledW4Mem m;
+    TL_TRY(m.wt.alloc(wbytes + 16384, alloc_failed));  // + slack: fixed-length wave slices
+    TL_TRY(m.sbt.alloc(sbytes + 1024, alloc_failed));
+    if (repack_w4_tiled(w.weight_dev, (const uint16_t *)w.scales_dev, (const uint16_t *)w.biases_dev, m.wt.at<uint32_t>(), m.sbt.at<uint32_t>(), w.rows,
+                        w.cols, st) != 0)
+        return fail(TL_ERR_HIP, repack_failed);
+    t.wt = m.wt.at<uint32_t>(), t.sbt = m.sbt.at<uint32_t>();
+    mem = std::move(m);
+    return TL_OK;
+}
 
 struct LinearCtx {
     hipStream_t stream = nullptr;
@@ -545,6 +559,7 @@ static bool rows_travel_in_fragment_order(const LinearCtx &ctx, const tl_layer_w
 struct tl_tiled_w4 {
     tl_w4 w{};
     tl::TiledW4 t{};
+    tl::TiledW4Mem mem;
 };
 
 extern "C" int tl_tiled_w4_create(const tl_w4 *w, void *stream, tl_tiled_w4 **out) {
@@ -553,35 +568,14 @@ extern "C" int tl_tiled_w4_create(const tl_w4 *w, void *stream, tl_tiled_w4 **ou
     TL_TRY(check_w4(*w, w->rows, w->cols, "tiled_w4_create"));
     TL_REQUIRE(w->rows > 0 && w->rows % 16 == 0 && w->cols > 0 && w->cols % 128 == 0,
                "tiled_w4_create: rows must be a multiple of 16 and cols a multiple of 128");
-    auto *t = new tl_tiled_w4();
+    auto t = std::make_unique<tl_tiled_w4>();
     t->w = *w;
-    const size_t wbytes = (size_t)w->rows * w->cols / 2, sbytes = (size_t)w->rows * (w->cols / 128) * 4;
-    if (hipMalloc((void **)&t->t.wt, wbytes + 16384) != hipSuccess) {
-        delete t;
-        return fail(TL_ERR_HIP, "tiled_w4_create: hipMalloc failed");
-    }
-    if (hipMalloc((void **)&t->t.sbt, sbytes + 1024) != hipSuccess) {
-        (void)hipFree(t->t.wt);
-        delete t;
-        return fail(TL_ERR_HIP, "tiled_w4_create: hipMalloc failed");
-    }
-    if (repack_w4_tiled(w->weight_dev, (const uint16_t *)w->scales_dev, (const uint16_t *)w->biases_dev, t->t.wt, t->t.sbt, w->rows,
-                        w->cols, (hipStream_t)stream) != 0) {
-        (void)hipFree(t->t.wt);
-        (void)hipFree(t->t.sbt);
-        delete t;
-        return fail(TL_ERR_HIP, "tiled_w4_create: repack launch failed");
-    }
-    *out = t;
+    TL_TRY(tiled_w4_make(*w, (hipStream_t)stream, t->mem, t->t, "tiled_w4_create: hipMalloc failed", "tiled_w4_create: repack launch failed"));
+    *out = t.release();
     return TL_OK;
 }
 
-extern "C" void tl_tiled_w4_destroy(tl_tiled_w4 *t) {
-    if (!t) return;
-    (void)hipFree(t->t.wt);
-    (void)hipFree(t->t.sbt);
-    delete t;
-}
+extern "C" void tl_tiled_w4_destroy(tl_tiled_w4 *t) { delete t; }
 
 extern "C" size_t tl_decode_linear_workspace_bytes(int M, int rows, int cols) {
     using namespace tl;

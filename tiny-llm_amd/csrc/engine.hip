@@ -11,6 +11,7 @@
 #include <memory>
 
 #include "decode_linear.h"  // the projection router; with it common.h, engine_kernels.h and the decode matmuls' headers
+#include "device_block.h"
 #include "step_end.h"  // the three step-end kernels; with it sample.h and logprob.h
 #include "logit_process.h"
 #include "truncate.h"
@@ -44,7 +45,7 @@ struct tl_vocab {
     int vocab = 0;
     std::vector<int32_t> offsets;
     std::vector<uint8_t> bytes;
-    char *mem = nullptr;
+    DeviceBlock mem;
     int32_t *offsets_dev = nullptr;
     uint8_t *bytes_dev = nullptr;
     // the long tokens (more than GR_LONG bytes): their ids, ascending, and per token its number among them
@@ -57,7 +58,7 @@ struct tl_grammar {
     std::vector<uint16_t> table;
     std::vector<uint8_t> accepting;
     std::vector<int32_t> eos;
-    char *mem = nullptr;
+    DeviceBlock mem;
     GrammarDev *dev = nullptr;  // what a slot's pointer is poked to
     bool is_eos(int token) const { return std::find(eos.begin(), eos.end(), token) != eos.end(); }
     // state' of the definition, on the host copies
@@ -112,7 +113,7 @@ struct tl_grammar {
 struct tl_stop {
     StopSet set;
     const tl_vocab *vocab = nullptr;  // the vocabulary the text is counted and the strings are matched in (borrowed); may be null for a set of ids
-    char *mem = nullptr;
+    DeviceBlock mem;
     StopDev *dev = nullptr;  // what a slot's pointer is poked to
 };
 
@@ -122,11 +123,20 @@ struct tl_engine {
     tl_w4 embed{}, lm_head{};
     const void *final_norm = nullptr;
     hipStream_t stream = nullptr;
-    bool owns_stream = false;
+    // the stream the engine created for itself (null: the caller's).  Declared ahead of every DeviceBlock: members go in reverse
+    // order, so the stream outlives the memory its work touched
+    struct OwnedStream {
+        hipStream_t s = nullptr;
+        ~OwnedStream() {
+            if (s) (void)hipStreamDestroy(s);
+        }
+    } owned_stream;
 
-    // device memory (one arena for state + activations, one for KV)
-    char *arena = nullptr;
+    // device memory (one arena for state + activations, one for KV).  Every allocation has its DeviceBlock here (device_block.h); the
+    // typed pointers beside them are what the launches read
+    DeviceBlock arena;
     size_t arena_bytes = 0;
+    DeviceBlock kv_mem[4];  // key pages, value pages, and (FP8) their scales
     uint16_t *kpool = nullptr, *vpool = nullptr;  // [layers][P, Hkv, page, D]
     size_t layer_pool_elems = 0, kv_bytes = 0;
     // FP8 pages (tl_engine_create_kv, kv8.h): the pools hold one byte per element and the rows' scales live beside them
@@ -138,6 +148,9 @@ struct tl_engine {
     float *layer_vs(int l) const { return vscale_pool ? vscale_pool + (size_t)l * layer_scale_elems : nullptr; }
     // what the projection router reads (decode_linear.h): weight copies, matmul workspace, routing options; stream, eps and xn as below
     LinearCtx lin;
+    std::vector<TiledW4Mem> tiled_mem;  // the owners of lin.tiled, lin.bf16w and lin.splitk_ws
+    std::vector<DeviceBlock> bf16w_mem;
+    DeviceBlock splitk_mem;
     size_t tiled_bytes = 0, bf16w_bytes = 0;
 
     int32_t *block_table = nullptr, *context_lens = nullptr, *tokens = nullptr, *live = nullptr, *produced = nullptr,
@@ -174,6 +187,7 @@ struct tl_engine {
         uint64_t seed[8];
         int32_t accept[8], alt[8];  // (results: behind everything the host writes)
     };
+    DeviceBlock spec_mem;
     SpecRecord *spec_rec = nullptr;
     int attn_rq = 0;             // query heads per decode-attention workgroup; 0 = by context (TL_ATTN_RQ at create: 1 or 4)
     int attn_rq1_ctx = 4096;     // contexts up to this many tokens use one query head per workgroup
@@ -192,13 +206,15 @@ struct tl_engine {
     // (slot_table.h).  Its calls report edits; apply_edits puts them on the stream.  `step_edits`: the decode step's list, reused
     SlotTable table;
     SlotEdits step_edits;
+    DeviceBlock kv_pools_mem;
     tl_kv_pool_desc *kv_pools_dev = nullptr;  // [kv_pools_n] every K / V (and scale) pool, for the tail copy of a hit (kv_copy.h)
     int kv_pools_n = 0;
     std::vector<tl_kv_pool_desc> kv_pools_host;  // the same table on the host (record offsets of kv_swap.h)
     // KV swap (tl_engine_swap_space / _park / _unpark; kv_swap.h, slot_table.h): nothing is allocated before the first swap_space.  A
     // parked slot stays live on the host (the table's slot and every per-slot setting keep their values) and is a slot without a
     // sequence on the device (live 0, context 0, block-table row -1): slot_runs() is what a decode step asks
-    char *swap_host = nullptr, *swap_staging = nullptr;  // pinned arena [records][record_bytes]; device staging [swap_staging_pages][record_bytes]
+    DeviceBlock swap_host, swap_staging;  // pinned arena [records][record_bytes]; device staging [swap_staging_pages][record_bytes]
+    DeviceBlock swap_offsets_mem;
     size_t *swap_offsets_dev = nullptr;                  // [kv_pools_n] where each pool's bytes start inside a record
     size_t swap_record_bytes = 0;
     int swap_staging_pages = 0;
@@ -215,14 +231,14 @@ struct tl_engine {
         bool samples() const { return temperature > 0.f; }
     };
     std::vector<SampleParams> smp;
-    char *smp_mem = nullptr;
+    DeviceBlock smp_mem;
     float *smp_temp = nullptr, *smp_topp = nullptr;
     int32_t *smp_topk = nullptr;
     uint64_t *smp_seed = nullptr;
     // per-slot log-probability records (tl_engine_set_logprobs, logprob.h): allocated on the first set_logprobs -- top-N per slot
     // (-1: off), the record ring [max_batch, ring_cap] and the pending record per slot; the host mirror of top-N and, per slot, the
     // value of the slot's `produced` when its records began (tokens since then have records)
-    char *lp_mem = nullptr;
+    DeviceBlock lp_mem;
     int32_t *lp_topn = nullptr;
     uint32_t *lp_ring = nullptr, *lp_pending = nullptr;
     std::vector<int> lp_n, lp_from;
@@ -237,13 +253,13 @@ struct tl_engine {
         bool processes() const { return repetition != 1.f || presence != 0.f || frequency != 0.f || !bias_ids.empty() || grammar; }
     };
     std::vector<PenaltyParams> pen;
-    char *pen_mem = nullptr;
+    DeviceBlock pen_mem;
     uint16_t *pen_history = nullptr, *pen_rows = nullptr;
     float *pen_rep = nullptr, *pen_pres = nullptr, *pen_freq = nullptr, *pen_bias_values = nullptr;
     int32_t *pen_bias_n = nullptr, *pen_bias_ids = nullptr;
     // grammars (tl_engine_set_grammar, grammar.h): allocated by the first call that sets one -- per slot the automaton's device pointer
     // and the state record; gr_pending (kept for every slot, grammar or not): the slot holds a pending token no step has consumed yet
-    char *gr_mem = nullptr;
+    DeviceBlock gr_mem, gr_stack_mem;
     const GrammarDev **gr_ptr = nullptr;
     GrammarRecord *gr_state = nullptr;
     std::vector<char> gr_pending;
@@ -258,16 +274,18 @@ struct tl_engine {
         bool truncates() const { return stateless() || mirostat(); }
     };
     std::vector<TruncParams> trn;
-    char *trn_mem = nullptr;
+    DeviceBlock trn_mem;
     uint16_t *trn_rows = nullptr;
     float *trn_minp = nullptr, *trn_typ = nullptr, *trn_tau = nullptr, *trn_eta = nullptr, *trn_mu = nullptr, *trn_logsum = nullptr;
     // tl_engine_score: the logits of one block of rows and the per-row targets / results, allocated on first use
+    DeviceBlock score_mem;
     uint16_t *score_logits = nullptr;
     int32_t *score_ids = nullptr, *score_argmax = nullptr;
     float *score_lp = nullptr;
     // embeddings (tl_engine_embed / _embed_packed, pool.h): the vectors of a call's finishing sequences [16, hidden] fp32, allocated by the
     // first embed call; the running sums of mean pooling [max_batch, hidden] fp32, allocated by the first MEAN call; and per slot (host
     // only) how many rows its running sum holds, -1: none
+    DeviceBlock emb_out_mem, emb_sums_mem;
     float *emb_out = nullptr, *emb_sums = nullptr;
     std::vector<int> emb_rows;
     // LoRA adapters (tl_engine_lora_load / tl_engine_set_lora, lora.h): per slot the adapter id on the host (-1: none; kept for every
@@ -276,14 +294,14 @@ struct tl_engine {
     // sums of squares, and the rows of residual + delta ahead of a base projection's residual epilogue
     enum { LORA_QKV, LORA_O, LORA_GU, LORA_DOWN, LORA_GROUPS };
     struct LoraResident {
-        char *mem = nullptr;  // the fused matrices of every layer
+        DeviceBlock mem;  // the fused matrices of every layer
         size_t bytes = 0;
         int rank = 0;
         std::vector<char> has;  // [layers][groups]: the adapter adapts that group
     };
     std::vector<LoraResident> lora_ad;
     std::vector<int> lora_of;
-    char *lora_mem = nullptr;
+    DeviceBlock lora_mem;
     LoraDesc *lora_table = nullptr;
     int32_t *lora_slot_dev = nullptr;
     LoraTile *lora_tiles_decode = nullptr, *lora_tiles_prefill = nullptr;
@@ -301,23 +319,28 @@ struct tl_engine {
     };
     std::vector<StopSlot> stop;
     std::vector<StopRecord> stop_host;
-    char *stop_mem = nullptr;
+    DeviceBlock stop_mem;
     const StopDev **stop_sets = nullptr;
     int32_t *stop_armed = nullptr, *stop_max_new = nullptr, *stop_automaton = nullptr;
     StopRecord *stop_rec = nullptr;
     bool stop_dirty = false;
 
     bool warmed = false;
-    std::map<std::pair<int, long>, hipGraphExec_t> graphs;  // (batch, n_splits << 32 | tokens_per_split)
+    // a captured decode step: the executable graph and, where the step may ride the AQL route (below), the same nodes as a program of
+    // dispatch packets.  Keyed by (batch, SplitPlan::key() | StepFeatures::key_bits())
+    struct DecodePlan {
+        hipGraphExec_t exec = nullptr;
+        std::unique_ptr<AqlProgram> program;
+    };
+    std::map<std::pair<int, long>, DecodePlan> plans;
     // AQL replay (aql.h; TL_AQL=1 at create): a captured step also becomes a program of hand-written dispatch packets on the engine's own
     // HSA queue; a plan without a program (a kernel outside the device-only code objects, a node that is not a kernel) stays on hipGraphLaunch
     bool aql_on = false;
     int device = 0;                  // the HIP device the engine was created on: its buffers, its stream, its AQL runtime
     AqlRuntime *aql_rt = nullptr;    // the runtime of that device (aql.h: one per device, process-wide)
     std::unique_ptr<AqlQueue> aql_queue;
-    std::map<std::pair<int, long>, std::unique_ptr<AqlProgram>> aql_programs;
     AqlFences aql_fences;
-    std::string aql_why;  // why the last plan got no program
+    std::string aql_why;  // why the route is not available to this engine (aql_on false)
     // Per-layer decode activations (common.h, "activations between the launches of a decode step"): with the AQL route every value a launch
     // hands to a later launch of the SAME step lives at an address written once per step -- layer l's x / h / weighted h / qkv / attention
     // rows and partials / SwiGLU rows / sums of squares have their own buffers (1-4 rows: the fused-GEMV route; 36 x ~0.3 MB at Qwen3-4B)
@@ -330,7 +353,7 @@ struct tl_engine {
         float *planes[2];
     };
     std::vector<LayerAct> layer_act;
-    char *layer_act_mem = nullptr;
+    DeviceBlock layer_act_mem;
     int layer_act_rows = 0;       // rows the per-layer buffers hold (0: none)
     size_t layer_ws_bytes = 0;    // attention partials per layer
     size_t layer_plane_bytes[2] = {0, 0};  // slice planes per layer: [0] wo, [1] w_down
@@ -340,11 +363,12 @@ struct tl_engine {
     // Qwen3-MoE layers (tl_engine_set_moe_layer): router + stacked experts instead of the dense gate|up / w_down of that layer
     std::vector<tl_moe_weights> moe;  // per layer; num_experts == 0: dense
     int moe_k_max = 0, moe_e_max = 0, moe_i_max = 0;
-    char *moe_ws = nullptr;  // one allocation: router logits, ids, scores, gate / up / act rows, expert outputs
+    DeviceBlock moe_ws;  // one allocation: router logits, ids, scores, gate / up / act rows, expert outputs
     size_t moe_ws_bytes = 0;
     uint16_t *moe_logits = nullptr, *moe_scores = nullptr, *moe_gate = nullptr, *moe_up = nullptr, *moe_act = nullptr, *moe_y = nullptr;
     int32_t *moe_ids = nullptr;
     bool is_moe(int l) const { return l < (int)moe.size() && moe[l].num_experts > 0; }
+    DeviceBlock rope_table_mem, rope_cur_mem;
     float2 *rope_table = nullptr, *rope_cur = nullptr;
     int rope_positions = 0;
     int logits_rows = 0;
@@ -378,15 +402,6 @@ static int poke(tl_engine *e, Pokes &items) {
     TL_CHECK_LAUNCH("engine poke");
     return TL_OK;
 }
-// one allocation laid out front to back: carve(bytes) is where the next 256-byte-aligned piece starts, carve.off the bytes taken so far
-struct Carve {
-    size_t off = 0;
-    size_t operator()(size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    }
-};
 // a float as its word; a 64-bit value (a pointer, a seed) as its two words
 static void poke_float(Pokes &pk, float *at, float v) { pk.emplace_back((int32_t *)at, __builtin_bit_cast(int32_t, v)); }
 static void poke_u64(Pokes &pk, void *at, uint64_t v) {
@@ -511,12 +526,15 @@ static int lp_write(tl_engine *e, int slot, int top_n) {
     if (!e->lp_mem) {
         const int B = e->cfg.max_batch;
         const size_t rec = (size_t)LP_RECORD_WORDS * 4, bytes = (size_t)B * 4 + ((size_t)B * e->ring_cap + B) * rec;
-        if (hipMalloc((void **)&e->lp_mem, bytes) != hipSuccess) return fail(TL_ERR_HIP, "engine_set_logprobs: hipMalloc(records) failed");
-        e->lp_topn = (int32_t *)e->lp_mem;
-        e->lp_pending = (uint32_t *)(e->lp_mem + (size_t)B * 4);
-        e->lp_ring = e->lp_pending + (size_t)B * LP_RECORD_WORDS;
         // all ones: top-N -1 (off), and a record nobody wrote reads as logprob NaN with ids -1
-        TL_HIP(hipMemsetAsync(e->lp_mem, 0xff, (size_t)B * 4 + (size_t)B * rec, e->stream));
+        TL_TRY(alloc_filled(e->lp_mem, bytes, "engine_set_logprobs: hipMalloc(records) failed", [&](char *m) -> int {
+            const hipError_t he = hipMemsetAsync(m, 0xff, (size_t)B * 4 + (size_t)B * rec, e->stream);
+            // (the text TL_HIP gave this call when it stood here on e->lp_mem)
+            return he == hipSuccess ? TL_OK : fail(TL_ERR_HIP, std::string("hipMemsetAsync(e->lp_mem, 0xff, (size_t)B * 4 + (size_t)B * rec, e->stream): ") + hipGetErrorString(he));
+        }));
+        e->lp_topn = e->lp_mem.at<int32_t>();
+        e->lp_pending = e->lp_mem.at<uint32_t>((size_t)B * 4);
+        e->lp_ring = e->lp_pending + (size_t)B * LP_RECORD_WORDS;
         e->lp_n.assign(B, -1);
         e->lp_from.assign(B, 0);
     }
@@ -549,27 +567,21 @@ static const tl_grammar *step_grammar_slot(const tl_engine *e, int slot) { retur
 static int gr_alloc(tl_engine *e) {
     if (e->gr_mem) return TL_OK;
     const size_t B = (size_t)e->cfg.max_batch, bytes = B * (sizeof(GrammarDev *) + sizeof(GrammarRecord));
-    char *m = nullptr;
-    if (hipMalloc((void **)&m, bytes) != hipSuccess) return fail(TL_ERR_HIP, "engine: hipMalloc(grammar slots) failed");
-    if (hipMemsetAsync(m, 0, bytes, e->stream) != hipSuccess) {
-        (void)hipFree(m);
-        return fail(TL_ERR_HIP, "engine: memset(grammar slots) failed");
-    }
-    e->gr_mem = m;
-    e->gr_ptr = (const GrammarDev **)m;
-    e->gr_state = (GrammarRecord *)(m + B * sizeof(GrammarDev *));
+    TL_TRY(alloc_filled(e->gr_mem, bytes, "engine: hipMalloc(grammar slots) failed", [&](char *m) -> int {
+        return hipMemsetAsync(m, 0, bytes, e->stream) == hipSuccess ? TL_OK : fail(TL_ERR_HIP, "engine: memset(grammar slots) failed");
+    }));
+    e->gr_ptr = e->gr_mem.at<const GrammarDev *>();
+    e->gr_state = e->gr_mem.at<GrammarRecord>(B * sizeof(GrammarDev *));
     e->stats.workspace_bytes += bytes;
     return TL_OK;
 }
 static int gr_stack_alloc(tl_engine *e) {
     if (e->gr_stack) return TL_OK;
     const size_t bytes = (size_t)e->cfg.max_batch * sizeof(GrammarStackRecord);
-    if (hipMalloc((void **)&e->gr_stack, bytes) != hipSuccess) return fail(TL_ERR_HIP, "engine: hipMalloc(stack grammar slots) failed");
-    if (hipMemsetAsync(e->gr_stack, 0, bytes, e->stream) != hipSuccess) {
-        (void)hipFree(e->gr_stack);
-        e->gr_stack = nullptr;
-        return fail(TL_ERR_HIP, "engine: memset(stack grammar slots) failed");
-    }
+    TL_TRY(alloc_filled(e->gr_stack_mem, bytes, "engine: hipMalloc(stack grammar slots) failed", [&](char *m) -> int {
+        return hipMemsetAsync(m, 0, bytes, e->stream) == hipSuccess ? TL_OK : fail(TL_ERR_HIP, "engine: memset(stack grammar slots) failed");
+    }));
+    e->gr_stack = e->gr_stack_mem.at<GrammarStackRecord>();
     e->stats.workspace_bytes += bytes;
     return TL_OK;
 }
@@ -588,21 +600,19 @@ static int pen_alloc(tl_engine *e) {
     Carve carve;
     const size_t o_hist = carve(B * V * 2), o_rows = carve(std::max<size_t>(B, 8) * V * 2), o_rep = carve(B * 4), o_pres = carve(B * 4),
                  o_freq = carve(B * 4), o_n = carve(B * 4), o_ids = carve(B * LPR_MAX_BIAS * 4), o_vals = carve(B * LPR_MAX_BIAS * 4);
-    char *m = nullptr;
-    if (hipMalloc((void **)&m, carve.off) != hipSuccess) return fail(TL_ERR_HIP, "engine: hipMalloc(logit processing) failed");
     // everything zero (empty histories, presence / frequency 0, empty lists) but the repetition penalties: 1
-    if (hipMemsetAsync(m, 0, carve.off, e->stream) != hipSuccess) {
-        (void)hipFree(m);
-        return fail(TL_ERR_HIP, "engine: memset(logit processing) failed");
-    }
-    hipLaunchKernelGGL(fill_i32_kernel, dim3(ceil_div((long)B, 256)), dim3(256), 0, e->stream, (int32_t *)(m + o_rep), __builtin_bit_cast(int32_t, 1.0f), (int)B);
-    e->pen_mem = m;
+    TL_TRY(alloc_filled(e->pen_mem, carve.off, "engine: hipMalloc(logit processing) failed", [&](char *m) -> int {
+        if (hipMemsetAsync(m, 0, carve.off, e->stream) != hipSuccess) return fail(TL_ERR_HIP, "engine: memset(logit processing) failed");
+        hipLaunchKernelGGL(fill_i32_kernel, dim3(ceil_div((long)B, 256)), dim3(256), 0, e->stream, (int32_t *)(m + o_rep), __builtin_bit_cast(int32_t, 1.0f), (int)B);
+        TL_CHECK_LAUNCH("engine logit-processing init");
+        return TL_OK;
+    }));
+    char *m = e->pen_mem.at();
     e->pen_history = (uint16_t *)(m + o_hist);
     e->pen_rows = (uint16_t *)(m + o_rows);
     e->pen_rep = (float *)(m + o_rep), e->pen_pres = (float *)(m + o_pres), e->pen_freq = (float *)(m + o_freq);
     e->pen_bias_n = (int32_t *)(m + o_n), e->pen_bias_ids = (int32_t *)(m + o_ids), e->pen_bias_values = (float *)(m + o_vals);
     e->stats.workspace_bytes += carve.off;
-    TL_CHECK_LAUNCH("engine logit-processing init");
     return TL_OK;
 }
 
@@ -705,14 +715,12 @@ static int trn_alloc(tl_engine *e) {
     Carve carve;
     const size_t o_rows = carve(R * V * 2), o_minp = carve(B * 4), o_tau = carve(B * 4), o_eta = carve(B * 4), o_sum = carve(R * 4), o_typ = carve(B * 4),
                  o_mu = carve(B * 4);
-    char *m = nullptr;
-    if (hipMalloc((void **)&m, carve.off) != hipSuccess) return fail(TL_ERR_HIP, "engine: hipMalloc(truncation) failed");
     // zero (min-p, tau, eta off) up to the typical-p array; typical-p and mu: all ones, a NaN (typical-p off, no Mirostat)
-    if (hipMemsetAsync(m, 0, o_typ, e->stream) != hipSuccess || hipMemsetAsync(m + o_typ, 0xff, carve.off - o_typ, e->stream) != hipSuccess) {
-        (void)hipFree(m);
-        return fail(TL_ERR_HIP, "engine: memset(truncation) failed");
-    }
-    e->trn_mem = m;
+    TL_TRY(alloc_filled(e->trn_mem, carve.off, "engine: hipMalloc(truncation) failed", [&](char *m) -> int {
+        const bool ok = hipMemsetAsync(m, 0, o_typ, e->stream) == hipSuccess && hipMemsetAsync(m + o_typ, 0xff, carve.off - o_typ, e->stream) == hipSuccess;
+        return ok ? TL_OK : fail(TL_ERR_HIP, "engine: memset(truncation) failed");
+    }));
+    char *m = e->trn_mem.at();
     e->trn_rows = (uint16_t *)(m + o_rows);
     e->trn_minp = (float *)(m + o_minp), e->trn_typ = (float *)(m + o_typ), e->trn_tau = (float *)(m + o_tau), e->trn_eta = (float *)(m + o_eta);
     e->trn_mu = (float *)(m + o_mu), e->trn_logsum = (float *)(m + o_sum);
@@ -766,7 +774,6 @@ static void launch_mirostat_update(tl_engine *e, const uint16_t *filtered, int r
     if (pc) prof_after(pc, 7, rows);
 }
 
-// Context split of the decode attention: power-of-two bucket >= context, fixed windows of C tokens per workgroup.
 // ---- LoRA adapters (lora.h) ---------------------------------------------------------------------------
 // the slot's adapter id, on the host and -- once an adapter has been loaded -- on the device (skipped while it is the value already)
 static int lora_write(tl_engine *e, int slot, int adapter) {
@@ -807,22 +814,19 @@ static int lora_alloc(tl_engine *e) {
     const size_t o_td = carve((size_t)decode_tiles * sizeof(LoraTile)), o_tp = carve((size_t)cap * sizeof(LoraTile));
     const size_t o_part = carve(lora_partial_floats(cap, in_max) * 4), o_ss = carve(lora_ss_floats(cap, in_max) * 4);
     const size_t o_tmp = carve((size_t)e->rows_cap * c.hidden_size * 2);
-    char *mem = nullptr;
-    if (hipMalloc((void **)&mem, carve.off) != hipSuccess) return fail(TL_ERR_HIP, "engine_lora_load: hipMalloc(adapter table and workspaces) failed");
     std::vector<LoraTile> tiles;
     lora_lookup_tiles(c.max_batch, tiles);
-    hipError_t rc = hipMemset(mem + o_table, 0, table_bytes);
-    if (rc == hipSuccess) rc = hipMemset(mem + o_slot, 0xff, (size_t)c.max_batch * 4);
-    if (rc == hipSuccess) rc = hipMemcpy(mem + o_td, tiles.data(), tiles.size() * sizeof(LoraTile), hipMemcpyHostToDevice);
-    if (rc != hipSuccess) {
-        (void)hipFree(mem);
-        return fail(TL_ERR_HIP, std::string("engine_lora_load: ") + hipGetErrorString(rc));
-    }
-    e->lora_mem = mem;
+    TL_TRY(alloc_filled(e->lora_mem, carve.off, "engine_lora_load: hipMalloc(adapter table and workspaces) failed", [&](char *m) -> int {
+        hipError_t rc = hipMemset(m + o_table, 0, table_bytes);
+        if (rc == hipSuccess) rc = hipMemset(m + o_slot, 0xff, (size_t)c.max_batch * 4);
+        if (rc == hipSuccess) rc = hipMemcpy(m + o_td, tiles.data(), tiles.size() * sizeof(LoraTile), hipMemcpyHostToDevice);
+        return rc == hipSuccess ? TL_OK : fail(TL_ERR_HIP, std::string("engine_lora_load: ") + hipGetErrorString(rc));
+    }));
+    char *mem = e->lora_mem.at();
     e->lora_table = (LoraDesc *)(mem + o_table), e->lora_slot_dev = (int32_t *)(mem + o_slot);
     e->lora_tiles_decode = (LoraTile *)(mem + o_td), e->lora_tiles_prefill = (LoraTile *)(mem + o_tp);
     e->lora_partial = (float *)(mem + o_part), e->lora_ss = (float *)(mem + o_ss), e->lora_tmp = (uint16_t *)(mem + o_tmp);
-    e->lora_ad.assign(TL_MAX_LORA_ADAPTERS, tl_engine::LoraResident{});
+    e->lora_ad.resize(TL_MAX_LORA_ADAPTERS);
     return TL_OK;
 }
 // One adapted projection group of layer l over `n_tiles` tiles: the shrink and the expand launch (lora.h).  norm_w: x is the row ahead
@@ -850,13 +854,10 @@ static int stop_alloc(tl_engine *e) {
     const size_t B = (size_t)e->cfg.max_batch;
     Carve carve;
     const size_t o_sets = carve(B * sizeof(StopDev *)), o_armed = carve(B * 4), o_max = carve(B * 4), o_state = carve(B * 4), o_rec = carve(B * sizeof(StopRecord));
-    char *m = nullptr;
-    if (hipMalloc((void **)&m, carve.off) != hipSuccess) return fail(TL_ERR_HIP, "engine_set_stop: hipMalloc(stop records) failed");
-    if (hipMemsetAsync(m, 0, carve.off, e->stream) != hipSuccess) {
-        (void)hipFree(m);
-        return fail(TL_ERR_HIP, "engine_set_stop: memset(stop records) failed");
-    }
-    e->stop_mem = m;
+    TL_TRY(alloc_filled(e->stop_mem, carve.off, "engine_set_stop: hipMalloc(stop records) failed", [&](char *m) -> int {
+        return hipMemsetAsync(m, 0, carve.off, e->stream) == hipSuccess ? TL_OK : fail(TL_ERR_HIP, "engine_set_stop: memset(stop records) failed");
+    }));
+    char *m = e->stop_mem.at();
     e->stop_sets = (const StopDev **)(m + o_sets);
     e->stop_armed = (int32_t *)(m + o_armed), e->stop_max_new = (int32_t *)(m + o_max), e->stop_automaton = (int32_t *)(m + o_state);
     e->stop_rec = (StopRecord *)(m + o_rec);
@@ -948,6 +949,14 @@ struct StepFeatures {
                (stop ? (1L << 54) : 0L);
     }
 };
+// Why a plan with these features never becomes an AQL program (null: it may), the one sentence tl_engine_replay_route reports: bits 54,
+// 55 and 56 above, the stop launch first
+static const char *graph_only_reason(const StepFeatures &f) {
+    if (f.stop) return "a slot is armed with stop conditions (the stop launch reads the token the step end stored and writes the live word)";
+    if (f.lora) return "a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)";
+    if (f.mirostat) return "a Mirostat slot is live (the update launch reads the token the step end stored)";
+    return nullptr;
+}
 static StepFeatures step_features(const tl_engine *e, int slot0, int n) {
     StepFeatures f;
     for (int slot = slot0; slot < slot0 + n && slot < e->cfg.max_batch; ++slot) {
@@ -991,6 +1000,7 @@ static void launch_logit_chain(tl_engine *e, const uint16_t *raw, int row0, int 
     if (f.stop) launch_stop(e, rows, slot0, pc);
 }
 
+// Context split of the decode attention: power-of-two bucket >= context, fixed windows of C tokens per workgroup.
 struct SplitPlan {
     int n_splits, tokens_per_split;
     int rq;  // query heads per workgroup
@@ -1226,7 +1236,7 @@ static int engine_attention(tl_engine *e, const AttnCall &t, int batch, const Sp
 static int engine_moe_mlp(tl_engine *e, int l, const uint16_t *xn, const uint16_t *h, uint16_t *out, int rows, ProfCtx *pc) {
     const tl_moe_weights &m = e->moe[l];
     const int D = e->cfg.hidden_size, E = m.num_experts, k = m.experts_per_token, I = m.intermediate_size;
-    TL_REQUIRE(e->moe_ws != nullptr && rows <= e->rows_cap && (long)rows * k <= 65535, "engine: MoE workspace missing or too many expert rows");
+    TL_REQUIRE(e->moe_ws && rows <= e->rows_cap && (long)rows * k <= 65535, "engine: MoE workspace missing or too many expert rows");
     // router logits [rows, E] through the reference-semantics matmul (quantized_linear of the router, moe.py:44)
     TL_TRY(engine_qmm(e->lin, m.router, xn, e->moe_logits, rows));
     hipLaunchKernelGGL(moe_route_kernel, dim3(rows), dim3(256), 0, e->stream, e->moe_logits, E, k, m.norm_topk_prob, e->moe_ids, e->moe_scores);
@@ -1275,7 +1285,9 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, const StepFeature
     LinearCtx &ctx = e->lin;
     StepRoute route = plan_step(e, batch, sp);
     // A step in which a live slot carries a LoRA adapter (lora.h): every projection leaves complete bf16 rows in the shared buffers, the
-    // shrink / expand launches stand around them (8 more per dense layer), and the step keeps its launch boundaries
+    // shrink / expand launches stand around them (8 more per dense layer), and the step keeps its launch boundaries.  Its layers are
+    // never batched and hand nothing over weighted, kept as slice partials or unmerged; the two residual projections add to
+    // residual + delta in lora_tmp, and gate|up stores complete rows for the expand launch's SwiGLU
     const bool lora = f.lora;
     if (lora) route.per_layer = route.per_layer_b = false;
     const int lora_tiles = ceil_div(batch, LORA_TILE);
@@ -1297,48 +1309,10 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, const StepFeature
     for (int l = 0; l < c.num_layers; ++l) {
         const tl_layer_weights &w = e->layers[l];
         const LayerRoute &rt = route.layers[l];
-        if (lora) {
-            const tl_engine::LayerAct &b = shared;
-            ProjResult r;
-            Proj p = proj(w.wqkv, x_cur, b.qkv, batch);
-            p.pro = PRO_RMSNORM, p.norm_w = w.input_norm_dev, p.ss_in = x_ss ? ssx_cur : nullptr, p.ss_in_n = x_ss;
-            TL_TRY(engine_linear(ctx, p, pc, &r));
-            TL_TRY(lora_group(e, l, tl_engine::LORA_QKV, e->lora_tiles_decode, lora_tiles, batch, x_cur, w.input_norm_dev, TL_LORA_ADD, nullptr, b.qkv));
-            AttnCall at{};
-            at.qkv = b.qkv, at.q_norm = w.q_norm_dev, at.k_norm = w.k_norm_dev, at.key_pages = e->layer_k(l), at.value_pages = e->layer_v(l);
-            at.key_scales = e->layer_ks(l), at.value_scales = e->layer_vs(l), at.out = b.attn, at.ws = b.attn_ws;
-            TL_TRY(engine_attention(e, at, batch, sp, pc));  // (no merging wo: the attention merges its own windows)
-            TL_TRY(lora_group(e, l, tl_engine::LORA_O, e->lora_tiles_decode, lora_tiles, batch, b.attn, nullptr, TL_LORA_RESIDUAL_PRE, x_cur, e->lora_tmp));
-            Proj po = proj(w.wo, b.attn, b.h, batch);
-            po.epi = EPI_RESIDUAL, po.residual = e->lora_tmp, po.kind = 1;
-            x_cur = b.x_out, ssx_cur = b.ss_x_out;
-            xw = false;
-            if (e->is_moe(l)) {
-                TL_TRY(engine_linear(ctx, po, pc));
-                TL_TRY(tl_rms_norm(b.h, w.post_norm_dev, b.xn, batch, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
-                TL_TRY(engine_moe_mlp(e, l, b.xn, b.h, b.x_out, batch, pc));
-                x_ss = 0;
-                continue;
-            }
-            TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
-            po.ss_out = b.ss_h;
-            TL_TRY(engine_linear(ctx, po, pc, &r));
-            const int h_ss = r.ss_n;
-            Proj pg = proj(w.wgu, b.h, ctx.gu, batch);  // complete gate|up rows; the expand launch's SwiGLU over base + delta
-            pg.pro = PRO_RMSNORM, pg.norm_w = w.post_norm_dev, pg.kind = 2, pg.ss_in = h_ss ? b.ss_h : nullptr, pg.ss_in_n = h_ss;
-            TL_TRY(engine_linear(ctx, pg, pc));
-            TL_TRY(lora_group(e, l, tl_engine::LORA_GU, e->lora_tiles_decode, lora_tiles, batch, b.h, w.post_norm_dev, TL_LORA_SWIGLU, ctx.gu, b.act));
-            TL_TRY(lora_group(e, l, tl_engine::LORA_DOWN, e->lora_tiles_decode, lora_tiles, batch, b.act, nullptr, TL_LORA_RESIDUAL_PRE, b.h, e->lora_tmp));
-            Proj pd = proj(w.wdown, b.act, b.x_out, batch);
-            pd.epi = EPI_RESIDUAL, pd.residual = e->lora_tmp, pd.kind = 3, pd.ss_out = b.ss_x_out;
-            TL_TRY(engine_linear(ctx, pd, pc, &r));
-            x_ss = r.ss_n;
-            continue;
-        }
         // The one input of a route that is not known ahead: are the row's sums of squares there when the layer starts?  In a dense model
         // they are -- QM3_SS per row from the embedding kernels, QM3_SS or rows / 16 from a w_down that leaves weighted rows -- so this cannot
         // fire there; should it ever, the step must not be replayed as "written once" over buffers written several times
-        const bool batched = rt.batched && x_ss > 0 && qmm3_takes_ss(x_ss);
+        const bool batched = !lora && rt.batched && x_ss > 0 && qmm3_takes_ss(x_ss);
         TL_REQUIRE(batched || !route.per_layer_b, "engine: a layer fell out of the batched branch of a step planned on the per-layer buffers");
         const tl_engine::LayerAct &b = (batched ? route.per_layer_b : route.per_layer) ? e->layer_act[l] : shared;
         ProjResult r;
@@ -1355,19 +1329,21 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, const StepFeature
         } else {
             Proj p = proj(w.wqkv, x_cur, b.qkv, batch);
             p.pro = PRO_RMSNORM, p.norm_w = w.input_norm_dev, p.ss_in = x_ss ? ssx_cur : nullptr, p.ss_in_n = x_ss;
-            p.keep = e->attn_qkv_partials && attn_takes_qkv_partials(c.head_dim, sp.rq);
+            p.keep = !lora && e->attn_qkv_partials && attn_takes_qkv_partials(c.head_dim, sp.rq);
             TL_TRY(engine_linear(ctx, p, pc, &r));
         }
+        if (lora) TL_TRY(lora_group(e, l, tl_engine::LORA_QKV, e->lora_tiles_decode, lora_tiles, batch, x_cur, w.input_norm_dev, TL_LORA_ADD, nullptr, b.qkv));
         xw = false;
         AttnCall at{};
         at.qkv = b.qkv, at.q_norm = w.q_norm_dev, at.k_norm = w.k_norm_dev, at.key_pages = e->layer_k(l), at.value_pages = e->layer_v(l);
         at.key_scales = e->layer_ks(l), at.value_scales = e->layer_vs(l), at.out = b.attn, at.ws = b.attn_ws;
-        at.qkv_parts = r.kept, at.merging_wo = &w.wo;
+        at.qkv_parts = r.kept, at.merging_wo = lora ? nullptr : &w.wo;
         bool merge_left = false;  // the wo GEMV of one row merges the attention windows itself where engine_attention leaves them to it
         TL_TRY(engine_attention(e, at, batch, sp, pc, &merge_left));
         TL_REQUIRE(!(batched && merge_left), "engine: a batched step left its attention windows unmerged");
+        if (lora) TL_TRY(lora_group(e, l, tl_engine::LORA_O, e->lora_tiles_decode, lora_tiles, batch, b.attn, nullptr, TL_LORA_RESIDUAL_PRE, x_cur, e->lora_tmp));
         Proj po = proj(w.wo, b.attn, b.h, batch);
-        po.epi = EPI_RESIDUAL, po.residual = x_cur, po.kind = 1;
+        po.epi = EPI_RESIDUAL, po.residual = lora ? e->lora_tmp : x_cur, po.kind = 1;
         if (merge_left) po.pro = PRO_ATTN_MERGE, po.merge_ws = b.attn_ws, po.n_splits = sp.n_splits;
         x_cur = b.x_out, ssx_cur = b.ss_x_out;  // where the layer leaves the residual stream
         if (e->is_moe(l)) {  // wo + residual, then the MoE MLP as its own launches (no producer-side sums for the next layer)
@@ -1380,20 +1356,27 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, const StepFeature
         TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
         // h leaves wo twice when gate|up can take it weighted (a batched layer; the GEMVs by weighted_rows_apply): as the residual
         // stream and, in xn, times the post-attention norm weight
-        const bool h_weighted = batched || rt.gemv_weighted;
-        po.ss_out = b.ss_h, po.norm_out = w.post_norm_dev, po.out_w = h_weighted ? b.xn : nullptr, po.frag = batched && route.frag;
-        po.planes = b.planes[0], po.planes_bytes = e->layer_plane_bytes[0];
+        const bool h_weighted = !lora && (batched || rt.gemv_weighted);
+        po.ss_out = b.ss_h;
+        if (!lora) {
+            po.norm_out = w.post_norm_dev, po.out_w = h_weighted ? b.xn : nullptr, po.frag = batched && route.frag;
+            po.planes = b.planes[0], po.planes_bytes = e->layer_plane_bytes[0];
+        }
         TL_TRY(batched && rt.wo6 ? engine_qmm6(ctx, po, pc, &r) : engine_linear(ctx, po, pc, &r));
         const int h_ss = r.ss_n;
         if (batched) TL_REQUIRE(h_ss > 0 && qmm3_takes_ss(h_ss), "engine: the wo projection left no sums of squares for its weighted rows");
         else if (h_weighted) TL_REQUIRE(h_ss > 0, "engine: the wo GEMV left no sums of squares for its weighted rows");
-        Proj pg = proj(w.wgu, h_weighted ? b.xn : b.h, b.act, batch);
-        pg.epi = EPI_SWIGLU, pg.kind = 2, pg.ss_in = h_ss ? b.ss_h : nullptr, pg.ss_in_n = h_ss, pg.frag = batched && route.frag;
+        Proj pg = proj(w.wgu, h_weighted ? b.xn : b.h, lora ? ctx.gu : b.act, batch);
+        pg.epi = lora ? EPI_STORE : EPI_SWIGLU, pg.kind = 2, pg.ss_in = h_ss ? b.ss_h : nullptr, pg.ss_in_n = h_ss, pg.frag = batched && route.frag;
         if (!batched) pg.pro = h_weighted ? PRO_RMS_WEIGHTED : PRO_RMSNORM, pg.norm_w = h_weighted ? nullptr : w.post_norm_dev;
         TL_TRY(batched ? engine_qmm6(ctx, pg, pc) : engine_linear(ctx, pg, pc));
+        if (lora) {
+            TL_TRY(lora_group(e, l, tl_engine::LORA_GU, e->lora_tiles_decode, lora_tiles, batch, b.h, w.post_norm_dev, TL_LORA_SWIGLU, ctx.gu, b.act));
+            TL_TRY(lora_group(e, l, tl_engine::LORA_DOWN, e->lora_tiles_decode, lora_tiles, batch, b.act, nullptr, TL_LORA_RESIDUAL_PRE, b.h, e->lora_tmp));
+        }
         Proj pd = proj(w.wdown, b.act, b.x_out, batch);
-        pd.epi = EPI_RESIDUAL, pd.residual = b.h, pd.kind = 3, pd.ss_out = b.ss_x_out;
-        pd.planes = b.planes[1], pd.planes_bytes = e->layer_plane_bytes[1];
+        pd.epi = EPI_RESIDUAL, pd.residual = lora ? e->lora_tmp : b.h, pd.kind = 3, pd.ss_out = b.ss_x_out;
+        if (!lora) pd.planes = b.planes[1], pd.planes_bytes = e->layer_plane_bytes[1];
         const bool x_weighted = batched && rt.down != LayerRoute::DOWN_ROUTER;
         if (x_weighted) {
             // the rows w_down leaves are weighted for their next reader: the next layer's input norm, or the final norm ahead of lm_head
@@ -1564,13 +1547,12 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     TL_TRY(check_w4(*embed, c.vocab_size, c.hidden_size, "embed_tokens"));
     if (lm_head) TL_TRY(check_w4(*lm_head, c.vocab_size, c.hidden_size, "lm_head"));
 
-    auto *e = new tl_engine();
+    // a failure below tears the partly built engine down like any other: tl_engine_destroy, and with it every block it holds so far
+    std::unique_ptr<tl_engine, void (*)(tl_engine *)> owner(new tl_engine(), tl_engine_destroy);
+    tl_engine *e = owner.get();
     e->cfg = c;
     e->kv_format = kv_format;
-    if (hipGetDevice(&e->device) != hipSuccess) {
-        delete e;
-        return fail(TL_ERR_HIP, "engine_create: hipGetDevice failed");
-    }
+    if (hipGetDevice(&e->device) != hipSuccess) return fail(TL_ERR_HIP, "engine_create: hipGetDevice failed");
     e->layers.assign(layers, layers + c.num_layers);
     e->embed = *embed;
     if (lm_head) e->lm_head = *lm_head;
@@ -1579,12 +1561,9 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     if (!e->stream) {
         // The legacy default stream cannot be captured into a graph: own a non-blocking stream instead, and
         // make sure everything the caller enqueued before (weight uploads / re-packing) has finished.
-        if (hipDeviceSynchronize() != hipSuccess ||
-            hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
-            delete e;
+        if (hipDeviceSynchronize() != hipSuccess || hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
             return fail(TL_ERR_HIP, "engine_create: could not create the engine stream");
-        }
-        e->owns_stream = true;
+        e->owned_stream.s = e->stream;
     }
     e->rows_cap = std::max(c.max_prefill_rows, c.max_batch);
 
@@ -1629,42 +1608,39 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     const size_t o_ws = carve(e->attn_ws_bytes);
     e->arena_bytes = carve.off;
 
-    // from here on a failure tears the partly built engine down like any other: tl_engine_destroy frees whatever it holds
-    auto destroy_fail = [&](const std::string &msg) {
-        tl_engine_destroy(e);
-        return fail(TL_ERR_HIP, msg);
-    };
-    if (hipMalloc((void **)&e->arena, e->arena_bytes) != hipSuccess) return destroy_fail("engine_create: hipMalloc(arena) failed");
+    TL_TRY(e->arena.alloc(e->arena_bytes, "engine_create: hipMalloc(arena) failed"));
     // sampling parameters per slot (all zero: greedy): seeds first for their 8-byte alignment
-    if (hipMalloc((void **)&e->smp_mem, (size_t)c.max_batch * 20) != hipSuccess) return destroy_fail("engine_create: hipMalloc(sampling) failed");
-    e->smp_seed = (uint64_t *)e->smp_mem;
-    e->smp_temp = (float *)(e->smp_mem + (size_t)c.max_batch * 8);
-    e->smp_topk = (int32_t *)(e->smp_mem + (size_t)c.max_batch * 12);
-    e->smp_topp = (float *)(e->smp_mem + (size_t)c.max_batch * 16);
-    if (hipMemsetAsync(e->smp_mem, 0, (size_t)c.max_batch * 20, e->stream) != hipSuccess) return destroy_fail("engine_create: memset failed");
+    TL_TRY(e->smp_mem.alloc((size_t)c.max_batch * 20, "engine_create: hipMalloc(sampling) failed"));
+    e->smp_seed = e->smp_mem.at<uint64_t>();
+    e->smp_temp = e->smp_mem.at<float>((size_t)c.max_batch * 8);
+    e->smp_topk = e->smp_mem.at<int32_t>((size_t)c.max_batch * 12);
+    e->smp_topp = e->smp_mem.at<float>((size_t)c.max_batch * 16);
+    if (hipMemsetAsync(e->smp_mem.at(), 0, (size_t)c.max_batch * 20, e->stream) != hipSuccess) return fail(TL_ERR_HIP, "engine_create: memset failed");
     e->layer_pool_elems = (size_t)c.num_pages * c.num_kv_heads * c.page_size * c.head_dim;
     const size_t pool_bytes = e->layer_pool_elems * e->kv_elem_bytes() * c.num_layers;
-    if (hipMalloc((void **)&e->kpool, pool_bytes) != hipSuccess) return destroy_fail("engine_create: hipMalloc(key pages) failed");
-    if (hipMalloc((void **)&e->vpool, pool_bytes) != hipSuccess) return destroy_fail("engine_create: hipMalloc(value pages) failed");
+    TL_TRY(e->kv_mem[0].alloc(pool_bytes, "engine_create: hipMalloc(key pages) failed"));
+    TL_TRY(e->kv_mem[1].alloc(pool_bytes, "engine_create: hipMalloc(value pages) failed"));
+    e->kpool = e->kv_mem[0].at<uint16_t>(), e->vpool = e->kv_mem[1].at<uint16_t>();
     e->kv_bytes = 2 * pool_bytes;
     if (kv_format == TL_KV_FP8_E4M3) {
         // one float32 scale per (page, kv head, slot) row; zero like the codes (a zero scale times a zero code is the zero the bf16 pool holds)
         e->layer_scale_elems = (size_t)c.num_pages * c.num_kv_heads * c.page_size;
         const size_t scale_bytes = e->layer_scale_elems * 4 * c.num_layers;
-        if (hipMalloc((void **)&e->kscale_pool, scale_bytes) != hipSuccess) return destroy_fail("engine_create: hipMalloc(key scales) failed");
-        if (hipMalloc((void **)&e->vscale_pool, scale_bytes) != hipSuccess) return destroy_fail("engine_create: hipMalloc(value scales) failed");
+        TL_TRY(e->kv_mem[2].alloc(scale_bytes, "engine_create: hipMalloc(key scales) failed"));
+        TL_TRY(e->kv_mem[3].alloc(scale_bytes, "engine_create: hipMalloc(value scales) failed"));
+        e->kscale_pool = e->kv_mem[2].at<float>(), e->vscale_pool = e->kv_mem[3].at<float>();
         if (hipMemsetAsync(e->kscale_pool, 0, scale_bytes, e->stream) != hipSuccess ||
             hipMemsetAsync(e->vscale_pool, 0, scale_bytes, e->stream) != hipSuccess)
-            return destroy_fail("engine_create: memset(KV scales) failed");
+            return fail(TL_ERR_HIP, "engine_create: memset(KV scales) failed");
         e->kv_bytes += 2 * scale_bytes;
     }
     // Masked (out-of-context) token slots are still loaded and multiplied by a zero weight in the decode kernel,
     // so the pools must never hold NaN/Inf bit patterns: start from zeros (kernels only ever write finite values).
     if (hipMemsetAsync(e->kpool, 0, pool_bytes, e->stream) != hipSuccess ||
         hipMemsetAsync(e->vpool, 0, pool_bytes, e->stream) != hipSuccess)
-        return destroy_fail("engine_create: memset(KV pools) failed");
+        return fail(TL_ERR_HIP, "engine_create: memset(KV pools) failed");
 
-    char *A = e->arena;
+    char *A = e->arena.at();
     e->block_table = (int32_t *)(A + o_bt);
     e->context_lens = (int32_t *)(A + o_ctx);
     e->tokens = (int32_t *)(A + o_tok);
@@ -1707,9 +1683,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
                 e->aql_why = rt.ok() ? why : rt.why();
                 e->aql_queue.reset();
                 if (aql_env != nullptr) {
-                    const std::string msg = "engine_create: TL_AQL=1 but the AQL route is not available: " + e->aql_why;
-                    tl_engine_destroy(e);
-                    return fail(TL_ERR_UNSUPPORTED, msg);
+                    return fail(TL_ERR_UNSUPPORTED, "engine_create: TL_AQL=1 but the AQL route is not available: " + e->aql_why);
                 }
             }
         }
@@ -1740,12 +1714,12 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
                     if (pd.ok) b_pl[1] = std::max(b_pl[1], align_up(pd.partial_bytes, 256));
                 }
                 const size_t per_layer = 2 * b_x + 2 * b_xf + b_qkv + b_attn + b_act + 2 * b_ss + b_ws + b_pl[0] + b_pl[1];
-                if (hipMalloc((void **)&e->layer_act_mem, per_layer * c.num_layers) != hipSuccess ||
-                    hipMemsetAsync(e->layer_act_mem, 0, per_layer * c.num_layers, e->stream) != hipSuccess)
-                    return destroy_fail("engine_create: hipMalloc(per-layer decode activations) failed");
+                TL_TRY(e->layer_act_mem.alloc(per_layer * c.num_layers, "engine_create: hipMalloc(per-layer decode activations) failed"));
+                if (hipMemsetAsync(e->layer_act_mem.at(), 0, per_layer * c.num_layers, e->stream) != hipSuccess)
+                    return fail(TL_ERR_HIP, "engine_create: hipMalloc(per-layer decode activations) failed");
                 e->layer_act.resize(c.num_layers);
                 for (int l = 0; l < c.num_layers; ++l) {
-                    char *m = e->layer_act_mem + (size_t)l * per_layer;
+                    char *m = e->layer_act_mem.at((size_t)l * per_layer);
                     tl_engine::LayerAct &a = e->layer_act[l];
                     a.x_out = (uint16_t *)m, m += b_x;
                     a.h = (uint16_t *)m, m += b_x;
@@ -1769,45 +1743,35 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     }
 
     // state words: zero everything up to the activations, then the block table to -1
-    if (hipMemsetAsync(e->arena, 0, o_x, e->stream) != hipSuccess) return destroy_fail("engine_create: memset failed");
+    if (hipMemsetAsync(e->arena.at(), 0, o_x, e->stream) != hipSuccess) return fail(TL_ERR_HIP, "engine_create: memset failed");
     const int bt_n = c.max_batch * c.max_pages_per_seq;
     hipLaunchKernelGGL(fill_i32_kernel, dim3(ceil_div(bt_n, 256)), dim3(256), 0, e->stream, e->block_table, -1, bt_n);
-    if (hipGetLastError() != hipSuccess) return destroy_fail("engine_create: block-table init failed");
+    if (hipGetLastError() != hipSuccess) return fail(TL_ERR_HIP, "engine_create: block-table init failed");
 
     // RoPE table for every position a sequence can reach
     {
         const long max_pos = std::min<long>((long)c.max_pages_per_seq * c.page_size + 1, 1 << 20);
         e->rope_positions = (int)max_pos;
         const int half = c.head_dim / 2;
-        if (hipMalloc((void **)&e->rope_table, (size_t)max_pos * half * sizeof(float2)) != hipSuccess)
-            return destroy_fail("engine_create: hipMalloc(rope table) failed");
+        TL_TRY(e->rope_table_mem.alloc((size_t)max_pos * half * sizeof(float2), "engine_create: hipMalloc(rope table) failed"));
+        e->rope_table = e->rope_table_mem.at<float2>();
         hipLaunchKernelGGL(rope_table_kernel, dim3(ceil_div(max_pos * half, 256)), dim3(256), 0, e->stream, e->rope_table,
                            (int)max_pos, half, c.rope_theta);
-        if (hipGetLastError() != hipSuccess) return destroy_fail("engine_create: rope table kernel failed");
-        if (hipMalloc((void **)&e->rope_cur, (size_t)c.max_batch * half * sizeof(float2)) != hipSuccess ||
-            hipMemsetAsync(e->rope_cur, 0, (size_t)c.max_batch * half * sizeof(float2), e->stream) != hipSuccess)
-            return destroy_fail("engine_create: hipMalloc(rope state) failed");
+        if (hipGetLastError() != hipSuccess) return fail(TL_ERR_HIP, "engine_create: rope table kernel failed");
+        TL_TRY(e->rope_cur_mem.alloc((size_t)c.max_batch * half * sizeof(float2), "engine_create: hipMalloc(rope state) failed"));
+        e->rope_cur = e->rope_cur_mem.at<float2>();
+        if (hipMemsetAsync(e->rope_cur, 0, (size_t)c.max_batch * half * sizeof(float2), e->stream) != hipSuccess)
+            return fail(TL_ERR_HIP, "engine_create: hipMalloc(rope state) failed");
     }
 
     // decode-path weight copies in the tiled MFMA layout
     {
         auto add_tiled = [&](const tl_w4 &w) -> bool {
             if (w.rows % 16 != 0 || w.cols % 128 != 0 || e->lin.tiled.count(w.weight_dev)) return true;
-            TiledW4 t;
-            const size_t wbytes = (size_t)w.rows * w.cols / 2, sbytes = (size_t)w.rows * (w.cols / 128) * 4;
-            if (hipMalloc((void **)&t.wt, wbytes + 16384) != hipSuccess) return false;  // + slack: fixed-length wave slices
-            if (hipMalloc((void **)&t.sbt, sbytes + 1024) != hipSuccess) {
-                (void)hipFree(t.wt);
-                return false;
-            }
-            if (repack_w4_tiled(w.weight_dev, (const uint16_t *)w.scales_dev, (const uint16_t *)w.biases_dev, t.wt, t.sbt, w.rows,
-                                w.cols, e->stream) != 0) {
-                (void)hipFree(t.wt);
-                (void)hipFree(t.sbt);
-                return false;
-            }
-            e->lin.tiled[w.weight_dev] = t;
-            e->tiled_bytes += wbytes + sbytes;
+            const char *failed = "engine_create: hipMalloc(tiled weights) failed";
+            e->tiled_mem.emplace_back();
+            if (tiled_w4_make(w, e->stream, e->tiled_mem.back(), e->lin.tiled[w.weight_dev], failed, failed) != TL_OK) return false;
+            e->tiled_bytes += (size_t)w.rows * w.cols / 2 + (size_t)w.rows * (w.cols / 128) * 4;
             return true;
         };
         bool ok = true;
@@ -1816,18 +1780,17 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
             if (l.wgu.weight_dev) ok = ok && add_tiled(l.wgu) && add_tiled(l.wdown);
         }
         ok = ok && add_tiled(e->head());
-        if (!ok) return destroy_fail("engine_create: hipMalloc(tiled weights) failed");
+        if (!ok) return fail(TL_ERR_HIP, "engine_create: hipMalloc(tiled weights) failed");
     }
     if (c.max_prefill_rows >= GEMM8_MIN_ROWS) {  // the caller asked for chunks the plain bf16 GEMM takes: expand the layer matrices once
         auto add_bf16 = [&](const tl_w4 &w) -> bool {
             if (!w.weight_dev || w.cols % 128 != 0 || e->lin.bf16w.count(w.weight_dev) || !gemm8_applicable(c.max_prefill_rows, w.rows, w.cols)) return true;
-            uint16_t *wb = nullptr;
             const size_t bytes = (size_t)w.rows * w.cols * 2;
-            if (hipMalloc((void **)&wb, bytes) != hipSuccess) return false;
-            if (dequant_w4_to_bf16(w.weight_dev, (const uint16_t *)w.scales_dev, (const uint16_t *)w.biases_dev, wb, w.rows, w.cols, e->stream) != 0) {
-                (void)hipFree(wb);
-                return false;
-            }
+            DeviceBlock copy;
+            if (copy.alloc(bytes, "engine_create: hipMalloc(bf16 weights for the prefill GEMM) failed") != TL_OK) return false;
+            uint16_t *wb = copy.at<uint16_t>();
+            if (dequant_w4_to_bf16(w.weight_dev, (const uint16_t *)w.scales_dev, (const uint16_t *)w.biases_dev, wb, w.rows, w.cols, e->stream) != 0) return false;
+            e->bf16w_mem.push_back(std::move(copy));
             e->lin.bf16w[w.weight_dev] = wb;
             e->bf16w_bytes += bytes;
             return true;
@@ -1837,7 +1800,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
             ok = ok && add_bf16(l.wqkv) && add_bf16(l.wo);
             if (l.wgu.weight_dev) ok = ok && add_bf16(l.wgu) && add_bf16(l.wdown);
         }
-        if (!ok) return destroy_fail("engine_create: hipMalloc(bf16 weights for the prefill GEMM) failed");
+        if (!ok) return fail(TL_ERR_HIP, "engine_create: hipMalloc(bf16 weights for the prefill GEMM) failed");
     }
 
     {
@@ -1862,8 +1825,8 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
                 need = std::max(need, tl_quantized_matmul_workspace_bytes(M, w->cols, w->rows, TL_BF16, 1, 1));
         }
         if (need > 0) {
-            if (hipMalloc(&e->lin.splitk_ws, need) != hipSuccess) return destroy_fail("engine_create: hipMalloc(matmul workspace) failed");
-            e->lin.splitk_ws_bytes = need;
+            TL_TRY(e->splitk_mem.alloc(need, "engine_create: hipMalloc(matmul workspace) failed"));
+            e->lin.splitk_ws = e->splitk_mem.at<void>(), e->lin.splitk_ws_bytes = need;
         }
     }
 
@@ -1878,7 +1841,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->stop.assign(c.max_batch, tl_engine::StopSlot{});
     e->stats.kv_bytes = e->kv_bytes;
     e->stats.workspace_bytes = e->arena_bytes + e->tiled_bytes + e->bf16w_bytes;
-    *out = e;
+    *out = owner.release();
     return TL_OK;
 }
 
@@ -1886,7 +1849,7 @@ extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_wei
     TL_REQUIRE(e && w, "engine_set_moe_layer: null argument");
     const tl_engine_config &c = e->cfg;
     TL_REQUIRE(layer >= 0 && layer < c.num_layers, "engine_set_moe_layer: layer out of range");
-    TL_REQUIRE(e->graphs.empty() && e->stats.decode_steps == 0 && e->stats.prefill_tokens == 0,
+    TL_REQUIRE(e->plans.empty() && e->stats.decode_steps == 0 && e->stats.prefill_tokens == 0,
                "engine_set_moe_layer: call it before the first prefill / decode");
     TL_REQUIRE(w->num_experts > 0 && w->num_experts <= 1024 && w->experts_per_token > 0 && w->experts_per_token <= 16 &&
                    w->experts_per_token <= w->num_experts,
@@ -1909,11 +1872,10 @@ extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_wei
         const size_t o_log = carve(R * E * 2), o_ids = carve(R * k * 4), o_sc = carve(R * k * 2), o_g = carve(R * k * I * 2),
                      o_u = carve(R * k * I * 2), o_a = carve(R * k * I * 2), o_y = carve(R * k * c.hidden_size * 2);
         TL_HIP(hipStreamSynchronize(e->stream));
-        if (e->moe_ws) (void)hipFree(e->moe_ws);
-        e->moe_ws = nullptr;
-        TL_HIP(hipMalloc((void **)&e->moe_ws, carve.off));
+        // (the text TL_HIP gave the hipMalloc that stood here)
+        TL_TRY(e->moe_ws.alloc(carve.off, "hipMalloc((void **)&e->moe_ws, carve.off): " + std::string(hipGetErrorString(hipErrorOutOfMemory))));
         e->moe_ws_bytes = carve.off;
-        char *A = e->moe_ws;
+        char *A = e->moe_ws.at();
         e->moe_logits = (uint16_t *)(A + o_log);
         e->moe_ids = (int32_t *)(A + o_ids);
         e->moe_scores = (uint16_t *)(A + o_sc);
@@ -1929,8 +1891,7 @@ extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_wei
     // hipGraph route): give the 17 MB per layer back (nothing captured holds them yet -- checked above)
     if (e->layer_act_mem) {
         TL_HIP(hipStreamSynchronize(e->stream));
-        (void)hipFree(e->layer_act_mem);
-        e->layer_act_mem = nullptr;
+        e->layer_act_mem.reset();
         e->layer_act.clear();
         e->layer_act_rows = 0, e->layer_act_bytes = 0, e->layer_ws_bytes = 0;
         e->layer_plane_bytes[0] = e->layer_plane_bytes[1] = 0;
@@ -1941,7 +1902,7 @@ extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_wei
 // Test / lab hook (header): routes that have an A/B twin, switched per engine before its first step.
 extern "C" int tl_engine_set_option(tl_engine *e, const char *name, int value) {
     TL_REQUIRE(e && name, "engine_set_option: null argument");
-    TL_REQUIRE(e->graphs.empty() && e->stats.decode_steps == 0 && e->stats.prefill_tokens == 0,
+    TL_REQUIRE(e->plans.empty() && e->stats.decode_steps == 0 && e->stats.prefill_tokens == 0,
                "engine_set_option: call it before the first prefill / decode (captured steps hold the routes they were captured with)");
     const std::string n = name;
     const bool on = value != 0;
@@ -1958,48 +1919,18 @@ extern "C" int tl_engine_set_option(tl_engine *e, const char *name, int value) {
     return TL_OK;
 }
 
+// the captured plans, all of them: their executable graphs are destroyed, their programs go with the records
+static void drop_plans(tl_engine *e) {
+    for (auto &kv : e->plans) (void)hipGraphExecDestroy(kv.second.exec);
+    e->plans.clear();
+}
+
 extern "C" void tl_engine_destroy(tl_engine *e) {
     if (!e) return;
     (void)aql_drain(e);
     (void)hipStreamSynchronize(e->stream);
-    e->aql_programs.clear();
-    e->aql_queue.reset();
-    if (e->layer_act_mem) (void)hipFree(e->layer_act_mem);
-    if (e->moe_ws) (void)hipFree(e->moe_ws);
-    for (auto &kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
-    if (e->arena) (void)hipFree(e->arena);
-    if (e->smp_mem) (void)hipFree(e->smp_mem);
-    if (e->lp_mem) (void)hipFree(e->lp_mem);
-    if (e->pen_mem) (void)hipFree(e->pen_mem);
-    if (e->trn_mem) (void)hipFree(e->trn_mem);
-    if (e->gr_mem) (void)hipFree(e->gr_mem);
-    if (e->gr_stack) (void)hipFree(e->gr_stack);
-    if (e->kv_pools_dev) (void)hipFree(e->kv_pools_dev);
-    if (e->swap_host) (void)hipHostFree(e->swap_host);
-    if (e->swap_staging) (void)hipFree(e->swap_staging);
-    if (e->swap_offsets_dev) (void)hipFree(e->swap_offsets_dev);
-    if (e->score_logits) (void)hipFree(e->score_logits);
-    if (e->spec_rec) (void)hipFree(e->spec_rec);
-    if (e->emb_out) (void)hipFree(e->emb_out);
-    if (e->emb_sums) (void)hipFree(e->emb_sums);
-    for (auto &r : e->lora_ad)
-        if (r.mem) (void)hipFree(r.mem);
-    if (e->lora_mem) (void)hipFree(e->lora_mem);
-    if (e->stop_mem) (void)hipFree(e->stop_mem);
-    if (e->kpool) (void)hipFree(e->kpool);
-    if (e->vpool) (void)hipFree(e->vpool);
-    if (e->kscale_pool) (void)hipFree(e->kscale_pool);
-    if (e->vscale_pool) (void)hipFree(e->vscale_pool);
-    if (e->lin.splitk_ws) (void)hipFree(e->lin.splitk_ws);
-    if (e->rope_table) (void)hipFree(e->rope_table);
-    if (e->rope_cur) (void)hipFree(e->rope_cur);
-    for (auto &kv : e->lin.tiled) {
-        (void)hipFree(kv.second.wt);
-        (void)hipFree(kv.second.sbt);
-    }
-    for (auto &kv : e->lin.bf16w) (void)hipFree(kv.second);
-    if (e->owns_stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    drop_plans(e);
+    delete e;  // the queue, every DeviceBlock, then the stream the engine created (tl_engine's member order)
 }
 
 extern "C" int tl_engine_kv_format(const tl_engine *e) { return e ? e->kv_format : TL_KV_BF16; }
@@ -2008,11 +1939,9 @@ extern "C" const char *tl_engine_replay_route(const tl_engine *e) {
     static thread_local std::string text;
     if (!e) return "";
     text = e->aql_on ? std::string("aql") : ("hipgraph" + (e->aql_why.empty() ? std::string() : ": " + e->aql_why));
-    // (a plan with a Mirostat slot keeps hipGraphLaunch on an engine whose other plans ride the route)
-    const StepFeatures f = step_features(e, 0, e->cfg.max_batch);
-    if (e->aql_on && f.mirostat) text = "hipgraph: a Mirostat slot is live (the update launch reads the token the step end stored)";
-    if (e->aql_on && f.lora) text = "hipgraph: a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)";
-    if (e->aql_on && f.stop) text = "hipgraph: a slot is armed with stop conditions (the stop launch reads the token the step end stored and writes the live word)";
+    // (a plan of the live slots that keeps hipGraphLaunch on an engine whose other plans ride the route)
+    const char *why = e->aql_on ? graph_only_reason(step_features(e, 0, e->cfg.max_batch)) : nullptr;
+    if (why) text = std::string("hipgraph: ") + why;
     return text.c_str();
 }
 
@@ -2101,14 +2030,11 @@ static int ensure_pool_table(tl_engine *e) {
             pools.push_back({e->layer_vs(l), sizeof(float)});
         }
     }
-    if (hipMalloc((void **)&e->kv_pools_dev, pools.size() * sizeof(tl_kv_pool_desc)) != hipSuccess)
-        return fail(TL_ERR_HIP, "engine: hipMalloc(pool table) failed");
-    const hipError_t rc = hipMemcpy(e->kv_pools_dev, pools.data(), pools.size() * sizeof(tl_kv_pool_desc), hipMemcpyHostToDevice);
-    if (rc != hipSuccess) {
-        (void)hipFree(e->kv_pools_dev);
-        e->kv_pools_dev = nullptr;
-        return fail(TL_ERR_HIP, std::string("engine: hipMemcpy(pool table): ") + hipGetErrorString(rc));
-    }
+    TL_TRY(alloc_filled(e->kv_pools_mem, pools.size() * sizeof(tl_kv_pool_desc), "engine: hipMalloc(pool table) failed", [&](char *m) -> int {
+        const hipError_t rc = hipMemcpy(m, pools.data(), pools.size() * sizeof(tl_kv_pool_desc), hipMemcpyHostToDevice);
+        return rc == hipSuccess ? TL_OK : fail(TL_ERR_HIP, std::string("engine: hipMemcpy(pool table): ") + hipGetErrorString(rc));
+    }));
+    e->kv_pools_dev = e->kv_pools_mem.at<tl_kv_pool_desc>();
     e->kv_pools_n = (int)pools.size();
     e->kv_pools_host = std::move(pools);
     return TL_OK;
@@ -2206,10 +2132,9 @@ extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
 static int swap_free(tl_engine *e) {
     if (!e->swap_host && !e->swap_staging) return TL_OK;
     TL_HIP(hipStreamSynchronize(e->stream));  // copies into / out of the arena may be in flight
-    if (e->swap_host) (void)hipHostFree(e->swap_host);
-    if (e->swap_staging) (void)hipFree(e->swap_staging);
+    e->swap_host.reset();
+    e->swap_staging.reset();
     e->stats.workspace_bytes -= (size_t)e->swap_staging_pages * e->swap_record_bytes;
-    e->swap_host = e->swap_staging = nullptr;
     e->swap_staging_pages = 0;
     e->table.arena.init(0);
     return TL_OK;
@@ -2231,26 +2156,18 @@ extern "C" int tl_engine_swap_space(tl_engine *e, int host_pages) {
             offsets[i] = at;
             at += (size_t)c.num_kv_heads * c.page_size * e->kv_pools_host[i].row_bytes;
         }
-        if (hipMalloc((void **)&e->swap_offsets_dev, offsets.size() * sizeof(size_t)) != hipSuccess)
-            return fail(TL_ERR_HIP, "engine_swap_space: hipMalloc(record offsets) failed");
-        const hipError_t rc = hipMemcpy(e->swap_offsets_dev, offsets.data(), offsets.size() * sizeof(size_t), hipMemcpyHostToDevice);
-        if (rc != hipSuccess) {
-            (void)hipFree(e->swap_offsets_dev);
-            e->swap_offsets_dev = nullptr;
-            return fail(TL_ERR_HIP, std::string("engine_swap_space: hipMemcpy(record offsets): ") + hipGetErrorString(rc));
-        }
+        TL_TRY(alloc_filled(e->swap_offsets_mem, offsets.size() * sizeof(size_t), "engine_swap_space: hipMalloc(record offsets) failed", [&](char *m) -> int {
+            const hipError_t rc = hipMemcpy(m, offsets.data(), offsets.size() * sizeof(size_t), hipMemcpyHostToDevice);
+            return rc == hipSuccess ? TL_OK : fail(TL_ERR_HIP, std::string("engine_swap_space: hipMemcpy(record offsets): ") + hipGetErrorString(rc));
+        }));
+        e->swap_offsets_dev = e->swap_offsets_mem.at<size_t>();
     }
     // the staging buffer: up to 32 MiB of records (a group of pages per gather + copy), at least one, never more than the arena holds
     const int staging_pages = (int)std::min<size_t>((size_t)host_pages, std::max<size_t>(1, ((size_t)32 << 20) / rec));
-    if (hipHostMalloc((void **)&e->swap_host, (size_t)host_pages * rec, hipHostMallocDefault) != hipSuccess) {
-        e->swap_host = nullptr;
-        return fail(TL_ERR_HIP, "engine_swap_space: hipHostMalloc(host arena) failed");
-    }
-    if (hipMalloc((void **)&e->swap_staging, (size_t)staging_pages * rec) != hipSuccess) {
-        (void)hipHostFree(e->swap_host);
-        e->swap_host = e->swap_staging = nullptr;
-        return fail(TL_ERR_HIP, "engine_swap_space: hipMalloc(staging) failed");
-    }
+    DeviceBlock host, staging;  // both, or the engine keeps neither
+    TL_TRY(host.alloc_pinned((size_t)host_pages * rec, "engine_swap_space: hipHostMalloc(host arena) failed"));
+    TL_TRY(staging.alloc((size_t)staging_pages * rec, "engine_swap_space: hipMalloc(staging) failed"));
+    e->swap_host = std::move(host), e->swap_staging = std::move(staging);
     e->swap_record_bytes = rec;
     e->swap_staging_pages = staging_pages;
     e->table.arena.init(host_pages);
@@ -2275,10 +2192,10 @@ extern "C" int tl_engine_park(tl_engine *e, int slot) {
         const int j1 = std::min(n, j0 + e->swap_staging_pages);
         const int tail = j1 == n ? ctx - (n - 1) * c.page_size : c.page_size;
         rc = kv_swap_pages<true>(e->kv_pools_dev, e->swap_offsets_dev, e->kv_pools_n, c.num_kv_heads, c.page_size, row + j0, j1 - j0, tail,
-                                 e->swap_staging, rec, e->stream);
+                                 e->swap_staging.at(), rec, e->stream);
         for (const auto &run : swap_runs(records, j0, j1)) {  // one copy per group while the arena hands out consecutive records
             if (rc != TL_OK) break;
-            if (hipMemcpyAsync(e->swap_host + (size_t)records[run.first] * rec, e->swap_staging + (size_t)(run.first - j0) * rec,
+            if (hipMemcpyAsync(e->swap_host.at((size_t)records[run.first] * rec), e->swap_staging.at((size_t)(run.first - j0) * rec),
                                (size_t)run.second * rec, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
                 rc = fail(TL_ERR_HIP, "engine_park: hipMemcpyAsync(device to host) failed");
         }
@@ -2319,10 +2236,10 @@ extern "C" int tl_engine_unpark(tl_engine *e, int slot) {
         const int j1 = std::min(n, j0 + e->swap_staging_pages);
         const int tail = j1 == n ? ctx - (n - 1) * c.page_size : c.page_size;
         for (const auto &run : swap_runs(records, j0, j1))
-            TL_HIP(hipMemcpyAsync(e->swap_staging + (size_t)(run.first - j0) * rec, e->swap_host + (size_t)records[run.first] * rec,
+            TL_HIP(hipMemcpyAsync(e->swap_staging.at((size_t)(run.first - j0) * rec), e->swap_host.at((size_t)records[run.first] * rec),
                                   (size_t)run.second * rec, hipMemcpyHostToDevice, e->stream));
         TL_TRY(kv_swap_pages<false>(e->kv_pools_dev, e->swap_offsets_dev, e->kv_pools_n, c.num_kv_heads, c.page_size, row + j0, j1 - j0, tail,
-                                    e->swap_staging, rec, e->stream));
+                                    e->swap_staging.at(), rec, e->stream));
     }
     pk.emplace_back(e->context_lens + slot, ctx);
     pk.emplace_back(e->live + slot, e->table.slots[slot].stopped ? 0 : 1);  // (an unparked stopped slot stays stopped)
@@ -2513,26 +2430,21 @@ extern "C" int tl_vocab_create(int vocab, const int32_t *offsets, const uint8_t 
         }
     const size_t o_bytes = align_up((size_t)(vocab + 1) * 4, 256), o_index = o_bytes + align_up(nb + 16, 256),
                  o_ids = o_index + align_up((size_t)vocab * 4, 256), total = o_ids + align_up(v->long_ids.size() * 4 + 4, 256);
-    if (hipMalloc((void **)&v->mem, total) != hipSuccess) return fail(TL_ERR_HIP, "vocab_create: hipMalloc failed");
-    v->offsets_dev = (int32_t *)v->mem, v->bytes_dev = (uint8_t *)(v->mem + o_bytes);
-    v->long_index_dev = (int32_t *)(v->mem + o_index), v->long_ids_dev = (int32_t *)(v->mem + o_ids);
+    TL_TRY(v->mem.alloc(total, "vocab_create: hipMalloc failed"));
+    v->offsets_dev = v->mem.at<int32_t>(), v->bytes_dev = v->mem.at<uint8_t>(o_bytes);
+    v->long_index_dev = v->mem.at<int32_t>(o_index), v->long_ids_dev = v->mem.at<int32_t>(o_ids);
     hipError_t he = hipMemcpyAsync(v->offsets_dev, v->offsets.data(), (size_t)(vocab + 1) * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
     if (he == hipSuccess && nb) he = hipMemcpyAsync(v->bytes_dev, v->bytes.data(), nb, hipMemcpyHostToDevice, (hipStream_t)stream);
     if (he == hipSuccess) he = hipMemcpyAsync(v->long_index_dev, long_index.data(), (size_t)vocab * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
     if (he == hipSuccess && !v->long_ids.empty())
         he = hipMemcpyAsync(v->long_ids_dev, v->long_ids.data(), v->long_ids.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
     if (he == hipSuccess) he = hipStreamSynchronize((hipStream_t)stream);
-    if (he != hipSuccess) {
-        (void)hipFree(v->mem);
-        return fail(TL_ERR_HIP, std::string("vocab_create: ") + hipGetErrorString(he));
-    }
+    if (he != hipSuccess) return fail(TL_ERR_HIP, std::string("vocab_create: ") + hipGetErrorString(he));
     *out = v.release();
     return TL_OK;
 }
 
 extern "C" void tl_vocab_destroy(tl_vocab *v) {
-    if (!v) return;
-    if (v->mem) (void)hipFree(v->mem);
     delete v;
 }
 
@@ -2559,27 +2471,25 @@ extern "C" int tl_grammar_create(const tl_vocab *v, int n_states, const uint16_t
     const int n_long = (int)v->long_ids.size(), long_words = 2 * ceil_div(n_long, 64);
     const size_t o_table = 256, o_acc = o_table + align_up(cells * 2, 256), o_long = o_acc + align_up((size_t)n_states, 256),
                  total = o_long + align_up((size_t)n_states * long_words * 4 + 4, 256);
-    if (hipMalloc((void **)&g->mem, total) != hipSuccess) return fail(TL_ERR_HIP, "grammar_create: hipMalloc failed");
+    TL_TRY(g->mem.alloc(total, "grammar_create: hipMalloc failed"));
+    char *const mem = g->mem.at();
     GrammarDev d{};
-    d.table = (const uint16_t *)(g->mem + o_table), d.accepting = (const uint8_t *)(g->mem + o_acc);
+    d.table = (const uint16_t *)(mem + o_table), d.accepting = (const uint8_t *)(mem + o_acc);
     d.offsets = v->offsets_dev, d.bytes = v->bytes_dev, d.n_states = n_states, d.n_eos = n_eos;
-    d.long_index = v->long_index_dev, d.long_bits = (const uint32_t *)(g->mem + o_long), d.long_words = long_words;
+    d.long_index = v->long_index_dev, d.long_bits = (const uint32_t *)(mem + o_long), d.long_words = long_words;
     for (int i = 0; i < GR_MAX_EOS; ++i) d.eos[i] = i < n_eos ? eos_ids[i] : -1;
     static_assert(sizeof(GrammarDev) <= 256, "GrammarDev heads the grammar's allocation");
-    hipError_t he = hipMemcpyAsync(g->mem, &d, sizeof(d), hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(g->mem + o_table, g->table.data(), cells * 2, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(g->mem + o_acc, g->accepting.data(), (size_t)n_states, hipMemcpyHostToDevice, (hipStream_t)stream);
+    hipError_t he = hipMemcpyAsync(mem, &d, sizeof(d), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(mem + o_table, g->table.data(), cells * 2, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(mem + o_acc, g->accepting.data(), (size_t)n_states, hipMemcpyHostToDevice, (hipStream_t)stream);
     if (he == hipSuccess && n_long > 0) {  // the walks of the long tokens from every state, once, on the device
-        const GrammarLongArgs la{d.table, d.offsets, d.bytes, v->long_ids_dev, n_long, long_words, (uint32_t *)(g->mem + o_long)};
+        const GrammarLongArgs la{d.table, d.offsets, d.bytes, v->long_ids_dev, n_long, long_words, (uint32_t *)(mem + o_long)};
         hipLaunchKernelGGL(grammar_long_bits_kernel, dim3(long_words / 2, n_states), dim3(64), 0, (hipStream_t)stream, la);
         he = hipGetLastError();
     }
     if (he == hipSuccess) he = hipStreamSynchronize((hipStream_t)stream);
-    if (he != hipSuccess) {
-        (void)hipFree(g->mem);
-        return fail(TL_ERR_HIP, std::string("grammar_create: ") + hipGetErrorString(he));
-    }
-    g->dev = (GrammarDev *)g->mem;
+    if (he != hipSuccess) return fail(TL_ERR_HIP, std::string("grammar_create: ") + hipGetErrorString(he));
+    g->dev = (GrammarDev *)mem;
     *out = g.release();
     return TL_OK;
 }
@@ -2622,35 +2532,31 @@ extern "C" int tl_grammar_create_stack(const tl_vocab *v, int n_states, const ui
     const int n_long = (int)v->long_ids.size();
     const size_t o_fused = 256, o_pop = o_fused + align_up(cells * 4, 256), o_acc = o_pop + align_up(pop8.size() * 2, 256),
                  o_long = o_acc + align_up((size_t)n_states, 256), total = o_long + align_up((size_t)n_states * n_long + 4, 256);
-    if (hipMalloc((void **)&g->mem, total) != hipSuccess) return fail(TL_ERR_HIP, "grammar_create_stack: hipMalloc failed");
+    TL_TRY(g->mem.alloc(total, "grammar_create_stack: hipMalloc failed"));
+    char *const mem = g->mem.at();
     GrammarDev d{};
-    d.accepting = (const uint8_t *)(g->mem + o_acc);
+    d.accepting = (const uint8_t *)(mem + o_acc);
     d.offsets = v->offsets_dev, d.bytes = v->bytes_dev, d.n_states = n_states, d.n_eos = n_eos, d.long_index = v->long_index_dev;
     d.kind = 1, d.n_pop = n_pop, d.n_long = n_long;
-    d.fused = (const uint32_t *)(g->mem + o_fused), d.pop = (const uint16_t *)(g->mem + o_pop), d.long_m = (const uint8_t *)(g->mem + o_long);
+    d.fused = (const uint32_t *)(mem + o_fused), d.pop = (const uint16_t *)(mem + o_pop), d.long_m = (const uint8_t *)(mem + o_long);
     for (int i = 0; i < GR_MAX_EOS; ++i) d.eos[i] = i < n_eos ? eos_ids[i] : -1;
-    hipError_t he = hipMemcpyAsync(g->mem, &d, sizeof(d), hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(g->mem + o_fused, fused.data(), cells * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(g->mem + o_pop, pop8.data(), pop8.size() * 2, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(g->mem + o_acc, g->accepting.data(), (size_t)n_states, hipMemcpyHostToDevice, (hipStream_t)stream);
+    hipError_t he = hipMemcpyAsync(mem, &d, sizeof(d), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(mem + o_fused, fused.data(), cells * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(mem + o_pop, pop8.data(), pop8.size() * 2, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(mem + o_acc, g->accepting.data(), (size_t)n_states, hipMemcpyHostToDevice, (hipStream_t)stream);
     if (he == hipSuccess && n_long > 0) {  // the walks of the long tokens from every state with an empty stack, once, on the device
-        const GrammarLongDepthArgs la{d.fused, d.pop, d.offsets, d.bytes, v->long_ids_dev, n_long, (uint8_t *)(g->mem + o_long)};
+        const GrammarLongDepthArgs la{d.fused, d.pop, d.offsets, d.bytes, v->long_ids_dev, n_long, (uint8_t *)(mem + o_long)};
         hipLaunchKernelGGL(grammar_long_depth_kernel, dim3(ceil_div(n_long, 64), n_states), dim3(64), 0, (hipStream_t)stream, la);
         he = hipGetLastError();
     }
     if (he == hipSuccess) he = hipStreamSynchronize((hipStream_t)stream);  // (the pageable host copies above are locals)
-    if (he != hipSuccess) {
-        (void)hipFree(g->mem);
-        return fail(TL_ERR_HIP, std::string("grammar_create_stack: ") + hipGetErrorString(he));
-    }
-    g->dev = (GrammarDev *)g->mem;
+    if (he != hipSuccess) return fail(TL_ERR_HIP, std::string("grammar_create_stack: ") + hipGetErrorString(he));
+    g->dev = (GrammarDev *)mem;
     *out = g.release();
     return TL_OK;
 }
 
 extern "C" void tl_grammar_destroy(tl_grammar *g) {
-    if (!g) return;
-    if (g->mem) (void)hipFree(g->mem);
     delete g;
 }
 
@@ -2729,33 +2635,29 @@ extern "C" int tl_stop_create(const tl_vocab *v, const int32_t *ids, int n_ids, 
     Carve carve;
     const size_t o_dev = carve(sizeof(StopDev)), o_ids = carve(h.ids.size() * 4 + 4), o_table = carve(h.table.size() * 2 + 2),
                  o_match = carve(h.match.size() * 2 + 2), o_len = carve(h.match_len.size() * 2 + 2);
-    if (hipMalloc((void **)&s->mem, carve.off) != hipSuccess) return fail(TL_ERR_HIP, "stop_create: hipMalloc failed");
+    TL_TRY(s->mem.alloc(carve.off, "stop_create: hipMalloc failed"));
+    char *const mem = s->mem.at();
     StopDev d{};
-    d.ids = (const int32_t *)(s->mem + o_ids);
+    d.ids = (const int32_t *)(mem + o_ids);
     d.n_ids = (int)h.ids.size(), d.max_len = h.max_len, d.n_states = h.n_states;
     if (h.n_strings) {
-        d.table = (const uint16_t *)(s->mem + o_table), d.match = (const int16_t *)(s->mem + o_match), d.match_len = (const uint16_t *)(s->mem + o_len);
+        d.table = (const uint16_t *)(mem + o_table), d.match = (const int16_t *)(mem + o_match), d.match_len = (const uint16_t *)(mem + o_len);
     }
     if (v) d.offsets = v->offsets_dev, d.bytes = v->bytes_dev, d.vocab = v->vocab;
     const hipStream_t st = (hipStream_t)stream;
-    hipError_t he = hipMemcpyAsync(s->mem + o_dev, &d, sizeof(d), hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && !h.ids.empty()) he = hipMemcpyAsync(s->mem + o_ids, h.ids.data(), h.ids.size() * 4, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && h.n_strings) he = hipMemcpyAsync(s->mem + o_table, h.table.data(), h.table.size() * 2, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && h.n_strings) he = hipMemcpyAsync(s->mem + o_match, h.match.data(), h.match.size() * 2, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && h.n_strings) he = hipMemcpyAsync(s->mem + o_len, h.match_len.data(), h.match_len.size() * 2, hipMemcpyHostToDevice, st);
+    hipError_t he = hipMemcpyAsync(mem + o_dev, &d, sizeof(d), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && !h.ids.empty()) he = hipMemcpyAsync(mem + o_ids, h.ids.data(), h.ids.size() * 4, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && h.n_strings) he = hipMemcpyAsync(mem + o_table, h.table.data(), h.table.size() * 2, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && h.n_strings) he = hipMemcpyAsync(mem + o_match, h.match.data(), h.match.size() * 2, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && h.n_strings) he = hipMemcpyAsync(mem + o_len, h.match_len.data(), h.match_len.size() * 2, hipMemcpyHostToDevice, st);
     if (he == hipSuccess) he = hipStreamSynchronize(st);  // (the copies read this frame's `d`)
-    if (he != hipSuccess) {
-        (void)hipFree(s->mem);
-        return fail(TL_ERR_HIP, std::string("stop_create: ") + hipGetErrorString(he));
-    }
-    s->dev = (StopDev *)(s->mem + o_dev);
+    if (he != hipSuccess) return fail(TL_ERR_HIP, std::string("stop_create: ") + hipGetErrorString(he));
+    s->dev = (StopDev *)(mem + o_dev);
     *out = s.release();
     return TL_OK;
 }
 
 extern "C" void tl_stop_destroy(tl_stop *s) {
-    if (!s) return;
-    if (s->mem) (void)hipFree(s->mem);
     delete s;
 }
 
@@ -2966,11 +2868,11 @@ extern "C" int tl_engine_lora_load(tl_engine *e, const tl_lora_layer *layers, in
             b_off[(size_t)l * G + g] = bytes;
             bytes = align_up(bytes + (size_t)out * rank * 2, 256);
         }
-    char *mem = nullptr;
-    if (hipMalloc((void **)&mem, bytes) != hipSuccess) return fail(TL_ERR_HIP, "engine_lora_load: hipMalloc(adapter) failed");
-    auto undo = [&](const std::string &msg) {
+    DeviceBlock block;  // the engine's once the table names it; a failure before that waits for the copies enqueued so far and releases it
+    TL_TRY(block.alloc(bytes, "engine_lora_load: hipMalloc(adapter) failed"));
+    char *const mem = block.at();
+    const auto undo = [&](const std::string &msg) {
         (void)hipStreamSynchronize(e->stream);
-        (void)hipFree(mem);
         return fail(TL_ERR_HIP, "engine_lora_load: " + msg);
     };
     if (hipMemsetAsync(mem, 0, bytes, e->stream) != hipSuccess) return undo("memset failed");
@@ -2999,7 +2901,7 @@ extern "C" int tl_engine_lora_load(tl_engine *e, const tl_lora_layer *layers, in
     if (hipMemcpy(e->lora_table + (size_t)id * descs.size(), descs.data(), descs.size() * sizeof(LoraDesc), hipMemcpyHostToDevice) != hipSuccess)
         return undo("hipMemcpy(table) failed");
     tl_engine::LoraResident &r = e->lora_ad[id];
-    r.mem = mem, r.bytes = bytes, r.rank = rank;
+    r.mem = std::move(block), r.bytes = bytes, r.rank = rank;
     r.has.assign(descs.size(), 0);
     for (size_t i = 0; i < descs.size(); ++i) r.has[i] = descs[i].rank > 0;
     *adapter = id;
@@ -3016,7 +2918,6 @@ extern "C" int tl_engine_lora_unload(tl_engine *e, int adapter) {
     const size_t n = (size_t)e->cfg.num_layers * tl_engine::LORA_GROUPS;
     TL_HIP(hipMemset(e->lora_table + (size_t)adapter * n, 0, n * sizeof(LoraDesc)));
     TL_HIP(hipDeviceSynchronize());
-    (void)hipFree(e->lora_ad[adapter].mem);
     e->lora_ad[adapter] = tl_engine::LoraResident{};
     return TL_OK;
 }
@@ -3085,8 +2986,9 @@ extern "C" int tl_lora_rows(const void *x_dev, int rows, int in, int out, const 
     Carve carve;
     const size_t o_table = carve(descs.size() * sizeof(LoraDesc)), o_tiles = carve(tiles.size() * sizeof(LoraTile));
     const size_t o_part = carve(lora_partial_floats(nt, std::max(in, 1)) * 4), o_ss = carve(lora_ss_floats(nt, std::max(in, 1)) * 4);
-    char *mem = nullptr;
-    if (hipMalloc((void **)&mem, carve.off) != hipSuccess) return fail(TL_ERR_HIP, "lora_rows: hipMalloc(workspace) failed");
+    DeviceBlock ws;  // (released behind the synchronisation below)
+    TL_TRY(ws.alloc(carve.off, "lora_rows: hipMalloc(workspace) failed"));
+    char *const mem = ws.at();
     int rc = TL_OK;
     if (hipMemcpy(mem + o_table, descs.data(), descs.size() * sizeof(LoraDesc), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(mem + o_tiles, tiles.data(), tiles.size() * sizeof(LoraTile), hipMemcpyHostToDevice) != hipSuccess)
@@ -3101,7 +3003,6 @@ extern "C" int tl_lora_rows(const void *x_dev, int rows, int in, int out, const 
         rc = lora_apply(c, (hipStream_t)stream);
     }
     const hipError_t se = hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(mem);
     if (rc == TL_OK && se != hipSuccess) rc = fail(TL_ERR_HIP, std::string("lora_rows: ") + hipGetErrorString(se));
     return rc;
 }
@@ -3412,8 +3313,9 @@ extern "C" int tl_engine_score(tl_engine *e, int slot, const int32_t *tokens, in
     TL_TRY(slot_check_feeds(e, slot));
     if (!e->score_logits) {
         const size_t R = (size_t)e->cfg.max_prefill_rows, logit_bytes = align_up((size_t)SCORE_BLOCK_ROWS * e->cfg.vocab_size * 2, 256);
-        if (hipMalloc((void **)&e->score_logits, logit_bytes + R * 12) != hipSuccess) return fail(TL_ERR_HIP, "engine_score: hipMalloc(scratch) failed");
-        e->score_ids = (int32_t *)((char *)e->score_logits + logit_bytes);
+        TL_TRY(e->score_mem.alloc(logit_bytes + R * 12, "engine_score: hipMalloc(scratch) failed"));
+        e->score_logits = e->score_mem.at<uint16_t>();
+        e->score_ids = e->score_mem.at<int32_t>(logit_bytes);
         e->score_lp = (float *)(e->score_ids + R);
         e->score_argmax = e->score_ids + 2 * R;
     }
@@ -3447,12 +3349,14 @@ static int embed_alloc(tl_engine *e, bool mean) {
     const size_t H = (size_t)e->cfg.hidden_size;
     if (!e->emb_out) {
         const size_t bytes = POOL_MAX_SEQS * H * sizeof(float);
-        if (hipMalloc((void **)&e->emb_out, bytes) != hipSuccess) return fail(TL_ERR_HIP, "engine_embed: hipMalloc(vectors) failed");
+        TL_TRY(e->emb_out_mem.alloc(bytes, "engine_embed: hipMalloc(vectors) failed"));
+        e->emb_out = e->emb_out_mem.at<float>();
         e->stats.workspace_bytes += bytes;
     }
     if (mean && !e->emb_sums) {
         const size_t bytes = (size_t)e->cfg.max_batch * H * sizeof(float);
-        if (hipMalloc((void **)&e->emb_sums, bytes) != hipSuccess) return fail(TL_ERR_HIP, "engine_embed: hipMalloc(running sums) failed");
+        TL_TRY(e->emb_sums_mem.alloc(bytes, "engine_embed: hipMalloc(running sums) failed"));
+        e->emb_sums = e->emb_sums_mem.at<float>();
         e->stats.workspace_bytes += bytes;
     }
     return TL_OK;
@@ -3541,7 +3445,8 @@ extern "C" int tl_engine_verify_sampled(tl_engine *e, int slot, const int32_t *t
     TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_verify_sampled: vocabulary larger than the sampler's 524,288 tokens");
     using Rec = tl_engine::SpecRecord;
     if (!e->spec_rec) {
-        if (hipMalloc((void **)&e->spec_rec, sizeof(Rec)) != hipSuccess) return fail(TL_ERR_HIP, "engine_verify_sampled: hipMalloc failed");
+        TL_TRY(e->spec_mem.alloc(sizeof(Rec), "engine_verify_sampled: hipMalloc failed"));
+        e->spec_rec = e->spec_mem.at<Rec>();
         e->stats.workspace_bytes += sizeof(Rec);
     }
     const int ctx = e->table.slots[slot].ctx;
@@ -3651,8 +3556,8 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
         TL_TRY(prepare_step(e, batch, &sp, &on_queue));
         if (use_graph && e->warmed) {
             const auto key = std::make_pair(batch, sp.key() | f.key_bits());
-            auto it = e->graphs.find(key);
-            if (it == e->graphs.end()) {
+            auto it = e->plans.find(key);
+            if (it == e->plans.end()) {
                 // The split plan (and with it the key) changes every 64 * n_splits tokens of context: a long run would keep one
                 // ~220-node executable graph per plan and row bucket for ever.  Plans are visited in order of growing context, so
                 // when the cache is full the old ones are dead: drop them all (a live plan is re-captured once, ~0.3 ms).
@@ -3660,11 +3565,9 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
                     TL_TRY(aql_drain(e));
                     on_queue = false;
                 }
-                if (e->graphs.size() >= 48) {
+                if (e->plans.size() >= 48) {
                     TL_HIP(hipStreamSynchronize(e->stream));
-                    for (auto &kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
-                    e->graphs.clear();
-                    e->aql_programs.clear();
+                    drop_plans(e);
                     e->stats.graph_cache_flushes++;
                 }
                 hipGraph_t graph = nullptr;
@@ -3676,32 +3579,28 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
                     return rc;
                 }
                 if (ce != hipSuccess) return fail(TL_ERR_HIP, std::string("engine_decode: graph capture failed: ") + hipGetErrorString(ce));
-                hipGraphExec_t exec = nullptr;
-                const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-                if (ie == hipSuccess && e->aql_on && !e->step_written_once)
-                    e->aql_why = f.lora ? "a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)"
-                                      : "a hand-over of this plan lives in a shared buffer (written more than once per step)";
-                if (ie == hipSuccess && e->aql_on && e->step_written_once && f.mirostat) e->aql_why = "a Mirostat slot is live (the update launch reads the token the step end stored)";
-                if (ie == hipSuccess && e->aql_on && e->step_written_once && f.stop)
-                    e->aql_why = "a slot is armed with stop conditions (the stop launch reads the token the step end stored and writes the live word)";
-                if (ie == hipSuccess && e->aql_on && e->step_written_once && !f.mirostat && !f.stop) {  // the same nodes as packet templates (aql.h); a plan that cannot be built keeps the graph route
+                tl_engine::DecodePlan plan;
+                const hipError_t ie = hipGraphInstantiate(&plan.exec, graph, nullptr, nullptr, 0);
+                // the same nodes as packet templates (aql.h) where every hand-over is written once per step and no launch needs a
+                // boundary with cache maintenance; a plan whose program cannot be built keeps the graph route
+                if (ie == hipSuccess && e->aql_on && e->step_written_once && !graph_only_reason(f)) {
                     auto prog = std::make_unique<AqlProgram>();
-                    if (aql_program_from_graph(*e->aql_rt, graph, e->stream, *prog, e->aql_why) == 0) e->aql_programs[key] = std::move(prog);
+                    std::string why;
+                    if (aql_program_from_graph(*e->aql_rt, graph, e->stream, *prog, why) == 0) plan.program = std::move(prog);
                 }
                 (void)hipGraphDestroy(graph);
                 if (ie != hipSuccess) return fail(TL_ERR_HIP, std::string("engine_decode: graph instantiate failed: ") + hipGetErrorString(ie));
-                it = e->graphs.emplace(key, exec).first;
+                it = e->plans.emplace(key, std::move(plan)).first;
                 e->stats.graph_captures++;
             }
-            const auto prog = e->aql_on ? e->aql_programs.find(key) : e->aql_programs.end();
-            if (prog != e->aql_programs.end()) {
+            if (it->second.program) {
                 bool first = false;
                 if (!on_queue) {  // hand-over stream -> queue: everything enqueued so far (embedding gather, pokes, earlier steps) has run
                     TL_HIP(hipStreamSynchronize(e->stream));
                     on_queue = first = true;
                 }
                 std::string why;
-                if (!e->aql_queue->submit(*prog->second, e->aql_fences, first, s + 1 == steps, why)) {
+                if (!e->aql_queue->submit(*it->second.program, e->aql_fences, first, s + 1 == steps, why)) {
                     (void)aql_drain(e);
                     return fail(TL_ERR_HIP, "engine_decode: " + why);
                 }
@@ -3711,7 +3610,7 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
                     TL_TRY(aql_drain(e));
                     on_queue = false;
                 }
-                TL_HIP(hipGraphLaunch(it->second, e->stream));
+                TL_HIP(hipGraphLaunch(it->second.exec, e->stream));
             }
             e->stats.graph_replays++;
         } else {
@@ -3845,48 +3744,46 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
     TL_TRY(aql_drain(e));
     TL_HIP(hipStreamSynchronize(e->stream));
     WrittenOnceCheck ck;
-    ck.region[0] = e->arena + e->arena_act_off, ck.bytes[0] = (e->arena_bytes - e->arena_act_off) / 4 * 4;
-    ck.region[1] = e->layer_act_mem, ck.bytes[1] = e->layer_act_mem ? e->layer_act_bytes / 4 * 4 : 0;
+    ck.region[0] = e->arena.at(e->arena_act_off), ck.bytes[0] = (e->arena_bytes - e->arena_act_off) / 4 * 4;
+    ck.region[1] = e->layer_act_mem.at(), ck.bytes[1] = e->layer_act_mem ? e->layer_act_bytes / 4 * 4 : 0;
+    // the checker's buffers live in this frame; every return below has waited for the stream before they go
+    struct StreamWait {
+        hipStream_t s;
+        ~StreamWait() { (void)hipStreamSynchronize(s); }
+    };
+    DeviceBlock shadow[2], written[2], report_mem;
     ProfCtx pc;
-    auto cleanup = [&]() {
-        for (int rg = 0; rg < 2; ++rg) {
-            if (ck.shadow[rg]) (void)hipFree(ck.shadow[rg]);
-            if (ck.written[rg]) (void)hipFree(ck.written[rg]);
-        }
-        if (ck.report) (void)hipFree(ck.report);
-    };
-    auto bail = [&](int code, const std::string &msg) {
-        (void)hipStreamSynchronize(e->stream);
-        cleanup();
-        return fail(code, msg);
-    };
-    bool ok = pc.alloc(e->cfg, batch, e->stream) && hipMalloc((void **)&ck.report, 8 * sizeof(unsigned long long)) == hipSuccess;
-    for (int rg = 0; rg < 2 && ok; ++rg)
-        if (ck.bytes[rg]) ok = hipMalloc((void **)&ck.shadow[rg], ck.bytes[rg]) == hipSuccess && hipMalloc((void **)&ck.written[rg], ck.bytes[rg] / 2) == hipSuccess;
-    if (!ok) return bail(TL_ERR_HIP, "engine_check_step: hipMalloc of the shadow buffers failed");
+    const StreamWait wait_first{e->stream};
+    const char *no_memory = "engine_check_step: hipMalloc of the shadow buffers failed";
+    if (!pc.alloc(e->cfg, batch, e->stream)) return fail(TL_ERR_HIP, no_memory);
+    TL_TRY(report_mem.alloc(8 * sizeof(unsigned long long), no_memory));
+    ck.report = report_mem.at<unsigned long long>();
+    for (int rg = 0; rg < 2; ++rg) {
+        if (!ck.bytes[rg]) continue;
+        TL_TRY(shadow[rg].alloc(ck.bytes[rg], no_memory));
+        TL_TRY(written[rg].alloc(ck.bytes[rg] / 2, no_memory));
+        ck.shadow[rg] = shadow[rg].at<uint32_t>(), ck.written[rg] = written[rg].at<uint8_t>();
+    }
+    bool ok = true;
     // the per-layer buffers start the step POISONED (every 16-bit and 32-bit pattern a NaN): a value read before this step wrote it
     // reaches the logits as NaN; the shared activations carry state between steps (x, its sums of squares) and keep their contents
     const unsigned long long report0[8] = {0, ~0ull, 0, 0, 0, 0, 0, 0};
     ok = hipMemcpyAsync(ck.report, report0, sizeof(report0), hipMemcpyHostToDevice, e->stream) == hipSuccess;
     if (ok && ck.bytes[1]) ok = hipMemsetAsync(ck.region[1], 0xff, ck.bytes[1], e->stream) == hipSuccess;
-    if (!ok) return bail(TL_ERR_HIP, "engine_check_step: initialisation failed");
+    if (!ok) return fail(TL_ERR_HIP, "engine_check_step: initialisation failed");
     launch_embed_slots(e, batch);
     // the shadows = the regions as the step finds them; nothing written yet
     for (int rg = 0; rg < 2 && ok; ++rg)
         if (ck.bytes[rg]) ok = hipMemcpyAsync(ck.shadow[rg], ck.region[rg], ck.bytes[rg], hipMemcpyDeviceToDevice, e->stream) == hipSuccess &&
                                hipMemsetAsync(ck.written[rg], 0, ck.bytes[rg] / 2, e->stream) == hipSuccess;
-    if (!ok) return bail(TL_ERR_HIP, "engine_check_step: shadow copy failed");
+    if (!ok) return fail(TL_ERR_HIP, "engine_check_step: shadow copy failed");
     SplitPlan sp;
     int rc = prepare_step(e, batch, &sp);
     if (rc == TL_OK) {
         pc.check = &ck;
         rc = enqueue_step(e, batch, sp, step_features(e, 0, batch), &pc);
     }
-    if (rc != TL_OK) {
-        (void)hipStreamSynchronize(e->stream);
-        cleanup();
-        return rc;
-    }
+    if (rc != TL_OK) return rc;
     e->warmed = true;
     step_done(e, batch);
     (void)stop_reconcile(e);
@@ -3894,7 +3791,6 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
     hipError_t he = hipStreamSynchronize(e->stream);
     if (he == hipSuccess) he = hipMemcpy(report, ck.report, sizeof(report), hipMemcpyDeviceToHost);
     const std::vector<int> &kinds = pc.kinds;
-    cleanup();
     if (he != hipSuccess) return fail(TL_ERR_HIP, std::string("engine_check_step: ") + hipGetErrorString(he));
     out->launches = (int)kinds.size();
     out->written_once_plan = e->step_written_once ? 1 : 0;
