@@ -80,9 +80,14 @@ def eos_ids(V):
     return [V - 1, V - 2]
 
 
-def bracket_automaton():
+POP_ROWS = [5, 40, 66, 69]  # "brackets-pops": the pop entry of each closer, two of them past the 64 entries the kernels keep in LDS
+
+
+def bracket_automaton(many_pops=False):
     """Four stack symbols, five states (< 16: in LDS whole): the state is what is on top of the stack (4: nothing); letters, digits
-    and spaces stay, an opener pushes its kind, the closer of the kind on top pops; the text may end where nothing is open."""
+    and spaces stay, an opener pushes its kind, the closer of the kind on top pops; the text may end where nothing is open.
+    many_pops: the same language over a pop table of 70 entries (more than 64: read through L2, not from LDS) -- every closer has an
+    entry of its own, POP_ROWS, and every other entry leads to a wrong state, so that a lookup of the wrong entry shows."""
     from tiny_llm_hip import grammar as G
 
     opens, closes = b"([{<", b")]}>"
@@ -94,17 +99,19 @@ def bracket_automaton():
         for a in range(4):
             table[s, opens[a]], ops[s, opens[a]] = a, 1 + a
         if s < 4:
-            table[s, closes[s]], ops[s, closes[s]] = 0, 5
-    return G.StackDFA(table, ops, [[0, 1, 2, 3, 4]], [0, 0, 0, 0, 1], 4)
+            table[s, closes[s]], ops[s, closes[s]] = (POP_ROWS[s] if many_pops else 0), 5
+    pops = [[0, 1, 2, 3, 4] if r in POP_ROWS else [(r + 1) % 4, (r + 2) % 4, 4, 0xFFFF, r % 4] for r in range(70)] if many_pops else [[0, 1, 2, 3, 4]]
+    return G.StackDFA(table, ops, pops, [0, 0, 0, 0, 1], 4)
 
 
 @functools.lru_cache(maxsize=None)
 def automaton(key):
-    """"brackets", "json" (any value, free whitespace), "json-object" (compact), or a regex pattern (bytes)"""
+    """"brackets", "brackets-pops" (the same over a large pop table), "json" (any value, free whitespace), "json-object" (compact), or a
+    regex pattern (bytes)"""
     from tiny_llm_hip import grammar as G
 
-    if key == "brackets":
-        return bracket_automaton()
+    if key in ("brackets", "brackets-pops"):
+        return bracket_automaton(many_pops=key == "brackets-pops")
     if key == "json":
         return G.compile_json("value", "free")
     if key == "json-object":
@@ -196,7 +203,7 @@ def bits_of(t):
 def _configurations(g, key, V):
     """(configuration, {token text: allowed?} that the row must show) -- END, depth 0, depth 32, depth 31 with a token that pushes twice,
     states reached mid-string, and both sides of the long-token rule"""
-    if key == "brackets":
+    if key in ("brackets", "brackets-pops"):
         rng = np.random.default_rng(7)
         full = [int(a) for a in rng.integers(0, 4, 32)]
         full[31], full[30] = 1, 1  # '[' on top, '[' under it
@@ -239,10 +246,20 @@ def _configurations(g, key, V):
 @pytest.mark.parametrize("V", [1024, 151936, 151941])
 @pytest.mark.parametrize("key", ["brackets", "json"])
 def test_mask_rows_stack_bit_for_bit(V, key):
+    _check_mask_rows_stack(V, key)
+
+
+def test_mask_rows_stack_pop_table_past_lds():
+    """more than 64 pop entries: the one path on which the pop lookups of a walk go through L2 (GRS_LDS_POPS)"""
+    assert automaton("brackets-pops").n_pop > 64 and max(POP_ROWS) >= 64
+    _check_mask_rows_stack(1024, "brackets-pops")
+
+
+def _check_mask_rows_stack(V, key):
     import tiny_llm_ext_hip as ext
 
     g = oracle_of(key, V)
-    assert (len(g.accepting) < 16) if key == "brackets" else (len(g.accepting) > 100)
+    assert (len(g.accepting) < 16) if key.startswith("brackets") else (len(g.accepting) > 100)
     dev = Device(V)
     try:
         rng = np.random.default_rng(V)

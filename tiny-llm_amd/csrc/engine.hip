@@ -55,52 +55,29 @@ struct tl_vocab {
 struct tl_grammar {
     const tl_vocab *vocab = nullptr;
     int n_states = 0, start = 0;
-    std::vector<uint16_t> table;
+    std::vector<uint16_t> table;  // a regex grammar's
     std::vector<uint8_t> accepting;
     std::vector<int32_t> eos;
     DeviceBlock mem;
     GrammarDev *dev = nullptr;  // what a slot's pointer is poked to
-    bool is_eos(int token) const { return std::find(eos.begin(), eos.end(), token) != eos.end(); }
-    // state' of the definition, on the host copies
-    int advance(int state, int token) const {
-        if (state < 0 || token < 0 || token >= vocab->vocab || is_eos(token)) return GR_END;
-        const int b0 = vocab->offsets[token], b1 = vocab->offsets[token + 1];
-        if (b1 <= b0) return GR_END;
-        uint32_t st = (uint32_t)state;
-        for (int k = b0; k < b1; ++k) {
-            st = table[(size_t)st * 256 + vocab->bytes[k]];
-            if (st == GR_DEAD) return GR_END;
-        }
-        return (int)st;
-    }
-    // a stack grammar (tl_grammar_create_stack, grammar_stack.h): ops and the pop table beside the table
+    // a stack grammar (tl_grammar_create_stack): in place of `table`, the two tables in the shape the device holds them (grammar_stack.h)
     bool stack = false;
     int n_pop = 0;
-    std::vector<uint8_t> ops;
-    std::vector<uint16_t> pop_table;  // [n_pop][5]
-    // advance of the definition on a configuration, on the host copies
-    GrsConfig advance_config(GrsConfig c, int token) const {
+    std::vector<uint32_t> fused;  // [n_states][256] entry | op << 16
+    std::vector<uint16_t> pop8;   // [max(n_pop, 1)][8]
+    bool is_eos(int token) const { return std::find(eos.begin(), eos.end(), token) != eos.end(); }
+    // advance of the definition on a configuration (a regex grammar's: (state, 0, 0)), END = (-1, 0, 0): the device's transition rules
+    // (gr_step, grs_step) on the host copies
+    GrsConfig advance(GrsConfig c, int token) const {
         const GrsConfig end{GR_END, 0, 0ull};
         if (c.state < 0 || token < 0 || token >= vocab->vocab || is_eos(token)) return end;
         const int b0 = vocab->offsets[token], b1 = vocab->offsets[token + 1];
         if (b1 <= b0) return end;
         for (int k = b0; k < b1; ++k) {
-            const size_t at = (size_t)c.state * 256 + vocab->bytes[k];
-            const uint32_t t = table[at], op = ops[at];
-            if (t == GR_DEAD) return end;
-            if (op == 0) {
-                c.state = (int)t;
-            } else if (op < GRS_POP) {
-                if (c.depth == GRS_DEPTH) return end;
-                c.stack |= (uint64_t)(op - 1) << (2 * c.depth);
-                c.depth += 1;
-                c.state = (int)t;
+            if (stack) {
+                if (!grs_step(fused.data(), pop8.data(), c, vocab->bytes[k])) return end;
             } else {
-                if (c.depth == 0) return end;
-                c.depth -= 1;
-                c.stack &= grs_mask(c.depth);
-                const uint32_t top = c.depth ? (uint32_t)(c.stack >> (2 * (c.depth - 1))) & 3u : 4u;
-                const uint32_t to = pop_table[(size_t)t * 5 + top];
+                const uint32_t to = gr_step(table.data(), (uint32_t)c.state, vocab->bytes[k]);
                 if (to == GR_DEAD) return end;
                 c.state = (int)to;
             }
@@ -559,30 +536,28 @@ static int lp_carry(tl_engine *e, int src, int dst, bool move) {
 // ---- per-slot logit processing (logit_process.h) ------------------------------------------------------------
 // does the slot, taking part in a step, process its logits?
 static bool step_processes_slot(const tl_engine *e, int slot) { return e->pen_mem && e->slot_runs(slot) && e->pen[slot].processes(); }
-// ... and the grammar it processes them under, or null (with one the step's processing launch is the grammar twin; with a stack grammar,
-// g->stack, the third twin of grammar_stack.h)
+// ... and the grammar it processes them under, or null (with one the step's processing launch runs in its regex mode; with a stack
+// grammar, g->stack, in its stack mode: logit_process.h)
 static const tl_grammar *step_grammar_slot(const tl_engine *e, int slot) { return step_processes_slot(e, slot) ? e->pen[slot].grammar : nullptr; }
 
-// the per-slot automaton pointers and state records: allocated by the first tl_engine_set_grammar
-static int gr_alloc(tl_engine *e) {
-    if (e->gr_mem) return TL_OK;
-    const size_t B = (size_t)e->cfg.max_batch, bytes = B * (sizeof(GrammarDev *) + sizeof(GrammarRecord));
-    TL_TRY(alloc_filled(e->gr_mem, bytes, "engine: hipMalloc(grammar slots) failed", [&](char *m) -> int {
-        return hipMemsetAsync(m, 0, bytes, e->stream) == hipSuccess ? TL_OK : fail(TL_ERR_HIP, "engine: memset(grammar slots) failed");
-    }));
+// the per-slot automaton pointers and state records: allocated by the first tl_engine_set_grammar; with `stack`, the records of slots
+// with a stack grammar too: allocated by the first one set.  Each block zeroed, and counted as workspace when it is made.
+static int gr_alloc(tl_engine *e, bool stack) {
+    const auto block = [e](DeviceBlock &mem, size_t bytes, const std::string &what) -> int {
+        if (mem) return TL_OK;
+        TL_TRY(alloc_filled(mem, bytes, "engine: hipMalloc(" + what + ") failed", [&](char *m) -> int {
+            return hipMemsetAsync(m, 0, bytes, e->stream) == hipSuccess ? TL_OK : fail(TL_ERR_HIP, "engine: memset(" + what + ") failed");
+        }));
+        e->stats.workspace_bytes += bytes;
+        return TL_OK;
+    };
+    const size_t B = (size_t)e->cfg.max_batch;
+    TL_TRY(block(e->gr_mem, B * (sizeof(GrammarDev *) + sizeof(GrammarRecord)), "grammar slots"));
     e->gr_ptr = e->gr_mem.at<const GrammarDev *>();
     e->gr_state = e->gr_mem.at<GrammarRecord>(B * sizeof(GrammarDev *));
-    e->stats.workspace_bytes += bytes;
-    return TL_OK;
-}
-static int gr_stack_alloc(tl_engine *e) {
-    if (e->gr_stack) return TL_OK;
-    const size_t bytes = (size_t)e->cfg.max_batch * sizeof(GrammarStackRecord);
-    TL_TRY(alloc_filled(e->gr_stack_mem, bytes, "engine: hipMalloc(stack grammar slots) failed", [&](char *m) -> int {
-        return hipMemsetAsync(m, 0, bytes, e->stream) == hipSuccess ? TL_OK : fail(TL_ERR_HIP, "engine: memset(stack grammar slots) failed");
-    }));
+    if (!stack) return TL_OK;
+    TL_TRY(block(e->gr_stack_mem, B * sizeof(GrammarStackRecord), "stack grammar slots"));
     e->gr_stack = e->gr_stack_mem.at<GrammarStackRecord>();
-    e->stats.workspace_bytes += bytes;
     return TL_OK;
 }
 // the slot's record becomes {no context length, state}; a stack grammar's: {no context length, (state, depth 0, word 0)} (the stack
@@ -650,8 +625,7 @@ static int pen_write(tl_engine *e, int slot, const tl_engine::PenaltyParams &v) 
     const bool bias_changed = cur.bias_ids != v.bias_ids || memcmp(cur.bias_values.data(), v.bias_values.data(), v.bias_values.size() * 4) != 0;
     if (bias_changed) pk.emplace_back(e->pen_bias_n + slot, (int32_t)v.bias_ids.size());
     if (cur.grammar != v.grammar) {  // the automaton's pointer (two words) and, for a new one, the record at its start state
-        TL_TRY(gr_alloc(e));
-        if (v.grammar && v.grammar->stack) TL_TRY(gr_stack_alloc(e));
+        TL_TRY(gr_alloc(e, v.grammar && v.grammar->stack));
         poke_u64(pk, e->gr_ptr + slot, (uint64_t)(uintptr_t)(v.grammar ? v.grammar->dev : nullptr));
         if (v.grammar) gr_poke_state(e, slot, v.grammar, pk);
     }
@@ -938,7 +912,7 @@ struct StepFeatures {
         // bit 62: the step ends with the sampling twin of step_end_kernel, bit 61: with the logprob twin (step_end.h)
         return (samples ? (1L << 62) : 0L) | (logprobs ? (1L << 61) : 0L) |
                // bit 60: the processing launch (logit_process.h) stands between the lm_head and the step end
-               // bit 59: ... and it is the grammar twin (grammar.h); bit 58: the stack-grammar twin (grammar_stack.h)
+               // bit 59: ... in its regex mode (grammar.h); bit 58: in its stack mode (grammar_stack.h)
                (processes ? (1L << 60) : 0L) | (grammar ? (1L << 59) : 0L) | (stack_grammar ? (1L << 58) : 0L) |
                // bit 57: the truncation launch (truncate.h) stands ahead of the step end and the Mirostat update behind it
                // bit 56: ... and a slot has Mirostat on (the plan keeps the hipGraphLaunch route)
@@ -2448,112 +2422,96 @@ extern "C" void tl_vocab_destroy(tl_vocab *v) {
     delete v;
 }
 
-extern "C" int tl_grammar_create(const tl_vocab *v, int n_states, const uint16_t *table, const uint8_t *accepting, int start, const int32_t *eos_ids,
-                                 int n_eos, void *stream, tl_grammar **out) {
-    TL_REQUIRE(out, "grammar_create: null argument");
+// tl_grammar_create (stack = false: ops, n_pop and pop_table unused) and tl_grammar_create_stack: validation, the host object, the device
+// allocation headed by its GrammarDev, the uploads and the walks of the long tokens.  `who` heads every error text.
+static int grammar_build(const std::string &who, bool stack, const tl_vocab *v, int n_states, const uint16_t *table, const uint8_t *ops, int n_pop,
+                         const uint16_t *pop_table, const uint8_t *accepting, int start, const int32_t *eos_ids, int n_eos, void *stream, tl_grammar **out) {
+    TL_REQUIRE(out, who + ": null argument");
     *out = nullptr;
-    TL_REQUIRE(v && table && accepting && eos_ids, "grammar_create: null argument");
-    TL_REQUIRE(n_states >= 1 && n_states <= GR_MAX_STATES, "grammar_create: between 1 and 32,768 states");
-    TL_REQUIRE(start >= 0 && start < n_states, "grammar_create: start state out of range");
-    TL_REQUIRE(n_eos >= 1 && n_eos <= GR_MAX_EOS, "grammar_create: between 1 and 8 EOS ids");
+    TL_REQUIRE(v && table && (ops || !stack) && accepting && eos_ids, who + ": null argument");
+    TL_REQUIRE(n_states >= 1 && n_states <= GR_MAX_STATES, who + ": between 1 and 32,768 states");
+    if (stack) TL_REQUIRE(n_pop >= 0 && n_pop <= GRS_MAX_POPS && (n_pop == 0 || pop_table), who + ": between 0 and 65,535 pop entries");
+    TL_REQUIRE(start >= 0 && start < n_states, who + ": start state out of range");
+    TL_REQUIRE(n_eos >= 1 && n_eos <= GR_MAX_EOS, who + ": between 1 and 8 EOS ids");
     for (int i = 0; i < n_eos; ++i) {
-        TL_REQUIRE(eos_ids[i] >= 0 && eos_ids[i] < v->vocab, "grammar_create: EOS id out of range");
-        for (int k = 0; k < i; ++k) TL_REQUIRE(eos_ids[k] != eos_ids[i], "grammar_create: an EOS id appears twice");
+        TL_REQUIRE(eos_ids[i] >= 0 && eos_ids[i] < v->vocab, who + ": EOS id out of range");
+        for (int k = 0; k < i; ++k) TL_REQUIRE(eos_ids[k] != eos_ids[i], who + ": an EOS id appears twice");
     }
     const size_t cells = (size_t)n_states * 256;
-    for (size_t i = 0; i < cells; ++i) TL_REQUIRE(table[i] == GR_DEAD || table[i] < n_states, "grammar_create: a transition leads outside the table");
     auto g = std::make_unique<tl_grammar>();
-    g->vocab = v, g->n_states = n_states, g->start = start;
-    g->table.assign(table, table + cells);
+    g->vocab = v, g->n_states = n_states, g->start = start, g->stack = stack, g->n_pop = stack ? n_pop : 0;
+    if (!stack) {
+        for (size_t i = 0; i < cells; ++i) TL_REQUIRE(table[i] == GR_DEAD || table[i] < n_states, who + ": a transition leads outside the table");
+        g->table.assign(table, table + cells);
+    } else {
+        g->fused.resize(cells);
+        for (size_t i = 0; i < cells; ++i) {
+            TL_REQUIRE(ops[i] <= GRS_POP, who + ": an op byte is not 0 .. 5");
+            if (table[i] != GR_DEAD) {
+                if (ops[i] == GRS_POP) TL_REQUIRE(table[i] < n_pop, who + ": a pop entry leads outside the pop table");
+                else TL_REQUIRE(table[i] < n_states, who + ": a transition leads outside the table");
+            }
+            g->fused[i] = (uint32_t)table[i] | (table[i] != GR_DEAD ? (uint32_t)ops[i] << 16 : 0u);
+        }
+        g->pop8.assign((size_t)std::max(n_pop, 1) * 8, (uint16_t)GR_DEAD);
+        for (size_t i = 0; i < (size_t)n_pop * 5; ++i) {
+            TL_REQUIRE(pop_table[i] == GR_DEAD || pop_table[i] < n_states, who + ": a pop leads outside the table");
+            g->pop8[i / 5 * 8 + i % 5] = pop_table[i];
+        }
+    }
     g->accepting.assign(accepting, accepting + n_states);
     g->eos.assign(eos_ids, eos_ids + n_eos);
-    // long_bits: one bit per (state, long token of the vocabulary), rows of whole 64-bit ballots
+    // per (state, long token of the vocabulary): one bit, in rows of whole 64-bit ballots (long_bits), or one depth byte (long_m)
     const int n_long = (int)v->long_ids.size(), long_words = 2 * ceil_div(n_long, 64);
-    const size_t o_table = 256, o_acc = o_table + align_up(cells * 2, 256), o_long = o_acc + align_up((size_t)n_states, 256),
-                 total = o_long + align_up((size_t)n_states * long_words * 4 + 4, 256);
-    TL_TRY(g->mem.alloc(total, "grammar_create: hipMalloc failed"));
+    const void *const table_host = stack ? (const void *)g->fused.data() : (const void *)g->table.data();
+    const size_t table_bytes = cells * (stack ? 4 : 2), pop_bytes = g->pop8.size() * 2;
+    Carve carve;
+    static_assert(sizeof(GrammarDev) <= 256, "GrammarDev heads the grammar's allocation");
+    carve(sizeof(GrammarDev));
+    const size_t o_table = carve(table_bytes), o_pop = stack ? carve(pop_bytes) : 0, o_acc = carve((size_t)n_states),
+                 o_long = carve(stack ? (size_t)n_states * n_long + 4 : (size_t)n_states * long_words * 4 + 4);
+    TL_TRY(g->mem.alloc(carve.off, who + ": hipMalloc failed"));
     char *const mem = g->mem.at();
     GrammarDev d{};
-    d.table = (const uint16_t *)(mem + o_table), d.accepting = (const uint8_t *)(mem + o_acc);
-    d.offsets = v->offsets_dev, d.bytes = v->bytes_dev, d.n_states = n_states, d.n_eos = n_eos;
-    d.long_index = v->long_index_dev, d.long_bits = (const uint32_t *)(mem + o_long), d.long_words = long_words;
+    d.accepting = (const uint8_t *)(mem + o_acc);
+    d.offsets = v->offsets_dev, d.bytes = v->bytes_dev, d.n_states = n_states, d.n_eos = n_eos, d.long_index = v->long_index_dev;
     for (int i = 0; i < GR_MAX_EOS; ++i) d.eos[i] = i < n_eos ? eos_ids[i] : -1;
-    static_assert(sizeof(GrammarDev) <= 256, "GrammarDev heads the grammar's allocation");
-    hipError_t he = hipMemcpyAsync(mem, &d, sizeof(d), hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(mem + o_table, g->table.data(), cells * 2, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(mem + o_acc, g->accepting.data(), (size_t)n_states, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (he == hipSuccess && n_long > 0) {  // the walks of the long tokens from every state, once, on the device
-        const GrammarLongArgs la{d.table, d.offsets, d.bytes, v->long_ids_dev, n_long, long_words, (uint32_t *)(mem + o_long)};
-        hipLaunchKernelGGL(grammar_long_bits_kernel, dim3(long_words / 2, n_states), dim3(64), 0, (hipStream_t)stream, la);
+    if (stack) {
+        d.kind = 1, d.n_pop = n_pop, d.n_long = n_long;
+        d.fused = (const uint32_t *)(mem + o_table), d.pop = (const uint16_t *)(mem + o_pop), d.long_m = (const uint8_t *)(mem + o_long);
+    } else {
+        d.table = (const uint16_t *)(mem + o_table), d.long_bits = (const uint32_t *)(mem + o_long), d.long_words = long_words;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t he = hipMemcpyAsync(mem, &d, sizeof(d), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(mem + o_table, table_host, table_bytes, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && stack) he = hipMemcpyAsync(mem + o_pop, g->pop8.data(), pop_bytes, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(mem + o_acc, g->accepting.data(), (size_t)n_states, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && n_long > 0) {  // the walks of the long tokens from every state (a stack grammar: with an empty stack), once, on the device
+        if (stack) {
+            const GrammarLongDepthArgs la{d.fused, d.pop, d.offsets, d.bytes, v->long_ids_dev, n_long, (uint8_t *)(mem + o_long)};
+            hipLaunchKernelGGL(grammar_long_depth_kernel, dim3(ceil_div(n_long, 64), n_states), dim3(64), 0, st, la);
+        } else {
+            const GrammarLongArgs la{d.table, d.offsets, d.bytes, v->long_ids_dev, n_long, long_words, (uint32_t *)(mem + o_long)};
+            hipLaunchKernelGGL(grammar_long_bits_kernel, dim3(long_words / 2, n_states), dim3(64), 0, st, la);
+        }
         he = hipGetLastError();
     }
-    if (he == hipSuccess) he = hipStreamSynchronize((hipStream_t)stream);
-    if (he != hipSuccess) return fail(TL_ERR_HIP, std::string("grammar_create: ") + hipGetErrorString(he));
+    if (he == hipSuccess) he = hipStreamSynchronize(st);  // (the copies read this frame's `d`)
+    if (he != hipSuccess) return fail(TL_ERR_HIP, who + ": " + hipGetErrorString(he));
     g->dev = (GrammarDev *)mem;
     *out = g.release();
     return TL_OK;
 }
 
+extern "C" int tl_grammar_create(const tl_vocab *v, int n_states, const uint16_t *table, const uint8_t *accepting, int start, const int32_t *eos_ids,
+                                 int n_eos, void *stream, tl_grammar **out) {
+    return grammar_build("grammar_create", false, v, n_states, table, nullptr, 0, nullptr, accepting, start, eos_ids, n_eos, stream, out);
+}
+
 extern "C" int tl_grammar_create_stack(const tl_vocab *v, int n_states, const uint16_t *table, const uint8_t *ops, int n_pop, const uint16_t *pop_table,
                                        const uint8_t *accepting, int start, const int32_t *eos_ids, int n_eos, void *stream, tl_grammar **out) {
-    TL_REQUIRE(out, "grammar_create_stack: null argument");
-    *out = nullptr;
-    TL_REQUIRE(v && table && ops && accepting && eos_ids, "grammar_create_stack: null argument");
-    TL_REQUIRE(n_states >= 1 && n_states <= GR_MAX_STATES, "grammar_create_stack: between 1 and 32,768 states");
-    TL_REQUIRE(n_pop >= 0 && n_pop <= GRS_MAX_POPS && (n_pop == 0 || pop_table), "grammar_create_stack: between 0 and 65,535 pop entries");
-    TL_REQUIRE(start >= 0 && start < n_states, "grammar_create_stack: start state out of range");
-    TL_REQUIRE(n_eos >= 1 && n_eos <= GR_MAX_EOS, "grammar_create_stack: between 1 and 8 EOS ids");
-    for (int i = 0; i < n_eos; ++i) {
-        TL_REQUIRE(eos_ids[i] >= 0 && eos_ids[i] < v->vocab, "grammar_create_stack: EOS id out of range");
-        for (int k = 0; k < i; ++k) TL_REQUIRE(eos_ids[k] != eos_ids[i], "grammar_create_stack: an EOS id appears twice");
-    }
-    const size_t cells = (size_t)n_states * 256;
-    std::vector<uint32_t> fused(cells);
-    for (size_t i = 0; i < cells; ++i) {
-        TL_REQUIRE(ops[i] <= GRS_POP, "grammar_create_stack: an op byte is not 0 .. 5");
-        if (table[i] != GR_DEAD) {
-            if (ops[i] == GRS_POP) TL_REQUIRE(table[i] < n_pop, "grammar_create_stack: a pop entry leads outside the pop table");
-            else TL_REQUIRE(table[i] < n_states, "grammar_create_stack: a transition leads outside the table");
-        }
-        fused[i] = (uint32_t)table[i] | (table[i] != GR_DEAD ? (uint32_t)ops[i] << 16 : 0u);
-    }
-    std::vector<uint16_t> pop8((size_t)std::max(n_pop, 1) * 8, (uint16_t)GR_DEAD);
-    for (size_t i = 0; i < (size_t)n_pop * 5; ++i) {
-        TL_REQUIRE(pop_table[i] == GR_DEAD || pop_table[i] < n_states, "grammar_create_stack: a pop leads outside the table");
-        pop8[i / 5 * 8 + i % 5] = pop_table[i];
-    }
-    auto g = std::make_unique<tl_grammar>();
-    g->vocab = v, g->n_states = n_states, g->start = start, g->stack = true, g->n_pop = n_pop;
-    g->table.assign(table, table + cells);
-    g->ops.assign(ops, ops + cells);
-    g->pop_table.assign(pop_table, pop_table + (size_t)n_pop * 5);
-    g->accepting.assign(accepting, accepting + n_states);
-    g->eos.assign(eos_ids, eos_ids + n_eos);
-    const int n_long = (int)v->long_ids.size();
-    const size_t o_fused = 256, o_pop = o_fused + align_up(cells * 4, 256), o_acc = o_pop + align_up(pop8.size() * 2, 256),
-                 o_long = o_acc + align_up((size_t)n_states, 256), total = o_long + align_up((size_t)n_states * n_long + 4, 256);
-    TL_TRY(g->mem.alloc(total, "grammar_create_stack: hipMalloc failed"));
-    char *const mem = g->mem.at();
-    GrammarDev d{};
-    d.accepting = (const uint8_t *)(mem + o_acc);
-    d.offsets = v->offsets_dev, d.bytes = v->bytes_dev, d.n_states = n_states, d.n_eos = n_eos, d.long_index = v->long_index_dev;
-    d.kind = 1, d.n_pop = n_pop, d.n_long = n_long;
-    d.fused = (const uint32_t *)(mem + o_fused), d.pop = (const uint16_t *)(mem + o_pop), d.long_m = (const uint8_t *)(mem + o_long);
-    for (int i = 0; i < GR_MAX_EOS; ++i) d.eos[i] = i < n_eos ? eos_ids[i] : -1;
-    hipError_t he = hipMemcpyAsync(mem, &d, sizeof(d), hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(mem + o_fused, fused.data(), cells * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(mem + o_pop, pop8.data(), pop8.size() * 2, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(mem + o_acc, g->accepting.data(), (size_t)n_states, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (he == hipSuccess && n_long > 0) {  // the walks of the long tokens from every state with an empty stack, once, on the device
-        const GrammarLongDepthArgs la{d.fused, d.pop, d.offsets, d.bytes, v->long_ids_dev, n_long, (uint8_t *)(mem + o_long)};
-        hipLaunchKernelGGL(grammar_long_depth_kernel, dim3(ceil_div(n_long, 64), n_states), dim3(64), 0, (hipStream_t)stream, la);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipStreamSynchronize((hipStream_t)stream);  // (the pageable host copies above are locals)
-    if (he != hipSuccess) return fail(TL_ERR_HIP, std::string("grammar_create_stack: ") + hipGetErrorString(he));
-    g->dev = (GrammarDev *)mem;
-    *out = g.release();
-    return TL_OK;
+    return grammar_build("grammar_create_stack", true, v, n_states, table, ops, n_pop, pop_table, accepting, start, eos_ids, n_eos, stream, out);
 }
 
 extern "C" void tl_grammar_destroy(tl_grammar *g) {
@@ -2575,24 +2533,37 @@ extern "C" int tl_engine_set_grammar(tl_engine *e, int slot, const tl_grammar *g
     return TL_OK;
 }
 
+// the configuration of a slot with grammar `g` (a regex grammar's: (state, 0, 0)) once everything submitted has run: the slot's record,
+// advanced on the host with the pending token where no step has consumed that yet
+static int gr_read_config(tl_engine *e, int slot, const tl_grammar *g, GrsConfig *out) {
+    TL_HIP(hipStreamSynchronize(e->stream));
+    GrsConfig c{GR_END, 0, 0ull};
+    if (g->stack) {
+        GrammarStackRecord rec{};
+        TL_HIP(hipMemcpy(&rec, e->gr_stack + slot, sizeof(rec), hipMemcpyDeviceToHost));
+        int which;
+        c = grs_unpack((uint32_t)(rec.rec >> 32), &which);
+        if (c.state >= 0) c.stack = rec.stack[which] & grs_mask(c.depth);
+    } else {
+        GrammarRecord rec{};
+        TL_HIP(hipMemcpy(&rec, e->gr_state + slot, sizeof(rec), hipMemcpyDeviceToHost));
+        c.state = rec.state;
+    }
+    int32_t pending = 0;
+    TL_HIP(hipMemcpy(&pending, e->tokens + slot, 4, hipMemcpyDeviceToHost));
+    *out = e->gr_pending[slot] ? g->advance(c, pending) : c;
+    return TL_OK;
+}
+
 extern "C" int tl_engine_grammar_state(tl_engine *e, int slot, int *state, int *accepting) {
     TL_TRY(slot_check(e, slot, true));
     TL_REQUIRE(state, "engine_grammar_state: null argument");
     const tl_grammar *g = e->pen[slot].grammar;
     TL_REQUIRE(g, "engine_grammar_state: the slot has no grammar");
-    if (g->stack) {
-        int depth = 0;
-        uint64_t stack = 0;
-        return tl_engine_grammar_config(e, slot, state, &depth, &stack, accepting);
-    }
-    TL_HIP(hipStreamSynchronize(e->stream));
-    GrammarRecord rec{};
-    int32_t pending = 0;
-    TL_HIP(hipMemcpy(&rec, e->gr_state + slot, sizeof(rec), hipMemcpyDeviceToHost));
-    TL_HIP(hipMemcpy(&pending, e->tokens + slot, 4, hipMemcpyDeviceToHost));
-    const int st = e->gr_pending[slot] ? g->advance(rec.state, pending) : rec.state;
-    *state = st;
-    if (accepting) *accepting = st < 0 || g->accepting[st] ? 1 : 0;
+    GrsConfig c;
+    TL_TRY(gr_read_config(e, slot, g, &c));
+    *state = c.state;
+    if (accepting) *accepting = c.state < 0 || g->accepting[c.state] ? 1 : 0;
     return TL_OK;
 }
 
@@ -2601,22 +2572,8 @@ extern "C" int tl_engine_grammar_config(tl_engine *e, int slot, int *state, int 
     TL_REQUIRE(state && depth && stack, "engine_grammar_config: null argument");
     const tl_grammar *g = e->pen[slot].grammar;
     TL_REQUIRE(g, "engine_grammar_config: the slot has no grammar");
-    GrsConfig c{GR_END, 0, 0ull};
-    if (!g->stack) {  // a regex grammar: its state, no stack
-        TL_TRY(tl_engine_grammar_state(e, slot, &c.state, nullptr));
-    } else {
-        TL_HIP(hipStreamSynchronize(e->stream));
-        GrammarStackRecord rec{};
-        int32_t pending = 0;
-        TL_HIP(hipMemcpy(&rec, e->gr_stack + slot, sizeof(rec), hipMemcpyDeviceToHost));
-        TL_HIP(hipMemcpy(&pending, e->tokens + slot, 4, hipMemcpyDeviceToHost));
-        const uint32_t packed = (uint32_t)(rec.rec >> 32);
-        if (packed != 0xffffffffu) {
-            c.state = (int)(packed & 0xffffu), c.depth = (int)(packed >> 16 & 0xffu);
-            c.stack = rec.stack[packed >> 24 & 1u] & grs_mask(c.depth);
-        }
-        if (e->gr_pending[slot]) c = g->advance_config(c, pending);
-    }
+    GrsConfig c;
+    TL_TRY(gr_read_config(e, slot, g, &c));
     *state = c.state, *depth = c.depth, *stack = c.stack;
     if (accepting) *accepting = c.state < 0 || g->accepting[c.state] ? 1 : 0;
     return TL_OK;

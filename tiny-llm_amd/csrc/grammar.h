@@ -9,6 +9,10 @@
 // first-byte lookup of the launch, where most tokens die) and reads the rest through L2.
 // Long tokens (more than GR_LONG bytes) are not walked there at all: tl_grammar_create walks each of them from every state once and
 // leaves one bit per (state, long token), so a round-by-round walk never runs longer than GR_LONG rounds.
+//
+// What exists once, for this automaton and the stack automaton of grammar_stack.h alike: the transition rule of a byte (gr_step here,
+// grs_step there: __host__ __device__, so the host's advance of a pending token is the device's rule), the opening of the walk
+// (grammar_walk_open.inc), the EOS rule (gr_eos_rule) and the frame of the mask-rows kernels (gr_mask_rows).
 #pragma once
 #include "common.h"
 
@@ -57,6 +61,14 @@ __device__ __forceinline__ bool gr_is_eos(GrRef g, int token) {
     return is;
 }
 
+// One byte of the automaton, the transition rule of the definition: the state after byte b from state s, GR_DEAD where there is none.
+// The one copy of the rule, on the device (gr_advance, grammar_long_bits_kernel) and on the host (tl_grammar::advance); TABLE is the
+// table's pointer type, so that a device caller keeps its address space (GR_GLOBAL above) and the host passes a plain pointer.
+template <class TABLE>
+__host__ __device__ __forceinline__ uint32_t gr_step(TABLE table, uint32_t s, uint32_t b) {
+    return table[s * 256u + b];
+}
+
 // state' of the definition: END after an EOS id or from END, else the walk with DEAD -> END.  Called by ONE WAVE (all 64 lanes, uniform
 // arguments): the lanes fetch 64 of the token's bytes with one load, then the serial chain is one table lookup per byte.
 __device__ __forceinline__ int gr_advance(GrRef g, int state, int token, int vocab) {
@@ -72,8 +84,7 @@ __device__ __forceinline__ int gr_advance(GrRef g, int state, int token, int voc
         const uint32_t mine = base + lane < b1 ? bytes[base + lane] : 0u;
         const int n = min(64, b1 - base);
         for (int k = 0; k < n; ++k) {
-            const uint32_t b = (uint32_t)__shfl((int)mine, k);
-            s = table[s * 256u + b];
+            s = gr_step(table, s, (uint32_t)__shfl((int)mine, k));
             if (s == GR_DEAD) return GR_END;
         }
     }
@@ -89,40 +100,11 @@ __device__ __forceinline__ uint32_t gr_walk8(GrRef g, int state, int c, int voca
     const auto offsets = GR_GLOBAL(int32_t, g.offsets);
     const auto bytes = GR_GLOBAL(uint8_t, g.bytes);
     const auto table = GR_GLOBAL(uint16_t, g.table);
-    int off[9];
-    if (c + 8 <= vocab) {  // (offsets is 256-byte aligned and c a multiple of 8: two 16-byte loads and one more entry)
-        const auto o4 = reinterpret_cast<const u32x4 __attribute__((address_space(1))) *>(offsets + c);
-        const u32x4 a = o4[0], b = o4[1];
-        off[0] = a[0], off[1] = a[1], off[2] = a[2], off[3] = a[3], off[4] = b[0], off[5] = b[1], off[6] = b[2], off[7] = b[3];
-        off[8] = offsets[c + 8];
-    } else {
-#pragma unroll
-        for (int e = 0; e < 9; ++e) off[e] = offsets[min(c + e, vocab)];
-    }
-    uint32_t s[8], cur[8], nxt[8], t[8];
-    int len[8];
-    uint32_t alive = 0u, ok = 0u;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) len[e] = c + e < vocab ? off[e + 1] - off[e] : 0;
-    uint32_t is_long = 0u;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) is_long |= len[e] > GR_LONG ? 1u << e : 0u;
-    if (is_long) {  // rare (a few hundred tokens of the vocabulary): the precomputed bit of (state, token); not a chain below
-        const auto long_index = GR_GLOBAL(int32_t, g.long_index);
-        const auto long_bits = GR_GLOBAL(uint32_t, g.long_bits) + (size_t)state * g.long_words;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            if (!(is_long >> e & 1u)) continue;
-            const int li = long_index[c + e];
-            ok |= (long_bits[li >> 5] >> (li & 31) & 1u) << e;
-            len[e] = 0;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) alive |= len[e] > 0 ? 1u << e : 0u;
-    // bytes 0 and 1 of every token (an empty token reads byte 0 of the buffer: in bounds, dropped)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) cur[e] = bytes[len[e] > 0 ? off[e] : 0];
+    // a long token: the precomputed bit of (state, token)
+    const auto long_ok = [&](int li) { return GR_GLOBAL(uint32_t, g.long_bits)[(size_t)state * g.long_words + (li >> 5)] >> (li & 31) & 1u; };
+#include "grammar_walk_open.inc"
+    uint32_t s[8], nxt[8], t[8];
+    // byte 1 of every token
 #pragma unroll
     for (int e = 0; e < 8; ++e) nxt[e] = bytes[len[e] > 1 ? off[e] + 1 : 0];
     // first byte: the current state's row, in LDS on both paths
@@ -159,18 +141,23 @@ __device__ __forceinline__ uint32_t gr_walk8(GrRef g, int state, int c, int voca
     return ok;
 }
 
-// bit e of the result: token c + e is allowed in `state` (uniform over the workgroup).  whole: s_table holds the table as it is;
-// otherwise the row of `state` alone (256 entries).
-__device__ __forceinline__ uint32_t gr_allowed8(GrRef g, int state, int c, int vocab, const uint16_t *s_table, bool whole) {
-    uint32_t ok = 0u;
-    if (state >= 0) ok = whole ? gr_walk8<true>(g, state, c, vocab, s_table) : gr_walk8<false>(g, state, c, vocab, s_table);  // uniform
-    // the EOS ids are decided by the state alone, whatever their bytes: allowed in END and in an accepting state, never otherwise
+// The EOS ids of a lane's 8 tokens are decided by the state alone, whatever their bytes (acceptance by final state): allowed in END and in
+// an accepting state, never otherwise.  `ok`: what the walk found; returns it with the EOS bits set or cleared.
+__device__ __forceinline__ uint32_t gr_eos_rule(GrRef g, int state, int c, int vocab, uint32_t ok) {
     const bool eos_ok = state < 0 || GR_GLOBAL(uint8_t, g.accepting)[state] != 0;
     for (int k = 0; k < g.n_eos; ++k) {
         const int d = g.eos[k] - c;
         if ((unsigned)d < 8u && g.eos[k] < vocab) ok = eos_ok ? (ok | 1u << d) : (ok & ~(1u << d));
     }
     return ok;
+}
+
+// bit e of the result: token c + e is allowed in `state` (uniform over the workgroup).  whole: s_table holds the table as it is;
+// otherwise the row of `state` alone (256 entries).
+__device__ __forceinline__ uint32_t gr_allowed8(GrRef g, int state, int c, int vocab, const uint16_t *s_table, bool whole) {
+    uint32_t ok = 0u;
+    if (state >= 0) ok = whole ? gr_walk8<true>(g, state, c, vocab, s_table) : gr_walk8<false>(g, state, c, vocab, s_table);  // uniform
+    return gr_eos_rule(g, state, c, vocab, ok);
 }
 
 // the table (or the current state's row) into LDS; s_table holds GR_LDS_STATES * 256 entries.  Returns whether the whole table is there.
@@ -226,7 +213,7 @@ static __global__ __launch_bounds__(64) void grammar_long_bits_kernel(const Gram
     if (li < a.n_long) {
         const int j = a.long_ids[li];
         uint32_t s = (uint32_t)state;
-        for (int k = a.offsets[j]; k < a.offsets[j + 1] && s != GR_DEAD; ++k) s = a.table[s * 256u + a.bytes[k]];
+        for (int k = a.offsets[j]; k < a.offsets[j + 1] && s != GR_DEAD; ++k) s = gr_step(a.table, s, a.bytes[k]);
         ok = s != GR_DEAD;
     }
     const unsigned long long m = __ballot(ok);
@@ -236,7 +223,19 @@ static __global__ __launch_bounds__(64) void grammar_long_bits_kernel(const Gram
     }
 }
 
-// tl_grammar_mask_rows: out[i][j] = logits[i][j] where j is allowed in states[i], else -inf (bf16 0xff80).  grid = (chunks of 2048, rows)
+// The frame of the mask-rows kernels (tl_grammar_mask_rows, tl_grammar_mask_rows_stack): out[i][j] = logits[i][j] where j is allowed in
+// row i's state, else -inf (bf16 0xff80).  grid = (chunks of 2048, rows); allowed(row, c): bit e = token c + e is allowed.
+template <class ALLOWED>
+__device__ __forceinline__ void gr_mask_rows(const uint16_t *logits, uint16_t *out, int vocab, ALLOWED allowed) {
+    const int row = blockIdx.y, c = blockIdx.x * 2048 + (int)threadIdx.x * 8;
+    const uint32_t ok = allowed(row, c);
+    const uint16_t *lg = logits + (long)row * vocab;
+    out += (long)row * vocab;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+        if (c + e < vocab) out[c + e] = (ok >> e & 1u) ? lg[c + e] : (uint16_t)0xff80u;
+}
+
 struct GrammarMaskArgs {
     const GrammarDev *g;
     const uint16_t *logits;
@@ -246,17 +245,13 @@ struct GrammarMaskArgs {
 };
 static __global__ __launch_bounds__(256) void grammar_mask_rows_kernel(const GrammarMaskArgs a) {
     __shared__ __attribute__((aligned(16))) uint16_t s_table[GR_LDS_STATES * 256];
-    GrRef g = *GR_GLOBAL(GrammarDev, a.g);
-    const int row = blockIdx.y, c = blockIdx.x * 2048 + (int)threadIdx.x * 8;
-    int state = a.states[row];
-    if (state >= g.n_states) state = GR_END;  // (validated by the caller where it can be; never an index past the table)
-    const bool whole = gr_stage_table(g, state, s_table, 256);
-    const uint32_t ok = gr_allowed8(g, state, c, a.vocab, s_table, whole);
-    const uint16_t *lg = a.logits + (long)row * a.vocab;
-    uint16_t *out = a.out + (long)row * a.vocab;
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-        if (c + e < a.vocab) out[c + e] = (ok >> e & 1u) ? lg[c + e] : (uint16_t)0xff80u;
+    gr_mask_rows(a.logits, a.out, a.vocab, [&](int row, int c) {
+        GrRef g = *GR_GLOBAL(GrammarDev, a.g);
+        int state = a.states[row];
+        if (state >= g.n_states) state = GR_END;  // (validated by the caller where it can be; never an index past the table)
+        const bool whole = gr_stage_table(g, state, s_table, 256);
+        return gr_allowed8(g, state, c, a.vocab, s_table, whole);
+    });
 }
 
 }  // namespace tl

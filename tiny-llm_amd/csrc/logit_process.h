@@ -8,7 +8,7 @@
 //   v = v - (f * float(count[j]))
 //   if count[j] > 0:               v = v - p
 //   v = v + bias[j]                (0 where the slot has no entry)
-//   if not allowed[j]:  v = -inf   (a slot with a grammar only: grammar.h, the GRAMMAR = true twin below)
+//   if not allowed[j]:  v = -inf   (a slot with a grammar only: grammar.h, grammar_stack.h; the grammar modes below)
 //   out[j] = bf16(v), round to nearest even
 // History: one uint16 per (slot, token): bit 15 = the token was in the prompt, bits 0-14 = how often the slot produced and fed it back,
 // saturating at 32,767.  A row whose slot does not process (r = 1, p = f = 0, no bias entry) is copied bit for bit.
@@ -17,9 +17,16 @@
 // pass reads two rows and writes one.  8 logits per lane by 16-byte loads and stores where the rows are 16-byte aligned.  The workgroup
 // whose chunk holds the slot's pending token counts it (the only store to the history inside a step); the slot's bias entries that fall
 // into the chunk are scattered into LDS and added from there.
+//
+// The launch body is written once (lpr_process) and compiled in three grammar modes, one __global__ entry point each, one plan-key bit
+// each: none (logit_process_kernel<false>), regex (logit_process_kernel<true>), and regex and stack (logit_process_stack_kernel).  A mode
+// adds the LDS of its tables, the row's `allowed` byte and the advance of the slot's record (lpr_allowed8); everything else -- the copy
+// path, the loads, the bias scatter, the history count, the element rule, the stores -- is the same text in all three.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
-#include "grammar.h"
+#include "grammar_stack.h"  // and with it grammar.h
 
 namespace tl {
 
@@ -42,7 +49,7 @@ struct LogitProcessArgs {
     const float *bias_values;    // [slots, LPR_MAX_BIAS]
     const int32_t *tokens;       // [slots] pending token ids: a decode step counts them; nullptr: nothing is counted (prefill, caller rows)
     prof_t *prof;
-    // the grammar twin only (logit_process_kernel<true>, grammar.h); poked between steps like the parameters above
+    // the grammar modes only (grammar.h); poked between steps like the parameters above
     const GrammarDev *const *grammar;  // [slots] the slot's automaton; nullptr: none
     GrammarRecord *grammar_state;      // [slots]
     const int32_t *context_lens;       // [slots] the tag of a record is compared with
@@ -67,15 +74,47 @@ __device__ __forceinline__ uint32_t lpr_element(uint32_t l, uint32_t h, float r,
     return (uint32_t)BF16::from_float(v);
 }
 
-// GRAMMAR = false: the program of a step without a live grammar slot, as it was.  GRAMMAR = true (its own plan-key bit): one more line at
-// the end of the element -- a token that is not allowed in the slot's automaton state becomes -inf -- and the state's advance: every
-// workgroup of a row derives the state that includes the pending token from the slot's record ({tag, state}: a record whose tag equals
-// the slot's context length already includes it, any other record is advanced here), and the row's first workgroup stores it.
-template <bool GRAMMAR>
-static __global__ __launch_bounds__(LPR_THREADS) void logit_process_kernel(const LogitProcessArgs a) {
-    __shared__ float s_bias[LPR_CHUNK];
-    __shared__ __attribute__((aligned(16))) uint16_t s_table[GRAMMAR ? GR_LDS_STATES * 256 : 8];
+// The grammar mode of the launch.  none: the program of a step without a live grammar slot.  regex and stack (each its own plan-key bit):
+// one more line at the end of the element -- a token that is not allowed in the slot's automaton state becomes -inf -- and the state's
+// advance: every workgroup of a row derives the state that includes the pending token from the slot's record ({tag, state}: a record
+// whose tag equals the slot's context length already includes it, any other record is advanced here), and the row's first workgroup
+// stores it.  stack: the rows may also belong to slots with a STACK grammar (GrammarDev::kind), whose record is a GrammarStackRecord; a
+// row with a regex grammar runs the regex mode's code there.
+enum class LprGrammar { none, regex, stack };
+
+// What a grammar mode adds for a row whose slot has the automaton `gp` (uniform): bit e = token c + e is allowed, the slot's record
+// advanced on the way.  The LDS declared here is the mode's: the regex rows' uint16 table (GR_LDS_STATES rows) or, in the stack mode,
+// the fused table (GRS_LDS_STATES rows), which holds either -- 32 KB both ways -- and the pop table.  Contains barriers.
+template <LprGrammar G>
+__device__ __forceinline__ uint32_t lpr_allowed8(const LogitProcessArgs a, GrammarStackRecord *stack_state, const GrammarDev *gp,
+                                                 const int32_t *tokens, int slot, int c) {
+    constexpr bool STACK = G == LprGrammar::stack;
+    __shared__ __attribute__((aligned(16))) std::conditional_t<STACK, uint32_t, uint16_t> s_table[(STACK ? GRS_LDS_STATES : GR_LDS_STATES) * 256];
     __shared__ int s_state;
+    static_assert(GRS_LDS_STATES * 256 * 4 >= GR_LDS_STATES * 256 * 2, "the stack mode's s_table holds either table");
+    GrRef g = *GR_GLOBAL(GrammarDev, gp);
+    if constexpr (STACK) {
+        __shared__ __attribute__((aligned(16))) uint16_t s_pop[GRS_LDS_POPS * 8];
+        __shared__ uint32_t s_cfg[4];
+        if (g.kind != 0) {
+            const GrsConfig cfg = grs_row_config(g, stack_state, tokens, a.context_lens, slot, a.vocab, blockIdx.x == 0, s_cfg);
+            bool whole, pop_lds;
+            grs_stage_tables(g, cfg.state, s_table, s_pop, LPR_THREADS, &whole, &pop_lds);
+            return grs_allowed8(g, cfg, c, a.vocab, s_table, s_pop, whole, pop_lds);
+        }
+    }
+    uint16_t *s_table16 = reinterpret_cast<uint16_t *>(s_table);
+    const int state = gr_row_state(g, a.grammar_state, tokens, a.context_lens, slot, a.vocab, blockIdx.x == 0, &s_state);
+    const bool whole = gr_stage_table(g, state, s_table16, LPR_THREADS);
+    return gr_allowed8(g, state, c, a.vocab, s_table16, whole);
+}
+
+// The launch body, in grammar mode G.  (The argument struct by value, as the kernels take it: passed by reference, the step end's
+// argument struct cost its logprob twin 36 bytes of scratch.)
+template <LprGrammar G>
+__device__ __forceinline__ void lpr_process(const LogitProcessArgs a, GrammarStackRecord *stack_state) {
+    constexpr bool GRAMMAR = G != LprGrammar::none;
+    __shared__ float s_bias[LPR_CHUNK];
     const prof_t prof_t0 = prof_begin(a.prof);
     const int row = blockIdx.y, slot = a.slot0 + row;
     const int c0 = blockIdx.x * LPR_CHUNK, c = c0 + (int)threadIdx.x * 8;
@@ -123,12 +162,7 @@ static __global__ __launch_bounds__(LPR_THREADS) void logit_process_kernel(const
     __syncthreads();
     uint32_t allowed = 0xffu;
     if constexpr (GRAMMAR) {
-        if (gp) {  // uniform
-            GrRef g = *GR_GLOBAL(GrammarDev, gp);
-            const int state = gr_row_state(g, a.grammar_state, tokens, a.context_lens, slot, a.vocab, blockIdx.x == 0, &s_state);
-            const bool whole = gr_stage_table(g, state, s_table, LPR_THREADS);
-            allowed = gr_allowed8(g, state, c, a.vocab, s_table, whole);
-        }
+        if (gp) allowed = lpr_allowed8<G>(a, stack_state, gp, tokens, slot, c);  // uniform
     }
     // the pending token (what the previous step produced and this step consumed) is counted before the row is processed
     const int pending = tokens ? tokens[slot] : -1;
@@ -153,6 +187,20 @@ static __global__ __launch_bounds__(LPR_THREADS) void logit_process_kernel(const
             if (c + e < a.vocab) act_store(out + c + e, (uint16_t)((o[e >> 1] >> ((e & 1) * 16)) & 0xffffu));
     }
     prof_end(a.prof, prof_t0);
+}
+
+// The three entry points: each its own kernel name, argument struct (by value: csrc/aql.cpp copies a captured node's block as it is) and
+// plan-key bit.
+template <bool GRAMMAR>
+static __global__ __launch_bounds__(LPR_THREADS) void logit_process_kernel(const LogitProcessArgs a) {
+    lpr_process<GRAMMAR ? LprGrammar::regex : LprGrammar::none>(a, nullptr);
+}
+struct LogitProcessStackArgs {
+    LogitProcessArgs base;
+    GrammarStackRecord *stack_state;  // [slots]
+};
+static __global__ __launch_bounds__(LPR_THREADS) void logit_process_stack_kernel(const LogitProcessStackArgs sa) {
+    lpr_process<LprGrammar::stack>(sa.base, sa.stack_state);
 }
 
 // Prompt marking: bit 15 of history[token] for n consumed tokens of one slot (behind the token upload of a prefill / score chunk).
