@@ -741,6 +741,59 @@ int tl_engine_stop_state(tl_engine *e, int slot, tl_stop_state *out);
 int tl_stop_rows(const tl_stop *set, const int32_t *tokens_dev, int rows, const int32_t *armed_dev, const int32_t *max_new_dev,
                  int32_t *automaton_dev, tl_stop_state *states_dev, void *stream);
 
+/* ---- Beam search (csrc/beam.h, csrc/slot_table.h) ----------------------------------------------------------------
+ * A beam group is `width` plain greedy slots [slot0, slot0 + width): it decodes through tl_engine_decode like any other slots (other
+ * requests may live in other slots of the batch; no plan, key or kernel of the step knows of beams), and between two steps the caller
+ *   1. selects: tl_engine_beam_select ranks the (beam, token) pairs of the step's logits rows on the device and returns the best n_cand;
+ *   2. decides on the host which candidates finish a hypothesis and which become the next beams (tiny_llm_hip/beam.py);
+ *   3. reorders: tl_engine_beam_reorder makes slot slot0 + i the continuation of slot slot0 + parents[i] with pending token tokens[i].
+ *
+ * Selection (tl_beam_rows; per row the log-normaliser of tl_engine_set_logprobs, bit for bit):
+ *   per row    lse = m + log(sum_j exp(l_j - m)) in fp32 over non-NaN entries, m their maximum, the sum in the fixed order that makes
+ *              the value depend on the row alone; logprob(t) = l_t - lse.  NaN logits are never ranked.  A row without a finite maximum
+ *              (all NaN / -inf, or holding +inf) contributes no candidate; neither does a row whose score is not finite (-inf: a dead beam)
+ *   candidate  (parent, token) with score = scores[parent] + logprob, one fp32 addition
+ *   order      score descending; equal scores by the lower parent, then by the row's own order, which is the sampler's (logit
+ *              descending, equal logits by the lower token id)
+ *   output     the first n_cand candidates of that order over all rows x vocab pairs; entries past the rankable pairs are
+ *              {-1, -1, -inf, -inf}.  The result is bit-identical from call to call.
+ * TL_MAX_BEAM_CANDIDATES is 32, not TL_MAX_TOP_LOGPROBS: a search keeps max(2, 1 + n_eos) * num_beams candidates, 24 for 8 beams and two
+ * EOS ids.  tl_beam_rows is the routine over caller rows: logits_dev [rows, vocab] bf16 (vocab <= 524,288), 1 <= rows <= TL_MAX_BEAMS,
+ * scores_dev [rows] float, 1 <= n_cand <= TL_MAX_BEAM_CANDIDATES -> out_dev, n_cand records.  Two launches on `stream`: one 1,024-thread
+ * workgroup per row finds the row's first n_cand, one workgroup ranks the survivors.  The 4 KB of survivors between them are allocated
+ * and freed by the call, so it returns after its launches have run (the engine's entry point keeps its own scratch and only enqueues).
+ *
+ * tl_engine_beam_select: tl_beam_rows on the engine stream over rows [row0, row0 + rows) of the most recent logits (after a decode step
+ * row i is slot i; after a prefill with want_logits there is one row, row 0, the prefilled slot's) with scores_host [rows] uploaded,
+ * the n_cand records copied to out_host; SYNCHRONISES.  TL_ERR_INVALID with nothing changed when the rows are not inside the most
+ * recent logits (or those are a packed prefill's), or when a slot behind a row is free, parked or stopped, samples, processes its
+ * logits (penalties, bias, grammar), truncates, records log-probabilities or is armed with a stop set.  The scratch (about 5 KB) is
+ * allocated by the first call: an engine that never selects allocates nothing.
+ *
+ * tl_engine_beam_reorder: before, slots [slot0, slot0 + n_src) are live, plain (as above) and not parked, slots [slot0 + n_src, slot0 +
+ * width) are free; 1 <= n_src, width <= TL_MAX_BEAMS; parents[i] in [0, n_src), tokens[i] in [0, vocab), i < width.  After, slot
+ * slot0 + i holds the sequence slot slot0 + parents[i] held: the same context length, pending token tokens[i].  One child of every
+ * chosen parent inherits the parent's block-table row, private tail page included, as tl_engine_move does; every further child shares
+ * the full pages by reference count and gets a copy of a partial tail page (one tl_kv_copy_rows launch per copy), as tl_engine_fork
+ * does.  A parent nobody chose lets go of its pages as tl_engine_release does; sources at index >= width are released.  No spare slot
+ * is needed.  All or nothing: the pages the copies need -- the further children of parents whose tail page is partial -- are compared
+ * with the obtainable pages (free plus evictable) before anything changes; pages the unchosen parents would give back are NOT counted.
+ * Failure is TL_ERR_INVALID "KV page pool exhausted" with every slot as it was; pages_in_use + pages_free + retained pages == num_pages
+ * at every return.  The prefix-cache record and the LoRA adapter travel with the parent (moved to the inheriting child, copied to the
+ * others); the token ring and `produced` restart as after a fork -- the caller holds the hypotheses' ids.  Stream work, does not
+ * synchronise: stream order protects the tail copies. */
+#define TL_MAX_BEAMS 8
+#define TL_MAX_BEAM_CANDIDATES 32
+typedef struct tl_beam_candidate { /* 16 bytes */
+    int32_t parent; /* row of the call (beam of the group); -1: no candidate */
+    int32_t token;
+    float score;   /* scores[parent] + logprob */
+    float logprob; /* of `token` in the parent's row */
+} tl_beam_candidate;
+int tl_beam_rows(const void *logits_dev, int rows, int vocab, const float *scores_dev, int n_cand, tl_beam_candidate *out_dev, void *stream);
+int tl_engine_beam_select(tl_engine *e, int row0, int rows, const float *scores_host, int n_cand, tl_beam_candidate *out_host);
+int tl_engine_beam_reorder(tl_engine *e, int slot0, int n_src, int width, const int *parents, const int32_t *tokens);
+
 /* Run `steps` decode steps over the live slots [0, batch): each step feeds every
  * slot's pending token at position context_len, appends K/V, and leaves the next
  * token as the next pending token: the argmax, or, for a slot with a nonzero

@@ -5,7 +5,7 @@ feature exists here).
   python main.py --model <checkpoint dir or cached repo> --prompt "..." [--solution engine|ops] [--draft-model <dir>]
 
 --solution engine  fused decode engine (tl_engine_*): greedy, or speculative with --draft-model (speculative sampling with a nonzero
-                   --sampler-temp: the answer is distributed as the model's own samples)
+                   --sampler-temp: the answer is distributed as the model's own samples), or beam search with --num-beams
 --solution ops     the op-by-op Week-3 model on the HIP operators (reference call structure); supports the sampler flags
 Checkpoints are MLX-format 4-bit directories (tiny_llm_hip.load); there is no network, so --model must exist locally.
 """
@@ -66,6 +66,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --solution engine (greedy or device sampling): print each generated token with its log-probability "
                          "and its N (0-20) most likely alternatives")
     ap.add_argument("--proposal-length", type=int, default=4)
+    ap.add_argument("--num-beams", type=int, default=None, metavar="N",
+                    help="with --solution engine: beam search over N (1-8) beams, candidates ranked on the device; prints the best "
+                         "hypothesis.  Excludes the sampler, penalty, grammar, --stop, --logprobs, --lora and draft options (--stop-id ids count "
+                         "as EOS ids)")
+    ap.add_argument("--length-penalty", type=float, default=1.0,
+                    help="with --num-beams: a hypothesis scores sum of log-probabilities / length ** this")
+    ap.add_argument("--early-stopping", action="store_true", help="with --num-beams: stop as soon as N hypotheses have finished")
     ap.add_argument("--lora", default=None, metavar="DIR",
                     help="with --solution engine: run the request under the LoRA adapter in DIR (a PEFT or an mlx_lm adapter directory; "
                          "tiny_llm_hip.lora), applied on the device beside the frozen weights")
@@ -81,6 +88,32 @@ def check_truncation_flags(ap, args) -> bool:
     return args.mirostat_tau > 0 or args.sampler_min_p > 0 or (args.sampler_typical_p is not None and args.sampler_typical_p < 1)
 
 
+def check_beam_flags(ap, args) -> None:
+    """--num-beams runs plain greedy slots (tl_engine_beam_select refuses any other): what it excludes is an error before anything is loaded."""
+    if args.num_beams is None:
+        if args.length_penalty != 1.0 or args.early_stopping:
+            ap.error("--length-penalty and --early-stopping apply with --num-beams only")
+        return
+    if not 1 <= args.num_beams <= 8:
+        ap.error("--num-beams must be 1 .. 8")
+    if (2 + len(set(args.stop_id))) * args.num_beams > 32:
+        ap.error("--num-beams: (1 + number of EOS ids) * beams must not exceed 32 (the EOS id and every --stop-id count)")
+    excluded = {
+        "--solution ops": args.solution != "engine",
+        "--draft-model": args.draft_model is not None,
+        "the sampler options": bool(args.sampler_temp) or args.sampler_top_p is not None or args.sampler_top_k is not None or
+        args.sampler_seed is not None or args.sampler_min_p > 0 or args.sampler_typical_p is not None or args.mirostat_tau > 0,
+        "the penalty options": (args.repetition_penalty, args.presence_penalty, args.frequency_penalty) != (1.0, 0.0, 0.0),
+        "--regex / --json / --json-schema": bool(args.regex or args.json or args.json_schema),
+        "--stop": bool(args.stop),
+        "--logprobs": args.logprobs is not None,
+        "--lora": args.lora is not None,
+    }
+    clash = [name for name, on in excluded.items() if on]
+    if clash:
+        ap.error("--num-beams cannot be combined with " + ", ".join(clash) + ": beam slots are plain greedy slots")
+
+
 def chat_prompt(tokenizer, text: str, enable_thinking: bool) -> str:
     messages = [{"role": "system", "content": "You are a helpful assistant."}, {"role": "user", "content": text}]
     return tokenizer.apply_chat_template(messages, tokenize=False, add_generation_prompt=True,
@@ -91,6 +124,7 @@ def main(argv=None) -> str:
     ap = build_parser()
     args = ap.parse_args(argv)
     truncates = check_truncation_flags(ap, args)
+    check_beam_flags(ap, args)
     from tiny_llm_hip import load
 
     model, tokenizer = load(args.model)
@@ -115,6 +149,8 @@ def main(argv=None) -> str:
 
     ids = tokenizer.encode(prompt, add_special_tokens=False)
     pages = (len(ids) + args.max_new_tokens) // 128 + 2
+    if args.num_beams is not None:
+        return beam_search_with_engine(model, tokenizer, ids, pages, args)
     engine = DecodeEngine(model, page_size=128, num_pages=pages, max_batch=1, max_prefill_rows=4096)
     eos = tokenizer.eos_token_id
     records = None
@@ -195,6 +231,23 @@ def main(argv=None) -> str:
         text = cut_text(out, token_bytes, cut_bytes=ended.cut_bytes)
     else:
         text = tokenizer.decode(out[:-1] if ended is not None and ended.reason == "id" and out and out[-1] in args.stop_id else out)
+    print(text)
+    return text
+
+
+def beam_search_with_engine(model, tokenizer, ids, pages, args) -> str:
+    """--num-beams: the best hypothesis of tiny_llm_hip.beam.beam_search_ids (every beam may hold a tail and fresh pages of its own)."""
+    from tiny_llm_hip.beam import beam_search_ids
+    from tiny_llm_hip.engine import DecodeEngine
+
+    eos = sorted({tokenizer.eos_token_id, *args.stop_id})
+    engine = DecodeEngine(model, page_size=128, num_pages=pages * args.num_beams, max_batch=args.num_beams, max_prefill_rows=4096)
+    try:
+        best, score = beam_search_ids(engine, ids, args.num_beams, args.max_new_tokens, eos_ids=eos, length_penalty=args.length_penalty,
+                                      early_stopping=args.early_stopping)[0]
+    finally:
+        engine.close()
+    text = tokenizer.decode(best[:-1] if best and best[-1] in eos else best)
     print(text)
     return text
 

@@ -20,6 +20,7 @@
 #include "aql.h"
 #include "prefix_cache.h"
 #include "kv_copy.h"
+#include "beam.h"
 #include "kv_swap.h"
 #include "pool.h"
 #include "lora.h"
@@ -349,6 +350,12 @@ struct tl_engine {
     float2 *rope_table = nullptr, *rope_cur = nullptr;
     int rope_positions = 0;
     int logits_rows = 0;
+    int logits_slot = -1;  // whose rows the most recent logits are: -1: row i is slot i (a decode step); >= 0: that slot's (a prefill, a verification); -2: a packed prefill's
+    // beam search (tl_engine_beam_select, beam.h): the group's scores, the records of one call and the survivors between its two
+    // launches, allocated by the first call
+    DeviceBlock beam_mem;
+    float *beam_scores = nullptr;
+    tl_beam_candidate *beam_out = nullptr, *beam_survivors = nullptr;
 
     int qkv_dim() const { return (cfg.num_heads + 2 * cfg.num_kv_heads) * cfg.head_dim; }
     int q_dim() const { return cfg.num_heads * cfg.head_dim; }
@@ -2101,6 +2108,82 @@ extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
     return settings_carry(e, src, dst, true);
 }
 
+// ---- beam search (include/tinyllm_engine.h "Beam search"; the selection is beam.h, the group's genealogy slot_table.h) ----------------
+// Why the slot cannot be a beam, or null: a group decodes through the plain greedy program and selects from the raw rows
+static const char *beam_slot_refusal(const tl_engine *e, int slot) {
+    const Slot &s = e->table.slots[slot];
+    if (!s.live) return "engine_beam: slot holds no sequence";
+    if (s.parked) return "engine_beam: the slot is parked (tl_engine_unpark first)";
+    if (s.stopped) return "engine_beam: the slot has stopped";
+    if (e->smp[slot].samples()) return "engine_beam: the slot samples (beam slots are greedy)";
+    if (e->pen[slot].processes()) return "engine_beam: the slot processes its logits (penalties, bias or a grammar)";
+    if (e->trn[slot].truncates()) return "engine_beam: the slot truncates";
+    if (!e->lp_n.empty() && e->lp_n[slot] >= 0) return "engine_beam: the slot records log-probabilities";
+    if (e->stop[slot].armed) return "engine_beam: the slot is armed with a stop set";
+    return nullptr;
+}
+
+extern "C" int tl_engine_beam_select(tl_engine *e, int row0, int rows, const float *scores_host, int n_cand, tl_beam_candidate *out_host) {
+    TL_REQUIRE(e && scores_host && out_host, "engine_beam_select: null argument");
+    TL_REQUIRE(rows >= 1 && rows <= TL_MAX_BEAMS, "engine_beam_select: rows must be 1 .. 8");
+    TL_REQUIRE(n_cand >= 1 && n_cand <= TL_MAX_BEAM_CANDIDATES, "engine_beam_select: n_cand must be 1 .. 32");
+    TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_beam_select: vocabulary larger than the sampler's 524,288 tokens");
+    TL_REQUIRE(e->logits_slot != -2, "engine_beam_select: the most recent logits are a packed prefill's");
+    TL_REQUIRE(row0 >= 0 && row0 <= e->logits_rows - rows, "engine_beam_select: the rows are not inside the most recent logits");
+    TL_TRY(stop_reconcile(e));
+    for (int i = 0; i < rows; ++i) TL_TRY(table_rc(beam_slot_refusal(e, e->logits_slot >= 0 ? e->logits_slot : row0 + i)));
+    if (!e->beam_mem) {
+        Carve carve;
+        const size_t scores = carve(TL_MAX_BEAMS * sizeof(float)), out = carve(TL_MAX_BEAM_CANDIDATES * sizeof(tl_beam_candidate)),
+                     survivors = carve(BM_SURVIVORS * sizeof(tl_beam_candidate));
+        TL_TRY(e->beam_mem.alloc(carve.off, "engine_beam_select: hipMalloc(scratch) failed"));
+        e->beam_scores = e->beam_mem.at<float>(scores);
+        e->beam_out = e->beam_mem.at<tl_beam_candidate>(out);
+        e->beam_survivors = e->beam_mem.at<tl_beam_candidate>(survivors);
+        e->stats.workspace_bytes += carve.off;
+    }
+    TL_HIP(hipMemcpyAsync(e->beam_scores, scores_host, (size_t)rows * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    TL_TRY(beam_rows_launch(e->logits + (size_t)row0 * e->cfg.vocab_size, rows, e->cfg.vocab_size, e->beam_scores, n_cand, e->beam_survivors,
+                            e->beam_out, e->stream));
+    TL_HIP(hipMemcpyAsync(out_host, e->beam_out, (size_t)n_cand * sizeof(tl_beam_candidate), hipMemcpyDeviceToHost, e->stream));
+    TL_HIP(hipStreamSynchronize(e->stream));
+    return TL_OK;
+}
+
+extern "C" int tl_engine_beam_reorder(tl_engine *e, int slot0, int n_src, int width, const int *parents, const int32_t *tokens) {
+    TL_REQUIRE(e && parents && tokens, "engine_beam_reorder: null argument");
+    TL_REQUIRE(n_src >= 1 && n_src <= TL_MAX_BEAMS && width >= 1 && width <= TL_MAX_BEAMS, "engine_beam_reorder: n_src and width are 1 .. 8");
+    const int span = std::max(n_src, width);
+    TL_REQUIRE(slot0 >= 0 && slot0 <= e->cfg.max_batch - span, "engine_beam_reorder: slots out of range");
+    for (int i = 0; i < width; ++i) {
+        TL_REQUIRE(parents[i] >= 0 && parents[i] < n_src, "engine_beam_reorder: parent out of range");
+        TL_REQUIRE(tokens[i] >= 0 && tokens[i] < e->cfg.vocab_size, "engine_beam_reorder: token id out of range");
+    }
+    TL_TRY(stop_reconcile(e));
+    for (int i = 0; i < n_src; ++i) TL_TRY(table_rc(beam_slot_refusal(e, slot0 + i)));
+    TL_TRY(ensure_pool_table(e));  // (the tail copies' pool table: built by the first call that needs it, before anything changes)
+    int lora[TL_MAX_BEAMS];
+    char pending[TL_MAX_BEAMS];
+    for (int i = 0; i < n_src; ++i) lora[i] = e->lora_of[slot0 + i], pending[i] = e->gr_pending[slot0 + i];
+    SlotEdits ed;
+    Pokes pk;
+    TL_TRY(table_rc(e->table.beam_reorder(slot0, n_src, width, parents, ed)));
+    TL_TRY(apply_edits(e, ed, pk));  // the tail copies before the row entries that publish the fresh pages
+    for (int i = 0; i < span; ++i) {
+        const int slot = slot0 + i;
+        const Slot &d = e->table.slots[slot];
+        pk.emplace_back(e->live + slot, d.live ? 1 : 0);
+        pk.emplace_back(e->context_lens + slot, d.ctx);
+        pk.emplace_back(e->tokens + slot, i < width ? tokens[i] : 0);
+        if (i < width) pk.emplace_back(e->produced + slot, 0);
+        e->gr_pending[slot] = i < width ? pending[parents[i]] : 0;
+        e->emb_rows[slot] = -1;  // (a running mean does not travel, as in settings_carry)
+    }
+    TL_TRY(poke(e, pk));
+    for (int i = 0; i < span; ++i) TL_TRY(lora_write(e, slot0 + i, i < width ? lora[parents[i]] : LORA_NONE));
+    return TL_OK;
+}
+
 
 // ---- KV swap (include/tinyllm_engine.h "KV swap"; kernels kv_swap.h, host accounting slot_table.h) ------------------------------------
 static int swap_free(tl_engine *e) {
@@ -2759,6 +2842,20 @@ extern "C" int tl_logprob_rows(const void *logits_dev, int rows, int vocab, cons
     return TL_OK;
 }
 
+// (the survivors between the two launches live in a block of the call's own: its release waits for the launches)
+extern "C" int tl_beam_rows(const void *logits_dev, int rows, int vocab, const float *scores_dev, int n_cand, tl_beam_candidate *out_dev,
+                            void *stream) {
+    TL_REQUIRE(logits_dev && scores_dev && out_dev, "beam_rows: null argument");
+    TL_REQUIRE(rows >= 1 && rows <= TL_MAX_BEAMS, "beam_rows: rows must be 1 .. 8");
+    TL_REQUIRE(vocab > 0 && vocab <= SMP_MAX_VOCAB, "beam_rows: vocabulary out of range (1 .. 524,288)");
+    TL_REQUIRE(n_cand >= 1 && n_cand <= TL_MAX_BEAM_CANDIDATES, "beam_rows: n_cand must be 1 .. 32");
+    DeviceBlock survivors;
+    TL_TRY(survivors.alloc(BM_SURVIVORS * sizeof(tl_beam_candidate), "beam_rows: hipMalloc(survivors) failed"));
+    TL_TRY(beam_rows_launch(logits_dev, rows, vocab, scores_dev, n_cand, survivors.at<tl_beam_candidate>(), out_dev, (hipStream_t)stream));
+    TL_HIP(hipStreamSynchronize((hipStream_t)stream));
+    return TL_OK;
+}
+
 extern "C" int tl_pool_rows(const void *rows_dev, int hidden, int n_seqs, const int *row0, const int *len, const int *finish, const int *prior,
                             int pooling, float *sums_dev, int normalize, int dim, float *out_dev, void *stream) {
     return pool_rows((const uint16_t *)rows_dev, hidden, n_seqs, row0, len, finish, prior, nullptr, pooling, sums_dev, normalize, dim, out_dev,
@@ -3169,7 +3266,7 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
     }
     if (logits_mode == 2) {
         TL_TRY(lm_head_rows(e, e->x, n));
-        e->logits_rows = n;
+        e->logits_rows = n, e->logits_slot = slot;
         hipLaunchKernelGGL(argmax_rows_kernel, dim3(n), dim3(1024), 0, e->stream, e->logits, c.vocab_size, e->verify_ids);
         TL_CHECK_LAUNCH("engine verify argmax");
     }
@@ -3177,7 +3274,7 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
         // logits_to_keep = 1 (reference qwen3_week3.py:331-336): last row only
         const uint16_t *last = e->x + (size_t)(n - 1) * c.hidden_size;
         TL_TRY(lm_head_rows(e, last, 1));
-        e->logits_rows = 1;
+        e->logits_rows = 1, e->logits_slot = slot;
         TL_TRY(prefill_first_token(e, slot, 0, "engine prefill argmax"));
     }
     return TL_OK;
@@ -3240,7 +3337,7 @@ static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const
     }
     if (n_logits > 0) {
         TL_TRY(lm_head_rows(e, e->xn, n_logits));
-        e->logits_rows = n_logits;
+        e->logits_rows = n_logits, e->logits_slot = -2;
         int j = 0;
         for (int i = 0; i < n_seqs; ++i) {
             if (!want_logits[i]) continue;
@@ -3488,7 +3585,7 @@ static void step_done(tl_engine *e, int batch) {
     for (int b = 0; b < batch; ++b)
         if (e->slot_runs(b)) e->gr_pending[b] = 1;
     e->stats.decode_steps++;
-    e->logits_rows = batch;
+    e->logits_rows = batch, e->logits_slot = -1;
 }
 
 extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_graph) {

@@ -240,6 +240,72 @@ public:
         return nullptr;
     }
 
+    // tl_engine_beam_reorder: a beam group changes generation in place.  Before, the sources [slot0, slot0 + n_src) run (live, not parked,
+    // not stopped) and [slot0 + n_src, slot0 + width) are free; after, slot0 + i (i < width) holds the sequence slot0 + parents[i] held.
+    // One child of every chosen parent -- the one in the parent's own slot where there is one, else its first -- inherits the parent's
+    // pages as a move does, private tail and pages reserved ahead included; every further child is a fork: the full pages shared, a partial
+    // tail copied (its ctx % page_size rows).  A parent nobody chose, and a source at index >= width, lets go as a release does.  The
+    // pages the copies need are asked of the pool BEFORE anything changes, and the pages the unchosen parents give back are not counted
+    // towards them: the copies are taken while every parent still holds its pages, so a group that fits only with those pages is refused.
+    static constexpr int BEAM_MAX = 8;  // TL_MAX_BEAMS
+    const char *beam_reorder(int slot0, int n_src, int width, const int *parents, SlotEdits &ed) {
+        if (n_src < 1 || n_src > BEAM_MAX || width < 1 || width > BEAM_MAX) return "engine_beam_reorder: n_src and width are 1 .. 8";
+        const int span = std::max(n_src, width);
+        if (slot0 < 0 || slot0 > (int)slots.size() - span) return "engine_beam_reorder: slots out of range";
+        if (!parents) return "engine_beam_reorder: null parents";
+        for (int i = 0; i < n_src; ++i) {
+            TL_SLOT_TRY(check_unparked(slot0 + i));
+            if (slots[slot0 + i].stopped) return "engine_beam_reorder: a source slot has stopped";
+        }
+        for (int i = n_src; i < width; ++i)
+            if (slots[slot0 + i].live) return "engine_beam_reorder: destination slot already holds a sequence";
+        int children[BEAM_MAX] = {}, heir[BEAM_MAX];
+        for (int i = 0; i < width; ++i) {
+            if (parents[i] < 0 || parents[i] >= n_src) return "engine_beam_reorder: parent out of range";
+            if (children[parents[i]]++ == 0 || parents[i] == i) heir[parents[i]] = i;
+        }
+        size_t need = 0;
+        for (int p = 0; p < n_src; ++p)
+            if (children[p] > 1 && slots[slot0 + p].ctx % page_size != 0) need += (size_t)children[p] - 1;
+        if (!pool.can_take(need)) return "engine_beam_reorder: KV page pool exhausted";
+        const std::vector<Slot> old(slots.begin() + slot0, slots.begin() + slot0 + span);
+        std::vector<Slot> now(span);
+        for (int i = 0; i < width; ++i) {
+            const Slot &s = old[parents[i]];
+            Slot &d = now[i];
+            if (heir[parents[i]] == i) {
+                d = s;
+            } else {
+                const int full = s.ctx / page_size;
+                for (int j = 0; j < full; ++j) {
+                    pool.share(s.pages[j]);
+                    d.pages.push_back(s.pages[j]);
+                }
+                if (s.ctx % page_size != 0) {
+                    d.pages.push_back(take(ed));
+                    ed.copies.push_back({s.pages[full], d.pages.back(), s.ctx % page_size});
+                }
+                d.live = true;
+                d.ctx = s.ctx;
+                d.rec = s.rec;
+            }
+            d.produced = 0;
+        }
+        for (int p = 0; p < n_src; ++p)
+            if (children[p] == 0)
+                for (int id : old[p].pages) pool.drop(id);
+        for (int i = width; i < span; ++i) now[i].produced = old[i].produced;  // (as after a release: the ids it produced stay readable)
+        for (int i = 0; i < span; ++i) {
+            const std::vector<int> &was = old[i].pages, &is = now[i].pages;
+            for (size_t j = 0; j < std::max(was.size(), is.size()); ++j) {
+                const int a = j < was.size() ? was[j] : -1, b = j < is.size() ? is[j] : -1;
+                if (a != b) ed.rows.push_back({slot0 + i, (int)j, b});
+            }
+            slots[slot0 + i] = std::move(now[i]);
+        }
+        return nullptr;
+    }
+
     // the sequence, parked or not, changes slots: pages or records change hands, no K/V byte moves
     const char *move(int src, int dst, SlotEdits &ed) {
         TL_SLOT_TRY(check(src, true));

@@ -132,6 +132,15 @@ class TlTokenLogprob(ctypes.Structure):
                 ("top_logprobs", ctypes.c_float * TL_MAX_TOP_LOGPROBS)]
 
 
+TL_MAX_BEAMS = 8
+TL_MAX_BEAM_CANDIDATES = 32
+
+
+class TlBeamCandidate(ctypes.Structure):
+    """tl_beam_candidate (include/tinyllm_engine.h "Beam search"): parent -1 / token -1 / -inf / -inf past the rankable pairs."""
+    _fields_ = [("parent", ctypes.c_int32), ("token", ctypes.c_int32), ("score", ctypes.c_float), ("logprob", ctypes.c_float)]
+
+
 class TlLinearInfo(ctypes.Structure):
     _fields_ = [("kernel", _c_int), ("launches", _c_int), ("rows_per_pass", _c_int), ("p", _c_int * 5)]
 
@@ -290,6 +299,9 @@ _SIGNATURES.update({
     "tl_engine_read_pending_logprobs": (_c_int, [_c_void_p, _c_int, _P(TlTokenLogprob)]),
     "tl_engine_score": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, ctypes.c_int32, _P(_c_float), _P(ctypes.c_int32)]),
     "tl_logprob_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "tl_beam_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p]),
+    "tl_engine_beam_select": (_c_int, [_c_void_p, _c_int, _c_int, _P(_c_float), _c_int, _P(TlBeamCandidate)]),
+    "tl_engine_beam_reorder": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _P(ctypes.c_int), _P(ctypes.c_int32)]),
     "tl_engine_embed_packed": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int), _P(ctypes.c_int32), _P(ctypes.c_int), _P(ctypes.c_int), _c_int, _c_int,
                                         _c_int, _P(_c_float)]),
     "tl_engine_embed": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _c_int, _c_int, _c_int, _c_int, _P(_c_float)]),
@@ -1114,6 +1126,28 @@ def logprob_rows(logits: torch.Tensor, ids=None, top_n: int = 0):
     check(_lib.tl_logprob_rows(logits.data_ptr(), rows, logits.shape[1], ids_t.data_ptr() if ids_t is not None else None, top_n,
                                lp.data_ptr(), top_ids.data_ptr() if top_n else None, top_lp.data_ptr() if top_n else None, _stream()))
     return lp, top_ids, top_lp
+
+
+def beam_rows(logits: torch.Tensor, scores, n_cand: int) -> list[tuple[int, int, float, float]]:
+    """The decode engine's beam-search selection (tl_beam_rows) over 1 .. 8 rows of bf16 logits [rows, vocab] with one cumulative
+    log-probability per row: the best ``n_cand`` (1 .. 32) (parent, token, score, logprob), best first; (-1, -1, -inf, -inf) past the
+    rankable pairs.  Synchronises."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("beam_rows takes a [rows, vocab] bf16 tensor on the GPU")
+    if isinstance(n_cand, bool) or not isinstance(n_cand, int) or not 1 <= n_cand <= TL_MAX_BEAM_CANDIDATES:
+        raise ValueError(f"n_cand must be an int in [1, {TL_MAX_BEAM_CANDIDATES}], got {n_cand!r}")
+    logits = logits.contiguous()
+    rows, dev = logits.shape[0], logits.device
+    if not 1 <= rows <= TL_MAX_BEAMS:
+        raise ValueError(f"beam_rows takes between 1 and {TL_MAX_BEAMS} rows")
+    scores_t = torch.as_tensor(scores, dtype=torch.float32).reshape(-1).contiguous().to(dev)
+    if scores_t.numel() != rows:
+        raise ValueError("scores needs one value per row")
+    out = torch.empty(n_cand * 4, dtype=torch.int32, device=dev)
+    check(_lib.tl_beam_rows(logits.data_ptr(), rows, logits.shape[1], scores_t.data_ptr(), n_cand, out.data_ptr(), _stream()))
+    words = out.cpu()
+    ints, floats = words.view(-1, 4), words.view(torch.float32).view(-1, 4)
+    return [(int(ints[i, 0]), int(ints[i, 1]), float(floats[i, 2]), float(floats[i, 3])) for i in range(n_cand)]
 
 
 POOL_LAST, POOL_MEAN = 0, 1  # TL_POOL_LAST / TL_POOL_MEAN

@@ -217,6 +217,34 @@ class DecodeEngine:
         if src in held:
             held[dst] = held[src]
 
+    # -- beam search (tl_engine_beam_*; include/tinyllm_engine.h "Beam search"; the policy is beam.py) --------
+    def beam_select(self, row0: int, rows: int, scores: Sequence[float], n_cand: int) -> list[tuple[int, int, float, float]]:
+        """The best ``n_cand`` (1 .. 32) continuations of the beams behind rows [row0, row0 + rows) of the most recent logits (after a
+        decode step row i is slot i; after a prefill there is row 0), ranked on the device: ``scores`` are the beams' cumulative
+        log-probabilities, the result (parent, token, score, logprob) tuples, best first, (-1, -1, -inf, -inf) past the rankable
+        pairs.  The slots must be plain greedy ones.  Synchronises."""
+        scores = [float(s) for s in scores]
+        if len(scores) != rows:
+            raise ValueError("beam_select needs one score per row")
+        if isinstance(n_cand, bool) or not isinstance(n_cand, int) or not 1 <= n_cand <= _ext.TL_MAX_BEAM_CANDIDATES:
+            raise ValueError(f"n_cand must be an int in [1, {_ext.TL_MAX_BEAM_CANDIDATES}], got {n_cand!r}")
+        arr = (ctypes.c_float * max(rows, 1))(*scores)
+        out = (_ext.TlBeamCandidate * n_cand)()
+        _ext.check(_lib.tl_engine_beam_select(self._h, row0, rows, arr, n_cand, out))
+        return [(c.parent, c.token, c.score, c.logprob) for c in out]
+
+    def beam_reorder(self, slot0: int, n_src: int, parents: Sequence[int], tokens: Sequence[int]) -> None:
+        """The beam group in slots [slot0, slot0 + n_src) becomes its next generation in place: slot ``slot0 + i`` continues the
+        sequence of slot ``slot0 + parents[i]`` with pending token ``tokens[i]``, for i < len(parents) (the new width; slots between
+        n_src and the width must be free, sources past the width are released).  Parents nobody chose are released; shared prefixes
+        stay shared, a partial tail page is copied for every further child.  All or nothing.  Does not synchronise."""
+        parents, tokens = [int(p) for p in parents], [int(t) for t in tokens]
+        if len(parents) != len(tokens) or not parents:
+            raise ValueError("beam_reorder needs one token per parent and at least one")
+        arr_p = (ctypes.c_int * len(parents))(*parents)
+        arr_t = (ctypes.c_int32 * len(tokens))(*tokens)
+        _ext.check(_lib.tl_engine_beam_reorder(self._h, slot0, n_src, len(parents), arr_p, arr_t))
+
     # -- prefix cache (tl_engine_prefix_*; include/tinyllm_engine.h "Prefix cache") --------------------------
     def prefix_attach(self, slot: int, tokens: Sequence[int]) -> int:
         """Give the freshly begun ``slot`` the cached K / V of the longest known prefix of ``tokens`` (at most len(tokens) - 1 of them:
