@@ -2,6 +2,7 @@
 """Continuous-batching CLI over the fused engine (counterpart of the reference batch-main.py:62-101).
 
   python batch_main.py --model <checkpoint dir> [--batch-size 5] [--prefill-step 128] [--max-seq-len 512] [--prompts-file f] [--prefix-cache [PAGES]] [--swap-pages N]
+                       [--draft-model <checkpoint dir> [--proposal-length 4]]
 """
 import argparse
 import sys
@@ -61,7 +62,30 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lora-assign", default="round-robin", choices=["round-robin", "first"],
                     help="which request runs under which adapter: round-robin = request i under adapter i mod n; first = request 0 under "
                          "the first adapter, every other request on the base model")
+    ap.add_argument("--draft-model", default=None, metavar="DIR",
+                    help="greedy speculative decoding in batch: the checkpoint in DIR proposes for every request, the model verifies all of "
+                         "them in one pass per round (tiny_llm_hip.engine.batch_speculative_generate_ids); the answers are the same ids")
+    ap.add_argument("--proposal-length", type=int, default=4, help="tokens the draft model proposes per request and round (1 .. 7)")
     return ap
+
+
+def check_draft_flags(ap: argparse.ArgumentParser, args, truncates: bool) -> None:
+    """--draft-model verifies raw logits greedily, one adapter-free model: refuse every flag that would not apply."""
+    if not args.draft_model:
+        return
+    clashes = [name for name, on in (
+        ("--sampler-temp / --sampler-top-p / --sampler-top-k", bool(args.sampler_temp) or args.sampler_top_p is not None or args.sampler_top_k is not None),
+        ("--sampler-min-p / --sampler-typical-p / --mirostat-tau", truncates),
+        ("--repetition-penalty / --presence-penalty / --frequency-penalty",
+         (args.repetition_penalty, args.presence_penalty, args.frequency_penalty) != (1.0, 0.0, 0.0)),
+        ("--regex / --json / --json-schema", bool(args.regex or args.json or args.json_schema)),
+        ("--stop / --stop-id", bool(args.stop or args.stop_id)),
+        ("--lora", bool(args.lora)),
+    ) if on]
+    if clashes:
+        ap.error("--draft-model runs greedy speculative decoding over the raw logits of one model; it does not combine with " + ", ".join(clashes))
+    if not 1 <= args.proposal_length <= 7:
+        ap.error("--proposal-length must be between 1 and 7 (8 verification rows per request)")
 
 
 def main(argv=None):
@@ -70,9 +94,10 @@ def main(argv=None):
     from main import check_truncation_flags
 
     truncates = check_truncation_flags(ap, args)
+    check_draft_flags(ap, args, truncates)
 
     from tiny_llm_hip import load
-    from tiny_llm_hip.engine import DecodeEngine, batch_generate_ids
+    from tiny_llm_hip.engine import DecodeEngine, batch_generate_ids, batch_speculative_generate_ids
     from main import chat_prompt
 
     model, tokenizer = load(args.model)
@@ -113,7 +138,19 @@ def main(argv=None):
 
         stop, token_bytes = cli_stop_set(engine, tokenizer, args.stop, args.stop_id, sorted(i for i in stops if i is not None))
         stops |= set(args.stop_id)
-        if stop is not None:  # the device ends every request: at a stop string, a stop id (the EOS ids among them) or its budget
+        if args.draft_model:
+            draft_model, draft_tok = load(args.draft_model)
+            if draft_tok.get_vocab() != tokenizer.get_vocab():
+                raise ValueError("draft and target tokenizers use different token ids")
+            draft = DecodeEngine(draft_model, page_size=128, num_pages=pages_per_seq * (args.batch_size + 1) + 2,
+                                 max_batch=args.batch_size + 1, max_prefill_rows=args.prefill_step)
+            try:
+                answers = batch_speculative_generate_ids(engine, draft, encoded, limits, proposal_length=args.proposal_length,
+                                                         eos_token_id=tokenizer.eos_token_id)
+            finally:
+                draft.close()
+            done = list(enumerate(answers))
+        elif stop is not None:  # the device ends every request: at a stop string, a stop id (the EOS ids among them) or its budget
             done = batch_generate_ids(engine, encoded, limits, batch_size=args.batch_size, prefill_step=args.prefill_step,
                                       sampling=sampling or None, base_seed=args.sampler_seed, stop=stop)
         else:

@@ -330,6 +330,31 @@ int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, int n, int32
 int tl_engine_verify_sampled(tl_engine *e, int slot, const int32_t *tokens, int n, const void *draft_logits_dev, float draft_temperature,
                              int draft_top_k, float draft_top_p, int32_t *out_ids, int *out_count);
 
+/* Batched speculative verification (csrc/verify_attn.h): up to 8 tokens for each of n_seqs >= 1 slots in ONE pass
+ * over the decode route, acceptance decided on the device.  `tokens` holds the chunks back to back as tl_engine_prefill_packed takes
+ * them; lens[i] is 1..8, their sum at most 64, no slot twice.  Sequence i appends its n = lens[i] tokens exactly like tl_engine_verify
+ * (the first is the pending token, the others the proposals).  With g[j] the greedy id behind row j (the lower id of a tie, never a
+ * NaN) and a the first j < n - 1 with g[j] != tokens[j + 1] (n - 1 when there is none): out[i].count = a + 1 and out[i].ids[0..a] =
+ * g[0..a] (the accepted proposals, then the correction or the bonus token); the other ids are -1.  Nothing is recorded as generated.
+ *   commit == 0   the caller rewinds n - 1 - a tokens and sets the next input itself, as after tl_engine_verify;
+ *   commit != 0   the call rewinds every slot by n - 1 - a and sets ids[a] as its pending token before it returns, by the paths of
+ *                 tl_engine_rewind and tl_engine_set_token (copy of a shared tail page, known tokens and page accounting as there).
+ * The pass is eager on the engine stream: per layer the projections over all rows at once on the shared-buffer decode route (the GEMV up
+ * to 4 rows, the batched matmuls from 5) and one attention stage for all sequences; its own logits block, so the rows of the last decode
+ * step or verification stay where they were.  All or nothing: every check -- slot state, the pages the chunks (and, with commit, the
+ * copy of a tail page a rewind may need) ask of the pool, token range -- is made before anything is reserved or written.  Refuses
+ * (TL_ERR_INVALID) what tl_engine_verify refuses -- parked or stopped slots, slots that sample, slots that process their logits -- a
+ * slot that carries a LoRA adapter, head_dim != 128, and a model with MoE layers when the rows exceed max(max_batch, max_prefill_rows).
+ * FP8 KV pages and MoE layers are supported.  Out of scope: speculative SAMPLING in batch (a follow-up can run tl_spec_sample_rows over
+ * the same rows), adapters, and captured or AQL replay of the pass.  The scratch (activations, logits and matmul workspace for 64 rows,
+ * descriptors, results) is allocated by the first call and counted in stats.workspace_bytes.  Synchronises once. */
+typedef struct tl_verify_result {
+    int32_t count;
+    int32_t ids[8];
+} tl_verify_result;
+int tl_engine_verify_batch(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, int commit,
+                           tl_verify_result *out);
+
 /* Set the pending input token of a slot explicitly (e.g. sampled on the host). */
 int tl_engine_set_token(tl_engine *e, int slot, int32_t token);
 
@@ -1073,6 +1098,22 @@ int tl_mirostat_update_rows(const void *filtered_dev, int rows, int vocab, const
 int tl_process_logits(const void *logits_dev, int rows, int vocab, const uint16_t *history_dev, const float *repetition_dev,
                       const float *presence_dev, const float *frequency_dev, const int32_t *bias_ids_dev, const float *bias_values_dev,
                       const int32_t *bias_n_dev, void *out_dev, void *stream);
+
+/* The attention stage of tl_engine_verify_batch over caller pools (csrc/verify_attn.h): qkv_dev [R, (Hq + 2 Hkv) * 128] bf16, the rows
+ * of n_seqs (1 .. 64) sequences back to back; sequence i (host arrays) holds lens[i] (1 .. 8) rows at positions starts[i] .. of
+ * block-table row slots[i] (R = sum of lens <= 64).  Per-head RMSNorm of q and k, RoPE, K and V appended to the pages the block table
+ * names (key_scales_dev / value_scales_dev not NULL: FP8 pages, kv8.h; NULL: bf16), then row j of sequence i attends to its first
+ * starts[i] + j + 1 tokens -> out_dev [R, Hq * 128] bf16, row-major.  head_dim 128.  The workspace is internal; *info (may be NULL)
+ * reports the split plan used.  Stream ordered (returns after the stream has run the stage); bad input is TL_ERR_INVALID. */
+int tl_verify_attention_rows(const void *qkv_dev, const void *q_norm_dev, const void *k_norm_dev, void *key_pages_dev, void *value_pages_dev,
+                             float *key_scales_dev, float *value_scales_dev, const int32_t *block_table_dev, int n_seqs, const int *slots,
+                             const int *starts, const int *lens, void *out_dev, int num_heads, int num_kv_heads, int page_size, int max_pages,
+                             float rope_theta, float eps, void *stream, tl_attention_info *info);
+/* The acceptance stage over caller rows: logits_dev [R, vocab] bf16; sequence i (host arrays) owns the rows [row0[i], row0[i] + lens[i]),
+ * lens[i] 1 .. 8, every row below 64; tokens_dev [R] int32 the tokens the rows were fed -> out_dev [n_seqs] as tl_engine_verify_batch
+ * defines them.  Stream ordered (returns after the stream has run it); bad input is TL_ERR_INVALID. */
+int tl_verify_accept_rows(const void *logits_dev, int vocab, int n_seqs, const int *row0, const int *lens, const int32_t *tokens_dev,
+                          tl_verify_result *out_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -880,6 +880,8 @@ static int pick_splits(int B, int Hkv, int row_chunks, int max_ctx) {
     s = std::min(s, 64);
     return std::max(s, 1);
 }
+// ... for the batched verification pass (verify_attn.h), which splits its contexts by the same rule
+int paged_decode_splits(int B, int Hkv, int row_chunks, int max_ctx) { return pick_splits(B, Hkv, row_chunks, max_ctx); }
 
 }  // namespace tl
 

@@ -27,6 +27,7 @@
 #include "slot_table.h"
 #include "stop.h"
 #include "stop_set.h"
+#include "verify_attn_host.h"  // the launches of the batched verification (their kernels: verify_attn.h, compiled by verify_attn.hip)
 
 namespace tl {
 
@@ -356,6 +357,22 @@ struct tl_engine {
     DeviceBlock beam_mem;
     float *beam_scores = nullptr;
     tl_beam_candidate *beam_out = nullptr, *beam_survivors = nullptr;
+    // batched verification (tl_engine_verify_batch, verify_attn.h): everything the pass touches besides the weights, the KV pools and
+    // the slot state, allocated by the first call -- the activations of 64 rows, their logits, the matmul workspace a 64-row M needs
+    // (the engine's own is sized for max(max_batch, max_prefill_rows) rows), the attention partials, the descriptors of one call
+    // (uploaded in one copy) and its results
+    struct VerifyScratch {
+        enum { TOKENS, ROW_SLOT, ROW_POS, SEQ_SLOT, SEQ_ROW0, SEQ_LEN, SEQ_CTX, DESC_ARRAYS };  // the arrays of `desc`, 64 words each
+        DeviceBlock mem;
+        uint16_t *x = nullptr, *h = nullptr, *xn = nullptr, *qkv = nullptr, *q = nullptr, *attn = nullptr, *act = nullptr, *gu = nullptr,
+                 *tmp = nullptr, *logits = nullptr;
+        float *ss_x = nullptr, *ss_h = nullptr, *attn_ws = nullptr;
+        void *splitk_ws = nullptr;
+        size_t splitk_ws_bytes = 0, attn_ws_rows = 0;
+        int32_t *desc = nullptr, *greedy = nullptr;
+        tl_verify_result *results = nullptr;
+        const int32_t *arr(int which) const { return desc + which * 64; }
+    } vb;
 
     int qkv_dim() const { return (cfg.num_heads + 2 * cfg.num_kv_heads) * cfg.head_dim; }
     int q_dim() const { return cfg.num_heads * cfg.head_dim; }
@@ -3524,6 +3541,227 @@ extern "C" int tl_engine_verify_sampled(tl_engine *e, int slot, const int32_t *t
     while (a < n - 1 && r.accept[a]) out_ids[a] = tokens[a + 1], ++a;
     out_ids[a] = r.alt[a];
     *out_count = a + 1;
+    return TL_OK;
+}
+
+// ---- batched verification (include/tinyllm_engine.h "tl_engine_verify_batch"; the kernels are verify_attn.h) --------------------------
+// the scratch of the pass, allocated by the first call
+static int verify_alloc(tl_engine *e) {
+    using V = tl_engine::VerifyScratch;
+    V &v = e->vb;
+    if (v.desc) return TL_OK;
+    const tl_engine_config &c = e->cfg;
+    const size_t R = VA_MAX_ROWS, H = (size_t)c.hidden_size;
+    // the matmul workspace of 1 .. 64 rows, as tl_engine_create sizes the engine's own for its rows: only where that one is too small
+    size_t need = 0;
+    {
+        const tl_layer_weights *dense = &e->layers[0];
+        for (const auto &l : e->layers)
+            if (l.wgu.weight_dev) {
+                dense = &l;
+                break;
+            }
+        std::vector<tl_w4> mats = {e->layers[0].wqkv, e->layers[0].wo, dense->wgu, dense->wdown, e->head()};
+        for (int l = 0; l < c.num_layers; ++l)
+            if (e->is_moe(l)) mats.push_back(e->moe[l].router);
+        for (const tl_w4 &w : mats) {
+            if (!w.weight_dev) continue;
+            for (int M = 1; M <= VA_MAX_ROWS; ++M) {
+                const Qmm3Plan p3 = qmm3_plan(M, w.cols, w.rows);
+                if (p3.ok) need = std::max(need, p3.partial_bytes);
+                need = std::max(need, tl_quantized_matmul_workspace_bytes(M, w.cols, w.rows, TL_BF16, 1, 1));
+            }
+        }
+    }
+    const bool own_ws = need > e->lin.splitk_ws_bytes;
+    const size_t ss_per_row = (size_t)std::max(QM3_SS, c.hidden_size / 16 + 1);
+    const size_t ws_rows = verify_ws_rows(c.num_heads);
+    Carve carve;
+    const size_t o_x = carve(R * H * 2), o_h = carve(R * H * 2), o_xn = carve(R * H * 2), o_tmp = carve(R * H * 2);
+    const size_t o_qkv = carve(R * e->qkv_dim() * 2), o_q = carve(R * e->q_dim() * 2), o_attn = carve(R * e->q_dim() * 2);
+    const size_t o_gu = carve(R * 2 * c.intermediate_size * 2), o_act = carve(R * c.intermediate_size * 2);
+    const size_t o_log = carve(R * c.vocab_size * 2);
+    const size_t o_ssx = carve(R * ss_per_row * 4), o_ssh = carve(R * ss_per_row * 4);
+    const size_t o_aws = carve(ws_rows * (VA_D + 2) * 4);
+    const size_t o_desc = carve((size_t)V::DESC_ARRAYS * 64 * 4), o_greedy = carve(R * 4), o_res = carve(R * sizeof(tl_verify_result));
+    const size_t o_ws = own_ws ? carve(need) : 0;
+    TL_TRY(v.mem.alloc(carve.off, "engine_verify_batch: hipMalloc(scratch) failed"));
+    char *A = v.mem.at();
+    v.x = (uint16_t *)(A + o_x), v.h = (uint16_t *)(A + o_h), v.xn = (uint16_t *)(A + o_xn), v.tmp = (uint16_t *)(A + o_tmp);
+    v.qkv = (uint16_t *)(A + o_qkv), v.q = (uint16_t *)(A + o_q), v.attn = (uint16_t *)(A + o_attn);
+    v.gu = (uint16_t *)(A + o_gu), v.act = (uint16_t *)(A + o_act), v.logits = (uint16_t *)(A + o_log);
+    v.ss_x = (float *)(A + o_ssx), v.ss_h = (float *)(A + o_ssh), v.attn_ws = (float *)(A + o_aws), v.attn_ws_rows = ws_rows;
+    v.greedy = (int32_t *)(A + o_greedy), v.results = (tl_verify_result *)(A + o_res);
+    v.splitk_ws = own_ws ? (void *)(A + o_ws) : e->lin.splitk_ws;
+    v.splitk_ws_bytes = own_ws ? need : e->lin.splitk_ws_bytes;
+    v.desc = (int32_t *)(A + o_desc);
+    e->stats.workspace_bytes += carve.off;
+    return TL_OK;
+}
+
+// The checks of a batched verification, all before anything is reserved or allocated (packed_seqs is the model), and its sequences.
+static int verify_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, bool commit, std::vector<PrefillSeq> &seqs) {
+    const tl_engine_config &c = e->cfg;
+    const std::string w = "engine_verify_batch: ";
+    TL_REQUIRE(n_seqs >= 1 && n_seqs <= VA_MAX_ROWS, w + "between 1 and 64 sequences per call");
+    TL_REQUIRE(c.head_dim == VA_D, w + "head_dim 128");
+    int total = 0;
+    for (int i = 0; i < n_seqs; ++i) {
+        TL_REQUIRE(lens[i] >= 1 && lens[i] <= VA_MAX_LEN, w + "between 1 and 8 tokens per sequence");
+        total += lens[i];
+    }
+    TL_REQUIRE(total <= VA_MAX_ROWS, w + "the chunks together exceed 64 rows");
+    bool moe = false;
+    for (int l = 0; l < c.num_layers; ++l) moe |= e->is_moe(l);
+    TL_REQUIRE(!moe || total <= e->rows_cap, w + "a model with MoE layers takes at most max(max_batch, max_prefill_rows) rows (the experts' workspace)");
+    size_t extra_pages = 0;
+    for (int i = 0; i < n_seqs; ++i) {
+        const int slot = slots[i];
+        TL_TRY(slot_check_feeds(e, slot));
+        for (int j = 0; j < i; ++j) TL_REQUIRE(slots[j] != slot, w + "a slot appears twice");
+        TL_REQUIRE(!e->smp[slot].samples(), w + "a slot samples (verification is greedy; set temperature 0 first)");
+        TL_REQUIRE(!e->pen[slot].processes(), w + "a slot processes its logits (verification takes the raw rows; make it neutral first)");
+        TL_REQUIRE(!e->trn[slot].mirostat(), w + "a slot has Mirostat on (switch it off first)");
+        TL_REQUIRE(!e->lora_slot(slot), w + "a slot carries a LoRA adapter (adapters are verified one slot at a time, tl_engine_verify)");
+        const Slot &s = e->table.slots[slot];
+        const int need = (s.ctx + lens[i] + c.page_size - 1) / c.page_size;
+        TL_REQUIRE(need <= c.max_pages_per_seq, "engine: sequence exceeds max_pages_per_seq * page_size tokens");
+        if (need > (int)s.pages.size()) extra_pages += (size_t)need - s.pages.size();
+        // commit: a rewind into a page this chunk filled copies it when the prefix index has taken it (SlotTable::rewind)
+        if (commit && lens[i] > 1 && e->table.pool.enabled && (s.ctx + lens[i]) / c.page_size > s.ctx / c.page_size) extra_pages += 1;
+    }
+    TL_REQUIRE(e->table.pool.can_take(extra_pages), "engine: KV page pool exhausted");
+    for (int i = 0; i < total; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < c.vocab_size, w + "token id out of range");
+    seqs.resize(n_seqs);
+    int rows = 0;
+    for (int i = 0; i < n_seqs; ++i) {
+        seqs[i] = {slots[i], e->table.slots[slots[i]].ctx, rows, lens[i]};
+        rows += lens[i];
+    }
+    return TL_OK;
+}
+
+// The pass over the `total` rows of the chunks in `seqs`, eager on the engine stream: pages reserved, tokens and descriptors uploaded in
+// one copy, the rows embedded, then every layer on the shared-buffer decode route over the scratch's own buffers -- the projections
+// through engine_linear with M = total (the sums of squares handed over where ProjResult says they were left, nothing weighted, no
+// per-layer buffer), the attention stage of verify_attn.h in between -- the lm_head over all rows into the scratch's logits and the
+// acceptance launches.  The slots end the pass as prefill_pass leaves them; e->logits and its owner stay as they were.
+static int verify_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const int32_t *tokens, int total) {
+    using V = tl_engine::VerifyScratch;
+    const tl_engine_config &c = e->cfg;
+    V &v = e->vb;
+    TL_TRY(aql_drain(e));
+    SlotEdits ed;
+    Pokes pk;
+    for (int i = 0; i < n_seqs; ++i) TL_TRY(table_rc(e->table.reserve(seqs[i].slot, seqs[i].start + seqs[i].len, ed)));
+    TL_TRY(apply_edits(e, ed, pk));
+    TL_TRY(poke(e, pk));
+    int32_t desc[V::DESC_ARRAYS * 64] = {};
+    int max_len = 1, max_ctx = 1;
+    for (int i = 0; i < n_seqs; ++i) {
+        const PrefillSeq &s = seqs[i];
+        desc[V::SEQ_SLOT * 64 + i] = s.slot, desc[V::SEQ_ROW0 * 64 + i] = s.row0, desc[V::SEQ_LEN * 64 + i] = s.len;
+        desc[V::SEQ_CTX * 64 + i] = s.start + s.len;
+        for (int j = 0; j < s.len; ++j) {
+            desc[V::TOKENS * 64 + s.row0 + j] = tokens[s.row0 + j];
+            desc[V::ROW_SLOT * 64 + s.row0 + j] = s.slot, desc[V::ROW_POS * 64 + s.row0 + j] = s.start + j;
+        }
+        max_len = std::max(max_len, s.len), max_ctx = std::max(max_ctx, s.start + s.len);
+    }
+    TL_HIP(hipMemcpyAsync(v.desc, desc, sizeof(desc), hipMemcpyHostToDevice, e->stream));
+    const VerifySplit sp = verify_pick_splits(n_seqs, c.num_heads, c.num_kv_heads, total, max_len, max_ctx, v.attn_ws_rows);
+
+    TL_TRY(tl_quantized_embedding(v.arr(V::TOKENS), 0, e->embed.scales_dev, e->embed.biases_dev, e->embed.weight_dev, v.x, total, c.hidden_size,
+                                  c.vocab_size, 128, 4, TL_BF16, e->stream));
+    // the router's scratch for the duration of the pass: the RMSNorm rows, the unfused epilogues' rows and the matmul workspace of 64 rows
+    // (the engine's own go back when the pass returns, however it returns: captured steps hold those addresses)
+    struct CtxScratch {
+        LinearCtx &ctx;
+        uint16_t *xn, *gu, *tmp;
+        void *ws;
+        size_t ws_bytes;
+        CtxScratch(LinearCtx &c_, const V &v_) : ctx(c_), xn(c_.xn), gu(c_.gu), tmp(c_.tmp), ws(c_.splitk_ws), ws_bytes(c_.splitk_ws_bytes) {
+            c_.xn = v_.xn, c_.gu = v_.gu, c_.tmp = v_.tmp, c_.splitk_ws = v_.splitk_ws, c_.splitk_ws_bytes = v_.splitk_ws_bytes;
+        }
+        ~CtxScratch() { ctx.xn = xn, ctx.gu = gu, ctx.tmp = tmp, ctx.splitk_ws = ws, ctx.splitk_ws_bytes = ws_bytes; }
+    } scratch(e->lin, v);
+    LinearCtx &ctx = e->lin;
+    const bool kv8 = e->kv_format == TL_KV_FP8_E4M3;
+    int x_ss = 0;  // partials per row in ss_x (0 = none): whatever the last writer of x left
+    for (int l = 0; l < c.num_layers; ++l) {
+        const tl_layer_weights &w = e->layers[l];
+        ProjResult r;
+        Proj p = proj(w.wqkv, v.x, v.qkv, total);
+        p.pro = PRO_RMSNORM, p.norm_w = w.input_norm_dev, p.ss_in = x_ss ? v.ss_x : nullptr, p.ss_in_n = x_ss;
+        TL_TRY(engine_linear(ctx, p));
+        VerifyRowsArgs q{};
+        q.qkv = v.qkv, q.q_norm_w = (const uint16_t *)w.q_norm_dev, q.k_norm_w = (const uint16_t *)w.k_norm_dev, q.q = v.q;
+        q.key_pages = e->layer_k(l), q.value_pages = e->layer_v(l), q.key_scales = e->layer_ks(l), q.value_scales = e->layer_vs(l);
+        q.block_table = e->block_table, q.row_slot = v.arr(V::ROW_SLOT), q.row_pos = v.arr(V::ROW_POS);
+        q.page_size = c.page_size, q.max_pages = c.max_pages_per_seq, q.num_heads = c.num_heads, q.num_kv_heads = c.num_kv_heads;
+        q.eps = c.rms_norm_eps, q.rope_base = c.rope_theta;
+        VerifyAttnArgs a{};
+        a.q = v.q, a.key_pages = q.key_pages, a.value_pages = q.value_pages, a.key_scales = q.key_scales, a.value_scales = q.value_scales;
+        a.block_table = e->block_table, a.seq_slot = v.arr(V::SEQ_SLOT), a.seq_row0 = v.arr(V::SEQ_ROW0), a.seq_len = v.arr(V::SEQ_LEN);
+        a.seq_ctx = v.arr(V::SEQ_CTX), a.out = v.attn, a.ws = v.attn_ws;
+        a.page_size = c.page_size, a.max_pages = c.max_pages_per_seq, a.num_heads = c.num_heads, a.num_kv_heads = c.num_kv_heads;
+        a.scale = 1.0f / sqrtf((float)c.head_dim);
+        TL_TRY(launch_verify_attention(q, a, sp, total, n_seqs, kv8, e->stream));
+        Proj po = proj(w.wo, v.attn, v.h, total);
+        po.epi = EPI_RESIDUAL, po.residual = v.x, po.kind = 1;
+        if (e->is_moe(l)) {  // wo + residual, then the MoE MLP as its own launches (no producer-side sums for the next layer)
+            TL_TRY(engine_linear(ctx, po));
+            TL_TRY(tl_rms_norm(v.h, w.post_norm_dev, v.xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
+            TL_TRY(engine_moe_mlp(e, l, v.xn, v.h, v.x, total, nullptr));
+            x_ss = 0;
+            continue;
+        }
+        TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
+        po.ss_out = v.ss_h;
+        TL_TRY(engine_linear(ctx, po, nullptr, &r));
+        const int h_ss = r.ss_n;
+        Proj pg = proj(w.wgu, v.h, v.act, total);
+        pg.pro = PRO_RMSNORM, pg.norm_w = w.post_norm_dev, pg.epi = EPI_SWIGLU, pg.kind = 2, pg.ss_in = h_ss ? v.ss_h : nullptr, pg.ss_in_n = h_ss;
+        TL_TRY(engine_linear(ctx, pg));
+        Proj pd = proj(w.wdown, v.act, v.x, total);
+        pd.epi = EPI_RESIDUAL, pd.residual = v.h, pd.kind = 3, pd.ss_out = v.ss_x;
+        TL_TRY(engine_linear(ctx, pd, nullptr, &r));
+        x_ss = r.ss_n;
+    }
+    Proj ph = proj(e->head(), v.x, v.logits, total);
+    ph.pro = PRO_RMSNORM, ph.norm_w = e->final_norm, ph.kind = 4, ph.ss_in = x_ss ? v.ss_x : nullptr, ph.ss_in_n = x_ss;
+    TL_TRY(engine_linear(ctx, ph));
+    TL_TRY(launch_verify_accept(v.logits, c.vocab_size, total, n_seqs, v.arr(V::TOKENS), v.arr(V::SEQ_ROW0), v.arr(V::SEQ_LEN), v.greedy, v.results,
+                                e->stream));
+    for (int i = 0; i < n_seqs; ++i) {
+        e->table.appended(seqs[i].slot, tokens + seqs[i].row0, seqs[i].len);
+        e->gr_pending[seqs[i].slot] = 0;  // a pending token that is appended is never fed again
+        e->emb_rows[seqs[i].slot] = -1;
+        pk.emplace_back(e->context_lens + seqs[i].slot, seqs[i].start + seqs[i].len);
+    }
+    TL_TRY(poke(e, pk));
+    e->stats.prefill_tokens += total;
+    return TL_OK;
+}
+
+extern "C" int tl_engine_verify_batch(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, int commit,
+                                      tl_verify_result *out) {
+    TL_REQUIRE(e && slots && tokens && lens && out, "engine_verify_batch: null argument");
+    std::vector<PrefillSeq> seqs;
+    TL_TRY(verify_seqs(e, n_seqs, slots, tokens, lens, commit != 0, seqs));
+    TL_TRY(verify_alloc(e));
+    int total = 0;
+    for (int i = 0; i < n_seqs; ++i) total += lens[i];
+    TL_TRY(verify_pass(e, seqs.data(), n_seqs, tokens, total));
+    TL_HIP(hipMemcpyAsync(out, e->vb.results, (size_t)n_seqs * sizeof(tl_verify_result), hipMemcpyDeviceToHost, e->stream));
+    TL_HIP(hipStreamSynchronize(e->stream));
+    if (!commit) return TL_OK;
+    for (int i = 0; i < n_seqs; ++i) {  // (stream ordered behind the pass: no second synchronisation)
+        const int a = out[i].count - 1;
+        TL_REQUIRE(a >= 0 && a < lens[i], "engine_verify_batch: the acceptance launch left an impossible count");
+        if (lens[i] - 1 - a > 0) TL_TRY(tl_engine_rewind(e, slots[i], lens[i] - 1 - a));
+        TL_TRY(tl_engine_set_token(e, slots[i], out[i].ids[a]));
+    }
     return TL_OK;
 }
 

@@ -208,6 +208,12 @@ class TlAttentionInfo(ctypes.Structure):
                 ("launches", _c_int)]
 
 
+class TlVerifyResult(ctypes.Structure):
+    """tl_verify_result (include/tinyllm_engine.h): one sequence of tl_engine_verify_batch -- ``count`` ids, the accepted proposals
+    followed by the correction or the bonus token (-1 behind them)."""
+    _fields_ = [("count", ctypes.c_int32), ("ids", ctypes.c_int32 * 8)]
+
+
 _P = ctypes.POINTER
 _SIGNATURES.update({
     "tl_tiled_w4_create": (_c_int, [_P(TlW4), _c_void_p, _P(_c_void_p)]),
@@ -270,6 +276,10 @@ _SIGNATURES.update({
     "tl_engine_verify": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _P(ctypes.c_int32)]),
     "tl_engine_verify_sampled": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _c_void_p, ctypes.c_float, _c_int, ctypes.c_float,
                                           _P(ctypes.c_int32), _P(_c_int)]),
+    "tl_engine_verify_batch": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int), _P(ctypes.c_int32), _P(ctypes.c_int), _c_int, _P(TlVerifyResult)]),
+    "tl_verify_attention_rows": (_c_int, [_c_void_p] * 8 + [_c_int, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _c_void_p] + [_c_int] * 4 +
+                                 [_c_float, _c_float, _c_void_p, _P(TlAttentionInfo)]),
+    "tl_verify_accept_rows": (_c_int, [_c_void_p, _c_int, _c_int, _P(ctypes.c_int), _P(ctypes.c_int), _c_void_p, _c_void_p, _c_void_p]),
     "tl_engine_set_token": (_c_int, [_c_void_p, _c_int, ctypes.c_int32]),
     "tl_engine_set_sampling": (_c_int, [_c_void_p, _c_int, _c_float, _c_int, _c_float, ctypes.c_uint64]),
     "tl_sample_logits": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 7),
@@ -915,6 +925,66 @@ def decode_attention_fused(qkv: torch.Tensor, q_norm: torch.Tensor, k_norm: torc
                                           num_kv_heads, D, page, int(block_table.shape[1]), float(rope_theta), float(eps),
                                           int(max_context), _ptr(ws), ws.numel(), _stream(), ctypes.byref(info)))
     return out, {name: getattr(info, name) for name, _ in info._fields_}
+
+
+def verify_attention_rows(qkv: torch.Tensor, q_norm: torch.Tensor, k_norm: torch.Tensor, key_pages: torch.Tensor, value_pages: torch.Tensor,
+                          block_table: torch.Tensor, slots, starts, lens, *, num_heads: int, num_kv_heads: int, rope_theta: float,
+                          eps: float, key_scales: torch.Tensor | None = None, value_scales: torch.Tensor | None = None) -> tuple[torch.Tensor, dict]:
+    """The attention stage of a batched verification pass (tl_verify_attention_rows): the rows of several sequences back to back in
+    qkv [R, (Hq + 2 Hkv) 128]; sequence i holds ``lens[i]`` (1 .. 8) rows from position ``starts[i]`` of block-table row ``slots[i]``.
+    q/k-norm + RoPE + in-place KV append (pages [P, Hkv, page, 128] bf16, or uint8 codes with key_scales / value_scales [P, Hkv, page]
+    float32) + causal paged attention -> ([R, Hq * 128] bf16 row-major, the split plan)."""
+    _require_gpu("verify_attention_rows", qkv, q_norm, k_norm, key_pages, value_pages, block_table)
+    fp8 = key_scales is not None or value_scales is not None
+    P, Hkv, page, D = (int(x) for x in key_pages.shape)
+    R = int(qkv.shape[0])
+    if D != 128 or Hkv != num_kv_heads or tuple(value_pages.shape) != tuple(key_pages.shape):
+        raise RuntimeError("verify_attention_rows: page pools must be [P, num_kv_heads, page_size, 128] and alike")
+    if qkv.dim() != 2 or qkv.shape[1] != (num_heads + 2 * num_kv_heads) * D or R != sum(int(n) for n in lens):
+        raise RuntimeError("verify_attention_rows: qkv must be [sum(lens), (Hq + 2 Hkv) * 128]")
+    for name, t in (("qkv", qkv), ("q_norm", q_norm), ("k_norm", k_norm)):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise RuntimeError(f"verify_attention_rows: {name} must be contiguous bfloat16")
+    want = torch.uint8 if fp8 else torch.bfloat16
+    for name, t in (("key_pages", key_pages), ("value_pages", value_pages)):
+        if t.dtype != want or not t.is_contiguous():
+            raise RuntimeError(f"verify_attention_rows: {name} must be contiguous {want}")
+    if fp8:
+        for name, t in (("key_scales", key_scales), ("value_scales", value_scales)):
+            if t is None or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (P, Hkv, page) or not t.is_contiguous():
+                raise RuntimeError(f"verify_attention_rows: {name} must be contiguous float32 [P, Hkv, page] on the GPU")
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or not block_table.is_contiguous():
+        raise RuntimeError("verify_attention_rows: block_table [slots, max_pages] must be contiguous int32")
+    n = len(lens)
+    if len(slots) != n or len(starts) != n or any(not 0 <= int(s) < block_table.shape[0] for s in slots):
+        raise RuntimeError("verify_attention_rows: slots, starts and lens must be alike, every slot a row of block_table")
+    out = torch.empty((R, num_heads * D), dtype=torch.bfloat16, device=qkv.device)
+    arr = lambda v: (ctypes.c_int * n)(*[int(x) for x in v])
+    info = TlAttentionInfo()
+    _check(_lib.tl_verify_attention_rows(_ptr(qkv), _ptr(q_norm), _ptr(k_norm), _ptr(key_pages), _ptr(value_pages),
+                                         _ptr(key_scales) if fp8 else None, _ptr(value_scales) if fp8 else None, _ptr(block_table), n,
+                                         arr(slots), arr(starts), arr(lens), _ptr(out), num_heads, num_kv_heads, page,
+                                         int(block_table.shape[1]), float(rope_theta), float(eps), _stream(), ctypes.byref(info)))
+    return out, {name: getattr(info, name) for name, _ in info._fields_}
+
+
+def verify_accept_rows(logits: torch.Tensor, row0, lens, tokens: torch.Tensor) -> list[list[int]]:
+    """The acceptance stage of a batched verification pass over caller rows (tl_verify_accept_rows): logits [R, vocab] bf16, tokens [R]
+    int32 (the tokens the rows were fed); sequence i owns the rows [row0[i], row0[i] + lens[i]).  Returns per sequence the accepted
+    proposals followed by the correction or the bonus token."""
+    _require_gpu("verify_accept_rows", logits, tokens)
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or not logits.is_contiguous():
+        raise RuntimeError("verify_accept_rows: logits must be contiguous bfloat16 [rows, vocab]")
+    if tokens.dtype != torch.int32 or tokens.dim() != 1 or tokens.shape[0] != logits.shape[0] or not tokens.is_contiguous():
+        raise RuntimeError("verify_accept_rows: tokens must be contiguous int32 [rows]")
+    n = len(lens)
+    if len(row0) != n or any(int(r) < 0 or int(r) + int(k) > logits.shape[0] for r, k in zip(row0, lens)):
+        raise RuntimeError("verify_accept_rows: every sequence's rows must lie inside logits")
+    arr = lambda v: (ctypes.c_int * n)(*[int(x) for x in v])
+    out = torch.zeros((max(n, 1), 9), dtype=torch.int32, device=logits.device)  # tl_verify_result: count, ids[8]
+    _check(_lib.tl_verify_accept_rows(_ptr(logits), int(logits.shape[1]), n, arr(row0), arr(lens), _ptr(tokens), _ptr(out), _stream()))
+    host = out.cpu().tolist()
+    return [rec[1:1 + rec[0]] for rec in host[:n]]
 
 
 # ---- FP8 (E4M3) KV pages: the quantised twins of paged_cache_update / paged_attention -------------------------------------

@@ -535,6 +535,28 @@ class DecodeEngine:
         _ext.check(_lib.tl_engine_verify(self._h, slot, arr, len(tokens), out))
         return list(out)
 
+    def verify_batch(self, chunks: Sequence[tuple[int, Sequence[int]]], commit: bool = False) -> list[list[int]]:
+        """Batched speculative verification (tl_engine_verify_batch): ``chunks`` = (slot, token ids) -- each slot's pending token and up
+        to 7 proposals, together at most 64 tokens, no slot twice -- verified greedily in ONE pass.  Returns per chunk the accepted
+        proposals followed by one more token (the correction, or the bonus token when every proposal was accepted).  ``commit``: the
+        engine also rewinds each slot's rejected suffix and sets that last token as its pending input; otherwise the caller rewinds
+        ``len(tokens) - len(result)`` tokens and sets it, as after ``verify``.  All or nothing.  Synchronises once."""
+        chunks = [(int(s), [int(t) for t in toks]) for s, toks in chunks]
+        if not chunks:
+            raise ValueError("verify_batch needs at least one chunk")
+        if any(not 1 <= len(toks) <= 8 for _, toks in chunks):
+            raise ValueError("verify_batch takes between 1 and 8 tokens per slot")
+        flat = [t for _, toks in chunks for t in toks]
+        if len(flat) > 64:
+            raise ValueError("verify_batch takes at most 64 tokens per call")
+        n = len(chunks)
+        slots = (ctypes.c_int * n)(*[s for s, _ in chunks])
+        lens = (ctypes.c_int * n)(*[len(toks) for _, toks in chunks])
+        arr = (ctypes.c_int32 * len(flat))(*flat)
+        out = (_ext.TlVerifyResult * n)()
+        _ext.check(_lib.tl_engine_verify_batch(self._h, n, slots, arr, lens, int(bool(commit)), out))
+        return [list(r.ids[:r.count]) for r in out]
+
     def verify_sampled(self, slot: int, tokens: Sequence[int], draft_rows: torch.Tensor | None, draft_sampling=(0.0, None, None)) -> list[int]:
         """Speculative sampling (tl_engine_verify_sampled): append 1..8 tokens to the slot -- its pending token and the draft's
         proposals -- and verify the proposals under the slot's own sampling parameters (set_sampling).  ``draft_rows`` [>= n-1, vocab]
@@ -1358,3 +1380,131 @@ def speculative_generate_ids(target: DecodeEngine, draft: DecodeEngine, prompt: 
         target.release(slot)
         if draft_live:
             draft.release(slot)
+
+
+def batch_speculative_generate_ids(target, draft, prompts: Sequence[Sequence[int]], max_new_tokens: int | Sequence[int], proposal_length: int = 4,
+                                   eos_token_id: int | None = None, *, stats: dict | None = None) -> list[list[int]]:
+    """Greedy speculative decoding for several prompts at once: ``speculative_generate_ids``' loop with every target call of a round
+    folded into ONE ``verify_batch(..., commit=True)``.  Prompts run in waves of at most ``min(target.max_batch, draft.max_batch,
+    64 // (proposal_length + 1))`` slots, prompt i of a wave on slot i of both engines.  Per round: the live slots' pending tokens go to
+    the draft, one ``draft.decode(k, batch)`` proposes for all of them (k = the most any of them may still emit; a slot with less
+    room, or whose draft proposed its own EOS, keeps fewer and its draft is rewound), one ``verify_batch`` accepts, and each slot's
+    draft is rewound to the accepted prefix -- or, where everything was accepted, takes the one step that consumes its last proposal
+    (one batched step for all slots, rewound again on the others).  A sequence that finishes is released and drops out of later rounds;
+    the last id it may emit is its pending token, which costs no pass, so every round of a sequence yields at least one id and
+    ``rounds`` stays below the ids emitted.
+    Returns, per prompt, exactly the target's greedy continuation (up to ``max_new_tokens`` ids -- one number, or one per prompt as
+    ``batch_generate_ids`` takes them -- stopping before ``eos_token_id``).
+    ``stats`` receives the single-slot loop's counters, summed over the prompts, and ``rounds`` (verify_batch calls);
+    ``target_calls`` counts one call per prefill and one per round."""
+    if not isinstance(proposal_length, int) or isinstance(proposal_length, bool) or not 0 <= proposal_length <= 7:
+        raise ValueError("proposal_length must be an integer in [0, 7] (8 verification rows per slot)")
+    prompts = [[int(t) for t in p] for p in prompts]
+    if any(not p for p in prompts):
+        raise ValueError("every prompt must hold at least one token")
+    limits = [max_new_tokens] * len(prompts) if isinstance(max_new_tokens, int) else list(max_new_tokens)
+    if len(limits) != len(prompts) or any(not isinstance(n, int) or isinstance(n, bool) or n < 0 for n in limits):
+        raise ValueError("max_new_tokens must be a non-negative integer, or one per prompt")
+    wave = min(int(target.max_batch), int(draft.max_batch), 64 // (proposal_length + 1))
+    if wave < 1:
+        raise ValueError("the engines hold no slot")
+    counts = {"target_calls": 0, "draft_steps": 0, "proposed": 0, "accepted": 0, "resampled": 0, "rounds": 0}
+    outs: list[list[int]] = [[] for _ in prompts]
+    for first in range(0, len(prompts), wave):
+        group = prompts[first:first + wave]
+        token: dict[int, int] = {}       # live slots: the pending token (predicted by the target, not yet emitted or cached)
+        drafted: set[int] = set()
+        held_t: set[int] = set()
+
+        def finish(s: int) -> None:
+            token.pop(s, None)
+            if s in held_t:
+                held_t.discard(s)
+                target.release(s)
+            if s in drafted:
+                drafted.discard(s)
+                draft.release(s)
+
+        def settle(s: int) -> None:
+            """The sequence ends where its pending token is the EOS or the last id it may emit (no pass is spent on that one)."""
+            if token[s] != eos_token_id and len(outs[first + s]) == limits[first + s] - 1:
+                outs[first + s].append(token[s])
+            if len(outs[first + s]) >= limits[first + s] or token[s] == eos_token_id:
+                finish(s)
+
+        try:
+            for s, prompt in enumerate(group):
+                if limits[first + s] == 0:
+                    continue
+                target.begin(s)
+                held_t.add(s)
+                target.prefill(s, prompt)
+                token[s] = target.read_tokens(s, 1)[0]
+                counts["target_calls"] += 1
+                if proposal_length > 0:
+                    draft.begin(s)
+                    drafted.add(s)
+                    draft.prefill(s, prompt, want_logits=False)
+            for s in list(token):
+                settle(s)
+            while True:
+                if not token:
+                    break
+                live = sorted(token)
+                batch = live[-1] + 1
+                room = {s: limits[first + s] - len(outs[first + s]) - 1 for s in live}  # proposals that could still be emitted after the pending token
+                k = min(proposal_length, max(room.values()))
+                proposals: dict[int, list[int]] = {s: [] for s in live}
+                if k > 0:
+                    for s in live:
+                        draft.set_token(s, token[s])
+                    draft.decode(k, batch=batch)
+                    for s in live:
+                        got = draft.read_tokens(s, k)
+                        counts["draft_steps"] += k
+                        keep = min(k, room[s])
+                        if eos_token_id in got[:keep]:  # the draft stops proposing after its own EOS
+                            keep = got.index(eos_token_id) + 1
+                        if keep < k:
+                            draft.rewind(s, k - keep)
+                        proposals[s] = got[:keep]
+                fed = {s: [token[s]] + proposals[s] for s in live}
+                results = target.verify_batch([(s, fed[s]) for s in live], commit=True)
+                counts["target_calls"] += 1
+                counts["rounds"] += 1
+                # fed[:a + 1] is what the target itself would have fed: emitted, unless an accepted proposal is the EOS
+                accepted = {s: len(r) - 1 for s, r in zip(live, results)}
+                for s, r in zip(live, results):
+                    a = accepted[s]
+                    counts["proposed"] += len(proposals[s])
+                    stop = next((i for i in range(1, a + 1) if fed[s][i] == eos_token_id), None)
+                    if stop is not None:
+                        outs[first + s].extend(fed[s][:stop])
+                        counts["accepted"] += stop - 1
+                        finish(s)
+                        continue
+                    outs[first + s].extend(fed[s][:a + 1])
+                    counts["accepted"] += a
+                    token[s] = r[a]
+                    settle(s)
+                # the drafts of the slots that go on: fed[:a + 1] stays.  A draft whose proposals were all accepted has not consumed
+                # the last one yet: one step for every live slot, taken back where it was not wanted.  (The step feeds each draft its
+                # device-side pending token: for a bonus slot that is its last proposal, because a slot that kept fewer than k proposals
+                # and had them all accepted has reached its limit or an EOS and is gone; what the others feed is rewound at once.)
+                going = [s for s in live if s in token and s in drafted]
+                bonus = [s for s in going if proposals[s] and accepted[s] == len(proposals[s])]
+                if bonus:
+                    draft.decode(1, batch=max(going) + 1)
+                    counts["draft_steps"] += len(bonus)
+                for s in going:
+                    if s in bonus:
+                        continue
+                    back = len(proposals[s]) - (accepted[s] + 1) + (1 if bonus else 0)
+                    if back > 0:
+                        draft.rewind(s, back)
+        finally:
+            for s in sorted(held_t | drafted):
+                finish(s)
+    if stats is not None:
+        stats.update(counts)
+    return [o[:n] for o, n in zip(outs, limits)]
