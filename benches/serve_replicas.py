@@ -142,7 +142,7 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="prompts prefilled together per turn (1 = the reference's one-at-a-time admission; > 1 packs the admitted "
                          "prompts' chunks into one multi-token pass of at most --prefill-budget rows)")
     ap.add_argument("--keep-slot-holes", action="store_true",
-                    help="do not move live requests into the decode slots finished requests left (benches/serving.py _close_holes): the step then "
+                    help="do not move live requests into the decode slots finished requests left (tiny_llm_hip/scheduler.py close_holes): the step then "
                          "decodes the prefix up to the highest live slot, as before round 5")
     ap.add_argument("--page-size", type=int, default=128)
     ap.add_argument("--kv-format", default="bf16", choices=["bf16", "fp8"],

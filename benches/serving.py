@@ -1,6 +1,9 @@
 """Continuous-batching serving loop over the decode engine, with the reference harness's report
 (reference: benches/bench.py:35-62 ServingMetrics, :351-572 run_batch_requests_serving, :787-830 report lines).
 
+The loop itself is tiny_llm_hip/scheduler.py's (one scheduler, shared with tiny_llm_hip.engine.batch_generate_ids); ``serve_requests``
+adds what is this front-end's own: a request is finished by its token count, and every engine call is timed and counted.
+
 One loop turn = (a) prefill work for the request being admitted, (b) hand it to a free decode slot once its prompt is
 in the cache, (c) ONE batched decode step over the occupied slots, (d) retire finished requests.  The reference does
 exactly one prefill chunk per turn; on an MI355X that makes admission the bottleneck of a 64-slot batch (a decode
@@ -10,7 +13,7 @@ reference's schedule), which is what lets config 4 ("64 concurrent requests") ac
 
 An engine whose ``prefix_cache_enabled`` is true (DecodeEngine(prefix_cache=...)) has every admitted request attach the cached
 prefix of its prompt (``prefix_attach`` right after ``begin``: the prompt then starts at the matched offset) and declare the answer
-tokens it fed at retirement (``prefix_extend(slot, out[:-1])`` before ``release``); the loops then also keep the produced ids.  With
+tokens it fed at retirement (``prefix_extend(slot, out[:-1])`` before ``release``); the loop then also keeps the produced ids.  With
 the cache off the call sequence is unchanged.
 
 An engine whose ``swap_enabled`` is true (DecodeEngine(swap_pages=N), ScheduleOnlyEngine(num_pages=..., swap_pages=N)) is preempted
@@ -29,8 +32,13 @@ from __future__ import annotations
 import time
 from dataclasses import dataclass, field
 
-# decode row counts the engine keeps captured graphs for (tiny_llm_hip.engine._DECODE_ROW_BUCKETS)
-ROW_BUCKETS = (1, 2, 3, 4, 8, 16, 32, 48, 64, 96, 128, 192, 256)
+
+def __getattr__(name):
+    if name == "ROW_BUCKETS":  # the decode row counts the engine keeps captured graphs for: they live with the scheduler
+        from tiny_llm_hip.scheduler import ROW_BUCKETS
+
+        return ROW_BUCKETS
+    raise AttributeError(name)
 
 
 @dataclass
@@ -91,89 +99,6 @@ def median(values) -> float:
     return ordered[mid] if len(ordered) % 2 else 0.5 * (ordered[mid - 1] + ordered[mid])
 
 
-def _row_bucket(n: int, batch_size: int) -> int:
-    return min(next((b for b in ROW_BUCKETS if b >= n), batch_size), batch_size)
-
-
-def _close_holes(engine, slots: list, live: set) -> None:
-    """Move the highest live decode slots into the holes finished requests left, when that lowers the step's row bucket.
-
-    The engine decodes the occupied PREFIX of the slots and a step's cost follows its row count (a staircase in 16-row blocks:
-    17-32 rows 1.77 ms, 33-64 rows 2.5 ms on the Qwen3-4B shape); with holes, 27 live requests spread over 48 slots pay for 48
-    rows.  A move hands over a block-table row, a context length and the pending token (tl_engine_move: no K/V byte moves).  The
-    reference decodes all ``batch_size`` rows of its batch cache every step (batch.py:136-285): slot numbers are invisible to it
-    and to every counter of the report."""
-    count = sum(s is not None for s in slots)
-    top = max((i for i, s in enumerate(slots) if s is not None), default=-1)
-    if count == 0 or _row_bucket(count, len(slots)) >= _row_bucket(top + 1, len(slots)):
-        return
-    lo, hi = 0, len(slots) - 1
-    while True:
-        while lo < hi and slots[lo] is not None:
-            lo += 1
-        while hi > lo and slots[hi] is None:
-            hi -= 1
-        if lo >= hi:
-            return
-        engine.move(hi, lo)
-        slots[lo], slots[hi] = slots[hi], None
-        live.discard(hi)
-        live.add(lo)
-
-
-class _NoPreemption:
-    """What the loops ask of tiny_llm_hip.preempt.Preemption, for an engine without swap space: every answer is "go ahead"."""
-    active = False
-
-    @staticmethod
-    def parked(state) -> bool:
-        return False
-
-    def admitted(self, state) -> None:
-        pass
-
-    def may_admit(self, slots) -> bool:
-        return True
-
-    def may_prefill(self, slot, tokens, slots, promised=0) -> bool:
-        return True
-
-    def chunk_pages(self, slot, tokens) -> int:
-        return 0
-
-    def before_step(self, slots, rows_of, staged, requeue) -> None:
-        pass
-
-    def report(self, metrics) -> None:
-        pass
-
-
-def _preemption(engine):
-    if not getattr(engine, "swap_enabled", False):
-        return _NoPreemption()
-    from tiny_llm_hip.preempt import Preemption  # pure host logic (the package is only needed by an engine that swaps)
-
-    return Preemption(engine)
-
-
-def _admit(engine, cached: bool, slot: int, request) -> dict:
-    """The state of a request that has just begun in ``slot``: with the prefix cache on it starts behind the cached part of its prompt."""
-    state = {"req": request, "offset": 0, "count": 0, "ctx": 0, "out": []}
-    lora = getattr(request, "lora", None)  # the id of a resident LoRA adapter (DecodeEngine.load_lora); such a request bypasses the prefix cache
-    if lora is not None and lora >= 0:
-        engine.set_lora(slot, lora)
-    if cached and len(request.prompt_token_ids) > 0:
-        state["offset"] = state["ctx"] = engine.prefix_attach(slot, request.prompt_token_ids)
-    return state
-
-
-def _retire(engine, cached: bool, slot: int, state: dict) -> None:
-    """Release the slot; with the prefix cache on the answer tokens that were fed are declared first (the last one never was)."""
-    if cached:
-        engine.prefix_extend(slot, state["out"][:-1])
-    engine.release(slot)
-
-
 def serve_requests(engine, requests, *, batch_size: int, prefill_step: int, prefill_budget: int | None = None,
                    page_size: int = 128, kv_bytes_per_page: int = 0, capacity_pages: int = 0,
                    clock=time.perf_counter, staging_slots: int = 1, compact: bool = True) -> ServingMetrics:
@@ -182,143 +107,97 @@ def serve_requests(engine, requests, *, batch_size: int, prefill_step: int, pref
     mx.eval inside them.  One staging slot = the reference's policy (one request prefilled at a time, batch.py:48-76);
     several = the admitted prompts' chunks go through ONE packed multi-token pass per turn (engine.prefill_packed), at most
     ``prefill_budget`` rows together.  ``compact``: close the holes in the decode slots before a step whenever that lowers its row
-    bucket (_close_holes)."""
-    if prefill_budget is None:
-        prefill_budget = prefill_step
-    if staging_slots > 1:
-        return _serve_requests_packed(engine, requests, batch_size=batch_size, prefill_step=prefill_step,
-                                      prefill_budget=prefill_budget, page_size=page_size, kv_bytes_per_page=kv_bytes_per_page,
-                                      capacity_pages=capacity_pages, clock=clock, staging_slots=staging_slots, compact=compact)
+    bucket (tiny_llm_hip.scheduler.close_holes).  The turn is tiny_llm_hip.scheduler.Scheduler's, shared with batch_generate_ids
+    (pure host logic: no GPU needed to import it); what is this front-end's own -- a request is finished by its token count, and the
+    whole measurement -- is the class below."""
+    from tiny_llm_hip.scheduler import Frontend, RequestSettings, Scheduler
+
     m = ServingMetrics()
     cached = bool(getattr(engine, "prefix_cache_enabled", False))
-    pre = _preemption(engine)
-    staging = batch_size
-    slots: list[dict | None] = [None] * batch_size
-    pending: dict | None = None
-    next_idx = 0
-    front: list = []  # requests a preemption put back: they are admitted before requests[next_idx]
-    live: set[int] = set()
+    has_step_bytes = hasattr(engine, "step_bytes")
     gaps_ms: list[float] = []
-    last_completion: float | None = None
 
-    def snapshot():
-        states = [s for s in slots if s is not None] + ([pending] if pending is not None else [])
-        m.peak_active_requests = max(m.peak_active_requests, len(states))
-        pages = sum((s["ctx"] + page_size - 1) // page_size for s in states)
-        waste = sum((-s["ctx"]) % page_size for s in states if s["ctx"] > 0)
-        m.peak_live_pages = max(m.peak_live_pages, pages)
-        m.peak_capacity_pages = max(m.peak_capacity_pages, capacity_pages)
-        m.peak_kv_bytes = max(m.peak_kv_bytes, capacity_pages * kv_bytes_per_page)
-        if waste > m.peak_tail_waste_slots:
-            m.peak_tail_waste_slots = waste
-            m.peak_tail_waste_live_slots = pages * page_size
-            m.peak_tail_waste_bytes = waste * (kv_bytes_per_page // page_size if page_size else 0)
-            m.peak_tail_waste_fraction = waste / (pages * page_size) if pages else 0.0
+    class Serving(Frontend):
+        t0 = 0.0
+        last_completion: float | None = None
 
-    try:
-        while front or next_idx < len(requests) or pending is not None or any(s is not None for s in slots):
-            m.turns += 1
-            budget = prefill_budget
-            while budget > 0:
-                if pending is None:
-                    if (not front and next_idx >= len(requests)) or not pre.may_admit(slots):
-                        break
-                    engine.begin(staging)
-                    live.add(staging)
-                    if front:
-                        pending = _admit(engine, cached, staging, front.pop(0))
-                    else:
-                        pending = _admit(engine, cached, staging, requests[next_idx])
-                        next_idx += 1
-                tokens = pending["req"].prompt_token_ids
-                if pending["offset"] < len(tokens):
-                    if not pre.may_prefill(staging, min(prefill_step, len(tokens) - pending["offset"]), slots):
-                        break  # the pool cannot hold the chunk yet: decoding goes on, pages come back
-                    chunk = tokens[pending["offset"]:pending["offset"] + prefill_step]
-                    last = pending["offset"] + len(chunk) >= len(tokens)
-                    t0 = clock()
-                    engine.prefill(staging, chunk, chunk=len(chunk), want_logits=last)
-                    engine.synchronize()
-                    m.prefill_time += clock() - t0
-                    m.prefill_chunks += 1
-                    budget -= len(chunk)
-                    pending["offset"] += len(chunk)
-                    pending["ctx"] += len(chunk)
-                    if last:
-                        pending["count"] = 1
-                        m.generated_tokens += 1
-                        if cached:
-                            pending["out"].append(engine.read_tokens(staging, 1)[0])
-                    snapshot()
-                if pending["offset"] < len(tokens):
-                    continue
-                if pending["count"] >= pending["req"].max_new_tokens:  # a one-token request never enters the batch
-                    _retire(engine, cached, staging, pending)
-                    live.discard(staging)
-                    pending = None
-                    continue
-                free = next((i for i, s in enumerate(slots) if s is None), None)
-                if free is None:
-                    break  # prefilled and waiting for a slot: admission stalls, decoding goes on
-                engine.move(staging, free)
-                live.discard(staging)
-                live.add(free)
-                slots[free] = pending
-                pre.admitted(pending)
-                pending = None
-            if pre.active and any(s is not None for s in slots):
-                def requeue(slot, state):  # the staging request gives way: released, admitted again first
-                    nonlocal pending
-                    engine.release(slot)
-                    live.discard(slot)
-                    m.generated_tokens -= state["count"]
-                    front.insert(0, state["req"])
-                    pending = None
+        def admit(self, slot, state):
+            request = state["req"]
+            state["tokens"], state["count"] = request.prompt_token_ids, 0
+            lora = getattr(request, "lora", None)  # the id of a resident LoRA adapter (DecodeEngine.load_lora); such a request bypasses the prefix cache
+            if lora is not None and lora >= 0:
+                RequestSettings(lora=lora).apply(engine, slot)
 
-                pre.before_step(slots, lambda: batch_size, [(staging, pending)] if pending is not None else [], requeue)
-            if compact:
-                _close_holes(engine, slots, live)
-            active = [i for i, s in enumerate(slots) if s is not None and not pre.parked(s)]
-            if not active:
-                last_completion = None  # idle time without an active decode request is not a fairness gap
-                continue
-            rows = _row_bucket(active[-1] + 1, batch_size)
-            m.decode_bytes += int(engine.step_bytes(rows)) if hasattr(engine, "step_bytes") else 0
-            t0 = clock()
-            engine.decode(1, batch=rows)  # the occupied prefix of the slots; idle rows inside it produce nothing
+        def before_prefill(self):
+            self.t0 = clock()
+
+        def prefilled(self, chunks):
+            engine.synchronize()
+            m.prefill_time += clock() - self.t0
+            m.prefill_chunks += len(chunks)
+            for state, _, last in chunks:
+                if last:
+                    state["count"] = 1
+                    m.generated_tokens += 1
+                    if cached:  # the produced ids are only kept for prefix_extend
+                        state["out"].append(engine.read_tokens(state["staging"], 1)[0])
+            self.snapshot()
+
+        def finished_in_staging(self, slot, state):  # a one-token request never enters the batch
+            return state["count"] >= state["req"].max_new_tokens
+
+        def before_step(self, rows):
+            m.decode_bytes += int(engine.step_bytes(rows)) if has_step_bytes else 0
+            self.t0 = clock()
+
+        def stepped(self, rows, active, steps):
             engine.synchronize()
             now = clock()
-            m.decode_time += now - t0
-            m.decode_step_ms.append((now - t0) * 1e3)
-            if last_completion is not None:
-                gaps_ms.append((now - last_completion) * 1e3)
-            last_completion = now
+            m.decode_time += now - self.t0
+            m.decode_step_ms.append((now - self.t0) * 1e3)
+            if self.last_completion is not None:
+                gaps_ms.append((now - self.last_completion) * 1e3)
+            self.last_completion = now
             produced = engine.read_pending(rows) if cached else None
+            slots = sched.slots
             for i in active:
-                s = slots[i]
-                s["count"] += 1
-                s["ctx"] += 1
-                m.generated_tokens += 1
-                m.decode_tokens += 1
+                slots[i]["count"] += 1
                 if produced is not None:
-                    s["out"].append(produced[i])
-            snapshot()
-            for i in active:
-                if slots[i]["count"] >= slots[i]["req"].max_new_tokens:
-                    _retire(engine, cached, i, slots[i])
-                    live.discard(i)
-                    slots[i] = None
-    finally:
-        for slot in list(live):
-            try:
-                engine.release(slot)
-            except RuntimeError:
-                pass
-    pre.report(m)
-    return _finish_metrics(engine, m, gaps_ms)
+                    slots[i]["out"].append(produced[i])
+            m.generated_tokens += len(active)
+            m.decode_tokens += len(active)
+            self.snapshot()
 
+        def collect(self, slot, state):
+            return state["count"] >= state["req"].max_new_tokens
 
-def _finish_metrics(engine, m: "ServingMetrics", gaps_ms: list) -> "ServingMetrics":
+        def requeued(self, state):
+            m.generated_tokens -= state["count"]
+
+        def idle(self):
+            self.last_completion = None  # idle time without an active decode request is not a fairness gap
+
+        def snapshot(self):
+            # context lengths: a running request holds its prompt and every produced token but the last, a staged one what was prefilled
+            ctx = [s["offset"] + s["count"] - 1 for s in sched.slots if s is not None] + [s["offset"] for s in sched.staged]
+            m.peak_active_requests = max(m.peak_active_requests, len(ctx))
+            pages = sum((c + page_size - 1) // page_size for c in ctx)
+            waste = sum((-c) % page_size for c in ctx if c > 0)
+            m.peak_live_pages = max(m.peak_live_pages, pages)
+            m.peak_capacity_pages = max(m.peak_capacity_pages, capacity_pages)
+            m.peak_kv_bytes = max(m.peak_kv_bytes, capacity_pages * kv_bytes_per_page)
+            if waste > m.peak_tail_waste_slots:
+                m.peak_tail_waste_slots = waste
+                m.peak_tail_waste_live_slots = pages * page_size
+                m.peak_tail_waste_bytes = waste * (kv_bytes_per_page // page_size if page_size else 0)
+                m.peak_tail_waste_fraction = waste / (pages * page_size) if pages else 0.0
+
+    fe = Serving()
+    fe.prefill_budget, fe.compact = prefill_step if prefill_budget is None else prefill_budget, compact
+    sched = Scheduler(engine, fe, requests, batch_size=batch_size, prefill_step=prefill_step, staging_slots=staging_slots)
+    sched.run()
+    m.turns = sched.turns
+    sched.pre.report(m)
     stats = engine.stats() if hasattr(engine, "stats") else {}
     m.reused_page_allocations = int(stats.get("reused_page_allocations", 0))
     m.decode_step_count = len(m.decode_step_ms)
@@ -330,147 +209,6 @@ def _finish_metrics(engine, m: "ServingMetrics", gaps_ms: list) -> "ServingMetri
     m.decode_gap_p95_ms = nearest_rank(gaps_ms, 0.95)
     m.decode_gap_max_ms = max(gaps_ms, default=0.0)
     return m
-
-
-def _serve_requests_packed(engine, requests, *, batch_size, prefill_step, prefill_budget, page_size, kv_bytes_per_page,
-                           capacity_pages, clock, staging_slots, compact=True) -> "ServingMetrics":
-    """The serving loop with several staging slots: every turn admits requests into the free staging slots, sends the next
-    chunk of every staged prompt through ONE packed prefill pass (at most ``prefill_budget`` rows together, ``prefill_step``
-    per prompt, 16 prompts), moves the prompts that finished into free decode slots (admission order), then runs one decode
-    step over the occupied prefix.  Same counters as the one-at-a-time loop."""
-    m = ServingMetrics()
-    cached = bool(getattr(engine, "prefix_cache_enabled", False))
-    pre = _preemption(engine)
-    front: list = []  # requests a preemption put back: they are admitted before requests[next_idx]
-    staging_slots = min(staging_slots, 16)
-    slots: list[dict | None] = [None] * batch_size
-    staged: list[dict] = []  # admission order; each holds its staging slot index
-    free_staging = list(range(batch_size, batch_size + staging_slots))
-    next_idx = 0
-    live: set[int] = set()
-    gaps_ms: list[float] = []
-    last_completion: float | None = None
-
-    def snapshot():
-        states = [s for s in slots if s is not None] + staged
-        m.peak_active_requests = max(m.peak_active_requests, len(states))
-        pages = sum((s["ctx"] + page_size - 1) // page_size for s in states)
-        waste = sum((-s["ctx"]) % page_size for s in states if s["ctx"] > 0)
-        m.peak_live_pages = max(m.peak_live_pages, pages)
-        m.peak_capacity_pages = max(m.peak_capacity_pages, capacity_pages)
-        m.peak_kv_bytes = max(m.peak_kv_bytes, capacity_pages * kv_bytes_per_page)
-        if waste > m.peak_tail_waste_slots:
-            m.peak_tail_waste_slots = waste
-            m.peak_tail_waste_live_slots = pages * page_size
-            m.peak_tail_waste_bytes = waste * (kv_bytes_per_page // page_size if page_size else 0)
-            m.peak_tail_waste_fraction = waste / (pages * page_size) if pages else 0.0
-
-    try:
-        while front or next_idx < len(requests) or staged or any(s is not None for s in slots):
-            m.turns += 1
-            while free_staging and (front or next_idx < len(requests)) and pre.may_admit(slots):
-                st = free_staging.pop(0)
-                engine.begin(st)
-                live.add(st)
-                if front:
-                    staged.append({**_admit(engine, cached, st, front.pop(0)), "staging": st})
-                else:
-                    staged.append({**_admit(engine, cached, st, requests[next_idx]), "staging": st})
-                    next_idx += 1
-            budget = prefill_budget
-            chunks = []
-            promised = 0  # pages of the chunks already in this pass (only counted by an engine with swap space)
-            for p in staged:
-                tokens = p["req"].prompt_token_ids
-                rem = len(tokens) - p["offset"]
-                if rem <= 0 or budget <= 0:
-                    continue
-                n = min(prefill_step, rem, budget)
-                if not pre.may_prefill(p["staging"], n, slots, promised):
-                    continue  # the pool cannot hold this chunk beside the pass's earlier ones yet
-                promised += pre.chunk_pages(p["staging"], n)
-                chunks.append((p, tokens[p["offset"]:p["offset"] + n], p["offset"] + n >= len(tokens)))
-                budget -= n
-            if chunks:
-                t0 = clock()
-                engine.prefill_packed([(p["staging"], chunk, last) for p, chunk, last in chunks])
-                engine.synchronize()
-                m.prefill_time += clock() - t0
-                m.prefill_chunks += len(chunks)
-                for p, chunk, last in chunks:
-                    p["offset"] += len(chunk)
-                    p["ctx"] += len(chunk)
-                    if last:
-                        p["count"] = 1
-                        m.generated_tokens += 1
-                        if cached:
-                            p["out"].append(engine.read_tokens(p["staging"], 1)[0])
-                snapshot()
-            for p in list(staged):  # admission order: the first prompt that finished takes the first free slot
-                if p["offset"] < len(p["req"].prompt_token_ids):
-                    continue
-                if p["count"] >= p["req"].max_new_tokens:  # a one-token request never enters the batch
-                    _retire(engine, cached, p["staging"], p)
-                elif (free := next((i for i, s in enumerate(slots) if s is None), None)) is not None:
-                    engine.move(p["staging"], free)
-                    live.add(free)
-                    slots[free] = p
-                    pre.admitted(p)
-                else:
-                    continue  # prefilled and waiting for a slot
-                live.discard(p["staging"])
-                free_staging.append(p["staging"])
-                staged.remove(p)
-            if pre.active and any(s is not None for s in slots):
-                def requeue(slot, state):  # a staged request gives way: released, admitted again first
-                    engine.release(slot)
-                    live.discard(slot)
-                    free_staging.append(slot)
-                    staged.remove(state)
-                    m.generated_tokens -= state["count"]
-                    front.insert(0, state["req"])
-
-                pre.before_step(slots, lambda: batch_size, [(p["staging"], p) for p in staged], requeue)
-            if compact:
-                _close_holes(engine, slots, live)
-            active = [i for i, s in enumerate(slots) if s is not None and not pre.parked(s)]
-            if not active:
-                last_completion = None
-                continue
-            rows = _row_bucket(active[-1] + 1, batch_size)
-            m.decode_bytes += int(engine.step_bytes(rows)) if hasattr(engine, "step_bytes") else 0
-            t0 = clock()
-            engine.decode(1, batch=rows)
-            engine.synchronize()
-            now = clock()
-            m.decode_time += now - t0
-            m.decode_step_ms.append((now - t0) * 1e3)
-            if last_completion is not None:
-                gaps_ms.append((now - last_completion) * 1e3)
-            last_completion = now
-            produced = engine.read_pending(rows) if cached else None
-            for i in active:
-                s = slots[i]
-                s["count"] += 1
-                s["ctx"] += 1
-                m.generated_tokens += 1
-                m.decode_tokens += 1
-                if produced is not None:
-                    s["out"].append(produced[i])
-            snapshot()
-            for i in active:
-                if slots[i]["count"] >= slots[i]["req"].max_new_tokens:
-                    _retire(engine, cached, i, slots[i])
-                    live.discard(i)
-                    slots[i] = None
-    finally:
-        for slot in list(live):
-            try:
-                engine.release(slot)
-            except RuntimeError:
-                pass
-    pre.report(m)
-    return _finish_metrics(engine, m, gaps_ms)
 
 
 def report_lines(num_seqs: int, prompt_tokens: int, total_time: float, m: ServingMetrics) -> list[str]:

@@ -94,7 +94,7 @@ def test_draw_rules():
 
 
 def test_python_argument_validation():
-    from tiny_llm_hip.engine import request_sampling, sampling_args
+    from tiny_llm_hip.engine import request_settings, sampling_args
 
     assert sampling_args() == (0.0, 0, 1.0, 0)
     assert sampling_args(0.7, 50, 0.9, 3) == (0.7, 50, 0.9, 3)
@@ -102,7 +102,10 @@ def test_python_argument_validation():
                 dict(top_k=2.5), dict(top_p=0.0), dict(top_p=1.5), dict(seed=-1), dict(seed=1 << 64)]:
         with pytest.raises(ValueError):
             sampling_args(**bad)
-    assert request_sampling(None, 3) is None
+    def request_sampling(sampling, n, base_seed=0):
+        return [s.sampling for s in request_settings(sampling, n, base_seed)]
+
+    assert [g[:3] for g in request_sampling(None, 3)] == [(0.0, 0, 1.0)] * 3  # greedy: RequestSettings.apply makes no call
     got = request_sampling({"temperature": 1.0}, 3, base_seed=10)
     assert [g[3] for g in got] == [10, 11, 12]
     got = request_sampling([{"temperature": 1.0, "seed": 5}, {}], 2)

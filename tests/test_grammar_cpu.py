@@ -250,9 +250,10 @@ def test_vocab_create_refuses_bad_input(built_libs):
 def test_request_dicts_accept_a_grammar():
     from tiny_llm_hip import engine as E
 
-    pens = E.request_penalties([{"grammar": None, "repetition_penalty": 1.2}], 1, 1024)
-    assert pens == [((1.2, 0.0, 0.0), {})]
-    assert E.request_grammars([{"grammar": None}, {}], 2) == [None, None] and E.request_grammars(None, 3) is None
+    pens = E.request_settings([{"grammar": None, "repetition_penalty": 1.2}], 1, vocab_size=1024)
+    assert [(s.penalties, s.bias) for s in pens] == [((1.2, 0.0, 0.0), {})]
+    assert [s.grammar for s in E.request_settings([{"grammar": None}, {}], 2)] == [None, None]
+    assert [s.grammar for s in E.request_settings(None, 3)] == [None] * 3
     with pytest.raises(ValueError):
-        E.request_grammars({"grammar": "a+"}, 1)
-    assert E.request_sampling({"grammar": None, "temperature": 0.5}, 1)[0][0] == 0.5
+        E.request_settings({"grammar": "a+"}, 1)
+    assert E.request_settings({"grammar": None, "temperature": 0.5}, 1)[0].sampling[0] == 0.5

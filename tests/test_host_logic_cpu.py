@@ -425,7 +425,8 @@ class _FakeDecodeEngine:
 def test_batch_generate_ids_decodes_only_the_occupied_slot_prefix():
     """engine.batch_generate_ids: same schedule as the reference (one prefill chunk + one decode step per turn), but a
     decode step covers a bucket over the occupied slot prefix instead of all batch_size rows."""
-    from tiny_llm_hip.engine import _DECODE_ROW_BUCKETS, batch_generate_ids
+    from tiny_llm_hip.engine import batch_generate_ids
+    from tiny_llm_hip.scheduler import ROW_BUCKETS as _DECODE_ROW_BUCKETS
 
     eng = _FakeDecodeEngine(max_batch=17)
     prompts = [[i + 1] * (3 + i % 5) for i in range(12)]

@@ -103,7 +103,7 @@ def test_history_follows_the_header_rule():
 
 
 def test_penalty_args_and_request_penalties():
-    from tiny_llm_hip.engine import penalty_args, request_penalties, request_sampling, sampling_args
+    from tiny_llm_hip.engine import penalty_args, request_settings, sampling_args
 
     assert penalty_args() == (1.0, 0.0, 0.0)
     assert penalty_args(1.3, -0.5, 2) == (1.3, -0.5, 2.0)
@@ -111,7 +111,13 @@ def test_penalty_args_and_request_penalties():
                 dict(presence=float("inf")), dict(frequency=float("nan")), dict(presence="1"), dict(frequency=True)):
         with pytest.raises(ValueError):
             penalty_args(**bad)
-    assert request_penalties(None, 3, 100) is None
+    def request_penalties(sampling, n, vocab_size):
+        return [(s.penalties, s.bias) for s in request_settings(sampling, n, vocab_size=vocab_size)]
+
+    def request_sampling(sampling, n, base_seed=0):
+        return [s.sampling for s in request_settings(sampling, n, base_seed, vocab_size=100)]
+
+    assert request_penalties(None, 3, 100) == [((1.0, 0.0, 0.0), {})] * 3  # neutral: RequestSettings.apply makes no call
     got = request_penalties({"presence_penalty": 1.5, "temperature": 0.7}, 2, 100)
     assert got == [((1.0, 1.5, 0.0), {})] * 2
     got = request_penalties([{"logit_bias": {3: -math.inf}}, {}], 2, 100)
@@ -123,7 +129,7 @@ def test_penalty_args_and_request_penalties():
         request_penalties([{}], 2, 100)
     # the sampling half is what tests/test_device_sampling_cpu.py expects, with or without the new keys in the dicts
     assert sampling_args() == (0.0, 0, 1.0, 0)
-    assert request_sampling(None, 3) is None
+    assert [g[:3] for g in request_sampling(None, 3)] == [(0.0, 0, 1.0)] * 3  # greedy
     assert [g[3] for g in request_sampling({"temperature": 1.0}, 3, base_seed=10)] == [10, 11, 12]
     assert request_sampling([{"temperature": 1.0, "seed": 5, "presence_penalty": 1.0}, {}], 2) == [(1.0, 0, 1.0, 5), (0.0, 0, 1.0, 1)]
     with pytest.raises(ValueError):

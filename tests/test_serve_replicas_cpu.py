@@ -125,7 +125,7 @@ def test_config1_week1_cpu_runner_smoke():
 
 
 def test_packed_admission_schedule_only():
-    """serve_requests with several staging slots (benches/serving.py _serve_requests_packed): every request gets exactly its
+    """serve_requests with several staging slots (tiny_llm_hip/scheduler.py Scheduler._stage_packed): every request gets exactly its
     tokens, a packed pass never exceeds the budget, 16 chunks or one chunk per slot, finished prompts enter the batch in
     admission order, all slots come back; with ONE staging slot the engine never sees a packed call (reference policy)."""
     from random import Random
@@ -166,7 +166,7 @@ def test_packed_admission_schedule_only():
 
 
 def test_hole_closing_keeps_the_decode_prefix_dense():
-    """benches/serving.py _close_holes: before a step the live decode slots are moved into the holes finished requests left whenever
+    """tiny_llm_hip/scheduler.py close_holes: before a step the live decode slots are moved into the holes finished requests left whenever
     that lowers the row bucket -- every step then runs at the bucket of the NUMBER of live requests, each request still gets exactly
     its tokens and every slot comes back; the counters the reference's report prints do not see slot numbers (same values with the
     moves switched off), only the clock does."""

@@ -113,7 +113,7 @@ def test_undecided_cap_over_the_generator_grid():
 
 
 def test_truncation_args_and_request_truncation():
-    from tiny_llm_hip.engine import request_penalties, request_sampling, request_truncation, truncation_args
+    from tiny_llm_hip.engine import request_settings, truncation_args
 
     assert truncation_args() == (0.0, 1.0, 0.0, 0.0)
     assert truncation_args(0.05, 0.9) == (0.05, 0.9, 0.0, 0.0)
@@ -128,17 +128,20 @@ def test_truncation_args_and_request_truncation():
     for bad in (dict(min_p=0.05), dict(typical_p=0.9), dict(top_k=40), dict(top_p=0.9)):
         with pytest.raises(ValueError, match="excludes"):
             truncation_args(mirostat_tau=5.0, **bad)
-    assert request_truncation(None, 3) is None
+    def request_truncation(sampling, n):
+        return [s.truncation for s in request_settings(sampling, n, vocab_size=100)]
+
+    assert request_truncation(None, 3) == [(0.0, 1.0, 0.0, 0.0)] * 3  # neutral: RequestSettings.apply makes no call
     d = {"temperature": 0.8, "min_p": 0.05, "typical_p": 0.9, "top_k": 40}
     assert request_truncation(d, 2) == [(0.05, 0.9, 0.0, 0.0)] * 2
     assert request_truncation([{"temperature": 1.0, "mirostat_tau": 5.0}, {}], 2) == [(0.0, 1.0, 5.0, 0.1), (0.0, 1.0, 0.0, 0.0)]
     with pytest.raises(ValueError, match="excludes"):
         request_truncation({"temperature": 1.0, "mirostat_tau": 5.0, "top_p": 0.9}, 1)
-    # the other readers of the same dicts accept the new keys
-    assert request_sampling(d, 1)[0][:3] == (0.8, 40, 1.0)
-    assert request_penalties(d, 1, 100)[0][0] == (1.0, 0.0, 0.0)
+    # the other fields of the same record
+    assert request_settings(d, 1, vocab_size=100)[0].sampling[:3] == (0.8, 40, 1.0)
+    assert request_settings(d, 1, vocab_size=100)[0].penalties == (1.0, 0.0, 0.0)
     with pytest.raises(ValueError):
-        request_sampling({"minp": 0.1}, 1)
+        request_settings({"minp": 0.1}, 1)
 
 
 def test_cli_flags_refuse_mirostat_with_another_truncation():

@@ -160,7 +160,7 @@ def _soak(model, route, n_seqs, total_steps, seed, page=16):
                 budget[s] -= k
                 trace.append(eng.read_tokens(s, k))
             crc = zlib.crc32(eng.logits(live).view(torch.int16).cpu().numpy().tobytes(), crc)
-            # finished sequences leave; the last live slot moves into each hole (benches/serving.py _close_holes)
+            # finished sequences leave; the last live slot moves into each hole (tiny_llm_hip/scheduler.py close_holes)
             s = 0
             while s < live:
                 if budget[s] > 0:

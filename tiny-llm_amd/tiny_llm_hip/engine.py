@@ -19,6 +19,8 @@ from typing import Any, NamedTuple, Sequence
 
 import torch
 
+from . import scheduler
+from .scheduler import RequestSettings
 from ._ext import tiny_llm_ext_hip as _ext
 
 _lib = _ext.lib()
@@ -766,28 +768,15 @@ class DecodeEngine:
         final StopState.  Without ``stop`` the call is unchanged."""
         if stop is not None and (isinstance(decode_block, bool) or not isinstance(decode_block, int) or decode_block < 1):
             raise ValueError("generate: decode_block is a positive int")
-        args = sampling_args(temperature, top_k, top_p, seed)
-        trn = truncation_args(min_p, typical_p, mirostat_tau, mirostat_eta, top_k=args[1], top_p=args[2])
-        top_n = logprobs_arg(logprobs)
-        pen = penalty_args(repetition_penalty, presence_penalty, frequency_penalty)
-        bias = _ext.logit_bias_arg(logit_bias, self.vocab_size)
+        settings = request_settings(
+            {"temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed, "min_p": min_p, "typical_p": typical_p,
+             "mirostat_tau": mirostat_tau, "mirostat_eta": mirostat_eta, "repetition_penalty": repetition_penalty,
+             "presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty, "logit_bias": logit_bias, "grammar": grammar,
+             "lora": lora}, 1, vocab_size=self.vocab_size, logprobs=logprobs, stop=stop, limits=[max_new_tokens])[0]
+        top_n = settings.top_n
         self.begin(slot)
         try:
-            if lora is not None and lora >= 0:
-                self.set_lora(slot, lora)
-            if pen != (1.0, 0.0, 0.0):
-                self.set_penalties(slot, *pen)
-            if bias[0]:
-                self.set_logit_bias(slot, logit_bias)
-            if grammar is not None:
-                self.set_grammar(slot, grammar)
-            if args[0] > 0.0:
-                self.set_sampling(slot, *args)
-            apply_truncation(self, slot, trn)
-            if top_n >= 0:
-                self.set_logprobs(slot, top_n)
-            if stop is not None:
-                self.set_stop(slot, stop, max_new_tokens)
+            settings.apply(self, slot)
             prompt = [int(t) for t in prompt]
             matched = self.prefix_attach(slot, prompt) if self.prefix_cache_enabled and prompt else 0
             self.prefill(slot, prompt[matched:], chunk=chunk)
@@ -947,18 +936,6 @@ class Grammar:
             pass
 
 
-def request_grammars(sampling, n_prompts: int) -> list["Grammar | None"] | None:
-    """The ``"grammar"`` key of batch_generate_ids' ``sampling`` dicts: per prompt a Grammar or None."""
-    if sampling is None:
-        return None
-    dicts = [sampling] * n_prompts if isinstance(sampling, dict) else list(sampling)
-    out = [d.get("grammar") if isinstance(d, dict) else None for d in dicts]
-    for g in out:
-        if g is not None and not isinstance(g, Grammar):
-            raise ValueError("sampling['grammar'] must be a Grammar (DecodeEngine.make_grammar) or None")
-    return out
-
-
 def penalty_args(repetition: float = 1.0, presence: float = 0.0, frequency: float = 0.0) -> tuple[float, float, float]:
     """Validated (repetition, presence, frequency) for tl_engine_set_penalties: repetition finite and > 0 (1 = off), presence and
     frequency finite (0 = off; negative values encourage repetition)."""
@@ -970,83 +947,48 @@ def penalty_args(repetition: float = 1.0, presence: float = 0.0, frequency: floa
     return float(repetition), float(presence), float(frequency)
 
 
-_SAMPLING_KEYS = {"temperature", "top_k", "top_p", "seed", "min_p", "typical_p", "mirostat_tau", "mirostat_eta"}  # (the last four: request_truncation)
-_PENALTY_KEYS = {"repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "grammar", "lora"}  # (grammar: request_grammars; lora: lora.request_loras)
+SETTINGS_KEYS = {"temperature", "top_k", "top_p", "seed", "min_p", "typical_p", "mirostat_tau", "mirostat_eta", "repetition_penalty",
+                 "presence_penalty", "frequency_penalty", "logit_bias", "grammar", "lora"}
 
 
-def request_penalties(sampling, n_prompts: int, vocab_size: int) -> list[tuple[tuple[float, float, float], dict]] | None:
-    """The penalty half of batch_generate_ids' ``sampling`` dicts (request_sampling reads the other keys): per prompt
-    ((repetition, presence, frequency), logit bias dict), validated; None when ``sampling`` is None."""
-    if sampling is None:
-        return None
-    if isinstance(sampling, dict):
-        sampling = [sampling] * n_prompts
-    sampling = list(sampling)
-    if len(sampling) != n_prompts:
+def request_settings(sampling, n_prompts: int, base_seed: int = 0, vocab_size: int = 0, logprobs: int | None = None, stop=None,
+                     limits: int | Sequence[int] = 0) -> list[RequestSettings]:
+    """One RequestSettings per prompt.  ``sampling``: None (greedy), one dict for every request or one dict per prompt, with the keys
+    SETTINGS_KEYS: temperature / top_k / top_p / seed (sampling_args; a request without a seed gets base_seed + its prompt index, so
+    requests do not share a random stream), min_p / typical_p / mirostat_tau / mirostat_eta (truncation_args, exclusivity against the
+    same dict's top_k / top_p included), repetition_penalty / presence_penalty / frequency_penalty (penalty_args), logit_bias
+    (logit_bias_arg over ``vocab_size``), grammar (a Grammar or None) and lora (lora.request_loras: also one list for all in a single
+    dict).  ``logprobs``: logprobs_arg, for every request.  ``stop``: stop.request_stops; a request is armed when it is not None.
+    ``limits``: max_new_tokens, one for all or one per prompt.  ValueError for anything else."""
+    from .lora import request_loras
+    from .stop import request_stops
+
+    stops = request_stops(stop, n_prompts)
+    limits = [limits] * n_prompts if isinstance(limits, int) else list(limits)
+    dicts = [{}] * n_prompts if sampling is None else [sampling] * n_prompts if isinstance(sampling, dict) else list(sampling)
+    if len(dicts) != n_prompts:
         raise ValueError("sampling needs one dict per prompt (or one dict for all)")
     out = []
-    for d in sampling:
+    for i, d in enumerate(dicts):
         if not isinstance(d, dict):
             raise ValueError("sampling entries must be dicts")
-        unknown = set(d) - _SAMPLING_KEYS - _PENALTY_KEYS
-        if unknown:
-            raise ValueError(f"unknown sampling keys: {sorted(unknown)}")
-        bias = d.get("logit_bias")
-        _ext.logit_bias_arg(bias, vocab_size)
-        out.append((penalty_args(d.get("repetition_penalty", 1.0), d.get("presence_penalty", 0.0), d.get("frequency_penalty", 0.0)),
-                    dict(bias) if bias else {}))
-    return out
-
-
-def request_sampling(sampling, n_prompts: int, base_seed: int = 0) -> list[tuple[float, int, float, int]] | None:
-    """batch_generate_ids' ``sampling``: None (greedy, today's behaviour), one dict for every request, or one dict per prompt, with
-    keys temperature / top_k / top_p / seed.  A request without a seed gets base_seed + its prompt index, so requests do not share
-    a random stream.  The keys repetition_penalty / presence_penalty / frequency_penalty / logit_bias are read by request_penalties."""
-    if sampling is None:
-        return None
-    if isinstance(sampling, dict):
-        sampling = [sampling] * n_prompts
-    sampling = list(sampling)
-    if len(sampling) != n_prompts:
-        raise ValueError("sampling needs one dict per prompt (or one dict for all)")
-    out = []
-    for i, d in enumerate(sampling):
-        if not isinstance(d, dict):
-            raise ValueError("sampling entries must be dicts")
-        unknown = set(d) - _SAMPLING_KEYS - _PENALTY_KEYS  # (the penalty keys are request_penalties')
+        unknown = set(d) - SETTINGS_KEYS
         if unknown:
             raise ValueError(f"unknown sampling keys: {sorted(unknown)}")
         seed = d.get("seed")
-        out.append(sampling_args(d.get("temperature", 0.0), d.get("top_k"), d.get("top_p"),
-                                 (base_seed + i) & 0xFFFFFFFFFFFFFFFF if seed is None else seed))
-    return out
-
-
-def apply_truncation(engine, slot: int, trn: tuple[float, float, float, float]) -> None:
-    """truncation_args' tuple on a slot; the defaults make no call."""
-    if trn[0] > 0.0 or trn[1] < 1.0:
-        engine.set_truncation(slot, trn[0], trn[1])
-    if trn[2] > 0.0:
-        engine.set_mirostat(slot, trn[2], trn[3])
-
-
-def request_truncation(sampling, n_prompts: int) -> list[tuple[float, float, float, float]] | None:
-    """The truncation keys of batch_generate_ids' ``sampling`` dicts -- min_p / typical_p / mirostat_tau / mirostat_eta -- per prompt as
-    truncation_args returns them (exclusivity against the same dict's top_k / top_p included); None when ``sampling`` is None."""
-    if sampling is None:
-        return None
-    dicts = [sampling] * n_prompts if isinstance(sampling, dict) else list(sampling)
-    out = []
-    for d in dicts:
-        if not isinstance(d, dict):
-            raise ValueError("sampling entries must be dicts")
-        _, k, p, _ = sampling_args(d.get("temperature", 0.0), d.get("top_k"), d.get("top_p"), 0)
-        out.append(truncation_args(d.get("min_p", 0.0), d.get("typical_p"), d.get("mirostat_tau", 0.0), d.get("mirostat_eta", 0.1), top_k=k, top_p=p))
-    return out
-
-
-# decode row counts used by the scheduler: exact up to 4 rows (fused GEMV), then the row-block sizes of the skinny matmul
-_DECODE_ROW_BUCKETS = (1, 2, 3, 4, 8, 16, 32, 48, 64, 96, 128, 192, 256)
+        smp = sampling_args(d.get("temperature", 0.0), d.get("top_k"), d.get("top_p"), (base_seed + i) & 0xFFFFFFFFFFFFFFFF if seed is None else seed)
+        bias = d.get("logit_bias")
+        _ext.logit_bias_arg(bias, vocab_size)
+        pen = penalty_args(d.get("repetition_penalty", 1.0), d.get("presence_penalty", 0.0), d.get("frequency_penalty", 0.0))
+        grammar = d.get("grammar")
+        if grammar is not None and not isinstance(grammar, Grammar):
+            raise ValueError("sampling['grammar'] must be a Grammar (DecodeEngine.make_grammar) or None")
+        trn = truncation_args(d.get("min_p", 0.0), d.get("typical_p"), d.get("mirostat_tau", 0.0), d.get("mirostat_eta", 0.1), top_k=smp[1], top_p=smp[2])
+        out.append(RequestSettings(sampling=smp, truncation=trn, penalties=pen, bias=dict(bias) if bias else {}, grammar=grammar,
+                                   armed=stops is not None, stop=stops[i] if stops is not None else None, budget=limits[i]))
+    loras = request_loras(sampling, n_prompts) or [-1] * n_prompts
+    top_n = logprobs_arg(logprobs)
+    return [s._replace(lora=lora, top_n=top_n) for s, lora in zip(out, loras)]
 
 
 def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], max_new_tokens: int | Sequence[int],
@@ -1061,9 +1003,9 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     nothing, so skipping the idle tail changes no result), (d) retires finished requests and returns their pages.
     Token-id in, token-id out (no tokenizer can be downloaded here).  Needs ``engine.max_batch >= batch_size + 1``:
     the last slot is the prefill staging slot.  Returns [(prompt_idx, generated ids)] in completion order.
-    ``sampling``: None (greedy), one dict or one dict per prompt (request_sampling; the dicts also take repetition_penalty /
-    presence_penalty / frequency_penalty / logit_bias, request_penalties, and ``grammar``: a Grammar, whose EOS ids then end the request
-    like ``eos_token_id``; and min_p / typical_p / mirostat_tau / mirostat_eta, request_truncation); applied when a request enters the staging slot,
+    ``sampling``: None (greedy), one dict or one dict per prompt (request_settings: temperature / top_k / top_p / seed, repetition_penalty /
+    presence_penalty / frequency_penalty / logit_bias, min_p / typical_p / mirostat_tau / mirostat_eta, and ``grammar``: a Grammar, whose
+    EOS ids then end the request like ``eos_token_id``); applied when a request enters the staging slot (RequestSettings.apply),
     and carried by the engine through its slot moves.  ``logprobs``: None, or an int (0 .. 20 alternatives): every request records
     its tokens' log-probabilities (set_logprobs), read in the same turn as the pending ids, and the result is
     [(prompt_idx, generated ids, records)].
@@ -1084,185 +1026,76 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     combined with it (put the id into the set), and a grammar's EOS ids end such a request only where the set holds them.
     ``decode_block`` > 1 (with ``stop``): while the queue is empty, nothing is staged and the engine has no swap space, a turn runs
     that many decode steps in one call -- a slot that stops inside the block freezes at its stopping token -- and reads each slot's
-    ids of the block from the ring by its ``generated`` count.  Calls that pass neither argument behave exactly as before."""
-    from .preempt import Preemption
-    from .stop import request_stops
-    per_request_stop = request_stops(stop, len(prompts))
+    ids of the block from the ring by its ``generated`` count.  Calls that pass neither argument behave exactly as before.
+    The turn itself is tiny_llm_hip.scheduler.Scheduler's, shared with benches/serving.py; what is this front-end's own is _BatchFrontend."""
     if isinstance(decode_block, bool) or not isinstance(decode_block, int) or decode_block < 1:
         raise ValueError("decode_block is a positive int")
-    if per_request_stop is None and decode_block != 1:
+    if stop is None and decode_block != 1:
         raise ValueError("decode_block > 1 needs stop conditions on the device (stop=)")
-    if per_request_stop is not None and eos_token_id is not None:
+    if stop is not None and eos_token_id is not None:
         raise ValueError("stop= and eos_token_id= are not combined: put the id into the stop set")
     if batch_size <= 0 or prefill_step <= 0:
         raise ValueError("batch_size and prefill_step must be positive")
     if engine.max_batch < batch_size + 1:
         raise ValueError("engine needs batch_size + 1 slots (one prefill staging slot)")
-    limits = [max_new_tokens] * len(prompts) if isinstance(max_new_tokens, int) else list(max_new_tokens)
-    per_request = request_sampling(sampling, len(prompts), base_seed)
-    per_request_pen = None if sampling is None else request_penalties(sampling, len(prompts), engine.vocab_size)
-    per_request_gr = request_grammars(sampling, len(prompts))
-    per_request_trn = request_truncation(sampling, len(prompts))
-    from .lora import request_loras
-    per_request_lora = request_loras(sampling, len(prompts))  # ("lora": an adapter id for every request, or a list with one per request)
+    settings = request_settings(sampling, len(prompts), base_seed, engine.vocab_size if sampling is not None else 0, logprobs, stop, max_new_tokens)
+    fe = _BatchFrontend(engine, prompts, settings, eos_token_id, on_step, decode_block)
+    sched = scheduler.Scheduler(engine, fe, range(len(prompts)), batch_size=batch_size, prefill_step=prefill_step)
+    sched.run()
+    return [(s["req"], s["out"]) + ((s["lp"],) if fe.top_n >= 0 else ()) for s in sched.finished]
 
-    def ends(req, token):  # the request's own EOS ids where it has a grammar
-        return token == eos_token_id or (req["eos"] is not None and token in req["eos"])
 
-    cached = bool(getattr(engine, "prefix_cache_enabled", False))
+class _BatchFrontend(scheduler.Frontend):
+    """batch_generate_ids' side of the scheduler: requests are prompt indices; every produced id is read back, and a request is
+    finished by the host's comparison (limit, ``eos_token_id``, its grammar's EOS ids) or, armed, by the device's stop state."""
+    rows_cover_parked = True
 
-    def retire(slot, req):  # with the cache on, the answer's fed tokens are declared first (the last produced one was never fed)
-        if cached:
-            engine.prefix_extend(slot, req["out"][:-1])
-        engine.release(slot)
+    def __init__(self, engine, prompts, settings, eos_token_id, on_step, decode_block):
+        self.engine, self.prompts, self.settings, self.eos_token_id, self.on_step = engine, prompts, settings, eos_token_id, on_step
+        self.decode_block = decode_block
+        self.top_n = settings[0].top_n if settings else -1
+        self.armed = bool(settings) and settings[0].armed
 
-    pre = Preemption(engine)
-    top_n = logprobs_arg(logprobs)
-    staging = batch_size
-    queue = list(range(len(prompts)))
-    slots: list[dict | None] = [None] * batch_size
-    pending: dict | None = None
-    finished: list[tuple[int, list[int]]] = []
-    live_slots: set[int] = set()
-    try:
-        while queue or pending is not None or any(s is not None for s in slots):
-            if queue and pending is None and pre.may_admit(slots):
-                idx = queue.pop(0)
-                engine.begin(staging)
-                live_slots.add(staging)
-                if per_request_lora is not None and per_request_lora[idx] >= 0:
-                    engine.set_lora(staging, per_request_lora[idx])
-                if per_request is not None and per_request[idx][0] > 0.0:
-                    engine.set_sampling(staging, *per_request[idx])
-                if per_request_trn is not None:
-                    apply_truncation(engine, staging, per_request_trn[idx])
-                if per_request_pen is not None:
-                    pen, bias = per_request_pen[idx]
-                    if pen != (1.0, 0.0, 0.0):
-                        engine.set_penalties(staging, *pen)
-                    if bias:
-                        engine.set_logit_bias(staging, bias)
-                grammar = per_request_gr[idx] if per_request_gr is not None else None
-                if grammar is not None:
-                    engine.set_grammar(staging, grammar)
-                if top_n >= 0:
-                    engine.set_logprobs(staging, top_n)
-                if per_request_stop is not None:
-                    engine.set_stop(staging, per_request_stop[idx], limits[idx])
-                pending = {"eos": grammar.eos_ids if grammar is not None else None, "idx": idx, "tokens": [int(t) for t in prompts[idx]], "offset": 0, "out": [], "limit": limits[idx], "lp": []}
-                if cached and pending["tokens"]:  # after the settings, before the first chunk: the prompt starts behind the cached prefix
-                    pending["offset"] = engine.prefix_attach(staging, pending["tokens"])
-            if pending is not None:
-                total = len(pending["tokens"])
-                if pending["offset"] < total and pre.may_prefill(staging, min(prefill_step, total - pending["offset"]), slots):
-                    chunk = pending["tokens"][pending["offset"]:pending["offset"] + prefill_step]
-                    last = pending["offset"] + len(chunk) >= total
-                    engine.prefill(staging, chunk, chunk=len(chunk), want_logits=last)
-                    pending["offset"] += len(chunk)
-                    if last:
-                        pending["out"].append(engine.read_tokens(staging, 1)[0])
-                        if top_n >= 0:
-                            pending["lp"].append(engine.read_logprobs(staging, 1)[0])
-                if pending["offset"] >= total:
-                    if per_request_stop is not None:
-                        done = engine.stop_state(staging).stopped
-                    else:
-                        done = len(pending["out"]) >= pending["limit"] or ends(pending, pending["out"][-1])
-                    if done:
-                        retire(staging, pending)
-                        live_slots.discard(staging)
-                        finished.append((pending["idx"], pending["out"]) + ((pending["lp"],) if top_n >= 0 else ()))
-                        pending = None
-                    else:
-                        free = next((i for i, s in enumerate(slots) if s is None), None)
-                        if free is not None:
-                            engine.move(staging, free)
-                            live_slots.discard(staging)
-                            live_slots.add(free)
-                            slots[free] = pending
-                            pre.admitted(pending)
-                            pending = None
-            if pre.active and any(s is not None for s in slots):
-                def requeue(slot, req):  # the staging request gives way: released, back at the front of the queue
-                    nonlocal pending
-                    engine.release(slot)
-                    live_slots.discard(slot)
-                    queue.insert(0, req["idx"])
-                    pending = None
+    def admit(self, slot, state):
+        s = self.settings[state["req"]]
+        s.apply(self.engine, slot)
+        state.update(tokens=[int(t) for t in self.prompts[state["req"]]], lp=[], limit=s.budget,
+                     eos=s.grammar.eos_ids if s.grammar is not None else None)
 
-                pre.before_step(slots, lambda: batch_size,
-                                [(staging, pending)] if pending is not None else [], requeue)
-            if any(s is not None and not pre.parked(s) for s in slots):
-                # slots fill lowest-first, so rows above the highest occupied one are idle: decode only a bucket that
-                # covers the occupied prefix (the engine keeps one captured graph per row count; buckets bound their number)
-                def bucket(n):
-                    return min(next((b for b in _DECODE_ROW_BUCKETS if b >= n), batch_size), batch_size)
+    def prefilled(self, chunks):
+        for state, _, last in chunks:
+            if last:
+                state["out"].append(self.engine.read_tokens(state["staging"], 1)[0])
+                if self.top_n >= 0:
+                    state["lp"].append(self.engine.read_logprobs(state["staging"], 1)[0])
 
-                top = max(i for i, s in enumerate(slots) if s is not None) + 1
-                count = sum(s is not None for s in slots)
-                if bucket(count) < bucket(top):
-                    # finished requests left holes below the highest live slot and closing them lowers the row bucket (a step
-                    # costs by its rows): hand the highest live slots over to the holes -- block-table row, context length and
-                    # pending token move, no K/V bytes (tl_engine_move); slot numbers are invisible to the results
-                    lo, hi = 0, batch_size - 1
-                    while True:
-                        while lo < hi and slots[lo] is not None:
-                            lo += 1
-                        while hi > lo and slots[hi] is None:
-                            hi -= 1
-                        if lo >= hi:
-                            break
-                        engine.move(hi, lo)
-                        slots[lo], slots[hi] = slots[hi], None
-                        live_slots.discard(hi)
-                        live_slots.add(lo)
-                    top = count
-                rows = bucket(top)
-                if per_request_stop is not None:
-                    # the device decides: decode_block steps in one call while nothing waits to be admitted, staged or resumed (a slot
-                    # that stops inside the block freezes there), then each slot's new ids from its ring, as many as its record counted
-                    steps = decode_block if not queue and pending is None and not pre.active else 1
-                    engine.decode(steps, batch=rows)
-                    if on_step is not None:
-                        for _ in range(steps):
-                            on_step(sum(s is not None and not pre.parked(s) for s in slots))
-                    for i, req in enumerate(slots):
-                        if req is None or pre.parked(req):
-                            continue
-                        state = engine.stop_state(i)
-                        new = state.generated - len(req["out"])
-                        req["out"].extend(engine.read_tokens(i, new))
-                        if top_n >= 0:
-                            req["lp"].extend(engine.read_logprobs(i, new))
-                        if state.stopped:
-                            retire(i, req)
-                            live_slots.discard(i)
-                            finished.append((req["idx"], req["out"]) + ((req["lp"],) if top_n >= 0 else ()))
-                            slots[i] = None
-                    continue
-                engine.decode(1, batch=rows)
-                tokens = engine.read_pending(rows)
-                records = engine.read_pending_logprobs(rows) if top_n >= 0 else None
-                if on_step is not None:
-                    on_step(sum(s is not None and not pre.parked(s) for s in slots))
-                for i, req in enumerate(slots):
-                    if req is None or pre.parked(req):
-                        continue
-                    req["out"].append(tokens[i])
-                    if records is not None:
-                        req["lp"].append(records[i])
-                    if len(req["out"]) >= req["limit"] or ends(req, tokens[i]):
-                        retire(i, req)
-                        live_slots.discard(i)
-                        finished.append((req["idx"], req["out"]) + ((req["lp"],) if top_n >= 0 else ()))
-                        slots[i] = None
-    finally:
-        for slot in list(live_slots):
-            try:
-                engine.release(slot)
-            except RuntimeError:
-                pass
-    return finished
+    def _ended(self, state):  # the host's comparison; the request's own EOS ids where it has a grammar
+        token = state["out"][-1]
+        return len(state["out"]) >= state["limit"] or token == self.eos_token_id or (state["eos"] is not None and token in state["eos"])
+
+    def finished_in_staging(self, slot, state):
+        return self.engine.stop_state(slot).stopped if self.armed else self._ended(state)
+
+    def stepped(self, rows, active, steps):
+        if not self.armed:
+            self.tokens = self.engine.read_pending(rows)
+            self.records = self.engine.read_pending_logprobs(rows) if self.top_n >= 0 else None
+        if self.on_step is not None:
+            for _ in range(steps):
+                self.on_step(len(active))
+
+    def collect(self, slot, state):
+        if self.armed:  # the device decided: the slot's new ids from its ring, as many as its record counted
+            stop = self.engine.stop_state(slot)
+            new = stop.generated - len(state["out"])
+            state["out"].extend(self.engine.read_tokens(slot, new))
+            if self.top_n >= 0:
+                state["lp"].extend(self.engine.read_logprobs(slot, new))
+            return stop.stopped
+        state["out"].append(self.tokens[slot])
+        if self.records is not None:
+            state["lp"].append(self.records[slot])
+        return self._ended(state)
 
 
 def speculative_generate_ids(target: DecodeEngine, draft: DecodeEngine, prompt: Sequence[int], max_new_tokens: int,

@@ -1,4 +1,5 @@
-"""Preemption under KV page pressure: the one policy behind ``batch_generate_ids``, ``serve_requests`` and its packed twin.
+"""Preemption under KV page pressure: the policy of the one scheduler (tiny_llm_hip/scheduler.py) behind ``batch_generate_ids`` and
+``serve_requests``.
 
 Pure host logic over the engine's duck-typed slot interface (``step_pages`` / ``park`` / ``unpark`` / ``context_len`` / ``swap_stats``;
 DecodeEngine(swap_pages=N), or benches/serving.py's ScheduleOnlyEngine): no torch, no extension.  The policy is vLLM's: when the next
@@ -8,7 +9,7 @@ decode step needs more pages than the pool can give, the youngest sequence gives
            1. the staging request, if it holds pages (the youngest staged one first): it is RELEASED and put back at the front of the
               queue -- recomputation is cheapest for the youngest, and the prefix cache helps it;
            2. else the running request admitted last: it is PARKED in place (its K/V goes to host memory, every per-slot setting stays);
-              holes are closed as before with ``move``, which carries a parked slot's records.
+              holes are closed as before with ``move`` (scheduler.close_holes), which carries a parked slot's records.
            With one running request left that still does not fit, nothing is done: the step raises the engine's own
            "KV page pool exhausted".
   resume   the oldest parked request first, when ``obtainable >= its pages + one per running request``.
@@ -16,8 +17,8 @@ decode step needs more pages than the pool can give, the youngest sequence gives
            pool cannot hold it while other requests are alive to free pages (``may_prefill``) -- a lone request goes ahead and gets the
            engine's error.
 
-Running requests are the loops' own state dicts: the helper stamps ``state["admitted"]`` (admission order) and ``state["parked"]``.
-An engine without swap space makes every method a no-op that answers "go ahead": the loops are then the programs they were.
+Running requests are the scheduler's state dicts: the helper stamps ``state["admitted"]`` (admission order) and ``state["parked"]``.
+An engine without swap space makes every method a no-op that answers "go ahead": the scheduler is then the program it was.
 """
 
 from __future__ import annotations
