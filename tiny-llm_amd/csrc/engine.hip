@@ -24,6 +24,7 @@
 #include "kv_swap.h"
 #include "pool.h"
 #include "lora.h"
+#include "slot_settings.h"
 #include "slot_table.h"
 #include "stop.h"
 #include "stop_set.h"
@@ -200,75 +201,29 @@ struct tl_engine {
     long swap_parks = 0, swap_unparks = 0, swap_pages_out = 0, swap_pages_in = 0;
     bool slot_runs(int slot) const { return table.runs(slot); }
     tl_engine_stats stats{};
-    // per-slot sampling (tl_engine_set_sampling, sample.h): host mirror + device arrays [max_batch] each, written on the stream between
-    // steps by poke; temperature 0 = greedy (the default, and what begin / release restore)
-    struct SampleParams {
-        float temperature = 0.f;
-        int top_k = 0;
-        float top_p = 0.f;
-        uint64_t seed = 0;
-        bool samples() const { return temperature > 0.f; }
-    };
-    std::vector<SampleParams> smp;
-    DeviceBlock smp_mem;
-    float *smp_temp = nullptr, *smp_topp = nullptr;
-    int32_t *smp_topk = nullptr;
-    uint64_t *smp_seed = nullptr;
-    // per-slot log-probability records (tl_engine_set_logprobs, logprob.h): allocated on the first set_logprobs -- top-N per slot
-    // (-1: off), the record ring [max_batch, ring_cap] and the pending record per slot; the host mirror of top-N and, per slot, the
-    // value of the slot's `produced` when its records began (tokens since then have records)
-    DeviceBlock lp_mem;
-    int32_t *lp_topn = nullptr;
-    uint32_t *lp_ring = nullptr, *lp_pending = nullptr;
-    std::vector<int> lp_n, lp_from;
-    // per-slot logit processing (tl_engine_set_penalties / tl_engine_set_logit_bias, logit_process.h): the host mirror, and -- allocated by the
-    // first call that makes a slot process -- the history table [max_batch, vocab], the processed rows [max(max_batch, 8), vocab] the step
-    // end chooses from, and the per-slot parameters and bias lists
-    struct PenaltyParams {
-        float repetition = 1.f, presence = 0.f, frequency = 0.f;
-        std::vector<int32_t> bias_ids;
-        std::vector<float> bias_values;
-        const tl_grammar *grammar = nullptr;  // tl_engine_set_grammar (borrowed)
-        bool processes() const { return repetition != 1.f || presence != 0.f || frequency != 0.f || !bias_ids.empty() || grammar; }
-    };
-    std::vector<PenaltyParams> pen;
-    DeviceBlock pen_mem;
-    uint16_t *pen_history = nullptr, *pen_rows = nullptr;
-    float *pen_rep = nullptr, *pen_pres = nullptr, *pen_freq = nullptr, *pen_bias_values = nullptr;
-    int32_t *pen_bias_n = nullptr, *pen_bias_ids = nullptr;
-    // grammars (tl_engine_set_grammar, grammar.h): allocated by the first call that sets one -- per slot the automaton's device pointer
-    // and the state record; gr_pending (kept for every slot, grammar or not): the slot holds a pending token no step has consumed yet
-    DeviceBlock gr_mem, gr_stack_mem;
-    const GrammarDev **gr_ptr = nullptr;
-    GrammarRecord *gr_state = nullptr;
-    std::vector<char> gr_pending;
-    GrammarStackRecord *gr_stack = nullptr;  // [slots] the records of slots with a stack grammar: allocated by the first one set
-    // per-slot truncation (tl_engine_set_truncation / tl_engine_set_mirostat, truncate.h): the host mirror, and -- allocated by the first
-    // call that makes a slot truncate -- the filtered rows [max(max_batch, 8), vocab] the step end chooses from, the per-slot parameters
-    // and Mirostat's state mu [max_batch] (NaN: no Mirostat) and the kept log-sums [max(max_batch, 8)] of the rows of one launch
-    struct TruncParams {
-        float min_p = 0.f, typical_p = 1.f, tau = 0.f, eta = 0.f;
-        bool stateless() const { return min_p > 0.f || (typical_p > 0.f && typical_p < 1.f); }
-        bool mirostat() const { return tau > 0.f; }
-        bool truncates() const { return stateless() || mirostat(); }
-    };
-    std::vector<TruncParams> trn;
-    DeviceBlock trn_mem;
-    uint16_t *trn_rows = nullptr;
-    float *trn_minp = nullptr, *trn_typ = nullptr, *trn_tau = nullptr, *trn_eta = nullptr, *trn_mu = nullptr, *trn_logsum = nullptr;
+    // the per-slot settings (slot_settings.h): the host mirrors of sampling, log-probability records, penalties / bias / grammar,
+    // truncation, the adapter id and the stop conditions, and the layout of each feature's device block.  Its calls report edits;
+    // settings_apply puts them on the stream.  The blocks are allocated by the first call that needs them (settings_blocks; the
+    // sampling block with the engine, the adapter ids inside lora_mem); the launches take their addresses from sdev()
+    SlotSettings settings;
+    DeviceBlock settings_mem[SB_COUNT];
+    template <class T>
+    T *sdev(int block, size_t off) const {
+        return block == SB_LORA ? (T *)((char *)lora_slot_dev + off) : settings_mem[block].at<T>(off);
+    }
+    const tl_grammar *grammar_of(int slot) const { return (const tl_grammar *)settings.slots[slot].pen.grammar.id; }
     // tl_engine_score: the logits of one block of rows and the per-row targets / results, allocated on first use
     DeviceBlock score_mem;
     uint16_t *score_logits = nullptr;
     int32_t *score_ids = nullptr, *score_argmax = nullptr;
     float *score_lp = nullptr;
     // embeddings (tl_engine_embed / _embed_packed, pool.h): the vectors of a call's finishing sequences [16, hidden] fp32, allocated by the
-    // first embed call; the running sums of mean pooling [max_batch, hidden] fp32, allocated by the first MEAN call; and per slot (host
-    // only) how many rows its running sum holds, -1: none
+    // first embed call; the running sums of mean pooling [max_batch, hidden] fp32, allocated by the first MEAN call (how many rows a
+    // slot's running sum holds: settings.slots[slot].emb_rows)
     DeviceBlock emb_out_mem, emb_sums_mem;
     float *emb_out = nullptr, *emb_sums = nullptr;
-    std::vector<int> emb_rows;
-    // LoRA adapters (tl_engine_lora_load / tl_engine_set_lora, lora.h): per slot the adapter id on the host (-1: none; kept for every
-    // slot) and -- allocated by the first load -- the device table [TL_MAX_LORA_ADAPTERS][layers][4 groups], the per-slot ids the
+    // LoRA adapters (tl_engine_lora_load / tl_engine_set_lora, lora.h; per slot the adapter id: settings.slots[slot].lora, -1: none):
+    // allocated by the first load -- the device table [TL_MAX_LORA_ADAPTERS][layers][4 groups], the per-slot ids the
     // decode step's tiles look up, the tile lists (decode: fixed blocks of 16 rows; prefill: written per pass), the shrink's partials and
     // sums of squares, and the rows of residual + delta ahead of a base projection's residual epilogue
     enum { LORA_QKV, LORA_O, LORA_GU, LORA_DOWN, LORA_GROUPS };
@@ -279,7 +234,6 @@ struct tl_engine {
         std::vector<char> has;  // [layers][groups]: the adapter adapts that group
     };
     std::vector<LoraResident> lora_ad;
-    std::vector<int> lora_of;
     DeviceBlock lora_mem;
     LoraDesc *lora_table = nullptr;
     int32_t *lora_slot_dev = nullptr;
@@ -287,26 +241,13 @@ struct tl_engine {
     float *lora_partial = nullptr, *lora_ss = nullptr;
     uint16_t *lora_tmp = nullptr;
     long lora_steps = 0, lora_prefill_rows = 0;
-    bool lora_slot(int slot) const { return lora_of[slot] >= 0; }
-    // stop conditions (tl_engine_set_stop, stop.h): per slot the host mirror of (set, budget, armed) and the records as the last
-    // reconciliation read them; allocated by the first call that arms a slot: the per-slot set pointers, armed words, budgets, automaton
-    // states and records.  stop_dirty: a stop launch was enqueued since the records were last read (stop_reconcile)
-    struct StopSlot {
-        const tl_stop *set = nullptr;
-        int max_new = 0;
-        bool armed = false;
-    };
-    std::vector<StopSlot> stop;
-    std::vector<StopRecord> stop_host;
-    DeviceBlock stop_mem;
-    const StopDev **stop_sets = nullptr;
-    int32_t *stop_armed = nullptr, *stop_max_new = nullptr, *stop_automaton = nullptr;
-    StopRecord *stop_rec = nullptr;
+    bool lora_slot(int slot) const { return settings.slots[slot].lora >= 0; }
+    // stop conditions (tl_engine_set_stop, stop.h): a stop launch was enqueued since the records were last read (stop_reconcile)
     bool stop_dirty = false;
 
     bool warmed = false;
     // a captured decode step: the executable graph and, where the step may ride the AQL route (below), the same nodes as a program of
-    // dispatch packets.  Keyed by (batch, SplitPlan::key() | StepFeatures::key_bits())
+    // dispatch packets.  Keyed by (batch, SplitPlan::key() | step_key_bits(features))
     struct DecodePlan {
         hipGraphExec_t exec = nullptr;
         std::unique_ptr<AqlProgram> program;
@@ -449,26 +390,6 @@ static __global__ __launch_bounds__(1024) void sample_rows_kernel(const uint16_t
     if (threadIdx.x == 0) ids[i] = tok;
 }
 
-// The per-slot predicates of a step's plan (StepFeatures below ORs them over the step's slots).  Does the slot, taking part in a decode
-// step, sample?  (with no such slot a step is the greedy program)
-static bool step_samples_slot(const tl_engine *e, int slot) { return e->slot_runs(slot) && e->smp[slot].samples(); }
-
-// the device copy of a slot's parameters follows the host mirror (stream-ordered, between steps)
-static int smp_write(tl_engine *e, int slot, const tl_engine::SampleParams &v) {
-    Pokes pk;
-    poke_float(pk, e->smp_temp + slot, v.temperature);
-    pk.emplace_back(e->smp_topk + slot, v.top_k);
-    poke_float(pk, e->smp_topp + slot, v.top_p);
-    poke_u64(pk, e->smp_seed + slot, v.seed);
-    e->smp[slot] = v;
-    return poke(e, pk);
-}
-static bool smp_is_default(const tl_engine::SampleParams &v) { return v.temperature == 0.f && v.top_k == 0 && v.top_p == 0.f && v.seed == 0; }
-static int smp_reset(tl_engine *e, int slot) { return smp_is_default(e->smp[slot]) ? TL_OK : smp_write(e, slot, tl_engine::SampleParams{}); }
-
-// ... record log-probabilities?
-static bool step_logprobs_slot(const tl_engine *e, int slot) { return !e->lp_n.empty() && e->slot_runs(slot) && e->lp_n[slot] >= 0; }
-
 // StepEndArgs over the engine's state: rows of `logits` for slots slot0.., the context advance (1: decode; 0: a prefill sets it on the host
 // side) and the next embedding rows into x; tile maxima, sums of squares and stamps where the step has them
 static StepEndArgs step_end_args(const tl_engine *e, const uint16_t *logits, int slot0, int advance, uint16_t *x, const f32x2 *tile_max = nullptr,
@@ -505,12 +426,14 @@ static StepEndArgs step_end_args(const tl_engine *e, const uint16_t *logits, int
 // (which also samples) when a slot records log-probabilities
 // `raw`: the rows of the model's logits where s.logits are processed rows (logit_process.h) -- the logprob twin records from them
 static void launch_step_end(tl_engine *e, const StepEndArgs &s, int rows, bool samples, bool logprobs, const uint16_t *raw = nullptr) {
+    const SlotSettings::Offsets &at = e->settings.at;
+    const SampleStepEndArgs q{s, e->sdev<float>(SB_SAMPLE, at.smp_temp), e->sdev<int32_t>(SB_SAMPLE, at.smp_topk), e->sdev<float>(SB_SAMPLE, at.smp_topp),
+                              e->sdev<uint64_t>(SB_SAMPLE, at.smp_seed)};
     if (logprobs) {
-        LogprobStepEndArgs l{{s, e->smp_temp, e->smp_topk, e->smp_topp, e->smp_seed}, e->lp_topn, e->lp_ring, e->lp_pending, nullptr};
+        LogprobStepEndArgs l{q, e->sdev<int32_t>(SB_LOGPROB, at.lp_topn), e->sdev<uint32_t>(SB_LOGPROB, at.lp_ring), e->sdev<uint32_t>(SB_LOGPROB, at.lp_pending), nullptr};
         if (raw) l.choice = s.logits, l.q.s.logits = raw;
         hipLaunchKernelGGL(logprob_step_end_kernel, dim3(rows), dim3(1024), 0, e->stream, l);
     } else if (samples) {
-        const SampleStepEndArgs q{s, e->smp_temp, e->smp_topk, e->smp_topp, e->smp_seed};
         hipLaunchKernelGGL(sample_step_end_kernel, dim3(rows), dim3(1024), 0, e->stream, q);
     } else {
         hipLaunchKernelGGL(step_end_kernel, dim3(rows), dim3(1024), 0, e->stream, s);
@@ -520,271 +443,130 @@ static void launch_step_end(tl_engine *e, const StepEndArgs &s, int rows, bool s
 // tl_engine_score: rows of the lm_head per W4 GEMM + logprob launch (the scratch holds one block of logits: 311 MB at Qwen3's vocabulary)
 constexpr int SCORE_BLOCK_ROWS = 1024;
 
-// ---- log-probability records (logprob.h) ----------------------------------------------------------------
-// the slot's top-N on the device follows the host mirror (stream-ordered, between steps); the first switch-on allocates the records
-static int lp_write(tl_engine *e, int slot, int top_n) {
-    if (e->lp_n.empty() ? top_n < 0 : e->lp_n[slot] == top_n) return TL_OK;
-    if (!e->lp_mem) {
-        const int B = e->cfg.max_batch;
-        const size_t rec = (size_t)LP_RECORD_WORDS * 4, bytes = (size_t)B * 4 + ((size_t)B * e->ring_cap + B) * rec;
-        // all ones: top-N -1 (off), and a record nobody wrote reads as logprob NaN with ids -1
-        TL_TRY(alloc_filled(e->lp_mem, bytes, "engine_set_logprobs: hipMalloc(records) failed", [&](char *m) -> int {
-            const hipError_t he = hipMemsetAsync(m, 0xff, (size_t)B * 4 + (size_t)B * rec, e->stream);
-            // (the text TL_HIP gave this call when it stood here on e->lp_mem)
-            return he == hipSuccess ? TL_OK : fail(TL_ERR_HIP, std::string("hipMemsetAsync(e->lp_mem, 0xff, (size_t)B * 4 + (size_t)B * rec, e->stream): ") + hipGetErrorString(he));
+// ---- the per-slot settings on the device (slot_settings.h) ----------------------------------------------------------------------------
+// the sizes the record's layouts are made of are the device headers'
+static_assert(sizeof(StopMirror) == sizeof(StopRecord) && offsetof(StopMirror, reason) == offsetof(StopRecord, reason) &&
+                  offsetof(StopMirror, context) == offsetof(StopRecord, context) && offsetof(StopMirror, cut_bytes) == offsetof(StopRecord, cut_bytes),
+              "StopMirror is the device's stop record");
+static_assert(offsetof(GrammarRecord, tag) == 0 && offsetof(GrammarRecord, state) == 4 && offsetof(GrammarStackRecord, rec) == 0,
+              "a grammar record starts with {tag, state}; a stack grammar's with the packed word whose low half is the tag");
+static_assert(sizeof(GrammarDev *) == 8 && sizeof(StopDev *) == 8 && LPR_MAX_BIAS == TL_MAX_LOGIT_BIAS, "pointers are two words");
+static SlotSettings::Sizes settings_sizes(const tl_engine *e) {
+    return {e->cfg.max_batch, e->cfg.vocab_size, e->ring_cap, LP_RECORD_WORDS, LP_MAX_TOP, LPR_MAX_BIAS, (int)sizeof(GrammarRecord), (int)sizeof(GrammarStackRecord),
+            (int)sizeof(StopRecord), SMP_MAX_VOCAB, LORA_NONE};
+}
+
+// What the allocation of each block reports when it fails (fill: the memsets and the launch that give a fresh block its first values), and
+// whether the block counts as workspace
+struct SettingsBlockTexts {
+    const char *malloc_failed, *fill_failed;
+    bool counted;
+};
+static const SettingsBlockTexts SETTINGS_BLOCK_TEXTS[SB_COUNT] = {
+    {"engine_create: hipMalloc(sampling) failed", "engine_create: memset failed", false},
+    {"engine_set_logprobs: hipMalloc(records) failed", nullptr, false},  // (the fill's text: below)
+    {"engine: hipMalloc(logit processing) failed", "engine: memset(logit processing) failed", true},
+    {"engine: hipMalloc(grammar slots) failed", "engine: memset(grammar slots) failed", true},
+    {"engine: hipMalloc(stack grammar slots) failed", "engine: memset(stack grammar slots) failed", true},
+    {"engine: hipMalloc(truncation) failed", "engine: memset(truncation) failed", true},
+    {"engine_set_stop: hipMalloc(stop records) failed", "engine_set_stop: memset(stop records) failed", true},
+    {nullptr, nullptr, false},  // (the adapter ids: inside lora_mem, lora_alloc)
+};
+// the blocks of `needs` that do not exist yet, each from its layout: all-or-nothing per block, filled on the engine stream
+static int settings_blocks(tl_engine *e, unsigned needs) {
+    for (int b = 0; b < SB_LORA; ++b) {
+        if (!(needs >> b & 1u) || e->settings_mem[b]) continue;
+        const BlockLayout &lay = e->settings.layout(b);
+        const SettingsBlockTexts &t = SETTINGS_BLOCK_TEXTS[b];
+        TL_TRY(alloc_filled(e->settings_mem[b], lay.bytes, t.malloc_failed, [&](char *m) -> int {
+            for (const BlockFill &f : lay.fill) {
+                if (f.word == 0u || f.word == 0xffffffffu) {
+                    const hipError_t he = hipMemsetAsync(m + f.off, (int)(f.word & 0xffu), f.bytes, e->stream);
+                    if (he == hipSuccess) continue;
+                    // (the log-probability records': the text TL_HIP gave this call when it stood on e->lp_mem)
+                    return fail(TL_ERR_HIP, t.fill_failed ? std::string(t.fill_failed)
+                                                          : std::string("hipMemsetAsync(e->lp_mem, 0xff, (size_t)B * 4 + (size_t)B * rec, e->stream): ") + hipGetErrorString(he));
+                }
+                const int n = (int)(f.bytes / 4);
+                hipLaunchKernelGGL(fill_i32_kernel, dim3(ceil_div((long)n, 256)), dim3(256), 0, e->stream, (int32_t *)(m + f.off), (int32_t)f.word, n);
+                TL_CHECK_LAUNCH("engine logit-processing init");
+            }
+            return TL_OK;
         }));
-        e->lp_topn = e->lp_mem.at<int32_t>();
-        e->lp_pending = e->lp_mem.at<uint32_t>((size_t)B * 4);
-        e->lp_ring = e->lp_pending + (size_t)B * LP_RECORD_WORDS;
-        e->lp_n.assign(B, -1);
-        e->lp_from.assign(B, 0);
+        if (t.counted) e->stats.workspace_bytes += lay.bytes;
+        e->settings.created(b);
     }
-    Pokes pk;
-    pk.emplace_back(e->lp_topn + slot, top_n);
-    if (e->lp_n[slot] < 0) e->lp_from[slot] = e->table.slots[slot].produced;  // records begin with the next produced token
-    e->lp_n[slot] = top_n;
-    return poke(e, pk);
-}
-
-// tl_engine_move (move = true) / tl_engine_fork: dst takes src's setting and pending record; a move switches src off
-static int lp_carry(tl_engine *e, int src, int dst, bool move) {
-    if (e->lp_n.empty()) return TL_OK;
-    const int n = e->lp_n[src];
-    TL_TRY(lp_write(e, dst, n));
-    e->lp_from[dst] = 0;  // dst's `produced` restarts at 0 with the sequence
-    TL_HIP(hipMemcpyAsync(e->lp_pending + (size_t)dst * LP_RECORD_WORDS, e->lp_pending + (size_t)src * LP_RECORD_WORDS, LP_RECORD_WORDS * 4,
-                          hipMemcpyDeviceToDevice, e->stream));
-    return move ? lp_write(e, src, -1) : TL_OK;
-}
-
-// ---- per-slot logit processing (logit_process.h) ------------------------------------------------------------
-// does the slot, taking part in a step, process its logits?
-static bool step_processes_slot(const tl_engine *e, int slot) { return e->pen_mem && e->slot_runs(slot) && e->pen[slot].processes(); }
-// ... and the grammar it processes them under, or null (with one the step's processing launch runs in its regex mode; with a stack
-// grammar, g->stack, in its stack mode: logit_process.h)
-static const tl_grammar *step_grammar_slot(const tl_engine *e, int slot) { return step_processes_slot(e, slot) ? e->pen[slot].grammar : nullptr; }
-
-// the per-slot automaton pointers and state records: allocated by the first tl_engine_set_grammar; with `stack`, the records of slots
-// with a stack grammar too: allocated by the first one set.  Each block zeroed, and counted as workspace when it is made.
-static int gr_alloc(tl_engine *e, bool stack) {
-    const auto block = [e](DeviceBlock &mem, size_t bytes, const std::string &what) -> int {
-        if (mem) return TL_OK;
-        TL_TRY(alloc_filled(mem, bytes, "engine: hipMalloc(" + what + ") failed", [&](char *m) -> int {
-            return hipMemsetAsync(m, 0, bytes, e->stream) == hipSuccess ? TL_OK : fail(TL_ERR_HIP, "engine: memset(" + what + ") failed");
-        }));
-        e->stats.workspace_bytes += bytes;
-        return TL_OK;
-    };
-    const size_t B = (size_t)e->cfg.max_batch;
-    TL_TRY(block(e->gr_mem, B * (sizeof(GrammarDev *) + sizeof(GrammarRecord)), "grammar slots"));
-    e->gr_ptr = e->gr_mem.at<const GrammarDev *>();
-    e->gr_state = e->gr_mem.at<GrammarRecord>(B * sizeof(GrammarDev *));
-    if (!stack) return TL_OK;
-    TL_TRY(block(e->gr_stack_mem, B * sizeof(GrammarStackRecord), "stack grammar slots"));
-    e->gr_stack = e->gr_stack_mem.at<GrammarStackRecord>();
     return TL_OK;
 }
-// the slot's record becomes {no context length, state}; a stack grammar's: {no context length, (state, depth 0, word 0)} (the stack
-// words are masked by the depth when they are read)
-static void gr_poke_state(tl_engine *e, int slot, const tl_grammar *g, Pokes &pk) {
-    int32_t *rec = g->stack ? (int32_t *)&e->gr_stack[slot].rec : &e->gr_state[slot].tag;
-    pk.emplace_back(rec, -1);
-    pk.emplace_back(rec + 1, g->start);
-}
-
-// the history table, the processed rows and the per-slot parameters: one allocation, made by the first call that makes a slot process
-static int pen_alloc(tl_engine *e) {
-    if (e->pen_mem) return TL_OK;
-    const size_t B = (size_t)e->cfg.max_batch, V = (size_t)e->cfg.vocab_size;
-    Carve carve;
-    const size_t o_hist = carve(B * V * 2), o_rows = carve(std::max<size_t>(B, 8) * V * 2), o_rep = carve(B * 4), o_pres = carve(B * 4),
-                 o_freq = carve(B * 4), o_n = carve(B * 4), o_ids = carve(B * LPR_MAX_BIAS * 4), o_vals = carve(B * LPR_MAX_BIAS * 4);
-    // everything zero (empty histories, presence / frequency 0, empty lists) but the repetition penalties: 1
-    TL_TRY(alloc_filled(e->pen_mem, carve.off, "engine: hipMalloc(logit processing) failed", [&](char *m) -> int {
-        if (hipMemsetAsync(m, 0, carve.off, e->stream) != hipSuccess) return fail(TL_ERR_HIP, "engine: memset(logit processing) failed");
-        hipLaunchKernelGGL(fill_i32_kernel, dim3(ceil_div((long)B, 256)), dim3(256), 0, e->stream, (int32_t *)(m + o_rep), __builtin_bit_cast(int32_t, 1.0f), (int)B);
-        TL_CHECK_LAUNCH("engine logit-processing init");
-        return TL_OK;
-    }));
-    char *m = e->pen_mem.at();
-    e->pen_history = (uint16_t *)(m + o_hist);
-    e->pen_rows = (uint16_t *)(m + o_rows);
-    e->pen_rep = (float *)(m + o_rep), e->pen_pres = (float *)(m + o_pres), e->pen_freq = (float *)(m + o_freq);
-    e->pen_bias_n = (int32_t *)(m + o_n), e->pen_bias_ids = (int32_t *)(m + o_ids), e->pen_bias_values = (float *)(m + o_vals);
-    e->stats.workspace_bytes += carve.off;
-    return TL_OK;
-}
-
-// The processing launch of a step reads a row's parameters from the device whatever the row's `live` word says, and a row that processes
-// counts its pending token and advances its grammar record.  A PARKED slot (tl_engine_park) keeps its pending token, so its device
-// parameters are switched to neutral while it is parked (on = false: penalties 1 / 0 / 0, an empty bias list, no automaton -- the row is
-// copied, nothing of the slot is written) and written back from the host mirror by tl_engine_unpark (on = true).  The bias entries, the
-// history row and the grammar record themselves are not touched either way.
-static int pen_device_switch(tl_engine *e, int slot, bool on) {
-    if (!e->pen_mem) return TL_OK;
-    const tl_engine::PenaltyParams neutral{};
-    const tl_engine::PenaltyParams &v = on ? e->pen[slot] : neutral;
-    Pokes pk;
-    poke_float(pk, e->pen_rep + slot, v.repetition);
-    poke_float(pk, e->pen_pres + slot, v.presence);
-    poke_float(pk, e->pen_freq + slot, v.frequency);
-    pk.emplace_back(e->pen_bias_n + slot, (int32_t)v.bias_ids.size());
-    if (e->gr_mem) poke_u64(pk, e->gr_ptr + slot, (uint64_t)(uintptr_t)(v.grammar ? v.grammar->dev : nullptr));
-    return poke(e, pk);
-}
-
-// the slot's parameters and bias list become `v` (validated by the caller): the device copy follows the host mirror, stream-ordered
-// between steps.  History is tracked from the call that makes the slot process: that call empties the slot's row of the table.
-static int pen_write(tl_engine *e, int slot, const tl_engine::PenaltyParams &v) {
-    tl_engine::PenaltyParams &cur = e->pen[slot];
-    const bool was = cur.processes(), now = v.processes();
-    if (!e->pen_mem && !now) return TL_OK;  // neutral on an engine that never processed: nothing to write
-    TL_TRY(pen_alloc(e));
-    const size_t V = (size_t)e->cfg.vocab_size;
-    if (now && !was) TL_HIP(hipMemsetAsync(e->pen_history + (size_t)slot * V, 0, V * 2, e->stream));
-    Pokes pk;
-    if (cur.repetition != v.repetition) poke_float(pk, e->pen_rep + slot, v.repetition);
-    if (cur.presence != v.presence) poke_float(pk, e->pen_pres + slot, v.presence);
-    if (cur.frequency != v.frequency) poke_float(pk, e->pen_freq + slot, v.frequency);
-    const bool bias_changed = cur.bias_ids != v.bias_ids || memcmp(cur.bias_values.data(), v.bias_values.data(), v.bias_values.size() * 4) != 0;
-    if (bias_changed) pk.emplace_back(e->pen_bias_n + slot, (int32_t)v.bias_ids.size());
-    if (cur.grammar != v.grammar) {  // the automaton's pointer (two words) and, for a new one, the record at its start state
-        TL_TRY(gr_alloc(e, v.grammar && v.grammar->stack));
-        poke_u64(pk, e->gr_ptr + slot, (uint64_t)(uintptr_t)(v.grammar ? v.grammar->dev : nullptr));
-        if (v.grammar) gr_poke_state(e, slot, v.grammar, pk);
+// An edit list in order on the engine stream.  Words join `pk` -- the caller's own words may wait there -- and are poked, eight per
+// launch, ahead of the next copy, fill or upload and at the end; within one list no word is written twice
+static int settings_apply(tl_engine *e, const SettingsEdits &ed, Pokes &pk) {
+    for (const SettingsEdit &x : ed.list) {
+        char *at = e->sdev<char>(x.block, x.off);
+        if (x.kind == SettingsEdit::WORD) {
+            pk.emplace_back((int32_t *)at, x.word);
+            continue;
+        }
+        if (!pk.empty()) TL_TRY(poke(e, pk));
+        if (x.kind == SettingsEdit::COPY) TL_HIP(hipMemcpyAsync(at, e->sdev<char>(x.block, x.from), x.bytes, hipMemcpyDeviceToDevice, e->stream));
+        else if (x.kind == SettingsEdit::FILL) TL_HIP(hipMemsetAsync(at, 0, x.bytes, e->stream));
+        else TL_HIP(hipMemcpyAsync(at, x.host, x.bytes, hipMemcpyHostToDevice, e->stream));
     }
-    cur = v;
-    if (bias_changed && !cur.bias_ids.empty()) {  // (from the mirror: it outlives the copy)
-        TL_HIP(hipMemcpyAsync(e->pen_bias_ids + (size_t)slot * LPR_MAX_BIAS, cur.bias_ids.data(), cur.bias_ids.size() * 4, hipMemcpyHostToDevice, e->stream));
-        TL_HIP(hipMemcpyAsync(e->pen_bias_values + (size_t)slot * LPR_MAX_BIAS, cur.bias_values.data(), cur.bias_values.size() * 4, hipMemcpyHostToDevice, e->stream));
-    }
-    if (!pk.empty()) TL_TRY(poke(e, pk));
-    return e->table.slots[slot].parked ? pen_device_switch(e, slot, false) : TL_OK;  // a parked slot's row of a step stays a copy (below)
+    return pk.empty() ? TL_OK : poke(e, pk);
 }
-static int pen_reset(tl_engine *e, int slot) { return e->pen[slot].processes() ? pen_write(e, slot, tl_engine::PenaltyParams{}) : TL_OK; }
-
-// tl_engine_move (move = true) / tl_engine_fork: dst takes src's parameters, bias list and history (a device-to-device copy of the
-// slot's row on the engine stream: no synchronisation); a move makes src neutral
-static int pen_carry(tl_engine *e, int src, int dst, bool move) {
-    if (!e->pen[src].processes() && !e->pen[dst].processes()) return TL_OK;
-    const tl_engine::PenaltyParams v = e->pen[src];
-    TL_TRY(pen_write(e, dst, v));
-    if (v.processes()) {
-        const size_t V = (size_t)e->cfg.vocab_size;
-        TL_HIP(hipMemcpyAsync(e->pen_history + (size_t)dst * V, e->pen_history + (size_t)src * V, V * 2, hipMemcpyDeviceToDevice, e->stream));
+// A setter's call of the record: the refusal, or the blocks it needs and its edits.  A block that cannot be made leaves the slot's
+// mirror as it was
+template <class Call>
+static int settings_set(tl_engine *e, int slot, Pokes &pk, Call call) {
+    SettingsEdits ed;
+    SlotSettings::State before = e->settings.slots[slot];
+    if (const char *why = call(ed)) return fail(TL_ERR_INVALID, why);
+    const int rc = settings_blocks(e, ed.needs);
+    if (rc != TL_OK) {
+        e->settings.slots[slot] = std::move(before);
+        return rc;
     }
-    if (v.grammar && v.grammar->stack) {  // the automaton state travels like the history
-        TL_HIP(hipMemcpyAsync(e->gr_stack + dst, e->gr_stack + src, sizeof(GrammarStackRecord), hipMemcpyDeviceToDevice, e->stream));
-    } else if (v.grammar) {
-        TL_HIP(hipMemcpyAsync(e->gr_state + dst, e->gr_state + src, sizeof(GrammarRecord), hipMemcpyDeviceToDevice, e->stream));
-    }
-    return move ? pen_reset(e, src) : TL_OK;
+    return settings_apply(e, ed, pk);
 }
 
 // the processing launch over `rows` rows of raw logits for slots slot0 .. (logit_process.h): processed rows into `out`.  A decode step
 // passes the pending tokens (counted before the row is processed); a prefill's last row has none to count.
 static void launch_logit_process(tl_engine *e, const uint16_t *logits, uint16_t *out, int rows, int slot0, const int32_t *tokens, bool grammar,
                                  bool stack, ProfCtx *pc) {
-    const LogitProcessArgs a{logits, out, e->cfg.vocab_size, slot0, e->pen_history, e->pen_rep, e->pen_pres, e->pen_freq, e->pen_bias_n,
-                             e->pen_bias_ids, e->pen_bias_values, tokens, pc ? pc->buf : nullptr,
-                             grammar ? e->gr_ptr : nullptr, grammar ? e->gr_state : nullptr, grammar ? e->context_lens : nullptr,
+    const SlotSettings::Offsets &at = e->settings.at;
+    const LogitProcessArgs a{logits, out, e->cfg.vocab_size, slot0, e->sdev<uint16_t>(SB_PROCESS, at.pen_history), e->sdev<float>(SB_PROCESS, at.pen_rep),
+                             e->sdev<float>(SB_PROCESS, at.pen_pres), e->sdev<float>(SB_PROCESS, at.pen_freq), e->sdev<int32_t>(SB_PROCESS, at.pen_bias_n),
+                             e->sdev<int32_t>(SB_PROCESS, at.pen_bias_ids), e->sdev<float>(SB_PROCESS, at.pen_bias_values), tokens, pc ? pc->buf : nullptr,
+                             grammar ? e->sdev<const GrammarDev *>(SB_GRAMMAR, at.gr_ptr) : nullptr,
+                             grammar ? e->sdev<GrammarRecord>(SB_GRAMMAR, at.gr_state) : nullptr, grammar ? e->context_lens : nullptr,
                              tokens ? e->live : nullptr};
     const dim3 grid(ceil_div(e->cfg.vocab_size, LPR_CHUNK), rows);
-    if (stack) hipLaunchKernelGGL(logit_process_stack_kernel, grid, dim3(LPR_THREADS), 0, e->stream, LogitProcessStackArgs{a, e->gr_stack});
+    if (stack) hipLaunchKernelGGL(logit_process_stack_kernel, grid, dim3(LPR_THREADS), 0, e->stream, LogitProcessStackArgs{a, e->sdev<GrammarStackRecord>(SB_STACK, 0)});
     else if (grammar) hipLaunchKernelGGL(logit_process_kernel<true>, grid, dim3(LPR_THREADS), 0, e->stream, a);
     else hipLaunchKernelGGL(logit_process_kernel<false>, grid, dim3(LPR_THREADS), 0, e->stream, a);
     if (pc) prof_after(pc, 7, (int)(grid.x * grid.y));
 }
 
-// ---- per-slot truncation (truncate.h) -------------------------------------------------------------------------
-// does the slot, taking part in a step, truncate?  Truncation applies to a slot that samples: a greedy slot is never filtered (every
-// filter keeps the maximum), so its parameters do not change the plan.
-static bool step_truncates_slot(const tl_engine *e, int slot) {
-    return e->trn_mem && e->slot_runs(slot) && e->trn[slot].truncates() && e->smp[slot].samples();
-}
-// ... with Mirostat?  Its update launch reads the token the step end has just stored -- a plain store, which only a launch boundary
-// with cache maintenance hands over: such a plan keeps the hipGraphLaunch route (tl_engine_replay_route says so)
-static bool step_mirostat_slot(const tl_engine *e, int slot) { return step_truncates_slot(e, slot) && e->trn[slot].mirostat(); }
-
-// the filtered rows, the per-slot parameters and the per-row log-sums: one allocation, made by the first call that makes a slot truncate
-static int trn_alloc(tl_engine *e) {
-    if (e->trn_mem) return TL_OK;
-    const size_t B = (size_t)e->cfg.max_batch, R = std::max<size_t>(B, 8), V = (size_t)e->cfg.vocab_size;
-    Carve carve;
-    const size_t o_rows = carve(R * V * 2), o_minp = carve(B * 4), o_tau = carve(B * 4), o_eta = carve(B * 4), o_sum = carve(R * 4), o_typ = carve(B * 4),
-                 o_mu = carve(B * 4);
-    // zero (min-p, tau, eta off) up to the typical-p array; typical-p and mu: all ones, a NaN (typical-p off, no Mirostat)
-    TL_TRY(alloc_filled(e->trn_mem, carve.off, "engine: hipMalloc(truncation) failed", [&](char *m) -> int {
-        const bool ok = hipMemsetAsync(m, 0, o_typ, e->stream) == hipSuccess && hipMemsetAsync(m + o_typ, 0xff, carve.off - o_typ, e->stream) == hipSuccess;
-        return ok ? TL_OK : fail(TL_ERR_HIP, "engine: memset(truncation) failed");
-    }));
-    char *m = e->trn_mem.at();
-    e->trn_rows = (uint16_t *)(m + o_rows);
-    e->trn_minp = (float *)(m + o_minp), e->trn_typ = (float *)(m + o_typ), e->trn_tau = (float *)(m + o_tau), e->trn_eta = (float *)(m + o_eta);
-    e->trn_mu = (float *)(m + o_mu), e->trn_logsum = (float *)(m + o_sum);
-    e->stats.workspace_bytes += carve.off;
-    return TL_OK;
-}
-
-// the slot's parameters become `v` (validated by the caller): the device copy follows the host mirror, stream-ordered between steps.
-// restart_mu: mu becomes 2 tau (NaN without Mirostat); move / fork copy the source's mu behind this call instead
-static int trn_write(tl_engine *e, int slot, const tl_engine::TruncParams &v, bool restart_mu = true) {
-    if (!e->trn_mem && !v.truncates()) {  // an engine that never truncated: nothing to write
-        e->trn[slot] = v;
-        return TL_OK;
-    }
-    TL_TRY(trn_alloc(e));
-    Pokes pk;
-    poke_float(pk, e->trn_minp + slot, v.min_p);
-    poke_float(pk, e->trn_typ + slot, v.typical_p);
-    poke_float(pk, e->trn_tau + slot, v.tau);
-    poke_float(pk, e->trn_eta + slot, v.eta);
-    if (restart_mu) pk.emplace_back((int32_t *)(e->trn_mu + slot), v.mirostat() ? __builtin_bit_cast(int32_t, 2.f * v.tau) : (int32_t)0x7fc00000);
-    e->trn[slot] = v;
-    return poke(e, pk);
-}
-static int trn_reset(tl_engine *e, int slot) {
-    const tl_engine::TruncParams d{};
-    const tl_engine::TruncParams &c = e->trn[slot];
-    if (c.min_p == d.min_p && c.typical_p == d.typical_p && c.tau == d.tau && c.eta == d.eta) return TL_OK;
-    return trn_write(e, slot, d);
-}
-// tl_engine_move (move = true) / tl_engine_fork: dst takes src's parameters and mu; a move leaves src at the defaults
-static int trn_carry(tl_engine *e, int src, int dst, bool move) {
-    if (!e->trn[src].truncates() && !e->trn[dst].truncates()) return TL_OK;
-    const tl_engine::TruncParams v = e->trn[src];
-    TL_TRY(trn_write(e, dst, v, false));
-    if (e->trn_mem) TL_HIP(hipMemcpyAsync(e->trn_mu + dst, e->trn_mu + src, sizeof(float), hipMemcpyDeviceToDevice, e->stream));
-    return move ? trn_reset(e, src) : TL_OK;
-}
-
 // the truncation launch over `rows` rows for slots slot0 .. (the rows the choice would be made from -> filtered rows into `out`), and the
 // Mirostat update launch behind the step end; `row0`: the index of the first row inside the engine's row buffers
 static void launch_truncate(tl_engine *e, const uint16_t *rows_in, uint16_t *out, int rows, int slot0, int row0, ProfCtx *pc) {
-    const TruncateArgs a{rows_in, out, e->cfg.vocab_size, slot0, e->smp_temp, e->trn_minp, e->trn_typ, e->trn_mu, e->trn_logsum + row0, pc ? pc->buf : nullptr};
+    const SlotSettings::Offsets &at = e->settings.at;
+    const TruncateArgs a{rows_in, out, e->cfg.vocab_size, slot0, e->sdev<float>(SB_SAMPLE, at.smp_temp), e->sdev<float>(SB_TRUNC, at.trn_minp),
+                         e->sdev<float>(SB_TRUNC, at.trn_typ), e->sdev<float>(SB_TRUNC, at.trn_mu), e->sdev<float>(SB_TRUNC, at.trn_logsum) + row0,
+                         pc ? pc->buf : nullptr};
     hipLaunchKernelGGL(truncate_rows_kernel, dim3(rows), dim3(1024), 0, e->stream, a);
     if (pc) prof_after(pc, 7, rows);
 }
 static void launch_mirostat_update(tl_engine *e, const uint16_t *filtered, int rows, int slot0, int row0, ProfCtx *pc) {
-    const MirostatUpdateArgs a{filtered, e->cfg.vocab_size, slot0, e->tokens, e->smp_temp, e->trn_logsum + row0, e->trn_tau, e->trn_eta, e->trn_mu, e->live,
+    const SlotSettings::Offsets &at = e->settings.at;
+    const MirostatUpdateArgs a{filtered, e->cfg.vocab_size, slot0, e->tokens, e->sdev<float>(SB_SAMPLE, at.smp_temp), e->sdev<float>(SB_TRUNC, at.trn_logsum) + row0,
+                               e->sdev<float>(SB_TRUNC, at.trn_tau), e->sdev<float>(SB_TRUNC, at.trn_eta), e->sdev<float>(SB_TRUNC, at.trn_mu), e->live,
                                pc ? pc->buf : nullptr};
     hipLaunchKernelGGL(mirostat_update_kernel, dim3(rows), dim3(64), 0, e->stream, a);
     if (pc) prof_after(pc, 7, rows);
 }
 
 // ---- LoRA adapters (lora.h) ---------------------------------------------------------------------------
-// the slot's adapter id, on the host and -- once an adapter has been loaded -- on the device (skipped while it is the value already)
-static int lora_write(tl_engine *e, int slot, int adapter) {
-    if (e->lora_of[slot] == adapter) return TL_OK;
-    e->lora_of[slot] = adapter;
-    if (!e->lora_slot_dev) return TL_OK;
-    Pokes pk;
-    pk.emplace_back(e->lora_slot_dev + slot, adapter);
-    return poke(e, pk);
-}
-// the slot, taking part in a decode step, carries an adapter: the step runs the adapter plan (enqueue_step)
-static bool step_lora_slot(const tl_engine *e, int slot) { return e->lora_mem && e->slot_runs(slot) && e->lora_of[slot] >= 0; }
-
 // input and output columns of a projection group and how its output columns map to segments
 struct LoraShape {
     int in, out, seg_mode, seg_end0, seg_end1;
@@ -808,7 +590,7 @@ static int lora_alloc(tl_engine *e) {
     const int cap = lora_tiles_cap(e), decode_tiles = ceil_div(c.max_batch, LORA_TILE);
     Carve carve;
     const size_t table_bytes = (size_t)TL_MAX_LORA_ADAPTERS * c.num_layers * tl_engine::LORA_GROUPS * sizeof(LoraDesc);
-    const size_t o_table = carve(table_bytes), o_slot = carve((size_t)c.max_batch * 4);
+    const size_t o_table = carve(table_bytes), o_slot = carve(e->settings.layout(SB_LORA).bytes);
     const size_t o_td = carve((size_t)decode_tiles * sizeof(LoraTile)), o_tp = carve((size_t)cap * sizeof(LoraTile));
     const size_t o_part = carve(lora_partial_floats(cap, in_max) * 4), o_ss = carve(lora_ss_floats(cap, in_max) * 4);
     const size_t o_tmp = carve((size_t)e->rows_cap * c.hidden_size * 2);
@@ -816,7 +598,7 @@ static int lora_alloc(tl_engine *e) {
     lora_lookup_tiles(c.max_batch, tiles);
     TL_TRY(alloc_filled(e->lora_mem, carve.off, "engine_lora_load: hipMalloc(adapter table and workspaces) failed", [&](char *m) -> int {
         hipError_t rc = hipMemset(m + o_table, 0, table_bytes);
-        if (rc == hipSuccess) rc = hipMemset(m + o_slot, 0xff, (size_t)c.max_batch * 4);
+        if (rc == hipSuccess) rc = hipMemset(m + o_slot, 0xff, e->settings.layout(SB_LORA).bytes);
         if (rc == hipSuccess) rc = hipMemcpy(m + o_td, tiles.data(), tiles.size() * sizeof(LoraTile), hipMemcpyHostToDevice);
         return rc == hipSuccess ? TL_OK : fail(TL_ERR_HIP, std::string("engine_lora_load: ") + hipGetErrorString(rc));
     }));
@@ -825,6 +607,7 @@ static int lora_alloc(tl_engine *e) {
     e->lora_tiles_decode = (LoraTile *)(mem + o_td), e->lora_tiles_prefill = (LoraTile *)(mem + o_tp);
     e->lora_partial = (float *)(mem + o_part), e->lora_ss = (float *)(mem + o_ss), e->lora_tmp = (uint16_t *)(mem + o_tmp);
     e->lora_ad.resize(TL_MAX_LORA_ADAPTERS);
+    e->settings.created(SB_LORA);
     return TL_OK;
 }
 // One adapted projection group of layer l over `n_tiles` tiles: the shrink and the expand launch (lora.h).  norm_w: x is the row ahead
@@ -842,28 +625,6 @@ static int lora_group(tl_engine *e, int l, int group, const LoraTile *tiles_dev,
 }
 
 // ---- stop conditions (stop.h) ---------------------------------------------------------------------------------------
-// the slot, taking part in a step, is armed: the step ends with the stop launch, in a plan of its own that keeps the hipGraphLaunch route
-// (the launch reads the token the step end stored and writes the live word the next step's launches read)
-static bool step_stop_slot(const tl_engine *e, int slot) { return e->stop_mem && e->slot_runs(slot) && e->stop[slot].armed; }
-
-// the per-slot arrays, all zero (unarmed, no budget, automaton at the root, empty records): made by the first call that arms a slot
-static int stop_alloc(tl_engine *e) {
-    if (e->stop_mem) return TL_OK;
-    const size_t B = (size_t)e->cfg.max_batch;
-    Carve carve;
-    const size_t o_sets = carve(B * sizeof(StopDev *)), o_armed = carve(B * 4), o_max = carve(B * 4), o_state = carve(B * 4), o_rec = carve(B * sizeof(StopRecord));
-    TL_TRY(alloc_filled(e->stop_mem, carve.off, "engine_set_stop: hipMalloc(stop records) failed", [&](char *m) -> int {
-        return hipMemsetAsync(m, 0, carve.off, e->stream) == hipSuccess ? TL_OK : fail(TL_ERR_HIP, "engine_set_stop: memset(stop records) failed");
-    }));
-    char *m = e->stop_mem.at();
-    e->stop_sets = (const StopDev **)(m + o_sets);
-    e->stop_armed = (int32_t *)(m + o_armed), e->stop_max_new = (int32_t *)(m + o_max), e->stop_automaton = (int32_t *)(m + o_state);
-    e->stop_rec = (StopRecord *)(m + o_rec);
-    e->stop_host.assign(B, StopRecord{});
-    e->stats.workspace_bytes += carve.off;
-    return TL_OK;
-}
-
 // Host mirrors after a stop.  The mirrors advance per step for every running slot, so a slot that froze in mid-call leaves them ahead of
 // the device.  Behind any call that enqueued a stop launch: wait for the stream (and the AQL queue), read the records in one copy, and
 // for every slot that newly stopped take the device's context length -- `produced` went up with it, one per step -- and mark the slot
@@ -872,81 +633,42 @@ static int stop_reconcile(tl_engine *e) {
     if (!e->stop_dirty) return TL_OK;
     TL_TRY(aql_drain(e));
     TL_HIP(hipStreamSynchronize(e->stream));
-    TL_HIP(hipMemcpy(e->stop_host.data(), e->stop_rec, e->stop_host.size() * sizeof(StopRecord), hipMemcpyDeviceToHost));
+    std::vector<StopMirror> read(e->cfg.max_batch);
+    TL_HIP(hipMemcpy(read.data(), e->sdev<StopRecord>(SB_STOP, e->settings.at.stop_rec), read.size() * sizeof(StopRecord), hipMemcpyDeviceToHost));
     e->stop_dirty = false;
-    for (int b = 0; b < e->cfg.max_batch; ++b) {
-        const Slot &s = e->table.slots[b];
-        if (!s.live || s.stopped || !e->stop[b].armed || e->stop_host[b].reason == STOP_NONE) continue;
-        const int ctx = e->stop_host[b].context;
-        e->table.stop(b, ctx, s.produced - (s.ctx - ctx));
-    }
+    std::vector<SlotSettings::StopEvent> stopped;
+    e->settings.stop_records_read(read.data(), [e](int b) -> const Slot & { return e->table.slots[b]; }, stopped);
+    for (const SlotSettings::StopEvent &s : stopped) e->table.stop(s.slot, s.context, s.produced);
     return TL_OK;
-}
-
-// the slot's device words: set pointer, armed, budget, automaton at the root, an empty record
-static void stop_poke(tl_engine *e, int slot, const tl_engine::StopSlot &v, Pokes &pk) {
-    poke_u64(pk, e->stop_sets + slot, (uint64_t)(uintptr_t)(v.set ? v.set->dev : nullptr));
-    pk.emplace_back(e->stop_armed + slot, v.armed ? 1 : 0);
-    pk.emplace_back(e->stop_max_new + slot, v.max_new);
-    pk.emplace_back(e->stop_automaton + slot, 0);
-    for (int w = 0; w < (int)(sizeof(StopRecord) / 4); ++w) pk.emplace_back((int32_t *)(e->stop_rec + slot) + w, 0);
-}
-// begin / release: the slot is unarmed and its record empty (the table's slot starts over: not stopped)
-static int stop_reset(tl_engine *e, int slot) {
-    if (!e->stop_mem || !e->stop[slot].armed) return TL_OK;
-    e->stop[slot] = tl_engine::StopSlot{};
-    e->stop_host[slot] = StopRecord{};
-    Pokes pk;
-    stop_poke(e, slot, e->stop[slot], pk);
-    return poke(e, pk);
-}
-// tl_engine_move (move = true) / tl_engine_fork: dst takes src's set, budget, record and automaton state (the table carried `stopped`);
-// a move leaves src unarmed
-static int stop_carry(tl_engine *e, int src, int dst, bool move) {
-    if (!e->stop_mem || (!e->stop[src].armed && !e->stop[dst].armed)) return TL_OK;
-    e->stop[dst] = e->stop[src];
-    e->stop_host[dst] = e->stop_host[src];
-    Pokes pk;
-    poke_u64(pk, e->stop_sets + dst, (uint64_t)(uintptr_t)(e->stop[dst].set ? e->stop[dst].set->dev : nullptr));
-    pk.emplace_back(e->stop_armed + dst, e->stop[dst].armed ? 1 : 0);
-    pk.emplace_back(e->stop_max_new + dst, e->stop[dst].max_new);
-    TL_TRY(poke(e, pk));
-    TL_HIP(hipMemcpyAsync(e->stop_automaton + dst, e->stop_automaton + src, 4, hipMemcpyDeviceToDevice, e->stream));
-    TL_HIP(hipMemcpyAsync(e->stop_rec + dst, e->stop_rec + src, sizeof(StopRecord), hipMemcpyDeviceToDevice, e->stream));
-    return move ? stop_reset(e, src) : TL_OK;
 }
 
 // the stop launch over `rows` rows for slots slot0 .., behind the step end (and the Mirostat update)
 static void launch_stop(tl_engine *e, int rows, int slot0, ProfCtx *pc) {
-    const StopArgs a{e->tokens, slot0, e->stop_sets, nullptr, e->stop_armed, e->stop_max_new, e->stop_automaton, e->stop_rec, e->live, e->context_lens,
-                     pc ? pc->buf : nullptr};
+    const SlotSettings::Offsets &at = e->settings.at;
+    const StopArgs a{e->tokens, slot0, e->sdev<const StopDev *>(SB_STOP, at.stop_sets), nullptr, e->sdev<int32_t>(SB_STOP, at.stop_armed),
+                     e->sdev<int32_t>(SB_STOP, at.stop_max_new), e->sdev<int32_t>(SB_STOP, at.stop_automaton), e->sdev<StopRecord>(SB_STOP, at.stop_rec), e->live,
+                     e->context_lens, pc ? pc->buf : nullptr};
     hipLaunchKernelGGL(stop_check_kernel, dim3(rows), dim3(64), 0, e->stream, a);
     if (pc) prof_after(pc, 7, rows);
     e->stop_dirty = true;
 }
 
 // ---- which launches a step needs ---------------------------------------------------------------------------------------------------
-// One record for slots [slot0, slot0 + n), re-derived from the slots' parameters by every call that enqueues or replays a step: the
-// per-slot predicates above, ORed.  A decode step asks over [0, batch), a prefill's first token over its one slot.
-struct StepFeatures {
-    bool samples = false, logprobs = false, processes = false, grammar = false, stack_grammar = false, truncates = false, mirostat = false,
-         lora = false, stop = false;
-    // the bits a decode plan's key carries above its split plan (tl_engine_decode): with all clear the step is the greedy program
-    long key_bits() const {
-        // bit 62: the step ends with the sampling twin of step_end_kernel, bit 61: with the logprob twin (step_end.h)
-        return (samples ? (1L << 62) : 0L) | (logprobs ? (1L << 61) : 0L) |
-               // bit 60: the processing launch (logit_process.h) stands between the lm_head and the step end
-               // bit 59: ... in its regex mode (grammar.h); bit 58: in its stack mode (grammar_stack.h)
-               (processes ? (1L << 60) : 0L) | (grammar ? (1L << 59) : 0L) | (stack_grammar ? (1L << 58) : 0L) |
-               // bit 57: the truncation launch (truncate.h) stands ahead of the step end and the Mirostat update behind it
-               // bit 56: ... and a slot has Mirostat on (the plan keeps the hipGraphLaunch route)
-               (truncates ? (1L << 57) : 0L) | (mirostat ? (1L << 56) : 0L) |
-               // bit 55: a slot carries a LoRA adapter: the adapter plan (lora.h; hipGraphLaunch)
-               (lora ? (1L << 55) : 0L) |
-               // bit 54: a slot is armed with stop conditions: the stop launch (stop.h) stands last (hipGraphLaunch)
-               (stop ? (1L << 54) : 0L);
-    }
-};
+// the bits a decode plan's key carries above its split plan (tl_engine_decode): with all clear the step is the greedy program
+static long step_key_bits(const StepFeatures &f) {
+    // bit 62: the step ends with the sampling twin of step_end_kernel, bit 61: with the logprob twin (step_end.h)
+    return (f.samples ? (1L << 62) : 0L) | (f.logprobs ? (1L << 61) : 0L) |
+           // bit 60: the processing launch (logit_process.h) stands between the lm_head and the step end
+           // bit 59: ... in its regex mode (grammar.h); bit 58: in its stack mode (grammar_stack.h)
+           (f.processes ? (1L << 60) : 0L) | (f.grammar ? (1L << 59) : 0L) | (f.stack_grammar ? (1L << 58) : 0L) |
+           // bit 57: the truncation launch (truncate.h) stands ahead of the step end and the Mirostat update behind it
+           // bit 56: ... and a slot has Mirostat on (the plan keeps the hipGraphLaunch route)
+           (f.truncates ? (1L << 57) : 0L) | (f.mirostat ? (1L << 56) : 0L) |
+           // bit 55: a slot carries a LoRA adapter: the adapter plan (lora.h; hipGraphLaunch)
+           (f.lora ? (1L << 55) : 0L) |
+           // bit 54: a slot is armed with stop conditions: the stop launch (stop.h) stands last (hipGraphLaunch)
+           (f.stop ? (1L << 54) : 0L);
+}
 // Why a plan with these features never becomes an AQL program (null: it may), the one sentence tl_engine_replay_route reports: bits 54,
 // 55 and 56 above, the stop launch first
 static const char *graph_only_reason(const StepFeatures &f) {
@@ -955,22 +677,13 @@ static const char *graph_only_reason(const StepFeatures &f) {
     if (f.mirostat) return "a Mirostat slot is live (the update launch reads the token the step end stored)";
     return nullptr;
 }
+// the plan of slots [slot0, slot0 + n), re-derived from the slots' parameters by every call that enqueues or replays a step: a decode step
+// asks over [0, batch), a prefill's first token over its one slot
 static StepFeatures step_features(const tl_engine *e, int slot0, int n) {
-    StepFeatures f;
-    for (int slot = slot0; slot < slot0 + n && slot < e->cfg.max_batch; ++slot) {
-        const tl_grammar *g = step_grammar_slot(e, slot);
-        f.samples |= step_samples_slot(e, slot);
-        f.logprobs |= step_logprobs_slot(e, slot);
-        f.processes |= step_processes_slot(e, slot);
-        f.grammar |= g != nullptr;  // (only with processes: step_grammar_slot)
-        f.stack_grammar |= g && g->stack;
-        f.truncates |= step_truncates_slot(e, slot);
-        f.mirostat |= step_mirostat_slot(e, slot);  // (only with truncates)
-        f.lora |= step_lora_slot(e, slot);
-        f.stop |= step_stop_slot(e, slot);
-    }
-    return f;
+    return e->settings.features(slot0, n, [e](int slot) { return e->slot_runs(slot); });
 }
+// does the slot, taking part in a step, process its logits?
+static bool step_processes_slot(const tl_engine *e, int slot) { return e->settings.processes(slot, e->slot_runs(slot)); }
 
 // The chain behind the lm_head over `rows` raw rows -- rows [row0, row0 + rows) of the engine's row buffers, slots slot0 .. -- in the one
 // order a decode step and a prefill's first token share: processing (logit_process.h), truncation (truncate.h), the step end, the
@@ -983,12 +696,12 @@ static void launch_logit_chain(tl_engine *e, const uint16_t *raw, int row0, int 
     const size_t at = (size_t)row0 * e->cfg.vocab_size;
     const uint16_t *choice = raw;  // the rows the token is chosen from
     if (f.processes) {  // raw rows -> processed rows (rows of slots that do not process are copied)
-        launch_logit_process(e, choice, e->pen_rows + at, rows, slot0, tokens, f.grammar, f.stack_grammar, pc);
-        choice = e->pen_rows + at;
+        launch_logit_process(e, choice, e->sdev<uint16_t>(SB_PROCESS, e->settings.at.pen_rows) + at, rows, slot0, tokens, f.grammar, f.stack_grammar, pc);
+        choice = e->sdev<uint16_t>(SB_PROCESS, e->settings.at.pen_rows) + at;
     }
     if (f.truncates) {  // ... -> filtered rows (rows of slots that do not truncate are copied)
-        launch_truncate(e, choice, e->trn_rows + at, rows, slot0, row0, pc);
-        choice = e->trn_rows + at;
+        launch_truncate(e, choice, e->sdev<uint16_t>(SB_TRUNC, e->settings.at.trn_rows) + at, rows, slot0, row0, pc);
+        choice = e->sdev<uint16_t>(SB_TRUNC, e->settings.at.trn_rows) + at;
     }
     const bool maxima = tile_max && choice == raw;
     const StepEndArgs s = step_end_args(e, choice, slot0, advance, x, maxima ? tile_max : nullptr, maxima ? tiles : 0, ss_out, pc ? pc->buf : nullptr);
@@ -1467,43 +1180,12 @@ static int slot_check_feeds(tl_engine *e, int slot) {
     return TL_OK;
 }
 
-// ---- the per-slot settings across the lifecycle: sampling, log-probability records, penalties / bias / grammar, the pending token ----
-// begin / release: everything back to the defaults (each skipped while it is the default already)
-static int settings_reset(tl_engine *e, int slot) {
-    e->gr_pending[slot] = 0;
-    e->emb_rows[slot] = -1;
-    TL_TRY(lp_write(e, slot, -1));
-    TL_TRY(pen_reset(e, slot));
-    TL_TRY(trn_reset(e, slot));
-    TL_TRY(lora_write(e, slot, LORA_NONE));
-    TL_TRY(stop_reset(e, slot));
-    return smp_reset(e, slot);
-}
-// fork / move (move = true): dst takes what src has, and a move leaves src at the defaults
-static int settings_carry(tl_engine *e, int src, int dst, bool move) {
-    e->gr_pending[dst] = e->gr_pending[src];
-    if (move) e->gr_pending[src] = 0;
-    e->emb_rows[dst] = -1;  // a running mean (pool.h) does not travel: the context of dst did not come from MEAN chunks of its own
-    if (move) e->emb_rows[src] = -1;
-    // the pending input token travels on the device
+// fork / move (move = true), behind the table's: the pending input token travels on the device, and the record says what else does
+static int settings_carry(tl_engine *e, int src, int dst, bool move, Pokes &pk) {
     TL_HIP(hipMemcpyAsync(e->tokens + dst, e->tokens + src, sizeof(int32_t), hipMemcpyDeviceToDevice, e->stream));
-    // the sampling parameters (seed included: give a fork's child its own seed, or both draw the same tokens)
-    if (!smp_is_default(e->smp[src]) || !smp_is_default(e->smp[dst])) {
-        const tl_engine::SampleParams v = e->smp[src];
-        TL_TRY(smp_write(e, dst, v));
-        if (move) TL_TRY(smp_write(e, src, tl_engine::SampleParams{}));
-    }
-    // ... the log-probability setting with the pending token's record (the record ring restarts, like the token ring)
-    TL_TRY(lp_carry(e, src, dst, move));
-    // ... the penalties, the bias list, the history and the grammar's state
-    TL_TRY(pen_carry(e, src, dst, move));
-    // ... the truncation parameters with Mirostat's mu
-    TL_TRY(trn_carry(e, src, dst, move));
-    // ... the stop set, its record and the automaton's state
-    TL_TRY(stop_carry(e, src, dst, move));
-    // ... and the LoRA adapter
-    TL_TRY(lora_write(e, dst, e->lora_of[src]));
-    return move ? lora_write(e, src, LORA_NONE) : TL_OK;
+    SettingsEdits ed;
+    e->settings.carry(src, dst, move, ed);
+    return settings_apply(e, ed, pk);
 }
 
 }  // namespace tl
@@ -1608,12 +1290,8 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
 
     TL_TRY(e->arena.alloc(e->arena_bytes, "engine_create: hipMalloc(arena) failed"));
     // sampling parameters per slot (all zero: greedy): seeds first for their 8-byte alignment
-    TL_TRY(e->smp_mem.alloc((size_t)c.max_batch * 20, "engine_create: hipMalloc(sampling) failed"));
-    e->smp_seed = e->smp_mem.at<uint64_t>();
-    e->smp_temp = e->smp_mem.at<float>((size_t)c.max_batch * 8);
-    e->smp_topk = e->smp_mem.at<int32_t>((size_t)c.max_batch * 12);
-    e->smp_topp = e->smp_mem.at<float>((size_t)c.max_batch * 16);
-    if (hipMemsetAsync(e->smp_mem.at(), 0, (size_t)c.max_batch * 20, e->stream) != hipSuccess) return fail(TL_ERR_HIP, "engine_create: memset failed");
+    e->settings.init(settings_sizes(e));
+    TL_TRY(settings_blocks(e, 1u << SB_SAMPLE));
     e->layer_pool_elems = (size_t)c.num_pages * c.num_kv_heads * c.page_size * c.head_dim;
     const size_t pool_bytes = e->layer_pool_elems * e->kv_elem_bytes() * c.num_layers;
     TL_TRY(e->kv_mem[0].alloc(pool_bytes, "engine_create: hipMalloc(key pages) failed"));
@@ -1830,13 +1508,6 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
 
     e->moe.assign(c.num_layers, tl_moe_weights{});
     e->table.init(c.max_batch, c.num_pages, c.page_size, c.max_pages_per_seq);  // (the pool hands out 0, 1, 2, ...)
-    e->smp.assign(c.max_batch, tl_engine::SampleParams{});
-    e->pen.assign(c.max_batch, tl_engine::PenaltyParams{});
-    e->trn.assign(c.max_batch, tl_engine::TruncParams{});
-    e->gr_pending.assign(c.max_batch, 0);
-    e->emb_rows.assign(c.max_batch, -1);
-    e->lora_of.assign(c.max_batch, LORA_NONE);
-    e->stop.assign(c.max_batch, tl_engine::StopSlot{});
     e->stats.kv_bytes = e->kv_bytes;
     e->stats.workspace_bytes = e->arena_bytes + e->tiled_bytes + e->bf16w_bytes;
     *out = owner.release();
@@ -1957,8 +1628,9 @@ extern "C" int tl_engine_begin(tl_engine *e, int slot) {
     pk.emplace_back(e->context_lens + slot, 0);
     pk.emplace_back(e->produced + slot, 0);
     pk.emplace_back(e->tokens + slot, 0);
-    TL_TRY(poke(e, pk));
-    return settings_reset(e, slot);
+    SettingsEdits sed;
+    e->settings.reset(slot, sed);
+    return settings_apply(e, sed, pk);
 }
 
 extern "C" int tl_engine_reserve(tl_engine *e, int slot, int total_tokens) {
@@ -1980,18 +1652,18 @@ extern "C" int tl_engine_release(tl_engine *e, int slot) {
     pk.emplace_back(e->live + slot, 0);
     pk.emplace_back(e->context_lens + slot, 0);
     pk.emplace_back(e->tokens + slot, 0);
-    TL_TRY(poke(e, pk));
-    return settings_reset(e, slot);
+    SettingsEdits sed;
+    e->settings.reset(slot, sed);
+    return settings_apply(e, sed, pk);
 }
 
 extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
     TL_TRY(slot_check_unparked(e, slot));
-    TL_REQUIRE(!e->pen[slot].processes(), "engine_rewind: the slot processes its logits (its history would keep the dropped tokens; make it neutral first)");
-    TL_REQUIRE(!e->trn[slot].mirostat(), "engine_rewind: the slot has Mirostat on (mu would no longer belong to the tokens held; switch it off first)");
+    TL_TRY(table_rc(e->settings.refuses_rewind(slot)));
     SlotEdits ed;
     Pokes pk;
     TL_TRY(table_rc(e->table.rewind(slot, n, ed)));
-    e->emb_rows[slot] = -1;
+    e->settings.rewound(slot);
     TL_TRY(apply_edits(e, ed, pk));  // the copy of a shared tail page before the row entry that publishes the fresh page
     pk.emplace_back(e->context_lens + slot, e->table.slots[slot].ctx);
     return poke(e, pk);
@@ -2010,8 +1682,7 @@ extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
     pk.emplace_back(e->live + dst, e->table.slots[dst].stopped ? 0 : 1);  // (a stopped sequence's copy is stopped: no sequence to a step)
     pk.emplace_back(e->context_lens + dst, e->table.slots[dst].ctx);
     pk.emplace_back(e->produced + dst, 0);
-    TL_TRY(poke(e, pk));
-    return settings_carry(e, src, dst, false);
+    return settings_carry(e, src, dst, false, pk);
 }
 
 // the device table of every K / V (and scale) pool, built once by the first call that needs it (prefix cache, swap space): pool
@@ -2096,7 +1767,7 @@ extern "C" int tl_engine_prefix_attach(tl_engine *e, int slot, const int32_t *to
         for (int at = 0; at < got; at += c.max_prefill_rows) {
             const int len = std::min(c.max_prefill_rows, got - at);
             TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens + at, (size_t)len * 4, hipMemcpyHostToDevice, e->stream));
-            const LogitMarkArgs mk{e->prefill_tokens, len, c.vocab_size, (uint32_t *)e->pen_history, (long)slot * c.vocab_size};
+            const LogitMarkArgs mk{e->prefill_tokens, len, c.vocab_size, e->sdev<uint32_t>(SB_PROCESS, e->settings.at.pen_history), (long)slot * c.vocab_size};
             hipLaunchKernelGGL(logit_mark_prompt_kernel, dim3(ceil_div(len, 256)), dim3(256), 0, e->stream, mk);
             TL_CHECK_LAUNCH("engine prompt marking");
         }
@@ -2121,8 +1792,7 @@ extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
     pk.emplace_back(e->live + dst, d.parked || d.stopped ? 0 : 1);  // (a stopped sequence stays stopped at dst)
     pk.emplace_back(e->live + src, 0);
     pk.emplace_back(e->produced + dst, 0);
-    TL_TRY(poke(e, pk));
-    return settings_carry(e, src, dst, true);
+    return settings_carry(e, src, dst, true, pk);
 }
 
 // ---- beam search (include/tinyllm_engine.h "Beam search"; the selection is beam.h, the group's genealogy slot_table.h) ----------------
@@ -2132,12 +1802,7 @@ static const char *beam_slot_refusal(const tl_engine *e, int slot) {
     if (!s.live) return "engine_beam: slot holds no sequence";
     if (s.parked) return "engine_beam: the slot is parked (tl_engine_unpark first)";
     if (s.stopped) return "engine_beam: the slot has stopped";
-    if (e->smp[slot].samples()) return "engine_beam: the slot samples (beam slots are greedy)";
-    if (e->pen[slot].processes()) return "engine_beam: the slot processes its logits (penalties, bias or a grammar)";
-    if (e->trn[slot].truncates()) return "engine_beam: the slot truncates";
-    if (!e->lp_n.empty() && e->lp_n[slot] >= 0) return "engine_beam: the slot records log-probabilities";
-    if (e->stop[slot].armed) return "engine_beam: the slot is armed with a stop set";
-    return nullptr;
+    return e->settings.refuses_beam(slot);
 }
 
 extern "C" int tl_engine_beam_select(tl_engine *e, int row0, int rows, const float *scores_host, int n_cand, tl_beam_candidate *out_host) {
@@ -2179,9 +1844,6 @@ extern "C" int tl_engine_beam_reorder(tl_engine *e, int slot0, int n_src, int wi
     TL_TRY(stop_reconcile(e));
     for (int i = 0; i < n_src; ++i) TL_TRY(table_rc(beam_slot_refusal(e, slot0 + i)));
     TL_TRY(ensure_pool_table(e));  // (the tail copies' pool table: built by the first call that needs it, before anything changes)
-    int lora[TL_MAX_BEAMS];
-    char pending[TL_MAX_BEAMS];
-    for (int i = 0; i < n_src; ++i) lora[i] = e->lora_of[slot0 + i], pending[i] = e->gr_pending[slot0 + i];
     SlotEdits ed;
     Pokes pk;
     TL_TRY(table_rc(e->table.beam_reorder(slot0, n_src, width, parents, ed)));
@@ -2193,12 +1855,10 @@ extern "C" int tl_engine_beam_reorder(tl_engine *e, int slot0, int n_src, int wi
         pk.emplace_back(e->context_lens + slot, d.ctx);
         pk.emplace_back(e->tokens + slot, i < width ? tokens[i] : 0);
         if (i < width) pk.emplace_back(e->produced + slot, 0);
-        e->gr_pending[slot] = i < width ? pending[parents[i]] : 0;
-        e->emb_rows[slot] = -1;  // (a running mean does not travel, as in settings_carry)
     }
-    TL_TRY(poke(e, pk));
-    for (int i = 0; i < span; ++i) TL_TRY(lora_write(e, slot0 + i, i < width ? lora[parents[i]] : LORA_NONE));
-    return TL_OK;
+    SettingsEdits sed;
+    e->settings.beam_reorder(slot0, n_src, width, parents, sed);  // the adapters and the pending flags follow the parents
+    return settings_apply(e, sed, pk);
 }
 
 
@@ -2281,14 +1941,14 @@ extern "C" int tl_engine_park(tl_engine *e, int slot) {
     SlotEdits ed;
     Pokes pk;
     e->table.park_commit(slot, ed);
-    e->emb_rows[slot] = -1;
     TL_TRY(apply_edits(e, ed, pk));
     pk.emplace_back(e->live + slot, 0);
     pk.emplace_back(e->context_lens + slot, 0);
     e->swap_parks++;
     e->swap_pages_out += n;
-    TL_TRY(poke(e, pk));
-    return e->pen[slot].processes() ? pen_device_switch(e, slot, false) : TL_OK;
+    SettingsEdits sed;
+    e->settings.park(slot, sed);  // (the processing parameters go neutral on the device)
+    return settings_apply(e, sed, pk);
 }
 
 extern "C" int tl_engine_unpark(tl_engine *e, int slot) {
@@ -2298,7 +1958,6 @@ extern "C" int tl_engine_unpark(tl_engine *e, int slot) {
     Pokes pk;
     std::vector<int> records;
     TL_TRY(table_rc(e->table.unpark(slot, ed, records)));
-    e->emb_rows[slot] = -1;
     const int ctx = e->table.slots[slot].ctx, n = (int)records.size();
     e->swap_unparks++;
     e->swap_pages_in += n;
@@ -2317,8 +1976,9 @@ extern "C" int tl_engine_unpark(tl_engine *e, int slot) {
     }
     pk.emplace_back(e->context_lens + slot, ctx);
     pk.emplace_back(e->live + slot, e->table.slots[slot].stopped ? 0 : 1);  // (an unparked stopped slot stays stopped)
-    TL_TRY(poke(e, pk));
-    return e->pen[slot].processes() ? pen_device_switch(e, slot, true) : TL_OK;
+    SettingsEdits sed;
+    e->settings.unpark(slot, sed);  // (... and come back from the mirror)
+    return settings_apply(e, sed, pk);
 }
 
 extern "C" int tl_engine_slot_parked(const tl_engine *e, int slot) {
@@ -2365,8 +2025,7 @@ extern "C" int tl_engine_context_len(const tl_engine *e, int slot) {
 extern "C" int tl_engine_set_token(tl_engine *e, int slot, int32_t token) {
     TL_TRY(slot_check(e, slot, true));
     TL_REQUIRE(token >= 0 && token < e->cfg.vocab_size, "engine_set_token: token id out of range");
-    TL_REQUIRE(!e->pen[slot].processes(), "engine_set_token: the slot processes its logits (its history counts the tokens the engine produced; make it neutral first)");
-    TL_REQUIRE(!e->trn[slot].mirostat(), "engine_set_token: the slot has Mirostat on (mu would no longer belong to the tokens held; switch it off first)");
+    TL_TRY(table_rc(e->settings.refuses_set_token(slot)));
     Pokes pk;
     pk.emplace_back(e->tokens + slot, token);
     return poke(e, pk);
@@ -2374,60 +2033,37 @@ extern "C" int tl_engine_set_token(tl_engine *e, int slot, int32_t token) {
 
 extern "C" int tl_engine_set_sampling(tl_engine *e, int slot, float temperature, int top_k, float top_p, uint64_t seed) {
     TL_TRY(slot_check(e, slot, true));
-    TL_REQUIRE(std::isfinite(temperature) && temperature >= 0.f, "engine_set_sampling: temperature must be finite and >= 0");
-    TL_REQUIRE(top_k >= 0, "engine_set_sampling: top_k must be >= 0 (0 = no top-k)");
-    TL_REQUIRE(!std::isnan(top_p), "engine_set_sampling: top_p is NaN");
-    TL_REQUIRE(temperature == 0.f || e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_set_sampling: vocabulary larger than the sampler's 524,288 tokens");
-    tl_engine::SampleParams v;
-    v.temperature = temperature;
-    v.top_k = top_k >= e->cfg.vocab_size ? 0 : top_k;  // beyond the vocabulary: no top-k
-    v.top_p = top_p > 0.f && top_p < 1.f ? top_p : 0.f;  // outside (0, 1): no top-p
-    v.seed = seed;
-    TL_REQUIRE(!e->trn[slot].mirostat() || (v.top_k == 0 && v.top_p == 0.f), "engine_set_sampling: the slot has Mirostat on, which excludes top-k and top-p");
-    return smp_write(e, slot, v);
+    Pokes pk;
+    return settings_set(e, slot, pk, [&](SettingsEdits &ed) { return e->settings.set_sampling(slot, temperature, top_k, top_p, seed, ed); });
 }
 
 extern "C" int tl_engine_set_truncation(tl_engine *e, int slot, float min_p, float typical_p) {
     TL_TRY(slot_check(e, slot, true));
-    TL_REQUIRE(min_p >= 0.f && min_p <= 1.f, "engine_set_truncation: min_p must be in [0, 1] (0 = off)");
-    TL_REQUIRE(!std::isnan(typical_p), "engine_set_truncation: typical_p is NaN");
-    TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_set_truncation: vocabulary larger than the sampler's 524,288 tokens");
-    tl_engine::TruncParams v = e->trn[slot];
-    v.min_p = min_p;
-    v.typical_p = typical_p > 0.f && typical_p < 1.f ? typical_p : 1.f;  // outside (0, 1): off
-    TL_REQUIRE(!v.mirostat() || !v.stateless(), "engine_set_truncation: the slot has Mirostat on, which excludes min-p and typical-p");
-    return trn_write(e, slot, v, false);
+    Pokes pk;
+    return settings_set(e, slot, pk, [&](SettingsEdits &ed) { return e->settings.set_truncation(slot, min_p, typical_p, ed); });
 }
 
 extern "C" int tl_engine_set_mirostat(tl_engine *e, int slot, float tau, float eta) {
     TL_TRY(slot_check(e, slot, true));
-    TL_REQUIRE(std::isfinite(tau) && tau >= 0.f, "engine_set_mirostat: tau must be finite and >= 0 (0 = off)");
-    TL_REQUIRE(tau == 0.f || (eta > 0.f && eta <= 1.f), "engine_set_mirostat: eta must be in (0, 1]");
-    TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_set_mirostat: vocabulary larger than the sampler's 524,288 tokens");
-    tl_engine::TruncParams v = e->trn[slot];
-    if (tau > 0.f) {
-        TL_REQUIRE(!v.stateless() && e->smp[slot].top_k == 0 && e->smp[slot].top_p == 0.f,
-                   "engine_set_mirostat: Mirostat excludes every other truncation of the slot (top-k, top-p, min-p, typical-p)");
-    }
-    v.tau = tau, v.eta = tau > 0.f ? eta : 0.f;
-    return trn_write(e, slot, v);  // mu restarts at 2 tau
+    Pokes pk;
+    return settings_set(e, slot, pk, [&](SettingsEdits &ed) { return e->settings.set_mirostat(slot, tau, eta, ed); });
 }
 
 extern "C" int tl_engine_mirostat_mu(tl_engine *e, int slot, float *mu) {
     TL_TRY(slot_check(e, slot, true));
     TL_REQUIRE(mu, "engine_mirostat_mu: null argument");
     *mu = __builtin_nanf("");
-    if (!e->trn_mem) return TL_OK;
+    if (!e->settings_mem[SB_TRUNC]) return TL_OK;
     TL_HIP(hipStreamSynchronize(e->stream));
-    TL_HIP(hipMemcpy(mu, e->trn_mu + slot, sizeof(float), hipMemcpyDeviceToHost));
+    TL_HIP(hipMemcpy(mu, e->sdev<float>(SB_TRUNC, e->settings.at.trn_mu) + slot, sizeof(float), hipMemcpyDeviceToHost));
     return TL_OK;
 }
 
 extern "C" int tl_engine_copy_filtered_logits(tl_engine *e, void *dst_dev, int rows) {
     TL_REQUIRE(e && dst_dev, "engine_copy_filtered_logits: null argument");
     TL_REQUIRE(rows > 0 && rows <= e->cfg.max_batch, "engine_copy_filtered_logits: rows out of range");
-    TL_REQUIRE(e->trn_rows, "engine_copy_filtered_logits: no slot of this engine has truncated yet");
-    TL_HIP(hipMemcpyAsync(dst_dev, e->trn_rows, (size_t)rows * e->cfg.vocab_size * 2, hipMemcpyDeviceToDevice, e->stream));
+    TL_REQUIRE(e->settings_mem[SB_TRUNC], "engine_copy_filtered_logits: no slot of this engine has truncated yet");
+    TL_HIP(hipMemcpyAsync(dst_dev, e->sdev<uint16_t>(SB_TRUNC, e->settings.at.trn_rows), (size_t)rows * e->cfg.vocab_size * 2, hipMemcpyDeviceToDevice, e->stream));
     return TL_OK;
 }
 
@@ -2456,30 +2092,14 @@ extern "C" int tl_mirostat_update_rows(const void *filtered_dev, int rows, int v
 
 extern "C" int tl_engine_set_penalties(tl_engine *e, int slot, float repetition_penalty, float presence_penalty, float frequency_penalty) {
     TL_TRY(slot_check(e, slot, true));
-    TL_REQUIRE(std::isfinite(repetition_penalty) && repetition_penalty > 0.f, "engine_set_penalties: repetition_penalty must be finite and > 0 (1 = off)");
-    TL_REQUIRE(std::isfinite(presence_penalty) && std::isfinite(frequency_penalty), "engine_set_penalties: presence_penalty and frequency_penalty must be finite (0 = off)");
-    TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_set_penalties: vocabulary larger than 524,288 tokens");
-    tl_engine::PenaltyParams v = e->pen[slot];
-    v.repetition = repetition_penalty, v.presence = presence_penalty, v.frequency = frequency_penalty;
-    return pen_write(e, slot, v);
+    Pokes pk;
+    return settings_set(e, slot, pk, [&](SettingsEdits &ed) { return e->settings.set_penalties(slot, repetition_penalty, presence_penalty, frequency_penalty, ed); });
 }
 
 extern "C" int tl_engine_set_logit_bias(tl_engine *e, int slot, const int32_t *ids, const float *values, int n) {
     TL_TRY(slot_check(e, slot, true));
-    TL_REQUIRE(n >= 0 && n <= TL_MAX_LOGIT_BIAS, "engine_set_logit_bias: between 0 and TL_MAX_LOGIT_BIAS (1,024) entries");
-    TL_REQUIRE(n == 0 || (ids && values), "engine_set_logit_bias: null argument");
-    TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_set_logit_bias: vocabulary larger than 524,288 tokens");
-    tl_engine::PenaltyParams v = e->pen[slot];
-    v.bias_ids.assign(ids, ids + n);
-    v.bias_values.assign(values, values + n);
-    std::vector<int32_t> sorted(v.bias_ids);
-    std::sort(sorted.begin(), sorted.end());
-    for (int i = 0; i < n; ++i) {
-        TL_REQUIRE(sorted[i] >= 0 && sorted[i] < e->cfg.vocab_size, "engine_set_logit_bias: token id out of range");
-        TL_REQUIRE(i == 0 || sorted[i] != sorted[i - 1], "engine_set_logit_bias: a token id appears twice");
-        TL_REQUIRE(std::isfinite(values[i]) || values[i] == -INFINITY, "engine_set_logit_bias: values must be finite or -inf");
-    }
-    return pen_write(e, slot, v);
+    Pokes pk;
+    return settings_set(e, slot, pk, [&](SettingsEdits &ed) { return e->settings.set_logit_bias(slot, ids, values, n, ed); });
 }
 
 // ---- grammars (grammar.h) ----------------------------------------------------------------------------------------------------------
@@ -2621,16 +2241,9 @@ extern "C" void tl_grammar_destroy(tl_grammar *g) {
 extern "C" int tl_engine_set_grammar(tl_engine *e, int slot, const tl_grammar *g) {
     TL_TRY(slot_check(e, slot, true));
     TL_REQUIRE(!g || g->vocab->vocab == e->cfg.vocab_size, "engine_set_grammar: the grammar's vocabulary is not the engine's size");
-    tl_engine::PenaltyParams v = e->pen[slot];
-    const bool same = g && v.grammar == g;
-    v.grammar = g;
-    TL_TRY(pen_write(e, slot, v));
-    if (same) {  // the same automaton again: back to its start state
-        Pokes pk;
-        gr_poke_state(e, slot, g, pk);
-        return poke(e, pk);
-    }
-    return TL_OK;
+    const GrammarRef ref = g ? GrammarRef{(uint64_t)(uintptr_t)g->dev, g->stack, g->start, g} : GrammarRef{};
+    Pokes pk;
+    return settings_set(e, slot, pk, [&](SettingsEdits &ed) { return e->settings.set_grammar(slot, ref, ed); });
 }
 
 // the configuration of a slot with grammar `g` (a regex grammar's: (state, 0, 0)) once everything submitted has run: the slot's record,
@@ -2640,25 +2253,25 @@ static int gr_read_config(tl_engine *e, int slot, const tl_grammar *g, GrsConfig
     GrsConfig c{GR_END, 0, 0ull};
     if (g->stack) {
         GrammarStackRecord rec{};
-        TL_HIP(hipMemcpy(&rec, e->gr_stack + slot, sizeof(rec), hipMemcpyDeviceToHost));
+        TL_HIP(hipMemcpy(&rec, e->sdev<GrammarStackRecord>(SB_STACK, 0) + slot, sizeof(rec), hipMemcpyDeviceToHost));
         int which;
         c = grs_unpack((uint32_t)(rec.rec >> 32), &which);
         if (c.state >= 0) c.stack = rec.stack[which] & grs_mask(c.depth);
     } else {
         GrammarRecord rec{};
-        TL_HIP(hipMemcpy(&rec, e->gr_state + slot, sizeof(rec), hipMemcpyDeviceToHost));
+        TL_HIP(hipMemcpy(&rec, e->sdev<GrammarRecord>(SB_GRAMMAR, e->settings.at.gr_state) + slot, sizeof(rec), hipMemcpyDeviceToHost));
         c.state = rec.state;
     }
     int32_t pending = 0;
     TL_HIP(hipMemcpy(&pending, e->tokens + slot, 4, hipMemcpyDeviceToHost));
-    *out = e->gr_pending[slot] ? g->advance(c, pending) : c;
+    *out = e->settings.slots[slot].gr_pending ? g->advance(c, pending) : c;
     return TL_OK;
 }
 
 extern "C" int tl_engine_grammar_state(tl_engine *e, int slot, int *state, int *accepting) {
     TL_TRY(slot_check(e, slot, true));
     TL_REQUIRE(state, "engine_grammar_state: null argument");
-    const tl_grammar *g = e->pen[slot].grammar;
+    const tl_grammar *g = e->grammar_of(slot);
     TL_REQUIRE(g, "engine_grammar_state: the slot has no grammar");
     GrsConfig c;
     TL_TRY(gr_read_config(e, slot, g, &c));
@@ -2670,7 +2283,7 @@ extern "C" int tl_engine_grammar_state(tl_engine *e, int slot, int *state, int *
 extern "C" int tl_engine_grammar_config(tl_engine *e, int slot, int *state, int *depth, uint64_t *stack, int *accepting) {
     TL_TRY(slot_check(e, slot, true));
     TL_REQUIRE(state && depth && stack, "engine_grammar_config: null argument");
-    const tl_grammar *g = e->pen[slot].grammar;
+    const tl_grammar *g = e->grammar_of(slot);
     TL_REQUIRE(g, "engine_grammar_config: the slot has no grammar");
     GrsConfig c;
     TL_TRY(gr_read_config(e, slot, g, &c));
@@ -2720,25 +2333,21 @@ extern "C" void tl_stop_destroy(tl_stop *s) {
 
 extern "C" int tl_engine_set_stop(tl_engine *e, int slot, const tl_stop *set, int max_new_tokens) {
     TL_TRY(slot_check(e, slot, true));
+    // (the record refuses a negative budget too; here it keeps its place ahead of the set's checks, which need the tl_stop)
     TL_REQUIRE(max_new_tokens >= 0, "engine_set_stop: max_new_tokens must be nonnegative (0 = no budget)");
     if (set) {
         TL_REQUIRE(!set->vocab || set->vocab->vocab == e->cfg.vocab_size, "engine_set_stop: the set's vocabulary is not the engine's size");
         for (int32_t id : set->set.ids) TL_REQUIRE(id < e->cfg.vocab_size, "engine_set_stop: a stop id lies outside the engine's vocabulary");
     }
     TL_TRY(stop_reconcile(e));
-    const bool arm = set != nullptr || max_new_tokens > 0;
-    Slot &s = e->table.slots[slot];
-    if (!arm && !e->stop_mem) return TL_OK;  // disarming on an engine that never armed a slot: nothing to write
-    TL_TRY(stop_alloc(e));
-    e->stop[slot] = tl_engine::StopSlot{set, max_new_tokens, arm};
-    e->stop_host[slot] = StopRecord{};
     Pokes pk;
-    stop_poke(e, slot, e->stop[slot], pk);
-    if (s.stopped) {  // the one way to resume: a decode step takes the slot again
-        e->table.resume(slot);
-        if (!s.parked) pk.emplace_back(e->live + slot, 1);
-    }
-    return poke(e, pk);
+    const Slot &s = e->table.slots[slot];
+    // the one way to resume: a decode step takes the slot again (a slot can only have stopped on an engine that armed one)
+    if (s.stopped && !s.parked) pk.emplace_back(e->live + slot, 1);
+    const StopRef ref{(uint64_t)(uintptr_t)(set ? set->dev : nullptr), set};
+    TL_TRY(settings_set(e, slot, pk, [&](SettingsEdits &ed) { return e->settings.set_stop(slot, ref, max_new_tokens, ed); }));
+    if (s.stopped) e->table.resume(slot);
+    return TL_OK;
 }
 
 extern "C" int tl_engine_stop_state(tl_engine *e, int slot, tl_stop_state *out) {
@@ -2747,13 +2356,13 @@ extern "C" int tl_engine_stop_state(tl_engine *e, int slot, tl_stop_state *out) 
     TL_TRY(stop_reconcile(e));
     *out = tl_stop_state{};
     out->context = e->table.slots[slot].ctx;
-    if (!e->stop_mem || !e->stop[slot].armed) return TL_OK;
+    if (!e->settings.slots[slot].stop.armed) return TL_OK;
     if (!e->table.slots[slot].stopped) {  // a running slot's record: read now (a stopped slot's was read when it stopped)
         TL_TRY(aql_drain(e));
         TL_HIP(hipStreamSynchronize(e->stream));
-        TL_HIP(hipMemcpy(&e->stop_host[slot], e->stop_rec + slot, sizeof(StopRecord), hipMemcpyDeviceToHost));
+        TL_HIP(hipMemcpy(&e->settings.slots[slot].stop_host, e->sdev<StopRecord>(SB_STOP, e->settings.at.stop_rec) + slot, sizeof(StopRecord), hipMemcpyDeviceToHost));
     }
-    const StopRecord &r = e->stop_host[slot];
+    const StopMirror &r = e->settings.slots[slot].stop_host;
     *out = tl_stop_state{r.reason, r.index, r.generated, e->table.slots[slot].ctx, r.text_bytes, r.cut_bytes};
     return TL_OK;
 }
@@ -2817,22 +2426,21 @@ extern "C" int tl_sample_logits(const void *logits_dev, int rows, int vocab, con
 
 extern "C" int tl_engine_set_logprobs(tl_engine *e, int slot, int top_n) {
     TL_TRY(slot_check(e, slot, false));
-    TL_REQUIRE(top_n >= -1 && top_n <= LP_MAX_TOP, "engine_set_logprobs: top_n must be -1 (off) or 0 .. 20");
-    TL_REQUIRE(top_n < 0 || e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_set_logprobs: vocabulary larger than the routine's 524,288 tokens");
-    return lp_write(e, slot, top_n);
+    Pokes pk;
+    return settings_set(e, slot, pk, [&](SettingsEdits &ed) { return e->settings.set_logprobs(slot, top_n, e->table.slots[slot].produced, ed); });
 }
 
 extern "C" int tl_engine_read_logprobs(tl_engine *e, int slot, int count, tl_token_logprob *out) {
     TL_TRY(slot_check(e, slot, false));
     TL_REQUIRE(out && count >= 0 && count <= e->ring_cap, "engine_read_logprobs: bad count");
-    const int have = e->lp_n.empty() || e->lp_n[slot] < 0 ? 0 : e->table.slots[slot].produced - e->lp_from[slot];
+    const int have = e->settings.slots[slot].lp_n < 0 ? 0 : e->table.slots[slot].produced - e->settings.slots[slot].lp_from;
     TL_REQUIRE(count <= have, "engine_read_logprobs: fewer tokens have been produced since logprobs were switched on");
     if (count == 0) return TL_OK;
     TL_HIP(hipStreamSynchronize(e->stream));
     const size_t rec = (size_t)LP_RECORD_WORDS * 4;
     const int produced = e->table.slots[slot].produced;
     std::vector<char> ring((size_t)e->ring_cap * rec);
-    TL_HIP(hipMemcpy(ring.data(), e->lp_ring + (size_t)slot * e->ring_cap * LP_RECORD_WORDS, ring.size(), hipMemcpyDeviceToHost));
+    TL_HIP(hipMemcpy(ring.data(), e->sdev<uint32_t>(SB_LOGPROB, e->settings.at.lp_ring) + (size_t)slot * e->ring_cap * LP_RECORD_WORDS, ring.size(), hipMemcpyDeviceToHost));
     for (int i = 0; i < count; ++i) memcpy(out + i, ring.data() + (size_t)((produced - count + i) % e->ring_cap) * rec, rec);
     return TL_OK;
 }
@@ -2840,9 +2448,9 @@ extern "C" int tl_engine_read_logprobs(tl_engine *e, int slot, int count, tl_tok
 extern "C" int tl_engine_read_pending_logprobs(tl_engine *e, int count, tl_token_logprob *out) {
     TL_REQUIRE(e && out, "engine_read_pending_logprobs: null argument");
     TL_REQUIRE(count > 0 && count <= e->cfg.max_batch, "engine_read_pending_logprobs: count out of range");
-    TL_REQUIRE(e->lp_mem, "engine_read_pending_logprobs: no slot has recorded log-probabilities (tl_engine_set_logprobs)");
+    TL_REQUIRE(e->settings_mem[SB_LOGPROB], "engine_read_pending_logprobs: no slot has recorded log-probabilities (tl_engine_set_logprobs)");
     TL_HIP(hipStreamSynchronize(e->stream));
-    TL_HIP(hipMemcpy(out, e->lp_pending, (size_t)count * LP_RECORD_WORDS * 4, hipMemcpyDeviceToHost));
+    TL_HIP(hipMemcpy(out, e->sdev<uint32_t>(SB_LOGPROB, e->settings.at.lp_pending), (size_t)count * LP_RECORD_WORDS * 4, hipMemcpyDeviceToHost));
     return TL_OK;
 }
 
@@ -2983,7 +2591,7 @@ extern "C" int tl_engine_lora_unload(tl_engine *e, int adapter) {
     TL_REQUIRE(e, "engine_lora_unload: null engine");
     TL_REQUIRE(adapter >= 0 && adapter < (int)e->lora_ad.size() && e->lora_ad[adapter].mem, "engine_lora_unload: no such adapter");
     for (int s = 0; s < e->cfg.max_batch; ++s)
-        TL_REQUIRE(e->lora_of[s] != adapter, "engine_lora_unload: a live or parked slot carries the adapter (release it first)");
+        TL_REQUIRE(e->settings.slots[s].lora != adapter, "engine_lora_unload: a live or parked slot carries the adapter (release it first)");
     TL_TRY(aql_drain(e));
     TL_HIP(hipStreamSynchronize(e->stream));
     const size_t n = (size_t)e->cfg.num_layers * tl_engine::LORA_GROUPS;
@@ -2999,12 +2607,13 @@ extern "C" int tl_engine_set_lora(tl_engine *e, int slot, int adapter) {
                "engine_set_lora: the adapter is -1 (none) or the id of a resident adapter");
     TL_REQUIRE(e->table.slots[slot].ctx == 0 && e->table.slots[slot].pages.empty(),
                "engine_set_lora: the slot already holds tokens (a sequence's K/V are all computed under one adapter: set it before the first prefill)");
-    return lora_write(e, slot, adapter);
+    Pokes pk;
+    return settings_set(e, slot, pk, [&](SettingsEdits &ed) { return e->settings.set_lora(slot, adapter, ed); });
 }
 
 extern "C" int tl_engine_slot_lora(const tl_engine *e, int slot) {
     if (!e || slot < 0 || slot >= e->cfg.max_batch) return LORA_NONE;
-    return e->lora_of[slot];
+    return e->settings.slots[slot].lora;
 }
 
 extern "C" int tl_engine_lora_stats(const tl_engine *e, tl_lora_stats *out) {
@@ -3131,7 +2740,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
     TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens, (size_t)total * 4, hipMemcpyHostToDevice, e->stream));
     for (int i = 0; i < n_seqs; ++i) {  // the chunk's tokens enter the history of a slot that processes its logits (logit_process.h)
         if (!step_processes_slot(e, seqs[i].slot)) continue;
-        const LogitMarkArgs mk{e->prefill_tokens + seqs[i].row0, seqs[i].len, c.vocab_size, (uint32_t *)e->pen_history, (long)seqs[i].slot * c.vocab_size};
+        const LogitMarkArgs mk{e->prefill_tokens + seqs[i].row0, seqs[i].len, c.vocab_size, e->sdev<uint32_t>(SB_PROCESS, e->settings.at.pen_history), (long)seqs[i].slot * c.vocab_size};
         hipLaunchKernelGGL(logit_mark_prompt_kernel, dim3(ceil_div(seqs[i].len, 256)), dim3(256), 0, e->stream, mk);
         TL_CHECK_LAUNCH("engine prompt marking");
     }
@@ -3150,7 +2759,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
         int row0[16], len[16], ad[16];
         bool any = false;
         for (int i = 0; i < n_seqs; ++i) {
-            row0[i] = seqs[i].row0, len[i] = seqs[i].len, ad[i] = e->lora_of[seqs[i].slot];
+            row0[i] = seqs[i].row0, len[i] = seqs[i].len, ad[i] = e->settings.slots[seqs[i].slot].lora;
             if (ad[i] >= 0) any = true, e->lora_prefill_rows += seqs[i].len;
         }
         if (any) {
@@ -3162,7 +2771,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
     const auto lora_on = [&](int l, int g) {
         if (lora_tiles == 0) return false;
         for (int i = 0; i < n_seqs; ++i) {
-            const int a = e->lora_of[seqs[i].slot];
+            const int a = e->settings.slots[seqs[i].slot].lora;
             if (a >= 0 && e->lora_ad[a].has[(size_t)l * tl_engine::LORA_GROUPS + g]) return true;
         }
         return false;
@@ -3238,7 +2847,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
     for (int i = 0; i < n_seqs; ++i) {
         // (seqs[i].start is the slot's context; the ids of a slot with a LoRA adapter stay unknown to the prefix cache: its K/V are the adapter's)
         e->table.appended(seqs[i].slot, tokens + seqs[i].row0, seqs[i].len, !e->lora_slot(seqs[i].slot));
-        e->gr_pending[seqs[i].slot] = 0;  // a pending token that is prefilled past is never fed
+        e->settings.appended(seqs[i].slot, true);  // a pending token that is prefilled past is never fed (an embedding keeps its mean: embed_pool)
         pk.emplace_back(e->context_lens + seqs[i].slot, seqs[i].start + seqs[i].len);
     }
     TL_TRY(poke(e, pk));
@@ -3253,7 +2862,7 @@ static int prefill_first_token(tl_engine *e, int slot, int row, const char *what
     launch_logit_chain(e, e->logits + (size_t)row * e->cfg.vocab_size, row, 1, slot, 0, e->h, nullptr, 0, nullptr, nullptr, step_features(e, slot, 1), nullptr);
     TL_CHECK_LAUNCH(what);
     e->table.slots[slot].produced += 1;
-    e->gr_pending[slot] = 1;
+    e->settings.pending_produced(slot);
     return TL_OK;
 }
 
@@ -3412,7 +3021,7 @@ static int embed_args_check(const tl_engine *e, int pooling, int dim, bool finis
 // MEAN: every chunk restarts its slot's running sum at context 0 or continues it at exactly the rows the sum holds
 static int embed_mean_check(const tl_engine *e, const PrefillSeq *seqs, int n_seqs) {
     for (int i = 0; i < n_seqs; ++i)
-        TL_REQUIRE(seqs[i].start == 0 || e->emb_rows[seqs[i].slot] == seqs[i].start,
+        TL_REQUIRE(seqs[i].start == 0 || e->settings.slots[seqs[i].slot].emb_rows == seqs[i].start,
                    "engine_embed: mean pooling continues a text embedded from context 0 with TL_POOL_MEAN chunks only (the slot's context came from elsewhere)");
     return TL_OK;
 }
@@ -3447,12 +3056,12 @@ static int embed_pool(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const in
         total += q.len;
         if (mean) {
             row0[n] = q.row0, len[n] = q.len, sum_index[n] = q.slot, fin[n] = finish[i] ? 1 : 0;
-            prior[n] = q.start == 0 ? 0 : e->emb_rows[q.slot];
-            e->emb_rows[q.slot] = prior[n] + q.len;
+            prior[n] = q.start == 0 ? 0 : e->settings.slots[q.slot].emb_rows;
+            e->settings.slots[q.slot].emb_rows = prior[n] + q.len;
             n_finish += fin[n++];
             continue;
         }
-        e->emb_rows[q.slot] = -1;
+        e->settings.rewound(q.slot);  // (a LAST chunk: the context no longer is a running mean's)
         if (!finish[i]) continue;
         TL_HIP(hipMemcpyAsync(e->h + (size_t)n * H, e->x + (size_t)(q.row0 + q.len - 1) * H, H * 2, hipMemcpyDeviceToDevice, e->stream));
         row0[n] = n, len[n] = 1, prior[n] = 0, sum_index[n] = 0, fin[n] = 1;
@@ -3496,8 +3105,7 @@ extern "C" int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, i
     TL_REQUIRE(e && out_ids, "engine_verify: null argument");
     TL_REQUIRE(n >= 1 && n <= 8, "engine_verify: between 1 and 8 tokens per call (the paged decode kernel's query rows)");
     TL_TRY(slot_check_feeds(e, slot));
-    TL_REQUIRE(!e->smp[slot].samples(), "engine_verify: the slot samples (verification is greedy; set temperature 0 first)");
-    TL_REQUIRE(!e->pen[slot].processes(), "engine_verify: the slot processes its logits (verification takes the raw rows; make it neutral first)");
+    TL_TRY(table_rc(e->settings.refuses_verify(slot)));
     TL_TRY(prefill_impl(e, slot, tokens, n, 2));
     TL_HIP(hipMemcpyAsync(out_ids, e->verify_ids, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
     TL_HIP(hipStreamSynchronize(e->stream));
@@ -3511,8 +3119,7 @@ extern "C" int tl_engine_verify_sampled(tl_engine *e, int slot, const int32_t *t
     TL_REQUIRE(n == 1 || draft_logits_dev, "engine_verify_sampled: the rows the proposals were drawn from are missing");
     TL_REQUIRE(std::isfinite(draft_temperature) && draft_temperature >= 0.f, "engine_verify_sampled: the draft's temperature must be finite and >= 0");
     TL_TRY(slot_check_feeds(e, slot));
-    TL_REQUIRE(!e->pen[slot].processes(), "engine_verify_sampled: the slot processes its logits (verification takes the raw rows; make it neutral first)");
-    TL_REQUIRE(!e->trn[slot].truncates(), "engine_verify_sampled: the slot truncates (min-p / typical-p / Mirostat keep other sets than the verification's; switch them off first)");
+    TL_TRY(table_rc(e->settings.refuses_verify_sampled(slot)));
     TL_REQUIRE(e->cfg.vocab_size <= SMP_MAX_VOCAB, "engine_verify_sampled: vocabulary larger than the sampler's 524,288 tokens");
     using Rec = tl_engine::SpecRecord;
     if (!e->spec_rec) {
@@ -3521,7 +3128,7 @@ extern "C" int tl_engine_verify_sampled(tl_engine *e, int slot, const int32_t *t
         e->stats.workspace_bytes += sizeof(Rec);
     }
     const int ctx = e->table.slots[slot].ctx;
-    const tl_engine::SampleParams &sp = e->smp[slot];
+    const SampleParams &sp = e->settings.slots[slot].smp;
     TL_TRY(prefill_impl(e, slot, tokens, n, 2));
     Rec r{};
     for (int i = 0; i < n; ++i) {
@@ -3619,10 +3226,7 @@ static int verify_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t
         const int slot = slots[i];
         TL_TRY(slot_check_feeds(e, slot));
         for (int j = 0; j < i; ++j) TL_REQUIRE(slots[j] != slot, w + "a slot appears twice");
-        TL_REQUIRE(!e->smp[slot].samples(), w + "a slot samples (verification is greedy; set temperature 0 first)");
-        TL_REQUIRE(!e->pen[slot].processes(), w + "a slot processes its logits (verification takes the raw rows; make it neutral first)");
-        TL_REQUIRE(!e->trn[slot].mirostat(), w + "a slot has Mirostat on (switch it off first)");
-        TL_REQUIRE(!e->lora_slot(slot), w + "a slot carries a LoRA adapter (adapters are verified one slot at a time, tl_engine_verify)");
+        TL_TRY(table_rc(e->settings.refuses_verify_batch(slot)));
         const Slot &s = e->table.slots[slot];
         const int need = (s.ctx + lens[i] + c.page_size - 1) / c.page_size;
         TL_REQUIRE(need <= c.max_pages_per_seq, "engine: sequence exceeds max_pages_per_seq * page_size tokens");
@@ -3735,8 +3339,7 @@ static int verify_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const i
                                 e->stream));
     for (int i = 0; i < n_seqs; ++i) {
         e->table.appended(seqs[i].slot, tokens + seqs[i].row0, seqs[i].len);
-        e->gr_pending[seqs[i].slot] = 0;  // a pending token that is appended is never fed again
-        e->emb_rows[seqs[i].slot] = -1;
+        e->settings.appended(seqs[i].slot, false);  // a pending token that is appended is never fed again
         pk.emplace_back(e->context_lens + seqs[i].slot, seqs[i].start + seqs[i].len);
     }
     TL_TRY(poke(e, pk));
@@ -3821,7 +3424,7 @@ static int prepare_step(tl_engine *e, int batch, SplitPlan *sp, bool *on_queue =
 static void step_done(tl_engine *e, int batch) {
     e->table.step_done(batch);
     for (int b = 0; b < batch; ++b)
-        if (e->slot_runs(b)) e->gr_pending[b] = 1;
+        if (e->slot_runs(b)) e->settings.pending_produced(b);
     e->stats.decode_steps++;
     e->logits_rows = batch, e->logits_slot = -1;
 }
@@ -3847,7 +3450,7 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
         SplitPlan sp;
         TL_TRY(prepare_step(e, batch, &sp, &on_queue));
         if (use_graph && e->warmed) {
-            const auto key = std::make_pair(batch, sp.key() | f.key_bits());
+            const auto key = std::make_pair(batch, sp.key() | step_key_bits(f));
             auto it = e->plans.find(key);
             if (it == e->plans.end()) {
                 // The split plan (and with it the key) changes every 64 * n_splits tokens of context: a long run would keep one
@@ -3944,8 +3547,8 @@ extern "C" int tl_engine_copy_logits(tl_engine *e, void *dst_dev, int rows) {
 extern "C" int tl_engine_copy_processed_logits(tl_engine *e, void *dst_dev, int rows) {
     TL_REQUIRE(e && dst_dev, "engine_copy_processed_logits: null argument");
     TL_REQUIRE(rows > 0 && rows <= e->cfg.max_batch, "engine_copy_processed_logits: rows out of range");
-    TL_REQUIRE(e->pen_rows, "engine_copy_processed_logits: no slot of this engine has processed its logits yet");
-    TL_HIP(hipMemcpyAsync(dst_dev, e->pen_rows, (size_t)rows * e->cfg.vocab_size * 2, hipMemcpyDeviceToDevice, e->stream));
+    TL_REQUIRE(e->settings_mem[SB_PROCESS], "engine_copy_processed_logits: no slot of this engine has processed its logits yet");
+    TL_HIP(hipMemcpyAsync(dst_dev, e->sdev<uint16_t>(SB_PROCESS, e->settings.at.pen_rows), (size_t)rows * e->cfg.vocab_size * 2, hipMemcpyDeviceToDevice, e->stream));
     return TL_OK;
 }
 extern "C" const int32_t *tl_engine_tokens_dev(const tl_engine *e) { return e ? e->tokens : nullptr; }
