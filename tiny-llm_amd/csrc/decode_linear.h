@@ -99,7 +99,15 @@ static int tiled_w4_make(const tl_w4 &w, hipStream_t st, TiledW4Mem &mem, TiledW
     return TL_OK;
 }
 
-struct LinearCtx {
+// the router's scratch: the buffers a caller may stand its own in for the duration of a pass (the batched verification's 64 rows)
+struct LinearScratch {
+    uint16_t *xn = nullptr;  // rows of an RMSNorm that runs as its own launch
+    uint16_t *gu = nullptr, *tmp = nullptr;  // GEMM path with separate epilogue launches: gate|up rows ahead of SwiGLU, the product ahead of the residual add
+    // split-K partials of the GEMM and slice planes of the skinny matmul (a call may bring planes of its own: Proj::planes)
+    void *splitk_ws = nullptr;
+    size_t splitk_ws_bytes = 0;
+};
+struct LinearCtx : LinearScratch {
     hipStream_t stream = nullptr;
     float rms_norm_eps = 0.f;
     // decode-path copy of every W4 matrix in the tiled MFMA layout (qmv3.h); keyed by the checkpoint pointer
@@ -108,11 +116,6 @@ struct LinearCtx {
     // bf16 -- bf16(q * s + beta), the B operand the reference's tile GEMM forms in threadgroup memory (quantized_matmul.metal:96-249) -- for
     // the plain bf16 GEMM of gemm8.h (256 x 256 tiles by LDS-DMA, no dequantisation in the loop).  7.3 GB at Qwen3-4B, of 288.
     std::map<const uint32_t *, uint16_t *> bf16w;
-    uint16_t *xn = nullptr;  // rows of an RMSNorm that runs as its own launch
-    // split-K partials of the GEMM and slice planes of the skinny matmul (a call may bring planes of its own: Proj::planes)
-    void *splitk_ws = nullptr;
-    size_t splitk_ws_bytes = 0;
-    uint16_t *gu = nullptr, *tmp = nullptr;  // GEMM path with separate epilogue launches: gate|up rows ahead of SwiGLU, the product ahead of the residual add
     bool use_gemm8 = true;  // tl_engine_set_option "gemm8" = 0: every chunk through the W4 GEMM (qmm.hip), the twin
     bool fuse_reduce_norm = true;  // "prefill_reduce_norm" = 0: the split-K residual reduction and the RMSNorm behind it as two launches, the twin
     bool gemm_fused_epilogue = true;    // tl_engine_set_option "gemm_fused_epilogue" = 0: residual / SwiGLU of the prefill GEMM as separate launches

@@ -12,6 +12,7 @@
 
 #include "decode_linear.h"  // the projection router; with it common.h, engine_kernels.h and the decode matmuls' headers
 #include "device_block.h"
+#include "engine_layout.h"
 #include "step_end.h"  // the three step-end kernels; with it sample.h and logprob.h
 #include "logit_process.h"
 #include "truncate.h"
@@ -135,15 +136,15 @@ struct tl_engine {
 
     int32_t *block_table = nullptr, *context_lens = nullptr, *tokens = nullptr, *live = nullptr, *produced = nullptr,
             *ring = nullptr, *scratch_ctx = nullptr, *prefill_tokens = nullptr;
-    uint16_t *x = nullptr, *h = nullptr, *xn = nullptr, *qkv = nullptr, *q_t = nullptr, *attn_t = nullptr,
-             *attn = nullptr, *act = nullptr, *logits = nullptr;
-    float *attn_ws = nullptr;
+    // the shared hand-over buffers (engine_layout.h Act; x_out is the residual stream x): every prefill pass, and the decode steps that
+    // do not run on the per-layer buffers below
+    Act shared;
+    uint16_t *q_t = nullptr, *attn_t = nullptr, *logits = nullptr;
     int last_attn_launches = 0;
     // lm_head GEMV of a 1-4-row decode step: per 16-logit tile (max, lowest index) pairs for step_end_kernel (qmv3.h tile_max);
     // tl_engine_set_option "lmhead_tile_max" = 0: step_end reads the logits row again
-    f32x2 *lm_tile_max = nullptr;            // [8][vocab / 16]
+    f32x2 *lm_tile_max = nullptr;            // [VERIFY_MAX_LEN][vocab / 16]
     bool lm_tile_max_on = true;
-    float *ss_x = nullptr, *ss_h = nullptr;  // [max_batch][QM3_SS] partial sums of squares of the rows of x / h (qmm3.h)
     // At 5 .. 64 decode rows the qkv projection's slice reduction is not launched; the decode-attention kernel adds the fp32 slice
     // partials itself (engine_kernels.h, QP).  Measured in round 3 (profiles/r03_labs/batched_decode_status.jsonl): 5 / 8 / 16 / 64
     // sequences 1.87 -> 1.81, 1.91 -> 1.89, 2.08 -> 2.03, 3.63 -> 3.52 ms per step.  tl_engine_set_option "attn_qkv_partials" = 0 launches the reduction.
@@ -155,17 +156,17 @@ struct tl_engine {
     // (128-token windows: 1.022).  Other split counts, more sequences or another head size keep the merge launch (wo_merge_applicable).
     bool wo_merges_attn = true;
     int32_t *verify_ids = nullptr;  // greedy ids of the rows of the last tl_engine_verify
-    // tl_engine_verify_sampled: the per-row arrays of its one tl_spec_sample_rows launch (8 rows), allocated by the first call
+    // tl_engine_verify_sampled: the per-row arrays of its one tl_spec_sample_rows launch (VERIFY_MAX_LEN rows), allocated by the first call
     struct SpecRecord {
-        int32_t proposal[8];
-        float t_temperature[8];
-        int32_t t_top_k[8];
-        float t_top_p[8], d_temperature[8];
-        int32_t d_top_k[8];
-        float d_top_p[8];
-        int32_t position[8];
-        uint64_t seed[8];
-        int32_t accept[8], alt[8];  // (results: behind everything the host writes)
+        int32_t proposal[VERIFY_MAX_LEN];
+        float t_temperature[VERIFY_MAX_LEN];
+        int32_t t_top_k[VERIFY_MAX_LEN];
+        float t_top_p[VERIFY_MAX_LEN], d_temperature[VERIFY_MAX_LEN];
+        int32_t d_top_k[VERIFY_MAX_LEN];
+        float d_top_p[VERIFY_MAX_LEN];
+        int32_t position[VERIFY_MAX_LEN];
+        uint64_t seed[VERIFY_MAX_LEN];
+        int32_t accept[VERIFY_MAX_LEN], alt[VERIFY_MAX_LEN];  // (results: behind everything the host writes)
     };
     DeviceBlock spec_mem;
     SpecRecord *spec_rec = nullptr;
@@ -264,15 +265,7 @@ struct tl_engine {
     // Per-layer decode activations (common.h, "activations between the launches of a decode step"): with the AQL route every value a launch
     // hands to a later launch of the SAME step lives at an address written once per step -- layer l's x / h / weighted h / qkv / attention
     // rows and partials / SwiGLU rows / sums of squares have their own buffers (1-4 rows: the fused-GEMV route; 36 x ~0.3 MB at Qwen3-4B)
-    struct LayerAct {
-        uint16_t *x_out, *h, *xn, *qkv, *attn, *act;
-        float *ss_x_out, *ss_h, *attn_ws;
-        // 5 .. 64 rows (round 5): x_out weighted for the NEXT RMSNorm, and the fp32 slice planes of the layer's K-sliced matmuls
-        // (wo at 17-32 rows, w_down at every row count): written once per step like everything else here
-        uint16_t *xw;
-        float *planes[2];
-    };
-    std::vector<LayerAct> layer_act;
+    std::vector<Act> layer_act;  // (5 .. 64 rows, round 5: xw is x_out weighted for the NEXT RMSNorm, planes the slice planes of wo / w_down)
     DeviceBlock layer_act_mem;
     int layer_act_rows = 0;       // rows the per-layer buffers hold (0: none)
     size_t layer_ws_bytes = 0;    // attention partials per layer
@@ -303,16 +296,15 @@ struct tl_engine {
     // (the engine's own is sized for max(max_batch, max_prefill_rows) rows), the attention partials, the descriptors of one call
     // (uploaded in one copy) and its results
     struct VerifyScratch {
-        enum { TOKENS, ROW_SLOT, ROW_POS, SEQ_SLOT, SEQ_ROW0, SEQ_LEN, SEQ_CTX, DESC_ARRAYS };  // the arrays of `desc`, 64 words each
+        enum { TOKENS, ROW_SLOT, ROW_POS, SEQ_SLOT, SEQ_ROW0, SEQ_LEN, SEQ_CTX, DESC_ARRAYS };  // the arrays of `desc`, VERIFY_BATCH_ROWS words each
         DeviceBlock mem;
-        uint16_t *x = nullptr, *h = nullptr, *xn = nullptr, *qkv = nullptr, *q = nullptr, *attn = nullptr, *act = nullptr, *gu = nullptr,
-                 *tmp = nullptr, *logits = nullptr;
-        float *ss_x = nullptr, *ss_h = nullptr, *attn_ws = nullptr;
-        void *splitk_ws = nullptr;
-        size_t splitk_ws_bytes = 0, attn_ws_rows = 0;
+        Act act;           // the hand-over buffers of every layer
+        LinearScratch lin;  // what the projection router uses for the duration of a pass: xn (act's), gu, tmp and the matmul workspace
+        uint16_t *q = nullptr, *logits = nullptr;
+        size_t attn_ws_rows = 0;
         int32_t *desc = nullptr, *greedy = nullptr;
         tl_verify_result *results = nullptr;
-        const int32_t *arr(int which) const { return desc + which * 64; }
+        const int32_t *arr(int which) const { return desc + which * VERIFY_BATCH_ROWS; }
     } vb;
 
     int qkv_dim() const { return (cfg.num_heads + 2 * cfg.num_kv_heads) * cfg.head_dim; }
@@ -581,7 +573,7 @@ static LoraShape lora_shape(const tl_engine *e, int group) {
         default: return {c.intermediate_size, c.hidden_size, LORA_SEG_PLAIN, 0, 0};
     }
 }
-static int lora_tiles_cap(const tl_engine *e) { return std::max(lora_max_tiles(e->rows_cap, 16), ceil_div(e->cfg.max_batch, LORA_TILE)); }
+static int lora_tiles_cap(const tl_engine *e) { return std::max(lora_max_tiles(e->rows_cap, PACKED_MAX_SEQS), ceil_div(e->cfg.max_batch, LORA_TILE)); }
 // the first load: the device table (all zero: nothing adapted), the per-slot ids (all none), the tile lists and the workspaces
 static int lora_alloc(tl_engine *e) {
     if (e->lora_mem) return TL_OK;
@@ -1011,12 +1003,11 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, const StepFeature
     // the w_down epilogue of the previous layer, or by one pointwise launch ahead of layer 0)
     bool xw = false;
     // where the residual stream, its weighted copy and its sums of squares stand (the shared buffers, or the last layer's own in a per-layer mode)
-    uint16_t *x_cur = e->x, *xw_cur = e->xn;
-    float *ssx_cur = e->ss_x;
-    // a layer's hand-over buffers: the shared ones, or -- the AQL route's per-layer modes -- its own (written once per step)
-    tl_engine::LayerAct shared{};
-    shared.x_out = e->x, shared.h = e->h, shared.xn = e->xn, shared.xw = e->xn, shared.qkv = e->qkv, shared.attn = e->attn, shared.act = e->act;
-    shared.ss_x_out = e->ss_x, shared.ss_h = e->ss_h, shared.attn_ws = e->attn_ws;  // (no slice planes: the context's workspace)
+    uint16_t *x_cur = e->shared.x_out, *xw_cur = e->shared.xn;
+    float *ssx_cur = e->shared.ss_x_out;
+    // a layer's hand-over buffers: the shared ones (no slice planes: the context's workspace), or -- the AQL route's per-layer modes -- its
+    // own (written once per step)
+    const Act &shared = e->shared;
     for (int l = 0; l < c.num_layers; ++l) {
         const tl_layer_weights &w = e->layers[l];
         const LayerRoute &rt = route.layers[l];
@@ -1025,14 +1016,14 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, const StepFeature
         // fire there; should it ever, the step must not be replayed as "written once" over buffers written several times
         const bool batched = !lora && rt.batched && x_ss > 0 && qmm3_takes_ss(x_ss);
         TL_REQUIRE(batched || !route.per_layer_b, "engine: a layer fell out of the batched branch of a step planned on the per-layer buffers");
-        const tl_engine::LayerAct &b = (batched ? route.per_layer_b : route.per_layer) ? e->layer_act[l] : shared;
+        const Act &b = (batched ? route.per_layer_b : route.per_layer) ? e->layer_act[l] : shared;
         ProjResult r;
         if (batched && rt.qkv6) {
             if (!xw) {
                 const long n8 = (long)batch * c.hidden_size / 8;
                 hipLaunchKernelGGL(weight_rows_kernel, dim3(ceil_div(n8, 256)), dim3(256), 0, e->stream, x_cur, (const uint16_t *)w.input_norm_dev,
-                                   e->xn, n8, c.hidden_size / 8, route.frag ? 1 : 0);
-                xw_cur = e->xn;
+                                   e->shared.xn, n8, c.hidden_size / 8, route.frag ? 1 : 0);
+                xw_cur = e->shared.xn;
             }
             Proj p = proj(w.wqkv, xw_cur, b.qkv, batch);
             p.ss_in = ssx_cur, p.ss_in_n = x_ss, p.frag = route.frag;
@@ -1111,7 +1102,7 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, const StepFeature
         TL_TRY(engine_linear(ctx, ph, pc, &rh));
     }
     const bool tile_max = rh.maxima_rows == batch;
-    launch_logit_chain(e, e->logits, 0, batch, 0, 1, e->x, tile_max ? e->lm_tile_max : nullptr, tile_max ? e->head().rows / 16 : 0, e->ss_x, e->tokens, f, pc);
+    launch_logit_chain(e, e->logits, 0, batch, 0, 1, e->shared.x_out, tile_max ? e->lm_tile_max : nullptr, tile_max ? e->head().rows / 16 : 0, e->shared.ss_x_out, e->tokens, f, pc);
     TL_CHECK_LAUNCH("engine step end");
     return TL_OK;
 }
@@ -1191,6 +1182,160 @@ static int settings_carry(tl_engine *e, int src, int dst, bool move, Pokes &pk) 
 }  // namespace tl
 
 // ================================================================================================
+// ---- the engine's memory (engine_layout.h) -------------------------------------------------------------------------------------------------
+static_assert(POOL_MAX_SEQS == PACKED_MAX_SEQS, "pool.h takes the sequences of a packed pass");
+static_assert(VA_MAX_ROWS == VERIFY_BATCH_ROWS && VA_MAX_LEN == VERIFY_MAX_LEN, "verify_attn_host.h and the layout size one pass");
+static_assert(sizeof(tl_engine::SpecRecord::proposal) == VERIFY_MAX_LEN * sizeof(int32_t), "SpecRecord holds the rows of one tl_engine_verify_sampled");
+static_assert(tl_engine::VerifyScratch::DESC_ARRAYS == VERIFY_DESC_ARRAYS, "the layout sizes `desc` by its arrays");
+
+// what the layouts ask of the device headers and of the engine as it stands (matmul_ws_need: verify_alloc's own)
+static LayoutInputs layout_inputs(const tl_engine *e) {
+    LayoutInputs in;
+    in.attn_ws_bytes = e->attn_ws_bytes, in.attn_ws_pad = ATTN_WS_PAD, in.qm3_ss = QM3_SS;
+    in.plane_bytes[0] = e->layer_plane_bytes[0], in.plane_bytes[1] = e->layer_plane_bytes[1];
+    in.matmul_ws_engine = e->lin.splitk_ws_bytes, in.aql = e->aql_on, in.ring_cap = e->ring_cap, in.tile_max_bytes = sizeof(f32x2);
+    in.verify_ws_rows = verify_ws_rows(e->cfg.num_heads), in.verify_head_dim = VA_D, in.verify_result_bytes = sizeof(tl_verify_result);
+    in.moe_k = e->moe_k_max, in.moe_e = e->moe_e_max, in.moe_i = e->moe_i_max;
+    return in;
+}
+
+// Bytes the matmuls of the engine's matrices need of the router's workspace: the fp32 slice partials of the skinny matmul's plans at
+// s0 .. s1 rows and the split-K partials of the GEMM at g0 .. g1 rows, over the five matrix shapes (the first layer that has a dense MLP
+// sizes the MLP's) and, with `routers`, the MoE routers
+static size_t matmul_ws_need(const tl_engine *e, int s0, int s1, int g0, int g1, bool routers) {
+    const tl_layer_weights *dense = &e->layers[0];
+    for (const auto &l : e->layers)
+        if (l.wgu.weight_dev) {
+            dense = &l;
+            break;
+        }
+    std::vector<tl_w4> mats = {e->layers[0].wqkv, e->layers[0].wo, dense->wgu, dense->wdown, e->head()};
+    for (int l = 0; routers && l < e->cfg.num_layers; ++l)
+        if (e->is_moe(l)) mats.push_back(e->moe[l].router);
+    size_t need = 0;
+    for (const tl_w4 &w : mats) {
+        if (!w.weight_dev) continue;
+        for (int M = s0; M <= s1; ++M) {
+            const Qmm3Plan p3 = qmm3_plan(M, w.cols, w.rows);
+            if (p3.ok) need = std::max(need, p3.partial_bytes);
+        }
+        for (int M = g0; M <= g1; ++M) need = std::max(need, tl_quantized_matmul_workspace_bytes(M, w.cols, w.rows, TL_BF16, 1, 1));
+    }
+    return need;
+}
+
+// ---- the steps of tl_engine_create_kv, in the order it takes them ----------------------------------------------------------------
+// the K / V page pools of every layer (FP8 pages: their row scales beside them), zeroed
+static int create_kv_pools(tl_engine *e) {
+    const tl_engine_config &c = e->cfg;
+    e->layer_pool_elems = (size_t)c.num_pages * c.num_kv_heads * c.page_size * c.head_dim;
+    const size_t pool_bytes = e->layer_pool_elems * e->kv_elem_bytes() * c.num_layers;
+    TL_TRY(e->kv_mem[0].alloc(pool_bytes, "engine_create: hipMalloc(key pages) failed"));
+    TL_TRY(e->kv_mem[1].alloc(pool_bytes, "engine_create: hipMalloc(value pages) failed"));
+    e->kpool = e->kv_mem[0].at<uint16_t>(), e->vpool = e->kv_mem[1].at<uint16_t>();
+    e->kv_bytes = 2 * pool_bytes;
+    if (e->kv_format == TL_KV_FP8_E4M3) {
+        // one float32 scale per (page, kv head, slot) row; zero like the codes (a zero scale times a zero code is the zero the bf16 pool holds)
+        e->layer_scale_elems = (size_t)c.num_pages * c.num_kv_heads * c.page_size;
+        const size_t scale_bytes = e->layer_scale_elems * 4 * c.num_layers;
+        TL_TRY(e->kv_mem[2].alloc(scale_bytes, "engine_create: hipMalloc(key scales) failed"));
+        TL_TRY(e->kv_mem[3].alloc(scale_bytes, "engine_create: hipMalloc(value scales) failed"));
+        e->kscale_pool = e->kv_mem[2].at<float>(), e->vscale_pool = e->kv_mem[3].at<float>();
+        if (hipMemsetAsync(e->kscale_pool, 0, scale_bytes, e->stream) != hipSuccess ||
+            hipMemsetAsync(e->vscale_pool, 0, scale_bytes, e->stream) != hipSuccess)
+            return fail(TL_ERR_HIP, "engine_create: memset(KV scales) failed");
+        e->kv_bytes += 2 * scale_bytes;
+    }
+    // Masked (out-of-context) token slots are still loaded and multiplied by a zero weight in the decode kernel,
+    // so the pools must never hold NaN/Inf bit patterns: start from zeros (kernels only ever write finite values).
+    if (hipMemsetAsync(e->kpool, 0, pool_bytes, e->stream) != hipSuccess ||
+        hipMemsetAsync(e->vpool, 0, pool_bytes, e->stream) != hipSuccess)
+        return fail(TL_ERR_HIP, "engine_create: memset(KV pools) failed");
+    return TL_OK;
+}
+
+// the per-layer decode activations of the AQL route (engine_layout.h LayerLayout), zeroed
+static int create_layer_acts(tl_engine *e) {
+    const tl_engine_config &c = e->cfg;
+    const int q_dim = e->q_dim();
+    // slice planes of the sliced matmuls a batched step can take (wo, w_down), the largest over 5 .. rows rows
+    for (int M = std::min(5, e->lin.qmm3_min_rows); M <= layer_act_rows(c.max_batch); ++M) {
+        const Qmm3Plan pw = qmm3_plan(M, q_dim, c.hidden_size, -1), pd = qmm3_plan(M, c.intermediate_size, c.hidden_size, -1);
+        if (pw.ok) e->layer_plane_bytes[0] = std::max(e->layer_plane_bytes[0], align_up(pw.partial_bytes, 256));
+        if (pd.ok) e->layer_plane_bytes[1] = std::max(e->layer_plane_bytes[1], align_up(pd.partial_bytes, 256));
+    }
+    const LayerLayout ll = layer_layout(c, layout_inputs(e));
+    e->layer_act_bytes = ll.bytes * c.num_layers;
+    TL_TRY(e->layer_act_mem.alloc(e->layer_act_bytes, "engine_create: hipMalloc(per-layer decode activations) failed"));
+    if (hipMemsetAsync(e->layer_act_mem.at(), 0, e->layer_act_bytes, e->stream) != hipSuccess)
+        return fail(TL_ERR_HIP, "engine_create: hipMalloc(per-layer decode activations) failed");
+    for (int l = 0; l < c.num_layers; ++l) e->layer_act.push_back(layer_act(e->layer_act_mem.at(), ll, l));
+    e->layer_act_rows = ll.rows;
+    e->layer_ws_bytes = ll[LayerLayout::PLANE0].off - ll[LayerLayout::ATTN_WS].off;  // (the piece, rounded up like every piece)
+    return TL_OK;
+}
+
+// RoPE table for every position a sequence can reach, and the slots' current rows
+static int create_rope_tables(tl_engine *e) {
+    const tl_engine_config &c = e->cfg;
+    const long max_pos = std::min<long>((long)c.max_pages_per_seq * c.page_size + 1, 1 << 20);
+    e->rope_positions = (int)max_pos;
+    const int half = c.head_dim / 2;
+    TL_TRY(e->rope_table_mem.alloc((size_t)max_pos * half * sizeof(float2), "engine_create: hipMalloc(rope table) failed"));
+    e->rope_table = e->rope_table_mem.at<float2>();
+    hipLaunchKernelGGL(rope_table_kernel, dim3(ceil_div(max_pos * half, 256)), dim3(256), 0, e->stream, e->rope_table,
+                       (int)max_pos, half, c.rope_theta);
+    if (hipGetLastError() != hipSuccess) return fail(TL_ERR_HIP, "engine_create: rope table kernel failed");
+    TL_TRY(e->rope_cur_mem.alloc((size_t)c.max_batch * half * sizeof(float2), "engine_create: hipMalloc(rope state) failed"));
+    e->rope_cur = e->rope_cur_mem.at<float2>();
+    if (hipMemsetAsync(e->rope_cur, 0, (size_t)c.max_batch * half * sizeof(float2), e->stream) != hipSuccess)
+        return fail(TL_ERR_HIP, "engine_create: hipMalloc(rope state) failed");
+    return TL_OK;
+}
+
+static int create_weight_copies(tl_engine *e) {
+    const tl_engine_config &c = e->cfg;
+    // decode-path weight copies in the tiled MFMA layout
+    {
+        auto add_tiled = [&](const tl_w4 &w) -> bool {
+            if (w.rows % 16 != 0 || w.cols % 128 != 0 || e->lin.tiled.count(w.weight_dev)) return true;
+            const char *failed = "engine_create: hipMalloc(tiled weights) failed";
+            e->tiled_mem.emplace_back();
+            if (tiled_w4_make(w, e->stream, e->tiled_mem.back(), e->lin.tiled[w.weight_dev], failed, failed) != TL_OK) return false;
+            e->tiled_bytes += (size_t)w.rows * w.cols / 2 + (size_t)w.rows * (w.cols / 128) * 4;
+            return true;
+        };
+        bool ok = true;
+        for (const auto &l : e->layers) {
+            ok = ok && add_tiled(l.wqkv) && add_tiled(l.wo);
+            if (l.wgu.weight_dev) ok = ok && add_tiled(l.wgu) && add_tiled(l.wdown);
+        }
+        ok = ok && add_tiled(e->head());
+        if (!ok) return fail(TL_ERR_HIP, "engine_create: hipMalloc(tiled weights) failed");
+    }
+    if (c.max_prefill_rows >= GEMM8_MIN_ROWS) {  // the caller asked for chunks the plain bf16 GEMM takes: expand the layer matrices once
+        auto add_bf16 = [&](const tl_w4 &w) -> bool {
+            if (!w.weight_dev || w.cols % 128 != 0 || e->lin.bf16w.count(w.weight_dev) || !gemm8_applicable(c.max_prefill_rows, w.rows, w.cols)) return true;
+            const size_t bytes = (size_t)w.rows * w.cols * 2;
+            DeviceBlock copy;
+            if (copy.alloc(bytes, "engine_create: hipMalloc(bf16 weights for the prefill GEMM) failed") != TL_OK) return false;
+            uint16_t *wb = copy.at<uint16_t>();
+            if (dequant_w4_to_bf16(w.weight_dev, (const uint16_t *)w.scales_dev, (const uint16_t *)w.biases_dev, wb, w.rows, w.cols, e->stream) != 0) return false;
+            e->bf16w_mem.push_back(std::move(copy));
+            e->lin.bf16w[w.weight_dev] = wb;
+            e->bf16w_bytes += bytes;
+            return true;
+        };
+        bool ok = true;
+        for (const auto &l : e->layers) {
+            ok = ok && add_bf16(l.wqkv) && add_bf16(l.wo);
+            if (l.wgu.weight_dev) ok = ok && add_bf16(l.wgu) && add_bf16(l.wdown);
+        }
+        if (!ok) return fail(TL_ERR_HIP, "engine_create: hipMalloc(bf16 weights for the prefill GEMM) failed");
+    }
+    return TL_OK;
+}
+
 extern "C" int tl_engine_create(const tl_engine_config *cfg, const tl_layer_weights *layers, const tl_w4 *embed,
                                 const void *final_norm_dev, const tl_w4 *lm_head, void *stream, tl_engine **out) {
     return tl_engine_create_kv(cfg, layers, embed, final_norm_dev, lm_head, stream, TL_KV_BF16, out);
@@ -1245,103 +1390,38 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
             return fail(TL_ERR_HIP, "engine_create: could not create the engine stream");
         e->owned_stream.s = e->stream;
     }
-    e->rows_cap = std::max(c.max_prefill_rows, c.max_batch);
+    e->rows_cap = prefill_rows(c);
 
-    // ---- arena layout
-    const size_t R = (size_t)e->rows_cap;
-    Carve carve;
-    const size_t o_bt = carve((size_t)c.max_batch * c.max_pages_per_seq * 4);
-    const size_t o_ctx = carve((size_t)c.max_batch * 4);
-    const size_t o_tok = carve((size_t)c.max_batch * 4);
-    const size_t o_live = carve((size_t)c.max_batch * 4);
-    const size_t o_prod = carve((size_t)c.max_batch * 4);
-    const size_t o_ring = carve((size_t)c.max_batch * e->ring_cap * 4);
-    const size_t o_sctx = carve(64);
-    const size_t o_ptok = carve(R * 4);
-    const size_t o_x = carve(R * c.hidden_size * 2);
-    e->arena_act_off = o_x;
-    const size_t o_h = carve(R * c.hidden_size * 2);
-    const size_t o_xn = carve((R + 15) / 16 * 16 * c.hidden_size * 2);  // weighted rows of a batched step lie in 16-row fragment blocks (qmm6.h)
-    const size_t o_tmp = carve(R * c.hidden_size * 2);
-    const size_t o_qkv = carve(R * qkv_dim * 2);
-    const size_t o_qt = carve(R * q_dim * 2);
-    const size_t o_at = carve(R * q_dim * 2);
-    const size_t o_attn = carve(R * q_dim * 2);
-    const size_t o_gu = carve(R * 2 * c.intermediate_size * 2);
-    const size_t o_act = carve(R * c.intermediate_size * 2);
-    const size_t o_log = carve((size_t)std::max(c.max_batch, 8) * c.vocab_size * 2);  // decode rows, or 8 verification rows
-    const size_t o_vid = carve(8 * 4);
-    const size_t o_tmax = carve((size_t)8 * (c.vocab_size / 16 + 1) * sizeof(f32x2));
-    // per-row partial sums of squares: QM3_SS per row from the skinny-matmul reduction / the embedding kernels, one per 16-row
-    // tile (hidden / 16) from the 1-4-row GEMVs
-    const size_t ss_per_row = (size_t)std::max(QM3_SS, c.hidden_size / 16 + 1);
-    const size_t o_ssx = carve((size_t)c.max_batch * ss_per_row * 4);
-    const size_t o_ssh = carve((size_t)c.max_batch * ss_per_row * 4);
-    // attention partials: decode (batch*Hq rows x 64 splits) or the L<=8 operator path during short prefills
-    // decode partials: at most 64 splits per row with many sequences, at most 256 split-rows per head with few (pick_decode_splits)
+    // ---- the arena (engine_layout.h): its attention partials first -- decode (batch*Hq rows x 64 splits) or the L<=8 operator path during
+    // short prefills; decode partials: at most 64 splits per row with many sequences, at most 256 split-rows per head with few (pick_decode_splits)
     const size_t ws_row = (size_t)c.head_dim + ATTN_WS_PAD;
     e->attn_ws_bytes = std::max((size_t)std::max(c.max_batch * 64, 4 * 256) * c.num_heads * ws_row * 4, (size_t)c.num_heads * 8 * 64 * ws_row * 4);
     for (int L = 1; L <= c.max_prefill_rows; ++L)  // the paged attention operator may split the context for any chunk length
         e->attn_ws_bytes = std::max(e->attn_ws_bytes, tl_paged_attention_workspace_bytes(c.num_heads, L, c.head_dim, c.page_size,
                                                                                          c.max_pages_per_seq, c.num_heads,
                                                                                          c.num_kv_heads, 0));
-    const size_t o_ws = carve(e->attn_ws_bytes);
-    e->arena_bytes = carve.off;
+    const ArenaLayout al = arena_layout(c, layout_inputs(e));
+    e->arena_bytes = al.bytes, e->arena_act_off = al.act_off;
 
     TL_TRY(e->arena.alloc(e->arena_bytes, "engine_create: hipMalloc(arena) failed"));
     // sampling parameters per slot (all zero: greedy): seeds first for their 8-byte alignment
     e->settings.init(settings_sizes(e));
     TL_TRY(settings_blocks(e, 1u << SB_SAMPLE));
-    e->layer_pool_elems = (size_t)c.num_pages * c.num_kv_heads * c.page_size * c.head_dim;
-    const size_t pool_bytes = e->layer_pool_elems * e->kv_elem_bytes() * c.num_layers;
-    TL_TRY(e->kv_mem[0].alloc(pool_bytes, "engine_create: hipMalloc(key pages) failed"));
-    TL_TRY(e->kv_mem[1].alloc(pool_bytes, "engine_create: hipMalloc(value pages) failed"));
-    e->kpool = e->kv_mem[0].at<uint16_t>(), e->vpool = e->kv_mem[1].at<uint16_t>();
-    e->kv_bytes = 2 * pool_bytes;
-    if (kv_format == TL_KV_FP8_E4M3) {
-        // one float32 scale per (page, kv head, slot) row; zero like the codes (a zero scale times a zero code is the zero the bf16 pool holds)
-        e->layer_scale_elems = (size_t)c.num_pages * c.num_kv_heads * c.page_size;
-        const size_t scale_bytes = e->layer_scale_elems * 4 * c.num_layers;
-        TL_TRY(e->kv_mem[2].alloc(scale_bytes, "engine_create: hipMalloc(key scales) failed"));
-        TL_TRY(e->kv_mem[3].alloc(scale_bytes, "engine_create: hipMalloc(value scales) failed"));
-        e->kscale_pool = e->kv_mem[2].at<float>(), e->vscale_pool = e->kv_mem[3].at<float>();
-        if (hipMemsetAsync(e->kscale_pool, 0, scale_bytes, e->stream) != hipSuccess ||
-            hipMemsetAsync(e->vscale_pool, 0, scale_bytes, e->stream) != hipSuccess)
-            return fail(TL_ERR_HIP, "engine_create: memset(KV scales) failed");
-        e->kv_bytes += 2 * scale_bytes;
-    }
-    // Masked (out-of-context) token slots are still loaded and multiplied by a zero weight in the decode kernel,
-    // so the pools must never hold NaN/Inf bit patterns: start from zeros (kernels only ever write finite values).
-    if (hipMemsetAsync(e->kpool, 0, pool_bytes, e->stream) != hipSuccess ||
-        hipMemsetAsync(e->vpool, 0, pool_bytes, e->stream) != hipSuccess)
-        return fail(TL_ERR_HIP, "engine_create: memset(KV pools) failed");
+    TL_TRY(create_kv_pools(e));
 
-    char *A = e->arena.at();
-    e->block_table = (int32_t *)(A + o_bt);
-    e->context_lens = (int32_t *)(A + o_ctx);
-    e->tokens = (int32_t *)(A + o_tok);
-    e->live = (int32_t *)(A + o_live);
-    e->produced = (int32_t *)(A + o_prod);
-    e->ring = (int32_t *)(A + o_ring);
-    e->scratch_ctx = (int32_t *)(A + o_sctx);
-    e->prefill_tokens = (int32_t *)(A + o_ptok);
-    e->x = (uint16_t *)(A + o_x);
-    e->h = (uint16_t *)(A + o_h);
-    e->xn = (uint16_t *)(A + o_xn);
-    e->lin.tmp = (uint16_t *)(A + o_tmp);
-    e->qkv = (uint16_t *)(A + o_qkv);
-    e->q_t = (uint16_t *)(A + o_qt);
-    e->attn_t = (uint16_t *)(A + o_at);
-    e->attn = (uint16_t *)(A + o_attn);
-    e->lin.gu = (uint16_t *)(A + o_gu);
-    e->act = (uint16_t *)(A + o_act);
-    e->logits = (uint16_t *)(A + o_log);
-    e->attn_ws = (float *)(A + o_ws);
-    e->verify_ids = (int32_t *)(A + o_vid);
-    e->lm_tile_max = (f32x2 *)(A + o_tmax);
-    e->ss_x = (float *)(A + o_ssx);
-    e->ss_h = (float *)(A + o_ssh);
-    e->lin.stream = e->stream, e->lin.rms_norm_eps = c.rms_norm_eps, e->lin.xn = e->xn;
+    {
+        using A = ArenaLayout;
+        char *m = e->arena.at();
+        e->block_table = piece_at<int32_t>(m, al[A::BLOCK_TABLE]), e->context_lens = piece_at<int32_t>(m, al[A::CONTEXT_LENS]);
+        e->tokens = piece_at<int32_t>(m, al[A::TOKENS]), e->live = piece_at<int32_t>(m, al[A::LIVE]), e->produced = piece_at<int32_t>(m, al[A::PRODUCED]);
+        e->ring = piece_at<int32_t>(m, al[A::RING]), e->scratch_ctx = piece_at<int32_t>(m, al[A::SCRATCH_CTX]);
+        e->prefill_tokens = piece_at<int32_t>(m, al[A::PREFILL_TOKENS]);
+        e->shared = arena_act(m, al);
+        e->lin.xn = e->shared.xn, e->lin.tmp = piece_at<uint16_t>(m, al[A::TMP]), e->lin.gu = piece_at<uint16_t>(m, al[A::GU]);
+        e->q_t = piece_at<uint16_t>(m, al[A::Q_T]), e->attn_t = piece_at<uint16_t>(m, al[A::ATTN_T]), e->logits = piece_at<uint16_t>(m, al[A::LOGITS]);
+        e->verify_ids = piece_at<int32_t>(m, al[A::VERIFY_IDS]), e->lm_tile_max = piece_at<f32x2>(m, al[A::LM_TILE_MAX]);
+    }
+    e->lin.stream = e->stream, e->lin.rms_norm_eps = c.rms_norm_eps;
     e->lin.read_env();
     read_attention_knobs(e);
     // Decode steps replay as AQL packets on the engine's own HSA queue (aql.h) unless TL_AQL=0: the same captured step, without the
@@ -1371,135 +1451,25 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
             // per-layer decode activations (1-4 rows: the fused-GEMV step; 5-64 rows since round 5: the batched-matmul step): every hand-over
             // address of a step is written once per step.  The attention partials hold 16 windows per row (at most 1,024 row-windows): a plan
             // beyond that keeps the shared buffers and the graph route.
-            {
-                const int rows = std::min(c.max_batch, 64);
-                const size_t ssr = (size_t)std::max(QM3_SS, c.hidden_size / 16 + 1);
-                // (weighted rows lie in 16-row fragment blocks, qmm6.h: a partly filled last block spans all 16 row slots -- sized like the shared xn;
-                // with `rows` itself a batch of 17-24 on a 24-slot engine wrote its block past xn into xw and past xw into qkv: dead bytes at that
-                // moment by the order of the launches, but a second write per step to addresses the replay route reads without cache maintenance)
-                const size_t b_xf = align_up((size_t)((rows + 15) / 16 * 16) * c.hidden_size * 2, 256);
-                const size_t b_x = align_up((size_t)rows * c.hidden_size * 2, 256), b_qkv = align_up((size_t)rows * qkv_dim * 2, 256),
-                             b_attn = align_up((size_t)rows * q_dim * 2, 256), b_act = align_up((size_t)rows * c.intermediate_size * 2, 256),
-                             b_ss = align_up((size_t)rows * ssr * 4, 256),
-                             b_ws = align_up((size_t)std::min(rows * 64, std::max(4 * 64, std::min(rows * 16, 1024))) * c.num_heads * ws_row * 4, 256);
-                // slice planes of the sliced matmuls a batched step can take (wo, w_down), the largest over 5 .. rows rows
-                size_t b_pl[2] = {0, 0};
-                for (int M = std::min(5, e->lin.qmm3_min_rows); M <= rows; ++M) {
-                    const Qmm3Plan pw = qmm3_plan(M, q_dim, c.hidden_size, -1), pd = qmm3_plan(M, c.intermediate_size, c.hidden_size, -1);
-                    if (pw.ok) b_pl[0] = std::max(b_pl[0], align_up(pw.partial_bytes, 256));
-                    if (pd.ok) b_pl[1] = std::max(b_pl[1], align_up(pd.partial_bytes, 256));
-                }
-                const size_t per_layer = 2 * b_x + 2 * b_xf + b_qkv + b_attn + b_act + 2 * b_ss + b_ws + b_pl[0] + b_pl[1];
-                TL_TRY(e->layer_act_mem.alloc(per_layer * c.num_layers, "engine_create: hipMalloc(per-layer decode activations) failed"));
-                if (hipMemsetAsync(e->layer_act_mem.at(), 0, per_layer * c.num_layers, e->stream) != hipSuccess)
-                    return fail(TL_ERR_HIP, "engine_create: hipMalloc(per-layer decode activations) failed");
-                e->layer_act.resize(c.num_layers);
-                for (int l = 0; l < c.num_layers; ++l) {
-                    char *m = e->layer_act_mem.at((size_t)l * per_layer);
-                    tl_engine::LayerAct &a = e->layer_act[l];
-                    a.x_out = (uint16_t *)m, m += b_x;
-                    a.h = (uint16_t *)m, m += b_x;
-                    a.xn = (uint16_t *)m, m += b_xf;
-                    a.xw = (uint16_t *)m, m += b_xf;
-                    a.qkv = (uint16_t *)m, m += b_qkv;
-                    a.attn = (uint16_t *)m, m += b_attn;
-                    a.act = (uint16_t *)m, m += b_act;
-                    a.ss_x_out = (float *)m, m += b_ss;
-                    a.ss_h = (float *)m, m += b_ss;
-                    a.attn_ws = (float *)m, m += b_ws;
-                    a.planes[0] = (float *)m, m += b_pl[0];
-                    a.planes[1] = (float *)m;
-                }
-                e->layer_plane_bytes[0] = b_pl[0], e->layer_plane_bytes[1] = b_pl[1];
-                e->layer_act_bytes = per_layer * c.num_layers;
-                e->layer_act_rows = rows;
-                e->layer_ws_bytes = b_ws;
-            }
+            TL_TRY(create_layer_acts(e));
         }
     }
 
     // state words: zero everything up to the activations, then the block table to -1
-    if (hipMemsetAsync(e->arena.at(), 0, o_x, e->stream) != hipSuccess) return fail(TL_ERR_HIP, "engine_create: memset failed");
+    if (hipMemsetAsync(e->arena.at(), 0, al.act_off, e->stream) != hipSuccess) return fail(TL_ERR_HIP, "engine_create: memset failed");
     const int bt_n = c.max_batch * c.max_pages_per_seq;
     hipLaunchKernelGGL(fill_i32_kernel, dim3(ceil_div(bt_n, 256)), dim3(256), 0, e->stream, e->block_table, -1, bt_n);
     if (hipGetLastError() != hipSuccess) return fail(TL_ERR_HIP, "engine_create: block-table init failed");
 
-    // RoPE table for every position a sequence can reach
-    {
-        const long max_pos = std::min<long>((long)c.max_pages_per_seq * c.page_size + 1, 1 << 20);
-        e->rope_positions = (int)max_pos;
-        const int half = c.head_dim / 2;
-        TL_TRY(e->rope_table_mem.alloc((size_t)max_pos * half * sizeof(float2), "engine_create: hipMalloc(rope table) failed"));
-        e->rope_table = e->rope_table_mem.at<float2>();
-        hipLaunchKernelGGL(rope_table_kernel, dim3(ceil_div(max_pos * half, 256)), dim3(256), 0, e->stream, e->rope_table,
-                           (int)max_pos, half, c.rope_theta);
-        if (hipGetLastError() != hipSuccess) return fail(TL_ERR_HIP, "engine_create: rope table kernel failed");
-        TL_TRY(e->rope_cur_mem.alloc((size_t)c.max_batch * half * sizeof(float2), "engine_create: hipMalloc(rope state) failed"));
-        e->rope_cur = e->rope_cur_mem.at<float2>();
-        if (hipMemsetAsync(e->rope_cur, 0, (size_t)c.max_batch * half * sizeof(float2), e->stream) != hipSuccess)
-            return fail(TL_ERR_HIP, "engine_create: hipMalloc(rope state) failed");
-    }
+    TL_TRY(create_rope_tables(e));
 
-    // decode-path weight copies in the tiled MFMA layout
-    {
-        auto add_tiled = [&](const tl_w4 &w) -> bool {
-            if (w.rows % 16 != 0 || w.cols % 128 != 0 || e->lin.tiled.count(w.weight_dev)) return true;
-            const char *failed = "engine_create: hipMalloc(tiled weights) failed";
-            e->tiled_mem.emplace_back();
-            if (tiled_w4_make(w, e->stream, e->tiled_mem.back(), e->lin.tiled[w.weight_dev], failed, failed) != TL_OK) return false;
-            e->tiled_bytes += (size_t)w.rows * w.cols / 2 + (size_t)w.rows * (w.cols / 128) * 4;
-            return true;
-        };
-        bool ok = true;
-        for (const auto &l : e->layers) {
-            ok = ok && add_tiled(l.wqkv) && add_tiled(l.wo);
-            if (l.wgu.weight_dev) ok = ok && add_tiled(l.wgu) && add_tiled(l.wdown);
-        }
-        ok = ok && add_tiled(e->head());
-        if (!ok) return fail(TL_ERR_HIP, "engine_create: hipMalloc(tiled weights) failed");
-    }
-    if (c.max_prefill_rows >= GEMM8_MIN_ROWS) {  // the caller asked for chunks the plain bf16 GEMM takes: expand the layer matrices once
-        auto add_bf16 = [&](const tl_w4 &w) -> bool {
-            if (!w.weight_dev || w.cols % 128 != 0 || e->lin.bf16w.count(w.weight_dev) || !gemm8_applicable(c.max_prefill_rows, w.rows, w.cols)) return true;
-            const size_t bytes = (size_t)w.rows * w.cols * 2;
-            DeviceBlock copy;
-            if (copy.alloc(bytes, "engine_create: hipMalloc(bf16 weights for the prefill GEMM) failed") != TL_OK) return false;
-            uint16_t *wb = copy.at<uint16_t>();
-            if (dequant_w4_to_bf16(w.weight_dev, (const uint16_t *)w.scales_dev, (const uint16_t *)w.biases_dev, wb, w.rows, w.cols, e->stream) != 0) return false;
-            e->bf16w_mem.push_back(std::move(copy));
-            e->lin.bf16w[w.weight_dev] = wb;
-            e->bf16w_bytes += bytes;
-            return true;
-        };
-        bool ok = true;
-        for (const auto &l : e->layers) {
-            ok = ok && add_bf16(l.wqkv) && add_bf16(l.wo);
-            if (l.wgu.weight_dev) ok = ok && add_bf16(l.wgu) && add_bf16(l.wdown);
-        }
-        if (!ok) return fail(TL_ERR_HIP, "engine_create: hipMalloc(bf16 weights for the prefill GEMM) failed");
-    }
+    TL_TRY(create_weight_copies(e));
 
     {
         // Workspace of every matmul the engine can launch, allocated once: fp32 slice partials of the skinny matmul
         // (qmm3_min_rows .. 64 decode rows, any of the five matrices) and split-K partials of the prefill GEMM (9 ..
         // rows_cap rows).  Graphs captured later hold this address, so it is never reallocated.
-        size_t need = 0;
-        const tl_layer_weights *dense = &e->layers[0];  // the first layer that has a dense MLP sizes the MLP workspaces
-        for (const auto &l : e->layers)
-            if (l.wgu.weight_dev) {
-                dense = &l;
-                break;
-            }
-        const tl_w4 *mats[5] = {&e->layers[0].wqkv, &e->layers[0].wo, &dense->wgu, &dense->wdown, &e->head()};
-        for (const tl_w4 *w : mats) {
-            if (!w->weight_dev) continue;
-            for (int M = 1; M <= std::min(64, e->rows_cap); ++M) {
-                const Qmm3Plan p3 = qmm3_plan(M, w->cols, w->rows);
-                if (p3.ok) need = std::max(need, p3.partial_bytes);
-            }
-            for (int M = 9; M <= e->rows_cap; ++M)
-                need = std::max(need, tl_quantized_matmul_workspace_bytes(M, w->cols, w->rows, TL_BF16, 1, 1));
-        }
+        const size_t need = matmul_ws_need(e, 1, std::min(64, e->rows_cap), 9, e->rows_cap, false);
         if (need > 0) {
             TL_TRY(e->splitk_mem.alloc(need, "engine_create: hipMalloc(matmul workspace) failed"));
             e->lin.splitk_ws = e->splitk_mem.at<void>(), e->lin.splitk_ws_bytes = need;
@@ -1536,22 +1506,18 @@ extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_wei
     const int k = std::max(e->moe_k_max, w->experts_per_token), E = std::max(e->moe_e_max, w->num_experts),
               I = std::max(e->moe_i_max, w->intermediate_size);
     if (k != e->moe_k_max || E != e->moe_e_max || I != e->moe_i_max) {  // (re)size the workspace: nothing captured holds it yet
-        const size_t R = (size_t)e->rows_cap;
-        Carve carve;
-        const size_t o_log = carve(R * E * 2), o_ids = carve(R * k * 4), o_sc = carve(R * k * 2), o_g = carve(R * k * I * 2),
-                     o_u = carve(R * k * I * 2), o_a = carve(R * k * I * 2), o_y = carve(R * k * c.hidden_size * 2);
+        LayoutInputs in = layout_inputs(e);
+        in.moe_k = k, in.moe_e = E, in.moe_i = I;
+        const MoeLayout ml = moe_layout(c, in);
         TL_HIP(hipStreamSynchronize(e->stream));
         // (the text TL_HIP gave the hipMalloc that stood here)
-        TL_TRY(e->moe_ws.alloc(carve.off, "hipMalloc((void **)&e->moe_ws, carve.off): " + std::string(hipGetErrorString(hipErrorOutOfMemory))));
-        e->moe_ws_bytes = carve.off;
-        char *A = e->moe_ws.at();
-        e->moe_logits = (uint16_t *)(A + o_log);
-        e->moe_ids = (int32_t *)(A + o_ids);
-        e->moe_scores = (uint16_t *)(A + o_sc);
-        e->moe_gate = (uint16_t *)(A + o_g);
-        e->moe_up = (uint16_t *)(A + o_u);
-        e->moe_act = (uint16_t *)(A + o_a);
-        e->moe_y = (uint16_t *)(A + o_y);
+        TL_TRY(e->moe_ws.alloc(ml.bytes, "hipMalloc((void **)&e->moe_ws, carve.off): " + std::string(hipGetErrorString(hipErrorOutOfMemory))));
+        e->moe_ws_bytes = ml.bytes;
+        char *m = e->moe_ws.at();
+        e->moe_logits = piece_at<uint16_t>(m, ml[MoeLayout::LOGITS]), e->moe_ids = piece_at<int32_t>(m, ml[MoeLayout::IDS]);
+        e->moe_scores = piece_at<uint16_t>(m, ml[MoeLayout::SCORES]), e->moe_gate = piece_at<uint16_t>(m, ml[MoeLayout::GATE]);
+        e->moe_up = piece_at<uint16_t>(m, ml[MoeLayout::UP]), e->moe_act = piece_at<uint16_t>(m, ml[MoeLayout::ACT]);
+        e->moe_y = piece_at<uint16_t>(m, ml[MoeLayout::Y]);
         e->moe_k_max = k, e->moe_e_max = E, e->moe_i_max = I;
         e->stats.workspace_bytes = e->arena_bytes + e->tiled_bytes + e->moe_ws_bytes;
     }
@@ -2693,10 +2659,10 @@ static int engine_paged_attention(tl_engine *e, int l, const uint16_t *q_t, cons
     const int D = c.head_dim, Hq = c.num_heads, Hkv = c.num_kv_heads;
     if (e->kv_format == TL_KV_FP8_E4M3)
         return tl_paged_attention_fp8(q_t, e->layer_k(l), e->layer_ks(l), e->layer_v(l), e->layer_vs(l), block_row, ctx_dev, attn_t, Hq, n, D,
-                                      c.num_pages, c.page_size, c.max_pages_per_seq, Hq, Hkv, 1.0f / sqrtf((float)D), 1, ctx_hint, e->attn_ws,
+                                      c.num_pages, c.page_size, c.max_pages_per_seq, Hq, Hkv, 1.0f / sqrtf((float)D), 1, ctx_hint, e->shared.attn_ws,
                                       e->attn_ws_bytes, e->stream);
     return tl_paged_attention(q_t, e->layer_k(l), e->layer_v(l), block_row, ctx_dev, attn_t, Hq, n, D, c.num_pages, c.page_size,
-                              c.max_pages_per_seq, Hq, Hkv, 1.0f / sqrtf((float)D), 1, ctx_hint, TL_BF16, e->attn_ws, e->attn_ws_bytes, e->stream);
+                              c.max_pages_per_seq, Hq, Hkv, 1.0f / sqrtf((float)D), 1, ctx_hint, TL_BF16, e->shared.attn_ws, e->attn_ws_bytes, e->stream);
 }
 static void launch_qkv_post(tl_engine *e, int l, QkvPostArgs &q, int n) {
     q.key_scales = e->layer_ks(l);
@@ -2716,10 +2682,6 @@ struct PrefillSeq {
     int slot, start, row0, len;
 };
 
-// The multi-token pass over the `total` rows of the chunks in `seqs`, side by side: their pages reserved (the caller has checked
-// whatever could fail part way) and their tokens embedded, then every layer -- the projections once over all rows, RoPE / KV append, the
-// paged FlashAttention and the head transpose per sequence (each has its own block-table row, start position and causal mask) -- and
-// the slots' context lengths advanced.  The last layer's rows stay in x.  `packed` names the caller in the errors.
 // the lm_head over `rows` rows of the residual stream through the GEMV with the final RMSNorm fused (a prefill's last rows, verification)
 static int lm_head_rows(tl_engine *e, const uint16_t *x, int rows) {
     Proj p = proj(e->head(), x, e->logits, rows);
@@ -2727,8 +2689,13 @@ static int lm_head_rows(tl_engine *e, const uint16_t *x, int rows) {
     return engine_qmv(e->lin, p);
 }
 
+// The multi-token pass over the `total` rows of the chunks in `seqs`, side by side: their pages reserved (the caller has checked
+// whatever could fail part way) and their tokens embedded, then every layer -- the projections once over all rows, RoPE / KV append, the
+// paged FlashAttention and the head transpose per sequence (each has its own block-table row, start position and causal mask) -- and
+// the slots' context lengths advanced.  The last layer's rows stay in x.  `packed` names the caller in the errors.
 static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const int32_t *tokens, int total, bool packed) {
     const tl_engine_config &c = e->cfg;
+    const Act &b = e->shared;  // every layer hands over in the shared buffers
     SlotEdits ed;
     Pokes pk;
     for (int i = 0; i < n_seqs; ++i) {
@@ -2746,7 +2713,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
     }
 
     const int D = c.head_dim, Hq = c.num_heads, Hkv = c.num_kv_heads;
-    TL_TRY(tl_quantized_embedding(e->prefill_tokens, 0, e->embed.scales_dev, e->embed.biases_dev, e->embed.weight_dev, e->x,
+    TL_TRY(tl_quantized_embedding(e->prefill_tokens, 0, e->embed.scales_dev, e->embed.biases_dev, e->embed.weight_dev, b.x_out,
                                   total, c.hidden_size, c.vocab_size, 128, 4, TL_BF16, e->stream));
     for (int i = 0; i < n_seqs; ++i)
         TL_REQUIRE(tl_paged_attention_workspace_bytes(Hq, seqs[i].len, D, c.page_size, c.max_pages_per_seq, Hq, Hkv, seqs[i].start + seqs[i].len) <=
@@ -2756,7 +2723,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
     int lora_tiles = 0;
     std::vector<LoraTile> lora_list;
     {
-        int row0[16], len[16], ad[16];
+        int row0[PACKED_MAX_SEQS], len[PACKED_MAX_SEQS], ad[PACKED_MAX_SEQS];
         bool any = false;
         for (int i = 0; i < n_seqs; ++i) {
             row0[i] = seqs[i].row0, len[i] = seqs[i].len, ad[i] = e->settings.slots[seqs[i].slot].lora;
@@ -2779,18 +2746,18 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
     bool x_normed = false;  // the previous layer's w_down reduction left this layer's normalised rows in xn (engine_gemm)
     for (int l = 0; l < c.num_layers; ++l) {
         const tl_layer_weights &w = e->layers[l];
-        if (!x_normed) TL_TRY(tl_rms_norm(e->x, w.input_norm_dev, e->xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
+        if (!x_normed) TL_TRY(tl_rms_norm(b.x_out, w.input_norm_dev, b.xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
         x_normed = false;
-        TL_TRY(engine_gemm(e->lin, proj(w.wqkv, e->xn, e->qkv, total)));
+        TL_TRY(engine_gemm(e->lin, proj(w.wqkv, b.xn, b.qkv, total)));
         if (lora_on(l, tl_engine::LORA_QKV))
-            TL_TRY(lora_group(e, l, tl_engine::LORA_QKV, e->lora_tiles_prefill, lora_tiles, total, e->xn, nullptr, TL_LORA_ADD, nullptr, e->qkv));
+            TL_TRY(lora_group(e, l, tl_engine::LORA_QKV, e->lora_tiles_prefill, lora_tiles, total, b.xn, nullptr, TL_LORA_ADD, nullptr, b.qkv));
         for (int i = 0; i < n_seqs; ++i) {
             const int n = seqs[i].len, start = seqs[i].start;
             const int32_t *block_row = e->block_table + (size_t)seqs[i].slot * c.max_pages_per_seq;
             uint16_t *q_t = e->q_t + (size_t)seqs[i].row0 * Hq * D;  // this sequence's [Hq][n][D] block
             uint16_t *attn_t = e->attn_t + (size_t)seqs[i].row0 * Hq * D;
             QkvPostArgs q{};
-            q.qkv = e->qkv + (size_t)seqs[i].row0 * (Hq + 2 * Hkv) * D;
+            q.qkv = b.qkv + (size_t)seqs[i].row0 * (Hq + 2 * Hkv) * D;
             q.q_norm_w = (const uint16_t *)w.q_norm_dev;
             q.k_norm_w = (const uint16_t *)w.k_norm_dev;
             q.q_t = q_t;
@@ -2810,34 +2777,34 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
             TL_TRY(engine_paged_attention(e, l, q_t, block_row, e->scratch_ctx + i, attn_t, n, start + n));
             const long items = (long)Hq * n * (D / 8);
             hipLaunchKernelGGL(heads_to_rows_kernel, dim3(ceil_div(items, 256)), dim3(256), 0, e->stream, attn_t,
-                               e->attn + (size_t)seqs[i].row0 * Hq * D, Hq, n, D);
+                               b.attn + (size_t)seqs[i].row0 * Hq * D, Hq, n, D);
         }
         bool h_normed = false;
-        Proj po = proj(w.wo, e->attn, e->h, total);
-        po.epi = EPI_RESIDUAL, po.residual = e->x, po.norm_out = w.post_norm_dev, po.out_w = e->xn;
+        Proj po = proj(w.wo, b.attn, b.h, total);
+        po.epi = EPI_RESIDUAL, po.residual = b.x_out, po.norm_out = w.post_norm_dev, po.out_w = b.xn;
         if (lora_on(l, tl_engine::LORA_O)) {  // x + delta first: the projection's residual epilogue then adds its product to that
-            TL_TRY(lora_group(e, l, tl_engine::LORA_O, e->lora_tiles_prefill, lora_tiles, total, e->attn, nullptr, TL_LORA_RESIDUAL_PRE, e->x, e->lora_tmp));
+            TL_TRY(lora_group(e, l, tl_engine::LORA_O, e->lora_tiles_prefill, lora_tiles, total, b.attn, nullptr, TL_LORA_RESIDUAL_PRE, b.x_out, e->lora_tmp));
             po.residual = e->lora_tmp;
         }
         TL_TRY(engine_gemm(e->lin, po, &h_normed));
-        if (!h_normed) TL_TRY(tl_rms_norm(e->h, w.post_norm_dev, e->xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
+        if (!h_normed) TL_TRY(tl_rms_norm(b.h, w.post_norm_dev, b.xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
         if (e->is_moe(l)) {
-            TL_TRY(engine_moe_mlp(e, l, e->xn, e->h, e->x, total, nullptr));
+            TL_TRY(engine_moe_mlp(e, l, b.xn, b.h, b.x_out, total, nullptr));
         } else {
             TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
-            Proj pg = proj(w.wgu, e->xn, e->act, total);
+            Proj pg = proj(w.wgu, b.xn, b.act, total);
             pg.epi = EPI_SWIGLU;
             if (lora_on(l, tl_engine::LORA_GU)) {  // the unfused route: complete gate|up rows, then the expand launch's SwiGLU over base + delta
                 pg.out = e->lin.gu, pg.epi = EPI_STORE;
                 TL_TRY(engine_gemm(e->lin, pg));
-                TL_TRY(lora_group(e, l, tl_engine::LORA_GU, e->lora_tiles_prefill, lora_tiles, total, e->xn, nullptr, TL_LORA_SWIGLU, e->lin.gu, e->act));
+                TL_TRY(lora_group(e, l, tl_engine::LORA_GU, e->lora_tiles_prefill, lora_tiles, total, b.xn, nullptr, TL_LORA_SWIGLU, e->lin.gu, b.act));
             } else {
                 TL_TRY(engine_gemm(e->lin, pg));
             }
-            Proj pd = proj(w.wdown, e->act, e->x, total);
-            pd.epi = EPI_RESIDUAL, pd.residual = e->h, pd.norm_out = l + 1 < c.num_layers ? e->layers[l + 1].input_norm_dev : nullptr, pd.out_w = e->xn;
+            Proj pd = proj(w.wdown, b.act, b.x_out, total);
+            pd.epi = EPI_RESIDUAL, pd.residual = b.h, pd.norm_out = l + 1 < c.num_layers ? e->layers[l + 1].input_norm_dev : nullptr, pd.out_w = b.xn;
             if (lora_on(l, tl_engine::LORA_DOWN)) {
-                TL_TRY(lora_group(e, l, tl_engine::LORA_DOWN, e->lora_tiles_prefill, lora_tiles, total, e->act, nullptr, TL_LORA_RESIDUAL_PRE, e->h, e->lora_tmp));
+                TL_TRY(lora_group(e, l, tl_engine::LORA_DOWN, e->lora_tiles_prefill, lora_tiles, total, b.act, nullptr, TL_LORA_RESIDUAL_PRE, b.h, e->lora_tmp));
                 pd.residual = e->lora_tmp;
             }
             TL_TRY(engine_gemm(e->lin, pd, &x_normed));
@@ -2859,7 +2826,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
 // context length), after which the slot has produced one id.  Its embedding row goes to scratch: the prefill activations in x must stay
 // intact; decode re-embeds from tokens
 static int prefill_first_token(tl_engine *e, int slot, int row, const char *what) {
-    launch_logit_chain(e, e->logits + (size_t)row * e->cfg.vocab_size, row, 1, slot, 0, e->h, nullptr, 0, nullptr, nullptr, step_features(e, slot, 1), nullptr);
+    launch_logit_chain(e, e->logits + (size_t)row * e->cfg.vocab_size, row, 1, slot, 0, e->shared.h, nullptr, 0, nullptr, nullptr, step_features(e, slot, 1), nullptr);
     TL_CHECK_LAUNCH(what);
     e->table.slots[slot].produced += 1;
     e->settings.pending_produced(slot);
@@ -2881,24 +2848,24 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
     if (logits_mode == 3) {
         // the final RMSNorm over the chunk's rows, then the lm_head through the W4 GEMM a block of rows at a time into the scoring
         // scratch, each block followed by the logprob routine in gather mode
-        TL_TRY(tl_rms_norm(e->x, e->final_norm, e->xn, n, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
+        TL_TRY(tl_rms_norm(e->shared.x_out, e->final_norm, e->shared.xn, n, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
         for (int r0 = 0; r0 < n; r0 += SCORE_BLOCK_ROWS) {
             const int rows = std::min(SCORE_BLOCK_ROWS, n - r0);
-            TL_TRY(engine_gemm(e->lin, proj(e->head(), e->xn + (size_t)r0 * c.hidden_size, e->score_logits, rows)));
+            TL_TRY(engine_gemm(e->lin, proj(e->head(), e->shared.xn + (size_t)r0 * c.hidden_size, e->score_logits, rows)));
             const LogprobRowsArgs a{e->score_logits, c.vocab_size, 0, e->score_ids + r0, e->score_lp + r0, nullptr, nullptr, e->score_argmax + r0};
             hipLaunchKernelGGL(logprob_rows_kernel, dim3(rows), dim3(1024), 0, e->stream, a);
             TL_CHECK_LAUNCH("engine score logprobs");
         }
     }
     if (logits_mode == 2) {
-        TL_TRY(lm_head_rows(e, e->x, n));
+        TL_TRY(lm_head_rows(e, e->shared.x_out, n));
         e->logits_rows = n, e->logits_slot = slot;
         hipLaunchKernelGGL(argmax_rows_kernel, dim3(n), dim3(1024), 0, e->stream, e->logits, c.vocab_size, e->verify_ids);
         TL_CHECK_LAUNCH("engine verify argmax");
     }
     if (logits_mode == 1) {
         // logits_to_keep = 1 (reference qwen3_week3.py:331-336): last row only
-        const uint16_t *last = e->x + (size_t)(n - 1) * c.hidden_size;
+        const uint16_t *last = e->shared.x_out + (size_t)(n - 1) * c.hidden_size;
         TL_TRY(lm_head_rows(e, last, 1));
         e->logits_rows = 1, e->logits_slot = slot;
         TL_TRY(prefill_first_token(e, slot, 0, "engine prefill argmax"));
@@ -2906,41 +2873,57 @@ static int prefill_impl(tl_engine *e, int slot, const int32_t *tokens, int n, in
     return TL_OK;
 }
 
-// The checks of a packed pass, all before anything is reserved, and the pass's sequences: `ends` (may be NULL: none) marks the chunks
-// that want a logits row.  `what` names the caller in the errors.
-static int packed_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, const int *ends, const char *what,
-                       std::vector<PrefillSeq> &seqs) {
+// What the passes over several sequences' chunks check alike, all before anything is reserved or allocated, and the pass's sequences with
+// the sum of their rows.  Per sequence: the slot feeds, the caller's own refusal (`per_seq(i)`), no slot twice, the pages its chunk needs
+// -- with `commit` one more where a rewind into a page the chunk filled copies it (SlotTable::rewind, when the prefix index has taken
+// it).  Then the caller's limits on the sum (`limits(total)`), the page pool and the token range.  `w` starts every message.
+template <class PerSeq, class Limits>
+static int pass_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, bool commit, const std::string &w, PerSeq per_seq,
+                     Limits limits, std::vector<PrefillSeq> &seqs, int *total) {
     const tl_engine_config &c = e->cfg;
-    const std::string w = std::string(what) + ": ";
-    TL_REQUIRE(n_seqs >= 1 && n_seqs <= 16, w + "between 1 and 16 sequences per call");
-    TL_REQUIRE(c.head_dim == 128, w + "head_dim 128 (bf16 FlashAttention)");
-    int total = 0;
+    std::vector<PrefillSeq> list(n_seqs);
+    int rows = 0;
     size_t extra_pages = 0;
     for (int i = 0; i < n_seqs; ++i) {
         TL_TRY(slot_check_feeds(e, slots[i]));
-        TL_REQUIRE(lens[i] > 0, w + "every sequence needs at least one token");
+        TL_TRY(per_seq(i));
         for (int j = 0; j < i; ++j) TL_REQUIRE(slots[j] != slots[i], w + "a slot appears twice");
         const Slot &s = e->table.slots[slots[i]];
         const int need = (s.ctx + lens[i] + c.page_size - 1) / c.page_size;
         TL_REQUIRE(need <= c.max_pages_per_seq, "engine: sequence exceeds max_pages_per_seq * page_size tokens");
         if (need > (int)s.pages.size()) extra_pages += (size_t)need - s.pages.size();
-        total += lens[i];
-    }
-    TL_REQUIRE(total <= c.max_prefill_rows, w + "the chunks together exceed max_prefill_rows");
-    if (ends) {
-        int wanted = 0;
-        for (int i = 0; i < n_seqs; ++i) wanted += ends[i] ? 1 : 0;
-        TL_REQUIRE(wanted <= std::max(c.max_batch, 8), w + "more prompts end in this pass than the logits buffer has rows (max(max_batch, 8))");
-    }
-    TL_REQUIRE(e->table.pool.can_take(extra_pages), "engine: KV page pool exhausted");  // checked before anything is mutated
-    for (int i = 0; i < total; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < c.vocab_size, w + "token id out of range");
-    seqs.resize(n_seqs);
-    int rows = 0;
-    for (int i = 0; i < n_seqs; ++i) {
-        seqs[i] = {slots[i], e->table.slots[slots[i]].ctx, rows, lens[i]};
+        if (commit && lens[i] > 1 && e->table.pool.enabled && (s.ctx + lens[i]) / c.page_size > s.ctx / c.page_size) extra_pages += 1;
+        list[i] = {slots[i], s.ctx, rows, lens[i]};
         rows += lens[i];
     }
+    TL_TRY(limits(rows));
+    TL_REQUIRE(e->table.pool.can_take(extra_pages), "engine: KV page pool exhausted");  // checked before anything is mutated
+    for (int i = 0; i < rows; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < c.vocab_size, w + "token id out of range");
+    seqs = std::move(list);
+    *total = rows;
     return TL_OK;
+}
+
+// The checks of a packed pass and the pass's sequences: `ends` (may be NULL: none) marks the chunks that want a logits row.  `what` names
+// the caller in the errors.
+static int packed_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, const int *ends, const char *what,
+                       std::vector<PrefillSeq> &seqs, int *total) {
+    const tl_engine_config &c = e->cfg;
+    const std::string w = std::string(what) + ": ";
+    TL_REQUIRE(n_seqs >= 1 && n_seqs <= PACKED_MAX_SEQS, w + "between 1 and 16 sequences per call");
+    TL_REQUIRE(c.head_dim == 128, w + "head_dim 128 (bf16 FlashAttention)");
+    const auto per_seq = [&](int i) {
+        TL_REQUIRE(lens[i] > 0, w + "every sequence needs at least one token");
+        return (int)TL_OK;
+    };
+    const auto limits = [&](int rows) {
+        TL_REQUIRE(rows <= c.max_prefill_rows, w + "the chunks together exceed max_prefill_rows");
+        int wanted = 0;
+        for (int i = 0; ends && i < n_seqs; ++i) wanted += ends[i] ? 1 : 0;
+        TL_REQUIRE(wanted <= logits_rows(c.max_batch), w + "more prompts end in this pass than the logits buffer has rows (max(max_batch, 8))");
+        return (int)TL_OK;
+    };
+    return pass_seqs(e, n_seqs, slots, tokens, lens, false, w, per_seq, limits, seqs, total);
 }
 
 // Several sequences' chunks in ONE prefill pass: the projections (97 % of the prefill FLOPs) run once over the concatenated rows -- a
@@ -2949,20 +2932,19 @@ static int prefill_packed_impl(tl_engine *e, int n_seqs, const int *slots, const
     const tl_engine_config &c = e->cfg;
     TL_REQUIRE(e && slots && tokens && lens && want_logits, "engine_prefill_packed: null argument");
     std::vector<PrefillSeq> seqs;
-    TL_TRY(packed_seqs(e, n_seqs, slots, tokens, lens, want_logits, "engine_prefill_packed", seqs));
     int total = 0;
-    for (int i = 0; i < n_seqs; ++i) total += lens[i];
+    TL_TRY(packed_seqs(e, n_seqs, slots, tokens, lens, want_logits, "engine_prefill_packed", seqs, &total));
     TL_TRY(prefill_pass(e, seqs.data(), n_seqs, tokens, total, true));
     int n_logits = 0;
     for (int i = 0; i < n_seqs; ++i) {
         if (!want_logits[i]) continue;
         // last rows side by side in xn: one lm_head pass over them (logits_to_keep = 1, qwen3_week3.py:331-336)
-        TL_HIP(hipMemcpyAsync(e->xn + (size_t)n_logits * c.hidden_size, e->x + (size_t)(seqs[i].row0 + lens[i] - 1) * c.hidden_size,
+        TL_HIP(hipMemcpyAsync(e->shared.xn + (size_t)n_logits * c.hidden_size, e->shared.x_out + (size_t)(seqs[i].row0 + lens[i] - 1) * c.hidden_size,
                               (size_t)c.hidden_size * 2, hipMemcpyDeviceToDevice, e->stream));
         ++n_logits;
     }
     if (n_logits > 0) {
-        TL_TRY(lm_head_rows(e, e->xn, n_logits));
+        TL_TRY(lm_head_rows(e, e->shared.xn, n_logits));
         e->logits_rows = n_logits, e->logits_slot = -2;
         int j = 0;
         for (int i = 0; i < n_seqs; ++i) {
@@ -3063,13 +3045,13 @@ static int embed_pool(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const in
         }
         e->settings.rewound(q.slot);  // (a LAST chunk: the context no longer is a running mean's)
         if (!finish[i]) continue;
-        TL_HIP(hipMemcpyAsync(e->h + (size_t)n * H, e->x + (size_t)(q.row0 + q.len - 1) * H, H * 2, hipMemcpyDeviceToDevice, e->stream));
+        TL_HIP(hipMemcpyAsync(e->shared.h + (size_t)n * H, e->shared.x_out + (size_t)(q.row0 + q.len - 1) * H, H * 2, hipMemcpyDeviceToDevice, e->stream));
         row0[n] = n, len[n] = 1, prior[n] = 0, sum_index[n] = 0, fin[n] = 1;
         ++n, ++n_finish;
     }
     if (n == 0) return TL_OK;  // LAST chunks that end no text: the pass has appended their K/V, nothing to pool
-    TL_TRY(tl_rms_norm(mean ? e->x : e->h, e->final_norm, e->xn, mean ? total : n, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
-    TL_TRY(pool_rows(e->xn, c.hidden_size, n, row0, len, fin, prior, sum_index, pooling, e->emb_sums, normalize, dim, e->emb_out, e->stream));
+    TL_TRY(tl_rms_norm(mean ? e->shared.x_out : e->shared.h, e->final_norm, e->shared.xn, mean ? total : n, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
+    TL_TRY(pool_rows(e->shared.xn, c.hidden_size, n, row0, len, fin, prior, sum_index, pooling, e->emb_sums, normalize, dim, e->emb_out, e->stream));
     if (n_finish == 0) return TL_OK;
     TL_HIP(hipMemcpyAsync(out_host, e->emb_out, (size_t)n_finish * dim * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     TL_HIP(hipStreamSynchronize(e->stream));
@@ -3080,10 +3062,10 @@ extern "C" int tl_engine_embed_packed(tl_engine *e, int n_seqs, const int *slots
                                       int pooling, int normalize, int dim, float *out_host) {
     TL_REQUIRE(e && slots && tokens && lens && finish, "engine_embed_packed: null argument");
     std::vector<PrefillSeq> seqs;
-    TL_TRY(packed_seqs(e, n_seqs, slots, tokens, lens, nullptr, "engine_embed_packed", seqs));
-    bool finishes = false;
     int total = 0;
-    for (int i = 0; i < n_seqs; ++i) finishes |= finish[i] != 0, total += lens[i];
+    TL_TRY(packed_seqs(e, n_seqs, slots, tokens, lens, nullptr, "engine_embed_packed", seqs, &total));
+    bool finishes = false;
+    for (int i = 0; i < n_seqs; ++i) finishes |= finish[i] != 0;
     TL_TRY(embed_args_check(e, pooling, dim, finishes, out_host));
     if (pooling == TL_POOL_MEAN) TL_TRY(embed_mean_check(e, seqs.data(), n_seqs));
     TL_TRY(prefill_pass(e, seqs.data(), n_seqs, tokens, total, true));
@@ -3103,7 +3085,7 @@ extern "C" int tl_engine_embed(tl_engine *e, int slot, const int32_t *tokens, in
 
 extern "C" int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, int n, int32_t *out_ids) {
     TL_REQUIRE(e && out_ids, "engine_verify: null argument");
-    TL_REQUIRE(n >= 1 && n <= 8, "engine_verify: between 1 and 8 tokens per call (the paged decode kernel's query rows)");
+    TL_REQUIRE(n >= 1 && n <= VERIFY_MAX_LEN, "engine_verify: between 1 and 8 tokens per call (the paged decode kernel's query rows)");
     TL_TRY(slot_check_feeds(e, slot));
     TL_TRY(table_rc(e->settings.refuses_verify(slot)));
     TL_TRY(prefill_impl(e, slot, tokens, n, 2));
@@ -3115,7 +3097,7 @@ extern "C" int tl_engine_verify(tl_engine *e, int slot, const int32_t *tokens, i
 extern "C" int tl_engine_verify_sampled(tl_engine *e, int slot, const int32_t *tokens, int n, const void *draft_logits_dev, float draft_temperature,
                                         int draft_top_k, float draft_top_p, int32_t *out_ids, int *out_count) {
     TL_REQUIRE(e && tokens && out_ids && out_count, "engine_verify_sampled: null argument");
-    TL_REQUIRE(n >= 1 && n <= 8, "engine_verify_sampled: between 1 and 8 tokens per call (the paged decode kernel's query rows)");
+    TL_REQUIRE(n >= 1 && n <= VERIFY_MAX_LEN, "engine_verify_sampled: between 1 and 8 tokens per call (the paged decode kernel's query rows)");
     TL_REQUIRE(n == 1 || draft_logits_dev, "engine_verify_sampled: the rows the proposals were drawn from are missing");
     TL_REQUIRE(std::isfinite(draft_temperature) && draft_temperature >= 0.f, "engine_verify_sampled: the draft's temperature must be finite and >= 0");
     TL_TRY(slot_check_feeds(e, slot));
@@ -3154,95 +3136,45 @@ extern "C" int tl_engine_verify_sampled(tl_engine *e, int slot, const int32_t *t
 // ---- batched verification (include/tinyllm_engine.h "tl_engine_verify_batch"; the kernels are verify_attn.h) --------------------------
 // the scratch of the pass, allocated by the first call
 static int verify_alloc(tl_engine *e) {
-    using V = tl_engine::VerifyScratch;
-    V &v = e->vb;
+    using V = VerifyLayout;
+    tl_engine::VerifyScratch &v = e->vb;
     if (v.desc) return TL_OK;
-    const tl_engine_config &c = e->cfg;
-    const size_t R = VA_MAX_ROWS, H = (size_t)c.hidden_size;
     // the matmul workspace of 1 .. 64 rows, as tl_engine_create sizes the engine's own for its rows: only where that one is too small
-    size_t need = 0;
-    {
-        const tl_layer_weights *dense = &e->layers[0];
-        for (const auto &l : e->layers)
-            if (l.wgu.weight_dev) {
-                dense = &l;
-                break;
-            }
-        std::vector<tl_w4> mats = {e->layers[0].wqkv, e->layers[0].wo, dense->wgu, dense->wdown, e->head()};
-        for (int l = 0; l < c.num_layers; ++l)
-            if (e->is_moe(l)) mats.push_back(e->moe[l].router);
-        for (const tl_w4 &w : mats) {
-            if (!w.weight_dev) continue;
-            for (int M = 1; M <= VA_MAX_ROWS; ++M) {
-                const Qmm3Plan p3 = qmm3_plan(M, w.cols, w.rows);
-                if (p3.ok) need = std::max(need, p3.partial_bytes);
-                need = std::max(need, tl_quantized_matmul_workspace_bytes(M, w.cols, w.rows, TL_BF16, 1, 1));
-            }
-        }
-    }
-    const bool own_ws = need > e->lin.splitk_ws_bytes;
-    const size_t ss_per_row = (size_t)std::max(QM3_SS, c.hidden_size / 16 + 1);
-    const size_t ws_rows = verify_ws_rows(c.num_heads);
-    Carve carve;
-    const size_t o_x = carve(R * H * 2), o_h = carve(R * H * 2), o_xn = carve(R * H * 2), o_tmp = carve(R * H * 2);
-    const size_t o_qkv = carve(R * e->qkv_dim() * 2), o_q = carve(R * e->q_dim() * 2), o_attn = carve(R * e->q_dim() * 2);
-    const size_t o_gu = carve(R * 2 * c.intermediate_size * 2), o_act = carve(R * c.intermediate_size * 2);
-    const size_t o_log = carve(R * c.vocab_size * 2);
-    const size_t o_ssx = carve(R * ss_per_row * 4), o_ssh = carve(R * ss_per_row * 4);
-    const size_t o_aws = carve(ws_rows * (VA_D + 2) * 4);
-    const size_t o_desc = carve((size_t)V::DESC_ARRAYS * 64 * 4), o_greedy = carve(R * 4), o_res = carve(R * sizeof(tl_verify_result));
-    const size_t o_ws = own_ws ? carve(need) : 0;
-    TL_TRY(v.mem.alloc(carve.off, "engine_verify_batch: hipMalloc(scratch) failed"));
-    char *A = v.mem.at();
-    v.x = (uint16_t *)(A + o_x), v.h = (uint16_t *)(A + o_h), v.xn = (uint16_t *)(A + o_xn), v.tmp = (uint16_t *)(A + o_tmp);
-    v.qkv = (uint16_t *)(A + o_qkv), v.q = (uint16_t *)(A + o_q), v.attn = (uint16_t *)(A + o_attn);
-    v.gu = (uint16_t *)(A + o_gu), v.act = (uint16_t *)(A + o_act), v.logits = (uint16_t *)(A + o_log);
-    v.ss_x = (float *)(A + o_ssx), v.ss_h = (float *)(A + o_ssh), v.attn_ws = (float *)(A + o_aws), v.attn_ws_rows = ws_rows;
-    v.greedy = (int32_t *)(A + o_greedy), v.results = (tl_verify_result *)(A + o_res);
-    v.splitk_ws = own_ws ? (void *)(A + o_ws) : e->lin.splitk_ws;
-    v.splitk_ws_bytes = own_ws ? need : e->lin.splitk_ws_bytes;
-    v.desc = (int32_t *)(A + o_desc);
-    e->stats.workspace_bytes += carve.off;
+    LayoutInputs in = layout_inputs(e);
+    in.matmul_ws_need = matmul_ws_need(e, 1, VERIFY_BATCH_ROWS, 1, VERIFY_BATCH_ROWS, true);
+    const VerifyLayout vl = verify_layout(e->cfg, in);
+    TL_TRY(v.mem.alloc(vl.bytes, "engine_verify_batch: hipMalloc(scratch) failed"));
+    char *m = v.mem.at();
+    v.act = verify_act(m, vl);
+    v.lin.xn = v.act.xn, v.lin.gu = piece_at<uint16_t>(m, vl[V::GU]), v.lin.tmp = piece_at<uint16_t>(m, vl[V::TMP]);
+    v.lin.splitk_ws = vl.own_ws ? piece_at<void>(m, vl[V::MATMUL_WS]) : e->lin.splitk_ws;
+    v.lin.splitk_ws_bytes = vl.own_ws ? in.matmul_ws_need : e->lin.splitk_ws_bytes;
+    v.q = piece_at<uint16_t>(m, vl[V::Q]), v.logits = piece_at<uint16_t>(m, vl[V::LOGITS]), v.attn_ws_rows = in.verify_ws_rows;
+    v.greedy = piece_at<int32_t>(m, vl[V::GREEDY]), v.results = piece_at<tl_verify_result>(m, vl[V::RESULTS]);
+    v.desc = piece_at<int32_t>(m, vl[V::DESC]);
+    e->stats.workspace_bytes += vl.bytes;
     return TL_OK;
 }
 
-// The checks of a batched verification, all before anything is reserved or allocated (packed_seqs is the model), and its sequences.
-static int verify_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, bool commit, std::vector<PrefillSeq> &seqs) {
+// The checks of a batched verification and its sequences (pass_seqs holds what it shares with a packed pass).
+static int verify_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, bool commit, std::vector<PrefillSeq> &seqs,
+                       int *total) {
     const tl_engine_config &c = e->cfg;
     const std::string w = "engine_verify_batch: ";
-    TL_REQUIRE(n_seqs >= 1 && n_seqs <= VA_MAX_ROWS, w + "between 1 and 64 sequences per call");
+    TL_REQUIRE(n_seqs >= 1 && n_seqs <= VERIFY_BATCH_ROWS, w + "between 1 and 64 sequences per call");
     TL_REQUIRE(c.head_dim == VA_D, w + "head_dim 128");
-    int total = 0;
-    for (int i = 0; i < n_seqs; ++i) {
-        TL_REQUIRE(lens[i] >= 1 && lens[i] <= VA_MAX_LEN, w + "between 1 and 8 tokens per sequence");
-        total += lens[i];
-    }
-    TL_REQUIRE(total <= VA_MAX_ROWS, w + "the chunks together exceed 64 rows");
-    bool moe = false;
-    for (int l = 0; l < c.num_layers; ++l) moe |= e->is_moe(l);
-    TL_REQUIRE(!moe || total <= e->rows_cap, w + "a model with MoE layers takes at most max(max_batch, max_prefill_rows) rows (the experts' workspace)");
-    size_t extra_pages = 0;
-    for (int i = 0; i < n_seqs; ++i) {
-        const int slot = slots[i];
-        TL_TRY(slot_check_feeds(e, slot));
-        for (int j = 0; j < i; ++j) TL_REQUIRE(slots[j] != slot, w + "a slot appears twice");
-        TL_TRY(table_rc(e->settings.refuses_verify_batch(slot)));
-        const Slot &s = e->table.slots[slot];
-        const int need = (s.ctx + lens[i] + c.page_size - 1) / c.page_size;
-        TL_REQUIRE(need <= c.max_pages_per_seq, "engine: sequence exceeds max_pages_per_seq * page_size tokens");
-        if (need > (int)s.pages.size()) extra_pages += (size_t)need - s.pages.size();
-        // commit: a rewind into a page this chunk filled copies it when the prefix index has taken it (SlotTable::rewind)
-        if (commit && lens[i] > 1 && e->table.pool.enabled && (s.ctx + lens[i]) / c.page_size > s.ctx / c.page_size) extra_pages += 1;
-    }
-    TL_REQUIRE(e->table.pool.can_take(extra_pages), "engine: KV page pool exhausted");
-    for (int i = 0; i < total; ++i) TL_REQUIRE(tokens[i] >= 0 && tokens[i] < c.vocab_size, w + "token id out of range");
-    seqs.resize(n_seqs);
     int rows = 0;
     for (int i = 0; i < n_seqs; ++i) {
-        seqs[i] = {slots[i], e->table.slots[slots[i]].ctx, rows, lens[i]};
+        TL_REQUIRE(lens[i] >= 1 && lens[i] <= VERIFY_MAX_LEN, w + "between 1 and 8 tokens per sequence");
         rows += lens[i];
     }
-    return TL_OK;
+    TL_REQUIRE(rows <= VERIFY_BATCH_ROWS, w + "the chunks together exceed 64 rows");
+    bool moe = false;
+    for (int l = 0; l < c.num_layers; ++l) moe |= e->is_moe(l);
+    TL_REQUIRE(!moe || rows <= e->rows_cap, w + "a model with MoE layers takes at most max(max_batch, max_prefill_rows) rows (the experts' workspace)");
+    // (a slot's refusal is met at its first appearance, ahead of "a slot appears twice" at its second, wherever it stands in the loop)
+    const auto per_seq = [&](int i) { return table_rc(e->settings.refuses_verify_batch(slots[i])); };
+    return pass_seqs(e, n_seqs, slots, tokens, lens, commit, w, per_seq, [](int) { return (int)TL_OK; }, seqs, total);
 }
 
 // The pass over the `total` rows of the chunks in `seqs`, eager on the engine stream: pages reserved, tokens and descriptors uploaded in
@@ -3254,52 +3186,50 @@ static int verify_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const i
     using V = tl_engine::VerifyScratch;
     const tl_engine_config &c = e->cfg;
     V &v = e->vb;
+    const Act &b = v.act;
     TL_TRY(aql_drain(e));
     SlotEdits ed;
     Pokes pk;
     for (int i = 0; i < n_seqs; ++i) TL_TRY(table_rc(e->table.reserve(seqs[i].slot, seqs[i].start + seqs[i].len, ed)));
     TL_TRY(apply_edits(e, ed, pk));
     TL_TRY(poke(e, pk));
-    int32_t desc[V::DESC_ARRAYS * 64] = {};
+    constexpr int N = VERIFY_BATCH_ROWS;  // words per array of `desc`
+    int32_t desc[V::DESC_ARRAYS * N] = {};
     int max_len = 1, max_ctx = 1;
     for (int i = 0; i < n_seqs; ++i) {
         const PrefillSeq &s = seqs[i];
-        desc[V::SEQ_SLOT * 64 + i] = s.slot, desc[V::SEQ_ROW0 * 64 + i] = s.row0, desc[V::SEQ_LEN * 64 + i] = s.len;
-        desc[V::SEQ_CTX * 64 + i] = s.start + s.len;
+        desc[V::SEQ_SLOT * N + i] = s.slot, desc[V::SEQ_ROW0 * N + i] = s.row0, desc[V::SEQ_LEN * N + i] = s.len;
+        desc[V::SEQ_CTX * N + i] = s.start + s.len;
         for (int j = 0; j < s.len; ++j) {
-            desc[V::TOKENS * 64 + s.row0 + j] = tokens[s.row0 + j];
-            desc[V::ROW_SLOT * 64 + s.row0 + j] = s.slot, desc[V::ROW_POS * 64 + s.row0 + j] = s.start + j;
+            desc[V::TOKENS * N + s.row0 + j] = tokens[s.row0 + j];
+            desc[V::ROW_SLOT * N + s.row0 + j] = s.slot, desc[V::ROW_POS * N + s.row0 + j] = s.start + j;
         }
         max_len = std::max(max_len, s.len), max_ctx = std::max(max_ctx, s.start + s.len);
     }
     TL_HIP(hipMemcpyAsync(v.desc, desc, sizeof(desc), hipMemcpyHostToDevice, e->stream));
     const VerifySplit sp = verify_pick_splits(n_seqs, c.num_heads, c.num_kv_heads, total, max_len, max_ctx, v.attn_ws_rows);
 
-    TL_TRY(tl_quantized_embedding(v.arr(V::TOKENS), 0, e->embed.scales_dev, e->embed.biases_dev, e->embed.weight_dev, v.x, total, c.hidden_size,
+    TL_TRY(tl_quantized_embedding(v.arr(V::TOKENS), 0, e->embed.scales_dev, e->embed.biases_dev, e->embed.weight_dev, b.x_out, total, c.hidden_size,
                                   c.vocab_size, 128, 4, TL_BF16, e->stream));
     // the router's scratch for the duration of the pass: the RMSNorm rows, the unfused epilogues' rows and the matmul workspace of 64 rows
     // (the engine's own go back when the pass returns, however it returns: captured steps hold those addresses)
     struct CtxScratch {
-        LinearCtx &ctx;
-        uint16_t *xn, *gu, *tmp;
-        void *ws;
-        size_t ws_bytes;
-        CtxScratch(LinearCtx &c_, const V &v_) : ctx(c_), xn(c_.xn), gu(c_.gu), tmp(c_.tmp), ws(c_.splitk_ws), ws_bytes(c_.splitk_ws_bytes) {
-            c_.xn = v_.xn, c_.gu = v_.gu, c_.tmp = v_.tmp, c_.splitk_ws = v_.splitk_ws, c_.splitk_ws_bytes = v_.splitk_ws_bytes;
-        }
-        ~CtxScratch() { ctx.xn = xn, ctx.gu = gu, ctx.tmp = tmp, ctx.splitk_ws = ws, ctx.splitk_ws_bytes = ws_bytes; }
-    } scratch(e->lin, v);
+        LinearScratch &ctx;
+        const LinearScratch own;
+        CtxScratch(LinearScratch &c_, const LinearScratch &pass) : ctx(c_), own(c_) { ctx = pass; }
+        ~CtxScratch() { ctx = own; }
+    } scratch(e->lin, v.lin);
     LinearCtx &ctx = e->lin;
     const bool kv8 = e->kv_format == TL_KV_FP8_E4M3;
     int x_ss = 0;  // partials per row in ss_x (0 = none): whatever the last writer of x left
     for (int l = 0; l < c.num_layers; ++l) {
         const tl_layer_weights &w = e->layers[l];
         ProjResult r;
-        Proj p = proj(w.wqkv, v.x, v.qkv, total);
-        p.pro = PRO_RMSNORM, p.norm_w = w.input_norm_dev, p.ss_in = x_ss ? v.ss_x : nullptr, p.ss_in_n = x_ss;
+        Proj p = proj(w.wqkv, b.x_out, b.qkv, total);
+        p.pro = PRO_RMSNORM, p.norm_w = w.input_norm_dev, p.ss_in = x_ss ? b.ss_x_out : nullptr, p.ss_in_n = x_ss;
         TL_TRY(engine_linear(ctx, p));
         VerifyRowsArgs q{};
-        q.qkv = v.qkv, q.q_norm_w = (const uint16_t *)w.q_norm_dev, q.k_norm_w = (const uint16_t *)w.k_norm_dev, q.q = v.q;
+        q.qkv = b.qkv, q.q_norm_w = (const uint16_t *)w.q_norm_dev, q.k_norm_w = (const uint16_t *)w.k_norm_dev, q.q = v.q;
         q.key_pages = e->layer_k(l), q.value_pages = e->layer_v(l), q.key_scales = e->layer_ks(l), q.value_scales = e->layer_vs(l);
         q.block_table = e->block_table, q.row_slot = v.arr(V::ROW_SLOT), q.row_pos = v.arr(V::ROW_POS);
         q.page_size = c.page_size, q.max_pages = c.max_pages_per_seq, q.num_heads = c.num_heads, q.num_kv_heads = c.num_kv_heads;
@@ -3307,33 +3237,33 @@ static int verify_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const i
         VerifyAttnArgs a{};
         a.q = v.q, a.key_pages = q.key_pages, a.value_pages = q.value_pages, a.key_scales = q.key_scales, a.value_scales = q.value_scales;
         a.block_table = e->block_table, a.seq_slot = v.arr(V::SEQ_SLOT), a.seq_row0 = v.arr(V::SEQ_ROW0), a.seq_len = v.arr(V::SEQ_LEN);
-        a.seq_ctx = v.arr(V::SEQ_CTX), a.out = v.attn, a.ws = v.attn_ws;
+        a.seq_ctx = v.arr(V::SEQ_CTX), a.out = b.attn, a.ws = b.attn_ws;
         a.page_size = c.page_size, a.max_pages = c.max_pages_per_seq, a.num_heads = c.num_heads, a.num_kv_heads = c.num_kv_heads;
         a.scale = 1.0f / sqrtf((float)c.head_dim);
         TL_TRY(launch_verify_attention(q, a, sp, total, n_seqs, kv8, e->stream));
-        Proj po = proj(w.wo, v.attn, v.h, total);
-        po.epi = EPI_RESIDUAL, po.residual = v.x, po.kind = 1;
+        Proj po = proj(w.wo, b.attn, b.h, total);
+        po.epi = EPI_RESIDUAL, po.residual = b.x_out, po.kind = 1;
         if (e->is_moe(l)) {  // wo + residual, then the MoE MLP as its own launches (no producer-side sums for the next layer)
             TL_TRY(engine_linear(ctx, po));
-            TL_TRY(tl_rms_norm(v.h, w.post_norm_dev, v.xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
-            TL_TRY(engine_moe_mlp(e, l, v.xn, v.h, v.x, total, nullptr));
+            TL_TRY(tl_rms_norm(b.h, w.post_norm_dev, b.xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
+            TL_TRY(engine_moe_mlp(e, l, b.xn, b.h, b.x_out, total, nullptr));
             x_ss = 0;
             continue;
         }
         TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
-        po.ss_out = v.ss_h;
+        po.ss_out = b.ss_h;
         TL_TRY(engine_linear(ctx, po, nullptr, &r));
         const int h_ss = r.ss_n;
-        Proj pg = proj(w.wgu, v.h, v.act, total);
-        pg.pro = PRO_RMSNORM, pg.norm_w = w.post_norm_dev, pg.epi = EPI_SWIGLU, pg.kind = 2, pg.ss_in = h_ss ? v.ss_h : nullptr, pg.ss_in_n = h_ss;
+        Proj pg = proj(w.wgu, b.h, b.act, total);
+        pg.pro = PRO_RMSNORM, pg.norm_w = w.post_norm_dev, pg.epi = EPI_SWIGLU, pg.kind = 2, pg.ss_in = h_ss ? b.ss_h : nullptr, pg.ss_in_n = h_ss;
         TL_TRY(engine_linear(ctx, pg));
-        Proj pd = proj(w.wdown, v.act, v.x, total);
-        pd.epi = EPI_RESIDUAL, pd.residual = v.h, pd.kind = 3, pd.ss_out = v.ss_x;
+        Proj pd = proj(w.wdown, b.act, b.x_out, total);
+        pd.epi = EPI_RESIDUAL, pd.residual = b.h, pd.kind = 3, pd.ss_out = b.ss_x_out;
         TL_TRY(engine_linear(ctx, pd, nullptr, &r));
         x_ss = r.ss_n;
     }
-    Proj ph = proj(e->head(), v.x, v.logits, total);
-    ph.pro = PRO_RMSNORM, ph.norm_w = e->final_norm, ph.kind = 4, ph.ss_in = x_ss ? v.ss_x : nullptr, ph.ss_in_n = x_ss;
+    Proj ph = proj(e->head(), b.x_out, v.logits, total);
+    ph.pro = PRO_RMSNORM, ph.norm_w = e->final_norm, ph.kind = 4, ph.ss_in = x_ss ? b.ss_x_out : nullptr, ph.ss_in_n = x_ss;
     TL_TRY(engine_linear(ctx, ph));
     TL_TRY(launch_verify_accept(v.logits, c.vocab_size, total, n_seqs, v.arr(V::TOKENS), v.arr(V::SEQ_ROW0), v.arr(V::SEQ_LEN), v.greedy, v.results,
                                 e->stream));
@@ -3351,10 +3281,9 @@ extern "C" int tl_engine_verify_batch(tl_engine *e, int n_seqs, const int *slots
                                       tl_verify_result *out) {
     TL_REQUIRE(e && slots && tokens && lens && out, "engine_verify_batch: null argument");
     std::vector<PrefillSeq> seqs;
-    TL_TRY(verify_seqs(e, n_seqs, slots, tokens, lens, commit != 0, seqs));
-    TL_TRY(verify_alloc(e));
     int total = 0;
-    for (int i = 0; i < n_seqs; ++i) total += lens[i];
+    TL_TRY(verify_seqs(e, n_seqs, slots, tokens, lens, commit != 0, seqs, &total));
+    TL_TRY(verify_alloc(e));
     TL_TRY(verify_pass(e, seqs.data(), n_seqs, tokens, total));
     TL_HIP(hipMemcpyAsync(out, e->vb.results, (size_t)n_seqs * sizeof(tl_verify_result), hipMemcpyDeviceToHost, e->stream));
     TL_HIP(hipStreamSynchronize(e->stream));
@@ -3391,8 +3320,8 @@ static int aql_drain(tl_engine *e) {
 static void launch_embed_slots(tl_engine *e, int batch) {
     const tl_engine_config &c = e->cfg;
     hipLaunchKernelGGL(embed_slots_kernel, dim3(batch), dim3(256), 0, e->stream, e->tokens, e->embed.weight_dev,
-                       (const uint16_t *)e->embed.scales_dev, (const uint16_t *)e->embed.biases_dev, e->x, c.hidden_size,
-                       c.vocab_size, e->context_lens, e->rope_table, e->rope_cur, e->rope_positions, c.head_dim / 2, e->ss_x);
+                       (const uint16_t *)e->embed.scales_dev, (const uint16_t *)e->embed.biases_dev, e->shared.x_out, c.hidden_size,
+                       c.vocab_size, e->context_lens, e->rope_table, e->rope_cur, e->rope_positions, c.head_dim / 2, e->shared.ss_x_out);
 }
 
 // the pages of this step's token in every live slot of [0, batch), poked into the block table, and the step's split plan.  A caller with
