@@ -431,11 +431,12 @@ HQ, HKV, D, PAGE = 32, 8, 128, 128
 THETA = 1e6
 
 
-def _attention_case(rng, ctxs, extra_pages=2):
+def _attention_case(rng, ctxs, extra_pages=2, page=PAGE):
     """Scattered physical pages (reference construction test_week_3_day_5.py:25-37), random bf16 K/V, one qkv row per
-    sequence; ctx = tokens already cached (an idle slot has ctx 0 and an all -1 block-table row)."""
+    sequence; ctx = tokens already cached (an idle slot has ctx 0 and an all -1 block-table row).  The pools' third axis is the page
+    size: the oracle and the checks below read it there."""
     B = len(ctxs)
-    need = [(c + 1 + PAGE - 1) // PAGE if c >= 0 else 0 for c in ctxs]
+    need = [(c + 1 + page - 1) // page if c >= 0 else 0 for c in ctxs]
     P = sum(need) + extra_pages
     ids = list(rng.permutation(P))
     max_pages = max(max(need), 1) + 1
@@ -443,8 +444,8 @@ def _attention_case(rng, ctxs, extra_pages=2):
     for b in range(B):
         for j in range(need[b]):
             table[b, j] = ids.pop()
-    kp = O.bf16(rng.standard_normal((P, HKV, PAGE, D), dtype=np.float32))
-    vp = O.bf16(rng.standard_normal((P, HKV, PAGE, D), dtype=np.float32))
+    kp = O.bf16(rng.standard_normal((P, HKV, page, D), dtype=np.float32))
+    vp = O.bf16(rng.standard_normal((P, HKV, page, D), dtype=np.float32))
     qkv = O.bf16(rng.standard_normal((B, (HQ + 2 * HKV) * D), dtype=np.float32))
     qn = O.bf16(1.0 + 0.1 * rng.standard_normal((D,), dtype=np.float32))
     kn = O.bf16(1.0 + 0.1 * rng.standard_normal((D,), dtype=np.float32))
@@ -454,7 +455,7 @@ def _attention_case(rng, ctxs, extra_pages=2):
 def _attention_oracle(kp, vp, table, ctx, qkv, qn, kn, idle):
     """Reference op order (qwen3_week3.py:63-86): q/k RMSNorm -> RoPE at offset ctx -> paged_cache_update -> paged_attention
     over ctx + 1 tokens."""
-    B = len(ctx)
+    B, page = len(ctx), kp.shape[2]
     kp, vp = kp.copy(), vp.copy()
     rows = qkv.reshape(B, HQ + 2 * HKV, D)
     q = O.rms_norm_fast(rows[:, :HQ], qn, EPS)[:, None]             # [B, L=1, Hq, D]
@@ -467,7 +468,7 @@ def _attention_oracle(kp, vp, table, ctx, qkv, qn, kn, idle):
         if idle[b]:
             lens[b] = 0
             continue
-        pid, slot = int(table[b, ctx[b] // PAGE]), int(ctx[b] % PAGE)
+        pid, slot = int(table[b, ctx[b] // page]), int(ctx[b] % page)
         kp[pid, :, slot, :] = k[b, 0]
         vp[pid, :, slot, :] = v[b, 0]
         lens[b] = ctx[b] + 1
@@ -495,10 +496,11 @@ def _check_attention(case, got, kp_after, vp_after, idle, what):
             assert not got[b].any(), f"{what}: idle slot {b} must produce zeros"
     np.testing.assert_array_equal(vp_after, vp_want, err_msg=f"{what}: value pages (appended V row, nothing else touched)")
     kp_before, table, ctx = case[0], case[2], case[3]
+    page = kp_before.shape[2]
     touched = np.zeros(kp_before.shape[:3], dtype=bool)  # [P, Hkv, slot]
     for b, is_idle in enumerate(idle):
         if not is_idle:
-            touched[int(table[b, ctx[b] // PAGE]), :, int(ctx[b] % PAGE)] = True
+            touched[int(table[b, ctx[b] // page]), :, int(ctx[b] % page)] = True
     np.testing.assert_array_equal(kp_after[~touched], kp_before[~touched], err_msg=f"{what}: key pages outside the appended rows")
     # the appended K row went through RMSNorm and RoPE in fp32 on both sides (two bf16 roundings): a one-ulp difference of a
     # normalised value moves the rotated pair by up to 2^-8 of the LARGER partner, whatever the size of the result
@@ -563,7 +565,7 @@ def test_decode_attention_long_contexts(ext, ctxs, mode, monkeypatch):
     ([8000] + [200, 1300, 77, 4100, 640, 31, 2500] * 3 + [129, -1], 1),  # 24 slots, one at 8,000 tokens, one idle
 ])
 def test_decode_attention_many_sequences_follow_the_remeasured_plan(ext, ctxs, windows, monkeypatch):
-    """The batched plans of the end of round 6 (engine.hip plan_splits; profiles/r06_labs/README.md section 9) at the kernel-level entry point, ragged
+    """The batched plans of the end of round 6 (csrc/attn_plan.h pick_decode_splits; profiles/r06_labs/README.md section 9) at the kernel-level entry point, ragged
     contexts, against the oracle: longer windows than the round-4 plan walked (up to a whole 8,000-token context in one workgroup)."""
     for name in ("TL_ATTN_RQ", "TL_ATTN_MAX_SPLITS", "TL_ATTN_MIN_TOKENS", "TL_ATTN_MFMA"):
         monkeypatch.delenv(name, raising=False)
@@ -576,6 +578,23 @@ def test_decode_attention_many_sequences_follow_the_remeasured_plan(ext, ctxs, w
     assert info["launches"] == (1 if windows == 1 else 2), what
     _check_attention(case, got, kpa, vpa, idle, what)
     log_parity({"what": "decode_attention_many", "ctxs": ctxs, **info})
+
+
+@pytest.mark.parametrize("ctxs", [[0], [15], [16], [100], [300], [300, 17, 5, 100, 64]])
+def test_decode_attention_on_16_token_pages(ext, ctxs, monkeypatch):
+    """The general walk (csrc/attn_plan.h AttnWalk::GENERAL: a 64-token window spans four pages, so neither the single-page nor the
+    stage-page walk applies, and a wave's 32 tokens cross pages, so neither does the matrix-core walk): the page id of every token looked
+    up on its own.  One sequence on either side of a page boundary and with 2 and 4 windows (one head per workgroup), and a ragged batch
+    of five (the whole GQA group per workgroup, one window)."""
+    for name in ("TL_ATTN_RQ", "TL_ATTN_MAX_SPLITS", "TL_ATTN_MIN_TOKENS", "TL_ATTN_MFMA"):
+        monkeypatch.delenv(name, raising=False)
+    rng = np.random.default_rng(1600 + sum(ctxs) + len(ctxs))
+    case = _attention_case(rng, ctxs, page=16)
+    got, kpa, vpa, info = _run_attention(ext, case, max(ctxs))
+    what = f"16-token pages, ctxs={ctxs} {info}"
+    assert info["n_splits"] * info["tokens_per_split"] >= max(ctxs) + 1 and info["heads_per_workgroup"] == (1 if len(ctxs) == 1 else 4), what
+    assert info["launches"] == (1 if info["n_splits"] == 1 else 2), what
+    _check_attention(case, got, kpa, vpa, [False] * len(ctxs), what)
 
 
 def test_flash_attention_2048_row_chunk_over_8k_context(ext):

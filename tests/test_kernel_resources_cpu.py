@@ -1,7 +1,7 @@
 """CPU tier: static resource check of every gfx950 kernel in the built library -- no GPU needed.
 
 A kernel that spills registers to scratch still computes the right answer, so no parity test notices; it just runs several times
-slower (one wide decode-attention variant did exactly that in round 2 and was re-planned onto 8 waves, csrc/engine.hip
+slower (one wide decode-attention variant did exactly that in round 2 and was re-planned onto 8 waves, csrc/attn_plan.h
 pick_decode_splits).  The code objects bundled in libtinyllm_hip.so carry the compiler's per-kernel metadata
 (private_segment_fixed_size, vgpr / sgpr spill counts): this test reads it with llvm-objdump / llvm-readelf and holds every
 kernel to "no scratch, no VGPR spills" (SGPR spills go to VGPR lanes and cost a v_readlane, not memory), except the ones listed

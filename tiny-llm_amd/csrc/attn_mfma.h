@@ -34,7 +34,7 @@ constexpr int AM_OFF_K = AM_NSLOT * AD_RQ * (128 + 2) * 4;  // 10,400: a multipl
 constexpr int AM_OFF_Q = AM_OFF_K + 4 * AM_KWAVE;
 constexpr int AM_OFF_QP = AM_OFF_Q + AD_RQ * 128 * 2;
 static_assert(AM_OFF_K % 16 == 0 && AM_OFF_Q % 16 == 0 && AM_OFF_QP % 16 == 0, "16-byte LDS rows");
-constexpr size_t attn_mfma_lds_bytes(bool qp) { return (size_t)AM_OFF_QP + (qp ? (2 + AD_RQ) * 128 * 2 : 0); }
+static_assert(AM_OFF_QP == ATTN_MFMA_LDS, "the plan (attn_plan.h) sizes the launch's LDS: AM_OFF_QP + (QP) the (2 + AD_RQ) staged rows");
 
 // KV8 = FP8 pages (kv8.h): a lane requests 8 bytes of codes per row instead of 16 of bf16, and the scales of its 8 tokens as two
 // 16-byte words per pool.  Codes become bf16 UNSCALED on their way into the K image / the V operands (exact); the K row's scale
@@ -431,7 +431,6 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(const AttnDecodeA
 }
 
 // launcher (attn_mfma.hip, compiled with the VGPR form of MFMA: the softmax reads and rescales every accumulator on the VALU)
-bool attn_decode_mfma_applicable(const AttnDecodeArgs &a, int head_dim, int rq);
-void launch_attn_decode_mfma(const AttnDecodeArgs &a, dim3 grid, hipStream_t st);
+void launch_attn_decode_mfma(const AttnDecodeArgs &a, const AttnPlan &plan, hipStream_t st);  // a MATRIX_CORE plan (attn_plan.h)
 
 }  // namespace tl

@@ -431,6 +431,23 @@ static bool takes_skinny_matmul(const LinearCtx &ctx, const tl_w4 &w, int M) {
     return !gemv_takes_rows(ctx, M) && ctx.use_qmm3 && M <= 64 && ctx.tiled.count(w.weight_dev) != 0 && qmm3_plan(M, w.cols, w.rows, ctx.qmm3_mode).ok;
 }
 
+// Can the wo GEMV of ONE decode row take the attention split partials instead of the merged row (qmv3.hip,
+// launch_qmv3_attn_merge_bf16: the instantiated plans)?  The answer is the attention plan's wo_can_merge (attn_plan.h).
+// Single-row decode with the context split 2 / 4 / 8 ways: no merge launch behind the attention kernel -- the wo GEMV forms the
+// merged row from the split partials while it stages it (qmv3.h, PRO_ATTN_MERGE).  Measured in round 3
+// (profiles/r03_labs/wo_merges_attn_ab_after_dpp.jsonl): 4 windows 1.023 -> 0.993 ms per token, 8 windows 1.033 -> 1.009 (the
+// merging GEMV costs +0.9 / +2.0 us per layer, the merge launch cost 0.6 us + a boundary); 64-token windows stay the best
+// (128-token windows: 1.022).  Other split counts, more sequences or another head size keep the merge launch.
+static bool wo_merge_applicable(const LinearCtx &ctx, const tl_w4 &wo, int batch, int n_splits, int head_dim, int num_heads) {
+    if (batch != 1 || ctx.force_linear != 0) return false;
+    if (n_splits != 2 && n_splits != 4 && n_splits != 8) return false;
+    if (head_dim != 128 || wo.cols != num_heads * 128 || ctx.tiled.count(wo.weight_dev) == 0) return false;
+    if (1 >= ctx.qmm3_min_rows && ctx.use_qmm3) return false;  // a single row would not take the GEMV
+    const Qmv3Plan pl = qmv3_plan(1, wo.cols, wo.rows);
+    const bool shape = (pl.KS == 2 && pl.CW == 4) || (pl.KS == 4 && pl.CW == 4) || (pl.KS == 8 && pl.CW == 8);
+    return pl.ok && pl.MR == 1 && shape && wo.cols / 8 <= 2 * pl.CW * 64;
+}
+
 // One projection of the decode step over `M` activation rows.  Up to 4 rows: the fused MFMA GEMV (weights streamed once,
 // RMSNorm / residual / SwiGLU inside).  5 .. 64 rows: the skinny matmul (qmm3.h) for every projection -- at 8 rows the GEMV
 // re-stages all rows in every workgroup (qkv 10.3 us against 4.8 + reduction; profiles/r02_labs/batched_rows_routing.log).  More rows, or option "qmm3" = 0: the

@@ -17,7 +17,7 @@
 #include "logit_process.h"
 #include "truncate.h"
 #include "grammar_stack.h"
-#include "attn_mfma.h"
+#include "decode_attention.h"  // the decode attention's launch; with it attn_plan.h and attn_mfma.h
 #include "aql.h"
 #include "prefix_cache.h"
 #include "kv_copy.h"
@@ -140,21 +140,11 @@ struct tl_engine {
     // do not run on the per-layer buffers below
     Act shared;
     uint16_t *q_t = nullptr, *attn_t = nullptr, *logits = nullptr;
-    int last_attn_launches = 0;
+    AttnCtx attn;  // what the decode attention reads (decode_attention.h): geometry, knobs, the slot state it walks, the arena's partials
     // lm_head GEMV of a 1-4-row decode step: per 16-logit tile (max, lowest index) pairs for step_end_kernel (qmv3.h tile_max);
     // tl_engine_set_option "lmhead_tile_max" = 0: step_end reads the logits row again
     f32x2 *lm_tile_max = nullptr;            // [VERIFY_MAX_LEN][vocab / 16]
     bool lm_tile_max_on = true;
-    // At 5 .. 64 decode rows the qkv projection's slice reduction is not launched; the decode-attention kernel adds the fp32 slice
-    // partials itself (engine_kernels.h, QP).  Measured in round 3 (profiles/r03_labs/batched_decode_status.jsonl): 5 / 8 / 16 / 64
-    // sequences 1.87 -> 1.81, 1.91 -> 1.89, 2.08 -> 2.03, 3.63 -> 3.52 ms per step.  tl_engine_set_option "attn_qkv_partials" = 0 launches the reduction.
-    bool attn_qkv_partials = true;
-    // Single-row decode with the context split 2 / 4 / 8 ways: no merge launch behind the attention kernel -- the wo GEMV forms the
-    // merged row from the split partials while it stages it (qmv3.h, PRO_ATTN_MERGE).  Measured in round 3
-    // (profiles/r03_labs/wo_merges_attn_ab_after_dpp.jsonl): 4 windows 1.023 -> 0.993 ms per token, 8 windows 1.033 -> 1.009 (the
-    // merging GEMV costs +0.9 / +2.0 us per layer, the merge launch cost 0.6 us + a boundary); 64-token windows stay the best
-    // (128-token windows: 1.022).  Other split counts, more sequences or another head size keep the merge launch (wo_merge_applicable).
-    bool wo_merges_attn = true;
     int32_t *verify_ids = nullptr;  // greedy ids of the rows of the last tl_engine_verify
     // tl_engine_verify_sampled: the per-row arrays of its one tl_spec_sample_rows launch (VERIFY_MAX_LEN rows), allocated by the first call
     struct SpecRecord {
@@ -170,16 +160,6 @@ struct tl_engine {
     };
     DeviceBlock spec_mem;
     SpecRecord *spec_rec = nullptr;
-    int attn_rq = 0;             // query heads per decode-attention workgroup; 0 = by context (TL_ATTN_RQ at create: 1 or 4)
-    int attn_rq1_ctx = 4096;     // contexts up to this many tokens use one query head per workgroup
-    int attn_rq1_batch = 2;      // ... and up to this many sequences; at 4 the re-read windows cost 261 vs 180 us
-    int attn_min_tokens = 64;    // tokens per attention workgroup before the context is split (TL_ATTN_MIN_TOKENS)
-    int attn_wg_cap = 0;         // most attention workgroups per launch; 0 = by sequences (pick_decode_splits)
-    bool attn_min_tokens_auto = true;  // ... or more, by context and sequences (pick_decode_splits)
-    bool attn_mfma = true;       // TL_ATTN_MFMA=0: the GQA-group walk on the VALU (attn_decode_fused_kernel), the A/B twin of attn_mfma.h
-    int attn_max_splits = 64;    // most context splits per sequence (TL_ATTN_MAX_SPLITS, a power of two <= 256)
-    int attn_max_splits_gqa = 32;  // ... when a workgroup takes a whole GQA group (TL_ATTN_MAX_SPLITS sets both)
-    size_t attn_ws_bytes = 0;
     int rows_cap = 0;
     int ring_cap = 4096;
 
@@ -248,7 +228,7 @@ struct tl_engine {
 
     bool warmed = false;
     // a captured decode step: the executable graph and, where the step may ride the AQL route (below), the same nodes as a program of
-    // dispatch packets.  Keyed by (batch, SplitPlan::key() | step_key_bits(features))
+    // dispatch packets.  Keyed by (batch, AttnPlan::key() | step_key_bits(features))
     struct DecodePlan {
         hipGraphExec_t exec = nullptr;
         std::unique_ptr<AqlProgram> program;
@@ -703,237 +683,6 @@ static void launch_logit_chain(tl_engine *e, const uint16_t *raw, int row0, int 
     if (f.stop) launch_stop(e, rows, slot0, pc);
 }
 
-// Context split of the decode attention: power-of-two bucket >= context, fixed windows of C tokens per workgroup.
-struct SplitPlan {
-    int n_splits, tokens_per_split;
-    int rq;  // query heads per workgroup
-    long key() const { return ((long)rq << 40) | ((long)n_splits << 24) | (long)tokens_per_split; }
-};
-// Measured on MI355X (profiles/README.md, profiles/r02_labs): a decode-attention workgroup is bound by its dependent latency
-// chain and by how many L2 misses ONE CU keeps in flight (~32 KiB), not by chip bandwidth.  Few sequences and short
-// contexts: one query head and a 64-token window (32 KiB of K/V) per workgroup, partials merged by the wo GEMV (2 / 4 / 8
-// windows of one sequence) or by a second launch.  Many sequences or long contexts: one workgroup per GQA group walking 64-token
-// stages, so that the K/V window is read from HBM once.  (A "wide" one-head kernel -- the whole 64..512-token window in one
-// workgroup, no merge -- was built in round 2, lost on every context it was meant for (8.2 us per layer against 2.9 + 1.3) and was
-// removed in round 3 together with the last-arriver in-kernel merge, which measured neutral.)
-// the attention plan's lab knobs (environment, read when an engine -- or the standalone operator's stand-in for one -- is set up)
-static void read_attention_knobs(tl_engine *e) {
-    if (const char *q = getenv("TL_ATTN_MFMA")) e->attn_mfma = atoi(q) != 0;
-    if (const char *q = getenv("TL_ATTN_RQ")) e->attn_rq = atoi(q) <= 0 ? 0 : (atoi(q) == 1 ? 1 : AD_RQ);
-    if (const char *q = getenv("TL_ATTN_MAX_SPLITS")) e->attn_max_splits = e->attn_max_splits_gqa = std::min(256, std::max(1, atoi(q)));
-    if (const char *q = getenv("TL_ATTN_MIN_TOKENS")) e->attn_min_tokens = std::max(64, atoi(q)), e->attn_min_tokens_auto = false;
-}
-static SplitPlan pick_decode_splits(const tl_engine *e, int batch, int max_ctx) {
-    const int rep = e->cfg.num_heads / e->cfg.num_kv_heads;
-    int rq = e->attn_rq;
-    // two sequences re-read twice the windows: the GQA-group walk takes over at a quarter of the context (round 3, 2 sequences at 1,500 tokens
-    // one head per workgroup 1.326 against 1.383 ms per step, at 3,000 tokens 1.527 against 1.465)
-    // (round 4, with the group walk on the matrix cores: 2 sequences at 1,500 tokens 1.46 -> 1.38 ms per step, at 700 a tie; one sequence
-    // at 700 / 1,500 / 3,000 tokens 1.05 / 1.11 / 1.24 for one head per workgroup against 1.13 / 1.21 / 1.24)
-    if (rq <= 0) rq = (max_ctx <= (batch <= 1 ? e->attn_rq1_ctx : e->attn_rq1_ctx / 4) && batch <= e->attn_rq1_batch) ? 1 : AD_RQ;
-    if (rq != 1) rq = AD_RQ;
-    int bucket = 64;
-    while (bucket < max_ctx) bucket *= 2;
-    const int chunks = (rep + rq - 1) / rq;
-    const int base = std::max(1, batch * e->cfg.num_kv_heads * chunks);
-    int s = 1;
-    // Windows grow with the context (round 3, tools/decode_ab.py; profiles/r03_labs/attention_window_size_*.jsonl).  Up to 512 tokens of
-    // context 64-token windows are the best at 1-4 sequences (one sequence at 200 tokens: 128-token windows 1.022 against 0.993 ms).
-    // Beyond, 256-token windows: one sequence 700 / 1,500 / 3,000 tokens 1.078 -> 1.060, 1.218 -> 1.143, 1.386 -> 1.246 ms per step (the wo
-    // GEMV still merges the 4 / 8 windows up to 2k tokens, 16 stand where 64 stood at 4k), two sequences 1.310 -> 1.245, 1.510 -> 1.361,
-    // 1.666 -> 1.540, four sequences at 1,000 tokens 1.762 -> 1.610.  Two exceptions at 257..512 tokens, both measured: one sequence
-    // 128-token windows (4 instead of 8 partials for the wo GEMV: 1.018 -> 1.014), 5-8 sequences 128 (1.882 -> 1.824 at 8).
-    // TL_ATTN_MIN_TOKENS pins one size (lab).
-    // Batched steps (5+ sequences) up to 1,024 tokens of context, re-measured at the end of round 6 on the round's kernels (matrix-core walk, shared prologue;
-    // tools/lab/ab_attn_splits_batched.sh, profiles/r06_labs/README.md section 9): ONE workgroup per CU at most and windows of 128+ tokens -- the merge launch
-    // and the second dependent trip of a short window cost more than a longer walk once every sequence's KV head has a workgroup: 5 / 8 / 12 / 16 / 23 sequences
-    // at ~600 tokens 1.47 / 1.52 / 1.56 / 1.59 / 2.04 -> 1.39 / 1.42 / 1.53 / 1.57 / 1.87 ms per step, 9-23 at ~300 tokens -3 ... -6 %.
-    const bool batched_short = e->attn_min_tokens_auto && batch >= 5 && bucket <= 1024;
-    int min_tokens = e->attn_min_tokens;
-    if (e->attn_min_tokens_auto) {
-        if (bucket > 512 && batch <= 4) min_tokens = 256;
-        else if (bucket == 512 && batch == 1) min_tokens = 128;
-        else if (batched_short) min_tokens = 128;
-    }
-    // few sequences: split for latency (up to 2048 short-lived workgroups); many sequences: the chip is already full, longer
-    // windows amortise the per-workgroup prologue and skip the merge launch (measured at 16 and 64 sequences)
-    // (5-7 sequences beyond 1,024 tokens too: 4 windows on 160-224 workgroups against 8 on 320-448 -- 5 / 6 / 7 sequences at 2,000 tokens 1.64 / 1.67 / 1.71 ->
-    // 1.57 / 1.63 / 1.70 ms per step, at 8,000 2.45 / 2.57 / 2.65 -> 2.26 / 2.43 / 2.62; 8 and 16 sequences keep 512: 8 x 4,000 2.11 against 2.19)
-    // (... and 8-16 sequences, the round's last sweep at 1,500 / 3,000 / 6,000 tokens: 10 sequences 1.80 / 2.17 / 2.96 -> 1.72 / 2.03 / 2.74 ms per step, 12: 1.85 / 2.27 / 3.08 ->
-    // 1.78 / 2.15 / 3.00, 14: -2 %, 8 and 16 within 1 % either way; from 17 sequences no split at all, below)
-    const bool few_long = e->attn_min_tokens_auto && batch >= 5 && batch <= 16 && bucket > 1024;
-    // (2-4 sequences on the GQA-group walk likewise, end of round 6: one workgroup per CU -- 3 / 4 sequences at 4,500 tokens 1.80 / 1.97 -> 1.66 / 1.81 ms per step,
-    // at 8,000 2.02 / 2.29 -> 1.86 / 2.10, two sequences at 4,500 / 8,000 1.42 / 1.59 -> 1.36 / 1.55, 4 x 32,000 4.55 -> 4.41; one sequence: 8 KV heads x 32 windows already)
-    const bool few_gqa = e->attn_min_tokens_auto && batch >= 2 && batch <= 4 && rq == AD_RQ;
-    const int wg_cap = e->attn_wg_cap > 0 ? e->attn_wg_cap : (batch <= 4 ? (few_gqa ? 256 : 2048) : ((batched_short || few_long) ? 256 : 512));
-    // a whole GQA group per workgroup (long contexts / several sequences): at most 32 windows -- one workgroup per CU for one sequence;
-    // measured at 8k 666 -> 680 tok/s against 64 windows, 32k unchanged (round 3)
-    int max_splits = rq == AD_RQ ? e->attn_max_splits_gqa : e->attn_max_splits;
-    // (64 windows = two workgroups per CU for the matrix-core walk at 32k: 1.931 / 1.896 -> 1.898 / 1.866 ms per step in one same-box
-    // A/B, 1.874 -> 1.891 in the next: within the noise, not taken)
-    // Many sequences at short contexts: one window per sequence and NO merge launch (round 4, same-box A/B at ~190 / ~660 tokens,
-    // profiles/r04_labs/README.md): 12 / 16 sequences 1.623 -> 1.603 / 1.661 -> 1.634 ms per step at ~190 tokens (at ~660 the split stays:
-    // 16 sequences 1.885 against 2.000), 24 / 32 sequences 2.15 -> 2.03 / 2.215 -> 2.07 at ~190 and 32 sequences 2.56 -> 2.495 at ~660.
-    // The merge launch and its boundary cost ~2.5 us per layer; the unsplit walk of a few stages costs less once every CU has a workgroup.
-    // (from 5 sequences at up to 256 tokens since the end of round 6: 5 / 7 / 9 / 10 sequences at ~150 tokens 1.30 / 1.35 / 1.44 / 1.45 -> 1.26 / 1.28 / 1.31 / 1.33 ms per step)
-    // (from 17 sequences up to 8,192 tokens too, end of round 6: 160+ workgroups walking whole contexts beat twice as many on halves + a merge launch -- 20 / 23 / 24 / 32
-    // sequences at 1,500 tokens 2.49 / 2.56 / 2.63 / 2.82 -> 2.25 / 2.36 / 2.40 / 2.70 ms per step, 24 at 2,500 / 4,000 / 8,000 3.10 / 4.20 / 6.44 -> 2.91 / 3.98 / 6.12;
-    // 16 sequences at 2,000 want their 4 windows: 2.16 against 2.29)
-    if (e->attn_min_tokens_auto && ((batch >= 24 && bucket <= 1024) || (batch >= 5 && bucket <= 256) || (batch >= 17 && bucket <= 8192))) max_splits = 1;  // (17-19 sequences measured last: 1,500 / 3,000 / 6,000 tokens 2.44 / 3.19 / 4.85 -> 2.20 / 2.87 / 4.13 ms per step)
-    while (s * 2 <= bucket / min_tokens && s * 2 * base <= wg_cap && s * 2 <= max_splits) s *= 2;  // >= min_tokens per workgroup
-    // Windows sized to the context, not to its power-of-two bucket: a workgroup walks its whole window in 64-token stages
-    // whether or not the tokens exist, so a 33k context on a 64k bucket spent half of every window on masked loads (r02:
-    // 63 us per layer in the step against 44 us for the same kernel on an exactly filled bucket).  The split COUNT stays a
-    // power of two (the kernels decode blockIdx with shifts); the plan (and its captured graph) changes every 64 * s tokens.
-    const int per_split = ((max_ctx + s - 1) / s + 63) / 64 * 64;
-    return SplitPlan{s, std::max(64, std::min(per_split, bucket / s)), rq};
-}
-
-// head_dim 128 with a whole GQA group per workgroup is the only shape that takes qkv slice partials (batched decode of 5+ rows)
-static bool attn_takes_qkv_partials(int head_dim, int rq) { return head_dim == 128 && rq == AD_RQ; }
-template <int VD, bool SP, bool IP = false>
-static void launch_attn_decode_sp(const AttnDecodeArgs &a, dim3 grid, hipStream_t st, int rq) {
-    const size_t lds = (size_t)16 * rq * (16 * VD + 2) * sizeof(float);
-    if constexpr (VD == 8) {
-        if (a.key_scales != nullptr) {  // FP8 pages (kv8.h)
-            if (a.qkv_partial != nullptr && rq == AD_RQ) {
-                const size_t staged = (size_t)(2 + AD_RQ) * 16 * VD * sizeof(uint16_t);
-                hipLaunchKernelGGL((attn_decode_fused_kernel<VD, 4, AD_RQ, SP, IP, true, true>), grid, dim3(256), lds + staged, st, a);
-            } else if (rq == 1) hipLaunchKernelGGL((attn_decode_fused_kernel<VD, 4, 1, SP, IP, false, true>), grid, dim3(256), lds, st, a);
-            else hipLaunchKernelGGL((attn_decode_fused_kernel<VD, 4, AD_RQ, SP, IP, false, true>), grid, dim3(256), lds, st, a);
-            return;
-        }
-        if (a.qkv_partial != nullptr && rq == AD_RQ) {
-            const size_t staged = (size_t)(2 + AD_RQ) * 16 * VD * sizeof(uint16_t);
-            hipLaunchKernelGGL((attn_decode_fused_kernel<VD, 4, AD_RQ, SP, IP, true>), grid, dim3(256), lds + staged, st, a);
-            return;
-        }
-    }
-    if (rq == 1) hipLaunchKernelGGL((attn_decode_fused_kernel<VD, 4, 1, SP, IP>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((attn_decode_fused_kernel<VD, 4, AD_RQ, SP, IP>), grid, dim3(256), lds, st, a);
-}
-template <int VD>
-static void launch_attn_decode(const AttnDecodeArgs &a, dim3 grid, hipStream_t st, int rq, bool mfma) {
-    if constexpr (VD == 8) {
-        // a whole GQA group per workgroup: the walk on the matrix cores (attn_mfma.h) from 128-token windows -- a stage is 4 waves x 32
-        // tokens, and on 64-token windows half of the waves idle (round 4, same-box A/B: 4 / 8 sequences at ~230 tokens 1.445 / 1.539
-        // against 1.416 / 1.527 ms per step for the VALU walk; 4 sequences at 2k 1.691 against 1.729, one at 8k / 32k 1.256 / 1.90
-        // against 1.35 / 2.13)
-        if (mfma && a.tokens_per_split >= 128 && attn_decode_mfma_applicable(a, 16 * VD, rq)) {
-            launch_attn_decode_mfma(a, grid, st);
-            return;
-        }
-    }
-    const bool single_page = a.tokens_per_split <= a.page_size && a.page_size % a.tokens_per_split == 0;
-    // every 64-token stage of a window inside one page: windows are multiples of 64 tokens, pages a power of two >= 64
-    const bool stage_page = !single_page && a.page_shift >= 6 && a.tokens_per_split % 64 == 0;
-    if (single_page) launch_attn_decode_sp<VD, true>(a, grid, st, rq);
-    else if (stage_page) launch_attn_decode_sp<VD, false, true>(a, grid, st, rq);
-    else launch_attn_decode_sp<VD, false>(a, grid, st, rq);
-}
-
-// Can the wo GEMV of ONE decode row take the attention split partials instead of the merged row (qmv3.hip,
-// launch_qmv3_attn_merge_bf16: the instantiated plans)?
-static bool wo_merge_applicable(const tl_engine *e, const tl_w4 &wo, int batch, const SplitPlan &sp) {
-    if (!e->wo_merges_attn || batch != 1 || e->lin.force_linear != 0) return false;
-    if (sp.n_splits != 2 && sp.n_splits != 4 && sp.n_splits != 8) return false;
-    if (e->cfg.head_dim != 128 || wo.cols != e->cfg.num_heads * 128 || e->lin.tiled.count(wo.weight_dev) == 0) return false;
-    if (1 >= e->lin.qmm3_min_rows && e->lin.use_qmm3) return false;  // a single row would not take the GEMV
-    const Qmv3Plan pl = qmv3_plan(1, wo.cols, wo.rows);
-    const bool shape = (pl.KS == 2 && pl.CW == 4) || (pl.KS == 4 && pl.CW == 4) || (pl.KS == 8 && pl.CW == 8);
-    return pl.ok && pl.MR == 1 && shape && wo.cols / 8 <= 2 * pl.CW * 64;
-}
-
-// One layer's decode attention: qkv [batch, (Hq + 2 Hkv) D] -> out [batch, Hq D] over slots [0, batch), split partials in ws.
-struct AttnCall {
-    const uint16_t *qkv = nullptr;
-    const void *q_norm = nullptr, *k_norm = nullptr;
-    uint16_t *key_pages = nullptr, *value_pages = nullptr;
-    float *key_scales = nullptr, *value_scales = nullptr;  // FP8 pages (kv8.h)
-    uint16_t *out = nullptr;
-    float *ws = nullptr;
-    KeptPartials qkv_parts;                   // where the qkv projection left its slice planes: the kernel adds them itself
-    const tl_w4 *merging_wo = nullptr;        // the wo projection behind it, where its GEMV may merge the split partials (wo_merge_applicable)
-};
-// q/k-norm + RoPE + KV append + decode attention of one layer (+ the merge launch when the context is split and *merge_left stays false)
-static int engine_attention(tl_engine *e, const AttnCall &t, int batch, const SplitPlan &sp, ProfCtx *pc, bool *merge_left = nullptr) {
-    if (merge_left) *merge_left = false;
-    const tl_engine_config &c = e->cfg;
-    const int D = c.head_dim;
-    const int n_splits = sp.n_splits;
-    const int rep = c.num_heads / c.num_kv_heads;
-    const int chunks = (rep + sp.rq - 1) / sp.rq;
-    AttnDecodeArgs a{};
-    a.qkv = t.qkv;
-    a.q_norm_w = (const uint16_t *)t.q_norm;
-    a.k_norm_w = (const uint16_t *)t.k_norm;
-    a.key_pages = t.key_pages;
-    a.value_pages = t.value_pages;
-    a.key_scales = t.key_scales;
-    a.value_scales = t.value_scales;
-    TL_REQUIRE(t.key_scales == nullptr || D == 128, "engine: FP8 pages need head_dim 128");
-    a.block_table = e->block_table;
-    a.context_lens = e->context_lens;
-    a.out = t.out;
-    a.ws = t.ws;
-    a.page_size = c.page_size;
-    a.max_pages = c.max_pages_per_seq;
-    a.num_heads = c.num_heads;
-    a.num_kv_heads = c.num_kv_heads;
-    a.scale = 1.0f / sqrtf((float)D);
-    a.eps = c.rms_norm_eps;
-    a.rope_base = c.rope_theta;
-    a.n_splits = n_splits;
-    a.n_row_chunks = chunks;
-    a.tokens_per_split = sp.tokens_per_split;
-    a.split_shift = 0;
-    while ((1 << a.split_shift) < n_splits) ++a.split_shift;
-    a.rep = rep;
-    a.page_shift = -1;
-    for (int sh = 0; sh < 30; ++sh)
-        if ((1 << sh) == c.page_size) a.page_shift = sh;
-    a.rope_cur = e->rope_cur;
-    a.prof = pc ? pc->buf : nullptr;
-    if (t.qkv_parts.partial) {
-        TL_REQUIRE(attn_takes_qkv_partials(D, sp.rq), "engine: this decode-attention plan does not read qkv slice partials");
-        a.qkv_partial = t.qkv_parts.partial;
-        a.qkv_slices = t.qkv_parts.slices;
-        a.qkv_plane = t.qkv_parts.plane;
-    }
-    TL_REQUIRE((size_t)batch * c.num_heads * n_splits * (D + ATTN_WS_PAD) * sizeof(float) <= e->attn_ws_bytes || n_splits == 1,
-               "engine: attention workspace too small for this split plan");
-    const dim3 grid(n_splits * chunks, c.num_kv_heads, batch);
-    switch (D) {
-        case 128: launch_attn_decode<8>(a, grid, e->stream, sp.rq, e->attn_mfma); break;
-        case 64: launch_attn_decode<4>(a, grid, e->stream, sp.rq, false); break;
-        case 32: launch_attn_decode<2>(a, grid, e->stream, sp.rq, false); break;
-        default: return fail(TL_ERR_UNSUPPORTED, "engine: head_dim must be 32, 64 or 128");
-    }
-    if (pc) prof_after(pc, 5, (int)(grid.x * grid.y * grid.z));
-    // the consumer (the wo GEMV of a single row) merges the partials itself: no merge launch, `out` is not written
-    const bool leave_merge = t.merging_wo != nullptr && merge_left != nullptr && wo_merge_applicable(e, *t.merging_wo, batch, sp);
-    if (leave_merge) *merge_left = true;
-    e->last_attn_launches = 1 + ((n_splits > 1 && !leave_merge) ? 1 : 0);
-    if (n_splits > 1 && !leave_merge) {
-        const dim3 mg(batch * c.num_heads), mb(128);
-        prof_t *pb = pc ? pc->buf : nullptr;
-        int merge_wg = batch * c.num_heads;
-        switch (n_splits) {
-            case 2: hipLaunchKernelGGL(attn_merge_kernel<2>, mg, mb, 0, e->stream, t.ws, t.out, D, pb); break;
-            case 4: hipLaunchKernelGGL(attn_merge_kernel<4>, mg, mb, 0, e->stream, t.ws, t.out, D, pb); break;
-            case 8: hipLaunchKernelGGL(attn_merge_kernel<8>, mg, mb, 0, e->stream, t.ws, t.out, D, pb); break;
-            default:  // 16 and more splits: a row's partials spread over D / 32 workgroups x 8 split groups
-                merge_wg *= (D + 31) / 32;
-                hipLaunchKernelGGL(attn_merge_cols_kernel, dim3(batch * c.num_heads, (D + 31) / 32), dim3(256), 0, e->stream, t.ws,
-                                   t.out, D, n_splits, pb);
-                break;
-        }
-        if (pc) prof_after(pc, 6, merge_wg);
-    }
-    TL_CHECK_LAUNCH("engine attention");
-    return TL_OK;
-}
-
 // The MLP of a Qwen3-MoE layer over `rows` activation rows: xn = RMSNorm(h) is given; out = h + sum_j score_j * expert_j(xn)
 // (reference: moe.py:69-89 inside qwen3_week3.py:204-205).  Every launch reads device-resident ids: graph-capturable.
 static int engine_moe_mlp(tl_engine *e, int l, const uint16_t *xn, const uint16_t *h, uint16_t *out, int rows, ProfCtx *pc) {
@@ -965,12 +714,12 @@ struct StepRoute {
     // or the rows of the batched-matmul step (5 .. 64) when every layer hands over inside its own buffers and slice planes (per_layer_b)
     bool per_layer = false, per_layer_b = false;
 };
-static StepRoute plan_step(const tl_engine *e, int batch, const SplitPlan &sp) {
+static StepRoute plan_step(const tl_engine *e, int batch, const AttnPlan &sp) {
     const LinearCtx &ctx = e->lin;
     StepRoute s;
     s.frag = rows_travel_in_fragment_order(ctx, e->layers[0], batch);
     s.head6 = qmm6_takes(ctx, e->head(), batch);
-    const bool ws_fits = sp.n_splits == 1 || (size_t)batch * e->cfg.num_heads * sp.n_splits * (e->cfg.head_dim + ATTN_WS_PAD) * sizeof(float) <= e->layer_ws_bytes;
+    const bool ws_fits = sp.n_splits == 1 || sp.partials_bytes(batch) <= e->layer_ws_bytes;
     const bool own_buffers = e->layer_act_rows > 0 && batch <= e->layer_act_rows && ws_fits;
     s.per_layer = own_buffers && gemv_takes_rows(ctx, batch);
     s.per_layer_b = own_buffers && !gemv_takes_rows(ctx, batch) && ctx.force_linear == 0 && s.head6;
@@ -983,7 +732,8 @@ static StepRoute plan_step(const tl_engine *e, int batch, const SplitPlan &sp) {
 }
 
 // One fused decode step over slots [0, batch); `f`: step_features(e, 0, batch).
-static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, const StepFeatures &f, ProfCtx *pc = nullptr) {
+// `sp`: the step's attention plan (prepare_step); every layer completes it with what its own projections hand over (plan_decode_launch)
+static int enqueue_step(tl_engine *e, int batch, const AttnPlan &sp, const StepFeatures &f, ProfCtx *pc = nullptr) {
     const tl_engine_config &c = e->cfg;
     LinearCtx &ctx = e->lin;
     StepRoute route = plan_step(e, batch, sp);
@@ -1031,7 +781,7 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, const StepFeature
         } else {
             Proj p = proj(w.wqkv, x_cur, b.qkv, batch);
             p.pro = PRO_RMSNORM, p.norm_w = w.input_norm_dev, p.ss_in = x_ss ? ssx_cur : nullptr, p.ss_in_n = x_ss;
-            p.keep = !lora && e->attn_qkv_partials && attn_takes_qkv_partials(c.head_dim, sp.rq);
+            p.keep = !lora && e->attn.knobs.qkv_partials && attn_takes_qkv_partials(c.head_dim, sp.rq);
             TL_TRY(engine_linear(ctx, p, pc, &r));
         }
         if (lora) TL_TRY(lora_group(e, l, tl_engine::LORA_QKV, e->lora_tiles_decode, lora_tiles, batch, x_cur, w.input_norm_dev, TL_LORA_ADD, nullptr, b.qkv));
@@ -1039,9 +789,11 @@ static int enqueue_step(tl_engine *e, int batch, SplitPlan sp, const StepFeature
         AttnCall at{};
         at.qkv = b.qkv, at.q_norm = w.q_norm_dev, at.k_norm = w.k_norm_dev, at.key_pages = e->layer_k(l), at.value_pages = e->layer_v(l);
         at.key_scales = e->layer_ks(l), at.value_scales = e->layer_vs(l), at.out = b.attn, at.ws = b.attn_ws;
-        at.qkv_parts = r.kept, at.merging_wo = lora ? nullptr : &w.wo;
-        bool merge_left = false;  // the wo GEMV of one row merges the attention windows itself where engine_attention leaves them to it
-        TL_TRY(engine_attention(e, at, batch, sp, pc, &merge_left));
+        at.qkv_parts = r.kept;
+        const bool wo_can_merge = !lora && wo_merge_applicable(ctx, w.wo, batch, sp.n_splits, c.head_dim, c.num_heads);
+        const AttnPlan ap = plan_decode_launch(sp, e->attn.geometry, e->attn.knobs, sp.kv8, r.kept.partial != nullptr, wo_can_merge);
+        TL_TRY(launch_decode_attention(e->attn, ap, at, batch, pc));
+        const bool merge_left = ap.wo_merges();  // the wo GEMV of one row merges the attention windows itself where the plan leaves them to it
         TL_REQUIRE(!(batched && merge_left), "engine: a batched step left its attention windows unmerged");
         if (lora) TL_TRY(lora_group(e, l, tl_engine::LORA_O, e->lora_tiles_decode, lora_tiles, batch, b.attn, nullptr, TL_LORA_RESIDUAL_PRE, x_cur, e->lora_tmp));
         Proj po = proj(w.wo, b.attn, b.h, batch);
@@ -1191,7 +943,7 @@ static_assert(tl_engine::VerifyScratch::DESC_ARRAYS == VERIFY_DESC_ARRAYS, "the 
 // what the layouts ask of the device headers and of the engine as it stands (matmul_ws_need: verify_alloc's own)
 static LayoutInputs layout_inputs(const tl_engine *e) {
     LayoutInputs in;
-    in.attn_ws_bytes = e->attn_ws_bytes, in.attn_ws_pad = ATTN_WS_PAD, in.qm3_ss = QM3_SS;
+    in.attn_ws_bytes = e->attn.ws_bytes, in.attn_ws_pad = ATTN_WS_PAD, in.qm3_ss = QM3_SS;
     in.plane_bytes[0] = e->layer_plane_bytes[0], in.plane_bytes[1] = e->layer_plane_bytes[1];
     in.matmul_ws_engine = e->lin.splitk_ws_bytes, in.aql = e->aql_on, in.ring_cap = e->ring_cap, in.tile_max_bytes = sizeof(f32x2);
     in.verify_ws_rows = verify_ws_rows(e->cfg.num_heads), in.verify_head_dim = VA_D, in.verify_result_bytes = sizeof(tl_verify_result);
@@ -1287,7 +1039,7 @@ static int create_rope_tables(tl_engine *e) {
                        (int)max_pos, half, c.rope_theta);
     if (hipGetLastError() != hipSuccess) return fail(TL_ERR_HIP, "engine_create: rope table kernel failed");
     TL_TRY(e->rope_cur_mem.alloc((size_t)c.max_batch * half * sizeof(float2), "engine_create: hipMalloc(rope state) failed"));
-    e->rope_cur = e->rope_cur_mem.at<float2>();
+    e->rope_cur = e->rope_cur_mem.at<float2>(), e->attn.rope_cur = e->rope_cur;
     if (hipMemsetAsync(e->rope_cur, 0, (size_t)c.max_batch * half * sizeof(float2), e->stream) != hipSuccess)
         return fail(TL_ERR_HIP, "engine_create: hipMalloc(rope state) failed");
     return TL_OK;
@@ -1393,13 +1145,14 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     e->rows_cap = prefill_rows(c);
 
     // ---- the arena (engine_layout.h): its attention partials first -- decode (batch*Hq rows x 64 splits) or the L<=8 operator path during
-    // short prefills; decode partials: at most 64 splits per row with many sequences, at most 256 split-rows per head with few (pick_decode_splits)
-    const size_t ws_row = (size_t)c.head_dim + ATTN_WS_PAD;
-    e->attn_ws_bytes = std::max((size_t)std::max(c.max_batch * 64, 4 * 256) * c.num_heads * ws_row * 4, (size_t)c.num_heads * 8 * 64 * ws_row * 4);
+    // short prefills (the decode partials: attn_plan.h, attn_partials_capacity)
+    e->attn.geometry = AttnGeometry{c.num_heads, c.num_kv_heads, c.head_dim, c.page_size, c.max_pages_per_seq};
+    e->attn.eps = c.rms_norm_eps, e->attn.rope_theta = c.rope_theta, e->attn.stream = e->stream;
+    e->attn.ws_bytes = attn_partials_capacity(e->attn.geometry, c.max_batch);
     for (int L = 1; L <= c.max_prefill_rows; ++L)  // the paged attention operator may split the context for any chunk length
-        e->attn_ws_bytes = std::max(e->attn_ws_bytes, tl_paged_attention_workspace_bytes(c.num_heads, L, c.head_dim, c.page_size,
-                                                                                         c.max_pages_per_seq, c.num_heads,
-                                                                                         c.num_kv_heads, 0));
+        e->attn.ws_bytes = std::max(e->attn.ws_bytes, tl_paged_attention_workspace_bytes(c.num_heads, L, c.head_dim, c.page_size,
+                                                                                       c.max_pages_per_seq, c.num_heads,
+                                                                                       c.num_kv_heads, 0));
     const ArenaLayout al = arena_layout(c, layout_inputs(e));
     e->arena_bytes = al.bytes, e->arena_act_off = al.act_off;
 
@@ -1413,6 +1166,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
         using A = ArenaLayout;
         char *m = e->arena.at();
         e->block_table = piece_at<int32_t>(m, al[A::BLOCK_TABLE]), e->context_lens = piece_at<int32_t>(m, al[A::CONTEXT_LENS]);
+        e->attn.block_table = e->block_table, e->attn.context_lens = e->context_lens;
         e->tokens = piece_at<int32_t>(m, al[A::TOKENS]), e->live = piece_at<int32_t>(m, al[A::LIVE]), e->produced = piece_at<int32_t>(m, al[A::PRODUCED]);
         e->ring = piece_at<int32_t>(m, al[A::RING]), e->scratch_ctx = piece_at<int32_t>(m, al[A::SCRATCH_CTX]);
         e->prefill_tokens = piece_at<int32_t>(m, al[A::PREFILL_TOKENS]);
@@ -1423,7 +1177,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     }
     e->lin.stream = e->stream, e->lin.rms_norm_eps = c.rms_norm_eps;
     e->lin.read_env();
-    read_attention_knobs(e);
+    e->attn.knobs.read_env();
     // Decode steps replay as AQL packets on the engine's own HSA queue (aql.h) unless TL_AQL=0: the same captured step, without the
     // cache maintenance HIP puts between its launches (0.987 -> 0.929 ms per token at Qwen3-4B, logits bit-identical).  Where the route is
     // not available (no code objects next to the library, no HSA agent for the device) the engine stays on hipGraphLaunch and says why
@@ -1544,7 +1298,7 @@ extern "C" int tl_engine_set_option(tl_engine *e, const char *name, int value) {
     if (n == "qmm3") e->lin.use_qmm3 = on;
     else if (n == "qmm6") e->lin.use_qmm6 = on;
     else if (n == "qmm7") e->lin.use_qmm7 = on;
-    else if (n == "attn_qkv_partials") e->attn_qkv_partials = on;
+    else if (n == "attn_qkv_partials") e->attn.knobs.qkv_partials = on;
     else if (n == "lmhead_tile_max") e->lm_tile_max_on = on;
     else if (n == "gemm_fused_epilogue") e->lin.gemm_fused_epilogue = on;
     else if (n == "gemm8") e->lin.use_gemm8 = on;
@@ -2660,9 +2414,9 @@ static int engine_paged_attention(tl_engine *e, int l, const uint16_t *q_t, cons
     if (e->kv_format == TL_KV_FP8_E4M3)
         return tl_paged_attention_fp8(q_t, e->layer_k(l), e->layer_ks(l), e->layer_v(l), e->layer_vs(l), block_row, ctx_dev, attn_t, Hq, n, D,
                                       c.num_pages, c.page_size, c.max_pages_per_seq, Hq, Hkv, 1.0f / sqrtf((float)D), 1, ctx_hint, e->shared.attn_ws,
-                                      e->attn_ws_bytes, e->stream);
+                                      e->attn.ws_bytes, e->stream);
     return tl_paged_attention(q_t, e->layer_k(l), e->layer_v(l), block_row, ctx_dev, attn_t, Hq, n, D, c.num_pages, c.page_size,
-                              c.max_pages_per_seq, Hq, Hkv, 1.0f / sqrtf((float)D), 1, ctx_hint, TL_BF16, e->shared.attn_ws, e->attn_ws_bytes, e->stream);
+                              c.max_pages_per_seq, Hq, Hkv, 1.0f / sqrtf((float)D), 1, ctx_hint, TL_BF16, e->shared.attn_ws, e->attn.ws_bytes, e->stream);
 }
 static void launch_qkv_post(tl_engine *e, int l, QkvPostArgs &q, int n) {
     q.key_scales = e->layer_ks(l);
@@ -2717,7 +2471,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
                                   total, c.hidden_size, c.vocab_size, 128, 4, TL_BF16, e->stream));
     for (int i = 0; i < n_seqs; ++i)
         TL_REQUIRE(tl_paged_attention_workspace_bytes(Hq, seqs[i].len, D, c.page_size, c.max_pages_per_seq, Hq, Hkv, seqs[i].start + seqs[i].len) <=
-                       e->attn_ws_bytes, std::string(packed ? "engine_prefill_packed" : "engine_prefill") + ": attention workspace too small");
+                       e->attn.ws_bytes, std::string(packed ? "engine_prefill_packed" : "engine_prefill") + ": attention workspace too small");
     // a pass in which some sequence carries a LoRA adapter (lora.h): tiles of 16 rows that never straddle two sequences, written here;
     // lora_on(l, g): some sequence's adapter adapts group g of layer l -- the shrink / expand launches run around that projection
     int lora_tiles = 0;
@@ -3327,7 +3081,7 @@ static void launch_embed_slots(tl_engine *e, int batch) {
 // the pages of this step's token in every live slot of [0, batch), poked into the block table, and the step's split plan.  A caller with
 // steps in flight on the AQL queue passes `on_queue`: a new page id drains them first (the poke is a stream launch and must land between
 // the steps), and a failed reservation returns with the queue drained.
-static int prepare_step(tl_engine *e, int batch, SplitPlan *sp, bool *on_queue = nullptr) {
+static int prepare_step(tl_engine *e, int batch, AttnPlan *sp, bool *on_queue = nullptr) {
     SlotEdits &ed = e->step_edits;  // (reused: a step in which no slot crosses a page boundary allocates nothing)
     ed.clear();
     int max_ctx = 1;
@@ -3345,7 +3099,7 @@ static int prepare_step(tl_engine *e, int batch, SplitPlan *sp, bool *on_queue =
         TL_TRY(apply_edits(e, ed, pk));
         TL_TRY(poke(e, pk));
     }
-    *sp = pick_decode_splits(e, batch, max_ctx);
+    *sp = e->attn.plan(batch, max_ctx, e->kv_format == TL_KV_FP8_E4M3);
     return TL_OK;
 }
 
@@ -3376,7 +3130,7 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
     if (f.stop) e->stop_dirty = true;  // (a replayed plan launches the stop check without passing through launch_stop)
     bool on_queue = false;  // steps of this call are in flight on the AQL queue (the stream is idle and must stay so until they are drained)
     for (int s = 0; s < steps; ++s) {
-        SplitPlan sp;
+        AttnPlan sp;
         TL_TRY(prepare_step(e, batch, &sp, &on_queue));
         if (use_graph && e->warmed) {
             const auto key = std::make_pair(batch, sp.key() | step_key_bits(f));
@@ -3518,7 +3272,7 @@ extern "C" int tl_engine_profile_step(tl_engine *e, int batch, tl_step_profile *
     ProfCtx pc;
     if (!pc.alloc(e->cfg, batch, e->stream)) return fail(TL_ERR_HIP, "engine_profile_step: hipMalloc / memset of the stamp buffers failed");
     launch_embed_slots(e, batch);
-    SplitPlan sp;
+    AttnPlan sp;
     int rc = prepare_step(e, batch, &sp);
     if (rc == TL_OK) rc = enqueue_step(e, batch, sp, step_features(e, 0, batch), &pc);
     if (rc != TL_OK) {
@@ -3601,7 +3355,7 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
         if (ck.bytes[rg]) ok = hipMemcpyAsync(ck.shadow[rg], ck.region[rg], ck.bytes[rg], hipMemcpyDeviceToDevice, e->stream) == hipSuccess &&
                                hipMemsetAsync(ck.written[rg], 0, ck.bytes[rg] / 2, e->stream) == hipSuccess;
     if (!ok) return fail(TL_ERR_HIP, "engine_check_step: shadow copy failed");
-    SplitPlan sp;
+    AttnPlan sp;
     int rc = prepare_step(e, batch, &sp);
     if (rc == TL_OK) {
         pc.check = &ck;
@@ -3670,8 +3424,7 @@ __global__ __launch_bounds__(64) void rope_rows_kernel(const int32_t *__restrict
 
 extern "C" size_t tl_decode_attention_fused_workspace_bytes(int batch, int num_heads, int head_dim) {
     if (batch <= 0 || num_heads <= 0 || head_dim <= 0) return 0;
-    return align_up((size_t)batch * (head_dim / 2) * sizeof(float2), 256) +
-           (size_t)batch * num_heads * 256 * (head_dim + ATTN_WS_PAD) * sizeof(float);
+    return align_up((size_t)batch * (head_dim / 2) * sizeof(float2), 256) + attn_partials_bytes(batch, num_heads, 256, head_dim);  // (TL_ATTN_MAX_SPLITS <= 256)
 }
 
 static int decode_attention_fused_impl(const void *qkv_dev, const void *q_norm_dev, const void *k_norm_dev, void *key_pages_dev,
@@ -3689,34 +3442,26 @@ static int decode_attention_fused_impl(const void *qkv_dev, const void *q_norm_d
     TL_REQUIRE(page_size > 0 && max_pages > 0 && max_context >= 0, "decode_attention_fused: bad page geometry");
     const size_t need = tl_decode_attention_fused_workspace_bytes(batch, num_heads, head_dim);
     TL_REQUIRE(workspace_dev && workspace_bytes >= need, "decode_attention_fused: workspace is missing or too small");
-    tl_engine e;
-    e.cfg.num_heads = num_heads;
-    e.cfg.num_kv_heads = num_kv_heads;
-    e.cfg.head_dim = head_dim;
-    e.cfg.page_size = page_size;
-    e.cfg.max_pages_per_seq = max_pages;
-    e.cfg.rope_theta = rope_theta;
-    e.cfg.rms_norm_eps = eps;
-    e.stream = (hipStream_t)stream;
-    e.block_table = const_cast<int32_t *>(block_table_dev);
-    e.context_lens = const_cast<int32_t *>(context_lens_dev);
-    e.rope_cur = (float2 *)workspace_dev;
+    AttnCtx ctx;
+    ctx.geometry = AttnGeometry{num_heads, num_kv_heads, head_dim, page_size, max_pages};
+    ctx.eps = eps, ctx.rope_theta = rope_theta, ctx.stream = (hipStream_t)stream;
+    ctx.block_table = block_table_dev, ctx.context_lens = context_lens_dev, ctx.rope_cur = (const float2 *)workspace_dev;
     const size_t rc_bytes = align_up((size_t)batch * (head_dim / 2) * sizeof(float2), 256);
-    e.attn_ws_bytes = workspace_bytes - rc_bytes;
-    read_attention_knobs(&e);
-    hipLaunchKernelGGL(rope_rows_kernel, dim3(batch), dim3(64), 0, e.stream, context_lens_dev, e.rope_cur, head_dim / 2, rope_theta);
+    ctx.ws_bytes = workspace_bytes - rc_bytes;
+    ctx.knobs.read_env();
+    hipLaunchKernelGGL(rope_rows_kernel, dim3(batch), dim3(64), 0, ctx.stream, context_lens_dev, (float2 *)workspace_dev, head_dim / 2, rope_theta);
     TL_CHECK_LAUNCH("decode_attention_fused rope");
-    const SplitPlan sp = pick_decode_splits(&e, batch, std::max(1, max_context + 1));
+    const AttnPlan sp = ctx.plan(batch, std::max(1, max_context + 1), key_scales_dev != nullptr);
     AttnCall at{};
     at.qkv = (const uint16_t *)qkv_dev, at.q_norm = q_norm_dev, at.k_norm = k_norm_dev, at.out = (uint16_t *)out_dev;
     at.key_pages = (uint16_t *)key_pages_dev, at.value_pages = (uint16_t *)value_pages_dev, at.key_scales = key_scales_dev, at.value_scales = value_scales_dev;
     at.ws = (float *)((char *)workspace_dev + rc_bytes);
-    const int rc = engine_attention(&e, at, batch, sp, nullptr);
+    const int rc = launch_decode_attention(ctx, sp, at, batch, nullptr);
     if (info) {
         info->n_splits = sp.n_splits;
         info->tokens_per_split = sp.tokens_per_split;
         info->heads_per_workgroup = sp.rq;
-        info->launches = e.last_attn_launches;
+        info->launches = rc == TL_OK ? sp.launches() : 0;
     }
     return rc;
 }
@@ -3769,13 +3514,10 @@ extern "C" int tl_decode_streaming_plan(int M, int rows, int cols, int *out4) {
 extern "C" int tl_decode_streaming_variant_compiled(int T, int GPW) { return qmm7_variant_in_table(T, GPW) ? 1 : 0; }
 extern "C" int tl_decode_attention_plan(int batch, int max_context, int num_heads, int num_kv_heads, int *out3) {
     if (!out3 || batch < 1 || max_context < 0 || num_heads <= 0 || num_kv_heads <= 0 || num_heads % num_kv_heads != 0) return 0;
-    tl_engine e;
-    e.cfg.num_heads = num_heads;
-    e.cfg.num_kv_heads = num_kv_heads;
-    e.cfg.head_dim = 128;  // the plan of the Qwen3 head size on 128-token pages
-    e.cfg.page_size = 128;
-    read_attention_knobs(&e);
-    const SplitPlan sp = pick_decode_splits(&e, batch, std::max(1, max_context + 1));
+    AttnCtx ctx;
+    ctx.geometry = AttnGeometry{num_heads, num_kv_heads, 128, 128, 1};  // the plan of the Qwen3 head size on 128-token pages
+    ctx.knobs.read_env();
+    const AttnPlan sp = ctx.plan(batch, std::max(1, max_context + 1), false);
     out3[0] = sp.n_splits, out3[1] = sp.tokens_per_split, out3[2] = sp.rq;
     return 1;
 }

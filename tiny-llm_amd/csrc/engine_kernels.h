@@ -4,13 +4,13 @@
 // and is compiled with its own MFMA flag; internal linkage keeps the two objects from defining the same symbols.)
 #pragma once
 #include <type_traits>
+#include "attn_plan.h"  // AD_RQ, ATTN_WS_PAD: what the host's plan and the kernels share
 #include "common.h"
 #include "kv8.h"
 
 namespace tl {
 
 constexpr float ENG_LOG2E = 1.44269504089f;
-constexpr int AD_RQ = 4;  // most query heads of one GQA group handled per workgroup
 
 // ---------------------------------------------------------------------------------------------
 // Shared prologue: RMSNorm over one head row (D = 16*VD, lane t holds dims [t*VD, t*VD+VD)) rounded to bf16
@@ -144,9 +144,7 @@ __device__ __forceinline__ float group16_allsum(float v) {
 //   reference semantics: paged_attention.metal:108-248 (decode), paged_cache_update :82-106,
 //   qwen3_week3.py:63-86 for the op order.
 // ---------------------------------------------------------------------------------------------
-// row of split partials in global memory: D value sums + (max, sum) + 2 floats of padding, so that rows start on 16 bytes (the wo GEMV
-// that merges them reads them with 16-byte loads); the LDS rows inside the kernels keep D + 2
-constexpr int ATTN_WS_PAD = 4;
+// (a row of split partials in global memory is D + ATTN_WS_PAD floats: attn_plan.h)
 struct AttnDecodeArgs {
     const uint16_t *qkv;  // [batch, (Hq + 2 Hkv) * D]
     const uint16_t *q_norm_w, *k_norm_w;
