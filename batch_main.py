@@ -34,6 +34,16 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--repetition-penalty", type=float, default=1.0, help="per request, on the device; over prompt and output (1 = off)")
     ap.add_argument("--presence-penalty", type=float, default=0.0, help="per request, on the device; over the output (0 = off)")
     ap.add_argument("--frequency-penalty", type=float, default=0.0, help="per request, on the device; times the count in the output (0 = off)")
+    ap.add_argument("--dry-multiplier", type=float, default=0.0,
+                    help="per request, on the device: DRY -- subtract multiplier * base ** (L - allowed_length) from the token that would "
+                         "extend a verbatim repeat of L tokens (0 = off)")
+    ap.add_argument("--dry-base", type=float, default=1.75, help="DRY's base (>= 1)")
+    ap.add_argument("--dry-allowed-length", type=int, default=2, help="the longest repeat DRY leaves alone, plus one (>= 1)")
+    ap.add_argument("--dry-range", type=int, default=0, help="DRY looks for repeats in the last N tokens (0 = all)")
+    ap.add_argument("--dry-breaker", action="append", default=[], metavar="STRING",
+                    help="a repeat never runs across the last token of STRING's encoding; repeatable (64)")
+    ap.add_argument("--no-repeat-ngram", type=int, default=0, metavar="N",
+                    help="per request, on the device: ban the token that would complete an N-gram the text already holds (0 = off, else 2 .. 64)")
     ap.add_argument("--sampler-min-p", type=float, default=0.0, help="per sampling request, on the device: keep tokens with p >= min_p * p_max (0 = off)")
     ap.add_argument("--sampler-typical-p", type=float, default=None, help="... locally typical sampling with this mass (1 = off)")
     ap.add_argument("--mirostat-tau", type=float, default=0.0,
@@ -81,6 +91,8 @@ def check_draft_flags(ap: argparse.ArgumentParser, args, truncates: bool) -> Non
         ("--regex / --json / --json-schema", bool(args.regex or args.json or args.json_schema)),
         ("--stop / --stop-id", bool(args.stop or args.stop_id)),
         ("--lora", bool(args.lora)),
+        ("--dry-multiplier / --dry-base / --dry-allowed-length / --dry-range / --dry-breaker / --no-repeat-ngram",
+         args.dry_multiplier > 0 or args.no_repeat_ngram > 0),
     ) if on]
     if clashes:
         ap.error("--draft-model runs greedy speculative decoding over the raw logits of one model; it does not combine with " + ", ".join(clashes))
@@ -122,6 +134,9 @@ def main(argv=None):
     if (args.repetition_penalty, args.presence_penalty, args.frequency_penalty) != (1.0, 0.0, 0.0):
         sampling.update(repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty,
                         frequency_penalty=args.frequency_penalty)
+    from main import dry_settings
+
+    sampling.update(dry_settings(args, tokenizer))
     stops = {tokenizer.eos_token_id}
     try:
         from tiny_llm_hip.grammar import cli_grammar

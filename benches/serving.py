@@ -127,6 +127,12 @@ def serve_requests(engine, requests, *, batch_size: int, prefill_step: int, pref
             lora = getattr(request, "lora", None)  # the id of a resident LoRA adapter (DecodeEngine.load_lora); such a request bypasses the prefix cache
             if lora is not None and lora >= 0:
                 RequestSettings(lora=lora).apply(engine, slot)
+            dry = getattr(request, "dry", None)  # DRY / the n-gram ban: a dict with the keys of DecodeEngine.set_dry
+            if dry:
+                from tiny_llm_hip.engine import dry_args
+
+                RequestSettings(dry=dry_args(dry.get("multiplier", 0.0), dry.get("base", 1.75), dry.get("allowed_length", 2), dry.get("range", 0),
+                                             dry.get("no_repeat_ngram", 0), dry.get("breakers") or ())).apply(engine, slot)
 
         def before_prefill(self):
             self.t0 = clock()

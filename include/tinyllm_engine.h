@@ -453,6 +453,46 @@ int tl_engine_read_pending_logprobs(tl_engine *e, int count, tl_token_logprob *o
 int tl_engine_set_penalties(tl_engine *e, int slot, float repetition_penalty, float presence_penalty, float frequency_penalty);
 int tl_engine_set_logit_bias(tl_engine *e, int slot, const int32_t *ids, const float *values, int n);
 
+/* DRY and the n-gram ban: repetition control that looks at the ORDER of the tokens (csrc/dry.h).  DRY ("don't repeat
+ * yourself", the sampler of text-generation-webui, llama.cpp and koboldcpp) penalises the token that would extend a verbatim repetition,
+ * growing exponentially with the length of the repeat; no_repeat_ngram (Hugging Face generate's no_repeat_ngram_size) bans the token that
+ * would complete an n-gram already present.  A slot with either on PROCESSES (above): the two launches of csrc/dry.h rewrite its
+ * processed row -- the row after repetition / presence / frequency, bias and grammar mask; the raw row where nothing else is on -- and
+ * the greedy rule, the sampler, the truncation launch and tl_engine_copy_processed_logits see that row.
+ *   sequence   at the moment a token is chosen the slot's recorded ids are S[s0 .. e]: s0 = the context length the slot had when it was
+ *              armed (0 right after tl_engine_begin, the normal use); S[e] = last = the token the step has just fed (for the first token
+ *              after a prefill with want_logits: the prompt's last token).  Ids before s0 are unknown and never matched.
+ *              M = TL_DRY_MAX_MATCH = 64.
+ *   candidate  every i in [s0, e) with S[i] == last; its continuation is S[i + 1].  raw(i) = the largest m in [1, min(M, i - s0 + 1)]
+ *              with S[i - j] == S[e - j] for all 0 <= j < m.
+ *   n-gram     no_repeat_ngram n = 0 (off) or 2 .. 64: every continuation with raw(i) >= n - 1 is banned.  Breakers and the range do not
+ *              apply to it.  With s0 = 0 this is transformers.NoRepeatNGramLogitsProcessor(n).
+ *   DRY        (multiplier, base, allowed_length, range, breakers): multiplier finite and >= 0 (0 = DRY off), base finite and >= 1,
+ *              allowed_length >= 1, range >= 0 (0 = the whole recorded sequence), up to TL_MAX_DRY_BREAKERS distinct token ids.
+ *                lo = range > 0 ? max(s0, e + 1 - range) : s0
+ *                B  = the number of consecutive j >= 0 with e - j >= lo and S[e - j] not a breaker, capped at M (a last token that is a
+ *                     breaker gives B = 0: no DRY penalty on this choice)
+ *                d(i) = min(raw(i), B, i - lo + 1), for a candidate with i >= lo whose continuation is not a breaker
+ *                L[t] = the largest d(i) over the candidates whose continuation is t; it counts where L[t] >= allowed_length
+ *              (text-generation-webui's loop with the match capped at 64; at the default base 1.75 a 64-token match is a ban in effect)
+ *   penalty    p = multiplier, then L[t] - allowed_length times p = p * base: fp32 products, rounded one by one (no powf).
+ *   element    a banned token becomes bf16 -inf.  A token with a DRY entry becomes bf16 round to nearest even of float(v) - p; -inf where p
+ *              is not finite; a NaN keeps its bits.  Every other token keeps its bits.  Log-probabilities go on describing the raw row.
+ *   life       as for every processing slot: tl_engine_begin / tl_engine_release switch it off, tl_engine_move carries the parameters, the
+ *              breakers, s0 and the sequence row, tl_engine_fork copies them, park / unpark keep them; tl_engine_rewind,
+ *              tl_engine_set_token, the verify calls and beam search refuse the slot.  Changing parameters of an armed slot keeps s0 and
+ *              the sequence; switching everything off and on again makes s0 the current context length.  The ids a slot consumes through
+ *              tl_engine_prefill, tl_engine_prefill_packed, tl_engine_score or tl_engine_prefix_attach while it is armed are recorded.  A
+ *              stopped slot's sequence and s0 stand where the text ended.
+ *   plans      a step in which no live slot is armed is the program it was.  One in which a slot is has two more launches behind the
+ *              processing launch, in a captured plan of its own (plan-key bit 53) that replays through hipGraphLaunch.
+ * The sequence rows (max_batch x max_pages_per_seq x page_size x 4 bytes), the match table (max_batch x vocab x 4 bytes, all zeros between
+ * steps) and the parameter arrays are allocated by the first call that arms a slot; an engine that never asks allocates nothing. */
+#define TL_DRY_MAX_MATCH 64
+#define TL_MAX_DRY_BREAKERS 64
+int tl_engine_set_dry(tl_engine *e, int slot, float multiplier, float base, int allowed_length, int range, int no_repeat_ngram,
+                      const int32_t *breaker_ids, int n_breakers);
+
 /* Truncation: min-p, locally typical sampling and Mirostat v2 (csrc/truncate.h).  For a slot that SAMPLES
  * (temperature T > 0) and truncates, the bf16 row x the choice would be made from -- the raw row, or the processed row when the slot
  * processes penalties, bias or a grammar -- is first turned into a FILTERED bf16 row, and the existing choice runs on the filtered row
@@ -1098,6 +1138,16 @@ int tl_mirostat_update_rows(const void *filtered_dev, int rows, int vocab, const
 int tl_process_logits(const void *logits_dev, int rows, int vocab, const uint16_t *history_dev, const float *repetition_dev,
                       const float *presence_dev, const float *frequency_dev, const int32_t *bias_ids_dev, const float *bias_values_dev,
                       const int32_t *bias_n_dev, void *out_dev, void *stream);
+
+/* The two launches of tl_engine_set_dry over caller rows: sequences_dev [rows, cap] int32 (row r holds S[start[r] .. end[r]], end[r] < cap;
+ * a row with end < start is left alone), the per-row parameters [rows] (a row with multiplier 0 and no_repeat_ngram 0 is left alone),
+ * breaker_ids_dev [rows, TL_MAX_DRY_BREAKERS] with n_breakers_dev [rows] entries each (the list may be NULL when every count is 0),
+ * table_dev [rows, vocab] uint32, all zeros before the call and all zeros after it, and logits_dev [rows, vocab] bf16 (vocab <= 524,288),
+ * rewritten in place.  The engine's kernels and semantics; nothing is stored to the sequences.  One launch of `rows` workgroups and one of
+ * ceil(vocab / 2,048) x rows.  Stream ordered. */
+int tl_dry_rows(int32_t *sequences_dev, int rows, int cap, const int32_t *start_dev, const int32_t *end_dev, const float *multiplier_dev,
+                const float *base_dev, const int32_t *allowed_length_dev, const int32_t *range_dev, const int32_t *no_repeat_ngram_dev,
+                const int32_t *breaker_ids_dev, const int32_t *n_breakers_dev, uint32_t *table_dev, void *logits_dev, int vocab, void *stream);
 
 /* The attention stage of tl_engine_verify_batch over caller pools (csrc/verify_attn.h): qkv_dev [R, (Hq + 2 Hkv) * 128] bf16, the rows
  * of n_seqs (1 .. 64) sequences back to back; sequence i (host arrays) holds lens[i] (1 .. 8) rows at positions starts[i] .. of

@@ -37,6 +37,16 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --solution engine: subtract this from the logit of every token the output already holds (0 = off)")
     ap.add_argument("--frequency-penalty", type=float, default=0.0,
                     help="with --solution engine: subtract this times the token's count in the output (0 = off)")
+    ap.add_argument("--dry-multiplier", type=float, default=0.0,
+                    help="with --solution engine: DRY, on the device -- subtract multiplier * base ** (L - allowed_length) from the token that "
+                         "would extend a verbatim repeat of L tokens (0 = off)")
+    ap.add_argument("--dry-base", type=float, default=1.75, help="DRY's base (>= 1)")
+    ap.add_argument("--dry-allowed-length", type=int, default=2, help="the longest repeat DRY leaves alone, plus one (>= 1)")
+    ap.add_argument("--dry-range", type=int, default=0, help="DRY looks for repeats in the last N tokens (0 = all)")
+    ap.add_argument("--dry-breaker", action="append", default=[], metavar="STRING",
+                    help="a repeat never runs across the last token of STRING's encoding; repeatable (64)")
+    ap.add_argument("--no-repeat-ngram", type=int, default=0, metavar="N",
+                    help="with --solution engine: ban, on the device, the token that would complete an N-gram the text already holds (0 = off, else 2 .. 64)")
     constraint = ap.add_mutually_exclusive_group()
     ap.add_argument("--sampler-min-p", type=float, default=0.0,
                     help="with --solution engine and a nonzero --sampler-temp, on the device: keep tokens with p >= min_p * p_max (0 = off)")
@@ -108,10 +118,25 @@ def check_beam_flags(ap, args) -> None:
         "--stop": bool(args.stop),
         "--logprobs": args.logprobs is not None,
         "--lora": args.lora is not None,
+        "the DRY / --no-repeat-ngram options": dry_flags_on(args),
     }
     clash = [name for name, on in excluded.items() if on]
     if clash:
         ap.error("--num-beams cannot be combined with " + ", ".join(clash) + ": beam slots are plain greedy slots")
+
+
+def dry_flags_on(args) -> bool:
+    return args.dry_multiplier > 0 or args.no_repeat_ngram > 0
+
+
+def dry_settings(args, tokenizer) -> dict:
+    """The --dry-* / --no-repeat-ngram flags as the keys of engine.generate / a sampling dict ({} when both are off)."""
+    if not dry_flags_on(args):
+        return {}
+    from tiny_llm_hip.engine import dry_breaker_ids
+
+    return {"dry_multiplier": args.dry_multiplier, "dry_base": args.dry_base, "dry_allowed_length": args.dry_allowed_length,
+            "dry_range": args.dry_range, "dry_breakers": tuple(dry_breaker_ids(tokenizer, args.dry_breaker)), "no_repeat_ngram": args.no_repeat_ngram}
 
 
 def chat_prompt(tokenizer, text: str, enable_thinking: bool) -> str:
@@ -140,6 +165,8 @@ def main(argv=None) -> str:
                                         proposal_length=args.proposal_length)
         if penalties != (1.0, 0.0, 0.0) or args.regex or args.json or args.json_schema:
             print("note: the penalty flags, --regex, --json and --json-schema apply to --solution engine only")
+        if dry_flags_on(args):
+            print("note: the --dry-* flags and --no-repeat-ngram apply to --solution engine only")
         if args.sampler_temp:
             print("note: the KV-cache loop is greedy like the reference's; sampler flags apply to --solution engine only")
         _ = make_sampler  # sampler surface kept importable for callers of the library
@@ -157,6 +184,7 @@ def main(argv=None) -> str:
     grammar = None
     lora = None
     stop, token_bytes = None, None
+    dry = dry_settings(args, tokenizer)
     try:
         if args.lora:
             if args.draft_model:
@@ -180,6 +208,8 @@ def main(argv=None) -> str:
             if penalties != (1.0, 0.0, 0.0) or args.regex or args.json or args.json_schema:
                 print("note: speculative decoding verifies the raw logits; the penalty flags, --regex, --json and --json-schema do not "
                       "apply with a draft model")
+            if dry:
+                print("note: speculative decoding verifies the raw logits; the --dry-* flags and --no-repeat-ngram do not apply with a draft model")
             if truncates:
                 print("note: speculative sampling verifies under temperature, top-k and top-p; --sampler-min-p, --sampler-typical-p and "
                       "--mirostat-tau do not apply with a draft model")
@@ -195,7 +225,7 @@ def main(argv=None) -> str:
             finally:
                 draft.close()
         elif args.sampler_temp and (args.sampler_seed is not None or lora is not None or penalties != (1.0, 0.0, 0.0) or grammar is not None or truncates
-                                    or stop is not None):
+                                    or stop is not None or dry):
             # the per-slot sampler on the device: the whole generation in one prefill + one decode(N) call.  The penalties and the
             # grammar exist on the device only, so they select this path; so do min-p, typical-p and Mirostat
             if args.sampler_seed is None:
@@ -204,7 +234,7 @@ def main(argv=None) -> str:
                                   top_p=args.sampler_top_p, seed=args.sampler_seed or 0, logprobs=args.logprobs,
                                   repetition_penalty=penalties[0], presence_penalty=penalties[1], frequency_penalty=penalties[2],
                                   grammar=grammar, min_p=args.sampler_min_p, typical_p=args.sampler_typical_p,
-                                  mirostat_tau=args.mirostat_tau, mirostat_eta=args.mirostat_eta, lora=lora, stop=stop)
+                                  mirostat_tau=args.mirostat_tau, mirostat_eta=args.mirostat_eta, lora=lora, stop=stop, **dry)
             if args.logprobs is not None:
                 out, records = out
             out = cut_at_eos(out, eos, grammar)
@@ -212,7 +242,7 @@ def main(argv=None) -> str:
             out = sample_with_engine(engine, ids, args, eos)
         else:
             out = engine.generate(ids, args.max_new_tokens, logprobs=args.logprobs, repetition_penalty=penalties[0],
-                                  presence_penalty=penalties[1], frequency_penalty=penalties[2], grammar=grammar, lora=lora, stop=stop)
+                                  presence_penalty=penalties[1], frequency_penalty=penalties[2], grammar=grammar, lora=lora, stop=stop, **dry)
             if args.logprobs is not None:
                 out, records = out
             out = cut_at_eos(out, eos, grammar)

@@ -14,6 +14,7 @@
 #include "device_block.h"
 #include "engine_layout.h"
 #include "step_end.h"  // the three step-end kernels; with it sample.h and logprob.h
+#include "dry.h"
 #include "logit_process.h"
 #include "truncate.h"
 #include "grammar_stack.h"
@@ -425,7 +426,7 @@ static_assert(offsetof(GrammarRecord, tag) == 0 && offsetof(GrammarRecord, state
 static_assert(sizeof(GrammarDev *) == 8 && sizeof(StopDev *) == 8 && LPR_MAX_BIAS == TL_MAX_LOGIT_BIAS, "pointers are two words");
 static SlotSettings::Sizes settings_sizes(const tl_engine *e) {
     return {e->cfg.max_batch, e->cfg.vocab_size, e->ring_cap, LP_RECORD_WORDS, LP_MAX_TOP, LPR_MAX_BIAS, (int)sizeof(GrammarRecord), (int)sizeof(GrammarStackRecord),
-            (int)sizeof(StopRecord), SMP_MAX_VOCAB, LORA_NONE};
+            (int)sizeof(StopRecord), SMP_MAX_VOCAB, LORA_NONE, e->cfg.max_pages_per_seq * e->cfg.page_size, DRY_MAX_BREAKERS, DRY_MAX_MATCH};
 }
 
 // What the allocation of each block reports when it fails (fill: the memsets and the launch that give a fresh block its first values), and
@@ -443,11 +444,12 @@ static const SettingsBlockTexts SETTINGS_BLOCK_TEXTS[SB_COUNT] = {
     {"engine: hipMalloc(truncation) failed", "engine: memset(truncation) failed", true},
     {"engine_set_stop: hipMalloc(stop records) failed", "engine_set_stop: memset(stop records) failed", true},
     {nullptr, nullptr, false},  // (the adapter ids: inside lora_mem, lora_alloc)
+    {"engine_set_dry: hipMalloc(sequence rows) failed", "engine_set_dry: memset(sequence rows) failed", true},
 };
 // the blocks of `needs` that do not exist yet, each from its layout: all-or-nothing per block, filled on the engine stream
 static int settings_blocks(tl_engine *e, unsigned needs) {
-    for (int b = 0; b < SB_LORA; ++b) {
-        if (!(needs >> b & 1u) || e->settings_mem[b]) continue;
+    for (int b = 0; b < SB_COUNT; ++b) {
+        if (b == SB_LORA || !(needs >> b & 1u) || e->settings_mem[b]) continue;
         const BlockLayout &lay = e->settings.layout(b);
         const SettingsBlockTexts &t = SETTINGS_BLOCK_TEXTS[b];
         TL_TRY(alloc_filled(e->settings_mem[b], lay.bytes, t.malloc_failed, [&](char *m) -> int {
@@ -517,6 +519,37 @@ static void launch_logit_process(tl_engine *e, const uint16_t *logits, uint16_t 
     else if (grammar) hipLaunchKernelGGL(logit_process_kernel<true>, grid, dim3(LPR_THREADS), 0, e->stream, a);
     else hipLaunchKernelGGL(logit_process_kernel<false>, grid, dim3(LPR_THREADS), 0, e->stream, a);
     if (pc) prof_after(pc, 7, (int)(grid.x * grid.y));
+}
+
+// the two launches of DRY and the n-gram ban (dry.h) over `rows` processed rows for slots slot0 .., rewritten in place.  A decode step
+// passes the fed tokens, which the match launch stores at S[e] = S[context length]; a prefill's row has recorded its ids already and
+// ends at context length - 1
+static DryArgs dry_args(tl_engine *e, uint16_t *rows, int slot0, const int32_t *tokens, prof_t *prof) {
+    const SlotSettings::Offsets &at = e->settings.at;
+    DryArgs a{};
+    a.seq = e->sdev<int32_t>(SB_DRY, at.dry_seq), a.table = e->sdev<uint32_t>(SB_DRY, at.dry_table), a.rows = rows;
+    a.cap = e->settings.sz.dry_seq_cap, a.vocab = e->cfg.vocab_size, a.slot0 = slot0, a.pos_bias = tokens ? 0 : -1;
+    a.pos = e->context_lens, a.tokens = tokens, a.live = e->live;
+    a.multiplier = e->sdev<float>(SB_DRY, at.dry_mult), a.base = e->sdev<float>(SB_DRY, at.dry_base);
+    a.allowed = e->sdev<int32_t>(SB_DRY, at.dry_allowed), a.range = e->sdev<int32_t>(SB_DRY, at.dry_range);
+    a.ngram = e->sdev<int32_t>(SB_DRY, at.dry_ngram), a.start = e->sdev<int32_t>(SB_DRY, at.dry_s0);
+    a.n_breakers = e->sdev<int32_t>(SB_DRY, at.dry_nbreak), a.breakers = e->sdev<int32_t>(SB_DRY, at.dry_breakers);
+    a.prof = prof;
+    return a;
+}
+static void launch_dry(tl_engine *e, uint16_t *processed, int rows, int slot0, const int32_t *tokens, ProfCtx *pc) {
+    const DryArgs a = dry_args(e, processed, slot0, tokens, pc ? pc->buf : nullptr);
+    hipLaunchKernelGGL(dry_match_kernel, dim3(rows), dim3(DRY_MATCH_THREADS), 0, e->stream, a);
+    if (pc) prof_after(pc, 7, rows);
+    const dim3 grid(ceil_div(e->cfg.vocab_size, DRY_APPLY_CHUNK), rows);
+    hipLaunchKernelGGL(dry_apply_kernel, grid, dim3(DRY_APPLY_THREADS), 0, e->stream, a);
+    if (pc) prof_after(pc, 7, (int)(grid.x * grid.y));
+}
+// a chunk's uploaded ids (at `tokens_dev`) enter the sequence row of a slot that records them, at positions start ..
+static void launch_dry_record(tl_engine *e, int slot, const int32_t *tokens_dev, int n, int start) {
+    const int cap = e->settings.sz.dry_seq_cap;
+    const DryRecordArgs a{tokens_dev, e->sdev<int32_t>(SB_DRY, e->settings.at.dry_seq) + (size_t)slot * cap, n, start, cap};
+    hipLaunchKernelGGL(dry_record_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, e->stream, a);
 }
 
 // the truncation launch over `rows` rows for slots slot0 .. (the rows the choice would be made from -> filtered rows into `out`), and the
@@ -639,7 +672,9 @@ static long step_key_bits(const StepFeatures &f) {
            // bit 55: a slot carries a LoRA adapter: the adapter plan (lora.h; hipGraphLaunch)
            (f.lora ? (1L << 55) : 0L) |
            // bit 54: a slot is armed with stop conditions: the stop launch (stop.h) stands last (hipGraphLaunch)
-           (f.stop ? (1L << 54) : 0L);
+           (f.stop ? (1L << 54) : 0L) |
+           // bit 53: a slot has DRY or the n-gram ban on: the match and apply launches (dry.h) stand behind the processing launch (hipGraphLaunch)
+           (f.dry ? (1L << 53) : 0L);
 }
 // Why a plan with these features never becomes an AQL program (null: it may), the one sentence tl_engine_replay_route reports: bits 54,
 // 55 and 56 above, the stop launch first
@@ -647,6 +682,7 @@ static const char *graph_only_reason(const StepFeatures &f) {
     if (f.stop) return "a slot is armed with stop conditions (the stop launch reads the token the step end stored and writes the live word)";
     if (f.lora) return "a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)";
     if (f.mirostat) return "a Mirostat slot is live (the update launch reads the token the step end stored)";
+    if (f.dry) return "a slot has DRY or the n-gram ban on (the apply launch writes the processed rows a second time)";
     return nullptr;
 }
 // the plan of slots [slot0, slot0 + n), re-derived from the slots' parameters by every call that enqueues or replays a step: a decode step
@@ -656,6 +692,8 @@ static StepFeatures step_features(const tl_engine *e, int slot0, int n) {
 }
 // does the slot, taking part in a step, process its logits?
 static bool step_processes_slot(const tl_engine *e, int slot) { return e->settings.processes(slot, e->slot_runs(slot)); }
+// ... and does it record the ids it is fed (dry.h)?
+static bool step_records_slot(const tl_engine *e, int slot) { return e->settings.records(slot, e->slot_runs(slot)); }
 
 // The chain behind the lm_head over `rows` raw rows -- rows [row0, row0 + rows) of the engine's row buffers, slots slot0 .. -- in the one
 // order a decode step and a prefill's first token share: processing (logit_process.h), truncation (truncate.h), the step end, the
@@ -670,6 +708,7 @@ static void launch_logit_chain(tl_engine *e, const uint16_t *raw, int row0, int 
     if (f.processes) {  // raw rows -> processed rows (rows of slots that do not process are copied)
         launch_logit_process(e, choice, e->sdev<uint16_t>(SB_PROCESS, e->settings.at.pen_rows) + at, rows, slot0, tokens, f.grammar, f.stack_grammar, pc);
         choice = e->sdev<uint16_t>(SB_PROCESS, e->settings.at.pen_rows) + at;
+        if (f.dry) launch_dry(e, e->sdev<uint16_t>(SB_PROCESS, e->settings.at.pen_rows) + at, rows, slot0, tokens, pc);
     }
     if (f.truncates) {  // ... -> filtered rows (rows of slots that do not truncate are copied)
         launch_truncate(e, choice, e->sdev<uint16_t>(SB_TRUNC, e->settings.at.trn_rows) + at, rows, slot0, row0, pc);
@@ -1489,6 +1528,7 @@ extern "C" int tl_engine_prefix_attach(tl_engine *e, int slot, const int32_t *to
             TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens + at, (size_t)len * 4, hipMemcpyHostToDevice, e->stream));
             const LogitMarkArgs mk{e->prefill_tokens, len, c.vocab_size, e->sdev<uint32_t>(SB_PROCESS, e->settings.at.pen_history), (long)slot * c.vocab_size};
             hipLaunchKernelGGL(logit_mark_prompt_kernel, dim3(ceil_div(len, 256)), dim3(256), 0, e->stream, mk);
+            if (step_records_slot(e, slot)) launch_dry_record(e, slot, e->prefill_tokens, len, at);  // (the slot held no tokens: they start at 0)
             TL_CHECK_LAUNCH("engine prompt marking");
         }
     }
@@ -1814,6 +1854,35 @@ extern "C" int tl_engine_set_penalties(tl_engine *e, int slot, float repetition_
     TL_TRY(slot_check(e, slot, true));
     Pokes pk;
     return settings_set(e, slot, pk, [&](SettingsEdits &ed) { return e->settings.set_penalties(slot, repetition_penalty, presence_penalty, frequency_penalty, ed); });
+}
+
+extern "C" int tl_engine_set_dry(tl_engine *e, int slot, float multiplier, float base, int allowed_length, int range, int no_repeat_ngram,
+                                 const int32_t *breaker_ids, int n_breakers) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_TRY(stop_reconcile(e));  // (the context length of a slot a stop froze in mid-call)
+    Pokes pk;
+    return settings_set(e, slot, pk, [&](SettingsEdits &ed) {
+        return e->settings.set_dry(slot, multiplier, base, allowed_length, range, no_repeat_ngram, breaker_ids, n_breakers, e->table.slots[slot].ctx, ed);
+    });
+}
+
+extern "C" int tl_dry_rows(int32_t *sequences_dev, int rows, int cap, const int32_t *start_dev, const int32_t *end_dev, const float *multiplier_dev,
+                           const float *base_dev, const int32_t *allowed_length_dev, const int32_t *range_dev, const int32_t *no_repeat_ngram_dev,
+                           const int32_t *breaker_ids_dev, const int32_t *n_breakers_dev, uint32_t *table_dev, void *logits_dev, int vocab, void *stream) {
+    TL_REQUIRE(sequences_dev && start_dev && end_dev && multiplier_dev && base_dev && allowed_length_dev && range_dev && no_repeat_ngram_dev &&
+                   n_breakers_dev && table_dev && logits_dev, "dry_rows: null argument");
+    TL_REQUIRE(rows > 0 && rows <= 65535, "dry_rows: rows out of range");
+    TL_REQUIRE(cap > 0, "dry_rows: sequence capacity out of range");
+    TL_REQUIRE(vocab > 0 && vocab <= SMP_MAX_VOCAB, "dry_rows: vocabulary out of range (1 .. 524,288)");
+    // (without breaker lists every count must be 0: the kernel reads no entry then)
+    DryArgs a{};
+    a.seq = sequences_dev, a.table = table_dev, a.rows = (uint16_t *)logits_dev, a.cap = cap, a.vocab = vocab, a.pos = end_dev;
+    a.multiplier = multiplier_dev, a.base = base_dev, a.allowed = allowed_length_dev, a.range = range_dev, a.ngram = no_repeat_ngram_dev;
+    a.start = start_dev, a.n_breakers = n_breakers_dev, a.breakers = breaker_ids_dev;
+    hipLaunchKernelGGL(dry_match_kernel, dim3(rows), dim3(DRY_MATCH_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(dry_apply_kernel, dim3(ceil_div(vocab, DRY_APPLY_CHUNK), rows), dim3(DRY_APPLY_THREADS), 0, (hipStream_t)stream, a);
+    TL_CHECK_LAUNCH("dry_rows");
+    return TL_OK;
 }
 
 extern "C" int tl_engine_set_logit_bias(tl_engine *e, int slot, const int32_t *ids, const float *values, int n) {
@@ -2459,6 +2528,11 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
     TL_TRY(apply_edits(e, ed, pk));
     TL_TRY(poke(e, pk));
     TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens, (size_t)total * 4, hipMemcpyHostToDevice, e->stream));
+    for (int i = 0; i < n_seqs; ++i) {  // ... and the sequence row of a slot that records its ids (dry.h)
+        if (!step_records_slot(e, seqs[i].slot)) continue;
+        launch_dry_record(e, seqs[i].slot, e->prefill_tokens + seqs[i].row0, seqs[i].len, seqs[i].start);
+        TL_CHECK_LAUNCH("engine sequence recording");
+    }
     for (int i = 0; i < n_seqs; ++i) {  // the chunk's tokens enter the history of a slot that processes its logits (logit_process.h)
         if (!step_processes_slot(e, seqs[i].slot)) continue;
         const LogitMarkArgs mk{e->prefill_tokens + seqs[i].row0, seqs[i].len, c.vocab_size, e->sdev<uint32_t>(SB_PROCESS, e->settings.at.pen_history), (long)seqs[i].slot * c.vocab_size};

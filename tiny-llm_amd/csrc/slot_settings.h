@@ -2,7 +2,7 @@
 // slot_table.h.  Host only, no HIP include and no device pointer dereferenced: engine.hip calls it and applies the edits it reports to
 // the device, and tests/slot_settings_model_check.cpp drives the same code alone against byte arrays that stand for the device.
 //
-//   state     one State per batch slot: the host mirrors of sampling, log-probability records, penalties / bias / grammar, truncation
+//   state     one State per batch slot: the host mirrors of sampling, log-probability records, penalties / bias / grammar / DRY, truncation
 //             and Mirostat, the LoRA adapter id and the stop conditions, and three host-only flags (the pending token, the rows of a
 //             running mean, parked).  The device copy of a live unparked slot follows its mirror; a parked slot's processing
 //             parameters are neutral on the device, because the processing launch reads them whatever the `live` word says.
@@ -23,7 +23,7 @@
 
 namespace tl {
 
-enum SettingsBlock { SB_SAMPLE, SB_LOGPROB, SB_PROCESS, SB_GRAMMAR, SB_STACK, SB_TRUNC, SB_STOP, SB_LORA, SB_COUNT };
+enum SettingsBlock { SB_SAMPLE, SB_LOGPROB, SB_PROCESS, SB_GRAMMAR, SB_STACK, SB_TRUNC, SB_STOP, SB_LORA, SB_DRY, SB_COUNT };
 
 // temperature 0 = greedy (the default, and what begin / release restore)
 struct SampleParams {
@@ -51,7 +51,16 @@ struct PenaltyParams {
     std::vector<int32_t> bias_ids;
     std::vector<float> bias_values;
     GrammarRef grammar;
-    bool processes() const { return repetition != 1.f || presence != 0.f || frequency != 0.f || !bias_ids.empty() || grammar; }
+    // DRY and the n-gram ban (dry.h): multiplier 0 = DRY off, ngram 0 = no ban; s0: the context length the slot had when it was armed
+    float dry_multiplier = 0.f, dry_base = 1.75f;
+    int dry_allowed = 2, dry_range = 0, ngram = 0, dry_s0 = 0;
+    std::vector<int32_t> dry_breakers;
+    bool dry_on() const { return dry_multiplier > 0.f || ngram > 0; }
+    bool dry_same(const PenaltyParams &o) const {
+        return dry_multiplier == o.dry_multiplier && dry_base == o.dry_base && dry_allowed == o.dry_allowed && dry_range == o.dry_range &&
+               ngram == o.ngram && dry_s0 == o.dry_s0 && dry_breakers == o.dry_breakers;
+    }
+    bool processes() const { return repetition != 1.f || presence != 0.f || frequency != 0.f || !bias_ids.empty() || grammar || dry_on(); }
 };
 struct TruncParams {
     float min_p = 0.f, typical_p = 1.f, tau = 0.f, eta = 0.f;
@@ -73,7 +82,7 @@ struct StopMirror {
 // which launches a step over some slots needs: the per-slot predicates ORed (SlotSettings::features; the engine keys its plans by them)
 struct StepFeatures {
     bool samples = false, logprobs = false, processes = false, grammar = false, stack_grammar = false, truncates = false, mirostat = false,
-         lora = false, stop = false;
+         lora = false, stop = false, dry = false;
 };
 
 struct SettingsEdit {
@@ -116,6 +125,10 @@ class SlotSettings {
         int stop_record_bytes;                         // stop.h
         int sampler_max_vocab;                         // sample.h
         int lora_none;                                 // lora_tiles.h
+        // (appended; zero: the feature is absent)
+        int dry_seq_cap = 0;       // ids a slot's sequence row holds (max_pages_per_seq * page_size); 0: no DRY / n-gram ban on this engine
+        int dry_max_breakers = 0;  // dry.h
+        int dry_max_match = 0;
     };
     struct State {
         SampleParams smp;
@@ -137,6 +150,7 @@ class SlotSettings {
         size_t gr_ptr, gr_state;
         size_t trn_rows, trn_minp, trn_tau, trn_eta, trn_logsum, trn_typ, trn_mu;  // [max(slots, 8), vocab]; logsum [max(slots, 8)]
         size_t stop_sets, stop_armed, stop_max_new, stop_automaton, stop_rec;
+        size_t dry_seq, dry_table, dry_mult, dry_base, dry_allowed, dry_range, dry_ngram, dry_s0, dry_nbreak, dry_breakers;  // [slots, dry_seq_cap]; [slots, vocab]; ...; [slots, dry_max_breakers]
     };
     std::vector<State> slots;
     Offsets at{};
@@ -177,6 +191,13 @@ class SlotSettings {
         layouts_[SB_STOP] = {off, {{0, off, 0}}};
         // the adapter ids inside the LoRA block: all none
         layouts_[SB_LORA] = {B * 4, {{0, B * 4, ones}}};
+        // DRY and the n-gram ban: the table and every parameter zero (off); the sequence rows are written before they are read
+        off = 0;
+        at.dry_seq = carve(off, B * (size_t)sz.dry_seq_cap * 4), at.dry_table = carve(off, sz.dry_seq_cap ? B * V * 4 : 0);
+        at.dry_mult = carve(off, B * 4), at.dry_base = carve(off, B * 4), at.dry_allowed = carve(off, B * 4), at.dry_range = carve(off, B * 4);
+        at.dry_ngram = carve(off, B * 4), at.dry_s0 = carve(off, B * 4), at.dry_nbreak = carve(off, B * 4);
+        at.dry_breakers = carve(off, B * (size_t)sz.dry_max_breakers * 4);
+        layouts_[SB_DRY] = {sz.dry_seq_cap ? off : 0, {{at.dry_table, off - at.dry_table, 0}}};
     }
     const BlockLayout &layout(int b) const { return layouts_[b]; }
     bool exists(int b) const { return exists_ >> b & 1u; }
@@ -241,6 +262,38 @@ class SlotSettings {
             if (sorted[i] < 0 || sorted[i] >= sz.vocab) return "engine_set_logit_bias: token id out of range";
             if (i != 0 && sorted[i] == sorted[i - 1]) return "engine_set_logit_bias: a token id appears twice";
             if (!(std::isfinite(values[i]) || values[i] == -INFINITY)) return "engine_set_logit_bias: values must be finite or -inf";
+        }
+        pen_write(slot, v, ed);
+        return nullptr;
+    }
+    // ctx: the slot's context length (slot_table.h).  Changing parameters of an armed slot keeps s0 and the sequence; switching
+    // everything off and on again makes s0 the current context length
+    const char *set_dry(int slot, float multiplier, float base, int allowed_length, int range, int no_repeat_ngram, const int32_t *breakers, int n_breakers,
+                        int ctx, SettingsEdits &ed) {
+        if (!(std::isfinite(multiplier) && multiplier >= 0.f)) return "engine_set_dry: multiplier must be finite and >= 0 (0 = off)";
+        if (!(std::isfinite(base) && base >= 1.f)) return "engine_set_dry: base must be finite and >= 1";
+        if (allowed_length < 1) return "engine_set_dry: allowed_length must be >= 1";
+        if (range < 0) return "engine_set_dry: range must be >= 0 (0 = the whole recorded sequence)";
+        if (no_repeat_ngram != 0 && (no_repeat_ngram < 2 || no_repeat_ngram > sz.dry_max_match)) return "engine_set_dry: no_repeat_ngram must be 0 (off) or 2 .. 64";
+        if (n_breakers < 0 || n_breakers > sz.dry_max_breakers) return "engine_set_dry: between 0 and TL_MAX_DRY_BREAKERS (64) breakers";
+        if (n_breakers != 0 && !breakers) return "engine_set_dry: null argument";
+        if (sz.vocab > sz.sampler_max_vocab) return "engine_set_dry: vocabulary larger than 524,288 tokens";
+        if (sz.dry_seq_cap <= 0) return "engine_set_dry: this engine holds no sequence rows";
+        PenaltyParams v = slots[slot].pen;
+        v.dry_breakers.assign(breakers, breakers + n_breakers);
+        std::vector<int32_t> sorted(v.dry_breakers);
+        std::sort(sorted.begin(), sorted.end());
+        for (int i = 0; i < n_breakers; ++i) {
+            if (sorted[i] < 0 || sorted[i] >= sz.vocab) return "engine_set_dry: breaker id out of range";
+            if (i != 0 && sorted[i] == sorted[i - 1]) return "engine_set_dry: a breaker id appears twice";
+        }
+        const bool was = v.dry_on();
+        v.dry_multiplier = multiplier, v.dry_base = base, v.dry_allowed = allowed_length, v.dry_range = range, v.ngram = no_repeat_ngram;
+        if (!v.dry_on()) {  // off: the defaults, so that two switched-off slots compare equal
+            const PenaltyParams d{};
+            v.dry_base = d.dry_base, v.dry_allowed = d.dry_allowed, v.dry_range = d.dry_range, v.dry_s0 = 0, v.dry_breakers.clear();
+        } else if (!was) {
+            v.dry_s0 = ctx;
         }
         pen_write(slot, v, ed);
         return nullptr;
@@ -314,6 +367,10 @@ class SlotSettings {
             pen_write(dst, v, ed);  // (a dst that starts to process has its history row cleared ahead of the copy)
             const size_t V = (size_t)sz.vocab;
             if (v.processes()) ed.list.push_back({SettingsEdit::COPY, SB_PROCESS, at.pen_history + dst * V * 2, 0, at.pen_history + src * V * 2, V * 2, nullptr});
+            if (v.dry_on()) {  // the sequence row travels too (the table is all zeros between steps)
+                const size_t row = (size_t)sz.dry_seq_cap * 4;
+                ed.list.push_back({SettingsEdit::COPY, SB_DRY, at.dry_seq + dst * row, 0, at.dry_seq + src * row, row, nullptr});
+            }
             if (v.grammar) {  // the automaton state travels like the history
                 const int b = v.grammar.stack ? SB_STACK : SB_GRAMMAR;
                 const size_t r = (size_t)(v.grammar.stack ? sz.stack_record_bytes : sz.grammar_record_bytes), o = v.grammar.stack ? 0 : at.gr_state;
@@ -414,6 +471,8 @@ class SlotSettings {
     }
     // Does the slot, taking part in a step, process its logits?  (runs: what the table says of the slot)
     bool processes(int slot, bool runs) const { return runs && slots[slot].pen.processes(); }
+    // ... and does it record the ids it is fed (dry.h)?
+    bool records(int slot, bool runs) const { return runs && slots[slot].pen.dry_on(); }
     // The step's plan over slots [slot0, slot0 + n): runs(slot) is the table's answer (live, neither parked nor stopped).  Truncation
     // applies to a slot that samples: a greedy slot is never filtered (every filter keeps the maximum), so its parameters do not change
     // the plan
@@ -429,6 +488,7 @@ class SlotSettings {
             f.processes |= processes;
             f.grammar |= processes && s.pen.grammar;
             f.stack_grammar |= processes && s.pen.grammar && s.pen.grammar.stack;
+            f.dry |= s.pen.dry_on();
             f.truncates |= truncates;
             f.mirostat |= truncates && s.trn.mirostat();
             f.lora |= exists(SB_LORA) && s.lora >= 0;
@@ -508,6 +568,10 @@ class SlotSettings {
         wordf(SB_PROCESS, at.pen_freq + slot * 4, v.frequency, ed);
         word(SB_PROCESS, at.pen_bias_n + slot * 4, (int32_t)v.bias_ids.size(), ed);
         if (has(SB_GRAMMAR, ed)) word64(SB_GRAMMAR, at.gr_ptr + slot * 8, v.grammar.dev, ed);
+        if (has(SB_DRY, ed)) {  // the two words that arm a row (dry.h)
+            wordf(SB_DRY, at.dry_mult + slot * 4, v.dry_multiplier, ed);
+            word(SB_DRY, at.dry_ngram + slot * 4, v.ngram, ed);
+        }
     }
     // the slot's parameters and bias list become `v` (validated).  History is tracked from the call that makes the slot process: that
     // call empties the slot's row of the table.  Only what differs from the mirror is written; a parked slot's words stay neutral
@@ -521,6 +585,9 @@ class SlotSettings {
         const bool rep = cur.repetition != v.repetition, pres = cur.presence != v.presence, freq = cur.frequency != v.frequency;
         const bool bias = cur.bias_ids != v.bias_ids || (!v.bias_values.empty() && memcmp(cur.bias_values.data(), v.bias_values.data(), v.bias_values.size() * 4) != 0);
         const bool grammar = cur.grammar.id != v.grammar.id;
+        const bool dry = !cur.dry_same(v), dry_mult = cur.dry_multiplier != v.dry_multiplier, dry_ngram = cur.ngram != v.ngram;
+        const bool dry_brk = cur.dry_breakers != v.dry_breakers;
+        if (v.dry_on()) ed.needs |= 1u << SB_DRY;
         if (grammar) ed.needs |= 1u << SB_GRAMMAR | (v.grammar && v.grammar.stack ? 1u << SB_STACK : 0u);
         cur = v;
         if (bias && !cur.bias_ids.empty()) {  // (from the mirror: it outlives the copy)
@@ -528,9 +595,20 @@ class SlotSettings {
             ed.list.push_back({SettingsEdit::UPLOAD, SB_PROCESS, at.pen_bias_ids + row, 0, 0, n, cur.bias_ids.data()});
             ed.list.push_back({SettingsEdit::UPLOAD, SB_PROCESS, at.pen_bias_values + row, 0, 0, n, cur.bias_values.data()});
         }
+        if (dry && has(SB_DRY, ed)) {  // the words a row reads only once it is armed
+            if (dry_brk && !cur.dry_breakers.empty())
+                ed.list.push_back({SettingsEdit::UPLOAD, SB_DRY, at.dry_breakers + (size_t)slot * sz.dry_max_breakers * 4, 0, 0, cur.dry_breakers.size() * 4, cur.dry_breakers.data()});
+            wordf(SB_DRY, at.dry_base + slot * 4, v.dry_base, ed);
+            word(SB_DRY, at.dry_allowed + slot * 4, v.dry_allowed, ed);
+            word(SB_DRY, at.dry_range + slot * 4, v.dry_range, ed);
+            word(SB_DRY, at.dry_s0 + slot * 4, v.dry_s0, ed);
+            word(SB_DRY, at.dry_nbreak + slot * 4, (int32_t)v.dry_breakers.size(), ed);
+        }
         if (parked) {
             processing_words(slot, false, ed);
         } else {
+            if (dry_mult && has(SB_DRY, ed)) wordf(SB_DRY, at.dry_mult + slot * 4, v.dry_multiplier, ed);
+            if (dry_ngram && has(SB_DRY, ed)) word(SB_DRY, at.dry_ngram + slot * 4, v.ngram, ed);
             if (rep) wordf(SB_PROCESS, at.pen_rep + slot * 4, v.repetition, ed);
             if (pres) wordf(SB_PROCESS, at.pen_pres + slot * 4, v.presence, ed);
             if (freq) wordf(SB_PROCESS, at.pen_freq + slot * 4, v.frequency, ed);

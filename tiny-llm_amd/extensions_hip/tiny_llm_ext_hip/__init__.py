@@ -124,6 +124,8 @@ class TlStepCheck(ctypes.Structure):
 
 TL_MAX_TOP_LOGPROBS = 20
 TL_MAX_LOGIT_BIAS = 1024  # entries of a slot's logit-bias list (include/tinyllm_engine.h)
+TL_DRY_MAX_MATCH = 64     # the longest match DRY and the n-gram ban look at
+TL_MAX_DRY_BREAKERS = 64  # entries of a slot's DRY breaker list
 
 
 class TlTokenLogprob(ctypes.Structure):
@@ -287,6 +289,8 @@ _SIGNATURES.update({
     "tl_engine_set_penalties": (_c_int, [_c_void_p, _c_int, _c_float, _c_float, _c_float]),
     "tl_engine_set_logit_bias": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _P(_c_float), _c_int]),
     "tl_process_logits": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 9),
+    "tl_engine_set_dry": (_c_int, [_c_void_p, _c_int, _c_float, _c_float, _c_int, _c_int, _c_int, _P(ctypes.c_int32), _c_int]),
+    "tl_dry_rows": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 11 + [_c_int, _c_void_p]),
     "tl_engine_set_truncation": (_c_int, [_c_void_p, _c_int, _c_float, _c_float]),
     "tl_engine_set_mirostat": (_c_int, [_c_void_p, _c_int, _c_float, _c_float]),
     "tl_engine_mirostat_mu": (_c_int, [_c_void_p, _c_int, _P(_c_float)]),
@@ -1359,6 +1363,56 @@ def process_logits(logits: torch.Tensor, history: torch.Tensor, repetition=1.0, 
     out = torch.empty_like(logits)
     check(_lib.tl_process_logits(logits.data_ptr(), rows, vocab, history.data_ptr(), r_t.data_ptr(), p_t.data_ptr(), f_t.data_ptr(),
                                  ids_t.data_ptr(), vals_t.data_ptr(), n_t.data_ptr(), out.data_ptr(), _stream()))
+    return out
+
+
+def dry_rows(logits: torch.Tensor, sequences: torch.Tensor, start, end, multiplier=0.0, base=1.75, allowed_length=2, range=0,  # noqa: A002
+             no_repeat_ngram=0, breakers=None, table: torch.Tensor | None = None) -> torch.Tensor:
+    """The decode engine's DRY and n-gram ban (tl_dry_rows) over rows of bf16 logits [rows, vocab]: ``sequences`` [rows, cap] int32 on the
+    GPU, row r holding S[start[r] .. end[r]]; the parameters a scalar or one value per row; ``breakers`` None, or one sequence of token ids
+    per row (at most TL_MAX_DRY_BREAKERS each).  ``table``: the match table [rows, vocab] of uint32 words in an int32 tensor, all zeros
+    (made here when None); it is all zeros again after the call.  Returns the rewritten rows [rows, vocab] bf16."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("dry_rows takes a [rows, vocab] bf16 tensor on the GPU")
+    if sequences.dtype != torch.int32 or sequences.dim() != 2 or sequences.shape[0] != logits.shape[0] or not sequences.is_cuda:
+        raise ValueError("sequences must be a [rows, cap] int32 tensor on the GPU")
+    rows, vocab, dev = logits.shape[0], logits.shape[1], logits.device
+    sequences = sequences.contiguous()
+    cap = sequences.shape[1]
+
+    def per_row(v, dtype, what):
+        t = torch.as_tensor(v, dtype=dtype).reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(rows)
+        if t.numel() != rows:
+            raise ValueError(f"{what} needs one value per row")
+        return t.contiguous().to(dev)
+
+    start_t, end_t = per_row(start, torch.int32, "start"), per_row(end, torch.int32, "end")
+    if int(end_t.max()) >= cap:
+        raise ValueError("end must lie inside the sequence capacity")
+    m_t, b_t = per_row(multiplier, torch.float32, "multiplier"), per_row(base, torch.float32, "base")
+    a_t, r_t = per_row(allowed_length, torch.int32, "allowed_length"), per_row(range, torch.int32, "range")
+    n_t = per_row(no_repeat_ngram, torch.int32, "no_repeat_ngram")
+    lists = [()] * rows if breakers is None else [tuple(b or ()) for b in breakers]
+    if len(lists) != rows:
+        raise ValueError("breakers needs one sequence (or None) per row")
+    nb_h = torch.zeros(rows, dtype=torch.int32)
+    brk_h = torch.zeros((rows, TL_MAX_DRY_BREAKERS), dtype=torch.int32)
+    for i, ids in enumerate(lists):
+        if len(ids) > TL_MAX_DRY_BREAKERS:
+            raise ValueError(f"at most {TL_MAX_DRY_BREAKERS} breakers per row")
+        nb_h[i] = len(ids)
+        if ids:
+            brk_h[i, :len(ids)] = torch.tensor(ids, dtype=torch.int32)
+    nb_t, brk_t = nb_h.to(dev), brk_h.to(dev)
+    if table is None:
+        table = torch.zeros((rows, vocab), dtype=torch.int32, device=dev)
+    if table.dtype != torch.int32 or tuple(table.shape) != (rows, vocab) or not table.is_cuda or not table.is_contiguous():
+        raise ValueError("table must be a contiguous [rows, vocab] int32 tensor on the GPU")
+    out = logits.contiguous().clone()
+    check(_lib.tl_dry_rows(sequences.data_ptr(), rows, cap, start_t.data_ptr(), end_t.data_ptr(), m_t.data_ptr(), b_t.data_ptr(), a_t.data_ptr(),
+                           r_t.data_ptr(), n_t.data_ptr(), brk_t.data_ptr(), nb_t.data_ptr(), table.data_ptr(), out.data_ptr(), vocab, _stream()))
     return out
 
 

@@ -388,6 +388,19 @@ class DecodeEngine:
         (1, 0, 0) forget it.  begin / release make the slot neutral, move carries everything along, fork copies it."""
         _ext.check(_lib.tl_engine_set_penalties(self._h, slot, *penalty_args(repetition, presence, frequency)))
 
+    def set_dry(self, slot: int, multiplier: float = 0.0, base: float = 1.75, allowed_length: int = 2, range: int = 0,  # noqa: A002
+                no_repeat_ngram: int = 0, breakers: Sequence[int] = ()) -> None:
+        """DRY and the n-gram ban on the device (tl_engine_set_dry): repetition control that looks at the order of the slot's tokens.
+        DRY (text-generation-webui's sampler) subtracts ``multiplier * base ** (L - allowed_length)`` from the token that would extend a
+        verbatim repeat of L >= ``allowed_length`` tokens (matches are capped at 64, looked for in the last ``range`` tokens, 0 = all, and
+        never run across a token of ``breakers``: dry_breaker_ids); ``no_repeat_ngram`` n (0 = off, else 2 .. 64) bans the token that
+        would complete an n-gram the sequence already holds, as Hugging Face's no_repeat_ngram_size.  The ids are recorded from the call
+        that arms the slot, so call this before the prompt's prefill; multiplier 0 with no_repeat_ngram 0 switches both off.  begin /
+        release switch them off, move carries everything along, fork copies it."""
+        args = dry_args(multiplier, base, allowed_length, range, no_repeat_ngram, breakers, self.vocab_size)
+        ids = (ctypes.c_int32 * max(1, len(args[5])))(*args[5])
+        _ext.check(_lib.tl_engine_set_dry(self._h, slot, args[0], args[1], args[2], args[3], args[4], ids, len(args[5])))
+
     def set_truncation(self, slot: int, min_p: float = 0.0, typical_p: float = 1.0) -> None:
         """Per-slot min-p and locally typical sampling on the device (tl_engine_set_truncation): every row a SAMPLING slot chooses a
         token from is first filtered -- min-p keeps p_i >= min_p * p_max (0 = off), typical-p the tokens whose surprise is closest to
@@ -752,7 +765,8 @@ class DecodeEngine:
                  logprobs: int | None = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                  frequency_penalty: float = 0.0, logit_bias=None, grammar: "Grammar | None" = None, min_p: float = 0.0,
                  typical_p: float = 1.0, mirostat_tau: float = 0.0, mirostat_eta: float = 0.1, lora: int | None = None,
-                 stop: "StopSet | None" = None, decode_block: int = 32):
+                 stop: "StopSet | None" = None, decode_block: int = 32, dry_multiplier: float = 0.0, dry_base: float = 1.75,
+                 dry_allowed_length: int = 2, dry_range: int = 0, dry_breakers: Sequence[int] = (), no_repeat_ngram: int = 0):
         """One request: prefill, then ``max_new_tokens - 1`` decode steps in one call; greedy unless ``temperature`` > 0 (the
         device sampler, set_sampling).  With ``logprobs`` an int (0 .. 20 alternatives, set_logprobs): returns (ids, records).
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` (set_penalties, set_logit_bias) are set
@@ -765,14 +779,17 @@ class DecodeEngine:
         ``stop``: a StopSet (make_stop_set).  The slot is armed with it and the budget ``max_new_tokens`` before the prefill, decodes in
         blocks of ``decode_block`` steps and leaves after the block in which it stopped; the result is the ids up to and including the
         stopping token -- exactly ``stop_state().generated`` of them -- and likewise the records; ``last_stop_state`` keeps the slot's
-        final StopState.  Without ``stop`` the call is unchanged."""
+        final StopState.  Without ``stop`` the call is unchanged.  ``dry_multiplier`` / ``dry_base`` / ``dry_allowed_length`` /
+        ``dry_range`` / ``dry_breakers`` and ``no_repeat_ngram`` (set_dry) are set before the prefill too, so the prompt's ids are part of
+        the sequence the matches are looked for in."""
         if stop is not None and (isinstance(decode_block, bool) or not isinstance(decode_block, int) or decode_block < 1):
             raise ValueError("generate: decode_block is a positive int")
         settings = request_settings(
             {"temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed, "min_p": min_p, "typical_p": typical_p,
              "mirostat_tau": mirostat_tau, "mirostat_eta": mirostat_eta, "repetition_penalty": repetition_penalty,
              "presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty, "logit_bias": logit_bias, "grammar": grammar,
-             "lora": lora}, 1, vocab_size=self.vocab_size, logprobs=logprobs, stop=stop, limits=[max_new_tokens])[0]
+             "lora": lora, "dry_multiplier": dry_multiplier, "dry_base": dry_base, "dry_allowed_length": dry_allowed_length,
+             "dry_range": dry_range, "dry_breakers": dry_breakers, "no_repeat_ngram": no_repeat_ngram}, 1, vocab_size=self.vocab_size, logprobs=logprobs, stop=stop, limits=[max_new_tokens])[0]
         top_n = settings.top_n
         self.begin(slot)
         try:
@@ -947,8 +964,58 @@ def penalty_args(repetition: float = 1.0, presence: float = 0.0, frequency: floa
     return float(repetition), float(presence), float(frequency)
 
 
+DRY_OFF = (0.0, 1.75, 2, 0, 0, ())  # dry_args of a request with neither DRY nor the n-gram ban
+
+
+def dry_args(multiplier: float = 0.0, base: float = 1.75, allowed_length: int = 2, range: int = 0, no_repeat_ngram: int = 0,  # noqa: A002
+             breakers: Sequence[int] = (), vocab_size: int = 0) -> tuple:
+    """Validated (multiplier, base, allowed_length, range, no_repeat_ngram, breakers) for tl_engine_set_dry: multiplier finite and >= 0
+    (0 = off), base finite and >= 1, allowed_length >= 1, range >= 0 (0 = everything recorded), no_repeat_ngram 0 (off) or 2 .. 64,
+    breakers up to 64 distinct ids (inside ``vocab_size`` where that is given)."""
+    for name, v in (("dry_multiplier", multiplier), ("dry_base", base)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+    if multiplier < 0:
+        raise ValueError(f"dry_multiplier must be >= 0, got {multiplier!r}")
+    if base < 1:
+        raise ValueError(f"dry_base must be >= 1, got {base!r}")
+    for name, v in (("dry_allowed_length", allowed_length), ("dry_range", range), ("no_repeat_ngram", no_repeat_ngram)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} must be an int, got {v!r}")
+    if allowed_length < 1:
+        raise ValueError(f"dry_allowed_length must be >= 1, got {allowed_length!r}")
+    if range < 0:
+        raise ValueError(f"dry_range must be >= 0, got {range!r}")
+    if no_repeat_ngram != 0 and not 2 <= no_repeat_ngram <= _ext.TL_DRY_MAX_MATCH:
+        raise ValueError(f"no_repeat_ngram must be 0 (off) or 2 .. {_ext.TL_DRY_MAX_MATCH}, got {no_repeat_ngram!r}")
+    ids = tuple(breakers or ())
+    if any(isinstance(t, bool) or not isinstance(t, int) or t < 0 or (vocab_size and t >= vocab_size) for t in ids):
+        raise ValueError("dry_breakers must be token ids inside the vocabulary")
+    if len(set(ids)) != len(ids):
+        raise ValueError("dry_breakers: a token id appears twice")
+    if len(ids) > _ext.TL_MAX_DRY_BREAKERS:
+        raise ValueError(f"dry_breakers takes at most {_ext.TL_MAX_DRY_BREAKERS} ids, got {len(ids)}")
+    return float(multiplier), float(base), allowed_length, range, no_repeat_ngram, ids
+
+
+def dry_breaker_ids(tokenizer, strings: Sequence[str]) -> list[int]:
+    """The breaker ids of ``strings`` as text-generation-webui derives them: each string gives the LAST id of its encoding (a breaker is
+    one token); duplicates are dropped, the order kept."""
+    out: list[int] = []
+    for s in strings:
+        try:
+            ids = tokenizer.encode(s, add_special_tokens=False)
+        except TypeError:
+            ids = tokenizer.encode(s)
+        ids = getattr(ids, "ids", ids)
+        if len(ids) and int(ids[-1]) not in out:
+            out.append(int(ids[-1]))
+    return out
+
+
 SETTINGS_KEYS = {"temperature", "top_k", "top_p", "seed", "min_p", "typical_p", "mirostat_tau", "mirostat_eta", "repetition_penalty",
-                 "presence_penalty", "frequency_penalty", "logit_bias", "grammar", "lora"}
+                 "presence_penalty", "frequency_penalty", "logit_bias", "grammar", "lora", "dry_multiplier", "dry_base",
+                 "dry_allowed_length", "dry_range", "dry_breakers", "no_repeat_ngram"}
 
 
 def request_settings(sampling, n_prompts: int, base_seed: int = 0, vocab_size: int = 0, logprobs: int | None = None, stop=None,
@@ -984,7 +1051,9 @@ def request_settings(sampling, n_prompts: int, base_seed: int = 0, vocab_size: i
         if grammar is not None and not isinstance(grammar, Grammar):
             raise ValueError("sampling['grammar'] must be a Grammar (DecodeEngine.make_grammar) or None")
         trn = truncation_args(d.get("min_p", 0.0), d.get("typical_p"), d.get("mirostat_tau", 0.0), d.get("mirostat_eta", 0.1), top_k=smp[1], top_p=smp[2])
-        out.append(RequestSettings(sampling=smp, truncation=trn, penalties=pen, bias=dict(bias) if bias else {}, grammar=grammar,
+        dry = dry_args(d.get("dry_multiplier", 0.0), d.get("dry_base", 1.75), d.get("dry_allowed_length", 2), d.get("dry_range", 0),
+                       d.get("no_repeat_ngram", 0), d.get("dry_breakers") or (), vocab_size)
+        out.append(RequestSettings(sampling=smp, truncation=trn, penalties=pen, bias=dict(bias) if bias else {}, grammar=grammar, dry=dry,
                                    armed=stops is not None, stop=stops[i] if stops is not None else None, budget=limits[i]))
     loras = request_loras(sampling, n_prompts) or [-1] * n_prompts
     top_n = logprobs_arg(logprobs)

@@ -78,6 +78,7 @@ class RequestSettings(NamedTuple):
     armed: bool = False                          # stop conditions on the device: the slot is armed with ``stop`` and ``budget``
     stop: Any = None                             # a StopSet or None
     budget: int = 0                              # the request's max_new_tokens
+    dry: tuple = (0.0, 1.75, 2, 0, 0, ())        # dry_args: multiplier, base, allowed_length, range, no_repeat_ngram, breaker ids
 
     def apply(self, engine, slot: int) -> None:
         """The one setter sequence, on a freshly begun slot and before its prompt's first chunk:
@@ -99,6 +100,8 @@ class RequestSettings(NamedTuple):
             engine.set_logit_bias(slot, self.bias)
         if self.grammar is not None:
             engine.set_grammar(slot, self.grammar)
+        if self.dry[0] > 0.0 or self.dry[4] > 0:
+            engine.set_dry(slot, *self.dry)
         if self.top_n >= 0:
             engine.set_logprobs(slot, self.top_n)
         if self.armed:
