@@ -922,7 +922,8 @@ size_t tl_engine_step_bytes(const tl_engine *e, int batch);
  *   7 step end (argmax + embed; with a processing slot also the logit-processing launch ahead of it).
  * gemv_bytes[k] = algorithmic W4 bytes those launches stream (packed nibbles + bf16 scales and biases).
  * span_us = first start to last end of the step (includes the small reduce kernels this mode inserts
- * between launches, so it is NOT the production step time).  Synchronises the stream. */
+ * between launches, so it is NOT the production step time).  Synchronises the stream.  Like tl_engine_decode it must be called
+ * with the engine's own device current (TL_ERR_INVALID otherwise). */
 typedef struct tl_step_profile {
     double kernel_us[8];
     int launches[8];
@@ -943,7 +944,9 @@ int tl_engine_profile_step(tl_engine *e, int batch, tl_step_profile *out);
  *                      first_offset (element index inside the region) name one offence of the earliest offending launch;
  *   written_once_plan  1 when the plan uses the per-layer buffers throughout -- the only plans the engine replays as AQL packets;
  *   a value read before the step wrote it is a NaN: the caller checks the logits (finite, and equal to an unchecked engine's).
- * A rewrite of an element with the value it already holds is not seen (and cannot be read stale).  Synchronises. */
+ * A rewrite of an element with the value it already holds is not seen (and cannot be read stale).  Synchronises.  Like
+ * tl_engine_decode it must be called with the engine's own device current (TL_ERR_INVALID otherwise), and it returns the status of
+ * the stop reconciliation behind the step. */
 typedef struct tl_step_check {
     int launches, written_once_plan, n_splits;
     long double_writes, elements_written;

@@ -159,4 +159,5 @@ def test_header_and_sources_declare_the_interface():
                    "tl_mirostat_update_rows", "closed under ties"):
         assert needle in header, needle
     engine = (ROOT / "tiny-llm_amd" / "csrc" / "engine.hip").read_text()
-    assert '#include "truncate.h"' in engine and "1L << 57" in engine
+    route = (ROOT / "tiny-llm_amd" / "csrc" / "replay_route.h").read_text()  # the plan key's bits, which engine.hip takes from there
+    assert '#include "truncate.h"' in engine and '#include "replay_route.h"' in engine and "1L << 57" in route

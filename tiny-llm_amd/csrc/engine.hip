@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 
 #include "decode_linear.h"  // the projection router; with it common.h, engine_kernels.h and the decode matmuls' headers
 #include "device_block.h"
@@ -21,6 +22,7 @@
 #include "decode_attention.h"  // the decode attention's launch; with it attn_plan.h and attn_mfma.h
 #include "aql.h"
 #include "prefix_cache.h"
+#include "replay_route.h"
 #include "kv_copy.h"
 #include "beam.h"
 #include "kv_swap.h"
@@ -229,12 +231,15 @@ struct tl_engine {
 
     bool warmed = false;
     // a captured decode step: the executable graph and, where the step may ride the AQL route (below), the same nodes as a program of
-    // dispatch packets.  Keyed by (batch, AttnPlan::key() | step_key_bits(features))
+    // dispatch packets.  Move-only; a plan that goes destroys its graph.  Keyed and kept by replay_route.h
     struct DecodePlan {
-        hipGraphExec_t exec = nullptr;
+        struct ExecDestroy {
+            void operator()(hipGraphExec_t exec) const { (void)hipGraphExecDestroy(exec); }
+        };
+        std::unique_ptr<std::remove_pointer_t<hipGraphExec_t>, ExecDestroy> exec;
         std::unique_ptr<AqlProgram> program;
     };
-    std::map<std::pair<int, long>, DecodePlan> plans;
+    PlanCache<DecodePlan> plans;
     // AQL replay (aql.h; TL_AQL=1 at create): a captured step also becomes a program of hand-written dispatch packets on the engine's own
     // HSA queue; a plan without a program (a kernel outside the device-only code objects, a node that is not a kernel) stays on hipGraphLaunch
     bool aql_on = false;
@@ -659,32 +664,7 @@ static void launch_stop(tl_engine *e, int rows, int slot0, ProfCtx *pc) {
 }
 
 // ---- which launches a step needs ---------------------------------------------------------------------------------------------------
-// the bits a decode plan's key carries above its split plan (tl_engine_decode): with all clear the step is the greedy program
-static long step_key_bits(const StepFeatures &f) {
-    // bit 62: the step ends with the sampling twin of step_end_kernel, bit 61: with the logprob twin (step_end.h)
-    return (f.samples ? (1L << 62) : 0L) | (f.logprobs ? (1L << 61) : 0L) |
-           // bit 60: the processing launch (logit_process.h) stands between the lm_head and the step end
-           // bit 59: ... in its regex mode (grammar.h); bit 58: in its stack mode (grammar_stack.h)
-           (f.processes ? (1L << 60) : 0L) | (f.grammar ? (1L << 59) : 0L) | (f.stack_grammar ? (1L << 58) : 0L) |
-           // bit 57: the truncation launch (truncate.h) stands ahead of the step end and the Mirostat update behind it
-           // bit 56: ... and a slot has Mirostat on (the plan keeps the hipGraphLaunch route)
-           (f.truncates ? (1L << 57) : 0L) | (f.mirostat ? (1L << 56) : 0L) |
-           // bit 55: a slot carries a LoRA adapter: the adapter plan (lora.h; hipGraphLaunch)
-           (f.lora ? (1L << 55) : 0L) |
-           // bit 54: a slot is armed with stop conditions: the stop launch (stop.h) stands last (hipGraphLaunch)
-           (f.stop ? (1L << 54) : 0L) |
-           // bit 53: a slot has DRY or the n-gram ban on: the match and apply launches (dry.h) stand behind the processing launch (hipGraphLaunch)
-           (f.dry ? (1L << 53) : 0L);
-}
-// Why a plan with these features never becomes an AQL program (null: it may), the one sentence tl_engine_replay_route reports: bits 54,
-// 55 and 56 above, the stop launch first
-static const char *graph_only_reason(const StepFeatures &f) {
-    if (f.stop) return "a slot is armed with stop conditions (the stop launch reads the token the step end stored and writes the live word)";
-    if (f.lora) return "a slot with a LoRA adapter is live (the adapter plan hands over in shared buffers)";
-    if (f.mirostat) return "a Mirostat slot is live (the update launch reads the token the step end stored)";
-    if (f.dry) return "a slot has DRY or the n-gram ban on (the apply launch writes the processed rows a second time)";
-    return nullptr;
-}
+// (the key bits of a plan and the features that keep it on hipGraphLaunch: replay_route.h)
 // the plan of slots [slot0, slot0 + n), re-derived from the slots' parameters by every call that enqueues or replays a step: a decode step
 // asks over [0, batch), a prefill's first token over its one slot
 static StepFeatures step_features(const tl_engine *e, int slot0, int n) {
@@ -1347,17 +1327,11 @@ extern "C" int tl_engine_set_option(tl_engine *e, const char *name, int value) {
     return TL_OK;
 }
 
-// the captured plans, all of them: their executable graphs are destroyed, their programs go with the records
-static void drop_plans(tl_engine *e) {
-    for (auto &kv : e->plans) (void)hipGraphExecDestroy(kv.second.exec);
-    e->plans.clear();
-}
-
 extern "C" void tl_engine_destroy(tl_engine *e) {
     if (!e) return;
     (void)aql_drain(e);
     (void)hipStreamSynchronize(e->stream);
-    drop_plans(e);
+    e->plans.clear();  // (the executable graphs go while their stream still exists)
     delete e;  // the queue, every DeviceBlock, then the stream the engine created (tl_engine's member order)
 }
 
@@ -1366,10 +1340,7 @@ extern "C" int tl_engine_kv_format(const tl_engine *e) { return e ? e->kv_format
 extern "C" const char *tl_engine_replay_route(const tl_engine *e) {
     static thread_local std::string text;
     if (!e) return "";
-    text = e->aql_on ? std::string("aql") : ("hipgraph" + (e->aql_why.empty() ? std::string() : ": " + e->aql_why));
-    // (a plan of the live slots that keeps hipGraphLaunch on an engine whose other plans ride the route)
-    const char *why = e->aql_on ? graph_only_reason(step_features(e, 0, e->cfg.max_batch)) : nullptr;
-    if (why) text = std::string("hipgraph: ") + why;
+    text = replay_route_text(e->aql_on, e->aql_why, step_features(e, 0, e->cfg.max_batch));
     return text.c_str();
 }
 
@@ -3144,31 +3115,55 @@ static int aql_drain(tl_engine *e) {
 }
 
 // ---- the parts of a decode step around enqueue_step (tl_engine_decode, tl_engine_profile_step, tl_engine_check_step)
-// input activations of slots [0, batch) from their pending token ids, with the RoPE factors and sums of squares of the first step
-static void launch_embed_slots(tl_engine *e, int batch) {
+// What the three entry points ask first: the batch, the device -- launches go to the CURRENT device's copy of a kernel, the AQL packets
+// to the engine's own agent: both must be the engine's device -- and the stops the device has seen (a prefill's first token may have
+// stopped its slot: the plan asks the table)
+static int step_call_begin(tl_engine *e, int batch, const char *who) {
+    TL_REQUIRE(batch > 0 && batch <= e->cfg.max_batch, std::string(who) + ": batch out of range");
+    int dev_now = -1;
+    TL_HIP(hipGetDevice(&dev_now));
+    TL_REQUIRE(dev_now == e->device, "engine_decode: the current HIP device is not the device this engine was created on");
+    return stop_reconcile(e);
+}
+
+// the features of a call's steps; input activations of slots [0, batch) for the first of them from their pending token ids, with its
+// RoPE factors and sums of squares
+static int step_inputs(tl_engine *e, int batch, StepFeatures *f) {
     const tl_engine_config &c = e->cfg;
     hipLaunchKernelGGL(embed_slots_kernel, dim3(batch), dim3(256), 0, e->stream, e->tokens, e->embed.weight_dev,
                        (const uint16_t *)e->embed.scales_dev, (const uint16_t *)e->embed.biases_dev, e->shared.x_out, c.hidden_size,
                        c.vocab_size, e->context_lens, e->rope_table, e->rope_cur, e->rope_positions, c.head_dim / 2, e->shared.ss_x_out);
+    TL_CHECK_LAUNCH("engine embed");
+    *f = step_features(e, 0, batch);
+    if (f->stop) e->stop_dirty = true;  // (a replayed plan launches the stop check without passing through launch_stop)
+    return TL_OK;
 }
 
-// the pages of this step's token in every live slot of [0, batch), poked into the block table, and the step's split plan.  A caller with
-// steps in flight on the AQL queue passes `on_queue`: a new page id drains them first (the poke is a stream launch and must land between
-// the steps), and a failed reservation returns with the queue drained.
-static int prepare_step(tl_engine *e, int batch, AttnPlan *sp, bool *on_queue = nullptr) {
+// what the replay route wants done before its answer is acted on (replay_route.h)
+static int route_first(tl_engine *e, unsigned first) {
+    if (first & DRAIN) TL_TRY(aql_drain(e));
+    if (first & SYNC_STREAM) TL_HIP(hipStreamSynchronize(e->stream));
+    if (first & FLUSH_PLANS) {
+        e->plans.clear();
+        e->stats.graph_cache_flushes++;
+    }
+    return TL_OK;
+}
+// every return of a call passes through ReplayCall::finish (an error return keeps its own status)
+struct ReplayCallEnd {
+    tl_engine *e;
+    ReplayCall &call;
+    ~ReplayCallEnd() { (void)route_first(e, call.finish()); }
+};
+
+// the pages of this step's token in every live slot of [0, batch), poked into the block table, and the step's split plan
+static int prepare_step(tl_engine *e, int batch, AttnPlan *sp, ReplayCall &call) {
     SlotEdits &ed = e->step_edits;  // (reused: a step in which no slot crosses a page boundary allocates nothing)
     ed.clear();
     int max_ctx = 1;
-    const int rc = table_rc(e->table.reserve_step(batch, ed, &max_ctx));
-    if (rc != TL_OK) {
-        if (on_queue) (void)aql_drain(e);
-        return rc;
-    }
+    TL_TRY(table_rc(e->table.reserve_step(batch, ed, &max_ctx)));
     if (!ed.rows.empty()) {
-        if (on_queue && *on_queue) {
-            TL_TRY(aql_drain(e));
-            *on_queue = false;
-        }
+        TL_TRY(route_first(e, call.pages_changed()));
         Pokes pk;
         TL_TRY(apply_edits(e, ed, pk));
         TL_TRY(poke(e, pk));
@@ -3177,107 +3172,98 @@ static int prepare_step(tl_engine *e, int batch, AttnPlan *sp, bool *on_queue = 
     return TL_OK;
 }
 
+// the launches of a step, eagerly on the stream (stamped and checked where `pc` says so)
+static int eager_step(tl_engine *e, int batch, const AttnPlan &sp, const StepFeatures &f, ProfCtx *pc = nullptr) {
+    TL_TRY(enqueue_step(e, batch, sp, f, pc));
+    e->warmed = true;
+    return TL_OK;
+}
+
 // the host mirrors after a step over slots [0, batch): every live slot holds one more token and has produced one more id
-static void step_done(tl_engine *e, int batch) {
+static void step_done(tl_engine *e, int batch, const StepFeatures &f) {
     e->table.step_done(batch);
     for (int b = 0; b < batch; ++b)
         if (e->slot_runs(b)) e->settings.pending_produced(b);
     e->stats.decode_steps++;
+    if (f.lora) e->lora_steps++;
     e->logits_rows = batch, e->logits_slot = -1;
+}
+
+// One REAL eager step as a call of its own (tl_engine_profile_step, tl_engine_check_step), behind step_call_begin and step_inputs: state
+// advances exactly like tl_engine_decode(e, batch, 1, 0)
+static int one_eager_step(tl_engine *e, int batch, const StepFeatures &f, ProfCtx *pc, AttnPlan *sp) {
+    ReplayCall call;  // (stays on the stream)
+    TL_TRY(prepare_step(e, batch, sp, call));
+    TL_TRY(eager_step(e, batch, *sp, f, pc));
+    step_done(e, batch, f);
+    return stop_reconcile(e);
+}
+
+// a step of tl_engine_decode behind prepare_step and the route's answer for it: captured into a plan of the cache
+static int capture_step(tl_engine *e, int batch, const AttnPlan &sp, const StepFeatures &f, const PlanKey &key, tl_engine::DecodePlan **out) {
+    hipGraph_t graph = nullptr;
+    TL_HIP(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue_step(e, batch, sp, f);
+    const hipError_t ce = hipStreamEndCapture(e->stream, &graph);
+    if (rc != TL_OK) {
+        if (graph) (void)hipGraphDestroy(graph);
+        return rc;
+    }
+    if (ce != hipSuccess) return fail(TL_ERR_HIP, std::string("engine_decode: graph capture failed: ") + hipGetErrorString(ce));
+    tl_engine::DecodePlan plan;
+    hipGraphExec_t exec = nullptr;
+    const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    plan.exec.reset(exec);
+    // the same nodes as packet templates (aql.h); a plan whose program cannot be built keeps the graph route
+    if (ie == hipSuccess && program_wanted(e->aql_on, e->step_written_once, f)) {
+        auto prog = std::make_unique<AqlProgram>();
+        std::string why;
+        if (aql_program_from_graph(*e->aql_rt, graph, e->stream, *prog, why) == 0) plan.program = std::move(prog);
+    }
+    (void)hipGraphDestroy(graph);
+    if (ie != hipSuccess) return fail(TL_ERR_HIP, std::string("engine_decode: graph instantiate failed: ") + hipGetErrorString(ie));
+    *out = e->plans.insert(key, std::move(plan));
+    e->stats.graph_captures++;
+    return TL_OK;
 }
 
 extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_graph) {
     TL_REQUIRE(e, "engine_decode: null engine");
-    TL_REQUIRE(batch > 0 && batch <= e->cfg.max_batch, "engine_decode: batch out of range");
+    TL_TRY(step_call_begin(e, batch, "engine_decode"));
     TL_REQUIRE(steps >= 0, "engine_decode: steps must be nonnegative");
     if (steps == 0) return TL_OK;
-    {  // launches go to the CURRENT device's copy of a kernel, the AQL packets to the engine's own agent: both must be the engine's device
-        int dev_now = -1;
-        TL_HIP(hipGetDevice(&dev_now));
-        TL_REQUIRE(dev_now == e->device, "engine_decode: the current HIP device is not the device this engine was created on");
-    }
-    TL_TRY(stop_reconcile(e));  // (a prefill's first token may have stopped its slot: the plan below asks the table)
-    // input activations of the first step come from the pending token ids
-    launch_embed_slots(e, batch);
-    TL_CHECK_LAUNCH("engine embed");
-    const StepFeatures f = step_features(e, 0, batch);
-    if (f.stop) e->stop_dirty = true;  // (a replayed plan launches the stop check without passing through launch_stop)
-    bool on_queue = false;  // steps of this call are in flight on the AQL queue (the stream is idle and must stay so until they are drained)
+    StepFeatures f;
+    TL_TRY(step_inputs(e, batch, &f));
+    ReplayCall call;
+    const ReplayCallEnd end{e, call};
     for (int s = 0; s < steps; ++s) {
         AttnPlan sp;
-        TL_TRY(prepare_step(e, batch, &sp, &on_queue));
-        if (use_graph && e->warmed) {
-            const auto key = std::make_pair(batch, sp.key() | step_key_bits(f));
-            auto it = e->plans.find(key);
-            if (it == e->plans.end()) {
-                // The split plan (and with it the key) changes every 64 * n_splits tokens of context: a long run would keep one
-                // ~220-node executable graph per plan and row bucket for ever.  Plans are visited in order of growing context, so
-                // when the cache is full the old ones are dead: drop them all (a live plan is re-captured once, ~0.3 ms).
-                if (on_queue) {
-                    TL_TRY(aql_drain(e));
-                    on_queue = false;
-                }
-                if (e->plans.size() >= 48) {
-                    TL_HIP(hipStreamSynchronize(e->stream));
-                    drop_plans(e);
-                    e->stats.graph_cache_flushes++;
-                }
-                hipGraph_t graph = nullptr;
-                TL_HIP(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-                const int rc = enqueue_step(e, batch, sp, f);
-                const hipError_t ce = hipStreamEndCapture(e->stream, &graph);
-                if (rc != TL_OK) {
-                    if (graph) (void)hipGraphDestroy(graph);
-                    return rc;
-                }
-                if (ce != hipSuccess) return fail(TL_ERR_HIP, std::string("engine_decode: graph capture failed: ") + hipGetErrorString(ce));
-                tl_engine::DecodePlan plan;
-                const hipError_t ie = hipGraphInstantiate(&plan.exec, graph, nullptr, nullptr, 0);
-                // the same nodes as packet templates (aql.h) where every hand-over is written once per step and no launch needs a
-                // boundary with cache maintenance; a plan whose program cannot be built keeps the graph route
-                if (ie == hipSuccess && e->aql_on && e->step_written_once && !graph_only_reason(f)) {
-                    auto prog = std::make_unique<AqlProgram>();
-                    std::string why;
-                    if (aql_program_from_graph(*e->aql_rt, graph, e->stream, *prog, why) == 0) plan.program = std::move(prog);
-                }
-                (void)hipGraphDestroy(graph);
-                if (ie != hipSuccess) return fail(TL_ERR_HIP, std::string("engine_decode: graph instantiate failed: ") + hipGetErrorString(ie));
-                it = e->plans.emplace(key, std::move(plan)).first;
-                e->stats.graph_captures++;
-            }
-            if (it->second.program) {
-                bool first = false;
-                if (!on_queue) {  // hand-over stream -> queue: everything enqueued so far (embedding gather, pokes, earlier steps) has run
-                    TL_HIP(hipStreamSynchronize(e->stream));
-                    on_queue = first = true;
-                }
+        TL_TRY(prepare_step(e, batch, &sp, call));
+        const PlanKey key{batch, sp.key() | step_key_bits(f)};
+        tl_engine::DecodePlan *plan = use_graph && e->warmed ? e->plans.find(key) : nullptr;
+        const StepAnswer step = call.step(use_graph != 0, e->warmed, plan != nullptr, e->plans.full());
+        TL_TRY(route_first(e, step.first));
+        if (step.kind == StepKind::EAGER) {
+            TL_TRY(eager_step(e, batch, sp, f));
+        } else {
+            if (step.kind == StepKind::CAPTURE) TL_TRY(capture_step(e, batch, sp, f, key, &plan));
+            const ReplayAnswer go = call.replay(plan->program != nullptr, s + 1 == steps);
+            TL_TRY(route_first(e, go.first));
+            if (go.submit) {
                 std::string why;
-                if (!e->aql_queue->submit(*it->second.program, e->aql_fences, first, s + 1 == steps, why)) {
-                    (void)aql_drain(e);
+                if (!e->aql_queue->submit(*plan->program, e->aql_fences, go.first_packet, go.last_packet, why)) {
+                    (void)route_first(e, call.finish());  // (ahead of the message below, which is the one the caller reads)
                     return fail(TL_ERR_HIP, "engine_decode: " + why);
                 }
                 e->stats.aql_steps++;
             } else {
-                if (on_queue) {
-                    TL_TRY(aql_drain(e));
-                    on_queue = false;
-                }
-                TL_HIP(hipGraphLaunch(it->second.exec, e->stream));
+                TL_HIP(hipGraphLaunch(plan->exec.get(), e->stream));
             }
             e->stats.graph_replays++;
-        } else {
-            if (on_queue) {
-                TL_TRY(aql_drain(e));
-                on_queue = false;
-            }
-            TL_TRY(enqueue_step(e, batch, sp, f));
-            e->warmed = true;
         }
-        step_done(e, batch);
-        if (f.lora) e->lora_steps++;
+        step_done(e, batch, f);
     }
-    // the queue is not the stream: what follows this call (reads, prefills, the next call's embedding gather) is stream-ordered
-    if (on_queue) TL_TRY(aql_drain(e));
+    TL_TRY(route_first(e, call.finish()));
     // a plan with an armed slot: the host mirrors follow the device before the call returns (synchronises, on every route)
     return stop_reconcile(e);
 }
@@ -3317,10 +3303,12 @@ extern "C" int tl_engine_get_stats(const tl_engine *e, tl_engine_stats *out) {
     return TL_OK;
 }
 
+// bytes of a W4 matrix a decode step streams: the packed weights and one (scale, bias) pair per group of 128
+static size_t w4_bytes(const tl_w4 &w) { return (size_t)w.rows * w.cols / 2 + (size_t)w.rows * (w.cols / 128) * 4; }
+
 extern "C" size_t tl_engine_step_bytes(const tl_engine *e, int batch) {
     if (!e) return 0;
     const tl_engine_config &c = e->cfg;
-    auto w4_bytes = [](const tl_w4 &w) { return (size_t)w.rows * w.cols / 2 + (size_t)w.rows * (w.cols / 128) * 4; };
     size_t total = 0;
     for (const auto &l : e->layers) total += w4_bytes(l.wqkv) + w4_bytes(l.wo) + w4_bytes(l.wgu) + w4_bytes(l.wdown);
     total += w4_bytes(e->head());
@@ -3336,26 +3324,21 @@ extern "C" size_t tl_engine_step_bytes(const tl_engine *e, int batch) {
 // in-kernel wall-clock stamps; see tl_step_profile in the header.
 extern "C" int tl_engine_profile_step(tl_engine *e, int batch, tl_step_profile *out) {
     TL_REQUIRE(e && out, "engine_profile_step: null argument");
-    TL_REQUIRE(batch > 0 && batch <= e->cfg.max_batch, "engine_profile_step: batch out of range");
+    TL_TRY(step_call_begin(e, batch, "engine_profile_step"));
     int rate_khz = 0;
-    int dev = 0;
-    TL_HIP(hipGetDevice(&dev));
-    TL_HIP(hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev));
+    TL_HIP(hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, e->device));
     TL_REQUIRE(rate_khz > 0, "engine_profile_step: device reports no wall clock rate");
     TL_HIP(hipStreamSynchronize(e->stream));
     ProfCtx pc;
     if (!pc.alloc(e->cfg, batch, e->stream)) return fail(TL_ERR_HIP, "engine_profile_step: hipMalloc / memset of the stamp buffers failed");
-    launch_embed_slots(e, batch);
+    StepFeatures f;
     AttnPlan sp;
-    int rc = prepare_step(e, batch, &sp);
-    if (rc == TL_OK) rc = enqueue_step(e, batch, sp, step_features(e, 0, batch), &pc);
+    int rc = step_inputs(e, batch, &f);
+    if (rc == TL_OK) rc = one_eager_step(e, batch, f, &pc, &sp);
     if (rc != TL_OK) {
         (void)hipStreamSynchronize(e->stream);
         return rc;
     }
-    e->warmed = true;
-    step_done(e, batch);
-    TL_TRY(stop_reconcile(e));
     std::vector<prof_t> pairs(pc.kinds.size() * 2);
     hipError_t he = hipStreamSynchronize(e->stream);
     if (he == hipSuccess) he = hipMemcpy(pairs.data(), pc.pairs, pairs.size() * sizeof(prof_t), hipMemcpyDeviceToHost);
@@ -3375,7 +3358,6 @@ extern "C" int tl_engine_profile_step(tl_engine *e, int batch, tl_step_profile *
         out->launches[pc.kinds[i]] += 1;
     }
     out->span_us = (last > first ? (double)(last - first) : 0.0) * us_per_tick;
-    auto w4_bytes = [](const tl_w4 &w) { return (double)w.rows * w.cols / 2 + (double)w.rows * (w.cols / 128) * 4; };
     for (const auto &l : e->layers) {
         out->gemv_bytes[0] += w4_bytes(l.wqkv);
         out->gemv_bytes[1] += w4_bytes(l.wo);
@@ -3390,7 +3372,7 @@ extern "C" int tl_engine_profile_step(tl_engine *e, int batch, tl_step_profile *
 // One REAL decode step, launched eagerly like tl_engine_profile_step, with the written-once checker behind every launch (header).
 extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out) {
     TL_REQUIRE(e && out, "engine_check_step: null argument");
-    TL_REQUIRE(batch > 0 && batch <= e->cfg.max_batch, "engine_check_step: batch out of range");
+    TL_TRY(step_call_begin(e, batch, "engine_check_step"));
     *out = tl_step_check{};
     out->first_launch = -1, out->first_kind = -1, out->first_region = -1, out->first_offset = -1;
     TL_TRY(aql_drain(e));
@@ -3423,22 +3405,16 @@ extern "C" int tl_engine_check_step(tl_engine *e, int batch, tl_step_check *out)
     ok = hipMemcpyAsync(ck.report, report0, sizeof(report0), hipMemcpyHostToDevice, e->stream) == hipSuccess;
     if (ok && ck.bytes[1]) ok = hipMemsetAsync(ck.region[1], 0xff, ck.bytes[1], e->stream) == hipSuccess;
     if (!ok) return fail(TL_ERR_HIP, "engine_check_step: initialisation failed");
-    launch_embed_slots(e, batch);
+    StepFeatures f;
+    TL_TRY(step_inputs(e, batch, &f));
     // the shadows = the regions as the step finds them; nothing written yet
     for (int rg = 0; rg < 2 && ok; ++rg)
         if (ck.bytes[rg]) ok = hipMemcpyAsync(ck.shadow[rg], ck.region[rg], ck.bytes[rg], hipMemcpyDeviceToDevice, e->stream) == hipSuccess &&
                                hipMemsetAsync(ck.written[rg], 0, ck.bytes[rg] / 2, e->stream) == hipSuccess;
     if (!ok) return fail(TL_ERR_HIP, "engine_check_step: shadow copy failed");
     AttnPlan sp;
-    int rc = prepare_step(e, batch, &sp);
-    if (rc == TL_OK) {
-        pc.check = &ck;
-        rc = enqueue_step(e, batch, sp, step_features(e, 0, batch), &pc);
-    }
-    if (rc != TL_OK) return rc;
-    e->warmed = true;
-    step_done(e, batch);
-    (void)stop_reconcile(e);
+    pc.check = &ck;
+    TL_TRY(one_eager_step(e, batch, f, &pc, &sp));
     unsigned long long report[8] = {0};
     hipError_t he = hipStreamSynchronize(e->stream);
     if (he == hipSuccess) he = hipMemcpy(report, ck.report, sizeof(report), hipMemcpyDeviceToHost);
