@@ -17,7 +17,11 @@ DEFAULT_PROMPTS = ["What is the capital of France?", "Where is New York City?", 
                    "What is the capital of China?", "Give me a short introduction to large language model."]
 
 
+from tiny_llm_hip import request  # noqa: E402
+
+
 def build_parser() -> argparse.ArgumentParser:
+    """The request flags come from tiny_llm_hip.request's table (shared with main.py) and hold per request; the rest are this script's own."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--model", required=True)
     ap.add_argument("--batch-size", type=int, default=5)
@@ -27,38 +31,7 @@ def build_parser() -> argparse.ArgumentParser:
                     help="K / V pages as bfloat16 (the reference's cache) or FP8 E4M3 codes + power-of-two row scales (extension)")
     ap.add_argument("--enable-thinking", action="store_true")
     ap.add_argument("--raw-prompts", action="store_true", help="do not wrap the prompts in the chat template")
-    ap.add_argument("--sampler-temp", type=float, default=0.0, help="0 = greedy; otherwise the device sampler per request")
-    ap.add_argument("--sampler-top-p", type=float, default=None)
-    ap.add_argument("--sampler-top-k", type=int, default=None)
-    ap.add_argument("--sampler-seed", type=int, default=0, help="request i draws from seed + i")
-    ap.add_argument("--repetition-penalty", type=float, default=1.0, help="per request, on the device; over prompt and output (1 = off)")
-    ap.add_argument("--presence-penalty", type=float, default=0.0, help="per request, on the device; over the output (0 = off)")
-    ap.add_argument("--frequency-penalty", type=float, default=0.0, help="per request, on the device; times the count in the output (0 = off)")
-    ap.add_argument("--dry-multiplier", type=float, default=0.0,
-                    help="per request, on the device: DRY -- subtract multiplier * base ** (L - allowed_length) from the token that would "
-                         "extend a verbatim repeat of L tokens (0 = off)")
-    ap.add_argument("--dry-base", type=float, default=1.75, help="DRY's base (>= 1)")
-    ap.add_argument("--dry-allowed-length", type=int, default=2, help="the longest repeat DRY leaves alone, plus one (>= 1)")
-    ap.add_argument("--dry-range", type=int, default=0, help="DRY looks for repeats in the last N tokens (0 = all)")
-    ap.add_argument("--dry-breaker", action="append", default=[], metavar="STRING",
-                    help="a repeat never runs across the last token of STRING's encoding; repeatable (64)")
-    ap.add_argument("--no-repeat-ngram", type=int, default=0, metavar="N",
-                    help="per request, on the device: ban the token that would complete an N-gram the text already holds (0 = off, else 2 .. 64)")
-    ap.add_argument("--sampler-min-p", type=float, default=0.0, help="per sampling request, on the device: keep tokens with p >= min_p * p_max (0 = off)")
-    ap.add_argument("--sampler-typical-p", type=float, default=None, help="... locally typical sampling with this mass (1 = off)")
-    ap.add_argument("--mirostat-tau", type=float, default=0.0,
-                    help="... Mirostat v2 with this target surprise in bits (0 = off); excludes top-k, top-p, min-p and typical-p")
-    ap.add_argument("--mirostat-eta", type=float, default=0.1, help="Mirostat's learning rate, in (0, 1]")
-    constraint = ap.add_mutually_exclusive_group()
-    constraint.add_argument("--regex", default=None, metavar="PATTERN",
-                            help="every answer must match PATTERN in full (tiny_llm_hip.grammar's dialect), enforced on the device per request")
-    constraint.add_argument("--json", default=None, choices=["object", "value"],
-                            help="JSON mode: every answer is one JSON object (or any JSON value), enforced on the device per request")
-    constraint.add_argument("--json-schema", default=None, metavar="FILE",
-                            help="every answer is compact JSON that conforms to the schema in FILE (tiny_llm_hip.grammar.schema_regex)")
-    ap.add_argument("--stop", action="append", default=[], metavar="STRING",
-                    help="end an answer where its text holds STRING (matched on the device, across token boundaries); repeatable (16)")
-    ap.add_argument("--stop-id", action="append", type=int, default=[], metavar="N", help="end an answer at token id N; repeatable")
+    request.add_request_flags(ap, "batch_main")
     ap.add_argument("--prefix-cache", nargs="?", type=int, const=0, default=None, metavar="PAGES",
                     help="keep the K / V of finished requests and reuse it for later prompts that start with the same tokens (the chat "
                          "template, a shared system prompt); PAGES caps the retained pages (default: no cap)")
@@ -83,16 +56,15 @@ def check_draft_flags(ap: argparse.ArgumentParser, args, truncates: bool) -> Non
     """--draft-model verifies raw logits greedily, one adapter-free model: refuse every flag that would not apply."""
     if not args.draft_model:
         return
+    flags = request.switched(args)
     clashes = [name for name, on in (
-        ("--sampler-temp / --sampler-top-p / --sampler-top-k", bool(args.sampler_temp) or args.sampler_top_p is not None or args.sampler_top_k is not None),
+        ("--sampler-temp / --sampler-top-p / --sampler-top-k", bool(flags.given & {"--sampler-temp", "--sampler-top-p", "--sampler-top-k"})),
         ("--sampler-min-p / --sampler-typical-p / --mirostat-tau", truncates),
-        ("--repetition-penalty / --presence-penalty / --frequency-penalty",
-         (args.repetition_penalty, args.presence_penalty, args.frequency_penalty) != (1.0, 0.0, 0.0)),
-        ("--regex / --json / --json-schema", bool(args.regex or args.json or args.json_schema)),
-        ("--stop / --stop-id", bool(args.stop or args.stop_id)),
+        ("--repetition-penalty / --presence-penalty / --frequency-penalty", "penalties" in flags.groups),
+        ("--regex / --json / --json-schema", "grammar" in flags.groups),
+        ("--stop / --stop-id", "stop" in flags.groups),
         ("--lora", bool(args.lora)),
-        ("--dry-multiplier / --dry-base / --dry-allowed-length / --dry-range / --dry-breaker / --no-repeat-ngram",
-         args.dry_multiplier > 0 or args.no_repeat_ngram > 0),
+        ("--dry-multiplier / --dry-base / --dry-allowed-length / --dry-range / --dry-breaker / --no-repeat-ngram", "dry" in flags.groups),
     ) if on]
     if clashes:
         ap.error("--draft-model runs greedy speculative decoding over the raw logits of one model; it does not combine with " + ", ".join(clashes))
@@ -103,20 +75,17 @@ def check_draft_flags(ap: argparse.ArgumentParser, args, truncates: bool) -> Non
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
-    from main import check_truncation_flags
-
-    truncates = check_truncation_flags(ap, args)
+    truncates = request.check_truncation_flags(ap, args)
     check_draft_flags(ap, args, truncates)
 
     from tiny_llm_hip import load
     from tiny_llm_hip.engine import DecodeEngine, batch_generate_ids, batch_speculative_generate_ids
-    from main import chat_prompt
 
     model, tokenizer = load(args.model)
     prompts = [l for l in Path(args.prompts_file).read_text().splitlines() if l.strip()] if args.prompts_file else DEFAULT_PROMPTS
     encoded, limits = [], []
     for text in prompts:
-        full = text if args.raw_prompts else chat_prompt(tokenizer, text, args.enable_thinking)
+        full = text if args.raw_prompts else request.chat_prompt(tokenizer, text, args.enable_thinking)
         ids = tokenizer.encode(full, add_special_tokens=False)
         if len(ids) >= args.max_seq_len:
             raise ValueError(f"prompt of {len(ids)} tokens exceeds max_seq_len {args.max_seq_len}")
@@ -126,17 +95,7 @@ def main(argv=None):
     engine = DecodeEngine(model, page_size=128, num_pages=pages_per_seq * (args.batch_size + 1) + 2,
                           max_batch=args.batch_size + 1, max_prefill_rows=args.prefill_step, kv_format=args.kv_format,
                           prefix_cache=False if args.prefix_cache is None else (args.prefix_cache or True), swap_pages=args.swap_pages)
-    sampling = {}
-    if args.sampler_temp:
-        sampling.update(temperature=args.sampler_temp, top_k=args.sampler_top_k, top_p=args.sampler_top_p)
-        if truncates:
-            sampling.update(min_p=args.sampler_min_p, typical_p=args.sampler_typical_p, mirostat_tau=args.mirostat_tau, mirostat_eta=args.mirostat_eta)
-    if (args.repetition_penalty, args.presence_penalty, args.frequency_penalty) != (1.0, 0.0, 0.0):
-        sampling.update(repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty,
-                        frequency_penalty=args.frequency_penalty)
-    from main import dry_settings
-
-    sampling.update(dry_settings(args, tokenizer))
+    sampling = request.sampling_dict(args, tokenizer, request.switched(args).groups)
     stops = {tokenizer.eos_token_id}
     try:
         from tiny_llm_hip.grammar import cli_grammar

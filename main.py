@@ -19,56 +19,19 @@ for p in (ROOT / "tiny-llm_amd", ROOT / "tiny-llm_amd" / "extensions_hip"):
         sys.path.insert(0, str(p))
 
 
+from tiny_llm_hip import request  # noqa: E402
+from tiny_llm_hip.request import chat_prompt, check_truncation_flags, dry_settings  # noqa: E402,F401  (dry_settings: the --dry-* flags as sampling keys)
+
+
 def build_parser() -> argparse.ArgumentParser:
+    """The request flags come from tiny_llm_hip.request's table (shared with batch_main.py); the rest are this script's own.  A request
+    flag that exists on the device only applies with --solution engine."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--model", required=True)
     ap.add_argument("--draft-model", default=None)
     ap.add_argument("--prompt", default="Give me a short introduction to large language model.")
     ap.add_argument("--solution", default="engine", choices=["engine", "ops"])
-    ap.add_argument("--sampler-temp", type=float, default=0)
-    ap.add_argument("--sampler-top-p", type=float, default=None)
-    ap.add_argument("--sampler-top-k", type=int, default=None)
-    ap.add_argument("--sampler-seed", type=int, default=None,
-                    help="with --solution engine and a nonzero --sampler-temp: sample on the device, in decode(N) calls, from this seed")
-    ap.add_argument("--repetition-penalty", type=float, default=1.0,
-                    help="with --solution engine: divide (multiply, where negative) the logits of the tokens of the prompt and the output "
-                         "by this before each choice, on the device (1 = off)")
-    ap.add_argument("--presence-penalty", type=float, default=0.0,
-                    help="with --solution engine: subtract this from the logit of every token the output already holds (0 = off)")
-    ap.add_argument("--frequency-penalty", type=float, default=0.0,
-                    help="with --solution engine: subtract this times the token's count in the output (0 = off)")
-    ap.add_argument("--dry-multiplier", type=float, default=0.0,
-                    help="with --solution engine: DRY, on the device -- subtract multiplier * base ** (L - allowed_length) from the token that "
-                         "would extend a verbatim repeat of L tokens (0 = off)")
-    ap.add_argument("--dry-base", type=float, default=1.75, help="DRY's base (>= 1)")
-    ap.add_argument("--dry-allowed-length", type=int, default=2, help="the longest repeat DRY leaves alone, plus one (>= 1)")
-    ap.add_argument("--dry-range", type=int, default=0, help="DRY looks for repeats in the last N tokens (0 = all)")
-    ap.add_argument("--dry-breaker", action="append", default=[], metavar="STRING",
-                    help="a repeat never runs across the last token of STRING's encoding; repeatable (64)")
-    ap.add_argument("--no-repeat-ngram", type=int, default=0, metavar="N",
-                    help="with --solution engine: ban, on the device, the token that would complete an N-gram the text already holds (0 = off, else 2 .. 64)")
-    constraint = ap.add_mutually_exclusive_group()
-    ap.add_argument("--sampler-min-p", type=float, default=0.0,
-                    help="with --solution engine and a nonzero --sampler-temp, on the device: keep tokens with p >= min_p * p_max (0 = off)")
-    ap.add_argument("--sampler-typical-p", type=float, default=None,
-                    help="... locally typical sampling: keep the tokens closest to the entropy until their mass reaches this (1 = off)")
-    ap.add_argument("--mirostat-tau", type=float, default=0.0,
-                    help="... Mirostat v2 with this target surprise in bits (0 = off); excludes top-k, top-p, min-p and typical-p")
-    ap.add_argument("--mirostat-eta", type=float, default=0.1, help="Mirostat's learning rate, in (0, 1]")
-    constraint.add_argument("--regex", default=None, metavar="PATTERN",
-                            help="with --solution engine: the answer must match PATTERN in full (tiny_llm_hip.grammar's dialect), enforced "
-                                 "on the device token by token; the vocabulary comes from the loaded tokenizer")
-    constraint.add_argument("--json", default=None, choices=["object", "value"],
-                            help="with --solution engine: JSON mode -- the answer is one JSON object (or any JSON value), nested up to "
-                                 "32 levels, enforced on the device by a stack automaton (tiny_llm_hip.grammar.compile_json)")
-    constraint.add_argument("--json-schema", default=None, metavar="FILE",
-                            help="with --solution engine: the answer is compact JSON that conforms to the schema in FILE (the "
-                                 "non-recursive subset of tiny_llm_hip.grammar.schema_regex)")
-    ap.add_argument("--stop", action="append", default=[], metavar="STRING",
-                    help="with --solution engine: end the answer where its text holds STRING (matched on the device, across token "
-                         "boundaries; the text is printed up to the match); repeat the flag for up to 16 strings")
-    ap.add_argument("--stop-id", action="append", type=int, default=[], metavar="N",
-                    help="with --solution engine: end the answer at token id N (not printed); repeatable")
+    request.add_request_flags(ap, "main")
     ap.add_argument("--enable-thinking", action="store_true")
     ap.add_argument("--raw-prompt", action="store_true", help="do not wrap the prompt in the chat template")
     ap.add_argument("--max-new-tokens", type=int, default=256)
@@ -89,15 +52,6 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
-def check_truncation_flags(ap, args) -> bool:
-    """The exclusivity rule of the engine (tl_engine_set_mirostat), raised before anything is loaded; True when a truncation flag is set."""
-    others = args.sampler_min_p > 0 or (args.sampler_typical_p is not None and args.sampler_typical_p < 1) or bool(args.sampler_top_k) or \
-        (args.sampler_top_p is not None and args.sampler_top_p < 1)
-    if args.mirostat_tau > 0 and others:
-        ap.error("Mirostat excludes every other truncation (--sampler-top-k, --sampler-top-p, --sampler-min-p, --sampler-typical-p)")
-    return args.mirostat_tau > 0 or args.sampler_min_p > 0 or (args.sampler_typical_p is not None and args.sampler_typical_p < 1)
-
-
 def check_beam_flags(ap, args) -> None:
     """--num-beams runs plain greedy slots (tl_engine_beam_select refuses any other): what it excludes is an error before anything is loaded."""
     if args.num_beams is None:
@@ -108,52 +62,33 @@ def check_beam_flags(ap, args) -> None:
         ap.error("--num-beams must be 1 .. 8")
     if (2 + len(set(args.stop_id))) * args.num_beams > 32:
         ap.error("--num-beams: (1 + number of EOS ids) * beams must not exceed 32 (the EOS id and every --stop-id count)")
+    flags = request.switched(args)
+    sampler = {f.option for s in request.SETTINGS if s.group in ("sampling", "truncation") for f in s.flags}
     excluded = {
         "--solution ops": args.solution != "engine",
         "--draft-model": args.draft_model is not None,
-        "the sampler options": bool(args.sampler_temp) or args.sampler_top_p is not None or args.sampler_top_k is not None or
-        args.sampler_seed is not None or args.sampler_min_p > 0 or args.sampler_typical_p is not None or args.mirostat_tau > 0,
-        "the penalty options": (args.repetition_penalty, args.presence_penalty, args.frequency_penalty) != (1.0, 0.0, 0.0),
-        "--regex / --json / --json-schema": bool(args.regex or args.json or args.json_schema),
-        "--stop": bool(args.stop),
+        "the sampler options": bool(flags.given & sampler),
+        "the penalty options": "penalties" in flags.groups,
+        "--regex / --json / --json-schema": "grammar" in flags.groups,
+        "--stop": "--stop" in flags.given,
         "--logprobs": args.logprobs is not None,
         "--lora": args.lora is not None,
-        "the DRY / --no-repeat-ngram options": dry_flags_on(args),
+        "the DRY / --no-repeat-ngram options": "dry" in flags.groups,
     }
     clash = [name for name, on in excluded.items() if on]
     if clash:
         ap.error("--num-beams cannot be combined with " + ", ".join(clash) + ": beam slots are plain greedy slots")
 
 
-def dry_flags_on(args) -> bool:
-    return args.dry_multiplier > 0 or args.no_repeat_ngram > 0
-
-
-def dry_settings(args, tokenizer) -> dict:
-    """The --dry-* / --no-repeat-ngram flags as the keys of engine.generate / a sampling dict ({} when both are off)."""
-    if not dry_flags_on(args):
-        return {}
-    from tiny_llm_hip.engine import dry_breaker_ids
-
-    return {"dry_multiplier": args.dry_multiplier, "dry_base": args.dry_base, "dry_allowed_length": args.dry_allowed_length,
-            "dry_range": args.dry_range, "dry_breakers": tuple(dry_breaker_ids(tokenizer, args.dry_breaker)), "no_repeat_ngram": args.no_repeat_ngram}
-
-
-def chat_prompt(tokenizer, text: str, enable_thinking: bool) -> str:
-    messages = [{"role": "system", "content": "You are a helpful assistant."}, {"role": "user", "content": text}]
-    return tokenizer.apply_chat_template(messages, tokenize=False, add_generation_prompt=True,
-                                         enable_thinking=enable_thinking)
-
-
 def main(argv=None) -> str:
     ap = build_parser()
     args = ap.parse_args(argv)
-    truncates = check_truncation_flags(ap, args)
+    check_truncation_flags(ap, args)
     check_beam_flags(ap, args)
+    on = request.switched(args).groups
     from tiny_llm_hip import load
 
     model, tokenizer = load(args.model)
-    penalties = (args.repetition_penalty, args.presence_penalty, args.frequency_penalty)
     prompt = args.prompt if args.raw_prompt else chat_prompt(tokenizer, args.prompt, args.enable_thinking)
     if args.solution == "ops":
         from tiny_llm_hip import Qwen3ModelWeek3, make_sampler, simple_generate_with_kv_cache, speculative_generate
@@ -163,9 +98,9 @@ def main(argv=None) -> str:
             draft, draft_tok = load(args.draft_model)
             return speculative_generate(Qwen3ModelWeek3(draft), net, draft_tok, tokenizer, prompt,
                                         proposal_length=args.proposal_length)
-        if penalties != (1.0, 0.0, 0.0) or args.regex or args.json or args.json_schema:
+        if on & {"penalties", "grammar"}:
             print("note: the penalty flags, --regex, --json and --json-schema apply to --solution engine only")
-        if dry_flags_on(args):
+        if "dry" in on:
             print("note: the --dry-* flags and --no-repeat-ngram apply to --solution engine only")
         if args.sampler_temp:
             print("note: the KV-cache loop is greedy like the reference's; sampler flags apply to --solution engine only")
@@ -180,11 +115,7 @@ def main(argv=None) -> str:
         return beam_search_with_engine(model, tokenizer, ids, pages, args)
     engine = DecodeEngine(model, page_size=128, num_pages=pages, max_batch=1, max_prefill_rows=4096)
     eos = tokenizer.eos_token_id
-    records = None
-    grammar = None
-    lora = None
-    stop, token_bytes = None, None
-    dry = dry_settings(args, tokenizer)
+    records = grammar = lora = stop = token_bytes = None
     try:
         if args.lora:
             if args.draft_model:
@@ -199,18 +130,18 @@ def main(argv=None) -> str:
 
             # (the EOS ids join the set: the device ends the request at whichever comes first)
             stop, token_bytes = cli_stop_set(engine, tokenizer, args.stop, args.stop_id, [eos, *(grammar.eos_ids if grammar is not None else ())])
-        elif args.stop or args.stop_id:
+        elif "stop" in on:
             print("note: --stop and --stop-id do not apply with a draft model")
         if args.draft_model:
             draft_model, draft_tok = load(args.draft_model)
             if draft_tok.get_vocab() != tokenizer.get_vocab():
                 raise ValueError("draft and target tokenizers use different token ids")
-            if penalties != (1.0, 0.0, 0.0) or args.regex or args.json or args.json_schema:
+            if on & {"penalties", "grammar"}:
                 print("note: speculative decoding verifies the raw logits; the penalty flags, --regex, --json and --json-schema do not "
                       "apply with a draft model")
-            if dry:
+            if "dry" in on:
                 print("note: speculative decoding verifies the raw logits; the --dry-* flags and --no-repeat-ngram do not apply with a draft model")
-            if truncates:
+            if "truncation" in on:
                 print("note: speculative sampling verifies under temperature, top-k and top-p; --sampler-min-p, --sampler-typical-p and "
                       "--mirostat-tau do not apply with a draft model")
             if args.sampler_temp and args.sampler_seed is None:
@@ -224,25 +155,17 @@ def main(argv=None) -> str:
                                                seed=args.sampler_seed or 0)
             finally:
                 draft.close()
-        elif args.sampler_temp and (args.sampler_seed is not None or lora is not None or penalties != (1.0, 0.0, 0.0) or grammar is not None or truncates
-                                    or stop is not None or dry):
-            # the per-slot sampler on the device: the whole generation in one prefill + one decode(N) call.  The penalties and the
-            # grammar exist on the device only, so they select this path; so do min-p, typical-p and Mirostat
-            if args.sampler_seed is None:
-                print("note: the penalty, truncation and Mirostat flags and --regex select the device sampler; no --sampler-seed given: seed 0")
-            out = engine.generate(ids, args.max_new_tokens, temperature=args.sampler_temp, top_k=args.sampler_top_k,
-                                  top_p=args.sampler_top_p, seed=args.sampler_seed or 0, logprobs=args.logprobs,
-                                  repetition_penalty=penalties[0], presence_penalty=penalties[1], frequency_penalty=penalties[2],
-                                  grammar=grammar, min_p=args.sampler_min_p, typical_p=args.sampler_typical_p,
-                                  mirostat_tau=args.mirostat_tau, mirostat_eta=args.mirostat_eta, lora=lora, stop=stop, **dry)
-            if args.logprobs is not None:
-                out, records = out
-            out = cut_at_eos(out, eos, grammar)
-        elif args.sampler_temp:
+        elif args.sampler_temp and not (args.sampler_seed is not None or lora is not None or grammar is not None or stop is not None
+                                        or on & {"penalties", "truncation", "dry"}):
             out = sample_with_engine(engine, ids, args, eos)
         else:
-            out = engine.generate(ids, args.max_new_tokens, logprobs=args.logprobs, repetition_penalty=penalties[0],
-                                  presence_penalty=penalties[1], frequency_penalty=penalties[2], grammar=grammar, lora=lora, stop=stop, **dry)
+            # greedy, or the per-slot sampler on the device (the whole generation in one prefill + one decode(N) call), which every flag
+            # that exists on the device only selects: the penalties, the grammar, min-p, typical-p, Mirostat, DRY, the stop set, the adapter
+            if args.sampler_temp and args.sampler_seed is None:
+                print("note: the penalty, truncation and Mirostat flags and --regex select the device sampler; no --sampler-seed given: seed 0")
+            # (a sampling request hands the truncation flags over at neutral values too: one that is out of range is refused, not ignored)
+            out = engine.generate(ids, args.max_new_tokens, seed=args.sampler_seed or 0, logprobs=args.logprobs, grammar=grammar, lora=lora, stop=stop,
+                                  **request.sampling_dict(args, tokenizer, on | {"truncation"}))
             if args.logprobs is not None:
                 out, records = out
             out = cut_at_eos(out, eos, grammar)

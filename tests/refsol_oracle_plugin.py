@@ -155,8 +155,12 @@ class FakeLib:
 
 
 def pytest_configure(config):
+    import mlx.core as mx
     import tiny_llm_ext_hip as ext
 
+    # FakeLib views raw pointers as HOST memory: on a machine with a GPU the facade's arrays would default to the device, and the
+    # host would read them unsynchronised (tests/facade_model_cases.py then misses its band in some runs and not in others)
+    mx.set_default_device(mx.cpu)
     ext._require_gpu = lambda op, *tensors: None
     ext._stream = lambda: 0
     ext._workspace = lambda nbytes, device: None

@@ -236,6 +236,9 @@ class RecordingEngine(ScheduleOnlyEngine):
     def set_logprobs(self, slot, top_n):
         self._log("set_logprobs", slot, top_n)
 
+    def set_dry(self, slot, *args):
+        self._log("set_dry", slot, *args)
+
 
 def trace(eng: RecordingEngine, call) -> dict:
     """Run ``call()`` and return what it did to ``eng`` and what came of it, as JSON would hand it back."""

@@ -13,14 +13,14 @@ rows interleaved) and then exposes a request-level API: ``begin`` / ``prefill`` 
 from __future__ import annotations
 
 import ctypes
-import math
 import os
 from typing import Any, NamedTuple, Sequence
 
 import torch
 
 from . import scheduler
-from .scheduler import RequestSettings
+from .request import (DRY_OFF, SETTINGS_KEYS, RequestSettings, dry_args, dry_breaker_ids, logprobs_arg, penalty_args,  # noqa: F401
+                      request_settings, sampling_args, truncation_args)
 from ._ext import tiny_llm_ext_hip as _ext
 
 _lib = _ext.lib()
@@ -760,43 +760,28 @@ class DecodeEngine:
         return {name: getattr(s, name) for name, _ in s._fields_}
 
     # -- convenience: one request, like benches/bench.py:run_one_request_week2 --------------------------
-    def generate(self, prompt: Sequence[int], max_new_tokens: int, *, slot: int = 0, chunk: int | None = None,
-                 temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None, seed: int = 0,
-                 logprobs: int | None = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                 frequency_penalty: float = 0.0, logit_bias=None, grammar: "Grammar | None" = None, min_p: float = 0.0,
-                 typical_p: float = 1.0, mirostat_tau: float = 0.0, mirostat_eta: float = 0.1, lora: int | None = None,
-                 stop: "StopSet | None" = None, decode_block: int = 32, dry_multiplier: float = 0.0, dry_base: float = 1.75,
-                 dry_allowed_length: int = 2, dry_range: int = 0, dry_breakers: Sequence[int] = (), no_repeat_ngram: int = 0):
-        """One request: prefill, then ``max_new_tokens - 1`` decode steps in one call; greedy unless ``temperature`` > 0 (the
-        device sampler, set_sampling).  With ``logprobs`` an int (0 .. 20 alternatives, set_logprobs): returns (ids, records).
-        ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` (set_penalties, set_logit_bias) are set
-        before the prefill, so the prompt's tokens are in the slot's history; so is ``grammar`` (set_grammar): the ids are then text of
-        its language, followed by EOS ids once it has ended.  ``min_p`` / ``typical_p`` (set_truncation) and ``mirostat_tau`` /
-        ``mirostat_eta`` (set_mirostat) filter the rows a sampling request draws from; Mirostat excludes top_k, top_p, min_p and
-        typical_p (ValueError).  ``lora``: the id of a resident adapter (load_lora) the request runs under; such a request bypasses the
-        prefix cache.  On an engine with the prefix cache on, the slot first attaches the cached
-        prefix of the prompt (prefix_attach) and prefills the rest, and declares the answer before its release (prefix_extend).
-        ``stop``: a StopSet (make_stop_set).  The slot is armed with it and the budget ``max_new_tokens`` before the prefill, decodes in
-        blocks of ``decode_block`` steps and leaves after the block in which it stopped; the result is the ids up to and including the
-        stopping token -- exactly ``stop_state().generated`` of them -- and likewise the records; ``last_stop_state`` keeps the slot's
-        final StopState.  Without ``stop`` the call is unchanged.  ``dry_multiplier`` / ``dry_base`` / ``dry_allowed_length`` /
-        ``dry_range`` / ``dry_breakers`` and ``no_repeat_ngram`` (set_dry) are set before the prefill too, so the prompt's ids are part of
-        the sequence the matches are looked for in."""
+    def generate(self, prompt: Sequence[int], max_new_tokens: int, *, slot: int = 0, chunk: int | None = None, logprobs: int | None = None,
+                 stop: "StopSet | None" = None, decode_block: int = 32, **settings):
+        """One request: prefill, then ``max_new_tokens - 1`` decode steps in one call.  ``settings``: what the request sets on its slot, as
+        keywords -- the keys of tiny_llm_hip.request.SETTINGS with their defaults there (a plain greedy request), validated by
+        request_settings (ValueError, also for an unknown key) and set before the prefill (RequestSettings.apply), so the prompt's
+        tokens are in the history that penalties, DRY and the n-gram ban look at.  With a ``grammar`` the ids are text of its language,
+        followed by EOS ids once it has ended.  On an engine with the prefix cache on, the slot first attaches the cached prefix of the
+        prompt (prefix_attach), prefills the rest and declares the answer before its release (prefix_extend); a ``lora`` request bypasses it.
+        With ``logprobs`` an int (0 .. 20 alternatives, set_logprobs): returns (ids, records).  ``stop``: a StopSet (make_stop_set).  The
+        slot is armed with it and the budget ``max_new_tokens`` before the prefill, decodes in blocks of ``decode_block`` steps and leaves
+        after the block in which it stopped; the result is the ids up to and including the stopping token -- exactly
+        ``stop_state().generated`` of them -- and likewise the records; ``last_stop_state`` keeps the slot's final StopState."""
         if stop is not None and (isinstance(decode_block, bool) or not isinstance(decode_block, int) or decode_block < 1):
             raise ValueError("generate: decode_block is a positive int")
-        settings = request_settings(
-            {"temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed, "min_p": min_p, "typical_p": typical_p,
-             "mirostat_tau": mirostat_tau, "mirostat_eta": mirostat_eta, "repetition_penalty": repetition_penalty,
-             "presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty, "logit_bias": logit_bias, "grammar": grammar,
-             "lora": lora, "dry_multiplier": dry_multiplier, "dry_base": dry_base, "dry_allowed_length": dry_allowed_length,
-             "dry_range": dry_range, "dry_breakers": dry_breakers, "no_repeat_ngram": no_repeat_ngram}, 1, vocab_size=self.vocab_size, logprobs=logprobs, stop=stop, limits=[max_new_tokens])[0]
-        top_n = settings.top_n
+        settings = request_settings(settings, 1, vocab_size=self.vocab_size, logprobs=logprobs, stop=stop, limits=[max_new_tokens])[0]
         self.begin(slot)
         try:
             settings.apply(self, slot)
             prompt = [int(t) for t in prompt]
             matched = self.prefix_attach(slot, prompt) if self.prefix_cache_enabled and prompt else 0
             self.prefill(slot, prompt[matched:], chunk=chunk)
+            count = max_new_tokens
             if stop is not None:
                 left = max_new_tokens - 1
                 state = self.stop_state(slot)
@@ -805,17 +790,15 @@ class DecodeEngine:
                     self.decode(steps, batch=slot + 1)
                     left -= steps
                     state = self.stop_state(slot)
-                ids = self.read_tokens(slot, state.generated)
+                count = state.generated
                 self.last_stop_state = state  # (why and where the request ended: the slot is released below)
-                if self.prefix_cache_enabled:  # only fed tokens are declared: the stopping token never was
-                    self.prefix_extend(slot, ids[:-1])
-                return (ids, self.read_logprobs(slot, state.generated)) if top_n >= 0 else ids
-            if max_new_tokens > 1:
+            elif max_new_tokens > 1:
                 self.decode(max_new_tokens - 1, batch=slot + 1)
-            ids = self.read_tokens(slot, max_new_tokens)
-            if self.prefix_cache_enabled:  # the answer's fed tokens are declared, so that a follow-up turn finds prompt and answer cached
+            ids = self.read_tokens(slot, count)
+            # only fed tokens are declared (the last one never was), so that a follow-up turn finds prompt and answer cached
+            if self.prefix_cache_enabled:
                 self.prefix_extend(slot, ids[:-1])
-            return (ids, self.read_logprobs(slot, max_new_tokens)) if top_n >= 0 else ids
+            return (ids, self.read_logprobs(slot, count)) if settings.top_n >= 0 else ids
         finally:
             self.release(slot)
 
@@ -829,58 +812,6 @@ class TokenLogprob(NamedTuple):
     @staticmethod
     def of(rec: "_ext.TlTokenLogprob") -> "TokenLogprob":
         return TokenLogprob(float(rec.logprob), [(int(i), float(v)) for i, v in zip(rec.top_ids, rec.top_logprobs) if i >= 0])
-
-
-def logprobs_arg(top_n: int | None) -> int:
-    """tl_engine_set_logprobs' top_n: None -> -1 (off), else an int in [0, 20]."""
-    if top_n is None:
-        return -1
-    if isinstance(top_n, bool) or not isinstance(top_n, int) or not 0 <= top_n <= _ext.TL_MAX_TOP_LOGPROBS:
-        raise ValueError(f"logprobs must be None or an int in [0, {_ext.TL_MAX_TOP_LOGPROBS}], got {top_n!r}")
-    return top_n
-
-
-def sampling_args(temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None,
-                  seed: int = 0) -> tuple[float, int, float, int]:
-    """Validated (temperature, top_k, top_p, seed) for tl_engine_set_sampling: temperature finite and >= 0 (0 = greedy); top_k None
-    or 0 = no top-k, else a positive int (beyond the vocabulary: none); top_p None = no top-p, else in (0, 1] (1 = none); seed an
-    int in [0, 2^64)."""
-    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or temperature < 0:
-        raise ValueError(f"temperature must be a finite number >= 0, got {temperature!r}")
-    if top_k is None:
-        top_k = 0
-    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
-        raise ValueError(f"top_k must be None or an int >= 0, got {top_k!r}")
-    if top_p is None:
-        top_p = 1.0
-    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not (0.0 < top_p <= 1.0):
-        raise ValueError(f"top_p must be None or in (0, 1], got {top_p!r}")
-    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed must be an int in [0, 2**64), got {seed!r}")
-    return float(temperature), min(int(top_k), 2**31 - 1), float(top_p), int(seed)
-
-
-def truncation_args(min_p: float = 0.0, typical_p: float | None = 1.0, mirostat_tau: float = 0.0, mirostat_eta: float = 0.1, *,
-                    top_k: int = 0, top_p: float = 1.0) -> tuple[float, float, float, float]:
-    """Validated (min_p, typical_p, tau, eta) for tl_engine_set_truncation / tl_engine_set_mirostat: min_p in [0, 1] (0 = off),
-    typical_p None or in (0, 1] (1 = off), mirostat_tau finite and >= 0 (0 = off), mirostat_eta in (0, 1].  Mirostat excludes every
-    other truncation: with tau > 0, min_p, typical_p and the request's ``top_k`` / ``top_p`` (as sampling_args returns them) must be off."""
-    if typical_p is None:
-        typical_p = 1.0
-    for name, v in (("min_p", min_p), ("typical_p", typical_p), ("mirostat_tau", mirostat_tau), ("mirostat_eta", mirostat_eta)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
-            raise ValueError(f"{name} must be a finite number, got {v!r}")
-    if not 0.0 <= min_p <= 1.0:
-        raise ValueError(f"min_p must be in [0, 1], got {min_p!r}")
-    if not 0.0 < typical_p <= 1.0:
-        raise ValueError(f"typical_p must be None or in (0, 1], got {typical_p!r}")
-    if mirostat_tau < 0:
-        raise ValueError(f"mirostat_tau must be >= 0, got {mirostat_tau!r}")
-    if not 0.0 < mirostat_eta <= 1.0:
-        raise ValueError(f"mirostat_eta must be in (0, 1], got {mirostat_eta!r}")
-    if mirostat_tau > 0 and (min_p > 0 or typical_p < 1 or top_k > 0 or top_p < 1):
-        raise ValueError("Mirostat excludes every other truncation (top_k, top_p, min_p, typical_p)")
-    return float(min_p), float(typical_p), float(mirostat_tau), float(mirostat_eta) if mirostat_tau > 0 else 0.0
 
 
 GRAMMAR_END = -1  # TL_GRAMMAR_END
@@ -953,113 +884,6 @@ class Grammar:
             pass
 
 
-def penalty_args(repetition: float = 1.0, presence: float = 0.0, frequency: float = 0.0) -> tuple[float, float, float]:
-    """Validated (repetition, presence, frequency) for tl_engine_set_penalties: repetition finite and > 0 (1 = off), presence and
-    frequency finite (0 = off; negative values encourage repetition)."""
-    for name, v in (("repetition_penalty", repetition), ("presence_penalty", presence), ("frequency_penalty", frequency)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
-            raise ValueError(f"{name} must be a finite number, got {v!r}")
-    if not repetition > 0:
-        raise ValueError(f"repetition_penalty must be > 0, got {repetition!r}")
-    return float(repetition), float(presence), float(frequency)
-
-
-DRY_OFF = (0.0, 1.75, 2, 0, 0, ())  # dry_args of a request with neither DRY nor the n-gram ban
-
-
-def dry_args(multiplier: float = 0.0, base: float = 1.75, allowed_length: int = 2, range: int = 0, no_repeat_ngram: int = 0,  # noqa: A002
-             breakers: Sequence[int] = (), vocab_size: int = 0) -> tuple:
-    """Validated (multiplier, base, allowed_length, range, no_repeat_ngram, breakers) for tl_engine_set_dry: multiplier finite and >= 0
-    (0 = off), base finite and >= 1, allowed_length >= 1, range >= 0 (0 = everything recorded), no_repeat_ngram 0 (off) or 2 .. 64,
-    breakers up to 64 distinct ids (inside ``vocab_size`` where that is given)."""
-    for name, v in (("dry_multiplier", multiplier), ("dry_base", base)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
-            raise ValueError(f"{name} must be a finite number, got {v!r}")
-    if multiplier < 0:
-        raise ValueError(f"dry_multiplier must be >= 0, got {multiplier!r}")
-    if base < 1:
-        raise ValueError(f"dry_base must be >= 1, got {base!r}")
-    for name, v in (("dry_allowed_length", allowed_length), ("dry_range", range), ("no_repeat_ngram", no_repeat_ngram)):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"{name} must be an int, got {v!r}")
-    if allowed_length < 1:
-        raise ValueError(f"dry_allowed_length must be >= 1, got {allowed_length!r}")
-    if range < 0:
-        raise ValueError(f"dry_range must be >= 0, got {range!r}")
-    if no_repeat_ngram != 0 and not 2 <= no_repeat_ngram <= _ext.TL_DRY_MAX_MATCH:
-        raise ValueError(f"no_repeat_ngram must be 0 (off) or 2 .. {_ext.TL_DRY_MAX_MATCH}, got {no_repeat_ngram!r}")
-    ids = tuple(breakers or ())
-    if any(isinstance(t, bool) or not isinstance(t, int) or t < 0 or (vocab_size and t >= vocab_size) for t in ids):
-        raise ValueError("dry_breakers must be token ids inside the vocabulary")
-    if len(set(ids)) != len(ids):
-        raise ValueError("dry_breakers: a token id appears twice")
-    if len(ids) > _ext.TL_MAX_DRY_BREAKERS:
-        raise ValueError(f"dry_breakers takes at most {_ext.TL_MAX_DRY_BREAKERS} ids, got {len(ids)}")
-    return float(multiplier), float(base), allowed_length, range, no_repeat_ngram, ids
-
-
-def dry_breaker_ids(tokenizer, strings: Sequence[str]) -> list[int]:
-    """The breaker ids of ``strings`` as text-generation-webui derives them: each string gives the LAST id of its encoding (a breaker is
-    one token); duplicates are dropped, the order kept."""
-    out: list[int] = []
-    for s in strings:
-        try:
-            ids = tokenizer.encode(s, add_special_tokens=False)
-        except TypeError:
-            ids = tokenizer.encode(s)
-        ids = getattr(ids, "ids", ids)
-        if len(ids) and int(ids[-1]) not in out:
-            out.append(int(ids[-1]))
-    return out
-
-
-SETTINGS_KEYS = {"temperature", "top_k", "top_p", "seed", "min_p", "typical_p", "mirostat_tau", "mirostat_eta", "repetition_penalty",
-                 "presence_penalty", "frequency_penalty", "logit_bias", "grammar", "lora", "dry_multiplier", "dry_base",
-                 "dry_allowed_length", "dry_range", "dry_breakers", "no_repeat_ngram"}
-
-
-def request_settings(sampling, n_prompts: int, base_seed: int = 0, vocab_size: int = 0, logprobs: int | None = None, stop=None,
-                     limits: int | Sequence[int] = 0) -> list[RequestSettings]:
-    """One RequestSettings per prompt.  ``sampling``: None (greedy), one dict for every request or one dict per prompt, with the keys
-    SETTINGS_KEYS: temperature / top_k / top_p / seed (sampling_args; a request without a seed gets base_seed + its prompt index, so
-    requests do not share a random stream), min_p / typical_p / mirostat_tau / mirostat_eta (truncation_args, exclusivity against the
-    same dict's top_k / top_p included), repetition_penalty / presence_penalty / frequency_penalty (penalty_args), logit_bias
-    (logit_bias_arg over ``vocab_size``), grammar (a Grammar or None) and lora (lora.request_loras: also one list for all in a single
-    dict).  ``logprobs``: logprobs_arg, for every request.  ``stop``: stop.request_stops; a request is armed when it is not None.
-    ``limits``: max_new_tokens, one for all or one per prompt.  ValueError for anything else."""
-    from .lora import request_loras
-    from .stop import request_stops
-
-    stops = request_stops(stop, n_prompts)
-    limits = [limits] * n_prompts if isinstance(limits, int) else list(limits)
-    dicts = [{}] * n_prompts if sampling is None else [sampling] * n_prompts if isinstance(sampling, dict) else list(sampling)
-    if len(dicts) != n_prompts:
-        raise ValueError("sampling needs one dict per prompt (or one dict for all)")
-    out = []
-    for i, d in enumerate(dicts):
-        if not isinstance(d, dict):
-            raise ValueError("sampling entries must be dicts")
-        unknown = set(d) - SETTINGS_KEYS
-        if unknown:
-            raise ValueError(f"unknown sampling keys: {sorted(unknown)}")
-        seed = d.get("seed")
-        smp = sampling_args(d.get("temperature", 0.0), d.get("top_k"), d.get("top_p"), (base_seed + i) & 0xFFFFFFFFFFFFFFFF if seed is None else seed)
-        bias = d.get("logit_bias")
-        _ext.logit_bias_arg(bias, vocab_size)
-        pen = penalty_args(d.get("repetition_penalty", 1.0), d.get("presence_penalty", 0.0), d.get("frequency_penalty", 0.0))
-        grammar = d.get("grammar")
-        if grammar is not None and not isinstance(grammar, Grammar):
-            raise ValueError("sampling['grammar'] must be a Grammar (DecodeEngine.make_grammar) or None")
-        trn = truncation_args(d.get("min_p", 0.0), d.get("typical_p"), d.get("mirostat_tau", 0.0), d.get("mirostat_eta", 0.1), top_k=smp[1], top_p=smp[2])
-        dry = dry_args(d.get("dry_multiplier", 0.0), d.get("dry_base", 1.75), d.get("dry_allowed_length", 2), d.get("dry_range", 0),
-                       d.get("no_repeat_ngram", 0), d.get("dry_breakers") or (), vocab_size)
-        out.append(RequestSettings(sampling=smp, truncation=trn, penalties=pen, bias=dict(bias) if bias else {}, grammar=grammar, dry=dry,
-                                   armed=stops is not None, stop=stops[i] if stops is not None else None, budget=limits[i]))
-    loras = request_loras(sampling, n_prompts) or [-1] * n_prompts
-    top_n = logprobs_arg(logprobs)
-    return [s._replace(lora=lora, top_n=top_n) for s, lora in zip(out, loras)]
-
-
 def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], max_new_tokens: int | Sequence[int],
                        batch_size: int, prefill_step: int = 128, eos_token_id: int | None = None,
                        on_step=None, sampling=None, base_seed: int = 0, logprobs: int | None = None, stop=None,
@@ -1072,8 +896,7 @@ def batch_generate_ids(engine: DecodeEngine, prompts: Sequence[Sequence[int]], m
     nothing, so skipping the idle tail changes no result), (d) retires finished requests and returns their pages.
     Token-id in, token-id out (no tokenizer can be downloaded here).  Needs ``engine.max_batch >= batch_size + 1``:
     the last slot is the prefill staging slot.  Returns [(prompt_idx, generated ids)] in completion order.
-    ``sampling``: None (greedy), one dict or one dict per prompt (request_settings: temperature / top_k / top_p / seed, repetition_penalty /
-    presence_penalty / frequency_penalty / logit_bias, min_p / typical_p / mirostat_tau / mirostat_eta, and ``grammar``: a Grammar, whose
+    ``sampling``: None (greedy), one dict or one dict per prompt (request_settings: the keys of tiny_llm_hip.request.SETTINGS; a ``grammar``'s
     EOS ids then end the request like ``eos_token_id``); applied when a request enters the staging slot (RequestSettings.apply),
     and carried by the engine through its slot moves.  ``logprobs``: None, or an int (0 .. 20 alternatives): every request records
     its tokens' log-probabilities (set_logprobs), read in the same turn as the pending ids, and the result is

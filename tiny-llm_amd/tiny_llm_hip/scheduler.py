@@ -2,7 +2,7 @@
 
 Pure host logic over the engine's duck-typed slot interface (``begin`` / ``prefill`` / ``prefill_packed`` / ``move`` / ``decode`` /
 ``release``, ``prefix_attach`` / ``prefix_extend`` with a prefix cache, what tiny_llm_hip.preempt asks with swap space; DecodeEngine,
-or benches/serving.py's ScheduleOnlyEngine): no torch, no extension.  Decode slots are [0, batch_size), staging slots follow them.
+or benches/serving.py's ScheduleOnlyEngine): no torch, no device.  Decode slots are [0, batch_size), staging slots follow them.
 
 One turn of ``Scheduler.run``:
 
@@ -24,9 +24,8 @@ reason beside it.  None of them is decided here: a step's arithmetic follows its
 
 from __future__ import annotations
 
-from typing import Any, NamedTuple
-
 from .preempt import Preemption
+from .request import RequestSettings  # noqa: F401  (what a front-end's ``admit`` applies; benches/serving.py takes it from here)
 
 # decode row counts the schedulers use: exact up to 4 rows (fused GEMV), then the row-block sizes of the skinny matmul; the engine
 # keeps one captured graph per row count, and the buckets bound their number
@@ -63,49 +62,6 @@ def close_holes(engine, slots: list, live: set) -> None:
         slots[lo], slots[hi] = slots[hi], None
         live.discard(hi)
         live.add(lo)
-
-
-class RequestSettings(NamedTuple):
-    """Everything one request sets on its slot, validated (engine.request_settings builds it from a ``sampling`` dict); the defaults
-    are a plain greedy request."""
-    sampling: tuple = (0.0, 0, 1.0, 0)           # sampling_args: temperature, top_k, top_p, seed
-    truncation: tuple = (0.0, 1.0, 0.0, 0.0)     # truncation_args: min_p, typical_p, mirostat tau, eta
-    penalties: tuple = (1.0, 0.0, 0.0)           # penalty_args: repetition, presence, frequency
-    bias: dict = {}                              # logit bias {token id: value}
-    grammar: "Grammar | None" = None
-    lora: int = -1                               # a resident adapter's id; -1: the base model
-    top_n: int = -1                              # logprobs_arg: alternatives per recorded token; -1: no records
-    armed: bool = False                          # stop conditions on the device: the slot is armed with ``stop`` and ``budget``
-    stop: Any = None                             # a StopSet or None
-    budget: int = 0                              # the request's max_new_tokens
-    dry: tuple = (0.0, 1.75, 2, 0, 0, ())        # dry_args: multiplier, base, allowed_length, range, no_repeat_ngram, breaker ids
-
-    def apply(self, engine, slot: int) -> None:
-        """The one setter sequence, on a freshly begun slot and before its prompt's first chunk:
-        lora, sampling, truncation / Mirostat, penalties, bias, grammar, logprobs, stop.
-        A neutral value makes no call.  The order is free but for one rule: each setter rewrites only its own per-slot record
-        (csrc/engine.hip), and the one cross-check -- truncation / Mirostat against the slot's top_k / top_p -- needs sampling first.
-        Any order that keeps that rule leaves the slot in the same end state."""
-        if self.lora >= 0:
-            engine.set_lora(slot, self.lora)
-        if self.sampling[0] > 0.0:
-            engine.set_sampling(slot, *self.sampling)
-        if self.truncation[0] > 0.0 or self.truncation[1] < 1.0:
-            engine.set_truncation(slot, self.truncation[0], self.truncation[1])
-        if self.truncation[2] > 0.0:
-            engine.set_mirostat(slot, self.truncation[2], self.truncation[3])
-        if self.penalties != (1.0, 0.0, 0.0):
-            engine.set_penalties(slot, *self.penalties)
-        if self.bias:
-            engine.set_logit_bias(slot, self.bias)
-        if self.grammar is not None:
-            engine.set_grammar(slot, self.grammar)
-        if self.dry[0] > 0.0 or self.dry[4] > 0:
-            engine.set_dry(slot, *self.dry)
-        if self.top_n >= 0:
-            engine.set_logprobs(slot, self.top_n)
-        if self.armed:
-            engine.set_stop(slot, self.stop, self.budget)
 
 
 class Frontend:
