@@ -140,7 +140,7 @@ static int run_check() {
                                         // sweep gets there: the workgroup caps of the split rule bound batch x n_splits by 512.)
                                         else if (!fits) require(p.n_splits > 64, "the partials exceed attn_partials_capacity at no more than 64 splits");
                                     }
-                                    // the wo GEMV of one row takes 2 / 4 / 8 windows at head_dim 128 (decode_linear.h, wo_merge_applicable)
+                                    // the wo GEMV of one row takes 2 / 4 / 8 windows at head_dim 128 (linear_plan.h, wo_merge_applicable)
                                     if (batch == 1 && d == 128 && (p.n_splits == 2 || p.n_splits == 4 || p.n_splits == 8)) {
                                         const AttnPlan q = plan_decode_attention(g, k, batch, ctx, kv8 != 0, offered != 0, true);
                                         check_plan(g, k, batch, ctx, kv8 != 0, offered != 0, true, q);

@@ -196,3 +196,34 @@ def test_fragment_order_rows_are_read_inside_ceil16_rows(ext, M):
                                 fragment_order=True, fragment_rows=M)
     torch.cuda.synchronize()
     assert torch.equal(got2, want)
+
+
+_wide = []
+
+
+@pytest.mark.parametrize("M", [33, 48])
+def test_three_row_blocks_over_88_workgroups_of_19_groups_per_wave(ext, M):
+    """5,120 columns (19 groups per wave: 16-row blocks are the only compiled variant) x 1,360 output rows (85 tiles) at 33 .. 48 rows: three
+    row blocks of 85 workgroups, rounded up to 88 each -- 264 workgroups, eight more than CUs.  Until csrc/linear_plan.h the planner's
+    one-workgroup-per-CU rule turned this, its only candidate, away (gate|up of a Qwen3-14B / 32B-width model left the batched route at
+    33 .. 48 sequences); the smallest shape that meets the case, with the oracle and the allowances of the w_down cases above."""
+    if not _wide:
+        PROJECTIONS["wide"] = (1360, 5120, PRO_NONE, EPI_RESIDUAL)
+        try:
+            _wide.append(_Projection(ext, "wide"))
+        finally:
+            del PROJECTIONS["wide"]
+    p = _wide[0]
+    got, info = ext.decode_linear(p.tiled, p.a[:M].contiguous(), prologue=PRO_NONE, epilogue=EPI_STORE, eps=EPS, kernel=5)
+    what = f"qmm6 store 1,360 x 5,120 M={M} {info['p']}"
+    assert info["kernel"] == 5 and info["launches"] == 1 and (info["p"][0], info["p"][1], info["p"][3], info["p"][4]) == (1, 19, 3, 264), what
+    assert_within(_bf16_host(got), p.want[(PRO_NONE, EPI_STORE)][:M], p.allowed[(PRO_NONE, EPI_STORE)][:M], what=what)
+    norm_out = (1.0 + 0.05 * torch.randn((p.K,), device=DEV, generator=torch.Generator(device=DEV).manual_seed(6))).to(torch.bfloat16)
+    got, info = ext.decode_linear(p.tiled, p.a[:M].contiguous(), prologue=PRO_NONE, epilogue=EPI_RESIDUAL, residual=p.residual[:M].contiguous(),
+                                  eps=EPS, kernel=5, want_ss_out=True, norm_out=norm_out)
+    what = f"qmm6 residual 1,360 x 5,120 M={M} {info['p']}"
+    assert info["kernel"] == 5 and info["launches"] == 1 and (info["p"][0], info["p"][1], info["p"][3], info["p"][4]) == (1, 19, 3, 264), what
+    assert_within(_bf16_host(got), p.want[(PRO_NONE, EPI_RESIDUAL)][:M], p.allowed[(PRO_NONE, EPI_RESIDUAL)][:M], what=what)
+    g64 = got.double()
+    assert torch.allclose(info["ss_out"].double(), (g64 * g64).reshape(M, p.K // 16, 16).sum(dim=2), rtol=1e-5, atol=1e-9), f"{what}: sums of squares"
+    assert torch.equal(info["out_w"], (got.float() * norm_out.float()).to(torch.bfloat16)), f"{what}: weighted rows"

@@ -1,6 +1,7 @@
 // The projection router of the decode path (host only; included by engine.hip, same translation unit): which kernel takes one
-// projection of `M` activation rows (Proj) given what an engine -- or an entry point, on its stack -- owns for it (LinearCtx), the route
-// of a layer (LayerRoute), and the kernel-level entry points tl_decode_linear[_ex] that run the same functions on caller-owned buffers.
+// projection of `M` activation rows (Proj) given what an engine -- or an entry point, on its stack -- owns for it (LinearCtx; the decisions
+// themselves are host-only code over its LinearKnobs, linear_plan.h: the planners, the routing predicates, the route of a layer), and the
+// kernel-level entry points tl_decode_linear[_ex] that run the same functions on caller-owned buffers.
 #pragma once
 
 #include <algorithm>
@@ -107,7 +108,7 @@ struct LinearScratch {
     void *splitk_ws = nullptr;
     size_t splitk_ws_bytes = 0;
 };
-struct LinearCtx : LinearScratch {
+struct LinearCtx : LinearScratch, LinearKnobs {
     hipStream_t stream = nullptr;
     float rms_norm_eps = 0.f;
     // decode-path copy of every W4 matrix in the tiled MFMA layout (qmv3.h); keyed by the checkpoint pointer
@@ -119,29 +120,10 @@ struct LinearCtx : LinearScratch {
     bool use_gemm8 = true;  // tl_engine_set_option "gemm8" = 0: every chunk through the W4 GEMM (qmm.hip), the twin
     bool fuse_reduce_norm = true;  // "prefill_reduce_norm" = 0: the split-K residual reduction and the RMSNorm behind it as two launches, the twin
     bool gemm_fused_epilogue = true;    // tl_engine_set_option "gemm_fused_epilogue" = 0: residual / SwiGLU of the prefill GEMM as separate launches
-    // The 1-4-row GEMVs add the partial sums of squares their producer left instead of re-deriving them (a row without partials --
-    // the first step after a MoE layer, a packed-dot fallback -- is still re-derived inside the kernel: qmv3.h, ss_given):
-    // qkv -0.44 us, gate|up -1.1 us per layer (abl_lab, bit 8)
-    bool gemv_producer_ss = true;
-    // The wo GEMV of 1-4 decode rows also leaves h * post_attention_layernorm (bf16) and the gate|up GEMV stages THAT row and
-    // multiplies its sums by the row's 1 / rms at the end (qmv3.h, PRO_RMS_WEIGHTED): the 1,216 workgroups of gate|up no longer
-    // fetch the norm weights and normalise the whole row each.  tools/lab/trace_lab, back to back: gate|up 7.82 -> 7.08 us, wo
-    // 3.91 -> 4.06; the qkv and lm_head GEMVs gain nothing from it and keep the fused RMSNorm (weighted_rows_apply decides by shape).
-    bool gemv_weighted_rows = true;
-    bool fuse_norm = true;                   // the skinny matmul normalises its own slice whenever its producer left sums of squares
-    int qmm3_min_rows = 5;  // rows from which a projection uses the K-sliced skinny matmul instead of the GEMV (TL_QMM3_MIN_M)
-    bool use_qmm3 = true;   // tl_engine_set_option "qmm3" = 0: rows > 8 go through the prefill GEMM path instead
-    // 5 .. 64 rows: the register-resident matmul (qmm6.h) takes every projection whose plan fits; rows travel WEIGHTED between the
-    // projections (qkv <- w_down / the embedding, gate|up <- wo).  tl_engine_set_option "qmm6" = 0: the K-sliced skinny matmul as before.
-    bool use_qmm6 = true;
-    // ... and, where its plan exists (round 6: gate|up and qkv of a 2,560-wide model), the row-streaming matmul (qmm7.h) instead of the
-    // register-resident one: the rows' arrival overlaps the walk, a step costs by its 16-row blocks (3 included).  force_qmm7: the
-    // kernel-level entry point asked for it by name (an error where it does not apply).
-    bool use_qmm7 = true, force_qmm7 = false;
     tl_linear_info *linfo = nullptr;    // kernel-level entry points: which kernel a projection ran
-    int force_linear = 0;               // kernel-level entry points: 1 = fused GEMV, 2 = skinny matmul
-    int qmm3_mode = -1;                 // skinny matmul grid: -1 by shape (qmm3_plan), 0 one-shot, 1 persistent
-    void read_env() { if (const char *q = getenv("TL_QMM3_MIN_M")) qmm3_min_rows = std::max(1, atoi(q)); }
+    // what the routing (linear_plan.h) sees of a matrix, of a layer
+    ProjShape shape(const tl_w4 &w) const { return ProjShape{w.rows, w.cols, tiled.count(w.weight_dev) != 0}; }
+    LayerShapes shapes(const tl_layer_weights &w) const { return LayerShapes{shape(w.wqkv), shape(w.wo), shape(w.wgu), shape(w.wdown), w.wgu.weight_dev != nullptr}; }
 };
 
 // ---- one projection, by name ------------------------------------------------------------------------------
@@ -278,7 +260,7 @@ static int engine_qmv(LinearCtx &ctx, const Proj &p, ProfCtx *pc = nullptr, Proj
                 a3.norm_out = (const uint16_t *)p.norm_out;
                 a3.out_w = p.out_w;
             }
-            if ((merge ? launch_qmv3_attn_merge_bf16(a3, p.n_splits, ctx.stream) : launch_qmv3_bf16(a3, p.pro, p.epi, ctx.stream)) != 0)
+            if ((merge ? launch_qmv3_attn_merge_bf16(a3, p3, p.n_splits, ctx.stream) : launch_qmv3_bf16(a3, p3, p.pro, p.epi, ctx.stream)) != 0)
                 return fail(TL_ERR_UNSUPPORTED, merge ? "engine: no wo GEMV that merges the attention partials for this shape" : "engine: MFMA GEMV launch failed");
             if (pc) prof_after(pc, p.kind, p3.blocks);
             report_launch(ctx, 1, 1, step, {p3.MR, p3.KS, p3.CW, p3.LM, p3.blocks});
@@ -359,11 +341,6 @@ static int engine_gemm(LinearCtx &ctx, const Proj &p, bool *norm_done = nullptr)
     return TL_OK;
 }
 
-// Does the register-resident matmul (qmm6.h) take this projection at M rows?
-static bool qmm6_takes(const LinearCtx &ctx, const tl_w4 &w, int M) {
-    return ctx.use_qmm6 && ctx.force_linear == 0 && M >= ctx.qmm3_min_rows && M <= 64 && ctx.tiled.count(w.weight_dev) != 0 &&
-           qmm6_plan(M, w.cols, w.rows).ok;
-}
 // One projection through qmm6: `a` plain rows, or (ss_in given) WEIGHTED rows whose 1 / rms scales the result.  EPI_RESIDUAL: ss_out
 // receives rows / 16 partial sums of squares per row, out_w the rows weighted for the next RMSNorm (norm_out).
 static int engine_qmm6(LinearCtx &ctx, const Proj &p, ProfCtx *pc = nullptr, ProjResult *res = nullptr) {
@@ -374,9 +351,9 @@ static int engine_qmm6(LinearCtx &ctx, const Proj &p, ProfCtx *pc = nullptr, Pro
     const auto tiled = ctx.tiled.find(w.weight_dev);
     TL_REQUIRE(tiled != ctx.tiled.end(), "engine: the register-resident matmul needs the tiled weights");
     const bool a_frag = p.frag && p.ss_in != nullptr && p.epi != EPI_RESIDUAL;
-    const Qmm7Plan p7 = (ctx.use_qmm7 || ctx.force_qmm7) && a_frag && p.out_w == nullptr ? qmm7_plan(M, w.cols, w.rows) : Qmm7Plan{};
+    const Qmm7Plan p7 = (ctx.use_qmm7 || ctx.force_qmm7) && a_frag && p.out_w == nullptr ? qmm7_plan(M, w.cols, w.rows, ctx.ncu) : Qmm7Plan{};
     TL_REQUIRE(p7.ok || !ctx.force_qmm7, "engine: the row-streaming matmul takes weighted rows in fragment order (store / SwiGLU) at the shapes of qmm7_plan");
-    const Qmm6Plan pl = qmm6_plan(M, w.cols, w.rows, a_frag);
+    const Qmm6Plan pl = qmm6_plan(M, w.cols, w.rows, a_frag, ctx.ncu);
     TL_REQUIRE(p7.ok || pl.ok, "engine: the register-resident matmul does not cover this shape");
     Qmm6Args q{};
     q.wt = tiled->second.wt;
@@ -396,56 +373,19 @@ static int engine_qmm6(LinearCtx &ctx, const Proj &p, ProfCtx *pc = nullptr, Pro
     q.prof = pc ? pc->buf : nullptr;
     q.a_frag = a_frag;
     q.out_w_frag = (p.out_w_frag >= 0 ? p.out_w_frag != 0 : p.frag) && p.out_w != nullptr;
-    int n_wg = 0;
     if (p7.ok) {
-        if (launch_qmm7_bf16(q, p.epi, ctx.stream, &n_wg) != 0) return fail(TL_ERR_UNSUPPORTED, "engine: row-streaming matmul launch failed");
-        if (pc) prof_after(pc, p.kind, n_wg);
-        report_launch(ctx, 6, 1, p7.MB * 16, {p7.MB, p7.GPW, p7.T, p7.row_blocks, n_wg});
+        if (launch_qmm7_bf16(q, p7, p.epi, ctx.stream) != 0) return fail(TL_ERR_UNSUPPORTED, "engine: row-streaming matmul launch failed");
+        if (pc) prof_after(pc, p.kind, p7.wgs);
+        report_launch(ctx, 6, 1, p7.MB * 16, {p7.MB, p7.GPW, p7.T, p7.row_blocks, p7.wgs});
         TL_CHECK_LAUNCH("engine row-streaming matmul");
         return TL_OK;
     }
-    if (launch_qmm6_bf16(q, p.epi, ctx.stream, &n_wg) != 0) return fail(TL_ERR_UNSUPPORTED, "engine: register-resident matmul launch failed");
-    if (pc) prof_after(pc, p.kind, n_wg);
+    if (launch_qmm6_bf16(q, pl, p.epi, ctx.stream) != 0) return fail(TL_ERR_UNSUPPORTED, "engine: register-resident matmul launch failed");
+    if (pc) prof_after(pc, p.kind, pl.wgs * pl.row_blocks);
     if (q.ss_out) r.ss_n = w.rows / 16;
-    report_launch(ctx, 5, 1, pl.MB * 16, {pl.MB, pl.GPW, pl.NSETS, pl.row_blocks, n_wg});
+    report_launch(ctx, 5, 1, pl.MB * 16, {pl.MB, pl.GPW, pl.NSETS, pl.row_blocks, pl.wgs * pl.row_blocks});
     TL_CHECK_LAUNCH("engine register-resident matmul");
     return TL_OK;
-}
-
-// rows that engine_linear hands to the GEMV before it considers anything else
-static bool gemv_takes_rows(const LinearCtx &ctx, int M) {
-    return ctx.force_linear == 1 || (ctx.force_linear != 2 && (M < ctx.qmm3_min_rows || (M <= 8 && !ctx.use_qmm3)));
-}
-// Can `producer` (EPI_RESIDUAL) leave its rows weighted for `consumer` (PRO_RMS_WEIGHTED)?  Both must be single-pass MFMA GEMVs,
-// the producer must leave the sums of squares, and the consumer's row must sit in its register chunks (qmv3.h, reg_path).
-static bool weighted_rows_apply(const LinearCtx &ctx, const tl_w4 &producer, const tl_w4 &consumer, int M) {
-    if (!ctx.gemv_weighted_rows || !ctx.gemv_producer_ss || !gemv_takes_rows(ctx, M) || M > 8) return false;
-    if (ctx.tiled.count(producer.weight_dev) == 0 || ctx.tiled.count(consumer.weight_dev) == 0) return false;
-    const Qmv3Plan pp = qmv3_plan(M, producer.cols, producer.rows), pcn = qmv3_plan(M, consumer.cols, consumer.rows);
-    if (!pp.ok || !pcn.ok || producer.rows != consumer.cols) return false;
-    return qmv3_takes_weighted_rows(pcn, consumer.cols, producer.rows / 16);
-}
-// Does engine_linear send M rows of this projection to the K-sliced skinny matmul (qmm3.h)?  ONE predicate for the router below and for
-// the route of a layer (plan_layer decides from it whether a producer will leave weighted rows).
-static bool takes_skinny_matmul(const LinearCtx &ctx, const tl_w4 &w, int M) {
-    return !gemv_takes_rows(ctx, M) && ctx.use_qmm3 && M <= 64 && ctx.tiled.count(w.weight_dev) != 0 && qmm3_plan(M, w.cols, w.rows, ctx.qmm3_mode).ok;
-}
-
-// Can the wo GEMV of ONE decode row take the attention split partials instead of the merged row (qmv3.hip,
-// launch_qmv3_attn_merge_bf16: the instantiated plans)?  The answer is the attention plan's wo_can_merge (attn_plan.h).
-// Single-row decode with the context split 2 / 4 / 8 ways: no merge launch behind the attention kernel -- the wo GEMV forms the
-// merged row from the split partials while it stages it (qmv3.h, PRO_ATTN_MERGE).  Measured in round 3
-// (profiles/r03_labs/wo_merges_attn_ab_after_dpp.jsonl): 4 windows 1.023 -> 0.993 ms per token, 8 windows 1.033 -> 1.009 (the
-// merging GEMV costs +0.9 / +2.0 us per layer, the merge launch cost 0.6 us + a boundary); 64-token windows stay the best
-// (128-token windows: 1.022).  Other split counts, more sequences or another head size keep the merge launch.
-static bool wo_merge_applicable(const LinearCtx &ctx, const tl_w4 &wo, int batch, int n_splits, int head_dim, int num_heads) {
-    if (batch != 1 || ctx.force_linear != 0) return false;
-    if (n_splits != 2 && n_splits != 4 && n_splits != 8) return false;
-    if (head_dim != 128 || wo.cols != num_heads * 128 || ctx.tiled.count(wo.weight_dev) == 0) return false;
-    if (1 >= ctx.qmm3_min_rows && ctx.use_qmm3) return false;  // a single row would not take the GEMV
-    const Qmv3Plan pl = qmv3_plan(1, wo.cols, wo.rows);
-    const bool shape = (pl.KS == 2 && pl.CW == 4) || (pl.KS == 4 && pl.CW == 4) || (pl.KS == 8 && pl.CW == 8);
-    return pl.ok && pl.MR == 1 && shape && wo.cols / 8 <= 2 * pl.CW * 64;
 }
 
 // One projection of the decode step over `M` activation rows.  Up to 4 rows: the fused MFMA GEMV (weights streamed once,
@@ -466,9 +406,9 @@ static int engine_linear(LinearCtx &ctx, const Proj &p, ProfCtx *pc = nullptr, P
     const uint16_t *in = p.a;
     // qmm3_min_rows .. 64 rows (batched decode): K-sliced skinny MFMA matmul over the tiled weights, then the slice
     // reduction with the epilogue.  RMSNorm runs as its own launch (a slice does not see the whole row).
-    if (takes_skinny_matmul(ctx, w, M)) {
+    const Qmm3Plan p3 = skinny_matmul_plan(ctx, ctx.shape(w), M);
+    if (p3.ok) {
         const auto tiled = ctx.tiled.find(w.weight_dev);
-        const Qmm3Plan p3 = qmm3_plan(M, w.cols, w.rows, ctx.qmm3_mode);
         const bool fused_norm = p.pro == PRO_RMSNORM && ss_in != nullptr && ctx.fuse_norm;
         if (p.pro == PRO_RMSNORM && !fused_norm) {
             TL_TRY(tl_rms_norm(p.a, p.norm_w, ctx.xn, M, w.cols, ctx.rms_norm_eps, TL_BF16, ctx.stream));
@@ -489,7 +429,7 @@ static int engine_linear(LinearCtx &ctx, const Proj &p, ProfCtx *pc = nullptr, P
         q.ss = ss_in;
         q.ss_n = p.ss_in_n;
         q.eps = ctx.rms_norm_eps;
-        if (launch_qmm3_bf16(q, ctx.stream, fused_norm ? PRO_RMSNORM : PRO_NONE, ctx.qmm3_mode) != 0)
+        if (launch_qmm3_bf16(q, p3, ctx.stream, fused_norm ? PRO_RMSNORM : PRO_NONE) != 0)
             return fail(TL_ERR_UNSUPPORTED, "engine: skinny matmul launch failed");
         if (pc) prof_after(pc, p.kind, p3.persistent ? p3.grid_x : p3.grid_x * p3.slices);
         float *ss_dst = (p.ss_out && ctx.fuse_norm && qmm3_reduce_can_emit_ss(p.epi, w.rows)) ? p.ss_out : nullptr;
@@ -522,52 +462,6 @@ static int engine_linear(LinearCtx &ctx, const Proj &p, ProfCtx *pc = nullptr, P
     if (ctx.linfo) ctx.linfo->kernel = 4;
     g.norm_out = nullptr;
     return engine_gemm(ctx, g);
-}
-
-// ---- the route of a layer -------------------------------------------------------------------------------
-// Which kernel takes each projection of one layer at `batch` rows, decided once per step.  5 .. 64 rows take the BATCHED hand-over when
-// gate|up is the register-resident matmul's (qmm6.h; its and lm_head's at every row count) and wo can leave h weighted for it: rows travel
-// WEIGHTED between the projections (qkv <- w_down / the embedding, gate|up <- wo), plain beside them for the residual stream.  Measured:
-//   qkv6    on the register-resident kernel at every row count since round 5 (rows in fragment order from 9 rows): same-box A/B at
-//           128-token contexts, two alternating rounds, 24 / 32 / 48 / 64 sequences 1.91 / 1.95 / 2.56 / 2.69 -> 1.87 / 1.89 / 2.50 / 2.59 ms
-//           per step (profiles/r05_labs/batched_qkv_on_qmm6_ab.log); the sliced matmul, whose slices the attention kernel adds, is the
-//           route behind option "qmm6" = 0 only
-//   wo6     likewise at EVERY row count (round 6: its planner deals 16-row blocks to more workgroups where the rows are long -- 17-32 rows
-//           6.9 us against 8.4-9.1 for the sliced matmul + reduction that took them until then, 33-48 rows 10.1 -> 7.1; qmm6.h, qmm6_plan)
-//   down    76 groups against 160 tiles -- every workgroup of the register-resident kernel would pull 311 KB of rows for ONE tile
-//           (measured 9.0 us at 8 rows, 18.9 at 64, against 6.5 / 13.0 for the K-sliced matmul + reduction): the sliced kernel keeps it
-//           wherever its plan exists, and its reduction leaves the weighted rows
-struct LayerRoute {
-    bool batched = false;  // the batched hand-over (it also needs the row's sums of squares when the layer starts: enqueue_step)
-    bool qkv6 = false, wo6 = false;  // batched: qkv / wo on engine_qmm6 (else engine_linear)
-    enum Down { DOWN_ROUTER, DOWN_SLICED_WEIGHTED, DOWN_QMM6 } down = DOWN_ROUTER;  // batched: engine_linear (plain rows only), engine_linear leaving weighted rows, engine_qmm6
-    bool gemv_weighted = false;  // not batched: the wo GEMV leaves h weighted for the gate|up GEMV (weighted_rows_apply)
-    // every hand-over of the layer has a per-layer buffer to itself (an RMSNorm launch or a plain-row w_down goes through shared scratch)
-    bool batched_written_once() const { return batched && qkv6 && down != DOWN_ROUTER; }
-};
-static LayerRoute plan_layer(const LinearCtx &ctx, const tl_layer_weights &w, int batch, bool is_moe) {
-    LayerRoute r;
-    if (is_moe || w.wgu.weight_dev == nullptr) return r;
-    // the sliced matmul as the producer of weighted rows: the router's own predicate + what its reduction needs to emit the hand-over
-    auto sliced_leaves_weighted = [&](const tl_w4 &m) {
-        return takes_skinny_matmul(ctx, m, batch) && ctx.fuse_norm && qmm3_reduce_can_emit_ss(EPI_RESIDUAL, m.rows);
-    };
-    auto qmm6_leaves_weighted = [&](const tl_w4 &m) { return qmm6_takes(ctx, m, batch) && qmm3_takes_ss(m.rows / 16); };
-    r.gemv_weighted = weighted_rows_apply(ctx, w.wo, w.wgu, batch);
-    r.wo6 = qmm6_leaves_weighted(w.wo);
-    r.batched = qmm6_takes(ctx, w.wgu, batch) && (r.wo6 || sliced_leaves_weighted(w.wo));
-    r.qkv6 = qmm6_takes(ctx, w.wqkv, batch);
-    r.down = sliced_leaves_weighted(w.wdown) ? LayerRoute::DOWN_SLICED_WEIGHTED
-                                             : (qmm6_leaves_weighted(w.wdown) ? LayerRoute::DOWN_QMM6 : LayerRoute::DOWN_ROUTER);
-    return r;
-}
-// The weighted rows of a batched step (5 .. 64 rows) travel in fragment order (qmm6.h) from 9 rows (same-box A/B,
-// profiles/r04_labs/README.md: 16 / 32 / 64 sequences -1.5 / -4 / -1.3 % per step; at 8 sequences +2 %: row-major there) -- and from 5
-// where the row-streaming matmul (qmm7.h) is the consumer (it reads nothing else): ONE answer per step for every producer and consumer.
-static bool rows_travel_in_fragment_order(const LinearCtx &ctx, const tl_layer_weights &first, int batch) {
-    if (batch > 8) return true;
-    if (!ctx.use_qmm7 || !first.wgu.weight_dev) return false;
-    return qmm7_plan(batch, first.wgu.cols, first.wgu.rows).ok && qmm7_plan(batch, first.wqkv.cols, first.wqkv.rows).ok;
 }
 
 }  // namespace tl
@@ -603,7 +497,7 @@ extern "C" size_t tl_decode_linear_workspace_bytes(int M, int rows, int cols) {
     size_t need = align_up((size_t)((M + 15) / 16 * 16) * cols * 2, 256);  // RMSNorm output ahead of the skinny matmul / rows in fragment order (kernel 5)
     size_t partial = 0;
     for (int mode = 0; mode < 2; ++mode) {  // either grid of the skinny matmul (kernel 3 / 4 pin one)
-        const Qmm3Plan p3 = qmm3_plan(std::min(M, 64), cols, rows, mode);
+        const Qmm3Plan p3 = qmm3_plan(std::min(M, 64), cols, rows, mode, qmm3_num_cus());
         if (p3.ok) partial = std::max(partial, p3.partial_bytes);
     }
     return need + partial;
@@ -647,6 +541,7 @@ static int decode_linear_impl(const tl_tiled_w4 *w, const void *a_dev, void *out
     ctx.use_qmm7 = false, ctx.force_qmm7 = kernel == 6;  // 5 and 6 name their kernel
     ctx.qmm3_mode = kernel == 3 ? 0 : (kernel == 4 ? 1 : -1);
     ctx.linfo = info;
+    ctx.ncu = qmm3_num_cus();
     ctx.read_env();
     Proj p = proj(w->w, (const uint16_t *)a_dev, (uint16_t *)out_dev, M);
     p.pro = prologue, p.epi = epilogue, p.norm_w = norm_w_dev, p.residual = (const uint16_t *)residual_dev;
@@ -664,9 +559,9 @@ static int decode_linear_impl(const tl_tiled_w4 *w, const void *a_dev, void *out
             return fail(TL_ERR_INVALID, "decode_linear_ex: weighted rows need ss_in (a multiple of 4, at most 256 partials per row)");
         if (ex && ((ex->out_w_dev != nullptr) != (ex->norm_out_dev != nullptr) || ((ex->out_w_dev || ex->ss_out_dev) && epilogue != EPI_RESIDUAL)))
             return fail(TL_ERR_INVALID, "decode_linear_ex: ss_out / (norm_out, out_w) belong to the residual epilogue; norm_out and out_w come together");
-        if (kernel == 5 && !qmm6_plan(M, w->w.cols, w->w.rows).ok)
+        if (kernel == 5 && !qmm6_plan(M, w->w.cols, w->w.rows, false, ctx.ncu).ok)
             return fail(TL_ERR_UNSUPPORTED, "decode_linear: the register-resident matmul does not cover this shape");
-        if (kernel == 6 && !qmm7_plan(M, w->w.cols, w->w.rows).ok)
+        if (kernel == 6 && !qmm7_plan(M, w->w.cols, w->w.rows, ctx.ncu).ok)
             return fail(TL_ERR_UNSUPPORTED, "decode_linear: the row-streaming matmul does not cover this shape");
         // weighted rows enter the kernel in fragment order (qmm6.h): as the caller left them (ex->fragment_order), or re-ordered here
         if (weighted && !ex->fragment_order) {

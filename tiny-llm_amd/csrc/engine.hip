@@ -736,14 +736,14 @@ struct StepRoute {
 static StepRoute plan_step(const tl_engine *e, int batch, const AttnPlan &sp) {
     const LinearCtx &ctx = e->lin;
     StepRoute s;
-    s.frag = rows_travel_in_fragment_order(ctx, e->layers[0], batch);
-    s.head6 = qmm6_takes(ctx, e->head(), batch);
+    s.frag = rows_travel_in_fragment_order(ctx, ctx.shapes(e->layers[0]), batch);
+    s.head6 = qmm6_takes(ctx, ctx.shape(e->head()), batch);
     const bool ws_fits = sp.n_splits == 1 || sp.partials_bytes(batch) <= e->layer_ws_bytes;
     const bool own_buffers = e->layer_act_rows > 0 && batch <= e->layer_act_rows && ws_fits;
     s.per_layer = own_buffers && gemv_takes_rows(ctx, batch);
     s.per_layer_b = own_buffers && !gemv_takes_rows(ctx, batch) && ctx.force_linear == 0 && s.head6;
     for (int l = 0; l < e->cfg.num_layers; ++l) {
-        s.layers.push_back(plan_layer(ctx, e->layers[l], batch, e->is_moe(l)));
+        s.layers.push_back(plan_layer(ctx, ctx.shapes(e->layers[l]), batch, e->is_moe(l)));
         if (e->is_moe(l)) s.per_layer = false;  // a MoE layer reads and writes the shared buffers
         if (!s.layers.back().batched_written_once()) s.per_layer_b = false;
     }
@@ -809,7 +809,7 @@ static int enqueue_step(tl_engine *e, int batch, const AttnPlan &sp, const StepF
         at.qkv = b.qkv, at.q_norm = w.q_norm_dev, at.k_norm = w.k_norm_dev, at.key_pages = e->layer_k(l), at.value_pages = e->layer_v(l);
         at.key_scales = e->layer_ks(l), at.value_scales = e->layer_vs(l), at.out = b.attn, at.ws = b.attn_ws;
         at.qkv_parts = r.kept;
-        const bool wo_can_merge = !lora && wo_merge_applicable(ctx, w.wo, batch, sp.n_splits, c.head_dim, c.num_heads);
+        const bool wo_can_merge = !lora && wo_merge_applicable(ctx, ctx.shape(w.wo), batch, sp.n_splits, c.head_dim, c.num_heads);
         const AttnPlan ap = plan_decode_launch(sp, e->attn.geometry, e->attn.knobs, sp.kv8, r.kept.partial != nullptr, wo_can_merge);
         TL_TRY(launch_decode_attention(e->attn, ap, at, batch, pc));
         const bool merge_left = ap.wo_merges();  // the wo GEMV of one row merges the attention windows itself where the plan leaves them to it
@@ -987,7 +987,7 @@ static size_t matmul_ws_need(const tl_engine *e, int s0, int s1, int g0, int g1,
     for (const tl_w4 &w : mats) {
         if (!w.weight_dev) continue;
         for (int M = s0; M <= s1; ++M) {
-            const Qmm3Plan p3 = qmm3_plan(M, w.cols, w.rows);
+            const Qmm3Plan p3 = qmm3_plan(M, w.cols, w.rows, -1, e->lin.ncu);
             if (p3.ok) need = std::max(need, p3.partial_bytes);
         }
         for (int M = g0; M <= g1; ++M) need = std::max(need, tl_quantized_matmul_workspace_bytes(M, w.cols, w.rows, TL_BF16, 1, 1));
@@ -1031,7 +1031,7 @@ static int create_layer_acts(tl_engine *e) {
     const int q_dim = e->q_dim();
     // slice planes of the sliced matmuls a batched step can take (wo, w_down), the largest over 5 .. rows rows
     for (int M = std::min(5, e->lin.qmm3_min_rows); M <= layer_act_rows(c.max_batch); ++M) {
-        const Qmm3Plan pw = qmm3_plan(M, q_dim, c.hidden_size, -1), pd = qmm3_plan(M, c.intermediate_size, c.hidden_size, -1);
+        const Qmm3Plan pw = qmm3_plan(M, q_dim, c.hidden_size, -1, e->lin.ncu), pd = qmm3_plan(M, c.intermediate_size, c.hidden_size, -1, e->lin.ncu);
         if (pw.ok) e->layer_plane_bytes[0] = std::max(e->layer_plane_bytes[0], align_up(pw.partial_bytes, 256));
         if (pd.ok) e->layer_plane_bytes[1] = std::max(e->layer_plane_bytes[1], align_up(pd.partial_bytes, 256));
     }
@@ -1195,6 +1195,7 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
         e->verify_ids = piece_at<int32_t>(m, al[A::VERIFY_IDS]), e->lm_tile_max = piece_at<f32x2>(m, al[A::LM_TILE_MAX]);
     }
     e->lin.stream = e->stream, e->lin.rms_norm_eps = c.rms_norm_eps;
+    e->lin.ncu = qmm3_num_cus();
     e->lin.read_env();
     e->attn.knobs.read_env();
     // Decode steps replay as AQL packets on the engine's own HSA queue (aql.h) unless TL_AQL=0: the same captured step, without the
@@ -3547,21 +3548,21 @@ extern "C" int tl_decode_gemv_plan(int M, int rows, int cols, int *out5) {
     out5[0] = pl.MR, out5[1] = pl.KS, out5[2] = pl.CW, out5[3] = pl.LM, out5[4] = pl.blocks;
     return pl.ok ? 1 : 0;
 }
-extern "C" int tl_decode_gemv_variant_compiled(int MR, int KS, int CW, int LM) { return qmv3_variant_in_table(MR, KS, CW, LM) ? 1 : 0; }
+extern "C" int tl_decode_gemv_variant_compiled(int MR, int KS, int CW, int LM) { return qmv3_has_variant(MR, KS, CW, LM) ? 1 : 0; }
 extern "C" int tl_decode_batched_plan(int M, int rows, int cols, int *out6) {
     if (!out6 || M < 1 || rows <= 0 || cols <= 0) return 0;
-    const Qmm6Plan pl = qmm6_plan(M, cols, rows);
+    const Qmm6Plan pl = qmm6_plan(M, cols, rows, false, qmm3_num_cus());
     out6[0] = pl.MB, out6[1] = pl.GPW, out6[2] = pl.NSETS, out6[3] = pl.row_blocks, out6[4] = pl.wgs, out6[5] = pl.tiles_per_wg;
     return pl.ok ? 1 : 0;
 }
-extern "C" int tl_decode_batched_variant_compiled(int MB, int GPW) { return qmm6_variant_in_table(MB, GPW) ? 1 : 0; }
+extern "C" int tl_decode_batched_variant_compiled(int MB, int GPW) { return qmm6_has_variant(MB, GPW) ? 1 : 0; }
 extern "C" int tl_decode_streaming_plan(int M, int rows, int cols, int *out4) {
     if (!out4 || M < 1 || rows <= 0 || cols <= 0) return 0;
-    const Qmm7Plan pl = qmm7_plan(M, cols, rows);
+    const Qmm7Plan pl = qmm7_plan(M, cols, rows, qmm3_num_cus());
     out4[0] = pl.MB, out4[1] = pl.T, out4[2] = pl.GPW, out4[3] = pl.wgs;
     return pl.ok ? 1 : 0;
 }
-extern "C" int tl_decode_streaming_variant_compiled(int T, int GPW) { return qmm7_variant_in_table(T, GPW) ? 1 : 0; }
+extern "C" int tl_decode_streaming_variant_compiled(int T, int GPW) { return qmm7_has_variant(T, GPW) ? 1 : 0; }
 extern "C" int tl_decode_attention_plan(int batch, int max_context, int num_heads, int num_kv_heads, int *out3) {
     if (!out3 || batch < 1 || max_context < 0 || num_heads <= 0 || num_kv_heads <= 0 || num_heads % num_kv_heads != 0) return 0;
     AttnCtx ctx;

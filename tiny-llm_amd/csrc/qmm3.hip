@@ -135,11 +135,8 @@ int qmm3_num_cus() {
     }();
     return n;
 }
-int qmm3_default_mode() { return -1; }  // the grid is chosen by shape (qmm3_prefers_persistent); callers that need one pass `mode`
-int qmm3_forced_lm() { return 0; }
 
-int launch_qmm3_bf16(const Qmm3Args &args, hipStream_t st, int pro, int mode) {
-    const Qmm3Plan pl = qmm3_plan(args.M, args.N, args.K, mode);
+int launch_qmm3_bf16(const Qmm3Args &args, const Qmm3Plan &pl, hipStream_t st, int pro) {
     if (!pl.ok) return -1;
     if (pro == PRO_RMSNORM && (!args.ss || !args.norm_w || !qmm3_takes_ss(args.ss_n))) return -1;
     const dim3 grid(pl.grid_x, pl.slices), block(QM3_WAVES * 64);
@@ -157,7 +154,7 @@ int launch_qmm3_bf16(const Qmm3Args &args, hipStream_t st, int pro, int mode) {
         hipLaunchKernelGGL(kern, pgrid, block, pl.lds, st, args, pl.pgrid);                                          \
         return hipGetLastError() == hipSuccess ? 0 : -1;                                                             \
     }
-        QM3P_CASE(1, 1) QM3P_CASE(1, 2) QM3P_CASE(2, 1) QM3P_CASE(2, 2) QM3P_CASE(3, 1) QM3P_CASE(3, 2) QM3P_CASE(4, 1) QM3P_CASE(4, 2)
+        QM3P_TABLE(QM3P_CASE)
 #undef QM3P_CASE
         return -2;
     }
@@ -169,9 +166,7 @@ int launch_qmm3_bf16(const Qmm3Args &args, hipStream_t st, int pro, int mode) {
         hipLaunchKernelGGL(kern, grid, block, pl.lds, st, args);                                                    \
         return hipGetLastError() == hipSuccess ? 0 : -1;                                                            \
     }
-#define QM3_LM(MBv, TWv) QM3_CASE(MBv, TWv, 4) QM3_CASE(MBv, TWv, 5) QM3_CASE(MBv, TWv, 8) QM3_CASE(MBv, TWv, 10)
-    QM3_LM(1, 1) QM3_LM(2, 1) QM3_CASE(4, 1, 4) QM3_CASE(4, 1, 5) QM3_CASE(4, 2, 4)
-#undef QM3_LM
+    QM3_TABLE(QM3_CASE)
 #undef QM3_CASE
     return -2;
 }

@@ -36,13 +36,7 @@
 
 namespace tl {
 
-constexpr int QM6_WAVES = 4;
-// 4-KiB units (16 rows x one group) of a wave's transposer ring, and how many units back a slot is re-used: 8 slots, 5 units (20 KiB per
-// wave, 80 per CU) in flight.  (Two workgroups per CU with half the ring and half the register file were measured and lost at every
-// row count but lm_head at 8-16 rows: profiles/r04_labs/README.md.)
-constexpr int QM6_RING = 8;
 constexpr int QM6_LAG = 2;
-constexpr int QM6_SS_MAX = 256;  // partial sums of squares per row the prologue can fetch (16 lanes x 4 x 16 bytes)
 
 struct Qmm6Args {
     const uint32_t *wt;        // tiled packed weights [K/16][G][64][4]
@@ -80,14 +74,6 @@ __host__ __device__ inline size_t qmm6_frag_offset(int row, int col, int cols) {
 #else
 #define QM6_STAMP() do { } while (0)
 #endif
-
-// LDS: the four waves' transposer rings -- re-used, once every wave holds its fragments, for a tile's partial sums x 2 --, the
-// per-(row, group) sums, 1 / rms per row
-// (rows in fragment order need no rings: only the tiles' partial sums live there)
-__host__ __device__ inline size_t qmm6_lds_ring_bytes(int MB, bool frag) { return frag ? (size_t)2 * QM6_WAVES * MB * 1024 : (size_t)QM6_WAVES * QM6_RING * 4096; }
-__host__ __device__ inline size_t qmm6_lds_bytes(int MB, int GPW, bool frag = false) {
-    return qmm6_lds_ring_bytes(MB, frag) + (size_t)QM6_WAVES * GPW * MB * 64 + (size_t)MB * 16 * 4;
-}
 
 template <int I, int E, typename F>
 __device__ __forceinline__ void qmm6_static_for(F &&f) {
@@ -489,77 +475,7 @@ __global__ __launch_bounds__(QM6_WAVES * 64, 1) void qmm6_kernel(const Qmm6Args 
 #endif
 }
 
-struct Qmm6Plan {
-    int MB, GPW, NSETS, row_blocks, wgs, tiles_per_wg;
-    size_t lds;
-    bool ok;
-};
-int qmm3_num_cus();  // qmm3.hip
-// The (MB, GPW) pairs qmm6.hip instantiates: the register file of one wave per SIMD holds MB x GPW x 16 fragment registers
-inline bool qmm6_has_variant(int MB, int GPW) {
-    if (MB != 1 && MB != 2 && MB != 4) return false;
-    if (GPW != 2 && GPW != 4 && GPW != 5 && GPW != 8 && GPW != 19) return false;
-    return MB * GPW * 16 <= 320;
-}
-// weight sets of a workgroup that walks several tiles: tiles in flight ahead of the one computed = sets - 1, as many as the registers
-// next to the fragments hold (a tile of few rows computes in a fraction of the memory latency) and the 6-bit vmcnt counts behind the
-// first ring of units (4 (RING - 1) + (sets - 1) 2 GPW <= 63)
-constexpr int qmm6_sets(int MB, int GPW) { return GPW > 8 ? 1 : (MB * GPW <= 5 ? 4 : (MB * GPW <= 10 ? 3 : 2)); }
-// sets for a workgroup of `tpw` tiles: whole rounds of `sets` tiles run in the branch-free loop, the rest behind it (qmm6_kernel)
-inline int qmm6_pick_sets(int MB, int GPW, int tpw) { return std::min(tpw, qmm6_sets(MB, GPW)); }
-inline int qmm6_round_gpw(int gpw) { return gpw <= 2 ? 2 : (gpw <= 4 ? 4 : (gpw <= 5 ? 5 : (gpw <= 8 ? 8 : 19))); }
-inline Qmm6Plan qmm6_plan(int M, int N, int K, bool frag = false) {
-    Qmm6Plan pl{};
-    if (M < 1 || M > 64 || N <= 0 || N % 128 != 0 || K <= 0 || K % 16 != 0) return pl;
-    const int G = N / 128, tiles = K / 16;
-    if ((G + QM6_WAVES - 1) / QM6_WAVES > 19) return pl;
-    pl.GPW = qmm6_round_gpw((G + QM6_WAVES - 1) / QM6_WAVES);
-    // Row blocks per workgroup (MB = 1, 2 or 4 blocks of 16 rows; the rows beyond go to further workgroups over the same tiles).  Until round 6: the largest
-    // block whose fragments fit the registers.  But what a workgroup costs is what its CU pulls -- MB x 16 rows of N columns + its tiles' weights, at ~13.5 ns
-    // per KiB (the L2 -> CU path, profiles/r05_labs) -- plus its walk (a tile: the four waves' meeting and the stores, + MB x GPW x 4 MFMAs on one wave per
-    // SIMD), and long rows against few tiles (wo: 4,096 columns, 160 tiles) are cheaper in MORE, SMALLER workgroups: 64 rows as 4 x 56 workgroups of 16 rows
-    // x 3 tiles pull 227 KiB each where 2 x 80 of 32 rows x 2 tiles pull 326 (lab: 10.3 -> 9.1 us; 33-48 rows, three blocks instead of a padded four: 10.1
-    // -> 7.2).  gate|up / lm_head (many tiles per workgroup) keep the largest block by the same arithmetic.
-    const int blocks16 = (M + 15) / 16;
-    const int ncu = qmm3_num_cus();
-    auto shape_for = [&](int mb, Qmm6Plan &q) {
-        q.MB = mb;
-        q.row_blocks = (blocks16 + mb - 1) / mb;
-        const int wgs = std::min(tiles, std::max(1, ncu / q.row_blocks));
-        q.tiles_per_wg = (tiles + wgs - 1) / wgs;
-        q.wgs = (tiles + q.tiles_per_wg - 1) / q.tiles_per_wg;
-        // the workgroups of one tile range sit a multiple of 8 apart in the launch order: one XCD, one L2 for the weights they share
-        if (q.row_blocks > 1) q.wgs = (q.wgs + 7) / 8 * 8;
-    };
-    const int mb_max = blocks16 >= 3 ? 4 : (blocks16 >= 2 ? 2 : 1);
-    double best = 0.0;
-    bool found = false;
-    for (int mb = mb_max; mb >= 1; mb /= 2) {
-        if (!qmm6_has_variant(mb, pl.GPW) || qmm6_lds_bytes(mb, pl.GPW, frag) > 150 * 1024) continue;
-        Qmm6Plan q = pl;
-        shape_for(mb, q);
-        // (the arithmetic below decides for LONG rows against FEW tiles only -- 8 groups per wave and more, at most two tiles per workgroup on the largest
-        // block: wo.  A projection whose workgroups walk more tiles keeps the largest block; so does qkv: the row-streaming kernel (qmm7.h) is its twin
-        // bit for bit, and the order in which a group's four k-steps are added follows the row-block count -- CH below)
-        if (found && (pl.tiles_per_wg > 2 || pl.GPW < 8)) break;
-        if ((long)q.wgs * q.row_blocks > ncu + 7) continue;  // one workgroup per CU
-        const double kib = (double)std::min(mb * 16, M) * N * 2 / 1024.0 + (double)q.tiles_per_wg * G;
-        // (plain rows come through each wave's 8-slot transposer ring: a second and third pass of the ring -- MB x GPW units -- is a dependent round trip each)
-        const double us = 0.0135 * kib + q.tiles_per_wg * (0.35 + 0.03 * mb * pl.GPW) + 1.3 * ((mb * pl.GPW - 1) / QM6_RING);
-#ifdef QMM6_PLAN_LARGEST_BLOCK  // tools/lab only: the rule of rounds 4-5
-        if (found) continue;
-#endif
-        if (!found || us < best - 1e-9) pl.MB = q.MB, pl.row_blocks = q.row_blocks, pl.tiles_per_wg = q.tiles_per_wg, pl.wgs = q.wgs, best = us, found = true;
-    }
-    if (!found) return pl;
-    pl.NSETS = qmm6_pick_sets(pl.MB, pl.GPW, pl.tiles_per_wg);
-    pl.lds = qmm6_lds_bytes(pl.MB, pl.GPW, frag);
-    pl.ok = pl.lds <= 150 * 1024;
-    return pl;
-}
-
-// qmm6.hip
-bool qmm6_variant_in_table(int MB, int GPW);
-int launch_qmm6_bf16(const Qmm6Args &args, int epi, hipStream_t st, int *n_wg = nullptr);  // -1: not applicable, nothing launched
+// qmm6.hip: the launch of `pl` = qmm6_plan(args.M, args.N, args.K, args.a_frag, ncu), pl.wgs * pl.row_blocks workgroups.  -1: not applicable, nothing launched
+int launch_qmm6_bf16(const Qmm6Args &args, const Qmm6Plan &pl, int epi, hipStream_t st);
 
 }  // namespace tl

@@ -3,17 +3,7 @@
 
 namespace tl {
 
-// The instantiation table, written once: QM6_TABLE(X) expands X(MB, GPW) for every compiled pair (qmm6_has_variant restates it for
-// the planner; tests/test_decode_plans_cpu.py holds the two together).
-#define QM6_TABLE(X) X(1, 2) X(1, 4) X(1, 5) X(1, 8) X(1, 19) X(2, 2) X(2, 4) X(2, 5) X(2, 8) X(4, 2) X(4, 4) X(4, 5)
-
-bool qmm6_variant_in_table(int MB, int GPW) {
-#define QM6_MEMBER(MBv, GPWv) if (MB == MBv && GPW == GPWv) return true;
-    QM6_TABLE(QM6_MEMBER)
-#undef QM6_MEMBER
-    return false;
-}
-
+// the dispatch is generated from the instantiation table (linear_plan.h, QM6_TABLE)
 template <int MB, int GPW, int EPI, int NS>
 static int launch_sets6(const Qmm6Args &a, const Qmm6Plan &pl, hipStream_t st) {
     if (pl.NSETS == NS) {
@@ -39,16 +29,14 @@ static int launch_variant6(const Qmm6Args &a, const Qmm6Plan &pl, hipStream_t st
     return -2;
 }
 
-int launch_qmm6_bf16(const Qmm6Args &args, int epi, hipStream_t st, int *n_wg) {
+int launch_qmm6_bf16(const Qmm6Args &args, const Qmm6Plan &pl, int epi, hipStream_t st) {
     if (args.a_frag && (epi == EPI_RESIDUAL || !args.ss)) return -1;  // fragment order is the layout of WEIGHTED rows
-    const Qmm6Plan pl = qmm6_plan(args.M, args.N, args.K, args.a_frag != 0);
     if (!pl.ok) return -1;
     if (args.ss && (args.ss_n <= 0 || args.ss_n > QM6_SS_MAX || args.ss_n % 4 != 0)) return -1;
     if (epi == EPI_RESIDUAL && !args.residual) return -1;
     if ((args.out_w != nullptr) != (args.norm_out != nullptr) || ((args.out_w || args.ss_out) && epi != EPI_RESIDUAL)) return -1;
     Qmm6Args a = args;
     a.tiles_per_wg = pl.tiles_per_wg;
-    if (n_wg) *n_wg = pl.wgs * pl.row_blocks;
     if (epi == EPI_STORE) return launch_variant6<EPI_STORE>(a, pl, st);
     if (epi == EPI_RESIDUAL) return launch_variant6<EPI_RESIDUAL>(a, pl, st);
     if (epi == EPI_SWIGLU) return launch_variant6<EPI_SWIGLU>(a, pl, st);

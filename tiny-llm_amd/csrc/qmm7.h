@@ -36,7 +36,6 @@
 
 namespace tl {
 
-constexpr int QM7_WAVES = 4;
 #ifndef QM7_PIN_ABOVE
 #define QM7_PIN_ABOVE 96
 #endif
@@ -46,8 +45,6 @@ constexpr int QM7_WAVES = 4;
 #else
 #define QM7_STAMP() do { } while (0)
 #endif
-
-__host__ __device__ inline size_t qmm7_lds_bytes(int MB, int T) { return (size_t)QM7_WAVES * T * MB * 1024 + (size_t)MB * 16 * 4; }
 
 #ifndef QM7_TIE2
 #define QM7_TIE2 1
@@ -297,35 +294,8 @@ __global__ __launch_bounds__(QM7_WAVES * 64, OCC) void qmm7_kernel(const Qmm6Arg
 #endif
 }
 
-struct Qmm7Plan {
-    int MB, T, GPW, wgs, row_blocks;
-    size_t lds;
-    bool ok;
-};
-// the (T, GPW) pairs qmm7.hip instantiates, each for MB = 1 .. 4 and the two epilogues
-inline bool qmm7_has_variant(int T, int GPW) { return GPW == 5 && (T == 2 || T == 5); }
-inline Qmm7Plan qmm7_plan(int M, int N, int K) {
-    Qmm7Plan pl{};
-    if (M < 1 || M > 64 || N <= 0 || N % 128 != 0 || K <= 0 || K % 16 != 0) return pl;
-    const int G = N / 128, tiles = K / 16;
-    pl.MB = (M + 15) / 16;
-    pl.row_blocks = 1;
-    const int gpw = (G + QM7_WAVES - 1) / QM7_WAVES;
-    pl.GPW = gpw <= 5 ? 5 : 0;
-    if (gpw < 4) return pl;  // a wave that idles through most of a 5-group body: the register-resident kernel's smaller variants take the shape
-    const int ncu = qmm3_num_cus();
-    const int tpw = (tiles + ncu - 1) / ncu;
-    pl.T = tpw <= 2 ? 2 : (tpw <= 5 ? 5 : 0);
-    if (!qmm7_has_variant(pl.T, pl.GPW)) return pl;
-    pl.wgs = (tiles + pl.T - 1) / pl.T;
-    pl.lds = qmm7_lds_bytes(pl.MB, pl.T);
-    pl.ok = pl.lds <= 150 * 1024;
-    return pl;
-}
-
-// qmm7.hip
-bool qmm7_variant_in_table(int T, int GPW);
+// qmm7.hip: the launch of `pl` = qmm7_plan(args.M, args.N, args.K, ncu), pl.wgs workgroups.
 // rows in fragment order with their sums of squares (a.a_frag, a.ss), epilogue store or SwiGLU.  -1: not applicable, nothing launched
-int launch_qmm7_bf16(const Qmm6Args &args, int epi, hipStream_t st, int *n_wg = nullptr);
+int launch_qmm7_bf16(const Qmm6Args &args, const Qmm7Plan &pl, int epi, hipStream_t st);
 
 }  // namespace tl

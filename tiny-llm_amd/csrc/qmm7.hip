@@ -3,17 +3,7 @@
 
 namespace tl {
 
-// The instantiation table, written once: QM7_TABLE(X) expands X(T, GPW) for every compiled pair (qmm7_has_variant restates it for the
-// planner; tests/test_decode_plans_cpu.py holds the two together).  Every pair exists for 1 .. 4 row blocks and both epilogues.
-#define QM7_TABLE(X) X(2, 5) X(5, 5)
-
-bool qmm7_variant_in_table(int T, int GPW) {
-#define QM7_MEMBER(Tv, GPWv) if (T == Tv && GPW == GPWv) return true;
-    QM7_TABLE(QM7_MEMBER)
-#undef QM7_MEMBER
-    return false;
-}
-
+// the dispatch is generated from the instantiation table (linear_plan.h, QM7_TABLE)
 #ifndef QM7_LAB_NB
 #define QM7_LAB_NB 0
 #endif
@@ -46,16 +36,11 @@ static int launch_variant7(const Qmm6Args &a, const Qmm7Plan &pl, hipStream_t st
     return -2;
 }
 
-int launch_qmm7_bf16(const Qmm6Args &args, int epi, hipStream_t st, int *n_wg) {
+int launch_qmm7_bf16(const Qmm6Args &args, const Qmm7Plan &pl, int epi, hipStream_t st) {
     if (!args.a_frag || !args.ss) return -1;  // weighted rows in fragment order, with their sums of squares
     if (args.ss_n <= 0 || args.ss_n > QM6_SS_MAX || args.ss_n % 4 != 0) return -1;
     if (args.out_w || args.ss_out || args.residual) return -1;
-    Qmm7Plan pl = qmm7_plan(args.M, args.N, args.K);
     if (!pl.ok) return -1;
-#if QM7_LAB_OCC == 2  // lab: the step's row blocks in two halves, two workgroups per CU
-    if (pl.MB == 4 || pl.MB == 2) pl.MB /= 2, pl.row_blocks = 2, pl.lds = qmm7_lds_bytes(pl.MB, pl.T);
-#endif
-    if (n_wg) *n_wg = pl.wgs;
     if (epi == EPI_STORE) return launch_variant7<EPI_STORE>(args, pl, st);
     if (epi == EPI_SWIGLU) return launch_variant7<EPI_SWIGLU>(args, pl, st);
     return -1;

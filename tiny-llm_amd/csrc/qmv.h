@@ -29,11 +29,9 @@
 //    backs the public operator.
 #pragma once
 #include "common.h"
+#include "linear_plan.h"
 
 namespace tl {
-
-enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_ATTN_MERGE = 2, PRO_RMS_WEIGHTED = 3 };  // the last two: qmv3.h only (Qmv3Args::merge_ws / ::ss_in)
-enum { EPI_STORE = 0, EPI_RESIDUAL = 1, EPI_SWIGLU = 2 };
 
 struct QmvArgs {
     const uint16_t *scales;    // [K, N/128]
@@ -92,13 +90,6 @@ struct QmvBatch {
     uint16_t s[QMV_U][RPL];
     uint16_t b[QMV_U][RPL];
 };
-
-__host__ __device__ inline size_t qmv_lds_bytes(int MR, int N, int WN, int RPL) {
-    size_t x = (size_t)MR * N * 2;
-    size_t as = (size_t)MR * (N / 32) * 4;
-    size_t red = WN > 1 ? (size_t)4 * RPL * 4 * MR * 4 : 0;  // [waves][RPL*4 rows][MR]
-    return x + as + red + 64;
-}
 
 template <typename TT, int MR, int WN, int RPL, int PRO, int EPI>
 __global__ __launch_bounds__(256) void qmv_kernel(const QmvArgs p_in) {
@@ -366,44 +357,6 @@ __global__ __launch_bounds__(256) void qmv_kernel(const QmvArgs p_in) {
         }
     }
     prof_end(p.prof, prof_t0);
-}
-
-// Host-side launch heuristic shared by the operator and the decode fast path.
-struct QmvPlan {
-    int MR, WN, RPL, RB, blocks;
-    size_t lds;
-};
-inline QmvPlan qmv_plan(int M, int N, int K) {
-    QmvPlan pl;
-    pl.MR = M <= 1 ? 1 : (M <= 2 ? 2 : (M <= 4 ? 4 : 8));
-    const int J = (N + 511) / 512;
-    // rows per workgroup: largest tile that still yields >= 3 workgroups per CU
-    // (256 CUs); small K falls back to splitting the reduction over the waves.
-    int rb = 4;
-    const int cands[3] = {32, 16, 8};
-    for (int c : cands) {
-        if ((K + c - 1) / c >= 768) {
-            rb = c;
-            break;
-        }
-    }
-    if (rb == 32) {
-        pl.WN = 1; pl.RPL = 2;
-    } else if (rb == 16) {
-        pl.WN = 1; pl.RPL = 1;
-    } else if (rb == 8) {
-        pl.WN = 2; pl.RPL = 1;
-    } else {
-        pl.WN = 4; pl.RPL = 1;
-    }
-    if (pl.WN > J) {  // not enough 512-column chunks to split: keep waves on rows
-        pl.WN = J >= 2 ? 2 : 1;
-        pl.RPL = 1;
-    }
-    pl.RB = 4 * (4 / pl.WN) * pl.RPL;
-    pl.blocks = (K + pl.RB - 1) / pl.RB;
-    pl.lds = qmv_lds_bytes(pl.MR, N, pl.WN, pl.RPL);
-    return pl;
 }
 
 // Fused-variant launcher (bf16 only), defined in qmv_fused.hip.  pro/epi are PRO_* / EPI_*.

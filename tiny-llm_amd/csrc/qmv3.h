@@ -31,9 +31,6 @@
 
 namespace tl {
 
-constexpr int Q3_LMAX = 10;  // most groups (1 KiB wave-loads) per compute wave; kernels are specialised on LM <= Q3_LMAX
-constexpr int Q3_PAD = 8;    // bf16 elements of padding per activation row in LDS
-
 struct Qmv3Args {
     const uint32_t *wt;   // tiled packed weights [K/16][G][64][4]
     const uint32_t *sbt;  // tiled scale|bias<<16 (bf16 pair) [K/16][G][16]
@@ -102,20 +99,6 @@ template <typename T> __device__ __forceinline__ void q3_store(T *ptr, T v) {
 #else
 #define Q3_ABL(bit) 0
 #endif
-
-// LDS: activation rows [MR][N + Q3_PAD] bf16, then Q3_LMAX zero groups (a wave's fixed-length body may run past the
-// end of the row: it then reads finite data it multiplies by a zero scale); per-group sums [G + Q3_LMAX][16] fp32;
-// split-K partials.
-__host__ __device__ inline size_t qmv3_lds_xsum_off(int MR, int N) {
-    return (((size_t)MR * (N + Q3_PAD) + (size_t)Q3_LMAX * 128) * 2 + 15) & ~(size_t)15;
-}
-__host__ __device__ inline size_t qmv3_lds_red_off(int MR, int N) {
-    return qmv3_lds_xsum_off(MR, N) + (size_t)(N / 128 + Q3_LMAX) * 16 * 4;
-}
-__host__ __device__ inline size_t qmv3_lds_bytes(int MR, int N, int KS, int CW) {
-    size_t red = KS > 1 ? (size_t)CW * MR * 16 * 4 : 0;
-    return qmv3_lds_red_off(MR, N) + red + (size_t)MR * CW * 4 + 64;  // + RMSNorm partial sums of squares
-}
 
 // 8 packed nibbles (n_i = q_2i, n_{i+4} = q_{2i+1}) -> four bf16 pairs (128+q_2i, 128+q_2i+1): 3 shifts + 4 v_and_or_b32
 // ((w >> 4i) & mask | magic).  With literal constants hipcc emits v_and + v_or (11 ops: VOP3 cannot take two literals), so
@@ -505,69 +488,9 @@ __global__ __launch_bounds__(CW * 64) void qmv3_kernel(const Qmv3Args p) {
     prof_end(p.prof, prof_t0);
 }
 
-struct Qmv3Plan {
-    int MR, KS, CW, LM, blocks;
-    size_t lds;
-    bool ok;
-};
-// The (MR, KS, CW, LM) combinations qmv3.hip instantiates (its Q3_TABLE, restated) = the ones the planner below can return:
-//   1 / 2 / 4 / 8 rows x {1, 2, 4 reduction splits on 4 waves} x {4, 5, 8, 10 groups per wave} (8 rows: 2 / 4 splits only beyond 10 groups,
-//   i.e. 8 or 10 per wave -- the finer cut of short reductions is a rule for 1-4 rows); 8 splits on 8 waves with 8 or 10 groups per wave
-//   (8 splits mean more than 40 groups; four rows over 65-80 groups go to 16 waves instead); 4 rows x 16 splits on 16 waves x {4, 5}.
-inline bool qmv3_has_variant(int MR, int KS, int CW, int LM) {
-    const bool mr = MR == 1 || MR == 2 || MR == 4 || MR == 8;
-    const bool lm4 = LM == 4 || LM == 5 || LM == 8 || LM == 10, hi = LM == 8 || LM == 10;
-    if (CW == 4 && KS == 1) return mr && lm4;
-    if (CW == 4 && (KS == 2 || KS == 4)) return mr && (MR == 8 ? hi : lm4);
-    if (CW == 8 && KS == 8) return mr && hi && !(MR == 4 && LM == 10);
-    return MR == 4 && KS == 16 && CW == 16 && (LM == 4 || LM == 5);
-}
-inline int qmv3_round_lm(int lper) { return lper <= 4 ? 4 : (lper <= 5 ? 5 : (lper <= 8 ? 8 : Q3_LMAX)); }
-inline Qmv3Plan qmv3_plan(int M, int N, int K, int force_ks = 0, int force_cw = 0) {
-    Qmv3Plan pl{};
-    pl.MR = M <= 1 ? 1 : (M <= 2 ? 2 : (M <= 4 ? 4 : 8));
-    const int G = N / 128;
-    const int tiles = K / 16;
-    int ks = 1;
-    while (ks < 8 && (G + ks - 1) / ks > Q3_LMAX) ks *= 2;
-    {
-        // a grid of 1 .. 4 workgroups per CU with a ragged last round (gate|up: 608 workgroups on 256 CUs = 3 rounds for
-        // 2.4 rounds of work) runs faster cut twice as fine (measured 7.3 -> 6.9 us); smaller and larger grids do not.
-        // Up to 4 rows since round 3 (tools/lab/plan_lab, gate|up with weighted rows: 2 rows 8.32 -> 7.47 us, 4 rows 10.05 -> 9.39;
-        // qkv and wo do not meet the condition and would lose: profiles/r03_labs/gemv_plan_sweep_rows_1_2_4.log)
-        const int blocks = (tiles + (4 / ks) - 1) / (4 / (ks > 4 ? 4 : ks));
-        const double x = blocks / 256.0;
-        const double rounds = (double)(int)(x + 0.999999);
-        if (M <= 4 && ks < 4 && x >= 1.0 && x < 4.0 && rounds / x > 1.2 && (G + 2 * ks - 1) / (2 * ks) >= 4) ks *= 2;
-    }
-    // four rows over a long reduction (w_down: 76 groups): 16 waves with 5 groups each stage the 4 x 9,728 activations and run
-    // their chains twice as fast as 8 waves with 10 (tools/lab/plan_lab: 9.50 -> 7.65 us; at 1 / 2 rows the 8-wave cut wins,
-    // 5.66 / 6.27 against 5.86 / 6.58)
-    // (only where a 16-wave kernel exists: 4 or 5 groups per wave, i.e. reductions of up to 80 groups; longer ones keep 8 waves)
-    if (pl.MR == 4 && ks == 8 && (G + 15) / 16 >= 4 && (G + 15) / 16 <= 5) ks = 16;
-    if (force_ks > 0) ks = force_ks;
-    pl.KS = ks;
-    pl.CW = ks >= 8 ? ks : 4;
-    if (force_cw > 0 && force_cw >= ks) pl.CW = force_cw;
-    pl.LM = qmv3_round_lm((G + ks - 1) / ks);
-    const int wr = pl.CW / pl.KS;
-    pl.blocks = (tiles + wr - 1) / wr;
-    pl.lds = qmv3_lds_bytes(pl.MR, N, pl.KS, pl.CW);
-    // ok = the shape fits AND a kernel is compiled for (MR, KS, CW, LM): everything else goes to the packed-dot GEMV (qmv.h)
-    pl.ok = K > 0 && K % 16 == 0 && N % 128 == 0 && M >= 1 && M <= 8 && (G + ks - 1) / ks <= Q3_LMAX &&
-            pl.lds <= 150 * 1024 && qmv3_has_variant(pl.MR, pl.KS, pl.CW, pl.LM);
-    return pl;
-}
-
-// PRO_RMS_WEIGHTED: the row must sit in the staging registers of one pass and its sums of squares in one 16-byte load per lane
-inline bool qmv3_takes_weighted_rows(const Qmv3Plan &pl, int N, int ss_n) {
-    return pl.ok && N / 8 <= (pl.MR <= 2 ? 3 : 2) * pl.CW * 64 && ss_n > 0 && ss_n <= 256 && (ss_n & 3) == 0;
-}
-
-// qmv3.hip
-bool qmv3_variant_in_table(int MR, int KS, int CW, int LM);  // the instantiation table itself (CPU test vs qmv3_has_variant)
-int launch_qmv3_bf16(const Qmv3Args &args, int pro, int epi, hipStream_t st, int force_ks = 0, int force_cw = 0);  // -1: not applicable
-int launch_qmv3_attn_merge_bf16(const Qmv3Args &args, int n_splits, hipStream_t st);  // -1: not applicable, nothing launched
+// qmv3.hip: the launch of `pl` = qmv3_plan(args.M, args.N, args.K[, force_ks, force_cw]).  -1: not applicable, nothing launched
+int launch_qmv3_bf16(const Qmv3Args &args, const Qmv3Plan &pl, int pro, int epi, hipStream_t st);
+int launch_qmv3_attn_merge_bf16(const Qmv3Args &args, const Qmv3Plan &pl, int n_splits, hipStream_t st);
 // standard checkpoint layout -> tiled layout (device to device, stream ordered)
 int repack_w4_tiled(const uint32_t *w, const uint16_t *scales, const uint16_t *biases, uint32_t *wt, uint32_t *sbt, int K,
                     int N, hipStream_t st);

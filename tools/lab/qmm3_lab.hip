@@ -44,16 +44,16 @@ int main(int argc, char **argv) {
             CK(hipMemcpy(nw_dev, hn.data(), N * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(ss, hss.data(), hss.size() * 4, hipMemcpyHostToDevice));
         }
         size_t pbytes = 0;
-        for (int mode = 0; mode < 2; ++mode) pbytes = std::max(pbytes, qmm3_plan(M, N, K, mode).partial_bytes);
+        for (int mode = 0; mode < 2; ++mode) pbytes = std::max(pbytes, qmm3_plan(M, N, K, mode, qmm3_num_cus()).partial_bytes);
         CK(hipMalloc(&partial, pbytes));
         const int pro = argc > 3 ? atoi(argv[3]) : PRO_NONE;
         std::vector<uint16_t> ho[3];
         for (int mode = 0; mode < 2; ++mode) {
             if (only_mode >= 0 && mode != only_mode) continue;
-            const Qmm3Plan pl = qmm3_plan(M, N, K, mode);
+            const Qmm3Plan pl = qmm3_plan(M, N, K, mode, qmm3_num_cus());
             const int iters = 24;
             auto mm = [&](int i) { Qmm3Args q{}; q.wt = w + (size_t)(i % copies) * wwords; q.sbt = sb + (size_t)(i % copies) * swords; q.a = a; q.partial = partial; q.M = M; q.N = N; q.K = K; q.norm_w = nw_dev; q.ss = ss; q.eps = 1e-6f;
-                                   if (launch_qmm3_bf16(q, 0, pro, mode) != 0) { printf("launch failed\n"); exit(1); } };
+                                   if (launch_qmm3_bf16(q, pl, 0, pro) != 0) { printf("launch failed\n"); exit(1); } };
             auto red = [&]() { if (launch_qmm3_reduce_bf16(partial, pl.slices, M, K, EPI_STORE, nullptr, out[mode], nullptr, 0) != 0) { printf("reduce failed\n"); exit(1); } };
             CK(hipMemset(partial, 0xff, pbytes));
             for (int i = 0; i < 3; ++i) { mm(i); red(); }
@@ -71,7 +71,7 @@ int main(int argc, char **argv) {
                 unsigned long long *pb; CK(hipMalloc(&pb, nw * 16 * 8)); CK(hipMemset(pb, 0, nw * 16 * 8));
                 Qmm3Args q{}; q.wt = w; q.sbt = sb; q.a = a; q.partial = partial; q.M = M; q.N = N; q.K = K; q.prof = pb;
                 q.norm_w = nw_dev; q.ss = ss; q.eps = 1e-6f;
-                launch_qmm3_bf16(q, 0, pro, mode); CK(hipDeviceSynchronize());
+                launch_qmm3_bf16(q, pl, 0, pro); CK(hipDeviceSynchronize());
                 std::vector<unsigned long long> hp(nw * 16); CK(hipMemcpy(hp.data(), pb, nw * 16 * 8, hipMemcpyDeviceToHost));
                 int rate = 0; CK(hipDeviceGetAttribute(&rate, hipDeviceAttributeWallClockRate, 0));
                 unsigned long long tmin = ~0ull, tmax = 0; for (size_t i = 0; i < nw; ++i) if (hp[i * 16]) { tmin = std::min(tmin, hp[i * 16]); for (int k = 0; k < 16; ++k) tmax = std::max(tmax, hp[i * 16 + k]); }

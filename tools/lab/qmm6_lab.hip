@@ -46,8 +46,8 @@ int main(int argc, char **argv) {
             std::vector<float> hss((size_t)M * 160, 10.f); CK(hipMemcpy(ss, hss.data(), hss.size() * 4, hipMemcpyHostToDevice));
         }
         const int frag = (argc > 2 ? atoi(argv[2]) : 0) && sh.epi != EPI_RESIDUAL;
-        const Qmm6Plan pl = qmm6_plan(M, N, K, frag != 0);
-        const Qmm3Plan p3 = qmm3_plan(M, N, K, -1);
+        const Qmm6Plan pl = qmm6_plan(M, N, K, frag != 0, qmm3_num_cus());
+        const Qmm3Plan p3 = qmm3_plan(M, N, K, -1, qmm3_num_cus());
         CK(hipMalloc(&partial, std::max<size_t>(p3.partial_bytes, 16)));
         if (!pl.ok) { printf("%-8s rows %d: no plan\n", sh.name, M); continue; }
         const int epi = sh.epi;
@@ -58,10 +58,10 @@ int main(int argc, char **argv) {
             Qmm6Args q{}; q.wt = w + (size_t)(i % copies) * wwords; q.sbt = sb + (size_t)(i % copies) * swords; q.a = a; q.out = out; q.M = M; q.N = N; q.K = K; q.eps = 1e-6f;
             if (epi == EPI_RESIDUAL) { q.residual = res; q.norm_out = nw_dev; q.out_w = outw; q.ss_out = ssout; } else { q.ss = ss; q.ss_n = 160; q.a_frag = frag; }
             q.prof = prof;
-            if (launch_qmm6_bf16(q, epi, 0) != 0) { printf("qmm6 launch failed\n"); exit(1); } };
+            if (launch_qmm6_bf16(q, pl, epi, 0) != 0) { printf("qmm6 launch failed\n"); exit(1); } };
         auto mm3 = [&](int i) {
             Qmm3Args q{}; q.wt = w + (size_t)(i % copies) * wwords; q.sbt = sb + (size_t)(i % copies) * swords; q.a = a; q.partial = partial; q.M = M; q.N = N; q.K = K; q.eps = 1e-6f;
-            if (launch_qmm3_bf16(q, 0, PRO_NONE, -1) != 0) { printf("qmm3 launch failed\n"); exit(1); }
+            if (launch_qmm3_bf16(q, p3, 0, PRO_NONE) != 0) { printf("qmm3 launch failed\n"); exit(1); }
             if (launch_qmm3_reduce_bf16(partial, p3.slices, M, K, epi, res, out, nullptr, 0) != 0) { printf("reduce failed\n"); exit(1); } };
         const int iters = 24;
         float ms6, ms3;
@@ -76,7 +76,7 @@ int main(int argc, char **argv) {
         printf("%-8s rows %2d  qmm6%s <MB %d GPW %2d sets %d> %3d x %d wg, %2d tiles each: %6.2f us   |   qmm3 + reduction (%d slices): %6.2f us\n", sh.name, M, frag ? " (fragment order)" : "", pl.MB, pl.GPW,
                pl.NSETS, pl.wgs, pl.row_blocks, pl.tiles_per_wg, ms6 * 1000.f / iters, p3.slices, ms3 * 1000.f / iters);
         {   // the row-streaming matmul (qmm7.h) on the same inputs: time, and bit equality with the register-resident kernel's output
-            const Qmm7Plan p7 = qmm7_plan(M, N, K);
+            const Qmm7Plan p7 = qmm7_plan(M, N, K, qmm3_num_cus());
             if (frag && p7.ok && epi != EPI_RESIDUAL) {
                 const size_t ob = (size_t)M * (epi == EPI_SWIGLU ? K / 2 : K) * 2;
                 std::vector<uint16_t> o6(ob / 2), o7(ob / 2);
@@ -85,7 +85,7 @@ int main(int argc, char **argv) {
                 auto mm7 = [&](int i) {
                     Qmm6Args q{}; q.wt = w + (size_t)(i % copies) * wwords; q.sbt = sb + (size_t)(i % copies) * swords; q.a = a; q.out = out; q.M = M; q.N = N; q.K = K; q.eps = 1e-6f;
                     q.ss = ss; q.ss_n = 160; q.a_frag = 1;
-                    if (launch_qmm7_bf16(q, epi, 0) != 0) { printf("qmm7 launch failed\n"); exit(1); } };
+                    if (launch_qmm7_bf16(q, p7, epi, 0) != 0) { printf("qmm7 launch failed\n"); exit(1); } };
                 mm7(0); CK(hipDeviceSynchronize()); CK(hipMemcpy(o7.data(), out, ob, hipMemcpyDeviceToHost));
                 size_t diff = 0; for (size_t i = 0; i < o6.size(); ++i) diff += o6[i] != o7[i];
                 float ms7;
@@ -99,7 +99,7 @@ int main(int argc, char **argv) {
                     const size_t nw7 = (size_t)p7.wgs * QM7_WAVES;
                     unsigned long long *pb7 = nullptr; CK(hipMalloc(&pb7, nw7 * 16 * 8)); CK(hipMemset(pb7, 0, nw7 * 16 * 8));
                     Qmm6Args q{}; q.wt = w; q.sbt = sb; q.a = a; q.out = out; q.M = M; q.N = N; q.K = K; q.eps = 1e-6f; q.ss = ss; q.ss_n = 160; q.a_frag = 1; q.prof = pb7;
-                    launch_qmm7_bf16(q, epi, 0); CK(hipDeviceSynchronize());
+                    launch_qmm7_bf16(q, p7, epi, 0); CK(hipDeviceSynchronize());
                     std::vector<unsigned long long> hp(nw7 * 16); CK(hipMemcpy(hp.data(), pb7, nw7 * 16 * 8, hipMemcpyDeviceToHost));
                     double sum[16] = {0}; size_t cnt[16] = {0}; unsigned long long tmin = ~0ull, tmax = 0, smax = 0;
                     for (size_t i = 0; i < nw7; ++i) if (hp[i * 16]) { tmin = std::min(tmin, hp[i * 16]); smax = std::max(smax, hp[i * 16]); for (int k = 1; k < 14; ++k) { if (hp[i * 16 + k]) { sum[k] += (double)(hp[i * 16 + k] - hp[i * 16]); cnt[k]++; tmax = std::max(tmax, hp[i * 16 + k]); } } }
