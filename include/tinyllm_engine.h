@@ -355,6 +355,43 @@ typedef struct tl_verify_result {
 int tl_engine_verify_batch(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, int commit,
                            tl_verify_result *out);
 
+/* Prompt lookup: draft-free proposals for tl_engine_verify_batch, made on the device (csrc/lookup.h).  The
+ * proposer -- "ngram" speculation, prompt_lookup_num_tokens -- finds the last few ids of a sequence earlier in the sequence and proposes
+ * what followed them.
+ *   rule       T[s0 .. e] are a row's ids, last = T[e]; N = max_ngram in 1 .. TL_LOOKUP_MAX_NGRAM, min_ngram in 1 .. N, K = num_proposals in
+ *              1 .. TL_LOOKUP_MAX_PROPOSALS.  A candidate is every i in [s0, e) with T[i] == last; raw(i) = the largest
+ *              m <= min(N, i - s0 + 1) with T[i - j] == T[e - j] for all 0 <= j < m; it is eligible with raw(i) >= min_ngram;
+ *              avail(i) = min(K, e - i).  The choice is the eligible candidate with the largest (raw, avail, i), compared in that order:
+ *              the longest match, then the most continuation ids, then the most recent.  The proposals are T[i + 1 .. i + avail]; none
+ *              where nothing is eligible.  Integer compares decide everything: the result is the same on every run.
+ *   history    tl_engine_set_lookup(e, slot, 1) arms a live slot: from then on the engine keeps the slot's ordered ids resident on the
+ *              device, H[j] = the id whose K/V sits at position j, for s0 <= j < context length, s0 = the context length at arming (ids
+ *              before it are unknown and never matched; arm right after tl_engine_begin to have the prompt matched).  e is the context
+ *              length and last the slot's pending token.  The ids of prefill, packed prefill, score, embed and verify chunks and of a
+ *              prefix attach are recorded as they are uploaded; tl_engine_set_token's token too.  A DECODE STEP RECORDS NOTHING: it is
+ *              the program it was, with or without an armed slot.  The ids the steps produced lie in the slot's token ring (4,096 ids);
+ *              the propose launch fetches them from there first, and so do tl_engine_rewind, tl_engine_fork, tl_engine_move and a chunk
+ *              about to be recorded (one small launch, only where the slot is behind).  A decode call that would leave more than 4,095
+ *              unrecorded ids launches that fetch ahead of itself; a single call of more than 4,095 steps starts the slot's history over
+ *              instead: s0 = the context length the call leaves.
+ *   life       tl_engine_begin and tl_engine_release switch it off, tl_engine_move carries the history, tl_engine_fork copies it, park /
+ *              unpark keep it, tl_engine_rewind shortens it (a rewind below s0 lowers s0), beam search refuses the slot.  Arming an
+ *              armed slot changes nothing.  The history rows (max_batch x max_pages_per_seq x page_size x 4 bytes) and the results of one
+ *              launch are allocated by the first arming call and counted in stats.workspace_bytes.
+ * tl_engine_lookup_propose: proposals for n_seqs (1 .. 64) armed slots in one launch (one workgroup per slot), one small device-to-host
+ * copy and one synchronisation.  tokens_out / lens_out are exactly the `tokens` / `lens` of tl_engine_verify_batch over the same slots:
+ * each chunk is the slot's pending token followed by its proposals, at most min(K, max_lens[i] - 1) of them (max_lens NULL: 8 each),
+ * the chunks back to back (tokens_out: room for the sum of max_lens, at most 64).  It refuses, with nothing done, whatever
+ * tl_engine_verify_batch refuses of a slot (parked, stopped, sampling, processing, Mirostat or adapter slots), an unarmed slot, a slot
+ * named twice, a sum of max_lens above 64 and parameters out of range.
+ * tl_engine_lookup_state: whether the slot is armed, s0, and how far H is recorded (NULL: not wanted). */
+#define TL_LOOKUP_MAX_NGRAM 16
+#define TL_LOOKUP_MAX_PROPOSALS 7
+int tl_engine_set_lookup(tl_engine *e, int slot, int on);
+int tl_engine_lookup_propose(tl_engine *e, int n_seqs, const int *slots, const int *max_lens, int max_ngram, int min_ngram, int num_proposals,
+                             int32_t *tokens_out, int *lens_out);
+int tl_engine_lookup_state(const tl_engine *e, int slot, int *armed, int *start, int *recorded);
+
 /* Set the pending input token of a slot explicitly (e.g. sampled on the host). */
 int tl_engine_set_token(tl_engine *e, int slot, int32_t token);
 
@@ -1151,6 +1188,14 @@ int tl_process_logits(const void *logits_dev, int rows, int vocab, const uint16_
 int tl_dry_rows(int32_t *sequences_dev, int rows, int cap, const int32_t *start_dev, const int32_t *end_dev, const float *multiplier_dev,
                 const float *base_dev, const int32_t *allowed_length_dev, const int32_t *range_dev, const int32_t *no_repeat_ngram_dev,
                 const int32_t *breaker_ids_dev, const int32_t *n_breakers_dev, uint32_t *table_dev, void *logits_dev, int vocab, void *stream);
+
+/* The prompt-lookup rule of tl_engine_lookup_propose over caller rows: sequences_dev [rows, cap] int32 (cap <= 16,777,216; row r holds
+ * T[start[r] .. end[r]], end[r] < cap; a row with end < start has no proposals), max_ngram 1 .. 16, min_ngram 1 .. max_ngram,
+ * num_proposals 1 .. 7 -> proposals_dev [rows, 8] (the proposals, -1 behind them), counts_dev [rows] and, where match_dev is not NULL,
+ * match_dev [rows, 2]: the chosen position i and raw(i), (-1, 0) without a choice.  Ids outside [start, end] are never read as data.
+ * One launch of `rows` workgroups; nothing is stored to the rows.  Stream ordered. */
+int tl_lookup_rows(const int32_t *sequences_dev, int rows, int cap, const int32_t *start_dev, const int32_t *end_dev, int max_ngram, int min_ngram,
+                   int num_proposals, int32_t *proposals_dev, int32_t *counts_dev, int32_t *match_dev, void *stream);
 
 /* The attention stage of tl_engine_verify_batch over caller pools (csrc/verify_attn.h): qkv_dev [R, (Hq + 2 Hkv) * 128] bf16, the rows
  * of n_seqs (1 .. 64) sequences back to back; sequence i (host arrays) holds lens[i] (1 .. 8) rows at positions starts[i] .. of

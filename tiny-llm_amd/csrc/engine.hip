@@ -16,6 +16,7 @@
 #include "engine_layout.h"
 #include "step_end.h"  // the three step-end kernels; with it sample.h and logprob.h
 #include "dry.h"
+#include "lookup.h"
 #include "logit_process.h"
 #include "truncate.h"
 #include "grammar_stack.h"
@@ -431,7 +432,7 @@ static_assert(offsetof(GrammarRecord, tag) == 0 && offsetof(GrammarRecord, state
 static_assert(sizeof(GrammarDev *) == 8 && sizeof(StopDev *) == 8 && LPR_MAX_BIAS == TL_MAX_LOGIT_BIAS, "pointers are two words");
 static SlotSettings::Sizes settings_sizes(const tl_engine *e) {
     return {e->cfg.max_batch, e->cfg.vocab_size, e->ring_cap, LP_RECORD_WORDS, LP_MAX_TOP, LPR_MAX_BIAS, (int)sizeof(GrammarRecord), (int)sizeof(GrammarStackRecord),
-            (int)sizeof(StopRecord), SMP_MAX_VOCAB, LORA_NONE, e->cfg.max_pages_per_seq * e->cfg.page_size, DRY_MAX_BREAKERS, DRY_MAX_MATCH};
+            (int)sizeof(StopRecord), SMP_MAX_VOCAB, LORA_NONE, e->cfg.max_pages_per_seq * e->cfg.page_size, DRY_MAX_BREAKERS, DRY_MAX_MATCH, e->cfg.max_pages_per_seq * e->cfg.page_size, LOOKUP_OUT_WORDS};
 }
 
 // What the allocation of each block reports when it fails (fill: the memsets and the launch that give a fresh block its first values), and
@@ -450,6 +451,7 @@ static const SettingsBlockTexts SETTINGS_BLOCK_TEXTS[SB_COUNT] = {
     {"engine_set_stop: hipMalloc(stop records) failed", "engine_set_stop: memset(stop records) failed", true},
     {nullptr, nullptr, false},  // (the adapter ids: inside lora_mem, lora_alloc)
     {"engine_set_dry: hipMalloc(sequence rows) failed", "engine_set_dry: memset(sequence rows) failed", true},
+    {"engine_set_lookup: hipMalloc(history rows) failed", "engine_set_lookup: memset(history rows) failed", true},
 };
 // the blocks of `needs` that do not exist yet, each from its layout: all-or-nothing per block, filled on the engine stream
 static int settings_blocks(tl_engine *e, unsigned needs) {
@@ -555,6 +557,63 @@ static void launch_dry_record(tl_engine *e, int slot, const int32_t *tokens_dev,
     const int cap = e->settings.sz.dry_seq_cap;
     const DryRecordArgs a{tokens_dev, e->sdev<int32_t>(SB_DRY, e->settings.at.dry_seq) + (size_t)slot * cap, n, start, cap};
     hipLaunchKernelGGL(dry_record_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, e->stream, a);
+}
+
+// ---- prompt lookup (lookup.h): the history row H of an armed slot; the accounting is the settings record's (slot_settings.h) ----
+static int32_t *lookup_row_dev(tl_engine *e, int slot) {
+    return e->sdev<int32_t>(SB_LOOKUP, e->settings.at.lk_seq) + (size_t)slot * e->settings.sz.lookup_seq_cap;
+}
+// ids at `tokens_dev` (uploaded, or the slot's pending token) enter H at positions start ..
+static int lookup_record(tl_engine *e, int slot, const int32_t *tokens_dev, int n, int start) {
+    const LookupRecordArgs a{tokens_dev, lookup_row_dev(e, slot), n, start, e->settings.sz.lookup_seq_cap};
+    hipLaunchKernelGGL(lookup_record_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, e->stream, a);
+    TL_CHECK_LAUNCH("engine lookup recording");
+    return TL_OK;
+}
+// H of an armed slot reaches the slot's context: the ids of the decode steps since the last recording come out of the token ring (the
+// steps themselves record nothing).  No launch where the slot is not armed or not behind
+static int lookup_catch_up(tl_engine *e, int slot) {
+    const Slot &t = e->table.slots[slot];
+    if (!e->settings.lookup_behind(slot, t.ctx)) return TL_OK;
+    TL_TRY(aql_drain(e));  // (steps of the AQL route wrote the ring)
+    const int rec = e->settings.slots[slot].lk_rec;
+    const LookupCatchUpArgs a{lookup_row_dev(e, slot), e->ring + (size_t)slot * e->ring_cap, e->ring_cap, rec, t.ctx, t.produced, e->settings.sz.lookup_seq_cap};
+    hipLaunchKernelGGL(lookup_catch_up_kernel, dim3(std::min(ceil_div(t.ctx - rec, 256), 64)), dim3(256), 0, e->stream, a);
+    TL_CHECK_LAUNCH("engine lookup catch-up");
+    e->settings.lookup_caught_up(slot, t.ctx);
+    return TL_OK;
+}
+// the pending token of an armed slot -- one the ring does not hold: tl_engine_set_token's, a fork's or move's, the one the slot was
+// armed with -- is stored at H[ctx], behind whatever put it into tokens[slot]
+static int lookup_store_pending(tl_engine *e, int slot) {
+    if (!e->settings.lookup_on(slot)) return TL_OK;
+    TL_TRY(lookup_catch_up(e, slot));
+    TL_TRY(lookup_record(e, slot, e->tokens + slot, 1, e->table.slots[slot].ctx));
+    e->settings.lookup_pending(slot, e->table.slots[slot].ctx);
+    return TL_OK;
+}
+// a chunk of n uploaded ids at `tokens_dev` is appended to the slot at position `start` (its context length)
+static int lookup_record_chunk(tl_engine *e, int slot, const int32_t *tokens_dev, int n, int start) {
+    if (!e->settings.lookup_on(slot)) return TL_OK;
+    TL_TRY(lookup_catch_up(e, slot));
+    TL_TRY(lookup_record(e, slot, tokens_dev, n, start));
+    e->settings.lookup_recorded(slot, start, n);
+    return TL_OK;
+}
+// ahead of `steps` decode steps over slots [0, batch): a slot whose unrecorded ids would outrun the ring is caught up first; `restart`
+// takes the slots a single call outruns the ring for (lookup_steps_done starts their history over behind the call)
+static int lookup_before_steps(tl_engine *e, int batch, long steps, std::vector<int> *restart) {
+    for (int b = 0; b < batch; ++b) {
+        if (!e->slot_runs(b) || !e->settings.lookup_on(b)) continue;
+        if (e->settings.lookup_pending_unknown(b, e->table.slots[b].ctx)) TL_TRY(lookup_store_pending(e, b));
+        const SlotSettings::LookupDecode d = e->settings.lookup_before_decode(b, e->table.slots[b].ctx, steps);
+        if (d == SlotSettings::LOOKUP_CATCH_UP) TL_TRY(lookup_catch_up(e, b));
+        if (d == SlotSettings::LOOKUP_RESTART && restart) restart->push_back(b);
+    }
+    return TL_OK;
+}
+static void lookup_steps_done(tl_engine *e, const std::vector<int> &restart) {
+    for (int b : restart) e->settings.lookup_restart(b, e->table.slots[b].ctx);
 }
 
 // the truncation launch over `rows` rows for slots slot0 .. (the rows the choice would be made from -> filtered rows into `out`), and the
@@ -1391,13 +1450,17 @@ extern "C" int tl_engine_release(tl_engine *e, int slot) {
 extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
     TL_TRY(slot_check_unparked(e, slot));
     TL_TRY(table_rc(e->settings.refuses_rewind(slot)));
+    TL_TRY(lookup_catch_up(e, slot));  // (an armed slot's history first reaches the context it is rewound from)
     SlotEdits ed;
     Pokes pk;
+    const int from = e->table.slots[slot].ctx;
     TL_TRY(table_rc(e->table.rewind(slot, n, ed)));
     e->settings.rewound(slot);
+    const bool pending_stored = e->settings.lookup_rewound(slot, from, e->table.slots[slot].ctx);
     TL_TRY(apply_edits(e, ed, pk));  // the copy of a shared tail page before the row entry that publishes the fresh page
     pk.emplace_back(e->context_lens + slot, e->table.slots[slot].ctx);
-    return poke(e, pk);
+    TL_TRY(poke(e, pk));
+    return pending_stored ? lookup_store_pending(e, slot) : (int)TL_OK;
 }
 
 // Fork: slot `dst` becomes a second sequence with the same prefix as `src` (reference KvPrefixGenerator fork / restore on
@@ -1406,6 +1469,7 @@ extern "C" int tl_engine_rewind(tl_engine *e, int slot, int n) {
 extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
     TL_REQUIRE(e, "engine: null engine");
     TL_TRY(stop_reconcile(e));
+    if (!e->table.check(src, true)) TL_TRY(lookup_catch_up(e, src));  // (the ring does not travel: an armed slot's history row is complete first)
     SlotEdits ed;
     Pokes pk;
     TL_TRY(table_rc(e->table.fork(src, dst, ed)));
@@ -1413,7 +1477,8 @@ extern "C" int tl_engine_fork(tl_engine *e, int src, int dst) {
     pk.emplace_back(e->live + dst, e->table.slots[dst].stopped ? 0 : 1);  // (a stopped sequence's copy is stopped: no sequence to a step)
     pk.emplace_back(e->context_lens + dst, e->table.slots[dst].ctx);
     pk.emplace_back(e->produced + dst, 0);
-    return settings_carry(e, src, dst, false, pk);
+    TL_TRY(settings_carry(e, src, dst, false, pk));
+    return lookup_store_pending(e, dst);
 }
 
 // the device table of every K / V (and scale) pool, built once by the first call that needs it (prefix cache, swap space): pool
@@ -1504,6 +1569,13 @@ extern "C" int tl_engine_prefix_attach(tl_engine *e, int slot, const int32_t *to
             TL_CHECK_LAUNCH("engine prompt marking");
         }
     }
+    if (e->settings.lookup_on(slot)) {  // ... and ids of the history of a slot armed for prompt lookup (lookup.h)
+        for (int at = 0; at < got; at += c.max_prefill_rows) {
+            const int len = std::min(c.max_prefill_rows, got - at);
+            TL_HIP(hipMemcpyAsync(e->prefill_tokens, tokens + at, (size_t)len * 4, hipMemcpyHostToDevice, e->stream));
+            TL_TRY(lookup_record_chunk(e, slot, e->prefill_tokens, len, at));
+        }
+    }
     return TL_OK;
 }
 
@@ -1513,6 +1585,7 @@ extern "C" int tl_engine_prefix_attach(tl_engine *e, int slot, const int32_t *to
 extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
     TL_REQUIRE(e, "engine: null engine");
     TL_TRY(stop_reconcile(e));
+    if (!e->table.check(src, true)) TL_TRY(lookup_catch_up(e, src));  // (as in tl_engine_fork)
     SlotEdits ed;
     Pokes pk;
     TL_TRY(table_rc(e->table.move(src, dst, ed)));
@@ -1524,7 +1597,8 @@ extern "C" int tl_engine_move(tl_engine *e, int src, int dst) {
     pk.emplace_back(e->live + dst, d.parked || d.stopped ? 0 : 1);  // (a stopped sequence stays stopped at dst)
     pk.emplace_back(e->live + src, 0);
     pk.emplace_back(e->produced + dst, 0);
-    return settings_carry(e, src, dst, true, pk);
+    TL_TRY(settings_carry(e, src, dst, true, pk));
+    return lookup_store_pending(e, dst);
 }
 
 // ---- beam search (include/tinyllm_engine.h "Beam search"; the selection is beam.h, the group's genealogy slot_table.h) ----------------
@@ -1760,7 +1834,8 @@ extern "C" int tl_engine_set_token(tl_engine *e, int slot, int32_t token) {
     TL_TRY(table_rc(e->settings.refuses_set_token(slot)));
     Pokes pk;
     pk.emplace_back(e->tokens + slot, token);
-    return poke(e, pk);
+    TL_TRY(poke(e, pk));
+    return lookup_store_pending(e, slot);  // (an armed slot: the ring will not hold this token)
 }
 
 extern "C" int tl_engine_set_sampling(tl_engine *e, int slot, float temperature, int top_k, float top_p, uint64_t seed) {
@@ -1854,6 +1929,91 @@ extern "C" int tl_dry_rows(int32_t *sequences_dev, int rows, int cap, const int3
     hipLaunchKernelGGL(dry_match_kernel, dim3(rows), dim3(DRY_MATCH_THREADS), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL(dry_apply_kernel, dim3(ceil_div(vocab, DRY_APPLY_CHUNK), rows), dim3(DRY_APPLY_THREADS), 0, (hipStream_t)stream, a);
     TL_CHECK_LAUNCH("dry_rows");
+    return TL_OK;
+}
+
+// ---- prompt lookup (include/tinyllm_engine.h "Prompt lookup"; the kernels are lookup.h, the accounting slot_settings.h) -------------------
+static int lookup_params_check(const char *who, int max_ngram, int min_ngram, int num_proposals) {
+    const std::string w = std::string(who) + ": ";
+    TL_REQUIRE(max_ngram >= 1 && max_ngram <= LOOKUP_MAX_NGRAM, w + "max_ngram must be 1 .. 16");
+    TL_REQUIRE(min_ngram >= 1 && min_ngram <= max_ngram, w + "min_ngram must be 1 .. max_ngram");
+    TL_REQUIRE(num_proposals >= 1 && num_proposals <= LOOKUP_MAX_PROPOSALS, w + "num_proposals must be 1 .. 7");
+    return TL_OK;
+}
+
+extern "C" int tl_lookup_rows(const int32_t *sequences_dev, int rows, int cap, const int32_t *start_dev, const int32_t *end_dev, int max_ngram, int min_ngram,
+                              int num_proposals, int32_t *proposals_dev, int32_t *counts_dev, int32_t *match_dev, void *stream) {
+    TL_REQUIRE(sequences_dev && start_dev && end_dev && proposals_dev && counts_dev, "lookup_rows: null argument");
+    TL_REQUIRE(rows > 0 && rows <= 65535, "lookup_rows: rows out of range");
+    TL_REQUIRE(cap > 0 && cap <= (1 << LOOKUP_POS_BITS), "lookup_rows: sequence capacity out of range (1 .. 16,777,216)");
+    TL_TRY(lookup_params_check("lookup_rows", max_ngram, min_ngram, num_proposals));
+    LookupArgs a{};
+    a.seq = const_cast<int32_t *>(sequences_dev), a.cap = cap, a.start = start_dev, a.end = end_dev;  // (this launch stores nothing to the rows)
+    a.max_ngram = max_ngram, a.min_ngram = min_ngram, a.k = num_proposals;
+    a.proposals = proposals_dev, a.counts = counts_dev, a.match = match_dev;
+    hipLaunchKernelGGL(lookup_rows_kernel, dim3(rows), dim3(LOOKUP_THREADS), 0, (hipStream_t)stream, a);
+    TL_CHECK_LAUNCH("lookup_rows");
+    return TL_OK;
+}
+
+extern "C" int tl_engine_set_lookup(tl_engine *e, int slot, int on) {
+    TL_TRY(slot_check(e, slot, true));
+    TL_TRY(stop_reconcile(e));  // (the context length of a slot a stop froze in mid-call)
+    const bool was = e->settings.lookup_on(slot);
+    Pokes pk;
+    TL_TRY(settings_set(e, slot, pk, [&](SettingsEdits &ed) { return e->settings.set_lookup(slot, on != 0, e->table.slots[slot].ctx, ed); }));
+    return on && !was ? lookup_store_pending(e, slot) : (int)TL_OK;  // (whatever pending token the slot holds: the ring may not know it)
+}
+
+extern "C" int tl_engine_lookup_state(const tl_engine *e, int slot, int *armed, int *start, int *recorded) {
+    TL_TRY(slot_check(e, slot, false));
+    const SlotSettings::State &s = e->settings.slots[slot];
+    if (armed) *armed = s.lookup ? 1 : 0;
+    if (start) *start = s.lk_s0;
+    if (recorded) *recorded = s.lk_rec;
+    return TL_OK;
+}
+
+extern "C" int tl_engine_lookup_propose(tl_engine *e, int n_seqs, const int *slots, const int *max_lens, int max_ngram, int min_ngram, int num_proposals,
+                                        int32_t *tokens_out, int *lens_out) {
+    TL_REQUIRE(e && slots && tokens_out && lens_out, "engine_lookup_propose: null argument");
+    TL_REQUIRE(n_seqs >= 1 && n_seqs <= LOOKUP_MAX_SLOTS, "engine_lookup_propose: between 1 and 64 sequences per call");
+    TL_TRY(lookup_params_check("engine_lookup_propose", max_ngram, min_ngram, num_proposals));
+    TL_TRY(stop_reconcile(e));
+    LookupSlots rows{};
+    int total = 0;
+    for (int i = 0; i < n_seqs; ++i) {
+        TL_TRY(slot_check_feeds(e, slots[i]));  // what tl_engine_verify_batch refuses: parked, stopped, ...
+        TL_TRY(table_rc(e->settings.refuses_verify_batch(slots[i])));
+        TL_REQUIRE(e->settings.lookup_on(slots[i]), "engine_lookup_propose: a slot is not armed (tl_engine_set_lookup)");
+        for (int j = 0; j < i; ++j) TL_REQUIRE(slots[j] != slots[i], "engine_lookup_propose: a slot appears twice");
+        const int max_len = max_lens ? max_lens[i] : VERIFY_MAX_LEN;
+        TL_REQUIRE(max_len >= 1 && max_len <= VERIFY_MAX_LEN, "engine_lookup_propose: max_lens must be 1 .. 8");
+        total += max_len;
+        const Slot &t = e->table.slots[slots[i]];
+        const SlotSettings::State &s = e->settings.slots[slots[i]];
+        rows.s[i] = {slots[i], s.lk_s0, s.lk_rec, t.ctx, t.produced, std::min(num_proposals, max_len - 1)};
+    }
+    TL_REQUIRE(total <= VERIFY_BATCH_ROWS, "engine_lookup_propose: the chunks together may exceed 64 rows (the sum of max_lens)");
+    TL_TRY(aql_drain(e));  // (steps of the AQL route wrote the ring)
+    int32_t *out = e->sdev<int32_t>(SB_LOOKUP, e->settings.at.lk_out);
+    LookupArgs a{};
+    a.seq = e->sdev<int32_t>(SB_LOOKUP, e->settings.at.lk_seq), a.cap = e->settings.sz.lookup_seq_cap;
+    a.max_ngram = max_ngram, a.min_ngram = min_ngram, a.k = num_proposals;
+    a.proposals = out, a.counts = out + LOOKUP_MAX_SLOTS * LOOKUP_ROW;
+    const LookupRing r{e->ring, e->tokens, e->ring_cap};
+    hipLaunchKernelGGL(lookup_engine_kernel, dim3(n_seqs), dim3(LOOKUP_THREADS), 0, e->stream, a, r, rows);
+    TL_CHECK_LAUNCH("engine_lookup_propose");
+    for (int i = 0; i < n_seqs; ++i) e->settings.lookup_caught_up(slots[i], rows.s[i].ctx);  // (the launch fetched what the ring held)
+    int32_t host[LOOKUP_OUT_WORDS];
+    TL_HIP(hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, e->stream));
+    TL_HIP(hipStreamSynchronize(e->stream));
+    int at = 0;
+    for (int i = 0; i < n_seqs; ++i) {
+        const int n = std::min(std::max(host[LOOKUP_MAX_SLOTS * LOOKUP_ROW + i], 0), rows.s[i].k);
+        lens_out[i] = 1 + n;
+        for (int j = 0; j <= n; ++j) tokens_out[at++] = host[i * LOOKUP_ROW + j];
+    }
     return TL_OK;
 }
 
@@ -2505,6 +2665,8 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
         launch_dry_record(e, seqs[i].slot, e->prefill_tokens + seqs[i].row0, seqs[i].len, seqs[i].start);
         TL_CHECK_LAUNCH("engine sequence recording");
     }
+    for (int i = 0; i < n_seqs; ++i)  // ... and the history row of a slot armed for prompt lookup (lookup.h)
+        TL_TRY(lookup_record_chunk(e, seqs[i].slot, e->prefill_tokens + seqs[i].row0, seqs[i].len, seqs[i].start));
     for (int i = 0; i < n_seqs; ++i) {  // the chunk's tokens enter the history of a slot that processes its logits (logit_process.h)
         if (!step_processes_slot(e, seqs[i].slot)) continue;
         const LogitMarkArgs mk{e->prefill_tokens + seqs[i].row0, seqs[i].len, c.vocab_size, e->sdev<uint32_t>(SB_PROCESS, e->settings.at.pen_history), (long)seqs[i].slot * c.vocab_size};
@@ -3007,6 +3169,8 @@ static int verify_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const i
         max_len = std::max(max_len, s.len), max_ctx = std::max(max_ctx, s.start + s.len);
     }
     TL_HIP(hipMemcpyAsync(v.desc, desc, sizeof(desc), hipMemcpyHostToDevice, e->stream));
+    for (int i = 0; i < n_seqs; ++i)  // the chunks enter the history rows of slots armed for prompt lookup (lookup.h)
+        TL_TRY(lookup_record_chunk(e, seqs[i].slot, v.arr(V::TOKENS) + seqs[i].row0, seqs[i].len, seqs[i].start));
     const VerifySplit sp = verify_pick_splits(n_seqs, c.num_heads, c.num_kv_heads, total, max_len, max_ctx, v.attn_ws_rows);
 
     TL_TRY(tl_quantized_embedding(v.arr(V::TOKENS), 0, e->embed.scales_dev, e->embed.biases_dev, e->embed.weight_dev, b.x_out, total, c.hidden_size,
@@ -3194,6 +3358,7 @@ static void step_done(tl_engine *e, int batch, const StepFeatures &f) {
 // advances exactly like tl_engine_decode(e, batch, 1, 0)
 static int one_eager_step(tl_engine *e, int batch, const StepFeatures &f, ProfCtx *pc, AttnPlan *sp) {
     ReplayCall call;  // (stays on the stream)
+    TL_TRY(lookup_before_steps(e, batch, 1, nullptr));
     TL_TRY(prepare_step(e, batch, sp, call));
     TL_TRY(eager_step(e, batch, *sp, f, pc));
     step_done(e, batch, f);
@@ -3233,6 +3398,13 @@ extern "C" int tl_engine_decode(tl_engine *e, int batch, int steps, int use_grap
     TL_TRY(step_call_begin(e, batch, "engine_decode"));
     TL_REQUIRE(steps >= 0, "engine_decode: steps must be nonnegative");
     if (steps == 0) return TL_OK;
+    std::vector<int> lookup_restart;  // (allocates nothing while no armed slot outruns the ring)
+    struct LookupRestartEnd {  // however the call returns, behind the reconciliation at its end
+        tl_engine *e;
+        const std::vector<int> &slots;
+        ~LookupRestartEnd() { lookup_steps_done(e, slots); }
+    } const lookup_end{e, lookup_restart};
+    TL_TRY(lookup_before_steps(e, batch, steps, &lookup_restart));
     StepFeatures f;
     TL_TRY(step_inputs(e, batch, &f));
     ReplayCall call;

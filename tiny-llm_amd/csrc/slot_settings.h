@@ -23,7 +23,7 @@
 
 namespace tl {
 
-enum SettingsBlock { SB_SAMPLE, SB_LOGPROB, SB_PROCESS, SB_GRAMMAR, SB_STACK, SB_TRUNC, SB_STOP, SB_LORA, SB_DRY, SB_COUNT };
+enum SettingsBlock { SB_SAMPLE, SB_LOGPROB, SB_PROCESS, SB_GRAMMAR, SB_STACK, SB_TRUNC, SB_STOP, SB_LORA, SB_DRY, SB_LOOKUP, SB_COUNT };
 
 // temperature 0 = greedy (the default, and what begin / release restore)
 struct SampleParams {
@@ -129,6 +129,8 @@ class SlotSettings {
         int dry_seq_cap = 0;       // ids a slot's sequence row holds (max_pages_per_seq * page_size); 0: no DRY / n-gram ban on this engine
         int dry_max_breakers = 0;  // dry.h
         int dry_max_match = 0;
+        int lookup_seq_cap = 0;   // ids a slot's lookup history row holds (max_pages_per_seq * page_size); 0: no prompt lookup on this engine
+        int lookup_out_words = 0;  // lookup.h: the words one propose launch leaves for the host
     };
     struct State {
         SampleParams smp;
@@ -141,6 +143,10 @@ class SlotSettings {
         bool gr_pending = false;  // the slot holds a pending token no step has consumed yet
         bool parked = false;
         int emb_rows = -1;  // rows the slot's running mean holds (pool.h), -1: none
+        // prompt lookup (lookup.h): the slot keeps its ordered ids H on the device.  H[j] is known for lk_s0 <= j < lk_rec; the ids of the
+        // decode steps since (positions lk_rec .. ctx - 1) still lie in the token ring and are fetched by a catch-up
+        bool lookup = false;
+        int lk_s0 = 0, lk_rec = 0;
     };
     // byte offsets of every array inside its block, [slots] entries each unless said otherwise
     struct Offsets {
@@ -151,6 +157,7 @@ class SlotSettings {
         size_t trn_rows, trn_minp, trn_tau, trn_eta, trn_logsum, trn_typ, trn_mu;  // [max(slots, 8), vocab]; logsum [max(slots, 8)]
         size_t stop_sets, stop_armed, stop_max_new, stop_automaton, stop_rec;
         size_t dry_seq, dry_table, dry_mult, dry_base, dry_allowed, dry_range, dry_ngram, dry_s0, dry_nbreak, dry_breakers;  // [slots, dry_seq_cap]; [slots, vocab]; ...; [slots, dry_max_breakers]
+        size_t lk_seq, lk_out;  // [slots, lookup_seq_cap]; [lookup_out_words]
     };
     std::vector<State> slots;
     Offsets at{};
@@ -198,6 +205,10 @@ class SlotSettings {
         at.dry_ngram = carve(off, B * 4), at.dry_s0 = carve(off, B * 4), at.dry_nbreak = carve(off, B * 4);
         at.dry_breakers = carve(off, B * (size_t)sz.dry_max_breakers * 4);
         layouts_[SB_DRY] = {sz.dry_seq_cap ? off : 0, {{at.dry_table, off - at.dry_table, 0}}};
+        // prompt lookup: the history rows and the results of one propose launch, all written before they are read
+        off = 0;
+        at.lk_seq = carve(off, B * (size_t)sz.lookup_seq_cap * 4), at.lk_out = carve(off, (size_t)sz.lookup_out_words * 4);
+        layouts_[SB_LOOKUP] = {sz.lookup_seq_cap ? off : 0, {}};
     }
     const BlockLayout &layout(int b) const { return layouts_[b]; }
     bool exists(int b) const { return exists_ >> b & 1u; }
@@ -298,6 +309,63 @@ class SlotSettings {
         pen_write(slot, v, ed);
         return nullptr;
     }
+    // ---- prompt lookup (lookup.h): the host half of the history's accounting ---------------------------------------------------------
+    // ctx: the slot's context length.  Arming an armed slot changes nothing; arming makes s0 = ctx and the caller records the pending
+    // token at H[ctx] (lookup_pending).  Switching off forgets the history
+    const char *set_lookup(int slot, bool on, int ctx, SettingsEdits &ed) {
+        State &s = slots[slot];
+        if (!on) {
+            s.lookup = false, s.lk_s0 = s.lk_rec = 0;
+            return nullptr;
+        }
+        if (sz.lookup_seq_cap <= 0) return "engine_set_lookup: this engine holds no history rows";
+        if (sz.lookup_seq_cap > (1 << 24)) return "engine_set_lookup: sequences longer than 16,777,216 tokens (the match key holds 24 bits of position)";
+        ed.needs |= 1u << SB_LOOKUP;
+        if (!s.lookup) s.lookup = true, s.lk_s0 = s.lk_rec = ctx;
+        return nullptr;
+    }
+    bool lookup_on(int slot) const { return slots[slot].lookup; }
+    // is H short of the context?  (then the ids of positions lk_rec .. ctx - 1 are the ring's: the caller launches the catch-up)
+    bool lookup_behind(int slot, int ctx) const { return slots[slot].lookup && slots[slot].lk_rec < ctx; }
+    // the catch-up for context length ctx is on the stream
+    void lookup_caught_up(int slot, int ctx) {
+        if (slots[slot].lookup) slots[slot].lk_rec = std::max(slots[slot].lk_rec, ctx);
+    }
+    // ids for positions start .. start + n - 1 were recorded from an upload (the slot was caught up to `start` first)
+    void lookup_recorded(int slot, int start, int n) {
+        if (slots[slot].lookup) slots[slot].lk_rec = start + n;
+    }
+    // the pending token was stored at H[ctx] (arming, set_token, a fork's or move's destination): the ring does not hold it
+    void lookup_pending(int slot, int ctx) {
+        if (slots[slot].lookup) slots[slot].lk_rec = ctx + 1;
+    }
+    // the slot was rewound from context length `from` to ctx (behind a catch-up): what lay behind ctx is forgotten.  True: the pending
+    // token had been stored at H[from] -- the ring may not hold it -- and the caller stores it again, at H[ctx]
+    bool lookup_rewound(int slot, int from, int ctx) {
+        State &s = slots[slot];
+        if (!s.lookup) return false;
+        const bool stored = s.lk_rec == from + 1;
+        s.lk_s0 = std::min(s.lk_s0, ctx), s.lk_rec = std::min(s.lk_rec, ctx);
+        return stored;
+    }
+    // does a step feed the slot a token the ring does not hold and H does not either?  (a prefill without a first token leaves whatever
+    // tokens[slot] held: the caller stores it at H[ctx] ahead of the step, as tl_engine_set_token would have)
+    bool lookup_pending_unknown(int slot, int ctx) const { return slots[slot].lookup && slots[slot].lk_rec <= ctx && !slots[slot].gr_pending; }
+    // A decode call of `steps` steps is about to run on the slot at context length ctx.  The ring holds ring_cap ids, the last of them
+    // the pending token: a catch-up reaches back ring_cap - 1 positions
+    enum LookupDecode { LOOKUP_KEEP, LOOKUP_CATCH_UP, LOOKUP_RESTART };
+    LookupDecode lookup_before_decode(int slot, int ctx, long steps) const {
+        const State &s = slots[slot];
+        if (!s.lookup) return LOOKUP_KEEP;
+        if (steps > sz.ring_cap - 1) return LOOKUP_RESTART;  // the call alone outruns the ring: the history starts over behind it
+        const int behind = std::max(ctx - s.lk_rec, 0);
+        return behind + steps > sz.ring_cap - 1 ? LOOKUP_CATCH_UP : LOOKUP_KEEP;
+    }
+    // ... after such a call: the history is empty at the context length the call left
+    void lookup_restart(int slot, int ctx) {
+        if (slots[slot].lookup) slots[slot].lk_s0 = slots[slot].lk_rec = ctx;
+    }
+
     // (the caller has checked the grammar's vocabulary)  The same automaton again: back to its start state
     const char *set_grammar(int slot, const GrammarRef &g, SettingsEdits &ed) {
         PenaltyParams v = slots[slot].pen;
@@ -336,6 +404,7 @@ class SlotSettings {
     void reset(int slot, SettingsEdits &ed) {
         State &s = slots[slot];
         s.gr_pending = false, s.parked = false, s.emb_rows = -1;
+        s.lookup = false, s.lk_s0 = s.lk_rec = 0;
         lp_write(slot, -1, 0, ed);
         if (s.pen.processes()) pen_write(slot, PenaltyParams{}, ed);
         trn_reset(slot, ed);
@@ -396,6 +465,12 @@ class SlotSettings {
         }
         lora_write(dst, s.lora, ed);
         if (move) lora_write(src, sz.lora_none, ed);
+        if (s.lookup) {  // the history row travels (the caller caught src up first and records dst's pending token behind this)
+            const size_t row = (size_t)sz.lookup_seq_cap * 4;
+            ed.list.push_back({SettingsEdit::COPY, SB_LOOKUP, at.lk_seq + dst * row, 0, at.lk_seq + src * row, row, nullptr});
+        }
+        d.lookup = s.lookup, d.lk_s0 = s.lk_s0, d.lk_rec = s.lk_rec;
+        if (move) s.lookup = false, s.lk_s0 = s.lk_rec = 0;
     }
     // park / unpark, after the table's.  The processing launch of a step reads a row's parameters whatever the row's `live` word says,
     // and a row that processes counts its pending token and advances its grammar record: a parked slot keeps its pending token, so its
@@ -467,6 +542,7 @@ class SlotSettings {
         if (slots[slot].trn.truncates()) return "engine_beam: the slot truncates";
         if (slots[slot].lp_n >= 0) return "engine_beam: the slot records log-probabilities";
         if (slots[slot].stop.armed) return "engine_beam: the slot is armed with a stop set";
+        if (slots[slot].lookup) return "engine_beam: the slot is armed for prompt lookup (its history row does not follow a reorder)";
         return nullptr;
     }
     // Does the slot, taking part in a step, process its logits?  (runs: what the table says of the slot)

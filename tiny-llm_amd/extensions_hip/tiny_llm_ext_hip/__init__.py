@@ -126,6 +126,8 @@ TL_MAX_TOP_LOGPROBS = 20
 TL_MAX_LOGIT_BIAS = 1024  # entries of a slot's logit-bias list (include/tinyllm_engine.h)
 TL_DRY_MAX_MATCH = 64     # the longest match DRY and the n-gram ban look at
 TL_MAX_DRY_BREAKERS = 64  # entries of a slot's DRY breaker list
+TL_LOOKUP_MAX_NGRAM = 16     # the longest match prompt lookup looks for
+TL_LOOKUP_MAX_PROPOSALS = 7  # proposals per slot (a verification chunk holds the pending token and up to 7 more)
 
 
 class TlTokenLogprob(ctypes.Structure):
@@ -283,6 +285,11 @@ _SIGNATURES.update({
                                  [_c_float, _c_float, _c_void_p, _P(TlAttentionInfo)]),
     "tl_verify_accept_rows": (_c_int, [_c_void_p, _c_int, _c_int, _P(ctypes.c_int), _P(ctypes.c_int), _c_void_p, _c_void_p, _c_void_p]),
     "tl_engine_set_token": (_c_int, [_c_void_p, _c_int, ctypes.c_int32]),
+    "tl_engine_set_lookup": (_c_int, [_c_void_p, _c_int, _c_int]),
+    "tl_engine_lookup_propose": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int), _P(ctypes.c_int), _c_int, _c_int, _c_int, _P(ctypes.c_int32),
+                                          _P(ctypes.c_int)]),
+    "tl_engine_lookup_state": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int)]),
+    "tl_lookup_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "tl_engine_set_sampling": (_c_int, [_c_void_p, _c_int, _c_float, _c_int, _c_float, ctypes.c_uint64]),
     "tl_sample_logits": (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 7),
     "tl_engine_set_logprobs": (_c_int, [_c_void_p, _c_int, _c_int]),
@@ -1414,6 +1421,53 @@ def dry_rows(logits: torch.Tensor, sequences: torch.Tensor, start, end, multipli
     check(_lib.tl_dry_rows(sequences.data_ptr(), rows, cap, start_t.data_ptr(), end_t.data_ptr(), m_t.data_ptr(), b_t.data_ptr(), a_t.data_ptr(),
                            r_t.data_ptr(), n_t.data_ptr(), brk_t.data_ptr(), nb_t.data_ptr(), table.data_ptr(), out.data_ptr(), vocab, _stream()))
     return out
+
+
+def lookup_params(max_ngram: int, min_ngram: int, num_proposals: int) -> tuple[int, int, int]:
+    """Validated (max_ngram, min_ngram, num_proposals) of the prompt-lookup rule: max_ngram 1 .. 16, min_ngram 1 .. max_ngram,
+    num_proposals 1 .. 7."""
+    for name, v in (("max_ngram", max_ngram), ("min_ngram", min_ngram), ("num_proposals", num_proposals)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} must be an int, got {v!r}")
+    if not 1 <= max_ngram <= TL_LOOKUP_MAX_NGRAM:
+        raise ValueError(f"max_ngram must be 1 .. {TL_LOOKUP_MAX_NGRAM}, got {max_ngram!r}")
+    if not 1 <= min_ngram <= max_ngram:
+        raise ValueError(f"min_ngram must be 1 .. max_ngram, got {min_ngram!r}")
+    if not 1 <= num_proposals <= TL_LOOKUP_MAX_PROPOSALS:
+        raise ValueError(f"num_proposals must be 1 .. {TL_LOOKUP_MAX_PROPOSALS}, got {num_proposals!r}")
+    return max_ngram, min_ngram, num_proposals
+
+
+def lookup_rows(sequences: torch.Tensor, start, end, max_ngram: int = 3, min_ngram: int = 1, num_proposals: int = 4, want_match: bool = False):
+    """The decode engine's prompt-lookup rule (tl_lookup_rows) over rows of ids: ``sequences`` [rows, cap] int32 on the GPU, row r holding
+    T[start[r] .. end[r]] (``start`` / ``end``: a scalar or one value per row; a row with end < start has no proposals).  Returns
+    (proposals [rows, 8] int32 with -1 behind each row's proposals, counts [rows] int32) and, with ``want_match``, also match [rows, 2]:
+    the chosen position and its match length, (-1, 0) without a choice."""
+    if not isinstance(sequences, torch.Tensor) or sequences.dtype != torch.int32 or sequences.dim() != 2 or not sequences.is_cuda:
+        raise ValueError("lookup_rows takes a [rows, cap] int32 tensor on the GPU")
+    lookup_params(max_ngram, min_ngram, num_proposals)
+    rows, cap, dev = sequences.shape[0], sequences.shape[1], sequences.device
+    if rows < 1 or cap < 1:
+        raise ValueError("lookup_rows needs at least one row and one id per row")
+    sequences = sequences.contiguous()
+
+    def per_row(v, what):
+        t = torch.as_tensor(v, dtype=torch.int32).reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(rows)
+        if t.numel() != rows:
+            raise ValueError(f"{what} needs one value per row")
+        return t.contiguous().to(dev)
+
+    start_t, end_t = per_row(start, "start"), per_row(end, "end")
+    if int(end_t.max()) >= cap:
+        raise ValueError("end must lie inside the sequence capacity")
+    proposals = torch.empty((rows, 8), dtype=torch.int32, device=dev)
+    counts = torch.empty(rows, dtype=torch.int32, device=dev)
+    match = torch.empty((rows, 2), dtype=torch.int32, device=dev) if want_match else None
+    check(_lib.tl_lookup_rows(sequences.data_ptr(), rows, cap, start_t.data_ptr(), end_t.data_ptr(), max_ngram, min_ngram, num_proposals,
+                              proposals.data_ptr(), counts.data_ptr(), match.data_ptr() if want_match else None, _stream()))
+    return (proposals, counts, match) if want_match else (proposals, counts)
 
 
 def _rows_f32(v, rows: int, dev, what: str) -> torch.Tensor:

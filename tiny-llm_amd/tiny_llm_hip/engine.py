@@ -367,6 +367,49 @@ class DecodeEngine:
     def set_token(self, slot: int, token: int) -> None:
         _ext.check(_lib.tl_engine_set_token(self._h, slot, int(token)))
 
+    def set_lookup(self, slot: int, on: bool = True) -> None:
+        """Arm (or disarm) a live slot for prompt lookup (tl_engine_set_lookup): from now on the engine keeps the slot's ordered ids
+        resident on the device, so that ``lookup_propose`` can propose continuations without the host seeing an id.  Ids the slot held
+        before the call are unknown and never matched: arm right after ``begin``.  Decode steps are unchanged.  begin / release switch
+        it off, move carries the history along, fork copies it, park / unpark keep it."""
+        _ext.check(_lib.tl_engine_set_lookup(self._h, slot, int(bool(on))))
+
+    def lookup_state(self, slot: int) -> tuple[bool, int, int]:
+        """(armed, the position the slot's history starts at, the position it is recorded up to) of tl_engine_lookup_state."""
+        a, s, r = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _ext.check(_lib.tl_engine_lookup_state(self._h, slot, ctypes.byref(a), ctypes.byref(s), ctypes.byref(r)))
+        return bool(a.value), s.value, r.value
+
+    def lookup_propose(self, slots: Sequence[int], max_lens: Sequence[int] | None = None, max_ngram: int = 3, min_ngram: int = 1,
+                       num_proposals: int = 4) -> list[list[int]]:
+        """Prompt-lookup proposals for several armed slots in one launch (tl_engine_lookup_propose): per slot the chunk
+        ``verify_batch`` takes -- the pending token followed by the ids that followed the longest earlier occurrence of the slot's last
+        1 .. ``max_ngram`` ids (at least ``min_ngram``), at most ``num_proposals`` and at most ``max_lens[i] - 1`` of them; the pending
+        token alone where nothing matches.  Synchronises once."""
+        slots = [int(s) for s in slots]
+        if not 1 <= len(slots) <= 64:
+            raise ValueError("lookup_propose takes between 1 and 64 slots")
+        _ext.lookup_params(max_ngram, min_ngram, num_proposals)
+        n = len(slots)
+        lens_in = None
+        if max_lens is not None:
+            max_lens = [int(m) for m in max_lens]
+            if len(max_lens) != n or any(not 1 <= m <= 8 for m in max_lens):
+                raise ValueError("max_lens needs one value in 1 .. 8 per slot")
+            if sum(max_lens) > 64:
+                raise ValueError("the chunks together may hold at most 64 tokens")
+            lens_in = (ctypes.c_int * n)(*max_lens)
+        elif 8 * n > 64:
+            raise ValueError("more than 8 slots need max_lens (the chunks together may hold at most 64 tokens)")
+        tokens = (ctypes.c_int32 * 64)()
+        lens = (ctypes.c_int * n)()
+        _ext.check(_lib.tl_engine_lookup_propose(self._h, n, (ctypes.c_int * n)(*slots), lens_in, max_ngram, min_ngram, num_proposals, tokens, lens))
+        out, at = [], 0
+        for i in range(n):
+            out.append(list(tokens[at:at + lens[i]]))
+            at += lens[i]
+        return out
+
     def set_sampling(self, slot: int, temperature: float = 0.0, top_k: int | None = None, top_p: float | None = None,
                      seed: int = 0) -> None:
         """Per-slot sampling on the device (tl_engine_set_sampling): every token the live slot produces from now on is drawn under
@@ -1229,6 +1272,100 @@ def batch_speculative_generate_ids(target, draft, prompts: Sequence[Sequence[int
                         draft.rewind(s, back)
         finally:
             for s in sorted(held_t | drafted):
+                finish(s)
+    if stats is not None:
+        stats.update(counts)
+    return [o[:n] for o, n in zip(outs, limits)]
+
+
+def lookup_generate_ids(engine, prompts: Sequence[Sequence[int]], max_new_tokens: int | Sequence[int], proposal_length: int = 4, max_ngram: int = 3,
+                        min_ngram: int = 1, eos_token_id: int | None = None, *, stats: dict | None = None) -> list[list[int]]:
+    """Greedy speculative decoding without a draft model: ``batch_speculative_generate_ids``' loop with prompt lookup as the proposer
+    (``DecodeEngine.lookup_propose``: the ids that followed the longest earlier occurrence of a sequence's last 1 .. ``max_ngram`` ids).
+    Prompts run in waves of at most ``min(engine.max_batch, 64 // (proposal_length + 1))`` slots, prompt i of a wave on slot i, each
+    armed before its prefill so that the prompt is part of what is matched.  Per round ONE ``lookup_propose`` over the live slots (each
+    clipped to the ids it may still emit); where any slot got a proposal, one ``verify_batch(..., commit=True)`` over all live slots --
+    a slot without a proposal goes in with its pending token alone -- and where none did, one captured ``decode(1, batch)`` step whose
+    ids are read back.  A sequence that finishes is released and drops out of later rounds; the last id it may emit is its pending
+    token, which costs no pass.
+    Returns, per prompt, the engine's greedy continuation (up to ``max_new_tokens`` ids -- one number, or one per prompt -- stopping
+    before ``eos_token_id``).  ``stats`` receives ``rounds`` (verify_batch calls), ``steps`` (decode steps), ``proposed`` and
+    ``accepted``."""
+    if not isinstance(proposal_length, int) or isinstance(proposal_length, bool) or not 1 <= proposal_length <= 7:
+        raise ValueError("proposal_length must be an integer in [1, 7] (8 verification rows per slot)")
+    _ext.lookup_params(max_ngram, min_ngram, proposal_length)
+    prompts = [[int(t) for t in p] for p in prompts]
+    if any(not p for p in prompts):
+        raise ValueError("every prompt must hold at least one token")
+    limits = [max_new_tokens] * len(prompts) if isinstance(max_new_tokens, int) else list(max_new_tokens)
+    if len(limits) != len(prompts) or any(not isinstance(n, int) or isinstance(n, bool) or n < 0 for n in limits):
+        raise ValueError("max_new_tokens must be a non-negative integer, or one per prompt")
+    wave = min(int(engine.max_batch), 64 // (proposal_length + 1))
+    if wave < 1:
+        raise ValueError("the engine holds no slot")
+    counts = {"rounds": 0, "steps": 0, "proposed": 0, "accepted": 0}
+    outs: list[list[int]] = [[] for _ in prompts]
+    for first in range(0, len(prompts), wave):
+        group = prompts[first:first + wave]
+        token: dict[int, int] = {}  # live slots: the pending token (predicted, not yet emitted or cached)
+        held: set[int] = set()
+
+        def finish(s: int) -> None:
+            token.pop(s, None)
+            if s in held:
+                held.discard(s)
+                engine.release(s)
+
+        def settle(s: int) -> None:
+            """The sequence ends where its pending token is the EOS or the last id it may emit (no pass is spent on that one)."""
+            if token[s] != eos_token_id and len(outs[first + s]) == limits[first + s] - 1:
+                outs[first + s].append(token[s])
+            if len(outs[first + s]) >= limits[first + s] or token[s] == eos_token_id:
+                finish(s)
+
+        try:
+            for s, prompt in enumerate(group):
+                if limits[first + s] == 0:
+                    continue
+                engine.begin(s)
+                held.add(s)
+                engine.set_lookup(s)
+                engine.prefill(s, prompt)
+                token[s] = engine.read_tokens(s, 1)[0]
+            for s in list(token):
+                settle(s)
+            while token:
+                live = sorted(token)
+                room = {s: limits[first + s] - len(outs[first + s]) - 1 for s in live}  # proposals that could still be emitted after the pending token
+                fed = dict(zip(live, engine.lookup_propose(live, [1 + min(proposal_length, room[s]) for s in live], max_ngram, min_ngram, proposal_length)))
+                for s in live:  # nothing is proposed behind an EOS
+                    if eos_token_id in fed[s][1:]:
+                        fed[s] = fed[s][:fed[s].index(eos_token_id, 1) + 1]
+                if all(len(fed[s]) == 1 for s in live):
+                    engine.decode(1, batch=live[-1] + 1)
+                    counts["steps"] += 1
+                    for s in live:
+                        outs[first + s].append(token[s])
+                        token[s] = engine.read_tokens(s, 1)[0]
+                        settle(s)
+                    continue
+                results = engine.verify_batch([(s, fed[s]) for s in live], commit=True)
+                counts["rounds"] += 1
+                for s, r in zip(live, results):
+                    a = len(r) - 1
+                    counts["proposed"] += len(fed[s]) - 1
+                    stop = next((i for i in range(1, a + 1) if fed[s][i] == eos_token_id), None)
+                    if stop is not None:  # fed[:a + 1] is what the engine itself would have fed: emitted, unless an accepted proposal is the EOS
+                        outs[first + s].extend(fed[s][:stop])
+                        counts["accepted"] += stop - 1
+                        finish(s)
+                        continue
+                    outs[first + s].extend(fed[s][:a + 1])
+                    counts["accepted"] += a
+                    token[s] = r[a]
+                    settle(s)
+        finally:
+            for s in sorted(held):
                 finish(s)
     if stats is not None:
         stats.update(counts)
