@@ -345,8 +345,8 @@ int tl_engine_verify_sampled(tl_engine *e, int slot, const int32_t *tokens, int 
  * copy of a tail page a rewind may need) ask of the pool, token range -- is made before anything is reserved or written.  Refuses
  * (TL_ERR_INVALID) what tl_engine_verify refuses -- parked or stopped slots, slots that sample, slots that process their logits -- a
  * slot that carries a LoRA adapter, head_dim != 128, and a model with MoE layers when the rows exceed max(max_batch, max_prefill_rows).
- * FP8 KV pages and MoE layers are supported.  Out of scope: speculative SAMPLING in batch (a follow-up can run tl_spec_sample_rows over
- * the same rows), adapters, and captured or AQL replay of the pass.  The scratch (activations, logits and matmul workspace for 64 rows,
+ * FP8 KV pages and MoE layers are supported.  Out of scope: adapters, and captured or AQL replay of the pass; slots that sample are
+ * verified in batch by tl_engine_verify_batch_sampled below.  The scratch (activations, logits and matmul workspace for 64 rows,
  * descriptors, results) is allocated by the first call and counted in stats.workspace_bytes.  Synchronises once. */
 typedef struct tl_verify_result {
     int32_t count;
@@ -354,6 +354,42 @@ typedef struct tl_verify_result {
 } tl_verify_result;
 int tl_engine_verify_batch(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, int commit,
                            tl_verify_result *out);
+
+/* Batched speculative SAMPLING (csrc/verify_sample.h): tl_engine_verify_batch for slots that sample.  The same
+ * checks, the same all-or-nothing behaviour, the same pass over the same scratch and the same `commit` handling; only the acceptance
+ * launches and what is refused of a slot differ.  Greedy and sampling slots may share a call.
+ *   rows       sequence i owns rows row0[i] .. row0[i] + lens[i] - 1 of the pass (the chunks back to back); its context length before
+ *              the call is starts[i].  For row r = row0[i] + j: the proposal is x = tokens[r + 1] for j < lens[i] - 1 and -1, a bonus
+ *              row, on the last row; the position is starts[i] + j + 1 (the sampler's own position rule, tl_engine_verify_sampled's);
+ *              the target parameters are the slot's own (temperature, top_k, top_p, seed), read on the device where
+ *              tl_engine_set_sampling keeps them -- no per-call record is uploaded.
+ *   weights    kept set, weights wp and Wp = sum wp (fp32), one-hot rows and the uniforms u_acc (third counter word 0x53504143) and
+ *              u_res (0x53505253) are exactly tl_spec_sample_rows'; a bonus row gives tl_sample_logits' own draw, bit for bit.
+ *   drafted    draft_logits_dev != NULL: row r of draft_logits_dev [R, V] bf16 is the row tokens[r + 1] was drawn from; one
+ *              (draft_temperature, draft_top_k, draft_top_p) holds for the whole call; the draft row at a bonus position is never read.
+ *              accept and alt of a row are tl_spec_sample_rows', unchanged.
+ *   point      draft_logits_dev == NULL: the proposal is a deterministic function of the sequence (prompt lookup), so its draft
+ *              distribution is one-hot at x.  Accepted iff u_acc Wp < wp_x (one fp32 product).  Rejected: r_j = wp_j for j != x, r_x = 0,
+ *              alt = the first id whose inclusive cumulative r exceeds u_res R, with tl_spec_sample_rows' fallbacks where rounding
+ *              leaves no crossing.  x >= V is rejected without a read at x and the residual is wp whole.  By construction this is what
+ *              tl_spec_sample_rows returns for a draft row whose first maximum is x under draft temperature 0 (wq = Wq = 1) -- without
+ *              the draft row: the target row alone is read.
+ *   result     a = the first j < lens[i] - 1 whose row rejects (lens[i] - 1 when none does): out[i].count = a + 1, ids[0 .. a) the
+ *              accepted proposals tokens[row0 + 1 .. row0 + a], ids[a] row a's alt (the residual draw, or the bonus row's ordinary
+ *              draw), the rest -1 -- distributed exactly as the slot's own samples, whatever was proposed.  A greedy slot (temperature
+ *              0) has a one-hot target row: its result is exactly tl_engine_verify_batch's.
+ * Refuses what tl_engine_verify_batch refuses except sampling -- parked or stopped slots, a slot twice, slots that process their logits,
+ * adapter slots, head_dim != 128, the MoE row limit -- and a slot that truncates (min-p, typical-p, Mirostat); needs V <= 524,288 and a
+ * finite draft_temperature >= 0.  Out of scope: a sampled draft-model loop on top of the drafted path, verification of processing or
+ * truncating slots, adapters, captured replay of the pass.  accept / alt of 64 rows are allocated by the first call (workspace_bytes).
+ * Synchronises once.
+ * tl_engine_copy_verify_logits: rows [row0, row0 + rows) of the last batched verification's own logits block (either call) to dst_dev
+ * [rows, V] bf16, device to device, stream ordered: the very rows its acceptance stage read.  TL_ERR_INVALID before the first pass or
+ * when the range lies outside the rows of the last pass. */
+int tl_engine_verify_batch_sampled(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens,
+                                   const void *draft_logits_dev, float draft_temperature, int draft_top_k, float draft_top_p, int commit,
+                                   tl_verify_result *out);
+int tl_engine_copy_verify_logits(tl_engine *e, int row0, int rows, void *dst_dev);
 
 /* Prompt lookup: draft-free proposals for tl_engine_verify_batch, made on the device (csrc/lookup.h).  The
  * proposer -- "ngram" speculation, prompt_lookup_num_tokens -- finds the last few ids of a sequence earlier in the sequence and proposes
@@ -391,6 +427,10 @@ int tl_engine_set_lookup(tl_engine *e, int slot, int on);
 int tl_engine_lookup_propose(tl_engine *e, int n_seqs, const int *slots, const int *max_lens, int max_ngram, int min_ngram, int num_proposals,
                              int32_t *tokens_out, int *lens_out);
 int tl_engine_lookup_state(const tl_engine *e, int slot, int *armed, int *start, int *recorded);
+/* tl_engine_lookup_propose for the slots of tl_engine_verify_batch_sampled: the same arguments, results and proposer launch; it refuses
+ * of a slot what that call refuses (so a sampling slot is taken, a truncating one is not) in place of what tl_engine_verify_batch refuses. */
+int tl_engine_lookup_propose_sampled(tl_engine *e, int n_seqs, const int *slots, const int *max_lens, int max_ngram, int min_ngram,
+                                     int num_proposals, int32_t *tokens_out, int *lens_out);
 
 /* Set the pending input token of a slot explicitly (e.g. sampled on the host). */
 int tl_engine_set_token(tl_engine *e, int slot, int32_t token);
@@ -1212,6 +1252,17 @@ int tl_verify_attention_rows(const void *qkv_dev, const void *q_norm_dev, const 
  * defines them.  Stream ordered (returns after the stream has run it); bad input is TL_ERR_INVALID. */
 int tl_verify_accept_rows(const void *logits_dev, int vocab, int n_seqs, const int *row0, const int *lens, const int32_t *tokens_dev,
                           tl_verify_result *out_dev, void *stream);
+/* The acceptance stage of tl_engine_verify_batch_sampled over caller rows (csrc/verify_sample.h): target_logits_dev [R, vocab] bf16
+ * (vocab <= 524,288); draft_logits_dev [R, vocab] (drafted proposals) or NULL (point proposals); sequence i (host arrays) owns the rows
+ * [row0[i], row0[i] + lens[i]) and held starts[i] tokens before them; tokens_dev [R] int32 the tokens the rows were fed; the target's
+ * temperature_dev / top_k_dev / top_p_dev / seed_dev hold one value per SEQUENCE, at i; one draft triple for the call.  -> out_dev
+ * [n_seqs] as tl_engine_verify_batch_sampled defines them and, where not NULL, accept_dev / alt_dev [R] int32: every row's own decision
+ * (alt -1 where accepted; a row no sequence owns: 0, -1).  Sequences are checked as tl_verify_accept_rows checks them.  Stream ordered
+ * (returns after the stream has run it); bad input is TL_ERR_INVALID. */
+int tl_verify_sample_rows(const void *target_logits_dev, const void *draft_logits_dev, int vocab, int n_seqs, const int *row0, const int *lens,
+                          const int *starts, const int32_t *tokens_dev, const float *temperature_dev, const int32_t *top_k_dev,
+                          const float *top_p_dev, const uint64_t *seed_dev, float draft_temperature, int draft_top_k, float draft_top_p,
+                          int32_t *accept_dev, int32_t *alt_dev, tl_verify_result *out_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Greedy generation with prompt-lookup speculative decoding: no draft model, the proposals come from the sequence itself.
+"""Generation with prompt-lookup speculative decoding: no draft model, the proposals come from the sequence itself.
 
   python lookup_main.py <checkpoint dir> [PROMPT ...] [--prompts-file f] [--proposal-length 4] [--max-ngram 3] [--min-ngram 1]
-                        [--max-seq-len 512] [--raw-prompts]
+                        [--max-seq-len 512] [--raw-prompts] [--sampler-temp T] [--sampler-top-k K] [--sampler-top-p P] [--sampler-seed S]
 
 Every round the engine looks, on the device, for the last --max-ngram .. --min-ngram ids of each sequence earlier in that sequence
 (prompt included) and proposes the up to --proposal-length ids that followed; one batched verification pass accepts what the model
 itself would have produced (tiny_llm_hip.engine.lookup_generate_ids).  The answers are the model's greedy answers; what changes is the
 number of passes, which the last line reports.  Prompts that are quoted, edited or summarised in the answer gain the most.
+With --sampler-temp above 0 the requests sample on the device (main.py's flags; request i draws from --sampler-seed + i) and the
+proposals are verified by speculative sampling: the answers are distributed exactly as the sampler's own, only the passes change.
 """
 import argparse
 import json
@@ -35,6 +37,10 @@ def build_parser():
     ap.add_argument("--kv-format", default="bf16", choices=["bf16", "fp8"])
     ap.add_argument("--enable-thinking", action="store_true")
     ap.add_argument("--raw-prompts", action="store_true", help="do not wrap the prompts in the chat template")
+    ap.add_argument("--sampler-temp", type=float, default=0.0, help="0 = greedy; else sample on the device, proposals verified by speculative sampling")
+    ap.add_argument("--sampler-top-k", type=int, default=None, help="sample among the K most likely tokens")
+    ap.add_argument("--sampler-top-p", type=float, default=None, help="sample among the likeliest tokens whose mass reaches this")
+    ap.add_argument("--sampler-seed", type=int, default=0, help="the device's seed: request i draws from seed + i")
     return ap
 
 
@@ -47,6 +53,8 @@ def main(argv=None):
         ap.error("--max-ngram must be between 1 and 16")
     if not 1 <= args.min_ngram <= args.max_ngram:
         ap.error("--min-ngram must be between 1 and --max-ngram")
+    if args.sampler_temp < 0.0:
+        ap.error("--sampler-temp must be >= 0")
 
     from tiny_llm_hip import load, request
     from tiny_llm_hip.engine import DecodeEngine, lookup_generate_ids
@@ -69,9 +77,13 @@ def main(argv=None):
     engine = DecodeEngine(model, page_size=128, num_pages=pages_per_seq * wave + 2, max_batch=wave, max_pages_per_seq=pages_per_seq,
                           max_prefill_rows=args.prefill_step, kv_format=args.kv_format)
     stats = {}
+    sampled = {}
+    if args.sampler_temp > 0.0:
+        sampled = {"sampling": {"temperature": args.sampler_temp, "top_k": args.sampler_top_k, "top_p": args.sampler_top_p},
+                   "base_seed": args.sampler_seed}
     try:
         answers = lookup_generate_ids(engine, encoded, limits, proposal_length=args.proposal_length, max_ngram=args.max_ngram,
-                                      min_ngram=args.min_ngram, eos_token_id=tokenizer.eos_token_id, stats=stats)
+                                      min_ngram=args.min_ngram, eos_token_id=tokenizer.eos_token_id, stats=stats, **sampled)
     finally:
         engine.close()
     results = []

@@ -292,6 +292,10 @@ struct tl_engine {
         int32_t *desc = nullptr, *greedy = nullptr;
         tl_verify_result *results = nullptr;
         const int32_t *arr(int which) const { return desc + which * VERIFY_BATCH_ROWS; }
+        int rows = 0;  // rows of `logits` the last pass wrote (tl_engine_copy_verify_logits)
+        // tl_engine_verify_batch_sampled: accept / alt of the pass's rows, allocated by its first call
+        DeviceBlock sampled_mem;
+        int32_t *accept = nullptr, *alt = nullptr;
     } vb;
 
     int qkv_dim() const { return (cfg.num_heads + 2 * cfg.num_kv_heads) * cfg.head_dim; }
@@ -1974,8 +1978,9 @@ extern "C" int tl_engine_lookup_state(const tl_engine *e, int slot, int *armed, 
     return TL_OK;
 }
 
-extern "C" int tl_engine_lookup_propose(tl_engine *e, int n_seqs, const int *slots, const int *max_lens, int max_ngram, int min_ngram, int num_proposals,
-                                        int32_t *tokens_out, int *lens_out) {
+// the body of tl_engine_lookup_propose and tl_engine_lookup_propose_sampled (sampled: the slots are those tl_engine_verify_batch_sampled takes)
+static int lookup_propose_call(tl_engine *e, int n_seqs, const int *slots, const int *max_lens, int max_ngram, int min_ngram, int num_proposals,
+                               int32_t *tokens_out, int *lens_out, bool sampled) {
     TL_REQUIRE(e && slots && tokens_out && lens_out, "engine_lookup_propose: null argument");
     TL_REQUIRE(n_seqs >= 1 && n_seqs <= LOOKUP_MAX_SLOTS, "engine_lookup_propose: between 1 and 64 sequences per call");
     TL_TRY(lookup_params_check("engine_lookup_propose", max_ngram, min_ngram, num_proposals));
@@ -1984,7 +1989,7 @@ extern "C" int tl_engine_lookup_propose(tl_engine *e, int n_seqs, const int *slo
     int total = 0;
     for (int i = 0; i < n_seqs; ++i) {
         TL_TRY(slot_check_feeds(e, slots[i]));  // what tl_engine_verify_batch refuses: parked, stopped, ...
-        TL_TRY(table_rc(e->settings.refuses_verify_batch(slots[i])));
+        TL_TRY(table_rc(sampled ? e->settings.refuses_verify_batch_sampled(slots[i]) : e->settings.refuses_verify_batch(slots[i])));
         TL_REQUIRE(e->settings.lookup_on(slots[i]), "engine_lookup_propose: a slot is not armed (tl_engine_set_lookup)");
         for (int j = 0; j < i; ++j) TL_REQUIRE(slots[j] != slots[i], "engine_lookup_propose: a slot appears twice");
         const int max_len = max_lens ? max_lens[i] : VERIFY_MAX_LEN;
@@ -2015,6 +2020,16 @@ extern "C" int tl_engine_lookup_propose(tl_engine *e, int n_seqs, const int *slo
         for (int j = 0; j <= n; ++j) tokens_out[at++] = host[i * LOOKUP_ROW + j];
     }
     return TL_OK;
+}
+
+extern "C" int tl_engine_lookup_propose(tl_engine *e, int n_seqs, const int *slots, const int *max_lens, int max_ngram, int min_ngram, int num_proposals,
+                                        int32_t *tokens_out, int *lens_out) {
+    return lookup_propose_call(e, n_seqs, slots, max_lens, max_ngram, min_ngram, num_proposals, tokens_out, lens_out, false);
+}
+
+extern "C" int tl_engine_lookup_propose_sampled(tl_engine *e, int n_seqs, const int *slots, const int *max_lens, int max_ngram, int min_ngram,
+                                                int num_proposals, int32_t *tokens_out, int *lens_out) {
+    return lookup_propose_call(e, n_seqs, slots, max_lens, max_ngram, min_ngram, num_proposals, tokens_out, lens_out, true);
 }
 
 extern "C" int tl_engine_set_logit_bias(tl_engine *e, int slot, const int32_t *ids, const float *values, int n) {
@@ -3119,10 +3134,17 @@ static int verify_alloc(tl_engine *e) {
 }
 
 // The checks of a batched verification and its sequences (pass_seqs holds what it shares with a packed pass).
-static int verify_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, bool commit, std::vector<PrefillSeq> &seqs,
-                       int *total) {
+// draft: NULL for the greedy call, else what tl_engine_verify_batch_sampled was given of the draft (its slots may sample).
+struct VerifyDraft {
+    const void *rows;  // [R, V] bf16 on the device; NULL: point proposals
+    float temperature;
+    int top_k;
+    float top_p;
+};
+static int verify_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, bool commit, const VerifyDraft *draft,
+                       std::vector<PrefillSeq> &seqs, int *total) {
     const tl_engine_config &c = e->cfg;
-    const std::string w = "engine_verify_batch: ";
+    const std::string w = draft ? "engine_verify_batch_sampled: " : "engine_verify_batch: ";
     TL_REQUIRE(n_seqs >= 1 && n_seqs <= VERIFY_BATCH_ROWS, w + "between 1 and 64 sequences per call");
     TL_REQUIRE(c.head_dim == VA_D, w + "head_dim 128");
     int rows = 0;
@@ -3135,7 +3157,13 @@ static int verify_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t
     for (int l = 0; l < c.num_layers; ++l) moe |= e->is_moe(l);
     TL_REQUIRE(!moe || rows <= e->rows_cap, w + "a model with MoE layers takes at most max(max_batch, max_prefill_rows) rows (the experts' workspace)");
     // (a slot's refusal is met at its first appearance, ahead of "a slot appears twice" at its second, wherever it stands in the loop)
-    const auto per_seq = [&](int i) { return table_rc(e->settings.refuses_verify_batch(slots[i])); };
+    if (draft) {
+        TL_REQUIRE(std::isfinite(draft->temperature) && draft->temperature >= 0.f, w + "the draft's temperature must be finite and >= 0");
+        TL_REQUIRE(c.vocab_size <= SMP_MAX_VOCAB, w + "vocabulary larger than the sampler's 524,288 tokens");
+    }
+    const auto per_seq = [&](int i) {
+        return table_rc(draft ? e->settings.refuses_verify_batch_sampled(slots[i]) : e->settings.refuses_verify_batch(slots[i]));
+    };
     return pass_seqs(e, n_seqs, slots, tokens, lens, commit, w, per_seq, [](int) { return (int)TL_OK; }, seqs, total);
 }
 
@@ -3143,8 +3171,9 @@ static int verify_seqs(tl_engine *e, int n_seqs, const int *slots, const int32_t
 // one copy, the rows embedded, then every layer on the shared-buffer decode route over the scratch's own buffers -- the projections
 // through engine_linear with M = total (the sums of squares handed over where ProjResult says they were left, nothing weighted, no
 // per-layer buffer), the attention stage of verify_attn.h in between -- the lm_head over all rows into the scratch's logits and the
-// acceptance launches.  The slots end the pass as prefill_pass leaves them; e->logits and its owner stay as they were.
-static int verify_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const int32_t *tokens, int total) {
+// acceptance launches: the greedy pair, or with `draft` the sampling pair of verify_sample.h, which reads every slot's sampler parameters
+// where SB_SAMPLE keeps them.  The slots end the pass as prefill_pass leaves them; e->logits and its owner stay as they were.
+static int verify_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const int32_t *tokens, int total, const VerifyDraft *draft) {
     using V = tl_engine::VerifyScratch;
     const tl_engine_config &c = e->cfg;
     V &v = e->vb;
@@ -3229,8 +3258,22 @@ static int verify_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const i
     Proj ph = proj(e->head(), b.x_out, v.logits, total);
     ph.pro = PRO_RMSNORM, ph.norm_w = e->final_norm, ph.kind = 4, ph.ss_in = x_ss ? b.ss_x_out : nullptr, ph.ss_in_n = x_ss;
     TL_TRY(engine_linear(ctx, ph));
-    TL_TRY(launch_verify_accept(v.logits, c.vocab_size, total, n_seqs, v.arr(V::TOKENS), v.arr(V::SEQ_ROW0), v.arr(V::SEQ_LEN), v.greedy, v.results,
-                                e->stream));
+    v.rows = total;
+    if (draft) {
+        const SlotSettings::Offsets &at = e->settings.at;
+        VerifySampleArgs a{};
+        a.target = v.logits, a.draft = (const uint16_t *)draft->rows, a.vocab = c.vocab_size, a.n_seqs = n_seqs;
+        a.tokens = v.arr(V::TOKENS), a.seq_row0 = v.arr(V::SEQ_ROW0), a.seq_len = v.arr(V::SEQ_LEN), a.seq_ctx = v.arr(V::SEQ_CTX);
+        a.seq_index = v.arr(V::SEQ_SLOT);
+        a.temperature = e->sdev<float>(SB_SAMPLE, at.smp_temp), a.top_k = e->sdev<int32_t>(SB_SAMPLE, at.smp_topk);
+        a.top_p = e->sdev<float>(SB_SAMPLE, at.smp_topp), a.seed = e->sdev<uint64_t>(SB_SAMPLE, at.smp_seed);
+        a.d_temperature = draft->temperature, a.d_top_k = draft->top_k, a.d_top_p = draft->top_p;
+        a.accept = v.accept, a.alt = v.alt;
+        TL_TRY(launch_verify_sample(a, nullptr, total, v.results, e->stream));
+    } else {
+        TL_TRY(launch_verify_accept(v.logits, c.vocab_size, total, n_seqs, v.arr(V::TOKENS), v.arr(V::SEQ_ROW0), v.arr(V::SEQ_LEN), v.greedy, v.results,
+                                    e->stream));
+    }
     for (int i = 0; i < n_seqs; ++i) {
         e->table.appended(seqs[i].slot, tokens + seqs[i].row0, seqs[i].len);
         e->settings.appended(seqs[i].slot, false);  // a pending token that is appended is never fed again
@@ -3241,14 +3284,22 @@ static int verify_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const i
     return TL_OK;
 }
 
-extern "C" int tl_engine_verify_batch(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, int commit,
-                                      tl_verify_result *out) {
-    TL_REQUIRE(e && slots && tokens && lens && out, "engine_verify_batch: null argument");
+// the body of tl_engine_verify_batch and tl_engine_verify_batch_sampled: the checks, the pass, the results and the commit
+static int verify_batch_call(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, int commit, const VerifyDraft *draft,
+                             tl_verify_result *out) {
+    TL_REQUIRE(e && slots && tokens && lens && out, draft ? "engine_verify_batch_sampled: null argument" : "engine_verify_batch: null argument");
     std::vector<PrefillSeq> seqs;
     int total = 0;
-    TL_TRY(verify_seqs(e, n_seqs, slots, tokens, lens, commit != 0, seqs, &total));
+    TL_TRY(verify_seqs(e, n_seqs, slots, tokens, lens, commit != 0, draft, seqs, &total));
     TL_TRY(verify_alloc(e));
-    TL_TRY(verify_pass(e, seqs.data(), n_seqs, tokens, total));
+    if (draft && !e->vb.accept) {
+        tl_engine::VerifyScratch &v = e->vb;
+        const size_t bytes = 2 * (size_t)VERIFY_BATCH_ROWS * 4;
+        TL_TRY(v.sampled_mem.alloc(bytes, "engine_verify_batch_sampled: hipMalloc failed"));
+        v.accept = v.sampled_mem.at<int32_t>(), v.alt = v.accept + VERIFY_BATCH_ROWS;
+        e->stats.workspace_bytes += bytes;
+    }
+    TL_TRY(verify_pass(e, seqs.data(), n_seqs, tokens, total, draft));
     TL_HIP(hipMemcpyAsync(out, e->vb.results, (size_t)n_seqs * sizeof(tl_verify_result), hipMemcpyDeviceToHost, e->stream));
     TL_HIP(hipStreamSynchronize(e->stream));
     if (!commit) return TL_OK;
@@ -3258,6 +3309,27 @@ extern "C" int tl_engine_verify_batch(tl_engine *e, int n_seqs, const int *slots
         if (lens[i] - 1 - a > 0) TL_TRY(tl_engine_rewind(e, slots[i], lens[i] - 1 - a));
         TL_TRY(tl_engine_set_token(e, slots[i], out[i].ids[a]));
     }
+    return TL_OK;
+}
+
+extern "C" int tl_engine_verify_batch(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens, int commit,
+                                      tl_verify_result *out) {
+    return verify_batch_call(e, n_seqs, slots, tokens, lens, commit, nullptr, out);
+}
+
+extern "C" int tl_engine_verify_batch_sampled(tl_engine *e, int n_seqs, const int *slots, const int32_t *tokens, const int *lens,
+                                              const void *draft_logits_dev, float draft_temperature, int draft_top_k, float draft_top_p, int commit,
+                                              tl_verify_result *out) {
+    const VerifyDraft draft{draft_logits_dev, draft_temperature, draft_top_k, draft_top_p};
+    return verify_batch_call(e, n_seqs, slots, tokens, lens, commit, &draft, out);
+}
+
+extern "C" int tl_engine_copy_verify_logits(tl_engine *e, int row0, int rows, void *dst_dev) {
+    TL_REQUIRE(e && dst_dev, "engine_copy_verify_logits: null argument");
+    TL_REQUIRE(e->vb.rows > 0, "engine_copy_verify_logits: no batched verification has run yet");
+    TL_REQUIRE(row0 >= 0 && rows >= 1 && row0 <= e->vb.rows - rows, "engine_copy_verify_logits: rows outside the last pass");
+    TL_HIP(hipMemcpyAsync(dst_dev, e->vb.logits + (size_t)row0 * e->cfg.vocab_size, (size_t)rows * e->cfg.vocab_size * 2, hipMemcpyDeviceToDevice,
+                          e->stream));
     return TL_OK;
 }
 

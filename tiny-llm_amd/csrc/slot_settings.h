@@ -535,6 +535,13 @@ class SlotSettings {
         if (slots[slot].lora >= 0) return "engine_verify_batch: a slot carries a LoRA adapter (adapters are verified one slot at a time, tl_engine_verify)";
         return nullptr;
     }
+    // what refuses_verify_batch refuses, except sampling; and truncation of any kind, as refuses_verify_sampled
+    const char *refuses_verify_batch_sampled(int slot) const {
+        if (slots[slot].pen.processes()) return "engine_verify_batch_sampled: a slot processes its logits (verification takes the raw rows; make it neutral first)";
+        if (slots[slot].trn.truncates()) return "engine_verify_batch_sampled: a slot truncates (min-p / typical-p / Mirostat keep other sets than the verification's; switch them off first)";
+        if (slots[slot].lora >= 0) return "engine_verify_batch_sampled: a slot carries a LoRA adapter (adapters are verified one slot at a time, tl_engine_verify_sampled)";
+        return nullptr;
+    }
     // a beam group decodes through the plain greedy program and selects from the raw rows
     const char *refuses_beam(int slot) const {
         if (slots[slot].smp.samples()) return "engine_beam: the slot samples (beam slots are greedy)";

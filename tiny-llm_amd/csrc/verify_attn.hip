@@ -64,7 +64,7 @@ using namespace tl;
 
 // The two stages over caller rows and pools (header, last section): the launches of the pass with descriptors built from the host arrays.
 // One allocation per call (descriptors, rotated queries, partials), released behind the synchronisation.
-static int verify_rows_check(const char *who, int n_seqs, const int *row0_or_null, const int *lens, int *total_out) {
+int tl::verify_rows_check(const char *who, int n_seqs, const int *row0_or_null, const int *lens, int *total_out) {
     const std::string w = std::string(who) + ": ";
     TL_REQUIRE(n_seqs >= 1 && n_seqs <= VA_MAX_ROWS && lens, w + "between 1 and 64 sequences");
     int total = 0;

@@ -56,4 +56,32 @@ int launch_verify_attention(const VerifyRowsArgs &q, VerifyAttnArgs a, const Ver
 int launch_verify_accept(const uint16_t *logits, int vocab, int total_rows, int n_seqs, const int32_t *tokens, const int32_t *seq_row0,
                          const int32_t *seq_len, int32_t *greedy, tl_verify_result *out, hipStream_t st);
 
+// The acceptance stage for slots that sample (verify_sample.h holds the kernels, verify_sample.hip compiles them): everything lives on
+// the device, the draft's one parameter triple rides in the arguments.
+struct VerifySampleArgs {
+    const uint16_t *target;  // [R, vocab]
+    const uint16_t *draft;   // [R, vocab], the row of a bonus proposal is never read; NULL: point proposals (one-hot at the proposed id)
+    int vocab, n_seqs;
+    const int32_t *tokens;                         // [R] the tokens the rows were fed
+    const int32_t *seq_row0, *seq_len, *seq_ctx;   // [n_seqs]; seq_ctx = the context length behind the sequence's last row
+    const int32_t *seq_index;                      // [n_seqs] where a sequence's parameters stand in the four arrays below (NULL: at i)
+    const float *temperature;
+    const int32_t *top_k;
+    const float *top_p;
+    const uint64_t *seed;
+    float d_temperature;
+    int d_top_k;
+    float d_top_p;
+    int32_t *accept, *alt;  // [R]
+};
+// the sequences of the routine over caller rows, handed over as kernel arguments (a.seq_* are not read then)
+struct VerifySeqsInline {
+    uint8_t row0[VA_MAX_ROWS], len[VA_MAX_ROWS];
+    int32_t ctx[VA_MAX_ROWS];
+};
+// accept / alt of `total_rows` rows, then one tl_verify_result per sequence; seqs NULL: the descriptors a.seq_* on the device
+int launch_verify_sample(const VerifySampleArgs &a, const VerifySeqsInline *seqs, int total_rows, tl_verify_result *out, hipStream_t st);
+// what the routines over caller rows ask of their sequences (`who` names the routine in the message)
+int verify_rows_check(const char *who, int n_seqs, const int *row0_or_null, const int *lens, int *total_out);
+
 }  // namespace tl

@@ -284,6 +284,13 @@ _SIGNATURES.update({
     "tl_verify_attention_rows": (_c_int, [_c_void_p] * 8 + [_c_int, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _c_void_p] + [_c_int] * 4 +
                                  [_c_float, _c_float, _c_void_p, _P(TlAttentionInfo)]),
     "tl_verify_accept_rows": (_c_int, [_c_void_p, _c_int, _c_int, _P(ctypes.c_int), _P(ctypes.c_int), _c_void_p, _c_void_p, _c_void_p]),
+    "tl_engine_verify_batch_sampled": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int), _P(ctypes.c_int32), _P(ctypes.c_int), _c_void_p, ctypes.c_float,
+                                                _c_int, ctypes.c_float, _c_int, _P(TlVerifyResult)]),
+    "tl_engine_copy_verify_logits": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p]),
+    "tl_verify_sample_rows": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int)] + [_c_void_p] * 5 +
+                              [ctypes.c_float, _c_int, ctypes.c_float, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "tl_engine_lookup_propose_sampled": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int), _P(ctypes.c_int), _c_int, _c_int, _c_int, _P(ctypes.c_int32),
+                                                  _P(ctypes.c_int)]),
     "tl_engine_set_token": (_c_int, [_c_void_p, _c_int, ctypes.c_int32]),
     "tl_engine_set_lookup": (_c_int, [_c_void_p, _c_int, _c_int]),
     "tl_engine_lookup_propose": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int), _P(ctypes.c_int), _c_int, _c_int, _c_int, _P(ctypes.c_int32),
@@ -996,6 +1003,52 @@ def verify_accept_rows(logits: torch.Tensor, row0, lens, tokens: torch.Tensor) -
     _check(_lib.tl_verify_accept_rows(_ptr(logits), int(logits.shape[1]), n, arr(row0), arr(lens), _ptr(tokens), _ptr(out), _stream()))
     host = out.cpu().tolist()
     return [rec[1:1 + rec[0]] for rec in host[:n]]
+
+
+def verify_sample_rows(target: torch.Tensor, draft, row0, lens, starts, tokens: torch.Tensor, temperature, top_k, top_p, seed,
+                       draft_sampling=(0.0, 0, 1.0)):
+    """The acceptance stage of a batched speculative-sampling pass over caller rows (tl_verify_sample_rows): ``target`` [R, vocab] bf16,
+    ``draft`` the rows the proposals were drawn from under ``draft_sampling`` = (temperature, top_k, top_p), or None for point proposals
+    (one-hot at the proposed id); ``tokens`` [R] int32 the tokens the rows were fed; sequence i owns the rows [row0[i], row0[i] +
+    lens[i]) and held starts[i] tokens before them; ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: a scalar or one value per
+    sequence.  Returns (accept int32 [R], alt int32 [R] on the device, per sequence the accepted proposals followed by one more token)."""
+    _require_gpu("verify_sample_rows", target, tokens)
+    if target.dtype != torch.bfloat16 or target.dim() != 2 or not target.is_contiguous():
+        raise RuntimeError("verify_sample_rows: target must be contiguous bfloat16 [rows, vocab]")
+    if draft is not None and (not isinstance(draft, torch.Tensor) or draft.dtype != torch.bfloat16 or draft.shape != target.shape or
+                              draft.device != target.device or not draft.is_contiguous()):
+        raise RuntimeError("verify_sample_rows: draft must be None or contiguous bfloat16 of the target's shape, on its device")
+    if tokens.dtype != torch.int32 or tokens.dim() != 1 or tokens.shape[0] != target.shape[0] or not tokens.is_contiguous():
+        raise RuntimeError("verify_sample_rows: tokens must be contiguous int32 [rows]")
+    n = len(lens)
+    if len(row0) != n or len(starts) != n or any(int(r) < 0 or int(r) + int(k) > target.shape[0] for r, k in zip(row0, lens)):
+        raise RuntimeError("verify_sample_rows: every sequence's rows must lie inside target (one row0 / lens / starts per sequence)")
+    dev = target.device
+
+    def per_seq(v, dtype):
+        t = torch.as_tensor(v, dtype=dtype).reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(max(n, 1))
+        if t.numel() != n:
+            raise ValueError("a verification parameter needs one value per sequence")
+        return t.contiguous().to(dev)
+
+    seeds = [int(s) & 0xFFFFFFFFFFFFFFFF for s in (seed if hasattr(seed, "__len__") else [seed] * n)]
+    if len(seeds) != n:
+        raise ValueError("a verification parameter needs one value per sequence")
+    seed_t = torch.tensor([s - (1 << 64) if s >= 1 << 63 else s for s in seeds], dtype=torch.int64).to(dev)  # uint64 bits
+    tt, tk, tp = per_seq(temperature, torch.float32), per_seq(top_k, torch.int32), per_seq(top_p, torch.float32)
+    arr = lambda v: (ctypes.c_int * n)(*[int(x) for x in v])
+    rows = int(target.shape[0])
+    accept = torch.zeros(rows, dtype=torch.int32, device=dev)
+    alt = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+    out = torch.zeros((max(n, 1), 9), dtype=torch.int32, device=dev)  # tl_verify_result: count, ids[8]
+    dt, dk, dp = draft_sampling
+    _check(_lib.tl_verify_sample_rows(_ptr(target), _ptr(draft) if draft is not None else None, int(target.shape[1]), n, arr(row0), arr(lens),
+                                      arr(starts), _ptr(tokens), _ptr(tt), _ptr(tk), _ptr(tp), _ptr(seed_t), float(dt), int(dk or 0),
+                                      float(1.0 if dp is None else dp), _ptr(accept), _ptr(alt), _ptr(out), _stream()))
+    host = out.cpu().tolist()
+    return accept, alt, [rec[1:1 + rec[0]] for rec in host[:n]]
 
 
 # ---- FP8 (E4M3) KV pages: the quantised twins of paged_cache_update / paged_attention -------------------------------------

@@ -381,11 +381,12 @@ class DecodeEngine:
         return bool(a.value), s.value, r.value
 
     def lookup_propose(self, slots: Sequence[int], max_lens: Sequence[int] | None = None, max_ngram: int = 3, min_ngram: int = 1,
-                       num_proposals: int = 4) -> list[list[int]]:
+                       num_proposals: int = 4, sampled: bool = False) -> list[list[int]]:
         """Prompt-lookup proposals for several armed slots in one launch (tl_engine_lookup_propose): per slot the chunk
         ``verify_batch`` takes -- the pending token followed by the ids that followed the longest earlier occurrence of the slot's last
         1 .. ``max_ngram`` ids (at least ``min_ngram``), at most ``num_proposals`` and at most ``max_lens[i] - 1`` of them; the pending
-        token alone where nothing matches.  Synchronises once."""
+        token alone where nothing matches.  ``sampled``: the chunks are meant for ``verify_batch_sampled`` (tl_engine_lookup_propose_sampled),
+        which takes slots that sample and refuses slots that truncate.  Synchronises once."""
         slots = [int(s) for s in slots]
         if not 1 <= len(slots) <= 64:
             raise ValueError("lookup_propose takes between 1 and 64 slots")
@@ -403,7 +404,8 @@ class DecodeEngine:
             raise ValueError("more than 8 slots need max_lens (the chunks together may hold at most 64 tokens)")
         tokens = (ctypes.c_int32 * 64)()
         lens = (ctypes.c_int * n)()
-        _ext.check(_lib.tl_engine_lookup_propose(self._h, n, (ctypes.c_int * n)(*slots), lens_in, max_ngram, min_ngram, num_proposals, tokens, lens))
+        propose = _lib.tl_engine_lookup_propose_sampled if sampled else _lib.tl_engine_lookup_propose
+        _ext.check(propose(self._h, n, (ctypes.c_int * n)(*slots), lens_in, max_ngram, min_ngram, num_proposals, tokens, lens))
         out, at = [], 0
         for i in range(n):
             out.append(list(tokens[at:at + lens[i]]))
@@ -614,6 +616,49 @@ class DecodeEngine:
         out = (_ext.TlVerifyResult * n)()
         _ext.check(_lib.tl_engine_verify_batch(self._h, n, slots, arr, lens, int(bool(commit)), out))
         return [list(r.ids[:r.count]) for r in out]
+
+    def verify_batch_sampled(self, chunks: Sequence[tuple[int, Sequence[int]]], commit: bool = False, draft_rows: torch.Tensor | None = None,
+                             draft_sampling=(0.0, None, None)) -> list[list[int]]:
+        """Batched speculative sampling (tl_engine_verify_batch_sampled): ``verify_batch`` for slots that sample -- every proposal is
+        verified under its slot's own sampling parameters (set_sampling), so the ids returned are distributed exactly as if the slot had
+        sampled them alone; a greedy slot in the same call gets ``verify_batch``'s result.  ``draft_rows`` None: point proposals, a
+        deterministic function of the sequence such as ``lookup_propose``'s (one-hot at the proposed id; only the target rows are read).
+        ``draft_rows`` [sum of chunk lengths, vocab] bf16 on the device: row r is the logits row the draft drew token r + 1 of the
+        flattened chunks from under ``draft_sampling`` = (temperature, top_k, top_p) (or a dict with those keys); the row at a chunk's
+        last position is never read.  ``commit`` as in ``verify_batch``.  All or nothing.  Synchronises once."""
+        chunks = [(int(s), [int(t) for t in toks]) for s, toks in chunks]
+        if not chunks:
+            raise ValueError("verify_batch_sampled needs at least one chunk")
+        if any(not 1 <= len(toks) <= 8 for _, toks in chunks):
+            raise ValueError("verify_batch_sampled takes between 1 and 8 tokens per slot")
+        flat = [t for _, toks in chunks for t in toks]
+        if len(flat) > 64:
+            raise ValueError("verify_batch_sampled takes at most 64 tokens per call")
+        if isinstance(draft_sampling, dict):
+            draft_sampling = (draft_sampling.get("temperature", 0.0), draft_sampling.get("top_k"), draft_sampling.get("top_p"))
+        t, k, p, _ = sampling_args(*draft_sampling)
+        ptr = None
+        if draft_rows is not None:
+            if not isinstance(draft_rows, torch.Tensor) or draft_rows.dtype != torch.bfloat16 or draft_rows.dim() != 2 or not draft_rows.is_cuda \
+                    or not draft_rows.is_contiguous() or draft_rows.shape[0] != len(flat) or draft_rows.shape[1] != self.vocab_size:
+                raise ValueError(f"draft_rows must be a contiguous bf16 tensor [{len(flat)}, {self.vocab_size}] on the GPU")
+            ptr = draft_rows.data_ptr()
+        n = len(chunks)
+        slots = (ctypes.c_int * n)(*[s for s, _ in chunks])
+        lens = (ctypes.c_int * n)(*[len(toks) for _, toks in chunks])
+        arr = (ctypes.c_int32 * len(flat))(*flat)
+        out = (_ext.TlVerifyResult * n)()
+        _ext.check(_lib.tl_engine_verify_batch_sampled(self._h, n, slots, arr, lens, ptr, t, k, p, int(bool(commit)), out))
+        return [list(r.ids[:r.count]) for r in out]
+
+    def verify_logits(self, rows: int, row0: int = 0) -> torch.Tensor:
+        """A copy of rows [row0, row0 + rows) of the last batched verification's own logits block [rows, vocab] (bf16)
+        (tl_engine_copy_verify_logits): the rows the acceptance stage of ``verify_batch`` / ``verify_batch_sampled`` read."""
+        out = torch.empty((rows, self.vocab_size), dtype=torch.bfloat16, device=self.device)
+        torch.cuda.current_stream().synchronize()
+        _ext.check(_lib.tl_engine_copy_verify_logits(self._h, int(row0), int(rows), out.data_ptr()))
+        self.synchronize()
+        return out
 
     def verify_sampled(self, slot: int, tokens: Sequence[int], draft_rows: torch.Tensor | None, draft_sampling=(0.0, None, None)) -> list[int]:
         """Speculative sampling (tl_engine_verify_sampled): append 1..8 tokens to the slot -- its pending token and the draft's
@@ -1279,8 +1324,9 @@ def batch_speculative_generate_ids(target, draft, prompts: Sequence[Sequence[int
 
 
 def lookup_generate_ids(engine, prompts: Sequence[Sequence[int]], max_new_tokens: int | Sequence[int], proposal_length: int = 4, max_ngram: int = 3,
-                        min_ngram: int = 1, eos_token_id: int | None = None, *, stats: dict | None = None) -> list[list[int]]:
-    """Greedy speculative decoding without a draft model: ``batch_speculative_generate_ids``' loop with prompt lookup as the proposer
+                        min_ngram: int = 1, eos_token_id: int | None = None, *, stats: dict | None = None, sampling=None,
+                        base_seed: int = 0) -> list[list[int]]:
+    """Speculative decoding without a draft model: ``batch_speculative_generate_ids``' loop with prompt lookup as the proposer
     (``DecodeEngine.lookup_propose``: the ids that followed the longest earlier occurrence of a sequence's last 1 .. ``max_ngram`` ids).
     Prompts run in waves of at most ``min(engine.max_batch, 64 // (proposal_length + 1))`` slots, prompt i of a wave on slot i, each
     armed before its prefill so that the prompt is part of what is matched.  Per round ONE ``lookup_propose`` over the live slots (each
@@ -1290,7 +1336,14 @@ def lookup_generate_ids(engine, prompts: Sequence[Sequence[int]], max_new_tokens
     token, which costs no pass.
     Returns, per prompt, the engine's greedy continuation (up to ``max_new_tokens`` ids -- one number, or one per prompt -- stopping
     before ``eos_token_id``).  ``stats`` receives ``rounds`` (verify_batch calls), ``steps`` (decode steps), ``proposed`` and
-    ``accepted``."""
+    ``accepted``.
+    ``sampling``: one dict for every request or one per prompt with the keys ``temperature``, ``top_k``, ``top_p`` and ``seed`` only
+    (verification takes the raw rows, so any other key is a ValueError that names it); a request without a seed draws from ``base_seed``
+    + its index.  Each slot then gets ``set_sampling`` before it is armed and prefilled -- its first token is the device sampler's --
+    the rounds use ``lookup_propose(..., sampled=True)`` and ``verify_batch_sampled(..., commit=True)``, and the ids returned are
+    distributed exactly as ``batch_generate_ids`` would sample them for the same settings (a lookup proposal is a deterministic function
+    of the sequence: its draft distribution is one-hot, and the accept / residual rule is exact for it).  None: the greedy loop, with
+    exactly the calls it has always made."""
     if not isinstance(proposal_length, int) or isinstance(proposal_length, bool) or not 1 <= proposal_length <= 7:
         raise ValueError("proposal_length must be an integer in [1, 7] (8 verification rows per slot)")
     _ext.lookup_params(max_ngram, min_ngram, proposal_length)
@@ -1300,6 +1353,13 @@ def lookup_generate_ids(engine, prompts: Sequence[Sequence[int]], max_new_tokens
     limits = [max_new_tokens] * len(prompts) if isinstance(max_new_tokens, int) else list(max_new_tokens)
     if len(limits) != len(prompts) or any(not isinstance(n, int) or isinstance(n, bool) or n < 0 for n in limits):
         raise ValueError("max_new_tokens must be a non-negative integer, or one per prompt")
+    settings = None
+    if sampling is not None:
+        dicts = [sampling] if isinstance(sampling, dict) else list(sampling)
+        other = sorted({k for d in dicts if isinstance(d, dict) for k in d} - {"temperature", "top_k", "top_p", "seed"})
+        if other:
+            raise ValueError(f"lookup_generate_ids verifies raw rows: sampling takes temperature, top_k, top_p and seed only, not {other}")
+        settings = [r.sampling for r in request_settings(sampling, len(prompts), base_seed)]
     wave = min(int(engine.max_batch), 64 // (proposal_length + 1))
     if wave < 1:
         raise ValueError("the engine holds no slot")
@@ -1329,6 +1389,8 @@ def lookup_generate_ids(engine, prompts: Sequence[Sequence[int]], max_new_tokens
                     continue
                 engine.begin(s)
                 held.add(s)
+                if settings is not None:
+                    engine.set_sampling(s, *settings[first + s])
                 engine.set_lookup(s)
                 engine.prefill(s, prompt)
                 token[s] = engine.read_tokens(s, 1)[0]
@@ -1337,7 +1399,8 @@ def lookup_generate_ids(engine, prompts: Sequence[Sequence[int]], max_new_tokens
             while token:
                 live = sorted(token)
                 room = {s: limits[first + s] - len(outs[first + s]) - 1 for s in live}  # proposals that could still be emitted after the pending token
-                fed = dict(zip(live, engine.lookup_propose(live, [1 + min(proposal_length, room[s]) for s in live], max_ngram, min_ngram, proposal_length)))
+                fed = dict(zip(live, engine.lookup_propose(live, [1 + min(proposal_length, room[s]) for s in live], max_ngram, min_ngram, proposal_length,
+                                                           **({} if settings is None else {"sampled": True}))))
                 for s in live:  # nothing is proposed behind an EOS
                     if eos_token_id in fed[s][1:]:
                         fed[s] = fed[s][:fed[s].index(eos_token_id, 1) + 1]
@@ -1349,7 +1412,8 @@ def lookup_generate_ids(engine, prompts: Sequence[Sequence[int]], max_new_tokens
                         token[s] = engine.read_tokens(s, 1)[0]
                         settle(s)
                     continue
-                results = engine.verify_batch([(s, fed[s]) for s in live], commit=True)
+                verify = engine.verify_batch if settings is None else engine.verify_batch_sampled
+                results = verify([(s, fed[s]) for s in live], commit=True)
                 counts["rounds"] += 1
                 for s, r in zip(live, results):
                     a = len(r) - 1
