@@ -1198,6 +1198,31 @@ int tl_logprob_rows(const void *logits_dev, int rows, int vocab, const int32_t *
 int tl_pool_rows(const void *rows_dev, int hidden, int n_seqs, const int *row0, const int *len, const int *finish, const int *prior, int pooling,
                  float *sums_dev, int normalize, int dim, float *out_dev, void *stream);
 
+/* The router of a MoE layer (tl_engine_set_moe_layer) over caller rows: logits_dev [rows, num_experts] bf16, the router's logits ->
+ * ids_dev [rows, top_k] int32 and scores_dev [rows, top_k] bf16.  Per row: softmax over the num_experts logits in fp32, each probability
+ * rounded to bf16; the top_k largest in descending order, equal probabilities the lower expert index first; the scores are those
+ * probabilities -- with norm_topk_prob != 0 divided by their sum (the fp32 sum in selection order rounded to bf16, each quotient rounded
+ * once).  A row with NaN / Inf logits still gets top_k distinct ids in [0, num_experts); its scores are unspecified.  The limits of
+ * tl_engine_set_moe_layer: 1 <= top_k <= min(16, num_experts), num_experts <= 1024; rows >= 1.  One launch of `rows` workgroups, the
+ * engine's kernel.  Stream ordered, no synchronisation. */
+int tl_moe_route_rows(const void *logits_dev, int rows, int num_experts, int top_k, int norm_topk_prob, int32_t *ids_dev, void *scores_dev,
+                      void *stream);
+
+/* Everything of a MoE layer's MLP behind the router, over caller rows, in the engine's five launches: xn_dev [rows, hidden] bf16 (the
+ * normalised rows the experts read), h_dev [rows, hidden] bf16 (the residual), ids_dev / scores_dev [rows, top_k] (int32 in
+ * [0, num_experts) -- the caller vouches for them -- and bf16; top_k = w->experts_per_token) -> out_dev [rows, hidden] bf16:
+ *   gate, up [rows * top_k, I] = xn[token] x gate / up of the row's expert (one grouped GEMV launch each);  act = bf16(bf16(silu(gate)) * up);
+ *   y [rows * top_k, hidden] = act x down of the row's expert;  out = bf16(h + bf16(sum_j bf16(y_j * score_j))), the sum over the token's
+ *   top_k rows in fp32, in the order of its ids, rounded once.
+ * Expert rows are token-major.  workspace_dev holds them for the caller to read, without gaps and in this order: gate, up, act
+ * [rows * top_k, I], then y [rows * top_k, hidden] -- tl_moe_experts_workspace_bytes(rows, top_k, hidden, intermediate) bytes (0 for a
+ * size that is not positive).  Of *w the expert tensors and the three sizes are read; router and norm_topk_prob are not.  Limits:
+ * those of tl_engine_set_moe_layer, hidden a multiple of 128, 1 <= rows * top_k <= 65,535, every row pointer 16-byte aligned.
+ * Stream ordered, no synchronisation. */
+size_t tl_moe_experts_workspace_bytes(int rows, int top_k, int hidden, int intermediate);
+int tl_moe_experts_rows(const void *xn_dev, const void *h_dev, const int32_t *ids_dev, const void *scores_dev, const tl_moe_weights *w, int rows,
+                        int hidden, void *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* The truncation routine of tl_engine_set_truncation / tl_engine_set_mirostat over caller rows: logits [rows, vocab] bf16 (vocab <=
  * 524,288), per-row device arrays of temperature, min_p, typical_p and mu (NaN = no Mirostat; a Mirostat row ignores min_p and
  * typical_p), filtered rows into out_dev (never the input) and, where kept_logsum_dev is not null, per row ln sum_kept exp(x_i / T) of a

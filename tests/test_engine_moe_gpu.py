@@ -17,18 +17,40 @@ from helpers import TINY_CFG
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def moe_model(tmp_path_factory):
+def _moe_checkpoint(tmp_path_factory, name, seed, **overrides):
     from checkpoint_fixture import MOE_CFG_OVERRIDES, make_moe_weights, write_checkpoint
     from tiny_llm_hip import load
 
     cfg = dict(TINY_CFG, **MOE_CFG_OVERRIDES)
-    w = make_moe_weights(cfg, seed=21)
+    cfg.update(overrides)
+    w = make_moe_weights(cfg, seed=seed)
     words = [f"w{i}" for i in range(cfg["vocab_size"] - 2)]
-    path = write_checkpoint(tmp_path_factory.mktemp("moe") / "ckpt", cfg, w, vocab_words=words)
+    path = write_checkpoint(tmp_path_factory.mktemp(name) / "ckpt", cfg, w, vocab_words=words)
     model, _ = load(str(path))
     model._oracle_weights = w  # the numpy weight dict the checkpoint was written from (oracle / truth side of the tests below)
     return cfg, model
+
+
+@pytest.fixture(scope="module")
+def moe_model(tmp_path_factory):
+    return _moe_checkpoint(tmp_path_factory, "moe", 21)
+
+
+# The expert counts the MoE kernels were written for (the layers stay 256 wide, the experts 128: what is new is the router's width, eight
+# expert rows per token, the tie rule at 128 bf16 probabilities): Qwen3-MoE's 128 experts, top 8, renormalised ...
+REAL_COUNTS = {"128x8": dict(num_experts=128, num_experts_per_tok=8, moe_intermediate_size=128, norm_topk_prob=True),
+               # ... and Qwen1.5/2-MoE's 60 experts, top 4, the probabilities as they are
+               "60x4": dict(num_experts=60, num_experts_per_tok=4, moe_intermediate_size=128, norm_topk_prob=False)}
+
+
+@pytest.fixture(scope="module")
+def moe_model_128(tmp_path_factory):
+    return _moe_checkpoint(tmp_path_factory, "moe128", 22, **REAL_COUNTS["128x8"])
+
+
+@pytest.fixture(scope="module")
+def moe_model_60(tmp_path_factory):
+    return _moe_checkpoint(tmp_path_factory, "moe60", 23, **REAL_COUNTS["60x4"])
 
 
 def mirror_logits(model, prompt, forced):
@@ -104,12 +126,9 @@ def test_moe_layers_must_be_attached_before_the_first_step(moe_model):
         eng.close()
 
 
-def test_two_sequences_decode_together_as_they_do_alone(moe_model):
-    """Batched decode over MoE layers: rows x top_k expert rows in one grouped launch; each sequence's logits stay within two bf16
-    steps of its own single-sequence run (the dense projections take the two-row GEMV plan) and free-running greedy ids repeat."""
+def two_sequences_together_and_alone(cfg, model):
     from tiny_llm_hip.engine import DecodeEngine
 
-    cfg, model = moe_model
     rng = np.random.default_rng(5)
     prompts = [[int(t) for t in rng.integers(2, cfg["vocab_size"], size=n)] for n in (9, 30)]
     forced = [[int(t) for t in rng.integers(2, cfg["vocab_size"], size=5)] for _ in prompts]
@@ -138,6 +157,17 @@ def test_two_sequences_decode_together_as_they_do_alone(moe_model):
         assert float(np.abs(have - want).max()) <= 2 * step, f"sequence {slot}: batched and single-sequence logits differ"
 
 
+def test_two_sequences_decode_together_as_they_do_alone(moe_model):
+    """Batched decode over MoE layers: rows x top_k expert rows in one grouped launch; each sequence's logits stay within two bf16
+    steps of its own single-sequence run (the dense projections take the two-row GEMV plan) and free-running greedy ids repeat."""
+    two_sequences_together_and_alone(*moe_model)
+
+
+def test_two_sequences_decode_together_as_they_do_alone_at_128_experts(moe_model_128):
+    """The same at 128 experts, eight per token: sixteen expert rows in each grouped launch of a step."""
+    two_sequences_together_and_alone(*moe_model_128)
+
+
 @pytest.mark.parametrize("n_prompt,chunk", [(5, 64), (7, 64), (23, 64)])
 def test_fused_engine_with_moe_layers_against_the_oracle_and_the_float64_truth(moe_model, n_prompt, chunk):
     """The comparand of the first test is the HIP op-by-op model (the same expert kernels on both sides).  Here it is the CPU side: the
@@ -147,23 +177,67 @@ def test_fused_engine_with_moe_layers_against_the_oracle_and_the_float64_truth(m
     choice, and a position counts only where the truth's own choice is the same set of experts (a toss-up between the k-th and the
     (k+1)-th expert is not an error of either side); at least two thirds of the positions must count.  Bar: the engine sits as close to
     the truth as the bf16 oracle does (helpers.check_against_truth); 5 and 7 prompt tokens prefill by GEMV rows, 23 by the tile GEMM."""
-    from helpers import check_against_truth
+    oracle_and_truth_case(*moe_model, n_prompt, chunk, seed=100 + n_prompt)
+
+
+def reference_side(cfg, w, prompt, forced):
+    """(bf16 oracle logits, float64 truth logits on the oracle's expert choice, which positions count) -- nothing here runs on a device.
+    A position counts where (1) the truth's own choice is the oracle's set of experts in every sparse layer and (2) the oracle's k-th and
+    (k+1)-th bf16 probabilities stand more than one bf16 step apart there: the engine's float32 softmax may round either of them one
+    step the other way and select differently without being wrong."""
+    from helpers import bf16_ulp
     from oracle import tiny_oracle as O
 
-    cfg, model = moe_model
-    w = model._oracle_weights
-    rng = np.random.default_rng(100 + n_prompt)
-    prompt = [int(t) for t in rng.integers(2, cfg["vocab_size"], size=n_prompt)]
-    forced = [int(t) for t in rng.integers(2, cfg["vocab_size"], size=6)]
-    got, stats = engine_logits(model, prompt, forced, chunk)
-    assert stats["graph_replays"] + stats["graph_captures"] >= len(forced)
     oracle, truth = O.OracleQwen3(cfg, w), O.TruthQwen3(cfg, w)
     want = [oracle.forward(prompt)[0, -1]] + [oracle.forward([t])[0, -1] for t in forced]
     truth.forced_moe_ids = oracle.moe_ids
     exact = [truth.forward(prompt)[0, -1]] + [truth.forward([t])[0, -1] for t in forced]
+    k = int(cfg["num_experts_per_tok"])
+
+    def clear_of_a_tie(c):
+        for calls in oracle.moe_probs.values():
+            srt = np.sort(calls[c][-1])[::-1]
+            if len(srt) > k and srt[k - 1] - srt[k] <= bf16_ulp(srt[k - 1]):
+                return False
+        return True
+
     # call c of a sparse layer = position c of the teacher-forced sequence (call 0: the prompt, its last token is the row compared)
-    counted = [all(bool(calls[c]["same_choice"][-1]) for calls in truth.moe_margins.values()) for c in range(len(forced) + 1)]
+    counted = [all(bool(calls[c]["same_choice"][-1]) for calls in truth.moe_margins.values()) and clear_of_a_tie(c) for c in range(len(forced) + 1)]
+    return np.stack(want), np.stack(exact), counted
+
+
+def prompt_and_forced(cfg, n_prompt, seed):
+    rng = np.random.default_rng(seed)
+    prompt = [int(t) for t in rng.integers(2, cfg["vocab_size"], size=n_prompt)]
+    return prompt, [int(t) for t in rng.integers(2, cfg["vocab_size"], size=6)]
+
+
+def oracle_and_truth_case(cfg, model, n_prompt, chunk, seed):
+    from helpers import check_against_truth
+
+    prompt, forced = prompt_and_forced(cfg, n_prompt, seed)
+    got, stats = engine_logits(model, prompt, forced, chunk)
+    assert stats["graph_replays"] + stats["graph_captures"] >= len(forced)
+    want, exact, counted = reference_side(cfg, model._oracle_weights, prompt, forced)
     assert sum(counted) >= 2 * len(counted) // 3 + 1, f"too many toss-up selections to compare: {counted}"
     keep = np.asarray(counted)
-    check_against_truth(np.asarray(got)[keep], np.stack(want)[keep], np.stack(exact)[keep],
-                        what=f"fused engine with 2 MoE layers, prompt {n_prompt} (chunk {chunk}), {int(keep.sum())} of {len(keep)} positions")
+    check_against_truth(np.asarray(got)[keep], want[keep], exact[keep],
+                        what=f"fused engine with 2 MoE layers ({cfg['num_experts']} experts, top {cfg['num_experts_per_tok']}), prompt {n_prompt} "
+                             f"(chunk {chunk}), {int(keep.sum())} of {len(keep)} positions")
+
+
+# Prompt seeds for which the reference side ALONE (reference_side on the CPU, no device) counts at least 6 of the 7 positions: the
+# two-thirds floor above stays a condition the comparison must meet, not a tolerance.  (All four count 7 of 7 there; of the seeds
+# tried before them 128 experts counted 4 to 6.)
+REAL_COUNT_SEEDS = {("128x8", 5): 355, ("128x8", 23): 573, ("60x4", 5): 305, ("60x4", 23): 323}
+
+
+@pytest.mark.parametrize("n_prompt", [5, 23])
+@pytest.mark.parametrize("which", ["128x8", "60x4"])
+def test_fused_engine_at_real_expert_counts_against_the_oracle_and_the_float64_truth(moe_model_128, moe_model_60, which, n_prompt):
+    """The oracle-and-truth test above at 128 experts top 8 (renormalised) and 60 experts top 4 (not): the router's 256-thread arg-max
+    across waves, eight or four expert rows per token through the grouped GEMVs, the weighted sum over more than two terms (where a sum
+    rounded after every add would be another operation).  5 prompt tokens prefill by GEMV rows, 23 by the tile GEMM."""
+    cfg, model = moe_model_128 if which == "128x8" else moe_model_60
+    assert (cfg["num_experts"], cfg["num_experts_per_tok"]) == tuple(int(v) for v in which.split("x"))
+    oracle_and_truth_case(cfg, model, n_prompt, 64, seed=REAL_COUNT_SEEDS[which, n_prompt])

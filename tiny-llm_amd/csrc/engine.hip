@@ -765,22 +765,49 @@ static void launch_logit_chain(tl_engine *e, const uint16_t *raw, int row0, int 
     if (f.stop) launch_stop(e, rows, slot0, pc);
 }
 
+// The router's launch over `rows` rows of router logits [rows, E]: ids / scores [rows, top_k] (engine_moe_mlp and tl_moe_route_rows).
+static void moe_route_launch(const uint16_t *logits, int rows, int E, int k, int norm, int32_t *ids, uint16_t *scores, hipStream_t st) {
+    hipLaunchKernelGGL(moe_route_kernel, dim3(rows), dim3(256), 0, st, logits, E, k, norm, ids, scores);
+}
+
+// The expert rows of a MoE MLP: rows x top_k of them, token-major, the token's experts in the order of its ids.  Side by side in one
+// block, in this order (tl_moe_experts_rows hands the block to its caller): gate, up, act [rows * k, I], y [rows * k, D].
+struct MoeExpertRows {
+    uint16_t *gate, *up, *act, *y;
+};
+inline size_t moe_expert_rows_bytes(int rows, int k, int D, int I) { return (size_t)rows * k * (3 * (size_t)I + D) * 2; }
+inline MoeExpertRows moe_expert_rows_at(void *base, int rows, int k, int I) {
+    uint16_t *p = (uint16_t *)base;
+    const size_t n = (size_t)rows * k * I;
+    return {p, p + n, p + 2 * n, p + 3 * n};
+}
+
+// Everything of a MoE MLP behind the router, five launches (engine_moe_mlp and tl_moe_experts_rows): gathered gate and up GEMVs (an
+// expert per expert row, the activation row of its token), SiLU x up, gathered down GEMV, weighted sum + residual.
+static int moe_experts_launch(const tl_moe_weights &m, const uint16_t *xn, const uint16_t *h, const int32_t *ids, const uint16_t *scores,
+                              const MoeExpertRows &w, uint16_t *out, int rows, int D, hipStream_t st) {
+    const int E = m.num_experts, k = m.experts_per_token, I = m.intermediate_size;
+    const int er = rows * k;  // expert rows: token-major, the token's top_k experts in descending probability
+    TL_TRY(gather_qmv_bf16(m.gate_scales_dev, m.gate_biases_dev, xn, m.gate_dev, ids, w.gate, er, D, I, E, k, st));
+    TL_TRY(gather_qmv_bf16(m.up_scales_dev, m.up_biases_dev, xn, m.up_dev, ids, w.up, er, D, I, E, k, st));
+    const long n8 = (long)er * I / 8;
+    hipLaunchKernelGGL(moe_silu_mul_kernel, dim3(ceil_div(n8, 256)), dim3(256), 0, st, w.gate, w.up, w.act, n8);
+    TL_TRY(gather_qmv_bf16(m.down_scales_dev, m.down_biases_dev, w.act, m.down_dev, ids, w.y, er, I, D, E, 1, st));
+    hipLaunchKernelGGL(moe_combine_kernel, dim3(rows), dim3(256), 0, st, w.y, scores, h, out, D, k);
+    return TL_OK;
+}
+
 // The MLP of a Qwen3-MoE layer over `rows` activation rows: xn = RMSNorm(h) is given; out = h + sum_j score_j * expert_j(xn)
 // (reference: moe.py:69-89 inside qwen3_week3.py:204-205).  Every launch reads device-resident ids: graph-capturable.
 static int engine_moe_mlp(tl_engine *e, int l, const uint16_t *xn, const uint16_t *h, uint16_t *out, int rows, ProfCtx *pc) {
     const tl_moe_weights &m = e->moe[l];
-    const int D = e->cfg.hidden_size, E = m.num_experts, k = m.experts_per_token, I = m.intermediate_size;
+    const int k = m.experts_per_token;
     TL_REQUIRE(e->moe_ws && rows <= e->rows_cap && (long)rows * k <= 65535, "engine: MoE workspace missing or too many expert rows");
     // router logits [rows, E] through the reference-semantics matmul (quantized_linear of the router, moe.py:44)
     TL_TRY(engine_qmm(e->lin, m.router, xn, e->moe_logits, rows));
-    hipLaunchKernelGGL(moe_route_kernel, dim3(rows), dim3(256), 0, e->stream, e->moe_logits, E, k, m.norm_topk_prob, e->moe_ids, e->moe_scores);
-    const int er = rows * k;  // expert rows: token-major, the token's top_k experts in descending probability
-    TL_TRY(gather_qmv_bf16(m.gate_scales_dev, m.gate_biases_dev, xn, m.gate_dev, e->moe_ids, e->moe_gate, er, D, I, E, k, e->stream));
-    TL_TRY(gather_qmv_bf16(m.up_scales_dev, m.up_biases_dev, xn, m.up_dev, e->moe_ids, e->moe_up, er, D, I, E, k, e->stream));
-    const long n8 = (long)er * I / 8;
-    hipLaunchKernelGGL(moe_silu_mul_kernel, dim3(ceil_div(n8, 256)), dim3(256), 0, e->stream, e->moe_gate, e->moe_up, e->moe_act, n8);
-    TL_TRY(gather_qmv_bf16(m.down_scales_dev, m.down_biases_dev, e->moe_act, m.down_dev, e->moe_ids, e->moe_y, er, I, D, E, 1, e->stream));
-    hipLaunchKernelGGL(moe_combine_kernel, dim3(rows), dim3(256), 0, e->stream, e->moe_y, e->moe_scores, h, out, D, k);
+    moe_route_launch(e->moe_logits, rows, m.num_experts, k, m.norm_topk_prob, e->moe_ids, e->moe_scores, e->stream);
+    TL_TRY(moe_experts_launch(m, xn, h, e->moe_ids, e->moe_scores, MoeExpertRows{e->moe_gate, e->moe_up, e->moe_act, e->moe_y}, out, rows,
+                              e->cfg.hidden_size, e->stream));
     (void)pc;  // the MoE launches carry no in-kernel stamps: tl_engine_profile_step leaves them out of its kinds
     TL_CHECK_LAUNCH("engine MoE layer");
     return TL_OK;
@@ -2421,6 +2448,46 @@ extern "C" int tl_pool_rows(const void *rows_dev, int hidden, int n_seqs, const 
                             int pooling, float *sums_dev, int normalize, int dim, float *out_dev, void *stream) {
     return pool_rows((const uint16_t *)rows_dev, hidden, n_seqs, row0, len, finish, prior, nullptr, pooling, sums_dev, normalize, dim, out_dev,
                      (hipStream_t)stream);
+}
+
+// ---- the MoE kernels over caller rows (include/tinyllm_engine.h, tl_moe_route_rows / tl_moe_experts_rows) ----------------------------
+extern "C" int tl_moe_route_rows(const void *logits_dev, int rows, int num_experts, int top_k, int norm_topk_prob, int32_t *ids_dev,
+                                 void *scores_dev, void *stream) {
+    TL_REQUIRE(logits_dev && ids_dev && scores_dev, "moe_route_rows: null argument");
+    TL_REQUIRE(rows >= 1, "moe_route_rows: rows must be positive");
+    TL_REQUIRE(num_experts > 0 && num_experts <= 1024 && top_k > 0 && top_k <= 16 && top_k <= num_experts,
+               "moe_route_rows: need 1 <= top_k <= min(16, num_experts) and num_experts <= 1024");
+    moe_route_launch((const uint16_t *)logits_dev, rows, num_experts, top_k, norm_topk_prob != 0, ids_dev, (uint16_t *)scores_dev,
+                     (hipStream_t)stream);
+    TL_CHECK_LAUNCH("moe_route_rows");
+    return TL_OK;
+}
+
+extern "C" size_t tl_moe_experts_workspace_bytes(int rows, int top_k, int hidden, int intermediate) {
+    if (rows < 1 || top_k < 1 || hidden < 1 || intermediate < 1) return 0;
+    return moe_expert_rows_bytes(rows, top_k, hidden, intermediate);
+}
+
+extern "C" int tl_moe_experts_rows(const void *xn_dev, const void *h_dev, const int32_t *ids_dev, const void *scores_dev, const tl_moe_weights *w,
+                                   int rows, int hidden, void *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    TL_REQUIRE(xn_dev && h_dev && ids_dev && scores_dev && w && out_dev && workspace_dev, "moe_experts_rows: null argument");
+    TL_REQUIRE(w->num_experts > 0 && w->num_experts <= 1024 && w->experts_per_token > 0 && w->experts_per_token <= 16 &&
+                   w->experts_per_token <= w->num_experts,
+               "moe_experts_rows: need 1 <= experts_per_token <= min(16, num_experts) and num_experts <= 1024");
+    TL_REQUIRE(w->intermediate_size > 0 && w->intermediate_size % 128 == 0, "moe_experts_rows: intermediate_size must be a positive multiple of 128");
+    TL_REQUIRE(hidden > 0 && hidden % 128 == 0, "moe_experts_rows: hidden must be a positive multiple of 128");
+    TL_REQUIRE(w->gate_dev && w->up_dev && w->down_dev && w->gate_scales_dev && w->gate_biases_dev && w->up_scales_dev && w->up_biases_dev &&
+                   w->down_scales_dev && w->down_biases_dev,
+               "moe_experts_rows: null expert tensor");
+    TL_REQUIRE(rows >= 1 && (long)rows * w->experts_per_token <= 65535, "moe_experts_rows: rows x experts_per_token must be 1 .. 65535 (one grouped launch)");
+    TL_REQUIRE(workspace_bytes >= moe_expert_rows_bytes(rows, w->experts_per_token, hidden, w->intermediate_size),
+               "moe_experts_rows: the workspace is smaller than tl_moe_experts_workspace_bytes");
+    TL_REQUIRE(((uintptr_t)xn_dev | (uintptr_t)h_dev | (uintptr_t)out_dev | (uintptr_t)workspace_dev) % 16 == 0, "moe_experts_rows: rows must be 16-byte aligned");
+    TL_TRY(moe_experts_launch(*w, (const uint16_t *)xn_dev, (const uint16_t *)h_dev, ids_dev, (const uint16_t *)scores_dev,
+                              moe_expert_rows_at(workspace_dev, rows, w->experts_per_token, w->intermediate_size), (uint16_t *)out_dev, rows, hidden,
+                              (hipStream_t)stream));
+    TL_CHECK_LAUNCH("moe_experts_rows");
+    return TL_OK;
 }
 
 // the paged attention operator over layer l's pages, by the engine's page format

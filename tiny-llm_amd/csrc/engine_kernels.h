@@ -1075,7 +1075,10 @@ static __global__ __launch_bounds__(256) void moe_route_kernel(const uint16_t *_
     if (lane == 0) red[wave] = sum;
     __syncthreads();
     sum = (red[0] + red[1]) + (red[2] + red[3]);
-    for (int i = tid; i < E; i += 256) probs[i] = BF16::from_float(expf(BF16::to_float(lr[i]) - mx) / sum);
+    for (int i = tid; i < E; i += 256) {
+        const uint16_t p = BF16::from_float(expf(BF16::to_float(lr[i]) - mx) / sum);
+        probs[i] = p == 0xffffu ? (uint16_t)0x7fc0u : p;  // 0xffff marks a picked expert below: a NaN that arrives with that pattern stays in the pool
+    }
     __syncthreads();
     for (int j = 0; j < top_k; ++j) {  // top_k rounds of a workgroup-wide arg-max; a picked expert leaves the pool
         float best = -1.f;

@@ -335,6 +335,10 @@ _SIGNATURES.update({
     "tl_engine_embed": (_c_int, [_c_void_p, _c_int, _P(ctypes.c_int32), _c_int, _c_int, _c_int, _c_int, _c_int, _P(_c_float)]),
     "tl_pool_rows": (_c_int, [_c_void_p, _c_int, _c_int, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _c_int, _c_void_p,
                               _c_int, _c_int, _c_void_p, _c_void_p]),
+    "tl_moe_route_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "tl_moe_experts_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
+    "tl_moe_experts_rows": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _P(TlMoeWeights), _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t,
+                                     _c_void_p]),
     "tl_engine_lora_load": (_c_int, [_c_void_p, _P(TlLoraLayer), _c_int, _c_float, _P(_c_int)]),
     "tl_engine_lora_unload": (_c_int, [_c_void_p, _c_int]),
     "tl_engine_set_lora": (_c_int, [_c_void_p, _c_int, _c_int]),
@@ -1282,6 +1286,50 @@ def beam_rows(logits: torch.Tensor, scores, n_cand: int) -> list[tuple[int, int,
     words = out.cpu()
     ints, floats = words.view(-1, 4), words.view(torch.float32).view(-1, 4)
     return [(int(ints[i, 0]), int(ints[i, 1]), float(floats[i, 2]), float(floats[i, 3])) for i in range(n_cand)]
+
+
+def moe_route_rows(logits: torch.Tensor, top_k: int, norm_topk_prob: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    """The decode engine's MoE router (tl_moe_route_rows) over rows of bf16 router logits [rows, experts]: (ids [rows, top_k] int32,
+    scores [rows, top_k] bf16), descending probability, equal probabilities the lower expert first.  Stream ordered."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("moe_route_rows takes a [rows, experts] bf16 tensor on the GPU")
+    logits = logits.contiguous()
+    rows, dev = logits.shape[0], logits.device
+    k = max(int(top_k), 0)
+    ids = torch.empty((rows, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((rows, k), dtype=torch.bfloat16, device=dev)
+    check(_lib.tl_moe_route_rows(logits.data_ptr(), rows, logits.shape[1], int(top_k), int(bool(norm_topk_prob)), ids.data_ptr(), scores.data_ptr(),
+                                 _stream()))
+    return ids, scores
+
+
+def moe_experts_rows(xn: torch.Tensor, h: torch.Tensor, ids: torch.Tensor, scores: torch.Tensor, gate, up, down) -> tuple[torch.Tensor, dict]:
+    """Everything of the engine's MoE MLP behind the router (tl_moe_experts_rows) over bf16 rows ``xn`` / ``h`` [rows, hidden] with the
+    caller's ``ids`` [rows, top_k] int32 and ``scores`` [rows, top_k] bf16.  ``gate`` / ``up`` / ``down``: (weight [E, out, in/8] int32 words,
+    scales, biases [E, out, in/128] bf16) of the stacked experts.  Returns (out [rows, hidden] bf16, the stages as the call's workspace
+    holds them: {"gate", "up", "act": [rows * top_k, I], "y": [rows * top_k, hidden]}).  Stream ordered."""
+    for t in (xn, h, scores, *gate[1:], *up[1:], *down[1:]):
+        if t.dtype != torch.bfloat16 or not t.is_cuda:
+            raise ValueError("moe_experts_rows takes bf16 tensors on the GPU")
+    if ids.dtype != torch.int32 or not ids.is_cuda or ids.dim() != 2 or ids.shape != scores.shape or xn.shape != h.shape or xn.dim() != 2:
+        raise ValueError("moe_experts_rows: xn / h [rows, hidden], ids (int32) / scores [rows, top_k]")
+    xn, h, ids, scores = xn.contiguous(), h.contiguous(), ids.contiguous(), scores.contiguous()
+    gate, up, down = (tuple(t.contiguous() for t in w) for w in (gate, up, down))
+    (rows, hidden), k, dev = xn.shape, ids.shape[1], xn.device
+    n_experts, inter = gate[0].shape[0], gate[0].shape[1]
+    if ids.shape[0] != rows or gate[0].shape[2] * 8 != hidden or up[0].shape != gate[0].shape or down[0].shape != (n_experts, hidden, inter // 8):
+        raise ValueError("moe_experts_rows: the expert tensors do not fit the rows")
+    w = TlMoeWeights(TlW4(), gate[0].data_ptr(), up[0].data_ptr(), down[0].data_ptr(), gate[1].data_ptr(), gate[2].data_ptr(), up[1].data_ptr(),
+                     up[2].data_ptr(), down[1].data_ptr(), down[2].data_ptr(), n_experts, k, inter, 0)
+    nbytes = _lib.tl_moe_experts_workspace_bytes(rows, k, hidden, inter)
+    ws = torch.empty(max(nbytes, 16) // 2, dtype=torch.bfloat16, device=dev)
+    out = torch.empty_like(xn)
+    check(_lib.tl_moe_experts_rows(xn.data_ptr(), h.data_ptr(), ids.data_ptr(), scores.data_ptr(), ctypes.byref(w), rows, hidden, out.data_ptr(),
+                                   ws.data_ptr(), nbytes, _stream()))
+    n = rows * k * inter
+    stages = {"gate": ws[:n].view(rows * k, inter), "up": ws[n:2 * n].view(rows * k, inter), "act": ws[2 * n:3 * n].view(rows * k, inter),
+              "y": ws[3 * n:3 * n + rows * k * hidden].view(rows * k, hidden)}
+    return out, stages
 
 
 POOL_LAST, POOL_MEAN = 0, 1  # TL_POOL_LAST / TL_POOL_MEAN

@@ -29,10 +29,14 @@ def grouped_expert_linear(x: torch.Tensor, w_experts: QuantizedWeights, expert_i
 
 def route_topk(x: torch.Tensor, w_router: QuantizedWeights, top_k: int, norm_topk_prob: bool = False):
     """Router: softmax over all experts in fp32, the top_k experts of every token and their probabilities (renormalised over
-    the selected experts when norm_topk_prob).  Returns (probs [..., E], expert_ids [..., top_k], scores [..., top_k])."""
+    the selected experts when norm_topk_prob).  Descending probability, equal probabilities the lower expert index first (a stable
+    sort: the engine's router and the oracle order them so; the reference's argpartition leaves the order open).
+    Returns (probs [..., E], expert_ids [..., top_k], scores [..., top_k])."""
     logits = quantized_linear(x, w_router)
     probs = torch.softmax(logits.to(torch.float32), dim=-1).to(logits.dtype)
-    scores, expert_ids = torch.topk(probs, top_k, dim=-1)
+    order = torch.sort(probs, dim=-1, descending=True, stable=True).indices
+    expert_ids = order[..., :top_k]
+    scores = torch.take_along_dim(probs, expert_ids, dim=-1)
     if norm_topk_prob:
         scores = scores / scores.sum(dim=-1, keepdim=True)
     return probs, expert_ids, scores
