@@ -131,6 +131,15 @@ int tl_engine_kv_format(const tl_engine *e);
  * MLP runs as the reference's op sequence inside the captured step: RMSNorm, router GEMV, route kernel, gathered gate and up
  * GEMVs (one launch each, an expert per row), SiLU x up, gathered down GEMV, weighted sum + residual. */
 int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_weights *w);
+/* The grouped-expert route for the experts of MoE layers (tl_moe_experts_rows_grouped) in eager passes -- prefill, packed prefill,
+ * score, embed, batched verification -- over at least min_rows activation rows; 0 (the default): never, every launch is the GEMV
+ * route's.  The decode step always keeps the GEMV route: its launches, plans and captured graphs do not depend on this setting.
+ * Before the first prefill / decode, in either order with tl_engine_set_moe_layer; min_rows < 0 is refused.  With the route on the
+ * expert words of every MoE layer must be 16-byte aligned (refused by whichever of the two calls sees both).  The sort's tables live
+ * in an allocation of their own, counted in stats.workspace_bytes.  tl_engine_moe_grouped_state: the setting and the number of MoE
+ * MLPs that took the route so far (either pointer may be null). */
+int tl_engine_set_moe_grouped(tl_engine *e, int min_rows);
+int tl_engine_moe_grouped_state(const tl_engine *e, int *min_rows, long *grouped_calls);
 /* Test / lab hook: switch a route that has an A/B twin, per engine, before its first prefill / decode (an error afterwards: captured
  * steps hold the routes they were captured with).  value 0 = off, anything else = on.  Options (defaults in brackets):
  *   "qmm3" [1] rows > 8 of a decode step on the K-sliced skinny matmul (0: the prefill GEMM's op sequence);  "qmm6" [1] the
@@ -1222,6 +1231,23 @@ int tl_moe_route_rows(const void *logits_dev, int rows, int num_experts, int top
 size_t tl_moe_experts_workspace_bytes(int rows, int top_k, int hidden, int intermediate);
 int tl_moe_experts_rows(const void *xn_dev, const void *h_dev, const int32_t *ids_dev, const void *scores_dev, const tl_moe_weights *w, int rows,
                         int hidden, void *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* The same stage on the grouped-expert route, four launches: the rows * top_k expert rows are sorted by expert on the device (one
+ * workgroup, a stable counting sort without atomics; ids are clamped to [0, num_experts - 1] as the GEMV route clamps them), gate | up
+ * and down run as W4 x bf16 MFMA tile GEMMs over tiles of at most tl_moe_grouped_tile_rows() rows that share an expert -- an expert is
+ * read once per tile of its rows, not once per row --, then the weighted sum + residual of tl_moe_experts_rows.  Arithmetic: the tile
+ * GEMM's (weights dequantised and rounded to bf16, fp32 accumulation on the matrix unit, one cast per output); gate and up rows stay in
+ * registers, act = bf16(bf16(silu(bf16 gate)) * bf16 up).  Same arguments and limits as tl_moe_experts_rows.  workspace_dev, front to
+ * back, every piece padded to 16 bytes: act [rows * top_k, I] bf16 and y [rows * top_k, hidden] bf16 (token-major, as above),
+ * perm [rows * top_k] int32 (sorted position -> expert row token * top_k + j), offsets [num_experts + 1] int32 (exclusive prefix of the
+ * per-expert counts), the tile table [1 + T] x 4 int32 with T = ceil(rows * top_k / tile_rows) + min(num_experts, rows * top_k): entry 0
+ * {n_tiles, 0, 0, 0}, entry 1 + t {expert, first sorted row, row count, 0}.  tl_moe_grouped_workspace_bytes gives the size (0 for sizes
+ * that are not positive or rows * top_k > 65,535).  gate_dev / up_dev / down_dev must be 16-byte aligned as well (a lane loads four
+ * packed words at once).  Stream ordered, no host read, no synchronisation; the same inputs give the same bytes. */
+int tl_moe_grouped_tile_rows(void);
+size_t tl_moe_grouped_workspace_bytes(int rows, int top_k, int hidden, int intermediate, int num_experts);
+int tl_moe_experts_rows_grouped(const void *xn_dev, const void *h_dev, const int32_t *ids_dev, const void *scores_dev, const tl_moe_weights *w,
+                                int rows, int hidden, void *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* The truncation routine of tl_engine_set_truncation / tl_engine_set_mirostat over caller rows: logits [rows, vocab] bf16 (vocab <=
  * 524,288), per-row device arrays of temperature, min_p, typical_p and mu (NaN = no Mirostat; a Mirostat row ignores min_p and

@@ -29,6 +29,7 @@
 #include "kv_swap.h"
 #include "pool.h"
 #include "lora.h"
+#include "moe_grouped.h"  // the grouped-expert route's sizes and launches (its kernels: moe_grouped.hip)
 #include "slot_settings.h"
 #include "slot_table.h"
 #include "stop.h"
@@ -267,6 +268,12 @@ struct tl_engine {
     size_t moe_ws_bytes = 0;
     uint16_t *moe_logits = nullptr, *moe_scores = nullptr, *moe_gate = nullptr, *moe_up = nullptr, *moe_act = nullptr, *moe_y = nullptr;
     int32_t *moe_ids = nullptr;
+    // the grouped-expert route of eager passes (tl_engine_set_moe_grouped; moe_grouped.h): off at 0; act / y are moe_act / moe_y
+    int moe_grouped_min = 0;
+    long moe_grouped_calls = 0;
+    DeviceBlock moe_grouped_ws;  // perm, offsets, tile table
+    size_t moe_grouped_bytes = 0;
+    MoeGroupedRows moe_grouped{};
     bool is_moe(int l) const { return l < (int)moe.size() && moe[l].num_experts > 0; }
     DeviceBlock rope_table_mem, rope_cur_mem;
     float2 *rope_table = nullptr, *rope_cur = nullptr;
@@ -797,17 +804,37 @@ static int moe_experts_launch(const tl_moe_weights &m, const uint16_t *xn, const
     return TL_OK;
 }
 
+// The same behind the router on the grouped-expert route, four launches (engine_moe_mlp and tl_moe_experts_rows_grouped): the sort by
+// expert, gate | up with the SwiGLU epilogue and down as tile GEMMs over rows that share an expert (moe_grouped.h), the GEMV route's
+// weighted sum + residual over the same token-major y.
+static int moe_experts_grouped_launch(const tl_moe_weights &m, const uint16_t *xn, const uint16_t *h, const int32_t *ids, const uint16_t *scores,
+                                      const MoeGroupedRows &w, uint16_t *out, int rows, int D, hipStream_t st) {
+    TL_TRY(moe_grouped_launch(m, xn, ids, w, rows, D, st));
+    hipLaunchKernelGGL(moe_combine_kernel, dim3(rows), dim3(256), 0, st, w.y, scores, h, out, D, m.experts_per_token);
+    return TL_OK;
+}
+
 // The MLP of a Qwen3-MoE layer over `rows` activation rows: xn = RMSNorm(h) is given; out = h + sum_j score_j * expert_j(xn)
 // (reference: moe.py:69-89 inside qwen3_week3.py:204-205).  Every launch reads device-resident ids: graph-capturable.
-static int engine_moe_mlp(tl_engine *e, int l, const uint16_t *xn, const uint16_t *h, uint16_t *out, int rows, ProfCtx *pc) {
+// eager_pass: the caller is a prefill / score / embed / verify pass, which may take the grouped-expert route (tl_engine_set_moe_grouped);
+// the decode step never does.
+static int engine_moe_mlp(tl_engine *e, int l, const uint16_t *xn, const uint16_t *h, uint16_t *out, int rows, ProfCtx *pc, bool eager_pass) {
     const tl_moe_weights &m = e->moe[l];
     const int k = m.experts_per_token;
     TL_REQUIRE(e->moe_ws && rows <= e->rows_cap && (long)rows * k <= 65535, "engine: MoE workspace missing or too many expert rows");
     // router logits [rows, E] through the reference-semantics matmul (quantized_linear of the router, moe.py:44)
     TL_TRY(engine_qmm(e->lin, m.router, xn, e->moe_logits, rows));
     moe_route_launch(e->moe_logits, rows, m.num_experts, k, m.norm_topk_prob, e->moe_ids, e->moe_scores, e->stream);
-    TL_TRY(moe_experts_launch(m, xn, h, e->moe_ids, e->moe_scores, MoeExpertRows{e->moe_gate, e->moe_up, e->moe_act, e->moe_y}, out, rows,
-                              e->cfg.hidden_size, e->stream));
+    if (eager_pass && e->moe_grouped_min > 0 && rows >= e->moe_grouped_min) {
+        TL_REQUIRE((bool)e->moe_grouped_ws, "engine: the grouped-expert route has no workspace");
+        MoeGroupedRows w = e->moe_grouped;
+        w.act = e->moe_act, w.y = e->moe_y;
+        TL_TRY(moe_experts_grouped_launch(m, xn, h, e->moe_ids, e->moe_scores, w, out, rows, e->cfg.hidden_size, e->stream));
+        e->moe_grouped_calls++;
+    } else {
+        TL_TRY(moe_experts_launch(m, xn, h, e->moe_ids, e->moe_scores, MoeExpertRows{e->moe_gate, e->moe_up, e->moe_act, e->moe_y}, out, rows,
+                                  e->cfg.hidden_size, e->stream));
+    }
     (void)pc;  // the MoE launches carry no in-kernel stamps: tl_engine_profile_step leaves them out of its kinds
     TL_CHECK_LAUNCH("engine MoE layer");
     return TL_OK;
@@ -912,7 +939,7 @@ static int enqueue_step(tl_engine *e, int batch, const AttnPlan &sp, const StepF
         if (e->is_moe(l)) {  // wo + residual, then the MoE MLP as its own launches (no producer-side sums for the next layer)
             TL_TRY(engine_linear(ctx, po, pc));
             TL_TRY(tl_rms_norm(b.h, w.post_norm_dev, b.xn, batch, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
-            TL_TRY(engine_moe_mlp(e, l, b.xn, b.h, b.x_out, batch, pc));
+            TL_TRY(engine_moe_mlp(e, l, b.xn, b.h, b.x_out, batch, pc, false));
             x_ss = 0;
             continue;
         }
@@ -1348,6 +1375,45 @@ extern "C" int tl_engine_create_kv(const tl_engine_config *cfg, const tl_layer_w
     return TL_OK;
 }
 
+// the tile GEMMs load a lane's four packed words as 16 bytes: every expert starts a multiple of 64 bytes behind its tensor's first word
+static bool moe_grouped_words_aligned(const tl_moe_weights &w) {
+    return ((uintptr_t)w.gate_dev | (uintptr_t)w.up_dev | (uintptr_t)w.down_dev) % 16 == 0;
+}
+
+// The grouped route's own block (perm, offsets, tile table), sized for rows_cap rows of the widest MoE layer seen so far: (re)made
+// when the route is on and the sizes are known, from either of the two calls that can make that true.
+static int moe_grouped_alloc(tl_engine *e) {
+    if (e->moe_grouped_min <= 0 || e->moe_k_max <= 0) return TL_OK;
+    const size_t bytes = moe_grouped_aux_bytes(e->rows_cap * e->moe_k_max, e->moe_e_max);
+    if (bytes == e->moe_grouped_bytes) return TL_OK;
+    TL_HIP(hipStreamSynchronize(e->stream));
+    e->stats.workspace_bytes -= e->moe_grouped_bytes;
+    e->moe_grouped_bytes = 0;
+    TL_TRY(e->moe_grouped_ws.alloc(bytes, "engine_set_moe_grouped: no device memory for the sort's tables"));
+    e->moe_grouped_bytes = bytes;
+    e->stats.workspace_bytes += bytes;
+    moe_grouped_aux_at(e->moe_grouped_ws.at(), e->rows_cap * e->moe_k_max, e->moe_e_max, &e->moe_grouped);
+    return TL_OK;
+}
+
+extern "C" int tl_engine_set_moe_grouped(tl_engine *e, int min_rows) {
+    TL_REQUIRE(min_rows >= 0, "engine_set_moe_grouped: min_rows must be >= 0 (0: never)");
+    TL_REQUIRE(e, "engine_set_moe_grouped: null argument");
+    TL_REQUIRE(e->plans.empty() && e->stats.decode_steps == 0 && e->stats.prefill_tokens == 0,
+               "engine_set_moe_grouped: call it before the first prefill / decode");
+    for (int l = 0; min_rows > 0 && l < e->cfg.num_layers; ++l)
+        TL_REQUIRE(!e->is_moe(l) || moe_grouped_words_aligned(e->moe[l]), "engine_set_moe_grouped: the expert words of a MoE layer are not 16-byte aligned");
+    e->moe_grouped_min = min_rows;
+    return moe_grouped_alloc(e);
+}
+
+extern "C" int tl_engine_moe_grouped_state(const tl_engine *e, int *min_rows, long *grouped_calls) {
+    TL_REQUIRE(e, "engine_moe_grouped_state: null argument");
+    if (min_rows) *min_rows = e->moe_grouped_min;
+    if (grouped_calls) *grouped_calls = e->moe_grouped_calls;
+    return TL_OK;
+}
+
 extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_weights *w) {
     TL_REQUIRE(e && w, "engine_set_moe_layer: null argument");
     const tl_engine_config &c = e->cfg;
@@ -1362,6 +1428,8 @@ extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_wei
     TL_REQUIRE(w->gate_dev && w->up_dev && w->down_dev && w->gate_scales_dev && w->gate_biases_dev && w->up_scales_dev &&
                    w->up_biases_dev && w->down_scales_dev && w->down_biases_dev,
                "engine_set_moe_layer: null expert tensor");
+    TL_REQUIRE(e->moe_grouped_min == 0 || moe_grouped_words_aligned(*w),
+               "engine_set_moe_layer: with the grouped-expert route on (tl_engine_set_moe_grouped) the expert words must be 16-byte aligned");
     TL_REQUIRE((long)e->rows_cap * w->experts_per_token <= 65535, "engine_set_moe_layer: max_prefill_rows x experts_per_token must stay below 65536 (one grouped launch)");
     // the router's matmul must fit the workspace sized at tl_engine_create (it does for every E <= the widest projection)
     for (int M : {1, 8, 9, e->rows_cap})
@@ -1383,7 +1451,8 @@ extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_wei
         e->moe_up = piece_at<uint16_t>(m, ml[MoeLayout::UP]), e->moe_act = piece_at<uint16_t>(m, ml[MoeLayout::ACT]);
         e->moe_y = piece_at<uint16_t>(m, ml[MoeLayout::Y]);
         e->moe_k_max = k, e->moe_e_max = E, e->moe_i_max = I;
-        e->stats.workspace_bytes = e->arena_bytes + e->tiled_bytes + e->moe_ws_bytes;
+        e->stats.workspace_bytes = e->arena_bytes + e->tiled_bytes + e->moe_ws_bytes + e->moe_grouped_bytes;
+        TL_TRY(moe_grouped_alloc(e));
     }
     e->moe[layer] = *w;
     // a model with a sparse layer never takes the per-layer decode buffers (enqueue_step: its steps stay on the shared buffers and the
@@ -2490,6 +2559,36 @@ extern "C" int tl_moe_experts_rows(const void *xn_dev, const void *h_dev, const 
     return TL_OK;
 }
 
+extern "C" int tl_moe_grouped_tile_rows(void) { return MOE_TM; }
+
+extern "C" size_t tl_moe_grouped_workspace_bytes(int rows, int top_k, int hidden, int intermediate, int num_experts) {
+    if (rows <= 0 || top_k <= 0 || hidden <= 0 || intermediate <= 0 || num_experts <= 0 || (long)rows * top_k > 65535) return 0;
+    return moe_grouped_rows_bytes(rows, top_k, hidden, intermediate, num_experts);
+}
+
+extern "C" int tl_moe_experts_rows_grouped(const void *xn_dev, const void *h_dev, const int32_t *ids_dev, const void *scores_dev, const tl_moe_weights *w,
+                                           int rows, int hidden, void *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    TL_REQUIRE(xn_dev && h_dev && ids_dev && scores_dev && w && out_dev && workspace_dev, "moe_experts_rows_grouped: null argument");
+    TL_REQUIRE(w->num_experts > 0 && w->num_experts <= 1024 && w->experts_per_token > 0 && w->experts_per_token <= 16 &&
+                   w->experts_per_token <= w->num_experts,
+               "moe_experts_rows_grouped: need 1 <= experts_per_token <= min(16, num_experts) and num_experts <= 1024");
+    TL_REQUIRE(w->intermediate_size > 0 && w->intermediate_size % 128 == 0, "moe_experts_rows_grouped: intermediate_size must be a positive multiple of 128");
+    TL_REQUIRE(hidden > 0 && hidden % 128 == 0, "moe_experts_rows_grouped: hidden must be a positive multiple of 128");
+    TL_REQUIRE(w->gate_dev && w->up_dev && w->down_dev && w->gate_scales_dev && w->gate_biases_dev && w->up_scales_dev &&
+                   w->up_biases_dev && w->down_scales_dev && w->down_biases_dev,
+               "moe_experts_rows_grouped: null expert tensor");
+    TL_REQUIRE(rows >= 1 && (long)rows * w->experts_per_token <= 65535, "moe_experts_rows_grouped: rows x experts_per_token must be 1 .. 65535");
+    TL_REQUIRE(workspace_bytes >= moe_grouped_rows_bytes(rows, w->experts_per_token, hidden, w->intermediate_size, w->num_experts),
+               "moe_experts_rows_grouped: the workspace is smaller than tl_moe_grouped_workspace_bytes");
+    TL_REQUIRE(((uintptr_t)xn_dev | (uintptr_t)h_dev | (uintptr_t)out_dev | (uintptr_t)workspace_dev) % 16 == 0, "moe_experts_rows_grouped: rows must be 16-byte aligned");
+    TL_REQUIRE(moe_grouped_words_aligned(*w), "moe_experts_rows_grouped: the expert words must be 16-byte aligned");
+    TL_TRY(moe_experts_grouped_launch(*w, (const uint16_t *)xn_dev, (const uint16_t *)h_dev, ids_dev, (const uint16_t *)scores_dev,
+                                      moe_grouped_rows_at(workspace_dev, rows, w->experts_per_token, hidden, w->intermediate_size, w->num_experts),
+                                      (uint16_t *)out_dev, rows, hidden, (hipStream_t)stream));
+    TL_CHECK_LAUNCH("moe_experts_rows_grouped");
+    return TL_OK;
+}
+
 // the paged attention operator over layer l's pages, by the engine's page format
 // ---- LoRA adapters (include/tinyllm_engine.h "LoRA adapters"; kernels lora.h) -----------------------------------------------------------
 extern "C" int tl_engine_lora_load(tl_engine *e, const tl_lora_layer *layers, int rank, float scale, int *adapter) {
@@ -2833,7 +2932,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
         TL_TRY(engine_gemm(e->lin, po, &h_normed));
         if (!h_normed) TL_TRY(tl_rms_norm(b.h, w.post_norm_dev, b.xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
         if (e->is_moe(l)) {
-            TL_TRY(engine_moe_mlp(e, l, b.xn, b.h, b.x_out, total, nullptr));
+            TL_TRY(engine_moe_mlp(e, l, b.xn, b.h, b.x_out, total, nullptr, true));
         } else {
             TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
             Proj pg = proj(w.wgu, b.xn, b.act, total);
@@ -3306,7 +3405,7 @@ static int verify_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const i
         if (e->is_moe(l)) {  // wo + residual, then the MoE MLP as its own launches (no producer-side sums for the next layer)
             TL_TRY(engine_linear(ctx, po));
             TL_TRY(tl_rms_norm(b.h, w.post_norm_dev, b.xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
-            TL_TRY(engine_moe_mlp(e, l, b.xn, b.h, b.x_out, total, nullptr));
+            TL_TRY(engine_moe_mlp(e, l, b.xn, b.h, b.x_out, total, nullptr, true));
             x_ss = 0;
             continue;
         }

@@ -5,6 +5,7 @@
 //   * otherwise                    -> qmm_vanilla_kernel (semantic definition)
 #include "common.h"
 #include "qmv.h"
+#include "qmm_frag.h"
 
 namespace tl {
 
@@ -61,39 +62,6 @@ __global__ __launch_bounds__(256) void qmm_vanilla_kernel(const uint16_t *__rest
 //   A operand (activations): staged once per workgroup into a double-buffered,
 //   XOR-swizzled LDS tile and read back with ds_read_b128.
 // ---------------------------------------------------------------------------
-template <typename TT>
-struct Mfma;
-template <>
-struct Mfma<BF16> {
-    __device__ __forceinline__ static f32x16 mma(const u32x4 &a, const u32x4 &b, const f32x16 &c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b),
-                                                       c, 0, 0, 0);
-    }
-};
-template <>
-struct Mfma<F16> {
-    __device__ __forceinline__ static f32x16 mma(const u32x4 &a, const u32x4 &b, const f32x16 &c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b),
-                                                      c, 0, 0, 0);
-    }
-};
-
-template <typename TT>
-__device__ __forceinline__ u32x4 dequant_word(uint32_t w, float s, float beta) {
-    // even nibbles as the bytes of one word, odd nibbles as the bytes of another: each of the 8 conversions is then a single
-    // v_cvt_f32_ubyteN (3 mask / shift instructions per word instead of 2 per nibble; the counters showed 11 VALU per MFMA)
-    uint32_t even = w & 0x0f0f0f0fu, odd = (w >> 4) & 0x0f0f0f0fu;
-    asm volatile("" : "+v"(even), "+v"(odd));  // or the optimiser folds the masks back into per-nibble shift + and
-    u32x4 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float lo = (float)((even >> (8 * e)) & 0xffu) * s + beta;
-        const float hi = (float)((odd >> (8 * e)) & 0xffu) * s + beta;
-        r[e] = TT::pack2(lo, hi);
-    }
-    return r;
-}
-
 #ifndef QMM_ABL
 #define QMM_ABL 0  // tools/lab/gemm_lab only: 1 = no dequant arithmetic, 2 = no MFMA, 4 = no activation re-staging, 8 = the next
                    // step's requests outside the branch (clamped step index: the last step requests itself again)

@@ -243,6 +243,8 @@ _SIGNATURES.update({
     "tl_decode_attention_fused_fp8": (_c_int, [_c_void_p] * 10 + [_c_int] * 6 + [_c_float, _c_float, _c_int, _c_void_p, _c_size_t,
                                                                   _c_void_p, _P(TlAttentionInfo)]),
     "tl_engine_set_moe_layer": (_c_int, [_c_void_p, _c_int, _P(TlMoeWeights)]),
+    "tl_engine_set_moe_grouped": (_c_int, [_c_void_p, _c_int]),
+    "tl_engine_moe_grouped_state": (_c_int, [_c_void_p, _P(_c_int), _P(ctypes.c_long)]),
     "tl_decode_gemv_plan": (_c_int, [_c_int, _c_int, _c_int, _P(_c_int)]),
     "tl_decode_batched_plan": (_c_int, [_c_int, _c_int, _c_int, _P(_c_int)]),
     "tl_decode_batched_variant_compiled": (_c_int, [_c_int, _c_int]),
@@ -337,6 +339,10 @@ _SIGNATURES.update({
                               _c_int, _c_int, _c_void_p, _c_void_p]),
     "tl_moe_route_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "tl_moe_experts_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
+    "tl_moe_grouped_tile_rows": (_c_int, []),
+    "tl_moe_grouped_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "tl_moe_experts_rows_grouped": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _P(TlMoeWeights), _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t,
+                                             _c_void_p]),
     "tl_moe_experts_rows": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _P(TlMoeWeights), _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t,
                                      _c_void_p]),
     "tl_engine_lora_load": (_c_int, [_c_void_p, _P(TlLoraLayer), _c_int, _c_float, _P(_c_int)]),
@@ -1329,6 +1335,37 @@ def moe_experts_rows(xn: torch.Tensor, h: torch.Tensor, ids: torch.Tensor, score
     n = rows * k * inter
     stages = {"gate": ws[:n].view(rows * k, inter), "up": ws[n:2 * n].view(rows * k, inter), "act": ws[2 * n:3 * n].view(rows * k, inter),
               "y": ws[3 * n:3 * n + rows * k * hidden].view(rows * k, hidden)}
+    return out, stages
+
+
+def moe_experts_rows_grouped(xn: torch.Tensor, h: torch.Tensor, ids: torch.Tensor, scores: torch.Tensor, gate, up, down) -> tuple[torch.Tensor, dict]:
+    """moe_experts_rows on the grouped-expert route (tl_moe_experts_rows_grouped): the expert rows sorted by expert on the device, gate | up
+    and down as MFMA tile GEMMs over rows that share an expert.  Same arguments.  Returns (out [rows, hidden] bf16, {"act": [rows * top_k, I],
+    "y": [rows * top_k, hidden] bf16, "perm": [rows * top_k], "offsets": [experts + 1] int32} as the call's workspace holds them)."""
+    for t in (xn, h, scores, *gate[1:], *up[1:], *down[1:]):
+        if t.dtype != torch.bfloat16 or not t.is_cuda:
+            raise ValueError("moe_experts_rows_grouped takes bf16 tensors on the GPU")
+    if ids.dtype != torch.int32 or not ids.is_cuda or ids.dim() != 2 or ids.shape != scores.shape or xn.shape != h.shape or xn.dim() != 2:
+        raise ValueError("moe_experts_rows_grouped: xn / h [rows, hidden], ids (int32) / scores [rows, top_k]")
+    xn, h, ids, scores = xn.contiguous(), h.contiguous(), ids.contiguous(), scores.contiguous()
+    gate, up, down = (tuple(t.contiguous() for t in w) for w in (gate, up, down))
+    (rows, hidden), k, dev = xn.shape, ids.shape[1], xn.device
+    n_experts, inter = gate[0].shape[0], gate[0].shape[1]
+    if ids.shape[0] != rows or gate[0].shape[2] * 8 != hidden or up[0].shape != gate[0].shape or down[0].shape != (n_experts, hidden, inter // 8):
+        raise ValueError("moe_experts_rows_grouped: the expert tensors do not fit the rows")
+    w = TlMoeWeights(TlW4(), gate[0].data_ptr(), up[0].data_ptr(), down[0].data_ptr(), gate[1].data_ptr(), gate[2].data_ptr(), up[1].data_ptr(),
+                     up[2].data_ptr(), down[1].data_ptr(), down[2].data_ptr(), n_experts, k, inter, 0)
+    nbytes = _lib.tl_moe_grouped_workspace_bytes(rows, k, hidden, inter, n_experts)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    out = torch.empty_like(xn)
+    check(_lib.tl_moe_experts_rows_grouped(xn.data_ptr(), h.data_ptr(), ids.data_ptr(), scores.data_ptr(), ctypes.byref(w), rows, hidden, out.data_ptr(),
+                                           ws.data_ptr(), nbytes, _stream()))
+    er, pad = rows * k, lambda b: (b + 15) // 16 * 16
+    a0, y0 = 0, er * inter * 2
+    p0 = y0 + er * hidden * 2
+    o0 = p0 + pad(er * 4)
+    stages = {"act": ws[a0:y0].view(torch.bfloat16).view(er, inter), "y": ws[y0:p0].view(torch.bfloat16).view(er, hidden),
+              "perm": ws[p0:p0 + er * 4].view(torch.int32), "offsets": ws[o0:o0 + (n_experts + 1) * 4].view(torch.int32)}
     return out, stages
 
 

@@ -64,8 +64,11 @@ class DecodeEngine:
 
     def __init__(self, mlx_model: Any, *, page_size: int = 128, num_pages: int = 512, max_batch: int = 1,
                  max_pages_per_seq: int | None = None, max_prefill_rows: int = 2048, options: dict | None = None,
-                 kv_format: str = "bf16", prefix_cache: bool | int = False, swap_pages: int = 0):
-        """``swap_pages``: room for that many KV pages in pinned host memory (tl_engine_swap_space): ``park`` moves a sequence's K / V
+                 kv_format: str = "bf16", prefix_cache: bool | int = False, swap_pages: int = 0, moe_grouped_rows: int = 0):
+        """``moe_grouped_rows``: MoE layers run their experts on the grouped-expert route (rows sorted by expert, MFMA tile GEMMs;
+        tl_engine_set_moe_grouped) in prefill, score, embed and verification passes over at least that many rows; 0 (the default):
+        never.  Decode steps always keep the per-row GEMV route.  ``moe_grouped_state()`` reports the setting and the count.
+        ``swap_pages``: room for that many KV pages in pinned host memory (tl_engine_swap_space): ``park`` moves a sequence's K / V
         there and frees its pages, ``unpark`` brings it back, and the serving loops preempt under page pressure instead of failing
         (tiny_llm_hip.preempt).  0 (the default): nothing is allocated and the loops are the programs they were.
         ``prefix_cache``: keep the K / V of full pages after their request is released and hand them to later requests that start
@@ -136,6 +139,9 @@ class DecodeEngine:
         opts.update(options or {})
         for name, value in opts.items():
             _ext.check(_lib.tl_engine_set_option(self._h, str(name).strip().encode(), int(value)))
+        if isinstance(moe_grouped_rows, bool) or not isinstance(moe_grouped_rows, int) or moe_grouped_rows < 0:
+            raise ValueError(f"moe_grouped_rows must be an int >= 0 (0: never), got {moe_grouped_rows!r}")
+        _ext.check(_lib.tl_engine_set_moe_grouped(self._h, moe_grouped_rows))
         for i, mlp in moe_layers.items():
             self._attach_moe(i, mlp, args)
         if isinstance(prefix_cache, bool):
@@ -171,6 +177,12 @@ class DecodeEngine:
                               u[1].data_ptr(), u[2].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), int(n_experts),
                               int(args.num_experts_per_tok), int(inter), int(bool(getattr(args, "norm_topk_prob", False))))
         _ext.check(_lib.tl_engine_set_moe_layer(self._h, layer, ctypes.byref(w)))
+
+    def moe_grouped_state(self) -> dict:
+        """{"min_rows": the ``moe_grouped_rows`` setting, "grouped_calls": MoE MLPs that took the grouped-expert route so far}."""
+        rows, calls = ctypes.c_int(), ctypes.c_long()
+        _ext.check(_lib.tl_engine_moe_grouped_state(self._h, ctypes.byref(rows), ctypes.byref(calls)))
+        return {"min_rows": rows.value, "grouped_calls": calls.value}
 
     @classmethod
     def from_model(cls, mlx_model: Any, **kwargs) -> "DecodeEngine":
