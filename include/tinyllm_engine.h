@@ -140,6 +140,15 @@ int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_weights *w);
  * MLPs that took the route so far (either pointer may be null). */
 int tl_engine_set_moe_grouped(tl_engine *e, int min_rows);
 int tl_engine_moe_grouped_state(const tl_engine *e, int *min_rows, long *grouped_calls);
+/* The decode-shaped route for the experts of MoE layers (tl_moe_experts_rows_decode) in decode steps -- captured or eager -- of at least
+ * min_rows rows; 0 (the default): never, every plan, launch and byte of a step is the GEMV route's.  Eager passes keep their routes
+ * whatever this says.  Before the first prefill / decode, in either order with tl_engine_set_moe_layer; min_rows < 0 is refused.  With
+ * the route on, max_batch must be at most 64 and every MoE layer within the route's limits (16-byte aligned expert words, at most 1,024
+ * experts, at most 16 per token, hidden and expert width multiples of 128): refused by whichever of the two calls sees both.  The route
+ * uses the MoE workspace's act and y rows: nothing is allocated.  tl_engine_moe_decode_state: the setting and the number of MoE MLPs
+ * that decode steps ran on the route so far, replays of captured steps included (either pointer may be null). */
+int tl_engine_set_moe_decode(tl_engine *e, int min_rows);
+int tl_engine_moe_decode_state(const tl_engine *e, int *min_rows, long *decode_calls);
 /* Test / lab hook: switch a route that has an A/B twin, per engine, before its first prefill / decode (an error afterwards: captured
  * steps hold the routes they were captured with).  value 0 = off, anything else = on.  Options (defaults in brackets):
  *   "qmm3" [1] rows > 8 of a decode step on the K-sliced skinny matmul (0: the prefill GEMM's op sequence);  "qmm6" [1] the
@@ -1248,6 +1257,27 @@ int tl_moe_grouped_tile_rows(void);
 size_t tl_moe_grouped_workspace_bytes(int rows, int top_k, int hidden, int intermediate, int num_experts);
 int tl_moe_experts_rows_grouped(const void *xn_dev, const void *h_dev, const int32_t *ids_dev, const void *scores_dev, const tl_moe_weights *w,
                                 int rows, int hidden, void *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* The same stage on the decode-shaped route, three launches, for 1 .. 64 rows (at most 1,024 expert rows): rows that name the same expert
+ * share ONE read of its gate, up and down weights.  No sort launch: every workgroup of gate | up and of down reads the ids (clamped to
+ * [0, num_experts - 1] as the other routes clamp them), takes the blockIdx.y-th expert named, in ascending order, and that expert's rows in
+ * ascending order; the grids are sized by min(rows * top_k, num_experts), nothing is read back, so a captured launch replays correctly over
+ * other ids.  Products on v_mfma_f32_16x16x32_bf16 with up to 16 of the expert's rows as the A operand, weights straight from the
+ * checkpoint layout; arithmetic: the GEMV's, per group of 128 columns acc += s * (q . x) + beta * sum(x) in fp32, one cast per output;
+ * gate and up rows stay in registers, act = bf16(bf16(silu(bf16 gate)) * bf16 up); then the weighted sum + residual of
+ * tl_moe_experts_rows.  Same arguments as tl_moe_experts_rows; limits: rows 1 .. 64, hidden and intermediate multiples of 128,
+ * num_experts <= 1,024, top_k <= 16, gate_dev / up_dev / down_dev 16-byte aligned -- anything else is refused, nothing is clamped.
+ * workspace_dev: act [rows * top_k, I] bf16, then y [rows * top_k, hidden] bf16, token-major; tl_moe_decode_workspace_bytes gives the size
+ * (0 for sizes the route does not take).  Stream ordered, no synchronisation; the same inputs give the same bytes.
+ * Host only, no device needed: tl_moe_decode_plan fills plan12 with {features per workgroup, waves along the reduction, groups per wave,
+ * grid x, grid y, threads} of gate | up, then of down, as the launch picks them for a device of `cus` compute units;
+ * tl_moe_decode_wave gives what wave `wave` of workgroup `block` (grid x) computes under such a stage over `groups` groups of 128
+ * columns: {first of its 16 features, first group, one past its last group} -- the function the kernels call. */
+size_t tl_moe_decode_workspace_bytes(int rows, int top_k, int hidden, int intermediate);
+int tl_moe_experts_rows_decode(const void *xn_dev, const void *h_dev, const int32_t *ids_dev, const void *scores_dev, const tl_moe_weights *w,
+                               int rows, int hidden, void *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int tl_moe_decode_plan(int rows, int top_k, int num_experts, int hidden, int intermediate, int cus, int *plan12);
+int tl_moe_decode_wave(int features, int wk, int per, int groups, int block, int wave, int *feature0_g0_g1);
 
 /* The truncation routine of tl_engine_set_truncation / tl_engine_set_mirostat over caller rows: logits [rows, vocab] bf16 (vocab <=
  * 524,288), per-row device arrays of temperature, min_p, typical_p and mu (NaN = no Mirostat; a Mirostat row ignores min_p and

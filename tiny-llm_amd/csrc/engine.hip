@@ -30,6 +30,7 @@
 #include "pool.h"
 #include "lora.h"
 #include "moe_grouped.h"  // the grouped-expert route's sizes and launches (its kernels: moe_grouped.hip)
+#include "moe_decode.h"   // the decode-shaped expert route's planner, sizes and launch (its kernels: moe_decode.hip)
 #include "slot_settings.h"
 #include "slot_table.h"
 #include "stop.h"
@@ -274,6 +275,9 @@ struct tl_engine {
     DeviceBlock moe_grouped_ws;  // perm, offsets, tile table
     size_t moe_grouped_bytes = 0;
     MoeGroupedRows moe_grouped{};
+    // the decode-shaped expert route of decode steps (tl_engine_set_moe_decode; moe_decode.h): off at 0; act / y are moe_act / moe_y
+    int moe_decode_min = 0;
+    long moe_decode_calls = 0;
     bool is_moe(int l) const { return l < (int)moe.size() && moe[l].num_experts > 0; }
     DeviceBlock rope_table_mem, rope_cur_mem;
     float2 *rope_table = nullptr, *rope_cur = nullptr;
@@ -814,10 +818,20 @@ static int moe_experts_grouped_launch(const tl_moe_weights &m, const uint16_t *x
     return TL_OK;
 }
 
+// The same behind the router on the decode-shaped route, three launches (engine_moe_mlp and tl_moe_experts_rows_decode): gate | up with
+// the SwiGLU epilogue and down over the rows of each named expert, one read of the expert for all of them (moe_decode.h), the GEMV
+// route's weighted sum + residual over the same token-major y.
+static int moe_experts_decode_launch(const tl_moe_weights &m, const uint16_t *xn, const uint16_t *h, const int32_t *ids, const uint16_t *scores,
+                                     uint16_t *act, uint16_t *y, uint16_t *out, int rows, int D, hipStream_t st) {
+    TL_TRY(moe_decode_launch(m, xn, ids, act, y, rows, D, qmm3_num_cus(), st));
+    hipLaunchKernelGGL(moe_combine_kernel, dim3(rows), dim3(256), 0, st, y, scores, h, out, D, m.experts_per_token);
+    return TL_OK;
+}
+
 // The MLP of a Qwen3-MoE layer over `rows` activation rows: xn = RMSNorm(h) is given; out = h + sum_j score_j * expert_j(xn)
 // (reference: moe.py:69-89 inside qwen3_week3.py:204-205).  Every launch reads device-resident ids: graph-capturable.
 // eager_pass: the caller is a prefill / score / embed / verify pass, which may take the grouped-expert route (tl_engine_set_moe_grouped);
-// the decode step never does.
+// a decode step (eager_pass false) takes the decode-shaped route from tl_engine_set_moe_decode's row count upward, never the grouped one.
 static int engine_moe_mlp(tl_engine *e, int l, const uint16_t *xn, const uint16_t *h, uint16_t *out, int rows, ProfCtx *pc, bool eager_pass) {
     const tl_moe_weights &m = e->moe[l];
     const int k = m.experts_per_token;
@@ -831,6 +845,9 @@ static int engine_moe_mlp(tl_engine *e, int l, const uint16_t *xn, const uint16_
         w.act = e->moe_act, w.y = e->moe_y;
         TL_TRY(moe_experts_grouped_launch(m, xn, h, e->moe_ids, e->moe_scores, w, out, rows, e->cfg.hidden_size, e->stream));
         e->moe_grouped_calls++;
+    } else if (!eager_pass && e->moe_decode_min > 0 && rows >= e->moe_decode_min) {
+        TL_REQUIRE(moe_decode_takes(rows, k, e->cfg.hidden_size, m.intermediate_size), "engine: a decode step outside the decode-shaped expert route's limits");
+        TL_TRY(moe_experts_decode_launch(m, xn, h, e->moe_ids, e->moe_scores, e->moe_act, e->moe_y, out, rows, e->cfg.hidden_size, e->stream));
     } else {
         TL_TRY(moe_experts_launch(m, xn, h, e->moe_ids, e->moe_scores, MoeExpertRows{e->moe_gate, e->moe_up, e->moe_act, e->moe_y}, out, rows,
                                   e->cfg.hidden_size, e->stream));
@@ -1414,6 +1431,32 @@ extern "C" int tl_engine_moe_grouped_state(const tl_engine *e, int *min_rows, lo
     return TL_OK;
 }
 
+// what the decode-shaped route asks of a layer's experts beyond tl_engine_set_moe_layer's own checks
+static bool moe_decode_layer_ok(const tl_engine *e, const tl_moe_weights &w) {
+    return moe_grouped_words_aligned(w) && w.num_experts <= MOE_DEC_MAX_E && w.experts_per_token <= MOE_DEC_MAX_K &&
+           e->cfg.hidden_size % 128 == 0 && w.intermediate_size % 128 == 0;
+}
+
+extern "C" int tl_engine_set_moe_decode(tl_engine *e, int min_rows) {
+    TL_REQUIRE(min_rows >= 0, "engine_set_moe_decode: min_rows must be >= 0 (0: never)");
+    TL_REQUIRE(e, "engine_set_moe_decode: null argument");
+    TL_REQUIRE(e->plans.empty() && e->stats.decode_steps == 0 && e->stats.prefill_tokens == 0,
+               "engine_set_moe_decode: call it before the first prefill / decode");
+    TL_REQUIRE(min_rows == 0 || e->cfg.max_batch <= MOE_DEC_MAX_ROWS, "engine_set_moe_decode: the route takes decode steps of at most 64 rows (max_batch)");
+    for (int l = 0; min_rows > 0 && l < e->cfg.num_layers; ++l)
+        TL_REQUIRE(!e->is_moe(l) || moe_decode_layer_ok(e, e->moe[l]),
+                   "engine_set_moe_decode: a MoE layer is outside the route's limits (16-byte aligned expert words, <= 1024 experts, <= 16 per token, widths multiples of 128)");
+    e->moe_decode_min = min_rows;
+    return TL_OK;
+}
+
+extern "C" int tl_engine_moe_decode_state(const tl_engine *e, int *min_rows, long *decode_calls) {
+    TL_REQUIRE(e, "engine_moe_decode_state: null argument");
+    if (min_rows) *min_rows = e->moe_decode_min;
+    if (decode_calls) *decode_calls = e->moe_decode_calls;
+    return TL_OK;
+}
+
 extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_weights *w) {
     TL_REQUIRE(e && w, "engine_set_moe_layer: null argument");
     const tl_engine_config &c = e->cfg;
@@ -1430,6 +1473,8 @@ extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_wei
                "engine_set_moe_layer: null expert tensor");
     TL_REQUIRE(e->moe_grouped_min == 0 || moe_grouped_words_aligned(*w),
                "engine_set_moe_layer: with the grouped-expert route on (tl_engine_set_moe_grouped) the expert words must be 16-byte aligned");
+    TL_REQUIRE(e->moe_decode_min == 0 || moe_decode_layer_ok(e, *w),
+               "engine_set_moe_layer: with the decode-shaped expert route on (tl_engine_set_moe_decode) a layer needs 16-byte aligned expert words, <= 1024 experts, <= 16 per token and widths that are multiples of 128");
     TL_REQUIRE((long)e->rows_cap * w->experts_per_token <= 65535, "engine_set_moe_layer: max_prefill_rows x experts_per_token must stay below 65536 (one grouped launch)");
     // the router's matmul must fit the workspace sized at tl_engine_create (it does for every E <= the widest projection)
     for (int M : {1, 8, 9, e->rows_cap})
@@ -2559,6 +2604,49 @@ extern "C" int tl_moe_experts_rows(const void *xn_dev, const void *h_dev, const 
     return TL_OK;
 }
 
+extern "C" size_t tl_moe_decode_workspace_bytes(int rows, int top_k, int hidden, int intermediate) {
+    return moe_decode_takes(rows, top_k, hidden, intermediate) ? moe_decode_rows_bytes(rows, top_k, hidden, intermediate) : 0;
+}
+
+extern "C" int tl_moe_decode_plan(int rows, int top_k, int num_experts, int hidden, int intermediate, int cus, int *plan12) {
+    TL_REQUIRE(plan12 && cus > 0 && num_experts > 0 && num_experts <= MOE_DEC_MAX_E && moe_decode_takes(rows, top_k, hidden, intermediate),
+               "moe_decode_plan: outside the route's limits");
+    const MoeDecodePlan p = moe_decode_split(rows, top_k, num_experts, hidden, intermediate, cus);
+    int at = 0;
+    for (const MoeDecodeStage *s : {&p.gate_up, &p.down})
+        for (int v : {s->features, s->wk, s->per, s->grid_x, s->grid_y, s->threads}) plan12[at++] = v;
+    return TL_OK;
+}
+
+extern "C" int tl_moe_decode_wave(int features, int wk, int per, int groups, int block, int wave, int *feature0_g0_g1) {
+    TL_REQUIRE(feature0_g0_g1 && features > 0 && wk > 0 && per > 0 && groups > 0 && block >= 0 && wave >= 0, "moe_decode_wave: bad argument");
+    moe_decode_wave_at(features, wk, per, groups, block, wave, feature0_g0_g1, feature0_g0_g1 + 1, feature0_g0_g1 + 2);
+    return TL_OK;
+}
+
+extern "C" int tl_moe_experts_rows_decode(const void *xn_dev, const void *h_dev, const int32_t *ids_dev, const void *scores_dev, const tl_moe_weights *w,
+                                          int rows, int hidden, void *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    TL_REQUIRE(xn_dev && h_dev && ids_dev && scores_dev && w && out_dev && workspace_dev, "moe_experts_rows_decode: null argument");
+    TL_REQUIRE(w->num_experts > 0 && w->num_experts <= MOE_DEC_MAX_E && w->experts_per_token > 0 && w->experts_per_token <= MOE_DEC_MAX_K &&
+                   w->experts_per_token <= w->num_experts,
+               "moe_experts_rows_decode: need 1 <= experts_per_token <= min(16, num_experts) and num_experts <= 1024");
+    TL_REQUIRE(w->intermediate_size > 0 && w->intermediate_size % 128 == 0, "moe_experts_rows_decode: intermediate_size must be a positive multiple of 128");
+    TL_REQUIRE(hidden > 0 && hidden % 128 == 0, "moe_experts_rows_decode: hidden must be a positive multiple of 128");
+    TL_REQUIRE(w->gate_dev && w->up_dev && w->down_dev && w->gate_scales_dev && w->gate_biases_dev && w->up_scales_dev &&
+                   w->up_biases_dev && w->down_scales_dev && w->down_biases_dev,
+               "moe_experts_rows_decode: null expert tensor");
+    TL_REQUIRE(rows >= 1 && rows <= MOE_DEC_MAX_ROWS, "moe_experts_rows_decode: rows must be 1 .. 64");
+    TL_REQUIRE(workspace_bytes >= moe_decode_rows_bytes(rows, w->experts_per_token, hidden, w->intermediate_size),
+               "moe_experts_rows_decode: the workspace is smaller than tl_moe_decode_workspace_bytes");
+    TL_REQUIRE(((uintptr_t)xn_dev | (uintptr_t)h_dev | (uintptr_t)out_dev | (uintptr_t)workspace_dev) % 16 == 0, "moe_experts_rows_decode: rows must be 16-byte aligned");
+    TL_REQUIRE(moe_grouped_words_aligned(*w), "moe_experts_rows_decode: the expert words must be 16-byte aligned");
+    uint16_t *act = (uint16_t *)workspace_dev, *y = act + (size_t)rows * w->experts_per_token * w->intermediate_size;
+    TL_TRY(moe_experts_decode_launch(*w, (const uint16_t *)xn_dev, (const uint16_t *)h_dev, ids_dev, (const uint16_t *)scores_dev, act, y,
+                                     (uint16_t *)out_dev, rows, hidden, (hipStream_t)stream));
+    TL_CHECK_LAUNCH("moe_experts_rows_decode");
+    return TL_OK;
+}
+
 extern "C" int tl_moe_grouped_tile_rows(void) { return MOE_TM; }
 
 extern "C" size_t tl_moe_grouped_workspace_bytes(int rows, int top_k, int hidden, int intermediate, int num_experts) {
@@ -3589,6 +3677,8 @@ static void step_done(tl_engine *e, int batch, const StepFeatures &f) {
         if (e->slot_runs(b)) e->settings.pending_produced(b);
     e->stats.decode_steps++;
     if (f.lora) e->lora_steps++;
+    if (e->moe_decode_min > 0 && batch >= e->moe_decode_min)  // (per step run, replays included: engine_moe_mlp is not passed on a replay)
+        for (int l = 0; l < e->cfg.num_layers; ++l) e->moe_decode_calls += e->is_moe(l);
     e->logits_rows = batch, e->logits_slot = -1;
 }
 

@@ -245,6 +245,8 @@ _SIGNATURES.update({
     "tl_engine_set_moe_layer": (_c_int, [_c_void_p, _c_int, _P(TlMoeWeights)]),
     "tl_engine_set_moe_grouped": (_c_int, [_c_void_p, _c_int]),
     "tl_engine_moe_grouped_state": (_c_int, [_c_void_p, _P(_c_int), _P(ctypes.c_long)]),
+    "tl_engine_set_moe_decode": (_c_int, [_c_void_p, _c_int]),
+    "tl_engine_moe_decode_state": (_c_int, [_c_void_p, _P(_c_int), _P(ctypes.c_long)]),
     "tl_decode_gemv_plan": (_c_int, [_c_int, _c_int, _c_int, _P(_c_int)]),
     "tl_decode_batched_plan": (_c_int, [_c_int, _c_int, _c_int, _P(_c_int)]),
     "tl_decode_batched_variant_compiled": (_c_int, [_c_int, _c_int]),
@@ -340,6 +342,11 @@ _SIGNATURES.update({
     "tl_moe_route_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "tl_moe_experts_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
     "tl_moe_grouped_tile_rows": (_c_int, []),
+    "tl_moe_decode_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
+    "tl_moe_experts_rows_decode": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _P(TlMoeWeights), _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t,
+                                            _c_void_p]),
+    "tl_moe_decode_plan": (_c_int, [_c_int] * 6 + [_P(_c_int)]),
+    "tl_moe_decode_wave": (_c_int, [_c_int] * 6 + [_P(_c_int)]),
     "tl_moe_grouped_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "tl_moe_experts_rows_grouped": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _P(TlMoeWeights), _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t,
                                              _c_void_p]),
@@ -1367,6 +1374,33 @@ def moe_experts_rows_grouped(xn: torch.Tensor, h: torch.Tensor, ids: torch.Tenso
     stages = {"act": ws[a0:y0].view(torch.bfloat16).view(er, inter), "y": ws[y0:p0].view(torch.bfloat16).view(er, hidden),
               "perm": ws[p0:p0 + er * 4].view(torch.int32), "offsets": ws[o0:o0 + (n_experts + 1) * 4].view(torch.int32)}
     return out, stages
+
+
+def moe_experts_rows_decode(xn: torch.Tensor, h: torch.Tensor, ids: torch.Tensor, scores: torch.Tensor, gate, up, down) -> tuple[torch.Tensor, dict]:
+    """moe_experts_rows on the decode-shaped route (tl_moe_experts_rows_decode): 1 .. 64 rows, the rows of an expert share one read of its
+    weights, MFMA products over up to 16 of them at a time.  Same arguments.  Returns (out [rows, hidden] bf16, {"act": [rows * top_k, I],
+    "y": [rows * top_k, hidden] bf16} as the call's workspace holds them)."""
+    for t in (xn, h, scores, *gate[1:], *up[1:], *down[1:]):
+        if t.dtype != torch.bfloat16 or not t.is_cuda:
+            raise ValueError("moe_experts_rows_decode takes bf16 tensors on the GPU")
+    if ids.dtype != torch.int32 or not ids.is_cuda or ids.dim() != 2 or ids.shape != scores.shape or xn.shape != h.shape or xn.dim() != 2:
+        raise ValueError("moe_experts_rows_decode: xn / h [rows, hidden], ids (int32) / scores [rows, top_k]")
+    xn, h, ids, scores = xn.contiguous(), h.contiguous(), ids.contiguous(), scores.contiguous()
+    gate, up, down = (tuple(t.contiguous() for t in w) for w in (gate, up, down))
+    (rows, hidden), k, dev = xn.shape, ids.shape[1], xn.device
+    n_experts, inter = gate[0].shape[0], gate[0].shape[1]
+    if ids.shape[0] != rows or gate[0].shape[2] * 8 != hidden or up[0].shape != gate[0].shape or down[0].shape != (n_experts, hidden, inter // 8):
+        raise ValueError("moe_experts_rows_decode: the expert tensors do not fit the rows")
+    w = TlMoeWeights(TlW4(), gate[0].data_ptr(), up[0].data_ptr(), down[0].data_ptr(), gate[1].data_ptr(), gate[2].data_ptr(), up[1].data_ptr(),
+                     up[2].data_ptr(), down[1].data_ptr(), down[2].data_ptr(), n_experts, k, inter, 0)
+    nbytes = _lib.tl_moe_decode_workspace_bytes(rows, k, hidden, inter)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    out = torch.empty_like(xn)
+    check(_lib.tl_moe_experts_rows_decode(xn.data_ptr(), h.data_ptr(), ids.data_ptr(), scores.data_ptr(), ctypes.byref(w), rows, hidden, out.data_ptr(),
+                                          ws.data_ptr(), nbytes, _stream()))
+    er = rows * k
+    y0 = er * inter * 2
+    return out, {"act": ws[:y0].view(torch.bfloat16).view(er, inter), "y": ws[y0:y0 + er * hidden * 2].view(torch.bfloat16).view(er, hidden)}
 
 
 POOL_LAST, POOL_MEAN = 0, 1  # TL_POOL_LAST / TL_POOL_MEAN

@@ -64,8 +64,12 @@ class DecodeEngine:
 
     def __init__(self, mlx_model: Any, *, page_size: int = 128, num_pages: int = 512, max_batch: int = 1,
                  max_pages_per_seq: int | None = None, max_prefill_rows: int = 2048, options: dict | None = None,
-                 kv_format: str = "bf16", prefix_cache: bool | int = False, swap_pages: int = 0, moe_grouped_rows: int = 0):
-        """``moe_grouped_rows``: MoE layers run their experts on the grouped-expert route (rows sorted by expert, MFMA tile GEMMs;
+                 kv_format: str = "bf16", prefix_cache: bool | int = False, swap_pages: int = 0, moe_grouped_rows: int = 0,
+                 moe_decode_rows: int = 0):
+        """``moe_decode_rows``: decode steps of at least that many sequences run the experts of MoE layers on the decode-shaped route
+        (one read of an expert for all rows that name it, MFMA products; tl_engine_set_moe_decode; max_batch <= 64); 0 (the default):
+        never.  Prefill, score, embed and verification passes keep their routes.  ``moe_decode_state()`` reports the setting and the count.
+        ``moe_grouped_rows``: MoE layers run their experts on the grouped-expert route (rows sorted by expert, MFMA tile GEMMs;
         tl_engine_set_moe_grouped) in prefill, score, embed and verification passes over at least that many rows; 0 (the default):
         never.  Decode steps always keep the per-row GEMV route.  ``moe_grouped_state()`` reports the setting and the count.
         ``swap_pages``: room for that many KV pages in pinned host memory (tl_engine_swap_space): ``park`` moves a sequence's K / V
@@ -142,6 +146,9 @@ class DecodeEngine:
         if isinstance(moe_grouped_rows, bool) or not isinstance(moe_grouped_rows, int) or moe_grouped_rows < 0:
             raise ValueError(f"moe_grouped_rows must be an int >= 0 (0: never), got {moe_grouped_rows!r}")
         _ext.check(_lib.tl_engine_set_moe_grouped(self._h, moe_grouped_rows))
+        if isinstance(moe_decode_rows, bool) or not isinstance(moe_decode_rows, int) or moe_decode_rows < 0:
+            raise ValueError(f"moe_decode_rows must be an int >= 0 (0: never), got {moe_decode_rows!r}")
+        _ext.check(_lib.tl_engine_set_moe_decode(self._h, moe_decode_rows))
         for i, mlp in moe_layers.items():
             self._attach_moe(i, mlp, args)
         if isinstance(prefix_cache, bool):
@@ -183,6 +190,12 @@ class DecodeEngine:
         rows, calls = ctypes.c_int(), ctypes.c_long()
         _ext.check(_lib.tl_engine_moe_grouped_state(self._h, ctypes.byref(rows), ctypes.byref(calls)))
         return {"min_rows": rows.value, "grouped_calls": calls.value}
+
+    def moe_decode_state(self) -> dict:
+        """{"min_rows": the ``moe_decode_rows`` setting, "calls": MoE MLPs that decode steps ran on the decode-shaped route so far}."""
+        rows, calls = ctypes.c_int(), ctypes.c_long()
+        _ext.check(_lib.tl_engine_moe_decode_state(self._h, ctypes.byref(rows), ctypes.byref(calls)))
+        return {"min_rows": rows.value, "calls": calls.value}
 
     @classmethod
     def from_model(cls, mlx_model: Any, **kwargs) -> "DecodeEngine":
