@@ -157,7 +157,11 @@ int tl_engine_moe_decode_state(const tl_engine *e, int *min_rows, long *decode_c
  *   "attn_qkv_partials" [1] the decode attention adds the qkv slice planes itself;  "lmhead_tile_max" [1] per-tile maxima from the lm_head
  *   GEMV;  "gemm_fused_epilogue" [1] residual / SwiGLU inside the prefill GEMM;  "prefill_reduce_norm" [1] the split-K residual
  *   reduction of a small prefill chunk also writes the RMSNorm behind it;  "aql_fences" [0] HIP's agent-scope fences back on every
- *   packet of the AQL route.  Not part of the reference's surface: product code never calls it. */
+ *   packet of the AQL route;  "prefill_fp8" [0] prefill, packed-prefill, score and embed chunks of the dense layer matrices (qkv, wo,
+ *   gate|up, down) with FP8 (E4M3) activations on the block-scaled matrix instruction (csrc/gemm_fp8.h): 1 = from the default row count
+ *   (512), a value of 128 or more = from that many rows; builds the E4M3 weight copies (all or nothing, counted in the workspace stats).
+ *   Decode steps, verification passes, lm_head, MoE experts and LoRA launches never take it.
+ *   Not part of the reference's surface: product code never calls it. */
 int tl_engine_set_option(tl_engine *e, const char *name, int value);
 void tl_engine_destroy(tl_engine *e);
 /* Block the host until everything enqueued on the engine stream has finished. */
@@ -1130,6 +1134,23 @@ int tl_decode_linear_ex(const tl_tiled_w4 *w, const void *a_dev, void *out_dev, 
 int tl_prefill_weights_bf16(const tl_w4 *w, void *out_dev, void *stream);
 int tl_prefill_matmul_bf16(const void *a_dev, const void *w_bf16_dev, void *out_dev, int M, int rows, int cols, int epilogue,
                            const void *residual_dev, void *stream);
+
+/* The same projection with FP8 (E4M3) ACTIVATIONS on the block-scaled matrix instruction of gfx950 (csrc/gemm_fp8.h; engine option "prefill_fp8",
+ * off by default; the reference has no counterpart).  With w = q s + beta per 128-column group g, every group of every activation row quantised as
+ * oracle/kv_fp8.py quantises a row (128 codes, one power-of-two fp32 scale alpha; a^ = decode(code) alpha, S = the group's fp32 sum of a^):
+ *   out[m, n] = epilogue( sum_g ( s[n, g] sum_{k in g} a^[m, k] q[n, k] + beta[n, g] S[m, g] ) ), fp32 accumulation, one rounding to bf16.
+ *   tl_prefill_weights_fp8_bytes: the size of the weight copy of a [rows, cols] matrix;
+ *   tl_prefill_weights_fp8: out_dev = [rows][cols] E4M3 codes of q - 8, row-major (byte n cols + k decodes to nibble k of row n, less 8: the
+ *     kernel works on w = (q - 8) s + (beta + 8 s)), then from byte ceil256(rows cols) s as fp32 [cols / 128][ceil256(rows)], then beta + 8 s
+ *     as fp32 [ceil256(rows)][ceil32(cols / 128)], the padding zero;
+ *   tl_prefill_quantize_rows_fp8: a [M, cols] bf16 -> codes [M, cols] uint8, scales and sums [M, cols / 128] fp32, one launch;
+ *   tl_prefill_matmul_fp8: out [M, rows] (epilogue 2: [M, rows / 2]) from those and the weight copy; epilogues as tl_prefill_matmul_bf16; cols a
+ *     multiple of 128, rows a multiple of 4.  Stream ordered. */
+size_t tl_prefill_weights_fp8_bytes(int rows, int cols);
+int tl_prefill_weights_fp8(const tl_w4 *w, void *out_dev, void *stream);
+int tl_prefill_quantize_rows_fp8(const void *a_dev, void *codes_dev, float *scales_dev, float *sums_dev, int M, int cols, void *stream);
+int tl_prefill_matmul_fp8(const void *codes_dev, const float *scales_dev, const float *sums_dev, const void *w_fp8_dev, void *out_dev, int M, int rows,
+                          int cols, int epilogue, const void *residual_dev, void *stream);
 
 /* The attention launch of one decode layer: q/k-RMSNorm + RoPE at position context_lens[b] + append of the new K/V row to
  * the pages (IN PLACE) + GQA attention over context_lens[b] + 1 tokens (+ the merge launch when the context is split).

@@ -22,6 +22,7 @@
 #include "qmm6.h"
 #include "qmm7.h"
 #include "gemm8.h"
+#include "gemm_fp8.h"
 
 namespace tl {
 
@@ -117,6 +118,12 @@ struct LinearCtx : LinearScratch, LinearKnobs {
     // bf16 -- bf16(q * s + beta), the B operand the reference's tile GEMM forms in threadgroup memory (quantized_matmul.metal:96-249) -- for
     // the plain bf16 GEMM of gemm8.h (256 x 256 tiles by LDS-DMA, no dequantisation in the loop).  7.3 GB at Qwen3-4B, of 288.
     std::map<const uint32_t *, uint16_t *> bf16w;
+    // Option "prefill_fp8" (off by default): the dense layer matrices once more as E4M3 codes + s / beta tables (gemm_fp8.h), and the chunk's quantised
+    // rows -- codes [rows_cap, widest K], scales and group sums [rows_cap, widest K / 128] -- for projections of fp8_min_rows rows and more that ask for it
+    std::map<const uint32_t *, const uint8_t *> fp8w;
+    int fp8_min_rows = 0;  // 0 = off
+    uint8_t *fp8_codes = nullptr;
+    float *fp8_scales = nullptr, *fp8_sums = nullptr;
     bool use_gemm8 = true;  // tl_engine_set_option "gemm8" = 0: every chunk through the W4 GEMM (qmm.hip), the twin
     bool fuse_reduce_norm = true;  // "prefill_reduce_norm" = 0: the split-K residual reduction and the RMSNorm behind it as two launches, the twin
     bool gemm_fused_epilogue = true;    // tl_engine_set_option "gemm_fused_epilogue" = 0: residual / SwiGLU of the prefill GEMM as separate launches
@@ -166,6 +173,7 @@ struct Proj {
     // PRO_ATTN_MERGE (the wo GEMV of ONE row, h = x + merge(attention partials) @ wo^T): the decode-attention split partials
     const float *merge_ws = nullptr;
     int n_splits = 0;
+    bool fp8 = false;  // a prefill chunk's projection: with option "prefill_fp8" on, engine_gemm takes it through quantise + FP8 GEMM from fp8_min_rows rows
     f32x2 *tile_max = nullptr;  // a single-pass EPI_STORE GEMV leaves its per-16-row (max, lowest index) pairs here (qmv3.h tile_max)
 };
 static Proj proj(const tl_w4 &w, const uint16_t *a, uint16_t *out, int M) { return Proj{&w, a, out, M}; }
@@ -309,6 +317,19 @@ static int engine_gemm(LinearCtx &ctx, const Proj &p, bool *norm_done = nullptr)
     const tl_w4 &w = *p.w;
     const int M = p.M;
     if (norm_done) *norm_done = false;
+    if (p.fp8 && ctx.fp8_min_rows > 0 && M >= ctx.fp8_min_rows) {
+        const auto wf = ctx.fp8w.find(w.weight_dev);
+        if (wf != ctx.fp8w.end() && gemm_fp8_applicable(M, w.rows, w.cols)) {
+            if (quantize_rows_fp8(p.a, ctx.fp8_codes, ctx.fp8_scales, ctx.fp8_sums, M, w.cols, ctx.stream) != 0) return fail(TL_ERR_UNSUPPORTED, "engine: FP8 row quantiser launch failed");
+            GemmFp8Args g{};
+            g.codes = ctx.fp8_codes, g.scales = ctx.fp8_scales, g.sums = ctx.fp8_sums, g.wq = wf->second;
+            g.ws = reinterpret_cast<const float *>(wf->second + gemm_fp8_off_s(w.rows, w.cols)), g.wb = reinterpret_cast<const float *>(wf->second + gemm_fp8_off_b(w.rows, w.cols));
+            g.out = p.out, g.residual = p.residual, g.M = M, g.N = w.rows, g.K = w.cols;
+            if (launch_gemm_fp8(g, p.epi, ctx.stream) != 0) return fail(TL_ERR_UNSUPPORTED, "engine: FP8 GEMM launch failed");
+            TL_CHECK_LAUNCH("engine FP8 matmul");
+            return TL_OK;
+        }
+    }
     if (ctx.use_gemm8 && gemm8_wins(M)) {
         const auto wb = ctx.bf16w.find(w.weight_dev);
         if (wb != ctx.bf16w.end() && gemm8_applicable(M, w.rows, w.cols)) {

@@ -139,6 +139,9 @@ struct tl_engine {
     std::vector<DeviceBlock> bf16w_mem;
     DeviceBlock splitk_mem;
     size_t tiled_bytes = 0, bf16w_bytes = 0;
+    std::vector<DeviceBlock> fp8w_mem;  // option "prefill_fp8": the owners of lin.fp8w, and of the chunk's quantised rows
+    DeviceBlock fp8_rows_mem;
+    size_t fp8_bytes = 0;
 
     int32_t *block_table = nullptr, *context_lens = nullptr, *tokens = nullptr, *live = nullptr, *produced = nullptr,
             *ring = nullptr, *scratch_ctx = nullptr, *prefill_tokens = nullptr;
@@ -1496,7 +1499,7 @@ extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_wei
         e->moe_up = piece_at<uint16_t>(m, ml[MoeLayout::UP]), e->moe_act = piece_at<uint16_t>(m, ml[MoeLayout::ACT]);
         e->moe_y = piece_at<uint16_t>(m, ml[MoeLayout::Y]);
         e->moe_k_max = k, e->moe_e_max = E, e->moe_i_max = I;
-        e->stats.workspace_bytes = e->arena_bytes + e->tiled_bytes + e->moe_ws_bytes + e->moe_grouped_bytes;
+        e->stats.workspace_bytes = e->arena_bytes + e->tiled_bytes + e->moe_ws_bytes + e->moe_grouped_bytes + e->fp8_bytes;
         TL_TRY(moe_grouped_alloc(e));
     }
     e->moe[layer] = *w;
@@ -1509,6 +1512,53 @@ extern "C" int tl_engine_set_moe_layer(tl_engine *e, int layer, const tl_moe_wei
         e->layer_act_rows = 0, e->layer_act_bytes = 0, e->layer_ws_bytes = 0;
         e->layer_plane_bytes[0] = e->layer_plane_bytes[1] = 0;
     }
+    return TL_OK;
+}
+
+// Option "prefill_fp8" (gemm_fp8.h): the E4M3 copies of every dense layer matrix and the buffers of a chunk's quantised rows, all or nothing --
+// a failed allocation leaves the option off and nothing behind.  value 1 = the default row threshold, 128 and more = that many rows.
+constexpr int FP8_DEFAULT_MIN_ROWS = 512, FP8_FLOOR_MIN_ROWS = 128;
+static int enable_prefill_fp8(tl_engine *e, int value) {
+    if (value == 0) {
+        e->lin.fp8_min_rows = 0;
+        return TL_OK;
+    }
+    TL_REQUIRE(value == 1 || value >= FP8_FLOOR_MIN_ROWS, "engine_set_option: prefill_fp8 is 0 (off), 1 (on, default row threshold) or a row threshold of 128 and more");
+    if (e->lin.fp8w.empty()) {
+        std::vector<DeviceBlock> mem;
+        std::map<const uint32_t *, const uint8_t *> copies;
+        size_t bytes = 0;
+        int k_max = 0;
+        auto add = [&](const tl_w4 &w) -> int {
+            if (!w.weight_dev || copies.count(w.weight_dev)) return TL_OK;
+            TL_REQUIRE(gemm_fp8_applicable(e->cfg.max_prefill_rows, w.rows, w.cols), "engine_set_option: prefill_fp8 does not cover a layer matrix of this shape");
+            const size_t n = gemm_fp8_weight_bytes(w.rows, w.cols);
+            DeviceBlock copy;
+            TL_TRY(copy.alloc(n, "engine_set_option: hipMalloc(FP8 weights for the prefill GEMM) failed"));
+            if (expand_w4_to_fp8(w.weight_dev, (const uint16_t *)w.scales_dev, (const uint16_t *)w.biases_dev, copy.at<uint8_t>(), w.rows, w.cols, e->stream) != 0)
+                return fail(TL_ERR_HIP, "engine_set_option: FP8 weight expansion launch failed");
+            copies[w.weight_dev] = copy.at<uint8_t>();
+            mem.push_back(std::move(copy));
+            bytes += n, k_max = std::max(k_max, w.cols);
+            return TL_OK;
+        };
+        for (const auto &l : e->layers) {
+            TL_TRY(add(l.wqkv));
+            TL_TRY(add(l.wo));
+            TL_TRY(add(l.wgu));
+            TL_TRY(add(l.wdown));
+        }
+        const size_t rows = (size_t)e->cfg.max_prefill_rows, code_bytes = align_up(rows * k_max, 256), table_bytes = align_up(rows * (k_max / 128) * 4, 256);
+        DeviceBlock rows_mem;
+        TL_TRY(rows_mem.alloc(code_bytes + 2 * table_bytes, "engine_set_option: hipMalloc(FP8 activation rows) failed"));
+        e->lin.fp8_codes = rows_mem.at<uint8_t>();
+        e->lin.fp8_scales = reinterpret_cast<float *>(rows_mem.at<char>() + code_bytes);
+        e->lin.fp8_sums = reinterpret_cast<float *>(rows_mem.at<char>() + code_bytes + table_bytes);
+        e->fp8_rows_mem = std::move(rows_mem), e->fp8w_mem = std::move(mem), e->lin.fp8w = std::move(copies);
+        e->fp8_bytes = bytes + code_bytes + 2 * table_bytes;
+        e->stats.workspace_bytes += e->fp8_bytes;
+    }
+    e->lin.fp8_min_rows = value == 1 ? FP8_DEFAULT_MIN_ROWS : value;
     return TL_OK;
 }
 
@@ -1528,7 +1578,8 @@ extern "C" int tl_engine_set_option(tl_engine *e, const char *name, int value) {
     else if (n == "gemm8") e->lin.use_gemm8 = on;
     else if (n == "prefill_reduce_norm") e->lin.fuse_reduce_norm = on;
     else if (n == "aql_fences") e->aql_fences.inner_acquire = e->aql_fences.inner_release = on ? HSA_FENCE_SCOPE_AGENT : HSA_FENCE_SCOPE_NONE;
-    else return fail(TL_ERR_INVALID, "engine_set_option: unknown option '" + n + "' (qmm3, qmm6, qmm7, gemm8, prefill_reduce_norm, attn_qkv_partials, lmhead_tile_max, gemm_fused_epilogue, aql_fences)");
+    else if (n == "prefill_fp8") return enable_prefill_fp8(e, value);
+    else return fail(TL_ERR_INVALID, "engine_set_option: unknown option '" + n + "' (qmm3, qmm6, qmm7, gemm8, prefill_reduce_norm, attn_qkv_partials, lmhead_tile_max, gemm_fused_epilogue, aql_fences, prefill_fp8)");
     return TL_OK;
 }
 
@@ -2979,7 +3030,9 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
         const tl_layer_weights &w = e->layers[l];
         if (!x_normed) TL_TRY(tl_rms_norm(b.x_out, w.input_norm_dev, b.xn, total, c.hidden_size, c.rms_norm_eps, TL_BF16, e->stream));
         x_normed = false;
-        TL_TRY(engine_gemm(e->lin, proj(w.wqkv, b.xn, b.qkv, total)));
+        Proj pq = proj(w.wqkv, b.xn, b.qkv, total);
+        pq.fp8 = true;
+        TL_TRY(engine_gemm(e->lin, pq));
         if (lora_on(l, tl_engine::LORA_QKV))
             TL_TRY(lora_group(e, l, tl_engine::LORA_QKV, e->lora_tiles_prefill, lora_tiles, total, b.xn, nullptr, TL_LORA_ADD, nullptr, b.qkv));
         for (int i = 0; i < n_seqs; ++i) {
@@ -3012,7 +3065,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
         }
         bool h_normed = false;
         Proj po = proj(w.wo, b.attn, b.h, total);
-        po.epi = EPI_RESIDUAL, po.residual = b.x_out, po.norm_out = w.post_norm_dev, po.out_w = b.xn;
+        po.epi = EPI_RESIDUAL, po.residual = b.x_out, po.norm_out = w.post_norm_dev, po.out_w = b.xn, po.fp8 = true;
         if (lora_on(l, tl_engine::LORA_O)) {  // x + delta first: the projection's residual epilogue then adds its product to that
             TL_TRY(lora_group(e, l, tl_engine::LORA_O, e->lora_tiles_prefill, lora_tiles, total, b.attn, nullptr, TL_LORA_RESIDUAL_PRE, b.x_out, e->lora_tmp));
             po.residual = e->lora_tmp;
@@ -3024,7 +3077,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
         } else {
             TL_REQUIRE(w.wgu.weight_dev != nullptr, "engine: a layer has neither a dense MLP nor experts (tl_engine_set_moe_layer)");
             Proj pg = proj(w.wgu, b.xn, b.act, total);
-            pg.epi = EPI_SWIGLU;
+            pg.epi = EPI_SWIGLU, pg.fp8 = true;
             if (lora_on(l, tl_engine::LORA_GU)) {  // the unfused route: complete gate|up rows, then the expand launch's SwiGLU over base + delta
                 pg.out = e->lin.gu, pg.epi = EPI_STORE;
                 TL_TRY(engine_gemm(e->lin, pg));
@@ -3033,7 +3086,7 @@ static int prefill_pass(tl_engine *e, const PrefillSeq *seqs, int n_seqs, const 
                 TL_TRY(engine_gemm(e->lin, pg));
             }
             Proj pd = proj(w.wdown, b.act, b.x_out, total);
-            pd.epi = EPI_RESIDUAL, pd.residual = b.h, pd.norm_out = l + 1 < c.num_layers ? e->layers[l + 1].input_norm_dev : nullptr, pd.out_w = b.xn;
+            pd.epi = EPI_RESIDUAL, pd.residual = b.h, pd.norm_out = l + 1 < c.num_layers ? e->layers[l + 1].input_norm_dev : nullptr, pd.out_w = b.xn, pd.fp8 = true;
             if (lora_on(l, tl_engine::LORA_DOWN)) {
                 TL_TRY(lora_group(e, l, tl_engine::LORA_DOWN, e->lora_tiles_prefill, lora_tiles, total, b.act, nullptr, TL_LORA_RESIDUAL_PRE, b.h, e->lora_tmp));
                 pd.residual = e->lora_tmp;
@@ -3956,6 +4009,40 @@ extern "C" int tl_prefill_matmul_bf16(const void *a_dev, const void *w_bf16_dev,
     g.M = M, g.N = rows, g.K = cols;
     if (launch_gemm8_bf16(g, epilogue, (hipStream_t)stream) != 0) return fail(TL_ERR_UNSUPPORTED, "prefill_matmul_bf16: launch failed");
     TL_CHECK_LAUNCH("prefill_matmul_bf16");
+    return TL_OK;
+}
+
+// ... and with FP8 activations (header): the W4 -> E4M3 expansion, the row quantiser, the block-scaled GEMM of gemm_fp8.h
+extern "C" size_t tl_prefill_weights_fp8_bytes(int rows, int cols) { return rows > 0 && cols > 0 && cols % 128 == 0 ? gemm_fp8_weight_bytes(rows, cols) : 0; }
+extern "C" int tl_prefill_weights_fp8(const tl_w4 *w, void *out_dev, void *stream) {
+    TL_REQUIRE(w && out_dev, "prefill_weights_fp8: null argument");
+    TL_TRY(check_w4(*w, w->rows, w->cols, "prefill_weights_fp8"));
+    TL_REQUIRE(w->cols % 128 == 0, "prefill_weights_fp8: columns must be a multiple of the quantisation group (128)");
+    if (expand_w4_to_fp8(w->weight_dev, (const uint16_t *)w->scales_dev, (const uint16_t *)w->biases_dev, (uint8_t *)out_dev, w->rows, w->cols, (hipStream_t)stream) != 0)
+        return fail(TL_ERR_HIP, "prefill_weights_fp8: launch failed");
+    return TL_OK;
+}
+extern "C" int tl_prefill_quantize_rows_fp8(const void *a_dev, void *codes_dev, float *scales_dev, float *sums_dev, int M, int cols, void *stream) {
+    TL_REQUIRE(a_dev && codes_dev && scales_dev && sums_dev, "prefill_quantize_rows_fp8: null argument");
+    TL_REQUIRE(M >= 1 && cols >= 128 && cols % 128 == 0, "prefill_quantize_rows_fp8: needs M >= 1 and columns in whole groups of 128");
+    if (quantize_rows_fp8((const uint16_t *)a_dev, (uint8_t *)codes_dev, scales_dev, sums_dev, M, cols, (hipStream_t)stream) != 0)
+        return fail(TL_ERR_HIP, "prefill_quantize_rows_fp8: launch failed");
+    TL_CHECK_LAUNCH("prefill_quantize_rows_fp8");
+    return TL_OK;
+}
+extern "C" int tl_prefill_matmul_fp8(const void *codes_dev, const float *scales_dev, const float *sums_dev, const void *w_fp8_dev, void *out_dev, int M, int rows,
+                                     int cols, int epilogue, const void *residual_dev, void *stream) {
+    TL_REQUIRE(codes_dev && scales_dev && sums_dev && w_fp8_dev && out_dev, "prefill_matmul_fp8: null argument");
+    TL_REQUIRE(epilogue == EPI_STORE || epilogue == EPI_RESIDUAL || epilogue == EPI_SWIGLU, "prefill_matmul_fp8: epilogue is 0 (store), 1 (residual add) or 2 (SwiGLU over interleaved rows)");
+    TL_REQUIRE(epilogue != EPI_RESIDUAL || residual_dev, "prefill_matmul_fp8: the residual epilogue needs the residual rows");
+    TL_REQUIRE(gemm_fp8_applicable(M, rows, cols), "prefill_matmul_fp8: needs M >= 1, weight rows in fours and columns in whole groups of 128");
+    const uint8_t *wf = (const uint8_t *)w_fp8_dev;
+    GemmFp8Args g{};
+    g.codes = (const uint8_t *)codes_dev, g.scales = scales_dev, g.sums = sums_dev, g.wq = wf;
+    g.ws = reinterpret_cast<const float *>(wf + gemm_fp8_off_s(rows, cols)), g.wb = reinterpret_cast<const float *>(wf + gemm_fp8_off_b(rows, cols));
+    g.out = (uint16_t *)out_dev, g.residual = (const uint16_t *)residual_dev, g.M = M, g.N = rows, g.K = cols;
+    if (launch_gemm_fp8(g, epilogue, (hipStream_t)stream) != 0) return fail(TL_ERR_UNSUPPORTED, "prefill_matmul_fp8: launch failed");
+    TL_CHECK_LAUNCH("prefill_matmul_fp8");
     return TL_OK;
 }
 

@@ -229,6 +229,10 @@ _SIGNATURES.update({
                                      _c_int, _c_void_p, _c_size_t, _c_void_p, _P(TlLinearEx), _P(TlLinearInfo)]),
     "tl_prefill_weights_bf16": (_c_int, [_P(TlW4), _c_void_p, _c_void_p]),
     "tl_prefill_matmul_bf16": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "tl_prefill_weights_fp8_bytes": (ctypes.c_size_t, [_c_int, _c_int]),
+    "tl_prefill_weights_fp8": (_c_int, [_P(TlW4), _c_void_p, _c_void_p]),
+    "tl_prefill_quantize_rows_fp8": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p]),
+    "tl_prefill_matmul_fp8": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
     "tl_decode_gemv_variant_compiled": (_c_int, [_c_int, _c_int, _c_int, _c_int]),
     "tl_decode_attention_fused_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
     "tl_decode_attention_fused": (_c_int, [_c_void_p] * 8 + [_c_int] * 6 + [_c_float, _c_float, _c_int, _c_void_p, _c_size_t,
@@ -910,6 +914,47 @@ def prefill_matmul_bf16(a: torch.Tensor, w_bf16: torch.Tensor, *, epilogue: int 
     res = residual.contiguous() if residual is not None else None
     _check(_lib.tl_prefill_matmul_bf16(_ptr(a.contiguous()), _ptr(w_bf16.contiguous()), _ptr(out), M, rows, cols, int(epilogue),
                                        _ptr(res) if res is not None else None, _stream()))
+    return out
+
+
+def prefill_weights_fp8(weight: torch.Tensor, scales: torch.Tensor, biases: torch.Tensor) -> torch.Tensor:
+    """W4 [rows, cols/8] -> the weight copy of the FP8-activation prefill GEMM (tl_prefill_weights_fp8), a uint8 block: bytes [0, rows * cols) are
+    the E4M3 codes of the nibbles, row-major [rows, cols]; the s (fp32) and beta (bf16) tables follow (include/tinyllm_engine.h)."""
+    _require_gpu("prefill_weights_fp8", weight, scales, biases)
+    rows, cols = int(weight.shape[0]), int(weight.shape[1]) * 8
+    w4 = TlW4(_ptr(weight.contiguous()), _ptr(scales.contiguous()), _ptr(biases.contiguous()), rows, cols)
+    out = torch.empty((int(_lib.tl_prefill_weights_fp8_bytes(rows, cols)),), dtype=torch.uint8, device=weight.device)
+    _check(_lib.tl_prefill_weights_fp8(ctypes.byref(w4), _ptr(out), _stream()))
+    return out
+
+
+def prefill_quantize_rows_fp8(a: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """a [M, cols] bf16 -> (codes [M, cols] uint8, scales [M, cols/128] fp32, group sums [M, cols/128] fp32): every 128-column group quantised as
+    oracle/kv_fp8.py quantises a row (tl_prefill_quantize_rows_fp8, one launch)."""
+    _require_gpu("prefill_quantize_rows_fp8", a)
+    if a.dtype != torch.bfloat16 or a.dim() != 2 or a.shape[1] % 128 != 0:
+        raise RuntimeError("prefill_quantize_rows_fp8: a [M, cols] must be bfloat16 with cols a multiple of 128")
+    M, cols = int(a.shape[0]), int(a.shape[1])
+    codes = torch.empty((M, cols), dtype=torch.uint8, device=a.device)
+    scales = torch.empty((M, cols // 128), dtype=torch.float32, device=a.device)
+    sums = torch.empty_like(scales)
+    _check(_lib.tl_prefill_quantize_rows_fp8(_ptr(a.contiguous()), _ptr(codes), _ptr(scales), _ptr(sums), M, cols, _stream()))
+    return codes, scales, sums
+
+
+def prefill_matmul_fp8(codes: torch.Tensor, scales: torch.Tensor, sums: torch.Tensor, w_fp8: torch.Tensor, rows: int, *, epilogue: int = 0,
+                       residual: torch.Tensor | None = None) -> torch.Tensor:
+    """out = epilogue(sum_g (s sum_k a^ q + beta S)) from quantised rows and the weight copy of a [rows, cols] matrix: the FP8-activation GEMM
+    (tl_prefill_matmul_fp8, csrc/gemm_fp8.h)."""
+    _require_gpu("prefill_matmul_fp8", codes, scales, sums, w_fp8)
+    M, cols = int(codes.shape[0]), int(codes.shape[1])
+    if codes.dtype != torch.uint8 or scales.dtype != torch.float32 or sums.dtype != torch.float32 or tuple(scales.shape) != (M, cols // 128) or \
+            tuple(sums.shape) != (M, cols // 128) or w_fp8.dtype != torch.uint8 or w_fp8.numel() != int(_lib.tl_prefill_weights_fp8_bytes(rows, cols)):
+        raise RuntimeError("prefill_matmul_fp8: codes [M, cols] uint8, scales / sums [M, cols/128] float32 and the weight copy of [rows, cols]")
+    out = torch.empty((M, rows // 2 if epilogue == 2 else rows), dtype=torch.bfloat16, device=codes.device)
+    res = residual.contiguous() if residual is not None else None
+    _check(_lib.tl_prefill_matmul_fp8(_ptr(codes.contiguous()), _ptr(scales.contiguous()), _ptr(sums.contiguous()), _ptr(w_fp8), _ptr(out), M, rows, cols,
+                                      int(epilogue), _ptr(res) if res is not None else None, _stream()))
     return out
 
 
