@@ -46,6 +46,7 @@ def main(argv=None):
     ap.add_argument("--max-seq-len", type=int, default=8192, help="longest text in tokens")
     ap.add_argument("--prefill-rows", type=int, default=4096, help="tokens per pass (max_prefill_rows)")
     ap.add_argument("--batch-size", type=int, default=16, help="texts per pass, at most 16")
+    ap.add_argument("--quantize", action="store_true", help="accept an unquantised checkpoint (bf16 safetensors): quantise it to W4 on the device while loading")
     args = ap.parse_args(argv)
     if not 1 <= args.batch_size <= 16:
         ap.error("--batch-size must be 1 .. 16")
@@ -54,7 +55,7 @@ def main(argv=None):
     from tiny_llm_hip.embedding import embed_ids, text_ids
     from tiny_llm_hip.engine import DecodeEngine
 
-    model, tokenizer = load(args.model)
+    model, tokenizer = load(args.model, quantize=args.quantize)
     texts = [l for l in Path(args.texts_file).read_text().splitlines() if l.strip()]
     encoded = [text_ids(tokenizer, t, task=args.instruct) for t in texts]
     longest = max((len(ids) for ids in encoded), default=0)

@@ -156,6 +156,21 @@ int tl_paged_attention_fp8(const void *q, const void *key_pages, const float *ke
                            int L, int D, int num_pages, int page_size, int max_pages, int num_heads, int num_kv_heads, float scale,
                            int is_causal, int max_context_hint, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ===== affine W4 quantiser -- mx.quantize as the reference's tests use it ========
+ * NO reference kernel is replaced: the reference receives its weights quantised.  This is the producer of the one
+ * weight format every matmul / gather / embedding entry point above consumes, for weights that arrive unquantised.
+ *   w      [rows, cols]      float32 / float16 / bfloat16 (src_dtype), row-major, cols % 128 == 0, 16-byte aligned;
+ *                            a stack [E, rows, cols] is the same thing with E * rows rows
+ *   packed [rows, cols/8]    uint32, element 8j+i in bits [4i, 4i+4); 16-byte aligned
+ *   scales [rows, cols/128]  bfloat16
+ *   biases [rows, cols/128]  bfloat16
+ * The rule is oracle/tiny_oracle.py::quantize_affine (group 128, 4 bits, bf16 scales / biases), one correctly rounded
+ * fp32 operation per line of that function, and the result equals that function's bit for bit (csrc/quantize_w4.h).
+ * TL_ERR_INVALID for cols <= 0 or not a multiple of 128, rows < 0, a null pointer, a misaligned w / packed, or another
+ * src_dtype; rows == 0 is a no-op that looks at no pointer. */
+int tl_quantize_w4(const void *w, long rows, int cols, tl_dtype src_dtype, uint32_t *packed, void *scales, void *biases,
+                   void *stream);
+
 /* ===== fused decode fast path (not visible through the reference API) ========
  * One Qwen3 decode step = the layer loop of Qwen3ModelWeek2/3.__call__
  * (qwen3_week2.py:357-392, qwen3_week3.py:320-338) for L=1, with the

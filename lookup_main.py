@@ -41,6 +41,7 @@ def build_parser():
     ap.add_argument("--sampler-top-k", type=int, default=None, help="sample among the K most likely tokens")
     ap.add_argument("--sampler-top-p", type=float, default=None, help="sample among the likeliest tokens whose mass reaches this")
     ap.add_argument("--sampler-seed", type=int, default=0, help="the device's seed: request i draws from seed + i")
+    ap.add_argument("--quantize", action="store_true", help="accept an unquantised checkpoint (bf16 safetensors): quantise it to W4 on the device while loading")
     return ap
 
 
@@ -59,7 +60,7 @@ def main(argv=None):
     from tiny_llm_hip import load, request
     from tiny_llm_hip.engine import DecodeEngine, lookup_generate_ids
 
-    model, tokenizer = load(args.model)
+    model, tokenizer = load(args.model, quantize=args.quantize)
     prompts = list(args.prompts)
     if args.prompts_file:
         prompts += [l for l in Path(args.prompts_file).read_text().splitlines() if l.strip()]

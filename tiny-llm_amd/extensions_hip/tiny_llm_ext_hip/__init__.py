@@ -71,6 +71,8 @@ _SIGNATURES = {
         _c_int,
         [_c_void_p] * 8 + [_c_int] * 8 + [_c_float, _c_int, _c_int, _c_void_p, _c_size_t, _c_void_p],
     ),
+    # affine W4 quantiser (include/tinyllm_hip.h; the rule is oracle/tiny_oracle.py::quantize_affine)
+    "tl_quantize_w4": (_c_int, [_c_void_p, ctypes.c_long, _c_int, _c_int] + [_c_void_p] * 4),
 }
 
 
@@ -578,6 +580,25 @@ def quantized_embedding(
 def _require_float(x: torch.Tensor, name: str) -> None:
     if x.dtype not in _DTYPES:
         raise RuntimeError(f"{name}: expected float32, float16, or bfloat16")
+
+
+def quantize_w4(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Affine 4-bit quantisation in groups of 128 along the last axis, on the device: ``w`` [rows, cols] or a stack [E, rows, cols]
+    (float32 / float16 / bfloat16) -> (packed [..., cols/8] int32 holding the uint32 words, scales [..., cols/128] bf16, biases
+    likewise): the triple ``quantized_matmul`` / ``quantized_embedding`` / the engine read.  Bit-identical to
+    oracle/tiny_oracle.py::quantize_affine (csrc/quantize_w4.h)."""
+    _require_float(w, "quantize_w4")
+    if w.dim() not in (2, 3):
+        raise RuntimeError("quantize_w4: expected a matrix [rows, cols] or a stack [E, rows, cols]")
+    _require_gpu("quantize_w4", w)
+    w = w.contiguous()
+    *lead, cols = w.shape
+    packed = torch.empty((*lead, cols // 8), dtype=torch.int32, device=w.device)
+    scales = torch.empty((*lead, cols // 128), dtype=torch.bfloat16, device=w.device)
+    biases = torch.empty_like(scales)
+    rows = w.numel() // cols if cols else 0
+    _check(_lib.tl_quantize_w4(_ptr(w), rows, cols, _DTYPES[w.dtype], _ptr(packed), _ptr(scales), _ptr(biases), _stream()))
+    return packed, scales, biases
 
 
 def rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float, stream=None) -> torch.Tensor:

@@ -15,7 +15,8 @@ Qwen3-MoE checkpoints (``num_experts`` in config.json) load too: sparse layers c
 (reference qwen3_week3.py:258-272).
 
 Only what the hot path supports is accepted: affine 4-bit weights in groups of 128 (SURVEY.md §8, quantize.py:103-121);
-anything else raises ``ValueError`` naming the offending field.  No network access: names are resolved in the local
+anything else raises ``ValueError`` naming the offending field.  An unquantised checkpoint (the Hugging Face bf16 layout) is refused
+too unless ``quantize=True`` is passed, which quantises it into that format on the device while loading.  No network access: names are resolved in the local
 Hugging Face cache only.
 """
 
@@ -92,14 +93,57 @@ def _quantization(config: dict) -> tuple[int, int]:
     return group_size, bits
 
 
-def load_weights(model_dir: str | Path, device: str = "cuda") -> SimpleNamespace:
-    """The mlx_lm-shaped model object of an MLX 4-bit Qwen3 checkpoint directory (see module docstring)."""
+def _quantize_on_load(src: _TensorSource, prefix: str, names: list[str], shape: tuple, device: str) -> SimpleNamespace:
+    """One W4 layer from unquantised tensors: ``names`` is one tensor of ``shape``, or ``shape[0]`` tensors of ``shape[1:]`` (the
+    per-expert matrices of a Hugging Face Qwen3-MoE layer, stacked here).  Each tensor is read, checked and staged on ``device`` in
+    bf16 (what tools/convert_hf_to_mlx4bit.py quantises, so both roads give the same model), the staged matrix is quantised by the HIP
+    kernel behind ``tiny_llm_ext_hip.quantize_w4`` and dropped before the next one is read.  On a CPU device the torch restatement
+    ``tiny_llm_hip.synthetic.quantize`` stands in: same bits, but the SLOW path, there for tests of the plumbing."""
+    each = shape if len(names) == 1 else shape[1:]
+    if shape[-1] % 128:
+        raise ValueError(f"{prefix}.weight: {shape[-1]} input features are not a multiple of the group size 128")
+    on_gpu = torch.device(device).type == "cuda"
+    staged = None
+    for e, name in enumerate(names):
+        w = src.get(name)
+        if not w.is_floating_point():
+            raise ValueError(f"{name}: expected an unquantised floating-point matrix, found {w.dtype}")
+        if tuple(w.shape) != tuple(each):
+            raise ValueError(f"{name}: shape {tuple(w.shape)} does not describe a {list(each)} matrix")
+        if len(names) == 1:
+            staged = w.to(device=device, dtype=torch.bfloat16)
+        else:
+            if staged is None:
+                staged = torch.empty(shape, dtype=torch.bfloat16, device=device)
+            staged[e].copy_(w)
+        del w
+    if on_gpu:
+        import tiny_llm_ext_hip as ext
+
+        packed, scales, biases = ext.quantize_w4(staged)
+    else:
+        from tiny_llm_hip.synthetic import quantize as host_quantize
+
+        packed, scales, biases = host_quantize(staged)
+    del staged
+    return SimpleNamespace(weight=packed, scales=scales, biases=biases, group_size=128, bits=4)
+
+
+def load_weights(model_dir: str | Path, device: str = "cuda", quantize: bool = False) -> SimpleNamespace:
+    """The mlx_lm-shaped model object of an MLX 4-bit Qwen3 checkpoint directory (see module docstring).
+
+    ``quantize=True`` also accepts an UNQUANTISED checkpoint (no ``quantization`` section in config.json; bf16 / f16 / f32 safetensors
+    under the Hugging Face names, per-expert ``mlp.experts.{e}.*_proj`` included, or the names of an unquantised mlx_lm save): every
+    linear weight and the embedding table are quantised to W4 on ``device`` as they are read, one tensor at a time, so the peak device
+    memory is the W4 model plus one bf16 matrix; norms stay as stored.  A quantised checkpoint loads as without the keyword.  With
+    ``device="cpu"`` the torch quantiser runs instead of the kernel: the slow path."""
     model_dir = Path(model_dir)
     config = json.loads((model_dir / "config.json").read_text())
     missing = [k for k in _CONFIG_KEYS if k not in config]
     if missing:
         raise ValueError(f"config.json lacks {missing}")
-    group_size, bits = _quantization(config)
+    on_load = quantize and not isinstance(config.get("quantization") or config.get("quantization_config"), dict)
+    group_size, bits = (128, 4) if on_load else _quantization(config)
     config.setdefault("head_dim", config["hidden_size"] // config["num_attention_heads"])
     # Only plain RoPE is what the hot path computes (reference qwen3_week3.py:230: theta alone): a scaled variant -- transformers >= 5's
     # {"rope_parameters": {"rope_type": "yarn" | "linear" | ...}} or the legacy {"rope_scaling": {...}} -- is refused whether or not a
@@ -118,7 +162,9 @@ def load_weights(model_dir: str | Path, device: str = "cuda") -> SimpleNamespace
     src = _TensorSource(model_dir)
 
     def linear(prefix: str, out_dim: int, in_dim: int) -> SimpleNamespace:
-        w, s, b = (src.get(f"{prefix}.{part}") for part in ("weight", "scales", "biases"))
+        if on_load:
+            return _quantize_on_load(src, prefix, [f"{prefix}.weight"], (out_dim, in_dim), device)
+        w, s, b =(src.get(f"{prefix}.{part}") for part in ("weight", "scales", "biases"))
         if w.dtype not in (torch.uint32, torch.int32):
             raise ValueError(f"{prefix}.weight: expected packed uint32 words, found {w.dtype}")
         if s.dtype not in (torch.bfloat16, torch.float16) or b.dtype != s.dtype:
@@ -134,12 +180,20 @@ def load_weights(model_dir: str | Path, device: str = "cuda") -> SimpleNamespace
         w = src.get(name)
         if tuple(w.shape) != (n,):
             raise ValueError(f"{name}: expected shape ({n},), found {tuple(w.shape)}")
+        if on_load:
+            w = w.to(torch.bfloat16)  # like the scales and biases beside it (and like the offline converter)
         return SimpleNamespace(weight=w.to(device))
 
     def experts(prefix: str, count: int, out_dim: int, in_dim: int) -> SimpleNamespace:
         """One stacked expert projection of a Qwen3-MoE layer (mlx_lm SwitchLinear): weight [E, out, in/8] u32,
         scales / biases [E, out, in/128] (what grouped_expert_linear consumes, reference moe.py:7-36)."""
-        w, s, b = (src.get(f"{prefix}.{part}") for part in ("weight", "scales", "biases"))
+        if on_load:
+            # mlx_lm saves the stack under this very name; transformers saves one matrix per expert under mlp.experts.{e}
+            names = [f"{prefix}.weight"]
+            if names[0] not in src:
+                names = [f"{prefix.replace('.switch_mlp.', f'.experts.{e}.')}.weight" for e in range(count)]
+            return _quantize_on_load(src, prefix, names, (count, out_dim, in_dim), device)
+        w, s, b =(src.get(f"{prefix}.{part}") for part in ("weight", "scales", "biases"))
         if w.dtype not in (torch.uint32, torch.int32) or s.dtype not in (torch.bfloat16, torch.float16) or b.dtype != s.dtype:
             raise ValueError(f"{prefix}: expected packed uint32 words with 16-bit float scales / biases, found "
                              f"{w.dtype}/{s.dtype}/{b.dtype}")
@@ -189,7 +243,7 @@ def load_weights(model_dir: str | Path, device: str = "cuda") -> SimpleNamespace
     out = SimpleNamespace(args=SimpleNamespace(**config), model=inner)
     if not config["tie_word_embeddings"]:
         out.lm_head = linear("lm_head", config["vocab_size"], hs)
-    elif "lm_head.weight" in src:
+    elif "lm_head.weight" in src and not on_load:  # (an unquantised export may repeat the tied table: the converter skips it too)
         raise ValueError("checkpoint ties the embeddings but also carries lm_head tensors")
     return out
 
@@ -273,10 +327,11 @@ class TokenizerWrapper:
         return self._detok
 
 
-def load(name_or_path: str, device: str = "cuda"):
-    """(model, tokenizer) like ``mlx_lm.load``; see the module docstring."""
+def load(name_or_path: str, device: str = "cuda", quantize: bool = False):
+    """(model, tokenizer) like ``mlx_lm.load``; see the module docstring.  ``quantize=True``: an unquantised checkpoint is quantised
+    to W4 on the device as it is read (``load_weights``)."""
     model_dir = resolve_model_dir(name_or_path)
-    model = load_weights(model_dir, device=device)
+    model = load_weights(model_dir, device=device, quantize=quantize)
     from transformers import AutoTokenizer
 
     hf_tok = AutoTokenizer.from_pretrained(str(model_dir), local_files_only=True)
